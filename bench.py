@@ -74,9 +74,15 @@ def parse_args(argv=None):
                     help="time only the HBM-resident slide (kernel-only; the line's value is then NOT the section-8(d) metric)")
     ap.add_argument("--no-legs", action="store_true", help="skip the exact-fp32 and training legs of the default N = 1 line")
     ap.add_argument("--master-port", type=int, default=29577)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32 / "
+                         "float64, < 64 MB in all: a larger array is a fixed, seeded sample with its flat C-order positions in "
+                         "DIR/<name>_index.npy)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="N>1 launch test: every rank prints its rank/world line and exits before touching a GPU")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.scaling is None:
         args.scaling = "strong" if args.workload in ("wsi-synth256", "solo-16384") else "weak"
     return args
@@ -354,11 +360,13 @@ def main():
             eng.infer_image_raw_submit(slot, host_u16.data_ptr(), 16, C_img, H, W, False, mean, std,
                                        host_outs[slot].data_ptr())
             inflight.append(slot)
+            return host_outs[slot]
         step_host.n = 0
 
         def step_resident():
             eng.infer_image_dev(band_f64.data_ptr(), C_img, H, W, mean, std, umx.MODE_ACCUMULATE, umx.STITCH_FP16_COMPAT,
                                 dev_out.data_ptr())
+            return dev_out
     else:
         # N > 1 (and --force-sharded at N = 1): the SAME product path as the N = 1 line, band by band -- umx_infer_image_sharded_raw_submit:
         # this rank's uint16 rows up from pinned host memory piece by piece under the tiles, im2double in the tile gather, stitched
@@ -452,7 +460,7 @@ def main():
             dt = float(t.item())
         return dt, prof, res
 
-    host_elapsed = host_prof = None
+    host_elapsed = host_prof = res_h = None
     host_sync = None
     if not args.resident_only:
         host_elapsed, host_prof, res_h = timed(step_host)
@@ -552,6 +560,11 @@ def main():
     ranks = ranks_block(dist if sharded else None, torch, hp, H, W, rank, agree)
 
     if rank == 0:
+        if args.dump_outputs:
+            # what the caller of the timed path holds after its last step: the uint8 probability planes (host path; on N > 1 the
+            # gathered stack) or, with --resident-only, the fp16 planes left in HBM
+            dump_outputs(args.dump_outputs, [("probabilities_u8", res_h)] if host_elapsed is not None
+                         else [("probabilities_f16", res_r)])
         ms_per_step = 1e3 * elapsed / args.steps
         value = tiles_total * args.steps / elapsed
         roofline = roofline_of(prof, elapsed, eng, args.batch)
@@ -627,6 +640,47 @@ def crc32_of(t):
     for i in range(0, a.size, step):
         crc = zlib.crc32(a[i:i + step].tobytes() if a.dtype.itemsize != 1 else memoryview(a[i:i + step]), crc)
     return crc & 0xFFFFFFFF
+
+
+DUMP_BYTES = 60 * 10 ** 6   # --dump-outputs: all .npy files of one dump together (under 64 MB, decimal or binary)
+DUMP_SEED = 20260101
+
+
+def dump_outputs(path, arrays):
+    """Write [(name, array)] (torch tensors on the host or the device, or numpy arrays) as <path>/<name>.npy: float64 stays float64,
+    everything else becomes float32 (exact for uint8 / fp16).  The smaller arrays are written whole first; an array that does not
+    fit its share of DUMP_BYTES is replaced by a sample at seeded positions (the same for every run with the same shapes), written
+    next to it as <name>_index.npy (float64 flat C-order positions, ascending)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    todo = sorted(arrays, key=lambda a: a[1].numel() if torch.is_tensor(a[1]) else a[1].size)
+    left = DUMP_BYTES - 4096 * 2 * len(todo)          # (room for the .npy headers)
+    written = []
+    for i, (name, a) in enumerate(todo):
+        share = left // (len(todo) - i)
+        n = a.numel() if torch.is_tensor(a) else a.size
+        f64 = (a.dtype == torch.float64) if torch.is_tensor(a) else (a.dtype == np.float64)
+        esize = 8 if f64 else 4
+        if n * esize <= share:
+            v = a.detach().reshape(-1).cpu().numpy() if torch.is_tensor(a) else np.asarray(a).reshape(-1)
+            v = v.astype(np.float64 if f64 else np.float32).reshape(tuple(a.shape))
+            np.save(os.path.join(path, name + ".npy"), v)
+            left -= v.nbytes
+            written.append("%s %s" % (name, list(v.shape)))
+            continue
+        k = share // (esize + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False, shuffle=False))
+        if torch.is_tensor(a):
+            v = a.detach().reshape(-1)[torch.from_numpy(idx).to(a.device)].cpu().numpy()
+        else:
+            v = np.asarray(a).reshape(-1)[idx]
+        v = v.astype(np.float64 if f64 else np.float32)
+        np.save(os.path.join(path, name + ".npy"), v)
+        np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+        left -= v.nbytes + 8 * k
+        written.append("%s: %d of %d values of %s" % (name, k, n, list(a.shape)))
+    print("bench.py: --dump-outputs %s: %s" % (path, "; ".join(written)), file=sys.stderr)
 
 
 CONFIG_LEGS = (   # (workload, rows, steps): the other BASELINE.json configs as short legs of the default N = 1 line (VERDICT r5 item 5)
@@ -783,6 +837,7 @@ def bench_train(args, torch):
     script's regime), 1 x MI355X.  A step = one umx_train_step on device-resident batches.  Not the headline metric:
     select it with --workload train-synth256.  N > 1 would need a gradient all-reduce the reference does not have
     (it trains on one GPU): replicas only, not run here."""
+    import numpy as np
     from unmicst_amd import model, trainer
     if int(os.environ.get("WORLD_SIZE", "1")) != 1 or args.gpus != 1:
         print("bench.py: the training workload runs on one GPU (the reference trains on one)", file=sys.stderr)
@@ -818,6 +873,10 @@ def bench_train(args, torch):
     last = tr.loss()[0]                          # synchronises the trainer's stream
     elapsed = time.perf_counter() - t0
     ph = tr.profile(False)
+    if args.dump_outputs:
+        # the last step's (loss, data term, regularisation), forward probabilities and the variables it left behind
+        dump_outputs(args.dump_outputs, [("loss", np.array(tr.loss(), dtype=np.float64)), ("probabilities", tr.probs()),
+                                         ("variables", tr.blob())])
     flops_step = tr.flops_per_image * B
     tflops = flops_step * args.steps / elapsed / 1e12
     cpu = None

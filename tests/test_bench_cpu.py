@@ -59,3 +59,27 @@ def test_bench_strong_and_weak_slide_sizes():
     assert bench.parse_args([]).scaling == "strong" and bench.parse_args(["--workload", "solo-16384"]).scaling == "strong"
     assert bench.parse_args(["--workload", "duo-4096"]).scaling == "weak" and bench.parse_args(["--scaling", "weak"]).scaling == "weak"
     assert bench.WORKLOADS["solo-16384"][0] == "nucleiDAPI1-5"
+
+
+def test_dump_outputs_is_bounded_and_reproducible(tmp_path):
+    """--dump-outputs: a small array whole (float32 / float64), a large one as a seeded sample with its positions, < 64 MB in all,
+    the same files for the same arrays."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    big = torch.arange(3 * 2048 * 4096, dtype=torch.int32).remainder(251).to(torch.uint8).reshape(3, 2048, 4096)
+    small = np.linspace(0, 1, 3 * 64 * 64).reshape(3, 64, 64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), [("planes", big), ("loss", small)])
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["loss.npy", "planes.npy", "planes_index.npy"] and files == sorted(os.listdir(tmp_path / "b"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) < 64 * 10 ** 6
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+    loss = np.load(tmp_path / "a" / "loss.npy")
+    assert loss.dtype == np.float64 and np.array_equal(loss, small)
+    v, idx = np.load(tmp_path / "a" / "planes.npy"), np.load(tmp_path / "a" / "planes_index.npy")
+    assert v.dtype == np.float32 and idx.dtype == np.float64 and v.size == idx.size and 0 < v.size < big.numel()
+    assert np.all(np.diff(idx) > 0)
+    assert np.array_equal(v, big.reshape(-1).numpy()[idx.astype(np.int64)].astype(np.float32))

@@ -104,14 +104,13 @@ def test_converted_model_dir_roundtrip(tmp_path):
     assert model.detect_graph(d) == model.GRAPH_LEGACY
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/models"), reason="reference tree not mounted")
 def test_detects_graph_of_reference_model_dirs():
-    assert model.detect_graph("/root/reference/models/nucleiDAPI") == model.GRAPH_LEGACY
-    assert model.detect_graph("/root/reference/models/nucleiDAPI1-5") == model.GRAPH_V2
-    assert model.detect_graph("/root/reference/models/nucleiDAPILAMIN") == model.GRAPH_V2
+    assert model.detect_graph(os.path.join(helpers.REFERENCE_MODELS, "nucleiDAPI")) == model.GRAPH_LEGACY
+    assert model.detect_graph(os.path.join(helpers.REFERENCE_MODELS, "nucleiDAPI1-5")) == model.GRAPH_V2
+    assert model.detect_graph(os.path.join(helpers.REFERENCE_MODELS, "nucleiDAPILAMIN")) == model.GRAPH_V2
     with pytest.raises(FileNotFoundError):     # weight shard not shipped: loud failure, like tf's restore error
-        model.load_model_dir("/root/reference/models/nucleiDAPI1-5")
-    art = model.load_model_dir("/root/reference/models/nucleiDAPILAMIN", synthetic_if_missing=True)
+        model.load_model_dir(os.path.join(helpers.REFERENCE_MODELS, "nucleiDAPI1-5"))
+    art = model.load_model_dir(os.path.join(helpers.REFERENCE_MODELS, "nucleiDAPILAMIN"), synthetic_if_missing=True)
     assert art.hp == model.KNOWN_HP["nucleiDAPILAMIN"] and (art.mean, art.std) == (0.18, 0.17)
 
 
@@ -129,7 +128,6 @@ def test_shipped_converted_models_match_their_golden_copies(name):
     assert hp.graph == model.GRAPH_LEGACY and np.isfinite(blob).all()
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/models"), reason="reference tree not mounted")
 @pytest.mark.parametrize("name", sorted(SHIPPED))
 def test_converter_reproduces_the_shipped_models_from_the_reference_checkpoints(name, tmp_path):
     """tools/convert_model.py on the reference's own model directories (TF tensor-bundle read without TensorFlow).  The
@@ -138,7 +136,7 @@ def test_converter_reproduces_the_shipped_models_from_the_reference_checkpoints(
     follow the checkpoint that is converted."""
     sys.path.insert(0, os.path.join(helpers.ROOT, "tools"))
     import convert_model
-    src = os.path.join("/root/reference/models", name)
+    src = helpers.reference_model_dir(name, tmp_path / "reference")
     argv = [src, str(tmp_path)] + (["--prefix", SHIPPED[name]] if SHIPPED[name] != "model.ckpt" else [])
     out = convert_model.main(argv)
     hp, blob, mean, std = helpers.load_nuclei_dapi(name)

@@ -9,8 +9,6 @@ import pytest
 import helpers
 from unmicst_amd import model, sharding, tfckpt, tiffio
 
-REF = "/root/reference"
-
 
 def _varint(n):
     out = b""
@@ -100,22 +98,40 @@ def test_model_dir_roundtrip(tmp_path, name):
     assert np.array_equal(art.blob, blob)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted")
-def test_reads_reference_checkpoints():
+def test_reads_reference_checkpoints(tmp_path):
     hp, blob, mean, std = helpers.load_nuclei_dapi()
-    art = model.load_model_dir(os.path.join(REF, "models", "nucleiDAPI"), model.GRAPH_LEGACY)
+    legacy = helpers.reference_model_dir("nucleiDAPI", tmp_path)
+    art = model.load_model_dir(legacy, model.GRAPH_LEGACY)
     assert art.hp == hp and np.array_equal(art.blob, blob) and (art.mean, art.std) == (mean, std)
     # solo / duo: index + hp only (data shards are downloaded by the reference's Dockerfile) -> loud failure
     with pytest.raises(FileNotFoundError):
-        model.load_model_dir(os.path.join(REF, "models", "nucleiDAPI1-5"), model.GRAPH_V2)
-    idx = tfckpt.read_index(os.path.join(REF, "models", "nucleiDAPILAMIN", "model.ckpt.index"))
+        model.load_model_dir(os.path.join(helpers.REFERENCE_MODELS, "nucleiDAPI1-5"), model.GRAPH_V2)
+    idx = tfckpt.read_index(os.path.join(helpers.REFERENCE_MODELS, "nucleiDAPILAMIN", "model.ckpt.index"))
     duo = model.KNOWN_HP["nucleiDAPILAMIN"]
     for name, shape in model.tensor_specs(duo):
         assert idx[model._ckpt_name(duo, name)]["shape"] == tuple(shape), name
     # a v2 graph cannot restore a legacy checkpoint (the reference fails with NotFoundError): KeyError here
     with pytest.raises(KeyError):
         model.blob_from_checkpoint(model.HParams(model.GRAPH_V2, 128, 1, 3, 16, 2, 5, 1),
-                                   os.path.join(REF, "models", "nucleiDAPI", "model.ckpt"))
+                                   os.path.join(legacy, "model.ckpt"))
+
+
+def test_rebuilt_reference_shards_are_checked_against_the_index_crcs():
+    """reference_model_dir() rebuilds the weight shards from the golden conversions: its byte check is the crc32c TensorFlow
+    stored per tensor, so the check itself must be the right function and must see every tensor."""
+    c = 0xE3069283                                          # CRC-32C of b"123456789" (the standard check value)
+    assert helpers.crc32c_masked(b"123456789") == ((((c >> 15) | (c << 17)) & 0xFFFFFFFF) + 0xA282EAD8) & 0xFFFFFFFF
+    for name, prefix in helpers.REFERENCE_SHARDS.items():
+        index = os.path.join(helpers.REFERENCE_MODELS, name, prefix + ".index")
+        crcs = helpers.bundle_crcs(index)
+        assert set(crcs) == set(tfckpt.read_index(index)) and None not in crcs.values()
+    hp, blob, _, _ = helpers.load_nuclei_dapi()
+    t = model.tensors_from_blob(hp, blob)["lt.w"]
+    raw = bytearray(np.ascontiguousarray(t, dtype="<f4").tobytes())
+    crcs = helpers.bundle_crcs(os.path.join(helpers.REFERENCE_MODELS, "nucleiDAPI", "model.ckpt.index"))
+    assert helpers.crc32c_masked(bytes(raw)) == crcs[model._ckpt_name(hp, "lt.w")]
+    raw[5] ^= 1
+    assert helpers.crc32c_masked(bytes(raw)) != crcs[model._ckpt_name(hp, "lt.w")]
 
 
 def test_tiff_roundtrip_and_foreign_layouts(tmp_path):
