@@ -7,7 +7,10 @@
  * (:367-373), gradients of every trainable variable, the optimiser update (:378-380) and the BN moving-average update
  * (UPDATE_OPS, :375,379).  Parameters live in the same flat blob layout umx_create takes, so a trained blob loads into
  * the inference engine unchanged.  Covered: UMX_GRAPH_V2 with nExtraConvs == 0 and 3x3 or 5x5 filters (every v2 model the
- * reference ships is 3x3).
+ * reference ships is 3x3), and UMX_GRAPH_LEGACY with nExtraConvs 0..2 and 3x3 or 5x5 filters -- the graph of every checkpoint the
+ * reference ships with weights, trained as UnMicst.py:270-279 (train() with restoreVariables): ReLU everywhere, BN only on the
+ * down blocks (on relu(conv + 1x1 shortcut), before the pool), unweighted cross-entropy, MomentumOptimizer; no dropout, no
+ * regulariser (umx_train_options_legacy).
  * Conventions as in umx.h: 0 = ok, umx_trainer_last_error() gives the message, the caller owns host buffers, one
  * trainer per host thread.  There is no CPU fallback.
  */
@@ -47,9 +50,11 @@ typedef struct umx_train_options {
 
 UMX_API void umx_train_options_solo(umx_train_options* o);   /* UnMicst1-5.py: Adam 5e-5 x0.98/5000, l1(8e-5), bottom dropout 0.35 */
 UMX_API void umx_train_options_duo(umx_train_options* o);    /* UnMicst2.py:  Adam 6e-5 x0.99/4000, l2(0.01/0.005), dropout everywhere */
+UMX_API void umx_train_options_legacy(umx_train_options* o); /* UnMicst.py:   Momentum(0.9) 0.01 x0.95/1000, no regulariser, no dropout, no clip */
 
 /* replaces UNet2D.setup + tf.global_variables_initializer / saver.restore (UnMicst1-5.py:55-237,445-449): the blob holds
- * the initial (or restored) variables incl. BN moving statistics; optimiser slots start at zero, step at 0. */
+ * the initial (or restored) variables incl. BN moving statistics; optimiser slots start at zero, step at 0.
+ * A legacy graph with a non-zero dropout rate or reg_kind != UMX_REG_NONE is UMX_ERR_INVALID (that graph has neither). */
 UMX_API int umx_trainer_create(const umx_hparams* hp, const float* weight_blob, size_t blob_floats,
                                const umx_train_options* opts, umx_trainer** out);
 UMX_API void umx_trainer_destroy(umx_trainer* tr);
@@ -57,7 +62,8 @@ UMX_API const char* umx_trainer_last_error(const umx_trainer* tr);
 
 /* One step on HOST buffers: data [B,P,P,nChannels], labels and weights [B,P,P,nClasses], float32 NHWC (the reference's
  * batchData / batchLabels / batchWeights, UnMicst1-5.py:455-457,483).  apply_update 0: loss and gradients only
- * (parameters, slots, moving statistics and the step counter stay).  loss3 = {total, data term, regularisation}. */
+ * (parameters, slots, moving statistics and the step counter stay).  loss3 = {total, data term, regularisation}.
+ * weights == NULL (legacy trainer only): every weight 1 -- the reference's unweighted loss (UnMicst.py:276). */
 UMX_API int umx_train_step(umx_trainer* tr, const float* data, const float* labels, const float* weights,
                            int apply_update, double* loss3);
 /* Same on DEVICE buffers; only enqueues on the trainer's stream.  umx_trainer_loss synchronises and reads the loss. */
@@ -77,6 +83,11 @@ UMX_API int umx_trainer_probs(umx_trainer* tr, float* probs_host);
  *                                             (BN output = z * scale + shift: the value the LeakyReLU / max-pool decisions are taken on);
  *   "lu<i>.us"                                the up-sampled tensor behind its LeakyReLU (UnMicst1-5.py:192-195), [B,2h,2h,C];
  *   "ds<i>"                                   input of down layer i (ds0 = the batch; pooled + dropped output of layer i-1).
+ * A legacy trainer's decision sites instead (every ReLU and max-pool decision is taken on one of these):
+ *   "ld<i>.x<e>" | "lu<i>.x<e>"               the pre-ReLU output that extra conv e reads (e < nExtraConvs), [B,H,W,C];
+ *   "ld<i>.z"                                 main chain + 1x1 shortcut, pre-ReLU;  "lu<i>.z" | "lb.z": the layer's last conv, pre-ReLU;
+ *   "ld<i>.stat"                              the batch statistics of relu(z), [4][C] as above (pool decisions on relu(z)*scale + shift);
+ *   "lu<i>.us"                                the up-sampled tensor behind its ReLU;  "lt.z": the logits;  "ds<i>" as above.
  * *n_floats in: capacity of `out`; out: the tensor's size (out == NULL just queries it).  Synchronises the trainer's stream.
  * The parity tests use it to take the oracle's gradient at the SAME activation / pooling decisions (tests/test_gpu_train.py). */
 UMX_API int umx_trainer_read_tensor(umx_trainer* tr, const char* name, float* out, size_t* n_floats);

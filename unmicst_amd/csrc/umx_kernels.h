@@ -297,7 +297,7 @@ hipError_t launch_act_bwd(const ActParams& a, const float* dy0, const float* dy1
 hipError_t launch_bn_bwd_finalize(const double* part, int nblk, size_t N, int C, float* dgamma, float* dbeta, float* m12,
                                   hipStream_t stream);
 // (bn_bwd_apply: g <- scale * (g - m1 - xhat*m2) in place, and leaky_bwd_s2d: gS[b,i,j,(pa*2+pb)*C + c] =
-//  d_us[b,2i+pa,2j+pb,c] * (us > 0 ? 1 : 0.2), are declared with the weight-gradient kernels below: they track max |v|)
+//  d_us[b,2i+pa,2j+pb,c] * (us > 0 ? 1 : slope) -- 0.2 in v2, 0 in the legacy graph -- are declared with the weight-gradient kernels below: they track max |v|)
 
 // top layer: t0 = x W (1x1 conv, K <= 8 classes)
 hipError_t launch_head_fwd(const float* x, size_t N, int C, int K, const float* w, float* t0, hipStream_t stream);
@@ -359,8 +359,10 @@ struct WgradParams {
 hipError_t launch_bn_bwd_apply_max(float* g, const float* z, const float* stat, const float* m12, size_t N, int C,
                                    unsigned* gmax, const unsigned* bw, float* inv_scale, _Float16* hi, _Float16* lo, int Cs,
                                    int* overflow, hipStream_t stream);
-hipError_t launch_leaky_bwd_s2d_max(const float* d_us, const float* us, int B, int S, int C, float* gS, unsigned* gmax,
+hipError_t launch_leaky_bwd_s2d_max(const float* d_us, const float* us, int B, int S, int C, float slope, float* gS, unsigned* gmax,
                                     hipStream_t stream);
+// g = v > 0 ? dy : 0 (the legacy graph's ReLU backward; g may alias dy), max |g| into gmax (nullable)
+hipError_t launch_relu_bwd_max(const float* dy, const float* v, float* g, size_t n, unsigned* gmax, hipStream_t stream);
 bool wgrad_setup(WgradParams* p, std::string* why);   // fills geometry, slab groups and slices from B,H,W,Cx,Cg,nslab,dy,dx,coff
 size_t wgrad_ws_floats(const WgradParams& p);
 hipError_t launch_wgrad(const WgradParams& p, hipStream_t stream);

@@ -69,6 +69,22 @@ struct BnSite {            // one batch-normalised tensor
 
 struct Seg { std::string name; size_t off, n; float reg; };
 
+struct LBlock {                 // one block of the legacy graph: a chain of nExtraConvs + 1 convolutions with ReLUs between them
+    std::vector<TConv> fwd;     // fwd[0] reads the block input (down: w1; up: unused, c_fwd_u is the concat conv), fwd[e >= 1] reads
+                                // a[e-1] (wextra_{e-1}); a down block's last one also reads the block input through the 1x1 shortcut
+    std::vector<TConv> dg;      // dg[e >= 1]: input gradient of fwd[e] into a[e-1]
+    std::vector<WgradParams> wg;   // wg[e >= 1]: weight gradient of wextra_{e-1}
+    std::vector<size_t> o_wx;   // wextra offsets in the parameter vector
+    std::vector<float*> y;      // y[e]: output of conv e, pre-ReLU (down: y[E] = z = main + shortcut)
+    std::vector<float*> a;      // a[e] = relu(y[e]) for the convolution after it: e < E (down), e <= E (up: a[E] is the output)
+    std::vector<H16> ha;        // their planes
+    std::vector<unsigned*> amax;   // max |a[e]| (split-precision weight gradients)
+    std::vector<unsigned*> gmax;   // max |d loss / d y[e]| of the current step
+    float* ident = nullptr;     // [4][C] identity statistics: act_fwd as a plain ReLU with the plane writer
+    TConv dg_sh;                // (down) input gradient of the shortcut
+    WgradParams wg_sh;          // (down) weight gradient of the shortcut: one slab
+};
+
 }  // namespace
 
 struct umx_trainer {
@@ -154,6 +170,19 @@ struct umx_trainer {
     double t_fwd = 0, t_bwd = 0, t_opt = 0;
     int t_steps = 0;
     bool pending = false;
+    // legacy graph (GRAPH_LEGACY, reference UnMicst.py:80-186): build_legacy / forward_legacy / enqueue_legacy
+    bool legacy = false;
+    int E = 0;                          // nExtraConvs
+    std::vector<LBlock> ldb, lub;       // down layer i / up layer idx
+    float* lb_z = nullptr;              // bottom conv output, pre-ReLU
+    float* lb_ident = nullptr;          // identity statistics of the bottom ReLU
+    unsigned* lb_gmax = nullptr;
+    float* lt_z = nullptr;              // logits
+    float* ident_k = nullptr;           // identity statistics of the logits: the loss / softmax kernels without BN
+    float* d_ones = nullptr;            // all-ones weights: the unweighted loss (weights == NULL)
+    float* TX = nullptr;                // second gradient buffer of a chain (with DZ)
+    float* DSUM = nullptr;              // [2][max_act]: first-conv and shortcut input gradients, summed in that order
+    size_t max_act = 0;
 };
 
 namespace {
@@ -853,7 +882,7 @@ int enqueue_step(umx_trainer* tr, const float* data, const float* labels, const 
         } else if (idx >= 1) {
             T_TRY(dgrad(tr->c_dg_skip[idx], dz, tr->h_dz[slot], tr->d_xinv + slot, tr->dskip[idx]));
         }
-        T_HIP(tr, launch_leaky_bwd_s2d_max(tr->DB, tr->us[idx], B, S / 2, Cup, gs, tr->smax[idx], st));
+        T_HIP(tr, launch_leaky_bwd_s2d_max(tr->DB, tr->us[idx], B, S / 2, Cup, 0.2f, gs, tr->smax[idx], st));
         const bool gs_planes = tr->hconv && (tr->c_dg_T[idx].hidx >= 0 || tr->wg_planes);
         if (gs_planes) {   // (in front of the event: the transposed convolution's weight gradient stages from these planes too)
             tr->h_gs[slot].Cs = round_up(4 * Cup, 8);
@@ -956,6 +985,104 @@ void fill_common(umx_train_options* o) {
     o->beta1 = 0.9f; o->beta2 = 0.999f; o->adam_eps = 1e-8f;
     o->bn_momentum = 0.99f;
     o->seed = 1234;
+}
+
+// a single-phase group of one source: C channels, master tensor(s) at w_off (+ w2_off) of dims [taps][d2][d3]
+GroupSpec one_group(int C, size_t w_off, size_t w2_off, int d2, int d3, int transpose, int c_off, const TapSet& ts) {
+    GroupSpec g;
+    g.C = C; g.w_off = w_off; g.w2_off = w2_off; g.d2 = d2; g.d3 = d3; g.transpose = transpose; g.c_off = c_off;
+    g.npar = 1; g.Cblk = std::max(C, 1);
+    g.taps[0] = ts;
+    return g;
+}
+
+// One up layer's convolutions (shared by both graphs): the stride-2 transposed conv (forward with `act_T` fused, input gradient on
+// the space-to-depth output gradient, weight gradient), then the concat conv [ds_idx, us] -> Cup (forward, input gradients into us and
+// -- idx >= 1 -- into the skip, weight gradients of both halves).  S: the layer's input size on entry, its output size on return.
+int setup_up_layer(umx_trainer* tr, int idx, int& S, int act_T, double& mac_total) {
+    const std::vector<int>& n = tr->n;
+    const int ks = tr->hp.ks;
+    const TapSet fwd = same_taps(ks, false), flp = same_taps(ks, true);
+    auto group = one_group;
+    char nm[64];
+    snprintf(nm, sizeof nm, "lu%d", idx);
+    const int pb = (ks - 2) / 2;   // pad_before of the stride-2 SAME conv whose gradient the transposed conv is
+    const int Cskip = n[idx], Cup = n[idx + 1], Cin = n[idx + 2];
+    {   // transposed conv forward: 4 sub-pixel phases (out[2i+a-pb] += in[i] * Wt[a]); its activation fused
+        GroupSpec g;
+        g.C = Cin; g.w_off = tr->o_wt[idx]; g.w2_off = SIZE_MAX; g.d2 = Cup; g.d3 = Cin; g.transpose = 1; g.c_off = 0;
+        g.npar = 1; g.Cblk = Cin;
+        int oy[4], ox[4];
+        for (int p = 0; p < 4; ++p) {
+            const int pu = p >> 1, pv = p & 1;
+            oy[p] = pu; ox[p] = pv;
+            for (int a = 0; a < ks; ++a) {
+                if (((a - pb - pu) & 1) != 0) continue;
+                for (int b = 0; b < ks; ++b) {
+                    if (((b - pb - pv) & 1) != 0) continue;
+                    g.taps[p].off.push_back({(pu + pb - a) / 2, (pv + pb - b) / 2});
+                    g.taps[p].m.push_back(a * ks + b);
+                }
+            }
+        }
+        T_TRY(setup_conv(tr, tr->c_T[idx], nm, S, S, Cup, act_T, 4, 2, oy, ox, 1, &g));
+        mac_total += (double)S * S * ks * ks * Cin * Cup;
+    }
+    {   // transposed conv backward on the space-to-depth gradient gS[.., (pa,pb)*Cup + c] = dY[2i+pa, 2j+pb, c]:
+        // dX[i] = sum_a dY[2i + a - pb] Wt[a]  ->  q = a - pb = 2*di + pa
+        auto split = [](int q, int* d, int* par) { *par = ((q % 2) + 2) % 2; *d = (q - *par) / 2; };
+        std::vector<std::pair<int, int>> offs;
+        for (int a = 0; a < ks; ++a)
+            for (int b = 0; b < ks; ++b) {
+                int di, pa, dj, pbb;
+                split(a - pb, &di, &pa);
+                split(b - pb, &dj, &pbb);
+                std::pair<int, int> od{di, dj};
+                if (std::find(offs.begin(), offs.end(), od) == offs.end()) offs.push_back(od);
+            }
+        GroupSpec g;
+        g.C = 4 * Cup; g.w_off = tr->o_wt[idx]; g.w2_off = SIZE_MAX; g.d2 = Cup; g.d3 = Cin; g.transpose = 0; g.c_off = 0;
+        g.npar = 4; g.Cblk = Cup;
+        g.taps[0].off = offs;
+        g.taps[0].m.assign(offs.size() * 4, -1);
+        TapSet slabs;                 // weight-gradient slabs, grouped by parity block
+        std::vector<int> coff;
+        for (int par = 0; par < 4; ++par)
+            for (int a = 0; a < ks; ++a)
+                for (int b = 0; b < ks; ++b) {
+                    int di, pa, dj, pbb;
+                    split(a - pb, &di, &pa);
+                    split(b - pb, &dj, &pbb);
+                    if (pa * 2 + pbb != par) continue;
+                    const size_t t = std::find(offs.begin(), offs.end(), std::make_pair(di, dj)) - offs.begin();
+                    g.taps[0].m[t * 4 + par] = a * ks + b;
+                    slabs.off.push_back({di, dj});
+                    slabs.m.push_back(a * ks + b);
+                    coff.push_back(par * Cup);
+                }
+        tr->cur_bwd = true; T_TRY(setup_conv(tr, tr->c_dg_T[idx], nm, S, S, Cin, ACT_NONE, 1, 1, nullptr, nullptr, 1, &g)); tr->cur_bwd = false;
+        T_TRY(setup_wgrad(tr, tr->wg_T[idx], nm, S, 4 * Cup, Cup, Cin, slabs, coff));
+        mac_total += 2.0 * S * S * ks * ks * Cin * Cup;
+    }
+    S *= 2;
+    {
+        GroupSpec g2[2] = {group(Cskip, tr->o_w2[idx], SIZE_MAX, Cskip + Cup, Cup, 0, 0, fwd),
+                           group(Cup, tr->o_w2[idx], SIZE_MAX, Cskip + Cup, Cup, 0, Cskip, fwd)};
+        T_TRY(setup_conv(tr, tr->c_fwd_u[idx], nm, S, S, Cup, ACT_NONE, 1, 1, nullptr, nullptr, 2, g2));
+        mac_total += tr->c_fwd_u[idx].mac;
+        GroupSpec gu = group(Cup, tr->o_w2[idx], SIZE_MAX, Cskip + Cup, Cup, 1, Cskip, flp);
+        tr->cur_bwd = true; T_TRY(setup_conv(tr, tr->c_dg_us[idx], nm, S, S, Cup, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gu)); tr->cur_bwd = false;
+        mac_total += tr->c_dg_us[idx].mac;
+        if (idx >= 1) {
+            GroupSpec gk = group(Cup, tr->o_w2[idx], SIZE_MAX, Cskip + Cup, Cup, 1, 0, flp);
+            tr->cur_bwd = true; T_TRY(setup_conv(tr, tr->c_dg_skip[idx], nm, S, S, Cskip, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gk)); tr->cur_bwd = false;
+            mac_total += tr->c_dg_skip[idx].mac;
+        }
+        T_TRY(setup_wgrad(tr, tr->wg_u0[idx], nm, S, Cskip, Cskip, Cup, fwd, {}));
+        T_TRY(setup_wgrad(tr, tr->wg_u1[idx], nm, S, Cup, Cup, Cup, fwd, {}));
+        mac_total += (double)S * S * ks * ks * (Cskip + Cup) * Cup;
+    }
+    return UMX_OK;
 }
 
 int build_trainer(umx_trainer* tr, const float* blob, size_t blob_floats) {
@@ -1134,85 +1261,7 @@ int build_trainer(umx_trainer* tr, const float* blob, size_t blob_floats) {
         T_TRY(setup_wgrad(tr, tr->wg_b, "lb", S, n[L], n[L], n[L + 1], fwd, {}));
         mac_total += tr->c_fwd_b.mac + tr->c_dg_b.mac + (double)S * S * ks * ks * n[L] * n[L + 1];
     }
-    const int pb = (ks - 2) / 2;   // pad_before of the stride-2 SAME conv whose gradient the transposed conv is
-    for (int idx = L - 1; idx >= 0; --idx) {
-        snprintf(nm, sizeof nm, "lu%d", idx);
-        const int Cskip = n[idx], Cup = n[idx + 1], Cin = n[idx + 2];
-        {   // transposed conv forward: 4 sub-pixel phases (out[2i+a-pb] += in[i] * Wt[a]); LeakyReLU fused
-            GroupSpec g;
-            g.C = Cin; g.w_off = tr->o_wt[idx]; g.w2_off = SIZE_MAX; g.d2 = Cup; g.d3 = Cin; g.transpose = 1; g.c_off = 0;
-            g.npar = 1; g.Cblk = Cin;
-            int oy[4], ox[4];
-            for (int p = 0; p < 4; ++p) {
-                const int pu = p >> 1, pv = p & 1;
-                oy[p] = pu; ox[p] = pv;
-                for (int a = 0; a < ks; ++a) {
-                    if (((a - pb - pu) & 1) != 0) continue;
-                    for (int b = 0; b < ks; ++b) {
-                        if (((b - pb - pv) & 1) != 0) continue;
-                        g.taps[p].off.push_back({(pu + pb - a) / 2, (pv + pb - b) / 2});
-                        g.taps[p].m.push_back(a * ks + b);
-                    }
-                }
-            }
-            T_TRY(setup_conv(tr, tr->c_T[idx], nm, S, S, Cup, ACT_LEAKY, 4, 2, oy, ox, 1, &g));
-            mac_total += (double)S * S * ks * ks * Cin * Cup;
-        }
-        {   // transposed conv backward on the space-to-depth gradient gS[.., (pa,pb)*Cup + c] = dY[2i+pa, 2j+pb, c]:
-            // dX[i] = sum_a dY[2i + a - pb] Wt[a]  ->  q = a - pb = 2*di + pa
-            auto split = [](int q, int* d, int* par) { *par = ((q % 2) + 2) % 2; *d = (q - *par) / 2; };
-            std::vector<std::pair<int, int>> offs;
-            for (int a = 0; a < ks; ++a)
-                for (int b = 0; b < ks; ++b) {
-                    int di, pa, dj, pbb;
-                    split(a - pb, &di, &pa);
-                    split(b - pb, &dj, &pbb);
-                    std::pair<int, int> od{di, dj};
-                    if (std::find(offs.begin(), offs.end(), od) == offs.end()) offs.push_back(od);
-                }
-            GroupSpec g;
-            g.C = 4 * Cup; g.w_off = tr->o_wt[idx]; g.w2_off = SIZE_MAX; g.d2 = Cup; g.d3 = Cin; g.transpose = 0; g.c_off = 0;
-            g.npar = 4; g.Cblk = Cup;
-            g.taps[0].off = offs;
-            g.taps[0].m.assign(offs.size() * 4, -1);
-            TapSet slabs;                 // weight-gradient slabs, grouped by parity block
-            std::vector<int> coff;
-            for (int par = 0; par < 4; ++par)
-                for (int a = 0; a < ks; ++a)
-                    for (int b = 0; b < ks; ++b) {
-                        int di, pa, dj, pbb;
-                        split(a - pb, &di, &pa);
-                        split(b - pb, &dj, &pbb);
-                        if (pa * 2 + pbb != par) continue;
-                        const size_t t = std::find(offs.begin(), offs.end(), std::make_pair(di, dj)) - offs.begin();
-                        g.taps[0].m[t * 4 + par] = a * ks + b;
-                        slabs.off.push_back({di, dj});
-                        slabs.m.push_back(a * ks + b);
-                        coff.push_back(par * Cup);
-                    }
-            tr->cur_bwd = true; T_TRY(setup_conv(tr, tr->c_dg_T[idx], nm, S, S, Cin, ACT_NONE, 1, 1, nullptr, nullptr, 1, &g)); tr->cur_bwd = false;
-            T_TRY(setup_wgrad(tr, tr->wg_T[idx], nm, S, 4 * Cup, Cup, Cin, slabs, coff));
-            mac_total += 2.0 * S * S * ks * ks * Cin * Cup;
-        }
-        S *= 2;
-        {
-            GroupSpec g2[2] = {group(Cskip, tr->o_w2[idx], SIZE_MAX, Cskip + Cup, Cup, 0, 0, fwd),
-                               group(Cup, tr->o_w2[idx], SIZE_MAX, Cskip + Cup, Cup, 0, Cskip, fwd)};
-            T_TRY(setup_conv(tr, tr->c_fwd_u[idx], nm, S, S, Cup, ACT_NONE, 1, 1, nullptr, nullptr, 2, g2));
-            mac_total += tr->c_fwd_u[idx].mac;
-            GroupSpec gu = group(Cup, tr->o_w2[idx], SIZE_MAX, Cskip + Cup, Cup, 1, Cskip, flp);
-            tr->cur_bwd = true; T_TRY(setup_conv(tr, tr->c_dg_us[idx], nm, S, S, Cup, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gu)); tr->cur_bwd = false;
-            mac_total += tr->c_dg_us[idx].mac;
-            if (idx >= 1) {
-                GroupSpec gk = group(Cup, tr->o_w2[idx], SIZE_MAX, Cskip + Cup, Cup, 1, 0, flp);
-                tr->cur_bwd = true; T_TRY(setup_conv(tr, tr->c_dg_skip[idx], nm, S, S, Cskip, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gk)); tr->cur_bwd = false;
-                mac_total += tr->c_dg_skip[idx].mac;
-            }
-            T_TRY(setup_wgrad(tr, tr->wg_u0[idx], nm, S, Cskip, Cskip, Cup, fwd, {}));
-            T_TRY(setup_wgrad(tr, tr->wg_u1[idx], nm, S, Cup, Cup, Cup, fwd, {}));
-            mac_total += (double)S * S * ks * ks * (Cskip + Cup) * Cup;
-        }
-    }
+    for (int idx = L - 1; idx >= 0; --idx) T_TRY(setup_up_layer(tr, idx, S, ACT_LEAKY, mac_total));
     mac_total += 3.0 * P * P * n[1] * K;
     tr->flops_per_image = 2.0 * mac_total;
     T_TRY(talloc(tr, &tr->d_ws, tr->ws_floats));
@@ -1279,6 +1328,433 @@ int pack_all(umx_trainer* tr, hipStream_t st, int part) {
     return UMX_OK;
 }
 
+// ================================================================================================================================
+// The legacy graph (GRAPH_LEGACY, reference UnMicst.py:80-186, the graph of every shipped checkpoint), trained as UnMicst.py:270-279:
+//   down i   y_0 = conv(x, w1); y_e = conv(relu(y_{e-1}), wextra_{e-1}); z = y_E + conv1x1(x, wshort) (second K slab of the last conv);
+//            ds_{i+1} = maxpool2(BN(relu(z))) with batch statistics -- ReLU, then BN, then the pool (on the BN output: gamma may be < 0)
+//   bottom   relu(conv(ds_L, lb.w))
+//   up idx   us = relu(convT_s2(x, wt)); y_0 = conv([ds_idx, us], w2); y_e = conv(relu(y_{e-1}), wextra_{e-1}); output relu(y_E)
+//   top      softmax(conv1x1(x, lt.w)); loss mean_{b,y,x}(-sum_k w labels log p) (w = 1: weights == NULL)
+// No BN outside the down blocks: the loss and softmax kernels read identity statistics.  ReLU forward = act_fwd on identity statistics
+// (it writes the planes of what the next convolution reads); ReLU backward = relu_bwd_kernel, then the planes (split_dyn).  Every
+// launch is on the main stream, in a fixed order; every reduction has a fixed order (no float atomics).
+// ================================================================================================================================
+int alloc_ident(umx_trainer* tr, float** out, int C) {
+    std::vector<float> h(4 * (size_t)C, 0.f);
+    for (int c = 0; c < C; ++c) { h[C + c] = 1.f; h[2 * C + c] = 1.f; }   // mean 0 | rstd 1 | scale 1 | shift 0
+    T_TRY(talloc(tr, out, h.size()));
+    T_HIP(tr, hipMemcpy(*out, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+    return UMX_OK;
+}
+
+int build_legacy(umx_trainer* tr, const float* blob, size_t blob_floats) {
+    const umx_hparams& hp = tr->hp;
+    const int L = hp.nLayers, ks = hp.ks, P = hp.imSize, K = hp.nClasses, B = tr->B, E = hp.nExtraConvs;
+    tr->L = L; tr->K = K; tr->P = P; tr->E = E;
+    tr->n = {hp.nChannels, hp.nOut0};
+    for (int i = 0; i < L; ++i) tr->n.push_back(tr->n.back() * hp.featMapsFact);
+    const std::vector<int>& n = tr->n;
+
+    // ---- parameter vector layout (== unmicst_amd/model.py tensor_specs, GRAPH_LEGACY)
+    size_t pos = 0;
+    auto seg = [&](const std::string& name, size_t cnt) { tr->segs.push_back({name, pos, cnt, 0.f}); pos += cnt; return pos - cnt; };
+    std::vector<size_t> bn_d_off(L);
+    tr->o_w1.resize(L); tr->o_ws.resize(L); tr->o_wt.resize(L); tr->o_w2.resize(L);
+    tr->ldb.resize(L); tr->lub.resize(L);
+    char nm[64];
+    for (int i = 0; i < L; ++i) {
+        const std::string p = "ld" + std::to_string(i);
+        tr->o_w1[i] = seg(p + ".w1", (size_t)ks * ks * n[i] * n[i + 1]);
+        for (int e = 0; e < E; ++e) tr->ldb[i].o_wx.push_back(seg(p + ".wextra" + std::to_string(e), (size_t)ks * ks * n[i + 1] * n[i + 1]));
+        tr->o_ws[i] = seg(p + ".wshort", (size_t)n[i] * n[i + 1]);
+        bn_d_off[i] = seg(p + ".bn", 4 * (size_t)n[i + 1]);
+    }
+    tr->o_lb = seg("lb.w", (size_t)ks * ks * n[L] * n[L + 1]);
+    for (int idx = L - 1; idx >= 0; --idx) {
+        const std::string p = "lu" + std::to_string(idx);
+        tr->o_wt[idx] = seg(p + ".wt", (size_t)ks * ks * n[idx + 1] * n[idx + 2]);
+        tr->o_w2[idx] = seg(p + ".w2", (size_t)ks * ks * (n[idx] + n[idx + 1]) * n[idx + 1]);
+        for (int e = 0; e < E; ++e) tr->lub[idx].o_wx.push_back(seg(p + ".wextra" + std::to_string(e), (size_t)ks * ks * n[idx + 1] * n[idx + 1]));
+    }
+    tr->o_lt = seg("lt.w", (size_t)n[1] * K);
+    tr->nparams = pos;
+    if (blob_floats != pos)
+        return tfail(tr, UMX_ERR_BLOB, "weight blob has %zu floats, the graph needs %zu", blob_floats, pos);
+    T_TRY(talloc(tr, &tr->d_w, pos));
+    T_HIP(tr, hipMemcpy(tr->d_w, blob, pos * sizeof(float), hipMemcpyHostToDevice));
+    T_TRY(tzero(tr, &tr->d_g, pos));
+    T_TRY(tzero(tr, &tr->d_m, pos));
+    T_TRY(tzero(tr, &tr->d_v, pos));
+
+    // ---- max words (zeroed every step), then the range flag
+    tr->n_maxw = 16 + 4 * (L + 1) * (2 * E + 6);
+    T_TRY(tzero(tr, &tr->d_maxw, (size_t)tr->n_maxw + 1));
+    int k = 0;
+    auto word = [&]() { return tr->d_maxw + k++; };
+    tr->dsmax.assign(L + 1, nullptr); tr->usmax.assign(L, nullptr); tr->smax.assign(L, nullptr);
+    for (int i = 0; i <= L; ++i) tr->dsmax[i] = word();
+    for (int i = 0; i < L; ++i) { tr->usmax[i] = word(); tr->smax[i] = word(); }
+    tr->bmax = word();
+    tr->lb_gmax = word();
+    for (std::vector<LBlock>* v : {&tr->ldb, &tr->lub})
+        for (LBlock& b : *v) {
+            for (int e = 0; e <= E; ++e) { b.amax.push_back(word()); b.gmax.push_back(word()); }
+        }
+    if (k > tr->n_maxw) return tfail(tr, UMX_ERR_INVALID, "internal: %d max words for %d", k, tr->n_maxw);
+
+    // ---- activations
+    tr->ds.assign(L + 1, nullptr);
+    tr->bn_d.resize(L);
+    tr->us.assign(L, nullptr); tr->dskip.assign(L, nullptr);
+    tr->hconv = !getenv("UMX_TRAIN_CONV_F32");
+    if (const char* e = getenv("UMX_TRAIN_WSCALE_EVERY")) tr->wscale_every = atoi(e);
+    tr->wg_planes = tr->hconv;
+    tr->h_blob = blob;
+    tr->h_ds.resize(L + 1); tr->h_us.resize(L);   // (no buffers on the exact-fp32 route)
+    if (tr->hconv) {
+        tr->pctx = new umx_ctx();
+        tr->pctx->device = tr->device;
+        tr->pctx->hp = hp;
+    }
+    auto planes = [&](H16& h, size_t npix, int C) -> int { return tr->hconv ? alloc_h16(tr, h, npix, C) : UMX_OK; };
+    // a chain's tensors: y[0..E], a[0..na)
+    auto chain = [&](LBlock& b, int S, int C, int na) -> int {
+        const size_t npix = (size_t)B * S * S;
+        b.y.assign(E + 1, nullptr); b.a.assign(na, nullptr); b.ha.resize(na);
+        for (int e = 0; e <= E; ++e) T_TRY(talloc(tr, &b.y[e], npix * C));
+        for (int e = 0; e < na; ++e) { T_TRY(talloc(tr, &b.a[e], npix * C)); T_TRY(planes(b.ha[e], npix, C)); }
+        return alloc_ident(tr, &b.ident, C);
+    };
+    size_t max_act = (size_t)B * P * P * std::max(n[0], K), max_dz = 0, max_gs = 0;
+    auto grad_size = [&](size_t npix, int C) { max_act = std::max(max_act, npix * C); max_dz = std::max(max_dz, npix * round_up(C, 8)); };
+    int S = P;
+    T_TRY(talloc(tr, &tr->ds[0], (size_t)B * P * P * n[0]));
+    if (tr->hconv) T_TRY(alloc_h16(tr, tr->h_ds[0], (size_t)B * P * P, n[0]));
+    for (int i = 0; i < L; ++i) {
+        T_TRY(chain(tr->ldb[i], S, n[i + 1], E));
+        T_TRY(bn_alloc(tr, tr->bn_d[i], n[i + 1], S, bn_d_off[i]));   // (its z: relu(z), what BN normalises)
+        grad_size((size_t)B * S * S, n[i + 1]);
+        T_TRY(talloc(tr, &tr->ds[i + 1], (size_t)B * (S / 2) * (S / 2) * n[i + 1]));
+        if (tr->hconv) T_TRY(alloc_h16(tr, tr->h_ds[i + 1], (size_t)B * (S / 2) * (S / 2), n[i + 1]));
+        if (i + 1 <= L - 1) T_TRY(talloc(tr, &tr->dskip[i + 1], (size_t)B * (S / 2) * (S / 2) * n[i + 1]));
+        S /= 2;
+    }
+    T_TRY(talloc(tr, &tr->lb_z, (size_t)B * S * S * n[L + 1]));
+    T_TRY(talloc(tr, &tr->act_b, (size_t)B * S * S * n[L + 1]));
+    T_TRY(planes(tr->h_b, (size_t)B * S * S, n[L + 1]));
+    T_TRY(alloc_ident(tr, &tr->lb_ident, n[L + 1]));
+    grad_size((size_t)B * S * S, n[L + 1]);
+    for (int idx = L - 1; idx >= 0; --idx) {
+        max_gs = std::max(max_gs, (size_t)B * S * S * round_up(4 * n[idx + 1], 8));
+        S *= 2;
+        T_TRY(talloc(tr, &tr->us[idx], (size_t)B * S * S * n[idx + 1]));
+        T_TRY(planes(tr->h_us[idx], (size_t)B * S * S, n[idx + 1]));
+        T_TRY(chain(tr->lub[idx], S, n[idx + 1], E + 1));
+        grad_size((size_t)B * S * S, n[idx + 1]);
+    }
+    T_TRY(talloc(tr, &tr->lt_z, (size_t)B * P * P * K));
+    T_TRY(alloc_ident(tr, &tr->ident_k, K));
+    T_TRY(talloc(tr, &tr->d_labels, (size_t)B * P * P * K));
+    T_TRY(talloc(tr, &tr->d_weights, (size_t)B * P * P * K));
+    T_TRY(talloc(tr, &tr->d_probs, (size_t)B * P * P * K));
+    T_TRY(talloc(tr, &tr->d_dt, (size_t)B * P * P * K));
+    {
+        const std::vector<float> ones((size_t)B * P * P * K, 1.f);
+        T_TRY(talloc(tr, &tr->d_ones, ones.size()));
+        T_HIP(tr, hipMemcpy(tr->d_ones, ones.data(), ones.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    tr->max_act = max_act;
+    T_TRY(talloc(tr, &tr->DA, max_act));
+    T_TRY(talloc(tr, &tr->DB, max_act));
+    T_TRY(talloc(tr, &tr->DZ, max_act));
+    T_TRY(talloc(tr, &tr->TX, max_act));
+    T_TRY(talloc(tr, &tr->GS, max_act));
+    T_TRY(talloc(tr, &tr->DSUM, 2 * max_act));
+    int maxC = K;
+    for (int v : n) maxC = std::max(maxC, v);
+    tr->part_doubles = std::max<size_t>((size_t)1024 * 2 * maxC, (size_t)1024 * n[1] * K) + 1024;
+    T_TRY(talloc(tr, &tr->d_part, tr->part_doubles));
+    T_TRY(tzero(tr, &tr->d_loss, 2));
+    if (tr->hconv) {   // gradient planes: two for a chain (alternating), one for the transposed conv's space-to-depth gradient
+        for (int sl = 0; sl < 2; ++sl) { T_TRY(tzero(tr, &tr->h_dz[sl].hi, max_dz)); T_TRY(tzero(tr, &tr->h_dz[sl].lo, max_dz)); }
+        T_TRY(tzero(tr, &tr->h_gs[0].hi, max_gs)); T_TRY(tzero(tr, &tr->h_gs[0].lo, max_gs));
+        T_TRY(tzero(tr, &tr->d_xinv, 2 * kSlots));
+    }
+
+    // ---- conv launches
+    tr->c_dg_d.resize(L); tr->c_T.resize(L); tr->c_fwd_u.resize(L);
+    tr->c_dg_us.resize(L); tr->c_dg_skip.resize(L); tr->c_dg_T.resize(L);
+    tr->wg_d.resize(L); tr->wg_u0.resize(L); tr->wg_u1.resize(L); tr->wg_T.resize(L);
+    for (std::vector<LBlock>* v : {&tr->ldb, &tr->lub})
+        for (LBlock& b : *v) { b.fwd.resize(E + 1); b.dg.resize(E + 1); b.wg.resize(E + 1); }
+    const TapSet fwd = same_taps(ks, false), flp = same_taps(ks, true);
+    TapSet ctr;   // the 1x1 shortcut: one tap at the centre
+    ctr.off.push_back({0, 0});
+    ctr.m.push_back(0);
+    double mac_total = 0.0;
+    // extra conv e >= 1 of a chain at size S with C channels: forward (ngroups 2: + the shortcut group g1), input and weight gradient
+    auto extra = [&](LBlock& b, int e, int S, int C, int ngroups, const GroupSpec* g1) -> int {
+        GroupSpec g[2] = {one_group(C, b.o_wx[e - 1], SIZE_MAX, C, C, 0, 0, fwd), g1 ? *g1 : GroupSpec()};
+        T_TRY(setup_conv(tr, b.fwd[e], nm, S, S, C, ACT_NONE, 1, 1, nullptr, nullptr, ngroups, g));
+        GroupSpec gd = one_group(C, b.o_wx[e - 1], SIZE_MAX, C, C, 1, 0, flp);
+        tr->cur_bwd = true; T_TRY(setup_conv(tr, b.dg[e], nm, S, S, C, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gd)); tr->cur_bwd = false;
+        T_TRY(setup_wgrad(tr, b.wg[e], nm, S, C, C, C, fwd, {}));
+        mac_total += b.fwd[e].mac + b.dg[e].mac + (double)S * S * ks * ks * C * C;
+        return UMX_OK;
+    };
+    S = P;
+    for (int i = 0; i < L; ++i) {
+        snprintf(nm, sizeof nm, "ld%d", i);
+        LBlock& b = tr->ldb[i];
+        const int Ci = n[i], C = n[i + 1];
+        const GroupSpec gsh = one_group(Ci, tr->o_ws[i], SIZE_MAX, Ci, C, 0, 0, ctr);
+        GroupSpec g[2] = {one_group(Ci, tr->o_w1[i], SIZE_MAX, Ci, C, 0, 0, fwd), gsh};
+        T_TRY(setup_conv(tr, b.fwd[0], nm, S, S, C, ACT_NONE, 1, 1, nullptr, nullptr, E == 0 ? 2 : 1, g));
+        mac_total += b.fwd[0].mac;
+        for (int e = 1; e <= E; ++e) T_TRY(extra(b, e, S, C, e == E ? 2 : 1, &gsh));
+        if (i >= 1) {
+            GroupSpec gd = one_group(C, tr->o_w1[i], SIZE_MAX, Ci, C, 1, 0, flp);
+            GroupSpec gs = one_group(C, tr->o_ws[i], SIZE_MAX, Ci, C, 1, 0, ctr);
+            tr->cur_bwd = true;
+            T_TRY(setup_conv(tr, tr->c_dg_d[i], nm, S, S, Ci, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gd));
+            T_TRY(setup_conv(tr, b.dg_sh, nm, S, S, Ci, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gs));
+            tr->cur_bwd = false;
+            mac_total += tr->c_dg_d[i].mac + b.dg_sh.mac;
+        }
+        T_TRY(setup_wgrad(tr, tr->wg_d[i], nm, S, Ci, Ci, C, fwd, {}));
+        T_TRY(setup_wgrad(tr, b.wg_sh, nm, S, Ci, Ci, C, ctr, {}));
+        mac_total += (double)S * S * (ks * ks + 1) * Ci * C;
+        S /= 2;
+    }
+    {
+        GroupSpec g = one_group(n[L], tr->o_lb, SIZE_MAX, n[L], n[L + 1], 0, 0, fwd);
+        T_TRY(setup_conv(tr, tr->c_fwd_b, "lb", S, S, n[L + 1], ACT_NONE, 1, 1, nullptr, nullptr, 1, &g));
+        GroupSpec gd = one_group(n[L + 1], tr->o_lb, SIZE_MAX, n[L], n[L + 1], 1, 0, flp);
+        tr->cur_bwd = true; T_TRY(setup_conv(tr, tr->c_dg_b, "lb", S, S, n[L], ACT_NONE, 1, 1, nullptr, nullptr, 1, &gd)); tr->cur_bwd = false;
+        T_TRY(setup_wgrad(tr, tr->wg_b, "lb", S, n[L], n[L], n[L + 1], fwd, {}));
+        mac_total += tr->c_fwd_b.mac + tr->c_dg_b.mac + (double)S * S * ks * ks * n[L] * n[L + 1];
+    }
+    for (int idx = L - 1; idx >= 0; --idx) {
+        T_TRY(setup_up_layer(tr, idx, S, ACT_RELU, mac_total));
+        snprintf(nm, sizeof nm, "lu%d", idx);
+        for (int e = 1; e <= E; ++e) T_TRY(extra(tr->lub[idx], e, S, n[idx + 1], 1, nullptr));
+    }
+    mac_total += 3.0 * P * P * n[1] * K;
+    tr->flops_per_image = 2.0 * mac_total;
+    T_TRY(talloc(tr, &tr->d_ws, tr->ws_floats));
+    T_TRY(talloc(tr, &tr->d_split, tr->split_floats));
+    std::stable_partition(tr->packs.begin(), tr->packs.end(), [](const PackDesc& d) { return d.bwd == 0; });
+    std::stable_partition(tr->rdescs.begin(), tr->rdescs.end(), [](const RepackDesc& d) { return d.bwd == 0; });
+    tr->n_fwd_packs = (int)std::count_if(tr->packs.begin(), tr->packs.end(), [](const PackDesc& d) { return d.bwd == 0; });
+    tr->n_fwd_rdescs = (int)std::count_if(tr->rdescs.begin(), tr->rdescs.end(), [](const RepackDesc& d) { return d.bwd == 0; });
+    T_TRY(talloc(tr, &tr->d_packs, tr->packs.size()));
+    if (!tr->packs.empty())
+        T_HIP(tr, hipMemcpy(tr->d_packs, tr->packs.data(), tr->packs.size() * sizeof(PackDesc), hipMemcpyHostToDevice));
+    if (!tr->rdescs.empty()) {
+        T_TRY(talloc(tr, &tr->d_rdescs, tr->rdescs.size()));
+        T_HIP(tr, hipMemcpy(tr->d_rdescs, tr->rdescs.data(), tr->rdescs.size() * sizeof(RepackDesc), hipMemcpyHostToDevice));
+    }
+    tr->h_blob = nullptr;
+    return UMX_OK;
+}
+
+// forward of the legacy graph up to the logits.  training: batch statistics (moving averages updated when `update`) and the max
+// words of every tensor a weight gradient reads; otherwise the moving statistics (tfTraining: 0)
+int forward_legacy(umx_trainer* tr, const float* data, bool training, bool update) {
+    const int L = tr->L, E = tr->E;
+    const std::vector<int>& n = tr->n;
+    hipStream_t st = tr->stream;
+    const size_t Bz = (size_t)tr->B;
+    int* const flagp = reinterpret_cast<int*>(tr->d_maxw + tr->n_maxw);
+    auto conv = [&](TConv& tc, const float* x0, const float* x1, const H16* h0, const H16* h1, float* dst) -> int {
+        if (tc.hidx >= 0) return run_hconv(tr, tc, *h0, h1, dst, nullptr, st);
+        return run_conv(tr, tc, x0, x1, dst);
+    };
+    auto act = [&](const float* z, const float* stat, int S, int C, int pool, int a_kind, float* out, const H16* h, unsigned* omax) -> int {
+        ActParams a;
+        a.z = z; a.stat = stat;
+        a.B = tr->B; a.H = a.W = S; a.C = C;
+        a.pool = pool; a.act = a_kind;
+        a.drop_rate = 0.f; a.drop_key = 0;
+        const bool pl = tr->hconv && h;
+        T_HIP(tr, launch_act_fwd(a, out, training ? omax : nullptr, pl ? h->hi : nullptr, pl ? h->lo : nullptr, pl ? h->Cs : 0, flagp, st));
+        return UMX_OK;
+    };
+    auto H = [&](H16& h) -> const H16* { return tr->hconv ? &h : nullptr; };
+    tr->ds[0] = const_cast<float*>(data);
+    if (training && !tr->hconv) T_HIP(tr, launch_absmax(data, Bz * tr->P * tr->P * n[0], tr->dsmax[0], st));
+    if (tr->hconv) T_TRY(to_h16(tr, data, Bz * tr->P * tr->P, n[0], tr->h_ds[0], nullptr, nullptr, st, training ? tr->dsmax[0] : nullptr));
+    int S = tr->P;
+    for (int i = 0; i < L; ++i) {
+        LBlock& b = tr->ldb[i];
+        BnSite& s = tr->bn_d[i];
+        const int C = n[i + 1];
+        for (int e = 0; e <= E; ++e) {
+            const bool last = e == E;   // (+ the shortcut on the block input)
+            T_TRY(conv(b.fwd[e], e == 0 ? tr->ds[i] : b.a[e - 1], last ? tr->ds[i] : nullptr, e == 0 ? H(tr->h_ds[i]) : H(b.ha[e - 1]),
+                       last ? H(tr->h_ds[i]) : nullptr, b.y[e]));
+            if (!last) T_TRY(act(b.y[e], b.ident, S, C, 0, ACT_RELU, b.a[e], H(b.ha[e]), b.amax[e]));
+        }
+        T_TRY(act(b.y[E], b.ident, S, C, 0, ACT_RELU, s.z, nullptr, nullptr));      // relu(z): what BN normalises
+        T_TRY(bn_forward_stats(tr, s, update, training));
+        T_TRY(act(s.z, s.stat, S, C, 1, ACT_NONE, tr->ds[i + 1], H(tr->h_ds[i + 1]), tr->dsmax[i + 1]));   // BN, then the pool
+        S /= 2;
+    }
+    T_TRY(conv(tr->c_fwd_b, tr->ds[L], nullptr, H(tr->h_ds[L]), nullptr, tr->lb_z));
+    T_TRY(act(tr->lb_z, tr->lb_ident, S, n[L + 1], 0, ACT_RELU, tr->act_b, H(tr->h_b), tr->bmax));
+    const float* cur = tr->act_b;
+    const H16* hcur = H(tr->h_b);
+    for (int idx = L - 1; idx >= 0; --idx) {
+        LBlock& b = tr->lub[idx];
+        const int C = n[idx + 1];
+        S *= 2;
+        T_TRY(conv(tr->c_T[idx], cur, nullptr, hcur, nullptr, tr->us[idx]));   // (ReLU fused)
+        if (training && !tr->hconv) T_HIP(tr, launch_absmax(tr->us[idx], Bz * S * S * C, tr->usmax[idx], st));
+        if (tr->hconv) T_TRY(to_h16(tr, tr->us[idx], Bz * S * S, C, tr->h_us[idx], nullptr, nullptr, st, training ? tr->usmax[idx] : nullptr));
+        for (int e = 0; e <= E; ++e) {
+            if (e == 0) T_TRY(conv(tr->c_fwd_u[idx], tr->ds[idx], tr->us[idx], H(tr->h_ds[idx]), H(tr->h_us[idx]), b.y[0]));
+            else T_TRY(conv(b.fwd[e], b.a[e - 1], nullptr, H(b.ha[e - 1]), nullptr, b.y[e]));
+            T_TRY(act(b.y[e], b.ident, S, C, 0, ACT_RELU, b.a[e], H(b.ha[e]), b.amax[e]));
+        }
+        cur = b.a[E];
+        hcur = H(b.ha[E]);
+    }
+    T_HIP(tr, launch_head_fwd(cur, Bz * tr->P * tr->P, n[1], tr->K, tr->d_w + tr->o_lt, tr->lt_z, st));
+    return UMX_OK;
+}
+
+int enqueue_legacy(umx_trainer* tr, const float* data, const float* labels, const float* weights, bool update) {
+    const int L = tr->L, K = tr->K, B = tr->B, P = tr->P, E = tr->E;
+    const std::vector<int>& n = tr->n;
+    hipStream_t st = tr->stream;
+    const umx_train_options& o = tr->o;
+    const size_t Npix = (size_t)B * P * P;
+    int* const flagp = reinterpret_cast<int*>(tr->d_maxw + tr->n_maxw);
+    if (update && tr->step > 0 && tr->wscale_every > 0 && tr->step % tr->wscale_every == 0) T_TRY(refresh_wscales(tr));
+    if (tr->prof) T_HIP(tr, hipEventRecord(tr->ev[0], st));
+    T_HIP(tr, hipMemsetAsync(tr->d_loss, 0, 2 * sizeof(double), st));
+    T_HIP(tr, hipMemsetAsync(tr->d_maxw, 0, tr->n_maxw * sizeof(unsigned), st));   // (the range flag behind them stays: see enqueue_step)
+    T_TRY(pack_all(tr, st, 2));
+    T_TRY(forward_legacy(tr, data, true, update));
+    {
+        const int nblk = loss_blocks(Npix);
+        T_HIP(tr, launch_softmax_loss(tr->lt_z, tr->ident_k, labels, weights ? weights : tr->d_ones, Npix, K, o.clip_eps, tr->d_probs,
+                                      tr->d_dt, tr->d_part, nblk, st));
+        T_HIP(tr, launch_sum_to_scalar(tr->d_part, nblk, 1.0 / (double)Npix, tr->d_loss, 0, 0, st));
+    }
+    if (tr->prof) T_HIP(tr, hipEventRecord(tr->ev[1], st));
+
+    // ------------------------------------------------------------------ backward
+    const float* top_in = tr->lub[0].a[E];
+    {   // top: d loss / d logits -> 1x1 conv
+        const int nblk = chan_blocks(Npix, n[1]);
+        T_HIP(tr, launch_head_bwd(top_in, tr->d_dt, tr->d_w + tr->o_lt, Npix, n[1], K, tr->DA, tr->d_part, nblk, st));
+        T_HIP(tr, launch_reduce_partials(tr->d_part, nblk, n[1] * K, 1.0, tr->d_g + tr->o_lt, tr->d_w + tr->o_lt, 0, 0.f, st));
+    }
+    float* const gb[2] = {tr->DZ, tr->TX};   // a chain's gradients alternate between these two, their planes between h_dz[0] / [1]
+    auto dgrad = [&](TConv& tc, const float* x, int pl, float* dst) -> int {
+        if (tc.hidx >= 0) return run_hconv(tr, tc, tr->h_dz[pl], nullptr, dst, tr->d_xinv + pl, st);
+        return run_conv(tr, tc, x, nullptr, dst);
+    };
+    // gradient w.r.t. y (pre-ReLU) from the gradient w.r.t. relu(y): into gb[pl], with its max word and planes
+    auto relu_bwd = [&](const float* dy, const float* y, int pl, size_t npix, int C, unsigned* gw) -> int {
+        T_HIP(tr, launch_relu_bwd_max(dy, y, gb[pl], npix * C, gw, st));
+        tr->h_dz[pl].Cs = round_up(C, 8);
+        return to_h16(tr, gb[pl], npix, C, tr->h_dz[pl], gw, tr->d_xinv + pl, st);
+    };
+    auto wgrad = [&](WgradParams& w, const float* X, const H16* xp, const unsigned* xmax, int pl, unsigned* gw, int Ctot, int c_off,
+                     size_t w_off) -> int {
+        return run_wgrad(tr, w, X, gb[pl], Ctot, c_off, w_off, 0.f, SIZE_MAX, xmax, gw, st, tr->hconv ? xp : nullptr, nullptr,
+                         tr->hconv ? &tr->h_dz[pl] : nullptr, tr->d_xinv + pl);
+    };
+    // the extra convolutions of a chain, last first: gb[(E - e) & 1] holds d/dy[e]; on return gb[E & 1] holds d/dy[0]
+    auto extras_bwd = [&](LBlock& b, size_t npix, int C) -> int {
+        for (int e = E; e >= 1; --e) {
+            const int pl = (E - e) & 1;
+            T_TRY(wgrad(b.wg[e], b.a[e - 1], &b.ha[e - 1], b.amax[e - 1], pl, b.gmax[e], C, 0, b.o_wx[e - 1]));
+            T_TRY(dgrad(b.dg[e], gb[pl], pl, tr->DA));
+            T_TRY(relu_bwd(tr->DA, b.y[e - 1], pl ^ 1, npix, C, b.gmax[e - 1]));
+        }
+        return UMX_OK;
+    };
+    int S = P;
+    for (int idx = 0; idx < L; ++idx) {    // up layers, output side first; DA: d loss / d (layer output)
+        LBlock& b = tr->lub[idx];
+        const int Cskip = n[idx], Cup = n[idx + 1];
+        const size_t npix = (size_t)B * S * S;
+        T_TRY(relu_bwd(tr->DA, b.y[E], 0, npix, Cup, b.gmax[E]));
+        T_TRY(extras_bwd(b, npix, Cup));
+        const int p0 = E & 1;
+        T_TRY(wgrad(tr->wg_u0[idx], tr->ds[idx], &tr->h_ds[idx], tr->dsmax[idx], p0, b.gmax[0], Cskip + Cup, 0, tr->o_w2[idx]));
+        T_TRY(wgrad(tr->wg_u1[idx], tr->us[idx], &tr->h_us[idx], tr->usmax[idx], p0, b.gmax[0], Cskip + Cup, Cskip, tr->o_w2[idx]));
+        T_TRY(dgrad(tr->c_dg_us[idx], gb[p0], p0, tr->DB));
+        if (idx >= 1) T_TRY(dgrad(tr->c_dg_skip[idx], gb[p0], p0, tr->dskip[idx]));
+        T_HIP(tr, launch_leaky_bwd_s2d_max(tr->DB, tr->us[idx], B, S / 2, Cup, 0.f, tr->GS, tr->smax[idx], st));   // ReLU: slope 0
+        if (tr->hconv) {
+            tr->h_gs[0].Cs = round_up(4 * Cup, 8);
+            T_TRY(to_h16(tr, tr->GS, (size_t)B * (S / 2) * (S / 2), 4 * Cup, tr->h_gs[0], tr->smax[idx], tr->d_xinv + kSlots, st));
+        }
+        const float* layer_in = idx == L - 1 ? tr->act_b : tr->lub[idx + 1].a[E];
+        const H16* hin = !tr->hconv ? nullptr : idx == L - 1 ? &tr->h_b : &tr->lub[idx + 1].ha[E];
+        T_TRY(run_wgrad(tr, tr->wg_T[idx], tr->GS, layer_in, Cup, 0, tr->o_wt[idx], 0.f, SIZE_MAX, tr->smax[idx],
+                        idx == L - 1 ? tr->bmax : tr->lub[idx + 1].amax[E], st, tr->hconv ? &tr->h_gs[0] : nullptr, tr->d_xinv + kSlots, hin,
+                        nullptr));
+        if (tr->c_dg_T[idx].hidx >= 0)
+            T_TRY(run_hconv(tr, tr->c_dg_T[idx], tr->h_gs[0], nullptr, tr->DA, tr->d_xinv + kSlots, st));
+        else
+            T_TRY(run_conv(tr, tr->c_dg_T[idx], tr->GS, nullptr, tr->DA));
+        S /= 2;
+    }
+    {   // bottom
+        const size_t npix = (size_t)B * S * S;
+        T_TRY(relu_bwd(tr->DA, tr->lb_z, 0, npix, n[L + 1], tr->lb_gmax));
+        T_TRY(wgrad(tr->wg_b, tr->ds[L], &tr->h_ds[L], tr->dsmax[L], 0, tr->lb_gmax, n[L], 0, tr->o_lb));
+        T_TRY(dgrad(tr->c_dg_b, gb[0], 0, tr->DB));
+    }
+    for (int i = L - 1; i >= 0; --i) {     // down layers; DB (+ dskip[i+1]): d loss / d ds[i+1]
+        S *= 2;
+        LBlock& b = tr->ldb[i];
+        BnSite& s = tr->bn_d[i];
+        const int Ci = n[i], C = n[i + 1];
+        const size_t npix = (size_t)B * S * S;
+        {   // pool -> BN backward on relu(z) (gamma / beta gradients in a fixed order) -> the ReLU mask
+            ActParams a = act_params(tr, s, 1, ACT_NONE, 0.f, 0);
+            const int nblk = chan_blocks(npix / 4, C);
+            T_HIP(tr, launch_act_bwd(a, tr->DB, i + 1 <= L - 1 ? tr->dskip[i + 1] : nullptr, gb[0], tr->d_part, nblk, nullptr, st));
+            T_HIP(tr, launch_bn_bwd_finalize(tr->d_part, nblk, npix, C, tr->d_g + s.gamma, tr->d_g + s.beta, s.m12, st));
+            T_HIP(tr, launch_bn_bwd_apply_max(gb[0], s.z, s.stat, s.m12, npix, C, nullptr, nullptr, nullptr, nullptr, nullptr, 0, flagp, st));
+            T_TRY(relu_bwd(gb[0], b.y[E], 0, npix, C, b.gmax[E]));
+        }
+        // the shortcut: weight gradient and (i >= 1) input gradient, before the chain reuses gb[0]
+        T_TRY(wgrad(b.wg_sh, tr->ds[i], &tr->h_ds[i], tr->dsmax[i], 0, b.gmax[E], Ci, 0, tr->o_ws[i]));
+        if (i >= 1) T_TRY(dgrad(b.dg_sh, gb[0], 0, tr->DSUM + tr->max_act));
+        T_TRY(extras_bwd(b, npix, C));
+        const int p0 = E & 1;
+        T_TRY(wgrad(tr->wg_d[i], tr->ds[i], &tr->h_ds[i], tr->dsmax[i], p0, b.gmax[0], Ci, 0, tr->o_w1[i]));
+        if (i >= 1) {   // d ds[i] = first-conv input gradient + shortcut input gradient
+            T_TRY(dgrad(tr->c_dg_d[i], gb[p0], p0, tr->DSUM));
+            T_HIP(tr, launch_split_reduce(tr->DSUM, 2, tr->max_act, npix * Ci, ACT_NONE, tr->DB, st));
+        }
+    }
+    if (tr->prof) T_HIP(tr, hipEventRecord(tr->ev[2], st));
+    if (update) {   // MomentumOptimizer (or Adam, when asked for) over the flat vector; BN moving statistics were updated in the forward pass
+        OptParams op;
+        op.kind = o.optimizer;
+        const double lr = (double)o.lr0 * std::pow((double)o.decay_rate, (double)(tr->step / std::max(1, o.decay_steps)));
+        const double tt = (double)(tr->step + 1);
+        op.lr = (float)lr;
+        op.lr_t = (float)(lr * std::sqrt(1.0 - std::pow((double)o.beta2, tt)) / (1.0 - std::pow((double)o.beta1, tt)));
+        op.beta1 = o.beta1; op.beta2 = o.beta2; op.eps = o.adam_eps; op.momentum = o.momentum;
+        T_HIP(tr, launch_optimizer(op, tr->d_w, tr->d_g, tr->d_m, tr->d_v, tr->nparams, st));
+        tr->step += 1;
+    }
+    if (tr->prof) {
+        T_HIP(tr, hipEventRecord(tr->ev[3], st));
+        tr->pending = true;
+    }
+    return UMX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1303,14 +1779,30 @@ void umx_train_options_duo(umx_train_options* o) {
     o->drop_up0 = 0.25f; o->drop_up_step = 0.05f;                           // :203
 }
 
+void umx_train_options_legacy(umx_train_options* o) {
+    fill_common(o);
+    o->optimizer = UMX_OPT_MOMENTUM;                                        // UnMicst.py:270-279
+    o->lr0 = 0.01f; o->decay_steps = 1000; o->decay_rate = 0.95f;
+    o->momentum = 0.9f;
+    o->reg_kind = UMX_REG_NONE;                                             // :276 (unweighted, no clip, no regulariser)
+}
+
 const char* umx_trainer_last_error(const umx_trainer* tr) { return tr ? tr->err.c_str() : g_terr.c_str(); }
 
 int umx_trainer_create(const umx_hparams* hp, const float* weight_blob, size_t blob_floats, const umx_train_options* opts,
                        umx_trainer** out) {
     if (!hp || !weight_blob || !opts || !out) return tfail(nullptr, UMX_ERR_INVALID, "null argument");
     *out = nullptr;
-    if (hp->graph != UMX_GRAPH_V2 || hp->nExtraConvs != 0)
+    const bool legacy = hp->graph == UMX_GRAPH_LEGACY;
+    if (legacy) {
+        if (hp->nExtraConvs < 0 || hp->nExtraConvs > 2)
+            return tfail(nullptr, UMX_ERR_INVALID, "the training step covers the legacy graph with nExtraConvs 0..2");
+        if (opts->reg_kind != UMX_REG_NONE || opts->drop_down_step != 0.f || opts->drop_bottom != 0.f || opts->drop_up0 != 0.f ||
+            opts->drop_up_step != 0.f)
+            return tfail(nullptr, UMX_ERR_INVALID, "the legacy graph has no dropout and no regulariser (umx_train_options_legacy)");
+    } else if (hp->graph != UMX_GRAPH_V2 || hp->nExtraConvs != 0) {
         return tfail(nullptr, UMX_ERR_INVALID, "the training step covers the v2 graph with nExtraConvs == 0");
+    }
     if (hp->nClasses < 1 || hp->nClasses > 8) return tfail(nullptr, UMX_ERR_INVALID, "nClasses must be 1..8");
     if (hp->nLayers < 1 || hp->nLayers > 8 || (hp->ks != 3 && hp->ks != 5) || hp->featMapsFact < 1 ||
         hp->nChannels < 1 || hp->nOut0 < 1)
@@ -1331,11 +1823,12 @@ int umx_trainer_create(const umx_hparams* hp, const float* weight_blob, size_t b
     tr->o = *opts;
     tr->device = opts->device_ordinal;
     tr->B = opts->batch > 0 ? opts->batch : 8;
+    tr->legacy = legacy;
     int rc = UMX_OK;
     if (hipSetDevice(tr->device) != hipSuccess) rc = tfail(tr, UMX_ERR_HIP, "hipSetDevice failed");
     if (rc == UMX_OK && hipStreamCreateWithFlags(&tr->stream, hipStreamNonBlocking) != hipSuccess)
         rc = tfail(tr, UMX_ERR_HIP, "hipStreamCreate failed");
-    if (rc == UMX_OK) rc = build_trainer(tr, weight_blob, blob_floats);
+    if (rc == UMX_OK) rc = legacy ? build_legacy(tr, weight_blob, blob_floats) : build_trainer(tr, weight_blob, blob_floats);
     if (rc == UMX_OK)
         for (int i = 0; i < 4; ++i)
             if (hipEventCreate(&tr->ev[i]) != hipSuccess) rc = tfail(tr, UMX_ERR_HIP, "hipEventCreate failed");
@@ -1393,11 +1886,12 @@ void umx_trainer_destroy(umx_trainer* tr) {
 
 int umx_train_step_dev(umx_trainer* tr, const float* data_dev, const float* labels_dev, const float* weights_dev,
                        int apply_update) {
-    if (!tr || !data_dev || !labels_dev || !weights_dev) return tfail(tr, UMX_ERR_INVALID, "null argument");
+    if (!tr || !data_dev || !labels_dev || (!weights_dev && !tr->legacy)) return tfail(tr, UMX_ERR_INVALID, "null argument");
     T_HIP(tr, hipSetDevice(tr->device));
     T_TRY(fold_profile(tr));
     float* own = tr->ds[0];
-    const int rc = enqueue_step(tr, data_dev, labels_dev, weights_dev, apply_update != 0);
+    const int rc = tr->legacy ? enqueue_legacy(tr, data_dev, labels_dev, weights_dev, apply_update != 0)
+                              : enqueue_step(tr, data_dev, labels_dev, weights_dev, apply_update != 0);
     tr->ds[0] = own;
     return rc;
 }
@@ -1428,13 +1922,13 @@ int umx_trainer_loss(umx_trainer* tr, double* loss3) {
 
 int umx_train_step(umx_trainer* tr, const float* data, const float* labels, const float* weights, int apply_update,
                    double* loss3) {
-    if (!tr || !data || !labels || !weights) return tfail(tr, UMX_ERR_INVALID, "null argument");
+    if (!tr || !data || !labels || (!weights && !tr->legacy)) return tfail(tr, UMX_ERR_INVALID, "null argument");
     T_HIP(tr, hipSetDevice(tr->device));
     const size_t npx = (size_t)tr->B * tr->P * tr->P;
     T_HIP(tr, hipMemcpyAsync(tr->ds[0], data, npx * tr->n[0] * sizeof(float), hipMemcpyHostToDevice, tr->stream));
     T_HIP(tr, hipMemcpyAsync(tr->d_labels, labels, npx * tr->K * sizeof(float), hipMemcpyHostToDevice, tr->stream));
-    T_HIP(tr, hipMemcpyAsync(tr->d_weights, weights, npx * tr->K * sizeof(float), hipMemcpyHostToDevice, tr->stream));
-    T_TRY(umx_train_step_dev(tr, tr->ds[0], tr->d_labels, tr->d_weights, apply_update));
+    if (weights) T_HIP(tr, hipMemcpyAsync(tr->d_weights, weights, npx * tr->K * sizeof(float), hipMemcpyHostToDevice, tr->stream));
+    T_TRY(umx_train_step_dev(tr, tr->ds[0], tr->d_labels, weights ? tr->d_weights : nullptr, apply_update));
     double l[3];
     T_TRY(umx_trainer_loss(tr, l));
     if (loss3) { loss3[0] = l[0]; loss3[1] = l[1]; loss3[2] = l[2]; }
@@ -1458,10 +1952,11 @@ int umx_trainer_eval(umx_trainer* tr, const float* data, float* probs_host) {
     }
     T_HIP(tr, hipMemcpyAsync(own, data, npx * tr->n[0] * sizeof(float), hipMemcpyHostToDevice, tr->stream));
     T_TRY(pack_all(tr, tr->stream, 0));
-    const int rc = forward_pass(tr, own, false, false);
+    const int rc = tr->legacy ? forward_legacy(tr, own, false, false) : forward_pass(tr, own, false, false);
     tr->ds[0] = own;
     T_TRY(rc);
-    T_HIP(tr, launch_softmax_only(tr->bn_t.z, tr->bn_t.stat, npx, tr->K, tr->d_probs, tr->stream));
+    if (tr->legacy) T_HIP(tr, launch_softmax_only(tr->lt_z, tr->ident_k, npx, tr->K, tr->d_probs, tr->stream));
+    else T_HIP(tr, launch_softmax_only(tr->bn_t.z, tr->bn_t.stat, npx, tr->K, tr->d_probs, tr->stream));
     T_HIP(tr, hipMemcpyAsync(probs_host, tr->d_probs, npx * tr->K * sizeof(float), hipMemcpyDeviceToHost, tr->stream));
     T_HIP(tr, hipMemcpyAsync(&flag, tr->d_maxw + tr->n_maxw, sizeof flag, hipMemcpyDeviceToHost, tr->stream));
     T_HIP(tr, hipStreamSynchronize(tr->stream));
@@ -1501,7 +1996,24 @@ int umx_trainer_read_tensor(umx_trainer* tr, const char* name, float* out, size_
     };
     const BnSite* site = nullptr;
     int i;
-    if (layer == "lb") site = &tr->bn_b;
+    // the legacy graph's decision sites: ld<i>.x<e> / lu<i>.x<e> (what extra conv e reads, pre-ReLU), ld<i>.z (main + shortcut) and
+    // lu<i>.z / lb.z (pre-ReLU), ld<i>.stat (statistics of relu(z)), lt.z (logits); lu<i>.us and ds<i> as in v2
+    if (tr->legacy && what.size() >= 2 && what[0] == 'x' && what.find_first_not_of("0123456789", 1) == std::string::npos) {
+        const int e = atoi(what.c_str() + 1);
+        const LBlock* b = (i = index_of("ld", tr->L)) >= 0 ? &tr->ldb[i] : (i = index_of("lu", tr->L)) >= 0 ? &tr->lub[i] : nullptr;
+        if (b && e < tr->E) { src = b->y[e]; n = (size_t)tr->B * (tr->P >> i) * (tr->P >> i) * tr->n[i + 1]; }
+    } else if (tr->legacy && what == "z" && (layer == "lb" || layer == "lt")) {
+        const int S = layer == "lb" ? tr->P >> tr->L : tr->P;
+        src = layer == "lb" ? tr->lb_z : tr->lt_z;
+        n = (size_t)tr->B * S * S * (layer == "lb" ? tr->n[tr->L + 1] : tr->K);
+    } else if (tr->legacy && what == "z" && ((i = index_of("ld", tr->L)) >= 0 || (i = index_of("lu", tr->L)) >= 0)) {
+        src = (layer[1] == 'd' ? tr->ldb[i] : tr->lub[i]).y[tr->E];
+        n = (size_t)tr->B * (tr->P >> i) * (tr->P >> i) * tr->n[i + 1];
+    } else if (tr->legacy && what == "stat" && (i = index_of("ld", tr->L)) >= 0) {
+        site = &tr->bn_d[i];
+    } else if (tr->legacy) {
+        // (us / ds below)
+    } else if (layer == "lb") site = &tr->bn_b;
     else if (layer == "lt") site = &tr->bn_t;
     else if ((i = index_of("ld", tr->L)) >= 0) site = &tr->bn_d[i];
     else if ((i = index_of("lu", tr->L)) >= 0) site = &tr->bn_u[i];

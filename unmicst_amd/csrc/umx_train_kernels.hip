@@ -828,7 +828,7 @@ hipError_t launch_bn_bwd_apply_max(float* g, const float* z, const float* stat, 
 }
 
 __global__ void __launch_bounds__(256) leaky_bwd_s2d_kernel(const float* __restrict__ d_us, const float* __restrict__ us,
-                                                            int S, int C, float* __restrict__ gS, size_t n, unsigned* gmax) {
+                                                            int S, int C, float* __restrict__ gS, size_t n, float slope, unsigned* gmax) {
     float mx = 0.f;
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
         const int c = (int)(e % C);
@@ -838,7 +838,7 @@ __global__ void __launch_bounds__(256) leaky_bwd_s2d_kernel(const float* __restr
         const int i = (int)(r % S);
         const size_t b = r / S;
         const size_t src = ((b * (2 * S) + 2 * i + (q >> 1)) * (size_t)(2 * S) + 2 * j + (q & 1)) * C + c;
-        const float v = d_us[src] * (us[src] > 0.f ? 1.f : 0.2f);
+        const float v = d_us[src] * (us[src] > 0.f ? 1.f : slope);
         gS[e] = v;
         mx = fmaxf(mx, fabsf(v));
     }
@@ -848,7 +848,8 @@ __global__ void __launch_bounds__(256) leaky_bwd_s2d_kernel(const float* __restr
 // C % 4 == 0 and < 2^32 elements (every layer of the shipped widths): four channels per thread, 16-byte accesses, 32-bit index
 // arithmetic (the scalar kernel: 146 us for 3 x 75 MB at 8 x 256 x 256 x 36, this one the memory time)
 __global__ void __launch_bounds__(256) leaky_bwd_s2d_v4_kernel(const float4* __restrict__ d_us, const float4* __restrict__ us,
-                                                               unsigned S, unsigned Q, float4* __restrict__ gS, unsigned n4, unsigned* gmax) {
+                                                               unsigned S, unsigned Q, float4* __restrict__ gS, unsigned n4, float slope,
+                                                               unsigned* gmax) {
     float mx = 0.f;
     for (unsigned e = blockIdx.x * 256 + threadIdx.x; e < n4; e += gridDim.x * 256) {
         const unsigned q4 = e % Q;
@@ -860,28 +861,47 @@ __global__ void __launch_bounds__(256) leaky_bwd_s2d_v4_kernel(const float4* __r
         const unsigned src = ((b * (2 * S) + 2 * i + (q >> 1)) * (2 * S) + 2 * j + (q & 1u)) * Q + q4;
         const float4 d = d_us[src], u = us[src];
         float4 v;
-        v.x = d.x * (u.x > 0.f ? 1.f : 0.2f);
-        v.y = d.y * (u.y > 0.f ? 1.f : 0.2f);
-        v.z = d.z * (u.z > 0.f ? 1.f : 0.2f);
-        v.w = d.w * (u.w > 0.f ? 1.f : 0.2f);
+        v.x = d.x * (u.x > 0.f ? 1.f : slope);
+        v.y = d.y * (u.y > 0.f ? 1.f : slope);
+        v.z = d.z * (u.z > 0.f ? 1.f : slope);
+        v.w = d.w * (u.w > 0.f ? 1.f : slope);
         gS[e] = v;
         mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
     }
     if (gmax) block_absmax_to(gmax, mx);
 }
 
-hipError_t launch_leaky_bwd_s2d_max(const float* d_us, const float* us, int B, int S, int C, float* gS, unsigned* gmax,
+hipError_t launch_leaky_bwd_s2d_max(const float* d_us, const float* us, int B, int S, int C, float slope, float* gS, unsigned* gmax,
                                     hipStream_t stream) {
     const size_t n = (size_t)B * S * S * 4 * C;
     if (C % 4 == 0 && n < 0xffffffffull) {
         const unsigned n4 = (unsigned)(n / 4);
         const unsigned blocks = std::min(2048u, (n4 + 255u) / 256u);
         hipLaunchKernelGGL(leaky_bwd_s2d_v4_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, stream, reinterpret_cast<const float4*>(d_us),
-                           reinterpret_cast<const float4*>(us), (unsigned)S, (unsigned)(C / 4), reinterpret_cast<float4*>(gS), n4, gmax);
+                           reinterpret_cast<const float4*>(us), (unsigned)S, (unsigned)(C / 4), reinterpret_cast<float4*>(gS), n4, slope, gmax);
         return hipGetLastError();
     }
     const unsigned blocks = (unsigned)std::min<size_t>(1024, (n + 255) / 256);
-    hipLaunchKernelGGL(leaky_bwd_s2d_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, stream, d_us, us, S, C, gS, n, gmax);
+    hipLaunchKernelGGL(leaky_bwd_s2d_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, stream, d_us, us, S, C, gS, n, slope, gmax);
+    return hipGetLastError();
+}
+
+// ReLU backward of the legacy graph (reference UnMicst.py:92,101,114,157,163): g = dy where v > 0, else 0 (v: the value in
+// front of the ReLU, or behind it -- the same decision); in place allowed; tracks max |g| for the planes and weight gradients
+__global__ void __launch_bounds__(256) relu_bwd_kernel(const float* dy, const float* __restrict__ v, float* g,
+                                                       size_t n, unsigned* gmax) {
+    float mx = 0.f;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
+        const float r = v[e] > 0.f ? dy[e] : 0.f;
+        g[e] = r;
+        mx = fmaxf(mx, fabsf(r));
+    }
+    if (gmax) block_absmax_to(gmax, mx);
+}
+
+hipError_t launch_relu_bwd_max(const float* dy, const float* v, float* g, size_t n, unsigned* gmax, hipStream_t stream) {
+    const unsigned blocks = (unsigned)std::min<size_t>(2048, (n + 255) / 256);
+    hipLaunchKernelGGL(relu_bwd_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, stream, dy, v, g, n, gmax);
     return hipGetLastError();
 }
 

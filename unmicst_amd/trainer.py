@@ -3,9 +3,10 @@ training regimes.
 
 ``Trainer.step(batchData, batchLabels, batchWeights)`` is one ``sess.run([optOp, loss], feed_dict=...)`` of the
 reference's loop (UnMicst1-5.py:483-484, UnMicst2.py:471-472); ``solo_options`` / ``duo_options`` carry the constants
-those scripts hard-code (optimiser, learning-rate schedule, regularisers, dropout rates, the probability clip).  The
-trained parameters come back in the blob layout ``umx.Engine`` loads (``Trainer.blob()``), so train -> infer needs no
-conversion.  No CPU fallback: without libumx and a gfx950 device every call raises.
+those scripts hard-code (optimiser, learning-rate schedule, regularisers, dropout rates, the probability clip).  The legacy
+graph of the shipped checkpoints trains with ``legacy_options`` (UnMicst.py:270-279: Momentum, unweighted loss -- ``weights``
+may be None -- no dropout, no regulariser).  The trained parameters come back in the blob layout ``umx.Engine`` loads
+(``Trainer.blob()``), so train -> infer needs no conversion.  No CPU fallback: without libumx and a gfx950 device every call raises.
 """
 from __future__ import annotations
 
@@ -16,7 +17,7 @@ from typing import Optional
 import numpy as np
 
 from . import umx as _umx
-from .model import GRAPH_V2, HParams
+from .model import GRAPH_LEGACY, GRAPH_V2, HParams
 
 OPT_ADAM, OPT_MOMENTUM = 0, 1
 REG_NONE, REG_L1, REG_L2 = 0, 1, 2
@@ -24,7 +25,7 @@ TV_PARAMS, TV_GRADS, TV_SLOT_M, TV_SLOT_V = 0, 1, 2, 3
 
 # every symbol include/umx_train.h declares (checked by tests/test_abi.py)
 EXPORTS = [
-    "umx_train_options_solo", "umx_train_options_duo", "umx_trainer_create", "umx_trainer_destroy",
+    "umx_train_options_solo", "umx_train_options_duo", "umx_train_options_legacy", "umx_trainer_create", "umx_trainer_destroy",
     "umx_trainer_last_error", "umx_train_step", "umx_train_step_dev", "umx_trainer_loss", "umx_trainer_read",
     "umx_trainer_probs", "umx_trainer_read_tensor", "umx_trainer_eval", "umx_trainer_step_count", "umx_trainer_batch", "umx_trainer_flops_per_image",
     "umx_trainer_profile",
@@ -80,6 +81,22 @@ def duo_options(**kw) -> TrainOptions:
     return TrainOptions(**base)
 
 
+def legacy_options(**kw) -> TrainOptions:
+    """UnMicst.py:270-279 (train() of the legacy graph): MomentumOptimizer(0.01 * 0.95^floor(step/1000), 0.9), the
+    unweighted, unclipped cross-entropy, no regulariser, no dropout."""
+    base = dict(optimizer=OPT_MOMENTUM, lr0=0.01, decay_steps=1000, decay_rate=0.95, momentum=0.9, reg_kind=REG_NONE,
+                reg_down=0.0, reg_bottom=0.0, reg_up=0.0, reg_top=0.0, clip_eps=0.0, drop_bottom=0.0)
+    base.update(kw)
+    return TrainOptions(**base)
+
+
+def _legacy_refusal(opts: TrainOptions) -> Optional[str]:
+    if opts.reg_kind != REG_NONE or any(getattr(opts, k) != 0.0 for k in ("drop_down_step", "drop_bottom", "drop_up0", "drop_up_step")):
+        return ("the legacy graph has no dropout and no regulariser: train it with legacy_options() "
+                "(reference UnMicst.py:270-279)")
+    return None
+
+
 def _bind(L):
     if getattr(L, "_umx_train_bound", False):
         return L
@@ -89,6 +106,8 @@ def _bind(L):
     L.umx_train_options_solo.argtypes = [ctypes.POINTER(_TrainOptions)]
     L.umx_train_options_duo.restype = None
     L.umx_train_options_duo.argtypes = [ctypes.POINTER(_TrainOptions)]
+    L.umx_train_options_legacy.restype = None
+    L.umx_train_options_legacy.argtypes = [ctypes.POINTER(_TrainOptions)]
     L.umx_trainer_create.restype = c_int
     L.umx_trainer_create.argtypes = [ctypes.POINTER(_umx._HP), c_void_p, ctypes.c_size_t, ctypes.POINTER(_TrainOptions),
                                      ctypes.POINTER(c_void_p)]
@@ -123,21 +142,28 @@ def _bind(L):
 
 
 def native_options(kind: str) -> TrainOptions:
-    """The presets as libumx fills them (umx_train_options_solo/_duo) -- tests compare them with the dataclasses."""
+    """The presets as libumx fills them (umx_train_options_solo/_duo/_legacy) -- tests compare them with the dataclasses."""
     L = _bind(_umx.load())
     o = _TrainOptions()
-    (L.umx_train_options_solo if kind == "solo" else L.umx_train_options_duo)(ctypes.byref(o))
+    fill = {"solo": L.umx_train_options_solo, "legacy": L.umx_train_options_legacy}.get(kind, L.umx_train_options_duo)
+    fill(ctypes.byref(o))
     return TrainOptions(**{f.name: getattr(o, f.name) for f in fields(TrainOptions)})
 
 
 class Trainer:
     def __init__(self, hp: HParams, blob: np.ndarray, opts: Optional[TrainOptions] = None, batch: int = 0,
                  device: int = 0):
-        if hp.graph != GRAPH_V2 or hp.nExtraConvs != 0:
+        self.opts = opts or TrainOptions()
+        if hp.graph == GRAPH_LEGACY:
+            if not 0 <= hp.nExtraConvs <= 2:
+                raise ValueError("the training step covers the legacy graph with nExtraConvs 0..2")
+            why = _legacy_refusal(self.opts)
+            if why:
+                raise ValueError(why)
+        elif hp.graph != GRAPH_V2 or hp.nExtraConvs != 0:
             raise ValueError("the training step covers the v2 graph with nExtraConvs == 0")
         self._lib = _bind(_umx.load())
         self.hp = hp
-        self.opts = opts or TrainOptions()
         o = _TrainOptions()
         for f in fields(TrainOptions):
             setattr(o, f.name, getattr(self.opts, f.name))
@@ -172,24 +198,31 @@ class Trainer:
 
     def _batch_arrays(self, data, labels, weights):
         hp, B = self.hp, self.batch
+        if weights is None and hp.graph != GRAPH_LEGACY:
+            raise ValueError("weights=None (the unweighted loss) is the legacy graph's; the v2 loss needs weights")
         d = np.ascontiguousarray(data, dtype=np.float32)
         y = np.ascontiguousarray(labels, dtype=np.float32)
-        w = np.ascontiguousarray(weights, dtype=np.float32)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32)
         if d.shape != (B, hp.imSize, hp.imSize, hp.nChannels):
             raise ValueError("data must be %r, got %r" % ((B, hp.imSize, hp.imSize, hp.nChannels), d.shape))
-        if y.shape != (B, hp.imSize, hp.imSize, hp.nClasses) or w.shape != y.shape:
+        if y.shape != (B, hp.imSize, hp.imSize, hp.nClasses) or (w is not None and w.shape != y.shape):
             raise ValueError("labels / weights must be %r" % ((B, hp.imSize, hp.imSize, hp.nClasses),))
         return d, y, w
 
-    def step(self, data, labels, weights, apply_update: bool = True):
-        """-> (loss, data term, regularisation loss) of this batch; parameters updated unless apply_update is False."""
+    def step(self, data, labels, weights=None, apply_update: bool = True):
+        """-> (loss, data term, regularisation loss) of this batch; parameters updated unless apply_update is False.
+        weights None (legacy graph only): the unweighted loss of UnMicst.py:276."""
         d, y, w = self._batch_arrays(data, labels, weights)
         out = (ctypes.c_double * 3)()
-        self._check(self._lib.umx_train_step(self._h, d.ctypes.data, y.ctypes.data, w.ctypes.data, int(apply_update), out))
+        self._check(self._lib.umx_train_step(self._h, d.ctypes.data, y.ctypes.data, None if w is None else w.ctypes.data,
+                                             int(apply_update), out))
         return float(out[0]), float(out[1]), float(out[2])
 
-    def step_dev(self, data_ptr: int, labels_ptr: int, weights_ptr: int, apply_update: bool = True):
-        """Device pointers (e.g. torch tensors' data_ptr()); only enqueues -- call loss() to synchronise."""
+    def step_dev(self, data_ptr: int, labels_ptr: int, weights_ptr: Optional[int], apply_update: bool = True):
+        """Device pointers (e.g. torch tensors' data_ptr()); only enqueues -- call loss() to synchronise.  weights_ptr None or 0:
+        the unweighted loss (legacy graph only)."""
+        if not weights_ptr and self.hp.graph != GRAPH_LEGACY:
+            raise ValueError("weights_ptr is required for the v2 graph")
         self._check(self._lib.umx_train_step_dev(self._h, ctypes.c_void_p(data_ptr), ctypes.c_void_p(labels_ptr),
                                                  ctypes.c_void_p(weights_ptr), int(apply_update)))
 
