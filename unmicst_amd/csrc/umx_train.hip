@@ -148,7 +148,6 @@ struct umx_trainer {
     std::vector<RepackDesc> rdescs;
     RepackDesc* d_rdescs = nullptr;
     int max_refs = 0;
-    bool cur_bwd = false;               // (during build) the convolution being set up belongs to the backward pass
     int n_fwd_packs = 0, n_fwd_rdescs = 0;   // descriptors [0, n_fwd) serve the forward pass, the rest the backward pass only
     hipEvent_t ev_begin = nullptr, ev_packed = nullptr;
     std::vector<H16> h_ds, h_us, h_cv;  // planes of ds[i], us[idx], cv[idx]
@@ -226,6 +225,13 @@ int tzero(umx_trainer* tr, T** out, size_t count) {
     return UMX_OK;
 }
 
+template <typename T>
+int tupload(umx_trainer* tr, T** out, const T* host, size_t count) {
+    T_TRY(talloc(tr, out, count));
+    if (count) T_HIP(tr, hipMemcpy(*out, host, count * sizeof(T), hipMemcpyHostToDevice));
+    return UMX_OK;
+}
+
 // N-tiles per workgroup.  A training batch is small (8 images): the deep layers have a handful of 256-pixel M-tiles, so
 // wide N blocks would leave most of the 256 CUs idle.  Cost model: rounds of 512 resident workgroups (2 per CU) times
 // the work of one workgroup (NT MFMAs per fragment pair + a fixed staging share); padded N counts as work.
@@ -275,9 +281,9 @@ int wscale_shift(double wmax) {
 
 // The same convolution as a split-precision plan (conv_f16x3, fp32 output): stage tables and the LDS-image layout of the weights
 // come from plan_f16 once; the values are filled every step by repack_f16x3_kernel from the fp32 operands this TConv already
-// rebuilds on the device.  A shape the planner refuses stays on the fp32 kernel.
+// rebuilds on the device.  A shape the planner refuses stays on the fp32 kernel.  bwd: see setup_conv.
 int setup_hconv(umx_trainer* tr, TConv& tc, const char* what, int H, int W, int Cout, int act, int nphase, int o_mul, const int* oy,
-                const int* ox, int ngroups, GroupSpec* gs) {
+                const int* ox, int ngroups, GroupSpec* gs, bool bwd) {
     if (!tr->hconv) return UMX_OK;
     umx::Launch L;
     L.name = what;
@@ -317,8 +323,7 @@ int setup_hconv(umx_trainer* tr, TConv& tc, const char* what, int H, int W, int 
     const int sh = wscale_shift(wmax);
     tc.wsh = sh;
     const float inv = std::ldexp(1.f, -sh);
-    T_TRY(talloc(tr, &tc.winv, 1));
-    T_HIP(tr, hipMemcpy(tc.winv, &inv, sizeof inv, hipMemcpyHostToDevice));
+    T_TRY(tupload(tr, &tc.winv, &inv, 1));
     static_assert(sizeof(umx::HWRef) == sizeof(HWRefDev) && sizeof(HWRefDev) == 12, "reference record layout");
     // The planner's references address the packed fp32 operand [tap][Cp][Np]; rewritten here into the master tensor's own
     // coordinates (the index arithmetic of pack_weights_kernel, done once on the host), the per-step repack reads the parameters
@@ -368,7 +373,7 @@ int setup_hconv(umx_trainer* tr, TConv& tc, const char* what, int H, int W, int 
         rd.stride = tc.cp.Np;
         rd.scale = std::ldexp(1.f, sh);
         rd.slab = const_cast<uint4*>(L.hcp.ph[ph].w);
-        rd.bwd = tr->cur_bwd ? 1 : 0;
+        rd.bwd = bwd ? 1 : 0;
         rd.owner = (int)tr->hconvs.size();
         tr->rdescs.push_back(rd);
         tr->max_refs = std::max(tr->max_refs, rd.n);
@@ -404,7 +409,7 @@ int setup_hconv(umx_trainer* tr, TConv& tc, const char* what, int H, int W, int 
             for (int ph = 0; ph < nphase; ++ph)
                 for (int si = 0; si < h.ph[ph].nstages; ++si) nk += L.stages_host[h.ph[ph].stage0 + si].nk;
             fprintf(stderr, "[umx train] %s%s: %d x %d -> %d ch, %d phase(s), NT %d x %d blocks, %d k-steps, %ld workgroups, K split %d\n",
-                    what, tr->cur_bwd ? " (backward)" : "", H, W, Cout, nphase, h.NT, h.nblocks, nk, wgs, S);
+                    what, bwd ? " (backward)" : "", H, W, Cout, nphase, h.NT, h.nblocks, nk, wgs, S);
         }
     }
     std::vector<HStage>().swap(L.stages_host);
@@ -414,8 +419,9 @@ int setup_hconv(umx_trainer* tr, TConv& tc, const char* what, int H, int W, int 
     return UMX_OK;
 }
 
+// bwd: the convolution belongs to the backward pass only (its operands are packed on the side stream while the forward pass runs)
 int setup_conv(umx_trainer* tr, TConv& tc, const char* what, int H, int W, int Cout, int act, int nphase, int o_mul,
-               const int* oy, const int* ox, int ngroups, GroupSpec* gs) {
+               const int* oy, const int* ox, int ngroups, GroupSpec* gs, bool bwd) {
     ConvParams& p = tc.cp;
     memset(&p, 0, sizeof p);
     {
@@ -509,19 +515,21 @@ int setup_conv(umx_trainer* tr, TConv& tc, const char* what, int H, int W, int C
             d.transpose = gs[g].transpose; d.c_off = gs[g].c_off;
             d.npar = gs[g].npar; d.Cblk = gs[g].Cblk;
             for (size_t i = 0; i < ts.m.size(); ++i) d.mtap[i] = (short)ts.m[i];
-            d.bwd = tr->cur_bwd ? 1 : 0;
+            d.bwd = bwd ? 1 : 0;
             tr->packs.push_back(d);
             ++npacks;
             tr->max_pack = std::max(tr->max_pack, elems);
             tc.mac += (double)H * W * nt * gs[g].C * Cout;
         }
     const size_t packs_before = tr->packs.size() - npacks;
-    T_TRY(setup_hconv(tr, tc, what, H, W, Cout, act, nphase, o_mul, oy, ox, ngroups, gs));
+    T_TRY(setup_hconv(tr, tc, what, H, W, Cout, act, nphase, o_mul, oy, ox, ngroups, gs, bwd));
     if (tc.hidx >= 0 && tc.direct) tr->packs.resize(packs_before);   // nothing reads this convolution's fp32 operands
     return UMX_OK;
 }
 
+// (nothing on the exact-fp32 route: its planes stay empty)
 int alloc_h16(umx_trainer* tr, H16& h, size_t npix, int C) {
+    if (!tr->hconv) return UMX_OK;
     h.Cs = round_up(std::max(C, 1), 8);
     T_TRY(tzero(tr, &h.hi, npix * h.Cs));
     T_TRY(tzero(tr, &h.lo, npix * h.Cs));
@@ -567,22 +575,34 @@ int run_hconv(umx_trainer* tr, TConv& tc, const H16& s0, const H16* s1, float* d
 int pack_all(umx_trainer* tr, hipStream_t st, int part);
 int refresh_wscales(umx_trainer* tr);
 
-int run_conv(umx_trainer* tr, TConv& tc, const float* src0, const float* src1, float* dst, bool on_side = false) {
+int run_conv(umx_trainer* tr, TConv& tc, const float* src0, const float* src1, float* dst) {
     ConvParams p = tc.cp;
     p.src[0] = src0;
     p.src[1] = src1;
     p.dst = dst;
     p.B = tr->B;
-    hipStream_t st = on_side ? tr->side : tr->stream;
-    float* split = on_side ? tr->d_split2 : tr->d_split;     // each stream has its own K-split scratch
-    if (p.ksplit > 1) {
-        p.dst = split;
+    if (p.ksplit > 1) {   // raw partial sums, then the ordered reduce applies the activation
+        p.dst = tr->d_split;
         p.act = ACT_NONE;
-        T_HIP(tr, launch_conv(p, tc.nt, tc.hpix, st));
-        T_HIP(tr, launch_split_reduce(split, p.ksplit, p.split_stride, p.split_stride, tc.cp.act, dst, st));
-        return UMX_OK;
     }
-    T_HIP(tr, launch_conv(p, tc.nt, tc.hpix, st));
+    T_HIP(tr, launch_conv(p, tc.nt, tc.hpix, tr->stream));
+    if (p.ksplit > 1) T_HIP(tr, launch_split_reduce(tr->d_split, p.ksplit, p.split_stride, p.split_stride, tc.cp.act, dst, tr->stream));
+    return UMX_OK;
+}
+
+// a convolution on the main stream, on whichever route its plan took: conv_f16x3 reads the (hi, lo) planes h (+ h1; xinv: their
+// inverse scale where they hold a gradient), conv_mfma_f32 the fp32 tensors x (+ x1)
+int run_tconv(umx_trainer* tr, TConv& tc, const float* x, const H16& h, const float* xinv, float* dst, const float* x1 = nullptr,
+              const H16* h1 = nullptr) {
+    if (tc.hidx >= 0) return run_hconv(tr, tc, h, h1, dst, xinv, tr->stream);
+    return run_conv(tr, tc, x, x1, dst);
+}
+
+// an activation written by a kernel without a plane writer (the input batch, the transposed convolutions' outputs): its max |x|
+// for the split-precision weight gradient (training) and, on the split-precision route, its planes -- there in the same pass
+int track_act(umx_trainer* tr, const float* x, size_t npix, int C, const H16& h, unsigned* xmax, bool training) {
+    if (training && !tr->hconv) T_HIP(tr, launch_absmax(x, npix * C, xmax, tr->stream));
+    if (tr->hconv) T_TRY(to_h16(tr, x, npix, C, h, nullptr, nullptr, tr->stream, training ? xmax : nullptr));
     return UMX_OK;
 }
 
@@ -719,61 +739,92 @@ int forward_pass(umx_trainer* tr, const float* data, bool training, bool update)
     const int L = tr->L;
     hipStream_t st = tr->stream;
     const umx_train_options& o = tr->o;
-    auto rate = [&](float r) { return training ? r : 0.f; };
+    int* const flagp = reinterpret_cast<int*>(tr->d_maxw + tr->n_maxw);
     // (training: every activation that the backward pass feeds to the split-precision weight gradient gets its max |v|
     // tracked by the kernel that writes it -- the input batch and the transposed-conv outputs by a pass of their own)
-    // a convolution on whichever route its plan took: conv_f16x3 reads the (hi, lo) planes, conv_mfma_f32 the fp32 tensors
-    auto conv = [&](TConv& tc, const float* x0, const float* x1, const H16* h0, const H16* h1, float* dst) -> int {
-        if (tc.hidx >= 0) return run_hconv(tr, tc, *h0, h1, dst, nullptr, st);
-        return run_conv(tr, tc, x0, x1, dst);
+    // BN + LeakyReLU (+ 2x2 max-pool) + dropout of site s into out, which gets its (hi, lo) planes h written by the same kernel
+    // (the exact-fp32 route has no plane buffers: h is empty then)
+    auto act = [&](BnSite& s, int pool, float rate, int layer_id, float* out, unsigned* omax, const H16& h) -> int {
+        T_HIP(tr, launch_act_fwd(act_params(tr, s, pool, ACT_LEAKY, training ? rate : 0.f, layer_id), out, training ? omax : nullptr,
+                                 h.hi, h.lo, h.Cs, flagp, st));
+        return UMX_OK;
     };
-    const size_t Bz = (size_t)tr->B;
-    int* const flagp = reinterpret_cast<int*>(tr->d_maxw + tr->n_maxw);
-    // (the (hi, lo) planes of an activation are written by the kernel that produces it)
-    static const H16 kNoPlanes;   // (the exact-fp32 route has no plane buffers: the vectors below are empty then)
-#define PL(h) (tr->hconv ? (h) : kNoPlanes).hi, (tr->hconv ? (h) : kNoPlanes).lo, (tr->hconv ? (h) : kNoPlanes).Cs, flagp
     tr->ds[0] = const_cast<float*>(data);
-    if (training && !tr->hconv) T_HIP(tr, launch_absmax(data, Bz * tr->P * tr->P * tr->n[0], tr->dsmax[0], st));
-    if (tr->hconv) T_TRY(to_h16(tr, data, Bz * tr->P * tr->P, tr->n[0], tr->h_ds[0], nullptr, nullptr, st, training ? tr->dsmax[0] : nullptr));
+    T_TRY(track_act(tr, data, (size_t)tr->B * tr->P * tr->P, tr->n[0], tr->h_ds[0], tr->dsmax[0], training));
     int S = tr->P;
     for (int i = 0; i < L; ++i) {
         BnSite& s = tr->bn_d[i];
-        T_TRY(conv(tr->c_fwd_d[i], tr->ds[i], nullptr, tr->hconv ? &tr->h_ds[i] : nullptr, nullptr, s.z));
+        T_TRY(run_tconv(tr, tr->c_fwd_d[i], tr->ds[i], tr->h_ds[i], nullptr, s.z));
         T_TRY(bn_forward_stats(tr, s, update, training));
-        T_HIP(tr, launch_act_fwd(act_params(tr, s, 1, ACT_LEAKY, rate(down_rate(tr, i)), LAYER_DOWN + i), tr->ds[i + 1],
-                                 training ? tr->dsmax[i + 1] : nullptr, PL(tr->h_ds[i + 1]), st));
+        T_TRY(act(s, 1, down_rate(tr, i), LAYER_DOWN + i, tr->ds[i + 1], tr->dsmax[i + 1], tr->h_ds[i + 1]));
         S /= 2;
     }
-    T_TRY(conv(tr->c_fwd_b, tr->ds[L], nullptr, tr->hconv ? &tr->h_ds[L] : nullptr, nullptr, tr->bn_b.z));
+    T_TRY(run_tconv(tr, tr->c_fwd_b, tr->ds[L], tr->h_ds[L], nullptr, tr->bn_b.z));
     T_TRY(bn_forward_stats(tr, tr->bn_b, update, training));
-    T_HIP(tr, launch_act_fwd(act_params(tr, tr->bn_b, 0, ACT_LEAKY, rate(o.drop_bottom), LAYER_BOTTOM), tr->act_b,
-                             training ? tr->bmax : nullptr, PL(tr->h_b), st));
+    T_TRY(act(tr->bn_b, 0, o.drop_bottom, LAYER_BOTTOM, tr->act_b, tr->bmax, tr->h_b));
     const float* cur = tr->act_b;
-    const H16* hcur = tr->hconv ? &tr->h_b : nullptr;
+    const H16* hcur = &tr->h_b;
     for (int idx = L - 1; idx >= 0; --idx) {
         BnSite& s = tr->bn_u[idx];
         S *= 2;
-        T_TRY(conv(tr->c_T[idx], cur, nullptr, hcur, nullptr, tr->us[idx]));
-        // (max |us| for the split-precision weight gradient: tracked by the plane split where there is one)
-        if (training && !tr->hconv) T_HIP(tr, launch_absmax(tr->us[idx], Bz * S * S * tr->n[idx + 1], tr->usmax[idx], st));
-        if (tr->hconv) T_TRY(to_h16(tr, tr->us[idx], Bz * S * S, tr->n[idx + 1], tr->h_us[idx], nullptr, nullptr, st,
-                                    training ? tr->usmax[idx] : nullptr));
-        T_TRY(conv(tr->c_fwd_u[idx], tr->ds[idx], tr->us[idx], tr->hconv ? &tr->h_ds[idx] : nullptr, tr->hconv ? &tr->h_us[idx] : nullptr, s.z));
+        T_TRY(run_tconv(tr, tr->c_T[idx], cur, *hcur, nullptr, tr->us[idx]));
+        T_TRY(track_act(tr, tr->us[idx], (size_t)tr->B * S * S, tr->n[idx + 1], tr->h_us[idx], tr->usmax[idx], training));
+        T_TRY(run_tconv(tr, tr->c_fwd_u[idx], tr->ds[idx], tr->h_ds[idx], nullptr, s.z, tr->us[idx], &tr->h_us[idx]));
         T_TRY(bn_forward_stats(tr, s, update, training));
-        if (tr->hconv && idx >= 1) {
-            T_HIP(tr, launch_act_fwd(act_params(tr, s, 0, ACT_LEAKY, rate(up_rate(tr, idx)), LAYER_UP + idx), tr->cv[idx],
-                                     training ? tr->cvmax[idx] : nullptr, PL(tr->h_cv[idx]), st));
-        } else {
-            T_HIP(tr, launch_act_fwd(act_params(tr, s, 0, ACT_LEAKY, rate(up_rate(tr, idx)), LAYER_UP + idx), tr->cv[idx],
-                                     training ? tr->cvmax[idx] : nullptr, nullptr, nullptr, 0, flagp, st));
-        }
+        // (cv[0] has no planes: only the 1x1 head reads it)
+        T_TRY(act(s, 0, up_rate(tr, idx), LAYER_UP + idx, tr->cv[idx], tr->cvmax[idx], tr->h_cv[idx]));
         cur = tr->cv[idx];
-        hcur = tr->hconv && idx >= 1 ? &tr->h_cv[idx] : nullptr;
+        hcur = &tr->h_cv[idx];
     }
-#undef PL
     BnSite& t = tr->bn_t;
     T_HIP(tr, launch_head_fwd(tr->cv[0], (size_t)tr->B * tr->P * tr->P, tr->n[1], tr->K, tr->d_w + tr->o_lt, t.z, st));
     T_TRY(bn_forward_stats(tr, t, update, training));
+    return UMX_OK;
+}
+
+// start of a step (both graphs): the weight scales' periodic refresh, the profile's first event, loss and max words zeroed
+int step_begin(umx_trainer* tr, bool update) {
+    hipStream_t st = tr->stream;
+    if (update && tr->step > 0 && tr->wscale_every > 0 && tr->step % tr->wscale_every == 0) T_TRY(refresh_wscales(tr));
+    if (tr->prof) T_HIP(tr, hipEventRecord(tr->ev[0], st));
+    T_HIP(tr, hipMemsetAsync(tr->d_loss, 0, 2 * sizeof(double), st));
+    // (the range flag behind the max words is NOT cleared here: it stays up until umx_trainer_loss / umx_trainer_eval has
+    // reported it, so an overflow in a step whose loss is never read is not lost under the next step -- ADVICE r4)
+    T_HIP(tr, hipMemsetAsync(tr->d_maxw, 0, tr->n_maxw * sizeof(unsigned), st));
+    return UMX_OK;
+}
+
+// softmax + weighted cross-entropy of the logits (normalised by stat) -> probs, d loss / d logits (d_dt) and the data term
+int loss_head(umx_trainer* tr, const float* logits, const float* stat, const float* labels, const float* weights) {
+    const size_t Npix = (size_t)tr->B * tr->P * tr->P;
+    const int nblk = loss_blocks(Npix);
+    T_HIP(tr, launch_softmax_loss(logits, stat, labels, weights, Npix, tr->K, tr->o.clip_eps, tr->d_probs, tr->d_dt, tr->d_part, nblk,
+                                  tr->stream));
+    T_HIP(tr, launch_sum_to_scalar(tr->d_part, nblk, 1.0 / (double)Npix, tr->d_loss, 0, 0, tr->stream));
+    return UMX_OK;
+}
+
+// end of a step (both graphs, every gradient in place on the main stream): the optimiser over the flat vector (UnMicst1-5.py:361-380,
+// UnMicst.py:270-279; BN moving statistics were updated in the forward pass) and the profile's last events
+int step_end(umx_trainer* tr, bool update) {
+    hipStream_t st = tr->stream;
+    const umx_train_options& o = tr->o;
+    if (tr->prof) T_HIP(tr, hipEventRecord(tr->ev[2], st));
+    if (update) {
+        OptParams op;
+        op.kind = o.optimizer;
+        const double lr = (double)o.lr0 * std::pow((double)o.decay_rate, (double)(tr->step / std::max(1, o.decay_steps)));
+        const double tt = (double)(tr->step + 1);
+        op.lr = (float)lr;
+        op.lr_t = (float)(lr * std::sqrt(1.0 - std::pow((double)o.beta2, tt)) / (1.0 - std::pow((double)o.beta1, tt)));
+        op.beta1 = o.beta1; op.beta2 = o.beta2; op.eps = o.adam_eps; op.momentum = o.momentum;
+        T_HIP(tr, launch_optimizer(op, tr->d_w, tr->d_g, tr->d_m, tr->d_v, tr->nparams, st));
+        tr->step += 1;
+    }
+    if (tr->prof) {
+        T_HIP(tr, hipEventRecord(tr->ev[3], st));
+        tr->pending = true;
+    }
     return UMX_OK;
 }
 
@@ -782,12 +833,7 @@ int enqueue_step(umx_trainer* tr, const float* data, const float* labels, const 
     hipStream_t st = tr->stream;
     const umx_train_options& o = tr->o;
     const size_t Npix = (size_t)B * P * P;
-    if (update && tr->step > 0 && tr->wscale_every > 0 && tr->step % tr->wscale_every == 0) T_TRY(refresh_wscales(tr));
-    if (tr->prof) T_HIP(tr, hipEventRecord(tr->ev[0], st));
-    T_HIP(tr, hipMemsetAsync(tr->d_loss, 0, 2 * sizeof(double), st));
-    // (the range flag behind the max words is NOT cleared here: it stays up until umx_trainer_loss / umx_trainer_eval has
-    // reported it, so an overflow in a step whose loss is never read is not lost under the next step -- ADVICE r4)
-    T_HIP(tr, hipMemsetAsync(tr->d_maxw, 0, tr->n_maxw * sizeof(unsigned), st));
+    T_TRY(step_begin(tr, update));
     if (tr->overlap) {
         // the side stream is idle until the first weight gradient: it packs the backward pass's operands and sums the regularisation
         // loss (both need nothing but this step's weights) while the main stream runs the forward pass
@@ -804,12 +850,7 @@ int enqueue_step(umx_trainer* tr, const float* data, const float* labels, const 
 
     T_TRY(forward_pass(tr, data, true, update));
     BnSite& t = tr->bn_t;
-    {
-        const int nblk = loss_blocks(Npix);
-        T_HIP(tr, launch_softmax_loss(t.z, t.stat, labels, weights, Npix, K, o.clip_eps, tr->d_probs, tr->d_dt, tr->d_part,
-                                      nblk, st));
-        T_HIP(tr, launch_sum_to_scalar(tr->d_part, nblk, 1.0 / (double)Npix, tr->d_loss, 0, 0, st));
-    }
+    T_TRY(loss_head(tr, t.z, t.stat, labels, weights));
     if (o.reg_kind != UMX_REG_NONE && !tr->overlap)
         T_HIP(tr, launch_reg_loss(tr->d_regsegs, tr->n_regsegs, o.reg_kind, tr->d_part, tr->d_loss, 1, st));
     if (tr->overlap) T_HIP(tr, hipStreamWaitEvent(st, tr->ev_packed, 0));   // the backward pass's operands are in place
@@ -851,10 +892,6 @@ int enqueue_step(umx_trainer* tr, const float* data, const float* labels, const 
         used[sl] = true;
         return UMX_OK;
     };
-    auto dgrad = [&](TConv& tc, const float* x, const H16& h, const float* xinv, float* dst) -> int {
-        if (tc.hidx >= 0) return run_hconv(tr, tc, h, nullptr, dst, xinv, st);
-        return run_conv(tr, tc, x, nullptr, dst);
-    };
     int S = P;
     for (int idx = 0; idx < L; ++idx) {    // up layers, output side first
         BnSite& s = tr->bn_u[idx];
@@ -872,7 +909,7 @@ int enqueue_step(umx_trainer* tr, const float* data, const float* labels, const 
                         tr->hconv ? &tr->h_ds[idx] : nullptr, nullptr, pdz, tr->d_xinv + slot));
         T_TRY(run_wgrad(tr, tr->wg_u1[idx], tr->us[idx], dz, Cskip + Cup, Cskip, tr->o_w2[idx], o.reg_up, SIZE_MAX, tr->usmax[idx], s.gmax, ws,
                         tr->hconv ? &tr->h_us[idx] : nullptr, nullptr, pdz, tr->d_xinv + slot));
-        T_TRY(dgrad(tr->c_dg_us[idx], dz, tr->h_dz[slot], tr->d_xinv + slot, tr->DB));
+        T_TRY(run_tconv(tr, tr->c_dg_us[idx], dz, tr->h_dz[slot], tr->d_xinv + slot, tr->DB));
         if (idx >= 1 && use_aux && tr->c_dg_skip[idx].hidx >= 0) {   // (on the weight gradients' stream it was 2 % slower; this stream is its own)
             T_HIP(tr, hipStreamWaitEvent(tr->aux, tr->ev_dz[slot], 0));
             T_TRY(run_hconv(tr, tr->c_dg_skip[idx], tr->h_dz[slot], nullptr, tr->dskip[idx], tr->d_xinv + slot, tr->aux));
@@ -880,7 +917,7 @@ int enqueue_step(umx_trainer* tr, const float* data, const float* labels, const 
             T_HIP(tr, hipEventRecord(tr->ev_skip[idx], tr->aux));
             aux_used[slot] = true;
         } else if (idx >= 1) {
-            T_TRY(dgrad(tr->c_dg_skip[idx], dz, tr->h_dz[slot], tr->d_xinv + slot, tr->dskip[idx]));
+            T_TRY(run_tconv(tr, tr->c_dg_skip[idx], dz, tr->h_dz[slot], tr->d_xinv + slot, tr->dskip[idx]));
         }
         T_HIP(tr, launch_leaky_bwd_s2d_max(tr->DB, tr->us[idx], B, S / 2, Cup, 0.2f, gs, tr->smax[idx], st));
         const bool gs_planes = tr->hconv && (tr->c_dg_T[idx].hidx >= 0 || tr->wg_planes);
@@ -899,7 +936,7 @@ int enqueue_step(umx_trainer* tr, const float* data, const float* labels, const 
                             nullptr));
         }
         T_TRY(side_done(slot));
-        T_TRY(dgrad(tr->c_dg_T[idx], gs, tr->h_gs[slot], tr->d_xinv + kSlots + slot, tr->DA));
+        T_TRY(run_tconv(tr, tr->c_dg_T[idx], gs, tr->h_gs[slot], tr->d_xinv + kSlots + slot, tr->DA));
         slot = (slot + 1) % tr->nslots;
         S /= 2;
     }
@@ -913,7 +950,7 @@ int enqueue_step(umx_trainer* tr, const float* data, const float* labels, const 
         T_TRY(run_wgrad(tr, tr->wg_b, tr->ds[L], dz, tr->n[L], 0, tr->o_lb, o.reg_bottom, SIZE_MAX, tr->dsmax[L], tr->bn_b.gmax, ws,
                         tr->hconv ? &tr->h_ds[L] : nullptr, nullptr, tr->hconv ? &tr->h_dz[slot] : nullptr, tr->d_xinv + slot));
         T_TRY(side_done(slot));
-        T_TRY(dgrad(tr->c_dg_b, dz, tr->h_dz[slot], tr->d_xinv + slot, tr->DB));
+        T_TRY(run_tconv(tr, tr->c_dg_b, dz, tr->h_dz[slot], tr->d_xinv + slot, tr->DB));
         slot = (slot + 1) % tr->nslots;
     }
     for (int i = L - 1; i >= 0; --i) {     // down layers
@@ -932,7 +969,7 @@ int enqueue_step(umx_trainer* tr, const float* data, const float* labels, const 
                         tr->d_xinv + slot));
         T_TRY(side_done(slot));
         S *= 2;
-        if (i >= 1) T_TRY(dgrad(tr->c_dg_d[i], dz, tr->h_dz[slot], tr->d_xinv + slot, tr->DB));
+        if (i >= 1) T_TRY(run_tconv(tr, tr->c_dg_d[i], dz, tr->h_dz[slot], tr->d_xinv + slot, tr->DB));
         slot = (slot + 1) % tr->nslots;
     }
 #undef ws
@@ -944,25 +981,7 @@ int enqueue_step(umx_trainer* tr, const float* data, const float* labels, const 
             T_HIP(tr, hipStreamWaitEvent(st, tr->ev_join2, 0));
         }
     }
-    if (tr->prof) T_HIP(tr, hipEventRecord(tr->ev[2], st));
-
-    // ------------------------------------------------------------------ update (UnMicst1-5.py:361-380)
-    if (update) {
-        OptParams op;
-        op.kind = o.optimizer;
-        const double lr = (double)o.lr0 * std::pow((double)o.decay_rate, (double)(tr->step / std::max(1, o.decay_steps)));
-        const double tt = (double)(tr->step + 1);
-        op.lr = (float)lr;
-        op.lr_t = (float)(lr * std::sqrt(1.0 - std::pow((double)o.beta2, tt)) / (1.0 - std::pow((double)o.beta1, tt)));
-        op.beta1 = o.beta1; op.beta2 = o.beta2; op.eps = o.adam_eps; op.momentum = o.momentum;
-        T_HIP(tr, launch_optimizer(op, tr->d_w, tr->d_g, tr->d_m, tr->d_v, tr->nparams, st));
-        tr->step += 1;
-    }
-    if (tr->prof) {
-        T_HIP(tr, hipEventRecord(tr->ev[3], st));
-        tr->pending = true;
-    }
-    return UMX_OK;
+    return step_end(tr, update);
 }
 
 int fold_profile(umx_trainer* tr) {
@@ -1003,15 +1022,12 @@ int setup_up_layer(umx_trainer* tr, int idx, int& S, int act_T, double& mac_tota
     const std::vector<int>& n = tr->n;
     const int ks = tr->hp.ks;
     const TapSet fwd = same_taps(ks, false), flp = same_taps(ks, true);
-    auto group = one_group;
     char nm[64];
     snprintf(nm, sizeof nm, "lu%d", idx);
     const int pb = (ks - 2) / 2;   // pad_before of the stride-2 SAME conv whose gradient the transposed conv is
     const int Cskip = n[idx], Cup = n[idx + 1], Cin = n[idx + 2];
     {   // transposed conv forward: 4 sub-pixel phases (out[2i+a-pb] += in[i] * Wt[a]); its activation fused
-        GroupSpec g;
-        g.C = Cin; g.w_off = tr->o_wt[idx]; g.w2_off = SIZE_MAX; g.d2 = Cup; g.d3 = Cin; g.transpose = 1; g.c_off = 0;
-        g.npar = 1; g.Cblk = Cin;
+        GroupSpec g = one_group(Cin, tr->o_wt[idx], SIZE_MAX, Cup, Cin, 1, 0, TapSet());
         int oy[4], ox[4];
         for (int p = 0; p < 4; ++p) {
             const int pu = p >> 1, pv = p & 1;
@@ -1025,7 +1041,7 @@ int setup_up_layer(umx_trainer* tr, int idx, int& S, int act_T, double& mac_tota
                 }
             }
         }
-        T_TRY(setup_conv(tr, tr->c_T[idx], nm, S, S, Cup, act_T, 4, 2, oy, ox, 1, &g));
+        T_TRY(setup_conv(tr, tr->c_T[idx], nm, S, S, Cup, act_T, 4, 2, oy, ox, 1, &g, false));
         mac_total += (double)S * S * ks * ks * Cin * Cup;
     }
     {   // transposed conv backward on the space-to-depth gradient gS[.., (pa,pb)*Cup + c] = dY[2i+pa, 2j+pb, c]:
@@ -1040,8 +1056,7 @@ int setup_up_layer(umx_trainer* tr, int idx, int& S, int act_T, double& mac_tota
                 std::pair<int, int> od{di, dj};
                 if (std::find(offs.begin(), offs.end(), od) == offs.end()) offs.push_back(od);
             }
-        GroupSpec g;
-        g.C = 4 * Cup; g.w_off = tr->o_wt[idx]; g.w2_off = SIZE_MAX; g.d2 = Cup; g.d3 = Cin; g.transpose = 0; g.c_off = 0;
+        GroupSpec g = one_group(4 * Cup, tr->o_wt[idx], SIZE_MAX, Cup, Cin, 0, 0, TapSet());
         g.npar = 4; g.Cblk = Cup;
         g.taps[0].off = offs;
         g.taps[0].m.assign(offs.size() * 4, -1);
@@ -1060,22 +1075,22 @@ int setup_up_layer(umx_trainer* tr, int idx, int& S, int act_T, double& mac_tota
                     slabs.m.push_back(a * ks + b);
                     coff.push_back(par * Cup);
                 }
-        tr->cur_bwd = true; T_TRY(setup_conv(tr, tr->c_dg_T[idx], nm, S, S, Cin, ACT_NONE, 1, 1, nullptr, nullptr, 1, &g)); tr->cur_bwd = false;
+        T_TRY(setup_conv(tr, tr->c_dg_T[idx], nm, S, S, Cin, ACT_NONE, 1, 1, nullptr, nullptr, 1, &g, true));
         T_TRY(setup_wgrad(tr, tr->wg_T[idx], nm, S, 4 * Cup, Cup, Cin, slabs, coff));
         mac_total += 2.0 * S * S * ks * ks * Cin * Cup;
     }
     S *= 2;
     {
-        GroupSpec g2[2] = {group(Cskip, tr->o_w2[idx], SIZE_MAX, Cskip + Cup, Cup, 0, 0, fwd),
-                           group(Cup, tr->o_w2[idx], SIZE_MAX, Cskip + Cup, Cup, 0, Cskip, fwd)};
-        T_TRY(setup_conv(tr, tr->c_fwd_u[idx], nm, S, S, Cup, ACT_NONE, 1, 1, nullptr, nullptr, 2, g2));
+        GroupSpec g2[2] = {one_group(Cskip, tr->o_w2[idx], SIZE_MAX, Cskip + Cup, Cup, 0, 0, fwd),
+                           one_group(Cup, tr->o_w2[idx], SIZE_MAX, Cskip + Cup, Cup, 0, Cskip, fwd)};
+        T_TRY(setup_conv(tr, tr->c_fwd_u[idx], nm, S, S, Cup, ACT_NONE, 1, 1, nullptr, nullptr, 2, g2, false));
         mac_total += tr->c_fwd_u[idx].mac;
-        GroupSpec gu = group(Cup, tr->o_w2[idx], SIZE_MAX, Cskip + Cup, Cup, 1, Cskip, flp);
-        tr->cur_bwd = true; T_TRY(setup_conv(tr, tr->c_dg_us[idx], nm, S, S, Cup, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gu)); tr->cur_bwd = false;
+        GroupSpec gu = one_group(Cup, tr->o_w2[idx], SIZE_MAX, Cskip + Cup, Cup, 1, Cskip, flp);
+        T_TRY(setup_conv(tr, tr->c_dg_us[idx], nm, S, S, Cup, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gu, true));
         mac_total += tr->c_dg_us[idx].mac;
         if (idx >= 1) {
-            GroupSpec gk = group(Cup, tr->o_w2[idx], SIZE_MAX, Cskip + Cup, Cup, 1, 0, flp);
-            tr->cur_bwd = true; T_TRY(setup_conv(tr, tr->c_dg_skip[idx], nm, S, S, Cskip, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gk)); tr->cur_bwd = false;
+            GroupSpec gk = one_group(Cup, tr->o_w2[idx], SIZE_MAX, Cskip + Cup, Cup, 1, 0, flp);
+            T_TRY(setup_conv(tr, tr->c_dg_skip[idx], nm, S, S, Cskip, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gk, true));
             mac_total += tr->c_dg_skip[idx].mac;
         }
         T_TRY(setup_wgrad(tr, tr->wg_u0[idx], nm, S, Cskip, Cskip, Cup, fwd, {}));
@@ -1085,12 +1100,89 @@ int setup_up_layer(umx_trainer* tr, int idx, int& S, int act_T, double& mac_tota
     return UMX_OK;
 }
 
-int build_trainer(umx_trainer* tr, const float* blob, size_t blob_floats) {
+// ---- the build frame both graphs share
+
+// L, K, P and the channel widths n[0..L+1] from the hyper-parameters
+void set_shape(umx_trainer* tr) {
     const umx_hparams& hp = tr->hp;
-    const int L = hp.nLayers, ks = hp.ks, P = hp.imSize, K = hp.nClasses, B = tr->B;
-    tr->L = L; tr->K = K; tr->P = P;
+    tr->L = hp.nLayers; tr->K = hp.nClasses; tr->P = hp.imSize;
     tr->n = {hp.nChannels, hp.nOut0};
-    for (int i = 0; i < L; ++i) tr->n.push_back(tr->n.back() * hp.featMapsFact);
+    for (int i = 0; i < tr->L; ++i) tr->n.push_back(tr->n.back() * hp.featMapsFact);
+}
+
+// the parameter vector (nparams floats, laid out by the graph's build) from the blob; its gradient and the optimiser's two slots
+int alloc_params(umx_trainer* tr, const float* blob, size_t blob_floats, size_t nparams) {
+    tr->nparams = nparams;
+    if (blob_floats != nparams)
+        return tfail(tr, UMX_ERR_BLOB, "weight blob has %zu floats, the graph needs %zu", blob_floats, nparams);
+    T_TRY(tupload(tr, &tr->d_w, blob, nparams));
+    T_TRY(tzero(tr, &tr->d_g, nparams));
+    T_TRY(tzero(tr, &tr->d_m, nparams));
+    T_TRY(tzero(tr, &tr->d_v, nparams));
+    return UMX_OK;
+}
+
+// the route of the forward / input-gradient convolutions: split precision (planes of every tensor they read; the graph's build
+// allocates them) unless UMX_TRAIN_CONV_F32 asks for the exact-fp32 kernels
+int select_route(umx_trainer* tr, const float* blob) {
+    tr->hconv = !getenv("UMX_TRAIN_CONV_F32");
+    if (const char* e = getenv("UMX_TRAIN_WSCALE_EVERY")) tr->wscale_every = atoi(e);
+    tr->wg_planes = tr->hconv;
+    tr->h_blob = blob;
+    tr->h_ds.resize(tr->L + 1); tr->h_us.resize(tr->L);   // (no buffers on the exact-fp32 route)
+    if (tr->hconv) {
+        tr->pctx = new umx_ctx();
+        tr->pctx->device = tr->device;
+        tr->pctx->hp = tr->hp;
+    }
+    return UMX_OK;
+}
+
+// the bottom layer (the same in both graphs) at size S: forward conv, input gradient, weight gradient
+int setup_bottom(umx_trainer* tr, int S, double& mac_total) {
+    const std::vector<int>& n = tr->n;
+    const int L = tr->L, ks = tr->hp.ks;
+    const TapSet fwd = same_taps(ks, false), flp = same_taps(ks, true);
+    GroupSpec g = one_group(n[L], tr->o_lb, SIZE_MAX, n[L], n[L + 1], 0, 0, fwd);
+    T_TRY(setup_conv(tr, tr->c_fwd_b, "lb", S, S, n[L + 1], ACT_NONE, 1, 1, nullptr, nullptr, 1, &g, false));
+    GroupSpec gd = one_group(n[L + 1], tr->o_lb, SIZE_MAX, n[L], n[L + 1], 1, 0, flp);
+    T_TRY(setup_conv(tr, tr->c_dg_b, "lb", S, S, n[L], ACT_NONE, 1, 1, nullptr, nullptr, 1, &gd, true));
+    T_TRY(setup_wgrad(tr, tr->wg_b, "lb", S, n[L], n[L], n[L + 1], fwd, {}));
+    mac_total += tr->c_fwd_b.mac + tr->c_dg_b.mac + (double)S * S * ks * ks * n[L] * n[L + 1];
+    return UMX_OK;
+}
+
+// end of build, once every convolution is set up: FLOPs per image (+ the 1x1 head), the weight gradients' slice workspace and the
+// K-split scratch (side_streams: also those of the side streams), the regularised segments, and the pack / repack descriptors
+int finish_build(umx_trainer* tr, double mac_total, bool side_streams) {
+    mac_total += 3.0 * tr->P * tr->P * tr->n[1] * tr->K;
+    tr->flops_per_image = 2.0 * mac_total;
+    T_TRY(talloc(tr, &tr->d_ws, tr->ws_floats));
+    if (side_streams) T_TRY(talloc(tr, &tr->d_ws2, tr->ws_floats));
+    T_TRY(talloc(tr, &tr->d_split, tr->split_floats));
+    if (side_streams) {
+        T_TRY(talloc(tr, &tr->d_split2, tr->split_floats));
+        T_TRY(talloc(tr, &tr->d_split3, tr->split_floats));
+    }
+    std::vector<RegSeg> rs;
+    for (const Seg& sg : tr->segs)
+        if (sg.reg > 0.f) rs.push_back(RegSeg{tr->d_w + sg.off, sg.n, sg.reg});
+    tr->n_regsegs = (int)rs.size();
+    if (!rs.empty()) T_TRY(tupload(tr, &tr->d_regsegs, rs.data(), rs.size()));
+    // forward operands first: the backward-only ones are packed on the side stream while the forward pass runs
+    tr->n_fwd_packs = (int)(std::stable_partition(tr->packs.begin(), tr->packs.end(), [](const PackDesc& d) { return d.bwd == 0; }) -
+                            tr->packs.begin());
+    tr->n_fwd_rdescs = (int)(std::stable_partition(tr->rdescs.begin(), tr->rdescs.end(), [](const RepackDesc& d) { return d.bwd == 0; }) -
+                             tr->rdescs.begin());
+    T_TRY(tupload(tr, &tr->d_packs, tr->packs.data(), tr->packs.size()));
+    if (!tr->rdescs.empty()) T_TRY(tupload(tr, &tr->d_rdescs, tr->rdescs.data(), tr->rdescs.size()));
+    tr->h_blob = nullptr;
+    return UMX_OK;
+}
+
+int build_trainer(umx_trainer* tr, const float* blob, size_t blob_floats) {
+    set_shape(tr);
+    const int L = tr->L, ks = tr->hp.ks, P = tr->P, K = tr->K, B = tr->B;
     const std::vector<int>& n = tr->n;
     const umx_train_options& o = tr->o;
 
@@ -1117,15 +1209,7 @@ int build_trainer(umx_trainer* tr, const float* blob, size_t blob_floats) {
     }
     tr->o_lt = seg("lt.w", (size_t)n[1] * K, o.reg_top);
     bn_t_off = seg("lt.bn", 4 * (size_t)K, 0.f);
-    tr->nparams = pos;
-    if (blob_floats != pos)
-        return tfail(tr, UMX_ERR_BLOB, "weight blob has %zu floats, the graph needs %zu", blob_floats, pos);
-
-    T_TRY(talloc(tr, &tr->d_w, pos));
-    T_HIP(tr, hipMemcpy(tr->d_w, blob, pos * sizeof(float), hipMemcpyHostToDevice));
-    T_TRY(tzero(tr, &tr->d_g, pos));
-    T_TRY(tzero(tr, &tr->d_m, pos));
-    T_TRY(tzero(tr, &tr->d_v, pos));
+    T_TRY(alloc_params(tr, blob, blob_floats, pos));
 
     // ---- activations
     tr->ds.assign(L + 1, nullptr);
@@ -1193,15 +1277,9 @@ int build_trainer(umx_trainer* tr, const float* blob, size_t blob_floats) {
     }
 
     // ---- split-precision route of the forward / input-gradient convolutions: planes of every tensor they read
-    tr->hconv = !getenv("UMX_TRAIN_CONV_F32");
-    if (const char* e = getenv("UMX_TRAIN_WSCALE_EVERY")) tr->wscale_every = atoi(e);
-    tr->wg_planes = tr->hconv;
-    tr->h_blob = blob;
+    T_TRY(select_route(tr, blob));
+    tr->h_cv.resize(L);   // (h_cv[0] stays empty: only the 1x1 head reads cv[0])
     if (tr->hconv) {
-        tr->pctx = new umx_ctx();
-        tr->pctx->device = tr->device;
-        tr->pctx->hp = hp;
-        tr->h_ds.resize(L + 1); tr->h_us.resize(L); tr->h_cv.resize(L);
         int S2 = P;
         size_t max_dz = 0, max_gs = 0;
         for (int i = 0; i <= L; ++i) {
@@ -1230,66 +1308,25 @@ int build_trainer(umx_trainer* tr, const float* blob, size_t blob_floats) {
     tr->c_dg_us.resize(L); tr->c_dg_skip.resize(L); tr->c_dg_T.resize(L);
     tr->wg_d.resize(L); tr->wg_u0.resize(L); tr->wg_u1.resize(L); tr->wg_T.resize(L);
     const TapSet fwd = same_taps(ks, false), flp = same_taps(ks, true);
-    auto group = [&](int C, size_t w_off, size_t w2_off, int d2, int d3, int transpose, int c_off, const TapSet& ts) {
-        GroupSpec g;
-        g.C = C; g.w_off = w_off; g.w2_off = w2_off; g.d2 = d2; g.d3 = d3; g.transpose = transpose; g.c_off = c_off;
-        g.npar = 1; g.Cblk = std::max(C, 1);
-        g.taps[0] = ts;
-        return g;
-    };
     double mac_total = 0.0;
     S = P;
     for (int i = 0; i < L; ++i) {
         snprintf(nm, sizeof nm, "ld%d", i);
-        GroupSpec g = group(n[i], tr->o_w1[i], tr->o_ws[i], n[i], n[i + 1], 0, 0, fwd);
-        T_TRY(setup_conv(tr, tr->c_fwd_d[i], nm, S, S, n[i + 1], ACT_NONE, 1, 1, nullptr, nullptr, 1, &g));
+        GroupSpec g = one_group(n[i], tr->o_w1[i], tr->o_ws[i], n[i], n[i + 1], 0, 0, fwd);
+        T_TRY(setup_conv(tr, tr->c_fwd_d[i], nm, S, S, n[i + 1], ACT_NONE, 1, 1, nullptr, nullptr, 1, &g, false));
         mac_total += tr->c_fwd_d[i].mac;
         if (i >= 1) {
-            GroupSpec gd = group(n[i + 1], tr->o_w1[i], tr->o_ws[i], n[i], n[i + 1], 1, 0, flp);
-            tr->cur_bwd = true; T_TRY(setup_conv(tr, tr->c_dg_d[i], nm, S, S, n[i], ACT_NONE, 1, 1, nullptr, nullptr, 1, &gd)); tr->cur_bwd = false;
+            GroupSpec gd = one_group(n[i + 1], tr->o_w1[i], tr->o_ws[i], n[i], n[i + 1], 1, 0, flp);
+            T_TRY(setup_conv(tr, tr->c_dg_d[i], nm, S, S, n[i], ACT_NONE, 1, 1, nullptr, nullptr, 1, &gd, true));
             mac_total += tr->c_dg_d[i].mac;
         }
         T_TRY(setup_wgrad(tr, tr->wg_d[i], nm, S, n[i], n[i], n[i + 1], fwd, {}));
         mac_total += (double)S * S * ks * ks * n[i] * n[i + 1];
         S /= 2;
     }
-    {
-        GroupSpec g = group(n[L], tr->o_lb, SIZE_MAX, n[L], n[L + 1], 0, 0, fwd);
-        T_TRY(setup_conv(tr, tr->c_fwd_b, "lb", S, S, n[L + 1], ACT_NONE, 1, 1, nullptr, nullptr, 1, &g));
-        GroupSpec gd = group(n[L + 1], tr->o_lb, SIZE_MAX, n[L], n[L + 1], 1, 0, flp);
-        tr->cur_bwd = true; T_TRY(setup_conv(tr, tr->c_dg_b, "lb", S, S, n[L], ACT_NONE, 1, 1, nullptr, nullptr, 1, &gd)); tr->cur_bwd = false;
-        T_TRY(setup_wgrad(tr, tr->wg_b, "lb", S, n[L], n[L], n[L + 1], fwd, {}));
-        mac_total += tr->c_fwd_b.mac + tr->c_dg_b.mac + (double)S * S * ks * ks * n[L] * n[L + 1];
-    }
+    T_TRY(setup_bottom(tr, S, mac_total));
     for (int idx = L - 1; idx >= 0; --idx) T_TRY(setup_up_layer(tr, idx, S, ACT_LEAKY, mac_total));
-    mac_total += 3.0 * P * P * n[1] * K;
-    tr->flops_per_image = 2.0 * mac_total;
-    T_TRY(talloc(tr, &tr->d_ws, tr->ws_floats));
-    T_TRY(talloc(tr, &tr->d_ws2, tr->ws_floats));
-    T_TRY(talloc(tr, &tr->d_split, tr->split_floats));
-    T_TRY(talloc(tr, &tr->d_split2, tr->split_floats));
-    T_TRY(talloc(tr, &tr->d_split3, tr->split_floats));
-    {
-        std::vector<RegSeg> rs;
-        for (const Seg& sg : tr->segs)
-            if (sg.reg > 0.f) rs.push_back(RegSeg{tr->d_w + sg.off, sg.n, sg.reg});
-        tr->n_regsegs = (int)rs.size();
-        T_TRY(talloc(tr, &tr->d_regsegs, rs.size()));
-        if (!rs.empty()) T_HIP(tr, hipMemcpy(tr->d_regsegs, rs.data(), rs.size() * sizeof(RegSeg), hipMemcpyHostToDevice));
-    }
-    // forward operands first: the backward-only ones are packed on the side stream while the forward pass runs
-    std::stable_partition(tr->packs.begin(), tr->packs.end(), [](const PackDesc& d) { return d.bwd == 0; });
-    std::stable_partition(tr->rdescs.begin(), tr->rdescs.end(), [](const RepackDesc& d) { return d.bwd == 0; });
-    tr->n_fwd_packs = (int)std::count_if(tr->packs.begin(), tr->packs.end(), [](const PackDesc& d) { return d.bwd == 0; });
-    tr->n_fwd_rdescs = (int)std::count_if(tr->rdescs.begin(), tr->rdescs.end(), [](const RepackDesc& d) { return d.bwd == 0; });
-    T_TRY(talloc(tr, &tr->d_packs, tr->packs.size()));
-    T_HIP(tr, hipMemcpy(tr->d_packs, tr->packs.data(), tr->packs.size() * sizeof(PackDesc), hipMemcpyHostToDevice));
-    if (!tr->rdescs.empty()) {
-        T_TRY(talloc(tr, &tr->d_rdescs, tr->rdescs.size()));
-        T_HIP(tr, hipMemcpy(tr->d_rdescs, tr->rdescs.data(), tr->rdescs.size() * sizeof(RepackDesc), hipMemcpyHostToDevice));
-    }
-    tr->h_blob = nullptr;
-    return UMX_OK;
+    return finish_build(tr, mac_total, true);
 }
 
 // the step's weights -> the operands of every convolution: fp32 [tap][Cp][Np] (both routes), then conv_f16x3's weight images
@@ -1342,17 +1379,13 @@ int pack_all(umx_trainer* tr, hipStream_t st, int part) {
 int alloc_ident(umx_trainer* tr, float** out, int C) {
     std::vector<float> h(4 * (size_t)C, 0.f);
     for (int c = 0; c < C; ++c) { h[C + c] = 1.f; h[2 * C + c] = 1.f; }   // mean 0 | rstd 1 | scale 1 | shift 0
-    T_TRY(talloc(tr, out, h.size()));
-    T_HIP(tr, hipMemcpy(*out, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    return UMX_OK;
+    return tupload(tr, out, h.data(), h.size());
 }
 
 int build_legacy(umx_trainer* tr, const float* blob, size_t blob_floats) {
-    const umx_hparams& hp = tr->hp;
-    const int L = hp.nLayers, ks = hp.ks, P = hp.imSize, K = hp.nClasses, B = tr->B, E = hp.nExtraConvs;
-    tr->L = L; tr->K = K; tr->P = P; tr->E = E;
-    tr->n = {hp.nChannels, hp.nOut0};
-    for (int i = 0; i < L; ++i) tr->n.push_back(tr->n.back() * hp.featMapsFact);
+    set_shape(tr);
+    const int L = tr->L, ks = tr->hp.ks, P = tr->P, K = tr->K, B = tr->B, E = tr->hp.nExtraConvs;
+    tr->E = E;
     const std::vector<int>& n = tr->n;
 
     // ---- parameter vector layout (== unmicst_amd/model.py tensor_specs, GRAPH_LEGACY)
@@ -1377,14 +1410,7 @@ int build_legacy(umx_trainer* tr, const float* blob, size_t blob_floats) {
         for (int e = 0; e < E; ++e) tr->lub[idx].o_wx.push_back(seg(p + ".wextra" + std::to_string(e), (size_t)ks * ks * n[idx + 1] * n[idx + 1]));
     }
     tr->o_lt = seg("lt.w", (size_t)n[1] * K);
-    tr->nparams = pos;
-    if (blob_floats != pos)
-        return tfail(tr, UMX_ERR_BLOB, "weight blob has %zu floats, the graph needs %zu", blob_floats, pos);
-    T_TRY(talloc(tr, &tr->d_w, pos));
-    T_HIP(tr, hipMemcpy(tr->d_w, blob, pos * sizeof(float), hipMemcpyHostToDevice));
-    T_TRY(tzero(tr, &tr->d_g, pos));
-    T_TRY(tzero(tr, &tr->d_m, pos));
-    T_TRY(tzero(tr, &tr->d_v, pos));
+    T_TRY(alloc_params(tr, blob, blob_floats, pos));
 
     // ---- max words (zeroed every step), then the range flag
     tr->n_maxw = 16 + 4 * (L + 1) * (2 * E + 6);
@@ -1406,49 +1432,39 @@ int build_legacy(umx_trainer* tr, const float* blob, size_t blob_floats) {
     tr->ds.assign(L + 1, nullptr);
     tr->bn_d.resize(L);
     tr->us.assign(L, nullptr); tr->dskip.assign(L, nullptr);
-    tr->hconv = !getenv("UMX_TRAIN_CONV_F32");
-    if (const char* e = getenv("UMX_TRAIN_WSCALE_EVERY")) tr->wscale_every = atoi(e);
-    tr->wg_planes = tr->hconv;
-    tr->h_blob = blob;
-    tr->h_ds.resize(L + 1); tr->h_us.resize(L);   // (no buffers on the exact-fp32 route)
-    if (tr->hconv) {
-        tr->pctx = new umx_ctx();
-        tr->pctx->device = tr->device;
-        tr->pctx->hp = hp;
-    }
-    auto planes = [&](H16& h, size_t npix, int C) -> int { return tr->hconv ? alloc_h16(tr, h, npix, C) : UMX_OK; };
+    T_TRY(select_route(tr, blob));
     // a chain's tensors: y[0..E], a[0..na)
     auto chain = [&](LBlock& b, int S, int C, int na) -> int {
         const size_t npix = (size_t)B * S * S;
         b.y.assign(E + 1, nullptr); b.a.assign(na, nullptr); b.ha.resize(na);
         for (int e = 0; e <= E; ++e) T_TRY(talloc(tr, &b.y[e], npix * C));
-        for (int e = 0; e < na; ++e) { T_TRY(talloc(tr, &b.a[e], npix * C)); T_TRY(planes(b.ha[e], npix, C)); }
+        for (int e = 0; e < na; ++e) { T_TRY(talloc(tr, &b.a[e], npix * C)); T_TRY(alloc_h16(tr, b.ha[e], npix, C)); }
         return alloc_ident(tr, &b.ident, C);
     };
     size_t max_act = (size_t)B * P * P * std::max(n[0], K), max_dz = 0, max_gs = 0;
     auto grad_size = [&](size_t npix, int C) { max_act = std::max(max_act, npix * C); max_dz = std::max(max_dz, npix * round_up(C, 8)); };
     int S = P;
     T_TRY(talloc(tr, &tr->ds[0], (size_t)B * P * P * n[0]));
-    if (tr->hconv) T_TRY(alloc_h16(tr, tr->h_ds[0], (size_t)B * P * P, n[0]));
+    T_TRY(alloc_h16(tr, tr->h_ds[0], (size_t)B * P * P, n[0]));
     for (int i = 0; i < L; ++i) {
         T_TRY(chain(tr->ldb[i], S, n[i + 1], E));
         T_TRY(bn_alloc(tr, tr->bn_d[i], n[i + 1], S, bn_d_off[i]));   // (its z: relu(z), what BN normalises)
         grad_size((size_t)B * S * S, n[i + 1]);
         T_TRY(talloc(tr, &tr->ds[i + 1], (size_t)B * (S / 2) * (S / 2) * n[i + 1]));
-        if (tr->hconv) T_TRY(alloc_h16(tr, tr->h_ds[i + 1], (size_t)B * (S / 2) * (S / 2), n[i + 1]));
+        T_TRY(alloc_h16(tr, tr->h_ds[i + 1], (size_t)B * (S / 2) * (S / 2), n[i + 1]));
         if (i + 1 <= L - 1) T_TRY(talloc(tr, &tr->dskip[i + 1], (size_t)B * (S / 2) * (S / 2) * n[i + 1]));
         S /= 2;
     }
     T_TRY(talloc(tr, &tr->lb_z, (size_t)B * S * S * n[L + 1]));
     T_TRY(talloc(tr, &tr->act_b, (size_t)B * S * S * n[L + 1]));
-    T_TRY(planes(tr->h_b, (size_t)B * S * S, n[L + 1]));
+    T_TRY(alloc_h16(tr, tr->h_b, (size_t)B * S * S, n[L + 1]));
     T_TRY(alloc_ident(tr, &tr->lb_ident, n[L + 1]));
     grad_size((size_t)B * S * S, n[L + 1]);
     for (int idx = L - 1; idx >= 0; --idx) {
         max_gs = std::max(max_gs, (size_t)B * S * S * round_up(4 * n[idx + 1], 8));
         S *= 2;
         T_TRY(talloc(tr, &tr->us[idx], (size_t)B * S * S * n[idx + 1]));
-        T_TRY(planes(tr->h_us[idx], (size_t)B * S * S, n[idx + 1]));
+        T_TRY(alloc_h16(tr, tr->h_us[idx], (size_t)B * S * S, n[idx + 1]));
         T_TRY(chain(tr->lub[idx], S, n[idx + 1], E + 1));
         grad_size((size_t)B * S * S, n[idx + 1]);
     }
@@ -1458,11 +1474,8 @@ int build_legacy(umx_trainer* tr, const float* blob, size_t blob_floats) {
     T_TRY(talloc(tr, &tr->d_weights, (size_t)B * P * P * K));
     T_TRY(talloc(tr, &tr->d_probs, (size_t)B * P * P * K));
     T_TRY(talloc(tr, &tr->d_dt, (size_t)B * P * P * K));
-    {
-        const std::vector<float> ones((size_t)B * P * P * K, 1.f);
-        T_TRY(talloc(tr, &tr->d_ones, ones.size()));
-        T_HIP(tr, hipMemcpy(tr->d_ones, ones.data(), ones.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
+    const std::vector<float> ones((size_t)B * P * P * K, 1.f);
+    T_TRY(tupload(tr, &tr->d_ones, ones.data(), ones.size()));
     tr->max_act = max_act;
     T_TRY(talloc(tr, &tr->DA, max_act));
     T_TRY(talloc(tr, &tr->DB, max_act));
@@ -1495,9 +1508,9 @@ int build_legacy(umx_trainer* tr, const float* blob, size_t blob_floats) {
     // extra conv e >= 1 of a chain at size S with C channels: forward (ngroups 2: + the shortcut group g1), input and weight gradient
     auto extra = [&](LBlock& b, int e, int S, int C, int ngroups, const GroupSpec* g1) -> int {
         GroupSpec g[2] = {one_group(C, b.o_wx[e - 1], SIZE_MAX, C, C, 0, 0, fwd), g1 ? *g1 : GroupSpec()};
-        T_TRY(setup_conv(tr, b.fwd[e], nm, S, S, C, ACT_NONE, 1, 1, nullptr, nullptr, ngroups, g));
+        T_TRY(setup_conv(tr, b.fwd[e], nm, S, S, C, ACT_NONE, 1, 1, nullptr, nullptr, ngroups, g, false));
         GroupSpec gd = one_group(C, b.o_wx[e - 1], SIZE_MAX, C, C, 1, 0, flp);
-        tr->cur_bwd = true; T_TRY(setup_conv(tr, b.dg[e], nm, S, S, C, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gd)); tr->cur_bwd = false;
+        T_TRY(setup_conv(tr, b.dg[e], nm, S, S, C, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gd, true));
         T_TRY(setup_wgrad(tr, b.wg[e], nm, S, C, C, C, fwd, {}));
         mac_total += b.fwd[e].mac + b.dg[e].mac + (double)S * S * ks * ks * C * C;
         return UMX_OK;
@@ -1509,16 +1522,14 @@ int build_legacy(umx_trainer* tr, const float* blob, size_t blob_floats) {
         const int Ci = n[i], C = n[i + 1];
         const GroupSpec gsh = one_group(Ci, tr->o_ws[i], SIZE_MAX, Ci, C, 0, 0, ctr);
         GroupSpec g[2] = {one_group(Ci, tr->o_w1[i], SIZE_MAX, Ci, C, 0, 0, fwd), gsh};
-        T_TRY(setup_conv(tr, b.fwd[0], nm, S, S, C, ACT_NONE, 1, 1, nullptr, nullptr, E == 0 ? 2 : 1, g));
+        T_TRY(setup_conv(tr, b.fwd[0], nm, S, S, C, ACT_NONE, 1, 1, nullptr, nullptr, E == 0 ? 2 : 1, g, false));
         mac_total += b.fwd[0].mac;
         for (int e = 1; e <= E; ++e) T_TRY(extra(b, e, S, C, e == E ? 2 : 1, &gsh));
         if (i >= 1) {
             GroupSpec gd = one_group(C, tr->o_w1[i], SIZE_MAX, Ci, C, 1, 0, flp);
             GroupSpec gs = one_group(C, tr->o_ws[i], SIZE_MAX, Ci, C, 1, 0, ctr);
-            tr->cur_bwd = true;
-            T_TRY(setup_conv(tr, tr->c_dg_d[i], nm, S, S, Ci, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gd));
-            T_TRY(setup_conv(tr, b.dg_sh, nm, S, S, Ci, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gs));
-            tr->cur_bwd = false;
+            T_TRY(setup_conv(tr, tr->c_dg_d[i], nm, S, S, Ci, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gd, true));
+            T_TRY(setup_conv(tr, b.dg_sh, nm, S, S, Ci, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gs, true));
             mac_total += tr->c_dg_d[i].mac + b.dg_sh.mac;
         }
         T_TRY(setup_wgrad(tr, tr->wg_d[i], nm, S, Ci, Ci, C, fwd, {}));
@@ -1526,36 +1537,13 @@ int build_legacy(umx_trainer* tr, const float* blob, size_t blob_floats) {
         mac_total += (double)S * S * (ks * ks + 1) * Ci * C;
         S /= 2;
     }
-    {
-        GroupSpec g = one_group(n[L], tr->o_lb, SIZE_MAX, n[L], n[L + 1], 0, 0, fwd);
-        T_TRY(setup_conv(tr, tr->c_fwd_b, "lb", S, S, n[L + 1], ACT_NONE, 1, 1, nullptr, nullptr, 1, &g));
-        GroupSpec gd = one_group(n[L + 1], tr->o_lb, SIZE_MAX, n[L], n[L + 1], 1, 0, flp);
-        tr->cur_bwd = true; T_TRY(setup_conv(tr, tr->c_dg_b, "lb", S, S, n[L], ACT_NONE, 1, 1, nullptr, nullptr, 1, &gd)); tr->cur_bwd = false;
-        T_TRY(setup_wgrad(tr, tr->wg_b, "lb", S, n[L], n[L], n[L + 1], fwd, {}));
-        mac_total += tr->c_fwd_b.mac + tr->c_dg_b.mac + (double)S * S * ks * ks * n[L] * n[L + 1];
-    }
+    T_TRY(setup_bottom(tr, S, mac_total));
     for (int idx = L - 1; idx >= 0; --idx) {
         T_TRY(setup_up_layer(tr, idx, S, ACT_RELU, mac_total));
         snprintf(nm, sizeof nm, "lu%d", idx);
         for (int e = 1; e <= E; ++e) T_TRY(extra(tr->lub[idx], e, S, n[idx + 1], 1, nullptr));
     }
-    mac_total += 3.0 * P * P * n[1] * K;
-    tr->flops_per_image = 2.0 * mac_total;
-    T_TRY(talloc(tr, &tr->d_ws, tr->ws_floats));
-    T_TRY(talloc(tr, &tr->d_split, tr->split_floats));
-    std::stable_partition(tr->packs.begin(), tr->packs.end(), [](const PackDesc& d) { return d.bwd == 0; });
-    std::stable_partition(tr->rdescs.begin(), tr->rdescs.end(), [](const RepackDesc& d) { return d.bwd == 0; });
-    tr->n_fwd_packs = (int)std::count_if(tr->packs.begin(), tr->packs.end(), [](const PackDesc& d) { return d.bwd == 0; });
-    tr->n_fwd_rdescs = (int)std::count_if(tr->rdescs.begin(), tr->rdescs.end(), [](const RepackDesc& d) { return d.bwd == 0; });
-    T_TRY(talloc(tr, &tr->d_packs, tr->packs.size()));
-    if (!tr->packs.empty())
-        T_HIP(tr, hipMemcpy(tr->d_packs, tr->packs.data(), tr->packs.size() * sizeof(PackDesc), hipMemcpyHostToDevice));
-    if (!tr->rdescs.empty()) {
-        T_TRY(talloc(tr, &tr->d_rdescs, tr->rdescs.size()));
-        T_HIP(tr, hipMemcpy(tr->d_rdescs, tr->rdescs.data(), tr->rdescs.size() * sizeof(RepackDesc), hipMemcpyHostToDevice));
-    }
-    tr->h_blob = nullptr;
-    return UMX_OK;
+    return finish_build(tr, mac_total, false);
 }
 
 // forward of the legacy graph up to the logits.  training: batch statistics (moving averages updated when `update`) and the max
@@ -1566,24 +1554,18 @@ int forward_legacy(umx_trainer* tr, const float* data, bool training, bool updat
     hipStream_t st = tr->stream;
     const size_t Bz = (size_t)tr->B;
     int* const flagp = reinterpret_cast<int*>(tr->d_maxw + tr->n_maxw);
-    auto conv = [&](TConv& tc, const float* x0, const float* x1, const H16* h0, const H16* h1, float* dst) -> int {
-        if (tc.hidx >= 0) return run_hconv(tr, tc, *h0, h1, dst, nullptr, st);
-        return run_conv(tr, tc, x0, x1, dst);
-    };
     auto act = [&](const float* z, const float* stat, int S, int C, int pool, int a_kind, float* out, const H16* h, unsigned* omax) -> int {
         ActParams a;
         a.z = z; a.stat = stat;
         a.B = tr->B; a.H = a.W = S; a.C = C;
         a.pool = pool; a.act = a_kind;
         a.drop_rate = 0.f; a.drop_key = 0;
-        const bool pl = tr->hconv && h;
-        T_HIP(tr, launch_act_fwd(a, out, training ? omax : nullptr, pl ? h->hi : nullptr, pl ? h->lo : nullptr, pl ? h->Cs : 0, flagp, st));
+        // (h: the planes the kernel writes, empty on the exact-fp32 route)
+        T_HIP(tr, launch_act_fwd(a, out, training ? omax : nullptr, h ? h->hi : nullptr, h ? h->lo : nullptr, h ? h->Cs : 0, flagp, st));
         return UMX_OK;
     };
-    auto H = [&](H16& h) -> const H16* { return tr->hconv ? &h : nullptr; };
     tr->ds[0] = const_cast<float*>(data);
-    if (training && !tr->hconv) T_HIP(tr, launch_absmax(data, Bz * tr->P * tr->P * n[0], tr->dsmax[0], st));
-    if (tr->hconv) T_TRY(to_h16(tr, data, Bz * tr->P * tr->P, n[0], tr->h_ds[0], nullptr, nullptr, st, training ? tr->dsmax[0] : nullptr));
+    T_TRY(track_act(tr, data, Bz * tr->P * tr->P, n[0], tr->h_ds[0], tr->dsmax[0], training));
     int S = tr->P;
     for (int i = 0; i < L; ++i) {
         LBlock& b = tr->ldb[i];
@@ -1591,33 +1573,32 @@ int forward_legacy(umx_trainer* tr, const float* data, bool training, bool updat
         const int C = n[i + 1];
         for (int e = 0; e <= E; ++e) {
             const bool last = e == E;   // (+ the shortcut on the block input)
-            T_TRY(conv(b.fwd[e], e == 0 ? tr->ds[i] : b.a[e - 1], last ? tr->ds[i] : nullptr, e == 0 ? H(tr->h_ds[i]) : H(b.ha[e - 1]),
-                       last ? H(tr->h_ds[i]) : nullptr, b.y[e]));
-            if (!last) T_TRY(act(b.y[e], b.ident, S, C, 0, ACT_RELU, b.a[e], H(b.ha[e]), b.amax[e]));
+            T_TRY(run_tconv(tr, b.fwd[e], e == 0 ? tr->ds[i] : b.a[e - 1], e == 0 ? tr->h_ds[i] : b.ha[e - 1], nullptr, b.y[e],
+                            last ? tr->ds[i] : nullptr, last ? &tr->h_ds[i] : nullptr));
+            if (!last) T_TRY(act(b.y[e], b.ident, S, C, 0, ACT_RELU, b.a[e], &b.ha[e], b.amax[e]));
         }
         T_TRY(act(b.y[E], b.ident, S, C, 0, ACT_RELU, s.z, nullptr, nullptr));      // relu(z): what BN normalises
         T_TRY(bn_forward_stats(tr, s, update, training));
-        T_TRY(act(s.z, s.stat, S, C, 1, ACT_NONE, tr->ds[i + 1], H(tr->h_ds[i + 1]), tr->dsmax[i + 1]));   // BN, then the pool
+        T_TRY(act(s.z, s.stat, S, C, 1, ACT_NONE, tr->ds[i + 1], &tr->h_ds[i + 1], tr->dsmax[i + 1]));   // BN, then the pool
         S /= 2;
     }
-    T_TRY(conv(tr->c_fwd_b, tr->ds[L], nullptr, H(tr->h_ds[L]), nullptr, tr->lb_z));
-    T_TRY(act(tr->lb_z, tr->lb_ident, S, n[L + 1], 0, ACT_RELU, tr->act_b, H(tr->h_b), tr->bmax));
+    T_TRY(run_tconv(tr, tr->c_fwd_b, tr->ds[L], tr->h_ds[L], nullptr, tr->lb_z));
+    T_TRY(act(tr->lb_z, tr->lb_ident, S, n[L + 1], 0, ACT_RELU, tr->act_b, &tr->h_b, tr->bmax));
     const float* cur = tr->act_b;
-    const H16* hcur = H(tr->h_b);
+    const H16* hcur = &tr->h_b;
     for (int idx = L - 1; idx >= 0; --idx) {
         LBlock& b = tr->lub[idx];
         const int C = n[idx + 1];
         S *= 2;
-        T_TRY(conv(tr->c_T[idx], cur, nullptr, hcur, nullptr, tr->us[idx]));   // (ReLU fused)
-        if (training && !tr->hconv) T_HIP(tr, launch_absmax(tr->us[idx], Bz * S * S * C, tr->usmax[idx], st));
-        if (tr->hconv) T_TRY(to_h16(tr, tr->us[idx], Bz * S * S, C, tr->h_us[idx], nullptr, nullptr, st, training ? tr->usmax[idx] : nullptr));
+        T_TRY(run_tconv(tr, tr->c_T[idx], cur, *hcur, nullptr, tr->us[idx]));   // (ReLU fused)
+        T_TRY(track_act(tr, tr->us[idx], Bz * S * S, C, tr->h_us[idx], tr->usmax[idx], training));
         for (int e = 0; e <= E; ++e) {
-            if (e == 0) T_TRY(conv(tr->c_fwd_u[idx], tr->ds[idx], tr->us[idx], H(tr->h_ds[idx]), H(tr->h_us[idx]), b.y[0]));
-            else T_TRY(conv(b.fwd[e], b.a[e - 1], nullptr, H(b.ha[e - 1]), nullptr, b.y[e]));
-            T_TRY(act(b.y[e], b.ident, S, C, 0, ACT_RELU, b.a[e], H(b.ha[e]), b.amax[e]));
+            if (e == 0) T_TRY(run_tconv(tr, tr->c_fwd_u[idx], tr->ds[idx], tr->h_ds[idx], nullptr, b.y[0], tr->us[idx], &tr->h_us[idx]));
+            else T_TRY(run_tconv(tr, b.fwd[e], b.a[e - 1], b.ha[e - 1], nullptr, b.y[e]));
+            T_TRY(act(b.y[e], b.ident, S, C, 0, ACT_RELU, b.a[e], &b.ha[e], b.amax[e]));
         }
         cur = b.a[E];
-        hcur = H(b.ha[E]);
+        hcur = &b.ha[E];
     }
     T_HIP(tr, launch_head_fwd(cur, Bz * tr->P * tr->P, n[1], tr->K, tr->d_w + tr->o_lt, tr->lt_z, st));
     return UMX_OK;
@@ -1627,21 +1608,12 @@ int enqueue_legacy(umx_trainer* tr, const float* data, const float* labels, cons
     const int L = tr->L, K = tr->K, B = tr->B, P = tr->P, E = tr->E;
     const std::vector<int>& n = tr->n;
     hipStream_t st = tr->stream;
-    const umx_train_options& o = tr->o;
     const size_t Npix = (size_t)B * P * P;
     int* const flagp = reinterpret_cast<int*>(tr->d_maxw + tr->n_maxw);
-    if (update && tr->step > 0 && tr->wscale_every > 0 && tr->step % tr->wscale_every == 0) T_TRY(refresh_wscales(tr));
-    if (tr->prof) T_HIP(tr, hipEventRecord(tr->ev[0], st));
-    T_HIP(tr, hipMemsetAsync(tr->d_loss, 0, 2 * sizeof(double), st));
-    T_HIP(tr, hipMemsetAsync(tr->d_maxw, 0, tr->n_maxw * sizeof(unsigned), st));   // (the range flag behind them stays: see enqueue_step)
+    T_TRY(step_begin(tr, update));
     T_TRY(pack_all(tr, st, 2));
     T_TRY(forward_legacy(tr, data, true, update));
-    {
-        const int nblk = loss_blocks(Npix);
-        T_HIP(tr, launch_softmax_loss(tr->lt_z, tr->ident_k, labels, weights ? weights : tr->d_ones, Npix, K, o.clip_eps, tr->d_probs,
-                                      tr->d_dt, tr->d_part, nblk, st));
-        T_HIP(tr, launch_sum_to_scalar(tr->d_part, nblk, 1.0 / (double)Npix, tr->d_loss, 0, 0, st));
-    }
+    T_TRY(loss_head(tr, tr->lt_z, tr->ident_k, labels, weights ? weights : tr->d_ones));
     if (tr->prof) T_HIP(tr, hipEventRecord(tr->ev[1], st));
 
     // ------------------------------------------------------------------ backward
@@ -1652,10 +1624,6 @@ int enqueue_legacy(umx_trainer* tr, const float* data, const float* labels, cons
         T_HIP(tr, launch_reduce_partials(tr->d_part, nblk, n[1] * K, 1.0, tr->d_g + tr->o_lt, tr->d_w + tr->o_lt, 0, 0.f, st));
     }
     float* const gb[2] = {tr->DZ, tr->TX};   // a chain's gradients alternate between these two, their planes between h_dz[0] / [1]
-    auto dgrad = [&](TConv& tc, const float* x, int pl, float* dst) -> int {
-        if (tc.hidx >= 0) return run_hconv(tr, tc, tr->h_dz[pl], nullptr, dst, tr->d_xinv + pl, st);
-        return run_conv(tr, tc, x, nullptr, dst);
-    };
     // gradient w.r.t. y (pre-ReLU) from the gradient w.r.t. relu(y): into gb[pl], with its max word and planes
     auto relu_bwd = [&](const float* dy, const float* y, int pl, size_t npix, int C, unsigned* gw) -> int {
         T_HIP(tr, launch_relu_bwd_max(dy, y, gb[pl], npix * C, gw, st));
@@ -1672,7 +1640,7 @@ int enqueue_legacy(umx_trainer* tr, const float* data, const float* labels, cons
         for (int e = E; e >= 1; --e) {
             const int pl = (E - e) & 1;
             T_TRY(wgrad(b.wg[e], b.a[e - 1], &b.ha[e - 1], b.amax[e - 1], pl, b.gmax[e], C, 0, b.o_wx[e - 1]));
-            T_TRY(dgrad(b.dg[e], gb[pl], pl, tr->DA));
+            T_TRY(run_tconv(tr, b.dg[e], gb[pl], tr->h_dz[pl], tr->d_xinv + pl, tr->DA));
             T_TRY(relu_bwd(tr->DA, b.y[e - 1], pl ^ 1, npix, C, b.gmax[e - 1]));
         }
         return UMX_OK;
@@ -1687,8 +1655,8 @@ int enqueue_legacy(umx_trainer* tr, const float* data, const float* labels, cons
         const int p0 = E & 1;
         T_TRY(wgrad(tr->wg_u0[idx], tr->ds[idx], &tr->h_ds[idx], tr->dsmax[idx], p0, b.gmax[0], Cskip + Cup, 0, tr->o_w2[idx]));
         T_TRY(wgrad(tr->wg_u1[idx], tr->us[idx], &tr->h_us[idx], tr->usmax[idx], p0, b.gmax[0], Cskip + Cup, Cskip, tr->o_w2[idx]));
-        T_TRY(dgrad(tr->c_dg_us[idx], gb[p0], p0, tr->DB));
-        if (idx >= 1) T_TRY(dgrad(tr->c_dg_skip[idx], gb[p0], p0, tr->dskip[idx]));
+        T_TRY(run_tconv(tr, tr->c_dg_us[idx], gb[p0], tr->h_dz[p0], tr->d_xinv + p0, tr->DB));
+        if (idx >= 1) T_TRY(run_tconv(tr, tr->c_dg_skip[idx], gb[p0], tr->h_dz[p0], tr->d_xinv + p0, tr->dskip[idx]));
         T_HIP(tr, launch_leaky_bwd_s2d_max(tr->DB, tr->us[idx], B, S / 2, Cup, 0.f, tr->GS, tr->smax[idx], st));   // ReLU: slope 0
         if (tr->hconv) {
             tr->h_gs[0].Cs = round_up(4 * Cup, 8);
@@ -1699,17 +1667,14 @@ int enqueue_legacy(umx_trainer* tr, const float* data, const float* labels, cons
         T_TRY(run_wgrad(tr, tr->wg_T[idx], tr->GS, layer_in, Cup, 0, tr->o_wt[idx], 0.f, SIZE_MAX, tr->smax[idx],
                         idx == L - 1 ? tr->bmax : tr->lub[idx + 1].amax[E], st, tr->hconv ? &tr->h_gs[0] : nullptr, tr->d_xinv + kSlots, hin,
                         nullptr));
-        if (tr->c_dg_T[idx].hidx >= 0)
-            T_TRY(run_hconv(tr, tr->c_dg_T[idx], tr->h_gs[0], nullptr, tr->DA, tr->d_xinv + kSlots, st));
-        else
-            T_TRY(run_conv(tr, tr->c_dg_T[idx], tr->GS, nullptr, tr->DA));
+        T_TRY(run_tconv(tr, tr->c_dg_T[idx], tr->GS, tr->h_gs[0], tr->d_xinv + kSlots, tr->DA));
         S /= 2;
     }
     {   // bottom
         const size_t npix = (size_t)B * S * S;
         T_TRY(relu_bwd(tr->DA, tr->lb_z, 0, npix, n[L + 1], tr->lb_gmax));
         T_TRY(wgrad(tr->wg_b, tr->ds[L], &tr->h_ds[L], tr->dsmax[L], 0, tr->lb_gmax, n[L], 0, tr->o_lb));
-        T_TRY(dgrad(tr->c_dg_b, gb[0], 0, tr->DB));
+        T_TRY(run_tconv(tr, tr->c_dg_b, gb[0], tr->h_dz[0], tr->d_xinv, tr->DB));
     }
     for (int i = L - 1; i >= 0; --i) {     // down layers; DB (+ dskip[i+1]): d loss / d ds[i+1]
         S *= 2;
@@ -1727,32 +1692,16 @@ int enqueue_legacy(umx_trainer* tr, const float* data, const float* labels, cons
         }
         // the shortcut: weight gradient and (i >= 1) input gradient, before the chain reuses gb[0]
         T_TRY(wgrad(b.wg_sh, tr->ds[i], &tr->h_ds[i], tr->dsmax[i], 0, b.gmax[E], Ci, 0, tr->o_ws[i]));
-        if (i >= 1) T_TRY(dgrad(b.dg_sh, gb[0], 0, tr->DSUM + tr->max_act));
+        if (i >= 1) T_TRY(run_tconv(tr, b.dg_sh, gb[0], tr->h_dz[0], tr->d_xinv, tr->DSUM + tr->max_act));
         T_TRY(extras_bwd(b, npix, C));
         const int p0 = E & 1;
         T_TRY(wgrad(tr->wg_d[i], tr->ds[i], &tr->h_ds[i], tr->dsmax[i], p0, b.gmax[0], Ci, 0, tr->o_w1[i]));
         if (i >= 1) {   // d ds[i] = first-conv input gradient + shortcut input gradient
-            T_TRY(dgrad(tr->c_dg_d[i], gb[p0], p0, tr->DSUM));
+            T_TRY(run_tconv(tr, tr->c_dg_d[i], gb[p0], tr->h_dz[p0], tr->d_xinv + p0, tr->DSUM));
             T_HIP(tr, launch_split_reduce(tr->DSUM, 2, tr->max_act, npix * Ci, ACT_NONE, tr->DB, st));
         }
     }
-    if (tr->prof) T_HIP(tr, hipEventRecord(tr->ev[2], st));
-    if (update) {   // MomentumOptimizer (or Adam, when asked for) over the flat vector; BN moving statistics were updated in the forward pass
-        OptParams op;
-        op.kind = o.optimizer;
-        const double lr = (double)o.lr0 * std::pow((double)o.decay_rate, (double)(tr->step / std::max(1, o.decay_steps)));
-        const double tt = (double)(tr->step + 1);
-        op.lr = (float)lr;
-        op.lr_t = (float)(lr * std::sqrt(1.0 - std::pow((double)o.beta2, tt)) / (1.0 - std::pow((double)o.beta1, tt)));
-        op.beta1 = o.beta1; op.beta2 = o.beta2; op.eps = o.adam_eps; op.momentum = o.momentum;
-        T_HIP(tr, launch_optimizer(op, tr->d_w, tr->d_g, tr->d_m, tr->d_v, tr->nparams, st));
-        tr->step += 1;
-    }
-    if (tr->prof) {
-        T_HIP(tr, hipEventRecord(tr->ev[3], st));
-        tr->pending = true;
-    }
-    return UMX_OK;
+    return step_end(tr, update);
 }
 
 }  // namespace
