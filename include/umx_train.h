@@ -102,6 +102,53 @@ UMX_API double umx_trainer_flops_per_image(const umx_trainer* tr);
 /* per-phase time of the steps since the last call (ms, accumulated with HIP events when enabled) */
 UMX_API int umx_trainer_profile(umx_trainer* tr, int enable, double* fwd_ms, double* bwd_ms, double* opt_ms, int* steps);
 
+/* ---- device-resident training set (unmicst_amd/csrc/umx_trainset.hip) ----
+ * The reference's annotated set (I%05d_Img.tif / _Ant.tif / _wt.tif, UnMicst1-5.py:295-312, UnMicst2.py:293-309,
+ * UnMicst.py:236-243) uploaded once; each step's batch is then built on the device from 32-byte descriptors. */
+typedef struct umx_trainset umx_trainset;
+
+/* The label / weight recipe: labels[k] = (code == k+1); weights[k] = intersect_weight[k] * wmap + class_weight[k] (float64, one
+ * rounding; UnMicst1-5.py:276-281,306-312: W * intersectWeight + contourWeight).  weighted == 0: no weights are built and the
+ * step takes the unweighted loss (legacy trainer only). */
+typedef struct umx_label_weights {
+    int32_t weighted;
+    float class_weight[8];
+    float intersect_weight[8];
+    int32_t reserved[7];      /* must be zero */
+} umx_label_weights;
+
+typedef struct umx_sample_desc {  /* 32 bytes: one image of a batch */
+    int32_t index, page, y0, x0;  /* sample, augmentation page, crop origin (0 <= y0, x0 <= size - imSize) */
+    int32_t transform;            /* 0..7: bit 2 swaps the axes, then bit 1 flips the rows, then bit 0 flips the columns of the crop */
+    float brightness, contrast;   /* data = float32((double)v * contrast + brightness), v the stored (normalised) value */
+    int32_t reserved;             /* must be zero */
+} umx_sample_desc;
+
+/* n_samples samples of size x size pixels (size >= hp.imSize), each with nChannels x n_pages image planes, one annotation plane
+ * and (weighted sets) one weight map, in the trainer's device memory.  Channels, classes and device come from the trainer.
+ * UMX_ERR_OOM when n_samples * size^2 * (4 nChannels n_pages + 1 + 4 weighted) bytes do not fit in the free device memory;
+ * UMX_ERR_INVALID for an unweighted set on a v2 trainer.  The set belongs to `tr` and must be destroyed before it. */
+UMX_API int umx_trainset_create(umx_trainer* tr, int n_samples, int n_pages, int size, const umx_label_weights* lw,
+                                umx_trainset** out);
+/* Upload sample `index`: planes [nChannels][n_pages][size][size] float32, already normalised ((im2double(x) - mean) / std);
+ * annotation [size][size] class codes (k + 1 = class k, 0 or > nClasses: unlabelled); weight_map [size][size] or NULL (= 0). */
+UMX_API int umx_trainset_set(umx_trainset* ts, int index, const float* planes, const uint8_t* annotation, const float* weight_map);
+UMX_API void umx_trainset_destroy(umx_trainset* ts);
+/* Exactly B descriptors (host memory): assemble the batch into the trainer's own data / labels / weights buffers, then enqueue
+ * the step of umx_train_step_dev on them (umx_trainer_loss reads the loss).  Every descriptor is checked first: a bad one is
+ * UMX_ERR_INVALID and nothing is enqueued. */
+UMX_API int umx_train_step_sampled(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, int apply_update);
+/* Assemble n <= B descriptors and copy the first n images to the host: data [n,P,P,nChannels], labels and weights
+ * [n,P,P,nClasses] (weights may be NULL; an unweighted set writes none).  Tests and diagnostics; synchronous. */
+UMX_API int umx_trainer_assemble(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, int n, float* data,
+                                 float* labels, float* weights);
+/* The validation pass: assemble n <= B descriptors (rows n..B-1 zero), the eval-mode forward of umx_trainer_eval with the
+ * probabilities kept on the device, then per class k: counts[k] = pixels labelled k whose argmax (first maximum) is k, counts[K + k]
+ * = pixels labelled k; *loss_sum = sum over labelled pixels of -log p[label], float64 in a fixed order.  Synchronous; reports
+ * the range flag as umx_trainer_eval does. */
+UMX_API int umx_trainer_evaluate(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, int n, int64_t* counts,
+                                 double* loss_sum);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,114 @@
+"""Images/s of a training step fed from the device-resident training set (Trainer.step_sampled) against the host-fed step
+(numpy batch assembly -- crop, augmentation page, dihedral transform, jitter, one-hot labels, weight maps -- then Trainer.step),
+in one process, alternating the two, on the same descriptor stream.  Every step reads its loss (one synchronisation per step on
+both paths).  Then the validation pass (Trainer.evaluate) over the whole set.  One JSON line per (shape, path, repeat).
+
+    python tools/bench_trainset.py [--steps 30] [--warmup 5] [--repeats 3] [--shapes nucleiDAPI,v2-256]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from unmicst_amd import model, trainer, trainset  # noqa: E402
+
+
+def host_batch(planes, ann, wmaps, d, P, K, lw):
+    """What a host-fed loop builds per step (the reference's own loop does this in numpy, UnMicst1-5.py:466-481)."""
+    n, C = len(d), planes.shape[1]
+    data = np.empty((n, P, P, C), np.float32)
+    labels = np.empty((n, P, P, K), np.float32)
+    weights = np.empty((n, P, P, K), np.float32) if lw.weighted else None
+    ks = np.arange(1, K + 1, dtype=np.uint8)
+    for b in range(n):
+        i, pg, y0, x0, t = (int(d[f][b]) for f in ("index", "page", "y0", "x0", "transform"))
+
+        def tf(a):
+            if t & 4:
+                a = np.swapaxes(a, -1, -2)
+            if t & 2:
+                a = a[..., ::-1, :]
+            if t & 1:
+                a = a[..., ::-1]
+            return a
+        v = tf(planes[i, :, pg, y0:y0 + P, x0:x0 + P]).astype(np.float64)
+        data[b] = np.moveaxis(v * np.float64(d["contrast"][b]) + np.float64(d["brightness"][b]), 0, -1)
+        code = tf(ann[i, y0:y0 + P, x0:x0 + P])
+        labels[b] = code[..., None] == ks
+        if weights is not None:
+            w = tf(wmaps[i, y0:y0 + P, x0:x0 + P]).astype(np.float64)[..., None]
+            weights[b] = w * np.asarray(lw.intersect_weight[:K], np.float64) + np.asarray(lw.class_weight[:K], np.float64)
+    return data, labels, weights
+
+
+def shapes(names):
+    out = []
+    for nm in names:
+        if nm == "nucleiDAPI":
+            out.append((nm, model.KNOWN_HP["nucleiDAPI"], 16, trainer.legacy_options(), trainset.UNWEIGHTED, 0.0, 0.0))
+        elif nm == "v2-256":
+            out.append((nm, model.KNOWN_HP["synthetic-256"], 8, trainer.duo_options(), trainset.LABEL_WEIGHTS["duo"], 0.17, 0.017))
+        else:
+            raise SystemExit("unknown shape %s" % nm)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--shapes", default="nucleiDAPI,v2-256")
+    ap.add_argument("--samples", type=int, default=32)
+    a = ap.parse_args()
+    for name, hp, B, opts, lw, mb, mc in shapes(a.shapes.split(",")):
+        P, S, pages = hp.imSize, hp.imSize + hp.imSize // 4, 2
+        rng = np.random.default_rng(0)
+        planes = rng.normal(0, 1, (a.samples, hp.nChannels, pages, S, S)).astype(np.float32)
+        ann = rng.integers(0, hp.nClasses + 1, (a.samples, S, S)).astype(np.uint8)
+        wmaps = rng.random((a.samples, S, S)).astype(np.float32)
+        blob = model.random_blob(hp, seed=1)
+        tr = trainer.Trainer(hp, blob, opts, batch=B)
+        ts = trainset.TrainSet.from_arrays(tr, planes, ann, list(wmaps), lw)
+        sampler = trainset.Sampler(1, a.samples, B, S, P, pages, mb, mc, transforms=True)
+        per_step = B * P * P * (hp.nChannels + (2 if lw.weighted else 1) * hp.nClasses) * 4
+
+        def run_sampled(n):
+            t0 = time.perf_counter()
+            for _ in range(n):
+                tr.step_sampled(ts, sampler.next())
+                tr.loss()
+            return time.perf_counter() - t0
+
+        def run_host(n):
+            t0 = time.perf_counter()
+            for _ in range(n):
+                tr.step(*host_batch(planes, ann, wmaps, sampler.next(), P, hp.nClasses, lw))
+            return time.perf_counter() - t0
+
+        run_sampled(a.warmup)
+        run_host(a.warmup)
+        for r in range(a.repeats):
+            for path, fn in (("step_sampled", run_sampled), ("host_fed", run_host)):
+                dt = fn(a.steps)
+                print(json.dumps({"shape": name, "batch": B, "path": path, "repeat": r, "steps": a.steps, "seconds": round(dt, 5),
+                                  "images_per_s": round(a.steps * B / dt, 1), "step_ms": round(1e3 * dt / a.steps, 4),
+                                  "host_fed_upload_bytes_per_step": per_step}), flush=True)
+        vd = trainset.validation_descriptors(a.samples, S, P)
+        tr.evaluate(ts, vd)
+        for r in range(a.repeats):
+            t0 = time.perf_counter()
+            ev = tr.evaluate(ts, vd)
+            dt = time.perf_counter() - t0
+            print(json.dumps({"shape": name, "batch": B, "path": "evaluate", "repeat": r, "images": len(vd), "seconds": round(dt, 5),
+                              "images_per_s": round(len(vd) / dt, 1), "labelled": int(ev["counts"][1].sum())}), flush=True)
+        ts.close()
+        tr.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/umx.h"
+#include "../../include/umx_train.h"
 #include "umx_kernels.h"
 
 
@@ -290,5 +291,39 @@ int tiles_range(umx_ctx* ctx, const double* image_dev, int C_img, const TileGeom
                 const unsigned* mm_dev = nullptr /* raw planes: rescale_intensity to each plane's (min, max) words, 16 words apart */);
 // the tile gather of this engine can read raw integer planes (im2double in the gather: no float64 image is written or read)
 bool gathers_raw(const umx_ctx* ctx);
+
+// ---- training step (umx_train.hip) as the training set (umx_trainset.hip) sees it ----
+struct TrainerIO {
+    int device, B, P, C, K;            // batch, tile, input channels, classes
+    bool legacy;
+    hipStream_t stream;
+    float *data, *labels, *weights;    // the step's own input buffers [B,P,P,C] / [B,P,P,K] (what umx_train_step uploads into)
+    const float* probs;                // softmax of the last forward pass [B,P,P,K]
+};
+TrainerIO trainer_io(umx_trainer* tr);
+int trainer_fail(umx_trainer* tr, int code, const char* msg);   // -> code, with msg as umx_trainer_last_error
+// umx_trainer_eval = begin (device, range-flag bookkeeping), batch into io.data, forward (-> io.probs), read-back, end (sync, flag)
+int trainer_eval_begin(umx_trainer* tr);
+int trainer_eval_forward(umx_trainer* tr);
+int trainer_eval_end(umx_trainer* tr);
+
+// ---- training-set kernels (umx_trainset.hip) ----
+constexpr int kDescChunk = 64;         // descriptors per assembly launch (passed by value: 2 KiB of kernel arguments)
+struct DescChunk { umx_sample_desc d[kDescChunk]; };
+struct TrainSetView {                  // device layout of one training set
+    const float* planes;               // [N][C][pages][S][row_f]
+    const uint8_t* ann;                // [N][S][row_a]
+    const float* wmap;                 // [N][S][row_f], or null (unweighted)
+    int S, pages, C, row_f, row_a;
+    float cw[8], iw[8];
+};
+// rows b0 .. b0+m-1 of data [B,P,P,C] / labels, weights [B,P,P,K] (weights null: none); a descriptor with index < 0 writes zeros
+hipError_t launch_assemble_batch(const TrainSetView& ts, const DescChunk& dc, int m, int b0, int P, int K, float* data, float* labels,
+                                 float* weights, hipStream_t stream);
+// counts [2K] int64 (correct | labelled) and loss [1] double over npix pixels of probs / labels [npix, K]; part: class_counts_parts(npix)
+// doubles of workspace
+size_t class_counts_parts(size_t npix, int K);
+hipError_t launch_class_counts(const float* probs, const float* labels, size_t npix, int K, double* part, long long* counts,
+                               double* loss, hipStream_t stream);
 
 }  // namespace umx

@@ -1706,6 +1706,64 @@ int enqueue_legacy(umx_trainer* tr, const float* data, const float* labels, cons
 
 }  // namespace
 
+// ---- the internal interface of umx_trainset.hip (umx_internal.h) ----
+namespace umx {
+
+TrainerIO trainer_io(umx_trainer* tr) {
+    TrainerIO io;
+    io.device = tr->device; io.B = tr->B; io.P = tr->P; io.C = tr->n[0]; io.K = tr->K;
+    io.legacy = tr->legacy;
+    io.stream = tr->stream;
+    io.data = tr->ds[0]; io.labels = tr->d_labels; io.weights = tr->d_weights; io.probs = tr->d_probs;
+    return io;
+}
+
+int trainer_fail(umx_trainer* tr, int code, const char* msg) { return tfail(tr, code, "%s", msg); }
+
+// umx_trainer_eval in three parts, so that umx_trainer_evaluate can assemble its batch on the device and keep the probabilities there.
+// begin: the range flag is shared with the training steps: what is up now belongs to a step whose loss was not read yet -- remember
+// it for umx_trainer_loss, so that the flag this pass raises (repack + split-precision forward) is this pass's own
+int trainer_eval_begin(umx_trainer* tr) {
+    T_HIP(tr, hipSetDevice(tr->device));
+    T_TRY(fold_profile(tr));
+    unsigned before = 0;
+    T_HIP(tr, hipMemcpyAsync(&before, tr->d_maxw + tr->n_maxw, sizeof before, hipMemcpyDeviceToHost, tr->stream));
+    T_HIP(tr, hipStreamSynchronize(tr->stream));
+    if (before) {
+        tr->range_pending = true;
+        T_HIP(tr, hipMemsetAsync(tr->d_maxw + tr->n_maxw, 0, sizeof(unsigned), tr->stream));   // (in the order of the work that can raise the flag)
+    }
+    return UMX_OK;
+}
+
+// forward: the eval-mode pass (moving statistics, no dropout) on the batch in ds[0] -> softmax in d_probs
+int trainer_eval_forward(umx_trainer* tr) {
+    const size_t npx = (size_t)tr->B * tr->P * tr->P;
+    float* own = tr->ds[0];
+    T_TRY(pack_all(tr, tr->stream, 0));
+    const int rc = tr->legacy ? forward_legacy(tr, own, false, false) : forward_pass(tr, own, false, false);
+    tr->ds[0] = own;
+    T_TRY(rc);
+    if (tr->legacy) T_HIP(tr, launch_softmax_only(tr->lt_z, tr->ident_k, npx, tr->K, tr->d_probs, tr->stream));
+    else T_HIP(tr, launch_softmax_only(tr->bn_t.z, tr->bn_t.stat, npx, tr->K, tr->d_probs, tr->stream));
+    return UMX_OK;
+}
+
+// end: wait for the pass and report the flag it raised
+int trainer_eval_end(umx_trainer* tr) {
+    unsigned flag = 0;
+    T_HIP(tr, hipMemcpyAsync(&flag, tr->d_maxw + tr->n_maxw, sizeof flag, hipMemcpyDeviceToHost, tr->stream));
+    T_HIP(tr, hipStreamSynchronize(tr->stream));
+    if (flag) {
+        T_HIP(tr, hipMemsetAsync(tr->d_maxw + tr->n_maxw, 0, sizeof(unsigned), tr->stream));   // (in the order of the work that can raise the flag)
+        return tfail(tr, UMX_ERR_RANGE, "an operand of the split-precision forward pass of umx_trainer_eval left the binary16 range (|v| >= 6e4 or "
+                                        "not finite): the probabilities are not valid; UMX_TRAIN_CONV_F32=1 selects the exact-fp32 kernels");
+    }
+    return UMX_OK;
+}
+
+}  // namespace umx
+
 extern "C" {
 
 void umx_train_options_solo(umx_train_options* o) {
@@ -1886,35 +1944,12 @@ int umx_train_step(umx_trainer* tr, const float* data, const float* labels, cons
 
 int umx_trainer_eval(umx_trainer* tr, const float* data, float* probs_host) {
     if (!tr || !data || !probs_host) return tfail(tr, UMX_ERR_INVALID, "null argument");
-    T_HIP(tr, hipSetDevice(tr->device));
-    T_TRY(fold_profile(tr));
+    T_TRY(umx::trainer_eval_begin(tr));
     const size_t npx = (size_t)tr->B * tr->P * tr->P;
-    float* own = tr->ds[0];
-    // the range flag is shared with the training steps: what is up now belongs to a step whose loss was not read yet -- remember it
-    // for umx_trainer_loss, so that the flag this pass raises (repack + split-precision forward) is this pass's own
-    unsigned before = 0, flag = 0;
-    T_HIP(tr, hipMemcpyAsync(&before, tr->d_maxw + tr->n_maxw, sizeof before, hipMemcpyDeviceToHost, tr->stream));
-    T_HIP(tr, hipStreamSynchronize(tr->stream));
-    if (before) {
-        tr->range_pending = true;
-        T_HIP(tr, hipMemsetAsync(tr->d_maxw + tr->n_maxw, 0, sizeof(unsigned), tr->stream));   // (in the order of the work that can raise the flag)
-    }
-    T_HIP(tr, hipMemcpyAsync(own, data, npx * tr->n[0] * sizeof(float), hipMemcpyHostToDevice, tr->stream));
-    T_TRY(pack_all(tr, tr->stream, 0));
-    const int rc = tr->legacy ? forward_legacy(tr, own, false, false) : forward_pass(tr, own, false, false);
-    tr->ds[0] = own;
-    T_TRY(rc);
-    if (tr->legacy) T_HIP(tr, launch_softmax_only(tr->lt_z, tr->ident_k, npx, tr->K, tr->d_probs, tr->stream));
-    else T_HIP(tr, launch_softmax_only(tr->bn_t.z, tr->bn_t.stat, npx, tr->K, tr->d_probs, tr->stream));
+    T_HIP(tr, hipMemcpyAsync(tr->ds[0], data, npx * tr->n[0] * sizeof(float), hipMemcpyHostToDevice, tr->stream));
+    T_TRY(umx::trainer_eval_forward(tr));
     T_HIP(tr, hipMemcpyAsync(probs_host, tr->d_probs, npx * tr->K * sizeof(float), hipMemcpyDeviceToHost, tr->stream));
-    T_HIP(tr, hipMemcpyAsync(&flag, tr->d_maxw + tr->n_maxw, sizeof flag, hipMemcpyDeviceToHost, tr->stream));
-    T_HIP(tr, hipStreamSynchronize(tr->stream));
-    if (flag) {
-        T_HIP(tr, hipMemsetAsync(tr->d_maxw + tr->n_maxw, 0, sizeof(unsigned), tr->stream));   // (in the order of the work that can raise the flag)
-        return tfail(tr, UMX_ERR_RANGE, "an operand of the split-precision forward pass of umx_trainer_eval left the binary16 range (|v| >= 6e4 or "
-                                        "not finite): the probabilities are not valid; UMX_TRAIN_CONV_F32=1 selects the exact-fp32 kernels");
-    }
-    return UMX_OK;
+    return umx::trainer_eval_end(tr);
 }
 
 int umx_trainer_read(umx_trainer* tr, int which, float* out, size_t n_floats) {

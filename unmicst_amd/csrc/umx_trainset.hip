@@ -1,0 +1,407 @@
+// libumx device-resident training set: storage, the two kernels that feed the training step from it, and the C ABI of the
+// umx_trainset_* / umx_train_step_sampled / umx_trainer_assemble / umx_trainer_evaluate entries of include/umx_train.h.
+//
+// The set is the reference's annotated layout (I%05d_Img.tif pages, _Ant.tif class codes, _wt.tif contour-intersection map;
+// UnMicst1-5.py:295-312, UnMicst2.py:293-309, UnMicst.py:236-243) uploaded once, already normalised.  A step then costs 32 bytes
+// of descriptors per image (passed as kernel arguments) and one small kernel that writes the step's own data / labels / weights
+// buffers; the validation pass reduces the eval-mode softmax to exact per-class counts on the device.  DESIGN.md section 9.2.
+//
+//   assemble_batch_kernel  data[b,y,x,c] = float32((double)v * contrast + brightness) at the transformed crop coordinate;
+//                          labels[b,y,x,k] = (code == k+1); weights[b,y,x,k] = float32((double)iw[k] * wmap + cw[k])
+//   class_counts_kernel    per block: correct / labelled per class (int64) and sum of -log p[label] (float64), fixed order;
+//   class_counts_final     one block sums the block partials in a fixed order
+#include "../../include/umx_train.h"
+#include "umx_internal.h"
+#include "umx_kernels.h"
+
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+using namespace umx;
+
+static_assert(sizeof(umx_sample_desc) == 32, "umx_sample_desc is 32 bytes");
+static_assert(sizeof(umx_label_weights) == 4 + 8 * 4 + 8 * 4 + 7 * 4, "umx_label_weights layout");
+static_assert(sizeof(DescChunk) <= 2048, "a descriptor chunk travels as kernel arguments");
+
+struct umx_trainset {
+    umx_trainer* tr = nullptr;
+    int N = 0, pages = 0, S = 0, C = 0, K = 0, row_f = 0, row_a = 0;
+    bool weighted = false;
+    umx_label_weights lw;
+    float* planes = nullptr;
+    uint8_t* ann = nullptr;
+    float* wmap = nullptr;
+    double* part = nullptr;             // class_counts workspace (B P^2 pixels at most)
+    long long* counts = nullptr;        // [2K]
+    double* loss = nullptr;             // [1]
+    std::vector<void*> allocs;
+};
+
+namespace umx {
+
+namespace {
+
+constexpr int kCountThreads = 256;
+constexpr int kMaxClasses = 8;       // umx_trainer_create: nClasses 1..8
+constexpr int kMaxCountBlocks = 1024;
+
+// float32(a * b + c) with the product and the sum rounded in float64, never fused into one fma (HIP's __dmul_rn / __dadd_rn are plain
+// operators that the default -ffp-contract=fast fuses): what numpy computes for (a * b + c).astype(float32) on float64 operands
+__device__ inline float mul_add_f64_rn(double a, double b, double c) {
+#pragma clang fp contract(off)
+    return (float)(a * b + c);
+}
+
+// one thread per output pixel (y, x) of image blockIdx.y of the chunk; every thread writes its C data, K label and K weight
+// values, so a wave stores one contiguous run of the NHWC outputs.  The source pixel is read through L2: a transform that swaps
+// the axes reads a column of the crop per wave (S floats apart), which at these sizes (a few MB per step) is not worth an LDS
+// transpose.
+__global__ void __launch_bounds__(256) assemble_batch_kernel(TrainSetView ts, DescChunk dc, int b0, int P, int K,
+                                                             float* __restrict__ data, float* __restrict__ labels,
+                                                             float* __restrict__ weights) {
+    const int j = blockIdx.y;
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= P * P) return;
+    const umx_sample_desc d = dc.d[j];
+    const size_t o = (size_t)(b0 + j) * P * P + pix;
+    float* dp = data + o * ts.C;
+    float* lp = labels + o * K;
+    float* wp = weights ? weights + o * K : nullptr;
+    if (d.index < 0) {   // padding row
+        for (int c = 0; c < ts.C; ++c) dp[c] = 0.f;
+        for (int k = 0; k < K; ++k) lp[k] = 0.f;
+        if (wp)
+            for (int k = 0; k < K; ++k) wp[k] = 0.f;
+        return;
+    }
+    const int y = pix / P, x = pix - (pix / P) * P;
+    // the dihedral transform of the P x P crop: bit 2 swaps the axes, then bit 1 flips the rows, then bit 0 flips the columns;
+    // out[y, x] therefore reads crop[sy, sx] with (u, v) = (flipped y, flipped x) and (sy, sx) = swap ? (v, u) : (u, v)
+    const int u = (d.transform & 2) ? P - 1 - y : y;
+    const int v = (d.transform & 1) ? P - 1 - x : x;
+    const int sy = d.y0 + ((d.transform & 4) ? v : u);
+    const int sx = d.x0 + ((d.transform & 4) ? u : v);
+    const size_t plane = (size_t)ts.S * ts.row_f;
+    const float* src = ts.planes + ((size_t)d.index * ts.C * ts.pages + d.page) * plane + (size_t)sy * ts.row_f + sx;
+    const double cont = (double)d.contrast, brig = (double)d.brightness;
+    // float64 product and sum, one rounding to float32 (the reference jitters its float64 arrays, UnMicst1-5.py:473-477)
+    for (int c = 0; c < ts.C; ++c) dp[c] = mul_add_f64_rn((double)src[(size_t)c * ts.pages * plane], cont, brig);
+    const int code = ts.ann[((size_t)d.index * ts.S + sy) * ts.row_a + sx];
+    for (int k = 0; k < K; ++k) lp[k] = code == k + 1 ? 1.f : 0.f;   // (im == i + 1), UnMicst1-5.py:306
+    if (wp) {
+        const double w = (double)ts.wmap[((size_t)d.index * ts.S + sy) * ts.row_f + sx];
+        for (int k = 0; k < K; ++k)   // W * intersectWeight + classWeight, UnMicst1-5.py:307-312
+            wp[k] = mul_add_f64_rn((double)ts.iw[k], w, (double)ts.cw[k]);
+    }
+}
+
+int count_blocks(size_t npix) {
+    const size_t per = (size_t)kCountThreads * 8;
+    return (int)std::min<size_t>(kMaxCountBlocks, std::max<size_t>(1, (npix + per - 1) / per));
+}
+
+// the block's values of 2K + 1 quantities summed over its threads by a tree in LDS (fixed order), thread 0 writes them
+template <typename T>
+__device__ T block_sum(T v, T* sm) {
+    const int t = threadIdx.x;
+    __syncthreads();
+    sm[t] = v;
+    __syncthreads();
+    for (int s = kCountThreads / 2; s > 0; s >>= 1) {
+        if (t < s) sm[t] += sm[t + s];
+        __syncthreads();
+    }
+    return sm[0];
+}
+
+// part: [gridDim.x][2K + 1] doubles -- the int64 counts stored as their bit patterns, then the loss
+__global__ void __launch_bounds__(kCountThreads) class_counts_kernel(const float* __restrict__ probs, const float* __restrict__ labels,
+                                                                     size_t npix, int K, double* __restrict__ part) {
+    __shared__ long long smi[kCountThreads];
+    __shared__ double smd[kCountThreads];
+    const size_t rpb = (npix + gridDim.x - 1) / gridDim.x;
+    const size_t r0 = (size_t)blockIdx.x * rpb, r1 = std::min(npix, r0 + rpb);
+    int correct[kMaxClasses], labelled[kMaxClasses];
+#pragma unroll
+    for (int k = 0; k < kMaxClasses; ++k) correct[k] = labelled[k] = 0;
+    double loss = 0.0;
+    for (size_t r = r0 + threadIdx.x; r < r1; r += kCountThreads) {
+        const float* p = probs + r * K;
+        const float* l = labels + r * K;
+        int lab = -1, arg = 0;
+        float best = p[0];
+        for (int k = 0; k < K; ++k) {
+            if (lab < 0 && l[k] != 0.f) lab = k;
+            if (k > 0 && p[k] > best) { best = p[k]; arg = k; }   // first maximum (tf.argmax)
+        }
+        if (lab < 0) continue;   // code 0 / above K: an all-zero label row is no pixel of any class
+#pragma unroll
+        for (int k = 0; k < kMaxClasses; ++k)
+            if (k == lab) { labelled[k] += 1; correct[k] += arg == k; }
+        loss += -log((double)p[lab]);
+    }
+    double* out = part + (size_t)blockIdx.x * (2 * K + 1);
+#pragma unroll
+    for (int k = 0; k < kMaxClasses; ++k)
+        if (k < K) {
+            const long long c = block_sum<long long>(correct[k], smi);
+            const long long n = block_sum<long long>(labelled[k], smi);
+            if (threadIdx.x == 0) { out[k] = __longlong_as_double(c); out[K + k] = __longlong_as_double(n); }
+        }
+    const double ls = block_sum<double>(loss, smd);
+    if (threadIdx.x == 0) out[2 * K] = ls;
+}
+
+__global__ void __launch_bounds__(kCountThreads) class_counts_final(const double* __restrict__ part, int nblk, int K,
+                                                                    long long* __restrict__ counts, double* __restrict__ loss) {
+    __shared__ long long smi[kCountThreads];
+    __shared__ double smd[kCountThreads];
+    for (int q = 0; q < 2 * K; ++q) {
+        long long s = 0;
+        for (int g = threadIdx.x; g < nblk; g += kCountThreads) s += __double_as_longlong(part[(size_t)g * (2 * K + 1) + q]);
+        s = block_sum<long long>(s, smi);
+        if (threadIdx.x == 0) counts[q] = s;
+    }
+    double s = 0.0;
+    for (int g = threadIdx.x; g < nblk; g += kCountThreads) s += part[(size_t)g * (2 * K + 1) + 2 * K];
+    s = block_sum<double>(s, smd);
+    if (threadIdx.x == 0) *loss = s;
+}
+
+}  // namespace
+
+hipError_t launch_assemble_batch(const TrainSetView& ts, const DescChunk& dc, int m, int b0, int P, int K, float* data, float* labels,
+                                 float* weights, hipStream_t stream) {
+    if (m < 1 || m > kDescChunk || K < 1 || K > 8) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(assemble_batch_kernel, dim3((unsigned)((P * P + 255) / 256), (unsigned)m), dim3(256), 0, stream, ts, dc, b0, P, K,
+                       data, labels, weights);
+    return hipGetLastError();
+}
+
+size_t class_counts_parts(size_t npix, int K) { return (size_t)count_blocks(npix) * (2 * K + 1); }
+
+hipError_t launch_class_counts(const float* probs, const float* labels, size_t npix, int K, double* part, long long* counts,
+                               double* loss, hipStream_t stream) {
+    if (K < 1 || K > kMaxClasses || npix == 0) return hipErrorInvalidValue;
+    const int nblk = count_blocks(npix);
+    hipLaunchKernelGGL(class_counts_kernel, dim3((unsigned)nblk), dim3(kCountThreads), 0, stream, probs, labels, npix, K, part);
+    hipLaunchKernelGGL(class_counts_final, dim3(1), dim3(kCountThreads), 0, stream, part, nblk, K, counts, loss);
+    return hipGetLastError();
+}
+
+}  // namespace umx
+
+namespace {
+
+int tsfail(umx_trainer* tr, int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return trainer_fail(tr, code, buf);
+}
+
+#define TS_HIP(tr, call)                                                                                   \
+    do {                                                                                                   \
+        hipError_t e_ = (call);                                                                            \
+        if (e_ != hipSuccess)                                                                              \
+            return tsfail(tr, e_ == hipErrorOutOfMemory ? UMX_ERR_OOM : UMX_ERR_HIP, "%s failed: %s", #call, \
+                          hipGetErrorString(e_));                                                          \
+    } while (0)
+#define TS_TRY(call)                   \
+    do {                               \
+        int rc_ = (call);              \
+        if (rc_ != UMX_OK) return rc_; \
+    } while (0)
+
+template <typename T>
+int ts_alloc(umx_trainset* ts, T** out, size_t count) {
+    void* d = nullptr;
+    TS_HIP(ts->tr, hipMalloc(&d, std::max<size_t>(16, count * sizeof(T))));
+    ts->allocs.push_back(d);
+    *out = reinterpret_cast<T*>(d);
+    return UMX_OK;
+}
+
+TrainSetView view_of(const umx_trainset* ts) {
+    TrainSetView v;
+    v.planes = ts->planes; v.ann = ts->ann; v.wmap = ts->wmap;
+    v.S = ts->S; v.pages = ts->pages; v.C = ts->C; v.row_f = ts->row_f; v.row_a = ts->row_a;
+    for (int k = 0; k < 8; ++k) { v.cw[k] = ts->lw.class_weight[k]; v.iw[k] = ts->lw.intersect_weight[k]; }
+    return v;
+}
+
+// every descriptor checked on the host before anything is enqueued (the kernel trusts them: its reads stay inside the sample)
+int check_descs(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, int n, int n_max, const char* what) {
+    if (!tr || !ts || !desc) return tsfail(tr, UMX_ERR_INVALID, "null argument");
+    if (ts->tr != tr) return tsfail(tr, UMX_ERR_INVALID, "%s: the training set belongs to another trainer", what);
+    const TrainerIO io = trainer_io(tr);
+    if (n < 1 || n > n_max) return tsfail(tr, UMX_ERR_INVALID, "%s: %d descriptors, the batch holds 1..%d", what, n, n_max);
+    for (int i = 0; i < n; ++i) {
+        const umx_sample_desc& d = desc[i];
+        const char* why = nullptr;
+        if (d.index < 0 || d.index >= ts->N) why = "sample index out of range";
+        else if (d.page < 0 || d.page >= ts->pages) why = "page out of range";
+        else if (d.y0 < 0 || d.x0 < 0 || d.y0 > ts->S - io.P || d.x0 > ts->S - io.P) why = "crop outside the sample";
+        else if (d.transform < 0 || d.transform > 7) why = "transform outside 0..7";
+        else if (!std::isfinite(d.brightness) || !std::isfinite(d.contrast)) why = "brightness / contrast not finite";
+        else if (d.reserved != 0) why = "reserved field not zero";
+        if (why)
+            return tsfail(tr, UMX_ERR_INVALID, "%s: descriptor %d (index %d, page %d, crop %d,%d, transform %d): %s", what, i, d.index, d.page,
+                          d.y0, d.x0, d.transform, why);
+    }
+    return UMX_OK;
+}
+
+// rows 0..n-1 from desc, rows n..B-1 zero; weights written only when `weights`
+int enqueue_assemble(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, int n, bool weights) {
+    const TrainerIO io = trainer_io(tr);
+    const TrainSetView v = view_of(ts);
+    for (int b0 = 0; b0 < io.B; b0 += kDescChunk) {
+        const int m = std::min(kDescChunk, io.B - b0);
+        DescChunk dc;
+        memset(&dc, 0, sizeof dc);
+        for (int j = 0; j < m; ++j) {
+            if (b0 + j < n) dc.d[j] = desc[b0 + j];
+            else dc.d[j].index = -1;
+        }
+        TS_HIP(tr, launch_assemble_batch(v, dc, m, b0, io.P, io.K, io.data, io.labels, weights ? io.weights : nullptr, io.stream));
+    }
+    return UMX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int umx_trainset_create(umx_trainer* tr, int n_samples, int n_pages, int size, const umx_label_weights* lw, umx_trainset** out) {
+    if (!tr || !lw || !out) return tsfail(tr, UMX_ERR_INVALID, "null argument");
+    *out = nullptr;
+    const TrainerIO io = trainer_io(tr);
+    if (n_samples < 1 || n_pages < 1) return tsfail(tr, UMX_ERR_INVALID, "a training set needs at least one sample and one page");
+    if (size < io.P || size > 65536)
+        return tsfail(tr, UMX_ERR_INVALID, "samples of %d pixels: the trainer's tile is %d (size must be imSize .. 65536)", size, io.P);
+    for (int i = 0; i < 7; ++i)
+        if (lw->reserved[i]) return tsfail(tr, UMX_ERR_INVALID, "umx_label_weights.reserved must be zero");
+    if (lw->weighted != 0 && lw->weighted != 1) return tsfail(tr, UMX_ERR_INVALID, "umx_label_weights.weighted must be 0 or 1");
+    if (!lw->weighted && !io.legacy)
+        return tsfail(tr, UMX_ERR_INVALID, "the v2 graph has no unweighted loss: give the set class / intersect weights");
+    for (int k = 0; k < 8; ++k)
+        if (!std::isfinite(lw->class_weight[k]) || !std::isfinite(lw->intersect_weight[k]))
+            return tsfail(tr, UMX_ERR_INVALID, "class / intersect weights must be finite");
+    umx_trainset* ts = new umx_trainset();
+    ts->tr = tr;
+    ts->N = n_samples; ts->pages = n_pages; ts->S = size; ts->C = io.C; ts->K = io.K;
+    ts->row_f = (size + 3) & ~3;        // 16-byte rows
+    ts->row_a = (size + 15) & ~15;
+    ts->weighted = lw->weighted != 0;
+    ts->lw = *lw;
+    const size_t px_f = (size_t)n_samples * size * ts->row_f, px_a = (size_t)n_samples * size * ts->row_a;
+    const size_t bytes = px_f * 4 * io.C * n_pages + px_a + (ts->weighted ? px_f * 4 : 0);
+    size_t free_b = 0, total_b = 0;
+    int rc = umx_device_mem_info(io.device, &free_b, &total_b);
+    if (rc != UMX_OK) rc = tsfail(tr, rc, "%s", umx_last_error(nullptr));
+    else if (bytes > free_b)
+        rc = tsfail(tr, UMX_ERR_OOM, "a training set of %d samples of %d x %d (%d channels x %d pages) needs %.1f MB, %.1f MB are free", n_samples,
+                    size, size, io.C, n_pages, bytes / 1e6, free_b / 1e6);
+    if (rc == UMX_OK) rc = hipSetDevice(io.device) == hipSuccess ? UMX_OK : tsfail(tr, UMX_ERR_HIP, "hipSetDevice failed");
+    if (rc == UMX_OK) rc = ts_alloc(ts, &ts->planes, px_f * io.C * n_pages);
+    if (rc == UMX_OK) rc = ts_alloc(ts, &ts->ann, px_a);
+    if (rc == UMX_OK && ts->weighted) rc = ts_alloc(ts, &ts->wmap, px_f);
+    if (rc == UMX_OK) rc = ts_alloc(ts, &ts->part, class_counts_parts((size_t)io.B * io.P * io.P, io.K));
+    if (rc == UMX_OK) rc = ts_alloc(ts, &ts->counts, 2 * (size_t)io.K);
+    if (rc == UMX_OK) rc = ts_alloc(ts, &ts->loss, 1);
+    if (rc != UMX_OK) {
+        umx_trainset_destroy(ts);
+        return rc;
+    }
+    *out = ts;
+    return UMX_OK;
+}
+
+int umx_trainset_set(umx_trainset* ts, int index, const float* planes, const uint8_t* annotation, const float* weight_map) {
+    if (!ts) return tsfail(nullptr, UMX_ERR_INVALID, "null training set");
+    umx_trainer* tr = ts->tr;
+    if (!planes || !annotation) return tsfail(tr, UMX_ERR_INVALID, "null argument");
+    if (index < 0 || index >= ts->N) return tsfail(tr, UMX_ERR_INVALID, "sample %d of a set of %d", index, ts->N);
+    const TrainerIO io = trainer_io(tr);
+    const size_t S = ts->S, plane = S * ts->row_f;
+    TS_HIP(tr, hipSetDevice(io.device));
+    TS_HIP(tr, hipStreamSynchronize(io.stream));   // (a step in flight may still read the set)
+    const int np = ts->C * ts->pages;
+    TS_HIP(tr, hipMemcpy2DAsync(ts->planes + (size_t)index * np * plane, ts->row_f * sizeof(float), planes, S * sizeof(float),
+                                S * sizeof(float), S * np, hipMemcpyHostToDevice, io.stream));
+    TS_HIP(tr, hipMemcpy2DAsync(ts->ann + (size_t)index * S * ts->row_a, ts->row_a, annotation, S, S, S, hipMemcpyHostToDevice, io.stream));
+    if (ts->weighted) {   // (an unweighted set has no map to keep)
+        float* dst = ts->wmap + (size_t)index * plane;
+        if (weight_map)
+            TS_HIP(tr, hipMemcpy2DAsync(dst, ts->row_f * sizeof(float), weight_map, S * sizeof(float), S * sizeof(float), S,
+                                        hipMemcpyHostToDevice, io.stream));
+        else
+            TS_HIP(tr, hipMemsetAsync(dst, 0, plane * sizeof(float), io.stream));   // a missing map counts as 0
+    }
+    TS_HIP(tr, hipStreamSynchronize(io.stream));
+    return UMX_OK;
+}
+
+void umx_trainset_destroy(umx_trainset* ts) {
+    if (!ts) return;
+    if (!ts->allocs.empty()) {
+        const TrainerIO io = trainer_io(ts->tr);
+        (void)hipSetDevice(io.device);
+        (void)hipStreamSynchronize(io.stream);
+        for (void* p : ts->allocs) (void)hipFree(p);
+    }
+    delete ts;
+}
+
+int umx_train_step_sampled(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, int apply_update) {
+    if (!tr) return tsfail(nullptr, UMX_ERR_INVALID, "null trainer");
+    const TrainerIO io = trainer_io(tr);
+    TS_TRY(check_descs(tr, ts, desc, io.B, io.B, "umx_train_step_sampled"));
+    TS_HIP(tr, hipSetDevice(io.device));
+    TS_TRY(enqueue_assemble(tr, ts, desc, io.B, ts->weighted));
+    return umx_train_step_dev(tr, io.data, io.labels, ts->weighted ? io.weights : nullptr, apply_update);
+}
+
+int umx_trainer_assemble(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, int n, float* data, float* labels,
+                         float* weights) {
+    if (!tr) return tsfail(nullptr, UMX_ERR_INVALID, "null trainer");
+    const TrainerIO io = trainer_io(tr);
+    TS_TRY(check_descs(tr, ts, desc, n, io.B, "umx_trainer_assemble"));
+    if (!data || !labels) return tsfail(tr, UMX_ERR_INVALID, "null argument");
+    TS_HIP(tr, hipSetDevice(io.device));
+    TS_TRY(enqueue_assemble(tr, ts, desc, n, ts->weighted));
+    const size_t npx = (size_t)n * io.P * io.P;
+    TS_HIP(tr, hipMemcpyAsync(data, io.data, npx * io.C * sizeof(float), hipMemcpyDeviceToHost, io.stream));
+    TS_HIP(tr, hipMemcpyAsync(labels, io.labels, npx * io.K * sizeof(float), hipMemcpyDeviceToHost, io.stream));
+    if (weights && ts->weighted)
+        TS_HIP(tr, hipMemcpyAsync(weights, io.weights, npx * io.K * sizeof(float), hipMemcpyDeviceToHost, io.stream));
+    TS_HIP(tr, hipStreamSynchronize(io.stream));
+    return UMX_OK;
+}
+
+int umx_trainer_evaluate(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, int n, int64_t* counts, double* loss_sum) {
+    if (!tr) return tsfail(nullptr, UMX_ERR_INVALID, "null trainer");
+    const TrainerIO io = trainer_io(tr);
+    TS_TRY(check_descs(tr, ts, desc, n, io.B, "umx_trainer_evaluate"));
+    if (!counts || !loss_sum) return tsfail(tr, UMX_ERR_INVALID, "null argument");
+    TS_TRY(trainer_eval_begin(tr));
+    TS_TRY(enqueue_assemble(tr, ts, desc, n, false));
+    TS_TRY(trainer_eval_forward(tr));
+    TS_HIP(tr, launch_class_counts(io.probs, io.labels, (size_t)n * io.P * io.P, io.K, ts->part, ts->counts, ts->loss, io.stream));
+    long long c[2 * kMaxClasses];
+    double l = 0.0;
+    TS_HIP(tr, hipMemcpyAsync(c, ts->counts, 2 * io.K * sizeof(long long), hipMemcpyDeviceToHost, io.stream));
+    TS_HIP(tr, hipMemcpyAsync(&l, ts->loss, sizeof l, hipMemcpyDeviceToHost, io.stream));
+    TS_TRY(trainer_eval_end(tr));
+    for (int q = 0; q < 2 * io.K; ++q) counts[q] = c[q];
+    *loss_sum = l;
+    return UMX_OK;
+}
+
+}  // extern "C"

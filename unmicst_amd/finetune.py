@@ -1,0 +1,154 @@
+"""Fine-tune a model on an annotated training set:
+
+    python -m unmicst_amd.finetune --model NAME|DIR --train DIR --valid DIR --out DIR [--steps N] [--batch B] [--pages A]
+                                   [--eval-every E] [--seed S] [--lr0 LR] [--transforms] [--device D]
+
+``--train`` / ``--valid`` hold the reference's published layout (``I%05d_Img.tif`` / ``_Ant.tif`` / ``_wt.tif``, see
+unmicst_amd/trainset.py).  Both sets are uploaded to the device once; each step draws its batch with ``Sampler`` and trains with
+``Trainer.step_sampled`` under the reference trainer's regime for the model's graph (legacy / solo / duo options, label weights
+and jitter).  Every ``--eval-every`` steps the whole validation set is evaluated on the device; the checkpoint with the lowest mean
+per-class pixel error is written to ``<out>/umx_model.npz`` with the base model's normalisation mean / std, so
+``UnMicst.py --model <out>`` runs on it, and every evaluation is one line of ``<out>/finetune_log.jsonl``.
+
+The run is a function of its arguments: the same seed gives the same descriptor stream, the same steps and the same files.
+There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import os
+import sys
+
+import numpy as np
+
+from . import model, trainer, trainset, umx
+
+LOG_NAME = "finetune_log.jsonl"
+
+
+class Refusal(Exception):
+    """An input the command does not take (reported before any device work)."""
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog="python -m unmicst_amd.finetune", description=__doc__.split("\n\n")[0])
+    p.add_argument("--model", required=True, help="model name under models/ (UMX_MODELS_DIR) or a model directory")
+    p.add_argument("--train", required=True, help="training set directory (I%%05d_Img.tif / _Ant.tif / _wt.tif)")
+    p.add_argument("--valid", required=True, help="validation set directory, same layout")
+    p.add_argument("--out", required=True, help="output model directory (umx_model.npz + finetune_log.jsonl)")
+    p.add_argument("--steps", type=int, default=1000)
+    p.add_argument("--batch", type=int, default=0, help="images per step (0: the model's batchSize)")
+    p.add_argument("--pages", type=int, default=1, help="augmentation pages per channel in the _Img.tif files")
+    p.add_argument("--eval-every", type=int, default=100)
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--lr0", type=float, default=None, help="initial learning rate (default: the graph's trainer)")
+    p.add_argument("--transforms", action="store_true", help="draw one of the 8 dihedral transforms per image")
+    p.add_argument("--device", type=int, default=0)
+    return p
+
+
+def resolve_model(name: str) -> str:
+    """As the drivers do (driver.run): a directory as given, else <repository>/models/<name> (UMX_MODELS_DIR overrides)."""
+    if os.path.isdir(name):
+        return name
+    from .driver import models_root
+    return os.path.join(models_root(os.path.dirname(os.path.dirname(os.path.realpath(__file__)))), name)
+
+
+def options_for(kind: str, seed: int, lr0=None) -> trainer.TrainOptions:
+    make = {"legacy": trainer.legacy_options, "solo": trainer.solo_options, "duo": trainer.duo_options}[kind]
+    kw = {"seed": int(seed)}
+    if lr0 is not None:
+        kw["lr0"] = float(lr0)
+    return make(**kw)
+
+
+def prepare(args):
+    """Everything that needs no device: the model, both sets read and checked.  Raises Refusal."""
+    if args.steps < 1 or args.eval_every < 1 or args.pages < 1 or args.batch < 0:
+        raise Refusal("--steps, --eval-every and --pages must be positive, --batch non-negative")
+    path = resolve_model(args.model)
+    if not os.path.isdir(path):
+        raise Refusal("model %s: no such directory (%s)" % (args.model, path))
+    for what, d in (("--train", args.train), ("--valid", args.valid)):
+        if not os.path.isdir(d):
+            raise Refusal("%s %s: no such directory" % (what, d))
+        if not trainset.dataset_indices(d):
+            raise Refusal("%s %s holds no I%%05d_Img.tif samples" % (what, d))
+    try:
+        art = model.load_model_dir(path)
+    except FileNotFoundError as e:
+        raise Refusal("model %s has no weights to fine-tune: %s" % (args.model, e))
+    hp = art.hp
+    sets = []
+    for what, d in (("--train", args.train), ("--valid", args.valid)):
+        try:
+            ds = trainset.read_dataset_dir(d, args.pages, hp.nChannels, art.mean, art.std)
+        except ValueError as e:
+            raise Refusal("%s: %s (the model takes %d channel(s), --pages is %d)" % (what, e, hp.nChannels, args.pages))
+        if ds.size < hp.imSize:
+            raise Refusal("%s: samples are %d x %d, smaller than the model's %d x %d tile" % (what, ds.size, ds.size, hp.imSize,
+                                                                                         hp.imSize))
+        sets.append(ds)
+    return art, sets[0], sets[1]
+
+
+def run(args) -> int:
+    art, train_ds, valid_ds = prepare(args)
+    hp = art.hp
+    kind = trainset.graph_kind(hp)
+    lw = trainset.LABEL_WEIGHTS[kind]
+    tr = trainer.Trainer(hp, art.blob, options_for(kind, args.seed, args.lr0), batch=args.batch, device=args.device)
+    try:
+        ts = trainset.upload(tr, train_ds, lw)
+        vs = trainset.upload(tr, valid_ds, lw)
+        mb, mc = trainset.default_jitter(kind, art.std)
+        sampler = trainset.Sampler(args.seed, train_ds.n_samples, tr.batch, train_ds.size, hp.imSize, args.pages, mb, mc,
+                                   transforms=args.transforms)
+        vdesc = trainset.validation_descriptors(valid_ds.n_samples, valid_ds.size, hp.imSize)
+        os.makedirs(args.out, exist_ok=True)
+        log_path = os.path.join(args.out, LOG_NAME)
+        best = None
+        train_loss = None
+        with open(log_path, "w") as log:
+            for step in range(args.steps + 1):
+                if step % args.eval_every == 0 or step == args.steps:
+                    ev = tr.evaluate(vs, vdesc)
+                    err = [None if math.isnan(e) else float(e) for e in ev["per_class_error"]]
+                    seen = [e for e in err if e is not None]
+                    mean_err = float(np.mean(seen)) if seen else float("nan")
+                    rec = {"step": step, "train_loss": train_loss, "loss": ev["loss"], "per_class_error": err, "mean_error": mean_err,
+                           "labelled": [int(v) for v in ev["counts"][1]]}
+                    log.write(json.dumps(rec) + "\n")
+                    log.flush()
+                    print("step %d: validation loss %.6g, per-class error %s" % (step, ev["loss"], err), flush=True)
+                    if best is None or mean_err < best[0]:
+                        best = (mean_err, step)
+                        model.save_converted(model.ModelArtefacts(hp, tr.blob(), art.mean, art.std), args.out)
+                if step == args.steps:
+                    break
+                tr.step_sampled(ts, sampler.next())
+                if (step + 1) % args.eval_every == 0 or step + 1 == args.steps:
+                    train_loss = tr.loss()[0]
+        print("best mean per-class error %.6g at step %d -> %s" % (best[0], best[1], os.path.join(args.out, model.CONVERTED_NAME)))
+    finally:
+        tr.close()
+    return 0
+
+
+def main(argv=None) -> int:
+    args = build_parser().parse_args(argv)
+    try:
+        return run(args)
+    except Refusal as e:
+        print("finetune: error: %s" % e, file=sys.stderr)
+        return 2
+    except umx.UmxError as e:
+        print("finetune: error: %s" % e, file=sys.stderr)
+        return 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -28,7 +28,8 @@ EXPORTS = [
     "umx_train_options_solo", "umx_train_options_duo", "umx_train_options_legacy", "umx_trainer_create", "umx_trainer_destroy",
     "umx_trainer_last_error", "umx_train_step", "umx_train_step_dev", "umx_trainer_loss", "umx_trainer_read",
     "umx_trainer_probs", "umx_trainer_read_tensor", "umx_trainer_eval", "umx_trainer_step_count", "umx_trainer_batch", "umx_trainer_flops_per_image",
-    "umx_trainer_profile",
+    "umx_trainer_profile", "umx_trainset_create", "umx_trainset_set", "umx_trainset_destroy", "umx_train_step_sampled",
+    "umx_trainer_assemble", "umx_trainer_evaluate",
 ]
 
 
@@ -66,6 +67,17 @@ class TrainOptions:
     drop_up_step: float = 0.0
     bn_momentum: float = 0.99
     seed: int = 1234
+
+
+class LabelWeightsC(ctypes.Structure):
+    """``umx_label_weights`` (include/umx_train.h)."""
+    _fields_ = [("weighted", ctypes.c_int32), ("class_weight", ctypes.c_float * 8), ("intersect_weight", ctypes.c_float * 8),
+                ("reserved", ctypes.c_int32 * 7)]
+
+
+# ``umx_sample_desc`` (include/umx_train.h): one image of a batch drawn from a training set, 32 bytes
+SAMPLE_DESC = np.dtype([("index", "<i4"), ("page", "<i4"), ("y0", "<i4"), ("x0", "<i4"), ("transform", "<i4"),
+                        ("brightness", "<f4"), ("contrast", "<f4"), ("reserved", "<i4")])
 
 
 def solo_options(**kw) -> TrainOptions:
@@ -137,6 +149,19 @@ def _bind(L):
     L.umx_trainer_flops_per_image.argtypes = [c_void_p]
     L.umx_trainer_profile.restype = c_int
     L.umx_trainer_profile.argtypes = [c_void_p, c_int, dp, dp, dp, ctypes.POINTER(c_int)]
+    # the device-resident training set (unmicst_amd/trainset.py)
+    L.umx_trainset_create.restype = c_int
+    L.umx_trainset_create.argtypes = [c_void_p, c_int, c_int, c_int, ctypes.POINTER(LabelWeightsC), ctypes.POINTER(c_void_p)]
+    L.umx_trainset_set.restype = c_int
+    L.umx_trainset_set.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p]
+    L.umx_trainset_destroy.restype = None
+    L.umx_trainset_destroy.argtypes = [c_void_p]
+    L.umx_train_step_sampled.restype = c_int
+    L.umx_train_step_sampled.argtypes = [c_void_p, c_void_p, c_void_p, c_int]
+    L.umx_trainer_assemble.restype = c_int
+    L.umx_trainer_assemble.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
+    L.umx_trainer_evaluate.restype = c_int
+    L.umx_trainer_evaluate.argtypes = [c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(ctypes.c_int64), dp]
     L._umx_train_bound = True
     return L
 
@@ -187,6 +212,8 @@ class Trainer:
 
     def close(self):
         if getattr(self, "_h", None):
+            for ts in list(getattr(self, "_sets", ())):   # a training set lives in this trainer's memory: it goes first
+                ts.close()
             self._lib.umx_trainer_destroy(self._h)
             self._h = None
 
@@ -270,6 +297,58 @@ class Trainer:
         out = np.empty((self.batch, hp.imSize, hp.imSize, hp.nClasses), np.float32)
         self._check(self._lib.umx_trainer_eval(self._h, d.ctypes.data, out.ctypes.data))
         return out
+
+    # ---- the device-resident training set (unmicst_amd/trainset.py) ----------------------------
+    def _descs(self, desc, n_max: int):
+        d = np.ascontiguousarray(desc, dtype=SAMPLE_DESC)
+        if d.ndim != 1 or not 1 <= d.size <= n_max:
+            raise ValueError("expected 1..%d descriptors (a 1-d SAMPLE_DESC array), got shape %r" % (n_max, d.shape))
+        return d
+
+    def step_sampled(self, ts, desc, apply_update: bool = True):
+        """One step on the batch that B descriptors draw from the training set ``ts`` (assembled on the device); only enqueues
+        -- call loss() to synchronise and read the loss."""
+        d = self._descs(desc, self.batch)
+        if d.size != self.batch:
+            raise ValueError("step_sampled takes exactly %d descriptors, got %d" % (self.batch, d.size))
+        self._check(self._lib.umx_train_step_sampled(self._h, ts._handle(), d.ctypes.data, int(apply_update)))
+
+    def assemble(self, ts, desc):
+        """The batch that n <= B descriptors assemble, copied to the host: (data [n,P,P,C], labels [n,P,P,K], weights or None)."""
+        hp = self.hp
+        d = self._descs(desc, self.batch)
+        n, P = d.size, hp.imSize
+        data = np.empty((n, P, P, hp.nChannels), np.float32)
+        labels = np.empty((n, P, P, hp.nClasses), np.float32)
+        weights = np.empty((n, P, P, hp.nClasses), np.float32) if ts.weighted else None
+        self._check(self._lib.umx_trainer_assemble(self._h, ts._handle(), d.ctypes.data, n, data.ctypes.data, labels.ctypes.data,
+                                                   None if weights is None else weights.ctypes.data))
+        return data, labels, weights
+
+    def evaluate(self, ts, descs) -> dict:
+        """The validation pass over any number of descriptors, B at a time (eval mode: moving statistics, no dropout):
+        {"per_class_error": 1 - correct / labelled per class (nan for a class with no pixel; UnMicst1-5.py:386-397),
+         "loss": mean -log p[label] over labelled pixels, "loss_sum": its sum, "counts": int64 [2, K] = correct | labelled}."""
+        d = np.ascontiguousarray(descs, dtype=SAMPLE_DESC).reshape(-1)
+        if d.size == 0:
+            raise ValueError("no descriptors to evaluate")
+        K = self.hp.nClasses
+        total = np.zeros(2 * K, np.int64)
+        loss_sum = 0.0
+        part = np.zeros(2 * K, np.int64)
+        ls = ctypes.c_double()
+        for b0 in range(0, d.size, self.batch):
+            chunk = np.ascontiguousarray(d[b0:b0 + self.batch])
+            self._check(self._lib.umx_trainer_evaluate(self._h, ts._handle(), chunk.ctypes.data, chunk.size,
+                                                       part.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(ls)))
+            total += part
+            loss_sum += ls.value
+        counts = total.reshape(2, K)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            err = 1.0 - counts[0] / counts[1].astype(np.float64)
+        n_lab = int(counts[1].sum())
+        return {"per_class_error": err, "loss": loss_sum / n_lab if n_lab else float("nan"), "loss_sum": loss_sum,
+                "counts": counts}
 
     @property
     def step_count(self) -> int:

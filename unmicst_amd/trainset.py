@@ -1,0 +1,314 @@
+"""A training set that lives in device memory, the sampler that draws batches from it, and the reader of the reference's
+published annotation layout.
+
+Layout (interface only; reference readers UnMicst1-5.py:295-312, UnMicst2.py:293-309, UnMicst.py:236-243), one triple per
+sample ``i`` of a directory:
+
+* ``I%05d_Img.tif``: ``n_pages x n_channels`` pages, page ``aug + n_pages * channel`` -- the extra pages are the "real
+  augmentation" z-planes;
+* ``I%05d_Ant.tif``: class codes, ``k + 1`` = class ``k`` (0 = unlabelled);
+* ``I%05d_wt.tif``: the contour-intersection weight map (optional here: a missing one counts as 0).
+
+``TrainSet`` uploads the normalised planes once (``umx_trainset_create`` / ``_set``); ``Sampler`` draws the 32-byte descriptors
+(``trainer.SAMPLE_DESC``) of each batch; ``Trainer.step_sampled`` / ``assemble`` / ``evaluate`` build the batch on the device
+(DESIGN.md section 9.2).  The labels and weights follow the reference's recipe: ``labels[k] = (code == k + 1)`` and
+``weights[k] = intersect_weight[k] * W + class_weight[k]``.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+import re
+from dataclasses import dataclass
+from typing import List, Optional, Tuple
+
+import numpy as np
+
+from . import imtools, tiffio
+from .trainer import SAMPLE_DESC, LabelWeightsC
+
+
+@dataclass(frozen=True)
+class LabelWeights:
+    """``umx_label_weights``: weighted=False is the unweighted loss (legacy graph only)."""
+    weighted: bool
+    class_weight: Tuple[float, ...] = ()
+    intersect_weight: Tuple[float, ...] = ()
+
+    def c_struct(self) -> LabelWeightsC:
+        lw = LabelWeightsC()
+        lw.weighted = int(bool(self.weighted))
+        for k, v in enumerate(self.class_weight):
+            lw.class_weight[k] = float(v)
+        for k, v in enumerate(self.intersect_weight):
+            lw.intersect_weight[k] = float(v)
+        return lw
+
+
+UNWEIGHTED = LabelWeights(False)
+
+# The reference's constants per trainer (bgWeight, contourWeight, nucleiWeight, intersectWeight and the jitter maxima):
+#   solo    UnMicst1-5.py:276-281 (weights), :464-477 (maxBrig = datasetStDev, maxCont = 0.1 datasetStDev)
+#   duo     UnMicst2.py:273-278, :453-463
+#   legacy  UnMicst.py:236-243, :343-350 -- labels only (an unweighted loss) and no jitter
+LABEL_WEIGHTS = {
+    "solo": LabelWeights(True, (1.0, 2.0, 7.0), (0.0, 15.0, 0.0)),
+    "duo": LabelWeights(True, (1.0, 2.0, 5.0), (0.0, 10.0, 0.0)),
+    "legacy": UNWEIGHTED,
+}
+
+
+def default_jitter(kind: str, std: float) -> Tuple[float, float]:
+    """(max_brightness, max_contrast) of a trainer kind, in the normalised domain: the reference adds ``maxBrig = 1 * datasetStDev``
+    and scales by ``1 +- 0.1 * datasetStDev`` after normalising (UnMicst1-5.py:464-477, UnMicst2.py:453-463); the legacy trainer
+    has no jitter."""
+    if kind == "legacy":
+        return 0.0, 0.0
+    return 1.0 * float(std), 0.1 * float(std)
+
+
+class TrainSet:
+    """``n_samples`` samples of ``size x size`` pixels with ``nChannels x n_pages`` normalised planes each, one annotation plane and
+    (weighted sets) one weight map, in the device memory of ``trainer``.  Close it (or the trainer) to free that memory."""
+
+    def __init__(self, trainer, n_samples: int, n_pages: int, size: int, label_weights: LabelWeights):
+        self.trainer = trainer
+        self.n_samples, self.n_pages, self.size = int(n_samples), int(n_pages), int(size)
+        self.label_weights = label_weights
+        self.weighted = bool(label_weights.weighted)
+        lib = trainer._lib
+        lw = label_weights.c_struct()
+        h = ctypes.c_void_p()
+        trainer._check(lib.umx_trainset_create(trainer._h, self.n_samples, self.n_pages, self.size, ctypes.byref(lw), ctypes.byref(h)))
+        self._h = h
+        self._lib = lib
+        if not hasattr(trainer, "_sets"):
+            import weakref
+            trainer._sets = weakref.WeakSet()
+        trainer._sets.add(self)
+
+    def _handle(self):
+        if not getattr(self, "_h", None):
+            raise ValueError("the training set is closed")
+        return self._h
+
+    def set(self, i: int, planes, annotation, weight_map=None) -> None:
+        """Upload sample ``i``: planes [nChannels][n_pages][size][size] (normalised, float32), annotation [size][size] class codes
+        (uint8), weight_map [size][size] or None (= 0; ignored by an unweighted set)."""
+        hp, S = self.trainer.hp, self.size
+        p = np.ascontiguousarray(planes, dtype=np.float32)
+        if p.shape != (hp.nChannels, self.n_pages, S, S):
+            raise ValueError("planes must be %r, got %r" % ((hp.nChannels, self.n_pages, S, S), p.shape))
+        a = np.asarray(annotation)
+        if a.shape != (S, S):
+            raise ValueError("annotation must be %r, got %r" % ((S, S), a.shape))
+        if a.dtype != np.uint8:
+            if a.size and (a.min() < 0 or a.max() > 255):
+                raise ValueError("annotation codes must be 0..255")
+            a = a.astype(np.uint8)
+        a = np.ascontiguousarray(a)
+        w = None
+        if weight_map is not None:
+            w = np.ascontiguousarray(weight_map, dtype=np.float32)
+            if w.shape != (S, S):
+                raise ValueError("weight_map must be %r, got %r" % ((S, S), w.shape))
+        self.trainer._check(self._lib.umx_trainset_set(self._handle(), int(i), p.ctypes.data, a.ctypes.data,
+                                                       None if w is None else w.ctypes.data))
+
+    @classmethod
+    def from_arrays(cls, trainer, planes, annotations, weight_maps=None, label_weights: LabelWeights = UNWEIGHTED) -> "TrainSet":
+        """planes [N][C][pages][S][S], annotations [N][S][S], weight_maps: None or a sequence of [S][S] arrays / None."""
+        planes = np.asarray(planes)
+        if planes.ndim != 5:
+            raise ValueError("planes must be [N][C][pages][S][S], got shape %r" % (planes.shape,))
+        n, _, pages, S, _ = planes.shape
+        ts = cls(trainer, n, pages, S, label_weights)
+        try:
+            for i in range(n):
+                ts.set(i, planes[i], annotations[i], None if weight_maps is None else weight_maps[i])
+        except BaseException:
+            ts.close()
+            raise
+        return ts
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.umx_trainset_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+@dataclass
+class Dataset:
+    """What ``read_dataset_dir`` returns: planes [N][C][pages][S][S] float32, annotations [N][S][S] uint8, weight maps (float32 or
+    None per sample)."""
+    planes: np.ndarray
+    annotations: np.ndarray
+    weight_maps: List[Optional[np.ndarray]]
+
+    @property
+    def n_samples(self) -> int:
+        return int(self.planes.shape[0])
+
+    @property
+    def size(self) -> int:
+        return int(self.planes.shape[-1])
+
+
+_IMG = re.compile(r"^I(\d{5})_Img\.tif$")
+
+
+def dataset_indices(path: str) -> List[int]:
+    """The sample numbers of a dataset directory (``I%05d_Img.tif`` files), sorted."""
+    if not os.path.isdir(path):
+        raise FileNotFoundError("%s is not a directory" % path)
+    return sorted(int(m.group(1)) for m in (_IMG.match(f) for f in os.listdir(path)) if m)
+
+
+def read_dataset_dir(path: str, n_pages: int, n_channels: int, mean: float, std: float) -> Dataset:
+    """Read every sample of the published layout and normalise it as the reference does, in float64, rounded once to float32:
+    ``(im2double(page) - mean) / std`` for page ``aug + n_pages * channel`` (UnMicst1-5.py:297-301).  Annotations keep their
+    codes; a missing ``_wt.tif`` gives None."""
+    idx = dataset_indices(path)
+    if not idx:
+        raise FileNotFoundError("%s holds no I%%05d_Img.tif samples" % path)
+    planes, anns, wmaps = [], [], []
+    size = None
+    for i in idx:
+        img = os.path.join(path, "I%05d_Img.tif" % i)
+        have = tiffio.num_pages(img)
+        if have != n_pages * n_channels:
+            raise ValueError("%s has %d pages, expected %d (%d pages x %d channels)" % (img, have, n_pages * n_channels, n_pages,
+                                                                                         n_channels))
+        p = np.empty((n_channels, n_pages), dtype=object)
+        for c in range(n_channels):
+            for a in range(n_pages):
+                im = imtools.im2double(tiffio.imread(img, key=a + n_pages * c))
+                p[c, a] = ((np.asarray(im, np.float64) - float(mean)) / float(std)).astype(np.float32)
+        shape = p[0, 0].shape
+        if len(shape) != 2 or shape[0] != shape[1]:
+            raise ValueError("%s: samples must be square, got %r" % (img, shape))
+        if size is None:
+            size = shape[0]
+        if shape[0] != size or any(q.shape != shape for q in p.flat):
+            raise ValueError("%s: every sample and page must be %d x %d" % (img, size, size))
+        planes.append(np.stack([np.stack(list(p[c])) for c in range(n_channels)]))
+        ant = tiffio.imread(os.path.join(path, "I%05d_Ant.tif" % i))
+        if ant.shape != shape:
+            raise ValueError("I%05d_Ant.tif is %r, the image %r" % (i, ant.shape, shape))
+        if ant.dtype != np.uint8:
+            if ant.min() < 0 or ant.max() > 255:
+                raise ValueError("I%05d_Ant.tif: class codes must be 0..255" % i)
+            ant = ant.astype(np.uint8)
+        anns.append(ant)
+        wt = os.path.join(path, "I%05d_wt.tif" % i)
+        if os.path.exists(wt):
+            w = tiffio.imread(wt)
+            if w.shape != shape:
+                raise ValueError("I%05d_wt.tif is %r, the image %r" % (i, w.shape, shape))
+            wmaps.append(np.asarray(w, np.float32))
+        else:
+            wmaps.append(None)
+    return Dataset(np.stack(planes), np.stack(anns), wmaps)
+
+
+class Sampler:
+    """Descriptor stream of a training run: every sample once per epoch in an order reshuffled each epoch, then per image a
+    uniform augmentation page, a uniform crop origin, optionally one of the 8 dihedral transforms, and the reference's jitter
+    (``brightness = max_brightness * (+-1) * U[0,1)``, ``contrast = 1 + max_contrast * (+-1) * U[0,1)``, UnMicst1-5.py:473-474).
+    All draws come from ``numpy.random.Generator(PCG64(seed))`` in a fixed order, so a seed fixes the stream."""
+
+    def __init__(self, seed: int, n_samples: int, batch: int, size: int, P: int, n_pages: int, max_brightness: float = 0.0,
+                 max_contrast: float = 0.0, transforms: bool = False):
+        if n_samples < 1 or batch < 1 or n_pages < 1 or size < P:
+            raise ValueError("a sampler needs samples, a batch, pages and size >= P")
+        self.rng = np.random.Generator(np.random.PCG64(seed))
+        self.n_samples, self.batch, self.size, self.P, self.n_pages = int(n_samples), int(batch), int(size), int(P), int(n_pages)
+        self.max_brightness, self.max_contrast = float(max_brightness), float(max_contrast)
+        self.transforms = bool(transforms)
+        self.epoch = 0
+        self._perm = self.rng.permutation(self.n_samples)
+        self._pos = 0
+
+    def _next_index(self) -> int:
+        if self._pos == self.n_samples:
+            self.epoch += 1
+            self._perm = self.rng.permutation(self.n_samples)
+            self._pos = 0
+        i = int(self._perm[self._pos])
+        self._pos += 1
+        return i
+
+    def next(self) -> np.ndarray:
+        """The next batch: ``batch`` descriptors (a SAMPLE_DESC array)."""
+        d = np.zeros(self.batch, SAMPLE_DESC)
+        r = self.rng
+        span = self.size - self.P + 1
+        for j in range(self.batch):
+            d["index"][j] = self._next_index()
+            d["page"][j] = r.integers(self.n_pages)
+            d["y0"][j] = r.integers(span)
+            d["x0"][j] = r.integers(span)
+            d["transform"][j] = r.integers(8) if self.transforms else 0
+            sb = -1.0 if r.random() < 0.5 else 1.0
+            d["brightness"][j] = self.max_brightness * sb * r.random() + 0.0   # (+ 0.0: no -0.0 when there is no jitter)
+            sc = -1.0 if r.random() < 0.5 else 1.0
+            d["contrast"][j] = 1.0 + self.max_contrast * sc * r.random()
+        return d
+
+    def __iter__(self):
+        while True:
+            yield self.next()
+
+    def validation_descriptors(self) -> np.ndarray:
+        return validation_descriptors(self.n_samples, self.size, self.P)
+
+
+def crop_origins(size: int, P: int) -> List[int]:
+    """Origins of the P-crops that cover 0..size-1: every P pixels, the last one flush with the far edge."""
+    o = list(range(0, size - P + 1, P))
+    if o[-1] != size - P:
+        o.append(size - P)
+    return o
+
+
+def validation_descriptors(n_samples: int, size: int, P: int) -> np.ndarray:
+    """Every sample once, covered by P-crops (page 0, no transform, no jitter)."""
+    org = crop_origins(size, P)
+    d = np.zeros(n_samples * len(org) ** 2, SAMPLE_DESC)
+    k = 0
+    for i in range(n_samples):
+        for y in org:
+            for x in org:
+                d[k] = (i, 0, y, x, 0, 0.0, 1.0, 0)
+                k += 1
+    return d
+
+
+def upload(trainer, ds: Dataset, label_weights: LabelWeights) -> TrainSet:
+    """A ``Dataset`` into the device memory of ``trainer``."""
+    return TrainSet.from_arrays(trainer, ds.planes, ds.annotations, ds.weight_maps, label_weights)
+
+
+def graph_kind(hp) -> str:
+    """Which of the reference's trainers a model's graph belongs to: legacy (UnMicst.py), solo (1 channel, UnMicst1-5.py) or
+    duo (2 channels, UnMicst2.py)."""
+    from .model import GRAPH_LEGACY
+    if hp.graph == GRAPH_LEGACY:
+        return "legacy"
+    return "solo" if hp.nChannels == 1 else "duo"
+
+
+__all__ = ["LabelWeights", "UNWEIGHTED", "LABEL_WEIGHTS", "default_jitter", "TrainSet", "Dataset", "dataset_indices",
+           "read_dataset_dir", "Sampler", "crop_origins", "validation_descriptors", "upload", "graph_kind", "SAMPLE_DESC"]
