@@ -35,7 +35,8 @@ enum umx_status {
     UMX_ERR_NO_DEVICE = 3,   /* no usable HIP device */
     UMX_ERR_HIP = 4,         /* a HIP runtime call failed */
     UMX_ERR_OOM = 5,
-    UMX_ERR_RANGE = 6        /* split-precision path only: an activation left the binary16 range (|v| >= 6e4) */
+    UMX_ERR_RANGE = 6,       /* split-precision path only: an activation left the binary16 range (|v| >= 6e4) */
+    UMX_ERR_GUARD = 7        /* debug guard mode only (UMX_DEBUG_GUARD, include/umx_train.h): a kernel wrote outside its buffer */
 };
 
 /* Arithmetic of the convolutions.  All hold the 1e-4 tolerance on the probability maps.

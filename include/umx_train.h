@@ -54,7 +54,8 @@ UMX_API void umx_train_options_legacy(umx_train_options* o); /* UnMicst.py:   Mo
 
 /* replaces UNet2D.setup + tf.global_variables_initializer / saver.restore (UnMicst1-5.py:55-237,445-449): the blob holds
  * the initial (or restored) variables incl. BN moving statistics; optimiser slots start at zero, step at 0.
- * A legacy graph with a non-zero dropout rate or reg_kind != UMX_REG_NONE is UMX_ERR_INVALID (that graph has neither). */
+ * A legacy graph with a non-zero dropout rate or reg_kind != UMX_REG_NONE is UMX_ERR_INVALID (that graph has neither), and so is
+ * nClasses < 2 (the softmax of one class is 1 everywhere: its cross-entropy has no gradient). */
 UMX_API int umx_trainer_create(const umx_hparams* hp, const float* weight_blob, size_t blob_floats,
                                const umx_train_options* opts, umx_trainer** out);
 UMX_API void umx_trainer_destroy(umx_trainer* tr);
@@ -148,6 +149,19 @@ UMX_API int umx_trainer_assemble(umx_trainer* tr, const umx_trainset* ts, const 
  * the range flag as umx_trainer_eval does. */
 UMX_API int umx_trainer_evaluate(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, int n, int64_t* counts,
                                  double* loss_sum);
+
+/* Debug guard mode.  UMX_DEBUG_GUARD=<byte> (e.g. 0xff), read by umx_trainer_create and umx_trainset_create, gives every device
+ * buffer of that trainer / set a red zone of max(64 KiB, its size rounded up to 4 KiB) on both sides.  The zones, and every buffer
+ * the library does not zero or upload, are filled with that byte, so a result that depends on the byte read memory nobody wrote.
+ * Every entry that enqueues work (umx_train_step, _step_dev, _step_sampled, umx_trainer_eval, _assemble, _evaluate,
+ * umx_trainset_set) then waits for the trainer's streams and checks every zone: UMX_ERR_GUARD names the buffer, the side and the
+ * first and last changed byte.  Slow; for tests.  Off (unset or empty), allocations and launches are exactly the normal ones.
+ *
+ * The host scan of one zone (no device needed): zone_bytes bytes that should all equal `fill`, in front of (side 0) or behind
+ * (side 1) a buffer of buf_bytes bytes named `label`.  UMX_OK if intact; else UMX_ERR_GUARD and, in msg (cap bytes, NUL-terminated),
+ * the label, the side and the first and last changed byte as offsets from the start of the buffer (negative in front of it). */
+UMX_API int umx_guard_scan(const uint8_t* zone, size_t zone_bytes, int side, size_t buf_bytes, int fill, const char* label,
+                           char* msg, size_t cap);
 
 #ifdef __cplusplus
 }

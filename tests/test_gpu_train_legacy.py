@@ -15,7 +15,9 @@ pytestmark = pytest.mark.gpu
 
 TIGHT = 2e-5
 SMALL = [("legacy_k5", 3), ("legacy_k3_x0", 4), ("legacy_k3_x2", 4)]
-ROUTES = [{}, {"UMX_TRAIN_CONV_F32": "1"}]
+# every convolution route of tests/test_gpu_train.py::ROUTES (UMX_TRAIN_* arithmetic switches)
+ROUTES = [{}, {"UMX_TRAIN_CONV_F32": "1"}, {"UMX_TRAIN_NO_KSPLIT": "1"}, {"UMX_TRAIN_WGRAD_F32": "1"},
+          {"UMX_TRAIN_CONV_F32": "1", "UMX_TRAIN_WGRAD_F32": "1"}]
 
 
 def _batch(hp, B, seed):
@@ -109,6 +111,59 @@ def test_loss_probabilities_and_gradients_match_reference(name, B, route, monkey
         assert np.abs(st[1] - 1 / np.sqrt(var + ref.BN_EPS)).max() <= 1e-5 * np.abs(st[1]).max()
     assert np.array_equal(tr.blob(), blob)
     tr.close()
+
+
+def _check_step(hp, B, blob, data, labels, weights, what):
+    """One step without update against the float64 reference on the kernels' own decisions: loss, probabilities, every gradient."""
+    tr = trainer.Trainer(hp, blob, trainer.legacy_options(), batch=B)
+    loss, data_term, reg = tr.step(data, labels, weights, apply_update=False)
+    assert reg == 0.0 and loss == data_term
+    want_loss, want_g, want_p, _ = ref.loss_and_grads(hp, blob, data, labels, weights, decisions=_decisions(tr, hp, B))
+    assert loss == pytest.approx(want_loss, rel=1e-5), what
+    assert np.abs(tr.probs() - want_p).max() <= 2e-5, what
+    _check_tight(hp, tr.grads(), want_g, what)
+    assert np.array_equal(tr.blob(), blob)
+    tr.close()
+
+
+# legacy shapes off the beaten path (HParams(GRAPH_LEGACY, imSize, nChannels, nClasses, nOut0, nLayers, ks, nExtraConvs), batch);
+# a 1x1 bottom is refused (tests/test_gpu_train_guard.py::test_a_1x1_bottom_is_refused)
+ODD = [
+    ((16, 1, 2, 4, 1, 3, 0), 1),      # one level, one image, two classes
+    ((16, 3, 4, 5, 2, 3, 1), 3),      # three input channels, four classes, odd widths and batch
+    ((64, 1, 3, 4, 5, 3, 0), 2),      # five levels down to a 2x2 bottom
+    ((16, 1, 3, 4, 2, 5, 2), 2),      # 5x5 filters, two extra convolutions, 4x4 bottom
+    ((128, 1, 3, 4, 2, 3, 1), 1),     # one large image
+]
+
+
+@pytest.mark.parametrize("hp_args,B", ODD, ids=["b1_l1", "c3k4_odd", "l5_2x2", "k5_x2_4x4", "im128"])
+def test_odd_shapes_match_reference(hp_args, B):
+    hp = model.HParams(model.GRAPH_LEGACY, *hp_args)
+    blob = model.random_blob(hp, seed=17)
+    data, labels = _batch(hp, B, 23)
+    _check_step(hp, B, blob, data, labels, None, "odd shape %r" % (hp_args,))
+
+
+@pytest.mark.parametrize("name,B", SMALL)
+def test_weighted_loss_matches_reference(name, B):
+    """The weighted form step_sampled uses with class / intersect weights: non-uniform per-pixel, per-class weights."""
+    hp = helpers.small_hps()[name]
+    blob = model.random_blob(hp, seed=8)
+    data, labels = _batch(hp, B, 12)
+    weights = np.random.default_rng(13).uniform(0.25, 4.0, labels.shape).astype(np.float32)
+    _check_step(hp, B, blob, data, labels, weights, "weighted " + name)
+
+
+@pytest.mark.parametrize("graph", [model.GRAPH_LEGACY, model.GRAPH_V2], ids=["legacy", "v2"])
+def test_one_class_is_refused(graph):
+    """nClasses == 1: the softmax of a single class is 1 everywhere, so the cross-entropy and all its gradients vanish -- the
+    trainer refuses the model instead of running a step that cannot learn."""
+    hp = model.HParams(graph, 16, 1, 1, 4, 2, 3, 0)
+    opts = trainer.legacy_options() if graph == model.GRAPH_LEGACY else trainer.duo_options()
+    with pytest.raises(umx.UmxError) as e:
+        trainer.Trainer(hp, model.random_blob(hp), opts, batch=2)
+    assert e.value.code == umx.ERR_INVALID and "nClasses" in str(e.value)
 
 
 def test_nucleidapi_gradients_at_real_size():

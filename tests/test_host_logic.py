@@ -263,3 +263,46 @@ print("ok", order, mode)
                 env["UMX_HIP_RUNTIME"] = mode
             r = subprocess.run([sys.executable, "-c", code, order], capture_output=True, text=True, timeout=300, env=env)
             assert r.returncode == 0 and "ok " + order in r.stdout, (order, mode, r.stdout[-500:], r.stderr[-1500:])
+
+
+def _guard_scan(zone, side, buf_bytes, fill, label=b"tr->DZ (#7)"):
+    """umx_guard_scan (include/umx_train.h) on a host copy of one red zone -> (status, message)."""
+    import ctypes
+    from unmicst_amd import build, trainer, umx
+    build.build()
+    L = trainer._bind(umx.load())
+    z = np.ascontiguousarray(zone, np.uint8)
+    msg = ctypes.create_string_buffer(512)
+    rc = L.umx_guard_scan(z.ctypes.data, z.size, side, buf_bytes, fill, label, msg, len(msg))
+    return rc, msg.value.decode()
+
+
+@pytest.mark.parametrize("fill", [0x00, 0xFF, 0x7F])
+def test_guard_scan_names_the_buffer_side_and_changed_bytes(fill):
+    """The red-zone scan of the trainer's debug guard mode, without a device: a zone that still holds the fill byte passes; a
+    changed byte is reported with the buffer's label, the side, and the first and last changed offset from the buffer's start."""
+    from unmicst_amd import umx
+    Z, n = 65536, 5000                                  # a 64 KiB zone around a 5000-byte buffer
+    clean = np.full(Z, fill, np.uint8)
+    other = (fill ^ 0x5A) & 0xFF
+    assert _guard_scan(clean, 0, n, fill) == (umx.UMX_OK, "")
+    assert _guard_scan(clean, 1, n, fill) == (umx.UMX_OK, "")
+
+    def hit(side, *pos):
+        z = clean.copy()
+        z[list(pos)] = other
+        rc, msg = _guard_scan(z, side, n, fill)
+        assert rc == umx.ERR_GUARD, msg
+        assert "tr->DZ (#7)" in msg and ("back" if side else "front") in msg and "%d bytes" % n in msg, msg
+        return msg
+
+    # back zone: the byte just past the buffer is offset n; its last byte n + Z - 1; a run in between reports both ends
+    assert "bytes %d .. %d " % (n, n) in hit(1, 0)
+    assert "bytes %d .. %d " % (n + Z - 1, n + Z - 1) in hit(1, Z - 1)
+    assert "bytes %d .. %d " % (n + 3, n + 4096) in hit(1, 3, 100, 4096)
+    # front zone: its first byte is offset -Z, the byte just before the buffer -1
+    assert "bytes %d .. %d " % (-Z, -Z) in hit(0, 0)
+    assert "bytes -1 .. -1 " in hit(0, Z - 1)
+    assert "bytes %d .. -1 " % (-Z + 17) in hit(0, 17, Z - 1)
+    # a bad side is an argument error, not a report
+    assert _guard_scan(clean, 2, n, fill)[0] == umx.ERR_INVALID

@@ -10,7 +10,7 @@ LOG=${1:-/tmp/umx_asan.log}
 ROCM=${ROCM_PATH:-/opt/rocm}
 RT=$(ls $ROCM/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.so | head -1)
 OBJ=unmicst_amd/_obj_asan; mkdir -p $OBJ
-SRCS="umx_kernels umx_conv_f16 umx_conv_first umx_graph umx_plan umx_engine umx_host umx_tiff umx_shard umx_train_kernels umx_train"
+SRCS="umx_kernels umx_conv_f16 umx_conv_first umx_graph umx_plan umx_engine umx_host umx_tiff umx_shard umx_train_kernels umx_train umx_trainset"
 FLAGS="-O1 -g -std=c++17 --offload-arch=gfx950 -fPIC -fvisibility=hidden -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -shared-libasan -Wno-unused-value -Wno-unused-result -Wno-option-ignored"
 pids=()
 for s in $SRCS; do

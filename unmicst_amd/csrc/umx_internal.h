@@ -292,6 +292,29 @@ int tiles_range(umx_ctx* ctx, const double* image_dev, int C_img, const TileGeom
 // the tile gather of this engine can read raw integer planes (im2double in the gather: no float64 image is written or read)
 bool gathers_raw(const umx_ctx* ctx);
 
+// ---- device memory of a trainer / training set (umx_train.hip) ----
+// Every allocation goes through arena_alloc.  Debug guard mode (UMX_DEBUG_GUARD=<byte>, read at umx_trainer_create /
+// umx_trainset_create) puts a red zone of max(64 KiB, round_up(bytes, 4 KiB)) in front of and behind each buffer, fills both
+// zones -- and the buffer itself unless the caller zeroes or uploads it -- with that byte, and arena_check names the first
+// buffer whose zones changed.  Off (the default), an allocation is the plain hipMalloc it always was.
+struct DevBlock {
+    void* base;                        // what hipMalloc returned
+    size_t front, bytes, back;         // the buffer is [base + front, base + front + bytes)
+    std::string label;
+};
+struct DevArena {
+    int fill = -1;                     // guard mode: the fill byte 0..255; -1 off
+    std::vector<void*> allocs;         // what hipFree takes
+    std::vector<DevBlock> blocks;      // (guard mode) one per allocation, in allocation order
+};
+// UMX_DEBUG_GUARD -> a->fill; UMX_ERR_INVALID (with *why) for a value that is not a byte
+int arena_init(DevArena* a, std::string* why);
+// bytes (at least 16) of device memory -> *out; zero: cleared, else uninitialised (guard mode: filled)
+hipError_t arena_alloc(DevArena* a, void** out, size_t bytes, bool zero, const char* label);
+// guard mode only, with every stream writing the arena idle: UMX_OK, or UMX_ERR_GUARD with the first damaged zone in *msg
+int arena_check(const DevArena& a, std::string* msg);
+void arena_free(DevArena* a);
+
 // ---- training step (umx_train.hip) as the training set (umx_trainset.hip) sees it ----
 struct TrainerIO {
     int device, B, P, C, K;            // batch, tile, input channels, classes
@@ -306,6 +329,8 @@ int trainer_fail(umx_trainer* tr, int code, const char* msg);   // -> code, with
 int trainer_eval_begin(umx_trainer* tr);
 int trainer_eval_forward(umx_trainer* tr);
 int trainer_eval_end(umx_trainer* tr);
+// guard mode: wait for every stream of the trainer, then check its red zones (UMX_OK when the mode is off)
+int trainer_guard_check(umx_trainer* tr);
 
 // ---- training-set kernels (umx_trainset.hip) ----
 constexpr int kDescChunk = 64;         // descriptors per assembly launch (passed by value: 2 KiB of kernel arguments)

@@ -94,7 +94,7 @@ struct umx_trainer {
     std::vector<int> n;                 // channel widths
     hipStream_t stream = nullptr;
     std::string err;
-    std::vector<void*> allocs;
+    umx::DevArena mem;                  // every device buffer below (UMX_DEBUG_GUARD: with red zones)
     int64_t step = 0;
     // parameters
     size_t nparams = 0;
@@ -209,28 +209,25 @@ int tfail(umx_trainer* tr, int code, const char* fmt, ...) {
         if (rc_ != UMX_OK) return rc_; \
     } while (0)
 
+// every device buffer of the trainer: arena_alloc (guard mode: red zones); the macros record the destination as the buffer's label
 template <typename T>
-int talloc(umx_trainer* tr, T** out, size_t count) {
+int talloc_(umx_trainer* tr, T** out, size_t count, bool zero, const char* label) {
     void* d = nullptr;
-    T_HIP(tr, hipMalloc(&d, std::max<size_t>(16, count * sizeof(T))));
-    tr->allocs.push_back(d);
+    T_HIP(tr, arena_alloc(&tr->mem, &d, count * sizeof(T), zero, label));
     *out = reinterpret_cast<T*>(d);
     return UMX_OK;
 }
 
 template <typename T>
-int tzero(umx_trainer* tr, T** out, size_t count) {
-    T_TRY(talloc(tr, out, count));
-    T_HIP(tr, hipMemset(*out, 0, std::max<size_t>(16, count * sizeof(T))));
-    return UMX_OK;
-}
-
-template <typename T>
-int tupload(umx_trainer* tr, T** out, const T* host, size_t count) {
-    T_TRY(talloc(tr, out, count));
+int tupload_(umx_trainer* tr, T** out, const T* host, size_t count, const char* label) {
+    T_TRY(talloc_(tr, out, count, false, label));
     if (count) T_HIP(tr, hipMemcpy(*out, host, count * sizeof(T), hipMemcpyHostToDevice));
     return UMX_OK;
 }
+
+#define talloc(tr, out, count) talloc_(tr, out, count, false, #out)
+#define tzero(tr, out, count) talloc_(tr, out, count, true, #out)
+#define tupload(tr, out, host, count) tupload_(tr, out, host, count, #out)
 
 // N-tiles per workgroup.  A training batch is small (8 images): the deep layers have a handful of 256-pixel M-tiles, so
 // wide N blocks would leave most of the 256 CUs idle.  Cost model: rounds of 512 resident workgroups (2 per CU) times
@@ -528,13 +525,14 @@ int setup_conv(umx_trainer* tr, TConv& tc, const char* what, int H, int W, int C
 }
 
 // (nothing on the exact-fp32 route: its planes stay empty)
-int alloc_h16(umx_trainer* tr, H16& h, size_t npix, int C) {
+int alloc_h16_(umx_trainer* tr, H16& h, size_t npix, int C, const char* label) {
     if (!tr->hconv) return UMX_OK;
     h.Cs = round_up(std::max(C, 1), 8);
-    T_TRY(tzero(tr, &h.hi, npix * h.Cs));
-    T_TRY(tzero(tr, &h.lo, npix * h.Cs));
+    T_TRY(talloc_(tr, &h.hi, npix * h.Cs, true, (std::string(label) + ".hi").c_str()));
+    T_TRY(talloc_(tr, &h.lo, npix * h.Cs, true, (std::string(label) + ".lo").c_str()));
     return UMX_OK;
 }
+#define alloc_h16(tr, h, npix, C) alloc_h16_(tr, h, npix, C, #h)
 
 // fp32 NHWC tensor -> the (hi, lo) planes conv_f16x3 reads (maxw / inv: a gradient tensor's dynamic scale, else NULL)
 int to_h16(umx_trainer* tr, const float* x, size_t npix, int C, const H16& h, const unsigned* maxw, float* inv, hipStream_t st,
@@ -1762,9 +1760,109 @@ int trainer_eval_end(umx_trainer* tr) {
     return UMX_OK;
 }
 
+// ---- the device memory of a trainer / training set (umx_internal.h) ----
+int arena_init(DevArena* a, std::string* why) {
+    a->fill = -1;
+    const char* e = getenv("UMX_DEBUG_GUARD");
+    if (!e || !*e) return UMX_OK;
+    char* end = nullptr;
+    const long v = strtol(e, &end, 0);
+    if (*end || v < 0 || v > 255) {
+        *why = std::string("UMX_DEBUG_GUARD=") + e + ": the fill must be one byte (0..255, e.g. 0xff)";
+        return UMX_ERR_INVALID;
+    }
+    a->fill = (int)v;
+    return UMX_OK;
+}
+
+hipError_t arena_alloc(DevArena* a, void** out, size_t bytes, bool zero, const char* label) {
+    bytes = std::max<size_t>(16, bytes);
+    void* d = nullptr;
+    if (a->fill < 0) {
+        hipError_t e = hipMalloc(&d, bytes);
+        if (e != hipSuccess) return e;
+        a->allocs.push_back(d);
+        if (zero && (e = hipMemset(d, 0, bytes)) != hipSuccess) return e;
+        *out = d;
+        return hipSuccess;
+    }
+    // a zone at least as large as the buffer: an index off by a whole image / plane / row lands in it, not in unmapped memory
+    const size_t zone = std::max<size_t>(64 << 10, (bytes + 4095) / 4096 * 4096);
+    hipError_t e = hipMalloc(&d, zone + bytes + zone);
+    if (e != hipSuccess) return e;
+    a->allocs.push_back(d);
+    char* p = static_cast<char*>(d);
+    if ((e = hipMemset(p, a->fill, zone + bytes + zone)) != hipSuccess) return e;
+    if (zero && (e = hipMemset(p + zone, 0, bytes)) != hipSuccess) return e;
+    if ((e = hipDeviceSynchronize()) != hipSuccess) return e;   // (the trainer's streams do not wait for the null stream)
+    while (*label == '&') ++label;
+    a->blocks.push_back({d, zone, bytes, zone, std::string(label) + " (#" + std::to_string(a->blocks.size()) + ")"});
+    *out = p + zone;
+    return hipSuccess;
+}
+
+int arena_check(const DevArena& a, std::string* msg) {
+    if (a.fill < 0) return UMX_OK;
+    std::vector<uint8_t> h;
+    char buf[512];
+    for (const DevBlock& b : a.blocks) {
+        for (int side = 0; side < 2; ++side) {
+            const size_t n = side ? b.back : b.front;
+            const char* src = static_cast<const char*>(b.base) + (side ? b.front + b.bytes : 0);
+            h.resize(n);
+            const hipError_t e = hipMemcpy(h.data(), src, n, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) {
+                *msg = std::string("guard check: hipMemcpy failed: ") + hipGetErrorString(e);
+                return UMX_ERR_HIP;
+            }
+            const int rc = umx_guard_scan(h.data(), n, side, b.bytes, a.fill, b.label.c_str(), buf, sizeof buf);
+            if (rc != UMX_OK) {
+                *msg = buf;
+                return rc;
+            }
+        }
+    }
+    return UMX_OK;
+}
+
+void arena_free(DevArena* a) {
+    for (void* p : a->allocs) (void)hipFree(p);
+    a->allocs.clear();
+    a->blocks.clear();
+}
+
+int trainer_guard_check(umx_trainer* tr) {
+    if (tr->mem.fill < 0) return UMX_OK;
+    T_HIP(tr, hipSetDevice(tr->device));
+    for (hipStream_t s : {tr->stream, tr->side, tr->side2, tr->aux})
+        if (s) T_HIP(tr, hipStreamSynchronize(s));
+    std::string msg;
+    const int rc = arena_check(tr->mem, &msg);
+    return rc == UMX_OK ? UMX_OK : tfail(tr, rc, "%s", msg.c_str());
+}
+
 }  // namespace umx
 
 extern "C" {
+
+int umx_guard_scan(const uint8_t* zone, size_t zone_bytes, int side, size_t buf_bytes, int fill, const char* label, char* msg,
+                   size_t cap) {
+    if (!zone || !label || (side != 0 && side != 1)) return UMX_ERR_INVALID;
+    size_t first = SIZE_MAX, last = 0;
+    for (size_t j = 0; j < zone_bytes; ++j)
+        if (zone[j] != (uint8_t)fill) {
+            if (first == SIZE_MAX) first = j;
+            last = j;
+        }
+    if (first == SIZE_MAX) return UMX_OK;
+    // offsets from the first byte of the buffer: the front zone ends at -1, the back zone starts at buf_bytes
+    const long long o1 = side ? (long long)(buf_bytes + first) : (long long)first - (long long)zone_bytes;
+    const long long o2 = side ? (long long)(buf_bytes + last) : (long long)last - (long long)zone_bytes;
+    if (msg && cap)
+        snprintf(msg, cap, "guard: %s (%zu bytes): the %s red zone was written, bytes %lld .. %lld of the buffer (fill 0x%02x)", label,
+                 buf_bytes, side ? "back" : "front", o1, o2, fill & 0xff);
+    return UMX_ERR_GUARD;
+}
 
 void umx_train_options_solo(umx_train_options* o) {
     fill_common(o);
@@ -1810,7 +1908,8 @@ int umx_trainer_create(const umx_hparams* hp, const float* weight_blob, size_t b
     } else if (hp->graph != UMX_GRAPH_V2 || hp->nExtraConvs != 0) {
         return tfail(nullptr, UMX_ERR_INVALID, "the training step covers the v2 graph with nExtraConvs == 0");
     }
-    if (hp->nClasses < 1 || hp->nClasses > 8) return tfail(nullptr, UMX_ERR_INVALID, "nClasses must be 1..8");
+    // one class: the softmax is identically 1, so the cross-entropy and every gradient of it are 0 -- nothing could be learnt
+    if (hp->nClasses < 2 || hp->nClasses > 8) return tfail(nullptr, UMX_ERR_INVALID, "nClasses must be 2..8 (a one-class softmax has no gradient)");
     if (hp->nLayers < 1 || hp->nLayers > 8 || (hp->ks != 3 && hp->ks != 5) || hp->featMapsFact < 1 ||
         hp->nChannels < 1 || hp->nOut0 < 1)
         return tfail(nullptr, UMX_ERR_INVALID, "unsupported hyper-parameters");
@@ -1832,7 +1931,9 @@ int umx_trainer_create(const umx_hparams* hp, const float* weight_blob, size_t b
     tr->B = opts->batch > 0 ? opts->batch : 8;
     tr->legacy = legacy;
     int rc = UMX_OK;
-    if (hipSetDevice(tr->device) != hipSuccess) rc = tfail(tr, UMX_ERR_HIP, "hipSetDevice failed");
+    std::string why;
+    if (arena_init(&tr->mem, &why) != UMX_OK) rc = tfail(tr, UMX_ERR_INVALID, "%s", why.c_str());
+    if (rc == UMX_OK && hipSetDevice(tr->device) != hipSuccess) rc = tfail(tr, UMX_ERR_HIP, "hipSetDevice failed");
     if (rc == UMX_OK && hipStreamCreateWithFlags(&tr->stream, hipStreamNonBlocking) != hipSuccess)
         rc = tfail(tr, UMX_ERR_HIP, "hipStreamCreate failed");
     if (rc == UMX_OK) rc = legacy ? build_legacy(tr, weight_blob, blob_floats) : build_trainer(tr, weight_blob, blob_floats);
@@ -1860,6 +1961,8 @@ int umx_trainer_create(const umx_hparams* hp, const float* weight_blob, size_t b
         umx_trainer_destroy(tr);
         return rc;
     }
+    if (tr->mem.fill >= 0)
+        fprintf(stderr, "[umx train] UMX_DEBUG_GUARD=0x%02x: %zu trainer buffers between red zones\n", tr->mem.fill, tr->mem.blocks.size());
     *out = tr;
     return UMX_OK;
 }
@@ -1868,7 +1971,7 @@ void umx_trainer_destroy(umx_trainer* tr) {
     if (!tr) return;
     (void)hipSetDevice(tr->device);
     if (tr->stream) (void)hipStreamSynchronize(tr->stream);
-    for (void* p : tr->allocs) (void)hipFree(p);
+    arena_free(&tr->mem);
     if (tr->pctx) {
         for (void* p : tr->pctx->allocs) (void)hipFree(p);
         delete tr->pctx;
@@ -1900,7 +2003,8 @@ int umx_train_step_dev(umx_trainer* tr, const float* data_dev, const float* labe
     const int rc = tr->legacy ? enqueue_legacy(tr, data_dev, labels_dev, weights_dev, apply_update != 0)
                               : enqueue_step(tr, data_dev, labels_dev, weights_dev, apply_update != 0);
     tr->ds[0] = own;
-    return rc;
+    T_TRY(rc);
+    return umx::trainer_guard_check(tr);
 }
 
 int umx_trainer_loss(umx_trainer* tr, double* loss3) {
@@ -1949,7 +2053,9 @@ int umx_trainer_eval(umx_trainer* tr, const float* data, float* probs_host) {
     T_HIP(tr, hipMemcpyAsync(tr->ds[0], data, npx * tr->n[0] * sizeof(float), hipMemcpyHostToDevice, tr->stream));
     T_TRY(umx::trainer_eval_forward(tr));
     T_HIP(tr, hipMemcpyAsync(probs_host, tr->d_probs, npx * tr->K * sizeof(float), hipMemcpyDeviceToHost, tr->stream));
-    return umx::trainer_eval_end(tr);
+    const int rc = umx::trainer_eval_end(tr);
+    T_TRY(umx::trainer_guard_check(tr));   // (a damaged zone before a range report)
+    return rc;
 }
 
 int umx_trainer_read(umx_trainer* tr, int which, float* out, size_t n_floats) {

@@ -37,7 +37,7 @@ struct umx_trainset {
     double* part = nullptr;             // class_counts workspace (B P^2 pixels at most)
     long long* counts = nullptr;        // [2K]
     double* loss = nullptr;             // [1]
-    std::vector<void*> allocs;
+    DevArena mem;                       // every device buffer above (UMX_DEBUG_GUARD: with red zones)
 };
 
 namespace umx {
@@ -45,7 +45,7 @@ namespace umx {
 namespace {
 
 constexpr int kCountThreads = 256;
-constexpr int kMaxClasses = 8;       // umx_trainer_create: nClasses 1..8
+constexpr int kMaxClasses = 8;       // umx_trainer_create: nClasses 2..8
 constexpr int kMaxCountBlocks = 1024;
 
 // float32(a * b + c) with the product and the sum rounded in float64, never fused into one fma (HIP's __dmul_rn / __dadd_rn are plain
@@ -219,12 +219,20 @@ int tsfail(umx_trainer* tr, int code, const char* fmt, ...) {
     } while (0)
 
 template <typename T>
-int ts_alloc(umx_trainset* ts, T** out, size_t count) {
+int ts_alloc_(umx_trainset* ts, T** out, size_t count, const char* label) {
     void* d = nullptr;
-    TS_HIP(ts->tr, hipMalloc(&d, std::max<size_t>(16, count * sizeof(T))));
-    ts->allocs.push_back(d);
+    TS_HIP(ts->tr, arena_alloc(&ts->mem, &d, count * sizeof(T), false, label));
     *out = reinterpret_cast<T*>(d);
     return UMX_OK;
+}
+#define ts_alloc(ts, out, count) ts_alloc_(ts, out, count, #out)
+
+// guard mode: the trainer's zones (its streams idle afterwards), then the set's own
+int guard_check(umx_trainer* tr, const umx_trainset* ts) {
+    TS_TRY(trainer_guard_check(tr));
+    std::string msg;
+    const int rc = arena_check(ts->mem, &msg);
+    return rc == UMX_OK ? UMX_OK : tsfail(tr, rc, "%s", msg.c_str());
 }
 
 TrainSetView view_of(const umx_trainset* ts) {
@@ -303,9 +311,11 @@ int umx_trainset_create(umx_trainer* tr, int n_samples, int n_pages, int size, c
     const size_t px_f = (size_t)n_samples * size * ts->row_f, px_a = (size_t)n_samples * size * ts->row_a;
     const size_t bytes = px_f * 4 * io.C * n_pages + px_a + (ts->weighted ? px_f * 4 : 0);
     size_t free_b = 0, total_b = 0;
-    int rc = umx_device_mem_info(io.device, &free_b, &total_b);
-    if (rc != UMX_OK) rc = tsfail(tr, rc, "%s", umx_last_error(nullptr));
-    else if (bytes > free_b)
+    std::string why;
+    int rc = arena_init(&ts->mem, &why);
+    if (rc != UMX_OK) rc = tsfail(tr, rc, "%s", why.c_str());
+    if (rc == UMX_OK && (rc = umx_device_mem_info(io.device, &free_b, &total_b)) != UMX_OK) rc = tsfail(tr, rc, "%s", umx_last_error(nullptr));
+    else if (rc == UMX_OK && bytes > free_b)
         rc = tsfail(tr, UMX_ERR_OOM, "a training set of %d samples of %d x %d (%d channels x %d pages) needs %.1f MB, %.1f MB are free", n_samples,
                     size, size, io.C, n_pages, bytes / 1e6, free_b / 1e6);
     if (rc == UMX_OK) rc = hipSetDevice(io.device) == hipSuccess ? UMX_OK : tsfail(tr, UMX_ERR_HIP, "hipSetDevice failed");
@@ -319,6 +329,8 @@ int umx_trainset_create(umx_trainer* tr, int n_samples, int n_pages, int size, c
         umx_trainset_destroy(ts);
         return rc;
     }
+    if (ts->mem.fill >= 0)
+        fprintf(stderr, "[umx train] UMX_DEBUG_GUARD=0x%02x: %zu training-set buffers between red zones\n", ts->mem.fill, ts->mem.blocks.size());
     *out = ts;
     return UMX_OK;
 }
@@ -345,16 +357,16 @@ int umx_trainset_set(umx_trainset* ts, int index, const float* planes, const uin
             TS_HIP(tr, hipMemsetAsync(dst, 0, plane * sizeof(float), io.stream));   // a missing map counts as 0
     }
     TS_HIP(tr, hipStreamSynchronize(io.stream));
-    return UMX_OK;
+    return guard_check(tr, ts);
 }
 
 void umx_trainset_destroy(umx_trainset* ts) {
     if (!ts) return;
-    if (!ts->allocs.empty()) {
+    if (!ts->mem.allocs.empty()) {
         const TrainerIO io = trainer_io(ts->tr);
         (void)hipSetDevice(io.device);
         (void)hipStreamSynchronize(io.stream);
-        for (void* p : ts->allocs) (void)hipFree(p);
+        arena_free(&ts->mem);
     }
     delete ts;
 }
@@ -365,7 +377,10 @@ int umx_train_step_sampled(umx_trainer* tr, const umx_trainset* ts, const umx_sa
     TS_TRY(check_descs(tr, ts, desc, io.B, io.B, "umx_train_step_sampled"));
     TS_HIP(tr, hipSetDevice(io.device));
     TS_TRY(enqueue_assemble(tr, ts, desc, io.B, ts->weighted));
-    return umx_train_step_dev(tr, io.data, io.labels, ts->weighted ? io.weights : nullptr, apply_update);
+    TS_TRY(umx_train_step_dev(tr, io.data, io.labels, ts->weighted ? io.weights : nullptr, apply_update));   // (checks the trainer's zones)
+    std::string msg;
+    const int rc = arena_check(ts->mem, &msg);
+    return rc == UMX_OK ? UMX_OK : tsfail(tr, rc, "%s", msg.c_str());
 }
 
 int umx_trainer_assemble(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, int n, float* data, float* labels,
@@ -382,7 +397,7 @@ int umx_trainer_assemble(umx_trainer* tr, const umx_trainset* ts, const umx_samp
     if (weights && ts->weighted)
         TS_HIP(tr, hipMemcpyAsync(weights, io.weights, npx * io.K * sizeof(float), hipMemcpyDeviceToHost, io.stream));
     TS_HIP(tr, hipStreamSynchronize(io.stream));
-    return UMX_OK;
+    return guard_check(tr, ts);
 }
 
 int umx_trainer_evaluate(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, int n, int64_t* counts, double* loss_sum) {
@@ -398,7 +413,9 @@ int umx_trainer_evaluate(umx_trainer* tr, const umx_trainset* ts, const umx_samp
     double l = 0.0;
     TS_HIP(tr, hipMemcpyAsync(c, ts->counts, 2 * io.K * sizeof(long long), hipMemcpyDeviceToHost, io.stream));
     TS_HIP(tr, hipMemcpyAsync(&l, ts->loss, sizeof l, hipMemcpyDeviceToHost, io.stream));
-    TS_TRY(trainer_eval_end(tr));
+    const int rc = trainer_eval_end(tr);
+    TS_TRY(guard_check(tr, ts));   // (a damaged zone before a range report)
+    TS_TRY(rc);
     for (int q = 0; q < 2 * io.K; ++q) counts[q] = c[q];
     *loss_sum = l;
     return UMX_OK;

@@ -29,7 +29,7 @@ EXPORTS = [
     "umx_trainer_last_error", "umx_train_step", "umx_train_step_dev", "umx_trainer_loss", "umx_trainer_read",
     "umx_trainer_probs", "umx_trainer_read_tensor", "umx_trainer_eval", "umx_trainer_step_count", "umx_trainer_batch", "umx_trainer_flops_per_image",
     "umx_trainer_profile", "umx_trainset_create", "umx_trainset_set", "umx_trainset_destroy", "umx_train_step_sampled",
-    "umx_trainer_assemble", "umx_trainer_evaluate",
+    "umx_trainer_assemble", "umx_trainer_evaluate", "umx_guard_scan",
 ]
 
 
@@ -162,6 +162,10 @@ def _bind(L):
     L.umx_trainer_assemble.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
     L.umx_trainer_evaluate.restype = c_int
     L.umx_trainer_evaluate.argtypes = [c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(ctypes.c_int64), dp]
+    # debug guard mode (UMX_DEBUG_GUARD): the host scan of one red zone
+    L.umx_guard_scan.restype = c_int
+    L.umx_guard_scan.argtypes = [c_void_p, ctypes.c_size_t, c_int, ctypes.c_size_t, c_int, ctypes.c_char_p, ctypes.c_char_p,
+                                 ctypes.c_size_t]
     L._umx_train_bound = True
     return L
 
