@@ -48,93 +48,116 @@ hipError_t launch_pack_weights(const PackDesc* descs_dev, int ndesc, size_t max_
     return hipGetLastError();
 }
 
-// ------------------------------------------------------------------------------------------------ channel layout
-// An NHWC tensor is [N rows][C channels].  A block of Cb*k threads (Cb = min(C, 256), k = 256 / Cb) walks k rows at
-// a time: thread (r, c) always sees channel c, so per-channel sums live in registers and the loads are contiguous.
-struct ChanLayout { int Cb, k, threads, cblocks; };
-static inline ChanLayout chan_layout(int C) {
+// ------------------------------------------------------------------------------------------------ per-element passes
+// The per-element passes of the step (BN statistics, BN + activation + pool + dropout forward, their backward with the BN sums,
+// the BN input gradient, the transposed convolution's activation backward) are each one template over the channels a thread
+// owns, V, and the index type, I.  Two instantiations of each run:
+//   <4, unsigned>  C % 4 == 0 and 32-bit indices suffice (every layer of the shipped widths): four consecutive channels per
+//                  thread, 16-byte loads and stores, the per-channel constants in registers, 32-bit index arithmetic.  The
+//                  scalar form spends most of its time on 4-byte accesses and 64-bit index arithmetic there (act_bwd on lu0,
+//                  19 M elements: 149 us against 50 us of memory time; leaky_bwd_s2d at 8 x 256 x 256 x 36: 146 us for 3 x 75 MB).
+//   <1, size_t>    every other shape (the v2 head's 2 - 3 classes, odd test widths): one channel per thread, 64-bit indices
+//                  (bn_bwd_apply's planes form: <1, unsigned>, its planes being limited to 32-bit indices anyway).
+// The two do not sum a block's rows in the same order, so which one a shape takes is fixed by its launcher.
+//
+// An NHWC tensor is [N rows][C channels], i.e. [N rows][C / V units].  The reductions run blocks of Ub * R threads (Ub =
+// min(C / V, 256), R = 256 / Ub) that walk R rows at a time: thread (r, u) always sees unit u, so per-channel sums live in
+// registers and the loads are contiguous.  Their partials are part[block][2][C] (fp64, fixed order) for either V.
+struct ChanLayout { int Ub, R, threads, cblocks; };
+static inline ChanLayout chan_layout(int C, int V) {
     ChanLayout l;
-    l.Cb = std::min(C, 256);
-    l.k = std::max(1, 256 / l.Cb);
-    l.threads = l.Cb * l.k;
-    l.cblocks = (C + 255) / 256;
+    const int U = C / V;
+    l.Ub = std::min(U, 256);
+    l.R = std::max(1, 256 / l.Ub);
+    l.threads = V == 1 ? l.Ub * l.R : 256;   // (the float4 reductions always run 256 threads; the spare ones idle)
+    l.cblocks = (U + 255) / 256;
     return l;
 }
 
 int chan_blocks(size_t N, int C) {
-    const ChanLayout l = chan_layout(C);
+    const ChanLayout l = chan_layout(C, 1);
     // (a handful of rows per block: the deep layers have 512 - 2048 rows, and 17 blocks walking 30 rows each left their
     //  activation-backward kernel latency-bound at 158 us for 1.2 MB -- round 4 time line)
-    const size_t want = N / ((size_t)l.k * 4) + 1;
+    const size_t want = N / ((size_t)l.R * 4) + 1;
     const size_t cap = std::max(64, 1024 / l.cblocks);
     return (int)std::min<size_t>(cap, std::max<size_t>(1, want));
 }
 
-__global__ void __launch_bounds__(256) chan_stats_kernel(const float* __restrict__ x, size_t N, int C, int Cb, int k,
-                                                         double* __restrict__ part) {
-    __shared__ double sm[2][256];
-    const int tid = threadIdx.x;
-    const int r = tid / Cb, cl = tid - r * Cb;
-    const int c = cl + blockIdx.y * 256;
-    const size_t rpb = (N + gridDim.x - 1) / gridDim.x;
-    const size_t r0 = (size_t)blockIdx.x * rpb, r1 = std::min(N, r0 + rpb);
-    double s = 0.0, q = 0.0;
-    if (c < C)
-        for (size_t row = r0 + r; row < r1; row += k) {
-            const double v = (double)x[row * C + c];
-            s += v;
-            q += v * v;
-        }
-    sm[0][tid] = s;
-    sm[1][tid] = q;
-    __syncthreads();
-    if (r == 0 && c < C) {
-        for (int j = 1; j < k; ++j) { s += sm[0][j * Cb + cl]; q += sm[1][j * Cb + cl]; }
-        part[((size_t)blockIdx.x * 2 + 0) * C + c] = s;
-        part[((size_t)blockIdx.x * 2 + 1) * C + c] = q;
+// unit i of p (V consecutive floats): one float4 or one float
+template <int V> __device__ __forceinline__ void ldv(float (&d)[V], const float* p, size_t i = 0) {
+    if constexpr (V == 4) {
+        const float4 t = reinterpret_cast<const float4*>(p)[i];
+        d[0] = t.x; d[1] = t.y; d[2] = t.z; d[3] = t.w;
+    } else {
+        d[0] = p[i];
+    }
+}
+template <int V> __device__ __forceinline__ void stv(float* p, size_t i, const float (&s)[V]) {
+    if constexpr (V == 4) reinterpret_cast<float4*>(p)[i] = make_float4(s[0], s[1], s[2], s[3]);
+    else p[i] = s[0];
+}
+// V values as (hi, lo) binary16 pairs; bad: a value binary16 cannot hold
+template <int V> __device__ __forceinline__ void st_planes(_Float16* hi, _Float16* lo, const float (&y)[V], bool& bad) {
+    union { _Float16 h[4]; uint2 u; } a, b;
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        bad = bad || !(fabsf(y[k]) < 60000.f);
+        a.h[k] = (_Float16)y[k];
+        b.h[k] = (_Float16)(y[k] - (float)a.h[k]);
+    }
+    if constexpr (V == 4) {
+        *reinterpret_cast<uint2*>(hi) = a.u;
+        *reinterpret_cast<uint2*>(lo) = b.u;
+    } else {
+        *hi = a.h[0];
+        *lo = b.h[0];
     }
 }
 
-// (C % 4 == 0: four channels per thread, 16-byte loads; same partial-sum layout)
-__global__ void __launch_bounds__(256) chan_stats_v4_kernel(const float* __restrict__ x, unsigned N, int C, int Qb, int R,
-                                                            double* __restrict__ part) {
-    __shared__ double sm[2][256][4];
+template <int V, typename I>
+__global__ void __launch_bounds__(256) chan_stats_kernel(const float* __restrict__ x, I N, int C, int Ub, int R,
+                                                         double* __restrict__ part) {
+    __shared__ double sm[2][256][V];
     const int tid = threadIdx.x;
-    const int r = tid / Qb, ql = tid - r * Qb;
-    const int Q = C >> 2, q = ql + blockIdx.y * 256;
-    const unsigned rpb = (N + gridDim.x - 1) / gridDim.x;
-    const unsigned r0 = blockIdx.x * rpb, r1 = min(N, r0 + rpb);
-    double s[4] = {0.0, 0.0, 0.0, 0.0}, w[4] = {0.0, 0.0, 0.0, 0.0};
-    if (r < R && q < Q)
-        for (unsigned row = r0 + r; row < r1; row += R) {
-            const float4 v4 = reinterpret_cast<const float4*>(x)[(size_t)row * Q + q];
-            const double v[4] = {(double)v4.x, (double)v4.y, (double)v4.z, (double)v4.w};
+    const int r = tid / Ub, ul = tid - r * Ub;
+    const int U = C >> (V / 2), u = ul + blockIdx.y * 256;   // (U = C / V)
+    const I rpb = (N + gridDim.x - 1) / gridDim.x;
+    const I r0 = (I)blockIdx.x * rpb, r1 = min(N, r0 + rpb);
+    double s[V] = {}, w[V] = {};
+    if (r < R && u < U)
+        for (I row = r0 + r; row < r1; row += R) {
+            float xv[V];
+            ldv<V>(xv, x, (size_t)row * U + u);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) { s[k] += v[k]; w[k] += v[k] * v[k]; }
+            for (int k = 0; k < V; ++k) {
+                const double v = (double)xv[k];
+                s[k] += v;
+                w[k] += v * v;
+            }
         }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { sm[0][tid][k] = s[k]; sm[1][tid][k] = w[k]; }
+    for (int k = 0; k < V; ++k) { sm[0][tid][k] = s[k]; sm[1][tid][k] = w[k]; }
     __syncthreads();
-    if (r == 0 && q < Q) {
+    if (r == 0 && u < U) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            double t1 = s[k], t2 = w[k];
-            for (int j = 1; j < R; ++j) { t1 += sm[0][j * Qb + ql][k]; t2 += sm[1][j * Qb + ql][k]; }
-            part[((size_t)blockIdx.x * 2 + 0) * C + 4 * q + k] = t1;
-            part[((size_t)blockIdx.x * 2 + 1) * C + 4 * q + k] = t2;
+        for (int k = 0; k < V; ++k) {
+            for (int j = 1; j < R; ++j) { s[k] += sm[0][j * Ub + ul][k]; w[k] += sm[1][j * Ub + ul][k]; }
+            part[((size_t)blockIdx.x * 2 + 0) * C + V * u + k] = s[k];
+            part[((size_t)blockIdx.x * 2 + 1) * C + V * u + k] = w[k];
         }
     }
 }
 
 hipError_t launch_chan_stats(const float* x, size_t N, int C, double* part, int nblk, hipStream_t stream) {
     if (C % 4 == 0 && N < 0x7fffffffull) {
-        const int Q = C / 4, Qb = std::min(Q, 256), R = std::max(1, 256 / Qb), cbl = (Q + 255) / 256;
-        hipLaunchKernelGGL(chan_stats_v4_kernel, dim3((unsigned)nblk, (unsigned)cbl), dim3(256), 0, stream, x, (unsigned)N, C, Qb, R, part);
+        const ChanLayout l = chan_layout(C, 4);
+        hipLaunchKernelGGL((chan_stats_kernel<4, unsigned>), dim3((unsigned)nblk, (unsigned)l.cblocks), dim3(l.threads), 0, stream,
+                           x, (unsigned)N, C, l.Ub, l.R, part);
         return hipGetLastError();
     }
-    const ChanLayout l = chan_layout(C);
-    hipLaunchKernelGGL(chan_stats_kernel, dim3((unsigned)nblk, (unsigned)l.cblocks), dim3((unsigned)l.threads), 0, stream,
-                       x, N, C, l.Cb, l.k, part);
+    const ChanLayout l = chan_layout(C, 1);
+    hipLaunchKernelGGL((chan_stats_kernel<1, size_t>), dim3((unsigned)nblk, (unsigned)l.cblocks), dim3(l.threads), 0, stream,
+                       x, N, C, l.Ub, l.R, part);
     return hipGetLastError();
 }
 
@@ -252,100 +275,50 @@ __device__ __forceinline__ void block_absmax_to(unsigned* dst, float v) {
     }
 }
 
-// (grid-stride; the block's max |output| goes to the tensor's max word with at most one atomic)
-__global__ void __launch_bounds__(256) act_fwd_kernel(const ActParams a, float* __restrict__ out, size_t nout,
-                                                      unsigned* omax, _Float16* __restrict__ hi, _Float16* __restrict__ lo, int Cs,
+// (grid-stride over units; the block's max |output| goes to the tensor's max word with at most one atomic; hi != NULL: the
+// output also as the (hi, lo) planes the next convolution reads, unscaled)
+template <int V, typename I>
+__global__ void __launch_bounds__(256) act_fwd_kernel(const ActParams a, float* __restrict__ out, I nu, unsigned* omax,
+                                                      _Float16* __restrict__ hi, _Float16* __restrict__ lo, int Cs,
                                                       int* __restrict__ overflow) {
     const int C = a.C;
-    bool bad = false;   // (hi != NULL: the output also as the (hi, lo) planes the next convolution reads, unscaled)
+    const I U = (unsigned)C / V;
     const float ks = 1.0f / (1.0f - a.drop_rate);
-    const int OW = a.W >> 1, OH = a.H >> 1;
-    float mx = 0.f;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < nout; e += (size_t)gridDim.x * 256) {
-        const int c = (int)(e % C);
-        const float sc = a.stat[2 * C + c], sh = a.stat[3 * C + c];
-        float y;
-        if (!a.pool) {
-            const float v = a.z[e] * sc + sh;
-            y = act_of(v, a.act) * drop_mul(a.drop_key, e, a.drop_rate, ks);
-        } else {
-            size_t r = e / C;
-            const int ox = (int)(r % OW); r /= OW;
-            const int oy = (int)(r % OH);
-            const int b = (int)(r / OH);
-            y = 0.f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const size_t idx = (((size_t)b * a.H + 2 * oy + (j >> 1)) * a.W + 2 * ox + (j & 1)) * C + c;
-                const float v = a.z[idx] * sc + sh;
-                const float yj = act_of(v, a.act) * drop_mul(a.drop_key, idx, a.drop_rate, ks);
-                if (j == 0 || yj > y) y = yj;
-            }
-        }
-        out[e] = y;
-        mx = fmaxf(mx, fabsf(y));
-        if (hi) {
-            const size_t at = (e / C) * Cs + c;
-            bad = bad || !(fabsf(y) < 60000.f);
-            const _Float16 h = (_Float16)y;
-            hi[at] = h;
-            lo[at] = (_Float16)(y - (float)h);
-        }
-    }
-    if (bad) atomicOr(overflow, 1);
-    if (omax) block_absmax_to(omax, mx);
-}
-
-// (C % 4 == 0: four channels of one output pixel per thread -- 16-byte accesses, 32-bit index arithmetic)
-__global__ void __launch_bounds__(256) act_fwd_v4_kernel(const ActParams a, float* __restrict__ out, unsigned nq, unsigned* omax,
-                                                         _Float16* __restrict__ hi, _Float16* __restrict__ lo, int Cs,
-                                                         int* __restrict__ overflow) {
-    const int C = a.C;
-    const unsigned Q = (unsigned)C >> 2;
-    const float ks = 1.0f / (1.0f - a.drop_rate);
-    const unsigned OW = a.W >> 1, OH = a.H >> 1;
+    const I OW = a.W >> 1, OH = a.H >> 1;
     float mx = 0.f;
     bool bad = false;
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < nq; i += gridDim.x * 256) {
-        const unsigned row = i / Q, q = i - row * Q;
-        const int c = 4 * (int)q;
-        const float4 sc4 = *reinterpret_cast<const float4*>(a.stat + 2 * C + c), sh4 = *reinterpret_cast<const float4*>(a.stat + 3 * C + c);
-        const float sc[4] = {sc4.x, sc4.y, sc4.z, sc4.w}, sh[4] = {sh4.x, sh4.y, sh4.z, sh4.w};
-        float y[4];
+    for (I i = (I)blockIdx.x * 256 + threadIdx.x; i < nu; i += (I)gridDim.x * 256) {
+        const I row = i / U, u = i - row * U;
+        const int c = V * (int)u;
+        float sc[V], sh[V], y[V];
+        ldv<V>(sc, a.stat + 2 * C + c);
+        ldv<V>(sh, a.stat + 3 * C + c);
         if (!a.pool) {
-            const float4 z4 = reinterpret_cast<const float4*>(a.z)[i];
-            const float zz[4] = {z4.x, z4.y, z4.z, z4.w};
+            float zz[V];
+            ldv<V>(zz, a.z, i);
             const size_t e = (size_t)row * C + c;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) y[k] = act_of(zz[k] * sc[k] + sh[k], a.act) * drop_mul(a.drop_key, e + k, a.drop_rate, ks);
+            for (int k = 0; k < V; ++k) y[k] = act_of(zz[k] * sc[k] + sh[k], a.act) * drop_mul(a.drop_key, e + k, a.drop_rate, ks);
         } else {
-            const unsigned ox = row % OW, t = row / OW, oy = t % OH, b = t / OH;
+            const I ox = row % OW, t = row / OW, oy = t % OH, b = t / OH;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const size_t px = ((size_t)b * a.H + 2 * oy + (j >> 1)) * a.W + 2 * ox + (j & 1);
-                const float4 z4 = reinterpret_cast<const float4*>(a.z)[px * Q + q];
-                const float zz[4] = {z4.x, z4.y, z4.z, z4.w};
+                float zz[V];
+                ldv<V>(zz, a.z, px * U + u);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
+                for (int k = 0; k < V; ++k) {
                     const float yj = act_of(zz[k] * sc[k] + sh[k], a.act) * drop_mul(a.drop_key, px * C + c + k, a.drop_rate, ks);
                     if (j == 0 || yj > y[k]) y[k] = yj;
                 }
             }
         }
-        reinterpret_cast<float4*>(out)[i] = make_float4(y[0], y[1], y[2], y[3]);
+        stv<V>(out, i, y);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) mx = fmaxf(mx, fabsf(y[k]));
+        for (int k = 0; k < V; ++k) mx = fmaxf(mx, fabsf(y[k]));
         if (hi) {
-            union { _Float16 h[4]; uint2 u; } va, vb;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                bad = bad || !(fabsf(y[k]) < 60000.f);
-                va.h[k] = (_Float16)y[k];
-                vb.h[k] = (_Float16)(y[k] - (float)va.h[k]);
-            }
             const size_t at = (size_t)row * Cs + c;
-            *reinterpret_cast<uint2*>(hi + at) = va.u;
-            *reinterpret_cast<uint2*>(lo + at) = vb.u;
+            st_planes<V>(hi + at, lo + at, y, bad);
         }
     }
     if (bad) atomicOr(overflow, 1);
@@ -358,11 +331,13 @@ hipError_t launch_act_fwd(const ActParams& a, float* out, unsigned* omax, _Float
     if (a.C % 4 == 0 && (!hi || Cs % 4 == 0) && nout < 0xfffffff0ull) {
         const unsigned nq = (unsigned)(nout / 4);
         const unsigned blocks = std::min<unsigned>(4096, (nq + 255) / 256);
-        hipLaunchKernelGGL(act_fwd_v4_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, stream, a, out, nq, omax, hi, lo, Cs, overflow);
+        hipLaunchKernelGGL((act_fwd_kernel<4, unsigned>), dim3(blocks ? blocks : 1), dim3(256), 0, stream, a, out, nq, omax, hi, lo, Cs,
+                           overflow);
         return hipGetLastError();
     }
     const unsigned blocks = (unsigned)std::min<size_t>(2048, (nout + 255) / 256);
-    hipLaunchKernelGGL(act_fwd_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, stream, a, out, nout, omax, hi, lo, Cs, overflow);
+    hipLaunchKernelGGL((act_fwd_kernel<1, size_t>), dim3(blocks ? blocks : 1), dim3(256), 0, stream, a, out, nout, omax, hi, lo, Cs,
+                       overflow);
     return hipGetLastError();
 }
 
@@ -444,33 +419,23 @@ __global__ void __launch_bounds__(256) split_dyn_kernel(const float* __restrict_
     bool bad = false;
     if ((C & 3) == 0 && Cs == C) {   // whole float4 / 8-byte units
         const size_t n4 = total / 4;
-        const float4* const x4 = reinterpret_cast<const float4*>(x);
-        uint2* const h2 = reinterpret_cast<uint2*>(hi);
-        uint2* const l2 = reinterpret_cast<uint2*>(lo);
         for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-            const float4 v = x4[i];
-            const float f[4] = {v.x * scale, v.y * scale, v.z * scale, v.w * scale};
-            union { _Float16 h[4]; uint2 u; } a, b;
+            float f[4];
+            ldv<4>(f, x, i);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
+                f[k] *= scale;
                 mx = fmaxf(mx, fabsf(f[k]));
-                bad = bad || !(fabsf(f[k]) < 60000.f);
-                a.h[k] = (_Float16)f[k];
-                b.h[k] = (_Float16)(f[k] - (float)a.h[k]);
             }
-            h2[i] = a.u;
-            l2[i] = b.u;
+            st_planes<4>(hi + 4 * i, lo + 4 * i, f, bad);
         }
     } else {
         for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
             const size_t px = e / Cs;
             const int c = (int)(e - px * Cs);
-            const float v = c < C ? x[px * C + c] * scale : 0.f;
-            mx = fmaxf(mx, fabsf(v));
-            bad = bad || !(fabsf(v) < 60000.f);
-            const _Float16 h = (_Float16)v;
-            hi[e] = h;
-            lo[e] = (_Float16)(v - (float)h);
+            const float v[1] = {c < C ? x[px * C + c] * scale : 0.f};
+            mx = fmaxf(mx, fabsf(v[0]));
+            st_planes<1>(hi + e, lo + e, v, bad);
         }
     }
     if (bad) atomicOr(overflow, 1);
@@ -486,127 +451,46 @@ hipError_t launch_split_dyn(const float* x, size_t npix, int C, int Cs, const un
     return hipGetLastError();
 }
 
+// (max |g| and max |xhat| of the block go to gx[0], gx[1]: with max |gamma rstd| they bound |dz| (bn_bwd_apply))
+template <int V, typename I>
 __global__ void __launch_bounds__(256) act_bwd_kernel(const ActParams a, const float* __restrict__ dy0,
-                                                      const float* __restrict__ dy1, float* __restrict__ g, size_t Nrows,
-                                                      int Cb, int k, double* __restrict__ part, unsigned* gx) {
-    __shared__ double sm[2][256];
-    __shared__ unsigned smx[2][256];
-    float mg = 0.f, mxh = 0.f;   // max |g| and max |xhat| seen by this thread: with max |gamma rstd| they bound |dz| (bn_bwd_apply)
-    const int tid = threadIdx.x;
-    const int r = tid / Cb, cl = tid - r * Cb;
-    const int C = a.C;
-    const int c = cl + blockIdx.y * 256;
-    const size_t rpb = (Nrows + gridDim.x - 1) / gridDim.x;
-    const size_t r0 = (size_t)blockIdx.x * rpb, r1 = std::min(Nrows, r0 + rpb);
-    double s1 = 0.0, s2 = 0.0;
-    if (c < C) {
-        const float mean = a.stat[c], rstd = a.stat[C + c], sc = a.stat[2 * C + c], sh = a.stat[3 * C + c];
-        const float ks = 1.0f / (1.0f - a.drop_rate);
-        const int OW = a.W >> 1, OH = a.H >> 1;
-        for (size_t row = r0 + r; row < r1; row += k) {
-            const size_t e = row * C + c;
-            float d = dy0[e];
-            if (dy1) d += dy1[e];
-            if (!a.pool) {
-                const float zz = a.z[e];
-                const float v = zz * sc + sh;
-                const float gg = d * drop_mul(a.drop_key, e, a.drop_rate, ks) * dact_of(v, a.act);
-                g[e] = gg;
-                const float xh = (zz - mean) * rstd;
-                s1 += (double)gg;
-                s2 += (double)gg * (double)xh;
-                mg = fmaxf(mg, fabsf(gg));
-                mxh = fmaxf(mxh, fabsf(xh));
-            } else {
-                size_t q = row;
-                const int ox = (int)(q % OW); q /= OW;
-                const int oy = (int)(q % OH);
-                const int b = (int)(q / OH);
-                size_t idx[4];
-                float zz[4], dm[4], vv[4];
-                int arg = 0;
-                float best = 0.f;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    idx[j] = (((size_t)b * a.H + 2 * oy + (j >> 1)) * a.W + 2 * ox + (j & 1)) * C + c;
-                    zz[j] = a.z[idx[j]];
-                    vv[j] = zz[j] * sc + sh;
-                    dm[j] = drop_mul(a.drop_key, idx[j], a.drop_rate, ks);
-                    const float y = act_of(vv[j], a.act) * dm[j];
-                    if (j == 0 || y > best) { best = y; arg = j; }
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float gg = j == arg ? d * dm[j] * dact_of(vv[j], a.act) : 0.f;
-                    g[idx[j]] = gg;
-                    const float xh = (zz[j] - mean) * rstd;
-                    mxh = fmaxf(mxh, fabsf(xh));
-                    if (j == arg) {
-                        s1 += (double)gg;
-                        s2 += (double)gg * (double)xh;
-                        mg = fmaxf(mg, fabsf(gg));
-                    }
-                }
-            }
-        }
-    }
-    sm[0][tid] = s1;
-    sm[1][tid] = s2;
-    smx[0][tid] = __float_as_uint(mg);
-    smx[1][tid] = __float_as_uint(mxh);
-    __syncthreads();
-    if (r == 0 && c < C) {
-        for (int j = 1; j < k; ++j) { s1 += sm[0][j * Cb + cl]; s2 += sm[1][j * Cb + cl]; }
-        part[((size_t)blockIdx.x * 2 + 0) * C + c] = s1;
-        part[((size_t)blockIdx.x * 2 + 1) * C + c] = s2;
-    }
-    if (gx && tid < 2) {   // (integer max of non-negative float bits: order-independent)
-        unsigned m = 0u;
-        for (int j = 0; j < (int)blockDim.x; ++j) m = max(m, smx[tid][j]);
-        if (m > *reinterpret_cast<volatile unsigned*>(gx + tid)) atomicMax(gx + tid, m);
-    }
-}
-
-// The same for C % 4 == 0 (every layer of the shipped widths): a thread owns FOUR consecutive channels of the rows it walks -- 16-byte
-// loads and stores, the per-channel constants in registers, no division in the row loop (the scalar kernel above spends most of
-// its time on 4-byte accesses and 64-bit index arithmetic: lu0, 19 M elements, 149 us against 50 us of memory time).  Same partial-sum
-// layout (part[block][2][C], fp64, fixed order), so the finalize kernel does not change.
-__global__ void __launch_bounds__(256) act_bwd_v4_kernel(const ActParams a, const float* __restrict__ dy0,
-                                                         const float* __restrict__ dy1, float* __restrict__ g, unsigned Nrows,
-                                                         int Qb, int R, double* __restrict__ part, unsigned* gx) {
-    __shared__ double sm[2][256][4];
+                                                      const float* __restrict__ dy1, float* __restrict__ g, I Nrows,
+                                                      int Ub, int R, double* __restrict__ part, unsigned* gx) {
+    __shared__ double sm[2][256][V];
     __shared__ unsigned smx[2][256];
     const int tid = threadIdx.x;
-    const int r = tid / Qb, ql = tid - r * Qb;
-    const int C = a.C, Q = C >> 2;
-    const int q = ql + blockIdx.y * 256;            // channel quad
-    const unsigned rpb = (Nrows + gridDim.x - 1) / gridDim.x;
-    const unsigned r0 = blockIdx.x * rpb, r1 = min(Nrows, r0 + rpb);
-    double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
+    const int r = tid / Ub, ul = tid - r * Ub;
+    const int C = a.C, U = C >> (V / 2);   // (U = C / V)
+    const int u = ul + blockIdx.y * 256;
+    const I rpb = (Nrows + gridDim.x - 1) / gridDim.x;
+    const I r0 = (I)blockIdx.x * rpb, r1 = min(Nrows, r0 + rpb);
+    double s1[V] = {}, s2[V] = {};
     float mg = 0.f, mxh = 0.f;
-    const bool on = r < R && q < Q;
-    if (on) {
-        const int c = 4 * q;
-        const float4 mean4 = *reinterpret_cast<const float4*>(a.stat + c), rstd4 = *reinterpret_cast<const float4*>(a.stat + C + c);
-        const float4 sc4 = *reinterpret_cast<const float4*>(a.stat + 2 * C + c), sh4 = *reinterpret_cast<const float4*>(a.stat + 3 * C + c);
-        const float mean[4] = {mean4.x, mean4.y, mean4.z, mean4.w}, rstd[4] = {rstd4.x, rstd4.y, rstd4.z, rstd4.w};
-        const float sc[4] = {sc4.x, sc4.y, sc4.z, sc4.w}, sh[4] = {sh4.x, sh4.y, sh4.z, sh4.w};
+    if (r < R && u < U) {
+        const int c = V * u;
+        float mean[V], rstd[V], sc[V], sh[V];
+        ldv<V>(mean, a.stat + c);
+        ldv<V>(rstd, a.stat + C + c);
+        ldv<V>(sc, a.stat + 2 * C + c);
+        ldv<V>(sh, a.stat + 3 * C + c);
         const float ks = 1.0f / (1.0f - a.drop_rate);
-        const unsigned OW = a.W >> 1, OH = a.H >> 1;
-        for (unsigned row = r0 + r; row < r1; row += R) {
-            float4 d4 = reinterpret_cast<const float4*>(dy0)[(size_t)row * Q + q];
+        const I OW = a.W >> 1, OH = a.H >> 1;
+        for (I row = r0 + r; row < r1; row += R) {
+            const size_t o = (size_t)row * U + u;
+            float d[V];
+            ldv<V>(d, dy0, o);
             if (dy1) {
-                const float4 e4 = reinterpret_cast<const float4*>(dy1)[(size_t)row * Q + q];
-                d4.x += e4.x; d4.y += e4.y; d4.z += e4.z; d4.w += e4.w;
+                float d1[V];
+                ldv<V>(d1, dy1, o);
+#pragma unroll
+                for (int k = 0; k < V; ++k) d[k] += d1[k];
             }
-            const float d[4] = {d4.x, d4.y, d4.z, d4.w};
             if (!a.pool) {
                 const size_t e = (size_t)row * C + c;
-                const float4 z4 = reinterpret_cast<const float4*>(a.z)[(size_t)row * Q + q];
-                const float zz[4] = {z4.x, z4.y, z4.z, z4.w};
-                float gg[4];
+                float zz[V], gg[V];
+                ldv<V>(zz, a.z, o);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
+                for (int k = 0; k < V; ++k) {
                     const float v = zz[k] * sc[k] + sh[k];
                     gg[k] = d[k] * drop_mul(a.drop_key, e + k, a.drop_rate, ks) * dact_of(v, a.act);
                     const float xh = (zz[k] - mean[k]) * rstd[k];
@@ -615,32 +499,31 @@ __global__ void __launch_bounds__(256) act_bwd_v4_kernel(const ActParams a, cons
                     mg = fmaxf(mg, fabsf(gg[k]));
                     mxh = fmaxf(mxh, fabsf(xh));
                 }
-                reinterpret_cast<float4*>(g)[(size_t)row * Q + q] = make_float4(gg[0], gg[1], gg[2], gg[3]);
+                stv<V>(g, o, gg);
             } else {
-                const unsigned ox = row % OW, t = row / OW, oy = t % OH, b = t / OH;
-                size_t px[4];
-                float zz[4][4], vv[4][4], dm[4][4];
-                int arg[4] = {0, 0, 0, 0};
-                float best[4] = {0.f, 0.f, 0.f, 0.f};
+                const I ox = row % OW, t = row / OW, oy = t % OH, b = t / OH;
+                size_t ow[4];   // (unit index of each pixel of the window)
+                float zz[4][V], vv[4][V], dm[4][V];
+                int arg[V] = {};
+                float best[V] = {};
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    px[j] = ((size_t)b * a.H + 2 * oy + (j >> 1)) * a.W + 2 * ox + (j & 1);
-                    const float4 z4 = reinterpret_cast<const float4*>(a.z)[px[j] * Q + q];
-                    const float zj[4] = {z4.x, z4.y, z4.z, z4.w};
+                    const size_t px = ((size_t)b * a.H + 2 * oy + (j >> 1)) * a.W + 2 * ox + (j & 1);
+                    ow[j] = px * U + u;
+                    ldv<V>(zz[j], a.z, ow[j]);
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        zz[j][k] = zj[k];
-                        vv[j][k] = zj[k] * sc[k] + sh[k];
-                        dm[j][k] = drop_mul(a.drop_key, px[j] * C + c + k, a.drop_rate, ks);
+                    for (int k = 0; k < V; ++k) {
+                        vv[j][k] = zz[j][k] * sc[k] + sh[k];
+                        dm[j][k] = drop_mul(a.drop_key, px * C + c + k, a.drop_rate, ks);
                         const float y = act_of(vv[j][k], a.act) * dm[j][k];
                         if (j == 0 || y > best[k]) { best[k] = y; arg[k] = j; }
                     }
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    float gg[4];
+                    float gg[V];
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) {
+                    for (int k = 0; k < V; ++k) {
                         gg[k] = j == arg[k] ? d[k] * dm[j][k] * dact_of(vv[j][k], a.act) : 0.f;
                         const float xh = (zz[j][k] - mean[k]) * rstd[k];
                         mxh = fmaxf(mxh, fabsf(xh));
@@ -650,44 +533,43 @@ __global__ void __launch_bounds__(256) act_bwd_v4_kernel(const ActParams a, cons
                             mg = fmaxf(mg, fabsf(gg[k]));
                         }
                     }
-                    reinterpret_cast<float4*>(g)[px[j] * Q + q] = make_float4(gg[0], gg[1], gg[2], gg[3]);
+                    stv<V>(g, ow[j], gg);
                 }
             }
         }
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { sm[0][tid][k] = s1[k]; sm[1][tid][k] = s2[k]; }
+    for (int k = 0; k < V; ++k) { sm[0][tid][k] = s1[k]; sm[1][tid][k] = s2[k]; }
     smx[0][tid] = __float_as_uint(mg);
     smx[1][tid] = __float_as_uint(mxh);
     __syncthreads();
-    if (r == 0 && q < Q) {
+    if (r == 0 && u < U) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            double t1 = s1[k], t2 = s2[k];
-            for (int j = 1; j < R; ++j) { t1 += sm[0][j * Qb + ql][k]; t2 += sm[1][j * Qb + ql][k]; }
-            part[((size_t)blockIdx.x * 2 + 0) * C + 4 * q + k] = t1;
-            part[((size_t)blockIdx.x * 2 + 1) * C + 4 * q + k] = t2;
+        for (int k = 0; k < V; ++k) {
+            for (int j = 1; j < R; ++j) { s1[k] += sm[0][j * Ub + ul][k]; s2[k] += sm[1][j * Ub + ul][k]; }
+            part[((size_t)blockIdx.x * 2 + 0) * C + V * u + k] = s1[k];
+            part[((size_t)blockIdx.x * 2 + 1) * C + V * u + k] = s2[k];
         }
     }
-    if (gx && tid < 2) {
+    if (gx && tid < 2) {   // (over the Ub * R threads that walk rows; integer max of non-negative float bits: order-independent)
         unsigned m = 0u;
-        for (int j = 0; j < 256; ++j) m = max(m, smx[tid][j]);
+        for (int j = 0; j < Ub * R; ++j) m = max(m, smx[tid][j]);
         if (m > *reinterpret_cast<volatile unsigned*>(gx + tid)) atomicMax(gx + tid, m);
     }
 }
 
 hipError_t launch_act_bwd(const ActParams& a, const float* dy0, const float* dy1, float* g, double* part, int nblk,
                           unsigned* gx, hipStream_t stream) {
-    const ChanLayout l = chan_layout(a.C);
     const size_t rows = (size_t)a.B * (a.pool ? a.H / 2 : a.H) * (a.pool ? a.W / 2 : a.W);
     if (a.C % 4 == 0 && rows < 0x7fffffffull) {
-        const int Q = a.C / 4, Qb = std::min(Q, 256), R = std::max(1, 256 / Qb), cbl = (Q + 255) / 256;
-        hipLaunchKernelGGL(act_bwd_v4_kernel, dim3((unsigned)nblk, (unsigned)cbl), dim3(256), 0, stream, a, dy0, dy1, g, (unsigned)rows,
-                           Qb, R, part, gx);
+        const ChanLayout l = chan_layout(a.C, 4);
+        hipLaunchKernelGGL((act_bwd_kernel<4, unsigned>), dim3((unsigned)nblk, (unsigned)l.cblocks), dim3(l.threads), 0, stream, a, dy0,
+                           dy1, g, (unsigned)rows, l.Ub, l.R, part, gx);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(act_bwd_kernel, dim3((unsigned)nblk, (unsigned)l.cblocks), dim3((unsigned)l.threads), 0, stream, a,
-                       dy0, dy1, g, rows, l.Cb, l.k, part, gx);
+    const ChanLayout l = chan_layout(a.C, 1);
+    hipLaunchKernelGGL((act_bwd_kernel<1, size_t>), dim3((unsigned)nblk, (unsigned)l.cblocks), dim3(l.threads), 0, stream, a, dy0,
+                       dy1, g, rows, l.Ub, l.R, part, gx);
     return hipGetLastError();
 }
 
@@ -715,33 +597,19 @@ hipError_t launch_bn_bwd_finalize(const double* part, int nblk, size_t N, int C,
     return hipGetLastError();
 }
 
-// (grid-stride; at most one atomic per block on the tensor's max word)
-__global__ void __launch_bounds__(256) bn_bwd_apply_kernel(float* __restrict__ g, const float* __restrict__ z,
-                                                           const float* __restrict__ stat, const float* __restrict__ m12,
-                                                           size_t n, int C, unsigned* gmax) {
-    float mx = 0.f;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
-        const int c = (int)(e % C);
-        const float xh = (z[e] - stat[c]) * stat[C + c];
-        const float v = stat[2 * C + c] * (g[e] - m12[c] - xh * m12[C + c]);
-        g[e] = v;
-        mx = fmaxf(mx, fabsf(v));
-    }
-    if (gmax) block_absmax_to(gmax, mx);
-}
-
-// The same with the (hi, lo) planes conv_f16x3's input-gradient launches read written in the same pass (round 4; no second trip
-// through the tensor).  Their power-of-two scale has to be known before the first element: |dz| <= max_c|gamma rstd| * (|g| +
+// dz = gamma rstd (g - mean g - xhat mean(g xhat)) in place (grid-stride over units; at most one atomic per block on the tensor's
+// max word).  PLANES: the (hi, lo) planes conv_f16x3's input-gradient launches read, written in the same pass (round 4; no second
+// trip through the tensor).  Their power-of-two scale has to be known before the first element: |dz| <= max_c|gamma rstd| * (|g| +
 // |mean g| + |xhat| |mean g xhat|) <= smax * gmax * (2 + xhmax)  (|mean g| <= gmax, |mean g xhat| <= gmax * E|xhat| <= gmax), the
 // three maxima tracked by bn_finalize / act_bwd -- a true bound, 2^2 .. 2^3 above the real maximum, placed at 2^14.
-template <bool VEC>
-__global__ void __launch_bounds__(256) bn_bwd_apply_planes_kernel(float* __restrict__ g, const float* __restrict__ z,
-                                                                  const float* __restrict__ stat, const float* __restrict__ m12,
-                                                                  unsigned n, int C, int Cs, unsigned* gmax, const unsigned* __restrict__ bw,
-                                                                  float* __restrict__ inv_scale, _Float16* __restrict__ hi,
-                                                                  _Float16* __restrict__ lo, int* __restrict__ overflow) {
+template <int V, typename I, bool PLANES>
+__global__ void __launch_bounds__(256) bn_bwd_apply_kernel(float* __restrict__ g, const float* __restrict__ z,
+                                                           const float* __restrict__ stat, const float* __restrict__ m12,
+                                                           I n, int C, int Cs, unsigned* gmax, const unsigned* __restrict__ bw,
+                                                           float* __restrict__ inv_scale, _Float16* __restrict__ hi,
+                                                           _Float16* __restrict__ lo, int* __restrict__ overflow) {
     float scale = 1.f;
-    {
+    if constexpr (PLANES) {
         const float bound = __uint_as_float(bw[0]) * __uint_as_float(bw[1]) * (2.f + __uint_as_float(bw[2]));
         const unsigned bb = __float_as_uint(bound);
         const int e = (int)((bb >> 23) & 0xFFu);
@@ -753,51 +621,36 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_planes_kernel(float* __restr
     }
     float mx = 0.f;
     bool bad = false;
-    if constexpr (VEC) {   // C % 4 == 0: four channels of one pixel per thread
-        const unsigned n4 = n / 4;
-        for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
-            const unsigned e = i * 4, px = e / (unsigned)C, c = e - px * (unsigned)C;
-            const float4 gv = reinterpret_cast<const float4*>(g)[i], zv = reinterpret_cast<const float4*>(z)[i];
-            const float4 mean = *reinterpret_cast<const float4*>(stat + c), rstd = *reinterpret_cast<const float4*>(stat + C + c);
-            const float4 sc = *reinterpret_cast<const float4*>(stat + 2 * C + c);
-            const float4 m1 = *reinterpret_cast<const float4*>(m12 + c), m2 = *reinterpret_cast<const float4*>(m12 + C + c);
-            float v[4];
-            v[0] = sc.x * (gv.x - m1.x - (zv.x - mean.x) * rstd.x * m2.x);
-            v[1] = sc.y * (gv.y - m1.y - (zv.y - mean.y) * rstd.y * m2.y);
-            v[2] = sc.z * (gv.z - m1.z - (zv.z - mean.z) * rstd.z * m2.z);
-            v[3] = sc.w * (gv.w - m1.w - (zv.w - mean.w) * rstd.w * m2.w);
-            reinterpret_cast<float4*>(g)[i] = make_float4(v[0], v[1], v[2], v[3]);
-            union { _Float16 h[4]; uint2 u; } a, b;
+    const I nu = n / V;
+    for (I i = (I)blockIdx.x * 256 + threadIdx.x; i < nu; i += (I)gridDim.x * 256) {
+        const I e = i * V, px = e / (I)C;
+        const int c = (int)(e - px * (I)C);
+        float gv[V], zv[V], mean[V], rstd[V], sc[V], m1[V], m2[V], v[V];
+        ldv<V>(gv, g, i);
+        ldv<V>(zv, z, i);
+        ldv<V>(mean, stat + c);
+        ldv<V>(rstd, stat + (C + c));
+        ldv<V>(sc, stat + (2 * C + c));
+        ldv<V>(m1, m12 + c);
+        ldv<V>(m2, m12 + (C + c));
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                mx = fmaxf(mx, fabsf(v[k]));
-                const float f = v[k] * scale;
-                bad = bad || !(fabsf(f) < 60000.f);
-                a.h[k] = (_Float16)f;
-                b.h[k] = (_Float16)(f - (float)a.h[k]);
-            }
-            const size_t at = (size_t)px * Cs + c;
-            *reinterpret_cast<uint2*>(hi + at) = a.u;
-            *reinterpret_cast<uint2*>(lo + at) = b.u;
-            if (c + 4 == (unsigned)C && Cs > C) {   // the pad channels of the pixel's last octet (the slot is shared between layers)
-                *reinterpret_cast<uint2*>(hi + at + 4) = make_uint2(0u, 0u);
-                *reinterpret_cast<uint2*>(lo + at + 4) = make_uint2(0u, 0u);
-            }
+        for (int k = 0; k < V; ++k) v[k] = sc[k] * (gv[k] - m1[k] - (zv[k] - mean[k]) * rstd[k] * m2[k]);
+        stv<V>(g, i, v);
+        float f[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            mx = fmaxf(mx, fabsf(v[k]));
+            f[k] = v[k] * scale;
         }
-    } else {
-        for (unsigned e = blockIdx.x * 256 + threadIdx.x; e < n; e += gridDim.x * 256) {
-            const unsigned px = e / (unsigned)C, c = e - px * (unsigned)C;
-            const float xh = (z[e] - stat[c]) * stat[C + c];
-            const float v = stat[2 * C + c] * (g[e] - m12[c] - xh * m12[C + c]);
-            g[e] = v;
-            mx = fmaxf(mx, fabsf(v));
-            const float f = v * scale;
-            bad = bad || !(fabsf(f) < 60000.f);
-            const _Float16 h = (_Float16)f;
-            hi[(size_t)px * Cs + c] = h;
-            lo[(size_t)px * Cs + c] = (_Float16)(f - (float)h);
-            if (c + 1 == (unsigned)C)
-                for (int k = C; k < Cs; ++k) { hi[(size_t)px * Cs + k] = (_Float16)0.f; lo[(size_t)px * Cs + k] = (_Float16)0.f; }
+        if constexpr (PLANES) {
+            const size_t at = (size_t)px * Cs + c;
+            st_planes<V>(hi + at, lo + at, f, bad);
+            if (c + V == C) {   // the pad channels C .. Cs-1 of the pixel's last octet (the slot is shared between layers)
+                const float zero[V] = {};
+#pragma unroll
+                for (int k = V; k < 8; k += V)   // (Cs - C < 8: launch_bn_bwd_apply_max)
+                    if (c + k < Cs) st_planes<V>(hi + at + k, lo + at + k, zero, bad);
+            }
         }
     }
     if (bad) atomicOr(overflow, 1);
@@ -813,60 +666,42 @@ hipError_t launch_bn_bwd_apply_max(float* g, const float* z, const float* stat, 
     // (planes asked for on a tensor the 32-bit-index kernel cannot address: refuse -- the caller's convolutions and weight
     // gradients would read planes and an inverse scale nobody wrote.  Batch x resolution x channels >= 2^32: not a shape of this graph)
     if (hi && n >= 0xFFFFFFF0ull) return hipErrorInvalidValue;
+    if (hi && (Cs < C || Cs - C >= 8)) return hipErrorInvalidValue;   // (the planes are C rounded up to 8 channels)
     if (hi) {
         const unsigned bv = (unsigned)std::min<size_t>(2048, (n / 4 + 255) / 256 + 1);
         if (C % 4 == 0 && Cs % 4 == 0)
-            hipLaunchKernelGGL(bn_bwd_apply_planes_kernel<true>, dim3(bv), dim3(256), 0, stream, g, z, stat, m12, (unsigned)n, C, Cs, gmax,
-                               bw, inv_scale, hi, lo, overflow);
+            hipLaunchKernelGGL((bn_bwd_apply_kernel<4, unsigned, true>), dim3(bv), dim3(256), 0, stream, g, z, stat, m12, (unsigned)n, C, Cs,
+                               gmax, bw, inv_scale, hi, lo, overflow);
         else
-            hipLaunchKernelGGL(bn_bwd_apply_planes_kernel<false>, dim3(blocks ? blocks : 1), dim3(256), 0, stream, g, z, stat, m12,
+            hipLaunchKernelGGL((bn_bwd_apply_kernel<1, unsigned, true>), dim3(blocks ? blocks : 1), dim3(256), 0, stream, g, z, stat, m12,
                                (unsigned)n, C, Cs, gmax, bw, inv_scale, hi, lo, overflow);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, stream, g, z, stat, m12, n, C, gmax);
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<1, size_t, false>), dim3(blocks ? blocks : 1), dim3(256), 0, stream, g, z, stat, m12, n, C, 0,
+                       gmax, nullptr, nullptr, nullptr, nullptr, nullptr);
     return hipGetLastError();
 }
 
-__global__ void __launch_bounds__(256) leaky_bwd_s2d_kernel(const float* __restrict__ d_us, const float* __restrict__ us,
-                                                            int S, int C, float* __restrict__ gS, size_t n, float slope, unsigned* gmax) {
+template <int V, typename I>
+__global__ void __launch_bounds__(256) leaky_bwd_s2d_kernel(const float* __restrict__ d_us, const float* __restrict__ us, I S, I U,
+                                                            float* __restrict__ gS, I nu, float slope, unsigned* gmax) {
     float mx = 0.f;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
-        const int c = (int)(e % C);
-        size_t r = e / C;
-        const int q = (int)(r & 3); r >>= 2;
-        const int j = (int)(r % S); r /= S;
-        const int i = (int)(r % S);
-        const size_t b = r / S;
-        const size_t src = ((b * (2 * S) + 2 * i + (q >> 1)) * (size_t)(2 * S) + 2 * j + (q & 1)) * C + c;
-        const float v = d_us[src] * (us[src] > 0.f ? 1.f : slope);
-        gS[e] = v;
-        mx = fmaxf(mx, fabsf(v));
-    }
-    if (gmax) block_absmax_to(gmax, mx);
-}
-
-// C % 4 == 0 and < 2^32 elements (every layer of the shipped widths): four channels per thread, 16-byte accesses, 32-bit index
-// arithmetic (the scalar kernel: 146 us for 3 x 75 MB at 8 x 256 x 256 x 36, this one the memory time)
-__global__ void __launch_bounds__(256) leaky_bwd_s2d_v4_kernel(const float4* __restrict__ d_us, const float4* __restrict__ us,
-                                                               unsigned S, unsigned Q, float4* __restrict__ gS, unsigned n4, float slope,
-                                                               unsigned* gmax) {
-    float mx = 0.f;
-    for (unsigned e = blockIdx.x * 256 + threadIdx.x; e < n4; e += gridDim.x * 256) {
-        const unsigned q4 = e % Q;
-        unsigned r = e / Q;
-        const unsigned q = r & 3u; r >>= 2;
-        const unsigned j = r % S; r /= S;
-        const unsigned i = r % S;
-        const unsigned b = r / S;
-        const unsigned src = ((b * (2 * S) + 2 * i + (q >> 1)) * (2 * S) + 2 * j + (q & 1u)) * Q + q4;
-        const float4 d = d_us[src], u = us[src];
-        float4 v;
-        v.x = d.x * (u.x > 0.f ? 1.f : slope);
-        v.y = d.y * (u.y > 0.f ? 1.f : slope);
-        v.z = d.z * (u.z > 0.f ? 1.f : slope);
-        v.w = d.w * (u.w > 0.f ? 1.f : slope);
-        gS[e] = v;
-        mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+    for (I e = (I)blockIdx.x * 256 + threadIdx.x; e < nu; e += (I)gridDim.x * 256) {
+        const I u = e % U;
+        I r = e / U;
+        const I q = r & 3; r >>= 2;
+        const I j = r % S; r /= S;
+        const I i = r % S;
+        const I b = r / S;
+        const I src = ((b * (2 * S) + 2 * i + (q >> 1)) * (2 * S) + 2 * j + (q & 1)) * U + u;
+        float d[V], y[V], v[V];
+        ldv<V>(d, d_us, src);
+        ldv<V>(y, us, src);
+#pragma unroll
+        for (int k = 0; k < V; ++k) v[k] = d[k] * (y[k] > 0.f ? 1.f : slope);
+        stv<V>(gS, e, v);
+#pragma unroll
+        for (int k = 0; k < V; ++k) mx = fmaxf(mx, fabsf(v[k]));
     }
     if (gmax) block_absmax_to(gmax, mx);
 }
@@ -877,12 +712,13 @@ hipError_t launch_leaky_bwd_s2d_max(const float* d_us, const float* us, int B, i
     if (C % 4 == 0 && n < 0xffffffffull) {
         const unsigned n4 = (unsigned)(n / 4);
         const unsigned blocks = std::min(2048u, (n4 + 255u) / 256u);
-        hipLaunchKernelGGL(leaky_bwd_s2d_v4_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, stream, reinterpret_cast<const float4*>(d_us),
-                           reinterpret_cast<const float4*>(us), (unsigned)S, (unsigned)(C / 4), reinterpret_cast<float4*>(gS), n4, slope, gmax);
+        hipLaunchKernelGGL((leaky_bwd_s2d_kernel<4, unsigned>), dim3(blocks ? blocks : 1), dim3(256), 0, stream, d_us, us, (unsigned)S,
+                           (unsigned)(C / 4), gS, n4, slope, gmax);
         return hipGetLastError();
     }
     const unsigned blocks = (unsigned)std::min<size_t>(1024, (n + 255) / 256);
-    hipLaunchKernelGGL(leaky_bwd_s2d_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, stream, d_us, us, S, C, gS, n, slope, gmax);
+    hipLaunchKernelGGL((leaky_bwd_s2d_kernel<1, size_t>), dim3(blocks ? blocks : 1), dim3(256), 0, stream, d_us, us, (size_t)S, (size_t)C,
+                       gS, n, slope, gmax);
     return hipGetLastError();
 }
 
@@ -1074,9 +910,9 @@ __global__ void __launch_bounds__(256) head_bwd_kernel(const float* __restrict__
 hipError_t launch_head_bwd(const float* x, const float* dt0, const float* w, size_t N, int C, int K, float* dx,
                            double* part, int nblk, hipStream_t stream) {
     if (K > kMaxK) return hipErrorInvalidValue;
-    const ChanLayout l = chan_layout(C);
+    const ChanLayout l = chan_layout(C, 1);
     hipLaunchKernelGGL(head_bwd_kernel, dim3((unsigned)nblk, (unsigned)l.cblocks), dim3((unsigned)l.threads), 0, stream, x,
-                       dt0, w, N, C, K, l.Cb, l.k, dx, part);
+                       dt0, w, N, C, K, l.Ub, l.R, dx, part);
     return hipGetLastError();
 }
 
