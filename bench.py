@@ -5,13 +5,19 @@ A "step" is one pass of the hot path over one synthetic slide, measured the way 
   H2D of the slide -> PI2D gather + normalise -> UNet forward (all classes) -> fp16-compat stitch
   [-> band halo exchange + RCCL all-gather, N>1] -> D2H of the probability stack.
 N = 1 goes through the library's host entry point (umx_infer_image_raw: uint16 planes up, uint8 planes down, in row slabs on
-two copy streams under the tile kernels); the same slide resident in HBM (umx_infer_image_dev) is timed right after it
-and reported as `resident` in the same JSON line (kernel-only number, never `value`).
+two copy streams under the tile kernels); with ``--full`` the same slide resident in HBM (umx_infer_image_dev) is timed right
+after it and reported as `resident` in the same JSON line (kernel-only number, never `value`).
 Default workload (``wsi-synth256``): BASELINE.json's metric tile (256x256x2, v2 graph, duo widths 36..1152, seeded
 weights) on the north star's 2-channel synthetic 16384 x 16384 slide (86 x 86 = 7396 tiles) at EVERY N ("strong": N ranks split
 the same slide into bands of patch rows; the N = 1 line is the denominator of the 1 -> 8 curve, 20 steps = 7 s of timed region).
 ``--scaling weak`` gives every rank a 2048-row band of a 2048*N x 16384 slide instead (946 tiles per GPU: rounds 1-3's line; at
-N = 1 the default line carries it as `weak_band`).  Other workloads are parity-test configs of BASELINE.json, not the headline.
+N = 1 the ``--full`` line carries it as `weak_band`).  Other workloads are parity-test configs of BASELINE.json, not the headline.
+
+A plain run does only what the headline needs: set-up, --warmup steps, the --steps timed steps (`value`, `ms_per_step` and the
+roofline of their sampled HIP events), --dump-outputs, the line.  ``--full`` adds everything else the line can carry, each in
+runs of its own after the timed steps (the training leg before them, on an idle chip): `resident`, `host_sync`, `weak_band`, the
+host-path == resident-path check and its CRC-32s, the N > 1 path's first-slide check against sharding.py, the CPU baselines
+and the `f32`, `train` and `configs` legs; those fields are null in a plain line.
 
 Prints ONE JSON line on rank 0.  Launch: `python bench.py [--gpus N]` -- for N > 1 outside torch.distributed.run this
 process starts `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` as a CHILD (before anything
@@ -60,7 +66,10 @@ def parse_args(argv=None):
                     help="conv arithmetic: exact fp32 MFMA, or 3 binary16 MFMA products per fp32 product (default)")
     ap.add_argument("--band-rows", type=int, default=0, help="override rows per GPU")
     ap.add_argument("--cols", type=int, default=0, help="override slide width")
-    ap.add_argument("--cpu-seconds", type=float, default=45.0, help="budget of the CPU-baseline legs (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline (resident path, synchronous call, 2048-row band, "
+                         "host == resident check, first-slide check of the N > 1 path, CPU baselines, f32 / train / configs legs)")
+    ap.add_argument("--cpu-seconds", type=float, default=45.0, help="budget of the CPU-baseline legs of --full (0 = skip)")
     ap.add_argument("--breakdown", action="store_true", help="print the per-layer table to stderr")
     ap.add_argument("--profile-every", type=int, default=5,
                     help="bracket every N-th launch of each layer with HIP events inside the timed region (1: every launch, "
@@ -72,7 +81,7 @@ def parse_args(argv=None):
     ap.add_argument("--native-shard", action="store_true", help="(the only N>1 path; kept for old command lines)")
     ap.add_argument("--resident-only", action="store_true",
                     help="time only the HBM-resident slide (kernel-only; the line's value is then NOT the section-8(d) metric)")
-    ap.add_argument("--no-legs", action="store_true", help="skip the exact-fp32 and training legs of the default N = 1 line")
+    ap.add_argument("--no-legs", action="store_true", help="skip the exact-fp32, training and configs legs of the --full N = 1 line")
     ap.add_argument("--master-port", type=int, default=29577)
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32 / "
@@ -317,10 +326,13 @@ def main():
 
     if args.batch <= 0:
         args.batch = umx.auto_batch(hp)
-    # the training leg of the default N = 1 line (BASELINE configs[4]) runs FIRST, on an idle chip like `--workload train-synth256`
+    # the training leg of the --full N = 1 line (BASELINE configs[4]) runs FIRST, on an idle chip like `--workload train-synth256`
     # does: its step is a chain of short launches whose time follows the clock, and behind a minute of inference at the package
     # power cap the same leg measured 9 % lower (1 413 vs 1 578 - 1 599 images/s on one box)
-    legs = world == 1 and not sharded and args.workload == "wsi-synth256" and not args.no_legs and not args.resident_only
+    legs = (args.full and world == 1 and not sharded and args.workload == "wsi-synth256" and not args.no_legs
+            and not args.resident_only)
+    # the HBM-resident twin of the slide: the timed path of --resident-only, otherwise only --full's resident run and checks use it
+    resident = args.full or args.resident_only
     train = train_leg(torch, dev) if legs else None
     eng = umx.Engine(hp, blob, device=local_rank, max_batch=args.batch, precision=args.precision)
     # every engine launch, torch op and RCCL call of this process is ordered on ONE non-default stream
@@ -338,7 +350,7 @@ def main():
         band_i32 = synth_rows_u16(torch, C_img, r0, rows, W, dev)
         host_u16 = torch.empty((C_img, rows, W), dtype=torch.int16).pin_memory()
         host_u16.copy_(band_i32.to(torch.int16))                      # bit pattern of the uint16 values
-        band_f64 = im2double(torch, band_i32)                          # the HBM-resident twin (kernel-only timing)
+        band_f64 = im2double(torch, band_i32) if resident else None    # the HBM-resident twin (kernel-only timing)
         del band_i32
     work.synchronize()
     K = hp.nClasses
@@ -346,7 +358,7 @@ def main():
     if not sharded:
         host_outs = [torch.empty((K, H, W), dtype=torch.uint8).pin_memory() for _ in range(2)]
         host_out = host_outs[0]
-        dev_out = torch.empty((K, H, W), dtype=torch.float16, device=dev)
+        dev_out = torch.empty((K, H, W), dtype=torch.float16, device=dev) if resident else None
         inflight = []
 
         def step_host():
@@ -390,32 +402,33 @@ def main():
             eng.infer_image_sharded_dev(band.data_ptr(), C_img, H, W, r0, band.shape[1], mean, std, umx.MODE_ACCUMULATE,
                                         umx.STITCH_FP16_COMPAT, args.slabs, full_f16.data_ptr())
             return full_f16
-        # first slide, outside the timed region: (1) the in-library schedule on the float64 band == sharding.py's over torch.distributed;
-        # (2) the raw entry's gathered uint8 stack and own rows == the drivers' uint8 recipe applied to (1)
-        with torch.cuda.stream(work):
-            a = native_dev(band_f64).clone()
-            b = sharding.infer_image_sharded(eng, band_f64, r0, H, W, mean, std, umx.MODE_ACCUMULATE, umx.STITCH_FP16_COMPAT,
-                                             nslabs=args.slabs, sync=False)
-            same_sched = bool(torch.equal(a, b))
-            first = (a * 255.0).to(torch.uint8)
-            want_u8 = (255.0 * (first.to(torch.float64) * (1.0 / 255))).to(torch.uint8)
-            del a, b, first
-        work.synchronize()
-        eng.infer_image_sharded_raw_submit(0, host_u16.data_ptr(), 16, C_img, H, W, r0, rows if pb > pa else 0, None, mean, std,
-                                           umx.MODE_ACCUMULATE, args.slabs, host_owns[0].data_ptr() if y1 > y0 else 0,
-                                           fulls_u8[0].data_ptr())
-        eng.infer_image_wait(0)
-        same_raw = bool(torch.equal(fulls_u8[0], want_u8)) and bool(torch.equal(host_owns[0], want_u8[:, y0:y1].cpu()))
-        okv = torch.tensor([1 if (same_sched and same_raw) else 0], dtype=torch.int32, device=dev)
-        if world > 1:
-            dist.all_reduce(okv, op=dist.ReduceOp.MIN)
-        if int(okv.item()) != 1:
-            print("bench.py: rank %d: the native sharded path is not bit-equal to its checkers (schedule vs sharding.py: %s, raw entry vs "
-                  "the uint8 recipe: %s) on some rank -- refusing to time anything else" % (rank, same_sched, same_raw), file=sys.stderr)
-            sys.exit(4)
-        del want_u8
+        # --full: the first slide, outside the timed region: (1) the in-library schedule on the float64 band == sharding.py's over
+        # torch.distributed; (2) the raw entry's gathered uint8 stack and own rows == the drivers' uint8 recipe applied to (1)
+        if args.full:
+            with torch.cuda.stream(work):
+                a = native_dev(band_f64).clone()
+                b = sharding.infer_image_sharded(eng, band_f64, r0, H, W, mean, std, umx.MODE_ACCUMULATE, umx.STITCH_FP16_COMPAT,
+                                                 nslabs=args.slabs, sync=False)
+                same_sched = bool(torch.equal(a, b))
+                first = (a * 255.0).to(torch.uint8)
+                want_u8 = (255.0 * (first.to(torch.float64) * (1.0 / 255))).to(torch.uint8)
+                del a, b, first
+            work.synchronize()
+            eng.infer_image_sharded_raw_submit(0, host_u16.data_ptr(), 16, C_img, H, W, r0, rows if pb > pa else 0, None, mean, std,
+                                               umx.MODE_ACCUMULATE, args.slabs, host_owns[0].data_ptr() if y1 > y0 else 0,
+                                               fulls_u8[0].data_ptr())
+            eng.infer_image_wait(0)
+            same_raw = bool(torch.equal(fulls_u8[0], want_u8)) and bool(torch.equal(host_owns[0], want_u8[:, y0:y1].cpu()))
+            okv = torch.tensor([1 if (same_sched and same_raw) else 0], dtype=torch.int32, device=dev)
+            if world > 1:
+                dist.all_reduce(okv, op=dist.ReduceOp.MIN)
+            if int(okv.item()) != 1:
+                print("bench.py: rank %d: the native sharded path is not bit-equal to its checkers (schedule vs sharding.py: %s, raw entry vs "
+                      "the uint8 recipe: %s) on some rank -- refusing to time anything else" % (rank, same_sched, same_raw), file=sys.stderr)
+                sys.exit(4)
+            del want_u8
         shard_path = {"path": "umx_infer_image_sharded_raw_submit (RCCL inside libumx; uint16 band up, uint8 slabs gathered, own rows down)",
-                      "first_slide_equals_sharding_py_and_uint8_recipe_all_ranks": True, "note": None}
+                      "first_slide_equals_sharding_py_and_uint8_recipe_all_ranks": True if args.full else None, "note": None}
 
         def step_host():   # H2D of this rank's band + tiles + halo exchange + stitch + uint8 all-gather + D2H of its own rows
             slot = step_host.n & 1
@@ -464,7 +477,7 @@ def main():
     host_sync = None
     if not args.resident_only:
         host_elapsed, host_prof, res_h = timed(step_host)
-        if not sharded:
+        if not sharded and args.full:
             # what ONE per-file driver call achieves: a synchronous umx_infer_image_raw with the drivers' intensity rescale, one
             # slide at a time
             sync_out = torch.empty((K, H, W), dtype=torch.uint8).pin_memory()
@@ -501,10 +514,13 @@ def main():
                                  "planes' (min, max) by host threads while the rows cross the bus, tiles start on the first slab; "
                                  "device_range (UMX_HOST_RANGE=0): whole upload + device min/max first, as in round 3 "
                                  "(`value` above streams two slides through submit / wait)"}
-    res_elapsed, res_prof, res_r = timed(step_resident)
+    res_elapsed = res_prof = res_r = None
+    if resident:
+        res_elapsed, res_prof, res_r = timed(step_resident)
     # rounds 1-3 quoted the 2048-row band of the same slide (946 tiles: one rank's share at N = 8): kept beside the slide at N = 1
     weak_band = None
-    if not sharded and args.workload == "wsi-synth256" and args.scaling == "strong" and host_elapsed is not None and H > 2048:
+    if (args.full and not sharded and args.workload == "wsi-synth256" and args.scaling == "strong" and host_elapsed is not None
+            and H > 2048):
         Hb = 2048
         nb_r, nb_c, _, _ = eng.tile_grid(Hb, W)
         band_u16 = torch.empty((C_img, Hb, W), dtype=torch.int16).pin_memory()
@@ -532,13 +548,14 @@ def main():
                      "steps": nbs, "ms_per_step": round(1e3 * dtb / nbs, 3),
                      "note": "the first 2048 rows as a slide of their own, same host path (H2D + D2H inside): the workload of the "
                              "round-1..3 lines"}
-    # the two paths must agree: uint8 planes of the host path == np.uint8(255 * fp16 planes) of the resident path
+    # --full: the two paths must agree: uint8 planes of the host path == np.uint8(255 * fp16 planes) of the resident path
+    both = host_elapsed is not None and res_elapsed is not None
     with torch.cuda.stream(work):
         if not sharded:
             # the drivers' uint8 recipe (UnMicst1-5.py:848-854): np.uint8(255 * pm) with the product rounded to float16,
             # resize at the identity grid (u8 * (1/255) in float64), np.uint8(255 * .)
             want_u8 = None
-            if host_elapsed is not None:
+            if both:
                 first = (dev_out * 255.0).to(torch.uint8)
                 want_u8 = (255.0 * (first.to(torch.float64) * (1.0 / 255))).to(torch.uint8).cpu()
             agree = None if want_u8 is None else bool(torch.equal(want_u8, host_outs[0]) and torch.equal(want_u8, host_outs[1]))
@@ -548,14 +565,14 @@ def main():
                                                      "crc32_u8_planes_resident_path": crc32_of(want_u8)}
         else:
             agree = None
-            if host_elapsed is not None:   # (both gathered stacks of the host path against the uint8 recipe on the resident path's)
+            if both:   # (both gathered stacks of the host path against the uint8 recipe on the resident path's)
                 first = (res_r * 255.0).to(torch.uint8)
                 want = (255.0 * (first.to(torch.float64) * (1.0 / 255))).to(torch.uint8)
                 agree = bool(torch.equal(want, fulls_u8[0]) and torch.equal(want, fulls_u8[1])
                              and torch.equal(want[:, y0:y1].cpu(), host_owns[0]) and torch.equal(want[:, y0:y1].cpu(), host_owns[1]))
                 del first, want
-            checksum = None if host_elapsed is None else {"crc32_u8_own_rows_host_path": crc32_of(host_owns[0]),
-                                                          "crc32_u8_stack_gathered": crc32_of(fulls_u8[0].cpu())}
+            checksum = None if not both else {"crc32_u8_own_rows_host_path": crc32_of(host_owns[0]),
+                                              "crc32_u8_stack_gathered": crc32_of(fulls_u8[0].cpu())}
     elapsed, prof = (host_elapsed, host_prof) if host_elapsed is not None else (res_elapsed, res_prof)
     ranks = ranks_block(dist if sharded else None, torch, hp, H, W, rank, agree)
 
@@ -571,9 +588,9 @@ def main():
         if args.breakdown:
             print_breakdown(prof)
         cpu = None
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             cpu = cpu_baseline(hp, blob, band_f64, mean, std, args.cpu_seconds)
-        # two short legs the default line carries at N = 1: the exact-fp32 engine on the 2048-row band and the
+        # two short legs the --full line carries at N = 1: the exact-fp32 engine on the 2048-row band and the
         # training step of BASELINE configs[4]; `--no-legs` (or any non-default workload / N > 1) skips them
         f32 = None
         if legs and eng.precision != "f32":
@@ -617,9 +634,10 @@ def main():
                        "tiles_per_step": tiles_total, "slide": [H, W], "flop_per_tile_as_written": hp.flops_per_tile(),
                        "flop_per_tile_executed_unpadded": umx.describe(hp)["flops_per_tile"], "checksum": checksum,
                        "host_path_equals_resident_path": agree},
-            "resident": {"value": round(tiles_total * args.steps / res_elapsed, 2), "unit": "tiles/s",
-                         "ms_per_step": round(1e3 * res_elapsed / args.steps, 3),
-                         "note": "same slide already in HBM as float64, result left in HBM (no H2D / D2H): kernel-only"},
+            "resident": None if res_elapsed is None else {
+                "value": round(tiles_total * args.steps / res_elapsed, 2), "unit": "tiles/s",
+                "ms_per_step": round(1e3 * res_elapsed / args.steps, 3),
+                "note": "same slide already in HBM as float64, result left in HBM (no H2D / D2H): kernel-only"},
             "host_sync": host_sync, "weak_band": weak_band, "ranks": ranks, "shard_path": shard_path if sharded else None,
             "roofline": roofline, "cpu_baseline": cpu, "f32": f32, "train": train, "configs": configs,
             "workload_note": "the default workload is the full 16384 x 16384 slide at every N since round 4 (rounds 1-3 quoted its first "
@@ -683,7 +701,7 @@ def dump_outputs(path, arrays):
     print("bench.py: --dump-outputs %s: %s" % (path, "; ".join(written)), file=sys.stderr)
 
 
-CONFIG_LEGS = (   # (workload, rows, steps): the other BASELINE.json configs as short legs of the default N = 1 line
+CONFIG_LEGS = (   # (workload, rows, steps): the other BASELINE.json configs as short legs of the --full N = 1 line
     ("solo-1024", 1024, 20),       # configs[1]: the reference's default tool (unmicstWrapper.py:55-57) on a 1024 x 1024 image
     ("duo-4096", 4096, 10),        # configs[2]
     ("solo-16384", 16384, 3),      # configs[3] as worded: the whole 16384 x 16384 slide, here on one GPU
@@ -797,7 +815,7 @@ def f32_leg(torch, umx, hp, blob, local_rank, batch, host_u16, C_img, W, mean, s
 
 
 def train_leg(torch, dev, B=8, steps=100, warmup=10):
-    """BASELINE.json configs[4] inside the default line: forward + backward + Adam on random 256x256x2 batches resident in HBM
+    """BASELINE.json configs[4] inside the --full line: forward + backward + Adam on random 256x256x2 batches resident in HBM
     (the reference's sess.run([optOp ...]), UnMicst1-5.py:483-484), timed like `--workload train-synth256`."""
     from unmicst_amd import model, trainer
     hp = model.KNOWN_HP["synthetic-256"]
@@ -880,7 +898,7 @@ def bench_train(args, torch):
     flops_step = tr.flops_per_image * B
     tflops = flops_step * args.steps / elapsed / 1e12
     cpu = None
-    if args.cpu_seconds > 0:
+    if args.full and args.cpu_seconds > 0:
         cpu = cpu_baseline_train(hp, blob, data[0].cpu().numpy(), labels[0].cpu().numpy(), weights[0].cpu().numpy(),
                                  args.cpu_seconds)
     line = {

@@ -61,6 +61,15 @@ def test_bench_strong_and_weak_slide_sizes():
     assert bench.WORKLOADS["solo-16384"][0] == "nucleiDAPI1-5"
 
 
+def test_bench_extras_only_with_full():
+    """A plain run times the headline alone: the other measurements, the checks and the CPU baselines wait for --full."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse_args([]).full is False
+    a = bench.parse_args(["--full", "--no-legs", "--cpu-seconds", "0"])
+    assert a.full and a.no_legs and a.cpu_seconds == 0
+
+
 def test_dump_outputs_is_bounded_and_reproducible(tmp_path):
     """--dump-outputs: a small array whole (float32 / float64), a large one as a seeded sample with its positions, < 64 MB in all,
     the same files for the same arrays."""

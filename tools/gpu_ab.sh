@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 O=gpurun_out/$1; mkdir -p $O
 while IFS='|' read -r label envs bargs; do
   label=$(echo $label); [ -z "$label" ] && continue
-  env $envs timeout 600 python bench.py --cpu-seconds 0 $bargs > $O/$label.log 2>&1
+  env $envs timeout 600 python bench.py --full --cpu-seconds 0 $bargs > $O/$label.log 2>&1
   python3 - "$O/$label.log" "$label" <<'PY'
 import json, sys
 line = None

@@ -1,12 +1,12 @@
 # usage: bash tools/gpu_pmc.sh <outdir-name> [bench args]: rocprofv3 kernel stats + PMC passes of one bench step.
 # The rocpd databases stay in /tmp on the box; only the per-layer CSV summaries land in gpurun_out/<name>/.
-# The --stats pass profiles the DEFAULT command (host path + synchronous call + resident slide); the counter passes run the resident
+# The --stats pass profiles the --full command without its legs (host path + synchronous call + resident slide); the counter passes run the resident
 # slide only, so that every UNet pass has the same launch sequence and the per-layer table lines up (same kernels, same shapes).
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 O=gpurun_out/$1; shift; mkdir -p $O
 D=/tmp/umx_prof; rm -rf $D; mkdir -p $D
-rocprofv3 --kernel-trace --stats -d $D/stats -o run -- python3 bench.py --steps 2 --warmup 1 --cpu-seconds 0 --no-legs "$@" > $O/stats.log 2>&1
+rocprofv3 --kernel-trace --stats -d $D/stats -o run -- python3 bench.py --steps 2 --warmup 1 --full --cpu-seconds 0 --no-legs "$@" > $O/stats.log 2>&1
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -d $D/pmc_sq -o run -- python3 bench.py --steps 1 --warmup 0 --cpu-seconds 0 --resident-only "$@" > $O/pmc_sq.log 2>&1
 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum -d $D/pmc_tcc -o run -- python3 bench.py --steps 1 --warmup 0 --cpu-seconds 0 --resident-only "$@" > $O/pmc_tcc.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $D/pmc_fetch -o run -- python3 bench.py --steps 1 --warmup 0 --cpu-seconds 0 --resident-only "$@" > $O/pmc_fetch.log 2>&1

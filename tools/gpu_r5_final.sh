@@ -7,13 +7,13 @@ export TMPDIR=/tmp
 O=gpurun_out/final; mkdir -p $O
 (time timeout 1500 python -m pytest tests -m gpu -q) > $O/pytest_gpu.log 2>&1
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
-timeout 900 python bench.py > $O/bench_default.log 2>&1
-timeout 600 python bench.py --force-sharded --cpu-seconds 0 > $O/bench_force_sharded.log 2>&1
+timeout 900 python bench.py --full > $O/bench_default.log 2>&1
+timeout 600 python bench.py --force-sharded --full --cpu-seconds 0 > $O/bench_force_sharded.log 2>&1
 timeout 600 python bench.py --steps 5 --warmup 2 --cpu-seconds 0 --resident-only --scaling weak --breakdown > $O/bench_f16x3_breakdown.log 2>&1
 for w in solo-16384 duo-4096 solo-1024 legacy-1024; do
-  timeout 900 python bench.py --workload $w --steps 10 --warmup 3 --cpu-seconds 20 --breakdown > $O/bench_$w.log 2>&1
+  timeout 900 python bench.py --workload $w --steps 10 --warmup 3 --full --cpu-seconds 20 --breakdown > $O/bench_$w.log 2>&1
 done
-timeout 900 python bench.py --workload train-synth256 --steps 50 --warmup 5 --cpu-seconds 30 > $O/bench_train.log 2>&1
+timeout 900 python bench.py --workload train-synth256 --steps 50 --warmup 5 --full --cpu-seconds 30 > $O/bench_train.log 2>&1
 for b in 16 32; do timeout 600 python bench.py --workload train-synth256 --train-batch $b --steps 20 --warmup 3 --cpu-seconds 0 > $O/bench_train_b$b.log 2>&1; done
 bash tools/gpu_pmc.sh final/pmc_synth256 --scaling weak > $O/pmc_synth256.log 2>&1
 grep -E "passed|failed" $O/pytest_gpu.log | tail -2; tail -1 $O/smoke.log
