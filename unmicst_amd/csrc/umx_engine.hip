@@ -27,17 +27,6 @@ int dev_alloc(umx_ctx* ctx, void** out, size_t bytes) {
     return UMX_OK;
 }
 
-int upload(umx_ctx* ctx, const std::vector<float>& h, float** out) {
-    *out = nullptr;
-    if (h.empty()) return UMX_OK;
-    void* d = nullptr;
-    int rc = dev_alloc(ctx, &d, h.size() * sizeof(float));
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    *out = (float*)d;
-    return UMX_OK;
-}
-
 
 int grow(umx_ctx* ctx, void** buf, size_t* cap, size_t bytes) {
     if (*cap >= bytes) return UMX_OK;
@@ -340,6 +329,98 @@ int tiles_range(umx_ctx* ctx, const double* image_dev, int C_img, const TileGeom
     return ll.join();
 }
 
+// A model planned on the host: the graph, the layout of each activation buffer (which depends on the graph alone) and, for the
+// split-precision engine (f16), the host plan of every launch.  UMX_ERR_INVALID with "<layer>: <reason>" in *why for a refused layer.
+struct ModelPlan {
+    std::vector<Launch> plan;
+    std::vector<Buffer> bufs;           // no device memory yet
+    std::vector<HostPlan> hplans;       // per launch (f16; nothing for the head)
+    size_t pos = 0;                     // blob floats the graph consumed
+};
+int plan_model(const umx_hparams& hp, const float* blob, bool f16, bool f6, int act_shift, ModelPlan* m, std::string* why) {
+    // (the raw-skip fold of the split-precision plan:
+    // only where the first layer takes the dense-K kernel: the input tiles are then stored once, in the compact form both read)
+    bool fold = f16 && conv_first_eligible(hp);
+    for (;;) {
+        std::vector<size_t> buf_floats;
+        std::vector<std::pair<int, int>> buf_geom;
+        m->plan.clear();
+        m->pos = 0;
+        build_graph(hp, blob, &m->plan, &buf_floats, &buf_geom, &m->pos, fold);
+        const int head_src = m->plan.back().g[0].src;   // the tensor the softmax head reads stays fp32
+        m->bufs.assign(buf_floats.size(), Buffer());
+        for (size_t i = 0; i < m->bufs.size(); ++i) {
+            Buffer& B = m->bufs[i];
+            B.floats_per_tile = buf_floats[i];
+            B.S = buf_geom[i].first;
+            B.C = buf_geom[i].second;
+            B.Cs = round_up(B.C, 8);
+            B.as_f32 = !f16 || (int)i == head_src;
+            // Octet-planar storage for the tensors whose consumers work on whole 16 x 16 (or 8 x 16) tiles of ONE image: a
+            // workgroup reads its halo once per octet chunk, and in NHWC every chunk touches every 128-byte line of the
+            // footprint (lu0.conv fetched 8.9 GB per launch through L2 for a 3 GB tensor); planar, a line belongs to one chunk.
+            // Same bytes per image either way, so batches slice identically.  With 8 stored channels the two forms coincide.
+            // Not for the output of a transposed convolution that runs one sub-pixel phase per workgroup (> 5 N-tiles): its
+            // stores are every second pixel of a row, 16 bytes at a 32-byte stride in the planar form (lu2.convT +19 %).
+            bool phase_written = false;
+            for (const Launch& Lp : m->plan)
+                if (Lp.dst == (int)i && Lp.nphase == 4 && !(Lp.o_mul == 2 && Lp.ngroups == 1 && (Lp.Cout + 15) / 16 <= 5 && Lp.H >= 8 && Lp.W >= 16))
+                    phase_written = true;
+            B.planar = !phase_written && !B.as_f32 && i != 0 && B.S >= 16 && B.Cs > 8 &&
+                       (size_t)B.S * B.S * 16 < (1u << 24);   // (the kernels form octet offsets with 24-bit multiplies)
+        }
+        m->hplans.assign(m->plan.size(), HostPlan());
+        bool folded = false, first = false;
+        for (size_t li = 0; li < m->plan.size(); ++li) {
+            Launch& L = m->plan[li];
+            if (L.head) continue;
+            if (f16) make_d2s(L);   // (narrow stride-2 transposed convolutions: depth-to-space form, before the geometry is laid out)
+            std::string w;
+            if (!conv_geometry(L, &w)) { *why = L.name + ": " + w; return UMX_ERR_INVALID; }
+            if (!f16) continue;
+            PlanInputs in;
+            in.f6 = f6; in.imSize = hp.imSize; in.act_shift = act_shift;
+            in.out_f32 = L.dst == head_src; in.head = &m->plan.back(); in.dst_planar = m->bufs[L.dst].planar;
+            if (int rc = plan_f16(L, in, &m->hplans[li], &w)) { *why = L.name + ": " + w; return rc; }
+            plan_first(L, &m->hplans[li]);
+            folded = folded || L.app_src == 0;
+            first = first || m->hplans[li].use_first;
+        }
+        // The fold was decided from the hyper-parameters (conv_first_eligible), the dense-K first layer from the plan: where the
+        // two disagree (a forced N-tile count, a first layer the planner split into N-blocks) the graph is planned again with the
+        // two-group top convolution -- not failed into the 4 x slower exact-fp32 kernels
+        if (!folded || first) return UMX_OK;
+        fold = false;
+    }
+}
+
+// a host plan on the device: its arrays in the context's allocations, the launch's parameters with their pointers set
+int upload_plan(umx_ctx* ctx, Launch& L, const HostPlan& P) {
+    int rc = UMX_OK;
+    auto up = [&](const auto& v) {   // (an empty array: null)
+        typename std::decay_t<decltype(v)>::value_type* d = nullptr;
+        if (!rc) rc = upload_raw(ctx, v, &d);
+        return d;
+    };
+    HConvParams& h = L.hcp;
+    h = P.h;
+    h.stages = up(P.stages);
+    h.econst = reinterpret_cast<const uint4*>(up(P.econst));
+    for (int list = 0; list < 4; ++list) h.ph[list].w = reinterpret_cast<const uint4*>(up(P.wimg[list]));
+    h.head_frag = reinterpret_cast<const uint4*>(up(P.head_frag));
+    h.zeros = ctx->d_zeros;
+    h.overflow_flag = ctx->d_flag;
+    L.nt16 = P.nt16;
+    L.exec_flops = P.exec_flops;
+    L.use_first = P.use_first;
+    if (P.use_first) {
+        L.first = P.first;
+        L.first.w = reinterpret_cast<const uint4*>(up(P.first_w));
+        L.first.econst = reinterpret_cast<const float*>(h.econst);
+    }
+    return rc;
+}
+
 }  // namespace umx
 
 // ---- accessors for umx_shard.hip (same shared object; hidden visibility)
@@ -437,27 +518,16 @@ int umx_describe(const umx_hparams* hp, int* n_launches, double* flops_per_tile,
     return UMX_OK;
 }
 
-// Would umx_create(UMX_PREC_F16X3) take this model?  Host only (no device): the graph is built with zero weights and every launch goes
-// through the split-precision planner's search (plan_f16 in its dry form: geometry, N-tile choice, (chunk, stage) search against the LDS
-// budget).  UMX_OK, or UMX_ERR_INVALID with the first refused layer and the planner's reason in umx_last_error(NULL).
+// Would umx_create(UMX_PREC_F16X3) take this model?  Host only (no device): the graph is built with zero weights and planned as
+// umx_create plans it, without the upload.  UMX_OK, or UMX_ERR_INVALID with the first refused layer and the planner's reason in
+// umx_last_error(NULL).
 int umx_plan_check(const umx_hparams* hp) {
     std::string why;
     int rc = check_hp(hp, &why);
     if (rc) return fail(nullptr, rc, "%s", why.c_str());
-    std::unique_ptr<umx_ctx> ctx(new umx_ctx());
-    ctx->hp = *hp;
-    ctx->precision = UMX_PREC_F16X3;
     std::vector<float> blob(blob_floats_needed(*hp), 0.f);
-    struct { std::vector<size_t> buf_floats; std::vector<std::pair<int, int>> buf_geom; size_t pos = 0; } b;
-    build_graph(*hp, blob.data(), &ctx->plan, &b.buf_floats, &b.buf_geom, &b.pos, conv_first_eligible(*hp));
-    const int head_src = ctx->plan.back().g[0].src;
-    for (auto& L : ctx->plan) {
-        if (L.head) continue;
-        make_d2s(L);
-        if (!conv_geometry(L, &why)) return fail(nullptr, UMX_ERR_INVALID, "%s: %s", L.name.c_str(), why.c_str());
-        if ((rc = plan_f16(ctx.get(), L, 0, L.dst == head_src, &ctx->plan.back(), &why, true)))
-            return fail(nullptr, rc, "%s: %s", L.name.c_str(), why.c_str());
-    }
+    ModelPlan m;
+    if ((rc = plan_model(*hp, blob.data(), true, false, 0, &m, &why))) return fail(nullptr, rc, "%s", why.c_str());
     return UMX_OK;
 }
 
@@ -575,6 +645,11 @@ int umx_create_opts(const umx_hparams* hp, const float* weight_blob, size_t blob
         return fail(nullptr, UMX_ERR_NO_DEVICE, "device %d is %s; libumx is built for gfx950 only", device_ordinal,
                     prop.gcnArchName);
 
+    const bool f16 = precision == UMX_PREC_F16X3;
+    ModelPlan mp;
+    if ((rc = plan_model(*hp, weight_blob, f16, f6, act_shift, &mp, &why))) return fail(nullptr, rc, "%s", why.c_str());
+    if (mp.pos != blob_floats) return fail(nullptr, UMX_ERR_BLOB, "internal blob walk mismatch");
+
     std::unique_ptr<umx_ctx> ctx(new umx_ctx());
     ctx->ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     ctx->hp = *hp;
@@ -583,47 +658,13 @@ int umx_create_opts(const umx_hparams* hp, const float* weight_blob, size_t blob
     ctx->precision = precision;
     ctx->f6 = f6;
     ctx->act_shift = act_shift;
+    ctx->plan = std::move(mp.plan);
+    ctx->bufs = std::move(mp.bufs);
     umx_ctx* c = ctx.get();
     HIP_TRY(nullptr, hipSetDevice(device_ordinal));
     HIP_TRY(nullptr, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
     c->stream = c->own_stream;
-
-    struct { std::vector<size_t> buf_floats; std::vector<std::pair<int, int>> buf_geom; size_t pos = 0; } b;
-    // (the raw-skip fold of the split-precision plan:
-    // only where the first layer takes the dense-K kernel: the input tiles are then stored once, in the compact form both read)
-    static thread_local bool t_no_fold = false;   // (set for the one retry below)
-    const bool fold = precision == UMX_PREC_F16X3 && conv_first_eligible(*hp) && !t_no_fold;
-    build_graph(*hp, weight_blob, &c->plan, &b.buf_floats, &b.buf_geom, &b.pos, fold);
-    if (b.pos != blob_floats) { umx_destroy(ctx.release()); return fail(nullptr, UMX_ERR_BLOB, "internal blob walk mismatch"); }
-    c->bufs.resize(b.buf_floats.size());
     auto bail = [&](int code) { std::string m = c->err; umx_destroy(ctx.release()); g_err = m; return code; };
-    const bool f16 = precision == UMX_PREC_F16X3;
-    const int head_src = c->plan.back().g[0].src;   // the tensor the softmax head reads stays fp32
-    for (size_t i = 0; i < c->bufs.size(); ++i) {
-        Buffer& B = c->bufs[i];
-        B.floats_per_tile = b.buf_floats[i];
-        B.S = b.buf_geom[i].first;
-        B.C = b.buf_geom[i].second;
-        B.Cs = round_up(B.C, 8);
-        B.as_f32 = !f16 || (int)i == head_src;
-        // Octet-planar storage for the tensors whose consumers work on whole 16 x 16 (or 8 x 16) tiles of ONE image: a
-        // workgroup reads its halo once per octet chunk, and in NHWC every chunk touches every 128-byte line of the
-        // footprint (lu0.conv fetched 8.9 GB per launch through L2 for a 3 GB tensor); planar, a line belongs to one chunk.
-        // Same bytes per image either way, so batches slice identically.  With 8 stored channels the two forms coincide.
-        // Not for the output of a transposed convolution that runs one sub-pixel phase per workgroup (> 5 N-tiles): its
-        // stores are every second pixel of a row, 16 bytes at a 32-byte stride in the planar form (lu2.convT +19 %).
-        bool phase_written = false;
-        for (const Launch& Lp : c->plan)
-            if (Lp.dst == (int)i && Lp.nphase == 4 && !(Lp.o_mul == 2 && Lp.ngroups == 1 && (Lp.Cout + 15) / 16 <= 5 && Lp.H >= 8 && Lp.W >= 16))
-                phase_written = true;
-        B.planar = !phase_written && !B.as_f32 && i != 0 && B.S >= 16 && B.Cs > 8 &&
-                   (size_t)B.S * B.S * 16 < (1u << 24);   // (the kernels form octet offsets with 24-bit multiplies)
-        // (hi, lo) binary16 planes with Cs channels take 4*Cs bytes per pixel
-        const size_t bytes_per_tile = B.as_f32 ? B.floats_per_tile * sizeof(float) : (size_t)B.S * B.S * B.Cs * 4;
-        void* d = nullptr;
-        if ((rc = dev_alloc(c, &d, bytes_per_tile * (size_t)max_batch))) return bail(rc);
-        B.d = (float*)d;
-    }
     {
         int lanes = opts->lanes;
         if (lanes == 0) lanes = 1;   // two lanes measured neutral on MI355X: off by default
@@ -638,14 +679,15 @@ int umx_create_opts(const umx_hparams* hp, const float* weight_blob, size_t blob
             return bail(UMX_ERR_HIP);
         }
         c->bufs2 = c->bufs;
-        for (size_t i = 0; i < c->bufs2.size(); ++i) {
-            Buffer& B = c->bufs2[i];
+    }
+    for (std::vector<Buffer>* set : {&c->bufs, &c->bufs2})
+        for (Buffer& B : *set) {
+            // (hi, lo) binary16 planes with Cs channels take 4*Cs bytes per pixel
             const size_t bytes_per_tile = B.as_f32 ? B.floats_per_tile * sizeof(float) : (size_t)B.S * B.S * B.Cs * 4;
             void* d = nullptr;
             if ((rc = dev_alloc(c, &d, bytes_per_tile * (size_t)max_batch))) return bail(rc);
             B.d = (float*)d;
         }
-    }
     if (f16) {
         void* d = nullptr;
         if ((rc = dev_alloc(c, &d, c->bufs[0].floats_per_tile * sizeof(float) * (size_t)max_batch))) return bail(rc);
@@ -663,24 +705,11 @@ int umx_create_opts(const umx_hparams* hp, const float* weight_blob, size_t blob
             return bail(UMX_ERR_HIP);
         }
     }
-    for (auto& L : c->plan) {
-        if ((rc = upload(c, L.pre_s, &L.d_pre_s)) || (rc = upload(c, L.pre_b, &L.d_pre_b)) ||
-            (rc = upload(c, L.post_s, &L.d_post_s)) || (rc = upload(c, L.post_b, &L.d_post_b)))
-            return bail(rc);
-        if (L.head) {
-            if ((rc = upload(c, L.head_w, &L.d_head_w))) return bail(rc);
-            continue;
-        }
-        if (f16) make_d2s(L);   // (narrow stride-2 transposed convolutions: depth-to-space form, before the geometry is laid out)
-        if (!conv_geometry(L, &why)) { c->err = L.name + ": " + why; return bail(UMX_ERR_INVALID); }
-        if (f16) {
-            if ((rc = plan_f16(c, L, act_shift, L.dst == head_src, &c->plan.back(), &why))) {
-                if (c->err.empty() || !why.empty()) c->err = L.name + ": " + why;
-                return bail(rc);
-            }
-            if ((rc = plan_first(c, L, act_shift, &why))) { c->err = L.name + ": " + why; return bail(rc); }
-            L.hcp.zeros = c->d_zeros;
-            L.hcp.overflow_flag = c->d_flag;
+    for (size_t li = 0; li < c->plan.size(); ++li) {
+        Launch& L = c->plan[li];
+        if (f16 && !L.head) {
+            if ((rc = upload_plan(c, L, mp.hplans[li]))) return bail(rc);
+            mp.hplans[li] = HostPlan();
             if (L.hcp.f6) c->f6_used = true;
             if (L.hcp.head_K > 0) {
                 c->head_fused = true;
@@ -692,31 +721,25 @@ int umx_create_opts(const umx_hparams* hp, const float* weight_blob, size_t blob
                 for (int gi = 0; gi < L.ngroups; ++gi) std::vector<float>().swap(L.g[gi].packed[ph]);
             continue;
         }
+        if ((rc = upload_raw(c, L.pre_s, &L.d_pre_s)) || (rc = upload_raw(c, L.pre_b, &L.d_pre_b)) ||
+            (rc = upload_raw(c, L.post_s, &L.d_post_s)) || (rc = upload_raw(c, L.post_b, &L.d_post_b)))
+            return bail(rc);
+        if (L.head) {
+            if ((rc = upload_raw(c, L.head_w, &L.d_head_w))) return bail(rc);
+            continue;
+        }
         for (int ph = 0; ph < L.nphase; ++ph)
             for (int gi = 0; gi < L.ngroups; ++gi) {
                 float* d = nullptr;
-                if ((rc = upload(c, L.g[gi].packed[ph], &d))) return bail(rc);
+                if ((rc = upload_raw(c, L.g[gi].packed[ph], &d))) return bail(rc);
                 L.cp.ph[ph].w[gi] = d;
                 std::vector<float>().swap(L.g[gi].packed[ph]);
             }
         L.cp.pre_s = L.d_pre_s; L.cp.pre_b = L.d_pre_b; L.cp.post_s = L.d_post_s; L.cp.post_b = L.d_post_b;
     }
     if (f16) c->split_launch.name = "input.split";
-    {   // compact input tiles: the graph folded the raw skip AND the first layer runs on the dense-K kernel
-        bool folded = false, first = false;
-        for (const Launch& L : c->plan) { folded = folded || L.app_src == 0; first = first || L.use_first; }
-        if (folded && !first) {
-            // The fold was decided from the hyper-parameters (conv_first_eligible), the dense-K first layer from the plan: where the
-            // two disagree (a forced N-tile count, a first layer the planner split into N-blocks) the graph is rebuilt ONCE with the
-            // two-group top convolution -- not failed into the 4 x slower exact-fp32 kernels
-            umx_destroy(ctx.release());
-            t_no_fold = true;
-            const int rc2 = umx_create_opts(hp, weight_blob, blob_floats, opts, out);
-            t_no_fold = false;
-            return rc2;
-        }
-        if (folded) c->in_cw = c->hp.nChannels == 1 ? 1 : c->hp.nChannels == 2 ? 2 : 4;
-    }
+    for (const Launch& L : c->plan)   // compact input tiles: the graph folded the raw skip (and so the first layer runs on the dense-K kernel)
+        if (L.app_src == 0) c->in_cw = c->hp.nChannels == 1 ? 1 : c->hp.nChannels == 2 ? 2 : 4;
     *out = ctx.release();
     return UMX_OK;
 }

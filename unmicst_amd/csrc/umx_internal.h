@@ -56,9 +56,6 @@ struct HWRef {
 struct Launch {
     std::string name;
     bool train = false;        // split-precision plan for the trainer: plain / per-phase kernels only, fp32 output, weights by reference
-    std::vector<HWRef> wrefs[4];   // (train) per stage list
-    size_t slab_units[4] = {0, 0, 0, 0};   // (train) uint4 units of each list's weight slab (all N-blocks)
-    std::vector<HStage> stages_host;       // (train) the stage table as uploaded: the trainer cuts it between halo chunks (K split)
     bool head = false;
     int ngroups = 0;
     Group g[2];
@@ -96,9 +93,6 @@ struct Launch {
     int d2s_oy[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, d2s_ox[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};   // sub-pixel offset of (block, phase slot)
     unsigned char d2s_tapmask[2][16] = {{0}, {0}};   // per block and tap of its window: bit j set = phase slot j has that tap
     int nt16 = 1;             // N-tiles per workgroup of the split-precision kernel
-    int force_nt16 = 0;       // > 0: the planner's N-tile choice is overridden (its own trial of narrower N-blocks)
-    int wshift = 0;           // weights are stored times 2^wshift
-    int n_ksteps = 0;         // K-slots of 32 executed per output tile, all phases (for the executed-FLOP figure)
     float* d_head_w = nullptr;
     float *d_pre_s = nullptr, *d_pre_b = nullptr, *d_post_s = nullptr, *d_post_b = nullptr;
 };
@@ -219,11 +213,33 @@ int build_graph(const umx_hparams& hp, const float* blob, std::vector<Launch>* p
                 std::vector<std::pair<int, int>>* buf_geom, size_t* pos, bool fold_top_skip = false);
 bool conv_geometry(Launch& L, std::string* why);
 
-// ---- umx_plan.hip: split-precision plan of one launch
+// ---- umx_plan.hip: split-precision plan of one launch, on the host (no context, no HIP call)
 int mx_pack_e2m3(const double (&v)[32], double amax, unsigned char (&out)[24]);   // umx_plan.hip: one OCP MX fp6 (e2m3) block of 32
-int plan_f16(umx_ctx* ctx, Launch& L, int act_shift, bool out_f32, const Launch* head, std::string* why, bool dry = false);
-// dense-K plan of the first down-sampling layer, for a launch plan_f16 has just planned (sets L.use_first when it applies)
-int plan_first(umx_ctx* ctx, Launch& L, int act_shift, std::string* why);
+struct PlanInputs {                // what the plan of a launch depends on besides the launch
+    bool f6 = false;               // the model may take the F6 form (UMX_PREC_F16X3_F6)
+    int imSize = 0, act_shift = 0; // the model's tile size; activations are stored times 2^act_shift
+    bool out_f32 = false;          // the launch writes fp32 (the head's input; every trainer launch)
+    bool dst_planar = false;       // the destination buffer is octet-planar (the depth-to-space table)
+    const Launch* head = nullptr;  // the softmax head its epilogue may fuse
+};
+struct HostPlan {
+    HConvParams h;                      // device pointers null: the engine's upload_plan / the trainer's setup_hconv set them
+    std::vector<HStage> stages;         // the stage table, every list's stages and a dummy behind them
+    std::vector<_Float16> wimg[4];      // per stage list: weight slab [N-block][stage blocks] (training plans: k-maps only)
+    std::vector<float> econst;          // epilogue constants per N-block (+ depth-to-space table, fused-head constants)
+    std::vector<_Float16> head_frag;    // the fused head's MFMA A-fragments, or empty
+    std::vector<HWRef> wrefs[4];        // (train) per stage list
+    int nt16 = 1, wshift = 0;           // N-tiles per workgroup; weights are stored times 2^wshift
+    int n_ksteps = 0;                   // K-slots of 32 executed per output tile, all phases ...
+    double exec_flops = 0.0;            // ... and the executed-FLOP figure
+    bool use_first = false;             // plan_first: the dense-K kernel takes the layer, with these parameters (pointers null) ...
+    FirstParams first;
+    std::vector<_Float16> first_w;      // ... and weight image
+};
+// UMX_ERR_INVALID with the reason in *why where the split-precision kernel cannot take the launch
+int plan_f16(const Launch& L, const PlanInputs& in, HostPlan* P, std::string* why);
+// dense-K plan of the first down-sampling layer, for a launch plan_f16 has just planned (sets P->use_first when it applies)
+void plan_first(const Launch& L, HostPlan* P);
 // depth-to-space rewrite of a narrow stride-2 transposed convolution (before conv_geometry / plan_f16); true if L was rewritten
 bool make_d2s(Launch& L);
 // the same decision from the hyper-parameters alone (the graph builder folds the raw skip only when the first layer takes this kernel)
@@ -231,7 +247,6 @@ bool conv_first_eligible(const umx_hparams& hp);
 
 // ---- umx_engine.hip
 int dev_alloc(umx_ctx* ctx, void** out, size_t bytes);
-int upload(umx_ctx* ctx, const std::vector<float>& h, float** out);
 template <typename T>
 int upload_raw(umx_ctx* ctx, const std::vector<T>& h, T** out) {
     *out = nullptr;

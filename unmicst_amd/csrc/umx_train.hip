@@ -139,9 +139,8 @@ struct umx_trainer {
     bool range_pending = false;         // a training step raised the range flag and an eval pass cleared it before umx_trainer_loss saw it
     bool hconv = true;
     bool wg_planes = true;              // the split-precision weight gradient stages from the planes
-    umx_ctx* pctx = nullptr;            // owner of the planner's device allocations (stage tables, weight slabs, constants)
     const float* h_blob = nullptr;      // (during build) the initial parameters on the host: weight scales
-    std::vector<umx::Launch> hls;
+    std::vector<HConvParams> hls;       // the split-precision plans' launch parameters
     std::vector<TConv*> hconvs;         // the convolutions that took the split-precision route, index = RepackDesc::owner
     int wscale_every = 256;             // steps between two refreshes of the weight scales (UMX_TRAIN_WSCALE_EVERY)
     std::vector<float> h_params;        // (refresh) host copy of the parameters
@@ -277,7 +276,7 @@ int wscale_shift(double wmax) {
 }
 
 // The same convolution as a split-precision plan (conv_f16x3, fp32 output): stage tables and the LDS-image layout of the weights
-// come from plan_f16 once; the values are filled every step by repack_f16x3_kernel from the fp32 operands this TConv already
+// come from the host plan (plan_f16) once; the values are filled every step by repack_f16x3_kernel from the fp32 operands this TConv already
 // rebuilds on the device.  A shape the planner refuses stays on the fp32 kernel.  bwd: see setup_conv.
 int setup_hconv(umx_trainer* tr, TConv& tc, const char* what, int H, int W, int Cout, int act, int nphase, int o_mul, const int* oy,
                 const int* ox, int ngroups, GroupSpec* gs, bool bwd) {
@@ -313,9 +312,25 @@ int setup_hconv(umx_trainer* tr, TConv& tc, const char* what, int H, int W, int 
     }
     wmax = operand_wmax(tc, tr->h_blob);
     std::string why;
-    if (!umx::conv_geometry(L, &why) || umx::plan_f16(tr->pctx, L, 0, true, nullptr, &why) != UMX_OK) {
+    umx::PlanInputs in;
+    in.imSize = tr->hp.imSize;
+    in.out_f32 = true;
+    umx::HostPlan P;
+    if (!umx::conv_geometry(L, &why) || umx::plan_f16(L, in, &P, &why) != UMX_OK) {
         if (getenv("UMX_DEBUG_PLAN")) fprintf(stderr, "[umx train] %s stays on the fp32 kernel: %s\n", what, why.c_str());
         return UMX_OK;
+    }
+    HConvParams& h = P.h;   // (the weight slabs hold the k-maps; repack_f16x3_kernel writes their values every step)
+    HStage* stages = nullptr;
+    float* econst = nullptr;
+    T_TRY(tupload(tr, &stages, P.stages.data(), P.stages.size()));
+    T_TRY(tupload(tr, &econst, P.econst.data(), P.econst.size()));
+    h.stages = stages;
+    h.econst = reinterpret_cast<const uint4*>(econst);
+    for (int ph = 0; ph < nphase; ++ph) {
+        _Float16* slab = nullptr;
+        if (!P.wimg[ph].empty()) T_TRY(tupload(tr, &slab, P.wimg[ph].data(), P.wimg[ph].size()));
+        h.ph[ph].w = reinterpret_cast<const uint4*>(slab);
     }
     const int sh = wscale_shift(wmax);
     tc.wsh = sh;
@@ -327,7 +342,7 @@ int setup_hconv(umx_trainer* tr, TConv& tc, const char* what, int H, int W, int 
     // directly and this convolution needs no fp32 operand at all.  An octet that straddles two parity blocks keeps the packed route.
     bool direct = true;
     for (int ph = 0; ph < nphase && direct; ++ph)
-        for (const umx::HWRef& r : L.wrefs[ph]) {
+        for (const umx::HWRef& r : P.wrefs[ph]) {
             const GroupSpec& G = gs[r.arr];
             const int c0 = (int)(((size_t)r.base / L.Np) % round_up(G.C, 4));
             if (c0 / G.Cblk != (c0 + r.nvalid - 1) / G.Cblk) { direct = false; break; }
@@ -335,8 +350,8 @@ int setup_hconv(umx_trainer* tr, TConv& tc, const char* what, int H, int W, int 
     if (direct)
         for (int ph = 0; ph < nphase; ++ph) {
             std::vector<umx::HWRef> out;
-            out.reserve(L.wrefs[ph].size());
-            for (const umx::HWRef& r : L.wrefs[ph]) {
+            out.reserve(P.wrefs[ph].size());
+            for (const umx::HWRef& r : P.wrefs[ph]) {
                 const GroupSpec& G = gs[r.arr];
                 const int Cp = round_up(G.C, 4);
                 const int co = (int)((size_t)r.base % L.Np);
@@ -349,11 +364,11 @@ int setup_hconv(umx_trainer* tr, TConv& tc, const char* what, int H, int W, int 
                 if (idx > (size_t)INT_MAX) return tfail(tr, UMX_ERR_INVALID, "%s: master tensor too large for a weight reference", what);
                 out.push_back(umx::HWRef{r.dst, (int)idx, r.nvalid, r.arr});
             }
-            L.wrefs[ph].swap(out);
+            P.wrefs[ph].swap(out);
         }
     tc.direct = direct;
     for (int ph = 0; ph < nphase; ++ph) {
-        const std::vector<umx::HWRef>& refs = L.wrefs[ph];
+        const std::vector<umx::HWRef>& refs = P.wrefs[ph];
         if (refs.empty()) continue;
         HWRefDev* d = nullptr;
         T_TRY(talloc(tr, &d, refs.size()));
@@ -369,15 +384,13 @@ int setup_hconv(umx_trainer* tr, TConv& tc, const char* what, int H, int W, int 
         }
         rd.stride = tc.cp.Np;
         rd.scale = std::ldexp(1.f, sh);
-        rd.slab = const_cast<uint4*>(L.hcp.ph[ph].w);
+        rd.slab = const_cast<uint4*>(h.ph[ph].w);
         rd.bwd = bwd ? 1 : 0;
         rd.owner = (int)tr->hconvs.size();
         tr->rdescs.push_back(rd);
         tr->max_refs = std::max(tr->max_refs, rd.n);
-        std::vector<umx::HWRef>().swap(L.wrefs[ph]);
     }
     {   // K split: enough workgroups to occupy the chip (two per CU) where a batch of 8 leaves a deep layer a few dozen
-        HConvParams& h = L.hcp;
         const long wgs = (long)((tr->B + h.imgs - 1) / h.imgs) * h.tiles_y * h.tiles_x * h.nblocks * nphase;
         // (one workgroup per CU: 512 / 768 / 1024 lose 3 / 7 / 10 % of the step to the ordered reduce over more partial sums, 128 / 192
         // lose 1 % to idle CUs -- profiles/r04/train_ksplit_sweep.txt)
@@ -387,7 +400,7 @@ int setup_hconv(umx_trainer* tr, TConv& tc, const char* what, int H, int W, int 
         std::vector<std::vector<int>> starts(nphase);   // per phase: stage indices (relative) where a halo chunk begins
         for (int ph = 0; ph < nphase && S > 1; ++ph) {
             for (int si = 0; si < h.ph[ph].nstages; ++si)
-                if (L.stages_host[h.ph[ph].stage0 + si].group >= 0) starts[ph].push_back(si);
+                if (P.stages[h.ph[ph].stage0 + si].group >= 0) starts[ph].push_back(si);
             S = std::min(S, (int)starts[ph].size());
         }
         if (S > 1) {
@@ -401,17 +414,12 @@ int setup_hconv(umx_trainer* tr, TConv& tc, const char* what, int H, int W, int 
             if (h.xcd_order == 2) h.xcd_order = 1;
             tr->split_floats = std::max(tr->split_floats, (size_t)S * h.split_stride);
         }
-        if (getenv("UMX_DEBUG_PLAN")) {
-            int nk = 0;
-            for (int ph = 0; ph < nphase; ++ph)
-                for (int si = 0; si < h.ph[ph].nstages; ++si) nk += L.stages_host[h.ph[ph].stage0 + si].nk;
+        if (getenv("UMX_DEBUG_PLAN"))
             fprintf(stderr, "[umx train] %s%s: %d x %d -> %d ch, %d phase(s), NT %d x %d blocks, %d k-steps, %ld workgroups, K split %d\n",
-                    what, bwd ? " (backward)" : "", H, W, Cout, nphase, h.NT, h.nblocks, nk, wgs, S);
-        }
+                    what, bwd ? " (backward)" : "", H, W, Cout, nphase, h.NT, h.nblocks, P.n_ksteps, wgs, S);
     }
-    std::vector<HStage>().swap(L.stages_host);
     tc.hidx = (int)tr->hls.size();
-    tr->hls.push_back(std::move(L));
+    tr->hls.push_back(h);
     tr->hconvs.push_back(&tc);
     return UMX_OK;
 }
@@ -543,7 +551,7 @@ int to_h16(umx_trainer* tr, const float* x, size_t npix, int C, const H16& h, co
 }
 
 int run_hconv(umx_trainer* tr, TConv& tc, const H16& s0, const H16* s1, float* dst, const float* xinv, hipStream_t st) {
-    HConvParams p = tr->hls[tc.hidx].hcp;
+    HConvParams p = tr->hls[tc.hidx];
     p.B = tr->B;
     p.overflow_flag = reinterpret_cast<int*>(tr->d_maxw + tr->n_maxw);
     const H16* src[2] = {&s0, s1 ? s1 : &s0};
@@ -1128,11 +1136,6 @@ int select_route(umx_trainer* tr, const float* blob) {
     tr->wg_planes = tr->hconv;
     tr->h_blob = blob;
     tr->h_ds.resize(tr->L + 1); tr->h_us.resize(tr->L);   // (no buffers on the exact-fp32 route)
-    if (tr->hconv) {
-        tr->pctx = new umx_ctx();
-        tr->pctx->device = tr->device;
-        tr->pctx->hp = tr->hp;
-    }
     return UMX_OK;
 }
 
@@ -1972,10 +1975,6 @@ void umx_trainer_destroy(umx_trainer* tr) {
     (void)hipSetDevice(tr->device);
     if (tr->stream) (void)hipStreamSynchronize(tr->stream);
     arena_free(&tr->mem);
-    if (tr->pctx) {
-        for (void* p : tr->pctx->allocs) (void)hipFree(p);
-        delete tr->pctx;
-    }
     for (int i = 0; i < 4; ++i)
         if (tr->ev[i]) (void)hipEventDestroy(tr->ev[i]);
     if (tr->side) { (void)hipStreamSynchronize(tr->side); (void)hipStreamDestroy(tr->side); }
