@@ -28,10 +28,11 @@ int dev_alloc(umx_ctx* ctx, void** out, size_t bytes) {
 }
 
 
-int grow(umx_ctx* ctx, void** buf, size_t* cap, size_t bytes) {
+int grow(umx_ctx* ctx, void** buf, size_t* cap, size_t bytes, bool device_wide) {
     if (*cap >= bytes) return UMX_OK;
     if (*buf) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (device_wide) HIP_TRY(ctx, hipDeviceSynchronize());
+        else HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         HIP_TRY(ctx, hipFree(*buf));
         *buf = nullptr;
         *cap = 0;
@@ -423,23 +424,6 @@ int upload_plan(umx_ctx* ctx, Launch& L, const HostPlan& P) {
 
 }  // namespace umx
 
-// ---- accessors for umx_shard.hip (same shared object; hidden visibility)
-static void (*g_destroy_hook)(umx_ctx*) = nullptr;
-hipStream_t umx_internal_stream(umx_ctx* ctx) { return ctx->stream; }
-int umx_internal_device(umx_ctx* ctx) { return ctx->device; }
-void umx_internal_hp(const umx_ctx* ctx, umx_hparams* out) { *out = ctx->hp; }
-int umx_internal_fail(umx_ctx* ctx, int code, const char* msg) { return fail(ctx, code, "%s", msg); }
-void umx_internal_set_destroy_hook(void (*hook)(umx_ctx*)) { g_destroy_hook = hook; }
-// (umx_shard.hip) how a submitted call's completion event is waited for on a context that holds a communicator: polling, so that a peer's
-// failure or a timeout ends the wait with a status instead of blocking for ever; NULL / no hook: hipEventSynchronize
-static int (*g_wait_hook)(umx_ctx*, hipEvent_t) = nullptr;
-void umx_internal_set_wait_hook(int (*hook)(umx_ctx*, hipEvent_t)) { g_wait_hook = hook; }
-int umx_internal_wait_event(umx_ctx* ctx, hipEvent_t ev) {
-    if (g_wait_hook) return g_wait_hook(ctx, ev);
-    const hipError_t e = hipEventSynchronize(ev);
-    return e == hipSuccess ? UMX_OK : fail(ctx, UMX_ERR_HIP, "hipEventSynchronize failed: %s", hipGetErrorString(e));
-}
-
 extern "C" {
 
 const char* umx_version(void) { return "umx 0.4 (gfx950)"; }
@@ -754,7 +738,7 @@ void umx_destroy(umx_ctx* ctx) {
     if (ctx->stream2) hipStreamSynchronize(ctx->stream2);
     if (ctx->up_stream) hipStreamSynchronize(ctx->up_stream);
     if (ctx->dn_stream) hipStreamSynchronize(ctx->dn_stream);
-    if (g_destroy_hook) g_destroy_hook(ctx);   // a communicator / buffers umx_shard_init attached to this context
+    shard_release(ctx);   // a communicator / buffers umx_shard_init attached to this context
     for (auto& pe : ctx->pending) { hipEventDestroy(pe.a); hipEventDestroy(pe.b); }
     for (auto e : ctx->free_events) hipEventDestroy(e);
     for (void* d : ctx->allocs) hipFree(d);

@@ -43,8 +43,80 @@ void range_threads(const T* x, size_t n, uint32_t* out) {
 }
 }  // namespace
 
+namespace umx {
 
-int umx_internal_wait_event(umx_ctx* ctx, hipEvent_t ev);   // umx_engine.hip
+int check_image(umx_ctx* ctx, bool ptrs, int C_img, int H, int W, bool raw, int bits, double stdv, int mode, int stitch,
+                const uint32_t* range) {
+    if (!ctx) return fail(nullptr, UMX_ERR_INVALID, "ctx is NULL");
+    if (!ptrs || H < 1 || W < 1 || C_img < 1) return fail(ctx, UMX_ERR_INVALID, "bad image/out/H/W");
+    if (raw && bits != 8 && bits != 16) return fail(ctx, UMX_ERR_INVALID, "raw planes must be uint8 or uint16 (bits = %d)", bits);
+    if (C_img != 1 && C_img != ctx->hp.nChannels)
+        return fail(ctx, UMX_ERR_INVALID, "image has %d channels, model wants 1 or %d", C_img, ctx->hp.nChannels);
+    if (!(stdv != 0.0)) return fail(ctx, UMX_ERR_INVALID, "std must be non-zero");
+    if (mode != UMX_MODE_ACCUMULATE && mode != UMX_MODE_REPLACE) return fail(ctx, UMX_ERR_INVALID, "bad mode %d", mode);
+    if (stitch != UMX_STITCH_FP16_COMPAT && stitch != UMX_STITCH_FP32) return fail(ctx, UMX_ERR_INVALID, "bad stitch %d", stitch);
+    const uint32_t top = bits == 8 ? 255u : 65535u;
+    for (int c = 0; range && c < C_img; ++c)
+        if (range[2 * c] > range[2 * c + 1] || range[2 * c + 1] > top)
+            return fail(ctx, UMX_ERR_INVALID, "plane %d: range (%u, %u) is not a (min, max) of %d-bit samples", c, range[2 * c],
+                        range[2 * c + 1], bits);
+    return UMX_OK;
+}
+
+int slot_submit(umx_ctx* ctx, int slot, const std::function<int()>& enqueue) {
+    if (slot < 0 || slot > 1) return fail(ctx, UMX_ERR_INVALID, "slot must be 0 or 1");
+    if (ctx->hs[slot].busy) return fail(ctx, UMX_ERR_INVALID, "slot %d still holds a submitted call: wait for it first", slot);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    umx_ctx::HostSlot& hs = ctx->hs[slot];
+    auto begin = [&]() -> int {
+        if (!hs.done) {
+            HIP_TRY(ctx, hipEventCreateWithFlags(&hs.done, hipEventDisableTiming));
+            HIP_TRY(ctx, hipHostMalloc((void**)&hs.flag_host, 64, hipHostMallocDefault));
+        }
+        if (!ctx->up_stream) {
+            HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->up_stream, hipStreamNonBlocking));
+            HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->dn_stream, hipStreamNonBlocking));
+        }
+        // this call's range flag: its own word, cleared in stream order in front of its kernels
+        const int fw = 16 * (slot + 1);
+        if (ctx->d_flag) HIP_TRY(ctx, hipMemsetAsync(ctx->d_flag + fw, 0, sizeof(int), ctx->stream));
+        ctx->flag_word = fw;
+        return enqueue();
+    };
+    const int rc = begin();
+    ctx->flag_word = 0;
+    if (rc) {
+        // an error in the middle of enqueueing: transfers that reference the caller's buffers and this slot's device buffers may
+        // be in flight -- drain them before the caller (or the next submit) frees or reuses anything
+        const std::string msg = ctx->err;
+        if (ctx->up_stream) hipStreamSynchronize(ctx->up_stream);
+        hipStreamSynchronize(ctx->stream);
+        if (ctx->dn_stream) hipStreamSynchronize(ctx->dn_stream);
+        ctx->err = msg;
+    }
+    return rc;
+}
+
+int slot_finish(umx_ctx* ctx, int slot, hipStream_t dn_s) {
+    umx_ctx::HostSlot& hs = ctx->hs[slot];
+    if (ctx->d_flag)
+        HIP_TRY(ctx, hipMemcpyAsync(hs.flag_host, ctx->d_flag + 16 * (slot + 1), sizeof(int), hipMemcpyDeviceToHost, dn_s));
+    else
+        *hs.flag_host = 0;
+    HIP_TRY(ctx, hipEventRecord(hs.done, dn_s));
+    hs.busy = true;
+    return UMX_OK;
+}
+
+int put_range(umx_ctx* ctx, unsigned* mm, const uint32_t* range, int C_img) {
+    for (int c = 0; c < C_img; ++c) {
+        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)(mm + 16 * c), (int)range[2 * c], 1, ctx->stream));
+        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)(mm + 16 * c + 1), (int)range[2 * c + 1], 1, ctx->stream));
+    }
+    return UMX_OK;
+}
+
+}  // namespace umx
 
 extern "C" {
 
@@ -62,20 +134,21 @@ static int host_wait(umx_ctx* ctx, int slot) {
     umx_ctx::HostSlot& hs = ctx->hs[slot];
     if (!hs.busy) return UMX_OK;
     hs.busy = false;
-    if (const int rc = umx_internal_wait_event(ctx, hs.done)) return rc;   // (a sharded context polls its communicator while it waits)
+    if (ctx->shard) {   // a sharded context polls its communicator while it waits
+        if (const int rc = shard_wait(ctx, hs.done)) return rc;
+    } else if (const hipError_t e = hipEventSynchronize(hs.done)) {
+        return fail(ctx, UMX_ERR_HIP, "hipEventSynchronize failed: %s", hipGetErrorString(e));
+    }
     if (*hs.flag_host)   // this slot's own flag word, cleared by the next submit on the slot in stream order
         return fail(ctx, UMX_ERR_RANGE, "an activation left the binary16 range of the split-precision path; "
                                         "create the context with UMX_PREC_F32 (or UMX_PRECISION=f32)");
     return UMX_OK;
 }
 
-static int host_submit_impl(umx_ctx* ctx, int slot, bool sync_call, const void* src, int src_bits, int C_img, int H, int W, int rescale,
-                            double mean, double stdv, int mode, int stitch, int out_u8, void* out_host) {
+// range: the planes' (min, max) as the caller's reader found them, or NULL
+static int host_enqueue(umx_ctx* ctx, int slot, bool sync_call, const void* src, int src_bits, int C_img, int H, int W, int rescale,
+                        const uint32_t* range, double mean, double stdv, int mode, int stitch, int out_u8, void* out_host) {
     umx_ctx::HostSlot& hs = ctx->hs[slot];
-    if (!hs.done) {
-        HIP_TRY(ctx, hipEventCreateWithFlags(&hs.done, hipEventDisableTiming));
-        HIP_TRY(ctx, hipHostMalloc((void**)&hs.flag_host, 64, hipHostMallocDefault));
-    }
     const TileGeom g = geom_of(ctx->hp, H, W);
     const size_t plane = (size_t)H * W, K = ctx->hp.nClasses;
     const size_t in_b = src_bits ? (size_t)(src_bits / 8) : sizeof(double);
@@ -93,10 +166,6 @@ static int host_submit_impl(umx_ctx* ctx, int slot, bool sync_call, const void* 
     if ((rc = grow(ctx, &hs.d_out, &hs.out_cap, mm_off + 64 * (size_t)C_img))) return rc;
     if ((rc = grow(ctx, (void**)&hs.d_probs, &hs.probs_cap, (size_t)g.npr * g.npc * g.P * g.P * K * sizeof(float)))) return rc;
     unsigned char* const base = (unsigned char*)hs.d_out;
-    if (!ctx->up_stream) {
-        HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->up_stream, hipStreamNonBlocking));
-        HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->dn_stream, hipStreamNonBlocking));
-    }
     // slabs = the launch groups of the tile loop (equal groups of <= max_batch tiles, exactly what umx_infer_image_dev
     // runs), so that pipelining the transfers does not change a single kernel launch
     const int T = g.npr * g.npc;
@@ -112,10 +181,6 @@ static int host_submit_impl(umx_ctx* ctx, int slot, bool sync_call, const void* 
     slide_flops *= (double)T;
     const bool single = S == 1 && (sync_call || slide_flops < 0.6e12);
     const hipStream_t up_s = single ? ctx->stream : ctx->up_stream, dn_s = single ? ctx->stream : ctx->dn_stream;
-    // this call's range flag: its own word, cleared in stream order in front of its kernels
-    const int fw = 16 * (slot + 1);
-    if (ctx->d_flag) HIP_TRY(ctx, hipMemsetAsync(ctx->d_flag + fw, 0, sizeof(int), ctx->stream));
-    ctx->flag_word = fw;
     while ((int)hs.events.size() < 2 * S + 1) {
         hipEvent_t ev;
         HIP_TRY(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -154,9 +219,8 @@ static int host_submit_impl(umx_ctx* ctx, int slot, bool sync_call, const void* 
     // planes' (min, max) found by host threads while the rows cross the bus (3 ms per 537 MB plane), and the tile kernels start on
     // the first slab as soon as that pass is done -- instead of behind the whole upload and a device reduction (UMX_HOST_RANGE=0)
     uint32_t own_range[2 * 8];
-    const uint32_t* range_in = ctx->range_in;
     std::vector<int> pre_r1;   // rows up after slab s, when the uploads were enqueued ahead
-    if (src_bits && rescale && !range_in && sync_call && C_img <= 8 && !(getenv("UMX_HOST_RANGE") && atoi(getenv("UMX_HOST_RANGE")) == 0)) {
+    if (src_bits && rescale && !range && sync_call && C_img <= 8 && !(getenv("UMX_HOST_RANGE") && atoi(getenv("UMX_HOST_RANGE")) == 0)) {
         pre_r1.resize(S);
         for (int s = 0; s < S; ++s) {
             const int r1 = s == S - 1 ? H : rows_needed((tcut[s + 1] - 1) / g.npc + 1);
@@ -170,18 +234,15 @@ static int host_submit_impl(umx_ctx* ctx, int slot, bool sync_call, const void* 
         for (int c = 0; c < C_img; ++c)
             if (umx_plane_range((const unsigned char*)src + (size_t)c * plane * in_b, src_bits, plane, own_range + 2 * c) != UMX_OK)
                 return fail(ctx, UMX_ERR_INVALID, "plane range");
-        range_in = own_range;
+        range = own_range;
     }
     if (src_bits) {
         for (int c = 0; c < C_img; ++c) HIP_TRY(ctx, launch_minmax_init(mm + 16 * c, ctx->stream));
-        if (rescale && range_in) {
+        if (rescale && range) {
             // the caller's file reader saw every sample and hands the planes' (min, max) in: the words the reduction below would
             // leave, so the slide goes up slab by slab under the tile kernels like an un-rescaled one (a synchronous rescaled
             // call otherwise spends the whole upload -- 21 ms for the 1.07 GB metric slide -- in front of its first tile)
-            for (int c = 0; c < C_img; ++c) {
-                HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)(mm + 16 * c), (int)range_in[2 * c], 1, ctx->stream));
-                HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)(mm + 16 * c + 1), (int)range_in[2 * c + 1], 1, ctx->stream));
-            }
+            if ((rc = put_range(ctx, mm, range, C_img))) return rc;
         } else if (rescale) {   // whole planes first: min / max per plane, reduced as the slabs arrive
             for (int s = 0; s < S; ++s) {
                 const int r1 = s == S - 1 ? H : rows_needed((tcut[s + 1] - 1) / g.npc + 1);
@@ -248,71 +309,34 @@ static int host_submit_impl(umx_ctx* ctx, int slot, bool sync_call, const void* 
     }
     // the range flag of the split-precision path rides down behind the last planes; `done` then says the call is complete
     // (every upload precedes a kernel that precedes a download on the download stream)
-    if (ctx->d_flag) {
-        if (!single) {
-            hipEvent_t ev_f = hs.events[2 * S];
-            HIP_TRY(ctx, hipEventRecord(ev_f, ctx->stream));
-            HIP_TRY(ctx, hipStreamWaitEvent(ctx->dn_stream, ev_f, 0));
-        }
-        HIP_TRY(ctx, hipMemcpyAsync(hs.flag_host, ctx->d_flag + fw, sizeof(int), hipMemcpyDeviceToHost, dn_s));
-    } else {
-        *hs.flag_host = 0;
+    if (ctx->d_flag && !single) {
+        hipEvent_t ev_f = hs.events[2 * S];
+        HIP_TRY(ctx, hipEventRecord(ev_f, ctx->stream));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->dn_stream, ev_f, 0));
     }
-    HIP_TRY(ctx, hipEventRecord(hs.done, dn_s));
-    hs.busy = true;
-    return UMX_OK;
+    return slot_finish(ctx, slot, dn_s);
 }
 
+// sync_call: a synchronous entry (slot 0), which also waits for the call
 static int host_submit(umx_ctx* ctx, int slot, bool sync_call, const void* src, int src_bits, int C_img, int H, int W, int rescale,
-                       double mean, double stdv, int mode, int stitch, int out_u8, void* out_host) {
-    if (slot < 0 || slot > 1) return fail(ctx, UMX_ERR_INVALID, "slot must be 0 or 1");
-    if (ctx->hs[slot].busy) return fail(ctx, UMX_ERR_INVALID, "slot %d still holds a submitted call: wait for it first", slot);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int rc = host_submit_impl(ctx, slot, sync_call, src, src_bits, C_img, H, W, rescale, mean, stdv, mode, stitch, out_u8, out_host);
-    ctx->flag_word = 0;
-    if (rc) {
-        // an error in the middle of enqueueing: transfers that reference the caller's buffers and this slot's device buffers may
-        // be in flight -- drain them before the caller (or the next submit) frees or reuses anything
-        const std::string msg = ctx->err;
-        if (ctx->up_stream) hipStreamSynchronize(ctx->up_stream);
-        hipStreamSynchronize(ctx->stream);
-        if (ctx->dn_stream) hipStreamSynchronize(ctx->dn_stream);
-        ctx->err = msg;
-    }
-    return rc;
+                       const uint32_t* range, double mean, double stdv, int mode, int stitch, int out_u8, void* out_host) {
+    const int rc = slot_submit(ctx, slot, [&] {
+        return host_enqueue(ctx, slot, sync_call, src, src_bits, C_img, H, W, rescale, range, mean, stdv, mode, stitch, out_u8, out_host);
+    });
+    return rc || !sync_call ? rc : host_wait(ctx, slot);
 }
-
-static int infer_host(umx_ctx* ctx, const void* src, int src_bits, int C_img, int H, int W, int rescale, double mean,
-                      double stdv, int mode, int stitch, int out_u8, void* out_host) {
-    int rc = host_submit(ctx, 0, true, src, src_bits, C_img, H, W, rescale, mean, stdv, mode, stitch, out_u8, out_host);
-    if (rc) return rc;
-    return host_wait(ctx, 0);
-}
-
-
 
 int umx_infer_image(umx_ctx* ctx, const double* image_host, int C_img, int H, int W, double mean, double stdv, int mode,
                     int stitch, void* out_host) {
-    if (!ctx) return fail(nullptr, UMX_ERR_INVALID, "ctx is NULL");
-    if (!image_host || !out_host || H < 1 || W < 1 || C_img < 1) return fail(ctx, UMX_ERR_INVALID, "bad image/out/H/W");
-    if (C_img != 1 && C_img != ctx->hp.nChannels)
-        return fail(ctx, UMX_ERR_INVALID, "image has %d channels, model wants 1 or %d", C_img, ctx->hp.nChannels);
-    if (!(stdv != 0.0)) return fail(ctx, UMX_ERR_INVALID, "std must be non-zero");
-    if (mode != UMX_MODE_ACCUMULATE && mode != UMX_MODE_REPLACE) return fail(ctx, UMX_ERR_INVALID, "bad mode %d", mode);
-    if (stitch != UMX_STITCH_FP16_COMPAT && stitch != UMX_STITCH_FP32) return fail(ctx, UMX_ERR_INVALID, "bad stitch %d", stitch);
-    return infer_host(ctx, image_host, 0, C_img, H, W, 0, mean, stdv, mode, stitch, 0, out_host);
+    if (const int rc = check_image(ctx, image_host && out_host, C_img, H, W, false, 0, stdv, mode, stitch, nullptr)) return rc;
+    return host_submit(ctx, 0, true, image_host, 0, C_img, H, W, 0, nullptr, mean, stdv, mode, stitch, 0, out_host);
 }
 
 int umx_infer_image_raw(umx_ctx* ctx, const void* raw_host, int bits, int C_img, int H, int W, int rescale, double mean,
                         double stdv, int mode, uint8_t* out_host) {
-    if (!ctx) return fail(nullptr, UMX_ERR_INVALID, "ctx is NULL");
-    if (!raw_host || !out_host || H < 1 || W < 1 || C_img < 1) return fail(ctx, UMX_ERR_INVALID, "bad image/out/H/W");
-    if (bits != 8 && bits != 16) return fail(ctx, UMX_ERR_INVALID, "raw planes must be uint8 or uint16 (bits = %d)", bits);
-    if (C_img != 1 && C_img != ctx->hp.nChannels)
-        return fail(ctx, UMX_ERR_INVALID, "image has %d channels, model wants 1 or %d", C_img, ctx->hp.nChannels);
-    if (!(stdv != 0.0)) return fail(ctx, UMX_ERR_INVALID, "std must be non-zero");
-    if (mode != UMX_MODE_ACCUMULATE && mode != UMX_MODE_REPLACE) return fail(ctx, UMX_ERR_INVALID, "bad mode %d", mode);
-    return infer_host(ctx, raw_host, bits, C_img, H, W, rescale, mean, stdv, mode, UMX_STITCH_FP16_COMPAT, 1, out_host);
+    if (const int rc = check_image(ctx, raw_host && out_host, C_img, H, W, true, bits, stdv, mode, UMX_STITCH_FP16_COMPAT, nullptr))
+        return rc;
+    return host_submit(ctx, 0, true, raw_host, bits, C_img, H, W, rescale, nullptr, mean, stdv, mode, UMX_STITCH_FP16_COMPAT, 1, out_host);
 }
 
 int umx_plane_range(const void* raw_host, int bits, size_t n, uint32_t* range) {
@@ -324,18 +348,9 @@ int umx_plane_range(const void* raw_host, int bits, size_t n, uint32_t* range) {
 
 int umx_infer_image_raw_range(umx_ctx* ctx, const void* raw_host, int bits, int C_img, int H, int W, const uint32_t* range,
                               double mean, double stdv, int mode, uint8_t* out_host) {
-    if (!ctx) return fail(nullptr, UMX_ERR_INVALID, "ctx is NULL");
-    if (!range) return umx_infer_image_raw(ctx, raw_host, bits, C_img, H, W, 1, mean, stdv, mode, out_host);
-    if (C_img < 1) return fail(ctx, UMX_ERR_INVALID, "bad image/out/H/W");
-    const uint32_t top = bits == 8 ? 255u : 65535u;
-    for (int c = 0; c < C_img; ++c)
-        if (range[2 * c] > range[2 * c + 1] || range[2 * c + 1] > top)
-            return fail(ctx, UMX_ERR_INVALID, "plane %d: range (%u, %u) is not a (min, max) of %d-bit samples", c, range[2 * c],
-                        range[2 * c + 1], bits);
-    ctx->range_in = range;
-    const int rc = umx_infer_image_raw(ctx, raw_host, bits, C_img, H, W, 1, mean, stdv, mode, out_host);
-    ctx->range_in = nullptr;
-    return rc;
+    if (const int rc = check_image(ctx, raw_host && out_host, C_img, H, W, true, bits, stdv, mode, UMX_STITCH_FP16_COMPAT, range))
+        return rc;
+    return host_submit(ctx, 0, true, raw_host, bits, C_img, H, W, 1, range, mean, stdv, mode, UMX_STITCH_FP16_COMPAT, 1, out_host);
 }
 
 // ---- the drivers' whole recipe at --scalingFactor != 1 on the device (reference UnMicst1-5.py:807-821,845-854):
@@ -375,18 +390,13 @@ static int resize_plane(umx_ctx* ctx, const double* src, int H, int W, int h, in
 // outlier < 0: rescale (if set) to the plane's (min, max); outlier in [0, 100]: to (min, np.percentile(plane, outlier))
 static int infer_raw_scaled_impl(umx_ctx* ctx, const void* raw_host, int bits, int C_img, int H, int W, double scaling, int rescale,
                                  double outlier, double mean, double stdv, int mode, uint8_t* out_host) {
-    if (!ctx) return fail(nullptr, UMX_ERR_INVALID, "ctx is NULL");
-    if (!raw_host || !out_host || H < 1 || W < 1 || C_img < 1) return fail(ctx, UMX_ERR_INVALID, "bad image/out/H/W");
-    if (bits != 8 && bits != 16) return fail(ctx, UMX_ERR_INVALID, "raw planes must be uint8 or uint16 (bits = %d)", bits);
-    if (C_img != 1 && C_img != ctx->hp.nChannels)
-        return fail(ctx, UMX_ERR_INVALID, "image has %d channels, model wants 1 or %d", C_img, ctx->hp.nChannels);
-    if (!(stdv != 0.0)) return fail(ctx, UMX_ERR_INVALID, "std must be non-zero");
+    if (const int rc = check_image(ctx, raw_host && out_host, C_img, H, W, true, bits, stdv, mode, UMX_STITCH_FP16_COMPAT, nullptr))
+        return rc;
     if (!(scaling > 0.0)) return fail(ctx, UMX_ERR_INVALID, "scaling factor must be positive");
     const int h = (int)((double)H * scaling), w = (int)((double)W * scaling);   // int(float(I.shape[0]) * float(sf))
     if (h < 1 || w < 1) return fail(ctx, UMX_ERR_INVALID, "scaled image is empty");
     const bool same = h == H && w == W;   // resize(I, I.shape) leaves im2double(I): the pipelined path does all but the percentile
     if (same && outlier < 0) return umx_infer_image_raw(ctx, raw_host, bits, C_img, H, W, rescale, mean, stdv, mode, out_host);
-    if (mode != UMX_MODE_ACCUMULATE && mode != UMX_MODE_REPLACE) return fail(ctx, UMX_ERR_INVALID, "bad mode %d", mode);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t big = (size_t)std::max(H, h) * std::max(W, w), plane = (size_t)H * W, sp = (size_t)h * w, K = ctx->hp.nClasses;
     const size_t in_b = bits / 8;
@@ -446,14 +456,9 @@ int umx_infer_image_raw_outlier(umx_ctx* ctx, const void* raw_host, int bits, in
 
 int umx_infer_image_raw_submit(umx_ctx* ctx, int slot, const void* raw_host, int bits, int C_img, int H, int W, int rescale,
                                double mean, double stdv, int mode, uint8_t* out_host) {
-    if (!ctx) return fail(nullptr, UMX_ERR_INVALID, "ctx is NULL");
-    if (!raw_host || !out_host || H < 1 || W < 1 || C_img < 1) return fail(ctx, UMX_ERR_INVALID, "bad image/out/H/W");
-    if (bits != 8 && bits != 16) return fail(ctx, UMX_ERR_INVALID, "raw planes must be uint8 or uint16 (bits = %d)", bits);
-    if (C_img != 1 && C_img != ctx->hp.nChannels)
-        return fail(ctx, UMX_ERR_INVALID, "image has %d channels, model wants 1 or %d", C_img, ctx->hp.nChannels);
-    if (!(stdv != 0.0)) return fail(ctx, UMX_ERR_INVALID, "std must be non-zero");
-    if (mode != UMX_MODE_ACCUMULATE && mode != UMX_MODE_REPLACE) return fail(ctx, UMX_ERR_INVALID, "bad mode %d", mode);
-    return host_submit(ctx, slot, false, raw_host, bits, C_img, H, W, rescale, mean, stdv, mode, UMX_STITCH_FP16_COMPAT, 1, out_host);
+    if (const int rc = check_image(ctx, raw_host && out_host, C_img, H, W, true, bits, stdv, mode, UMX_STITCH_FP16_COMPAT, nullptr))
+        return rc;
+    return host_submit(ctx, slot, false, raw_host, bits, C_img, H, W, rescale, nullptr, mean, stdv, mode, UMX_STITCH_FP16_COMPAT, 1, out_host);
 }
 
 int umx_infer_image_wait(umx_ctx* ctx, int slot) {

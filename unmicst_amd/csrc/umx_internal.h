@@ -9,6 +9,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <string>
@@ -118,6 +119,8 @@ struct PendingEvent {
     hipEvent_t a, b;
 };
 
+struct Shard;   // umx_shard.hip: the communicator, transport and buffers umx_shard_init attaches to a context
+
 }  // namespace umx
 
 struct umx_ctx {
@@ -142,7 +145,6 @@ struct umx_ctx {
     int ncu = 256;
     // host entry points: uploads / downloads on their own streams, slab by slab, under the tile kernels
     hipStream_t up_stream = nullptr, dn_stream = nullptr;
-    const uint32_t* range_in = nullptr;   // (during umx_infer_image_raw_range) the planes' (min, max) as the caller's reader found them
     struct HostSlot {   // device buffers + events of one in-flight host call (two slots: slide i+1 uploads while slide i computes)
         double* d_image = nullptr;  size_t image_cap = 0;
         float* d_probs = nullptr;   size_t probs_cap = 0;
@@ -181,6 +183,7 @@ struct umx_ctx {
     uint4* d_zeros = nullptr;
     bool head_fused = false;
     Launch split_launch;
+    umx::Shard* shard = nullptr;   // set by umx_shard_init / umx_shard_init_transport once it has fully succeeded
 };
 
 namespace umx {
@@ -259,7 +262,8 @@ int upload_raw(umx_ctx* ctx, const std::vector<T>& h, T** out) {
     return UMX_OK;
 }
 
-int grow(umx_ctx* ctx, void** buf, size_t* cap, size_t bytes);
+// a buffer is freed to grow once the context's stream -- or, for one other streams read, the whole device (device_wide) -- is idle
+int grow(umx_ctx* ctx, void** buf, size_t* cap, size_t bytes, bool device_wide = false);
 int site_of(umx_ctx* ctx, const std::string& name, const std::string& kernel);
 int prof_fold(umx_ctx* ctx);
 struct ProfScope {
@@ -306,6 +310,21 @@ int tiles_range(umx_ctx* ctx, const double* image_dev, int C_img, const TileGeom
                 const unsigned* mm_dev = nullptr /* raw planes: rescale_intensity to each plane's (min, max) words, 16 words apart */);
 // the tile gather of this engine can read raw integer planes (im2double in the gather: no float64 image is written or read)
 bool gathers_raw(const umx_ctx* ctx);
+
+// ---- umx_host.hip: the image entries' argument checks (nothing enqueued; raw: 8 / 16-bit planes, else float64; range may be NULL)
+int check_image(umx_ctx* ctx, bool ptrs, int C_img, int H, int W, bool raw, int bits, double stdv, int mode, int stitch,
+                const uint32_t* range);
+// a call on host slot `slot` (umx_ctx::hs): slot checks, hipSetDevice, the slot's prologue (its range-flag word cleared and made the
+// launches'), then `enqueue`, which ends in slot_finish; an error after the checks drains the upload, context and download streams
+int slot_submit(umx_ctx* ctx, int slot, const std::function<int()>& enqueue);
+// the slot's range flag goes down on dn_s behind what that stream holds, `done` is recorded there and the slot is busy
+int slot_finish(umx_ctx* ctx, int slot, hipStream_t dn_s);
+// a caller's planes' (min, max) -> each plane's mm words (16 apart), on the context's stream
+int put_range(umx_ctx* ctx, unsigned* mm, const uint32_t* range, int C_img);
+
+// ---- umx_shard.hip
+void shard_release(umx_ctx* ctx);               // frees ctx->shard
+int shard_wait(umx_ctx* ctx, hipEvent_t ev);    // the bounded wait of a submitted call on a sharded context
 
 // ---- device memory of a trainer / training set (umx_train.hip) ----
 // Every allocation goes through arena_alloc.  Debug guard mode (UMX_DEBUG_GUARD=<byte>, read at umx_trainer_create /
