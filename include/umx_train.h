@@ -150,11 +150,50 @@ UMX_API int umx_trainer_assemble(umx_trainer* tr, const umx_trainset* ts, const 
 UMX_API int umx_trainer_evaluate(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, int n, int64_t* counts,
                                  double* loss_sum);
 
+/* ---- computed defocus and saturation ("Blur and saturation") ----
+ * Per image of a batch, next to its umx_sample_desc: a blur level (index into the set's table of Gaussian kernels, 0 = none) and a
+ * saturation gain >= 1 (1 = none).  Order per image and channel: page plane -> blur -> saturation -> crop + dihedral transform ->
+ * brightness / contrast jitter.  Labels and weight maps are never filtered.
+ *   blur        separable, edges replicated at the SAMPLE's edge (a crop in the middle of a sample sees its real neighbours):
+ *               h[r][x] = float32(sum over t = -R..R, ascending, of (double)w[|t|] * (double)p[r][clamp(x + t, 0, size-1)]), then the
+ *               same down the columns of h; the sum starts at 0.0, every product and every sum is one float64 rounding (no fma).
+ *               Level 0 is skipped, not multiplied by w[0].
+ *   saturation  only when gain != 1: r = (double)b * std + mean; r2 = min(r * gain, 1.0); s = float32((r2 - mean) / std), each
+ *               operation one float64 rounding: the pixel back on the im2double scale, amplified, clipped at the sensor's ceiling. */
+#define UMX_AUGMENT_MAX_LEVELS 16
+#define UMX_AUGMENT_MAX_RADIUS 12
+typedef struct umx_augment_table {
+    float mean, std;                  /* the set's normalisation (planes hold (im2double(x) - mean) / std) */
+    int32_t n_levels;                 /* 1..16; level 0 is "no blur" and must have radius 0 */
+    int32_t radius[UMX_AUGMENT_MAX_LEVELS];   /* 0..12 */
+    float taps[UMX_AUGMENT_MAX_LEVELS][UMX_AUGMENT_MAX_RADIUS + 1];   /* taps[l][t]: weight at distance t <= radius[l] */
+    int32_t reserved[5];              /* must be zero */
+} umx_augment_table;
+
+typedef struct umx_augment_desc {     /* 8 bytes: one image of a batch, parallel to its umx_sample_desc */
+    int32_t blur_level;               /* 0 .. n_levels - 1 */
+    float gain;                       /* finite, >= 1 */
+} umx_augment_desc;
+
+/* Host validation of a table (no device needed): 1 <= n_levels <= 16, level 0 has radius 0, radii in 0..12, taps finite and
+ * non-negative, mean finite, std finite and > 0, reserved zero.  UMX_OK, or UMX_ERR_INVALID with the broken
+ * rule in msg (cap bytes, NUL-terminated; msg may be NULL). */
+UMX_API int umx_augment_table_check(const umx_augment_table* table, char* msg, size_t cap);
+/* Attach (or replace) the table of a set; waits for the trainer's stream first.  The table is copied. */
+UMX_API int umx_trainset_set_augment(umx_trainset* ts, const umx_augment_table* table);
+/* umx_train_step_sampled / umx_trainer_assemble with a parallel array of umx_augment_desc (B resp. n of them).  Checked on the host
+ * like the descriptors, before anything is enqueued: UMX_ERR_INVALID for a set without a table, a level outside the table, a gain
+ * that is not finite or < 1.  An image with (level 0, gain 1) is assembled exactly as the plain entries assemble it. */
+UMX_API int umx_train_step_augmented(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc,
+                                     const umx_augment_desc* aug, int apply_update);
+UMX_API int umx_trainer_assemble_augmented(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc,
+                                           const umx_augment_desc* aug, int n, float* data, float* labels, float* weights);
+
 /* Debug guard mode.  UMX_DEBUG_GUARD=<byte> (e.g. 0xff), read by umx_trainer_create and umx_trainset_create, gives every device
  * buffer of that trainer / set a red zone of max(64 KiB, its size rounded up to 4 KiB) on both sides.  The zones, and every buffer
  * the library does not zero or upload, are filled with that byte, so a result that depends on the byte read memory nobody wrote.
- * Every entry that enqueues work (umx_train_step, _step_dev, _step_sampled, umx_trainer_eval, _assemble, _evaluate,
- * umx_trainset_set) then waits for the trainer's streams and checks every zone: UMX_ERR_GUARD names the buffer, the side and the
+ * Every entry that enqueues work (umx_train_step, _step_dev, _step_sampled, _step_augmented, umx_trainer_eval, _assemble,
+ * _assemble_augmented, _evaluate, umx_trainset_set) then waits for the trainer's streams and checks every zone: UMX_ERR_GUARD names the buffer, the side and the
  * first and last changed byte.  Slow; for tests.  Off (unset or empty), allocations and launches are exactly the normal ones.
  *
  * The host scan of one zone (no device needed): zone_bytes bytes that should all equal `fill`, in front of (side 0) or behind

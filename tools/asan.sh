@@ -24,12 +24,12 @@ rc=0; for p in "${pids[@]:-}"; do [ -n "$p" ] && { wait $p || rc=1; }; done
 $ROCM/bin/hipcc --offload-arch=gfx950 -shared -fPIC -no-hip-rt -fsanitize=address,undefined -shared-libasan -o unmicst_amd/libumx_asan.so $(for s in $SRCS; do echo $OBJ/$s.o; done) -ldl || exit 2
 {
   echo "# tools/asan.sh at $(git rev-parse --short HEAD 2>/dev/null) on $(date -u +%FT%TZ): host-side ASan + UBSan build of libumx ($RT)"
-  echo "# tests: test_abi test_host_logic test_meta_wiring test_tiffio_cpu test_driver_cpu test_sharding_cpu test_plan_check_cpu (no GPU in this container)"
+  echo "# tests: test_abi test_host_logic test_meta_wiring test_tiffio_cpu test_driver_cpu test_sharding_cpu test_plan_check_cpu test_trainset_augment_cpu (no GPU in this container)"
 } > $LOG
 # leak detection off: CPython itself never frees its arenas; halt on the first real error
 UMX_LIB=$PWD/unmicst_amd/libumx_asan.so LD_PRELOAD=$RT ASAN_OPTIONS=detect_leaks=0:abort_on_error=0:halt_on_error=1:exitcode=66 \
 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 \
-  python -m pytest tests/test_abi.py tests/test_host_logic.py tests/test_meta_wiring.py tests/test_tiffio_cpu.py tests/test_driver_cpu.py tests/test_sharding_cpu.py tests/test_plan_check_cpu.py -q -x -p no:cacheprovider >> $LOG 2>&1
+  python -m pytest tests/test_abi.py tests/test_host_logic.py tests/test_meta_wiring.py tests/test_tiffio_cpu.py tests/test_driver_cpu.py tests/test_sharding_cpu.py tests/test_plan_check_cpu.py tests/test_trainset_augment_cpu.py -q -x -p no:cacheprovider >> $LOG 2>&1
 rc=$?
 echo "# pytest exit status $rc; sanitizer reports in this log: $(grep -c 'ERROR: AddressSanitizer\|runtime error:' $LOG)" >> $LOG
 tail -5 $LOG

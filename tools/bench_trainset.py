@@ -1,7 +1,10 @@
 """Images/s of a training step fed from the device-resident training set (Trainer.step_sampled) against the host-fed step
 (numpy batch assembly -- crop, augmentation page, dihedral transform, jitter, one-hot labels, weight maps -- then Trainer.step),
 in one process, alternating the two, on the same descriptor stream.  Every step reads its loss (one synchronisation per step on
-both paths).  Then the validation pass (Trainer.evaluate) over the whole set.  One JSON line per (shape, path, repeat).
+both paths).  A third leg, "augmented", is Trainer.step_augmented with every image at the largest blur level of the sigmas
+0.75, 1.5, 3 and gain 2 -- the worst case of the computed defocus / saturation -- alternated with the other two in the same process,
+so that step_sampled of the same run is its yardstick.  Then the validation pass (Trainer.evaluate) over the whole set.  One JSON
+line per (shape, path, repeat).
 
     python tools/bench_trainset.py [--steps 30] [--warmup 5] [--repeats 3] [--shapes nucleiDAPI,v2-256]
 """
@@ -74,6 +77,9 @@ def main():
         blob = model.random_blob(hp, seed=1)
         tr = trainer.Trainer(hp, blob, opts, batch=B)
         ts = trainset.TrainSet.from_arrays(tr, planes, ann, list(wmaps), lw)
+        ts.set_augment(trainset.AugmentTable.from_sigmas((0.75, 1.5, 3.0), 0.3, 0.2))
+        worst = np.zeros(B, trainer.AUGMENT_DESC)
+        worst["blur_level"], worst["gain"] = 3, 2.0
         sampler = trainset.Sampler(1, a.samples, B, S, P, pages, mb, mc, transforms=True)
         per_step = B * P * P * (hp.nChannels + (2 if lw.weighted else 1) * hp.nClasses) * 4
 
@@ -84,6 +90,13 @@ def main():
                 tr.loss()
             return time.perf_counter() - t0
 
+        def run_augmented(n):
+            t0 = time.perf_counter()
+            for _ in range(n):
+                tr.step_augmented(ts, sampler.next(), worst)
+                tr.loss()
+            return time.perf_counter() - t0
+
         def run_host(n):
             t0 = time.perf_counter()
             for _ in range(n):
@@ -91,9 +104,10 @@ def main():
             return time.perf_counter() - t0
 
         run_sampled(a.warmup)
+        run_augmented(a.warmup)
         run_host(a.warmup)
         for r in range(a.repeats):
-            for path, fn in (("step_sampled", run_sampled), ("host_fed", run_host)):
+            for path, fn in (("step_sampled", run_sampled), ("augmented", run_augmented), ("host_fed", run_host)):
                 dt = fn(a.steps)
                 print(json.dumps({"shape": name, "batch": B, "path": path, "repeat": r, "steps": a.steps, "seconds": round(dt, 5),
                                   "images_per_s": round(a.steps * B / dt, 1), "step_ms": round(1e3 * dt / a.steps, 4),

@@ -379,6 +379,18 @@ struct TrainSetView {                  // device layout of one training set
 // rows b0 .. b0+m-1 of data [B,P,P,C] / labels, weights [B,P,P,K] (weights null: none); a descriptor with index < 0 writes zeros
 hipError_t launch_assemble_batch(const TrainSetView& ts, const DescChunk& dc, int m, int b0, int P, int K, float* data, float* labels,
                                  float* weights, hipStream_t stream);
+// the data planes of the images that ask for blur or saturation (umx_augment_desc), written over what launch_assemble_batch wrote
+constexpr int kAugChunk = 16;          // such images per launch (passed by value: 1.5 KiB of kernel arguments)
+struct AugImage {
+    umx_sample_desc d;
+    int row;                           // image of the batch
+    int R;                             // blur radius; -1: no blur (level 0)
+    float gain;
+    float taps[UMX_AUGMENT_MAX_RADIUS + 1];
+};
+struct AugChunk { AugImage im[kAugChunk]; };
+hipError_t launch_assemble_augmented(const TrainSetView& ts, const AugChunk& ac, int m, int P, float mean, float std, float* data,
+                                     hipStream_t stream);
 // counts [2K] int64 (correct | labelled) and loss [1] double over npix pixels of probs / labels [npix, K]; part: class_counts_parts(npix)
 // doubles of workspace
 size_t class_counts_parts(size_t npix, int K);

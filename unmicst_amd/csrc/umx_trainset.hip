@@ -1,5 +1,6 @@
 // libumx device-resident training set: storage, the two kernels that feed the training step from it, and the C ABI of the
-// umx_trainset_* / umx_train_step_sampled / umx_trainer_assemble / umx_trainer_evaluate entries of include/umx_train.h.
+// umx_trainset_* / umx_train_step_sampled / _augmented / umx_trainer_assemble / _augmented / umx_trainer_evaluate entries of
+// include/umx_train.h.
 //
 // The set is the reference's annotated layout (I%05d_Img.tif pages, _Ant.tif class codes, _wt.tif contour-intersection map;
 // UnMicst1-5.py:295-312, UnMicst2.py:293-309, UnMicst.py:236-243) uploaded once, already normalised.  A step then costs 32 bytes
@@ -8,6 +9,8 @@
 //
 //   assemble_batch_kernel  data[b,y,x,c] = float32((double)v * contrast + brightness) at the transformed crop coordinate;
 //                          labels[b,y,x,k] = (code == k+1); weights[b,y,x,k] = float32((double)iw[k] * wmap + cw[k])
+//   assemble_augmented_kernel  the data planes of the images that ask for a blur level or a saturation gain (umx_augment_desc):
+//                          page plane -> separable Gaussian blur -> saturation -> crop + transform -> jitter, float64 in a fixed order
 //   class_counts_kernel    per block: correct / labelled per class (int64) and sum of -log p[label] (float64), fixed order;
 //   class_counts_final     one block sums the block partials in a fixed order
 #include "../../include/umx_train.h"
@@ -25,12 +28,17 @@ using namespace umx;
 static_assert(sizeof(umx_sample_desc) == 32, "umx_sample_desc is 32 bytes");
 static_assert(sizeof(umx_label_weights) == 4 + 8 * 4 + 8 * 4 + 7 * 4, "umx_label_weights layout");
 static_assert(sizeof(DescChunk) <= 2048, "a descriptor chunk travels as kernel arguments");
+static_assert(sizeof(umx_augment_desc) == 8, "umx_augment_desc is 8 bytes");
+static_assert(sizeof(umx_augment_table) == 12 + 16 * 4 + 16 * 13 * 4 + 5 * 4, "umx_augment_table layout");
+static_assert(sizeof(AugChunk) <= 2048, "a chunk of augmented images travels as kernel arguments");
 
 struct umx_trainset {
     umx_trainer* tr = nullptr;
     int N = 0, pages = 0, S = 0, C = 0, K = 0, row_f = 0, row_a = 0;
     bool weighted = false;
     umx_label_weights lw;
+    bool has_aug = false;               // umx_trainset_set_augment was called
+    umx_augment_table aug;              // (host copy: levels travel to the kernel as arguments)
     float* planes = nullptr;
     uint8_t* ann = nullptr;
     float* wmap = nullptr;
@@ -95,6 +103,76 @@ __global__ void __launch_bounds__(256) assemble_batch_kernel(TrainSetView ts, De
         const double w = (double)ts.wmap[((size_t)d.index * ts.S + sy) * ts.row_f + sx];
         for (int k = 0; k < K; ++k)   // W * intersectWeight + classWeight, UnMicst1-5.py:307-312
             wp[k] = mul_add_f64_rn((double)ts.iw[k], w, (double)ts.cw[k]);
+    }
+}
+
+constexpr int kAugTile = 32;                                         // output tile of one workgroup, in crop orientation
+constexpr int kAugWin = kAugTile + 2 * UMX_AUGMENT_MAX_RADIUS;       // its source window at the largest radius
+constexpr int kAugHStride = kAugTile + 1;                            // (odd: a wave may walk a column of `hor` without bank conflicts)
+
+// float32(sum over t = -R..R, ascending, of w[|t|] * p[t]); p points at t = -R.  The sum starts at 0.0 and every product and every
+// sum is rounded in float64 on its own, as numpy does it tap by tap.
+__device__ inline float blur_taps(const float* p, int stride, int R, const double* w) {
+#pragma clang fp contract(off)
+    double acc = 0.0;
+    for (int t = -R; t <= R; ++t) acc = acc + w[t < 0 ? -t : t] * (double)p[(t + R) * stride];
+    return (float)acc;
+}
+
+// back to the im2double scale, amplified, clipped at 1 (np.minimum: a NaN stays), normalised again; one rounding per operation
+__device__ inline float saturate_f64_rn(float b, double gain, double mean, double std) {
+#pragma clang fp contract(off)
+    const double r = (double)b * std + mean;
+    const double rg = r * gain;
+    const double r2 = rg > 1.0 ? 1.0 : rg;
+    return (float)((r2 - mean) / std);
+}
+
+// one workgroup per (32 x 32 tile of the crop, channel, image).  The (32 + 2R)^2 source window goes to LDS with both coordinates
+// clamped to the sample, so a crop at the sample's edge sees the replicated edge and a crop inside it its real neighbours; the row pass
+// writes `hor` (float32, the rounding the recipe asks for), the column pass reads it.  A wave owns one row of the tile -- or, under a
+// transform that swaps the axes, one column, so that its 32 stores are neighbours in the NHWC output either way.
+__global__ void __launch_bounds__(256) assemble_augmented_kernel(TrainSetView ts, AugChunk ac, int P, float mean, float std,
+                                                                 float* __restrict__ data) {
+    __shared__ float win[kAugWin * kAugWin];
+    __shared__ float hor[kAugWin * kAugHStride];
+    __shared__ double w64[UMX_AUGMENT_MAX_RADIUS + 1];
+    const AugImage& im = ac.im[blockIdx.z];
+    const umx_sample_desc d = im.d;
+    const int c = blockIdx.y;
+    const int tiles = (P + kAugTile - 1) / kAugTile;
+    const int cy0 = (blockIdx.x / tiles) * kAugTile, cx0 = (blockIdx.x % tiles) * kAugTile;
+    const int lane = threadIdx.x & 31, grp = threadIdx.x >> 5;
+    const int R = im.R;
+    const bool swap = (d.transform & 4) != 0;
+    const float* src = ts.planes + (((size_t)d.index * ts.C + c) * ts.pages + d.page) * ((size_t)ts.S * ts.row_f);
+    if (R >= 0) {
+        const int W = kAugTile + 2 * R;
+        for (int r = grp; r < W; r += 8) {
+            const int sy = min(max(d.y0 + cy0 - R + r, 0), ts.S - 1);
+            for (int q = lane; q < W; q += 32) {
+                const int sx = min(max(d.x0 + cx0 - R + q, 0), ts.S - 1);
+                win[r * W + q] = src[(size_t)sy * ts.row_f + sx];
+            }
+        }
+        if ((int)threadIdx.x <= R) w64[threadIdx.x] = (double)im.taps[threadIdx.x];
+        __syncthreads();
+        for (int r = grp; r < W; r += 8) hor[r * kAugHStride + lane] = blur_taps(&win[r * W + lane], 1, R, w64);
+        __syncthreads();
+    }
+    const double gain = (double)im.gain, cont = (double)d.contrast, brig = (double)d.brightness;
+    for (int i = 0; i < kAugTile / 8; ++i) {
+        const int yy = swap ? lane : grp + 8 * i, xx = swap ? grp + 8 * i : lane;   // pixel of the tile, crop orientation
+        const int cy = cy0 + yy, cx = cx0 + xx;
+        if (cy >= P || cx >= P) continue;
+        float v = R >= 0 ? blur_taps(&hor[yy * kAugHStride + xx], kAugHStride, R, w64)
+                         : src[(size_t)(d.y0 + cy) * ts.row_f + d.x0 + cx];
+        if (im.gain != 1.f) v = saturate_f64_rn(v, gain, (double)mean, (double)std);
+        // where assemble_batch_kernel's out[y, x] reads crop[cy, cx]: the inverse of its map
+        const int u = swap ? cx : cy, w = swap ? cy : cx;
+        const int y = (d.transform & 2) ? P - 1 - u : u;
+        const int x = (d.transform & 1) ? P - 1 - w : w;
+        data[(((size_t)im.row * P + y) * P + x) * ts.C + c] = mul_add_f64_rn((double)v, cont, brig);
     }
 }
 
@@ -178,6 +256,17 @@ hipError_t launch_assemble_batch(const TrainSetView& ts, const DescChunk& dc, in
     if (m < 1 || m > kDescChunk || K < 1 || K > 8) return hipErrorInvalidValue;
     hipLaunchKernelGGL(assemble_batch_kernel, dim3((unsigned)((P * P + 255) / 256), (unsigned)m), dim3(256), 0, stream, ts, dc, b0, P, K,
                        data, labels, weights);
+    return hipGetLastError();
+}
+
+hipError_t launch_assemble_augmented(const TrainSetView& ts, const AugChunk& ac, int m, int P, float mean, float std, float* data,
+                                     hipStream_t stream) {
+    if (m < 1 || m > kAugChunk || P < 1) return hipErrorInvalidValue;
+    for (int j = 0; j < m; ++j)
+        if (ac.im[j].R < -1 || ac.im[j].R > UMX_AUGMENT_MAX_RADIUS) return hipErrorInvalidValue;   // (the LDS window is sized for 12)
+    const unsigned tiles = (unsigned)((P + kAugTile - 1) / kAugTile);
+    hipLaunchKernelGGL(assemble_augmented_kernel, dim3(tiles * tiles, (unsigned)ts.C, (unsigned)m), dim3(256), 0, stream, ts, ac, P, mean,
+                       std, data);
     return hipGetLastError();
 }
 
@@ -282,6 +371,85 @@ int enqueue_assemble(umx_trainer* tr, const umx_trainset* ts, const umx_sample_d
     return UMX_OK;
 }
 
+// the parallel array of umx_augment_desc, checked like the descriptors: before anything is enqueued
+int check_augs(umx_trainer* tr, const umx_trainset* ts, const umx_augment_desc* aug, int n, const char* what) {
+    if (!aug) return tsfail(tr, UMX_ERR_INVALID, "null argument");
+    if (!ts->has_aug) return tsfail(tr, UMX_ERR_INVALID, "%s: the training set has no augmentation table (umx_trainset_set_augment)", what);
+    for (int i = 0; i < n; ++i) {
+        const char* why = nullptr;
+        if (aug[i].blur_level < 0 || aug[i].blur_level >= ts->aug.n_levels) why = "blur level outside the table";
+        else if (!std::isfinite(aug[i].gain) || aug[i].gain < 1.f) why = "gain not finite or below 1";
+        if (why)
+            return tsfail(tr, UMX_ERR_INVALID, "%s: augmentation %d (blur level %d of %d, gain %g): %s", what, i, aug[i].blur_level,
+                          ts->aug.n_levels, (double)aug[i].gain, why);
+    }
+    return UMX_OK;
+}
+
+// enqueue_assemble for every image (labels, weights and the plain data: today's path), then the data planes of the images that ask
+// for a blur level or a gain written over it on the same stream.  An image with (level 0, gain 1) is never touched again.
+int enqueue_assemble_augmented(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug, int n,
+                               bool weights) {
+    TS_TRY(enqueue_assemble(tr, ts, desc, n, weights));
+    const TrainerIO io = trainer_io(tr);
+    const TrainSetView v = view_of(ts);
+    AugChunk ac;
+    memset(&ac, 0, sizeof ac);
+    int m = 0;
+    for (int i = 0; i < n; ++i) {
+        if (aug[i].blur_level != 0 || aug[i].gain != 1.f) {
+            AugImage& im = ac.im[m++];
+            im.d = desc[i];
+            im.row = i;
+            im.gain = aug[i].gain;
+            im.R = aug[i].blur_level == 0 ? -1 : ts->aug.radius[aug[i].blur_level];
+            if (im.R >= 0) memcpy(im.taps, ts->aug.taps[aug[i].blur_level], sizeof im.taps);
+        }
+        if (m == kAugChunk || (m > 0 && i == n - 1)) {
+            TS_HIP(tr, launch_assemble_augmented(v, ac, m, io.P, ts->aug.mean, ts->aug.std, io.data, io.stream));
+            memset(&ac, 0, sizeof ac);
+            m = 0;
+        }
+    }
+    return UMX_OK;
+}
+
+// umx_train_step_sampled / _augmented (aug null: the plain step)
+int step_from_set(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug, bool augmented,
+                  int apply_update, const char* what) {
+    if (!tr) return tsfail(nullptr, UMX_ERR_INVALID, "null trainer");
+    const TrainerIO io = trainer_io(tr);
+    TS_TRY(check_descs(tr, ts, desc, io.B, io.B, what));
+    if (augmented) TS_TRY(check_augs(tr, ts, aug, io.B, what));
+    TS_HIP(tr, hipSetDevice(io.device));
+    if (augmented) TS_TRY(enqueue_assemble_augmented(tr, ts, desc, aug, io.B, ts->weighted));
+    else TS_TRY(enqueue_assemble(tr, ts, desc, io.B, ts->weighted));
+    TS_TRY(umx_train_step_dev(tr, io.data, io.labels, ts->weighted ? io.weights : nullptr, apply_update));   // (checks the trainer's zones)
+    std::string msg;
+    const int rc = arena_check(ts->mem, &msg);
+    return rc == UMX_OK ? UMX_OK : tsfail(tr, rc, "%s", msg.c_str());
+}
+
+// umx_trainer_assemble / _augmented
+int assemble_to_host(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug, bool augmented,
+                     int n, float* data, float* labels, float* weights, const char* what) {
+    if (!tr) return tsfail(nullptr, UMX_ERR_INVALID, "null trainer");
+    const TrainerIO io = trainer_io(tr);
+    TS_TRY(check_descs(tr, ts, desc, n, io.B, what));
+    if (augmented) TS_TRY(check_augs(tr, ts, aug, n, what));
+    if (!data || !labels) return tsfail(tr, UMX_ERR_INVALID, "null argument");
+    TS_HIP(tr, hipSetDevice(io.device));
+    if (augmented) TS_TRY(enqueue_assemble_augmented(tr, ts, desc, aug, n, ts->weighted));
+    else TS_TRY(enqueue_assemble(tr, ts, desc, n, ts->weighted));
+    const size_t npx = (size_t)n * io.P * io.P;
+    TS_HIP(tr, hipMemcpyAsync(data, io.data, npx * io.C * sizeof(float), hipMemcpyDeviceToHost, io.stream));
+    TS_HIP(tr, hipMemcpyAsync(labels, io.labels, npx * io.K * sizeof(float), hipMemcpyDeviceToHost, io.stream));
+    if (weights && ts->weighted)
+        TS_HIP(tr, hipMemcpyAsync(weights, io.weights, npx * io.K * sizeof(float), hipMemcpyDeviceToHost, io.stream));
+    TS_HIP(tr, hipStreamSynchronize(io.stream));
+    return guard_check(tr, ts);
+}
+
 }  // namespace
 
 extern "C" {
@@ -372,32 +540,56 @@ void umx_trainset_destroy(umx_trainset* ts) {
 }
 
 int umx_train_step_sampled(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, int apply_update) {
-    if (!tr) return tsfail(nullptr, UMX_ERR_INVALID, "null trainer");
-    const TrainerIO io = trainer_io(tr);
-    TS_TRY(check_descs(tr, ts, desc, io.B, io.B, "umx_train_step_sampled"));
-    TS_HIP(tr, hipSetDevice(io.device));
-    TS_TRY(enqueue_assemble(tr, ts, desc, io.B, ts->weighted));
-    TS_TRY(umx_train_step_dev(tr, io.data, io.labels, ts->weighted ? io.weights : nullptr, apply_update));   // (checks the trainer's zones)
-    std::string msg;
-    const int rc = arena_check(ts->mem, &msg);
-    return rc == UMX_OK ? UMX_OK : tsfail(tr, rc, "%s", msg.c_str());
+    return step_from_set(tr, ts, desc, nullptr, false, apply_update, "umx_train_step_sampled");
+}
+
+int umx_train_step_augmented(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
+                             int apply_update) {
+    return step_from_set(tr, ts, desc, aug, true, apply_update, "umx_train_step_augmented");
 }
 
 int umx_trainer_assemble(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, int n, float* data, float* labels,
                          float* weights) {
-    if (!tr) return tsfail(nullptr, UMX_ERR_INVALID, "null trainer");
+    return assemble_to_host(tr, ts, desc, nullptr, false, n, data, labels, weights, "umx_trainer_assemble");
+}
+
+int umx_trainer_assemble_augmented(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
+                                   int n, float* data, float* labels, float* weights) {
+    return assemble_to_host(tr, ts, desc, aug, true, n, data, labels, weights, "umx_trainer_assemble_augmented");
+}
+
+int umx_augment_table_check(const umx_augment_table* t, char* msg, size_t cap) {
+    char buf[160] = "";
+    if (!t) snprintf(buf, sizeof buf, "null table");
+    else if (t->n_levels < 1 || t->n_levels > UMX_AUGMENT_MAX_LEVELS)
+        snprintf(buf, sizeof buf, "n_levels is %d: a table holds 1..%d levels", t->n_levels, UMX_AUGMENT_MAX_LEVELS);
+    else if (t->radius[0] != 0) snprintf(buf, sizeof buf, "level 0 is 'no blur': its radius must be 0, not %d", t->radius[0]);
+    else if (!std::isfinite(t->mean)) snprintf(buf, sizeof buf, "mean is not finite");
+    else if (!std::isfinite(t->std) || !(t->std > 0.f)) snprintf(buf, sizeof buf, "std must be finite and > 0");
+    for (int l = 0; !buf[0] && l < t->n_levels; ++l) {
+        if (t->radius[l] < 0 || t->radius[l] > UMX_AUGMENT_MAX_RADIUS)
+            snprintf(buf, sizeof buf, "radius of level %d is %d, outside 0..%d", l, t->radius[l], UMX_AUGMENT_MAX_RADIUS);
+        for (int k = 0; !buf[0] && k <= t->radius[l]; ++k)
+            if (!std::isfinite(t->taps[l][k]) || t->taps[l][k] < 0.f)
+                snprintf(buf, sizeof buf, "tap %d of level %d is not finite or negative", k, l);
+    }
+    for (int i = 0; !buf[0] && i < 5; ++i)
+        if (t->reserved[i]) snprintf(buf, sizeof buf, "reserved must be zero");
+    if (msg && cap) snprintf(msg, cap, "%s", buf);
+    return buf[0] ? UMX_ERR_INVALID : UMX_OK;
+}
+
+int umx_trainset_set_augment(umx_trainset* ts, const umx_augment_table* table) {
+    if (!ts) return tsfail(nullptr, UMX_ERR_INVALID, "null training set");
+    umx_trainer* tr = ts->tr;
+    char why[160];
+    if (umx_augment_table_check(table, why, sizeof why) != UMX_OK) return tsfail(tr, UMX_ERR_INVALID, "umx_augment_table: %s", why);
     const TrainerIO io = trainer_io(tr);
-    TS_TRY(check_descs(tr, ts, desc, n, io.B, "umx_trainer_assemble"));
-    if (!data || !labels) return tsfail(tr, UMX_ERR_INVALID, "null argument");
     TS_HIP(tr, hipSetDevice(io.device));
-    TS_TRY(enqueue_assemble(tr, ts, desc, n, ts->weighted));
-    const size_t npx = (size_t)n * io.P * io.P;
-    TS_HIP(tr, hipMemcpyAsync(data, io.data, npx * io.C * sizeof(float), hipMemcpyDeviceToHost, io.stream));
-    TS_HIP(tr, hipMemcpyAsync(labels, io.labels, npx * io.K * sizeof(float), hipMemcpyDeviceToHost, io.stream));
-    if (weights && ts->weighted)
-        TS_HIP(tr, hipMemcpyAsync(weights, io.weights, npx * io.K * sizeof(float), hipMemcpyDeviceToHost, io.stream));
     TS_HIP(tr, hipStreamSynchronize(io.stream));
-    return guard_check(tr, ts);
+    ts->aug = *table;
+    ts->has_aug = true;
+    return UMX_OK;
 }
 
 int umx_trainer_evaluate(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, int n, int64_t* counts, double* loss_sum) {

@@ -2,6 +2,7 @@
 
     python -m unmicst_amd.finetune --model NAME|DIR --train DIR --valid DIR --out DIR [--steps N] [--batch B] [--pages A]
                                    [--eval-every E] [--seed S] [--lr0 LR] [--transforms] [--device D]
+                                   [--blur-sigmas 0.75,1.5,3] [--blur-prob P] [--saturate-prob P] [--max-gain G]
 
 ``--train`` / ``--valid`` hold the reference's published layout (``I%05d_Img.tif`` / ``_Ant.tif`` / ``_wt.tif``, see
 unmicst_amd/trainset.py).  Both sets are uploaded to the device once; each step draws its batch with ``Sampler`` and trains with
@@ -9,6 +10,13 @@ unmicst_amd/trainset.py).  Both sets are uploaded to the device once; each step 
 and jitter).  Every ``--eval-every`` steps the whole validation set is evaluated on the device; the checkpoint with the lowest mean
 per-class pixel error is written to ``<out>/umx_model.npz`` with the base model's normalisation mean / std, so
 ``UnMicst.py --model <out>`` runs on it, and every evaluation is one line of ``<out>/finetune_log.jsonl``.
+
+Computed defocus and saturation, for sets with one in-focus plane per sample (the published sets carry re-imaged defocused and
+saturated planes as extra pages instead): ``--blur-sigmas`` lists the Gaussian blur levels in pixels and ``--blur-prob`` is the chance
+that an image gets one of them; ``--saturate-prob`` is the chance that an image is amplified by a gain drawn from
+``[1, --max-gain)`` on the im2double scale and clipped at 1.  Both are applied on the device while the batch is built
+(``Trainer.step_augmented``); validation stays unaugmented.  When any of the four flags is given, the settings are the first line of
+the log.
 
 The run is a function of its arguments: the same seed gives the same descriptor stream, the same steps and the same files.
 There is no CPU fallback.
@@ -46,7 +54,43 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--lr0", type=float, default=None, help="initial learning rate (default: the graph's trainer)")
     p.add_argument("--transforms", action="store_true", help="draw one of the 8 dihedral transforms per image")
     p.add_argument("--device", type=int, default=0)
+    p.add_argument("--blur-sigmas", default=None, help="blur levels: comma-separated Gaussian sigmas in pixels, each in (0, 4]")
+    p.add_argument("--blur-prob", type=float, default=None, help="chance that an image is blurred (default 0.5 with --blur-sigmas)")
+    p.add_argument("--saturate-prob", type=float, default=None, help="chance that an image is amplified and clipped (default 0)")
+    p.add_argument("--max-gain", type=float, default=None, help="gains are drawn from [1, G) (default 2 with --saturate-prob)")
     return p
+
+
+def augment_settings(args):
+    """The four augmentation flags -> None when none is given, else {"blur_sigmas", "blur_prob", "saturate_prob", "max_gain"}.
+    Raises Refusal."""
+    given = [getattr(args, k, None) for k in ("blur_sigmas", "blur_prob", "saturate_prob", "max_gain")]
+    if all(v is None for v in given):
+        return None
+    sigmas = []
+    if args.blur_sigmas is not None:
+        try:
+            sigmas = [float(v) for v in args.blur_sigmas.split(",")]
+        except ValueError:
+            raise Refusal("--blur-sigmas %r: expected comma-separated numbers" % args.blur_sigmas)
+    if len(sigmas) > trainer.AUGMENT_MAX_LEVELS - 1:
+        raise Refusal("--blur-sigmas: at most %d levels" % (trainer.AUGMENT_MAX_LEVELS - 1))
+    for v in sigmas:
+        try:
+            trainset.gaussian_taps(v)
+        except ValueError as e:
+            raise Refusal("--blur-sigmas: %s" % e)
+    blur_prob = (0.5 if sigmas else 0.0) if args.blur_prob is None else args.blur_prob
+    sat_prob = 0.0 if args.saturate_prob is None else args.saturate_prob
+    max_gain = (2.0 if sat_prob > 0 else 1.0) if args.max_gain is None else args.max_gain
+    for name, v in (("--blur-prob", blur_prob), ("--saturate-prob", sat_prob)):
+        if not 0.0 <= v <= 1.0:   # (a NaN fails both comparisons)
+            raise Refusal("%s %r is not a probability" % (name, v))
+    if blur_prob > 0 and not sigmas:
+        raise Refusal("--blur-prob needs --blur-sigmas")
+    if not (math.isfinite(max_gain) and max_gain >= 1.0):
+        raise Refusal("--max-gain %r: a gain is finite and >= 1" % max_gain)
+    return {"blur_sigmas": sigmas, "blur_prob": float(blur_prob), "saturate_prob": float(sat_prob), "max_gain": float(max_gain)}
 
 
 def resolve_model(name: str) -> str:
@@ -69,6 +113,7 @@ def prepare(args):
     """Everything that needs no device: the model, both sets read and checked.  Raises Refusal."""
     if args.steps < 1 or args.eval_every < 1 or args.pages < 1 or args.batch < 0:
         raise Refusal("--steps, --eval-every and --pages must be positive, --batch non-negative")
+    augment_settings(args)
     path = resolve_model(args.model)
     if not os.path.isdir(path):
         raise Refusal("model %s: no such directory (%s)" % (args.model, path))
@@ -97,6 +142,7 @@ def prepare(args):
 
 def run(args) -> int:
     art, train_ds, valid_ds = prepare(args)
+    aug = augment_settings(args)
     hp = art.hp
     kind = trainset.graph_kind(hp)
     lw = trainset.LABEL_WEIGHTS[kind]
@@ -105,14 +151,21 @@ def run(args) -> int:
         ts = trainset.upload(tr, train_ds, lw)
         vs = trainset.upload(tr, valid_ds, lw)
         mb, mc = trainset.default_jitter(kind, art.std)
+        akw = {}
+        if aug is not None:
+            ts.set_augment(trainset.AugmentTable.from_sigmas(aug["blur_sigmas"], art.mean, art.std))
+            akw = dict(blur_levels=len(aug["blur_sigmas"]) + 1, blur_prob=aug["blur_prob"], saturate_prob=aug["saturate_prob"],
+                       max_gain=aug["max_gain"])
         sampler = trainset.Sampler(args.seed, train_ds.n_samples, tr.batch, train_ds.size, hp.imSize, args.pages, mb, mc,
-                                   transforms=args.transforms)
+                                   transforms=args.transforms, **akw)
         vdesc = trainset.validation_descriptors(valid_ds.n_samples, valid_ds.size, hp.imSize)
         os.makedirs(args.out, exist_ok=True)
         log_path = os.path.join(args.out, LOG_NAME)
         best = None
         train_loss = None
         with open(log_path, "w") as log:
+            if aug is not None:
+                log.write(json.dumps({"augment": aug}) + "\n")
             for step in range(args.steps + 1):
                 if step % args.eval_every == 0 or step == args.steps:
                     ev = tr.evaluate(vs, vdesc)
@@ -129,7 +182,10 @@ def run(args) -> int:
                         model.save_converted(model.ModelArtefacts(hp, tr.blob(), art.mean, art.std), args.out)
                 if step == args.steps:
                     break
-                tr.step_sampled(ts, sampler.next())
+                if aug is None:
+                    tr.step_sampled(ts, sampler.next())
+                else:
+                    tr.step_augmented(ts, *sampler.next_augmented())
                 if (step + 1) % args.eval_every == 0 or step + 1 == args.steps:
                     train_loss = tr.loss()[0]
         print("best mean per-class error %.6g at step %d -> %s" % (best[0], best[1], os.path.join(args.out, model.CONVERTED_NAME)))

@@ -29,7 +29,8 @@ EXPORTS = [
     "umx_trainer_last_error", "umx_train_step", "umx_train_step_dev", "umx_trainer_loss", "umx_trainer_read",
     "umx_trainer_probs", "umx_trainer_read_tensor", "umx_trainer_eval", "umx_trainer_step_count", "umx_trainer_batch", "umx_trainer_flops_per_image",
     "umx_trainer_profile", "umx_trainset_create", "umx_trainset_set", "umx_trainset_destroy", "umx_train_step_sampled",
-    "umx_trainer_assemble", "umx_trainer_evaluate", "umx_guard_scan",
+    "umx_trainer_assemble", "umx_trainer_evaluate", "umx_guard_scan", "umx_augment_table_check", "umx_trainset_set_augment",
+    "umx_train_step_augmented", "umx_trainer_assemble_augmented",
 ]
 
 
@@ -78,6 +79,17 @@ class LabelWeightsC(ctypes.Structure):
 # ``umx_sample_desc`` (include/umx_train.h): one image of a batch drawn from a training set, 32 bytes
 SAMPLE_DESC = np.dtype([("index", "<i4"), ("page", "<i4"), ("y0", "<i4"), ("x0", "<i4"), ("transform", "<i4"),
                         ("brightness", "<f4"), ("contrast", "<f4"), ("reserved", "<i4")])
+
+# ``umx_augment_desc``: the blur level and saturation gain of one image, parallel to its SAMPLE_DESC
+AUGMENT_DESC = np.dtype([("blur_level", "<i4"), ("gain", "<f4")])
+AUGMENT_MAX_LEVELS, AUGMENT_MAX_RADIUS = 16, 12
+
+
+class AugmentTableC(ctypes.Structure):
+    """``umx_augment_table`` (include/umx_train.h)."""
+    _fields_ = [("mean", ctypes.c_float), ("std", ctypes.c_float), ("n_levels", ctypes.c_int32),
+                ("radius", ctypes.c_int32 * AUGMENT_MAX_LEVELS), ("taps", (ctypes.c_float * (AUGMENT_MAX_RADIUS + 1)) * AUGMENT_MAX_LEVELS),
+                ("reserved", ctypes.c_int32 * 5)]
 
 
 def solo_options(**kw) -> TrainOptions:
@@ -162,6 +174,15 @@ def _bind(L):
     L.umx_trainer_assemble.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
     L.umx_trainer_evaluate.restype = c_int
     L.umx_trainer_evaluate.argtypes = [c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(ctypes.c_int64), dp]
+    # computed defocus / saturation (umx_augment_table, umx_augment_desc)
+    L.umx_augment_table_check.restype = c_int
+    L.umx_augment_table_check.argtypes = [ctypes.POINTER(AugmentTableC), ctypes.c_char_p, ctypes.c_size_t]
+    L.umx_trainset_set_augment.restype = c_int
+    L.umx_trainset_set_augment.argtypes = [c_void_p, ctypes.POINTER(AugmentTableC)]
+    L.umx_train_step_augmented.restype = c_int
+    L.umx_train_step_augmented.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int]
+    L.umx_trainer_assemble_augmented.restype = c_int
+    L.umx_trainer_assemble_augmented.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
     # debug guard mode (UMX_DEBUG_GUARD): the host scan of one red zone
     L.umx_guard_scan.restype = c_int
     L.umx_guard_scan.argtypes = [c_void_p, ctypes.c_size_t, c_int, ctypes.c_size_t, c_int, ctypes.c_char_p, ctypes.c_char_p,
@@ -327,6 +348,34 @@ class Trainer:
         weights = np.empty((n, P, P, hp.nClasses), np.float32) if ts.weighted else None
         self._check(self._lib.umx_trainer_assemble(self._h, ts._handle(), d.ctypes.data, n, data.ctypes.data, labels.ctypes.data,
                                                    None if weights is None else weights.ctypes.data))
+        return data, labels, weights
+
+    def _augs(self, aug, n: int):
+        a = np.ascontiguousarray(aug, dtype=AUGMENT_DESC)
+        if a.shape != (n,):
+            raise ValueError("expected %d augmentation descriptors (a 1-d AUGMENT_DESC array), got shape %r" % (n, a.shape))
+        return a
+
+    def step_augmented(self, ts, desc, aug, apply_update: bool = True):
+        """``step_sampled`` with a blur level and a saturation gain per image (``aug``: B AUGMENT_DESC rows; the set needs a table,
+        ``TrainSet.set_augment``).  Only enqueues."""
+        d = self._descs(desc, self.batch)
+        if d.size != self.batch:
+            raise ValueError("step_augmented takes exactly %d descriptors, got %d" % (self.batch, d.size))
+        a = self._augs(aug, d.size)
+        self._check(self._lib.umx_train_step_augmented(self._h, ts._handle(), d.ctypes.data, a.ctypes.data, int(apply_update)))
+
+    def assemble_augmented(self, ts, desc, aug):
+        """``assemble`` with a blur level and a saturation gain per image."""
+        hp = self.hp
+        d = self._descs(desc, self.batch)
+        a = self._augs(aug, d.size)
+        n, P = d.size, hp.imSize
+        data = np.empty((n, P, P, hp.nChannels), np.float32)
+        labels = np.empty((n, P, P, hp.nClasses), np.float32)
+        weights = np.empty((n, P, P, hp.nClasses), np.float32) if ts.weighted else None
+        self._check(self._lib.umx_trainer_assemble_augmented(self._h, ts._handle(), d.ctypes.data, a.ctypes.data, n, data.ctypes.data,
+                                                             labels.ctypes.data, None if weights is None else weights.ctypes.data))
         return data, labels, weights
 
     def evaluate(self, ts, descs) -> dict:

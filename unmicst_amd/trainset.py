@@ -13,6 +13,10 @@ sample ``i`` of a directory:
 (``trainer.SAMPLE_DESC``) of each batch; ``Trainer.step_sampled`` / ``assemble`` / ``evaluate`` build the batch on the device
 (DESIGN.md section 9.2).  The labels and weights follow the reference's recipe: ``labels[k] = (code == k + 1)`` and
 ``weights[k] = intersect_weight[k] * W + class_weight[k]``.
+
+Computed defocus and saturation (the stand-in for the re-imaged pages of the published sets when a user has one in-focus plane
+per sample): ``AugmentTable.from_sigmas`` makes the Gaussian levels, ``TrainSet.set_augment`` attaches them, ``Sampler.next_augmented``
+draws a blur level and a saturation gain per image and ``Trainer.step_augmented`` applies them on the device.
 """
 from __future__ import annotations
 
@@ -25,7 +29,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import imtools, tiffio
-from .trainer import SAMPLE_DESC, LabelWeightsC
+from .trainer import AUGMENT_DESC, AUGMENT_MAX_LEVELS, AUGMENT_MAX_RADIUS, SAMPLE_DESC, AugmentTableC, LabelWeightsC
 
 
 @dataclass(frozen=True)
@@ -65,6 +69,57 @@ def default_jitter(kind: str, std: float) -> Tuple[float, float]:
     if kind == "legacy":
         return 0.0, 0.0
     return 1.0 * float(std), 0.1 * float(std)
+
+
+def gaussian_taps(sigma: float) -> np.ndarray:
+    """The one-sided taps ``w[0..R]`` (float32) of a Gaussian of ``sigma`` pixels, by scipy.ndimage's rule with truncate = 3:
+    ``R = int(3 sigma + 0.5)``, ``exp(-0.5 (t / sigma)^2)`` normalised over ``-R..R`` in float64, then rounded (not renormalised)."""
+    sigma = float(sigma)
+    if not (np.isfinite(sigma) and sigma > 0.0):
+        raise ValueError("a blur sigma must be finite and > 0, got %r" % sigma)
+    R = int(3.0 * sigma + 0.5)
+    if R > AUGMENT_MAX_RADIUS:
+        raise ValueError("sigma %g gives radius %d; the kernel takes radii up to %d (sigma <= 4)" % (sigma, R, AUGMENT_MAX_RADIUS))
+    t = np.arange(-R, R + 1, dtype=np.float64)
+    w = np.exp(-0.5 * (t / sigma) ** 2)
+    w /= w.sum()
+    return w[R:].astype(np.float32)
+
+
+@dataclass(frozen=True)
+class AugmentTable:
+    """``umx_augment_table``: ``taps[l]`` are the one-sided taps of blur level ``l`` (level 0: no blur), ``mean`` / ``std`` the set's
+    normalisation (the saturation ceiling is ``(1 - mean) / std``)."""
+    mean: float
+    std: float
+    taps: Tuple[np.ndarray, ...]
+
+    @classmethod
+    def from_sigmas(cls, sigmas, mean: float, std: float) -> "AugmentTable":
+        """Level 0 = no blur, level ``i + 1`` = a Gaussian of ``sigmas[i]`` pixels."""
+        sigmas = list(sigmas)
+        if len(sigmas) + 1 > AUGMENT_MAX_LEVELS:
+            raise ValueError("a table holds %d blur levels besides 'none', got %d sigmas" % (AUGMENT_MAX_LEVELS - 1, len(sigmas)))
+        if not (np.isfinite(mean) and np.isfinite(std) and std > 0):
+            raise ValueError("mean must be finite and std finite and > 0")
+        return cls(float(mean), float(std), (np.ones(1, np.float32),) + tuple(gaussian_taps(s) for s in sigmas))
+
+    @property
+    def n_levels(self) -> int:
+        return len(self.taps)
+
+    @property
+    def radius(self) -> Tuple[int, ...]:
+        return tuple(len(w) - 1 for w in self.taps)
+
+    def c_struct(self) -> AugmentTableC:
+        t = AugmentTableC()
+        t.mean, t.std, t.n_levels = self.mean, self.std, self.n_levels
+        for l, w in enumerate(self.taps):
+            t.radius[l] = len(w) - 1
+            for k, v in enumerate(w):
+                t.taps[l][k] = float(v)
+        return t
 
 
 class TrainSet:
@@ -114,6 +169,12 @@ class TrainSet:
                 raise ValueError("weight_map must be %r, got %r" % ((S, S), w.shape))
         self.trainer._check(self._lib.umx_trainset_set(self._handle(), int(i), p.ctypes.data, a.ctypes.data,
                                                        None if w is None else w.ctypes.data))
+
+    def set_augment(self, table: AugmentTable) -> None:
+        """Attach (or replace) the blur levels and the normalisation that ``Trainer.step_augmented`` / ``assemble_augmented`` use."""
+        c = table.c_struct()
+        self.trainer._check(self._lib.umx_trainset_set_augment(self._handle(), ctypes.byref(c)))
+        self.augment = table
 
     @classmethod
     def from_arrays(cls, trainer, planes, annotations, weight_maps=None, label_weights: LabelWeights = UNWEIGHTED) -> "TrainSet":
@@ -227,12 +288,26 @@ class Sampler:
     """Descriptor stream of a training run: every sample once per epoch in an order reshuffled each epoch, then per image a
     uniform augmentation page, a uniform crop origin, optionally one of the 8 dihedral transforms, and the reference's jitter
     (``brightness = max_brightness * (+-1) * U[0,1)``, ``contrast = 1 + max_contrast * (+-1) * U[0,1)``, UnMicst1-5.py:473-474).
-    All draws come from ``numpy.random.Generator(PCG64(seed))`` in a fixed order, so a seed fixes the stream."""
+    All draws come from ``numpy.random.Generator(PCG64(seed))`` in a fixed order, so a seed fixes the stream.
+
+    Blur and saturation (off by default; then nothing extra is drawn): with ``blur_prob`` an image gets a blur level uniform over
+    ``1..blur_levels - 1`` (``blur_levels`` = the levels of the set's table, level 0 included), with ``saturate_prob`` a gain
+    ``1 + (max_gain - 1) U[0,1)``.  When either probability is positive, four draws follow every image's contrast draw -- blur coin,
+    level, saturation coin, gain -- whatever the coins say, so one image's outcome never shifts the next one's draws."""
 
     def __init__(self, seed: int, n_samples: int, batch: int, size: int, P: int, n_pages: int, max_brightness: float = 0.0,
-                 max_contrast: float = 0.0, transforms: bool = False):
+                 max_contrast: float = 0.0, transforms: bool = False, blur_levels: int = 1, blur_prob: float = 0.0,
+                 saturate_prob: float = 0.0, max_gain: float = 1.0):
         if n_samples < 1 or batch < 1 or n_pages < 1 or size < P:
             raise ValueError("a sampler needs samples, a batch, pages and size >= P")
+        if not (0.0 <= blur_prob <= 1.0 and 0.0 <= saturate_prob <= 1.0):
+            raise ValueError("blur_prob and saturate_prob are probabilities")
+        if not 1 <= blur_levels <= AUGMENT_MAX_LEVELS or (blur_prob > 0 and blur_levels < 2):
+            raise ValueError("blur_levels counts the table's levels (1..%d); blurring needs one besides level 0" % AUGMENT_MAX_LEVELS)
+        if not (np.isfinite(max_gain) and max_gain >= 1.0):
+            raise ValueError("max_gain must be finite and >= 1")
+        self.blur_levels, self.blur_prob = int(blur_levels), float(blur_prob)
+        self.saturate_prob, self.max_gain = float(saturate_prob), float(max_gain)
         self.rng = np.random.Generator(np.random.PCG64(seed))
         self.n_samples, self.batch, self.size, self.P, self.n_pages = int(n_samples), int(batch), int(size), int(P), int(n_pages)
         self.max_brightness, self.max_contrast = float(max_brightness), float(max_contrast)
@@ -250,9 +325,19 @@ class Sampler:
         self._pos += 1
         return i
 
+    @property
+    def augmenting(self) -> bool:
+        return self.blur_prob > 0.0 or self.saturate_prob > 0.0
+
     def next(self) -> np.ndarray:
         """The next batch: ``batch`` descriptors (a SAMPLE_DESC array)."""
+        return self.next_augmented()[0]
+
+    def next_augmented(self) -> Tuple[np.ndarray, np.ndarray]:
+        """The next batch: ``batch`` descriptors and their blur level / gain (a SAMPLE_DESC and an AUGMENT_DESC array)."""
         d = np.zeros(self.batch, SAMPLE_DESC)
+        a = np.zeros(self.batch, AUGMENT_DESC)
+        a["gain"] = 1.0
         r = self.rng
         span = self.size - self.P + 1
         for j in range(self.batch):
@@ -265,7 +350,14 @@ class Sampler:
             d["brightness"][j] = self.max_brightness * sb * r.random() + 0.0   # (+ 0.0: no -0.0 when there is no jitter)
             sc = -1.0 if r.random() < 0.5 else 1.0
             d["contrast"][j] = 1.0 + self.max_contrast * sc * r.random()
-        return d
+            if self.augmenting:
+                blur = r.random() < self.blur_prob
+                level = 1 + int(r.integers(max(self.blur_levels - 1, 1)))
+                sat = r.random() < self.saturate_prob
+                gain = 1.0 + (self.max_gain - 1.0) * r.random()
+                a["blur_level"][j] = level if blur else 0
+                a["gain"][j] = gain if sat else 1.0
+        return d, a
 
     def __iter__(self):
         while True:
@@ -311,4 +403,4 @@ def graph_kind(hp) -> str:
 
 
 __all__ = ["LabelWeights", "UNWEIGHTED", "LABEL_WEIGHTS", "default_jitter", "TrainSet", "Dataset", "dataset_indices",
-           "read_dataset_dir", "Sampler", "crop_origins", "validation_descriptors", "upload", "graph_kind", "SAMPLE_DESC"]
+           "read_dataset_dir", "Sampler", "gaussian_taps", "AugmentTable", "AUGMENT_DESC", "crop_origins", "validation_descriptors", "upload", "graph_kind", "SAMPLE_DESC"]
