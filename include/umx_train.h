@@ -189,11 +189,43 @@ UMX_API int umx_train_step_augmented(umx_trainer* tr, const umx_trainset* ts, co
 UMX_API int umx_trainer_assemble_augmented(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc,
                                            const umx_augment_desc* aug, int n, float* data, float* labels, float* weights);
 
+/* ---- rotation and zoom ("Rotation and zoom") ----
+ * Per image of a batch, next to its umx_sample_desc (and its umx_augment_desc, when there is one): a 2 x 2 matrix, made on the host
+ * in float64 and rounded to float32, M = (1 / zoom) * [[cos t, -sin t], [sin t, cos t]] (zoom > 1 magnifies).  m == {1, 0, 0, 1}
+ * exactly is "no warp": such an image is assembled exactly as the entries above assemble it, blur's edge rule included.
+ * Order per image and channel: page plane -> warp -> blur -> saturation -> crop orientation + dihedral transform -> jitter.  The warp
+ * gives the image on the crop's own pixel grid, at every integer (y, x), also outside 0 .. P-1: the blur's halo reads those, so under
+ * a warp the blur has no edge rule of its own.  With P = imSize, S = size, c = (P - 1) / 2, in float64, every product, sum, division
+ * and floor one rounding (no fma):
+ *   1. sy = (m[0] * (y - c) + m[1] * (x - c)) + (y0 + c);  sx = (m[2] * (y - c) + m[3] * (x - c)) + (x0 + c).
+ *   2. mirror about the centres of the sample's edge pixels (d c b | a b c d | c b a), per axis: T = 2 (S - 1), q = floor(s / T),
+ *      t = s - T * q, t = T - t where t > S - 1, and t = 0 where t < 0 (s / T may round up to an integer; t is then a hair below 0).
+ *   3. data: i = floor(t), f = t - i, i1 = min(i + 1, S - 1) per axis; top = (1 - fx) * p[iy][ix] + fx * p[iy][ix1], bot likewise on
+ *      row iy1, v = float32((1 - fy) * top + fy * bot).
+ *   4. labels and the weight map: the nearest source pixel, n = min(floor(t + 0.5), S - 1) per axis, the same pixel for both; then
+ *      labels[k] = (code == k+1) and weights[k] = intersect_weight[k] * wmap + class_weight[k] as in umx_label_weights.  Never
+ *      interpolated, never blurred; mirrored pixels keep their (mirrored) labels. */
+typedef struct umx_warp_desc {        /* 16 bytes: one image of a batch */
+    float m[4];                       /* source step per output step: (sy, sx) = M (y - c, x - c) + centre of the crop */
+} umx_warp_desc;
+
+/* Host validation of n descriptors (no device needed): every entry finite and |m[i]| <= 4, determinant != 0.  UMX_OK, or
+ * UMX_ERR_INVALID with the first broken one in msg (cap bytes, NUL-terminated; msg may be NULL). */
+UMX_API int umx_warp_desc_check(const umx_warp_desc* warp, int n, char* msg, size_t cap);
+/* umx_train_step_augmented / umx_trainer_assemble_augmented with a parallel array of umx_warp_desc (B resp. n of them).  aug == NULL:
+ * no blur and gain 1 for every image, and then the set needs no table.  Everything is checked on the host before anything is
+ * enqueued: UMX_ERR_INVALID for what those entries refuse, for what umx_warp_desc_check refuses, and for a set of 1-pixel samples. */
+UMX_API int umx_train_step_warped(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
+                                  const umx_warp_desc* warp, int apply_update);
+UMX_API int umx_trainer_assemble_warped(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc,
+                                        const umx_augment_desc* aug, const umx_warp_desc* warp, int n, float* data, float* labels,
+                                        float* weights);
+
 /* Debug guard mode.  UMX_DEBUG_GUARD=<byte> (e.g. 0xff), read by umx_trainer_create and umx_trainset_create, gives every device
  * buffer of that trainer / set a red zone of max(64 KiB, its size rounded up to 4 KiB) on both sides.  The zones, and every buffer
  * the library does not zero or upload, are filled with that byte, so a result that depends on the byte read memory nobody wrote.
- * Every entry that enqueues work (umx_train_step, _step_dev, _step_sampled, _step_augmented, umx_trainer_eval, _assemble,
- * _assemble_augmented, _evaluate, umx_trainset_set) then waits for the trainer's streams and checks every zone: UMX_ERR_GUARD names the buffer, the side and the
+ * Every entry that enqueues work (umx_train_step, _step_dev, _step_sampled, _step_augmented, _step_warped, umx_trainer_eval, _assemble,
+ * _assemble_augmented, _assemble_warped, _evaluate, umx_trainset_set) then waits for the trainer's streams and checks every zone: UMX_ERR_GUARD names the buffer, the side and the
  * first and last changed byte.  Slow; for tests.  Off (unset or empty), allocations and launches are exactly the normal ones.
  *
  * The host scan of one zone (no device needed): zone_bytes bytes that should all equal `fill`, in front of (side 0) or behind

@@ -3,7 +3,8 @@
 in one process, alternating the two, on the same descriptor stream.  Every step reads its loss (one synchronisation per step on
 both paths).  A third leg, "augmented", is Trainer.step_augmented with every image at the largest blur level of the sigmas
 0.75, 1.5, 3 and gain 2 -- the worst case of the computed defocus / saturation -- alternated with the other two in the same process,
-so that step_sampled of the same run is its yardstick.  Then the validation pass (Trainer.evaluate) over the whole set.  One JSON
+so that step_sampled of the same run is its yardstick.  A fourth leg, "warped", is Trainer.step_warped with the same blur and gain and
+every image rotated by 30 degrees at zoom 1.25, alternated in the same way.  Then the validation pass (Trainer.evaluate) over the whole set.  One JSON
 line per (shape, path, repeat).
 
     python tools/bench_trainset.py [--steps 30] [--warmup 5] [--repeats 3] [--shapes nucleiDAPI,v2-256]
@@ -80,6 +81,8 @@ def main():
         ts.set_augment(trainset.AugmentTable.from_sigmas((0.75, 1.5, 3.0), 0.3, 0.2))
         worst = np.zeros(B, trainer.AUGMENT_DESC)
         worst["blur_level"], worst["gain"] = 3, 2.0
+        turned = np.zeros(B, trainer.WARP_DESC)
+        turned["m"] = trainset.warp_matrix(30.0, 1.25)
         sampler = trainset.Sampler(1, a.samples, B, S, P, pages, mb, mc, transforms=True)
         per_step = B * P * P * (hp.nChannels + (2 if lw.weighted else 1) * hp.nClasses) * 4
 
@@ -97,6 +100,13 @@ def main():
                 tr.loss()
             return time.perf_counter() - t0
 
+        def run_warped(n):
+            t0 = time.perf_counter()
+            for _ in range(n):
+                tr.step_warped(ts, sampler.next(), worst, turned)
+                tr.loss()
+            return time.perf_counter() - t0
+
         def run_host(n):
             t0 = time.perf_counter()
             for _ in range(n):
@@ -105,9 +115,11 @@ def main():
 
         run_sampled(a.warmup)
         run_augmented(a.warmup)
+        run_warped(a.warmup)
         run_host(a.warmup)
         for r in range(a.repeats):
-            for path, fn in (("step_sampled", run_sampled), ("augmented", run_augmented), ("host_fed", run_host)):
+            for path, fn in (("step_sampled", run_sampled), ("augmented", run_augmented), ("warped", run_warped),
+                             ("host_fed", run_host)):
                 dt = fn(a.steps)
                 print(json.dumps({"shape": name, "batch": B, "path": path, "repeat": r, "steps": a.steps, "seconds": round(dt, 5),
                                   "images_per_s": round(a.steps * B / dt, 1), "step_ms": round(1e3 * dt / a.steps, 4),

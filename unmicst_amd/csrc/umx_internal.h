@@ -380,17 +380,22 @@ struct TrainSetView {                  // device layout of one training set
 hipError_t launch_assemble_batch(const TrainSetView& ts, const DescChunk& dc, int m, int b0, int P, int K, float* data, float* labels,
                                  float* weights, hipStream_t stream);
 // the data planes of the images that ask for blur or saturation (umx_augment_desc), written over what launch_assemble_batch wrote
-constexpr int kAugChunk = 16;          // such images per launch (passed by value: 1.5 KiB of kernel arguments)
+constexpr int kAugChunk = 16;          // such images per launch (passed by value: 1.75 KiB of kernel arguments)
 struct AugImage {
     umx_sample_desc d;
     int row;                           // image of the batch
     int R;                             // blur radius; -1: no blur (level 0)
     float gain;
     float taps[UMX_AUGMENT_MAX_RADIUS + 1];
+    float m[4];                        // umx_warp_desc (read by the warped launches only)
 };
 struct AugChunk { AugImage im[kAugChunk]; };
 hipError_t launch_assemble_augmented(const TrainSetView& ts, const AugChunk& ac, int m, int P, float mean, float std, float* data,
                                      hipStream_t stream);
+// the same for images with a rotation / zoom (umx_warp_desc, never the identity): the data planes resampled, then blur, saturation,
+// transform and jitter as above, and their labels / weights (null: none) from the nearest source pixel.  Needs ts.S >= 2.
+hipError_t launch_assemble_warped(const TrainSetView& ts, const AugChunk& ac, int m, int P, int K, float mean, float std, float* data,
+                                  float* labels, float* weights, hipStream_t stream);
 // counts [2K] int64 (correct | labelled) and loss [1] double over npix pixels of probs / labels [npix, K]; part: class_counts_parts(npix)
 // doubles of workspace
 size_t class_counts_parts(size_t npix, int K);

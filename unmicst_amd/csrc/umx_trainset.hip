@@ -1,6 +1,6 @@
 // libumx device-resident training set: storage, the two kernels that feed the training step from it, and the C ABI of the
-// umx_trainset_* / umx_train_step_sampled / _augmented / umx_trainer_assemble / _augmented / umx_trainer_evaluate entries of
-// include/umx_train.h.
+// umx_trainset_* / umx_train_step_sampled / _augmented / _warped / umx_trainer_assemble / _augmented / _warped /
+// umx_trainer_evaluate entries of include/umx_train.h.
 //
 // The set is the reference's annotated layout (I%05d_Img.tif pages, _Ant.tif class codes, _wt.tif contour-intersection map;
 // UnMicst1-5.py:295-312, UnMicst2.py:293-309, UnMicst.py:236-243) uploaded once, already normalised.  A step then costs 32 bytes
@@ -11,6 +11,9 @@
 //                          labels[b,y,x,k] = (code == k+1); weights[b,y,x,k] = float32((double)iw[k] * wmap + cw[k])
 //   assemble_augmented_kernel  the data planes of the images that ask for a blur level or a saturation gain (umx_augment_desc):
 //                          page plane -> separable Gaussian blur -> saturation -> crop + transform -> jitter, float64 in a fixed order
+//   assemble_augmented_kernel<true>  the same for the images with a rotation / zoom (umx_warp_desc): the window is resampled
+//                          (mirror fold, bilinear, float64 in a fixed order) instead of copied
+//   assemble_warped_labels_kernel  their labels and weights, from the nearest source pixel
 //   class_counts_kernel    per block: correct / labelled per class (int64) and sum of -log p[label] (float64), fixed order;
 //   class_counts_final     one block sums the block partials in a fixed order
 #include "../../include/umx_train.h"
@@ -31,6 +34,8 @@ static_assert(sizeof(DescChunk) <= 2048, "a descriptor chunk travels as kernel a
 static_assert(sizeof(umx_augment_desc) == 8, "umx_augment_desc is 8 bytes");
 static_assert(sizeof(umx_augment_table) == 12 + 16 * 4 + 16 * 13 * 4 + 5 * 4, "umx_augment_table layout");
 static_assert(sizeof(AugChunk) <= 2048, "a chunk of augmented images travels as kernel arguments");
+static_assert(sizeof(umx_warp_desc) == 16, "umx_warp_desc is 16 bytes");
+static_assert(sizeof(AugImage) == 112, "an augmented image is 112 bytes of kernel arguments");
 
 struct umx_trainset {
     umx_trainer* tr = nullptr;
@@ -128,10 +133,54 @@ __device__ inline float saturate_f64_rn(float b, double gain, double mean, doubl
     return (float)((r2 - mean) / std);
 }
 
+// a source coordinate mirrored into 0 .. S-1 about the centres of the sample's edge pixels (d c b | a b c d | c b a), S >= 2.  A
+// quotient that rounds up to the next integer leaves t a hair below 0: that is the edge pixel.
+__device__ inline double warp_fold(double s, int S) {
+#pragma clang fp contract(off)
+    const double T = 2.0 * (double)(S - 1);
+    const double q = floor(s / T);
+    double t = s - T * q;
+    if (t > (double)(S - 1)) t = T - t;
+    return t < 0.0 ? 0.0 : t;
+}
+
+// where pixel (y, x) of the crop's own grid (any integer, also outside 0 .. P-1) lies in the sample: M (y - c, x - c) + the crop's
+// centre, folded.  Every product and every sum is rounded in float64 on its own.
+__device__ inline void warp_source(const float* m, int y, int x, int P, int y0, int x0, int S, double* ty, double* tx) {
+#pragma clang fp contract(off)
+    const double c = 0.5 * (double)(P - 1);
+    const double dy = (double)y - c, dx = (double)x - c;
+    *ty = warp_fold(((double)m[0] * dy + (double)m[1] * dx) + ((double)y0 + c), S);
+    *tx = warp_fold(((double)m[2] * dy + (double)m[3] * dx) + ((double)x0 + c), S);
+}
+
+// bilinear value of a sample plane at a folded coordinate: along the row first, then between the two rows, one float32 rounding
+__device__ inline float warp_bilinear(const float* plane, int row_f, int S, double ty, double tx) {
+#pragma clang fp contract(off)
+    const int iy = min(max((int)ty, 0), S - 1), ix = min(max((int)tx, 0), S - 1);   // (0 <= t <= S-1: truncation is floor; the clamp is for a NaN)
+    const double fy = ty - (double)iy, fx = tx - (double)ix;
+    const int iy1 = min(iy + 1, S - 1), ix1 = min(ix + 1, S - 1);
+    const float* r0 = plane + (size_t)iy * row_f;
+    const float* r1 = plane + (size_t)iy1 * row_f;
+    const double gx = 1.0 - fx;
+    const double top = gx * (double)r0[ix] + fx * (double)r0[ix1];
+    const double bot = gx * (double)r1[ix] + fx * (double)r1[ix1];
+    return (float)((1.0 - fy) * top + fy * bot);
+}
+
+// the nearest source pixel of a folded coordinate (labels and weight maps are never interpolated)
+__device__ inline int warp_nearest(double t, int S) {
+#pragma clang fp contract(off)
+    return min(max((int)(t + 0.5), 0), S - 1);
+}
+
 // one workgroup per (32 x 32 tile of the crop, channel, image).  The (32 + 2R)^2 source window goes to LDS with both coordinates
 // clamped to the sample, so a crop at the sample's edge sees the replicated edge and a crop inside it its real neighbours; the row pass
 // writes `hor` (float32, the rounding the recipe asks for), the column pass reads it.  A wave owns one row of the tile -- or, under a
 // transform that swaps the axes, one column, so that its 32 stores are neighbours in the NHWC output either way.
+// kWarp: every window element is resampled from the plane instead (im.m: rotation and zoom about the crop's centre).  The warped
+// image exists at every integer coordinate, so the window needs no clamp; without a blur each thread resamples its own pixel.
+template <bool kWarp>
 __global__ void __launch_bounds__(256) assemble_augmented_kernel(TrainSetView ts, AugChunk ac, int P, float mean, float std,
                                                                  float* __restrict__ data) {
     __shared__ float win[kAugWin * kAugWin];
@@ -149,10 +198,16 @@ __global__ void __launch_bounds__(256) assemble_augmented_kernel(TrainSetView ts
     if (R >= 0) {
         const int W = kAugTile + 2 * R;
         for (int r = grp; r < W; r += 8) {
-            const int sy = min(max(d.y0 + cy0 - R + r, 0), ts.S - 1);
             for (int q = lane; q < W; q += 32) {
-                const int sx = min(max(d.x0 + cx0 - R + q, 0), ts.S - 1);
-                win[r * W + q] = src[(size_t)sy * ts.row_f + sx];
+                if constexpr (kWarp) {
+                    double ty, tx;
+                    warp_source(im.m, cy0 - R + r, cx0 - R + q, P, d.y0, d.x0, ts.S, &ty, &tx);
+                    win[r * W + q] = warp_bilinear(src, ts.row_f, ts.S, ty, tx);
+                } else {
+                    const int sy = min(max(d.y0 + cy0 - R + r, 0), ts.S - 1);
+                    const int sx = min(max(d.x0 + cx0 - R + q, 0), ts.S - 1);
+                    win[r * W + q] = src[(size_t)sy * ts.row_f + sx];
+                }
             }
         }
         if ((int)threadIdx.x <= R) w64[threadIdx.x] = (double)im.taps[threadIdx.x];
@@ -165,14 +220,46 @@ __global__ void __launch_bounds__(256) assemble_augmented_kernel(TrainSetView ts
         const int yy = swap ? lane : grp + 8 * i, xx = swap ? grp + 8 * i : lane;   // pixel of the tile, crop orientation
         const int cy = cy0 + yy, cx = cx0 + xx;
         if (cy >= P || cx >= P) continue;
-        float v = R >= 0 ? blur_taps(&hor[yy * kAugHStride + xx], kAugHStride, R, w64)
-                         : src[(size_t)(d.y0 + cy) * ts.row_f + d.x0 + cx];
+        float v;
+        if (R >= 0) {
+            v = blur_taps(&hor[yy * kAugHStride + xx], kAugHStride, R, w64);
+        } else if constexpr (kWarp) {
+            double ty, tx;
+            warp_source(im.m, cy, cx, P, d.y0, d.x0, ts.S, &ty, &tx);
+            v = warp_bilinear(src, ts.row_f, ts.S, ty, tx);
+        } else {
+            v = src[(size_t)(d.y0 + cy) * ts.row_f + d.x0 + cx];
+        }
         if (im.gain != 1.f) v = saturate_f64_rn(v, gain, (double)mean, (double)std);
         // where assemble_batch_kernel's out[y, x] reads crop[cy, cx]: the inverse of its map
         const int u = swap ? cx : cy, w = swap ? cy : cx;
         const int y = (d.transform & 2) ? P - 1 - u : u;
         const int x = (d.transform & 1) ? P - 1 - w : w;
         data[(((size_t)im.row * P + y) * P + x) * ts.C + c] = mul_add_f64_rn((double)v, cont, brig);
+    }
+}
+
+// labels and weights of the warped images, written over what assemble_batch_kernel wrote: one thread per output pixel, its K values
+// each, as there.  The pixel's place in the crop is that kernel's map; its label and its weight come from the one source pixel
+// nearest to the warped coordinate.
+__global__ void __launch_bounds__(256) assemble_warped_labels_kernel(TrainSetView ts, AugChunk ac, int P, int K,
+                                                                     float* __restrict__ labels, float* __restrict__ weights) {
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= P * P) return;
+    const AugImage& im = ac.im[blockIdx.y];
+    const umx_sample_desc d = im.d;
+    const int y = pix / P, x = pix - (pix / P) * P;
+    const int u = (d.transform & 2) ? P - 1 - y : y;
+    const int v = (d.transform & 1) ? P - 1 - x : x;
+    double ty, tx;
+    warp_source(im.m, (d.transform & 4) ? v : u, (d.transform & 4) ? u : v, P, d.y0, d.x0, ts.S, &ty, &tx);
+    const int sy = warp_nearest(ty, ts.S), sx = warp_nearest(tx, ts.S);
+    const size_t o = ((size_t)im.row * P * P + pix) * K;
+    const int code = ts.ann[((size_t)d.index * ts.S + sy) * ts.row_a + sx];
+    for (int k = 0; k < K; ++k) labels[o + k] = code == k + 1 ? 1.f : 0.f;
+    if (weights) {
+        const double w = (double)ts.wmap[((size_t)d.index * ts.S + sy) * ts.row_f + sx];
+        for (int k = 0; k < K; ++k) weights[o + k] = mul_add_f64_rn((double)ts.iw[k], w, (double)ts.cw[k]);
     }
 }
 
@@ -265,8 +352,21 @@ hipError_t launch_assemble_augmented(const TrainSetView& ts, const AugChunk& ac,
     for (int j = 0; j < m; ++j)
         if (ac.im[j].R < -1 || ac.im[j].R > UMX_AUGMENT_MAX_RADIUS) return hipErrorInvalidValue;   // (the LDS window is sized for 12)
     const unsigned tiles = (unsigned)((P + kAugTile - 1) / kAugTile);
-    hipLaunchKernelGGL(assemble_augmented_kernel, dim3(tiles * tiles, (unsigned)ts.C, (unsigned)m), dim3(256), 0, stream, ts, ac, P, mean,
-                       std, data);
+    hipLaunchKernelGGL(assemble_augmented_kernel<false>, dim3(tiles * tiles, (unsigned)ts.C, (unsigned)m), dim3(256), 0, stream, ts, ac, P,
+                       mean, std, data);
+    return hipGetLastError();
+}
+
+hipError_t launch_assemble_warped(const TrainSetView& ts, const AugChunk& ac, int m, int P, int K, float mean, float std, float* data,
+                                  float* labels, float* weights, hipStream_t stream) {
+    if (m < 1 || m > kAugChunk || P < 1 || K < 1 || K > 8 || ts.S < 2) return hipErrorInvalidValue;   // (S = 1 has no mirror period)
+    for (int j = 0; j < m; ++j)
+        if (ac.im[j].R < -1 || ac.im[j].R > UMX_AUGMENT_MAX_RADIUS) return hipErrorInvalidValue;
+    const unsigned tiles = (unsigned)((P + kAugTile - 1) / kAugTile);
+    hipLaunchKernelGGL(assemble_augmented_kernel<true>, dim3(tiles * tiles, (unsigned)ts.C, (unsigned)m), dim3(256), 0, stream, ts, ac, P,
+                       mean, std, data);
+    hipLaunchKernelGGL(assemble_warped_labels_kernel, dim3((unsigned)((P * P + 255) / 256), (unsigned)m), dim3(256), 0, stream, ts, ac, P, K,
+                       labels, weights);
     return hipGetLastError();
 }
 
@@ -371,6 +471,9 @@ int enqueue_assemble(umx_trainer* tr, const umx_trainset* ts, const umx_sample_d
     return UMX_OK;
 }
 
+// which entry a batch came in by: plain descriptors, + umx_augment_desc, + umx_warp_desc (there aug may be null: no blur, gain 1)
+enum Entry { kSampled, kAugmented, kWarped };
+
 // the parallel array of umx_augment_desc, checked like the descriptors: before anything is enqueued
 int check_augs(umx_trainer* tr, const umx_trainset* ts, const umx_augment_desc* aug, int n, const char* what) {
     if (!aug) return tsfail(tr, UMX_ERR_INVALID, "null argument");
@@ -386,61 +489,87 @@ int check_augs(umx_trainer* tr, const umx_trainset* ts, const umx_augment_desc* 
     return UMX_OK;
 }
 
-// enqueue_assemble for every image (labels, weights and the plain data: today's path), then the data planes of the images that ask
-// for a blur level or a gain written over it on the same stream.  An image with (level 0, gain 1) is never touched again.
-int enqueue_assemble_augmented(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug, int n,
-                               bool weights) {
+bool warp_is_identity(const umx_warp_desc& w) { return w.m[0] == 1.f && w.m[1] == 0.f && w.m[2] == 0.f && w.m[3] == 1.f; }
+
+// the parallel array of umx_warp_desc, likewise
+int check_warps(umx_trainer* tr, const umx_trainset* ts, const umx_warp_desc* warp, int n, const char* what) {
+    if (!warp) return tsfail(tr, UMX_ERR_INVALID, "null argument");
+    if (ts->S < 2) return tsfail(tr, UMX_ERR_INVALID, "%s: a sample of one pixel cannot be warped", what);
+    char why[160];
+    if (umx_warp_desc_check(warp, n, why, sizeof why) != UMX_OK) return tsfail(tr, UMX_ERR_INVALID, "%s: %s", what, why);
+    return UMX_OK;
+}
+
+// the checks of an entry, in the order descriptors, augmentations, warps; nothing is enqueued before all of them pass
+int check_batch(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug, const umx_warp_desc* warp,
+                Entry entry, int n, int n_max, const char* what) {
+    TS_TRY(check_descs(tr, ts, desc, n, n_max, what));
+    if (entry == kAugmented || (entry == kWarped && aug)) TS_TRY(check_augs(tr, ts, aug, n, what));
+    if (entry == kWarped) TS_TRY(check_warps(tr, ts, warp, n, what));
+    return UMX_OK;
+}
+
+// enqueue_assemble for every image (labels, weights and the plain data: today's path), then, on the same stream, the images that ask
+// for more written over it, 16 per launch: the data planes of those with a blur level or a gain (aug, may be null), and data, labels
+// and weights of those with a warp other than the identity (warp, may be null).  An image with (level 0, gain 1, identity) is never
+// touched again, and one with the identity never meets the warp code.
+int enqueue_batch(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
+                  const umx_warp_desc* warp, int n, bool weights) {
     TS_TRY(enqueue_assemble(tr, ts, desc, n, weights));
+    if (!aug && !warp) return UMX_OK;
     const TrainerIO io = trainer_io(tr);
     const TrainSetView v = view_of(ts);
-    AugChunk ac;
-    memset(&ac, 0, sizeof ac);
-    int m = 0;
+    const float mean = ts->has_aug ? ts->aug.mean : 0.f, std = ts->has_aug ? ts->aug.std : 1.f;   // (read only when a gain != 1)
+    AugChunk chunk[2];   // [0] blur / gain only, [1] warped
+    int m[2] = {0, 0};
+    memset(chunk, 0, sizeof chunk);
     for (int i = 0; i < n; ++i) {
-        if (aug[i].blur_level != 0 || aug[i].gain != 1.f) {
-            AugImage& im = ac.im[m++];
+        const bool warped = warp && !warp_is_identity(warp[i]);
+        if (warped || (aug && (aug[i].blur_level != 0 || aug[i].gain != 1.f))) {
+            AugImage& im = chunk[warped].im[m[warped]++];
             im.d = desc[i];
             im.row = i;
-            im.gain = aug[i].gain;
-            im.R = aug[i].blur_level == 0 ? -1 : ts->aug.radius[aug[i].blur_level];
+            im.gain = aug ? aug[i].gain : 1.f;
+            im.R = !aug || aug[i].blur_level == 0 ? -1 : ts->aug.radius[aug[i].blur_level];
             if (im.R >= 0) memcpy(im.taps, ts->aug.taps[aug[i].blur_level], sizeof im.taps);
+            if (warped) memcpy(im.m, warp[i].m, sizeof im.m);
         }
-        if (m == kAugChunk || (m > 0 && i == n - 1)) {
-            TS_HIP(tr, launch_assemble_augmented(v, ac, m, io.P, ts->aug.mean, ts->aug.std, io.data, io.stream));
-            memset(&ac, 0, sizeof ac);
-            m = 0;
-        }
+        for (int k = 0; k < 2; ++k)
+            if (m[k] == kAugChunk || (m[k] > 0 && i == n - 1)) {
+                if (k == 0) TS_HIP(tr, launch_assemble_augmented(v, chunk[0], m[0], io.P, mean, std, io.data, io.stream));
+                else
+                    TS_HIP(tr, launch_assemble_warped(v, chunk[1], m[1], io.P, io.K, mean, std, io.data, io.labels,
+                                                      weights ? io.weights : nullptr, io.stream));
+                memset(&chunk[k], 0, sizeof chunk[k]);
+                m[k] = 0;
+            }
     }
     return UMX_OK;
 }
 
-// umx_train_step_sampled / _augmented (aug null: the plain step)
-int step_from_set(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug, bool augmented,
-                  int apply_update, const char* what) {
+// umx_train_step_sampled / _augmented / _warped
+int step_from_set(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
+                  const umx_warp_desc* warp, Entry entry, int apply_update, const char* what) {
     if (!tr) return tsfail(nullptr, UMX_ERR_INVALID, "null trainer");
     const TrainerIO io = trainer_io(tr);
-    TS_TRY(check_descs(tr, ts, desc, io.B, io.B, what));
-    if (augmented) TS_TRY(check_augs(tr, ts, aug, io.B, what));
+    TS_TRY(check_batch(tr, ts, desc, aug, warp, entry, io.B, io.B, what));
     TS_HIP(tr, hipSetDevice(io.device));
-    if (augmented) TS_TRY(enqueue_assemble_augmented(tr, ts, desc, aug, io.B, ts->weighted));
-    else TS_TRY(enqueue_assemble(tr, ts, desc, io.B, ts->weighted));
+    TS_TRY(enqueue_batch(tr, ts, desc, aug, warp, io.B, ts->weighted));
     TS_TRY(umx_train_step_dev(tr, io.data, io.labels, ts->weighted ? io.weights : nullptr, apply_update));   // (checks the trainer's zones)
     std::string msg;
     const int rc = arena_check(ts->mem, &msg);
     return rc == UMX_OK ? UMX_OK : tsfail(tr, rc, "%s", msg.c_str());
 }
 
-// umx_trainer_assemble / _augmented
-int assemble_to_host(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug, bool augmented,
-                     int n, float* data, float* labels, float* weights, const char* what) {
+// umx_trainer_assemble / _augmented / _warped
+int assemble_to_host(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
+                     const umx_warp_desc* warp, Entry entry, int n, float* data, float* labels, float* weights, const char* what) {
     if (!tr) return tsfail(nullptr, UMX_ERR_INVALID, "null trainer");
     const TrainerIO io = trainer_io(tr);
-    TS_TRY(check_descs(tr, ts, desc, n, io.B, what));
-    if (augmented) TS_TRY(check_augs(tr, ts, aug, n, what));
+    TS_TRY(check_batch(tr, ts, desc, aug, warp, entry, n, io.B, what));
     if (!data || !labels) return tsfail(tr, UMX_ERR_INVALID, "null argument");
     TS_HIP(tr, hipSetDevice(io.device));
-    if (augmented) TS_TRY(enqueue_assemble_augmented(tr, ts, desc, aug, n, ts->weighted));
-    else TS_TRY(enqueue_assemble(tr, ts, desc, n, ts->weighted));
+    TS_TRY(enqueue_batch(tr, ts, desc, aug, warp, n, ts->weighted));
     const size_t npx = (size_t)n * io.P * io.P;
     TS_HIP(tr, hipMemcpyAsync(data, io.data, npx * io.C * sizeof(float), hipMemcpyDeviceToHost, io.stream));
     TS_HIP(tr, hipMemcpyAsync(labels, io.labels, npx * io.K * sizeof(float), hipMemcpyDeviceToHost, io.stream));
@@ -540,22 +669,49 @@ void umx_trainset_destroy(umx_trainset* ts) {
 }
 
 int umx_train_step_sampled(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, int apply_update) {
-    return step_from_set(tr, ts, desc, nullptr, false, apply_update, "umx_train_step_sampled");
+    return step_from_set(tr, ts, desc, nullptr, nullptr, kSampled, apply_update, "umx_train_step_sampled");
 }
 
 int umx_train_step_augmented(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
                              int apply_update) {
-    return step_from_set(tr, ts, desc, aug, true, apply_update, "umx_train_step_augmented");
+    return step_from_set(tr, ts, desc, aug, nullptr, kAugmented, apply_update, "umx_train_step_augmented");
+}
+
+int umx_train_step_warped(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
+                          const umx_warp_desc* warp, int apply_update) {
+    return step_from_set(tr, ts, desc, aug, warp, kWarped, apply_update, "umx_train_step_warped");
 }
 
 int umx_trainer_assemble(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, int n, float* data, float* labels,
                          float* weights) {
-    return assemble_to_host(tr, ts, desc, nullptr, false, n, data, labels, weights, "umx_trainer_assemble");
+    return assemble_to_host(tr, ts, desc, nullptr, nullptr, kSampled, n, data, labels, weights, "umx_trainer_assemble");
 }
 
 int umx_trainer_assemble_augmented(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
                                    int n, float* data, float* labels, float* weights) {
-    return assemble_to_host(tr, ts, desc, aug, true, n, data, labels, weights, "umx_trainer_assemble_augmented");
+    return assemble_to_host(tr, ts, desc, aug, nullptr, kAugmented, n, data, labels, weights, "umx_trainer_assemble_augmented");
+}
+
+int umx_trainer_assemble_warped(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
+                                const umx_warp_desc* warp, int n, float* data, float* labels, float* weights) {
+    return assemble_to_host(tr, ts, desc, aug, warp, kWarped, n, data, labels, weights, "umx_trainer_assemble_warped");
+}
+
+int umx_warp_desc_check(const umx_warp_desc* warp, int n, char* msg, size_t cap) {
+    char buf[160] = "";
+    if (!warp) snprintf(buf, sizeof buf, "null warp descriptors");
+    for (int i = 0; !buf[0] && i < n; ++i) {
+        const float* m = warp[i].m;
+        const char* why = nullptr;
+        for (int k = 0; k < 4 && !why; ++k)
+            if (!std::isfinite(m[k])) why = "an entry is not finite";
+            else if (std::fabs(m[k]) > 4.f) why = "an entry is above 4 in magnitude";
+        if (!why && (double)m[0] * (double)m[3] - (double)m[1] * (double)m[2] == 0.0) why = "the matrix is singular";
+        if (why)
+            snprintf(buf, sizeof buf, "warp %d (%g, %g, %g, %g): %s", i, (double)m[0], (double)m[1], (double)m[2], (double)m[3], why);
+    }
+    if (msg && cap) snprintf(msg, cap, "%s", buf);
+    return buf[0] ? UMX_ERR_INVALID : UMX_OK;
 }
 
 int umx_augment_table_check(const umx_augment_table* t, char* msg, size_t cap) {

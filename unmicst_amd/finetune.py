@@ -3,6 +3,7 @@
     python -m unmicst_amd.finetune --model NAME|DIR --train DIR --valid DIR --out DIR [--steps N] [--batch B] [--pages A]
                                    [--eval-every E] [--seed S] [--lr0 LR] [--transforms] [--device D]
                                    [--blur-sigmas 0.75,1.5,3] [--blur-prob P] [--saturate-prob P] [--max-gain G]
+                                   [--rotate-prob P] [--zoom-prob P] [--zoom-range LO,HI]
 
 ``--train`` / ``--valid`` hold the reference's published layout (``I%05d_Img.tif`` / ``_Ant.tif`` / ``_wt.tif``, see
 unmicst_amd/trainset.py).  Both sets are uploaded to the device once; each step draws its batch with ``Sampler`` and trains with
@@ -17,6 +18,13 @@ that an image gets one of them; ``--saturate-prob`` is the chance that an image 
 ``[1, --max-gain)`` on the im2double scale and clipped at 1.  Both are applied on the device while the batch is built
 (``Trainer.step_augmented``); validation stays unaugmented.  When any of the four flags is given, the settings are the first line of
 the log.
+
+Rotation and zoom, the geometry a small set of ``imSize``-wide samples cannot get from crops and the 8 dihedral transforms:
+``--rotate-prob`` is the chance that an image is rotated about its crop's centre by an angle uniform over the full turn,
+``--zoom-prob`` (0.5 when ``--zoom-range`` is given) the chance that it is magnified by a factor drawn log-uniformly from
+``--zoom-range LO,HI`` (``0.5 <= LO <= 1 <= HI <= 2``).  Data is resampled bilinearly and mirrored at the sample's edges; labels and
+weight maps take the nearest source pixel (``Trainer.step_warped``).  Validation stays unwarped.  When one of the three flags is given,
+the log's first line carries the settings as its ``"warp"`` object (next to ``"augment"`` when both are on).
 
 The run is a function of its arguments: the same seed gives the same descriptor stream, the same steps and the same files.
 There is no CPU fallback.
@@ -58,7 +66,35 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--blur-prob", type=float, default=None, help="chance that an image is blurred (default 0.5 with --blur-sigmas)")
     p.add_argument("--saturate-prob", type=float, default=None, help="chance that an image is amplified and clipped (default 0)")
     p.add_argument("--max-gain", type=float, default=None, help="gains are drawn from [1, G) (default 2 with --saturate-prob)")
+    p.add_argument("--rotate-prob", type=float, default=None, help="chance that an image is rotated by a uniform angle (default 0)")
+    p.add_argument("--zoom-prob", type=float, default=None, help="chance that an image is magnified (default 0.5 with --zoom-range)")
+    p.add_argument("--zoom-range", default=None, help="LO,HI: magnifications are drawn log-uniformly, 0.5 <= LO <= 1 <= HI <= 2")
     return p
+
+
+def warp_settings(args):
+    """The three warp flags -> None when none is given, else {"rotate_prob", "zoom_prob", "zoom_range"}.  Raises Refusal."""
+    given = [getattr(args, k, None) for k in ("rotate_prob", "zoom_prob", "zoom_range")]
+    if all(v is None for v in given):
+        return None
+    zr = None
+    if args.zoom_range is not None:
+        try:
+            zr = [float(v) for v in args.zoom_range.split(",")]
+        except ValueError:
+            zr = []
+        if len(zr) != 2:
+            raise Refusal("--zoom-range %r: expected LO,HI" % args.zoom_range)
+        if not 0.5 <= zr[0] <= 1.0 <= zr[1] <= 2.0:   # (a NaN fails the chain)
+            raise Refusal("--zoom-range %r: 0.5 <= LO <= 1 <= HI <= 2" % args.zoom_range)
+    rot_prob = 0.0 if args.rotate_prob is None else args.rotate_prob
+    zoom_prob = (0.5 if zr else 0.0) if args.zoom_prob is None else args.zoom_prob
+    for name, v in (("--rotate-prob", rot_prob), ("--zoom-prob", zoom_prob)):
+        if not 0.0 <= v <= 1.0:
+            raise Refusal("%s %r is not a probability" % (name, v))
+    if zoom_prob > 0 and zr is None:
+        raise Refusal("--zoom-prob needs --zoom-range")
+    return {"rotate_prob": float(rot_prob), "zoom_prob": float(zoom_prob), "zoom_range": zr or [1.0, 1.0]}
 
 
 def augment_settings(args):
@@ -114,6 +150,7 @@ def prepare(args):
     if args.steps < 1 or args.eval_every < 1 or args.pages < 1 or args.batch < 0:
         raise Refusal("--steps, --eval-every and --pages must be positive, --batch non-negative")
     augment_settings(args)
+    warp_settings(args)
     path = resolve_model(args.model)
     if not os.path.isdir(path):
         raise Refusal("model %s: no such directory (%s)" % (args.model, path))
@@ -143,6 +180,7 @@ def prepare(args):
 def run(args) -> int:
     art, train_ds, valid_ds = prepare(args)
     aug = augment_settings(args)
+    warp = warp_settings(args)
     hp = art.hp
     kind = trainset.graph_kind(hp)
     lw = trainset.LABEL_WEIGHTS[kind]
@@ -156,6 +194,8 @@ def run(args) -> int:
             ts.set_augment(trainset.AugmentTable.from_sigmas(aug["blur_sigmas"], art.mean, art.std))
             akw = dict(blur_levels=len(aug["blur_sigmas"]) + 1, blur_prob=aug["blur_prob"], saturate_prob=aug["saturate_prob"],
                        max_gain=aug["max_gain"])
+        if warp is not None:
+            akw.update(rotate_prob=warp["rotate_prob"], zoom_prob=warp["zoom_prob"], zoom_range=tuple(warp["zoom_range"]))
         sampler = trainset.Sampler(args.seed, train_ds.n_samples, tr.batch, train_ds.size, hp.imSize, args.pages, mb, mc,
                                    transforms=args.transforms, **akw)
         vdesc = trainset.validation_descriptors(valid_ds.n_samples, valid_ds.size, hp.imSize)
@@ -164,8 +204,9 @@ def run(args) -> int:
         best = None
         train_loss = None
         with open(log_path, "w") as log:
-            if aug is not None:
-                log.write(json.dumps({"augment": aug}) + "\n")
+            settings = {k: v for k, v in (("augment", aug), ("warp", warp)) if v is not None}
+            if settings:
+                log.write(json.dumps(settings) + "\n")
             for step in range(args.steps + 1):
                 if step % args.eval_every == 0 or step == args.steps:
                     ev = tr.evaluate(vs, vdesc)
@@ -182,7 +223,10 @@ def run(args) -> int:
                         model.save_converted(model.ModelArtefacts(hp, tr.blob(), art.mean, art.std), args.out)
                 if step == args.steps:
                     break
-                if aug is None:
+                if warp is not None:
+                    d, a, w = sampler.next_warped()
+                    tr.step_warped(ts, d, None if aug is None else a, w)
+                elif aug is None:
                     tr.step_sampled(ts, sampler.next())
                 else:
                     tr.step_augmented(ts, *sampler.next_augmented())

@@ -30,7 +30,8 @@ EXPORTS = [
     "umx_trainer_probs", "umx_trainer_read_tensor", "umx_trainer_eval", "umx_trainer_step_count", "umx_trainer_batch", "umx_trainer_flops_per_image",
     "umx_trainer_profile", "umx_trainset_create", "umx_trainset_set", "umx_trainset_destroy", "umx_train_step_sampled",
     "umx_trainer_assemble", "umx_trainer_evaluate", "umx_guard_scan", "umx_augment_table_check", "umx_trainset_set_augment",
-    "umx_train_step_augmented", "umx_trainer_assemble_augmented",
+    "umx_train_step_augmented", "umx_trainer_assemble_augmented", "umx_warp_desc_check", "umx_train_step_warped",
+    "umx_trainer_assemble_warped",
 ]
 
 
@@ -83,6 +84,9 @@ SAMPLE_DESC = np.dtype([("index", "<i4"), ("page", "<i4"), ("y0", "<i4"), ("x0",
 # ``umx_augment_desc``: the blur level and saturation gain of one image, parallel to its SAMPLE_DESC
 AUGMENT_DESC = np.dtype([("blur_level", "<i4"), ("gain", "<f4")])
 AUGMENT_MAX_LEVELS, AUGMENT_MAX_RADIUS = 16, 12
+
+# ``umx_warp_desc``: rotation and zoom of one image, parallel to its SAMPLE_DESC; (sy, sx) = M (y - c, x - c) + the crop's centre
+WARP_DESC = np.dtype([("m", "<f4", (4,))])
 
 
 class AugmentTableC(ctypes.Structure):
@@ -183,6 +187,13 @@ def _bind(L):
     L.umx_train_step_augmented.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int]
     L.umx_trainer_assemble_augmented.restype = c_int
     L.umx_trainer_assemble_augmented.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
+    # rotation and zoom (umx_warp_desc)
+    L.umx_warp_desc_check.restype = c_int
+    L.umx_warp_desc_check.argtypes = [c_void_p, c_int, ctypes.c_char_p, ctypes.c_size_t]
+    L.umx_train_step_warped.restype = c_int
+    L.umx_train_step_warped.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]
+    L.umx_trainer_assemble_warped.restype = c_int
+    L.umx_trainer_assemble_warped.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
     # debug guard mode (UMX_DEBUG_GUARD): the host scan of one red zone
     L.umx_guard_scan.restype = c_int
     L.umx_guard_scan.argtypes = [c_void_p, ctypes.c_size_t, c_int, ctypes.c_size_t, c_int, ctypes.c_char_p, ctypes.c_char_p,
@@ -376,6 +387,38 @@ class Trainer:
         weights = np.empty((n, P, P, hp.nClasses), np.float32) if ts.weighted else None
         self._check(self._lib.umx_trainer_assemble_augmented(self._h, ts._handle(), d.ctypes.data, a.ctypes.data, n, data.ctypes.data,
                                                              labels.ctypes.data, None if weights is None else weights.ctypes.data))
+        return data, labels, weights
+
+    def _warps(self, warp, n: int):
+        w = np.ascontiguousarray(warp, dtype=WARP_DESC)
+        if w.shape != (n,):
+            raise ValueError("expected %d warp descriptors (a 1-d WARP_DESC array), got shape %r" % (n, w.shape))
+        return w
+
+    def step_warped(self, ts, desc, aug, warp, apply_update: bool = True):
+        """``step_augmented`` with a rotation / zoom matrix per image (``warp``: B WARP_DESC rows, ``trainset.warp_matrix``).  ``aug``
+        None: no blur and gain 1 for every image, and the set needs no table.  Only enqueues."""
+        d = self._descs(desc, self.batch)
+        if d.size != self.batch:
+            raise ValueError("step_warped takes exactly %d descriptors, got %d" % (self.batch, d.size))
+        a = None if aug is None else self._augs(aug, d.size)
+        w = self._warps(warp, d.size)
+        self._check(self._lib.umx_train_step_warped(self._h, ts._handle(), d.ctypes.data, None if a is None else a.ctypes.data,
+                                                    w.ctypes.data, int(apply_update)))
+
+    def assemble_warped(self, ts, desc, aug, warp):
+        """``assemble_augmented`` with a rotation / zoom matrix per image; ``aug`` may be None."""
+        hp = self.hp
+        d = self._descs(desc, self.batch)
+        a = None if aug is None else self._augs(aug, d.size)
+        w = self._warps(warp, d.size)
+        n, P = d.size, hp.imSize
+        data = np.empty((n, P, P, hp.nChannels), np.float32)
+        labels = np.empty((n, P, P, hp.nClasses), np.float32)
+        weights = np.empty((n, P, P, hp.nClasses), np.float32) if ts.weighted else None
+        self._check(self._lib.umx_trainer_assemble_warped(self._h, ts._handle(), d.ctypes.data, None if a is None else a.ctypes.data,
+                                                          w.ctypes.data, n, data.ctypes.data, labels.ctypes.data,
+                                                          None if weights is None else weights.ctypes.data))
         return data, labels, weights
 
     def evaluate(self, ts, descs) -> dict:

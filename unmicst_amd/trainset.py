@@ -17,6 +17,9 @@ sample ``i`` of a directory:
 Computed defocus and saturation (the stand-in for the re-imaged pages of the published sets when a user has one in-focus plane
 per sample): ``AugmentTable.from_sigmas`` makes the Gaussian levels, ``TrainSet.set_augment`` attaches them, ``Sampler.next_augmented``
 draws a blur level and a saturation gain per image and ``Trainer.step_augmented`` applies them on the device.
+
+Rotation and zoom: ``warp_matrix`` makes the 2 x 2 matrix of an angle and a magnification, ``Sampler.next_warped`` draws one per
+image (``rotate_prob``, ``zoom_prob``, ``zoom_range``) and ``Trainer.step_warped`` resamples data, labels and weights on the device.
 """
 from __future__ import annotations
 
@@ -29,7 +32,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import imtools, tiffio
-from .trainer import AUGMENT_DESC, AUGMENT_MAX_LEVELS, AUGMENT_MAX_RADIUS, SAMPLE_DESC, AugmentTableC, LabelWeightsC
+from .trainer import AUGMENT_DESC, AUGMENT_MAX_LEVELS, AUGMENT_MAX_RADIUS, SAMPLE_DESC, WARP_DESC, AugmentTableC, LabelWeightsC
 
 
 @dataclass(frozen=True)
@@ -84,6 +87,17 @@ def gaussian_taps(sigma: float) -> np.ndarray:
     w = np.exp(-0.5 * (t / sigma) ** 2)
     w /= w.sum()
     return w[R:].astype(np.float32)
+
+
+def warp_matrix(angle_deg: float, zoom: float) -> np.ndarray:
+    """``umx_warp_desc.m``: ``(1 / zoom) * [[cos t, -sin t], [sin t, cos t]]`` in float64, rounded to float32 -- the source step per
+    output step, so ``zoom > 1`` magnifies.  An angle of 0 at zoom 1 is the exact identity ("no warp")."""
+    angle_deg, zoom = float(angle_deg), float(zoom)
+    if not (np.isfinite(angle_deg) and np.isfinite(zoom) and zoom > 0.0):
+        raise ValueError("a warp needs a finite angle and a finite zoom > 0, got %r, %r" % (angle_deg, zoom))
+    t = np.deg2rad(np.float64(angle_deg))
+    c, s = np.cos(t) / zoom, np.sin(t) / zoom
+    return (np.array([c, -s, s, c], np.float64) + 0.0).astype(np.float32)   # (+ 0.0: no -0.0)
 
 
 @dataclass(frozen=True)
@@ -293,11 +307,17 @@ class Sampler:
     Blur and saturation (off by default; then nothing extra is drawn): with ``blur_prob`` an image gets a blur level uniform over
     ``1..blur_levels - 1`` (``blur_levels`` = the levels of the set's table, level 0 included), with ``saturate_prob`` a gain
     ``1 + (max_gain - 1) U[0,1)``.  When either probability is positive, four draws follow every image's contrast draw -- blur coin,
-    level, saturation coin, gain -- whatever the coins say, so one image's outcome never shifts the next one's draws."""
+    level, saturation coin, gain -- whatever the coins say, so one image's outcome never shifts the next one's draws.
+
+    Rotation and zoom (off by default; then nothing extra is drawn): with ``rotate_prob`` an image is rotated by ``360 U[0,1)`` degrees,
+    with ``zoom_prob`` magnified by ``lo (hi / lo)^U[0,1)``, ``(lo, hi) = zoom_range`` (log-uniform).  When either probability is
+    positive, four more draws follow the image's previous ones (after the gain draw when blur / saturation are on, else after the
+    contrast draw) -- rotation coin, angle, zoom coin, zoom -- again whatever the coins say."""
 
     def __init__(self, seed: int, n_samples: int, batch: int, size: int, P: int, n_pages: int, max_brightness: float = 0.0,
                  max_contrast: float = 0.0, transforms: bool = False, blur_levels: int = 1, blur_prob: float = 0.0,
-                 saturate_prob: float = 0.0, max_gain: float = 1.0):
+                 saturate_prob: float = 0.0, max_gain: float = 1.0, rotate_prob: float = 0.0, zoom_prob: float = 0.0,
+                 zoom_range: Tuple[float, float] = (1.0, 1.0)):
         if n_samples < 1 or batch < 1 or n_pages < 1 or size < P:
             raise ValueError("a sampler needs samples, a batch, pages and size >= P")
         if not (0.0 <= blur_prob <= 1.0 and 0.0 <= saturate_prob <= 1.0):
@@ -306,6 +326,12 @@ class Sampler:
             raise ValueError("blur_levels counts the table's levels (1..%d); blurring needs one besides level 0" % AUGMENT_MAX_LEVELS)
         if not (np.isfinite(max_gain) and max_gain >= 1.0):
             raise ValueError("max_gain must be finite and >= 1")
+        if not (0.0 <= rotate_prob <= 1.0 and 0.0 <= zoom_prob <= 1.0):
+            raise ValueError("rotate_prob and zoom_prob are probabilities")
+        lo, hi = (float(v) for v in zoom_range)
+        if not 0.5 <= lo <= 1.0 <= hi <= 2.0:   # (no anti-aliased minification: the floor of 0.5)
+            raise ValueError("zoom_range must satisfy 0.5 <= lo <= 1 <= hi <= 2, got %r" % ((lo, hi),))
+        self.rotate_prob, self.zoom_prob, self.zoom_range = float(rotate_prob), float(zoom_prob), (lo, hi)
         self.blur_levels, self.blur_prob = int(blur_levels), float(blur_prob)
         self.saturate_prob, self.max_gain = float(saturate_prob), float(max_gain)
         self.rng = np.random.Generator(np.random.PCG64(seed))
@@ -329,15 +355,27 @@ class Sampler:
     def augmenting(self) -> bool:
         return self.blur_prob > 0.0 or self.saturate_prob > 0.0
 
+    @property
+    def warping(self) -> bool:
+        return self.rotate_prob > 0.0 or self.zoom_prob > 0.0
+
     def next(self) -> np.ndarray:
         """The next batch: ``batch`` descriptors (a SAMPLE_DESC array)."""
-        return self.next_augmented()[0]
+        return self.next_warped()[0]
 
     def next_augmented(self) -> Tuple[np.ndarray, np.ndarray]:
         """The next batch: ``batch`` descriptors and their blur level / gain (a SAMPLE_DESC and an AUGMENT_DESC array)."""
+        return self.next_warped()[:2]
+
+    def next_warped(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The next batch: ``batch`` descriptors, their blur level / gain and their rotation / zoom matrix (a SAMPLE_DESC, an
+        AUGMENT_DESC and a WARP_DESC array)."""
         d = np.zeros(self.batch, SAMPLE_DESC)
         a = np.zeros(self.batch, AUGMENT_DESC)
         a["gain"] = 1.0
+        w = np.zeros(self.batch, WARP_DESC)
+        w["m"] = (1.0, 0.0, 0.0, 1.0)
+        lo, hi = self.zoom_range
         r = self.rng
         span = self.size - self.P + 1
         for j in range(self.batch):
@@ -357,7 +395,13 @@ class Sampler:
                 gain = 1.0 + (self.max_gain - 1.0) * r.random()
                 a["blur_level"][j] = level if blur else 0
                 a["gain"][j] = gain if sat else 1.0
-        return d, a
+            if self.warping:
+                rot = r.random() < self.rotate_prob
+                angle = 360.0 * r.random()
+                zoomed = r.random() < self.zoom_prob
+                zoom = lo * (hi / lo) ** r.random()
+                w["m"][j] = warp_matrix(angle if rot else 0.0, zoom if zoomed else 1.0)
+        return d, a, w
 
     def __iter__(self):
         while True:
@@ -403,4 +447,4 @@ def graph_kind(hp) -> str:
 
 
 __all__ = ["LabelWeights", "UNWEIGHTED", "LABEL_WEIGHTS", "default_jitter", "TrainSet", "Dataset", "dataset_indices",
-           "read_dataset_dir", "Sampler", "gaussian_taps", "AugmentTable", "AUGMENT_DESC", "crop_origins", "validation_descriptors", "upload", "graph_kind", "SAMPLE_DESC"]
+           "read_dataset_dir", "Sampler", "gaussian_taps", "AugmentTable", "AUGMENT_DESC", "warp_matrix", "WARP_DESC", "crop_origins", "validation_descriptors", "upload", "graph_kind", "SAMPLE_DESC"]
