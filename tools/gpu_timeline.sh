@@ -1,10 +1,12 @@
 # usage: bash tools/gpu_timeline.sh <outdir-name> [bench args]: kernel + memory-copy timeline of the default (host-path) bench;
 # prints the busy / idle split of the GPU's kernel activity over the last step and the largest gaps.
-cd $GRAFT_REPO_ROOT
+cd "$(dirname "$0")/.."
+. tools/gpu_step.sh
 export TMPDIR=/tmp
 O=gpurun_out/$1; shift; mkdir -p $O
+exec 3>&2; trap 's=$?; [ $s -eq 0 ] || echo "gpu_timeline: stopped with status $s (log: $O/bench.log)" >&3' EXIT   # (fd 3: step's own message follows the caller's redirection into the log)
 D=/tmp/umx_tl; rm -rf $D; mkdir -p $D
-rocprofv3 --kernel-trace --memory-copy-trace -d $D -o run -- python3 bench.py --steps 3 --warmup 1 --cpu-seconds 0 "$@" > $O/bench.log 2>&1
+step 600 rocprofv3 --kernel-trace --memory-copy-trace -d $D -o run -- python3 bench.py --steps 3 --warmup 1 --cpu-seconds 0 "$@" > $O/bench.log 2>&1
 python3 - "$D/run_results.db" > $O/timeline.txt <<'PY'
 import sqlite3, sys
 c = sqlite3.connect(sys.argv[1])

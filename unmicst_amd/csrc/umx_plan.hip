@@ -46,7 +46,7 @@ int mx_pack_e2m3(const double (&v)[32], double amax, unsigned char (&out)[24]) {
 namespace {
 
 struct Form {   // conv_f16x3's form of a launch
-    bool fused = false, f6 = false, w2 = false;
+    bool fused = false, f6 = false;
     int nt16 = 1, Np16 = 16;   // N-tiles per workgroup, padded N
     int nlists = 1;            // independent stage lists (= kernel phases)
 };
@@ -109,27 +109,14 @@ Form choose_form(const Launch& L, const PlanInputs& in, int want_nt16, HConvPara
     // ... and, of those, the plain convolutions of >= 2 N-blocks on tiles of one image (>= 16 x 16 pixels): the per-phase transposed
     // convolutions (1 - 4 taps: a handful of stages per workgroup) and the 8 x 8-pixel layers (four images per tile: a 400-pixel halo,
     // chunks of one octet in the two-tile workgroup's LDS) measured 15 - 22 % SLOWER in the form, the single-N-block layers at 1/4
-    // resolution level (+0.3 ... +3 %), the long-K convolutions of 2 - 4 N-blocks 5 - 13 % faster (docs/experiments.md); UMX_F6_ALL=1
-    // takes every eligible layer (the A/B)
-    const bool f6_all = getenv("UMX_F6_ALL") && atoi(getenv("UMX_F6_ALL")) == 1;
+    // resolution level (+0.3 ... +3 %), the long-K convolutions of 2 - 4 N-blocks 5 - 13 % faster (docs/experiments.md).
+    // The form runs two tiles per eight-wave workgroup; for the 3-product kernel alone that shape measured 4 % SLOWER (docs/experiments.md,
+    // round 6: two independent four-wave workgroups per CU de-phase and cover each other's stage waits; one eight-wave workgroup runs its
+    // waves in lock-step), so nothing else takes it
     const bool f6 = in.f6 && !fused && !L.d2s && !L.train && !in.out_f32 && nt16 == kMaxNT16 && !h.pk && L.H * 4 <= in.imSize &&
-                    (f6_all || (L.nphase == 1 && g.imgs == 1 && h.nblocks >= 2)) && !getenv("UMX_DEBUG_STAMPS");
+                    L.nphase == 1 && g.imgs == 1 && h.nblocks >= 2 && !getenv("UMX_DEBUG_STAMPS");
     F.f6 = f6;
     h.f6 = f6 ? 1 : 0;
-    // two tiles per eight-wave workgroup (conv_f16x3's W2 form): the F6 form runs on it.  For the 3-product kernel alone it measured 4 %
-    // SLOWER (docs/experiments.md, round 6: two independent four-wave workgroups per CU de-phase and cover each other's stage waits; one
-    // eight-wave workgroup runs its waves in lock-step) -- UMX_W2=1 selects it there for that A/B
-    F.w2 = f6 || (getenv("UMX_W2") && atoi(getenv("UMX_W2")) == 1 && !fused && !L.d2s && !L.train && !in.out_f32 && nt16 == kMaxNT16 &&
-                  !h.pk && !getenv("UMX_DEBUG_STAMPS"));
-    h.w2 = F.w2 ? 1 : 0;
-    if (f6)
-        if (const char* e = getenv("UMX_F6_ABLATE"))
-            if (atoi(e) & 3) {   // timing-only ablations of docs/experiments.md (conv_f16x3, f6step): WRONG RESULTS, said so once per process
-                static std::atomic<bool> told{false};
-                if (!told.exchange(true))
-                    fprintf(stderr, "[umx] UMX_F6_ABLATE=%s: parts of the fp6 cross-term stage are switched off -- timing only, the results are WRONG\n", e);
-                h.f6 |= (atoi(e) & 3) << 1;
-            }
     h.outH = L.outH; h.outW = L.outW; h.pool = L.pool; h.act = L.act;
     return F;
 }
@@ -155,7 +142,7 @@ std::vector<Chunk> chunks_for(const Launch& L, int OC, int ph /* -1: every group
 // slots over one pair of weight buffers, and has its CU's whole LDS)
 int wbuf_of(const Form& F, int ss) { return 64 + F.nt16 * (F.f6 ? 4096 : ss * 2048); }
 int lds_total(const Form& F, int nslots, int oc, int ss, int plane_pair_bytes) {
-    return (F.w2 ? 2 : 1) * nslots * oc * plane_pair_bytes + 2 * wbuf_of(F, ss);
+    return (F.f6 ? 2 : 1) * nslots * oc * plane_pair_bytes + 2 * wbuf_of(F, ss);
 }
 // the kernel keeps one pixel index per (wave, piece of a chunk) in registers
 bool pieces_fit(const HConvParams& h, int OC, int maxp) { return ((h.nhalo + 64 / OC - 1) / (64 / OC) + kWaves - 1) / kWaves <= maxp; }
@@ -270,7 +257,7 @@ bool search(const Launch& L, const Form& F, HConvParams& h, Choice* out, std::st
     double bestCost = 1e30;
     for (size_t at = 0; at < attempts.size() && !best.OC; ++at) {
     best.maxp = attempts[at].maxp;
-    const int lds_cap = F.w2 ? 160 * 1024 - 512 : attempts[at].cap;
+    const int lds_cap = F.f6 ? 160 * 1024 - 512 : attempts[at].cap;
     for (int OC = 1; OC <= 9; ++OC) {
         int nslots = 1;
         double sectors = 0;   // 64-byte memory requests of the halo loads of one workgroup
@@ -341,8 +328,8 @@ int narrower_nt16(const Launch& L, const PlanInputs& in) {
         HConvParams h;
         const Form F = choose_form(L, in, c, h);
         Choice ch;
-        std::string w2;
-        if (F.fused || F.nt16 != c || !search(L, F, h, &ch, &w2)) continue;   // (F.nt16 != c: c does not keep the padded width)
+        std::string warn;
+        if (F.fused || F.nt16 != c || !search(L, F, h, &ch, &warn)) continue;   // (F.nt16 != c: c does not keep the padded width)
         int k = 0;
         for (int list = 0; list < F.nlists; ++list) k += plan_list(L, F, ch.OC, ch.S, list, nullptr, nullptr, nullptr);
         if (!base_nt) { base_nt = c; base_k = k; best_nt = c; best_k = k; }   // the default choice comes first
@@ -383,7 +370,7 @@ void build_stages(const Launch& L, const Form& F, const Choice& ch, HConvParams&
     h.b_off = 2 * h.lo_off;
     h.wbuf_bytes = wbuf_of(F, S);
     h.xcd_order = 1;   // XCD-aware tile order (run_launch_f16 turns it into order 2 where its rule says so)
-    h.lds_bytes = (F.w2 ? 2 : 1) * h.b_off + 2 * h.wbuf_bytes;
+    h.lds_bytes = (F.f6 ? 2 : 1) * h.b_off + 2 * h.wbuf_bytes;
     h.kmt = F.fused ? 2 : kMT;
     std::vector<HStage>& stages = P->stages;
     P->n_ksteps = 0;
@@ -665,7 +652,7 @@ int plan_f16(const Launch& L, const PlanInputs& in, HostPlan* P, std::string* wh
     if (!build_constants(L, in, F, h, P, why)) return UMX_ERR_INVALID;
     if (getenv("UMX_DEBUG_PLAN"))
         fprintf(stderr, "[umx plan] %-12s %sNT %d x %d blocks, OC %d x %d halo slot(s), S %d, LDS %d B, k-steps %d, wshift %d\n",
-                L.name.c_str(), F.fused ? (h.pk ? "fused-phase packed " : "fused-phase ") : (h.pk ? "packed " : h.f6 ? "fp6-cross " : h.w2 ? "two-tile " : ""), F.nt16, h.nblocks, ch.OC, ch.slots, ch.S, h.lds_bytes, P->n_ksteps,
+                L.name.c_str(), F.fused ? (h.pk ? "fused-phase packed " : "fused-phase ") : (h.pk ? "packed " : h.f6 ? "fp6-cross " : ""), F.nt16, h.nblocks, ch.OC, ch.slots, ch.S, h.lds_bytes, P->n_ksteps,
                 P->wshift);
     h.inv_imgplane = 1.f / (float)h.imgplane;
     h.inv_hw = 1.f / (float)h.hw;
