@@ -61,6 +61,43 @@ UMX_API int umx_trainer_create(const umx_hparams* hp, const float* weight_blob, 
 UMX_API void umx_trainer_destroy(umx_trainer* tr);
 UMX_API const char* umx_trainer_last_error(const umx_trainer* tr);
 
+/* ---- the initial state: tf.global_variables_initializer() of the trainer's graph, made on the device ----
+ * replaces train(..., restoreVariables=False) (UnMicst2.py:434-438, UnMicst1-5.py, UnMicst.py).  Tensors are those of
+ * unmicst_amd/model.py tensor_specs, in that order (t = index of the tensor there, BN tensors counted).
+ *   BatchNorm     gamma 1, beta 0, moving mean 0, moving variance 1.
+ *   filters       float32(z * sigma), one rounding, z a standard normal redrawn while |z| > 2 (tf.truncated_normal).
+ *   sigma         legacy graph: (double)std_dev0 for every filter (UnMicst.py:83-168).  v2 graph: (double)std_dev0 for ld<i>.w1
+ *                 (kernelD<i>); every other filter VarianceScaling(scale=1, mode='fan_in') of tf.compat.v1.keras, read as
+ *                 sigma = sqrt(1.0 / fan_in) / UMX_INIT_TRUNC_STD with fan_in = the product of every dimension of the variable's
+ *                 shape but the last (also for the transposed filters [ks, ks, Cout, Cin]); all in float64.
+ *   the stream    a value depends on (seed, t, e = flat index of the element inside its tensor) only -- not on the grid, the launch
+ *                 or the tensor's offset.  With mix64 the finaliser the dropout stream uses (x ^= x >> 30, *= 0xBF58476D1CE4E5B9,
+ *                 x ^= x >> 27, *= 0x94D049BB133111EB, x ^= x >> 31), all arithmetic modulo 2^64:
+ *                     key = mix64((seed ^ UMX_INIT_DOMAIN) + 0x9E3779B97F4A7C15 * (t + 1))
+ *                 and for attempt a = 0 .. UMX_INIT_MAX_ATTEMPTS - 1, c = e * UMX_INIT_MAX_ATTEMPTS + a:
+ *                     u1 = ((mix64(key ^ (2 c)) >> 11) + 1) * 2^-53   in (0, 1]
+ *                     u2 =  (mix64(key ^ (2 c + 1)) >> 11) * 2^-53    in [0, 1)
+ *                     z  = sqrt(-2.0 * log(u1)) * cos(UMX_INIT_TWO_PI * u2)      float64, every operation one rounding
+ *                 The first attempt with |z| <= 2 is taken.  When all are refused (odds 0.0455^16, about 3e-22 per element)
+ *                 z = 0: the loop on the device is bounded.
+ * tests/init_ref.py restates this in numpy; device and host log / cos / sqrt may differ in the last bits, so a value may sit one
+ * float32 ulp from the restatement where z * sigma falls next to a rounding boundary (tests/test_gpu_init.py). */
+#define UMX_INIT_DOMAIN 0x554D58494E495431ull          /* "UMXINIT1" */
+#define UMX_INIT_MAX_ATTEMPTS 16
+#define UMX_INIT_TWO_PI 6.283185307179586              /* float64 nearest 2 pi, 0x401921FB54442D18 */
+#define UMX_INIT_TRUNC_STD 0.87962566103423978         /* standard deviation of a standard normal truncated at +-2 */
+typedef struct umx_init_options {
+    uint64_t seed;            /* of the initial state only: umx_train_options.seed (the dropout stream) is not touched */
+    float std_dev0;           /* the reference's stdDev0 (hp.data; 0.007 in its UNet2D.setup example, UnMicstCyto2.py:689) */
+    int32_t reserved[5];      /* must be zero */
+} umx_init_options;
+/* The trainer's variables become the initial state (one kernel over the parameter vector); gradient vector and optimiser slots are
+ * zeroed, the step counter goes to 0, a range report not yet read is dropped, and the weight scales of the split-precision
+ * convolutions are re-derived from the new variables: the next step is exactly the first step of a trainer created from the blob
+ * umx_trainer_read returns now.  Waits for the trainer's streams.  std_dev0 not finite or <= 0, or a non-zero reserved:
+ * UMX_ERR_INVALID before anything is enqueued (the variables stay). */
+UMX_API int umx_trainer_init(umx_trainer* tr, const umx_init_options* init);
+
 /* One step on HOST buffers: data [B,P,P,nChannels], labels and weights [B,P,P,nClasses], float32 NHWC (the reference's
  * batchData / batchLabels / batchWeights, UnMicst1-5.py:455-457,483).  apply_update 0: loss and gradients only
  * (parameters, slots, moving statistics and the step counter stay).  loss3 = {total, data term, regularisation}.
@@ -225,7 +262,7 @@ UMX_API int umx_trainer_assemble_warped(umx_trainer* tr, const umx_trainset* ts,
  * buffer of that trainer / set a red zone of max(64 KiB, its size rounded up to 4 KiB) on both sides.  The zones, and every buffer
  * the library does not zero or upload, are filled with that byte, so a result that depends on the byte read memory nobody wrote.
  * Every entry that enqueues work (umx_train_step, _step_dev, _step_sampled, _step_augmented, _step_warped, umx_trainer_eval, _assemble,
- * _assemble_augmented, _assemble_warped, _evaluate, umx_trainset_set) then waits for the trainer's streams and checks every zone: UMX_ERR_GUARD names the buffer, the side and the
+ * _assemble_augmented, _assemble_warped, _evaluate, umx_trainer_init, umx_trainset_set) then waits for the trainer's streams and checks every zone: UMX_ERR_GUARD names the buffer, the side and the
  * first and last changed byte.  Slow; for tests.  Off (unset or empty), allocations and launches are exactly the normal ones.
  *
  * The host scan of one zone (no device needed): zone_bytes bytes that should all equal `fill`, in front of (side 0) or behind

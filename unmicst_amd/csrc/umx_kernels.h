@@ -378,6 +378,17 @@ hipError_t launch_split_reduce(const float* part, int nsplit, size_t stride, siz
                                hipStream_t stream);
 hipError_t launch_optimizer(const OptParams& o, float* w, const float* g, float* m, float* v, size_t n, hipStream_t stream);
 
+// One tensor of the initial state (include/umx_train.h, umx_trainer_init): elements [off, off + count) of the parameter vector.
+enum { INIT_FILTER = 0, INIT_ONE = 1, INIT_ZERO = 2 };
+struct InitSeg {
+    unsigned long long off, count;
+    unsigned long long key;   // INIT_FILTER: the tensor's stream key
+    double sigma;             // INIT_FILTER
+    int kind, pad;
+};
+// w[0 .. n) from nseg segments (device memory, ascending and contiguous from 0 to n); one launch, grid-stride
+hipError_t launch_init_params(const InitSeg* segs_dev, int nseg, size_t n, float* w, hipStream_t stream);
+
 __host__ __device__ inline uint16_t double_to_half_rne(double d);
 
 }  // namespace umx

@@ -67,7 +67,7 @@ struct BnSite {            // one batch-normalised tensor
                                 // that scales its (hi, lo) planes before the tensor exists (bn_bwd_apply)
 };
 
-struct Seg { std::string name; size_t off, n; float reg; };
+struct Seg { std::string name; size_t off, n; float reg; int last; };   // last: the filter's last dimension (0: a BN block of 4 C)
 
 struct LBlock {                 // one block of the legacy graph: a chain of nExtraConvs + 1 convolutions with ReLUs between them
     std::vector<TConv> fwd;     // fwd[0] reads the block input (down: w1; up: unused, c_fwd_u is the concat conv), fwd[e >= 1] reads
@@ -160,6 +160,7 @@ struct umx_trainer {
     std::vector<PackDesc> packs;
     PackDesc* d_packs = nullptr;
     RegSeg* d_regsegs = nullptr;  int n_regsegs = 0;
+    InitSeg* d_initsegs = nullptr;  int cap_initsegs = 0;   // umx_trainer_init's table (allocated by its first call)
     size_t max_pack = 0;
     double flops_per_image = 0.0;
     // profiling
@@ -1189,27 +1190,27 @@ int build_trainer(umx_trainer* tr, const float* blob, size_t blob_floats) {
 
     // ---- parameter vector layout (== unmicst_amd/model.py tensor_specs, nExtraConvs == 0)
     size_t pos = 0;
-    auto seg = [&](const std::string& name, size_t cnt, float reg) { tr->segs.push_back({name, pos, cnt, reg}); pos += cnt; return pos - cnt; };
+    auto seg = [&](const std::string& name, size_t cnt, float reg, int last) { tr->segs.push_back({name, pos, cnt, reg, last}); pos += cnt; return pos - cnt; };
     std::vector<size_t> bn_d_off(L), bn_u_off(L);
     size_t bn_b_off, bn_t_off;
     tr->o_w1.resize(L); tr->o_ws.resize(L); tr->o_wt.resize(L); tr->o_w2.resize(L);
     char nm[64];
     for (int i = 0; i < L; ++i) {
         snprintf(nm, sizeof nm, "ld%d", i);
-        tr->o_w1[i] = seg(std::string(nm) + ".w1", (size_t)ks * ks * n[i] * n[i + 1], 0.f);
-        tr->o_ws[i] = seg(std::string(nm) + ".wshort", (size_t)ks * ks * n[i] * n[i + 1], o.reg_down);
-        bn_d_off[i] = seg(std::string(nm) + ".bn", 4 * (size_t)n[i + 1], 0.f);
+        tr->o_w1[i] = seg(std::string(nm) + ".w1", (size_t)ks * ks * n[i] * n[i + 1], 0.f, n[i + 1]);
+        tr->o_ws[i] = seg(std::string(nm) + ".wshort", (size_t)ks * ks * n[i] * n[i + 1], o.reg_down, n[i + 1]);
+        bn_d_off[i] = seg(std::string(nm) + ".bn", 4 * (size_t)n[i + 1], 0.f, 0);
     }
-    tr->o_lb = seg("lb.w", (size_t)ks * ks * n[L] * n[L + 1], o.reg_bottom);
-    bn_b_off = seg("lb.bn", 4 * (size_t)n[L + 1], 0.f);
+    tr->o_lb = seg("lb.w", (size_t)ks * ks * n[L] * n[L + 1], o.reg_bottom, n[L + 1]);
+    bn_b_off = seg("lb.bn", 4 * (size_t)n[L + 1], 0.f, 0);
     for (int idx = L - 1; idx >= 0; --idx) {
         snprintf(nm, sizeof nm, "lu%d", idx);
-        tr->o_wt[idx] = seg(std::string(nm) + ".wt", (size_t)ks * ks * n[idx + 1] * n[idx + 2], o.reg_up);
-        tr->o_w2[idx] = seg(std::string(nm) + ".w2", (size_t)ks * ks * (n[idx] + n[idx + 1]) * n[idx + 1], o.reg_up);
-        bn_u_off[idx] = seg(std::string(nm) + ".bn", 4 * (size_t)n[idx + 1], 0.f);
+        tr->o_wt[idx] = seg(std::string(nm) + ".wt", (size_t)ks * ks * n[idx + 1] * n[idx + 2], o.reg_up, n[idx + 2]);
+        tr->o_w2[idx] = seg(std::string(nm) + ".w2", (size_t)ks * ks * (n[idx] + n[idx + 1]) * n[idx + 1], o.reg_up, n[idx + 1]);
+        bn_u_off[idx] = seg(std::string(nm) + ".bn", 4 * (size_t)n[idx + 1], 0.f, 0);
     }
-    tr->o_lt = seg("lt.w", (size_t)n[1] * K, o.reg_top);
-    bn_t_off = seg("lt.bn", 4 * (size_t)K, 0.f);
+    tr->o_lt = seg("lt.w", (size_t)n[1] * K, o.reg_top, K);
+    bn_t_off = seg("lt.bn", 4 * (size_t)K, 0.f, 0);
     T_TRY(alloc_params(tr, blob, blob_floats, pos));
 
     // ---- activations
@@ -1391,26 +1392,26 @@ int build_legacy(umx_trainer* tr, const float* blob, size_t blob_floats) {
 
     // ---- parameter vector layout (== unmicst_amd/model.py tensor_specs, GRAPH_LEGACY)
     size_t pos = 0;
-    auto seg = [&](const std::string& name, size_t cnt) { tr->segs.push_back({name, pos, cnt, 0.f}); pos += cnt; return pos - cnt; };
+    auto seg = [&](const std::string& name, size_t cnt, int last) { tr->segs.push_back({name, pos, cnt, 0.f, last}); pos += cnt; return pos - cnt; };
     std::vector<size_t> bn_d_off(L);
     tr->o_w1.resize(L); tr->o_ws.resize(L); tr->o_wt.resize(L); tr->o_w2.resize(L);
     tr->ldb.resize(L); tr->lub.resize(L);
     char nm[64];
     for (int i = 0; i < L; ++i) {
         const std::string p = "ld" + std::to_string(i);
-        tr->o_w1[i] = seg(p + ".w1", (size_t)ks * ks * n[i] * n[i + 1]);
-        for (int e = 0; e < E; ++e) tr->ldb[i].o_wx.push_back(seg(p + ".wextra" + std::to_string(e), (size_t)ks * ks * n[i + 1] * n[i + 1]));
-        tr->o_ws[i] = seg(p + ".wshort", (size_t)n[i] * n[i + 1]);
-        bn_d_off[i] = seg(p + ".bn", 4 * (size_t)n[i + 1]);
+        tr->o_w1[i] = seg(p + ".w1", (size_t)ks * ks * n[i] * n[i + 1], n[i + 1]);
+        for (int e = 0; e < E; ++e) tr->ldb[i].o_wx.push_back(seg(p + ".wextra" + std::to_string(e), (size_t)ks * ks * n[i + 1] * n[i + 1], n[i + 1]));
+        tr->o_ws[i] = seg(p + ".wshort", (size_t)n[i] * n[i + 1], n[i + 1]);
+        bn_d_off[i] = seg(p + ".bn", 4 * (size_t)n[i + 1], 0);
     }
-    tr->o_lb = seg("lb.w", (size_t)ks * ks * n[L] * n[L + 1]);
+    tr->o_lb = seg("lb.w", (size_t)ks * ks * n[L] * n[L + 1], n[L + 1]);
     for (int idx = L - 1; idx >= 0; --idx) {
         const std::string p = "lu" + std::to_string(idx);
-        tr->o_wt[idx] = seg(p + ".wt", (size_t)ks * ks * n[idx + 1] * n[idx + 2]);
-        tr->o_w2[idx] = seg(p + ".w2", (size_t)ks * ks * (n[idx] + n[idx + 1]) * n[idx + 1]);
-        for (int e = 0; e < E; ++e) tr->lub[idx].o_wx.push_back(seg(p + ".wextra" + std::to_string(e), (size_t)ks * ks * n[idx + 1] * n[idx + 1]));
+        tr->o_wt[idx] = seg(p + ".wt", (size_t)ks * ks * n[idx + 1] * n[idx + 2], n[idx + 2]);
+        tr->o_w2[idx] = seg(p + ".w2", (size_t)ks * ks * (n[idx] + n[idx + 1]) * n[idx + 1], n[idx + 1]);
+        for (int e = 0; e < E; ++e) tr->lub[idx].o_wx.push_back(seg(p + ".wextra" + std::to_string(e), (size_t)ks * ks * n[idx + 1] * n[idx + 1], n[idx + 1]));
     }
-    tr->o_lt = seg("lt.w", (size_t)n[1] * K);
+    tr->o_lt = seg("lt.w", (size_t)n[1] * K, K);
     T_TRY(alloc_params(tr, blob, blob_floats, pos));
 
     // ---- max words (zeroed every step), then the range flag
@@ -1968,6 +1969,56 @@ int umx_trainer_create(const umx_hparams* hp, const float* weight_blob, size_t b
         fprintf(stderr, "[umx train] UMX_DEBUG_GUARD=0x%02x: %zu trainer buffers between red zones\n", tr->mem.fill, tr->mem.blocks.size());
     *out = tr;
     return UMX_OK;
+}
+
+int umx_trainer_init(umx_trainer* tr, const umx_init_options* init) {
+    if (!tr || !init) return tfail(tr, UMX_ERR_INVALID, "null argument");
+    if (!std::isfinite(init->std_dev0) || !(init->std_dev0 > 0.f))
+        return tfail(tr, UMX_ERR_INVALID, "umx_init_options.std_dev0 must be finite and > 0, got %g", (double)init->std_dev0);
+    for (int i = 0; i < 5; ++i)
+        if (init->reserved[i]) return tfail(tr, UMX_ERR_INVALID, "umx_init_options.reserved must be zero");
+    // one entry per tensor of unmicst_amd/model.py tensor_specs, in that order (t counts the BN tensors too)
+    std::vector<InitSeg> tab;
+    unsigned long long t = 0, pos = 0;
+    for (const Seg& sg : tr->segs) {
+        if (sg.off != pos) return tfail(tr, UMX_ERR_INVALID, "parameter segments are not contiguous at %s", sg.name.c_str());
+        pos += sg.n;
+        if (sg.last == 0) {   // gamma 1 | beta 0 | moving mean 0 | moving variance 1
+            const unsigned long long C = sg.n / 4;
+            for (int k = 0; k < 4; ++k) tab.push_back(InitSeg{sg.off + k * C, C, 0, 0.0, k == 0 || k == 3 ? INIT_ONE : INIT_ZERO, 0});
+            t += 4;
+            continue;
+        }
+        const bool first = sg.name.size() > 3 && sg.name.compare(sg.name.size() - 3, 3, ".w1") == 0;   // kernel1 / kernelD<i>
+        const double fan_in = (double)(sg.n / (size_t)sg.last);
+        const double sigma = tr->legacy || first ? (double)init->std_dev0 : std::sqrt(1.0 / fan_in) / UMX_INIT_TRUNC_STD;
+        const unsigned long long key = mix64_host((init->seed ^ UMX_INIT_DOMAIN) + 0x9E3779B97F4A7C15ull * (t + 1));
+        tab.push_back(InitSeg{sg.off, sg.n, key, sigma, INIT_FILTER, 0});
+        t += 1;
+    }
+    if (pos != tr->nparams || tab.empty()) return tfail(tr, UMX_ERR_INVALID, "parameter segments cover %llu of %zu floats", pos, tr->nparams);
+    T_HIP(tr, hipSetDevice(tr->device));
+    T_TRY(fold_profile(tr));
+    for (hipStream_t s : {tr->stream, tr->side, tr->side2, tr->aux})
+        if (s) T_HIP(tr, hipStreamSynchronize(s));
+    if (!tr->d_initsegs) {
+        T_TRY(talloc(tr, &tr->d_initsegs, tab.size()));
+        tr->cap_initsegs = (int)tab.size();
+    }
+    if ((int)tab.size() != tr->cap_initsegs) return tfail(tr, UMX_ERR_INVALID, "the initial state's table changed size");
+    T_HIP(tr, hipMemcpy(tr->d_initsegs, tab.data(), tab.size() * sizeof(InitSeg), hipMemcpyHostToDevice));
+    T_HIP(tr, launch_init_params(tr->d_initsegs, (int)tab.size(), tr->nparams, tr->d_w, tr->stream));
+    T_HIP(tr, hipMemsetAsync(tr->d_g, 0, tr->nparams * sizeof(float), tr->stream));
+    T_HIP(tr, hipMemsetAsync(tr->d_m, 0, tr->nparams * sizeof(float), tr->stream));
+    T_HIP(tr, hipMemsetAsync(tr->d_v, 0, tr->nparams * sizeof(float), tr->stream));
+    T_HIP(tr, hipMemsetAsync(tr->d_maxw + tr->n_maxw, 0, sizeof(unsigned), tr->stream));   // the range flag of the old variables
+    tr->range_pending = false;
+    tr->step = 0;
+    // the derived copies: packed operands and weight images are rebuilt from the variables by every step; the scales they are stored
+    // with were derived from the variables the trainer was created with
+    T_TRY(refresh_wscales(tr));
+    T_HIP(tr, hipStreamSynchronize(tr->stream));
+    return umx::trainer_guard_check(tr);
 }
 
 void umx_trainer_destroy(umx_trainer* tr) {

@@ -6,6 +6,7 @@
 //
 // Every reduction has a fixed summation order (per-thread serial sums, in-block sums in thread order, partials summed
 // in block order, fp64): a step is bit-reproducible from run to run.  No floating-point atomics anywhere.
+#include "../../include/umx_train.h"
 #include "umx_kernels.h"
 
 #include <algorithm>
@@ -779,7 +780,16 @@ __global__ void __launch_bounds__(256) head_fwd_kernel(const float* __restrict__
 hipError_t launch_head_fwd(const float* x, size_t N, int C, int K, const float* w, float* t0, hipStream_t stream) {
     if (K > kMaxK) return hipErrorInvalidValue;
     const size_t lds = sizeof(float) * ((size_t)C * K + 256 * (size_t)(C + 1));
-    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds > 64 * 1024) {   // (nOut0 > 63, the solo model's 80 features: more dynamic LDS than a kernel gets by default)
+        static bool attr_set = false;
+        if (!attr_set) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(head_fwd_kernel),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e != hipSuccess) return e;
+            attr_set = true;
+        }
+    }
     hipLaunchKernelGGL(head_fwd_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), lds, stream, x, N, C, K, w, t0);
     return hipGetLastError();
 }
@@ -2001,6 +2011,45 @@ __global__ void __launch_bounds__(256) optimizer_kernel(const OptParams o, float
 
 hipError_t launch_optimizer(const OptParams& o, float* w, const float* g, float* m, float* v, size_t n, hipStream_t stream) {
     hipLaunchKernelGGL(optimizer_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, o, w, g, m, v, n);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ initial state
+// tf.global_variables_initializer() of the graph, written into the flat parameter vector (include/umx_train.h, umx_trainer_init;
+// == tests/init_ref.py).  A value depends on its tensor's key and its index inside the tensor only: the grid is free.
+__device__ __forceinline__ float init_draw(unsigned long long key, unsigned long long e, double sigma) {
+    double z = 0.0;   // (every attempt refused: 0)
+    for (int a = 0; a < UMX_INIT_MAX_ATTEMPTS; ++a) {
+        const unsigned long long c = e * UMX_INIT_MAX_ATTEMPTS + a;
+        const double u1 = (double)((mix64(key ^ (2 * c)) >> 11) + 1) * 0x1p-53;
+        const double u2 = (double)(mix64(key ^ (2 * c + 1)) >> 11) * 0x1p-53;
+        const double r = sqrt(-2.0 * log(u1));
+        const double zz = r * cos(UMX_INIT_TWO_PI * u2);
+        if (fabs(zz) <= 2.0) { z = zz; break; }
+    }
+    return (float)(z * sigma);
+}
+
+__global__ void __launch_bounds__(256) init_params_kernel(const InitSeg* __restrict__ segs, int nseg, size_t n,
+                                                          float* __restrict__ w) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        int lo = 0, hi = nseg - 1;   // the last segment that starts at or before i
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (segs[mid].off <= i) lo = mid; else hi = mid - 1;
+        }
+        const InitSeg sg = segs[lo];
+        const unsigned long long e = i - sg.off;
+        float v = 0.f;
+        if (e < sg.count) v = sg.kind == INIT_ONE ? 1.f : sg.kind == INIT_FILTER ? init_draw(sg.key, e, sg.sigma) : 0.f;
+        w[i] = v;
+    }
+}
+
+hipError_t launch_init_params(const InitSeg* segs_dev, int nseg, size_t n, float* w, hipStream_t stream) {
+    if (nseg < 1 || n == 0) return hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(init_params_kernel, dim3(blocks), dim3(256), 0, stream, segs_dev, nseg, n, w);
     return hipGetLastError();
 }
 

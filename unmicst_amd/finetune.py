@@ -1,9 +1,10 @@
-"""Fine-tune a model on an annotated training set:
+"""Fine-tune a model on an annotated training set, or train one from the initial state:
 
     python -m unmicst_amd.finetune --model NAME|DIR --train DIR --valid DIR --out DIR [--steps N] [--batch B] [--pages A]
                                    [--eval-every E] [--seed S] [--lr0 LR] [--transforms] [--device D]
                                    [--blur-sigmas 0.75,1.5,3] [--blur-prob P] [--saturate-prob P] [--max-gain G]
                                    [--rotate-prob P] [--zoom-prob P] [--zoom-range LO,HI]
+                                   [--from-scratch [--init-seed S] [--std-dev0 V] [--mean M --std S]]
 
 ``--train`` / ``--valid`` hold the reference's published layout (``I%05d_Img.tif`` / ``_Ant.tif`` / ``_wt.tif``, see
 unmicst_amd/trainset.py).  Both sets are uploaded to the device once; each step draws its batch with ``Sampler`` and trains with
@@ -25,6 +26,15 @@ Rotation and zoom, the geometry a small set of ``imSize``-wide samples cannot ge
 ``--zoom-range LO,HI`` (``0.5 <= LO <= 1 <= HI <= 2``).  Data is resampled bilinearly and mirrored at the sample's edges; labels and
 weight maps take the nearest source pixel (``Trainer.step_warped``).  Validation stays unwarped.  When one of the three flags is given,
 the log's first line carries the settings as its ``"warp"`` object (next to ``"augment"`` when both are on).
+
+``--from-scratch`` starts from the graph's initial state instead of the model's weights (the reference's
+``train(..., restoreVariables=False)``: ``tf.global_variables_initializer()``, made on the device by ``Trainer.from_scratch``; DESIGN.md
+section 9.3).  ``--model`` then supplies hyper-parameters only: a directory without weights (the shipped ``nucleiDAPI1-5`` /
+``nucleiDAPILAMIN`` stand-ins) is accepted, and the weights of one that has them are not read.  ``--init-seed`` (default: ``--seed``)
+seeds the initial state, ``--std-dev0`` overrides the reference's ``stdDev0`` (default: the directory's ``hp.data``, else 0.007), and
+``--mean`` / ``--std`` (both or neither) set the new model's normalisation instead of the model directory's scalars.  The log's first
+line then starts with the ``"init"`` object: seed, std_dev0, mean and std of the run (and ``"weights_not_read": true`` when the
+model directory has weights).
 
 The run is a function of its arguments: the same seed gives the same descriptor stream, the same steps and the same files.
 There is no CPU fallback.
@@ -69,7 +79,47 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--rotate-prob", type=float, default=None, help="chance that an image is rotated by a uniform angle (default 0)")
     p.add_argument("--zoom-prob", type=float, default=None, help="chance that an image is magnified (default 0.5 with --zoom-range)")
     p.add_argument("--zoom-range", default=None, help="LO,HI: magnifications are drawn log-uniformly, 0.5 <= LO <= 1 <= HI <= 2")
+    p.add_argument("--from-scratch", action="store_true", help="start from the graph's initial state, not from the model's weights")
+    p.add_argument("--init-seed", type=int, default=None, help="seed of the initial state (default: --seed); needs --from-scratch")
+    p.add_argument("--std-dev0", type=float, default=None,
+                   help="the reference's stdDev0 (default: the model directory's hp.data, else %g); needs --from-scratch" % trainer.DEFAULT_STD_DEV0)
+    p.add_argument("--mean", type=float, default=None, help="normalisation mean of the new model (with --std); needs --from-scratch")
+    p.add_argument("--std", type=float, default=None, help="normalisation std of the new model (with --mean); needs --from-scratch")
     return p
+
+
+def init_settings(args, model_path=None):
+    """The from-scratch flags -> None without --from-scratch, else {"seed", "std_dev0", "mean", "std"}.  ``model_path`` supplies what
+    the flags leave open (hp.data's stdDev0, the directory's mean / std); without it those stay None and only the flags are checked.
+    Raises Refusal."""
+    flags = (("--init-seed", "init_seed"), ("--std-dev0", "std_dev0"), ("--mean", "mean"), ("--std", "std"))
+    if not getattr(args, "from_scratch", False):
+        for flag, key in flags:
+            if getattr(args, key, None) is not None:
+                raise Refusal("%s needs --from-scratch" % flag)
+        return None
+    if args.std_dev0 is not None and not (math.isfinite(args.std_dev0) and args.std_dev0 > 0):
+        raise Refusal("--std-dev0 %r: a standard deviation is finite and > 0" % args.std_dev0)
+    if (args.mean is None) != (args.std is None):
+        raise Refusal("--mean and --std go together: got only %s" % ("--mean" if args.std is None else "--std"))
+    if args.std is not None and not (math.isfinite(args.std) and args.std > 0):
+        raise Refusal("--std %r: a standard deviation is finite and > 0" % args.std)
+    if args.mean is not None and not math.isfinite(args.mean):
+        raise Refusal("--mean %r is not finite" % args.mean)
+    out = {"seed": int(args.seed if args.init_seed is None else args.init_seed), "std_dev0": args.std_dev0, "mean": args.mean,
+           "std": args.std}
+    if model_path is not None:
+        _, mean, std, sd0 = model.load_hparams_dir(model_path)
+        if out["std_dev0"] is None:
+            out["std_dev0"] = trainer.DEFAULT_STD_DEV0 if sd0 is None else sd0
+        if out["mean"] is None:
+            out["mean"], out["std"] = mean, std
+    return {k: (v if v is None or k == "seed" else float(v)) for k, v in out.items()}
+
+
+def has_weights(model_path: str) -> bool:
+    """Whether load_model_dir would find weights in this directory (the converted blob or the reference's checkpoint shard)."""
+    return any(os.path.exists(os.path.join(model_path, n)) for n in (model.CONVERTED_NAME, "model.ckpt.data-00000-of-00001"))
 
 
 def warp_settings(args):
@@ -151,6 +201,7 @@ def prepare(args):
         raise Refusal("--steps, --eval-every and --pages must be positive, --batch non-negative")
     augment_settings(args)
     warp_settings(args)
+    scratch = init_settings(args) is not None
     path = resolve_model(args.model)
     if not os.path.isdir(path):
         raise Refusal("model %s: no such directory (%s)" % (args.model, path))
@@ -159,10 +210,19 @@ def prepare(args):
             raise Refusal("%s %s: no such directory" % (what, d))
         if not trainset.dataset_indices(d):
             raise Refusal("%s %s holds no I%%05d_Img.tif samples" % (what, d))
-    try:
-        art = model.load_model_dir(path)
-    except FileNotFoundError as e:
-        raise Refusal("model %s has no weights to fine-tune: %s" % (args.model, e))
+    if scratch:
+        # hyper-parameters only: the artefacts carry no blob, and the normalisation the new model is trained with
+        try:
+            hp0 = model.load_hparams_dir(path)[0]
+            init = init_settings(args, path)
+        except (FileNotFoundError, KeyError) as e:
+            raise Refusal("model %s has no hyper-parameters to start from: %s" % (args.model, e))
+        art = model.ModelArtefacts(hp0, None, init["mean"], init["std"])
+    else:
+        try:
+            art = model.load_model_dir(path)
+        except FileNotFoundError as e:
+            raise Refusal("model %s has no weights to fine-tune: %s" % (args.model, e))
     hp = art.hp
     sets = []
     for what, d in (("--train", args.train), ("--valid", args.valid)):
@@ -184,7 +244,15 @@ def run(args) -> int:
     hp = art.hp
     kind = trainset.graph_kind(hp)
     lw = trainset.LABEL_WEIGHTS[kind]
-    tr = trainer.Trainer(hp, art.blob, options_for(kind, args.seed, args.lr0), batch=args.batch, device=args.device)
+    init = init_settings(args, resolve_model(args.model))
+    if init is None:
+        tr = trainer.Trainer(hp, art.blob, options_for(kind, args.seed, args.lr0), batch=args.batch, device=args.device)
+    else:
+        if has_weights(resolve_model(args.model)):
+            init["weights_not_read"] = True
+            print("--from-scratch: the weights of model %s are not read (it supplies the hyper-parameters only)" % args.model, flush=True)
+        tr = trainer.Trainer.from_scratch(hp, options_for(kind, args.seed, args.lr0), init["seed"], init["std_dev0"], batch=args.batch,
+                                          device=args.device)
     try:
         ts = trainset.upload(tr, train_ds, lw)
         vs = trainset.upload(tr, valid_ds, lw)
@@ -204,7 +272,7 @@ def run(args) -> int:
         best = None
         train_loss = None
         with open(log_path, "w") as log:
-            settings = {k: v for k, v in (("augment", aug), ("warp", warp)) if v is not None}
+            settings = {k: v for k, v in (("init", init), ("augment", aug), ("warp", warp)) if v is not None}
             if settings:
                 log.write(json.dumps(settings) + "\n")
             for step in range(args.steps + 1):

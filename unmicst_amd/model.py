@@ -329,6 +329,34 @@ def save_converted(art: "ModelArtefacts", model_path: str) -> str:
     return out
 
 
+def load_hparams_dir(model_path: str, graph: int = None, prefix: str = "model.ckpt"):
+    """-> (hp, mean, std, std_dev0 or None) of a model directory, reading no weights: what a run from the initial state needs
+    (``python -m unmicst_amd.finetune --from-scratch``).  Takes what ``load_model_dir`` takes -- a converted directory
+    (``umx_model.npz``), an ``umx_hp.npz`` stand-in, or the reference's ``hp.data`` + ``datasetMean.data`` / ``datasetStDev.data``
+    (the graph kind from ``<prefix>.index`` unless ``graph`` names it) -- in the same order of preference.  ``std_dev0`` is
+    ``hp.data``'s ``stdDev0`` (the sigma ``UNet2D.setup`` was called with, reference UnMicst1-5.py:55-66) when the directory has one."""
+    std_dev0 = None
+    hp_data = os.path.join(model_path, "hp.data")
+    hp_dict = load_pickle(hp_data) if os.path.exists(hp_data) else None
+    if hp_dict is not None and hp_dict.get("stdDev0") is not None:
+        std_dev0 = float(hp_dict["stdDev0"])
+    for name in (CONVERTED_NAME, HP_ONLY_NAME):
+        path = os.path.join(model_path, name)
+        if os.path.exists(path) and (name == CONVERTED_NAME or hp_dict is None):
+            with np.load(path) as z:
+                return hparams_from_vector(z["hp"]), float(z["mean"]), float(z["std"]), std_dev0
+    if hp_dict is None:
+        raise FileNotFoundError("%s holds neither %s, %s nor hp.data" % (model_path, CONVERTED_NAME, HP_ONLY_NAME))
+    if graph is None:
+        graph = detect_graph(model_path, prefix)
+    if prefix != "model.ckpt":
+        hp_dict = hp_dict_from_checkpoint(hp_dict, tfckpt.read_index(os.path.join(model_path, prefix + ".index")))
+    hp = hparams_from_dict(hp_dict, graph)
+    mean = float(load_pickle(os.path.join(model_path, "datasetMean.data")))
+    std = float(load_pickle(os.path.join(model_path, "datasetStDev.data")))
+    return hp, mean, std, std_dev0
+
+
 def load_model_dir(model_path: str, graph: int = None, synthetic_if_missing: bool = False,
                    prefix: str = "model.ckpt") -> ModelArtefacts:
     """Read a model directory: the converted ``umx_model.npz`` if present, else the reference's own artefacts

@@ -31,7 +31,7 @@ EXPORTS = [
     "umx_trainer_profile", "umx_trainset_create", "umx_trainset_set", "umx_trainset_destroy", "umx_train_step_sampled",
     "umx_trainer_assemble", "umx_trainer_evaluate", "umx_guard_scan", "umx_augment_table_check", "umx_trainset_set_augment",
     "umx_train_step_augmented", "umx_trainer_assemble_augmented", "umx_warp_desc_check", "umx_train_step_warped",
-    "umx_trainer_assemble_warped",
+    "umx_trainer_assemble_warped", "umx_trainer_init",
 ]
 
 
@@ -44,6 +44,15 @@ class _TrainOptions(ctypes.Structure):
                 ("clip_eps", ctypes.c_float), ("drop_down_step", ctypes.c_float), ("drop_bottom", ctypes.c_float),
                 ("drop_up0", ctypes.c_float), ("drop_up_step", ctypes.c_float), ("bn_momentum", ctypes.c_float),
                 ("seed", ctypes.c_uint64), ("reserved", ctypes.c_int32 * 8)]
+
+
+class _InitOptions(ctypes.Structure):
+    """``umx_init_options`` (include/umx_train.h)."""
+    _fields_ = [("seed", ctypes.c_uint64), ("std_dev0", ctypes.c_float), ("reserved", ctypes.c_int32 * 5)]
+
+
+# the reference's stdDev0 where a model directory has no hp.data: its own UNet2D.setup(...) example (UnMicstCyto2.py:689)
+DEFAULT_STD_DEV0 = 0.007
 
 
 @dataclass
@@ -141,6 +150,8 @@ def _bind(L):
                                      ctypes.POINTER(c_void_p)]
     L.umx_trainer_destroy.restype = None
     L.umx_trainer_destroy.argtypes = [c_void_p]
+    L.umx_trainer_init.restype = c_int
+    L.umx_trainer_init.argtypes = [c_void_p, ctypes.POINTER(_InitOptions)]
     L.umx_trainer_last_error.restype = ctypes.c_char_p
     L.umx_trainer_last_error.argtypes = [c_void_p]
     L.umx_train_step.restype = c_int
@@ -240,6 +251,29 @@ class Trainer:
         self._h = h
         self.batch = int(self._lib.umx_trainer_batch(h))
         self.device = int(device)
+
+    @classmethod
+    def from_scratch(cls, hp: HParams, opts: Optional[TrainOptions], init_seed: int, std_dev0: float, batch: int = 0,
+                     device: int = 0) -> "Trainer":
+        """A trainer whose variables are the graph's initial state (``tf.global_variables_initializer()``):
+        created from a zero blob of the graph's length, then initialised on the device (``init``)."""
+        from .model import tensor_specs
+        n = sum(int(np.prod(shape)) for _, shape in tensor_specs(hp))
+        tr = cls(hp, np.zeros(n, np.float32), opts, batch=batch, device=device)
+        try:
+            tr.init(init_seed, std_dev0)
+        except Exception:
+            tr.close()
+            raise
+        return tr
+
+    def init(self, seed: int, std_dev0: float):
+        """Replace the variables by the initial state of (seed, std_dev0) (umx_trainer_init): truncated-normal filters, BN at its
+        identity; gradients and optimiser slots zeroed, step counter 0.  The dropout stream (``TrainOptions.seed``) is not touched."""
+        o = _InitOptions()
+        o.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        o.std_dev0 = float(std_dev0)
+        self._check(self._lib.umx_trainer_init(self._h, ctypes.byref(o)))
 
     # ------------------------------------------------------------------------------------------
     def _check(self, rc):

@@ -62,7 +62,10 @@ class UNet2D:
     def train(*args, **kwargs):
         """Out of scope: the reference's data loading, augmentation and bookkeeping around the
         optimisation step (UnMicst1-5.py:240-578) are not part of the path this package replaces.  The step itself is
-        ``unmicst_amd.trainer.Trainer.step`` (include/umx_train.h); INTEGRATION.md shows where it goes in the reference's loop."""
+        ``unmicst_amd.trainer.Trainer.step`` (include/umx_train.h); INTEGRATION.md shows where it goes in the reference's loop.
+        Both starts of the reference's ``train`` have a counterpart: ``restoreVariables=True`` is ``Trainer(hp, blob, ...)`` on a
+        model's weights, ``restoreVariables=False`` (``tf.global_variables_initializer()``) is ``Trainer.from_scratch`` -- the
+        initial state made on the device; ``python -m unmicst_amd.finetune [--from-scratch]`` runs either."""
         raise NotImplementedError("UNet2D.train is out of scope: drive unmicst_amd.trainer.Trainer.step from your own loop "
                                   "(INTEGRATION.md, 'Training step')")
 
