@@ -258,11 +258,53 @@ UMX_API int umx_trainer_assemble_warped(umx_trainer* tr, const umx_trainset* ts,
                                         const umx_augment_desc* aug, const umx_warp_desc* warp, int n, float* data, float* labels,
                                         float* weights);
 
+/* ---- elastic deformation ("Elastic deformation") ----
+ * Per image of a batch, next to its umx_sample_desc (and its umx_augment_desc / umx_warp_desc, when there are any): a lattice of n x n
+ * displacement vectors, drawn on the host, that a uniform cubic B-spline spreads over the crop (n - 3 spline cells across it).  The
+ * displacement is added to the pixel's coordinate on the crop's own grid in front of the rotation / zoom, so the image is resampled
+ * once.  n == 0 is "no deformation": such an image is assembled exactly as the entries above assemble it.
+ * Order per image and channel: page plane -> elastic + warp (one resampling) -> blur -> saturation -> crop orientation + dihedral
+ * transform -> jitter.  For pixel (y, x) of the crop's own grid -- any integers, also outside 0 .. P-1 (the blur's halo) -- with
+ * P = imSize, D = (double)d, in float64, every product, sum, division and floor one rounding (no fma):
+ *   0a. per axis, t the pixel's coordinate on it: tc = min(max(t, 0), P - 1) (a pixel outside the crop takes the displacement of the
+ *       nearest crop-edge pixel); scale = (double)(n - 3) / (double)(P - 1); u = tc * scale; i = min(floor(u), n - 4); f = u - i;
+ *       g = 1 - f, f2 = f * f, f3 = f2 * f;  W0 = (g * g) * g;  W1 = (3 f3 - 6 f2) + 4;  W2 = ((-3 f3 + 3 f2) + 3 f) + 1;  W3 = f3
+ *       (six times the B-spline's weights).
+ *   0b. per component k (0: rows, 1: columns), with (Wy, iy) of y and (Wx, ix) of x:
+ *       row_a = ((Wx0 D[k][iy+a][ix] + Wx1 D[k][iy+a][ix+1]) + Wx2 D[k][iy+a][ix+2]) + Wx3 D[k][iy+a][ix+3], a = 0..3;
+ *       e_k = (((Wy0 row_0 + Wy1 row_1) + Wy2 row_2) + Wy3 row_3) / 36.0.   |e_k| <= max |D| (convex hull); a zero lattice gives +0.0.
+ *   1'. step 1 of the warp recipe with ((y + e_0) - c) and ((x + e_1) - c) in place of (y - c) and (x - c); without a umx_warp_desc,
+ *       or with the identity, the same formula with m = {1, 0, 0, 1}.
+ *   2-4. as there: the mirror fold, bilinear data with one float32 rounding, label and weight from the one nearest source pixel.
+ * The device draws no random number and evaluates no transcendental for this. */
+#define UMX_ELASTIC_MAX_GRID 6        /* lattice points per axis: 4..6 = 1..3 spline cells across the crop */
+#define UMX_ELASTIC_MAX_DISP 32.0f    /* |d| bound, pixels */
+typedef struct umx_elastic_desc {     /* 304 bytes: one image of a batch, parallel to its umx_sample_desc */
+    int32_t n;                        /* 0 = no elastic deformation for this image; else 4..6 */
+    int32_t reserved[3];              /* must be zero */
+    float d[2][6][6];                 /* d[0][a][b]: row (y) displacement of lattice point (a, b), d[1]: column (x); pixels.
+                                         Entries with a >= n or b >= n must be 0 */
+} umx_elastic_desc;
+
+/* Host validation of n_desc descriptors (no device needed): n in {0, 4, 5, 6}, reserved zero, every entry finite and
+ * |d| <= UMX_ELASTIC_MAX_DISP, every entry outside the n x n block zero (n == 0: all of them).  UMX_OK, or UMX_ERR_INVALID with the first
+ * broken one in msg ("elastic <index> ...": cap bytes, NUL-terminated; msg may be NULL). */
+UMX_API int umx_elastic_desc_check(const umx_elastic_desc* e, int n_desc, char* msg, size_t cap);
+/* umx_train_step_warped / umx_trainer_assemble_warped with a parallel array of umx_elastic_desc (B resp. n of them).  aug == NULL: no
+ * blur and gain 1; warp == NULL: the identity for every image; elastic == NULL is UMX_ERR_INVALID.  Everything is checked on the host
+ * before anything is enqueued, in the order descriptors, augmentations (when given), warps (when given), lattices: UMX_ERR_INVALID
+ * for what those entries refuse, for what umx_elastic_desc_check refuses, and for a set of 1-pixel samples. */
+UMX_API int umx_train_step_elastic(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
+                                   const umx_warp_desc* warp, const umx_elastic_desc* elastic, int apply_update);
+UMX_API int umx_trainer_assemble_elastic(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc,
+                                         const umx_augment_desc* aug, const umx_warp_desc* warp, const umx_elastic_desc* elastic, int n,
+                                         float* data, float* labels, float* weights);
+
 /* Debug guard mode.  UMX_DEBUG_GUARD=<byte> (e.g. 0xff), read by umx_trainer_create and umx_trainset_create, gives every device
  * buffer of that trainer / set a red zone of max(64 KiB, its size rounded up to 4 KiB) on both sides.  The zones, and every buffer
  * the library does not zero or upload, are filled with that byte, so a result that depends on the byte read memory nobody wrote.
- * Every entry that enqueues work (umx_train_step, _step_dev, _step_sampled, _step_augmented, _step_warped, umx_trainer_eval, _assemble,
- * _assemble_augmented, _assemble_warped, _evaluate, umx_trainer_init, umx_trainset_set) then waits for the trainer's streams and checks every zone: UMX_ERR_GUARD names the buffer, the side and the
+ * Every entry that enqueues work (umx_train_step, _step_dev, _step_sampled, _step_augmented, _step_warped, _step_elastic, umx_trainer_eval, _assemble,
+ * _assemble_augmented, _assemble_warped, _assemble_elastic, _evaluate, umx_trainer_init, umx_trainset_set) then waits for the trainer's streams and checks every zone: UMX_ERR_GUARD names the buffer, the side and the
  * first and last changed byte.  Slow; for tests.  Off (unset or empty), allocations and launches are exactly the normal ones.
  *
  * The host scan of one zone (no device needed): zone_bytes bytes that should all equal `fill`, in front of (side 0) or behind

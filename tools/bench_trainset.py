@@ -4,10 +4,12 @@ in one process, alternating the two, on the same descriptor stream.  Every step 
 both paths).  A third leg, "augmented", is Trainer.step_augmented with every image at the largest blur level of the sigmas
 0.75, 1.5, 3 and gain 2 -- the worst case of the computed defocus / saturation -- alternated with the other two in the same process,
 so that step_sampled of the same run is its yardstick.  A fourth leg, "warped", is Trainer.step_warped with the same blur and gain and
-every image rotated by 30 degrees at zoom 1.25, alternated in the same way.  Then the validation pass (Trainer.evaluate) over the whole set.  One JSON
-line per (shape, path, repeat).
+every image rotated by 30 degrees at zoom 1.25, alternated in the same way.  A fifth leg, "elastic", is Trainer.step_elastic with the
+warped leg's settings plus a 5 x 5 lattice (2 spline cells, sigma 4 pixels) on every image.  Then the validation pass
+(Trainer.evaluate) over the whole set.  One JSON line per (shape, path, repeat).  --paths picks the legs (for a profile of one of them).
 
     python tools/bench_trainset.py [--steps 30] [--warmup 5] [--repeats 3] [--shapes nucleiDAPI,v2-256]
+                                   [--paths step_sampled,augmented,warped,elastic,host_fed,evaluate]
 """
 import argparse
 import json
@@ -68,7 +70,12 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--shapes", default="nucleiDAPI,v2-256")
     ap.add_argument("--samples", type=int, default=32)
+    ap.add_argument("--paths", default="step_sampled,augmented,warped,elastic,host_fed,evaluate")
     a = ap.parse_args()
+    paths = a.paths.split(",")
+    unknown = set(paths) - {"step_sampled", "augmented", "warped", "elastic", "host_fed", "evaluate"}
+    if unknown:
+        raise SystemExit("unknown path(s) %s" % sorted(unknown))
     for name, hp, B, opts, lw, mb, mc in shapes(a.shapes.split(",")):
         P, S, pages = hp.imSize, hp.imSize + hp.imSize // 4, 2
         rng = np.random.default_rng(0)
@@ -83,6 +90,11 @@ def main():
         worst["blur_level"], worst["gain"] = 3, 2.0
         turned = np.zeros(B, trainer.WARP_DESC)
         turned["m"] = trainset.warp_matrix(30.0, 1.25)
+        bent = np.zeros(B, trainer.ELASTIC_DESC)
+        bent["n"] = 5
+        lrng = np.random.default_rng(2)
+        for j in range(B):
+            bent["d"][j] = trainset.elastic_lattice(lrng.standard_normal(50), 4.0, 5)
         sampler = trainset.Sampler(1, a.samples, B, S, P, pages, mb, mc, transforms=True)
         per_step = B * P * P * (hp.nChannels + (2 if lw.weighted else 1) * hp.nClasses) * 4
 
@@ -107,26 +119,33 @@ def main():
                 tr.loss()
             return time.perf_counter() - t0
 
+        def run_elastic(n):
+            t0 = time.perf_counter()
+            for _ in range(n):
+                tr.step_elastic(ts, sampler.next(), worst, turned, bent)
+                tr.loss()
+            return time.perf_counter() - t0
+
         def run_host(n):
             t0 = time.perf_counter()
             for _ in range(n):
                 tr.step(*host_batch(planes, ann, wmaps, sampler.next(), P, hp.nClasses, lw))
             return time.perf_counter() - t0
 
-        run_sampled(a.warmup)
-        run_augmented(a.warmup)
-        run_warped(a.warmup)
-        run_host(a.warmup)
+        legs = [(path, fn) for path, fn in (("step_sampled", run_sampled), ("augmented", run_augmented), ("warped", run_warped),
+                                            ("elastic", run_elastic), ("host_fed", run_host)) if path in paths]
+        for _, fn in legs:
+            fn(a.warmup)
         for r in range(a.repeats):
-            for path, fn in (("step_sampled", run_sampled), ("augmented", run_augmented), ("warped", run_warped),
-                             ("host_fed", run_host)):
+            for path, fn in legs:
                 dt = fn(a.steps)
                 print(json.dumps({"shape": name, "batch": B, "path": path, "repeat": r, "steps": a.steps, "seconds": round(dt, 5),
                                   "images_per_s": round(a.steps * B / dt, 1), "step_ms": round(1e3 * dt / a.steps, 4),
                                   "host_fed_upload_bytes_per_step": per_step}), flush=True)
         vd = trainset.validation_descriptors(a.samples, S, P)
-        tr.evaluate(ts, vd)
-        for r in range(a.repeats):
+        if "evaluate" in paths:
+            tr.evaluate(ts, vd)
+        for r in range(a.repeats if "evaluate" in paths else 0):
             t0 = time.perf_counter()
             ev = tr.evaluate(ts, vd)
             dt = time.perf_counter() - t0

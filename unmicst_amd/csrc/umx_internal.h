@@ -396,6 +396,17 @@ hipError_t launch_assemble_augmented(const TrainSetView& ts, const AugChunk& ac,
 // transform and jitter as above, and their labels / weights (null: none) from the nearest source pixel.  Needs ts.S >= 2.
 hipError_t launch_assemble_warped(const TrainSetView& ts, const AugChunk& ac, int m, int P, int K, float mean, float std, float* data,
                                   float* labels, float* weights, hipStream_t stream);
+// the same for images with an elastic deformation (umx_elastic_desc, n != 0): the lattice rides behind the image's other arguments;
+// im.m is always read (the identity for an image without a rotation / zoom).  Needs ts.S >= 2 and P >= 2.
+constexpr int kElasticChunk = 8;       // such images per launch (passed by value: 3.2 KiB of the 4 KiB a launch may carry)
+struct ElasticImage {
+    AugImage a;
+    int n;                             // lattice points per axis, 4..6
+    float d[2][UMX_ELASTIC_MAX_GRID][UMX_ELASTIC_MAX_GRID];
+};
+struct ElasticChunk { ElasticImage im[kElasticChunk]; };
+hipError_t launch_assemble_elastic(const TrainSetView& ts, const ElasticChunk& ec, int m, int P, int K, float mean, float std, float* data,
+                                   float* labels, float* weights, hipStream_t stream);
 // counts [2K] int64 (correct | labelled) and loss [1] double over npix pixels of probs / labels [npix, K]; part: class_counts_parts(npix)
 // doubles of workspace
 size_t class_counts_parts(size_t npix, int K);

@@ -1,5 +1,5 @@
 // libumx device-resident training set: storage, the two kernels that feed the training step from it, and the C ABI of the
-// umx_trainset_* / umx_train_step_sampled / _augmented / _warped / umx_trainer_assemble / _augmented / _warped /
+// umx_trainset_* / umx_train_step_sampled / _augmented / _warped / _elastic / umx_trainer_assemble / _augmented / _warped / _elastic /
 // umx_trainer_evaluate entries of include/umx_train.h.
 //
 // The set is the reference's annotated layout (I%05d_Img.tif pages, _Ant.tif class codes, _wt.tif contour-intersection map;
@@ -14,6 +14,9 @@
 //   assemble_augmented_kernel<true>  the same for the images with a rotation / zoom (umx_warp_desc): the window is resampled
 //                          (mirror fold, bilinear, float64 in a fixed order) instead of copied
 //   assemble_warped_labels_kernel  their labels and weights, from the nearest source pixel
+//   assemble_augmented_kernel<true, true>  the images with an elastic deformation (umx_elastic_desc): the B-spline displacement of the
+//                          lattice is added to the pixel's coordinate in front of the warp matrix; one resampling
+//   assemble_elastic_labels_kernel  their labels and weights, from the nearest source pixel
 //   class_counts_kernel    per block: correct / labelled per class (int64) and sum of -log p[label] (float64), fixed order;
 //   class_counts_final     one block sums the block partials in a fixed order
 #include "../../include/umx_train.h"
@@ -36,6 +39,11 @@ static_assert(sizeof(umx_augment_table) == 12 + 16 * 4 + 16 * 13 * 4 + 5 * 4, "u
 static_assert(sizeof(AugChunk) <= 2048, "a chunk of augmented images travels as kernel arguments");
 static_assert(sizeof(umx_warp_desc) == 16, "umx_warp_desc is 16 bytes");
 static_assert(sizeof(AugImage) == 112, "an augmented image is 112 bytes of kernel arguments");
+static_assert(sizeof(umx_elastic_desc) == 304, "umx_elastic_desc is 304 bytes");
+static_assert(sizeof(ElasticImage) == 404, "an elastic image is 404 bytes of kernel arguments");
+// the widest launch: TrainSetView, the chunk, P, K (or mean, std) and up to two pointers -- inside the 4 KB of arguments a launch may carry
+static_assert(sizeof(TrainSetView) + sizeof(ElasticChunk) + 2 * sizeof(float) + 8 + 2 * sizeof(void*) <= 4096,
+              "a chunk of elastic images travels as kernel arguments");
 
 struct umx_trainset {
     umx_trainer* tr = nullptr;
@@ -174,19 +182,71 @@ __device__ inline int warp_nearest(double t, int S) {
     return min(max((int)(t + 0.5), 0), S - 1);
 }
 
+// six times the uniform cubic B-spline's weights at integer coordinate t of an axis of the crop's grid (recipe 0a of umx_elastic_desc):
+// n - 3 spline cells across 0 .. P-1, a coordinate outside the crop clamped to its edge.  *i0: the first of the 4 lattice points.
+__device__ inline void elastic_weights(int t, int P, int n, double* W, int* i0) {
+#pragma clang fp contract(off)
+    const double tc = (double)min(max(t, 0), P - 1);
+    const double scale = (double)(n - 3) / (double)(P - 1);
+    const double u = tc * scale;
+    const int i = min(max((int)u, 0), n - 4);   // (u >= 0: truncation is floor; the lower clamp is for a NaN)
+    const double f = u - (double)i;
+    const double g = 1.0 - f, f2 = f * f, f3 = f2 * f;
+    W[0] = (g * g) * g;
+    W[1] = (3.0 * f3 - 6.0 * f2) + 4.0;
+    W[2] = ((-3.0 * f3 + 3.0 * f2) + 3.0 * f) + 1.0;
+    W[3] = f3;
+    *i0 = i;
+}
+
+// one component of the displacement (recipe 0b): D the component's 6 x 6 lattice, along the lattice rows first, then between them
+__device__ inline double elastic_disp(const double* D, const double* Wy, int iy, const double* Wx, int ix) {
+#pragma clang fp contract(off)
+    double row[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const double* r = D + (iy + a) * UMX_ELASTIC_MAX_GRID + ix;
+        row[a] = ((Wx[0] * r[0] + Wx[1] * r[1]) + Wx[2] * r[2]) + Wx[3] * r[3];
+    }
+    return (((Wy[0] * row[0] + Wy[1] * row[1]) + Wy[2] * row[2]) + Wy[3] * row[3]) / 36.0;
+}
+
+// warp_source for a pixel displaced by (ey, ex) on the crop's own grid (recipe 1')
+__device__ inline void elastic_source(const float* m, int y, int x, double ey, double ex, int P, int y0, int x0, int S, double* ty,
+                                      double* tx) {
+#pragma clang fp contract(off)
+    const double c = 0.5 * (double)(P - 1);
+    const double dy = ((double)y + ey) - c, dx = ((double)x + ex) - c;
+    *ty = warp_fold(((double)m[0] * dy + (double)m[1] * dx) + ((double)y0 + c), S);
+    *tx = warp_fold(((double)m[2] * dy + (double)m[3] * dx) + ((double)x0 + c), S);
+}
+
+// the kernels' argument types: an image's lattice rides behind its AugImage
+template <bool kElastic> struct ChunkOf { using type = AugChunk; };
+template <> struct ChunkOf<true> { using type = ElasticChunk; };
+__device__ inline const AugImage& aug_image(const AugChunk& c, unsigned j) { return c.im[j]; }
+__device__ inline const AugImage& aug_image(const ElasticChunk& c, unsigned j) { return c.im[j].a; }
+
 // one workgroup per (32 x 32 tile of the crop, channel, image).  The (32 + 2R)^2 source window goes to LDS with both coordinates
 // clamped to the sample, so a crop at the sample's edge sees the replicated edge and a crop inside it its real neighbours; the row pass
 // writes `hor` (float32, the rounding the recipe asks for), the column pass reads it.  A wave owns one row of the tile -- or, under a
 // transform that swaps the axes, one column, so that its 32 stores are neighbours in the NHWC output either way.
 // kWarp: every window element is resampled from the plane instead (im.m: rotation and zoom about the crop's centre).  The warped
 // image exists at every integer coordinate, so the window needs no clamp; without a blur each thread resamples its own pixel.
-template <bool kWarp>
-__global__ void __launch_bounds__(256) assemble_augmented_kernel(TrainSetView ts, AugChunk ac, int P, float mean, float std,
-                                                                 float* __restrict__ data) {
+// kElastic (with kWarp): the source coordinate of a window element also takes the lattice's displacement.  The spline weights depend on
+// the integer coordinate alone, so the workgroup computes those of its window's rows and of its columns once (2 (32 + 2R) sets), next to
+// the lattice as float64, and an element combines them with 16 lattice values per component.
+template <bool kWarp, bool kElastic = false>
+__global__ void __launch_bounds__(256) assemble_augmented_kernel(TrainSetView ts, typename ChunkOf<kElastic>::type ac, int P, float mean,
+                                                                 float std, float* __restrict__ data) {
+    static_assert(kWarp || !kElastic, "the elastic displacement is a term of the warp's source coordinate");
     __shared__ float win[kAugWin * kAugWin];
     __shared__ float hor[kAugWin * kAugHStride];
     __shared__ double w64[UMX_AUGMENT_MAX_RADIUS + 1];
-    const AugImage& im = ac.im[blockIdx.z];
+    __shared__ double lat64[kElastic ? 2 * UMX_ELASTIC_MAX_GRID * UMX_ELASTIC_MAX_GRID : 1];
+    __shared__ double ew64[kElastic ? 2 * kAugWin * 4 : 1];   // [axis][window row resp. column][4]
+    __shared__ int ei[kElastic ? 2 * kAugWin : 1];            // the first lattice point of each
+    const AugImage& im = aug_image(ac, blockIdx.z);
     const umx_sample_desc d = im.d;
     const int c = blockIdx.y;
     const int tiles = (P + kAugTile - 1) / kAugTile;
@@ -195,11 +255,39 @@ __global__ void __launch_bounds__(256) assemble_augmented_kernel(TrainSetView ts
     const int R = im.R;
     const bool swap = (d.transform & 4) != 0;
     const float* src = ts.planes + (((size_t)d.index * ts.C + c) * ts.pages + d.page) * ((size_t)ts.S * ts.row_f);
+    [[maybe_unused]] const int halo = R >= 0 ? R : 0;    // (the elastic tables: window element (r, q) is pixel (cy0 - halo + r, cx0 - halo + q))
+    if constexpr (kElastic) {
+        const ElasticImage& el = ac.im[blockIdx.z];
+        const int W = kAugTile + 2 * halo;
+        const int n = min(max(el.n, 4), UMX_ELASTIC_MAX_GRID);
+        constexpr int kLat = 2 * UMX_ELASTIC_MAX_GRID * UMX_ELASTIC_MAX_GRID;
+        if ((int)threadIdx.x < kLat) lat64[threadIdx.x] = (double)(&el.d[0][0][0])[threadIdx.x];
+        if ((int)threadIdx.x < 2 * W) {
+            const int axis = (int)threadIdx.x >= W, r = (int)threadIdx.x - axis * W;
+            elastic_weights((axis ? cx0 : cy0) - halo + r, P, n, &ew64[(axis * kAugWin + r) * 4], &ei[axis * kAugWin + r]);
+        }
+        __syncthreads();
+    }
+    // the source of window element (r, q) under the lattice, from the tables above
+    [[maybe_unused]] auto displaced = [&](int r, int q, double* ty, double* tx) {
+        if constexpr (kElastic) {
+            const double* wy = &ew64[r * 4];
+            const double* wx = &ew64[(kAugWin + q) * 4];
+            const int iy = ei[r], ix = ei[kAugWin + q];
+            const double ey = elastic_disp(lat64, wy, iy, wx, ix);
+            const double ex = elastic_disp(lat64 + UMX_ELASTIC_MAX_GRID * UMX_ELASTIC_MAX_GRID, wy, iy, wx, ix);
+            elastic_source(im.m, cy0 - halo + r, cx0 - halo + q, ey, ex, P, d.y0, d.x0, ts.S, ty, tx);
+        }
+    };
     if (R >= 0) {
         const int W = kAugTile + 2 * R;
         for (int r = grp; r < W; r += 8) {
             for (int q = lane; q < W; q += 32) {
-                if constexpr (kWarp) {
+                if constexpr (kElastic) {
+                    double ty, tx;
+                    displaced(r, q, &ty, &tx);
+                    win[r * W + q] = warp_bilinear(src, ts.row_f, ts.S, ty, tx);
+                } else if constexpr (kWarp) {
                     double ty, tx;
                     warp_source(im.m, cy0 - R + r, cx0 - R + q, P, d.y0, d.x0, ts.S, &ty, &tx);
                     win[r * W + q] = warp_bilinear(src, ts.row_f, ts.S, ty, tx);
@@ -223,6 +311,10 @@ __global__ void __launch_bounds__(256) assemble_augmented_kernel(TrainSetView ts
         float v;
         if (R >= 0) {
             v = blur_taps(&hor[yy * kAugHStride + xx], kAugHStride, R, w64);
+        } else if constexpr (kElastic) {
+            double ty, tx;
+            displaced(yy, xx, &ty, &tx);
+            v = warp_bilinear(src, ts.row_f, ts.S, ty, tx);
         } else if constexpr (kWarp) {
             double ty, tx;
             warp_source(im.m, cy, cx, P, d.y0, d.x0, ts.S, &ty, &tx);
@@ -253,6 +345,40 @@ __global__ void __launch_bounds__(256) assemble_warped_labels_kernel(TrainSetVie
     const int v = (d.transform & 1) ? P - 1 - x : x;
     double ty, tx;
     warp_source(im.m, (d.transform & 4) ? v : u, (d.transform & 4) ? u : v, P, d.y0, d.x0, ts.S, &ty, &tx);
+    const int sy = warp_nearest(ty, ts.S), sx = warp_nearest(tx, ts.S);
+    const size_t o = ((size_t)im.row * P * P + pix) * K;
+    const int code = ts.ann[((size_t)d.index * ts.S + sy) * ts.row_a + sx];
+    for (int k = 0; k < K; ++k) labels[o + k] = code == k + 1 ? 1.f : 0.f;
+    if (weights) {
+        const double w = (double)ts.wmap[((size_t)d.index * ts.S + sy) * ts.row_f + sx];
+        for (int k = 0; k < K; ++k) weights[o + k] = mul_add_f64_rn((double)ts.iw[k], w, (double)ts.cw[k]);
+    }
+}
+
+// the same for the images with an elastic deformation: the pixel's place in the crop is displaced by its lattice first.  A thread
+// computes the spline weights of its own row and column (once per pixel here, not once per window element and channel).
+__global__ void __launch_bounds__(256) assemble_elastic_labels_kernel(TrainSetView ts, ElasticChunk ec, int P, int K,
+                                                                      float* __restrict__ labels, float* __restrict__ weights) {
+    __shared__ double lat64[2 * UMX_ELASTIC_MAX_GRID * UMX_ELASTIC_MAX_GRID];
+    const ElasticImage& el = ec.im[blockIdx.y];
+    const AugImage& im = el.a;
+    if ((int)threadIdx.x < 2 * UMX_ELASTIC_MAX_GRID * UMX_ELASTIC_MAX_GRID) lat64[threadIdx.x] = (double)(&el.d[0][0][0])[threadIdx.x];
+    __syncthreads();
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= P * P) return;
+    const umx_sample_desc d = im.d;
+    const int n = min(max(el.n, 4), UMX_ELASTIC_MAX_GRID);
+    const int y = pix / P, x = pix - (pix / P) * P;
+    const int u = (d.transform & 2) ? P - 1 - y : y;
+    const int v = (d.transform & 1) ? P - 1 - x : x;
+    const int cy = (d.transform & 4) ? v : u, cx = (d.transform & 4) ? u : v;
+    double wy[4], wx[4], ty, tx;
+    int iy, ix;
+    elastic_weights(cy, P, n, wy, &iy);
+    elastic_weights(cx, P, n, wx, &ix);
+    const double ey = elastic_disp(lat64, wy, iy, wx, ix);
+    const double ex = elastic_disp(lat64 + UMX_ELASTIC_MAX_GRID * UMX_ELASTIC_MAX_GRID, wy, iy, wx, ix);
+    elastic_source(im.m, cy, cx, ey, ex, P, d.y0, d.x0, ts.S, &ty, &tx);
     const int sy = warp_nearest(ty, ts.S), sx = warp_nearest(tx, ts.S);
     const size_t o = ((size_t)im.row * P * P + pix) * K;
     const int code = ts.ann[((size_t)d.index * ts.S + sy) * ts.row_a + sx];
@@ -370,6 +496,21 @@ hipError_t launch_assemble_warped(const TrainSetView& ts, const AugChunk& ac, in
     return hipGetLastError();
 }
 
+hipError_t launch_assemble_elastic(const TrainSetView& ts, const ElasticChunk& ec, int m, int P, int K, float mean, float std, float* data,
+                                   float* labels, float* weights, hipStream_t stream) {
+    if (m < 1 || m > kElasticChunk || P < 2 || K < 1 || K > 8 || ts.S < 2) return hipErrorInvalidValue;   // (P = 1 has no spline cell)
+    for (int j = 0; j < m; ++j) {
+        if (ec.im[j].a.R < -1 || ec.im[j].a.R > UMX_AUGMENT_MAX_RADIUS) return hipErrorInvalidValue;
+        if (ec.im[j].n < 4 || ec.im[j].n > UMX_ELASTIC_MAX_GRID) return hipErrorInvalidValue;             // (the LDS lattice is 6 x 6)
+    }
+    const unsigned tiles = (unsigned)((P + kAugTile - 1) / kAugTile);
+    hipLaunchKernelGGL((assemble_augmented_kernel<true, true>), dim3(tiles * tiles, (unsigned)ts.C, (unsigned)m), dim3(256), 0, stream, ts,
+                       ec, P, mean, std, data);
+    hipLaunchKernelGGL(assemble_elastic_labels_kernel, dim3((unsigned)((P * P + 255) / 256), (unsigned)m), dim3(256), 0, stream, ts, ec, P,
+                       K, labels, weights);
+    return hipGetLastError();
+}
+
 size_t class_counts_parts(size_t npix, int K) { return (size_t)count_blocks(npix) * (2 * K + 1); }
 
 hipError_t launch_class_counts(const float* probs, const float* labels, size_t npix, int K, double* part, long long* counts,
@@ -471,8 +612,9 @@ int enqueue_assemble(umx_trainer* tr, const umx_trainset* ts, const umx_sample_d
     return UMX_OK;
 }
 
-// which entry a batch came in by: plain descriptors, + umx_augment_desc, + umx_warp_desc (there aug may be null: no blur, gain 1)
-enum Entry { kSampled, kAugmented, kWarped };
+// which entry a batch came in by: plain descriptors, + umx_augment_desc, + umx_warp_desc (there aug may be null: no blur, gain 1),
+// + umx_elastic_desc (there warp may be null too: the identity)
+enum Entry { kSampled, kAugmented, kWarped, kElastic };
 
 // the parallel array of umx_augment_desc, checked like the descriptors: before anything is enqueued
 int check_augs(umx_trainer* tr, const umx_trainset* ts, const umx_augment_desc* aug, int n, const char* what) {
@@ -500,39 +642,65 @@ int check_warps(umx_trainer* tr, const umx_trainset* ts, const umx_warp_desc* wa
     return UMX_OK;
 }
 
-// the checks of an entry, in the order descriptors, augmentations, warps; nothing is enqueued before all of them pass
+// the parallel array of umx_elastic_desc, likewise
+int check_elastics(umx_trainer* tr, const umx_trainset* ts, const umx_elastic_desc* elastic, int n, const char* what) {
+    if (!elastic) return tsfail(tr, UMX_ERR_INVALID, "null argument");
+    if (ts->S < 2) return tsfail(tr, UMX_ERR_INVALID, "%s: a sample of one pixel cannot be deformed", what);
+    char why[160];
+    if (umx_elastic_desc_check(elastic, n, why, sizeof why) != UMX_OK) return tsfail(tr, UMX_ERR_INVALID, "%s: %s", what, why);
+    return UMX_OK;
+}
+
+// the checks of an entry, in the order descriptors, augmentations, warps, lattices; nothing is enqueued before all of them pass
 int check_batch(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug, const umx_warp_desc* warp,
-                Entry entry, int n, int n_max, const char* what) {
+                const umx_elastic_desc* elastic, Entry entry, int n, int n_max, const char* what) {
     TS_TRY(check_descs(tr, ts, desc, n, n_max, what));
-    if (entry == kAugmented || (entry == kWarped && aug)) TS_TRY(check_augs(tr, ts, aug, n, what));
-    if (entry == kWarped) TS_TRY(check_warps(tr, ts, warp, n, what));
+    if (entry == kAugmented || ((entry == kWarped || entry == kElastic) && aug)) TS_TRY(check_augs(tr, ts, aug, n, what));
+    if (entry == kWarped || (entry == kElastic && warp)) TS_TRY(check_warps(tr, ts, warp, n, what));
+    if (entry == kElastic) TS_TRY(check_elastics(tr, ts, elastic, n, what));
     return UMX_OK;
 }
 
 // enqueue_assemble for every image (labels, weights and the plain data: today's path), then, on the same stream, the images that ask
 // for more written over it, 16 per launch: the data planes of those with a blur level or a gain (aug, may be null), and data, labels
 // and weights of those with a warp other than the identity (warp, may be null).  An image with (level 0, gain 1, identity) is never
-// touched again, and one with the identity never meets the warp code.
+// touched again, and one with the identity never meets the warp code.  The images with a lattice (elastic, may be null; n != 0) go,
+// 8 per launch, to the elastic instances instead -- with the identity matrix where they have no warp -- and the others never meet those.
 int enqueue_batch(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
-                  const umx_warp_desc* warp, int n, bool weights) {
+                  const umx_warp_desc* warp, const umx_elastic_desc* elastic, int n, bool weights) {
     TS_TRY(enqueue_assemble(tr, ts, desc, n, weights));
-    if (!aug && !warp) return UMX_OK;
+    if (!aug && !warp && !elastic) return UMX_OK;
     const TrainerIO io = trainer_io(tr);
     const TrainSetView v = view_of(ts);
     const float mean = ts->has_aug ? ts->aug.mean : 0.f, std = ts->has_aug ? ts->aug.std : 1.f;   // (read only when a gain != 1)
     AugChunk chunk[2];   // [0] blur / gain only, [1] warped
     int m[2] = {0, 0};
     memset(chunk, 0, sizeof chunk);
+    ElasticChunk ec;
+    int me = 0;
+    memset(&ec, 0, sizeof ec);
     for (int i = 0; i < n; ++i) {
+        const bool deformed = elastic && elastic[i].n != 0;
         const bool warped = warp && !warp_is_identity(warp[i]);
-        if (warped || (aug && (aug[i].blur_level != 0 || aug[i].gain != 1.f))) {
-            AugImage& im = chunk[warped].im[m[warped]++];
+        if (deformed || warped || (aug && (aug[i].blur_level != 0 || aug[i].gain != 1.f))) {
+            if (deformed) {
+                ec.im[me].n = elastic[i].n;
+                memcpy(ec.im[me].d, elastic[i].d, sizeof ec.im[me].d);
+            }
+            AugImage& im = deformed ? ec.im[me++].a : chunk[warped].im[m[warped]++];
             im.d = desc[i];
             im.row = i;
             im.gain = aug ? aug[i].gain : 1.f;
             im.R = !aug || aug[i].blur_level == 0 ? -1 : ts->aug.radius[aug[i].blur_level];
             if (im.R >= 0) memcpy(im.taps, ts->aug.taps[aug[i].blur_level], sizeof im.taps);
             if (warped) memcpy(im.m, warp[i].m, sizeof im.m);
+            else if (deformed) im.m[0] = im.m[3] = 1.f;
+        }
+        if (me == kElasticChunk || (me > 0 && i == n - 1)) {
+            TS_HIP(tr, launch_assemble_elastic(v, ec, me, io.P, io.K, mean, std, io.data, io.labels, weights ? io.weights : nullptr,
+                                               io.stream));
+            memset(&ec, 0, sizeof ec);
+            me = 0;
         }
         for (int k = 0; k < 2; ++k)
             if (m[k] == kAugChunk || (m[k] > 0 && i == n - 1)) {
@@ -547,29 +715,30 @@ int enqueue_batch(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc
     return UMX_OK;
 }
 
-// umx_train_step_sampled / _augmented / _warped
+// umx_train_step_sampled / _augmented / _warped / _elastic
 int step_from_set(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
-                  const umx_warp_desc* warp, Entry entry, int apply_update, const char* what) {
+                  const umx_warp_desc* warp, const umx_elastic_desc* elastic, Entry entry, int apply_update, const char* what) {
     if (!tr) return tsfail(nullptr, UMX_ERR_INVALID, "null trainer");
     const TrainerIO io = trainer_io(tr);
-    TS_TRY(check_batch(tr, ts, desc, aug, warp, entry, io.B, io.B, what));
+    TS_TRY(check_batch(tr, ts, desc, aug, warp, elastic, entry, io.B, io.B, what));
     TS_HIP(tr, hipSetDevice(io.device));
-    TS_TRY(enqueue_batch(tr, ts, desc, aug, warp, io.B, ts->weighted));
+    TS_TRY(enqueue_batch(tr, ts, desc, aug, warp, elastic, io.B, ts->weighted));
     TS_TRY(umx_train_step_dev(tr, io.data, io.labels, ts->weighted ? io.weights : nullptr, apply_update));   // (checks the trainer's zones)
     std::string msg;
     const int rc = arena_check(ts->mem, &msg);
     return rc == UMX_OK ? UMX_OK : tsfail(tr, rc, "%s", msg.c_str());
 }
 
-// umx_trainer_assemble / _augmented / _warped
+// umx_trainer_assemble / _augmented / _warped / _elastic
 int assemble_to_host(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
-                     const umx_warp_desc* warp, Entry entry, int n, float* data, float* labels, float* weights, const char* what) {
+                     const umx_warp_desc* warp, const umx_elastic_desc* elastic, Entry entry, int n, float* data, float* labels,
+                     float* weights, const char* what) {
     if (!tr) return tsfail(nullptr, UMX_ERR_INVALID, "null trainer");
     const TrainerIO io = trainer_io(tr);
-    TS_TRY(check_batch(tr, ts, desc, aug, warp, entry, n, io.B, what));
+    TS_TRY(check_batch(tr, ts, desc, aug, warp, elastic, entry, n, io.B, what));
     if (!data || !labels) return tsfail(tr, UMX_ERR_INVALID, "null argument");
     TS_HIP(tr, hipSetDevice(io.device));
-    TS_TRY(enqueue_batch(tr, ts, desc, aug, warp, n, ts->weighted));
+    TS_TRY(enqueue_batch(tr, ts, desc, aug, warp, elastic, n, ts->weighted));
     const size_t npx = (size_t)n * io.P * io.P;
     TS_HIP(tr, hipMemcpyAsync(data, io.data, npx * io.C * sizeof(float), hipMemcpyDeviceToHost, io.stream));
     TS_HIP(tr, hipMemcpyAsync(labels, io.labels, npx * io.K * sizeof(float), hipMemcpyDeviceToHost, io.stream));
@@ -669,32 +838,65 @@ void umx_trainset_destroy(umx_trainset* ts) {
 }
 
 int umx_train_step_sampled(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, int apply_update) {
-    return step_from_set(tr, ts, desc, nullptr, nullptr, kSampled, apply_update, "umx_train_step_sampled");
+    return step_from_set(tr, ts, desc, nullptr, nullptr, nullptr, kSampled, apply_update, "umx_train_step_sampled");
 }
 
 int umx_train_step_augmented(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
                              int apply_update) {
-    return step_from_set(tr, ts, desc, aug, nullptr, kAugmented, apply_update, "umx_train_step_augmented");
+    return step_from_set(tr, ts, desc, aug, nullptr, nullptr, kAugmented, apply_update, "umx_train_step_augmented");
 }
 
 int umx_train_step_warped(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
                           const umx_warp_desc* warp, int apply_update) {
-    return step_from_set(tr, ts, desc, aug, warp, kWarped, apply_update, "umx_train_step_warped");
+    return step_from_set(tr, ts, desc, aug, warp, nullptr, kWarped, apply_update, "umx_train_step_warped");
 }
 
 int umx_trainer_assemble(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, int n, float* data, float* labels,
                          float* weights) {
-    return assemble_to_host(tr, ts, desc, nullptr, nullptr, kSampled, n, data, labels, weights, "umx_trainer_assemble");
+    return assemble_to_host(tr, ts, desc, nullptr, nullptr, nullptr, kSampled, n, data, labels, weights, "umx_trainer_assemble");
 }
 
 int umx_trainer_assemble_augmented(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
                                    int n, float* data, float* labels, float* weights) {
-    return assemble_to_host(tr, ts, desc, aug, nullptr, kAugmented, n, data, labels, weights, "umx_trainer_assemble_augmented");
+    return assemble_to_host(tr, ts, desc, aug, nullptr, nullptr, kAugmented, n, data, labels, weights, "umx_trainer_assemble_augmented");
 }
 
 int umx_trainer_assemble_warped(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
                                 const umx_warp_desc* warp, int n, float* data, float* labels, float* weights) {
-    return assemble_to_host(tr, ts, desc, aug, warp, kWarped, n, data, labels, weights, "umx_trainer_assemble_warped");
+    return assemble_to_host(tr, ts, desc, aug, warp, nullptr, kWarped, n, data, labels, weights, "umx_trainer_assemble_warped");
+}
+
+int umx_train_step_elastic(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
+                           const umx_warp_desc* warp, const umx_elastic_desc* elastic, int apply_update) {
+    return step_from_set(tr, ts, desc, aug, warp, elastic, kElastic, apply_update, "umx_train_step_elastic");
+}
+
+int umx_trainer_assemble_elastic(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
+                                 const umx_warp_desc* warp, const umx_elastic_desc* elastic, int n, float* data, float* labels,
+                                 float* weights) {
+    return assemble_to_host(tr, ts, desc, aug, warp, elastic, kElastic, n, data, labels, weights, "umx_trainer_assemble_elastic");
+}
+
+int umx_elastic_desc_check(const umx_elastic_desc* e, int n_desc, char* msg, size_t cap) {
+    char buf[160] = "";
+    if (!e) snprintf(buf, sizeof buf, "null elastic descriptors");
+    for (int i = 0; !buf[0] && i < n_desc; ++i) {
+        const int n = e[i].n;
+        const char* why = nullptr;
+        if (n != 0 && (n < 4 || n > UMX_ELASTIC_MAX_GRID)) why = "n is not 0 or 4..6";
+        else if (e[i].reserved[0] || e[i].reserved[1] || e[i].reserved[2]) why = "reserved field not zero";
+        for (int k = 0; k < 2 && !why; ++k)
+            for (int a = 0; a < UMX_ELASTIC_MAX_GRID && !why; ++a)
+                for (int b = 0; b < UMX_ELASTIC_MAX_GRID && !why; ++b) {
+                    const float v = e[i].d[k][a][b];
+                    if (!std::isfinite(v)) why = "an entry is not finite";
+                    else if (std::fabs(v) > UMX_ELASTIC_MAX_DISP) why = "an entry is above 32 pixels in magnitude";
+                    else if ((a >= n || b >= n) && v != 0.f) why = "a non-zero entry outside the n x n block";
+                }
+        if (why) snprintf(buf, sizeof buf, "elastic %d (n %d): %s", i, n, why);
+    }
+    if (msg && cap) snprintf(msg, cap, "%s", buf);
+    return buf[0] ? UMX_ERR_INVALID : UMX_OK;
 }
 
 int umx_warp_desc_check(const umx_warp_desc* warp, int n, char* msg, size_t cap) {

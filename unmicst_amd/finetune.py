@@ -4,6 +4,7 @@
                                    [--eval-every E] [--seed S] [--lr0 LR] [--transforms] [--device D]
                                    [--blur-sigmas 0.75,1.5,3] [--blur-prob P] [--saturate-prob P] [--max-gain G]
                                    [--rotate-prob P] [--zoom-prob P] [--zoom-range LO,HI]
+                                   [--elastic-sigma PX] [--elastic-prob P] [--elastic-grid G]
                                    [--from-scratch [--init-seed S] [--std-dev0 V] [--mean M --std S]]
 
 ``--train`` / ``--valid`` hold the reference's published layout (``I%05d_Img.tif`` / ``_Ant.tif`` / ``_wt.tif``, see
@@ -26,6 +27,15 @@ Rotation and zoom, the geometry a small set of ``imSize``-wide samples cannot ge
 ``--zoom-range LO,HI`` (``0.5 <= LO <= 1 <= HI <= 2``).  Data is resampled bilinearly and mirrored at the sample's edges; labels and
 weight maps take the nearest source pixel (``Trainer.step_warped``).  Validation stays unwarped.  When one of the three flags is given,
 the log's first line carries the settings as its ``"warp"`` object (next to ``"augment"`` when both are on).
+
+Elastic deformation, the one augmentation here that changes a nucleus's shape: ``--elastic-sigma PX`` is the standard deviation of the
+displacement vectors on a lattice of ``--elastic-grid G`` (1..3, default 2) spline cells across the tile, drawn on the host and clipped
+at two sigmas; ``--elastic-prob`` (0.5 when a sigma is given) is the chance that an image gets one.  A uniform cubic B-spline spreads
+the lattice over the crop on the device, and the displacement is added to the source coordinate of the rotation / zoom resampling, so
+data is still interpolated once and labels and weight maps still take the nearest source pixel (``Trainer.step_elastic``).  A sigma of
+``(imSize - 1) / (8 G)`` or more is refused: below it the deformation cannot fold the image over itself.  Validation stays undeformed.
+When one of the three flags is given, the log's first line carries the settings as its ``"elastic"`` object (after ``"init"``,
+``"augment"`` and ``"warp"``).
 
 ``--from-scratch`` starts from the graph's initial state instead of the model's weights (the reference's
 ``train(..., restoreVariables=False)``: ``tf.global_variables_initializer()``, made on the device by ``Trainer.from_scratch``; DESIGN.md
@@ -79,6 +89,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--rotate-prob", type=float, default=None, help="chance that an image is rotated by a uniform angle (default 0)")
     p.add_argument("--zoom-prob", type=float, default=None, help="chance that an image is magnified (default 0.5 with --zoom-range)")
     p.add_argument("--zoom-range", default=None, help="LO,HI: magnifications are drawn log-uniformly, 0.5 <= LO <= 1 <= HI <= 2")
+    p.add_argument("--elastic-sigma", type=float, default=None, help="standard deviation of a lattice displacement in pixels, > 0")
+    p.add_argument("--elastic-prob", type=float, default=None, help="chance that an image is deformed (default 0.5 with --elastic-sigma)")
+    p.add_argument("--elastic-grid", type=int, default=None, help="spline cells across the tile, 1..3 (default 2)")
     p.add_argument("--from-scratch", action="store_true", help="start from the graph's initial state, not from the model's weights")
     p.add_argument("--init-seed", type=int, default=None, help="seed of the initial state (default: --seed); needs --from-scratch")
     p.add_argument("--std-dev0", type=float, default=None,
@@ -147,6 +160,37 @@ def warp_settings(args):
     return {"rotate_prob": float(rot_prob), "zoom_prob": float(zoom_prob), "zoom_range": zr or [1.0, 1.0]}
 
 
+def elastic_settings(args, im_size=None):
+    """The three elastic flags -> None when none is given, else {"prob", "sigma", "grid"}.  ``im_size`` (the model's tile) adds the
+    bounds that depend on it; without it only the flags are checked.  Raises Refusal."""
+    given = [getattr(args, k, None) for k in ("elastic_sigma", "elastic_prob", "elastic_grid")]
+    if all(v is None for v in given):
+        return None
+    sigma = args.elastic_sigma
+    if sigma is not None and not (math.isfinite(sigma) and sigma > 0):
+        raise Refusal("--elastic-sigma %r: a standard deviation is finite and > 0" % sigma)
+    prob = (0.5 if sigma is not None else 0.0) if args.elastic_prob is None else args.elastic_prob
+    if not 0.0 <= prob <= 1.0:   # (a NaN fails both comparisons)
+        raise Refusal("--elastic-prob %r is not a probability" % prob)
+    if prob > 0 and sigma is None:
+        raise Refusal("--elastic-prob needs --elastic-sigma")
+    grid = 2 if args.elastic_grid is None else args.elastic_grid
+    if not 1 <= grid <= trainer.ELASTIC_MAX_GRID - 3:
+        raise Refusal("--elastic-grid %r: 1..%d spline cells across the tile" % (grid, trainer.ELASTIC_MAX_GRID - 3))
+    sigma = 0.0 if sigma is None else float(sigma)
+    if im_size is not None and sigma > 0:
+        # lattice values are clipped at 2 sigma, so a partial derivative of the displacement is at most g = 4 sigma / h with
+        # h = (P - 1) / G; the map is invertible for certain while 1 - 2 g > 0
+        bound = (im_size - 1) / (8.0 * grid)
+        if sigma >= bound:
+            raise Refusal("--elastic-sigma %g: with %d cell(s) across a %d-pixel tile a sigma of %g or more may fold the image over itself"
+                          % (sigma, grid, im_size, bound))
+        if 2.0 * sigma > trainer.ELASTIC_MAX_DISP:
+            raise Refusal("--elastic-sigma %g: displacements are clipped at 2 sigma, which must stay within %g pixels"
+                          % (sigma, trainer.ELASTIC_MAX_DISP))
+    return {"prob": float(prob), "sigma": sigma, "grid": int(grid)}
+
+
 def augment_settings(args):
     """The four augmentation flags -> None when none is given, else {"blur_sigmas", "blur_prob", "saturate_prob", "max_gain"}.
     Raises Refusal."""
@@ -201,6 +245,7 @@ def prepare(args):
         raise Refusal("--steps, --eval-every and --pages must be positive, --batch non-negative")
     augment_settings(args)
     warp_settings(args)
+    elastic_settings(args)
     scratch = init_settings(args) is not None
     path = resolve_model(args.model)
     if not os.path.isdir(path):
@@ -224,6 +269,7 @@ def prepare(args):
         except FileNotFoundError as e:
             raise Refusal("model %s has no weights to fine-tune: %s" % (args.model, e))
     hp = art.hp
+    elastic_settings(args, hp.imSize)
     sets = []
     for what, d in (("--train", args.train), ("--valid", args.valid)):
         try:
@@ -242,6 +288,7 @@ def run(args) -> int:
     aug = augment_settings(args)
     warp = warp_settings(args)
     hp = art.hp
+    elastic = elastic_settings(args, hp.imSize)
     kind = trainset.graph_kind(hp)
     lw = trainset.LABEL_WEIGHTS[kind]
     init = init_settings(args, resolve_model(args.model))
@@ -264,6 +311,8 @@ def run(args) -> int:
                        max_gain=aug["max_gain"])
         if warp is not None:
             akw.update(rotate_prob=warp["rotate_prob"], zoom_prob=warp["zoom_prob"], zoom_range=tuple(warp["zoom_range"]))
+        if elastic is not None:
+            akw.update(elastic_prob=elastic["prob"], elastic_sigma=elastic["sigma"], elastic_grid=elastic["grid"])
         sampler = trainset.Sampler(args.seed, train_ds.n_samples, tr.batch, train_ds.size, hp.imSize, args.pages, mb, mc,
                                    transforms=args.transforms, **akw)
         vdesc = trainset.validation_descriptors(valid_ds.n_samples, valid_ds.size, hp.imSize)
@@ -272,7 +321,8 @@ def run(args) -> int:
         best = None
         train_loss = None
         with open(log_path, "w") as log:
-            settings = {k: v for k, v in (("init", init), ("augment", aug), ("warp", warp)) if v is not None}
+            settings = {k: v for k, v in (("init", init), ("augment", aug), ("warp", warp), ("elastic", elastic))
+                        if v is not None}
             if settings:
                 log.write(json.dumps(settings) + "\n")
             for step in range(args.steps + 1):
@@ -291,7 +341,10 @@ def run(args) -> int:
                         model.save_converted(model.ModelArtefacts(hp, tr.blob(), art.mean, art.std), args.out)
                 if step == args.steps:
                     break
-                if warp is not None:
+                if elastic is not None:
+                    d, a, w, e = sampler.next_elastic()
+                    tr.step_elastic(ts, d, None if aug is None else a, None if warp is None else w, e)
+                elif warp is not None:
                     d, a, w = sampler.next_warped()
                     tr.step_warped(ts, d, None if aug is None else a, w)
                 elif aug is None:

@@ -31,7 +31,8 @@ EXPORTS = [
     "umx_trainer_profile", "umx_trainset_create", "umx_trainset_set", "umx_trainset_destroy", "umx_train_step_sampled",
     "umx_trainer_assemble", "umx_trainer_evaluate", "umx_guard_scan", "umx_augment_table_check", "umx_trainset_set_augment",
     "umx_train_step_augmented", "umx_trainer_assemble_augmented", "umx_warp_desc_check", "umx_train_step_warped",
-    "umx_trainer_assemble_warped", "umx_trainer_init",
+    "umx_trainer_assemble_warped", "umx_trainer_init", "umx_elastic_desc_check", "umx_train_step_elastic",
+    "umx_trainer_assemble_elastic",
 ]
 
 
@@ -96,6 +97,11 @@ AUGMENT_MAX_LEVELS, AUGMENT_MAX_RADIUS = 16, 12
 
 # ``umx_warp_desc``: rotation and zoom of one image, parallel to its SAMPLE_DESC; (sy, sx) = M (y - c, x - c) + the crop's centre
 WARP_DESC = np.dtype([("m", "<f4", (4,))])
+
+# ``umx_elastic_desc``: the displacement lattice of one image, parallel to its SAMPLE_DESC, 304 bytes; n = 0 (no deformation) or 4..6
+# lattice points per axis, d[0] / d[1] the row / column displacements in pixels (zero outside the n x n block)
+ELASTIC_MAX_GRID, ELASTIC_MAX_DISP = 6, 32.0
+ELASTIC_DESC = np.dtype([("n", "<i4"), ("reserved", "<i4", (3,)), ("d", "<f4", (2, ELASTIC_MAX_GRID, ELASTIC_MAX_GRID))])
 
 
 class AugmentTableC(ctypes.Structure):
@@ -205,6 +211,13 @@ def _bind(L):
     L.umx_train_step_warped.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]
     L.umx_trainer_assemble_warped.restype = c_int
     L.umx_trainer_assemble_warped.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
+    # elastic deformation (umx_elastic_desc)
+    L.umx_elastic_desc_check.restype = c_int
+    L.umx_elastic_desc_check.argtypes = [c_void_p, c_int, ctypes.c_char_p, ctypes.c_size_t]
+    L.umx_train_step_elastic.restype = c_int
+    L.umx_train_step_elastic.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]
+    L.umx_trainer_assemble_elastic.restype = c_int
+    L.umx_trainer_assemble_elastic.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
     # debug guard mode (UMX_DEBUG_GUARD): the host scan of one red zone
     L.umx_guard_scan.restype = c_int
     L.umx_guard_scan.argtypes = [c_void_p, ctypes.c_size_t, c_int, ctypes.c_size_t, c_int, ctypes.c_char_p, ctypes.c_char_p,
@@ -453,6 +466,40 @@ class Trainer:
         self._check(self._lib.umx_trainer_assemble_warped(self._h, ts._handle(), d.ctypes.data, None if a is None else a.ctypes.data,
                                                           w.ctypes.data, n, data.ctypes.data, labels.ctypes.data,
                                                           None if weights is None else weights.ctypes.data))
+        return data, labels, weights
+
+    def _elastics(self, elastic, n: int):
+        e = np.ascontiguousarray(elastic, dtype=ELASTIC_DESC)
+        if e.shape != (n,):
+            raise ValueError("expected %d elastic descriptors (a 1-d ELASTIC_DESC array), got shape %r" % (n, e.shape))
+        return e
+
+    def step_elastic(self, ts, desc, aug, warp, elastic, apply_update: bool = True):
+        """``step_warped`` with a displacement lattice per image (``elastic``: B ELASTIC_DESC rows, ``trainset.elastic_lattice``).
+        ``aug`` None: no blur and gain 1; ``warp`` None: no rotation or zoom.  Only enqueues."""
+        d = self._descs(desc, self.batch)
+        if d.size != self.batch:
+            raise ValueError("step_elastic takes exactly %d descriptors, got %d" % (self.batch, d.size))
+        a = None if aug is None else self._augs(aug, d.size)
+        w = None if warp is None else self._warps(warp, d.size)
+        e = self._elastics(elastic, d.size)
+        self._check(self._lib.umx_train_step_elastic(self._h, ts._handle(), d.ctypes.data, None if a is None else a.ctypes.data,
+                                                     None if w is None else w.ctypes.data, e.ctypes.data, int(apply_update)))
+
+    def assemble_elastic(self, ts, desc, aug, warp, elastic):
+        """``assemble_warped`` with a displacement lattice per image; ``aug`` and ``warp`` may be None."""
+        hp = self.hp
+        d = self._descs(desc, self.batch)
+        a = None if aug is None else self._augs(aug, d.size)
+        w = None if warp is None else self._warps(warp, d.size)
+        e = self._elastics(elastic, d.size)
+        n, P = d.size, hp.imSize
+        data = np.empty((n, P, P, hp.nChannels), np.float32)
+        labels = np.empty((n, P, P, hp.nClasses), np.float32)
+        weights = np.empty((n, P, P, hp.nClasses), np.float32) if ts.weighted else None
+        self._check(self._lib.umx_trainer_assemble_elastic(self._h, ts._handle(), d.ctypes.data, None if a is None else a.ctypes.data,
+                                                           None if w is None else w.ctypes.data, e.ctypes.data, n, data.ctypes.data,
+                                                           labels.ctypes.data, None if weights is None else weights.ctypes.data))
         return data, labels, weights
 
     def evaluate(self, ts, descs) -> dict:

@@ -20,6 +20,10 @@ draws a blur level and a saturation gain per image and ``Trainer.step_augmented`
 
 Rotation and zoom: ``warp_matrix`` makes the 2 x 2 matrix of an angle and a magnification, ``Sampler.next_warped`` draws one per
 image (``rotate_prob``, ``zoom_prob``, ``zoom_range``) and ``Trainer.step_warped`` resamples data, labels and weights on the device.
+
+Elastic deformation: ``elastic_lattice`` lays clipped normal draws into the displacement lattice of ``trainer.ELASTIC_DESC``,
+``Sampler.next_elastic`` draws one per image (``elastic_prob``, ``elastic_sigma``, ``elastic_grid``) and ``Trainer.step_elastic``
+adds its cubic B-spline displacement to the source coordinate of that one resampling.
 """
 from __future__ import annotations
 
@@ -32,7 +36,8 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import imtools, tiffio
-from .trainer import AUGMENT_DESC, AUGMENT_MAX_LEVELS, AUGMENT_MAX_RADIUS, SAMPLE_DESC, WARP_DESC, AugmentTableC, LabelWeightsC
+from .trainer import (AUGMENT_DESC, AUGMENT_MAX_LEVELS, AUGMENT_MAX_RADIUS, ELASTIC_DESC, ELASTIC_MAX_DISP, ELASTIC_MAX_GRID, SAMPLE_DESC,
+                      WARP_DESC, AugmentTableC, LabelWeightsC)
 
 
 @dataclass(frozen=True)
@@ -98,6 +103,22 @@ def warp_matrix(angle_deg: float, zoom: float) -> np.ndarray:
     t = np.deg2rad(np.float64(angle_deg))
     c, s = np.cos(t) / zoom, np.sin(t) / zoom
     return (np.array([c, -s, s, c], np.float64) + 0.0).astype(np.float32)   # (+ 0.0: no -0.0)
+
+
+def elastic_lattice(z, sigma: float, n: int) -> np.ndarray:
+    """``umx_elastic_desc.d``: ``float32(sigma * clip(z, -2, 2))`` for ``2 n n`` standard normal draws ``z`` (row displacements first),
+    laid into the ``n x n`` corner of the 2 x 6 x 6 block; the rest is zero.  ``n`` = lattice points per axis, 4..6."""
+    sigma, n = float(sigma), int(n)
+    if not 4 <= n <= ELASTIC_MAX_GRID:
+        raise ValueError("a lattice has 4..%d points per axis, got %d" % (ELASTIC_MAX_GRID, n))
+    if not (np.isfinite(sigma) and 0.0 <= sigma and 2.0 * sigma <= ELASTIC_MAX_DISP):
+        raise ValueError("an elastic sigma is finite, >= 0 and at most %g, got %r" % (ELASTIC_MAX_DISP / 2.0, sigma))
+    z = np.asarray(z, np.float64)
+    if z.size != 2 * n * n or not np.isfinite(z).all():
+        raise ValueError("a %d x %d lattice takes %d finite draws, got shape %r" % (n, n, 2 * n * n, z.shape))
+    d = np.zeros((2, ELASTIC_MAX_GRID, ELASTIC_MAX_GRID), np.float32)
+    d[:, :n, :n] = (sigma * np.clip(z.reshape(2, n, n), -2.0, 2.0) + 0.0).astype(np.float32)   # (+ 0.0: no -0.0)
+    return d
 
 
 @dataclass(frozen=True)
@@ -312,12 +333,18 @@ class Sampler:
     Rotation and zoom (off by default; then nothing extra is drawn): with ``rotate_prob`` an image is rotated by ``360 U[0,1)`` degrees,
     with ``zoom_prob`` magnified by ``lo (hi / lo)^U[0,1)``, ``(lo, hi) = zoom_range`` (log-uniform).  When either probability is
     positive, four more draws follow the image's previous ones (after the gain draw when blur / saturation are on, else after the
-    contrast draw) -- rotation coin, angle, zoom coin, zoom -- again whatever the coins say."""
+    contrast draw) -- rotation coin, angle, zoom coin, zoom -- again whatever the coins say.
+
+    Elastic deformation (off by default; then nothing extra is drawn): with ``elastic_prob`` an image gets a lattice of
+    ``n = elastic_grid + 3`` points per axis (``elastic_grid`` = 1..3 spline cells across the crop) whose displacements are
+    ``elastic_sigma`` pixels times standard normal draws clipped at +-2 (``elastic_lattice``).  When ``elastic_prob`` is positive, two
+    draws follow the image's previous ones -- the coin, then ``standard_normal(2 n n)`` -- whatever the coin says."""
 
     def __init__(self, seed: int, n_samples: int, batch: int, size: int, P: int, n_pages: int, max_brightness: float = 0.0,
                  max_contrast: float = 0.0, transforms: bool = False, blur_levels: int = 1, blur_prob: float = 0.0,
                  saturate_prob: float = 0.0, max_gain: float = 1.0, rotate_prob: float = 0.0, zoom_prob: float = 0.0,
-                 zoom_range: Tuple[float, float] = (1.0, 1.0)):
+                 zoom_range: Tuple[float, float] = (1.0, 1.0), elastic_prob: float = 0.0, elastic_sigma: float = 0.0,
+                 elastic_grid: int = 2):
         if n_samples < 1 or batch < 1 or n_pages < 1 or size < P:
             raise ValueError("a sampler needs samples, a batch, pages and size >= P")
         if not (0.0 <= blur_prob <= 1.0 and 0.0 <= saturate_prob <= 1.0):
@@ -331,6 +358,15 @@ class Sampler:
         lo, hi = (float(v) for v in zoom_range)
         if not 0.5 <= lo <= 1.0 <= hi <= 2.0:   # (no anti-aliased minification: the floor of 0.5)
             raise ValueError("zoom_range must satisfy 0.5 <= lo <= 1 <= hi <= 2, got %r" % ((lo, hi),))
+        if not 0.0 <= elastic_prob <= 1.0:
+            raise ValueError("elastic_prob is a probability")
+        if int(elastic_grid) != elastic_grid or not 1 <= elastic_grid <= ELASTIC_MAX_GRID - 3:
+            raise ValueError("elastic_grid counts the spline cells across the crop, 1..%d, got %r" % (ELASTIC_MAX_GRID - 3, elastic_grid))
+        if not (np.isfinite(elastic_sigma) and 0.0 <= elastic_sigma and 2.0 * elastic_sigma <= ELASTIC_MAX_DISP):
+            raise ValueError("elastic_sigma must be finite, >= 0 and at most %g" % (ELASTIC_MAX_DISP / 2.0))
+        if elastic_prob > 0 and not elastic_sigma > 0:
+            raise ValueError("an elastic deformation needs elastic_sigma > 0")
+        self.elastic_prob, self.elastic_sigma, self.elastic_grid = float(elastic_prob), float(elastic_sigma), int(elastic_grid)
         self.rotate_prob, self.zoom_prob, self.zoom_range = float(rotate_prob), float(zoom_prob), (lo, hi)
         self.blur_levels, self.blur_prob = int(blur_levels), float(blur_prob)
         self.saturate_prob, self.max_gain = float(saturate_prob), float(max_gain)
@@ -367,14 +403,25 @@ class Sampler:
         """The next batch: ``batch`` descriptors and their blur level / gain (a SAMPLE_DESC and an AUGMENT_DESC array)."""
         return self.next_warped()[:2]
 
+    @property
+    def deforming(self) -> bool:
+        return self.elastic_prob > 0.0
+
     def next_warped(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """The next batch: ``batch`` descriptors, their blur level / gain and their rotation / zoom matrix (a SAMPLE_DESC, an
         AUGMENT_DESC and a WARP_DESC array)."""
+        return self.next_elastic()[:3]
+
+    def next_elastic(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """The next batch: ``batch`` descriptors, their blur level / gain, their rotation / zoom matrix and their displacement lattice (a
+        SAMPLE_DESC, an AUGMENT_DESC, a WARP_DESC and an ELASTIC_DESC array)."""
         d = np.zeros(self.batch, SAMPLE_DESC)
         a = np.zeros(self.batch, AUGMENT_DESC)
         a["gain"] = 1.0
         w = np.zeros(self.batch, WARP_DESC)
         w["m"] = (1.0, 0.0, 0.0, 1.0)
+        e = np.zeros(self.batch, ELASTIC_DESC)
+        n_lat = self.elastic_grid + 3
         lo, hi = self.zoom_range
         r = self.rng
         span = self.size - self.P + 1
@@ -401,7 +448,13 @@ class Sampler:
                 zoomed = r.random() < self.zoom_prob
                 zoom = lo * (hi / lo) ** r.random()
                 w["m"][j] = warp_matrix(angle if rot else 0.0, zoom if zoomed else 1.0)
-        return d, a, w
+            if self.deforming:
+                deformed = r.random() < self.elastic_prob
+                z = r.standard_normal(2 * n_lat * n_lat)
+                if deformed:
+                    e["n"][j] = n_lat
+                    e["d"][j] = elastic_lattice(z, self.elastic_sigma, n_lat)
+        return d, a, w, e
 
     def __iter__(self):
         while True:
@@ -447,4 +500,4 @@ def graph_kind(hp) -> str:
 
 
 __all__ = ["LabelWeights", "UNWEIGHTED", "LABEL_WEIGHTS", "default_jitter", "TrainSet", "Dataset", "dataset_indices",
-           "read_dataset_dir", "Sampler", "gaussian_taps", "AugmentTable", "AUGMENT_DESC", "warp_matrix", "WARP_DESC", "crop_origins", "validation_descriptors", "upload", "graph_kind", "SAMPLE_DESC"]
+           "read_dataset_dir", "Sampler", "gaussian_taps", "AugmentTable", "AUGMENT_DESC", "warp_matrix", "WARP_DESC", "elastic_lattice", "ELASTIC_DESC", "crop_origins", "validation_descriptors", "upload", "graph_kind", "SAMPLE_DESC"]
