@@ -300,11 +300,48 @@ UMX_API int umx_trainer_assemble_elastic(umx_trainer* tr, const umx_trainset* ts
                                          const umx_augment_desc* aug, const umx_warp_desc* warp, const umx_elastic_desc* elastic, int n,
                                          float* data, float* labels, float* weights);
 
+/* ---- border weight maps ("Border weight maps") ----
+ * For a set whose samples bring no _wt.tif: the contour-intersection map W of weights[k] = intersect_weight[k] * W + class_weight[k],
+ * computed on the device from the stored annotation as the border term of Ronneberger et al. 2015 (U-Net), exp(-(d1 + d2)^2 /
+ * (2 sigma^2)), d1 the distance to the nearest object and d2 to the nearest other one.  This is a reading of the published maps: the
+ * reference reads them from files it never makes.  Per sample, with A its annotation [S][S], c = object_code, sg = (double)sigma:
+ *   1. objects     a pixel is an object pixel iff A == c.  Components are 4-connected (UMX_BORDER_CONNECTIVITY; a one-pixel-wide
+ *                  diagonal contour line separates two objects only under 4-connectivity).  label = 1 + y * S + x of the component's
+ *                  first pixel in raster order; 0 off the objects.
+ *   2. distances   R = ceil(4 sg) <= 32.  d1sq: the least dy^2 + dx^2 <= R^2 over object pixels (0 inside an object); d2sq: the least
+ *                  over object pixels whose label differs from that of a nearest one (two components at the same least distance:
+ *                  d2sq == d1sq whichever is taken first).  Integers; -1: none.  Pixels outside the sample do not exist (no mirror).
+ *   3. the map     W = float32(exp(-(sqrt((double)d1sq) + sqrt((double)d2sq))^2 / (2 sg^2))) where d2sq >= 0, else 0.0f: float64,
+ *                  every operation one rounding.  The cut at R drops values below exp(-8) = 3.4e-4; it is part of the definition.
+ * tests/trainset_border_ref.py restates this with scipy.ndimage.label; labels, d1sq and d2sq are bit-equal to it, W within one float32
+ * ulp (the device's float64 exp may differ from the host's in its last bit). */
+#define UMX_BORDER_MAX_SIGMA 8.0f
+#define UMX_BORDER_CONNECTIVITY 4
+typedef struct umx_border_options {
+    int32_t object_code;          /* the annotation code of the objects, 1..nClasses (the reference's sets: 3, nuclei) */
+    float sigma;                  /* pixels, 0 < sigma <= UMX_BORDER_MAX_SIGMA */
+    int32_t reserved[6];          /* must be zero */
+} umx_border_options;
+/* Host validation (no device needed): object_code in 1..n_classes, sigma in (0, 8] (a NaN is refused), reserved zero.  UMX_OK, or
+ * UMX_ERR_INVALID with the broken rule in msg (cap bytes, NUL-terminated; msg may be NULL). */
+UMX_API int umx_border_options_check(const umx_border_options* o, int n_classes, char* msg, size_t cap);
+/* Replace the weight map of sample `index` (or of every sample: index == -1) by the map computed from its stored annotation.  Waits
+ * for the trainer's stream before and after, like umx_trainset_set; a later umx_trainset_set of the sample overwrites the map as ever.
+ * UMX_ERR_INVALID, with nothing enqueued, for an unweighted set, an index outside -1 .. n_samples-1, what umx_border_options_check
+ * refuses, and samples of more than 46340 pixels a side (a label is an int32).  The first call allocates an int32 workspace of
+ * n_samples * size^2 words in the set's device memory: UMX_ERR_OOM if it does not fit (umx_trainset_create does not count it). */
+UMX_API int umx_trainset_border_weights(umx_trainset* ts, int index, const umx_border_options* o);
+/* Diagnostics / tests, synchronous: recompute sample `index` (>= 0) with the same kernels and copy out what is asked for (any pointer
+ * may be NULL), each [size][size]; the stored map is left as it was.  The first call allocates four more planes of size^2 words. */
+UMX_API int umx_trainset_border_planes(umx_trainset* ts, int index, const umx_border_options* o, int32_t* labels, int32_t* d1sq,
+                                       int32_t* d2sq, float* wmap);
+
 /* Debug guard mode.  UMX_DEBUG_GUARD=<byte> (e.g. 0xff), read by umx_trainer_create and umx_trainset_create, gives every device
  * buffer of that trainer / set a red zone of max(64 KiB, its size rounded up to 4 KiB) on both sides.  The zones, and every buffer
  * the library does not zero or upload, are filled with that byte, so a result that depends on the byte read memory nobody wrote.
  * Every entry that enqueues work (umx_train_step, _step_dev, _step_sampled, _step_augmented, _step_warped, _step_elastic, umx_trainer_eval, _assemble,
- * _assemble_augmented, _assemble_warped, _assemble_elastic, _evaluate, umx_trainer_init, umx_trainset_set) then waits for the trainer's streams and checks every zone: UMX_ERR_GUARD names the buffer, the side and the
+ * _assemble_augmented, _assemble_warped, _assemble_elastic, _evaluate, umx_trainer_init, umx_trainset_set, umx_trainset_border_weights,
+ * umx_trainset_border_planes) then waits for the trainer's streams and checks every zone: UMX_ERR_GUARD names the buffer, the side and the
  * first and last changed byte.  Slow; for tests.  Off (unset or empty), allocations and launches are exactly the normal ones.
  *
  * The host scan of one zone (no device needed): zone_bytes bytes that should all equal `fill`, in front of (side 0) or behind

@@ -121,6 +121,16 @@ struct PendingEvent {
 
 struct Shard;   // umx_shard.hip: the communicator, transport and buffers umx_shard_init attaches to a context
 
+// ---- border weight maps (umx_trainset_border.hip) ----
+// 4-connected components of (annotation == code) of n samples (ann: the first one's plane, [S][row_a] each) into ws [n][S][S]: the
+// flat index of the component's first pixel in raster order, -1 off the objects.  One workgroup per sample; S * S fits an int32.
+hipError_t launch_border_label(const uint8_t* ann, int n, int S, int row_a, int code, int* ws, hipStream_t stream);
+// from those planes: wmap (sample stride plane_w, row stride row_w floats) and, where given, labels (root + 1; 0 off the objects),
+// d1sq and d2sq [n][S][S].  R = border_radius(sigma) <= 32, den = 2 sigma^2.
+hipError_t launch_border_map(const int* ws, int n, int S, int R, double den, float* wmap, int row_w, size_t plane_w, int* labels,
+                             int* d1sq, int* d2sq, hipStream_t stream);
+int border_radius(float sigma);        // ceil(4 sigma)
+
 }  // namespace umx
 
 struct umx_ctx {
@@ -412,5 +422,15 @@ hipError_t launch_assemble_elastic(const TrainSetView& ts, const ElasticChunk& e
 size_t class_counts_parts(size_t npix, int K);
 hipError_t launch_class_counts(const float* probs, const float* labels, size_t npix, int K, double* part, long long* counts,
                                double* loss, hipStream_t stream);
+
+// ---- border weight maps (umx_trainset_border.hip) ----
+// 4-connected components of (annotation == code) of n samples (ann: the first one's plane, [S][row_a] each) into ws [n][S][S]: the
+// flat index of the component's first pixel in raster order, -1 off the objects.  One workgroup per sample; S * S fits an int32.
+hipError_t launch_border_label(const uint8_t* ann, int n, int S, int row_a, int code, int* ws, hipStream_t stream);
+// from those planes: wmap (sample stride plane_w, row stride row_w floats) and, where given, labels (root + 1; 0 off the objects),
+// d1sq and d2sq [n][S][S].  R = border_radius(sigma) <= 32, den = 2 sigma^2.
+hipError_t launch_border_map(const int* ws, int n, int S, int R, double den, float* wmap, int row_w, size_t plane_w, int* labels,
+                             int* d1sq, int* d2sq, hipStream_t stream);
+int border_radius(float sigma);        // ceil(4 sigma)
 
 }  // namespace umx

@@ -1,6 +1,7 @@
 // libumx device-resident training set: storage, the two kernels that feed the training step from it, and the C ABI of the
 // umx_trainset_* / umx_train_step_sampled / _augmented / _warped / _elastic / umx_trainer_assemble / _augmented / _warped / _elastic /
-// umx_trainer_evaluate entries of include/umx_train.h.
+// umx_trainer_evaluate / umx_trainset_border_weights / _border_planes entries of include/umx_train.h (the kernels of the last two:
+// umx_trainset_border.hip).
 //
 // The set is the reference's annotated layout (I%05d_Img.tif pages, _Ant.tif class codes, _wt.tif contour-intersection map;
 // UnMicst1-5.py:295-312, UnMicst2.py:293-309, UnMicst.py:236-243) uploaded once, already normalised.  A step then costs 32 bytes
@@ -58,6 +59,8 @@ struct umx_trainset {
     double* part = nullptr;             // class_counts workspace (B P^2 pixels at most)
     long long* counts = nullptr;        // [2K]
     double* loss = nullptr;             // [1]
+    int* border_ws = nullptr;           // [N][S][S] labelling workspace, allocated by the first umx_trainset_border_* call
+    int* border_diag = nullptr;         // [4][S][S] labels | d1sq | d2sq | map of umx_trainset_border_planes, allocated by its first call
     DevArena mem;                       // every device buffer above (UMX_DEBUG_GUARD: with red zones)
 };
 
@@ -748,9 +751,68 @@ int assemble_to_host(umx_trainer* tr, const umx_trainset* ts, const umx_sample_d
     return guard_check(tr, ts);
 }
 
+// umx_trainset_border_weights / _border_planes: everything checked and the workspace there before anything is enqueued
+int border_begin(umx_trainset* ts, int index, int index_min, const umx_border_options* o, bool diag, const char* what) {
+    if (!ts) return tsfail(nullptr, UMX_ERR_INVALID, "null training set");
+    umx_trainer* tr = ts->tr;
+    if (!ts->weighted) return tsfail(tr, UMX_ERR_INVALID, "%s: an unweighted set has no weight map", what);
+    if (index < index_min || index >= ts->N) return tsfail(tr, UMX_ERR_INVALID, "%s: sample %d of a set of %d", what, index, ts->N);
+    char why[160];
+    if (umx_border_options_check(o, ts->K, why, sizeof why) != UMX_OK) return tsfail(tr, UMX_ERR_INVALID, "%s: %s", what, why);
+    if (ts->S > 46340) return tsfail(tr, UMX_ERR_INVALID, "%s: samples of %d pixels a side: a label (1 + y * size + x) is an int32", what, ts->S);
+    const TrainerIO io = trainer_io(tr);
+    TS_HIP(tr, hipSetDevice(io.device));
+    const size_t plane = (size_t)ts->S * ts->S;
+    const size_t need = (ts->border_ws ? 0 : plane * ts->N * sizeof(int)) + (diag && !ts->border_diag ? 4 * plane * sizeof(int) : 0);
+    if (need) {
+        size_t free_b = 0, total_b = 0;
+        if (umx_device_mem_info(io.device, &free_b, &total_b) != UMX_OK) return tsfail(tr, UMX_ERR_HIP, "%s", umx_last_error(nullptr));
+        if (need > free_b)
+            return tsfail(tr, UMX_ERR_OOM, "%s: the labelling workspace of %d samples of %d x %d needs %.1f MB, %.1f MB are free", what,
+                          ts->N, ts->S, ts->S, need / 1e6, free_b / 1e6);
+        if (!ts->border_ws) TS_TRY(ts_alloc(ts, &ts->border_ws, plane * ts->N));
+        if (diag && !ts->border_diag) TS_TRY(ts_alloc(ts, &ts->border_diag, 4 * plane));
+    }
+    return UMX_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int umx_trainset_border_weights(umx_trainset* ts, int index, const umx_border_options* o) {
+    TS_TRY(border_begin(ts, index, -1, o, false, "umx_trainset_border_weights"));
+    umx_trainer* tr = ts->tr;
+    const TrainerIO io = trainer_io(tr);
+    const int first = index < 0 ? 0 : index, n = index < 0 ? ts->N : 1;
+    const size_t plane = (size_t)ts->S * ts->S, plane_w = (size_t)ts->S * ts->row_f;
+    int* ws = ts->border_ws + first * plane;
+    TS_HIP(tr, hipStreamSynchronize(io.stream));   // (a step in flight may still read the map)
+    TS_HIP(tr, launch_border_label(ts->ann + (size_t)first * ts->S * ts->row_a, n, ts->S, ts->row_a, o->object_code, ws, io.stream));
+    TS_HIP(tr, launch_border_map(ws, n, ts->S, border_radius(o->sigma), 2.0 * ((double)o->sigma * (double)o->sigma),
+                                 ts->wmap + first * plane_w, ts->row_f, plane_w, nullptr, nullptr, nullptr, io.stream));
+    TS_HIP(tr, hipStreamSynchronize(io.stream));
+    return guard_check(tr, ts);
+}
+
+int umx_trainset_border_planes(umx_trainset* ts, int index, const umx_border_options* o, int32_t* labels, int32_t* d1sq, int32_t* d2sq,
+                               float* wmap) {
+    TS_TRY(border_begin(ts, index, 0, o, true, "umx_trainset_border_planes"));
+    umx_trainer* tr = ts->tr;
+    const TrainerIO io = trainer_io(tr);
+    const size_t plane = (size_t)ts->S * ts->S;
+    int* ws = ts->border_ws + index * plane;
+    int* dg = ts->border_diag;
+    TS_HIP(tr, hipStreamSynchronize(io.stream));
+    TS_HIP(tr, launch_border_label(ts->ann + (size_t)index * ts->S * ts->row_a, 1, ts->S, ts->row_a, o->object_code, ws, io.stream));
+    TS_HIP(tr, launch_border_map(ws, 1, ts->S, border_radius(o->sigma), 2.0 * ((double)o->sigma * (double)o->sigma),
+                                 reinterpret_cast<float*>(dg + 3 * plane), ts->S, plane, dg, dg + plane, dg + 2 * plane, io.stream));
+    void* host[4] = {labels, d1sq, d2sq, wmap};
+    for (int k = 0; k < 4; ++k)
+        if (host[k]) TS_HIP(tr, hipMemcpyAsync(host[k], dg + k * plane, plane * sizeof(int), hipMemcpyDeviceToHost, io.stream));
+    TS_HIP(tr, hipStreamSynchronize(io.stream));
+    return guard_check(tr, ts);
+}
 
 int umx_trainset_create(umx_trainer* tr, int n_samples, int n_pages, int size, const umx_label_weights* lw, umx_trainset** out) {
     if (!tr || !lw || !out) return tsfail(tr, UMX_ERR_INVALID, "null argument");

@@ -5,6 +5,7 @@
                                    [--blur-sigmas 0.75,1.5,3] [--blur-prob P] [--saturate-prob P] [--max-gain G]
                                    [--rotate-prob P] [--zoom-prob P] [--zoom-range LO,HI]
                                    [--elastic-sigma PX] [--elastic-prob P] [--elastic-grid G]
+                                   [--border-sigma PX [--border-class K]]
                                    [--from-scratch [--init-seed S] [--std-dev0 V] [--mean M --std S]]
 
 ``--train`` / ``--valid`` hold the reference's published layout (``I%05d_Img.tif`` / ``_Ant.tif`` / ``_wt.tif``, see
@@ -36,6 +37,15 @@ data is still interpolated once and labels and weight maps still take the neares
 ``(imSize - 1) / (8 G)`` or more is refused: below it the deformation cannot fold the image over itself.  Validation stays undeformed.
 When one of the three flags is given, the log's first line carries the settings as its ``"elastic"`` object (after ``"init"``,
 ``"augment"`` and ``"warp"``).
+
+Border weight maps, for sets annotated without ``_wt.tif`` files (without them, and without this flag, the contour-intersection term of
+the weighted loss is 0 for those samples): ``--border-sigma PX`` (``0 < PX <= 8``; U-Net's own choice is 5) computes the map of every
+sample of either set that brings none, on the device, as ``exp(-(d1 + d2)^2 / (2 PX^2))`` with ``d1`` / ``d2`` the distances to the nearest
+and the second nearest 4-connected object of class ``--border-class K`` (0-based; default: the last class, nuclei), cut at
+``ceil(4 PX)`` pixels.  That is U-Net's border term (Ronneberger et al. 2015) and this project's reading of the published maps: the
+reference never makes them ("Border weight maps").  A sample with a ``_wt.tif`` keeps it.  The legacy graph's
+loss takes no weights, so the flag is refused there.  With the flag the log's first line carries the ``"border"`` object (after
+``"elastic"``): sigma, class, radius and ``"computed": [n_train, n_valid]``, the samples whose map was computed.
 
 ``--from-scratch`` starts from the graph's initial state instead of the model's weights (the reference's
 ``train(..., restoreVariables=False)``: ``tf.global_variables_initializer()``, made on the device by ``Trainer.from_scratch``; DESIGN.md
@@ -92,6 +102,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--elastic-sigma", type=float, default=None, help="standard deviation of a lattice displacement in pixels, > 0")
     p.add_argument("--elastic-prob", type=float, default=None, help="chance that an image is deformed (default 0.5 with --elastic-sigma)")
     p.add_argument("--elastic-grid", type=int, default=None, help="spline cells across the tile, 1..3 (default 2)")
+    p.add_argument("--border-sigma", type=float, default=None,
+                   help="compute the weight map of samples without _wt.tif: sigma of the border term in pixels, in (0, 8]")
+    p.add_argument("--border-class", type=int, default=None, help="0-based class of the objects (default: the last class); needs --border-sigma")
     p.add_argument("--from-scratch", action="store_true", help="start from the graph's initial state, not from the model's weights")
     p.add_argument("--init-seed", type=int, default=None, help="seed of the initial state (default: --seed); needs --from-scratch")
     p.add_argument("--std-dev0", type=float, default=None,
@@ -191,6 +204,30 @@ def elastic_settings(args, im_size=None):
     return {"prob": float(prob), "sigma": sigma, "grid": int(grid)}
 
 
+def border_settings(args, hp=None):
+    """The two border flags -> None when neither is given, else {"sigma", "class", "radius"}.  ``hp`` (the model's hyper-parameters)
+    adds the checks that depend on the graph and resolves the default class; without it only the flags are checked and a class left
+    open stays None.  Raises Refusal."""
+    sigma, cls = getattr(args, "border_sigma", None), getattr(args, "border_class", None)
+    if sigma is None and cls is None:
+        return None
+    if sigma is None:
+        raise Refusal("--border-class needs --border-sigma")
+    if not 0.0 < sigma <= trainer.BORDER_MAX_SIGMA:   # (a NaN fails the chain)
+        raise Refusal("--border-sigma %r: a sigma is above 0 and at most %g pixels" % (sigma, trainer.BORDER_MAX_SIGMA))
+    if cls is not None and cls < 0:
+        raise Refusal("--border-class %r: classes are 0-based" % cls)
+    if hp is not None:
+        if cls is not None and cls >= hp.nClasses:
+            raise Refusal("--border-class %d: the model has classes 0..%d" % (cls, hp.nClasses - 1))
+        if not trainset.LABEL_WEIGHTS[trainset.graph_kind(hp)].weighted:
+            raise Refusal("--border-sigma: the legacy loss takes no weights, so a weight map would never be read")
+        if cls is None:
+            cls = hp.nClasses - 1
+    opts = trainset.BorderOptions(float(sigma), cls)
+    return {"sigma": float(sigma), "class": None if cls is None else int(cls), "radius": opts.radius}
+
+
 def augment_settings(args):
     """The four augmentation flags -> None when none is given, else {"blur_sigmas", "blur_prob", "saturate_prob", "max_gain"}.
     Raises Refusal."""
@@ -246,6 +283,7 @@ def prepare(args):
     augment_settings(args)
     warp_settings(args)
     elastic_settings(args)
+    border_settings(args)
     scratch = init_settings(args) is not None
     path = resolve_model(args.model)
     if not os.path.isdir(path):
@@ -270,6 +308,7 @@ def prepare(args):
             raise Refusal("model %s has no weights to fine-tune: %s" % (args.model, e))
     hp = art.hp
     elastic_settings(args, hp.imSize)
+    border_settings(args, hp)
     sets = []
     for what, d in (("--train", args.train), ("--valid", args.valid)):
         try:
@@ -289,6 +328,7 @@ def run(args) -> int:
     warp = warp_settings(args)
     hp = art.hp
     elastic = elastic_settings(args, hp.imSize)
+    border = border_settings(args, hp)
     kind = trainset.graph_kind(hp)
     lw = trainset.LABEL_WEIGHTS[kind]
     init = init_settings(args, resolve_model(args.model))
@@ -301,8 +341,11 @@ def run(args) -> int:
         tr = trainer.Trainer.from_scratch(hp, options_for(kind, args.seed, args.lr0), init["seed"], init["std_dev0"], batch=args.batch,
                                           device=args.device)
     try:
-        ts = trainset.upload(tr, train_ds, lw)
-        vs = trainset.upload(tr, valid_ds, lw)
+        bopts = None if border is None else trainset.BorderOptions(border["sigma"], border["class"])
+        ts = trainset.upload(tr, train_ds, lw, border=bopts)
+        vs = trainset.upload(tr, valid_ds, lw, border=bopts)
+        if border is not None:
+            border["computed"] = [ts.border_computed, vs.border_computed]
         mb, mc = trainset.default_jitter(kind, art.std)
         akw = {}
         if aug is not None:
@@ -321,7 +364,7 @@ def run(args) -> int:
         best = None
         train_loss = None
         with open(log_path, "w") as log:
-            settings = {k: v for k, v in (("init", init), ("augment", aug), ("warp", warp), ("elastic", elastic))
+            settings = {k: v for k, v in (("init", init), ("augment", aug), ("warp", warp), ("elastic", elastic), ("border", border))
                         if v is not None}
             if settings:
                 log.write(json.dumps(settings) + "\n")

@@ -32,7 +32,7 @@ EXPORTS = [
     "umx_trainer_assemble", "umx_trainer_evaluate", "umx_guard_scan", "umx_augment_table_check", "umx_trainset_set_augment",
     "umx_train_step_augmented", "umx_trainer_assemble_augmented", "umx_warp_desc_check", "umx_train_step_warped",
     "umx_trainer_assemble_warped", "umx_trainer_init", "umx_elastic_desc_check", "umx_train_step_elastic",
-    "umx_trainer_assemble_elastic",
+    "umx_trainer_assemble_elastic", "umx_border_options_check", "umx_trainset_border_weights", "umx_trainset_border_planes",
 ]
 
 
@@ -109,6 +109,15 @@ class AugmentTableC(ctypes.Structure):
     _fields_ = [("mean", ctypes.c_float), ("std", ctypes.c_float), ("n_levels", ctypes.c_int32),
                 ("radius", ctypes.c_int32 * AUGMENT_MAX_LEVELS), ("taps", (ctypes.c_float * (AUGMENT_MAX_RADIUS + 1)) * AUGMENT_MAX_LEVELS),
                 ("reserved", ctypes.c_int32 * 5)]
+
+
+# ``umx_border_options``: the computed border weight map of a sample ("Border weight maps")
+BORDER_MAX_SIGMA, BORDER_CONNECTIVITY = 8.0, 4
+
+
+class BorderOptionsC(ctypes.Structure):
+    """``umx_border_options`` (include/umx_train.h)."""
+    _fields_ = [("object_code", ctypes.c_int32), ("sigma", ctypes.c_float), ("reserved", ctypes.c_int32 * 6)]
 
 
 def solo_options(**kw) -> TrainOptions:
@@ -218,6 +227,13 @@ def _bind(L):
     L.umx_train_step_elastic.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]
     L.umx_trainer_assemble_elastic.restype = c_int
     L.umx_trainer_assemble_elastic.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
+    # border weight maps (umx_border_options)
+    L.umx_border_options_check.restype = c_int
+    L.umx_border_options_check.argtypes = [ctypes.POINTER(BorderOptionsC), c_int, ctypes.c_char_p, ctypes.c_size_t]
+    L.umx_trainset_border_weights.restype = c_int
+    L.umx_trainset_border_weights.argtypes = [c_void_p, c_int, ctypes.POINTER(BorderOptionsC)]
+    L.umx_trainset_border_planes.restype = c_int
+    L.umx_trainset_border_planes.argtypes = [c_void_p, c_int, ctypes.POINTER(BorderOptionsC), c_void_p, c_void_p, c_void_p, c_void_p]
     # debug guard mode (UMX_DEBUG_GUARD): the host scan of one red zone
     L.umx_guard_scan.restype = c_int
     L.umx_guard_scan.argtypes = [c_void_p, ctypes.c_size_t, c_int, ctypes.c_size_t, c_int, ctypes.c_char_p, ctypes.c_char_p,

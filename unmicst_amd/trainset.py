@@ -7,7 +7,8 @@ sample ``i`` of a directory:
 * ``I%05d_Img.tif``: ``n_pages x n_channels`` pages, page ``aug + n_pages * channel`` -- the extra pages are the "real
   augmentation" z-planes;
 * ``I%05d_Ant.tif``: class codes, ``k + 1`` = class ``k`` (0 = unlabelled);
-* ``I%05d_wt.tif``: the contour-intersection weight map (optional here: a missing one counts as 0).
+* ``I%05d_wt.tif``: the contour-intersection weight map (optional here: a missing one counts as 0, or -- ``upload(..., border=...)``,
+  ``TrainSet.border_weights`` -- is computed on the device from the annotation).
 
 ``TrainSet`` uploads the normalised planes once (``umx_trainset_create`` / ``_set``); ``Sampler`` draws the 32-byte descriptors
 (``trainer.SAMPLE_DESC``) of each batch; ``Trainer.step_sampled`` / ``assemble`` / ``evaluate`` build the batch on the device
@@ -24,6 +25,12 @@ image (``rotate_prob``, ``zoom_prob``, ``zoom_range``) and ``Trainer.step_warped
 Elastic deformation: ``elastic_lattice`` lays clipped normal draws into the displacement lattice of ``trainer.ELASTIC_DESC``,
 ``Sampler.next_elastic`` draws one per image (``elastic_prob``, ``elastic_sigma``, ``elastic_grid``) and ``Trainer.step_elastic``
 adds its cubic B-spline displacement to the source coordinate of that one resampling.
+
+Border weight maps, for sets annotated without a ``_wt.tif`` (the reference reads that file and never makes it): ``BorderOptions`` names
+the objects' class and a sigma, ``TrainSet.border_weights`` replaces the stored map of a sample by U-Net's border term
+``exp(-(d1 + d2)^2 / (2 sigma^2))`` of its annotation's 4-connected objects (``umx_trainset_border_weights``; DESIGN.md section 9.2,
+"Border weight maps" -- a reading of the published maps, not something the reference pins), ``TrainSet.border_planes`` returns the
+labels, both squared distances and the map of one sample.
 """
 from __future__ import annotations
 
@@ -36,8 +43,8 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import imtools, tiffio
-from .trainer import (AUGMENT_DESC, AUGMENT_MAX_LEVELS, AUGMENT_MAX_RADIUS, ELASTIC_DESC, ELASTIC_MAX_DISP, ELASTIC_MAX_GRID, SAMPLE_DESC,
-                      WARP_DESC, AugmentTableC, LabelWeightsC)
+from .trainer import (AUGMENT_DESC, AUGMENT_MAX_LEVELS, AUGMENT_MAX_RADIUS, BORDER_MAX_SIGMA, ELASTIC_DESC, ELASTIC_MAX_DISP,
+                      ELASTIC_MAX_GRID, SAMPLE_DESC, WARP_DESC, AugmentTableC, BorderOptionsC, LabelWeightsC)
 
 
 @dataclass(frozen=True)
@@ -157,6 +164,37 @@ class AugmentTable:
         return t
 
 
+@dataclass(frozen=True)
+class BorderOptions:
+    """``umx_border_options``: ``sigma`` in pixels, ``0 < sigma <= 8`` (the map is cut at ``radius = ceil(4 sigma)`` pixels);
+    ``object_class`` the 0-based class of the objects, None = the last class (nuclei in the reference's sets)."""
+    sigma: float = 5.0
+    object_class: Optional[int] = None
+
+    def __post_init__(self):
+        sigma = float(np.float32(self.sigma))
+        if not 0.0 < sigma <= BORDER_MAX_SIGMA:   # (a NaN fails the chain)
+            raise ValueError("a border sigma is above 0 and at most %g, got %r" % (BORDER_MAX_SIGMA, self.sigma))
+        if self.object_class is not None and (int(self.object_class) != self.object_class or self.object_class < 0):
+            raise ValueError("object_class is a 0-based class index or None, got %r" % (self.object_class,))
+
+    @property
+    def radius(self) -> int:
+        return int(np.ceil(4.0 * np.float64(np.float32(self.sigma))))
+
+    def object_code(self, n_classes: int) -> int:
+        """The annotation code of the objects: class + 1."""
+        k = n_classes - 1 if self.object_class is None else int(self.object_class)
+        if not 0 <= k < n_classes:
+            raise ValueError("object_class %d: the model has classes 0..%d" % (k, n_classes - 1))
+        return k + 1
+
+    def c_struct(self, n_classes: int) -> BorderOptionsC:
+        o = BorderOptionsC()
+        o.object_code, o.sigma = self.object_code(n_classes), float(self.sigma)
+        return o
+
+
 class TrainSet:
     """``n_samples`` samples of ``size x size`` pixels with ``nChannels x n_pages`` normalised planes each, one annotation plane and
     (weighted sets) one weight map, in the device memory of ``trainer``.  Close it (or the trainer) to free that memory."""
@@ -172,6 +210,7 @@ class TrainSet:
         trainer._check(lib.umx_trainset_create(trainer._h, self.n_samples, self.n_pages, self.size, ctypes.byref(lw), ctypes.byref(h)))
         self._h = h
         self._lib = lib
+        self.border_computed = 0          # samples whose weight map ``upload`` computed on the device
         if not hasattr(trainer, "_sets"):
             import weakref
             trainer._sets = weakref.WeakSet()
@@ -210,6 +249,23 @@ class TrainSet:
         c = table.c_struct()
         self.trainer._check(self._lib.umx_trainset_set_augment(self._handle(), ctypes.byref(c)))
         self.augment = table
+
+    def border_weights(self, options: BorderOptions, index: Optional[int] = None) -> None:
+        """Replace the stored weight map of sample ``index`` (None: of every sample) by the border map computed from its annotation
+        (weighted sets only)."""
+        o = options.c_struct(self.trainer.hp.nClasses)
+        self.trainer._check(self._lib.umx_trainset_border_weights(self._handle(), -1 if index is None else int(index), ctypes.byref(o)))
+
+    def border_planes(self, index: int, options: BorderOptions):
+        """Diagnostics: ``(labels, d1sq, d2sq, wmap)`` of sample ``index``, int32 / int32 / int32 / float32 [size][size], recomputed by
+        the kernels of ``border_weights``; the stored map stays."""
+        S = self.size
+        o = options.c_struct(self.trainer.hp.nClasses)
+        labels, d1sq, d2sq = (np.empty((S, S), np.int32) for _ in range(3))
+        wmap = np.empty((S, S), np.float32)
+        self.trainer._check(self._lib.umx_trainset_border_planes(self._handle(), int(index), ctypes.byref(o), labels.ctypes.data,
+                                                                 d1sq.ctypes.data, d2sq.ctypes.data, wmap.ctypes.data))
+        return labels, d1sq, d2sq, wmap
 
     @classmethod
     def from_arrays(cls, trainer, planes, annotations, weight_maps=None, label_weights: LabelWeights = UNWEIGHTED) -> "TrainSet":
@@ -485,9 +541,28 @@ def validation_descriptors(n_samples: int, size: int, P: int) -> np.ndarray:
     return d
 
 
-def upload(trainer, ds: Dataset, label_weights: LabelWeights) -> TrainSet:
-    """A ``Dataset`` into the device memory of ``trainer``."""
-    return TrainSet.from_arrays(trainer, ds.planes, ds.annotations, ds.weight_maps, label_weights)
+def upload(trainer, ds: Dataset, label_weights: LabelWeights, border: Optional[BorderOptions] = None) -> TrainSet:
+    """A ``Dataset`` into the device memory of ``trainer``.  ``border``: the weight map of exactly those samples that bring none
+    (``weight_maps[i] is None``) is computed on the device; ``TrainSet.border_computed`` counts them."""
+    if border is not None:
+        if not label_weights.weighted:
+            raise ValueError("a border weight map needs a weighted set: the legacy loss takes no weights")
+        border.object_code(trainer.hp.nClasses)
+    ts = TrainSet.from_arrays(trainer, ds.planes, ds.annotations, ds.weight_maps, label_weights)
+    if border is not None:
+        try:
+            maps = [None] * ts.n_samples if ds.weight_maps is None else ds.weight_maps
+            missing = [i for i, w in enumerate(maps) if w is None]
+            if len(missing) == ts.n_samples:
+                ts.border_weights(border)
+            else:
+                for i in missing:
+                    ts.border_weights(border, i)
+            ts.border_computed = len(missing)
+        except BaseException:
+            ts.close()
+            raise
+    return ts
 
 
 def graph_kind(hp) -> str:
@@ -499,5 +574,5 @@ def graph_kind(hp) -> str:
     return "solo" if hp.nChannels == 1 else "duo"
 
 
-__all__ = ["LabelWeights", "UNWEIGHTED", "LABEL_WEIGHTS", "default_jitter", "TrainSet", "Dataset", "dataset_indices",
+__all__ = ["LabelWeights", "UNWEIGHTED", "LABEL_WEIGHTS", "default_jitter", "BorderOptions", "TrainSet", "Dataset", "dataset_indices",
            "read_dataset_dir", "Sampler", "gaussian_taps", "AugmentTable", "AUGMENT_DESC", "warp_matrix", "WARP_DESC", "elastic_lattice", "ELASTIC_DESC", "crop_origins", "validation_descriptors", "upload", "graph_kind", "SAMPLE_DESC"]
