@@ -336,12 +336,60 @@ UMX_API int umx_trainset_border_weights(umx_trainset* ts, int index, const umx_b
 UMX_API int umx_trainset_border_planes(umx_trainset* ts, int index, const umx_border_options* o, int32_t* labels, int32_t* d1sq,
                                        int32_t* d2sq, float* wmap);
 
+/* ---- object score of the validation pass ("Object score") ----
+ * umx_trainer_evaluate counts pixels: two nuclei merged through a three-pixel bridge cost it three pixels and are, downstream, one
+ * wrong cell.  This pass counts objects instead.  The reference has only the pixel error: the definition below is this project's own,
+ * as the border maps are.  Per image of a validation batch (a P x P crop), with c = object_code and min_area >= 1:
+ *   1. planes      truth[y][x] = k + 1 where the assembled one-hot label of class k is 1, 0 where the pixel has no label;
+ *                  pred[y][x] = 1 + argmax over the K probabilities (first maximum, as the pixel counts take it), and 0 where truth is 0:
+ *                  an unlabelled pixel is outside the evaluation, as it is for the pixel error.
+ *   2. objects     truth objects: the 4-connected components (UMX_BORDER_CONNECTIVITY) of truth == c; predicted objects: those of
+ *                  pred == c with an area of at least min_area pixels (the smaller ones do not exist in anything below).  Objects are
+ *                  taken as they appear inside the crop: one cut by the crop's edge is cut the same way on both sides.
+ *                  label = 1 + y * P + x of the component's first pixel in raster order; 0 off the objects.
+ *   3. overlap     for a truth object t and a kept predicted object p: I shared pixels, areas a_t and a_p.  Integer arithmetic only:
+ *                    matched    pairs with 3 I > a_t + a_p            (IoU > 1/2, strictly: above one half an object has at most one
+ *                                                                      partner, so no assignment step exists)
+ *                    matched75  pairs with 7 I > 3 (a_t + a_p)        (IoU > 3/4)
+ *                    merged     kept predicted objects p for which at least two truth objects have 2 I > a_t
+ *                    split      truth objects t for which at least two kept predicted objects have 2 I > a_p
+ *   4. counts      int64[UMX_OBJECT_COUNTS] = truth, predicted, matched, matched75, merged, split, 0, 0 per image; a call returns the
+ *                  sum over its images.  F1 = 2 matched / (truth + predicted) is the host's to compute (NaN when both are 0).
+ * tests/trainset_objects_ref.py restates this with scipy.ndimage.label; counts and labels are bit-equal to it.  On the device every
+ * value is an integer sum of atomics, so no result depends on their order, and every loop is bounded. */
+#define UMX_OBJECT_COUNTS 8
+#define UMX_OBJECT_MAX_MIN_AREA 65536
+typedef struct umx_object_options {
+    int32_t object_code;          /* the class code of the objects, 1..nClasses (the reference's sets: 3, nuclei) */
+    int32_t min_area;             /* predicted objects below this many pixels are dropped, 1..65536 */
+    int32_t reserved[6];          /* must be zero */
+} umx_object_options;
+/* Host validation (no device needed): object_code in 1..n_classes, min_area in 1..65536, reserved zero.  UMX_OK, or UMX_ERR_INVALID
+ * with the broken rule in msg (cap bytes, NUL-terminated; msg may be NULL). */
+UMX_API int umx_object_options_check(const umx_object_options* o, int n_classes, char* msg, size_t cap);
+/* Exactly umx_trainer_evaluate -- the same launches, counts and *loss_sum bit-equal to its -- and then, on the same forward pass, the
+ * object pass: objects = int64[UMX_OBJECT_COUNTS], summed over the n images.  truth_codes / pred_codes: the two planes, uint8 [n][P][P]
+ * each (either may be NULL; diagnostics and tests).  Every argument is checked before anything is enqueued (UMX_ERR_INVALID: what
+ * umx_trainer_evaluate and umx_object_options_check refuse, a NULL objects, a tile above 4096 pixels a side).  The first call of either
+ * object entry allocates the pass's workspace for B images in the set's device memory -- 26 B P^2 bytes of planes and words and 12 bytes
+ * per slot of B pair tables of at least 2 P^2 slots each: UMX_ERR_OOM if it does not fit (umx_trainset_create does not count it).  It
+ * is cleared on the trainer's stream at each call.  Synchronous. */
+UMX_API int umx_trainer_evaluate_objects(umx_trainer* tr, umx_trainset* ts, const umx_sample_desc* desc, int n,
+                                         const umx_object_options* o, int64_t* counts, double* loss_sum, int64_t* objects,
+                                         uint8_t* truth_codes, uint8_t* pred_codes);
+/* Diagnostics / tests, synchronous: n <= B pairs of HOST planes, uint8 [n][P][P] each, are uploaded into the same two device planes
+ * (rule 1's pred = 0 where truth = 0 is applied to them on the device, by the code that applies it above) and the same launches run
+ * from the labelling on.  per_image = int64[n][UMX_OBJECT_COUNTS]; truth_labels / pred_labels (either may be NULL) = int32 [n][P][P],
+ * the labels of rule 2 -- of every predicted component, also of those below min_area.  No forward pass; the trainer's buffers stay. */
+UMX_API int umx_trainer_object_counts(umx_trainer* tr, umx_trainset* ts, const uint8_t* truth_codes, const uint8_t* pred_codes, int n,
+                                      const umx_object_options* o, int64_t* per_image, int32_t* truth_labels, int32_t* pred_labels);
+
 /* Debug guard mode.  UMX_DEBUG_GUARD=<byte> (e.g. 0xff), read by umx_trainer_create and umx_trainset_create, gives every device
  * buffer of that trainer / set a red zone of max(64 KiB, its size rounded up to 4 KiB) on both sides.  The zones, and every buffer
  * the library does not zero or upload, are filled with that byte, so a result that depends on the byte read memory nobody wrote.
  * Every entry that enqueues work (umx_train_step, _step_dev, _step_sampled, _step_augmented, _step_warped, _step_elastic, umx_trainer_eval, _assemble,
  * _assemble_augmented, _assemble_warped, _assemble_elastic, _evaluate, umx_trainer_init, umx_trainset_set, umx_trainset_border_weights,
- * umx_trainset_border_planes) then waits for the trainer's streams and checks every zone: UMX_ERR_GUARD names the buffer, the side and the
+ * umx_trainset_border_planes, umx_trainer_evaluate_objects, umx_trainer_object_counts) then waits for the trainer's streams and checks every zone: UMX_ERR_GUARD names the buffer, the side and the
  * first and last changed byte.  Slow; for tests.  Off (unset or empty), allocations and launches are exactly the normal ones.
  *
  * The host scan of one zone (no device needed): zone_bytes bytes that should all equal `fill`, in front of (side 0) or behind

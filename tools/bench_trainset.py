@@ -7,9 +7,12 @@ so that step_sampled of the same run is its yardstick.  A fourth leg, "warped", 
 every image rotated by 30 degrees at zoom 1.25, alternated in the same way.  A fifth leg, "elastic", is Trainer.step_elastic with the
 warped leg's settings plus a 5 x 5 lattice (2 spline cells, sigma 4 pixels) on every image.  Then the validation pass
 (Trainer.evaluate) over the whole set.  One JSON line per (shape, path, repeat).  --paths picks the legs (for a profile of one of them).
+--objects adds the object-score leg: the validation pass over a set of blob annotations (random codes have no objects worth the name),
+alternating Trainer.evaluate without and with ObjectOptions in the same process, so that the plain pass of the same run is the yardstick;
+one line per (shape, repeat) with the milliseconds per validation batch of both and the object counts.
 
     python tools/bench_trainset.py [--steps 30] [--warmup 5] [--repeats 3] [--shapes nucleiDAPI,v2-256]
-                                   [--paths step_sampled,augmented,warped,elastic,host_fed,evaluate]
+                                   [--paths step_sampled,augmented,warped,elastic,host_fed,evaluate] [--objects]
 """
 import argparse
 import json
@@ -51,6 +54,27 @@ def host_batch(planes, ann, wmaps, d, P, K, lw):
     return data, labels, weights
 
 
+def blob_annotation(S, K, seed):
+    """Smoothed noise thresholded into blobs of the last class with a one-pixel ring of the class before it, class 0 elsewhere: what a
+    nuclei annotation looks like to the object pass.  numpy only (a 9-tap box filter, five times)."""
+    rng = np.random.default_rng(seed)
+    f = rng.random((S + 40, S + 40))
+    for _ in range(5):                                    # each pass takes 8 pixels off either axis
+        c = np.cumsum(np.cumsum(np.pad(f, ((1, 0), (1, 0))), axis=0), axis=1)
+        f = c[9:, 9:] - c[:-9, 9:] - c[9:, :-9] + c[:-9, :-9]
+    obj = f > np.quantile(f, 0.7)
+    grown = obj.copy()
+    grown[1:] |= obj[:-1]
+    grown[:-1] |= obj[1:]
+    grown[:, 1:] |= obj[:, :-1]
+    grown[:, :-1] |= obj[:, 1:]
+    A = np.ones((S, S), np.uint8)
+    if K > 2:
+        A[grown & ~obj] = K - 1
+    A[obj] = K
+    return A
+
+
 def shapes(names):
     out = []
     for nm in names:
@@ -71,6 +95,7 @@ def main():
     ap.add_argument("--shapes", default="nucleiDAPI,v2-256")
     ap.add_argument("--samples", type=int, default=32)
     ap.add_argument("--paths", default="step_sampled,augmented,warped,elastic,host_fed,evaluate")
+    ap.add_argument("--objects", action="store_true", help="add the object-score leg: evaluate with and without ObjectOptions, alternated")
     a = ap.parse_args()
     paths = a.paths.split(",")
     unknown = set(paths) - {"step_sampled", "augmented", "warped", "elastic", "host_fed", "evaluate"}
@@ -151,6 +176,25 @@ def main():
             dt = time.perf_counter() - t0
             print(json.dumps({"shape": name, "batch": B, "path": "evaluate", "repeat": r, "images": len(vd), "seconds": round(dt, 5),
                               "images_per_s": round(len(vd) / dt, 1), "labelled": int(ev["counts"][1].sum())}), flush=True)
+        if a.objects:
+            bann = np.stack([blob_annotation(S, hp.nClasses, 100 + i) for i in range(a.samples)])
+            bs = trainset.TrainSet.from_arrays(tr, planes, bann, list(wmaps), lw)
+            oopts = trainset.ObjectOptions()
+            batches = -(-len(vd) // B)
+            for _ in range(max(1, a.warmup // 3)):
+                tr.evaluate(bs, vd)
+                tr.evaluate(bs, vd, objects=oopts)
+            for r in range(a.repeats):
+                t0 = time.perf_counter()
+                tr.evaluate(bs, vd)
+                t1 = time.perf_counter()
+                ev = tr.evaluate(bs, vd, objects=oopts)
+                t2 = time.perf_counter()
+                print(json.dumps({"shape": name, "batch": B, "path": "objects", "repeat": r, "images": len(vd), "batches": batches,
+                                  "evaluate_ms_per_batch": round(1e3 * (t1 - t0) / batches, 4),
+                                  "evaluate_objects_ms_per_batch": round(1e3 * (t2 - t1) / batches, 4),
+                                  "objects": {k: v for k, v in ev["objects"].items() if k != "f1"}}), flush=True)
+            bs.close()
         ts.close()
         tr.close()
 

@@ -423,6 +423,28 @@ size_t class_counts_parts(size_t npix, int K);
 hipError_t launch_class_counts(const float* probs, const float* labels, size_t npix, int K, double* part, long long* counts,
                                double* loss, hipStream_t stream);
 
+// ---- object score (umx_trainset_objects.hip; the labelling is launch_border_label below) ----
+constexpr int kObjectMaxTile = 4096;   // P^2 fits an int32 with room to spare and a pair key t * P^2 + p + 1 a uint64
+// the device memory of the pass, for B images of P x P (allocated by the first call of an object entry, in the set's arena)
+struct ObjectWorkspace {
+    int B = 0, P = 0;
+    size_t slots = 0;                  // object_table_slots(P), per image
+    uint8_t* planes = nullptr;         // [2][B][P][P] class codes: truth | prediction
+    int* words = nullptr;              // [6][B][P^2]: roots of truth | of the prediction | areas at the roots, twice | partner counts, twice
+    unsigned long long* keys = nullptr;   // [B][slots] pair keys, 0 = empty
+    int* overlap = nullptr;            // [B][slots] shared pixels of the slot's pair
+    long long* counts = nullptr;       // [B][UMX_OBJECT_COUNTS]
+};
+size_t object_table_slots(int P);      // the least power of two >= max(64, 2 P^2)
+// truth / pred [n][P][P] from probs / labels [n,P,P,K]: the label's code (0: none) and 1 + argmax (first maximum; 0 where the truth is 0)
+hipError_t launch_object_planes(const float* probs, const float* labels, int n, int P, int K, uint8_t* truth, uint8_t* pred,
+                                hipStream_t stream);
+// pred = 0 where truth = 0, in place: the same rule for planes that came from the host
+hipError_t launch_object_rule(const uint8_t* truth, uint8_t* pred, int n, int P, hipStream_t stream);
+// from the planes of images 0..n-1 on: clears areas, partner counts and tables, labels both planes (roots in words[0] / words[1]),
+// counts areas and overlaps, reduces to counts[n][8]
+hipError_t launch_object_counts(const ObjectWorkspace& w, int n, int code, int min_area, hipStream_t stream);
+
 // ---- border weight maps (umx_trainset_border.hip) ----
 // 4-connected components of (annotation == code) of n samples (ann: the first one's plane, [S][row_a] each) into ws [n][S][S]: the
 // flat index of the component's first pixel in raster order, -1 off the objects.  One workgroup per sample; S * S fits an int32.

@@ -1,7 +1,7 @@
 // libumx device-resident training set: storage, the two kernels that feed the training step from it, and the C ABI of the
 // umx_trainset_* / umx_train_step_sampled / _augmented / _warped / _elastic / umx_trainer_assemble / _augmented / _warped / _elastic /
-// umx_trainer_evaluate / umx_trainset_border_weights / _border_planes entries of include/umx_train.h (the kernels of the last two:
-// umx_trainset_border.hip).
+// umx_trainer_evaluate / _evaluate_objects / umx_trainer_object_counts / umx_trainset_border_weights / _border_planes entries of
+// include/umx_train.h (the kernels of the border maps: umx_trainset_border.hip; of the object score: umx_trainset_objects.hip).
 //
 // The set is the reference's annotated layout (I%05d_Img.tif pages, _Ant.tif class codes, _wt.tif contour-intersection map;
 // UnMicst1-5.py:295-312, UnMicst2.py:293-309, UnMicst.py:236-243) uploaded once, already normalised.  A step then costs 32 bytes
@@ -41,6 +41,7 @@ static_assert(sizeof(AugChunk) <= 2048, "a chunk of augmented images travels as 
 static_assert(sizeof(umx_warp_desc) == 16, "umx_warp_desc is 16 bytes");
 static_assert(sizeof(AugImage) == 112, "an augmented image is 112 bytes of kernel arguments");
 static_assert(sizeof(umx_elastic_desc) == 304, "umx_elastic_desc is 304 bytes");
+static_assert(sizeof(umx_object_options) == 32, "umx_object_options is 32 bytes");
 static_assert(sizeof(ElasticImage) == 404, "an elastic image is 404 bytes of kernel arguments");
 // the widest launch: TrainSetView, the chunk, P, K (or mean, std) and up to two pointers -- inside the 4 KB of arguments a launch may carry
 static_assert(sizeof(TrainSetView) + sizeof(ElasticChunk) + 2 * sizeof(float) + 8 + 2 * sizeof(void*) <= 4096,
@@ -61,6 +62,7 @@ struct umx_trainset {
     double* loss = nullptr;             // [1]
     int* border_ws = nullptr;           // [N][S][S] labelling workspace, allocated by the first umx_trainset_border_* call
     int* border_diag = nullptr;         // [4][S][S] labels | d1sq | d2sq | map of umx_trainset_border_planes, allocated by its first call
+    ObjectWorkspace obj;                // the object score's planes, words and pair tables, allocated by the first call of an object entry
     DevArena mem;                       // every device buffer above (UMX_DEBUG_GUARD: with red zones)
 };
 
@@ -776,6 +778,74 @@ int border_begin(umx_trainset* ts, int index, int index_min, const umx_border_op
     return UMX_OK;
 }
 
+// umx_trainer_evaluate_objects / umx_trainer_object_counts: the options checked and the workspace there before anything is enqueued
+int object_begin(umx_trainer* tr, umx_trainset* ts, const umx_object_options* o, const char* what) {
+    char why[160];
+    if (umx_object_options_check(o, ts->K, why, sizeof why) != UMX_OK) return tsfail(tr, UMX_ERR_INVALID, "%s: %s", what, why);
+    const TrainerIO io = trainer_io(tr);
+    if (io.P > kObjectMaxTile) return tsfail(tr, UMX_ERR_INVALID, "%s: a tile of %d pixels a side, the object pass takes up to %d", what, io.P, kObjectMaxTile);
+    TS_HIP(tr, hipSetDevice(io.device));
+    ObjectWorkspace& w = ts->obj;
+    if (w.planes) return UMX_OK;
+    const size_t part = (size_t)io.B * io.P * io.P, slots = object_table_slots(io.P);
+    const size_t need = 2 * part + 6 * part * sizeof(int) + (size_t)io.B * slots * (sizeof(unsigned long long) + sizeof(int)) +
+                        (size_t)io.B * UMX_OBJECT_COUNTS * sizeof(long long);
+    size_t free_b = 0, total_b = 0;
+    if (umx_device_mem_info(io.device, &free_b, &total_b) != UMX_OK) return tsfail(tr, UMX_ERR_HIP, "%s", umx_last_error(nullptr));
+    if (need > free_b)
+        return tsfail(tr, UMX_ERR_OOM, "%s: the object workspace of %d images of %d x %d needs %.1f MB, %.1f MB are free", what, io.B, io.P,
+                      io.P, need / 1e6, free_b / 1e6);
+    ObjectWorkspace n;
+    n.B = io.B; n.P = io.P; n.slots = slots;
+    TS_TRY(ts_alloc(ts, &n.planes, 2 * part));
+    TS_TRY(ts_alloc(ts, &n.words, 6 * part));
+    TS_TRY(ts_alloc(ts, &n.keys, (size_t)io.B * slots));
+    TS_TRY(ts_alloc(ts, &n.overlap, (size_t)io.B * slots));
+    TS_TRY(ts_alloc(ts, &n.counts, (size_t)io.B * UMX_OBJECT_COUNTS));
+    w = n;
+    return UMX_OK;
+}
+
+// umx_trainer_evaluate (o == nullptr: nothing below the class counts is enqueued or read) and umx_trainer_evaluate_objects
+int evaluate_batch(umx_trainer* tr, umx_trainset* ts, const umx_sample_desc* desc, int n, const umx_object_options* o, int64_t* counts,
+                   double* loss_sum, int64_t* objects, uint8_t* truth_codes, uint8_t* pred_codes, const char* what) {
+    if (!tr) return tsfail(nullptr, UMX_ERR_INVALID, "null trainer");
+    const TrainerIO io = trainer_io(tr);
+    TS_TRY(check_descs(tr, ts, desc, n, io.B, what));
+    if (!counts || !loss_sum || (o && !objects)) return tsfail(tr, UMX_ERR_INVALID, "null argument");
+    if (o) TS_TRY(object_begin(tr, ts, o, what));
+    TS_TRY(trainer_eval_begin(tr));
+    TS_TRY(enqueue_assemble(tr, ts, desc, n, false));
+    TS_TRY(trainer_eval_forward(tr));
+    TS_HIP(tr, launch_class_counts(io.probs, io.labels, (size_t)n * io.P * io.P, io.K, ts->part, ts->counts, ts->loss, io.stream));
+    long long c[2 * kMaxClasses];
+    double l = 0.0;
+    TS_HIP(tr, hipMemcpyAsync(c, ts->counts, 2 * io.K * sizeof(long long), hipMemcpyDeviceToHost, io.stream));
+    TS_HIP(tr, hipMemcpyAsync(&l, ts->loss, sizeof l, hipMemcpyDeviceToHost, io.stream));
+    std::vector<long long> per;
+    if (o) {
+        const ObjectWorkspace& w = ts->obj;
+        const size_t npix = (size_t)n * io.P * io.P, part = (size_t)w.B * w.P * w.P;
+        per.resize((size_t)n * UMX_OBJECT_COUNTS);
+        TS_HIP(tr, launch_object_planes(io.probs, io.labels, n, io.P, io.K, w.planes, w.planes + part, io.stream));
+        TS_HIP(tr, launch_object_counts(w, n, o->object_code, o->min_area, io.stream));
+        TS_HIP(tr, hipMemcpyAsync(per.data(), w.counts, per.size() * sizeof(long long), hipMemcpyDeviceToHost, io.stream));
+        if (truth_codes) TS_HIP(tr, hipMemcpyAsync(truth_codes, w.planes, npix, hipMemcpyDeviceToHost, io.stream));
+        if (pred_codes) TS_HIP(tr, hipMemcpyAsync(pred_codes, w.planes + part, npix, hipMemcpyDeviceToHost, io.stream));
+    }
+    const int rc = trainer_eval_end(tr);
+    TS_TRY(guard_check(tr, ts));   // (a damaged zone before a range report)
+    TS_TRY(rc);
+    for (int q = 0; q < 2 * io.K; ++q) counts[q] = c[q];
+    *loss_sum = l;
+    if (o)
+        for (int q = 0; q < UMX_OBJECT_COUNTS; ++q) {
+            objects[q] = 0;
+            for (int i = 0; i < n; ++i) objects[q] += per[(size_t)i * UMX_OBJECT_COUNTS + q];
+        }
+    return UMX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1013,23 +1083,40 @@ int umx_trainset_set_augment(umx_trainset* ts, const umx_augment_table* table) {
 }
 
 int umx_trainer_evaluate(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, int n, int64_t* counts, double* loss_sum) {
+    // (without options the set is only read)
+    return evaluate_batch(tr, const_cast<umx_trainset*>(ts), desc, n, nullptr, counts, loss_sum, nullptr, nullptr, nullptr, "umx_trainer_evaluate");
+}
+
+int umx_trainer_evaluate_objects(umx_trainer* tr, umx_trainset* ts, const umx_sample_desc* desc, int n, const umx_object_options* o,
+                                 int64_t* counts, double* loss_sum, int64_t* objects, uint8_t* truth_codes, uint8_t* pred_codes) {
+    if (!o) return tsfail(tr, UMX_ERR_INVALID, "umx_trainer_evaluate_objects: null object options");
+    return evaluate_batch(tr, ts, desc, n, o, counts, loss_sum, objects, truth_codes, pred_codes, "umx_trainer_evaluate_objects");
+}
+
+int umx_trainer_object_counts(umx_trainer* tr, umx_trainset* ts, const uint8_t* truth_codes, const uint8_t* pred_codes, int n,
+                              const umx_object_options* o, int64_t* per_image, int32_t* truth_labels, int32_t* pred_labels) {
+    const char* what = "umx_trainer_object_counts";
     if (!tr) return tsfail(nullptr, UMX_ERR_INVALID, "null trainer");
+    if (!ts || !truth_codes || !pred_codes || !per_image) return tsfail(tr, UMX_ERR_INVALID, "null argument");
+    if (ts->tr != tr) return tsfail(tr, UMX_ERR_INVALID, "%s: the training set belongs to another trainer", what);
     const TrainerIO io = trainer_io(tr);
-    TS_TRY(check_descs(tr, ts, desc, n, io.B, "umx_trainer_evaluate"));
-    if (!counts || !loss_sum) return tsfail(tr, UMX_ERR_INVALID, "null argument");
-    TS_TRY(trainer_eval_begin(tr));
-    TS_TRY(enqueue_assemble(tr, ts, desc, n, false));
-    TS_TRY(trainer_eval_forward(tr));
-    TS_HIP(tr, launch_class_counts(io.probs, io.labels, (size_t)n * io.P * io.P, io.K, ts->part, ts->counts, ts->loss, io.stream));
-    long long c[2 * kMaxClasses];
-    double l = 0.0;
-    TS_HIP(tr, hipMemcpyAsync(c, ts->counts, 2 * io.K * sizeof(long long), hipMemcpyDeviceToHost, io.stream));
-    TS_HIP(tr, hipMemcpyAsync(&l, ts->loss, sizeof l, hipMemcpyDeviceToHost, io.stream));
-    const int rc = trainer_eval_end(tr);
-    TS_TRY(guard_check(tr, ts));   // (a damaged zone before a range report)
-    TS_TRY(rc);
-    for (int q = 0; q < 2 * io.K; ++q) counts[q] = c[q];
-    *loss_sum = l;
+    if (n < 1 || n > io.B) return tsfail(tr, UMX_ERR_INVALID, "%s: %d images, the batch holds 1..%d", what, n, io.B);
+    TS_TRY(object_begin(tr, ts, o, what));
+    const ObjectWorkspace& w = ts->obj;
+    const size_t plane = (size_t)w.P * w.P, npix = (size_t)n * plane, part = (size_t)w.B * plane;
+    TS_HIP(tr, hipMemcpyAsync(w.planes, truth_codes, npix, hipMemcpyHostToDevice, io.stream));
+    TS_HIP(tr, hipMemcpyAsync(w.planes + part, pred_codes, npix, hipMemcpyHostToDevice, io.stream));
+    TS_HIP(tr, launch_object_rule(w.planes, w.planes + part, n, w.P, io.stream));
+    TS_HIP(tr, launch_object_counts(w, n, o->object_code, o->min_area, io.stream));
+    std::vector<long long> per((size_t)n * UMX_OBJECT_COUNTS);
+    TS_HIP(tr, hipMemcpyAsync(per.data(), w.counts, per.size() * sizeof(long long), hipMemcpyDeviceToHost, io.stream));
+    if (truth_labels) TS_HIP(tr, hipMemcpyAsync(truth_labels, w.words, npix * sizeof(int), hipMemcpyDeviceToHost, io.stream));
+    if (pred_labels) TS_HIP(tr, hipMemcpyAsync(pred_labels, w.words + part, npix * sizeof(int), hipMemcpyDeviceToHost, io.stream));
+    TS_HIP(tr, hipStreamSynchronize(io.stream));
+    TS_TRY(guard_check(tr, ts));
+    for (size_t q = 0; q < per.size(); ++q) per_image[q] = per[q];
+    for (int32_t* lab : {truth_labels, pred_labels})       // the planes hold roots (-1 off the objects): a label is root + 1
+        for (size_t q = 0; lab && q < npix; ++q) lab[q] += 1;
     return UMX_OK;
 }
 

@@ -6,13 +6,14 @@
                                    [--rotate-prob P] [--zoom-prob P] [--zoom-range LO,HI]
                                    [--elastic-sigma PX] [--elastic-prob P] [--elastic-grid G]
                                    [--border-sigma PX [--border-class K]]
+                                   [--object-score [--object-class K] [--object-min-area A] [--select pixel|object]]
                                    [--from-scratch [--init-seed S] [--std-dev0 V] [--mean M --std S]]
 
 ``--train`` / ``--valid`` hold the reference's published layout (``I%05d_Img.tif`` / ``_Ant.tif`` / ``_wt.tif``, see
 unmicst_amd/trainset.py).  Both sets are uploaded to the device once; each step draws its batch with ``Sampler`` and trains with
 ``Trainer.step_sampled`` under the reference trainer's regime for the model's graph (legacy / solo / duo options, label weights
 and jitter).  Every ``--eval-every`` steps the whole validation set is evaluated on the device; the checkpoint with the lowest mean
-per-class pixel error is written to ``<out>/umx_model.npz`` with the base model's normalisation mean / std, so
+per-class pixel error (or, with ``--select object``, the highest object F1) is written to ``<out>/umx_model.npz`` with the base model's normalisation mean / std, so
 ``UnMicst.py --model <out>`` runs on it, and every evaluation is one line of ``<out>/finetune_log.jsonl``.
 
 Computed defocus and saturation, for sets with one in-focus plane per sample (the published sets carry re-imaged defocused and
@@ -46,6 +47,18 @@ and the second nearest 4-connected object of class ``--border-class K`` (0-based
 reference never makes them ("Border weight maps").  A sample with a ``_wt.tif`` keeps it.  The legacy graph's
 loss takes no weights, so the flag is refused there.  With the flag the log's first line carries the ``"border"`` object (after
 ``"elastic"``): sigma, class, radius and ``"computed": [n_train, n_valid]``, the samples whose map was computed.
+
+Object score, for users who count objects: the pixel error cannot see whether touching nuclei come apart (two of them merged through a
+three-pixel bridge cost three pixels).  ``--object-score`` adds an object pass to every evaluation, on the device and on the same forward
+pass (``umx_trainer_evaluate_objects``; DESIGN.md section 9.2, "Object score" -- this project's own definition, the reference has only the
+pixel error): per validation crop, the 4-connected objects of class ``--object-class K`` (0-based; default: the last class, nuclei) in the
+annotation and in the arg-max prediction -- predicted ones below ``--object-min-area A`` pixels (default 1) dropped -- are paired by
+overlap; every evaluation line of the log gains ``"objects"``: ``truth``, ``predicted``, ``matched`` (IoU > 1/2), ``matched75`` (IoU > 3/4),
+``merged``, ``split`` and ``f1 = 2 matched / (truth + predicted)`` (``null`` when there is no object on either side).  ``--select object``
+keeps the checkpoint with the highest F1 instead of the lowest mean per-class pixel error (an F1 that is not a number never replaces a
+kept checkpoint; ties keep the earlier step); ``--select pixel`` is the default.  With ``--object-score`` the log's first line carries the
+``"objects"`` settings object (after ``"border"``): class, min_area and select.  Without it the log and the saved model are byte for
+byte what they were.
 
 ``--from-scratch`` starts from the graph's initial state instead of the model's weights (the reference's
 ``train(..., restoreVariables=False)``: ``tf.global_variables_initializer()``, made on the device by ``Trainer.from_scratch``; DESIGN.md
@@ -105,6 +118,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--border-sigma", type=float, default=None,
                    help="compute the weight map of samples without _wt.tif: sigma of the border term in pixels, in (0, 8]")
     p.add_argument("--border-class", type=int, default=None, help="0-based class of the objects (default: the last class); needs --border-sigma")
+    p.add_argument("--object-score", action="store_true", help="add the object-level score to every evaluation")
+    p.add_argument("--object-class", type=int, default=None, help="0-based class of the objects (default: the last class); needs --object-score")
+    p.add_argument("--object-min-area", type=int, default=None,
+                   help="predicted objects below this many pixels are dropped, 1..%d (default 1); needs --object-score" % trainer.OBJECT_MAX_MIN_AREA)
+    p.add_argument("--select", choices=("pixel", "object"), default=None,
+                   help="keep the checkpoint with the lowest mean per-class pixel error (default) or the highest object F1 (needs --object-score)")
     p.add_argument("--from-scratch", action="store_true", help="start from the graph's initial state, not from the model's weights")
     p.add_argument("--init-seed", type=int, default=None, help="seed of the initial state (default: --seed); needs --from-scratch")
     p.add_argument("--std-dev0", type=float, default=None,
@@ -228,6 +247,42 @@ def border_settings(args, hp=None):
     return {"sigma": float(sigma), "class": None if cls is None else int(cls), "radius": opts.radius}
 
 
+def object_settings(args, hp=None):
+    """The four object-score flags -> None without --object-score, else {"class", "min_area", "select"}.  ``hp`` (the model's
+    hyper-parameters) adds the check that depends on the model and resolves the default class; without it only the flags are checked and
+    a class left open stays None.  Raises Refusal."""
+    cls, area, select = (getattr(args, k, None) for k in ("object_class", "object_min_area", "select"))
+    if not getattr(args, "object_score", False):
+        for flag, v in (("--object-class", cls), ("--object-min-area", area)):
+            if v is not None:
+                raise Refusal("%s needs --object-score" % flag)
+        if select == "object":
+            raise Refusal("--select object needs --object-score")
+        return None
+    if cls is not None and cls < 0:
+        raise Refusal("--object-class %r: classes are 0-based" % cls)
+    area = 1 if area is None else area
+    if not 1 <= area <= trainer.OBJECT_MAX_MIN_AREA:
+        raise Refusal("--object-min-area %r: an area is 1..%d pixels" % (area, trainer.OBJECT_MAX_MIN_AREA))
+    if hp is not None:
+        if cls is not None and cls >= hp.nClasses:
+            raise Refusal("--object-class %d: the model has classes 0..%d" % (cls, hp.nClasses - 1))
+        if cls is None:
+            cls = hp.nClasses - 1
+    return {"class": None if cls is None else int(cls), "min_area": int(area), "select": select or "pixel"}
+
+
+def better_f1(f1: float, kept) -> bool:
+    """Whether an evaluation with this F1 replaces the kept one (``kept`` = its F1, or None when nothing is kept yet: the first
+    evaluation is always kept, so that the run leaves a model).  An F1 that is not a number never replaces a kept checkpoint; an equal
+    one keeps the earlier step."""
+    if kept is None:
+        return True
+    if math.isnan(f1):
+        return False
+    return math.isnan(kept) or f1 > kept
+
+
 def augment_settings(args):
     """The four augmentation flags -> None when none is given, else {"blur_sigmas", "blur_prob", "saturate_prob", "max_gain"}.
     Raises Refusal."""
@@ -284,6 +339,7 @@ def prepare(args):
     warp_settings(args)
     elastic_settings(args)
     border_settings(args)
+    object_settings(args)
     scratch = init_settings(args) is not None
     path = resolve_model(args.model)
     if not os.path.isdir(path):
@@ -309,6 +365,7 @@ def prepare(args):
     hp = art.hp
     elastic_settings(args, hp.imSize)
     border_settings(args, hp)
+    object_settings(args, hp)
     sets = []
     for what, d in (("--train", args.train), ("--valid", args.valid)):
         try:
@@ -329,6 +386,9 @@ def run(args) -> int:
     hp = art.hp
     elastic = elastic_settings(args, hp.imSize)
     border = border_settings(args, hp)
+    objects = object_settings(args, hp)
+    oopts = None if objects is None else trainset.ObjectOptions(objects["class"], objects["min_area"])
+    by_f1 = objects is not None and objects["select"] == "object"
     kind = trainset.graph_kind(hp)
     lw = trainset.LABEL_WEIGHTS[kind]
     init = init_settings(args, resolve_model(args.model))
@@ -364,23 +424,30 @@ def run(args) -> int:
         best = None
         train_loss = None
         with open(log_path, "w") as log:
-            settings = {k: v for k, v in (("init", init), ("augment", aug), ("warp", warp), ("elastic", elastic), ("border", border))
-                        if v is not None}
+            settings = {k: v for k, v in (("init", init), ("augment", aug), ("warp", warp), ("elastic", elastic), ("border", border),
+                                          ("objects", objects)) if v is not None}
             if settings:
                 log.write(json.dumps(settings) + "\n")
             for step in range(args.steps + 1):
                 if step % args.eval_every == 0 or step == args.steps:
-                    ev = tr.evaluate(vs, vdesc)
+                    ev = tr.evaluate(vs, vdesc) if oopts is None else tr.evaluate(vs, vdesc, objects=oopts)
                     err = [None if math.isnan(e) else float(e) for e in ev["per_class_error"]]
                     seen = [e for e in err if e is not None]
                     mean_err = float(np.mean(seen)) if seen else float("nan")
                     rec = {"step": step, "train_loss": train_loss, "loss": ev["loss"], "per_class_error": err, "mean_error": mean_err,
                            "labelled": [int(v) for v in ev["counts"][1]]}
+                    f1 = float("nan")
+                    if oopts is not None:
+                        f1 = ev["objects"]["f1"]
+                        rec["objects"] = dict(ev["objects"], f1=None if math.isnan(f1) else f1)
                     log.write(json.dumps(rec) + "\n")
                     log.flush()
                     print("step %d: validation loss %.6g, per-class error %s" % (step, ev["loss"], err), flush=True)
-                    if best is None or mean_err < best[0]:
-                        best = (mean_err, step)
+                    if oopts is not None:
+                        print("step %d: objects %s" % (step, json.dumps(rec["objects"])), flush=True)
+                    keep = better_f1(f1, None if best is None else best[0]) if by_f1 else best is None or mean_err < best[0]
+                    if keep:
+                        best = (f1 if by_f1 else mean_err, step)
                         model.save_converted(model.ModelArtefacts(hp, tr.blob(), art.mean, art.std), args.out)
                 if step == args.steps:
                     break
@@ -396,7 +463,8 @@ def run(args) -> int:
                     tr.step_augmented(ts, *sampler.next_augmented())
                 if (step + 1) % args.eval_every == 0 or step + 1 == args.steps:
                     train_loss = tr.loss()[0]
-        print("best mean per-class error %.6g at step %d -> %s" % (best[0], best[1], os.path.join(args.out, model.CONVERTED_NAME)))
+        print("best %s %.6g at step %d -> %s" % ("object F1" if by_f1 else "mean per-class error", best[0], best[1],
+                                                 os.path.join(args.out, model.CONVERTED_NAME)))
     finally:
         tr.close()
     return 0

@@ -33,6 +33,7 @@ EXPORTS = [
     "umx_train_step_augmented", "umx_trainer_assemble_augmented", "umx_warp_desc_check", "umx_train_step_warped",
     "umx_trainer_assemble_warped", "umx_trainer_init", "umx_elastic_desc_check", "umx_train_step_elastic",
     "umx_trainer_assemble_elastic", "umx_border_options_check", "umx_trainset_border_weights", "umx_trainset_border_planes",
+    "umx_object_options_check", "umx_trainer_evaluate_objects", "umx_trainer_object_counts",
 ]
 
 
@@ -118,6 +119,21 @@ BORDER_MAX_SIGMA, BORDER_CONNECTIVITY = 8.0, 4
 class BorderOptionsC(ctypes.Structure):
     """``umx_border_options`` (include/umx_train.h)."""
     _fields_ = [("object_code", ctypes.c_int32), ("sigma", ctypes.c_float), ("reserved", ctypes.c_int32 * 6)]
+
+
+# ``umx_object_options``: the object score of the validation pass (DESIGN.md section 9.2, "Object score")
+OBJECT_COUNTS, OBJECT_MAX_MIN_AREA = 8, 65536
+OBJECT_COUNT_NAMES = ("truth", "predicted", "matched", "matched75", "merged", "split")
+
+
+class ObjectOptionsC(ctypes.Structure):
+    """``umx_object_options`` (include/umx_train.h)."""
+    _fields_ = [("object_code", ctypes.c_int32), ("min_area", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6)]
+
+
+def object_f1(matched: int, truth: int, predicted: int) -> float:
+    """``2 matched / (truth + predicted)``; NaN when there is no object on either side."""
+    return 2.0 * matched / (truth + predicted) if truth + predicted else float("nan")
 
 
 def solo_options(**kw) -> TrainOptions:
@@ -234,6 +250,15 @@ def _bind(L):
     L.umx_trainset_border_weights.argtypes = [c_void_p, c_int, ctypes.POINTER(BorderOptionsC)]
     L.umx_trainset_border_planes.restype = c_int
     L.umx_trainset_border_planes.argtypes = [c_void_p, c_int, ctypes.POINTER(BorderOptionsC), c_void_p, c_void_p, c_void_p, c_void_p]
+    # object score (umx_object_options)
+    L.umx_object_options_check.restype = c_int
+    L.umx_object_options_check.argtypes = [ctypes.POINTER(ObjectOptionsC), c_int, ctypes.c_char_p, ctypes.c_size_t]
+    L.umx_trainer_evaluate_objects.restype = c_int
+    L.umx_trainer_evaluate_objects.argtypes = [c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(ObjectOptionsC),
+                                               ctypes.POINTER(ctypes.c_int64), dp, ctypes.POINTER(ctypes.c_int64), c_void_p, c_void_p]
+    L.umx_trainer_object_counts.restype = c_int
+    L.umx_trainer_object_counts.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(ObjectOptionsC), c_void_p,
+                                            c_void_p, c_void_p]
     # debug guard mode (UMX_DEBUG_GUARD): the host scan of one red zone
     L.umx_guard_scan.restype = c_int
     L.umx_guard_scan.argtypes = [c_void_p, ctypes.c_size_t, c_int, ctypes.c_size_t, c_int, ctypes.c_char_p, ctypes.c_char_p,
@@ -518,10 +543,13 @@ class Trainer:
                                                            labels.ctypes.data, None if weights is None else weights.ctypes.data))
         return data, labels, weights
 
-    def evaluate(self, ts, descs) -> dict:
+    def evaluate(self, ts, descs, objects=None) -> dict:
         """The validation pass over any number of descriptors, B at a time (eval mode: moving statistics, no dropout):
         {"per_class_error": 1 - correct / labelled per class (nan for a class with no pixel; UnMicst1-5.py:386-397),
-         "loss": mean -log p[label] over labelled pixels, "loss_sum": its sum, "counts": int64 [2, K] = correct | labelled}."""
+         "loss": mean -log p[label] over labelled pixels, "loss_sum": its sum, "counts": int64 [2, K] = correct | labelled}.
+        ``objects`` (a ``trainset.ObjectOptions``): the object pass runs on the same forward (umx_trainer_evaluate_objects) and the
+        result gains "objects": {"truth", "predicted", "matched", "matched75", "merged", "split"} summed over all chunks, and "f1" =
+        2 matched / (truth + predicted) (nan without objects).  The other entries are what they are without it."""
         d = np.ascontiguousarray(descs, dtype=SAMPLE_DESC).reshape(-1)
         if d.size == 0:
             raise ValueError("no descriptors to evaluate")
@@ -530,18 +558,66 @@ class Trainer:
         loss_sum = 0.0
         part = np.zeros(2 * K, np.int64)
         ls = ctypes.c_double()
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        oc = None if objects is None else objects.c_struct(K)
+        obj_total, obj_part = np.zeros(OBJECT_COUNTS, np.int64), np.zeros(OBJECT_COUNTS, np.int64)
         for b0 in range(0, d.size, self.batch):
             chunk = np.ascontiguousarray(d[b0:b0 + self.batch])
-            self._check(self._lib.umx_trainer_evaluate(self._h, ts._handle(), chunk.ctypes.data, chunk.size,
-                                                       part.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(ls)))
+            if oc is None:
+                self._check(self._lib.umx_trainer_evaluate(self._h, ts._handle(), chunk.ctypes.data, chunk.size,
+                                                           part.ctypes.data_as(i64p), ctypes.byref(ls)))
+            else:
+                self._check(self._lib.umx_trainer_evaluate_objects(self._h, ts._handle(), chunk.ctypes.data, chunk.size, ctypes.byref(oc),
+                                                                   part.ctypes.data_as(i64p), ctypes.byref(ls),
+                                                                   obj_part.ctypes.data_as(i64p), None, None))
+                obj_total += obj_part
             total += part
             loss_sum += ls.value
         counts = total.reshape(2, K)
         with np.errstate(invalid="ignore", divide="ignore"):
             err = 1.0 - counts[0] / counts[1].astype(np.float64)
         n_lab = int(counts[1].sum())
-        return {"per_class_error": err, "loss": loss_sum / n_lab if n_lab else float("nan"), "loss_sum": loss_sum,
-                "counts": counts}
+        out = {"per_class_error": err, "loss": loss_sum / n_lab if n_lab else float("nan"), "loss_sum": loss_sum,
+               "counts": counts}
+        if oc is not None:
+            o = {name: int(v) for name, v in zip(OBJECT_COUNT_NAMES, obj_total)}
+            o["f1"] = object_f1(o["matched"], o["truth"], o["predicted"])
+            out["objects"] = o
+        return out
+
+    def evaluate_objects(self, ts, desc, objects):
+        """One chunk of n <= B descriptors through umx_trainer_evaluate_objects, with the planes: (counts int64 [2, K], loss_sum,
+        objects int64 [8], truth_codes uint8 [n, P, P], pred_codes uint8 [n, P, P]).  Diagnostics and tests."""
+        d = self._descs(desc, self.batch)
+        K, P = self.hp.nClasses, self.hp.imSize
+        oc = objects.c_struct(K)
+        counts, obj = np.zeros(2 * K, np.int64), np.zeros(OBJECT_COUNTS, np.int64)
+        ls = ctypes.c_double()
+        truth, pred = np.empty((d.size, P, P), np.uint8), np.empty((d.size, P, P), np.uint8)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        self._check(self._lib.umx_trainer_evaluate_objects(self._h, ts._handle(), d.ctypes.data, d.size, ctypes.byref(oc),
+                                                           counts.ctypes.data_as(i64p), ctypes.byref(ls), obj.ctypes.data_as(i64p),
+                                                           truth.ctypes.data, pred.ctypes.data))
+        return counts.reshape(2, K), ls.value, obj, truth, pred
+
+    def object_counts(self, ts, truth, pred, options, labels: bool = False):
+        """The object pass on n <= B pairs of class-code planes (uint8 [n, P, P]) given by the host (umx_trainer_object_counts): int64
+        [n, 8] = truth, predicted, matched, matched75, merged, split, 0, 0 per image; with ``labels`` also the two int32 label planes
+        [n, P, P] (1 + y * P + x of the component's first pixel, 0 off the objects)."""
+        P = self.hp.imSize
+        t = np.ascontiguousarray(truth, dtype=np.uint8)
+        p = np.ascontiguousarray(pred, dtype=np.uint8)
+        if t.ndim != 3 or t.shape[1:] != (P, P) or p.shape != t.shape or not 1 <= t.shape[0] <= self.batch:
+            raise ValueError("truth and pred must both be [n, %d, %d] with 1 <= n <= %d, got %r and %r" % (P, P, self.batch, t.shape, p.shape))
+        n = t.shape[0]
+        oc = options.c_struct(self.hp.nClasses)
+        per = np.zeros((n, OBJECT_COUNTS), np.int64)
+        tl = np.empty((n, P, P), np.int32) if labels else None
+        pl = np.empty((n, P, P), np.int32) if labels else None
+        self._check(self._lib.umx_trainer_object_counts(self._h, ts._handle(), t.ctypes.data, p.ctypes.data, n, ctypes.byref(oc),
+                                                        per.ctypes.data, None if tl is None else tl.ctypes.data,
+                                                        None if pl is None else pl.ctypes.data))
+        return (per, tl, pl) if labels else per
 
     @property
     def step_count(self) -> int:

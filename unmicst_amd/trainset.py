@@ -31,6 +31,11 @@ the objects' class and a sigma, ``TrainSet.border_weights`` replaces the stored 
 ``exp(-(d1 + d2)^2 / (2 sigma^2))`` of its annotation's 4-connected objects (``umx_trainset_border_weights``; DESIGN.md section 9.2,
 "Border weight maps" -- a reading of the published maps, not something the reference pins), ``TrainSet.border_planes`` returns the
 labels, both squared distances and the map of one sample.
+
+Object score of the validation pass: ``ObjectOptions`` names the objects' class and a least area, ``Trainer.evaluate(ts, descs,
+objects=...)`` then also counts annotated and predicted 4-connected objects, the pairs with IoU > 1/2 and > 3/4, merges and splits, on
+the device (``umx_trainer_evaluate_objects``; DESIGN.md section 9.2, "Object score" -- this project's own definition), and
+``Trainer.object_counts`` runs the same pass on planes the host supplies.
 """
 from __future__ import annotations
 
@@ -44,7 +49,8 @@ import numpy as np
 
 from . import imtools, tiffio
 from .trainer import (AUGMENT_DESC, AUGMENT_MAX_LEVELS, AUGMENT_MAX_RADIUS, BORDER_MAX_SIGMA, ELASTIC_DESC, ELASTIC_MAX_DISP,
-                      ELASTIC_MAX_GRID, SAMPLE_DESC, WARP_DESC, AugmentTableC, BorderOptionsC, LabelWeightsC)
+                      ELASTIC_MAX_GRID, OBJECT_MAX_MIN_AREA, SAMPLE_DESC, WARP_DESC, AugmentTableC, BorderOptionsC, LabelWeightsC,
+                      ObjectOptionsC)
 
 
 @dataclass(frozen=True)
@@ -192,6 +198,33 @@ class BorderOptions:
     def c_struct(self, n_classes: int) -> BorderOptionsC:
         o = BorderOptionsC()
         o.object_code, o.sigma = self.object_code(n_classes), float(self.sigma)
+        return o
+
+
+@dataclass(frozen=True)
+class ObjectOptions:
+    """``umx_object_options``: ``object_class`` the 0-based class of the objects, None = the last class (nuclei in the reference's sets);
+    ``min_area`` in pixels, 1..65536: predicted objects below it are dropped before anything is counted."""
+    object_class: Optional[int] = None
+    min_area: int = 1
+
+    def __post_init__(self):
+        if self.object_class is not None and (int(self.object_class) != self.object_class or self.object_class < 0):
+            raise ValueError("object_class is a 0-based class index or None, got %r" % (self.object_class,))
+        whole = isinstance(self.min_area, (int, np.integer)) or (isinstance(self.min_area, float) and self.min_area.is_integer())
+        if not whole or not 1 <= self.min_area <= OBJECT_MAX_MIN_AREA:
+            raise ValueError("min_area is 1..%d pixels, got %r" % (OBJECT_MAX_MIN_AREA, self.min_area))
+
+    def object_code(self, n_classes: int) -> int:
+        """The class code of the objects: class + 1."""
+        k = n_classes - 1 if self.object_class is None else int(self.object_class)
+        if not 0 <= k < n_classes:
+            raise ValueError("object_class %d: the model has classes 0..%d" % (k, n_classes - 1))
+        return k + 1
+
+    def c_struct(self, n_classes: int) -> ObjectOptionsC:
+        o = ObjectOptionsC()
+        o.object_code, o.min_area = self.object_code(n_classes), int(self.min_area)
         return o
 
 
@@ -574,5 +607,5 @@ def graph_kind(hp) -> str:
     return "solo" if hp.nChannels == 1 else "duo"
 
 
-__all__ = ["LabelWeights", "UNWEIGHTED", "LABEL_WEIGHTS", "default_jitter", "BorderOptions", "TrainSet", "Dataset", "dataset_indices",
+__all__ = ["LabelWeights", "UNWEIGHTED", "LABEL_WEIGHTS", "default_jitter", "BorderOptions", "ObjectOptions", "TrainSet", "Dataset", "dataset_indices",
            "read_dataset_dir", "Sampler", "gaussian_taps", "AugmentTable", "AUGMENT_DESC", "warp_matrix", "WARP_DESC", "elastic_lattice", "ELASTIC_DESC", "crop_origins", "validation_descriptors", "upload", "graph_kind", "SAMPLE_DESC"]
