@@ -300,6 +300,28 @@ UMX_API int umx_prof_entry_size(void);
 UMX_API void umx_test_double_to_half(const double* in, uint16_t* out, size_t n);
 /* the same conversion by the DEVICE routine the stitch kernel uses (needs a GPU): must equal the host routine bit for bit */
 UMX_API int umx_test_double_to_half_dev(const double* in, uint16_t* out, size_t n);
+/* Test entries of the driver-side image kernels (--scalingFactor, --outlier, the device-side range search): each is a thin
+ * wrapper around the production function on caller-given planes, so that the kernels can be held to scipy / numpy plane by
+ * plane and not only through a whole network and a uint8 cast (tests/test_gpu_imagekernels.py).
+ * umx_test_gauss_weights (host only): the anti-aliasing weights the resize builds for one axis, out[0] = centre tap ..
+ *   out[radius]; returns the radius, or -1 (sigma <= 1e-15, radius + 1 > cap, radius beyond the resize kernel's limit). */
+UMX_API int umx_test_gauss_weights(double sigma, double* out, int cap);
+/* One resize [H, W] -> [h, w] of a float64 plane as the scaled path runs it (Gaussian when an axis shrinks, order-1 zoom, clip
+ * to the filtered plane's range); out_f64 [h, w] and / or out_u8 [h, w] = np.uint8(255 * .), the form of the way back.
+ * out_filtered [H, W] (or NULL): the plane the zoom read, i.e. the source after the Gaussian. */
+UMX_API int umx_test_resize_dev(const double* src_f64, int H, int W, int h, int w, double* out_f64, uint8_t* out_u8,
+                                double* out_filtered);
+/* rescale_intensity(plane, (min, limit), (0, 0.983)) of n non-negative doubles: limit = max when outlier < 0, else
+ * np.percentile(plane, outlier).  out_plane [n]; range2 = (min, limit). */
+UMX_API int umx_test_rescale_dev(const double* plane_f64, size_t n, double outlier, double* out_plane, double* range2);
+/* The device range search of the raw entry points, njobs planes per call (raw holds them back to back, bits = 8 | 16): plane j
+ * of n[j] elements is copied to offset_elems[j] elements past a 256-byte-aligned device address and reduced over nslabs[j]
+ * consecutive slabs (of odd length when nslabs[j] > 1), accumulating as the slab-wise upload does.  range2 [njobs][2] = (min, max). */
+UMX_API int umx_test_plane_range_dev(const void* raw, int bits, const size_t* n, const size_t* offset_elems, const int* nslabs,
+                                     int njobs, uint32_t* range2);
+/* The drivers' uint8 cast of n float16 probabilities: out_u8 = np.uint8(255 * (np.uint8(255 * pm) * (1 / 255))) (the identity
+ * grid), out_f64 = np.uint8(255 * pm) * (1 / 255) (the plane a resize back to the raw size starts from). */
+UMX_API int umx_test_half_to_u8_dev(const uint16_t* half_bits, size_t n, uint8_t* out_u8, double* out_f64);
 UMX_API int umx_describe(const umx_hparams* hp, int* n_launches, double* flops_per_tile, double* executed_flops_per_tile);
 /* The library's wiring of a model as JSON text (host only): activation buffers (spatial size, channels), the launch list in
  * execution order -- per launch its operand groups (source buffer, channels, filter taps: concat order = group order), output

@@ -255,7 +255,7 @@ def test_duo_script_on_a_two_page_ome_tiff_4096(tmp_path):
     assert np.array_equal(prev[0], want[1])
 
 
-@pytest.mark.parametrize("scaling,rescale", [(0.5, True), (0.75, False), (1.6, True)])
+@pytest.mark.parametrize("scaling,rescale", [(0.5, True), (0.75, False), (1.6, True), (0.3, True)])
 def test_scaled_raw_path_matches_the_host_recipe(scaling, rescale):
     """--scalingFactor != 1 on the device (umx_infer_image_raw_scaled: skimage.transform.resize's defaults restated in
     float64 kernels, both ways) against the host-side recipe (unmicst_amd/imtools.py: scipy.ndimage gaussian_filter + zoom):

@@ -353,12 +353,52 @@ int umx_infer_image_raw_range(umx_ctx* ctx, const void* raw_host, int bits, int 
     return host_submit(ctx, 0, true, raw_host, bits, C_img, H, W, 1, range, mean, stdv, mode, UMX_STITCH_FP16_COMPAT, 1, out_host);
 }
 
+// numpy's float64 add.reduce over a contiguous vector (what ndarray.sum() runs): sequential below 8 terms, eight accumulators
+// combined pairwise up to 128 terms with the tail added in order, two halves (the first a multiple of 8) beyond
+static double pairwise_sum(const double* a, size_t n) {
+    if (n < 8) {
+        double res = 0.0;
+        for (size_t i = 0; i < n; ++i) res += a[i];
+        return res;
+    }
+    if (n <= 128) {
+        double r[8];
+        for (int j = 0; j < 8; ++j) r[j] = a[j];
+        size_t i = 8;
+        for (; i < n - n % 8; i += 8)
+            for (int j = 0; j < 8; ++j) r[j] += a[i + j];
+        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (; i < n; ++i) res += a[i];
+        return res;
+    }
+    size_t n2 = n / 2;
+    n2 -= n2 % 8;
+    return pairwise_sum(a, n2) + pairwise_sum(a + n2, n - n2);
+}
+
+// The anti-aliasing weights of one axis in scipy.ndimage's operation order (_gaussian_kernel1d): radius = int(4 sigma + 0.5),
+// phi = exp(c * (x * x)) with c = -0.5 / (sigma * sigma), divided by phi.sum().  wts[0] is the centre tap.  What is left to the
+// platform is exp itself: numpy's and the C library's differ by an ulp on a few taps (DESIGN.md has the table).
+static int gauss_weights(double sigma, std::vector<double>* wts) {
+    const int radius = (int)(4.0 * sigma + 0.5);
+    const double c = -0.5 / (sigma * sigma);
+    std::vector<double> full(2 * (size_t)radius + 1);
+    for (int x = -radius; x <= radius; ++x) full[x + radius] = std::exp(c * ((double)x * (double)x));
+    const double sum = pairwise_sum(full.data(), full.size());
+    wts->resize((size_t)radius + 1);
+    for (int j = 0; j <= radius; ++j) (*wts)[j] = full[radius + j] / sum;
+    return radius;
+}
+
+constexpr int kMaxGaussTaps = 4096;   // radius + 1 weights per axis in the device scratch
+
 // ---- the drivers' whole recipe at --scalingFactor != 1 on the device (reference UnMicst1-5.py:807-821,845-854):
 // raw planes -> im2double -> resize to (int(H*sf), int(W*sf)) -> [rescale_intensity((min, max) -> (0, 0.983))] -> inference
 // -> np.uint8(255 * pm) -> resize back to (H, W) -> np.uint8(255 * .).  One resize = skimage.transform.resize's defaults
 // (umx_kernels.hip).  Synchronous; the planes are small next to the tile work, so nothing is pipelined here.
-static int resize_plane(umx_ctx* ctx, const double* src, int H, int W, int h, int w, double* tmpA, double* tmpB, double* wdev,
-                        unsigned long long* mm64, double* dst, unsigned char* dst_u8) {
+// ctx only receives the error text (NULL from the test entries); *filtered: the plane the zoom read (src, tmpA or tmpB)
+static int resize_plane(umx_ctx* ctx, hipStream_t stream, const double* src, int H, int W, int h, int w, double* tmpA, double* tmpB,
+                        double* wdev, unsigned long long* mm64, double* dst, unsigned char* dst_u8, const double** filtered = nullptr) {
     const double* cur = src;
     const double fy = (double)H / h, fx = (double)W / w;
     const double sig[2] = {std::max(0.0, (fy - 1.0) / 2.0), std::max(0.0, (fx - 1.0) / 2.0)};
@@ -367,23 +407,19 @@ static int resize_plane(umx_ctx* ctx, const double* src, int H, int W, int h, in
         int which = 0;
         for (int axis = 0; axis < 2; ++axis) {
             if (!(sig[axis] > 1e-15)) continue;   // scipy skips axes with sigma <= 1e-15
-            const int radius = (int)(4.0 * sig[axis] + 0.5);
-            std::vector<double> wts((size_t)radius + 1);
-            double sum = 0.0;
-            std::vector<double> full(2 * (size_t)radius + 1);
-            for (int x = -radius; x <= radius; ++x) full[x + radius] = std::exp(-0.5 / (sig[axis] * sig[axis]) * (double)x * (double)x);
-            for (double v : full) sum += v;
-            for (int j = 0; j <= radius; ++j) wts[j] = full[radius + j] / sum;
-            if (radius + 1 > 4096) return fail(ctx, UMX_ERR_INVALID, "scaling factor too small for the resize kernel");
-            HIP_TRY(ctx, hipMemcpyAsync(wdev + axis * 4096, wts.data(), wts.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (wts is a stack-lifetime host buffer)
-            HIP_TRY(ctx, launch_gauss1d(cur, bufs[which], H, W, axis, radius, wdev + axis * 4096, ctx->stream));
+            if (4.0 * sig[axis] + 0.5 >= (double)kMaxGaussTaps) return fail(ctx, UMX_ERR_INVALID, "scaling factor too small for the resize kernel");
+            std::vector<double> wts;
+            const int radius = gauss_weights(sig[axis], &wts);
+            HIP_TRY(ctx, hipMemcpyAsync(wdev + axis * kMaxGaussTaps, wts.data(), wts.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+            HIP_TRY(ctx, hipStreamSynchronize(stream));   // (wts is a stack-lifetime host buffer)
+            HIP_TRY(ctx, launch_gauss1d(cur, bufs[which], H, W, axis, radius, wdev + axis * kMaxGaussTaps, stream));
             cur = bufs[which];
             which ^= 1;
         }
     }
-    HIP_TRY(ctx, launch_minmax_f64(cur, (size_t)H * W, mm64, ctx->stream));   // resize clips to the (filtered) input's range
-    HIP_TRY(ctx, launch_zoom1(cur, H, W, h, w, mm64, dst, dst_u8, ctx->stream));
+    if (filtered) *filtered = cur;
+    HIP_TRY(ctx, launch_minmax_f64(cur, (size_t)H * W, mm64, stream));   // resize clips to the (filtered) input's range
+    HIP_TRY(ctx, launch_zoom1(cur, H, W, h, w, mm64, dst, dst_u8, stream));
     return UMX_OK;
 }
 
@@ -404,7 +440,7 @@ static int infer_raw_scaled_impl(umx_ctx* ctx, const void* raw_host, int bits, i
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
     const size_t o_raw = take(plane * C_img * in_b), o_a = take(big * 8), o_b = take(big * 8), o_c = take(big * 8);
-    const size_t o_in = take(sp * C_img * 8), o_pm = take(K * sp * 2), o_u8 = take(K * plane), o_w = take(2 * 4096 * 8), o_mm = take(256);
+    const size_t o_in = take(sp * C_img * 8), o_pm = take(K * sp * 2), o_u8 = take(K * plane), o_w = take(2 * kMaxGaussTaps * 8), o_mm = take(256);
     const size_t o_sel = take(64 + 512 * 4);   // radix-selection state + histograms of the percentile
     int rc;
     umx_ctx::HostSlot& hs = ctx->hs[0];
@@ -420,7 +456,7 @@ static int infer_raw_scaled_impl(umx_ctx* ctx, const void* raw_host, int bits, i
         HIP_TRY(ctx, launch_minmax_init(mm32, ctx->stream));
         HIP_TRY(ctx, launch_raw_convert(base + o_raw + (size_t)c * plane * in_b, bits, plane, 0, mm32, A, ctx->stream));   // im2double
         if (same) HIP_TRY(ctx, hipMemcpyAsync(din + (size_t)c * sp, A, sp * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        else if ((rc = resize_plane(ctx, A, H, W, h, w, B, Cw, wdev, mm64, din + (size_t)c * sp, nullptr))) return rc;
+        else if ((rc = resize_plane(ctx, ctx->stream, A, H, W, h, w, B, Cw, wdev, mm64, din + (size_t)c * sp, nullptr))) return rc;
         if (rescale) {   // rescale_intensity(I, (min, max | percentile), (0, 0.983)) of the RESIZED plane (UnMicst1-5.py:817-821)
             HIP_TRY(ctx, launch_minmax_f64(din + (size_t)c * sp, sp, mm64, ctx->stream));
             if (outlier >= 0)
@@ -436,7 +472,7 @@ static int infer_raw_scaled_impl(umx_ctx* ctx, const void* raw_host, int bits, i
             continue;
         }
         HIP_TRY(ctx, launch_half_to_u8_f64(base + o_pm + k * sp * 2, sp, A, ctx->stream));   // np.uint8(255 * pm) as float u8/255
-        if ((rc = resize_plane(ctx, A, h, w, H, W, B, Cw, wdev, mm64, nullptr, base + o_u8 + k * plane))) return rc;
+        if ((rc = resize_plane(ctx, ctx->stream, A, h, w, H, W, B, Cw, wdev, mm64, nullptr, base + o_u8 + k * plane))) return rc;
     }
     HIP_TRY(ctx, hipMemcpyAsync(out_host, base + o_u8, K * plane, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -464,6 +500,124 @@ int umx_infer_image_raw_submit(umx_ctx* ctx, int slot, const void* raw_host, int
 int umx_infer_image_wait(umx_ctx* ctx, int slot) {
     if (!ctx) return fail(nullptr, UMX_ERR_INVALID, "ctx is NULL");
     return host_wait(ctx, slot);
+}
+
+// ---- test entries of the driver-side image kernels (tests/test_gpu_imagekernels.py, tests/test_imagekernels_cpu.py): thin wrappers
+// around the production functions above on caller-given planes, on the default stream, with scratch of their own
+
+namespace {
+struct DevScratch {   // one allocation cut into 256-byte-aligned pieces, as infer_raw_scaled_impl cuts the slot's buffer
+    unsigned char* base = nullptr;
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; }
+    ~DevScratch() { if (base) hipFree(base); }
+};
+int test_device(const char* who) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, UMX_ERR_NO_DEVICE, "%s: no HIP device available", who);
+    return UMX_OK;
+}
+}  // namespace
+
+int umx_test_gauss_weights(double sigma, double* out, int cap) {
+    if (!out || !(sigma > 1e-15) || !(4.0 * sigma + 0.5 < (double)kMaxGaussTaps)) return -1;
+    std::vector<double> wts;
+    const int radius = gauss_weights(sigma, &wts);
+    if (radius + 1 > cap) return -1;
+    memcpy(out, wts.data(), wts.size() * sizeof(double));
+    return radius;
+}
+
+int umx_test_resize_dev(const double* src, int H, int W, int h, int w, double* out_f64, uint8_t* out_u8, double* out_filtered) {
+    if (!src || (!out_f64 && !out_u8) || H < 1 || W < 1 || h < 1 || w < 1) return fail(nullptr, UMX_ERR_INVALID, "umx_test_resize_dev: bad arguments");
+    if (const int rc = test_device("umx_test_resize_dev")) return rc;
+    const size_t big = (size_t)std::max(H, h) * std::max(W, w), plane = (size_t)H * W, sp = (size_t)h * w;
+    DevScratch d;
+    const size_t o_a = d.take(big * 8), o_b = d.take(big * 8), o_c = d.take(big * 8), o_dst = d.take(sp * 8), o_u8 = d.take(sp);
+    const size_t o_w = d.take(2 * kMaxGaussTaps * 8), o_mm = d.take(256);
+    HIP_TRY(nullptr, hipMalloc((void**)&d.base, d.off));
+    double *A = (double*)(d.base + o_a), *B = (double*)(d.base + o_b), *Cw = (double*)(d.base + o_c);
+    HIP_TRY(nullptr, hipMemcpy(A, src, plane * 8, hipMemcpyHostToDevice));
+    int rc;
+    const double* filt = nullptr;
+    if (out_f64) {
+        if ((rc = resize_plane(nullptr, nullptr, A, H, W, h, w, B, Cw, (double*)(d.base + o_w), (unsigned long long*)(d.base + o_mm),
+                               (double*)(d.base + o_dst), nullptr, &filt)))
+            return rc;
+        HIP_TRY(nullptr, hipMemcpy(out_f64, d.base + o_dst, sp * 8, hipMemcpyDeviceToHost));
+    }
+    if (out_u8) {
+        if ((rc = resize_plane(nullptr, nullptr, A, H, W, h, w, B, Cw, (double*)(d.base + o_w), (unsigned long long*)(d.base + o_mm),
+                               nullptr, d.base + o_u8, &filt)))
+            return rc;
+        HIP_TRY(nullptr, hipMemcpy(out_u8, d.base + o_u8, sp, hipMemcpyDeviceToHost));
+    }
+    if (out_filtered) HIP_TRY(nullptr, hipMemcpy(out_filtered, filt, plane * 8, hipMemcpyDeviceToHost));
+    return UMX_OK;
+}
+
+int umx_test_rescale_dev(const double* plane, size_t n, double outlier, double* out_plane, double* range2) {
+    if (!plane || !out_plane || !range2 || n == 0 || !(outlier <= 100.0)) return fail(nullptr, UMX_ERR_INVALID, "umx_test_rescale_dev: bad arguments");
+    if (const int rc = test_device("umx_test_rescale_dev")) return rc;
+    DevScratch d;
+    const size_t o_x = d.take(n * 8), o_mm = d.take(256), o_sel = d.take(64 + 512 * 4);
+    HIP_TRY(nullptr, hipMalloc((void**)&d.base, d.off));
+    double* const x = (double*)(d.base + o_x);
+    unsigned long long* const mm64 = (unsigned long long*)(d.base + o_mm);
+    HIP_TRY(nullptr, hipMemcpy(x, plane, n * 8, hipMemcpyHostToDevice));
+    HIP_TRY(nullptr, launch_minmax_f64(x, n, mm64, nullptr));
+    if (outlier >= 0)
+        HIP_TRY(nullptr, launch_percentile_f64(x, n, outlier, (unsigned long long*)(d.base + o_sel), (unsigned*)(d.base + o_sel + 64), mm64, nullptr));
+    HIP_TRY(nullptr, launch_rescale_f64(x, n, mm64, nullptr));
+    HIP_TRY(nullptr, hipMemcpy(range2, mm64, 16, hipMemcpyDeviceToHost));   // the (min, limit) doubles the rescale read
+    HIP_TRY(nullptr, hipMemcpy(out_plane, x, n * 8, hipMemcpyDeviceToHost));
+    return UMX_OK;
+}
+
+int umx_test_plane_range_dev(const void* raw, int bits, const size_t* n, const size_t* offset_elems, const int* nslabs, int njobs,
+                             uint32_t* range2) {
+    if (!raw || !n || !offset_elems || !nslabs || !range2 || njobs < 1 || (bits != 8 && bits != 16))
+        return fail(nullptr, UMX_ERR_INVALID, "umx_test_plane_range_dev: bad arguments");
+    if (const int rc = test_device("umx_test_plane_range_dev")) return rc;
+    const size_t el = bits / 8;
+    size_t most = 0;
+    for (int j = 0; j < njobs; ++j) {
+        if (n[j] == 0 || nslabs[j] < 1) return fail(nullptr, UMX_ERR_INVALID, "umx_test_plane_range_dev: empty job %d", j);
+        most = std::max(most, (n[j] + offset_elems[j]) * el);
+    }
+    DevScratch d;
+    const size_t o_raw = d.take(most), o_mm = d.take((size_t)njobs * 8);
+    HIP_TRY(nullptr, hipMalloc((void**)&d.base, d.off));   // (hipMalloc's addresses are 256-byte aligned, and so is every piece)
+    unsigned* const mm = (unsigned*)(d.base + o_mm);
+    const unsigned char* src = (const unsigned char*)raw;
+    for (int j = 0; j < njobs; ++j) {   // the jobs share the plane buffer: the default stream orders copy j + 1 behind reduction j
+        unsigned char* const plane = d.base + o_raw + offset_elems[j] * el;
+        HIP_TRY(nullptr, hipMemcpyAsync(plane, src, n[j] * el, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(nullptr, launch_minmax_init(mm + 2 * j, nullptr));
+        // consecutive slabs as host_enqueue reduces the rows it uploads; with more than one slab their length is odd, so that
+        // the second slab of a 16-bit plane starts at an odd element
+        size_t len = (n[j] + nslabs[j] - 1) / nslabs[j];
+        if (nslabs[j] > 1) len |= 1;
+        for (size_t e0 = 0; e0 < n[j]; e0 += len)
+            HIP_TRY(nullptr, launch_minmax(plane + e0 * el, bits, std::min(len, n[j] - e0), mm + 2 * j, nullptr));
+        src += n[j] * el;
+    }
+    HIP_TRY(nullptr, hipMemcpy(range2, mm, (size_t)njobs * 8, hipMemcpyDeviceToHost));
+    return UMX_OK;
+}
+
+int umx_test_half_to_u8_dev(const uint16_t* half_bits, size_t n, uint8_t* out_u8, double* out_f64) {
+    if (!half_bits || !out_u8 || !out_f64 || n == 0) return fail(nullptr, UMX_ERR_INVALID, "umx_test_half_to_u8_dev: bad arguments");
+    if (const int rc = test_device("umx_test_half_to_u8_dev")) return rc;
+    DevScratch d;
+    const size_t o_pm = d.take(n * 2), o_u8 = d.take(n), o_f = d.take(n * 8);
+    HIP_TRY(nullptr, hipMalloc((void**)&d.base, d.off));
+    HIP_TRY(nullptr, hipMemcpy(d.base + o_pm, half_bits, n * 2, hipMemcpyHostToDevice));
+    HIP_TRY(nullptr, launch_half_to_u8(d.base + o_pm, n, d.base + o_u8, nullptr));
+    HIP_TRY(nullptr, launch_half_to_u8_f64(d.base + o_pm, n, (double*)(d.base + o_f), nullptr));
+    HIP_TRY(nullptr, hipMemcpy(out_u8, d.base + o_u8, n, hipMemcpyDeviceToHost));
+    HIP_TRY(nullptr, hipMemcpy(out_f64, d.base + o_f, n * 8, hipMemcpyDeviceToHost));
+    return UMX_OK;
 }
 
 }  // extern "C"

@@ -486,8 +486,8 @@ hipError_t launch_d2h_rne_test(const double* in, uint16_t* out, size_t n, hipStr
     return hipGetLastError();
 }
 
-// the drivers' uint8 cast of one float16 probability (reference UnMicst1-5.py:848-854 at the identity grid; the same IEEE operations
-// as half_to_u8_kernel below, one rounding each): np.uint8(255 * pm) in float16, resize = u8 * (1 / 255) in float64, np.uint8(255 * .)
+// the drivers' uint8 cast of one float16 probability (reference UnMicst1-5.py:848-854 at the identity grid; what half_to_u8_kernel
+// below runs too; the same IEEE operations as numpy's, one rounding each): np.uint8(255 * pm) in float16, resize = u8 * (1 / 255) in float64, np.uint8(255 * .)
 __device__ __forceinline__ unsigned char u8_of_half(__half pm) {
     const __half p255 = __hmul(__float2half_rn(255.f), pm);
     const unsigned char first = (unsigned char)(int)__half2float(p255);
@@ -595,7 +595,7 @@ hipError_t launch_stitch(const float* probs, int tpr0, int tpr1, const TileGeom&
 //   raw uint8/uint16 plane -> float64 in [0,1] (skimage's resize converts with a multiply by 1/max) -> optional
 //   rescale_intensity((min, max) -> (0, 0.983)); float16 probability plane -> uint8 by the reference's double cast.
 // Every operation is the same IEEE operation numpy performs, one rounding each (contraction is switched off), so the
-// results are bit-identical to the host path in unmicst_amd/driver.py.
+// results are bit-identical to the host path in unmicst_amd/driver.py (held plane by plane by tests/test_gpu_imagekernels.py).
 // ------------------------------------------------------------------------------------------------------------
 #pragma clang fp contract(off)
 
@@ -658,10 +658,7 @@ __global__ void __launch_bounds__(256) raw_to_double_kernel(const T* __restrict_
 
 __global__ void __launch_bounds__(256) half_to_u8_kernel(const __half* __restrict__ pm, size_t n, unsigned char* __restrict__ out) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const __half p255 = __hmul(__float2half_rn(255.f), pm[i]);          // 255 * float16 -> float16 (numpy)
-        const unsigned char first = (unsigned char)(int)__half2float(p255);   // np.uint8: truncation
-        const double f = (double)first * (1.0 / 255);                       // resize at the identity grid: u8 * (1/255)
-        out[i] = (unsigned char)(int)(255.0 * f);                           // np.uint8(255 * PM)
+        out[i] = u8_of_half(pm[i]);   // the stitch's uint8 output (stitch == 2) and this kernel are one recipe
     }
 }
 
@@ -714,7 +711,12 @@ hipError_t launch_raw_to_double(const void* raw, int bits, size_t n, int rescale
 //   sigma = max(0, (in/out - 1) / 2) per axis; scipy.ndimage.gaussian_filter (truncate 4: radius int(4 sigma + 0.5),
 //   weights exp(-x^2 / (2 sigma^2)) / sum, mode 'mirror': d c b | a b c d | c b a), then scipy.ndimage.zoom(order 1,
 //   mode 'mirror', grid_mode True): input coordinate (o + 0.5) * in / out - 0.5, linear interpolation.
-// float64 throughout, same operation order as scipy's correlate1d (centre tap, then symmetric pairs from the outside in).
+// float64 throughout, same operation order as scipy's correlate1d (centre tap, then symmetric pairs from the outside in) and as
+// scipy's zoom (the coordinate mapped into the image first, weights 1 - t and 1 - (1 - t), the 2 x 2 support in C order): given the
+// same weights both kernels are bit-identical to scipy.ndimage, the mirrored border included (tests/test_gpu_imagekernels.py).
+// The weights come from the host (umx_host.hip: gauss_weights) in scipy's operation order with the C library's exp: within
+// 4 ulp of scipy's, bit-equal where the two exp agree -- so against imtools.resize the planes are
+// bit-identical when they are, and a few ulp apart when not.
 // ------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int mirror_index(int i, int n) {   // scipy 'mirror' (reflect about the edge sample)
     if (n == 1) return 0;
@@ -772,17 +774,24 @@ __global__ void __launch_bounds__(256) zoom1_kernel(const double* __restrict__ s
     const size_t n = (size_t)h * w;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
         const int oy = (int)(e / w), ox = (int)(e - (size_t)oy * w);
-        const double cy = ((double)oy + 0.5) * zy - 0.5, cx = ((double)ox + 0.5) * zx - 0.5;
+        double cy = ((double)oy + 0.5) * zy - 0.5, cx = ((double)ox + 0.5) * zx - 0.5;
+        // scipy maps the COORDINATE into the image before it splits it: below sample 0 it is reflected (c -> -c), so the nearer
+        // sample comes first in the sum; above sample n - 1 it stays (c < n always) and only the index n is mirrored.  Mirroring
+        // the two indices of the unreflected coordinate instead swaps the terms and rounds the weights differently (1-2 ulp).
+        cy = H == 1 ? 0.0 : cy < 0.0 ? -cy : cy;
+        cx = W == 1 ? 0.0 : cx < 0.0 ? -cx : cx;
         const double fy = floor(cy), fx = floor(cx);
-        const double ty = cy - fy, tx = cx - fx;
+        // scipy's spline weights of order 1: w0 = 1 - t, and the last one as 1 - (the others), not t itself
+        const double wy0 = 1.0 - (cy - fy), wx0 = 1.0 - (cx - fx);
+        const double wy1 = 1.0 - wy0, wx1 = 1.0 - wx0;
         const int y0 = mirror_index((int)fy, H), y1 = mirror_index((int)fy + 1, H);
         const int x0 = mirror_index((int)fx, W), x1 = mirror_index((int)fx + 1, W);
-        // scipy's separable evaluation: rows weighted (1-ty, ty), columns (1-tx, tx), accumulated in this order
+        // scipy's separable evaluation: rows weighted (wy0, wy1), columns (wx0, wx1), accumulated in this order
         double v = 0.0;
-        v += src[(size_t)y0 * W + x0] * (1.0 - ty) * (1.0 - tx);   // value * w_axis0 * w_axis1, C order of the 2x2 support
-        v += src[(size_t)y0 * W + x1] * (1.0 - ty) * tx;
-        v += src[(size_t)y1 * W + x0] * ty * (1.0 - tx);
-        v += src[(size_t)y1 * W + x1] * ty * tx;
+        v += src[(size_t)y0 * W + x0] * wy0 * wx0;   // value * w_axis0 * w_axis1, C order of the 2x2 support
+        v += src[(size_t)y0 * W + x1] * wy0 * wx1;
+        v += src[(size_t)y1 * W + x0] * wy1 * wx0;
+        v += src[(size_t)y1 * W + x1] * wy1 * wx1;
         v = fmin(fmax(v, lo), hi);
         if (out_u8) out_u8[e] = (unsigned char)(int)(255.0 * v);
         else dst[e] = v;

@@ -12,7 +12,13 @@ below restates the published semantics of the call it replaces and cites the cal
 Pinning: at ``--scalingFactor 1`` (the only configuration with a golden output, "UNet sample data") resize is the
 identity grid and the pipeline is pinned end to end by tests/test_oracle_golden.py / test_gpu_parity.py.  For other
 scaling factors the interpolation follows scikit-image >= 0.19 (gaussian pre-filter + ``scipy.ndimage.zoom`` with
-``grid_mode=True``); scikit-image is not installed here, so that branch is **unpinned**.
+``grid_mode=True``).  What is pinned there: the device kernels to THIS recipe, plane by plane and bit for bit -- the Gaussian
+to ``scipy.ndimage.correlate1d``, the zoom (mirrored border included) to ``scipy.ndimage.zoom``, the clip, ``np.percentile``,
+``rescale_intensity`` below and the uint8 cast (tests/test_gpu_imagekernels.py; tests/test_imagekernels_cpu.py holds the
+kernels' arithmetic, restated in numpy, to scipy without a GPU), and the Gaussian weights to scipy's within 4 ulp (same
+operations in the same order; ``exp`` is the C library's, numpy's own differs by an ulp on some taps on some machines).  What is
+not: that this recipe is scikit-image's.  scikit-image is not installed here, so ``resize`` and ``rescale_intensity`` are held
+to our reading of its source, not to its output.
 """
 from __future__ import annotations
 

@@ -31,6 +31,7 @@ EXPORTS = [
     "umx_tiff_packbits_decode", "umx_shard_unique_id", "umx_shard_init", "umx_shard_init_transport", "umx_shard_fini", "umx_shard_plan",
     "umx_infer_image_sharded_dev", "umx_infer_image_sharded_raw", "umx_infer_image_sharded_raw_submit",
     "umx_band_tiles_dev", "umx_stitch_dev", "umx_profile_enable", "umx_profile_read", "umx_prof_entry_size", "umx_test_double_to_half", "umx_test_double_to_half_dev",
+    "umx_test_gauss_weights", "umx_test_resize_dev", "umx_test_rescale_dev", "umx_test_plane_range_dev", "umx_test_half_to_u8_dev",
     "umx_describe", "umx_describe_graph", "umx_plan_check", "umx_test_mx_pack_e2m3", "umx_version",
 ]
 
@@ -338,6 +339,76 @@ def double_to_half_dev(x: np.ndarray) -> np.ndarray:
     if rc:
         raise UmxError(rc, L.umx_last_error(None).decode())
     return out.view(np.float16)
+
+
+def _check(L, rc: int) -> None:
+    if rc:
+        raise UmxError(rc, L.umx_last_error(None).decode())
+
+
+def gauss_weights(sigma: float) -> np.ndarray:
+    """umx_test_gauss_weights: the resize's anti-aliasing weights of one axis, [0] = centre tap .. [radius].  Host only."""
+    L = load()
+    out = np.empty(4096, np.float64)
+    L.umx_test_gauss_weights.restype = ctypes.c_int
+    L.umx_test_gauss_weights.argtypes = [ctypes.c_double, ctypes.c_void_p, ctypes.c_int]
+    radius = L.umx_test_gauss_weights(float(sigma), out.ctypes.data, out.size)
+    if radius < 0:
+        raise ValueError("no resize weights for sigma %r" % (sigma,))
+    return out[:radius + 1].copy()
+
+
+def resize_dev(src: np.ndarray, h: int, w: int):
+    """umx_test_resize_dev: one resize of a float64 plane to (h, w) on the device -> (float64 plane, uint8 plane, the plane after
+    the Gaussian)."""
+    src = np.ascontiguousarray(src, np.float64)
+    H, W = src.shape
+    out, out8, filt = np.empty((h, w), np.float64), np.empty((h, w), np.uint8), np.empty((H, W), np.float64)
+    L = load()
+    L.umx_test_resize_dev.restype = ctypes.c_int
+    L.umx_test_resize_dev.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 3
+    _check(L, L.umx_test_resize_dev(src.ctypes.data, H, W, h, w, out.ctypes.data, out8.ctypes.data, filt.ctypes.data))
+    return out, out8, filt
+
+
+def rescale_dev(plane: np.ndarray, outlier: float = -1.0):
+    """umx_test_rescale_dev: (rescaled plane, (min, limit)); limit = max, or np.percentile(plane, outlier) for outlier >= 0."""
+    plane = np.ascontiguousarray(plane, np.float64)
+    out, rng = np.empty(plane.shape, np.float64), np.empty(2, np.float64)
+    L = load()
+    L.umx_test_rescale_dev.restype = ctypes.c_int
+    L.umx_test_rescale_dev.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]
+    _check(L, L.umx_test_rescale_dev(plane.ctypes.data, plane.size, float(outlier), out.ctypes.data, rng.ctypes.data))
+    return out, rng
+
+
+def plane_range_dev(planes, offsets, nslabs) -> np.ndarray:
+    """umx_test_plane_range_dev: the device range search on a list of 1-D uint8 / uint16 planes (one dtype), each at its own
+    element offset from an aligned address and over its own number of slabs -> [len(planes), 2] (min, max)."""
+    dtype = planes[0].dtype
+    assert dtype in (np.uint8, np.uint16) and all(p.dtype == dtype and p.ndim == 1 for p in planes)
+    raw = np.ascontiguousarray(planes[0] if len(planes) == 1 else np.concatenate(planes))
+    n = np.array([p.size for p in planes], np.uintp)
+    off, ns = np.ascontiguousarray(offsets, np.uintp), np.ascontiguousarray(nslabs, np.int32)
+    assert off.shape == ns.shape == n.shape
+    out = np.empty((len(planes), 2), np.uint32)
+    L = load()
+    L.umx_test_plane_range_dev.restype = ctypes.c_int
+    L.umx_test_plane_range_dev.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p]
+    _check(L, L.umx_test_plane_range_dev(raw.ctypes.data, 8 * dtype.itemsize, n.ctypes.data, off.ctypes.data, ns.ctypes.data,
+                                         len(planes), out.ctypes.data))
+    return out
+
+
+def half_to_u8_dev(pm: np.ndarray):
+    """umx_test_half_to_u8_dev: the drivers' uint8 cast of float16 probabilities -> (uint8, the float64 u8 / 255 plane)."""
+    pm = np.ascontiguousarray(pm, np.float16)
+    out8, outf = np.empty(pm.shape, np.uint8), np.empty(pm.shape, np.float64)
+    L = load()
+    L.umx_test_half_to_u8_dev.restype = ctypes.c_int
+    L.umx_test_half_to_u8_dev.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+    _check(L, L.umx_test_half_to_u8_dev(pm.ctypes.data, pm.size, out8.ctypes.data, outf.ctypes.data))
+    return out8, outf
 
 
 def tiff_decode(kind: str, buf: bytes, nbytes: int) -> bytes:
