@@ -253,6 +253,61 @@ UMX_API int umx_infer_image_sharded_raw(umx_ctx* ctx, const void* band_host, int
                                         int band_rows, const uint32_t* range, double mean, double std, int mode, int nslabs,
                                         uint8_t* own_out_host, uint8_t* out_full_dev);
 
+/*
+ * Label mask (no reference counterpart: the reference's tools stop at probability maps).  From the stack
+ * u8[K][H][W] of final uint8 probability planes in the model's class order, a class c and a minimum area A:
+ *   object pixels  pred(y, x) == c, pred = the index of the FIRST maximum of u8[0..K-1][y][x] (a tie goes to the lower class);
+ *   objects        their 4-connected components (UMX_BORDER_CONNECTIVITY of include/umx_train.h);
+ *   labels         int32 [H][W]: the kept objects (area >= A) numbered 1..N in raster order of their first pixel, 0 elsewhere --
+ *                  scipy.ndimage.label with its default structure, the area filter, and a renumbering that keeps the order;
+ *   table          one umx_label_object per kept object in label order, integers throughout (centroid = sum / area on the host).
+ * Every value is an integer, so nothing depends on the order in which atomics arrive: two calls give the same bytes.
+ * A labeler needs no model: it owns a stream and its device buffers (two int32 planes of H * W, the K input planes, one int32 per
+ * UMX_LABEL_SCAN_BLOCK pixels and the table), grown on demand and kept between runs.  UMX_DEBUG_GUARD (include/umx_train.h) puts red
+ * zones round them; a run then ends with their check (UMX_ERR_GUARD).  One labeler per host thread.
+ */
+typedef struct umx_label_options {
+    int32_t cls;             /* 0 .. K-1, in the model's class order */
+    int32_t min_area;        /* 1 .. UMX_LABEL_MAX_MIN_AREA pixels */
+    int32_t reserved[6];     /* must be zero */
+} umx_label_options;
+typedef struct umx_label_object {
+    int32_t area, y0, x0, y1, x1, reserved;   /* pixels; the inclusive bounding box */
+    int64_t sum_y, sum_x;                     /* over the object's pixels */
+} umx_label_object;                           /* 40 bytes */
+typedef struct umx_labeler umx_labeler;
+#define UMX_LABEL_MAX_CLASSES 16
+#define UMX_LABEL_MAX_MIN_AREA 65536   /* == UMX_OBJECT_MAX_MIN_AREA */
+/* The geometry of the kernels (umx_label.hip), for tests that must cross every boundary of it: rows of the image one workgroup
+ * merges in the first merge launch (the seams between such strips are joined pairwise in log2 further launches), threads of a merge
+ * workgroup (a seam is walked UMX_LABEL_THREADS pixels at a time), pixels per block of the numbering scan (whose block counts one
+ * workgroup scans UMX_LABEL_THREADS at a time). */
+#define UMX_LABEL_STRIP_ROWS 32
+#define UMX_LABEL_THREADS 1024
+#define UMX_LABEL_SCAN_BLOCK 2048
+/* Host only, no device: H, W >= 1; H * W <= 2^31 - 1 (a flat pixel index is an int32); 1 <= K <= 16; 0 <= cls < K;
+ * 1 <= min_area <= 65536; reserved words zero.  UMX_OK, or UMX_ERR_INVALID with the reason in msg (cap bytes; may be NULL). */
+UMX_API int umx_label_options_check(const umx_label_options* o, int K, int H, int W, char* msg, size_t cap);
+/* UMX_ERR_NO_DEVICE without a gfx950 device: there is no CPU fallback. */
+UMX_API int umx_labeler_create(int device_ordinal, umx_labeler** out);
+UMX_API void umx_labeler_destroy(umx_labeler* lb);   /* NULL is a no-op */
+/* Message of the last failure of this labeler (NULL: of a labeler-less call on this thread). */
+UMX_API const char* umx_labeler_last_error(const umx_labeler* lb);
+/* Synchronous.  planes_host: uint8 [K][H][W]; labels_host: int32 [H][W], or NULL when only the count and the table are wanted.
+ * A refused call (UMX_ERR_INVALID) has touched nothing and leaves the labeler usable. */
+UMX_API int umx_labeler_run(umx_labeler* lb, const uint8_t* planes_host, int K, int H, int W, const umx_label_options* o,
+                            int32_t* labels_host, int64_t* n_objects);
+/* The same on DEVICE pointers of the labeler's device (e.g. the out_full_dev of umx_infer_image_sharded_raw): no upload and no
+ * download of the planes.  The planes must be complete when the call is made (the labeler's stream does not wait for the stream that
+ * wrote them), and the call returns with the labeler's stream idle: the count comes back to the host in the middle of it. */
+UMX_API int umx_labeler_run_dev(umx_labeler* lb, const uint8_t* planes_dev, int K, int H, int W, const umx_label_options* o,
+                                int32_t* labels_dev, int64_t* n_objects);
+/* The table of the last run: min(cap, N) records into out (may be NULL with cap 0), N into *n. */
+UMX_API int umx_labeler_objects(const umx_labeler* lb, umx_label_object* out, int64_t cap, int64_t* n);
+/* Milliseconds of the last run by HIP events on the labeler's stream: the upload of the planes, the launches (the read-back of the
+ * count in their middle included), the download of the labels and the table.  0 for a part the call did not have.  Any may be NULL. */
+UMX_API int umx_labeler_last_ms(const umx_labeler* lb, double* upload_ms, double* kernel_ms, double* download_ms);
+
 /* Strip / tile decoders of the drivers' own TIFF reader (unmicst_amd/tiffio.py; the reference reads through tifffile /
  * imagecodecs, UnMicst1-5.py:794-797): TIFF 6.0 LZW (compression 5, the OME-TIFF / Bio-Formats default) and PackBits
  * (32773).  Host code, no device needed.  Return the decoded byte count (<= cap) or -1 on a malformed stream. */

@@ -3,7 +3,9 @@
 nucleiDAPI weights) on an N x N uint16 TIFF, with the per-stage breakdown the driver prints under UMX_CLI_TIMING=1
 (interpreter start + imports, engine set-up, TIFF read, engine call, page writes, clean-up).
 usage: cli_walltime.py [N=16384] [other-tree ...]   -- every further argument is another checkout of the repo (with its own built
-libumx.so) whose UnMicst.py is timed on the same file, same box: how a round's change is compared with the round before."""
+libumx.so) whose UnMicst.py is timed on the same file, same box: how a round's change is compared with the round before.
+       cli_walltime.py N --label   -- only this tree: twice without and twice with --labelMask (the `label` stage: stacking the
+planes, the labelling call, the int32 page and the table)."""
 import json
 import os
 import subprocess
@@ -20,11 +22,11 @@ import helpers  # noqa: E402
 from unmicst_amd import model, tiffio  # noqa: E402
 
 
-def one(tree, path, out, env_extra, label, n, script="UnMicst.py", what="legacy nucleiDAPI"):
+def one(tree, path, out, env_extra, label, n, script="UnMicst.py", what="legacy nucleiDAPI", extra=()):
     e = dict(os.environ, UMX_CLI_TIMING="1", **env_extra)
     e["UMX_CLI_T0"] = repr(time.time())
     t = time.perf_counter()
-    r = subprocess.run([sys.executable, os.path.join(tree, script), path, "--stackOutput", "--outputPath", out], env=e,
+    r = subprocess.run([sys.executable, os.path.join(tree, script), path, "--stackOutput", "--outputPath", out] + list(extra), env=e,
                        capture_output=True, text=True)
     dt = time.perf_counter() - t
     assert r.returncode == 0, r.stderr[-2000:]
@@ -36,7 +38,8 @@ def one(tree, path, out, env_extra, label, n, script="UnMicst.py", what="legacy 
 
 def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 16384
-    others = sys.argv[2:]
+    label_only = "--label" in sys.argv[2:]
+    others = [a for a in sys.argv[2:] if a != "--label"]
     hp, blob, mean, std = helpers.load_nuclei_dapi()
     raw = helpers.load_sample_105()[0]
     reps = (-(-n // raw.shape[0]), -(-n // raw.shape[1]))
@@ -47,6 +50,15 @@ def main():
         path = os.path.join(d, "x", "registration", "slide.tif")
         tiffio.imsave(path, img)
         env = {"UMX_MODELS_DIR": os.path.join(d, "models")}
+        if label_only:
+            for rep in range(2):
+                one(ROOT, path, os.path.join(d, "out_plain%d" % rep), env, "this tree, run %d" % (rep + 1), n)
+                one(ROOT, path, os.path.join(d, "out_label%d" % rep), env, "this tree, --labelMask, run %d" % (rep + 1), n,
+                    extra=["--labelMask"])
+            for f in sorted(os.listdir(os.path.join(d, "out_label0"))):
+                if "_Labels_" in f or "_Objects_" in f:
+                    print("  %-40s %d bytes" % (f, os.path.getsize(os.path.join(d, "out_label0", f))))
+            return
         for rep in range(2):
             one(ROOT, path, os.path.join(d, "out_new%d" % rep), env, "this tree, run %d" % (rep + 1), n)
             for i, tree in enumerate(others):

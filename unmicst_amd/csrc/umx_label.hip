@@ -1,0 +1,554 @@
+// libumx label mask: whole-slide object labelling on the device -- the kernels and the C ABI behind umx_labeler_* (include/umx.h,
+// DESIGN.md section 8.1 "Label mask").  Two int32 planes of H * W: P (parents, then roots, then the labels) and Q (roots of the run
+// heads, then areas, then numbers).  A run is a maximal row segment of object pixels, its head the first pixel of it.  One call is this
+// sequence of launches on the labeler's stream:
+//
+//   label_runs_kernel     one wave per row: the class rule (first maximum of the K planes == cls) and the row runs; every object pixel
+//                         points at its run's head, every other pixel holds -1 (phase 0 of border_label_kernel)
+//   label_strip_kernel    one workgroup per strip of UMX_LABEL_STRIP_ROWS rows: the vertical merges between the rows of the strip
+//                         (phase 1 of border_label_kernel, the same pruning, atomicMin unions)
+//   label_seam_kernel     level l = 0, 1, ...: groups of 2^(l+1) strips; one workgroup per group merges across the one seam in the
+//                         group's middle, where its two halves -- each joined by the levels before -- meet
+//   label_heads_kernel    one thread per pixel: the root of every run head into Q (P is only read)
+//   label_flatten_kernel  one wave per row: every object pixel takes Q of its run's head into P: P = root, -1 off the objects
+//   (Q is cleared)
+//   label_area_kernel     one wave per row: every run adds its length to Q[root]
+//   label_count_kernel    kept(i) = P[i] == i and Q[i] >= min_area; per block of UMX_LABEL_SCAN_BLOCK pixels the number of kept roots
+//   label_scan_kernel     ONE workgroup: exclusive prefix sum of the block counts in place, the total N to a word the host reads
+//   label_number_kernel   per block again: Q[root] = 1 + (kept roots before it in raster order), 0 at a root that is not kept
+//   (N comes back to the host: the only synchronisation inside a call; the table is sized for it)
+//   label_table_init_kernel, label_write_kernel   one wave per row: labels = Q[P], 0 off the objects, in place over P or into the
+//                         caller's plane; every run adds its length, y * length, the sum of its x and its extent to record label - 1
+//
+// Why no workgroup waits for another one, and none reads inside a kernel what another one writes in it: in the strip launch a workgroup
+// touches only pixels of its strip -- a link made there joins two run heads of the strip, so a walk from a pixel of the strip stays in
+// it.  By induction a tree that exists before level l lies inside one half-group of that level; the workgroup of a group walks and
+// changes only trees of its own two halves, and the groups of a level are disjoint.  Every other kernel writes only its own pixel's
+// word (or an atomic sum / min / max that nothing reads before the launch ends) and reads words that the launches before it
+// finished.  The launch boundary is the only synchronisation: no spin, no flag, no look-back.
+// Why the result does not depend on any order: links only decrease, so a component's root is its least flat index however the unions
+// interleave; every accumulated value is an integer sum, minimum or maximum.
+#include "../../include/umx.h"
+#include "../../include/umx_train.h"
+#include "umx_internal.h"
+#include "umx_unionfind.h"
+
+#include <climits>
+#include <cstdarg>
+#include <cstdio>
+
+namespace umx {
+
+namespace {
+
+constexpr int kRowWaves = 4;                             // rows of the image per workgroup of the one-wave-per-row kernels
+constexpr int kStripRows = UMX_LABEL_STRIP_ROWS;
+constexpr int kMergeThreads = UMX_LABEL_THREADS;
+constexpr int kPixThreads = 256;                         // one thread per pixel
+constexpr int kScanBlock = UMX_LABEL_SCAN_BLOCK;
+constexpr int kScanWaves = 4;                            // a block of the scan: 4 waves x 8 chunks x 64 pixels
+constexpr int kScanChunks = kScanBlock / (64 * kScanWaves);
+static_assert(kScanChunks * 64 * kScanWaves == kScanBlock, "a scan block is a whole number of 64-pixel chunks per wave");
+static_assert(UMX_LABEL_MAX_MIN_AREA == UMX_OBJECT_MAX_MIN_AREA, "one bound on min_area");
+static_assert(UMX_BORDER_CONNECTIVITY == 4, "the merges below join a pixel with the one above it and row runs: 4-connectivity");
+static_assert(sizeof(umx_label_object) == 40, "the table's record");
+
+// grid ceil(H / 4).  planes [K][H][W].  Bounds: row y < H; ceil(W / 64) chunks; a lane is in the row iff lane < W - x0 (no x0 + lane
+// is formed past the row's end, W may be 2^31 - 1); the word written is y * W + x < H * W <= INT_MAX, its value y * W + start likewise.
+__global__ void __launch_bounds__(64 * kRowWaves) label_runs_kernel(const uint8_t* __restrict__ planes, int K, int H, int W, int cls,
+                                                                     int* __restrict__ P) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if ((long long)blockIdx.x * kRowWaves + wave >= H) return;    // (the whole wave: no barrier below)
+    const int y = blockIdx.x * kRowWaves + wave;
+    const size_t npix = (size_t)H * W, row = (size_t)y * W;
+    const int nchunks = (W - 1) / 64 + 1;
+    int carry = -1;   // first column of the run that reaches the end of the previous chunk; -1: none
+    for (int c = 0; c < nchunks; ++c) {
+        const int x0 = c * 64;
+        const bool in = lane < W - x0;
+        const int x = in ? x0 + lane : x0;
+        bool obj = false;
+        if (in) {
+            int arg = 0, best = planes[row + x];
+            for (int k = 1; k < K; ++k) {
+                const int v = planes[(size_t)k * npix + row + x];
+                if (v > best) { best = v; arg = k; }      // first maximum, as object_planes_kernel
+            }
+            obj = arg == cls;
+        }
+        const unsigned long long mask = __ballot(obj);
+        if (in) {
+            int v = -1;
+            if (obj) {
+                const unsigned long long gaps = ~mask & ((1ull << lane) - 1ull);   // pixels off the object left of this one
+                const int start = gaps ? x0 + (64 - __clzll((long long)gaps)) : (carry >= 0 ? carry : x0);
+                v = (int)(row + start);
+            }
+            P[row + x] = v;
+        }
+        if (mask >> 63) {
+            const unsigned long long gaps = ~mask;
+            carry = gaps ? x0 + (64 - __clzll((long long)gaps)) : (carry >= 0 ? carry : x0);
+        } else {
+            carry = -1;
+        }
+    }
+}
+
+// the merge of pixel i (row >= 1, column x) with the one above it, pruned as in border_label_kernel: skipped when the left neighbour
+// and that one's upper neighbour are object pixels too -- then the left neighbour's merge connects the same two runs
+__device__ inline void merge_up(int* P, int i, int x, int W) {
+    if (parent_load(P + i) < 0 || parent_load(P + i - W) < 0) return;
+    if (x > 0 && parent_load(P + i - 1) >= 0 && parent_load(P + i - 1 - W) >= 0) return;
+    union_trees(P, i, i - W);
+}
+
+// grid ceil(H / 32).  Strip rows [y0, y1), y1 - y0 <= 32; the pixels of rows y0 + 1 .. y1 - 1 are merged upwards: n = (y1 - y0 - 1) * W
+// of them, ceil(n / 1024) rounds; i = (y0 + 1) * W + j < y1 * W <= H * W.  Every word read or changed lies in rows [y0, y1).
+__global__ void __launch_bounds__(kMergeThreads) label_strip_kernel(int* __restrict__ P, int H, int W) {
+    const int y0 = blockIdx.x * kStripRows;
+    const int rows = H - y0 > kStripRows ? kStripRows : H - y0;
+    const long long n = (long long)(rows - 1) * W;
+    const long long first = (long long)(y0 + 1) * W;
+    for (long long j = threadIdx.x; j < n; j += kMergeThreads) merge_up(P, (int)(first + j), (int)(j % W), W);
+}
+
+// span = 32 * 2^level rows.  grid: the groups g whose seam row y = (2 g + 1) * span is < H (host).  ceil(W / 1024) rounds (a seam
+// exists only when H > 32, so W < 2^26 and x + 1024 fits).  Words read or changed: rows [2 g span, min(H, (2 g + 2) span)).
+__global__ void __launch_bounds__(kMergeThreads) label_seam_kernel(int* __restrict__ P, int H, int W, long long span) {
+    const long long y = (2ll * blockIdx.x + 1ll) * span;
+    if (y >= H) return;
+    const long long first = y * W;
+    for (int x = threadIdx.x; x < W; x += kMergeThreads) merge_up(P, (int)(first + x), x, W);
+}
+
+// one thread per pixel, i < npix.  P is not written in this launch; Q[i] only by the thread of pixel i.
+__global__ void __launch_bounds__(kPixThreads) label_heads_kernel(const int* __restrict__ P, int* __restrict__ Q, long long npix, int W) {
+    const long long i = (long long)blockIdx.x * kPixThreads + threadIdx.x;
+    if (i >= npix) return;
+    if (P[i] < 0 || (i % W > 0 && P[i - 1] >= 0)) return;
+    Q[i] = find_root(P, (int)i);
+}
+
+// grid ceil(H / 4).  An object pixel that is not a head still holds its head's index (unions change heads only): it reads Q there; a
+// head reads its own.  Which one a pixel is comes from the ballot and the bit carried over from the chunk before, not from memory:
+// a thread reads P only at its own pixel, which is the only word it writes.
+__global__ void __launch_bounds__(64 * kRowWaves) label_flatten_kernel(int* __restrict__ P, const int* __restrict__ Q, int H, int W) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if ((long long)blockIdx.x * kRowWaves + wave >= H) return;    // (the whole wave: no barrier below)
+    const int y = blockIdx.x * kRowWaves + wave;
+    const size_t row = (size_t)y * W;
+    const int nchunks = (W - 1) / 64 + 1;
+    unsigned left_of_chunk = 0;                           // the last pixel of the chunk before is an object pixel
+    for (int c = 0; c < nchunks; ++c) {
+        const int x0 = c * 64;
+        const bool in = lane < W - x0;
+        const int x = in ? x0 + lane : x0;
+        const int p = in ? P[row + x] : -1;
+        const unsigned long long mask = __ballot(p >= 0);
+        const unsigned left = lane > 0 ? (unsigned)((mask >> (lane - 1)) & 1ull) : left_of_chunk;
+        if (p >= 0) P[row + x] = Q[left ? (size_t)p : row + x];
+        left_of_chunk = (unsigned)(mask >> 63);
+    }
+}
+
+// The runs of one row by one wave: key_at(x) is called once for every pixel of the row (>= 0: the pixel's object; < 0: none), and
+// flush(key, start, len) once for every maximal segment [start, start + len) of equal key >= 0 -- by one lane, the others idle.  A
+// segment that reaches the end of a 64-pixel chunk is carried into the next one (the wave walks its chunks in order), so a long run
+// costs one flush, not one per chunk.  ceil(W / 64) rounds; len <= W.
+template <typename KeyAt, typename Flush>
+__device__ inline void for_each_run(int W, int lane, KeyAt key_at, Flush flush) {
+    int ckey = -1, cstart = 0, clen = 0;                  // the carried segment; ckey < 0: none
+    const int nchunks = (W - 1) / 64 + 1;
+    for (int c = 0; c < nchunks; ++c) {
+        const int x0 = c * 64;
+        const bool in = lane < W - x0;
+        const int x = in ? x0 + lane : x0;
+        const int t = in ? key_at(x) : -2;                // past the row's end: a key no pixel has
+        const int tl = __shfl_up(t, 1);
+        const bool head = lane == 0 || t != tl;
+        const unsigned long long heads = __ballot(head);  // (bit 0 is always set)
+        const unsigned long long later = lane == 63 ? 0ull : heads >> (lane + 1);
+        int len = later ? __ffsll((long long)later) : 64 - lane;   // pixels up to the next head, or to the chunk's end
+        int start = x;
+        const int t0 = __shfl(t, 0);
+        if (lane == 0 && ckey >= 0) {
+            if (t0 == ckey) { start = cstart; len += clen; }
+            else flush(ckey, cstart, clen);
+        }
+        const bool last = c + 1 == nchunks;
+        if (head && t >= 0 && (later || last)) flush(t, start, len);
+        const int hl = 63 - __clzll((long long)heads);    // the head of the chunk's last segment
+        const int lk = __shfl(t, hl), ls = __shfl(start, hl), ll = __shfl(len, hl);
+        if (!last && lk >= 0) { ckey = lk; cstart = ls; clen = ll; }
+        else ckey = -1;
+    }
+}
+
+// grid ceil(H / 4).  P: roots (-1 off the objects), read only; Q (zero on entry): atomicAdd at the roots, read by nobody here.
+__global__ void __launch_bounds__(64 * kRowWaves) label_area_kernel(const int* __restrict__ P, int* __restrict__ Q, int H, int W) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if ((long long)blockIdx.x * kRowWaves + wave >= H) return;    // (the whole wave: no barrier below)
+    const int y = blockIdx.x * kRowWaves + wave;
+    const int* row = P + (size_t)y * W;
+    for_each_run(W, lane, [&](int x) { return row[x]; }, [&](int key, int, int len) { atomicAdd(Q + key, len); });
+}
+
+// Block b of the scan covers pixels [2048 b, 2048 b + 2048), wave w of it 512 consecutive ones in 8 chunks; a pixel >= npix is
+// never read.  The kept roots of the wave's pixels, in every lane.
+__device__ inline int wave_kept(const int* P, const int* Q, long long base, long long npix, int min_area, int lane) {
+    int n = 0;
+    for (int c = 0; c < kScanChunks; ++c) {
+        const long long i = base + c * 64 + lane;
+        const bool kept = i < npix && P[i] == (int)i && Q[i] >= min_area;
+        n += __popcll(__ballot(kept));
+    }
+    return n;
+}
+
+// grid nblocks = ceil(npix / 2048).
+__global__ void __launch_bounds__(64 * kScanWaves) label_count_kernel(const int* __restrict__ P, const int* __restrict__ Q, long long npix,
+                                                                       int min_area, int* __restrict__ counts) {
+    __shared__ int wn[kScanWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = wave_kept(P, Q, (long long)blockIdx.x * kScanBlock + wave * (kScanBlock / kScanWaves), npix, min_area, lane);
+    if (lane == 0) wn[wave] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int s = 0;
+        for (int k = 0; k < kScanWaves; ++k) s += wn[k];
+        counts[blockIdx.x] = s;
+    }
+}
+
+// ONE workgroup.  counts[0 .. nblocks) -> their exclusive prefix sums, in place (a thread reads and writes its own element of a
+// round); *total = the sum (<= npix <= INT_MAX).  ceil(nblocks / 1024) rounds, nblocks <= 2^20.
+__global__ void __launch_bounds__(kMergeThreads) label_scan_kernel(int* __restrict__ counts, int nblocks, long long* __restrict__ total) {
+    __shared__ int wsum[kMergeThreads / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int carry = 0;
+    for (int base = 0; base < nblocks; base += kMergeThreads) {
+        const int idx = base + threadIdx.x;
+        const int v = idx < nblocks ? counts[idx] : 0;
+        int s = v;
+        for (int d = 1; d < 64; d <<= 1) {
+            const int t = __shfl_up(s, d);
+            if (lane >= d) s += t;
+        }
+        if (lane == 63) wsum[wave] = s;
+        __syncthreads();
+        int before = 0, all = 0;
+        for (int k = 0; k < kMergeThreads / 64; ++k) {
+            if (k < wave) before += wsum[k];
+            all += wsum[k];
+        }
+        if (idx < nblocks) counts[idx] = carry + before + s - v;
+        carry += all;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+
+// grid nblocks.  counts: the exclusive prefix sums.  Q[i] is read (the area) and written (the number) by the thread of pixel i alone,
+// and only at roots.
+__global__ void __launch_bounds__(64 * kScanWaves) label_number_kernel(const int* __restrict__ P, int* __restrict__ Q, long long npix,
+                                                                        int min_area, const int* __restrict__ counts) {
+    __shared__ int wn[kScanWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long base = (long long)blockIdx.x * kScanBlock + wave * (kScanBlock / kScanWaves);
+    const int n = wave_kept(P, Q, base, npix, min_area, lane);
+    if (lane == 0) wn[wave] = n;
+    __syncthreads();
+    int off = counts[blockIdx.x];
+    for (int k = 0; k < wave; ++k) off += wn[k];
+    for (int c = 0; c < kScanChunks; ++c) {
+        const long long i = base + c * 64 + lane;
+        const bool root = i < npix && P[i] == (int)i;
+        const bool kept = root && Q[i] >= min_area;
+        const unsigned long long mask = __ballot(kept);
+        if (root) Q[i] = kept ? off + __popcll(mask & ((1ull << lane) - 1ull)) + 1 : 0;
+        off += __popcll(mask);
+    }
+}
+
+// one thread per record, j < n
+__global__ void __launch_bounds__(kPixThreads) label_table_init_kernel(umx_label_object* __restrict__ table, long long n) {
+    const long long j = (long long)blockIdx.x * kPixThreads + threadIdx.x;
+    if (j >= n) return;
+    umx_label_object o;
+    o.area = 0; o.y0 = INT_MAX; o.x0 = INT_MAX; o.y1 = -1; o.x1 = -1; o.reserved = 0; o.sum_y = 0; o.sum_x = 0;
+    table[j] = o;
+}
+
+// grid ceil(H / 4).  P: roots; Q: the numbers at the roots (0: dropped).  out (may be null, may be P itself): a thread reads P at its
+// own pixel and writes out there; Q is only read.  table[label - 1], label <= N: integer atomics that nothing reads in this launch.
+__global__ void __launch_bounds__(64 * kRowWaves) label_write_kernel(const int* P, const int* __restrict__ Q, int H, int W, int* out,
+                                                                      umx_label_object* __restrict__ table) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if ((long long)blockIdx.x * kRowWaves + wave >= H) return;    // (the whole wave: no barrier below)
+    const int y = blockIdx.x * kRowWaves + wave;
+    const size_t row = (size_t)y * W;
+    for_each_run(
+        W, lane,
+        [&](int x) {
+            const int p = P[row + x];
+            const int label = p >= 0 ? Q[p] : 0;
+            if (out) out[row + x] = label;
+            return label - 1;
+        },
+        [&](int key, int start, int len) {
+            umx_label_object* o = table + key;
+            atomicAdd(&o->area, len);
+            atomicMin(&o->y0, y);
+            atomicMax(&o->y1, y);
+            atomicMin(&o->x0, start);
+            atomicMax(&o->x1, start + len - 1);
+            const unsigned long long l = (unsigned long long)len;
+            atomicAdd(reinterpret_cast<unsigned long long*>(&o->sum_y), (unsigned long long)y * l);
+            atomicAdd(reinterpret_cast<unsigned long long*>(&o->sum_x), (unsigned long long)start * l + l * (l - 1ull) / 2ull);
+        });
+}
+
+}  // namespace
+
+}  // namespace umx
+
+struct umx_labeler {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // upload begins | launches begin | downloads begin | all done
+    umx::DevArena mem;
+    uint8_t* d_planes = nullptr;  size_t planes_cap = 0;       // bytes
+    int* d_P = nullptr;
+    int* d_Q = nullptr;           size_t pix_cap = 0;          // words of either plane
+    int* d_counts = nullptr;      size_t counts_cap = 0;       // words
+    long long* d_n = nullptr;
+    umx_label_object* d_table = nullptr;  size_t table_cap = 0;   // records
+    std::vector<umx_label_object> table;                       // of the last run
+    double ms[3] = {0.0, 0.0, 0.0};
+    std::string err;
+};
+
+namespace umx {
+
+namespace {
+
+int lfail(umx_labeler* lb, int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (lb) lb->err = buf;
+    g_err = buf;
+    return code;
+}
+
+#define L_HIP(lb, expr)                                                                                                  \
+    do {                                                                                                                 \
+        hipError_t e__ = (expr);                                                                                         \
+        if (e__ != hipSuccess)                                                                                           \
+            return lfail(lb, e__ == hipErrorOutOfMemory ? UMX_ERR_OOM : UMX_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e__)); \
+    } while (0)
+
+// Buffers for K planes of H x W.  Nothing shrinks; when one is too small the arena is emptied and every buffer allocated again at the
+// larger of its old and its needed size (the arena frees as a whole, and the red zones of guard mode are per allocation).
+int ensure_buffers(umx_labeler* lb, size_t plane_bytes, size_t npix, size_t nblocks) {
+    if (plane_bytes <= lb->planes_cap && npix <= lb->pix_cap && nblocks <= lb->counts_cap && lb->d_n) return UMX_OK;
+    L_HIP(lb, hipStreamSynchronize(lb->stream));
+    arena_free(&lb->mem);
+    lb->d_planes = nullptr; lb->d_P = lb->d_Q = lb->d_counts = nullptr; lb->d_n = nullptr; lb->d_table = nullptr;
+    const size_t pb = std::max(plane_bytes, lb->planes_cap), px = std::max(npix, lb->pix_cap), nb = std::max(nblocks, lb->counts_cap);
+    const size_t tc = std::max<size_t>(lb->table_cap, 1024);
+    lb->planes_cap = lb->pix_cap = lb->counts_cap = lb->table_cap = 0;
+    L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_P, px * sizeof(int), false, "label parents"));
+    L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_Q, px * sizeof(int), false, "label areas"));
+    L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_counts, nb * sizeof(int), false, "label block counts"));
+    L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_n, sizeof(long long), true, "label count"));
+    L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_table, tc * sizeof(umx_label_object), false, "label table"));
+    if (pb) L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_planes, pb, false, "label planes"));
+    lb->planes_cap = pb; lb->pix_cap = px; lb->counts_cap = nb; lb->table_cap = tc;
+    return UMX_OK;
+}
+
+// (a table that grows leaves its old block in the arena until the arena is next emptied: sizes double, so that is less than the new one)
+int ensure_table(umx_labeler* lb, size_t n) {
+    if (n <= lb->table_cap) return UMX_OK;
+    const size_t tc = std::max(n, 2 * lb->table_cap);
+    L_HIP(lb, hipStreamSynchronize(lb->stream));
+    lb->table_cap = 0;
+    L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_table, tc * sizeof(umx_label_object), false, "label table"));
+    lb->table_cap = tc;
+    return UMX_OK;
+}
+
+inline unsigned row_grid(int H) { return (unsigned)((H - 1) / kRowWaves + 1); }
+
+// the launches of one call on planes already on the device; out: null, the caller's plane or lb->d_P.  Returns with the stream idle
+// up to the count's read-back and the last launches enqueued.
+int run_launches(umx_labeler* lb, const uint8_t* planes, int K, int H, int W, const umx_label_options* o, int* out, long long* n_out) {
+    const long long npix = (long long)H * W;
+    const int nblocks = (int)((npix + kScanBlock - 1) / kScanBlock);
+    const unsigned pix_grid = (unsigned)((npix + kPixThreads - 1) / kPixThreads);
+    hipStream_t s = lb->stream;
+    int *P = lb->d_P, *Q = lb->d_Q;
+    hipLaunchKernelGGL(label_runs_kernel, dim3(row_grid(H)), dim3(64 * kRowWaves), 0, s, planes, K, H, W, o->cls, P);
+    hipLaunchKernelGGL(label_strip_kernel, dim3((unsigned)((H - 1) / kStripRows + 1)), dim3(kMergeThreads), 0, s, P, H, W);
+    for (long long span = kStripRows; span < H; span *= 2) {   // at most 26 levels
+        const long long seams = (H - span + 2 * span - 1) / (2 * span);
+        hipLaunchKernelGGL(label_seam_kernel, dim3((unsigned)seams), dim3(kMergeThreads), 0, s, P, H, W, span);
+    }
+    hipLaunchKernelGGL(label_heads_kernel, dim3(pix_grid), dim3(kPixThreads), 0, s, P, Q, npix, W);
+    hipLaunchKernelGGL(label_flatten_kernel, dim3(row_grid(H)), dim3(64 * kRowWaves), 0, s, P, Q, H, W);
+    L_HIP(lb, hipMemsetAsync(Q, 0, (size_t)npix * sizeof(int), s));
+    hipLaunchKernelGGL(label_area_kernel, dim3(row_grid(H)), dim3(64 * kRowWaves), 0, s, P, Q, H, W);
+    hipLaunchKernelGGL(label_count_kernel, dim3((unsigned)nblocks), dim3(64 * kScanWaves), 0, s, P, Q, npix, o->min_area, lb->d_counts);
+    hipLaunchKernelGGL(label_scan_kernel, dim3(1), dim3(kMergeThreads), 0, s, lb->d_counts, nblocks, lb->d_n);
+    hipLaunchKernelGGL(label_number_kernel, dim3((unsigned)nblocks), dim3(64 * kScanWaves), 0, s, P, Q, npix, o->min_area, lb->d_counts);
+    L_HIP(lb, hipGetLastError());
+    long long n = 0;
+    L_HIP(lb, hipMemcpyAsync(&n, lb->d_n, sizeof n, hipMemcpyDeviceToHost, s));
+    L_HIP(lb, hipStreamSynchronize(s));
+    if (n < 0 || n > npix) return lfail(lb, UMX_ERR_HIP, "the label scan counted %lld objects in %lld pixels", n, npix);
+    const int rc = ensure_table(lb, (size_t)n);
+    if (rc) return rc;
+    if (n > 0)
+        hipLaunchKernelGGL(label_table_init_kernel, dim3((unsigned)((n + kPixThreads - 1) / kPixThreads)), dim3(kPixThreads), 0, s, lb->d_table, n);
+    hipLaunchKernelGGL(label_write_kernel, dim3(row_grid(H)), dim3(64 * kRowWaves), 0, s, P, Q, H, W, out, lb->d_table);
+    L_HIP(lb, hipGetLastError());
+    *n_out = n;
+    return UMX_OK;
+}
+
+int run_any(umx_labeler* lb, const uint8_t* planes, bool on_host, int K, int H, int W, const umx_label_options* o, int32_t* labels,
+            int64_t* n_objects) {
+    if (!lb) return lfail(nullptr, UMX_ERR_INVALID, "null labeler");
+    char msg[200];
+    if (umx_label_options_check(o, K, H, W, msg, sizeof msg) != UMX_OK) return lfail(lb, UMX_ERR_INVALID, "%s", msg);
+    if (!planes) return lfail(lb, UMX_ERR_INVALID, "null planes");
+    L_HIP(lb, hipSetDevice(lb->device));
+    const size_t npix = (size_t)H * W, plane_bytes = (size_t)K * npix;
+    int rc = ensure_buffers(lb, on_host ? plane_bytes : 0, npix, (npix + kScanBlock - 1) / kScanBlock);
+    if (rc) return rc;
+    hipStream_t s = lb->stream;
+    lb->table.clear();
+    lb->ms[0] = lb->ms[1] = lb->ms[2] = 0.0;
+    L_HIP(lb, hipEventRecord(lb->ev[0], s));
+    if (on_host) L_HIP(lb, hipMemcpyAsync(lb->d_planes, planes, plane_bytes, hipMemcpyHostToDevice, s));
+    L_HIP(lb, hipEventRecord(lb->ev[1], s));
+    long long n = 0;
+    int* out = !labels ? nullptr : on_host ? lb->d_P : labels;
+    rc = run_launches(lb, on_host ? lb->d_planes : planes, K, H, W, o, out, &n);
+    if (rc) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    L_HIP(lb, hipEventRecord(lb->ev[2], s));
+    if (on_host && labels) L_HIP(lb, hipMemcpyAsync(labels, lb->d_P, npix * sizeof(int), hipMemcpyDeviceToHost, s));
+    lb->table.resize((size_t)n);
+    if (n > 0) L_HIP(lb, hipMemcpyAsync(lb->table.data(), lb->d_table, (size_t)n * sizeof(umx_label_object), hipMemcpyDeviceToHost, s));
+    L_HIP(lb, hipEventRecord(lb->ev[3], s));
+    L_HIP(lb, hipStreamSynchronize(s));
+    for (int k = 0; k < 3; ++k) {
+        float f = 0.f;
+        if (hipEventElapsedTime(&f, lb->ev[k], lb->ev[k + 1]) == hipSuccess) lb->ms[k] = f;
+    }
+    if (!on_host) lb->ms[0] = 0.0;
+    std::string gmsg;
+    if ((rc = arena_check(lb->mem, &gmsg)) != UMX_OK) return lfail(lb, rc, "%s", gmsg.c_str());
+    if (n_objects) *n_objects = n;
+    return UMX_OK;
+}
+
+}  // namespace
+
+}  // namespace umx
+
+using namespace umx;
+
+extern "C" {
+
+int umx_label_options_check(const umx_label_options* o, int K, int H, int W, char* msg, size_t cap) {
+    char buf[200] = "";
+    if (!o) snprintf(buf, sizeof buf, "null label options");
+    else if (H < 1 || W < 1) snprintf(buf, sizeof buf, "the image is %d x %d: both sides must be at least 1", H, W);
+    else if ((long long)H * W > INT_MAX)
+        snprintf(buf, sizeof buf, "the image is %d x %d: a flat pixel index is an int32, so H * W may be at most %d", H, W, INT_MAX);
+    else if (K < 1 || K > UMX_LABEL_MAX_CLASSES) snprintf(buf, sizeof buf, "there are %d planes: 1..%d classes", K, UMX_LABEL_MAX_CLASSES);
+    else if (o->cls < 0 || o->cls >= K) snprintf(buf, sizeof buf, "cls is %d: the class is 0..%d, in the model's class order", o->cls, K - 1);
+    else if (o->min_area < 1 || o->min_area > UMX_LABEL_MAX_MIN_AREA)
+        snprintf(buf, sizeof buf, "min_area is %d: it must be 1..%d pixels", o->min_area, UMX_LABEL_MAX_MIN_AREA);
+    for (int i = 0; o && !buf[0] && i < 6; ++i)
+        if (o->reserved[i]) snprintf(buf, sizeof buf, "reserved must be zero");
+    if (msg && cap) snprintf(msg, cap, "%s", buf);
+    return buf[0] ? UMX_ERR_INVALID : UMX_OK;
+}
+
+int umx_labeler_create(int device_ordinal, umx_labeler** out) {
+    if (!out) return lfail(nullptr, UMX_ERR_INVALID, "null output pointer");
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return lfail(nullptr, UMX_ERR_NO_DEVICE, "no HIP device available (libumx has no CPU fallback)");
+    if (device_ordinal < 0 || device_ordinal >= ndev)
+        return lfail(nullptr, UMX_ERR_INVALID, "device ordinal %d out of range (%d devices)", device_ordinal, ndev);
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device_ordinal) != hipSuccess) return lfail(nullptr, UMX_ERR_HIP, "hipGetDeviceProperties failed");
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return lfail(nullptr, UMX_ERR_NO_DEVICE, "device %d is %s; libumx is built for gfx950 only", device_ordinal, prop.gcnArchName);
+    std::unique_ptr<umx_labeler> lb(new umx_labeler());
+    lb->device = device_ordinal;
+    std::string why;
+    int rc = arena_init(&lb->mem, &why);
+    if (rc) return lfail(nullptr, rc, "%s", why.c_str());
+    L_HIP(nullptr, hipSetDevice(device_ordinal));
+    hipError_t e = hipStreamCreateWithFlags(&lb->stream, hipStreamNonBlocking);
+    for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipEventCreate(&lb->ev[k]);
+    if (e != hipSuccess) {
+        umx_labeler_destroy(lb.release());
+        return lfail(nullptr, UMX_ERR_HIP, "creating the labeler's stream and events failed: %s", hipGetErrorString(e));
+    }
+    *out = lb.release();
+    return UMX_OK;
+}
+
+void umx_labeler_destroy(umx_labeler* lb) {
+    if (!lb) return;
+    (void)hipSetDevice(lb->device);
+    if (lb->stream) (void)hipStreamSynchronize(lb->stream);
+    arena_free(&lb->mem);
+    for (hipEvent_t ev : lb->ev)
+        if (ev) (void)hipEventDestroy(ev);
+    if (lb->stream) (void)hipStreamDestroy(lb->stream);
+    delete lb;
+}
+
+const char* umx_labeler_last_error(const umx_labeler* lb) { return lb ? lb->err.c_str() : g_err.c_str(); }
+
+int umx_labeler_run(umx_labeler* lb, const uint8_t* planes_host, int K, int H, int W, const umx_label_options* o, int32_t* labels_host,
+                    int64_t* n_objects) {
+    return run_any(lb, planes_host, true, K, H, W, o, labels_host, n_objects);
+}
+
+int umx_labeler_run_dev(umx_labeler* lb, const uint8_t* planes_dev, int K, int H, int W, const umx_label_options* o, int32_t* labels_dev,
+                        int64_t* n_objects) {
+    return run_any(lb, planes_dev, false, K, H, W, o, labels_dev, n_objects);
+}
+
+int umx_labeler_objects(const umx_labeler* lb, umx_label_object* out, int64_t cap, int64_t* n) {
+    if (!lb || cap < 0 || (cap > 0 && !out)) return lfail(nullptr, UMX_ERR_INVALID, "umx_labeler_objects: null labeler, or a capacity without a buffer");
+    const int64_t have = (int64_t)lb->table.size(), m = std::min(cap, have);
+    if (m > 0) memcpy(out, lb->table.data(), (size_t)m * sizeof(umx_label_object));
+    if (n) *n = have;
+    return UMX_OK;
+}
+
+int umx_labeler_last_ms(const umx_labeler* lb, double* upload_ms, double* kernel_ms, double* download_ms) {
+    if (!lb) return lfail(nullptr, UMX_ERR_INVALID, "null labeler");
+    if (upload_ms) *upload_ms = lb->ms[0];
+    if (kernel_ms) *kernel_ms = lb->ms[1];
+    if (download_ms) *download_ms = lb->ms[2];
+    return UMX_OK;
+}
+
+}  // extern "C"

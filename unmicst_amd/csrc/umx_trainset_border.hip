@@ -12,6 +12,7 @@
 // finished labels of the launch before it.
 #include "../../include/umx_train.h"
 #include "umx_internal.h"
+#include "umx_unionfind.h"   // parent_load / parent_store / find_root / union_trees
 
 #include <algorithm>
 #include <climits>
@@ -28,40 +29,10 @@ constexpr int kBorderMaxR = 32;                          // ceil(4 * UMX_BORDER_
 constexpr int kBorderWin = kBorderTile + 2 * kBorderMaxR;   // 96 x 96 int32 = 36 KiB of LDS
 static_assert(kBorderMaxR == (int)(4.0f * UMX_BORDER_MAX_SIGMA), "the LDS window is sized for the largest sigma");
 
-// The parent plane is read and written through L2 only (relaxed, agent scope): the unions below change it with atomicMin, which
-// executes in L2, so a copy of a line in the CU's L1 could be stale inside the kernel.
-__device__ inline int parent_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline void parent_store(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
 // between two phases of the labelling: every store of the workgroup has reached L2 before any thread goes on
 __device__ inline void phase_barrier() {
     __threadfence();
     __syncthreads();
-}
-
-// The root of object pixel i.  Bound: a link of a non-root points at a strictly smaller index, so the walk takes at most i steps; a
-// value that is not such a link (>= i: the root; negative: never on an object pixel) ends it.
-__device__ inline int find_root(const int* P, int i) {
-    for (;;) {
-        const int p = parent_load(P + i);
-        if (p >= i || p < 0) return i;
-        i = p;
-    }
-}
-
-// Merge the trees of a and b: the larger root is hung under the smaller one with atomicMin.  When the larger one stopped being a root
-// in between (old != a), its link now points at min(old, b) and the pair (old, b) is still to be merged.  Bound: a retry only happens
-// with old < a, so the larger index of the pair strictly decreases from retry to retry: at most max(a, b) retries.
-__device__ inline void union_trees(int* P, int a, int b) {
-    for (;;) {
-        a = find_root(P, a);
-        b = find_root(P, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = atomicMin(P + a, b);
-        if (old == a) return;
-        a = old;
-    }
 }
 
 // P: the sample's [S][S] plane of the workspace.  Four phases, a barrier between them:

@@ -81,7 +81,39 @@ def build_parser(spec: ToolSpec) -> argparse.ArgumentParser:
     # host-side pre-processing, then one full pass of the engine per class written.  Same bytes in the files.
     p.add_argument("--compat-per-class", dest="compat_per_class", action="store_true",
                    help="A/B timing only: one full inference pass per output class, like the reference (same output bytes)")
+    # three more the reference does not have: the nuclei themselves ("Label mask").  From the uint8 planes
+    # this run writes -- whatever --classOrder says about their pages -- the 4-connected objects of one class, labelled on the device:
+    # <stem>_Labels_<suffix>.tif (one int32 page) and <stem>_Objects_<suffix>.csv next to the probability files.
+    p.add_argument("--labelMask", dest="labelMask", action="store_true",
+                   help="also write a label mask of the nuclei (int32 TIFF) and their table (CSV)")
+    p.add_argument("--labelClass", dest="labelClass", type=int, default=None,
+                   help="class whose objects are labelled, 0-based in the MODEL's class order (not --classOrder's); default: the last")
+    p.add_argument("--labelMinArea", dest="labelMinArea", type=int, default=None,
+                   help="objects of fewer pixels are dropped from the label mask (default 1)")
     return p
+
+
+def check_label_args(parser: argparse.ArgumentParser, args) -> None:
+    """The refusals of the label flags that need no model (parser.error: exit status 2, like any bad flag)."""
+    if not args.labelMask:
+        for flag, v in (("--labelClass", args.labelClass), ("--labelMinArea", args.labelMinArea)):
+            if v is not None:
+                parser.error("%s needs --labelMask" % flag)
+        return
+    if args.labelClass is not None and args.labelClass < 0:
+        parser.error("--labelClass %d: classes are numbered from 0" % args.labelClass)
+    if args.labelMinArea is not None and not 1 <= args.labelMinArea <= 65536:
+        parser.error("--labelMinArea %d: it must be 1..65536 pixels" % args.labelMinArea)
+
+
+def write_objects_csv(path: str, objects) -> None:
+    """label,area,y0,x0,y1,x1,centroid_y,centroid_x -- one line per kept object, label order; centroid = sum / area in float64."""
+    with open(path, "w") as f:
+        f.write("label,area,y0,x0,y1,x1,centroid_y,centroid_x\n")
+        area = objects["area"].astype(np.float64)
+        cols = [range(1, len(objects) + 1)] + [objects[n].tolist() for n in ("area", "y0", "x0", "y1", "x1")]
+        cols += [(objects["sum_y"] / area).tolist(), (objects["sum_x"] / area).tolist()]   # (sums below 2^53: exact in float64)
+        f.writelines("%d,%d,%d,%d,%d,%d,%.6f,%.6f\n" % row for row in zip(*cols))
 
 
 def models_root(script_dir: str) -> str:
@@ -179,13 +211,22 @@ def preview_u8(raw: np.ndarray, top_value=None) -> np.ndarray:
 def run(tool: str, argv=None, script_dir: str = None) -> int:
     spec = TOOLS[tool]
     st = _Stages()
-    args = build_parser(spec).parse_args(argv)
+    parser = build_parser(spec)
+    args = parser.parse_args(argv)
+    check_label_args(parser, args)
     script_dir = script_dir or os.path.dirname(os.path.dirname(os.path.realpath(__file__)))
     model_path = args.model if os.path.isdir(args.model) else os.path.join(models_root(script_dir), args.model)
 
     def channel_list():
         ch = [int(c) for c in args.channel] if spec.multi_channel else [int(args.channel)]
         return ([ch[0], ch[0]] if len(ch) == 1 else ch[:2]) if spec.n_inputs == 2 else [ch[0]]
+
+    label_art = None
+    if args.labelMask:
+        from . import model as _model
+        label_art = _model.load_model_dir(model_path, None, synthetic_if_missing=os.environ.get("UMX_SYNTHETIC_WEIGHTS", "0") not in ("", "0"))
+        if args.labelClass is not None and args.labelClass >= label_art.hp.nClasses:
+            parser.error("--labelClass %d: the model has classes 0..%d" % (args.labelClass, label_art.hp.nClasses - 1))
 
     # the page(s) are read on a thread while the engine is set up (model load, planning, weight packing: 0.2 - 0.6 s against
     # 0.18 s of file reading for a 16384 x 16384 page; both release the GIL).  An error of the read surfaces where the reference
@@ -197,7 +238,10 @@ def run(tool: str, argv=None, script_dir: str = None) -> int:
     if args.GPU == -1:
         print("automatically choosing GPU")
     try:
-        UNet2D.singleImageInferenceSetup(model_path, args.GPU, args.mean, args.std, graph=None)
+        if args.labelMask:   # (the class count comes from the model: its directory is read first, the engine set up after the check)
+            UNet2D.setupWithArtefacts(label_art, args.GPU, args.mean, args.std)
+        else:
+            UNet2D.singleImageInferenceSetup(model_path, args.GPU, args.mean, args.std, graph=None)
     except BaseException:
         _pool.shutdown(wait=True)
         raise
@@ -292,6 +336,14 @@ def run(tool: str, argv=None, script_dir: str = None) -> int:
             tiffio.imsave(cont, preview_job.result() if preview_job else preview_u8(raw, top_value), append=True)
             tiffio.imsave(out_dir + "//" + stem + "_NucleiPM_" + suffix + ".tif", plane_u8(class_order[2]), append=False)
         st.mark("write")
+        if args.labelMask:
+            from . import umx as _umx
+            stack_u8 = u8_planes if fast else np.stack([plane_u8(k) for k in range(n_class)])
+            with _umx.Labeler(UNet2D.Engine.device) as labeler:
+                labels, objects = labeler.run(stack_u8, args.labelClass, 1 if args.labelMinArea is None else args.labelMinArea)
+            tiffio.imsave(out_dir + "//" + stem + "_Labels_" + suffix + ".tif", labels, append=False)
+            write_objects_csv(out_dir + "//" + stem + "_Objects_" + suffix + ".csv", objects)
+            st.mark("label")
     finally:
         if args.compat_per_class:
             UNet2D.reuse_pass = reuse_before

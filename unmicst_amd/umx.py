@@ -33,7 +33,13 @@ EXPORTS = [
     "umx_band_tiles_dev", "umx_stitch_dev", "umx_profile_enable", "umx_profile_read", "umx_prof_entry_size", "umx_test_double_to_half", "umx_test_double_to_half_dev",
     "umx_test_gauss_weights", "umx_test_resize_dev", "umx_test_rescale_dev", "umx_test_plane_range_dev", "umx_test_half_to_u8_dev",
     "umx_describe", "umx_describe_graph", "umx_plan_check", "umx_test_mx_pack_e2m3", "umx_version",
+    "umx_label_options_check", "umx_labeler_create", "umx_labeler_destroy", "umx_labeler_last_error", "umx_labeler_run",
+    "umx_labeler_run_dev", "umx_labeler_objects", "umx_labeler_last_ms",
 ]
+
+# the label mask's limits and the geometry of its kernels (the UMX_LABEL_* macros of include/umx.h; tests/test_label_cpu.py compares)
+LABEL_MAX_CLASSES, LABEL_MAX_MIN_AREA = 16, 65536
+LABEL_STRIP_ROWS, LABEL_THREADS, LABEL_SCAN_BLOCK = 32, 1024, 2048
 
 
 class UmxError(RuntimeError):
@@ -57,6 +63,20 @@ class ProfEntry(ctypes.Structure):
                 ("total_ms", ctypes.c_double), ("flops", ctypes.c_double), ("bytes", ctypes.c_double),
                 ("exec_flops", ctypes.c_double), ("launches_seen", ctypes.c_int64), ("xcd_order", ctypes.c_int32),
                 ("reserved", ctypes.c_int32)]
+
+
+class _LabelOptions(ctypes.Structure):
+    """umx_label_options"""
+    _fields_ = [("cls", ctypes.c_int32), ("min_area", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6)]
+
+
+class LabelObject(ctypes.Structure):
+    """umx_label_object: 40 bytes"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("area", "y0", "x0", "y1", "x1", "reserved")] + [("sum_y", ctypes.c_int64), ("sum_x", ctypes.c_int64)]
+
+
+# the same record as a numpy dtype: what Labeler.run returns its table in
+LABEL_OBJECT_DTYPE = np.dtype([(n, "<i4") for n in ("area", "y0", "x0", "y1", "x1", "reserved")] + [("sum_y", "<i8"), ("sum_x", "<i8")])
 
 
 _SEND_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p)
@@ -223,6 +243,21 @@ def load(path: Optional[str] = None):
     L.umx_describe_graph.argtypes = [ctypes.POINTER(_HP), ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     L.umx_describe_graph.restype = c_int
     L.umx_version.restype = ctypes.c_char_p
+    L.umx_label_options_check.restype = c_int
+    L.umx_label_options_check.argtypes = [ctypes.POINTER(_LabelOptions), c_int, c_int, c_int, ctypes.c_char_p, ctypes.c_size_t]
+    L.umx_labeler_create.restype = c_int
+    L.umx_labeler_create.argtypes = [c_int, ctypes.POINTER(c_void_p)]
+    L.umx_labeler_destroy.restype = None
+    L.umx_labeler_destroy.argtypes = [c_void_p]
+    L.umx_labeler_last_error.restype = ctypes.c_char_p
+    L.umx_labeler_last_error.argtypes = [c_void_p]
+    for fn in (L.umx_labeler_run, L.umx_labeler_run_dev):
+        fn.restype = c_int
+        fn.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(_LabelOptions), c_void_p, ctypes.POINTER(ctypes.c_int64)]
+    L.umx_labeler_objects.restype = c_int
+    L.umx_labeler_objects.argtypes = [c_void_p, c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+    L.umx_labeler_last_ms.restype = c_int
+    L.umx_labeler_last_ms.argtypes = [c_void_p] + [ctypes.POINTER(c_double)] * 3
     L.umx_prof_entry_size.restype = c_int
     if L.umx_prof_entry_size() != ctypes.sizeof(ProfEntry):
         raise RuntimeError("libumx (%s) lays umx_prof_entry out in %d bytes, this binding in %d: mixed builds" % (
@@ -433,6 +468,91 @@ def shard_plan(hp: HParams, H: int, W: int, rank: int, world: int, nslabs: int =
         raise UmxError(rc, L.umx_last_error(None).decode())
     names = ("patch_row0", "patch_row1", "need_row0", "need_row1", "own_row0", "own_row1", "slab_row0", "slab_row1", "nslabs")
     return {n: x.value for n, x in zip(names, v)}
+
+
+def label_options_check(K: int, H: int, W: int, cls: int, min_area: int = 1, reserved=None) -> str:
+    """umx_label_options_check: "" if a label mask of K planes of H x W for class ``cls`` and ``min_area`` is accepted, else the
+    reason.  Host only."""
+    o = _LabelOptions(int(cls), int(min_area))
+    for j, v in enumerate(reserved or ()):
+        o.reserved[j] = int(v)
+    buf = ctypes.create_string_buffer(256)
+    rc = load().umx_label_options_check(ctypes.byref(o), int(K), int(H), int(W), buf, len(buf))
+    return "" if rc == 0 else buf.value.decode()
+
+
+class Labeler:
+    """One umx_labeler: the label mask (include/umx.h) of uint8 probability stacks on one MI355X.  It needs no
+    model; its device buffers grow on demand and are kept between runs."""
+
+    def __init__(self, device: int = 0):
+        self._L = load()
+        self._lb = ctypes.c_void_p()
+        rc = self._L.umx_labeler_create(int(device), ctypes.byref(self._lb))
+        if rc:
+            raise UmxError(rc, self._L.umx_labeler_last_error(None).decode())
+        self.device = device
+
+    def close(self) -> None:
+        if getattr(self, "_lb", None) and self._lb.value:
+            self._L.umx_labeler_destroy(self._lb)
+            self._lb = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _check(self, rc: int) -> None:
+        if rc:
+            raise UmxError(rc, self._L.umx_labeler_last_error(self._lb).decode())
+
+    def objects(self) -> np.ndarray:
+        """The table of the last run: a structured array (LABEL_OBJECT_DTYPE), one record per kept object in label order."""
+        n = ctypes.c_int64()
+        self._check(self._L.umx_labeler_objects(self._lb, None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, LABEL_OBJECT_DTYPE)
+        if n.value:
+            self._check(self._L.umx_labeler_objects(self._lb, out.ctypes.data, n.value, ctypes.byref(n)))
+        return out
+
+    def last_ms(self):
+        """(upload, kernel, download) milliseconds of the last run, by HIP events on the labeler's stream."""
+        v = [ctypes.c_double() for _ in range(3)]
+        self._check(self._L.umx_labeler_last_ms(self._lb, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def run(self, planes: np.ndarray, cls: Optional[int] = None, min_area: int = 1, want_labels: bool = True):
+        """planes uint8 [K, H, W] in the model's class order -> (labels int32 [H, W], objects); ``cls`` None: the last class.
+        want_labels False: labels is None (only the count and the table come down)."""
+        planes = np.ascontiguousarray(planes)
+        if planes.dtype != np.uint8 or planes.ndim != 3:
+            raise TypeError("planes must be uint8 [K, H, W]")
+        K, H, W = planes.shape
+        o = _LabelOptions(K - 1 if cls is None else int(cls), int(min_area))
+        labels = np.empty((H, W), np.int32) if want_labels else None
+        n = ctypes.c_int64()
+        self._check(self._L.umx_labeler_run(self._lb, planes.ctypes.data, K, H, W, ctypes.byref(o),
+                                            labels.ctypes.data if want_labels else None, ctypes.byref(n)))
+        objs = self.objects()
+        assert len(objs) == n.value
+        return labels, objs
+
+    def run_ptr(self, planes_ptr: int, K: int, H: int, W: int, labels_ptr: int = 0, cls: Optional[int] = None, min_area: int = 1) -> np.ndarray:
+        """umx_labeler_run_dev on DEVICE addresses (e.g. torch.Tensor.data_ptr()): uint8 [K, H, W] in, int32 [H, W] out (0: no label
+        plane) -> objects.  The planes must be complete; the call returns with the labels complete."""
+        o = _LabelOptions(K - 1 if cls is None else int(cls), int(min_area))
+        n = ctypes.c_int64()
+        self._check(self._L.umx_labeler_run_dev(self._lb, ctypes.c_void_p(planes_ptr), int(K), int(H), int(W), ctypes.byref(o),
+                                                ctypes.c_void_p(labels_ptr or None), ctypes.byref(n)))
+        return self.objects()
 
 
 class Engine:
