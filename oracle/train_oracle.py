@@ -178,7 +178,10 @@ def _conv_transpose_s2(x, wt_tf):
     return full[:, :, pbh:pbh + H2, pbw:pbw + W2]
 
 
-def _bn(x, P, prefix, training, stats):
+def _bn(x, P, prefix, training, stats, trace=None, fused=False):
+    """fused (test aid): the kernels' form, z * scale + shift with ONE rounding (the product of two float32 is exact in float64), so
+    that the sign of the result is a function of z, scale and shift alone; trace receives <prefix>.z, <prefix>.stat ([mean,
+    1 / sqrt(var + eps), scale, shift], the layout umx_trainer_read_tensor serves) and, after backward(), <prefix>.dz."""
     g, b = P[prefix + ".bn.gamma"], P[prefix + ".bn.beta"]
     if training:
         mean = x.mean(dim=(0, 2, 3))
@@ -187,6 +190,17 @@ def _bn(x, P, prefix, training, stats):
         stats[prefix] = (mean.detach(), var.detach(), n)
     else:
         mean, var = P[prefix + ".bn.mean"], P[prefix + ".bn.var"]
+    if trace is not None:
+        trace[prefix + ".z"] = x.detach()
+        if x.requires_grad:
+            x.register_hook(lambda gz: trace.__setitem__(prefix + ".dz", gz.detach()))
+    if fused:
+        rstd = torch.rsqrt(var + BN_EPS)
+        scale = g * rstd
+        shift = b - mean * scale
+        if trace is not None:
+            trace[prefix + ".stat"] = torch.stack([mean, rstd, scale, shift]).detach()
+        return (x.double() * scale.double()[None, :, None, None] + shift.double()[None, :, None, None]).to(x.dtype)
     xh = (x - mean[None, :, None, None]) * torch.rsqrt(var[None, :, None, None] + BN_EPS)
     return xh * g[None, :, None, None] + b[None, :, None, None]
 
@@ -206,7 +220,7 @@ def _leaky(a, site, decisions, trace):
     if trace is not None:
         trace[site] = a.detach()
     if decisions is not None and site in decisions:
-        return a * decisions[site]
+        return a * decisions[site].to(a.dtype)
     return F.leaky_relu(a, LEAK)
 
 
@@ -222,29 +236,30 @@ def _pool(a, site, decisions, trace):
 
 
 def forward(hp, P: Dict[str, torch.Tensor], data_nhwc: torch.Tensor, o: TrainOptions, step: int, training: bool,
-            decisions=None, trace=None):
+            decisions=None, trace=None, fused_bn=False):
     """-> (softmax probabilities NHWC, BN batch statistics per layer).
 
     decisions (test aid, tests/test_gpu_train.py): {"ld<i>" | "lb" | "lu<i>" | "us<i>": slopes, "pool<i>": window elements} -- the
     LeakyReLU branches and max-pool choices of ANOTHER evaluation of the same step (the HIP kernels'), so that two implementations
-    are compared on the same smooth piece of the loss; trace: dict that receives the tensor in front of every such decision."""
+    are compared on the same smooth piece of the loss; trace: dict that receives the tensor in front of every such decision (and
+    what _bn adds); fused_bn: see _bn."""
     L = hp.nLayers
     stats: Dict[str, tuple] = {}
     x = data_nhwc.permute(0, 3, 1, 2)
     ds = [x]
     for i in range(L):
         z = _conv_same(ds[i], P["ld%d.w1" % i]) + _conv_same(ds[i], P["ld%d.wshort" % i])
-        a = _leaky(_bn(z, P, "ld%d" % i, training, stats), "ld%d" % i, decisions, trace)
+        a = _leaky(_bn(z, P, "ld%d" % i, training, stats, trace, fused_bn), "ld%d" % i, decisions, trace)
         a = _drop(a, o.drop_down_step * i, o, step, LAYER_DOWN + i, training)
         ds.append(_pool(a, "pool%d" % i, decisions, trace))
-    b = _leaky(_bn(_conv_same(ds[L], P["lb.w"]), P, "lb", training, stats), "lb", decisions, trace)
+    b = _leaky(_bn(_conv_same(ds[L], P["lb.w"]), P, "lb", training, stats, trace, fused_bn), "lb", decisions, trace)
     cur = _drop(b, o.drop_bottom, o, step, LAYER_BOTTOM, training)
     for idx in range(L - 1, -1, -1):
         us = _leaky(_conv_transpose_s2(cur, P["lu%d.wt" % idx]), "us%d" % idx, decisions, trace)
         cc = torch.cat([ds[idx], us], dim=1)
-        cv = _leaky(_bn(_conv_same(cc, P["lu%d.w2" % idx]), P, "lu%d" % idx, training, stats), "lu%d" % idx, decisions, trace)
+        cv = _leaky(_bn(_conv_same(cc, P["lu%d.w2" % idx]), P, "lu%d" % idx, training, stats, trace, fused_bn), "lu%d" % idx, decisions, trace)
         cur = _drop(cv, o.drop_up0 - o.drop_up_step * idx, o, step, LAYER_UP + idx, training)
-    t = _bn(_conv_same(cur, P["lt.w"]), P, "lt", training, stats)
+    t = _bn(_conv_same(cur, P["lt.w"]), P, "lt", training, stats, trace, fused_bn)
     return torch.softmax(t, dim=1).permute(0, 2, 3, 1), stats
 
 
@@ -281,7 +296,8 @@ class TrainState:
             self.v = np.zeros_like(self.blob)
 
 
-def loss_and_grads(hp, blob, data, labels, weights, o: TrainOptions, step: int, dtype=torch.float64, decisions=None, trace=None):
+def loss_and_grads(hp, blob, data, labels, weights, o: TrainOptions, step: int, dtype=torch.float64, decisions=None, trace=None,
+                   fused_bn=False):
     """-> (loss, data_term, reg, grads as a blob-shaped float64 vector (0 for the moving statistics), probs, stats).
     decisions / trace: see forward()."""
     T = split_blob(hp, np.asarray(blob, dtype=np.float64))
@@ -289,7 +305,7 @@ def loss_and_grads(hp, blob, data, labels, weights, o: TrainOptions, step: int, 
     d = torch.tensor(np.asarray(data), dtype=dtype)
     y = torch.tensor(np.asarray(labels), dtype=dtype)
     w = torch.tensor(np.asarray(weights), dtype=dtype)
-    probs, stats = forward(hp, P, d, o, step, training=True, decisions=decisions, trace=trace)
+    probs, stats = forward(hp, P, d, o, step, training=True, decisions=decisions, trace=trace, fused_bn=fused_bn)
     loss, data_term, reg = loss_of(hp, P, probs, y, w, o)
     loss.backward()
     grads = {k: (P[k].grad.numpy() if trainable(k) and P[k].grad is not None else np.zeros(T[k].shape)) for k in T}

@@ -20,102 +20,11 @@ import numpy as np
 import pytest
 
 import helpers
+import train_parity
+from train_parity import LOOSE, TIGHT, _batch, _count_flips, _hip_decisions, _oracle_opts, _per_tensor
 from unmicst_amd import model, trainer, umx
 
 pytestmark = pytest.mark.gpu
-
-
-def _batch(hp, B, seed):
-    rng = np.random.default_rng(seed)
-    data = rng.normal(0, 1, (B, hp.imSize, hp.imSize, hp.nChannels)).astype(np.float32)
-    cls = rng.integers(0, hp.nClasses, (B, hp.imSize, hp.imSize))
-    labels = np.eye(hp.nClasses, dtype=np.float32)[cls]
-    weights = rng.uniform(0.5, 3.0, labels.shape).astype(np.float32)
-    return data, labels, weights
-
-
-def _oracle_opts(o: trainer.TrainOptions):
-    from oracle import train_oracle as to
-    kw = {k: getattr(o, k) for k in ("lr0", "decay_steps", "decay_rate", "momentum", "beta1", "beta2", "adam_eps",
-                                      "reg_kind", "reg_down", "reg_bottom", "reg_up", "reg_top", "clip_eps",
-                                      "drop_down_step", "drop_bottom", "drop_up0", "drop_up_step", "bn_momentum", "seed")}
-    kw["optimizer"] = "adam" if o.optimizer == trainer.OPT_ADAM else "momentum"
-    return to.TrainOptions(**kw)
-
-
-TIGHT, LOOSE = 2e-5, 5e-2
-TOP = ("lt.w", "lt.bn.gamma", "lt.bn.beta", "lu0.bn.gamma", "lu0.bn.beta", "lu0.w2")
-
-
-def _per_tensor(hp, got, want, what, rel=LOOSE, top=TIGHT):
-    """-> worst relative error over the tensors; asserts rel on every tensor and `top` on the top of the graph."""
-    from oracle import train_oracle as to
-    G, W = to.split_blob(hp, got), to.split_blob(hp, want)
-    worst = 0.0
-    for name in W:
-        scale = np.abs(W[name]).max()
-        err = np.abs(G[name] - W[name]).max()
-        assert err <= (top if name in TOP else rel) * scale + 1e-7, (what, name, err, scale)
-        worst = max(worst, err / (scale + 1e-30))
-    return worst
-
-
-def _hip_decisions(tr, hp, opts, step, B):
-    """The LeakyReLU branches and max-pool choices the HIP kernels took in their last forward pass, rebuilt from the tensors they
-    were taken on (umx_trainer_read_tensor): BN output = z * scale + shift evaluated exactly (float64 product of two float32 +
-    one rounding: the sign of the kernels' fused multiply-add), the pooled element = first maximum of act(v) * dropout in float32
-    like act_fwd_kernel.  Given to the oracle (train_oracle.forward(decisions=...)) the two implementations differentiate the SAME
-    smooth piece of the loss, so every gradient tensor can be held to TIGHT -- at any size, however many activations sit within
-    rounding distance of zero."""
-    import torch
-    from oracle import train_oracle as to
-    n, L, S = hp.nOutX, hp.nLayers, hp.imSize
-    dec = {}
-
-    def nchw(a):
-        return torch.from_numpy(np.ascontiguousarray(a.transpose(0, 3, 1, 2)))
-
-    def bn_value(layer, S, C):
-        z = tr.read_tensor(layer + ".z").reshape(B, S, S, C).astype(np.float64)
-        st = tr.read_tensor(layer + ".stat").reshape(4, C).astype(np.float64)
-        return z * st[2] + st[3]
-
-    for i in range(L):
-        C = n[i + 1]
-        v = bn_value("ld%d" % i, S, C)
-        dec["ld%d" % i] = nchw(np.where(v > 0, 1.0, to.LEAK))
-        v32 = v.astype(np.float32)
-        y = np.where(v32 > 0, v32, np.float32(0.2) * v32).astype(np.float32)
-        m = to.dropout_mask(opts.seed, step, to.LAYER_DOWN + i, (B, S, S, C), opts.drop_down_step * i).astype(np.float32)
-        y = y * m
-        win = y.reshape(B, S // 2, 2, S // 2, 2, C).transpose(0, 1, 3, 5, 2, 4).reshape(B, S // 2, S // 2, C, 4)   # element 2 dy + dx
-        dec["pool%d" % i] = torch.from_numpy(np.ascontiguousarray(win.argmax(-1).transpose(0, 3, 1, 2))).long()
-        S //= 2
-    dec["lb"] = nchw(np.where(bn_value("lb", S, n[L + 1]) > 0, 1.0, to.LEAK))
-    for idx in range(L - 1, -1, -1):
-        S *= 2
-        C = n[idx + 1]
-        us = tr.read_tensor("lu%d.us" % idx).reshape(B, S, S, C)
-        dec["us%d" % idx] = nchw(np.where(us > 0, 1.0, to.LEAK))
-        dec["lu%d" % idx] = nchw(np.where(bn_value("lu%d" % idx, S, C) > 0, 1.0, to.LEAK))
-    return dec
-
-
-def _count_flips(dec, trace):
-    """Per site: decisions of `dec` (the kernels') that differ from what the oracle's own values (trace) would take."""
-    import torch
-    from oracle import train_oracle as to
-    flips = {}
-    for site, d in dec.items():
-        a = trace[site]
-        if site.startswith("pool"):
-            B, C, H, W = a.shape
-            win = a.reshape(B, C, H // 2, 2, W // 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(B, C, H // 2, W // 2, 4)
-            own = win.argmax(-1)
-            flips[site] = (int((own != d).sum()), int(d.numel()))
-        else:   # (slopes: 1 on the positive branch, 0.2 on the other)
-            flips[site] = (int(((a > 0) != (d > 0.5)).sum()), int(d.numel()))
-    return flips
 
 
 CASES = [("v2_solo_like", 4, "solo"), ("v2_duo_like", 4, "duo"), ("v2_deep", 3, "duo"), ("v2_wide", 2, "solo"),
@@ -397,7 +306,7 @@ def test_baseline_config_256x256x2_batch8_against_the_oracle():
     tr = trainer.Trainer(hp, blob, opts, batch=8)
     loss, data_term, reg = tr.step(data, labels, weights, apply_update=False)
     g = tr.grads()
-    dec = _hip_decisions(tr, hp, opts, 0, 8)
+    dec = _hip_decisions(tr.read_tensor, hp, opts, 0, 8)
     tr.close()
     torch.set_num_threads(max(1, torch.get_num_threads()))
     trace = {}
@@ -464,7 +373,8 @@ def test_weight_gradient_of_a_deep_layer_against_finite_differences_of_the_kerne
 ])
 def test_odd_shapes_match_oracle(hp_args, B):
     """Shapes off the beaten path: every launch geometry (image groups, partial channel tiles, tiny layers) must still be
-    right -- loss 1e-5, gradients within the discontinuity bound, nothing out of range."""
+    right -- loss 1e-5, gradients within the discontinuity bound against the free float64 run and within TIGHT on the kernels' own
+    decisions (train_parity.check_on_decisions), nothing out of range."""
     from oracle import train_oracle as to
     hp = model.HParams(model.GRAPH_V2, *hp_args)
     opts = trainer.duo_options()
@@ -472,10 +382,16 @@ def test_odd_shapes_match_oracle(hp_args, B):
     data, labels, weights = _batch(hp, B, 23)
     want = to.loss_and_grads(hp, blob, data, labels, weights, _oracle_opts(opts), step=0)
     tr = trainer.Trainer(hp, blob, opts, batch=B)
-    loss = tr.step(data, labels, weights, apply_update=False)[0]
+    loss, _, reg = tr.step(data, labels, weights, apply_update=False)
     assert loss == pytest.approx(want[0], rel=1e-5)
     _per_tensor(hp, tr.grads(), want[3], "odd shape grads", rel=0.1, top=0.1)
     assert np.abs(tr.probs() - want[4]).max() <= 2e-5
+    # ... and, on the kernels' own decisions, every gradient tensor within TIGHT (and the decisions within the flip cap)
+    dec = _hip_decisions(tr.read_tensor, hp, opts, 0, B)
+    trace = {}
+    on_dec = to.loss_and_grads(hp, blob, data, labels, weights, _oracle_opts(opts), step=0, decisions=dec, trace=trace)
+    train_parity.check_on_decisions(hp, {"loss": loss, "reg": reg, "probs": tr.probs(), "grads": tr.grads()}, on_dec, dec, trace,
+                                    "odd shape %r" % (hp_args,))
     l2 = tr.step(data, labels, weights)[0]
     assert l2 == pytest.approx(want[0], rel=1e-5) and tr.step_count == 1
     tr.close()

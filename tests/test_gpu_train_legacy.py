@@ -2,7 +2,7 @@
 C ABI of include/umx_train.h, against tests/legacy_train_ref.py (float64 autograd).
 
 The gradients are compared on the kernels' own decisions (every ReLU branch and pool choice rebuilt from umx_trainer_read_tensor,
-as tests/test_gpu_train.py::_hip_decisions does for v2), so every tensor is held to TIGHT: max-abs error <= 2e-5 of its max-abs."""
+as tests/train_parity.py::_hip_decisions does for v2), so every tensor is held to TIGHT: max-abs error <= 2e-5 of its max-abs."""
 import numpy as np
 import pytest
 import torch

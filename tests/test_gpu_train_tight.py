@@ -1,0 +1,191 @@
+"""GPU tests of the v2 training step ON THE KERNELS' OWN DECISIONS, at every case, convolution route and odd shape: one
+Trainer.step(apply_update=False) against oracle/train_oracle.py given the LeakyReLU branches and pool choices the kernels took
+(tests/train_parity.py: _hip_decisions from umx_trainer_read_tensor, check_on_decisions).  Loss and regulariser 1e-5 relative,
+probabilities 2e-5, EVERY trainable tensor's gradient within TIGHT = 2e-5 of its max-abs value, and per decision site at most
+1e-4 * n + 2 branches that differ from the float64 run's own.  tests/test_train_parity_cpu.py proves the same code on a float32 run of
+the oracle for every case, seed and step used here (worst tensor 1.0e-6 .. 4.1e-6, at most 3 flips).
+
+A gradient outside TIGHT here, with the stand-in inside TIGHT / 2 on the same case, is a finding about a kernel: the message names the
+tensor, the failing test prints the trainer's launch plan (UMX_DEBUG_PLAN), and the routes separate the kernels (UMX_TRAIN_WGRAD_F32
+the weight gradients, UMX_TRAIN_CONV_F32 the forward / input-gradient convolutions, UMX_TRAIN_NO_KSPLIT the split and its reduce).
+
+MEASURED (MI355X; worst gradient tensor over its max-abs value, the float32 stand-in of the CPU test beside the five routes; records,
+not tolerances):
+  case                     stand-in | f16x3     CONV_F32  NO_KSPLIT WGRAD_F32 CONV+WGRAD_F32
+  v2_solo_like-solo         2.2e-06 | 1.7e-06   1.7e-06   1.6e-06   1.7e-06   1.7e-06  
+  v2_duo_like-duo           2.5e-06 | 1.4e-06   1.9e-06   1.7e-06   1.4e-06   1.9e-06  
+  v2_deep-duo               2.3e-06 | 1.6e-06   2.4e-06   2.0e-06   1.6e-06   2.4e-06  
+  v2_wide-solo              3.1e-06 | 2.6e-06   2.0e-06   3.3e-06   2.6e-06   2.0e-06  
+  v2_wide-duo               3.0e-06 | 3.0e-06   2.5e-06   2.8e-06   3.0e-06   2.6e-06  
+  v2_k5-duo                 1.9e-06 | 1.2e-06   1.9e-06   1.1e-06   1.2e-06   1.9e-06  
+  odd_b1_l1                 1.2e-06 | 7.5e-07   4.5e-07   5.9e-07   7.5e-07   4.5e-07  
+  odd_c3k4                  4.1e-06 | 2.7e-06   3.2e-06   2.5e-06   2.7e-06   3.2e-06  
+  odd_l5_2x2                2.8e-06 | 3.7e-06   1.7e-06   3.9e-06   3.7e-06   1.7e-06  
+  odd_k5_4x4                1.5e-06 | 8.8e-07   1.7e-06   1.8e-06   8.8e-07   1.7e-06  
+  odd_128                   4.1e-06 | 2.2e-06   1.5e-06   2.5e-06   2.2e-06   1.5e-06  
+  group_b7_l3               2.4e-06 | 2.7e-06   2.4e-06   3.3e-06   2.7e-06   2.4e-06  
+  group_b3_l5               2.7e-06 | 3.9e-06   1.8e-06   3.0e-06   3.9e-06   1.8e-06  
+  scalar_n6                 1.2e-06 | 9.5e-07   1.1e-06   7.3e-07   9.4e-07   1.2e-06  
+  scalar_n5                 9.8e-07 | 1.0e-06   1.2e-06   9.9e-07   1.0e-06   1.2e-06  
+  first_c5                  1.6e-06 | 1.8e-06   1.3e-06   1.6e-06   1.8e-06   1.3e-06  
+  first_c9                  1.9e-06 | 1.7e-06   1.5e-06   1.4e-06   1.7e-06   1.5e-06  
+  first_wide                2.3e-06 | 6.8e-07   9.3e-07   1.8e-06   6.8e-07   9.9e-07  
+  classes_2                 1.0e-06 | 1.3e-06   9.8e-07   9.0e-07   1.3e-06   9.7e-07  
+  classes_5                 1.5e-06 | 1.3e-06   1.0e-06   1.2e-06   1.3e-06   1.0e-06  
+  momentum                  2.2e-06 | 1.5e-06   1.9e-06   2.3e-06   1.5e-06   1.9e-06  
+  v2_duo_like-duo step 1    1.9e-06 | 1.0e-06   1.8e-06   1.3e-06   1.3e-06   1.6e-06  
+  scalar_n5 step 1          9.1e-07 | 8.5e-07   1.1e-06   8.7e-07   7.4e-07   1.0e-06  
+  momentum step 1           1.6e-06 | 1.1e-06   2.0e-06   1.2e-06   9.5e-07   1.7e-06
+Flips (decisions differing from the float64 run's own, of 3.8e3 .. 1.7e6 per case): none but one element of one site in
+v2_wide-solo (lu2; us0 on the CONV_F32 routes), v2_deep-duo, odd_l5_2x2, group_b7_l3 and first_wide (CONV_F32 routes: us0 / us3 / lu2);
+the stand-in has 3 in v2_wide-solo (lu2 2, us0 1) and 1 in classes_2 (us1).  No case found a kernel outside the bound."""
+import re
+
+import numpy as np
+import pytest
+
+import train_parity as tp
+from oracle import train_oracle as to
+from unmicst_amd import model, trainer
+
+pytestmark = pytest.mark.gpu
+
+CASES = tp.tight_cases()
+ROUTES = list(zip(tp.ROUTE_IDS, tp.ROUTES))
+
+
+def _trainer(monkeypatch, capfd, hp, blob, opts, B, route):
+    """-> (trainer on this route, the lines of its launch plan)."""
+    for k, v in route.items():
+        monkeypatch.setenv(k, v)
+    monkeypatch.setenv("UMX_DEBUG_PLAN", "1")
+    capfd.readouterr()
+    tr = trainer.Trainer(hp, blob, opts, batch=B)
+    plan = [ln for ln in capfd.readouterr().err.splitlines() if ln.startswith("[umx train]")]
+    return tr, plan
+
+
+def _check_last_step(tr, out, hp, blob, batch, opts, step, B, what, plan):
+    """The step `tr` just took without an update (out: its losses) against the oracle on the kernels' decisions."""
+    got = {"loss": out[0], "reg": out[2], "probs": tr.probs(), "grads": tr.grads()}
+    dec = tp._hip_decisions(tr.read_tensor, hp, opts, step, B)
+    trace = {}
+    want = to.loss_and_grads(hp, blob, *batch, tp._oracle_opts(opts), step=step, decisions=dec, trace=trace)
+    try:
+        res = tp.check_on_decisions(hp, got, want, dec, trace, what)
+    except AssertionError:
+        print("\n".join(plan))
+        raise
+    print("%s: worst %.2e (%s), flips %s of %d" % (what, res["worst"], res["tensor"], res["flips"] or "none", res["sites"]))
+
+
+@pytest.mark.parametrize("rid,route", ROUTES, ids=tp.ROUTE_IDS)
+@pytest.mark.parametrize("cid", list(CASES))
+def test_step_matches_the_oracle_on_the_kernels_decisions(cid, rid, route, monkeypatch, capfd):
+    hp, B, regime, blob_seed, batch_seed = CASES[cid]
+    opts = tp.trainer_options(regime)
+    blob = model.random_blob(hp, seed=blob_seed)
+    batch = tp._batch(hp, B, batch_seed)
+    tr, plan = _trainer(monkeypatch, capfd, hp, blob, opts, B, route)
+    try:
+        out = tr.step(*batch, apply_update=False)
+        assert tr.step_count == 0
+        _check_last_step(tr, out, hp, blob, batch, opts, 0, B, "%s %s" % (cid, rid), plan)
+        assert np.array_equal(tr.blob(), blob)
+    finally:
+        tr.close()
+
+
+@pytest.mark.parametrize("rid,route", ROUTES, ids=tp.ROUTE_IDS)
+@pytest.mark.parametrize("cid", tp.STEP1_CASES)
+def test_second_step_matches_the_oracle_on_the_kernels_decisions(cid, rid, route, monkeypatch, capfd):
+    """After one applied update (Adam, or momentum): the step counter is 1, so every dropout layer draws from the stream of step 1,
+    and the parameters are the trainer's own (tr.blob()), moving statistics included."""
+    hp, B, regime, blob_seed, batch_seed = CASES[cid]
+    opts = tp.trainer_options(regime)
+    blob = model.random_blob(hp, seed=blob_seed)
+    tr, plan = _trainer(monkeypatch, capfd, hp, blob, opts, B, route)
+    try:
+        tr.step(*tp._batch(hp, B, batch_seed))
+        assert tr.step_count == 1
+        blob1 = tr.blob()
+        assert not np.array_equal(blob1, blob)
+        batch = tp._batch(hp, B, batch_seed + 1)
+        out = tr.step(*batch, apply_update=False)
+        assert tr.step_count == 1 and np.array_equal(tr.blob(), blob1)
+        _check_last_step(tr, out, hp, blob1, batch, opts, 1, B, "%s step 1 %s" % (cid, rid), plan)
+    finally:
+        tr.close()
+
+
+_WGRAD = re.compile(r"wgrad (\S+): (\d+) x \d+, X (\d+) \(of \d+\) ch x G (\d+) ch, \d+ slabs in groups (\S+), (thin|f16x3|fp32 mfma), "
+                    r"(\d+) img/tile, \d+ tiles, (\d+) slices x")
+_HCONV = re.compile(r"\] (.+): \d+ x \d+ -> \d+ ch, \d+ phase\(s\), NT \d+ x \d+ blocks, \d+ k-steps, \d+ workgroups, K split (\d+)")
+_FCONV = re.compile(r"\] (.+): fp32 conv, (\d+) x \d+ -> \d+ ch, \d+ phase\(s\), NT \d+, (\d+) img/group, \d+ workgroups, K split (\d+)")
+
+
+def test_the_cases_reach_the_launch_forms(monkeypatch, capfd):
+    """The union of the cases x routes above (their trainers, created as the tests create them) reaches every launch form the planner
+    prints but two.  NOT REACHED by any shape of this file:
+      * wgrad_thin_kernel on strips of more than one row: needs B * H >= 2048 rows (wgrad_setup);
+        tests/test_gpu_train.py::test_baseline_config_256x256x2_batch8_against_the_oracle runs it;
+      * a convolution that "stays on the fp32 kernel" beside conv_f16x3: no shape the trainer accepts reaches it.  plan_f16 refuses a
+        halo of more than 1024 pixels, and setup_conv refuses the same halo for the whole trainer first ("halo too large"); below
+        that the planner's last attempt (one octet per chunk, one k-step per stage, a CU's whole LDS) always fits.  Asserted below, so
+        that a planner change which makes it reachable asks for a case here."""
+    reached = {}
+
+    def note(form, where):
+        reached.setdefault(form, where)
+
+    for cid, (hp, B, regime, blob_seed, _) in CASES.items():
+        blob = model.random_blob(hp, seed=blob_seed)
+        for rid, route in ROUTES:
+            with monkeypatch.context() as mp:
+                tr, plan = _trainer(mp, capfd, hp, blob, tp.trainer_options(regime), B, route)
+                tr.close()
+            where = "%s %s" % (cid, rid)
+            assert plan, where
+            for ln in plan:
+                m = _WGRAD.search(ln)
+                if m:
+                    layer, H, X, G, groups, form, imgs, slices = m.groups()
+                    note("wgrad " + form, where)
+                    if form != "thin" and int(X) <= 4:
+                        note("wgrad %s on <= 4 input channels" % form, where)
+                    if layer.startswith("ld0") and int(X) > 4:
+                        note("wgrad %s on a first layer of > 4 channels" % form, where)
+                    if layer.startswith("ld0") and form != "thin" and int(X) <= 4 and int(G) > 128:
+                        note("wgrad %s on a first layer of > 128 filters" % form, where)
+                    if "/" in groups:
+                        note("wgrad in more than one slab group", where)
+                    if int(slices) > 1:
+                        note("wgrad in more than one slice", where)
+                    if int(imgs) > 1:
+                        note("wgrad tile of more than one image", where)
+                    continue
+                m = _FCONV.search(ln)
+                if m:
+                    if "UMX_TRAIN_CONV_F32" in route:
+                        note("fp32 conv, K split %s" % ("1" if m.group(4) == "1" else "> 1"), where)
+                    if int(m.group(3)) > 1:
+                        note("conv image group of more than one image", where)
+                        if B % int(m.group(3)):
+                            note("conv image group left partial by the batch (%s images a group)" % m.group(3), where)
+                    continue
+                m = _HCONV.search(ln)
+                if m:
+                    note("conv_f16x3, K split %s" % ("1" if m.group(2) == "1" else "> 1"), where)
+                elif "stays on the fp32 kernel" in ln:
+                    note("a convolution that stays on the fp32 kernel", where)
+    print("\n".join("%-70s first at %s" % kv for kv in sorted(reached.items())))
+    need = ["wgrad thin", "wgrad f16x3", "wgrad fp32 mfma", "wgrad fp32 mfma on <= 4 input channels",
+            "wgrad f16x3 on a first layer of > 4 channels", "wgrad fp32 mfma on a first layer of > 4 channels",
+            "wgrad fp32 mfma on a first layer of > 128 filters",
+            "wgrad in more than one slab group", "wgrad in more than one slice", "wgrad tile of more than one image",
+            "conv_f16x3, K split 1", "conv_f16x3, K split > 1",
+            "fp32 conv, K split 1", "fp32 conv, K split > 1", "conv image group of more than one image",
+            "conv image group left partial by the batch (4 images a group)", "conv image group left partial by the batch (16 images a group)",
+            "conv image group left partial by the batch (64 images a group)"]
+    assert [f for f in need if f not in reached] == []
+    assert "a convolution that stays on the fp32 kernel" not in reached, "reachable now: drop it from the docstring and require it"

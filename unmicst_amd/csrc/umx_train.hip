@@ -530,6 +530,10 @@ int setup_conv(umx_trainer* tr, TConv& tc, const char* what, int H, int W, int C
     const size_t packs_before = tr->packs.size() - npacks;
     T_TRY(setup_hconv(tr, tc, what, H, W, Cout, act, nphase, o_mul, oy, ox, ngroups, gs, bwd));
     if (tc.hidx >= 0 && tc.direct) tr->packs.resize(packs_before);   // nothing reads this convolution's fp32 operands
+    if (tc.hidx < 0 && getenv("UMX_DEBUG_PLAN"))
+        fprintf(stderr, "[umx train] %s%s: fp32 conv, %d x %d -> %d ch, %d phase(s), NT %d, %d img/group, %ld workgroups, K split %d\n", what,
+                bwd ? " (backward)" : "", H, W, Cout, nphase, tc.nt, p.imgs,
+                (long)((tr->B + p.imgs - 1) / p.imgs) * p.tiles_y * p.tiles_x * nphase * (p.Np / 16 / tc.nt), p.ksplit);
     return UMX_OK;
 }
 
