@@ -49,7 +49,29 @@ struct H16 {                         // (hi, lo) binary16 NHWC planes of one ten
     int Cs = 0;
 };
 
+struct Act {                         // one fp32 NHWC tensor of the step and what travels with it
+    float* x = nullptr;              // [B, S, S, C]
+    H16 h;                           // its (hi, lo) planes; empty where none exist (the exact-fp32 route, cv[0]) or are withheld
+    unsigned* max = nullptr;         // its max-|x| word in d_maxw, or NULL
+    float* inv = nullptr;            // inverse scale its planes were stored with (a gradient: written with the planes), NULL for activations
+    int S = 0, C = 0;
+    size_t npix(int B) const { return (size_t)B * S * S; }
+    Act without_planes() const { Act a = *this; a.h = H16(); return a; }
+};
+
 constexpr int kSlots = 4;   // dz / gS buffers the main stream may run ahead of the weight gradients by
+
+struct GradSlot {                    // a gradient buffer the layers take turns in
+    float* x = nullptr;              // fp32, max_act floats
+    _Float16 *hi = nullptr, *lo = nullptr;   // plane storage for the widest gradient the slot holds (NULL on the exact-fp32 route)
+    float* inv = nullptr;            // where in d_xinv the writer of the planes leaves their inverse scale
+    // the slot as the [B, S, S, C] gradient whose max word is `max` (planes false: withheld from its readers, and not written)
+    Act view(int S, int C, unsigned* max, bool planes = true) const {
+        Act a{x, H16(), max, inv, S, C};
+        if (planes && hi) a.h = H16{hi, lo, round_up(C, 8)};
+        return a;
+    }
+};
 
 struct TapSet {
     std::vector<std::pair<int, int>> off;   // (dy, dx) input offsets
@@ -76,9 +98,7 @@ struct LBlock {                 // one block of the legacy graph: a chain of nEx
     std::vector<WgradParams> wg;   // wg[e >= 1]: weight gradient of wextra_{e-1}
     std::vector<size_t> o_wx;   // wextra offsets in the parameter vector
     std::vector<float*> y;      // y[e]: output of conv e, pre-ReLU (down: y[E] = z = main + shortcut)
-    std::vector<float*> a;      // a[e] = relu(y[e]) for the convolution after it: e < E (down), e <= E (up: a[E] is the output)
-    std::vector<H16> ha;        // their planes
-    std::vector<unsigned*> amax;   // max |a[e]| (split-precision weight gradients)
+    std::vector<Act> a;         // a[e] = relu(y[e]) for the convolution after it: e < E (down), e <= E (up: a[E] is the output)
     std::vector<unsigned*> gmax;   // max |d loss / d y[e]| of the current step
     float* ident = nullptr;     // [4][C] identity statistics: act_fwd as a plain ReLU with the plane writer
     TConv dg_sh;                // (down) input gradient of the shortcut
@@ -103,18 +123,18 @@ struct umx_trainer {
     // per-layer offsets into the parameter vector
     std::vector<size_t> o_w1, o_ws, o_wt, o_w2;
     size_t o_lb = 0, o_lt = 0;
-    // activations
-    std::vector<float*> ds;             // ds[0] = data, ds[i+1] = pooled output of down layer i
+    // activations, each with its planes and its max word (max |activation|, for the split-precision weight gradients)
+    std::vector<Act> ds;                // ds[0] = data, ds[i+1] = pooled output of down layer i
     std::vector<BnSite> bn_d, bn_u;     // down layers / up layers (index = idx)
     BnSite bn_b, bn_t;
-    float* act_b = nullptr;             // bottom output
-    std::vector<float*> us, cv;         // per up layer idx
+    Act act_b;                          // bottom output
+    std::vector<Act> us, cv;            // per up layer idx
     float *d_labels = nullptr, *d_weights = nullptr, *d_probs = nullptr, *d_dt = nullptr;
     std::vector<float*> dskip;          // gradient w.r.t. ds[idx] from the up path (idx >= 1)
-    float *DA = nullptr, *DB = nullptr, *DZ = nullptr, *GS = nullptr;
-    float* DZ2[kSlots] = {};   // gradient w.r.t. a conv output, one per slot: the weight gradients of layer l run on a side stream
-    float* GS2[kSlots] = {};   // while the main stream moves on to layers l+1 .. l+nslots-1
-    int nslots = kSlots;
+    float *DA = nullptr, *DB = nullptr;
+    GradSlot dz[kSlots];       // gradient w.r.t. a conv output, one per slot: the weight gradients of layer l run on a side stream
+    GradSlot gs[kSlots];       // while the main stream moves on to layers l+1 .. l+nslots-1 (legacy: a chain alternates between dz[0] and
+    int nslots = kSlots;       // dz[1]; gs[0] is the transposed conv's space-to-depth gradient)
     hipStream_t side = nullptr;
     hipStream_t side2 = nullptr;          // a second side stream: the dz / gS slots alternate between the two
     hipEvent_t ev_join2 = nullptr;
@@ -128,8 +148,6 @@ struct umx_trainer {
     double* d_loss = nullptr;           // [0] data term, [1] regularisation
     unsigned* d_maxw = nullptr;  int n_maxw = 0;   // per-tensor max |gradient| words, then the binary16 range flag
     std::vector<unsigned*> smax;        // max |gS| per up layer
-    std::vector<unsigned*> dsmax, usmax, cvmax;   // max |activation| of ds[i], us[idx], cv[idx]
-    unsigned* bmax = nullptr;           // ... of the bottom layer's output
     float* d_ws = nullptr;  size_t ws_floats = 0;
     float* d_ws2 = nullptr;             // ... of the second side stream
     float* d_split = nullptr;  size_t split_floats = 0;   // partial outputs of K-split convolutions
@@ -149,8 +167,6 @@ struct umx_trainer {
     int max_refs = 0;
     int n_fwd_packs = 0, n_fwd_rdescs = 0;   // descriptors [0, n_fwd) serve the forward pass, the rest the backward pass only
     hipEvent_t ev_begin = nullptr, ev_packed = nullptr;
-    std::vector<H16> h_ds, h_us, h_cv;  // planes of ds[i], us[idx], cv[idx]
-    H16 h_b, h_dz[kSlots], h_gs[kSlots];
     float* d_xinv = nullptr;            // [2 * kSlots] inverse scales of the dz / gS slots' planes, written by split_dyn_kernel
     // launches
     std::vector<TConv> c_fwd_d, c_dg_d, c_T, c_fwd_u, c_dg_us, c_dg_skip, c_dg_T;
@@ -179,7 +195,6 @@ struct umx_trainer {
     float* lt_z = nullptr;              // logits
     float* ident_k = nullptr;           // identity statistics of the logits: the loss / softmax kernels without BN
     float* d_ones = nullptr;            // all-ones weights: the unweighted loss (weights == NULL)
-    float* TX = nullptr;                // second gradient buffer of a chain (with DZ)
     float* DSUM = nullptr;              // [2][max_act]: first-conv and shortcut input gradients, summed in that order
     size_t max_act = 0;
 };
@@ -537,29 +552,60 @@ int setup_conv(umx_trainer* tr, TConv& tc, const char* what, int H, int W, int C
     return UMX_OK;
 }
 
-// (nothing on the exact-fp32 route: its planes stay empty)
-int alloc_h16_(umx_trainer* tr, H16& h, size_t npix, int C, const char* label) {
-    if (!tr->hconv) return UMX_OK;
-    h.Cs = round_up(std::max(C, 1), 8);
-    T_TRY(talloc_(tr, &h.hi, npix * h.Cs, true, (std::string(label) + ".hi").c_str()));
-    T_TRY(talloc_(tr, &h.lo, npix * h.Cs, true, (std::string(label) + ".lo").c_str()));
-    return UMX_OK;
-}
-#define alloc_h16(tr, h, npix, C) alloc_h16_(tr, h, npix, C, #h)
+std::string label_of(const std::string& array, int i) { return array + "[" + std::to_string(i) + "]"; }
 
-// fp32 NHWC tensor -> the (hi, lo) planes conv_f16x3 reads (maxw / inv: a gradient tensor's dynamic scale, else NULL)
-int to_h16(umx_trainer* tr, const float* x, size_t npix, int C, const H16& h, const unsigned* maxw, float* inv, hipStream_t st,
-           unsigned* omax = nullptr) {
+// The planes of a (nothing on the exact-fp32 route: they stay empty)
+int alloc_planes(umx_trainer* tr, Act& a, const std::string& label) {
     if (!tr->hconv) return UMX_OK;
-    T_HIP(tr, launch_split_dyn(x, npix, C, h.Cs, maxw, inv, h.hi, h.lo, reinterpret_cast<int*>(tr->d_maxw + tr->n_maxw), omax, st));
+    a.h.Cs = round_up(std::max(a.C, 1), 8);
+    T_TRY(talloc_(tr, &a.h.hi, a.npix(tr->B) * a.h.Cs, true, (label + ".hi").c_str()));
+    T_TRY(talloc_(tr, &a.h.lo, a.npix(tr->B) * a.h.Cs, true, (label + ".lo").c_str()));
     return UMX_OK;
 }
 
-int run_hconv(umx_trainer* tr, TConv& tc, const H16& s0, const H16* s1, float* dst, const float* xinv, hipStream_t st) {
+// One tensor of the step (label: its name in the guard mode's messages): the fp32 buffer [B, S, S, C] and, unless withheld, its planes
+int alloc_act(umx_trainer* tr, Act& a, const std::string& label, int S, int C, bool planes = true) {
+    a.S = S; a.C = C;
+    T_TRY(talloc_(tr, &a.x, a.npix(tr->B) * C, false, label.c_str()));
+    return planes ? alloc_planes(tr, a, label) : UMX_OK;
+}
+
+// The gradient slots of a graph, in the order `slots` lists them (k < kSlots: dz[k], else gs[k - kSlots]; slot k's inverse scale is
+// d_xinv[k]): their fp32 buffers of max_act floats ...
+GradSlot& slot_of(umx_trainer* tr, int k) { return k < kSlots ? tr->dz[k] : tr->gs[k - kSlots]; }
+std::string slot_label(int k) { return k < kSlots ? label_of("dz", k) : label_of("gs", k - kSlots); }
+int alloc_slots(umx_trainer* tr, const std::vector<int>& slots, size_t max_act) {
+    for (int k : slots) T_TRY(talloc_(tr, &slot_of(tr, k).x, max_act, false, slot_label(k).c_str()));
+    return UMX_OK;
+}
+// ... and their planes, max_dz / max_gs halves each (the widest tensor a slot holds), with the inverse scales
+int alloc_slot_planes(umx_trainer* tr, const std::vector<int>& slots, size_t max_dz, size_t max_gs) {
+    if (!tr->hconv) return UMX_OK;
+    for (int k : slots) {
+        GradSlot& s = slot_of(tr, k);
+        T_TRY(talloc_(tr, &s.hi, k < kSlots ? max_dz : max_gs, true, (slot_label(k) + ".hi").c_str()));
+        T_TRY(talloc_(tr, &s.lo, k < kSlots ? max_dz : max_gs, true, (slot_label(k) + ".lo").c_str()));
+    }
+    T_TRY(tzero(tr, &tr->d_xinv, 2 * kSlots));
+    for (int k : slots) slot_of(tr, k).inv = tr->d_xinv + k;
+    return UMX_OK;
+}
+
+// a's fp32 tensor -> the (hi, lo) planes conv_f16x3 reads.  A gradient (a.inv) is scaled by its max word, which its writer has left in
+// place; an activation is stored as it is and (omax) gets its max word written in the same pass
+int to_h16(umx_trainer* tr, const Act& a, hipStream_t st, bool omax = false) {
+    if (!tr->hconv) return UMX_OK;
+    T_HIP(tr, launch_split_dyn(a.x, a.npix(tr->B), a.C, a.h.Cs, a.inv ? a.max : nullptr, a.inv, a.h.hi, a.h.lo,
+                               reinterpret_cast<int*>(tr->d_maxw + tr->n_maxw), omax ? a.max : nullptr, st));
+    return UMX_OK;
+}
+
+// (s0.inv: the inverse scale of its planes where they hold a gradient)
+int run_hconv(umx_trainer* tr, TConv& tc, const Act& s0, const Act* s1, float* dst, hipStream_t st) {
     HConvParams p = tr->hls[tc.hidx];
     p.B = tr->B;
     p.overflow_flag = reinterpret_cast<int*>(tr->d_maxw + tr->n_maxw);
-    const H16* src[2] = {&s0, s1 ? s1 : &s0};
+    const H16* src[2] = {&s0.h, s1 ? &s1->h : &s0.h};
     for (int gi = 0; gi < 2; ++gi) {
         p.src_hi[gi] = gi == 0 || s1 ? src[gi]->hi : nullptr;
         p.src_lo[gi] = gi == 0 || s1 ? src[gi]->lo : nullptr;
@@ -569,7 +615,7 @@ int run_hconv(umx_trainer* tr, TConv& tc, const H16& s0, const H16* s1, float* d
     }
     p.dst_f32 = dst;
     p.dyn[0] = tc.winv;
-    p.dyn[1] = xinv;
+    p.dyn[1] = s0.inv;
     if (p.ksplit > 1) {   // raw partial sums, then the ordered reduce applies the activation
         const int act = p.act;
         p.act = ACT_NONE;
@@ -601,20 +647,18 @@ int run_conv(umx_trainer* tr, TConv& tc, const float* src0, const float* src1, f
     return UMX_OK;
 }
 
-// a convolution on the main stream, on whichever route its plan took: conv_f16x3 reads the (hi, lo) planes h (+ h1; xinv: their
-// inverse scale where they hold a gradient), conv_mfma_f32 the fp32 tensors x (+ x1)
-int run_tconv(umx_trainer* tr, TConv& tc, const float* x, const H16& h, const float* xinv, float* dst, const float* x1 = nullptr,
-              const H16* h1 = nullptr) {
-    if (tc.hidx >= 0) return run_hconv(tr, tc, h, h1, dst, xinv, tr->stream);
-    return run_conv(tr, tc, x, x1, dst);
+// a convolution on the main stream, on whichever route its plan took: conv_f16x3 reads the (hi, lo) planes of src (+ src1),
+// conv_mfma_f32 their fp32 tensors
+int run_tconv(umx_trainer* tr, TConv& tc, const Act& src, float* dst, const Act* src1 = nullptr) {
+    if (tc.hidx >= 0) return run_hconv(tr, tc, src, src1, dst, tr->stream);
+    return run_conv(tr, tc, src.x, src1 ? src1->x : nullptr, dst);
 }
 
 // an activation written by a kernel without a plane writer (the input batch, the transposed convolutions' outputs): its max |x|
 // for the split-precision weight gradient (training) and, on the split-precision route, its planes -- there in the same pass
-int track_act(umx_trainer* tr, const float* x, size_t npix, int C, const H16& h, unsigned* xmax, bool training) {
-    if (training && !tr->hconv) T_HIP(tr, launch_absmax(x, npix * C, xmax, tr->stream));
-    if (tr->hconv) T_TRY(to_h16(tr, x, npix, C, h, nullptr, nullptr, tr->stream, training ? xmax : nullptr));
-    return UMX_OK;
+int track_act(umx_trainer* tr, const Act& a, bool training) {
+    if (training && !tr->hconv) T_HIP(tr, launch_absmax(a.x, a.npix(tr->B) * a.C, a.max, tr->stream));
+    return to_h16(tr, a, tr->stream, training);
 }
 
 TapSet same_taps(int ks, bool flipped) {   // stride-1 SAME conv (or its input gradient: offsets negated)
@@ -699,39 +743,36 @@ ActParams act_params(const umx_trainer* tr, const BnSite& s, int pool, int act, 
     return a;
 }
 
-// dy (+dy1) -> gradient w.r.t. z in tr->DZ ; BN parameter gradients into the gradient vector
-// (planes / inv: where an input-gradient convolution on conv_f16x3 reads dz, its (hi, lo) planes are written in the same pass)
-int bn_backward(umx_trainer* tr, BnSite& s, const ActParams& a, const float* dy0, const float* dy1, float* dz,
-                const H16* planes = nullptr, float* inv = nullptr) {
+// dy (+dy1) -> gradient w.r.t. z in dz (its max word: s.gmax); BN parameter gradients into the gradient vector
+// (where dz has planes -- an input-gradient convolution on conv_f16x3 reads it -- they and their inverse scale are written in the same pass)
+int bn_backward(umx_trainer* tr, BnSite& s, const ActParams& a, const float* dy0, const float* dy1, const Act& dz) {
     const size_t N = (size_t)tr->B * s.H * s.W;
     const size_t rows = a.pool ? N / 4 : N;
     const int nblk = chan_blocks(rows, s.C);
-    T_HIP(tr, launch_act_bwd(a, dy0, dy1, dz, tr->d_part, nblk, planes ? s.bw + 1 : nullptr, tr->stream));
+    const bool planes = dz.h.hi != nullptr;
+    T_HIP(tr, launch_act_bwd(a, dy0, dy1, dz.x, tr->d_part, nblk, planes ? s.bw + 1 : nullptr, tr->stream));
     T_HIP(tr, launch_bn_bwd_finalize(tr->d_part, nblk, N, s.C, tr->d_g + s.gamma, tr->d_g + s.beta, s.m12, tr->stream));
-    T_HIP(tr, launch_bn_bwd_apply_max(dz, s.z, s.stat, s.m12, N, s.C, s.gmax, s.bw, inv, planes ? planes->hi : nullptr,
-                                      planes ? planes->lo : nullptr, planes ? planes->Cs : 0,
+    T_HIP(tr, launch_bn_bwd_apply_max(dz.x, s.z, s.stat, s.m12, N, s.C, s.gmax, s.bw, dz.inv, dz.h.hi, dz.h.lo, dz.h.Cs,
                                       reinterpret_cast<int*>(tr->d_maxw + tr->n_maxw), tr->stream));
     return UMX_OK;
 }
 
-// (xp / gp: the operands' (hi, lo) planes and xi / gi the inverse scales they were stored with, where they exist: the split-precision
-// kernel then stages from them -- half the bytes, no conversion)
-int run_wgrad(umx_trainer* tr, WgradParams& w, const float* X, const float* G, int Ctot, int c_off, size_t w_off,
-              float reg, size_t pair_off /* SIZE_MAX: none */, const unsigned* xmax, const unsigned* gmax,
-              hipStream_t stream, const H16* xp = nullptr, const float* xi = nullptr, const H16* gp = nullptr,
-              const float* gi = nullptr) {
-    w.X = X;
-    w.G = G;
+// (where both operands have (hi, lo) planes the split-precision kernel stages from them -- half the bytes, no conversion -- and undoes
+// the inverse scales they were stored with)
+int run_wgrad(umx_trainer* tr, WgradParams& w, const Act& X, const Act& G, int Ctot, int c_off, size_t w_off, float reg,
+              size_t pair_off /* SIZE_MAX: none */, hipStream_t stream) {
+    w.X = X.x;
+    w.G = G.x;
     w.planes = 0;
-    if (w.f16 && tr->wg_planes && xp && gp && xp->hi && gp->hi && w.Cxt <= xp->Cs && w.Cg <= gp->Cs) {
+    if (w.f16 && tr->wg_planes && X.h.hi && G.h.hi && w.Cxt <= X.h.Cs && w.Cg <= G.h.Cs) {
         w.planes = 1;
-        w.Xhi = xp->hi; w.Xlo = xp->lo; w.XCs = xp->Cs;
-        w.Ghi = gp->hi; w.Glo = gp->lo; w.GCs = gp->Cs;
-        w.xinv = xi; w.ginv = gi;
+        w.Xhi = X.h.hi; w.Xlo = X.h.lo; w.XCs = X.h.Cs;
+        w.Ghi = G.h.hi; w.Glo = G.h.lo; w.GCs = G.h.Cs;
+        w.xinv = X.inv; w.ginv = G.inv;
     }
     w.ws = stream == tr->side2 ? tr->d_ws2 : tr->d_ws;   // (each side stream has its own slice workspace)
-    w.xmax = xmax;
-    w.gmax = gmax;
+    w.xmax = X.max;
+    w.gmax = G.max;
     w.overflow = reinterpret_cast<int*>(tr->d_maxw + tr->n_maxw);
     T_HIP(tr, launch_wgrad(w, stream));
     T_HIP(tr, launch_wgrad_reduce(w, Ctot, c_off, tr->d_g + w_off, tr->d_w + w_off, reg > 0.f ? tr->o.reg_kind : 0, reg,
@@ -753,42 +794,37 @@ int forward_pass(umx_trainer* tr, const float* data, bool training, bool update)
     int* const flagp = reinterpret_cast<int*>(tr->d_maxw + tr->n_maxw);
     // (training: every activation that the backward pass feeds to the split-precision weight gradient gets its max |v|
     // tracked by the kernel that writes it -- the input batch and the transposed-conv outputs by a pass of their own)
-    // BN + LeakyReLU (+ 2x2 max-pool) + dropout of site s into out, which gets its (hi, lo) planes h written by the same kernel
-    // (the exact-fp32 route has no plane buffers: h is empty then)
-    auto act = [&](BnSite& s, int pool, float rate, int layer_id, float* out, unsigned* omax, const H16& h) -> int {
-        T_HIP(tr, launch_act_fwd(act_params(tr, s, pool, ACT_LEAKY, training ? rate : 0.f, layer_id), out, training ? omax : nullptr,
-                                 h.hi, h.lo, h.Cs, flagp, st));
+    // BN + LeakyReLU (+ 2x2 max-pool) + dropout of site s into out, which gets its (hi, lo) planes written by the same kernel
+    // (the exact-fp32 route has no plane buffers: out.h is empty then)
+    auto act = [&](BnSite& s, int pool, float rate, int layer_id, const Act& out) -> int {
+        T_HIP(tr, launch_act_fwd(act_params(tr, s, pool, ACT_LEAKY, training ? rate : 0.f, layer_id), out.x, training ? out.max : nullptr,
+                                 out.h.hi, out.h.lo, out.h.Cs, flagp, st));
         return UMX_OK;
     };
-    tr->ds[0] = const_cast<float*>(data);
-    T_TRY(track_act(tr, data, (size_t)tr->B * tr->P * tr->P, tr->n[0], tr->h_ds[0], tr->dsmax[0], training));
-    int S = tr->P;
+    tr->ds[0].x = const_cast<float*>(data);
+    T_TRY(track_act(tr, tr->ds[0], training));
     for (int i = 0; i < L; ++i) {
         BnSite& s = tr->bn_d[i];
-        T_TRY(run_tconv(tr, tr->c_fwd_d[i], tr->ds[i], tr->h_ds[i], nullptr, s.z));
+        T_TRY(run_tconv(tr, tr->c_fwd_d[i], tr->ds[i], s.z));
         T_TRY(bn_forward_stats(tr, s, update, training));
-        T_TRY(act(s, 1, down_rate(tr, i), LAYER_DOWN + i, tr->ds[i + 1], tr->dsmax[i + 1], tr->h_ds[i + 1]));
-        S /= 2;
+        T_TRY(act(s, 1, down_rate(tr, i), LAYER_DOWN + i, tr->ds[i + 1]));
     }
-    T_TRY(run_tconv(tr, tr->c_fwd_b, tr->ds[L], tr->h_ds[L], nullptr, tr->bn_b.z));
+    T_TRY(run_tconv(tr, tr->c_fwd_b, tr->ds[L], tr->bn_b.z));
     T_TRY(bn_forward_stats(tr, tr->bn_b, update, training));
-    T_TRY(act(tr->bn_b, 0, o.drop_bottom, LAYER_BOTTOM, tr->act_b, tr->bmax, tr->h_b));
-    const float* cur = tr->act_b;
-    const H16* hcur = &tr->h_b;
+    T_TRY(act(tr->bn_b, 0, o.drop_bottom, LAYER_BOTTOM, tr->act_b));
+    const Act* cur = &tr->act_b;
     for (int idx = L - 1; idx >= 0; --idx) {
         BnSite& s = tr->bn_u[idx];
-        S *= 2;
-        T_TRY(run_tconv(tr, tr->c_T[idx], cur, *hcur, nullptr, tr->us[idx]));
-        T_TRY(track_act(tr, tr->us[idx], (size_t)tr->B * S * S, tr->n[idx + 1], tr->h_us[idx], tr->usmax[idx], training));
-        T_TRY(run_tconv(tr, tr->c_fwd_u[idx], tr->ds[idx], tr->h_ds[idx], nullptr, s.z, tr->us[idx], &tr->h_us[idx]));
+        T_TRY(run_tconv(tr, tr->c_T[idx], *cur, tr->us[idx].x));
+        T_TRY(track_act(tr, tr->us[idx], training));
+        T_TRY(run_tconv(tr, tr->c_fwd_u[idx], tr->ds[idx], s.z, &tr->us[idx]));
         T_TRY(bn_forward_stats(tr, s, update, training));
         // (cv[0] has no planes: only the 1x1 head reads it)
-        T_TRY(act(s, 0, up_rate(tr, idx), LAYER_UP + idx, tr->cv[idx], tr->cvmax[idx], tr->h_cv[idx]));
-        cur = tr->cv[idx];
-        hcur = &tr->h_cv[idx];
+        T_TRY(act(s, 0, up_rate(tr, idx), LAYER_UP + idx, tr->cv[idx]));
+        cur = &tr->cv[idx];
     }
     BnSite& t = tr->bn_t;
-    T_HIP(tr, launch_head_fwd(tr->cv[0], (size_t)tr->B * tr->P * tr->P, tr->n[1], tr->K, tr->d_w + tr->o_lt, t.z, st));
+    T_HIP(tr, launch_head_fwd(tr->cv[0].x, (size_t)tr->B * tr->P * tr->P, tr->n[1], tr->K, tr->d_w + tr->o_lt, t.z, st));
     T_TRY(bn_forward_stats(tr, t, update, training));
     return UMX_OK;
 }
@@ -870,9 +906,9 @@ int enqueue_step(umx_trainer* tr, const float* data, const float* labels, const 
     // ------------------------------------------------------------------ backward
     {   // top layer: softmax/CE gradient -> BN -> 1x1 conv
         ActParams a = act_params(tr, t, 0, ACT_NONE, 0.f, 0);
-        T_TRY(bn_backward(tr, t, a, tr->d_dt, nullptr, tr->d_dt));   // in place: dt -> dt0
+        T_TRY(bn_backward(tr, t, a, tr->d_dt, nullptr, Act{tr->d_dt}));   // in place: dt -> dt0
         const int nblk = chan_blocks(Npix, tr->n[1]);
-        T_HIP(tr, launch_head_bwd(tr->cv[0], tr->d_dt, tr->d_w + tr->o_lt, Npix, tr->n[1], K, tr->DA, tr->d_part, nblk, st));
+        T_HIP(tr, launch_head_bwd(tr->cv[0].x, tr->d_dt, tr->d_w + tr->o_lt, Npix, tr->n[1], K, tr->DA, tr->d_part, nblk, st));
         T_HIP(tr, launch_reduce_partials(tr->d_part, nblk, tr->n[1] * K, 1.0, tr->d_g + tr->o_lt, tr->d_w + tr->o_lt,
                                          o.reg_top > 0.f ? o.reg_kind : 0, o.reg_top, st));
     }
@@ -886,15 +922,17 @@ int enqueue_step(umx_trainer* tr, const float* data, const float* labels, const 
     int slot = 0;
     bool used[kSlots] = {}, aux_used[kSlots] = {};
     const bool use_aux = tr->overlap && tr->aux && tr->hconv;
-    auto dz_begin = [&](int sl) -> int {      // main: the slot's previous consumers on the side stream are done
-        if (tr->overlap && used[sl]) T_HIP(tr, hipStreamWaitEvent(st, tr->ev_side[sl], 0));
-        if (aux_used[sl]) { T_HIP(tr, hipStreamWaitEvent(st, tr->ev_aux[sl], 0)); aux_used[sl] = false; }
-        return UMX_OK;
-    };
-    auto dz_ready = [&](int sl) -> int {      // main has written DZ2[sl]; the side stream may read it
-        if (tr->overlap) {
-            T_HIP(tr, hipEventRecord(tr->ev_dz[sl], st));
-            T_HIP(tr, hipStreamWaitEvent(wss[sl & 1], tr->ev_dz[sl], 0));
+    // the gradient w.r.t. site s's conv output from dy0 (+ dy1), into the current slot (planes: with its (hi, lo) planes): *dz is the
+    // slot's view of it
+    auto dz_slot = [&](BnSite& s, const ActParams& a, const float* dy0, const float* dy1, bool planes, Act* dz) -> int {
+        // main: the slot's previous consumers on the side and aux streams are done
+        if (tr->overlap && used[slot]) T_HIP(tr, hipStreamWaitEvent(st, tr->ev_side[slot], 0));
+        if (aux_used[slot]) { T_HIP(tr, hipStreamWaitEvent(st, tr->ev_aux[slot], 0)); aux_used[slot] = false; }
+        *dz = tr->dz[slot].view(s.H, s.C, s.gmax, planes);
+        T_TRY(bn_backward(tr, s, a, dy0, dy1, *dz));
+        if (tr->overlap) {   // main has written the slot; the side stream may read it
+            T_HIP(tr, hipEventRecord(tr->ev_dz[slot], st));
+            T_HIP(tr, hipStreamWaitEvent(ws, tr->ev_dz[slot], 0));
         }
         return UMX_OK;
     };
@@ -903,84 +941,59 @@ int enqueue_step(umx_trainer* tr, const float* data, const float* labels, const 
         used[sl] = true;
         return UMX_OK;
     };
-    int S = P;
     for (int idx = 0; idx < L; ++idx) {    // up layers, output side first
         BnSite& s = tr->bn_u[idx];
-        const int Cskip = tr->n[idx], Cup = tr->n[idx + 1];
-        const float* layer_in = idx == L - 1 ? tr->act_b : tr->cv[idx + 1];
-        float* dz = tr->DZ2[slot];
-        float* gs = tr->GS2[slot];
-        ActParams a = act_params(tr, s, 0, ACT_LEAKY, up_rate(tr, idx), LAYER_UP + idx);
-        T_TRY(dz_begin(slot));
-        tr->h_dz[slot].Cs = round_up(Cup, 8);
-        T_TRY(bn_backward(tr, s, a, tr->DA, nullptr, dz, tr->hconv ? &tr->h_dz[slot] : nullptr, tr->d_xinv + slot));
-        T_TRY(dz_ready(slot));
-        const H16* const pdz = tr->hconv ? &tr->h_dz[slot] : nullptr;
-        T_TRY(run_wgrad(tr, tr->wg_u0[idx], tr->ds[idx], dz, Cskip + Cup, 0, tr->o_w2[idx], o.reg_up, SIZE_MAX, tr->dsmax[idx], s.gmax, ws,
-                        tr->hconv ? &tr->h_ds[idx] : nullptr, nullptr, pdz, tr->d_xinv + slot));
-        T_TRY(run_wgrad(tr, tr->wg_u1[idx], tr->us[idx], dz, Cskip + Cup, Cskip, tr->o_w2[idx], o.reg_up, SIZE_MAX, tr->usmax[idx], s.gmax, ws,
-                        tr->hconv ? &tr->h_us[idx] : nullptr, nullptr, pdz, tr->d_xinv + slot));
-        T_TRY(run_tconv(tr, tr->c_dg_us[idx], dz, tr->h_dz[slot], tr->d_xinv + slot, tr->DB));
+        const int Cskip = tr->n[idx], Cup = tr->n[idx + 1], Sh = tr->us[idx].S / 2;
+        const Act& layer_in = idx == L - 1 ? tr->act_b : tr->cv[idx + 1];
+        Act dz;
+        T_TRY(dz_slot(s, act_params(tr, s, 0, ACT_LEAKY, up_rate(tr, idx), LAYER_UP + idx), tr->DA, nullptr, true, &dz));
+        T_TRY(run_wgrad(tr, tr->wg_u0[idx], tr->ds[idx], dz, Cskip + Cup, 0, tr->o_w2[idx], o.reg_up, SIZE_MAX, ws));
+        T_TRY(run_wgrad(tr, tr->wg_u1[idx], tr->us[idx], dz, Cskip + Cup, Cskip, tr->o_w2[idx], o.reg_up, SIZE_MAX, ws));
+        T_TRY(run_tconv(tr, tr->c_dg_us[idx], dz, tr->DB));
         if (idx >= 1 && use_aux && tr->c_dg_skip[idx].hidx >= 0) {   // (on the weight gradients' stream it was 2 % slower; this stream is its own)
             T_HIP(tr, hipStreamWaitEvent(tr->aux, tr->ev_dz[slot], 0));
-            T_TRY(run_hconv(tr, tr->c_dg_skip[idx], tr->h_dz[slot], nullptr, tr->dskip[idx], tr->d_xinv + slot, tr->aux));
+            T_TRY(run_hconv(tr, tr->c_dg_skip[idx], dz, nullptr, tr->dskip[idx], tr->aux));
             T_HIP(tr, hipEventRecord(tr->ev_aux[slot], tr->aux));
             T_HIP(tr, hipEventRecord(tr->ev_skip[idx], tr->aux));
             aux_used[slot] = true;
         } else if (idx >= 1) {
-            T_TRY(run_tconv(tr, tr->c_dg_skip[idx], dz, tr->h_dz[slot], tr->d_xinv + slot, tr->dskip[idx]));
+            T_TRY(run_tconv(tr, tr->c_dg_skip[idx], dz, tr->dskip[idx]));
         }
-        T_HIP(tr, launch_leaky_bwd_s2d_max(tr->DB, tr->us[idx], B, S / 2, Cup, 0.2f, gs, tr->smax[idx], st));
+        const Act gs = tr->gs[slot].view(Sh, 4 * Cup, tr->smax[idx]);
+        T_HIP(tr, launch_leaky_bwd_s2d_max(tr->DB, tr->us[idx].x, B, Sh, Cup, 0.2f, gs.x, gs.max, st));
         const bool gs_planes = tr->hconv && (tr->c_dg_T[idx].hidx >= 0 || tr->wg_planes);
-        if (gs_planes) {   // (in front of the event: the transposed convolution's weight gradient stages from these planes too)
-            tr->h_gs[slot].Cs = round_up(4 * Cup, 8);
-            T_TRY(to_h16(tr, gs, (size_t)B * (S / 2) * (S / 2), 4 * Cup, tr->h_gs[slot], tr->smax[idx], tr->d_xinv + kSlots + slot, st));
-        }
+        // (in front of the event: the transposed convolution's weight gradient stages from these planes too)
+        if (gs_planes) T_TRY(to_h16(tr, gs, st));
         if (tr->overlap) {
             T_HIP(tr, hipEventRecord(tr->ev_gs[slot], st));
             T_HIP(tr, hipStreamWaitEvent(ws, tr->ev_gs[slot], 0));
         }
-        {
-            const H16* const pin = !tr->hconv ? nullptr : idx == L - 1 ? &tr->h_b : &tr->h_cv[idx + 1];
-            T_TRY(run_wgrad(tr, tr->wg_T[idx], gs, layer_in, Cup, 0, tr->o_wt[idx], o.reg_up, SIZE_MAX, tr->smax[idx],
-                            idx == L - 1 ? tr->bmax : tr->cvmax[idx + 1], ws, gs_planes ? &tr->h_gs[slot] : nullptr, tr->d_xinv + kSlots + slot, pin,
-                            nullptr));
-        }
+        // (the transposed convolution's filter: X is gS, G the layer's input)
+        T_TRY(run_wgrad(tr, tr->wg_T[idx], gs_planes ? gs : gs.without_planes(), layer_in, Cup, 0, tr->o_wt[idx], o.reg_up, SIZE_MAX, ws));
         T_TRY(side_done(slot));
-        T_TRY(run_tconv(tr, tr->c_dg_T[idx], gs, tr->h_gs[slot], tr->d_xinv + kSlots + slot, tr->DA));
+        T_TRY(run_tconv(tr, tr->c_dg_T[idx], gs, tr->DA));
         slot = (slot + 1) % tr->nslots;
-        S /= 2;
     }
     {   // bottom layer
-        float* dz = tr->DZ2[slot];
-        ActParams a = act_params(tr, tr->bn_b, 0, ACT_LEAKY, o.drop_bottom, LAYER_BOTTOM);
-        T_TRY(dz_begin(slot));
-        tr->h_dz[slot].Cs = round_up(tr->n[L + 1], 8);
-        T_TRY(bn_backward(tr, tr->bn_b, a, tr->DA, nullptr, dz, tr->hconv ? &tr->h_dz[slot] : nullptr, tr->d_xinv + slot));
-        T_TRY(dz_ready(slot));
-        T_TRY(run_wgrad(tr, tr->wg_b, tr->ds[L], dz, tr->n[L], 0, tr->o_lb, o.reg_bottom, SIZE_MAX, tr->dsmax[L], tr->bn_b.gmax, ws,
-                        tr->hconv ? &tr->h_ds[L] : nullptr, nullptr, tr->hconv ? &tr->h_dz[slot] : nullptr, tr->d_xinv + slot));
+        Act dz;
+        T_TRY(dz_slot(tr->bn_b, act_params(tr, tr->bn_b, 0, ACT_LEAKY, o.drop_bottom, LAYER_BOTTOM), tr->DA, nullptr, true, &dz));
+        T_TRY(run_wgrad(tr, tr->wg_b, tr->ds[L], dz, tr->n[L], 0, tr->o_lb, o.reg_bottom, SIZE_MAX, ws));
         T_TRY(side_done(slot));
-        T_TRY(run_tconv(tr, tr->c_dg_b, dz, tr->h_dz[slot], tr->d_xinv + slot, tr->DB));
+        T_TRY(run_tconv(tr, tr->c_dg_b, dz, tr->DB));
         slot = (slot + 1) % tr->nslots;
     }
     for (int i = L - 1; i >= 0; --i) {     // down layers
         BnSite& s = tr->bn_d[i];
-        float* dz = tr->DZ2[slot];
-        ActParams a = act_params(tr, s, 1, ACT_LEAKY, down_rate(tr, i), LAYER_DOWN + i);
         const float* dy1 = (i + 1 <= L - 1) ? tr->dskip[i + 1] : nullptr;
         if (dy1 && use_aux && tr->c_dg_skip[i + 1].hidx >= 0) T_HIP(tr, hipStreamWaitEvent(st, tr->ev_skip[i + 1], 0));
-        T_TRY(dz_begin(slot));
-        tr->h_dz[slot].Cs = round_up(tr->n[i + 1], 8);
-        T_TRY(bn_backward(tr, s, a, tr->DB, dy1, dz, tr->hconv && i >= 1 ? &tr->h_dz[slot] : nullptr, tr->d_xinv + slot));
-        T_TRY(dz_ready(slot));
+        // (layer 0: no convolution reads dz's planes, so none are written, and the weight gradient stages from the fp32 tensors)
+        Act dz;
+        T_TRY(dz_slot(s, act_params(tr, s, 1, ACT_LEAKY, down_rate(tr, i), LAYER_DOWN + i), tr->DB, dy1, i >= 1, &dz));
         // c00 + shortcut = conv(x, W1 + Wshort): both filters receive the same data gradient (UnMicst1-5.py:102-114)
-        T_TRY(run_wgrad(tr, tr->wg_d[i], tr->ds[i], dz, tr->n[i], 0, tr->o_ws[i], o.reg_down, tr->o_w1[i], tr->dsmax[i], s.gmax, ws,
-                        tr->hconv && i >= 1 ? &tr->h_ds[i] : nullptr, nullptr, tr->hconv && i >= 1 ? &tr->h_dz[slot] : nullptr,
-                        tr->d_xinv + slot));
+        T_TRY(run_wgrad(tr, tr->wg_d[i], i >= 1 ? tr->ds[i] : tr->ds[i].without_planes(), dz, tr->n[i], 0, tr->o_ws[i], o.reg_down,
+                        tr->o_w1[i], ws));
         T_TRY(side_done(slot));
-        S *= 2;
-        if (i >= 1) T_TRY(run_tconv(tr, tr->c_dg_d[i], dz, tr->h_dz[slot], tr->d_xinv + slot, tr->DB));
+        if (i >= 1) T_TRY(run_tconv(tr, tr->c_dg_d[i], dz, tr->DB));
         slot = (slot + 1) % tr->nslots;
     }
 #undef ws
@@ -1140,7 +1153,7 @@ int select_route(umx_trainer* tr, const float* blob) {
     if (const char* e = getenv("UMX_TRAIN_WSCALE_EVERY")) tr->wscale_every = atoi(e);
     tr->wg_planes = tr->hconv;
     tr->h_blob = blob;
-    tr->h_ds.resize(tr->L + 1); tr->h_us.resize(tr->L);   // (no buffers on the exact-fp32 route)
+    tr->ds.resize(tr->L + 1); tr->us.resize(tr->L);
     return UMX_OK;
 }
 
@@ -1217,44 +1230,42 @@ int build_trainer(umx_trainer* tr, const float* blob, size_t blob_floats) {
     bn_t_off = seg("lt.bn", 4 * (size_t)K, 0.f, 0);
     T_TRY(alloc_params(tr, blob, blob_floats, pos));
 
-    // ---- activations
-    tr->ds.assign(L + 1, nullptr);
+    // ---- activations: shapes and fp32 buffers; their planes follow below
+    T_TRY(select_route(tr, blob));
     tr->bn_d.resize(L); tr->bn_u.resize(L);
-    tr->us.assign(L, nullptr); tr->cv.assign(L, nullptr); tr->dskip.assign(L, nullptr);
-    size_t max_act = (size_t)B * P * P * std::max(n[0], K);
+    tr->cv.resize(L); tr->dskip.assign(L, nullptr);
+    size_t max_act = (size_t)B * P * P * std::max(n[0], K), max_dz = 0, max_gs = 0;
+    auto grad_size = [&](size_t npix, int C) { max_act = std::max(max_act, npix * C); max_dz = std::max(max_dz, npix * round_up(C, 8)); };
     int S = P;
     for (int i = 0; i < L; ++i) {
         T_TRY(bn_alloc(tr, tr->bn_d[i], n[i + 1], S, bn_d_off[i]));
-        max_act = std::max(max_act, (size_t)B * S * S * n[i + 1]);
-        T_TRY(talloc(tr, &tr->ds[i + 1], (size_t)B * (S / 2) * (S / 2) * n[i + 1]));
+        grad_size((size_t)B * S * S, n[i + 1]);
+        T_TRY(alloc_act(tr, tr->ds[i + 1], label_of("ds", i + 1), S / 2, n[i + 1], false));
         if (i + 1 <= L - 1) T_TRY(talloc(tr, &tr->dskip[i + 1], (size_t)B * (S / 2) * (S / 2) * n[i + 1]));
         S /= 2;
     }
     T_TRY(bn_alloc(tr, tr->bn_b, n[L + 1], S, bn_b_off));
-    T_TRY(talloc(tr, &tr->act_b, (size_t)B * S * S * n[L + 1]));
-    max_act = std::max(max_act, (size_t)B * S * S * n[L + 1]);
+    T_TRY(alloc_act(tr, tr->act_b, "act_b", S, n[L + 1], false));
+    grad_size((size_t)B * S * S, n[L + 1]);
     for (int idx = L - 1; idx >= 0; --idx) {
+        max_gs = std::max(max_gs, (size_t)B * S * S * round_up(4 * n[idx + 1], 8));
         S *= 2;
-        T_TRY(talloc(tr, &tr->us[idx], (size_t)B * S * S * n[idx + 1]));
+        T_TRY(alloc_act(tr, tr->us[idx], label_of("us", idx), S, n[idx + 1], false));
         T_TRY(bn_alloc(tr, tr->bn_u[idx], n[idx + 1], S, bn_u_off[idx]));
-        T_TRY(talloc(tr, &tr->cv[idx], (size_t)B * S * S * n[idx + 1]));
-        max_act = std::max(max_act, (size_t)B * S * S * n[idx + 1]);
+        T_TRY(alloc_act(tr, tr->cv[idx], label_of("cv", idx), S, n[idx + 1], false));
+        grad_size((size_t)B * S * S, n[idx + 1]);
     }
     T_TRY(bn_alloc(tr, tr->bn_t, K, P, bn_t_off));
     T_TRY(talloc(tr, &tr->d_labels, (size_t)B * P * P * K));
     T_TRY(talloc(tr, &tr->d_weights, (size_t)B * P * P * K));
     T_TRY(talloc(tr, &tr->d_probs, (size_t)B * P * P * K));
     T_TRY(talloc(tr, &tr->d_dt, (size_t)B * P * P * K));
-    T_TRY(talloc(tr, &tr->ds[0], (size_t)B * P * P * n[0]));
+    T_TRY(alloc_act(tr, tr->ds[0], label_of("ds", 0), P, n[0], false));
     T_TRY(talloc(tr, &tr->DA, max_act));
     T_TRY(talloc(tr, &tr->DB, max_act));
-    T_TRY(talloc(tr, &tr->DZ, max_act));
-    T_TRY(talloc(tr, &tr->GS, max_act));
-    tr->DZ2[0] = tr->DZ; tr->GS2[0] = tr->GS;
-    for (int sl = 1; sl < tr->nslots; ++sl) {
-        T_TRY(talloc(tr, &tr->DZ2[sl], max_act));
-        T_TRY(talloc(tr, &tr->GS2[sl], max_act));
-    }
+    std::vector<int> slots;   // dz[0], gs[0], dz[1], gs[1], ...
+    for (int sl = 0; sl < tr->nslots; ++sl) { slots.push_back(sl); slots.push_back(kSlots + sl); }
+    T_TRY(alloc_slots(tr, slots, max_act));
     int maxC = K;
     for (int v : n) maxC = std::max(maxC, v);
     tr->part_doubles = std::max<size_t>((size_t)1024 * 2 * maxC, (size_t)1024 * n[1] * K) + 1024;
@@ -1271,11 +1282,9 @@ int build_trainer(umx_trainer* tr, const float* blob, size_t blob_floats) {
         tr->bn_t.gmax = tr->d_maxw + k++;
         tr->smax.assign(L, nullptr);
         for (int i = 0; i < L; ++i) tr->smax[i] = tr->d_maxw + k++;
-        tr->dsmax.assign(L + 1, nullptr); tr->usmax.assign(L, nullptr); tr->cvmax.assign(L, nullptr);
-        for (int i = 0; i <= L; ++i) tr->dsmax[i] = tr->d_maxw + k++;
-        for (int i = 0; i < L; ++i) tr->usmax[i] = tr->d_maxw + k++;
-        for (int i = 0; i < L; ++i) tr->cvmax[i] = tr->d_maxw + k++;
-        tr->bmax = tr->d_maxw + k++;
+        for (std::vector<Act>* v : {&tr->ds, &tr->us, &tr->cv})
+            for (Act& a : *v) a.max = tr->d_maxw + k++;
+        tr->act_b.max = tr->d_maxw + k++;
         for (int i = 0; i < L; ++i) { tr->bn_d[i].bw = tr->d_maxw + k; k += 3; }
         for (int i = 0; i < L; ++i) { tr->bn_u[i].bw = tr->d_maxw + k; k += 3; }
         tr->bn_b.bw = tr->d_maxw + k; k += 3;
@@ -1283,31 +1292,14 @@ int build_trainer(umx_trainer* tr, const float* blob, size_t blob_floats) {
     }
 
     // ---- split-precision route of the forward / input-gradient convolutions: planes of every tensor they read
-    T_TRY(select_route(tr, blob));
-    tr->h_cv.resize(L);   // (h_cv[0] stays empty: only the 1x1 head reads cv[0])
-    if (tr->hconv) {
-        int S2 = P;
-        size_t max_dz = 0, max_gs = 0;
-        for (int i = 0; i <= L; ++i) {
-            T_TRY(alloc_h16(tr, tr->h_ds[i], (size_t)B * S2 * S2, n[i]));
-            if (i < L) max_dz = std::max(max_dz, (size_t)B * S2 * S2 * round_up(n[i + 1], 8));
-            if (i < L) S2 /= 2;
-        }
-        T_TRY(alloc_h16(tr, tr->h_b, (size_t)B * S2 * S2, n[L + 1]));
-        max_dz = std::max(max_dz, (size_t)B * S2 * S2 * round_up(n[L + 1], 8));
-        for (int idx = L - 1; idx >= 0; --idx) {
-            max_gs = std::max(max_gs, (size_t)B * S2 * S2 * round_up(4 * n[idx + 1], 8));
-            S2 *= 2;
-            T_TRY(alloc_h16(tr, tr->h_us[idx], (size_t)B * S2 * S2, n[idx + 1]));
-            if (idx >= 1) T_TRY(alloc_h16(tr, tr->h_cv[idx], (size_t)B * S2 * S2, n[idx + 1]));
-            max_dz = std::max(max_dz, (size_t)B * S2 * S2 * round_up(n[idx + 1], 8));
-        }
-        for (int sl = 0; sl < tr->nslots; ++sl) {   // gradient planes, one set per dz / gS slot; Cs is set per use
-            T_TRY(tzero(tr, &tr->h_dz[sl].hi, max_dz)); T_TRY(tzero(tr, &tr->h_dz[sl].lo, max_dz));
-            T_TRY(tzero(tr, &tr->h_gs[sl].hi, max_gs)); T_TRY(tzero(tr, &tr->h_gs[sl].lo, max_gs));
-        }
-        T_TRY(tzero(tr, &tr->d_xinv, 2 * kSlots));
+    // (after every fp32 buffer, in this order: the allocation sequence, and with it the address layout, is the one this graph always had)
+    for (int i = 0; i <= L; ++i) T_TRY(alloc_planes(tr, tr->ds[i], label_of("ds", i)));
+    T_TRY(alloc_planes(tr, tr->act_b, "act_b"));
+    for (int idx = L - 1; idx >= 0; --idx) {
+        T_TRY(alloc_planes(tr, tr->us[idx], label_of("us", idx)));
+        if (idx >= 1) T_TRY(alloc_planes(tr, tr->cv[idx], label_of("cv", idx)));   // (cv[0] has none: only the 1x1 head reads it)
     }
+    T_TRY(alloc_slot_planes(tr, slots, max_dz, max_gs));
 
     // ---- conv launches
     tr->c_fwd_d.resize(L); tr->c_dg_d.resize(L); tr->c_T.resize(L); tr->c_fwd_u.resize(L);
@@ -1418,60 +1410,42 @@ int build_legacy(umx_trainer* tr, const float* blob, size_t blob_floats) {
     tr->o_lt = seg("lt.w", (size_t)n[1] * K, K);
     T_TRY(alloc_params(tr, blob, blob_floats, pos));
 
-    // ---- max words (zeroed every step), then the range flag
+    // ---- max words (zeroed every step), then the range flag; handed out below, once the tensors exist
     tr->n_maxw = 16 + 4 * (L + 1) * (2 * E + 6);
     T_TRY(tzero(tr, &tr->d_maxw, (size_t)tr->n_maxw + 1));
-    int k = 0;
-    auto word = [&]() { return tr->d_maxw + k++; };
-    tr->dsmax.assign(L + 1, nullptr); tr->usmax.assign(L, nullptr); tr->smax.assign(L, nullptr);
-    for (int i = 0; i <= L; ++i) tr->dsmax[i] = word();
-    for (int i = 0; i < L; ++i) { tr->usmax[i] = word(); tr->smax[i] = word(); }
-    tr->bmax = word();
-    tr->lb_gmax = word();
-    for (std::vector<LBlock>* v : {&tr->ldb, &tr->lub})
-        for (LBlock& b : *v) {
-            for (int e = 0; e <= E; ++e) { b.amax.push_back(word()); b.gmax.push_back(word()); }
-        }
-    if (k > tr->n_maxw) return tfail(tr, UMX_ERR_INVALID, "internal: %d max words for %d", k, tr->n_maxw);
 
     // ---- activations
-    tr->ds.assign(L + 1, nullptr);
     tr->bn_d.resize(L);
-    tr->us.assign(L, nullptr); tr->dskip.assign(L, nullptr);
+    tr->dskip.assign(L, nullptr);
     T_TRY(select_route(tr, blob));
     // a chain's tensors: y[0..E], a[0..na)
-    auto chain = [&](LBlock& b, int S, int C, int na) -> int {
-        const size_t npix = (size_t)B * S * S;
-        b.y.assign(E + 1, nullptr); b.a.assign(na, nullptr); b.ha.resize(na);
-        for (int e = 0; e <= E; ++e) T_TRY(talloc(tr, &b.y[e], npix * C));
-        for (int e = 0; e < na; ++e) { T_TRY(talloc(tr, &b.a[e], npix * C)); T_TRY(alloc_h16(tr, b.ha[e], npix, C)); }
+    auto chain = [&](LBlock& b, const std::string& name, int S, int C, int na) -> int {
+        b.y.assign(E + 1, nullptr); b.a.resize(na);
+        for (int e = 0; e <= E; ++e) T_TRY(talloc(tr, &b.y[e], (size_t)B * S * S * C));
+        for (int e = 0; e < na; ++e) T_TRY(alloc_act(tr, b.a[e], label_of(name + ".a", e), S, C));
         return alloc_ident(tr, &b.ident, C);
     };
     size_t max_act = (size_t)B * P * P * std::max(n[0], K), max_dz = 0, max_gs = 0;
     auto grad_size = [&](size_t npix, int C) { max_act = std::max(max_act, npix * C); max_dz = std::max(max_dz, npix * round_up(C, 8)); };
     int S = P;
-    T_TRY(talloc(tr, &tr->ds[0], (size_t)B * P * P * n[0]));
-    T_TRY(alloc_h16(tr, tr->h_ds[0], (size_t)B * P * P, n[0]));
+    T_TRY(alloc_act(tr, tr->ds[0], label_of("ds", 0), P, n[0]));
     for (int i = 0; i < L; ++i) {
-        T_TRY(chain(tr->ldb[i], S, n[i + 1], E));
+        T_TRY(chain(tr->ldb[i], label_of("ldb", i), S, n[i + 1], E));
         T_TRY(bn_alloc(tr, tr->bn_d[i], n[i + 1], S, bn_d_off[i]));   // (its z: relu(z), what BN normalises)
         grad_size((size_t)B * S * S, n[i + 1]);
-        T_TRY(talloc(tr, &tr->ds[i + 1], (size_t)B * (S / 2) * (S / 2) * n[i + 1]));
-        T_TRY(alloc_h16(tr, tr->h_ds[i + 1], (size_t)B * (S / 2) * (S / 2), n[i + 1]));
+        T_TRY(alloc_act(tr, tr->ds[i + 1], label_of("ds", i + 1), S / 2, n[i + 1]));
         if (i + 1 <= L - 1) T_TRY(talloc(tr, &tr->dskip[i + 1], (size_t)B * (S / 2) * (S / 2) * n[i + 1]));
         S /= 2;
     }
     T_TRY(talloc(tr, &tr->lb_z, (size_t)B * S * S * n[L + 1]));
-    T_TRY(talloc(tr, &tr->act_b, (size_t)B * S * S * n[L + 1]));
-    T_TRY(alloc_h16(tr, tr->h_b, (size_t)B * S * S, n[L + 1]));
+    T_TRY(alloc_act(tr, tr->act_b, "act_b", S, n[L + 1]));
     T_TRY(alloc_ident(tr, &tr->lb_ident, n[L + 1]));
     grad_size((size_t)B * S * S, n[L + 1]);
     for (int idx = L - 1; idx >= 0; --idx) {
         max_gs = std::max(max_gs, (size_t)B * S * S * round_up(4 * n[idx + 1], 8));
         S *= 2;
-        T_TRY(talloc(tr, &tr->us[idx], (size_t)B * S * S * n[idx + 1]));
-        T_TRY(alloc_h16(tr, tr->h_us[idx], (size_t)B * S * S, n[idx + 1]));
-        T_TRY(chain(tr->lub[idx], S, n[idx + 1], E + 1));
+        T_TRY(alloc_act(tr, tr->us[idx], label_of("us", idx), S, n[idx + 1]));
+        T_TRY(chain(tr->lub[idx], label_of("lub", idx), S, n[idx + 1], E + 1));
         grad_size((size_t)B * S * S, n[idx + 1]);
     }
     T_TRY(talloc(tr, &tr->lt_z, (size_t)B * P * P * K));
@@ -1485,20 +1459,31 @@ int build_legacy(umx_trainer* tr, const float* blob, size_t blob_floats) {
     tr->max_act = max_act;
     T_TRY(talloc(tr, &tr->DA, max_act));
     T_TRY(talloc(tr, &tr->DB, max_act));
-    T_TRY(talloc(tr, &tr->DZ, max_act));
-    T_TRY(talloc(tr, &tr->TX, max_act));
-    T_TRY(talloc(tr, &tr->GS, max_act));
+    const std::vector<int> slots = {0, 1, kSlots};   // gradient slots: dz[0] and dz[1] for a chain (alternating), gs[0] for the
+    T_TRY(alloc_slots(tr, slots, max_act));          // transposed conv's space-to-depth gradient
     T_TRY(talloc(tr, &tr->DSUM, 2 * max_act));
     int maxC = K;
     for (int v : n) maxC = std::max(maxC, v);
     tr->part_doubles = std::max<size_t>((size_t)1024 * 2 * maxC, (size_t)1024 * n[1] * K) + 1024;
     T_TRY(talloc(tr, &tr->d_part, tr->part_doubles));
     T_TRY(tzero(tr, &tr->d_loss, 2));
-    if (tr->hconv) {   // gradient planes: two for a chain (alternating), one for the transposed conv's space-to-depth gradient
-        for (int sl = 0; sl < 2; ++sl) { T_TRY(tzero(tr, &tr->h_dz[sl].hi, max_dz)); T_TRY(tzero(tr, &tr->h_dz[sl].lo, max_dz)); }
-        T_TRY(tzero(tr, &tr->h_gs[0].hi, max_gs)); T_TRY(tzero(tr, &tr->h_gs[0].lo, max_gs));
-        T_TRY(tzero(tr, &tr->d_xinv, 2 * kSlots));
-    }
+
+    T_TRY(alloc_slot_planes(tr, slots, max_dz, max_gs));
+
+    // ---- every tensor's max word
+    int k = 0;
+    auto word = [&]() { return tr->d_maxw + k++; };
+    tr->smax.assign(L, nullptr);
+    for (Act& a : tr->ds) a.max = word();
+    for (int i = 0; i < L; ++i) { tr->us[i].max = word(); tr->smax[i] = word(); }
+    tr->act_b.max = word();
+    tr->lb_gmax = word();
+    for (std::vector<LBlock>* v : {&tr->ldb, &tr->lub})
+        for (LBlock& b : *v) {
+            for (Act& a : b.a) a.max = word();
+            for (int e = 0; e <= E; ++e) b.gmax.push_back(word());
+        }
+    if (k > tr->n_maxw) return tfail(tr, UMX_ERR_INVALID, "internal: %d max words for %d", k, tr->n_maxw);
 
     // ---- conv launches
     tr->c_dg_d.resize(L); tr->c_T.resize(L); tr->c_fwd_u.resize(L);
@@ -1556,57 +1541,47 @@ int build_legacy(umx_trainer* tr, const float* blob, size_t blob_floats) {
 // words of every tensor a weight gradient reads; otherwise the moving statistics (tfTraining: 0)
 int forward_legacy(umx_trainer* tr, const float* data, bool training, bool update) {
     const int L = tr->L, E = tr->E;
-    const std::vector<int>& n = tr->n;
     hipStream_t st = tr->stream;
-    const size_t Bz = (size_t)tr->B;
     int* const flagp = reinterpret_cast<int*>(tr->d_maxw + tr->n_maxw);
-    auto act = [&](const float* z, const float* stat, int S, int C, int pool, int a_kind, float* out, const H16* h, unsigned* omax) -> int {
+    // act(z) (pool: + the 2x2 max-pool) into out, with its max word and the planes it has (none on the exact-fp32 route)
+    auto act = [&](const float* z, const float* stat, int pool, int a_kind, const Act& out) -> int {
         ActParams a;
         a.z = z; a.stat = stat;
-        a.B = tr->B; a.H = a.W = S; a.C = C;
+        a.B = tr->B; a.H = a.W = pool ? 2 * out.S : out.S; a.C = out.C;
         a.pool = pool; a.act = a_kind;
         a.drop_rate = 0.f; a.drop_key = 0;
-        // (h: the planes the kernel writes, empty on the exact-fp32 route)
-        T_HIP(tr, launch_act_fwd(a, out, training ? omax : nullptr, h ? h->hi : nullptr, h ? h->lo : nullptr, h ? h->Cs : 0, flagp, st));
+        T_HIP(tr, launch_act_fwd(a, out.x, training ? out.max : nullptr, out.h.hi, out.h.lo, out.h.Cs, flagp, st));
         return UMX_OK;
     };
-    tr->ds[0] = const_cast<float*>(data);
-    T_TRY(track_act(tr, data, Bz * tr->P * tr->P, n[0], tr->h_ds[0], tr->dsmax[0], training));
-    int S = tr->P;
+    tr->ds[0].x = const_cast<float*>(data);
+    T_TRY(track_act(tr, tr->ds[0], training));
     for (int i = 0; i < L; ++i) {
         LBlock& b = tr->ldb[i];
         BnSite& s = tr->bn_d[i];
-        const int C = n[i + 1];
         for (int e = 0; e <= E; ++e) {
             const bool last = e == E;   // (+ the shortcut on the block input)
-            T_TRY(run_tconv(tr, b.fwd[e], e == 0 ? tr->ds[i] : b.a[e - 1], e == 0 ? tr->h_ds[i] : b.ha[e - 1], nullptr, b.y[e],
-                            last ? tr->ds[i] : nullptr, last ? &tr->h_ds[i] : nullptr));
-            if (!last) T_TRY(act(b.y[e], b.ident, S, C, 0, ACT_RELU, b.a[e], &b.ha[e], b.amax[e]));
+            T_TRY(run_tconv(tr, b.fwd[e], e == 0 ? tr->ds[i] : b.a[e - 1], b.y[e], last ? &tr->ds[i] : nullptr));
+            if (!last) T_TRY(act(b.y[e], b.ident, 0, ACT_RELU, b.a[e]));
         }
-        T_TRY(act(b.y[E], b.ident, S, C, 0, ACT_RELU, s.z, nullptr, nullptr));      // relu(z): what BN normalises
+        T_TRY(act(b.y[E], b.ident, 0, ACT_RELU, Act{s.z, H16(), nullptr, nullptr, s.H, s.C}));      // relu(z): what BN normalises
         T_TRY(bn_forward_stats(tr, s, update, training));
-        T_TRY(act(s.z, s.stat, S, C, 1, ACT_NONE, tr->ds[i + 1], &tr->h_ds[i + 1], tr->dsmax[i + 1]));   // BN, then the pool
-        S /= 2;
+        T_TRY(act(s.z, s.stat, 1, ACT_NONE, tr->ds[i + 1]));   // BN, then the pool
     }
-    T_TRY(run_tconv(tr, tr->c_fwd_b, tr->ds[L], tr->h_ds[L], nullptr, tr->lb_z));
-    T_TRY(act(tr->lb_z, tr->lb_ident, S, n[L + 1], 0, ACT_RELU, tr->act_b, &tr->h_b, tr->bmax));
-    const float* cur = tr->act_b;
-    const H16* hcur = &tr->h_b;
+    T_TRY(run_tconv(tr, tr->c_fwd_b, tr->ds[L], tr->lb_z));
+    T_TRY(act(tr->lb_z, tr->lb_ident, 0, ACT_RELU, tr->act_b));
+    const Act* cur = &tr->act_b;
     for (int idx = L - 1; idx >= 0; --idx) {
         LBlock& b = tr->lub[idx];
-        const int C = n[idx + 1];
-        S *= 2;
-        T_TRY(run_tconv(tr, tr->c_T[idx], cur, *hcur, nullptr, tr->us[idx]));   // (ReLU fused)
-        T_TRY(track_act(tr, tr->us[idx], Bz * S * S, C, tr->h_us[idx], tr->usmax[idx], training));
+        T_TRY(run_tconv(tr, tr->c_T[idx], *cur, tr->us[idx].x));   // (ReLU fused)
+        T_TRY(track_act(tr, tr->us[idx], training));
         for (int e = 0; e <= E; ++e) {
-            if (e == 0) T_TRY(run_tconv(tr, tr->c_fwd_u[idx], tr->ds[idx], tr->h_ds[idx], nullptr, b.y[0], tr->us[idx], &tr->h_us[idx]));
-            else T_TRY(run_tconv(tr, b.fwd[e], b.a[e - 1], b.ha[e - 1], nullptr, b.y[e]));
-            T_TRY(act(b.y[e], b.ident, S, C, 0, ACT_RELU, b.a[e], &b.ha[e], b.amax[e]));
+            if (e == 0) T_TRY(run_tconv(tr, tr->c_fwd_u[idx], tr->ds[idx], b.y[0], &tr->us[idx]));
+            else T_TRY(run_tconv(tr, b.fwd[e], b.a[e - 1], b.y[e]));
+            T_TRY(act(b.y[e], b.ident, 0, ACT_RELU, b.a[e]));
         }
-        cur = b.a[E];
-        hcur = &b.ha[E];
+        cur = &b.a[E];
     }
-    T_HIP(tr, launch_head_fwd(cur, Bz * tr->P * tr->P, n[1], tr->K, tr->d_w + tr->o_lt, tr->lt_z, st));
+    T_HIP(tr, launch_head_fwd(cur->x, cur->npix(tr->B), cur->C, tr->K, tr->d_w + tr->o_lt, tr->lt_z, st));
     return UMX_OK;
 }
 
@@ -1623,87 +1598,73 @@ int enqueue_legacy(umx_trainer* tr, const float* data, const float* labels, cons
     if (tr->prof) T_HIP(tr, hipEventRecord(tr->ev[1], st));
 
     // ------------------------------------------------------------------ backward
-    const float* top_in = tr->lub[0].a[E];
     {   // top: d loss / d logits -> 1x1 conv
         const int nblk = chan_blocks(Npix, n[1]);
-        T_HIP(tr, launch_head_bwd(top_in, tr->d_dt, tr->d_w + tr->o_lt, Npix, n[1], K, tr->DA, tr->d_part, nblk, st));
+        T_HIP(tr, launch_head_bwd(tr->lub[0].a[E].x, tr->d_dt, tr->d_w + tr->o_lt, Npix, n[1], K, tr->DA, tr->d_part, nblk, st));
         T_HIP(tr, launch_reduce_partials(tr->d_part, nblk, n[1] * K, 1.0, tr->d_g + tr->o_lt, tr->d_w + tr->o_lt, 0, 0.f, st));
     }
-    float* const gb[2] = {tr->DZ, tr->TX};   // a chain's gradients alternate between these two, their planes between h_dz[0] / [1]
-    // gradient w.r.t. y (pre-ReLU) from the gradient w.r.t. relu(y): into gb[pl], with its max word and planes
-    auto relu_bwd = [&](const float* dy, const float* y, int pl, size_t npix, int C, unsigned* gw) -> int {
-        T_HIP(tr, launch_relu_bwd_max(dy, y, gb[pl], npix * C, gw, st));
-        tr->h_dz[pl].Cs = round_up(C, 8);
-        return to_h16(tr, gb[pl], npix, C, tr->h_dz[pl], gw, tr->d_xinv + pl, st);
+    // A chain's gradients alternate between the slots dz[0] and dz[1].
+    // gradient w.r.t. y (pre-ReLU, [B, S, S, C]) from the gradient w.r.t. relu(y): *g is slot pl's view of it, with its max word gw and planes
+    auto relu_bwd = [&](const float* dy, const float* y, int pl, int S, int C, unsigned* gw, Act* g) -> int {
+        *g = tr->dz[pl].view(S, C, gw);
+        T_HIP(tr, launch_relu_bwd_max(dy, y, g->x, g->npix(B) * C, gw, st));
+        return to_h16(tr, *g, st);
     };
-    auto wgrad = [&](WgradParams& w, const float* X, const H16* xp, const unsigned* xmax, int pl, unsigned* gw, int Ctot, int c_off,
-                     size_t w_off) -> int {
-        return run_wgrad(tr, w, X, gb[pl], Ctot, c_off, w_off, 0.f, SIZE_MAX, xmax, gw, st, tr->hconv ? xp : nullptr, nullptr,
-                         tr->hconv ? &tr->h_dz[pl] : nullptr, tr->d_xinv + pl);
+    auto wgrad = [&](WgradParams& w, const Act& X, const Act& G, int Ctot, int c_off, size_t w_off) -> int {
+        return run_wgrad(tr, w, X, G, Ctot, c_off, w_off, 0.f, SIZE_MAX, st);
     };
-    // the extra convolutions of a chain, last first: gb[(E - e) & 1] holds d/dy[e]; on return gb[E & 1] holds d/dy[0]
-    auto extras_bwd = [&](LBlock& b, size_t npix, int C) -> int {
+    // the extra convolutions of a chain, last first: *g is d/dy[E] (slot 0) on entry, d/dy[e] in slot (E - e) & 1 on the way, d/dy[0] on return
+    auto extras_bwd = [&](LBlock& b, Act* g) -> int {
         for (int e = E; e >= 1; --e) {
-            const int pl = (E - e) & 1;
-            T_TRY(wgrad(b.wg[e], b.a[e - 1], &b.ha[e - 1], b.amax[e - 1], pl, b.gmax[e], C, 0, b.o_wx[e - 1]));
-            T_TRY(run_tconv(tr, b.dg[e], gb[pl], tr->h_dz[pl], tr->d_xinv + pl, tr->DA));
-            T_TRY(relu_bwd(tr->DA, b.y[e - 1], pl ^ 1, npix, C, b.gmax[e - 1]));
+            T_TRY(wgrad(b.wg[e], b.a[e - 1], *g, g->C, 0, b.o_wx[e - 1]));
+            T_TRY(run_tconv(tr, b.dg[e], *g, tr->DA));
+            T_TRY(relu_bwd(tr->DA, b.y[e - 1], ((E - e) & 1) ^ 1, g->S, g->C, b.gmax[e - 1], g));
         }
         return UMX_OK;
     };
-    int S = P;
+    Act g;
     for (int idx = 0; idx < L; ++idx) {    // up layers, output side first; DA: d loss / d (layer output)
         LBlock& b = tr->lub[idx];
-        const int Cskip = n[idx], Cup = n[idx + 1];
-        const size_t npix = (size_t)B * S * S;
-        T_TRY(relu_bwd(tr->DA, b.y[E], 0, npix, Cup, b.gmax[E]));
-        T_TRY(extras_bwd(b, npix, Cup));
-        const int p0 = E & 1;
-        T_TRY(wgrad(tr->wg_u0[idx], tr->ds[idx], &tr->h_ds[idx], tr->dsmax[idx], p0, b.gmax[0], Cskip + Cup, 0, tr->o_w2[idx]));
-        T_TRY(wgrad(tr->wg_u1[idx], tr->us[idx], &tr->h_us[idx], tr->usmax[idx], p0, b.gmax[0], Cskip + Cup, Cskip, tr->o_w2[idx]));
-        T_TRY(run_tconv(tr, tr->c_dg_us[idx], gb[p0], tr->h_dz[p0], tr->d_xinv + p0, tr->DB));
-        if (idx >= 1) T_TRY(run_tconv(tr, tr->c_dg_skip[idx], gb[p0], tr->h_dz[p0], tr->d_xinv + p0, tr->dskip[idx]));
-        T_HIP(tr, launch_leaky_bwd_s2d_max(tr->DB, tr->us[idx], B, S / 2, Cup, 0.f, tr->GS, tr->smax[idx], st));   // ReLU: slope 0
-        if (tr->hconv) {
-            tr->h_gs[0].Cs = round_up(4 * Cup, 8);
-            T_TRY(to_h16(tr, tr->GS, (size_t)B * (S / 2) * (S / 2), 4 * Cup, tr->h_gs[0], tr->smax[idx], tr->d_xinv + kSlots, st));
-        }
-        const float* layer_in = idx == L - 1 ? tr->act_b : tr->lub[idx + 1].a[E];
-        const H16* hin = !tr->hconv ? nullptr : idx == L - 1 ? &tr->h_b : &tr->lub[idx + 1].ha[E];
-        T_TRY(run_wgrad(tr, tr->wg_T[idx], tr->GS, layer_in, Cup, 0, tr->o_wt[idx], 0.f, SIZE_MAX, tr->smax[idx],
-                        idx == L - 1 ? tr->bmax : tr->lub[idx + 1].amax[E], st, tr->hconv ? &tr->h_gs[0] : nullptr, tr->d_xinv + kSlots, hin,
-                        nullptr));
-        T_TRY(run_tconv(tr, tr->c_dg_T[idx], tr->GS, tr->h_gs[0], tr->d_xinv + kSlots, tr->DA));
-        S /= 2;
+        const int Cskip = n[idx], Cup = n[idx + 1], S = tr->us[idx].S;
+        T_TRY(relu_bwd(tr->DA, b.y[E], 0, S, Cup, b.gmax[E], &g));
+        T_TRY(extras_bwd(b, &g));
+        T_TRY(wgrad(tr->wg_u0[idx], tr->ds[idx], g, Cskip + Cup, 0, tr->o_w2[idx]));
+        T_TRY(wgrad(tr->wg_u1[idx], tr->us[idx], g, Cskip + Cup, Cskip, tr->o_w2[idx]));
+        T_TRY(run_tconv(tr, tr->c_dg_us[idx], g, tr->DB));
+        if (idx >= 1) T_TRY(run_tconv(tr, tr->c_dg_skip[idx], g, tr->dskip[idx]));
+        const Act gs = tr->gs[0].view(S / 2, 4 * Cup, tr->smax[idx]);
+        T_HIP(tr, launch_leaky_bwd_s2d_max(tr->DB, tr->us[idx].x, B, S / 2, Cup, 0.f, gs.x, gs.max, st));   // ReLU: slope 0
+        T_TRY(to_h16(tr, gs, st));
+        // (the transposed convolution's filter: X is gS, G the layer's input)
+        T_TRY(wgrad(tr->wg_T[idx], gs, idx == L - 1 ? tr->act_b : tr->lub[idx + 1].a[E], Cup, 0, tr->o_wt[idx]));
+        T_TRY(run_tconv(tr, tr->c_dg_T[idx], gs, tr->DA));
     }
     {   // bottom
-        const size_t npix = (size_t)B * S * S;
-        T_TRY(relu_bwd(tr->DA, tr->lb_z, 0, npix, n[L + 1], tr->lb_gmax));
-        T_TRY(wgrad(tr->wg_b, tr->ds[L], &tr->h_ds[L], tr->dsmax[L], 0, tr->lb_gmax, n[L], 0, tr->o_lb));
-        T_TRY(run_tconv(tr, tr->c_dg_b, gb[0], tr->h_dz[0], tr->d_xinv, tr->DB));
+        T_TRY(relu_bwd(tr->DA, tr->lb_z, 0, tr->act_b.S, n[L + 1], tr->lb_gmax, &g));
+        T_TRY(wgrad(tr->wg_b, tr->ds[L], g, n[L], 0, tr->o_lb));
+        T_TRY(run_tconv(tr, tr->c_dg_b, g, tr->DB));
     }
     for (int i = L - 1; i >= 0; --i) {     // down layers; DB (+ dskip[i+1]): d loss / d ds[i+1]
-        S *= 2;
         LBlock& b = tr->ldb[i];
         BnSite& s = tr->bn_d[i];
         const int Ci = n[i], C = n[i + 1];
-        const size_t npix = (size_t)B * S * S;
+        const size_t npix = (size_t)B * s.H * s.W;
         {   // pool -> BN backward on relu(z) (gamma / beta gradients in a fixed order) -> the ReLU mask
+            float* const g0 = tr->dz[0].x;
             ActParams a = act_params(tr, s, 1, ACT_NONE, 0.f, 0);
             const int nblk = chan_blocks(npix / 4, C);
-            T_HIP(tr, launch_act_bwd(a, tr->DB, i + 1 <= L - 1 ? tr->dskip[i + 1] : nullptr, gb[0], tr->d_part, nblk, nullptr, st));
+            T_HIP(tr, launch_act_bwd(a, tr->DB, i + 1 <= L - 1 ? tr->dskip[i + 1] : nullptr, g0, tr->d_part, nblk, nullptr, st));
             T_HIP(tr, launch_bn_bwd_finalize(tr->d_part, nblk, npix, C, tr->d_g + s.gamma, tr->d_g + s.beta, s.m12, st));
-            T_HIP(tr, launch_bn_bwd_apply_max(gb[0], s.z, s.stat, s.m12, npix, C, nullptr, nullptr, nullptr, nullptr, nullptr, 0, flagp, st));
-            T_TRY(relu_bwd(gb[0], b.y[E], 0, npix, C, b.gmax[E]));
+            T_HIP(tr, launch_bn_bwd_apply_max(g0, s.z, s.stat, s.m12, npix, C, nullptr, nullptr, nullptr, nullptr, nullptr, 0, flagp, st));
+            T_TRY(relu_bwd(g0, b.y[E], 0, s.H, C, b.gmax[E], &g));
         }
-        // the shortcut: weight gradient and (i >= 1) input gradient, before the chain reuses gb[0]
-        T_TRY(wgrad(b.wg_sh, tr->ds[i], &tr->h_ds[i], tr->dsmax[i], 0, b.gmax[E], Ci, 0, tr->o_ws[i]));
-        if (i >= 1) T_TRY(run_tconv(tr, b.dg_sh, gb[0], tr->h_dz[0], tr->d_xinv, tr->DSUM + tr->max_act));
-        T_TRY(extras_bwd(b, npix, C));
-        const int p0 = E & 1;
-        T_TRY(wgrad(tr->wg_d[i], tr->ds[i], &tr->h_ds[i], tr->dsmax[i], p0, b.gmax[0], Ci, 0, tr->o_w1[i]));
+        // the shortcut: weight gradient and (i >= 1) input gradient, before the chain reuses slot 0
+        T_TRY(wgrad(b.wg_sh, tr->ds[i], g, Ci, 0, tr->o_ws[i]));
+        if (i >= 1) T_TRY(run_tconv(tr, b.dg_sh, g, tr->DSUM + tr->max_act));
+        T_TRY(extras_bwd(b, &g));
+        T_TRY(wgrad(tr->wg_d[i], tr->ds[i], g, Ci, 0, tr->o_w1[i]));
         if (i >= 1) {   // d ds[i] = first-conv input gradient + shortcut input gradient
-            T_TRY(run_tconv(tr, tr->c_dg_d[i], gb[p0], tr->h_dz[p0], tr->d_xinv + p0, tr->DSUM));
+            T_TRY(run_tconv(tr, tr->c_dg_d[i], g, tr->DSUM));
             T_HIP(tr, launch_split_reduce(tr->DSUM, 2, tr->max_act, npix * Ci, ACT_NONE, tr->DB, st));
         }
     }
@@ -1720,7 +1681,7 @@ TrainerIO trainer_io(umx_trainer* tr) {
     io.device = tr->device; io.B = tr->B; io.P = tr->P; io.C = tr->n[0]; io.K = tr->K;
     io.legacy = tr->legacy;
     io.stream = tr->stream;
-    io.data = tr->ds[0]; io.labels = tr->d_labels; io.weights = tr->d_weights; io.probs = tr->d_probs;
+    io.data = tr->ds[0].x; io.labels = tr->d_labels; io.weights = tr->d_weights; io.probs = tr->d_probs;
     return io;
 }
 
@@ -1745,10 +1706,10 @@ int trainer_eval_begin(umx_trainer* tr) {
 // forward: the eval-mode pass (moving statistics, no dropout) on the batch in ds[0] -> softmax in d_probs
 int trainer_eval_forward(umx_trainer* tr) {
     const size_t npx = (size_t)tr->B * tr->P * tr->P;
-    float* own = tr->ds[0];
+    float* own = tr->ds[0].x;
     T_TRY(pack_all(tr, tr->stream, 0));
     const int rc = tr->legacy ? forward_legacy(tr, own, false, false) : forward_pass(tr, own, false, false);
-    tr->ds[0] = own;
+    tr->ds[0].x = own;
     T_TRY(rc);
     if (tr->legacy) T_HIP(tr, launch_softmax_only(tr->lt_z, tr->ident_k, npx, tr->K, tr->d_probs, tr->stream));
     else T_HIP(tr, launch_softmax_only(tr->bn_t.z, tr->bn_t.stat, npx, tr->K, tr->d_probs, tr->stream));
@@ -2053,10 +2014,10 @@ int umx_train_step_dev(umx_trainer* tr, const float* data_dev, const float* labe
     if (!tr || !data_dev || !labels_dev || (!weights_dev && !tr->legacy)) return tfail(tr, UMX_ERR_INVALID, "null argument");
     T_HIP(tr, hipSetDevice(tr->device));
     T_TRY(fold_profile(tr));
-    float* own = tr->ds[0];
+    float* own = tr->ds[0].x;
     const int rc = tr->legacy ? enqueue_legacy(tr, data_dev, labels_dev, weights_dev, apply_update != 0)
                               : enqueue_step(tr, data_dev, labels_dev, weights_dev, apply_update != 0);
-    tr->ds[0] = own;
+    tr->ds[0].x = own;
     T_TRY(rc);
     return umx::trainer_guard_check(tr);
 }
@@ -2090,10 +2051,10 @@ int umx_train_step(umx_trainer* tr, const float* data, const float* labels, cons
     if (!tr || !data || !labels || (!weights && !tr->legacy)) return tfail(tr, UMX_ERR_INVALID, "null argument");
     T_HIP(tr, hipSetDevice(tr->device));
     const size_t npx = (size_t)tr->B * tr->P * tr->P;
-    T_HIP(tr, hipMemcpyAsync(tr->ds[0], data, npx * tr->n[0] * sizeof(float), hipMemcpyHostToDevice, tr->stream));
+    T_HIP(tr, hipMemcpyAsync(tr->ds[0].x, data, npx * tr->n[0] * sizeof(float), hipMemcpyHostToDevice, tr->stream));
     T_HIP(tr, hipMemcpyAsync(tr->d_labels, labels, npx * tr->K * sizeof(float), hipMemcpyHostToDevice, tr->stream));
     if (weights) T_HIP(tr, hipMemcpyAsync(tr->d_weights, weights, npx * tr->K * sizeof(float), hipMemcpyHostToDevice, tr->stream));
-    T_TRY(umx_train_step_dev(tr, tr->ds[0], tr->d_labels, weights ? tr->d_weights : nullptr, apply_update));
+    T_TRY(umx_train_step_dev(tr, tr->ds[0].x, tr->d_labels, weights ? tr->d_weights : nullptr, apply_update));
     double l[3];
     T_TRY(umx_trainer_loss(tr, l));
     if (loss3) { loss3[0] = l[0]; loss3[1] = l[1]; loss3[2] = l[2]; }
@@ -2104,7 +2065,7 @@ int umx_trainer_eval(umx_trainer* tr, const float* data, float* probs_host) {
     if (!tr || !data || !probs_host) return tfail(tr, UMX_ERR_INVALID, "null argument");
     T_TRY(umx::trainer_eval_begin(tr));
     const size_t npx = (size_t)tr->B * tr->P * tr->P;
-    T_HIP(tr, hipMemcpyAsync(tr->ds[0], data, npx * tr->n[0] * sizeof(float), hipMemcpyHostToDevice, tr->stream));
+    T_HIP(tr, hipMemcpyAsync(tr->ds[0].x, data, npx * tr->n[0] * sizeof(float), hipMemcpyHostToDevice, tr->stream));
     T_TRY(umx::trainer_eval_forward(tr));
     T_HIP(tr, hipMemcpyAsync(probs_host, tr->d_probs, npx * tr->K * sizeof(float), hipMemcpyDeviceToHost, tr->stream));
     const int rc = umx::trainer_eval_end(tr);
@@ -2163,12 +2124,10 @@ int umx_trainer_read_tensor(umx_trainer* tr, const char* name, float* out, size_
     else if ((i = index_of("lu", tr->L)) >= 0) site = &tr->bn_u[i];
     if (site && what == "z") { src = site->z; n = (size_t)tr->B * site->H * site->W * site->C; }
     else if (site && what == "stat") { src = site->stat; n = 4 * (size_t)site->C; }
-    else if (what == "us" && (i = index_of("lu", tr->L)) >= 0) {
-        const int S = tr->P >> i;
-        src = tr->us[i]; n = (size_t)tr->B * S * S * tr->n[i + 1];
-    } else if (what.empty() && (i = index_of("ds", tr->L + 1)) >= 0) {
-        const int S = tr->P >> i;
-        src = tr->ds[i]; n = (size_t)tr->B * S * S * tr->n[i];
+    else {
+        const Act* a = what == "us" && (i = index_of("lu", tr->L)) >= 0 ? &tr->us[i]
+                       : what.empty() && (i = index_of("ds", tr->L + 1)) >= 0 ? &tr->ds[i] : nullptr;
+        if (a) { src = a->x; n = a->npix(tr->B) * a->C; }
     }
     if (!src) return tfail(tr, UMX_ERR_INVALID, "unknown tensor %s", name);
     const size_t cap = *n_floats;
