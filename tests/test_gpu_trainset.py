@@ -12,6 +12,7 @@ import pytest
 
 import helpers
 import trainset_ref as ref
+from trainset_cases import _descs
 from unmicst_amd import finetune, model, tiffio, trainer, trainset, umx
 
 pytestmark = pytest.mark.gpu
@@ -31,13 +32,6 @@ def _random_set(hp, N, pages, S, seed):
     wmaps = [rng.random((S, S)).astype(np.float32) * 2 for _ in range(N)]
     wmaps[1] = None                                                          # a missing map counts as 0
     return planes, ann, wmaps
-
-
-def _descs(rows):
-    d = np.zeros(len(rows), trainer.SAMPLE_DESC)
-    for j, r in enumerate(rows):
-        d[j] = tuple(r) + (0,)
-    return d
 
 
 def _ref(planes, ann, wmaps, d, hp, lw):

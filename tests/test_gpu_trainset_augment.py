@@ -15,6 +15,7 @@ import pytest
 import helpers
 import trainset_augment_ref as aref
 import trainset_ref as ref
+from trainset_cases import MEAN, STD, _augs, _descs, _random_set, _same_bits, _state
 from unmicst_amd import finetune, model, tiffio, trainer, trainset, umx
 
 pytestmark = pytest.mark.gpu
@@ -26,47 +27,11 @@ LEG_P16 = helpers.small_hps()["legacy_k3_x2"]           # 16-pixel tile, 2 chann
 LW3 = trainset.LabelWeights(True, (1.0, 2.0, 7.0), (0.0, 15.0, 0.25))
 SIGMAS = (0.75, 1.5, 4.0)                               # radii 2, 5 and 12 (the largest the kernel takes)
 GAINS = (1.0, 1.5, 4.0)
-MEAN, STD = 0.2, 0.15
-
-
-def _random_set(hp, N, pages, S, seed):
-    """Normalised planes whose im2double values lie in 0..1, so that gains of 1.5 and 4 clip some pixels and leave others."""
-    rng = np.random.default_rng(seed)
-    raw = rng.random((N, hp.nChannels, pages, S, S)) ** 2
-    planes = ((raw - MEAN) / STD).astype(np.float32)
-    ann = rng.integers(0, hp.nClasses + 2, (N, S, S)).astype(np.uint8)
-    wmaps = [rng.random((S, S)).astype(np.float32) * 2 for _ in range(N)]
-    wmaps[1] = None
-    return planes, ann, wmaps
-
-
-def _descs(rows):
-    d = np.zeros(len(rows), trainer.SAMPLE_DESC)
-    for j, r in enumerate(rows):
-        d[j] = tuple(r) + (0,)
-    return d
-
-
-def _augs(rows):
-    a = np.zeros(len(rows), trainer.AUGMENT_DESC)
-    for j, r in enumerate(rows):
-        a[j] = tuple(r)
-    return a
 
 
 def _ref(planes, ann, wmaps, d, a, table, hp, lw):
     cw, iw = (lw.class_weight, lw.intersect_weight) if lw.weighted else (None, None)
     return aref.assemble_augmented(planes, ann, wmaps, d, a, table, hp.imSize, hp.nClasses, cw, iw)
-
-
-def _same_bits(got, want, what):
-    for k, (g, w) in enumerate(zip(got, want)):
-        if w is None:
-            assert g is None, what
-            continue
-        assert g.dtype == np.float32 and g.shape == w.shape, (what, k)
-        ne = g.view(np.uint32) != w.view(np.uint32)
-        assert not ne.any(), (what, ("data", "labels", "weights")[k], int(ne.sum()), np.argwhere(ne)[:4].tolist())
 
 
 def _cases(S, P, N, pages):
@@ -119,11 +84,6 @@ def test_assemble_augmented_is_bit_equal_to_the_restatement(which):
     ceiling = np.float32((1.0 - np.float64(np.float32(MEAN))) / np.float64(np.float32(STD)))
     assert 0.05 < float((s == ceiling).mean()) < 0.95
     tr.close()
-
-
-def _state(tr):
-    m, v = tr.slots()
-    return tr.blob().tobytes(), m.tobytes(), v.tobytes()
 
 
 @pytest.mark.parametrize("which", ["v2", "legacy"])

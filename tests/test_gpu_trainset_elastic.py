@@ -15,6 +15,7 @@ import helpers
 import trainset_elastic_ref as eref
 import trainset_ref as ref
 import trainset_warp_ref as wref
+from trainset_cases import MEAN, STD, _augs, _descs, _elastics, _random_set, _same_bits, _state, _warps
 from unmicst_amd import finetune, model, trainer, trainset, umx
 
 pytestmark = pytest.mark.gpu
@@ -25,49 +26,8 @@ V2_C2K3 = helpers.small_hps()["v2_duo_like"]            # 32-pixel tile
 LW3 = trainset.LabelWeights(True, (1.0, 2.0, 7.0), (0.0, 15.0, 0.25))
 SIGMAS = (0.75, 1.5, 4.0)                               # radii 2, 5 and 12 (the largest the kernel takes)
 GAINS = (1.0, 1.5, 4.0)
-MEAN, STD = 0.2, 0.15
 IDENTITY = (1.0, 0.0, 0.0, 1.0)
 WARPS = ((30.0, 1.25), (0.0, 1.0), (133.7, 0.5), (-171.0, 2.0), (7.0, 1.0), (0.0, 0.8), (90.0, 1.0), (261.0, 1.7))
-
-
-def _random_set(hp, N, pages, S, seed):
-    rng = np.random.default_rng(seed)
-    raw = rng.random((N, hp.nChannels, pages, S, S)) ** 2
-    planes = ((raw - MEAN) / STD).astype(np.float32)
-    ann = rng.integers(0, hp.nClasses + 2, (N, S, S)).astype(np.uint8)
-    wmaps = [rng.random((S, S)).astype(np.float32) * 2 for _ in range(N)]
-    wmaps[1] = None
-    return planes, ann, wmaps
-
-
-def _descs(rows):
-    d = np.zeros(len(rows), trainer.SAMPLE_DESC)
-    for j, r in enumerate(rows):
-        d[j] = tuple(r) + (0,)
-    return d
-
-
-def _augs(rows):
-    a = np.zeros(len(rows), trainer.AUGMENT_DESC)
-    for j, r in enumerate(rows):
-        a[j] = tuple(r)
-    return a
-
-
-def _warps(ms):
-    w = np.zeros(len(ms), trainer.WARP_DESC)
-    for j, m in enumerate(ms):
-        w["m"][j] = m
-    return w
-
-
-def _elastics(lats):
-    """lats: per image None (n = 0) or (n, d [2][6][6])."""
-    e = np.zeros(len(lats), trainer.ELASTIC_DESC)
-    for j, l in enumerate(lats):
-        if l is not None:
-            e["n"][j], e["d"][j] = l
-    return e
 
 
 def _lattice(rng, n, sigma):
@@ -77,17 +37,6 @@ def _lattice(rng, n, sigma):
 def _ref(planes, ann, wmaps, d, a, w, e, table, hp, lw):
     cw, iw = (lw.class_weight, lw.intersect_weight) if lw.weighted else (None, None)
     return eref.assemble_elastic(planes, ann, wmaps, d, a, w, e, table, hp.imSize, hp.nClasses, cw, iw)
-
-
-def _same_bits(got, want, what, rows=slice(None)):
-    for k, (g, w) in enumerate(zip(got, want)):
-        if w is None:
-            assert g is None, what
-            continue
-        g, w = g[rows], w[rows]
-        assert g.dtype == np.float32 and g.shape == w.shape, (what, k)
-        ne = g.view(np.uint32) != w.view(np.uint32)
-        assert not ne.any(), (what, ("data", "labels", "weights")[k], int(ne.sum()), np.argwhere(ne)[:4].tolist())
 
 
 def _cases(S, P, N, pages):
@@ -179,11 +128,6 @@ def test_assemble_elastic_is_bit_equal_to_the_restatement(which, wider):
     for j in range(B):
         assert (got[0][j] != plain[0][j]).mean() > 0.5 and (got[1][j] != plain[1][j]).any()
     tr.close()
-
-
-def _state(tr):
-    m, v = tr.slots()
-    return tr.blob().tobytes(), m.tobytes(), v.tobytes()
 
 
 @pytest.mark.parametrize("with_aug", [True, False])

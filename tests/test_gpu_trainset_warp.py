@@ -14,6 +14,7 @@ import pytest
 import helpers
 import trainset_ref as ref
 import trainset_warp_ref as wref
+from trainset_cases import MEAN, STD, _augs, _descs, _random_set, _same_bits, _state, _warps
 from unmicst_amd import finetune, model, trainer, trainset, umx
 
 pytestmark = pytest.mark.gpu
@@ -24,58 +25,15 @@ V2_C2K3 = helpers.small_hps()["v2_duo_like"]            # 32-pixel tile
 LW3 = trainset.LabelWeights(True, (1.0, 2.0, 7.0), (0.0, 15.0, 0.25))
 SIGMAS = (0.75, 1.5, 4.0)                               # radii 2, 5 and 12 (the largest the kernel takes)
 GAINS = (1.0, 1.5, 4.0)
-MEAN, STD = 0.2, 0.15
 IDENTITY = (1.0, 0.0, 0.0, 1.0)
 QUARTER_TURNS = (((0.0, -1.0, 1.0, 0.0), 5), ((-1.0, 0.0, 0.0, -1.0), 3))   # (matrix, the transform code it equals)
 # (angle, zoom) per image: every quadrant, both ends of the zoom range the sampler may draw and beyond the crop's own sample
 WARPS = ((30.0, 1.25), (0.0, 1.0), (133.7, 0.5), (-171.0, 2.0), (7.0, 1.0), (0.0, 0.8), (90.0, 1.0), (261.0, 1.7))
 
 
-def _random_set(hp, N, pages, S, seed):
-    rng = np.random.default_rng(seed)
-    raw = rng.random((N, hp.nChannels, pages, S, S)) ** 2
-    planes = ((raw - MEAN) / STD).astype(np.float32)
-    ann = rng.integers(0, hp.nClasses + 2, (N, S, S)).astype(np.uint8)
-    wmaps = [rng.random((S, S)).astype(np.float32) * 2 for _ in range(N)]
-    wmaps[1] = None
-    return planes, ann, wmaps
-
-
-def _descs(rows):
-    d = np.zeros(len(rows), trainer.SAMPLE_DESC)
-    for j, r in enumerate(rows):
-        d[j] = tuple(r) + (0,)
-    return d
-
-
-def _augs(rows):
-    a = np.zeros(len(rows), trainer.AUGMENT_DESC)
-    for j, r in enumerate(rows):
-        a[j] = tuple(r)
-    return a
-
-
-def _warps(ms):
-    w = np.zeros(len(ms), trainer.WARP_DESC)
-    for j, m in enumerate(ms):
-        w["m"][j] = m
-    return w
-
-
 def _ref(planes, ann, wmaps, d, a, w, table, hp, lw):
     cw, iw = (lw.class_weight, lw.intersect_weight) if lw.weighted else (None, None)
     return wref.assemble_warped(planes, ann, wmaps, d, a, w, table, hp.imSize, hp.nClasses, cw, iw)
-
-
-def _same_bits(got, want, what, rows=slice(None)):
-    for k, (g, w) in enumerate(zip(got, want)):
-        if w is None:
-            assert g is None, what
-            continue
-        g, w = g[rows], w[rows]
-        assert g.dtype == np.float32 and g.shape == w.shape, (what, k)
-        ne = g.view(np.uint32) != w.view(np.uint32)
-        assert not ne.any(), (what, ("data", "labels", "weights")[k], int(ne.sum()), np.argwhere(ne)[:4].tolist())
 
 
 def _cases(S, P, N, pages):
@@ -155,11 +113,6 @@ def test_quarter_turns_equal_the_plain_entry_with_the_matching_transform(wider):
         got = tr.assemble_warped(ts, _descs(rows), None, _warps([m] * B))
         _same_bits(got, tr.assemble(ts, _descs([r[:4] + (code,) + r[5:] for r in rows])), (m, code, S))
     tr.close()
-
-
-def _state(tr):
-    m, v = tr.slots()
-    return tr.blob().tobytes(), m.tobytes(), v.tobytes()
 
 
 def _step_pair(hp, blob, opts, B, planes, ann, wmaps, lw, table, batches, with_aug):

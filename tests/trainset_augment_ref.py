@@ -1,5 +1,5 @@
-"""numpy restatement of assemble_augmented_kernel (unmicst_amd/csrc/umx_trainset.hip): per image and channel
-page plane -> separable Gaussian blur -> saturation -> crop + dihedral transform -> jitter.  Every product and every sum is its own
+"""numpy restatement of assemble_augmented_kernel (unmicst_amd/csrc/umx_trainset_assemble.hip): per image and
+channel page plane -> separable Gaussian blur -> saturation -> crop + dihedral transform -> jitter.  Every product and every sum is its own
 float64 rounding, in the kernel's order, so the device result must equal this bit for bit.  Labels, weights and every image with
 (level 0, gain 1) come from tests/trainset_ref.py unchanged."""
 import numpy as np

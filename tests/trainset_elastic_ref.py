@@ -1,5 +1,5 @@
-"""numpy restatement of the elastic deformation path (assemble_augmented_kernel<true, true> and assemble_elastic_labels_kernel of
-unmicst_amd/csrc/umx_trainset.hip; include/umx_train.h and DESIGN.md section 9.2, "Elastic deformation"): per image and channel
+"""numpy restatement of the elastic deformation path (assemble_augmented_kernel<true, true> and assemble_resampled_labels_kernel<ElasticChunk>
+of unmicst_amd/csrc/umx_trainset_assemble.hip; include/umx_train.h and DESIGN.md section 9.2, "Elastic deformation"): per image and channel
 page plane -> elastic + warp (one resampling) -> blur -> saturation -> crop orientation + dihedral transform -> jitter, and labels /
 weights from the nearest source pixel.  Every product, sum, division and floor is its own float64 rounding, in the kernel's order, so
 the device result must equal this bit for bit.  Images without a lattice (n == 0) come from tests/trainset_warp_ref.py unchanged."""

@@ -1,4 +1,5 @@
-"""numpy restatement of the two training-set kernels (unmicst_amd/csrc/umx_trainset.hip).
+"""numpy restatement of the two training-set kernels (assemble_batch_kernel of unmicst_amd/csrc/umx_trainset_assemble.hip and
+class_counts_kernel of unmicst_amd/csrc/umx_trainset.hip).
 
 ``assemble`` is what assemble_batch_kernel writes for a list of descriptors; the device result must equal it bit for bit (float64
 product and sum, one rounding -- numpy does not fuse them).  ``class_counts`` is class_counts_kernel on host arrays."""

@@ -1,5 +1,5 @@
-"""numpy restatement of the rotation / zoom path (assemble_augmented_kernel<true> and assemble_warped_labels_kernel of
-unmicst_amd/csrc/umx_trainset.hip; include/umx_train.h and DESIGN.md section 9.2, "Rotation and zoom"): per image and channel
+"""numpy restatement of the rotation / zoom path (assemble_augmented_kernel<true> and assemble_resampled_labels_kernel<AugChunk> of
+unmicst_amd/csrc/umx_trainset_assemble.hip; include/umx_train.h and DESIGN.md section 9.2, "Rotation and zoom"): per image and channel
 page plane -> warp -> blur -> saturation -> crop orientation + dihedral transform -> jitter, and labels / weights from the nearest
 source pixel.  Every product, sum, division and floor is its own float64 rounding, in the kernel's order, so the device result must
 equal this bit for bit.  Images whose warp is the identity come from tests/trainset_augment_ref.py (or trainset_ref.py) unchanged."""

@@ -376,7 +376,7 @@ int trainer_eval_end(umx_trainer* tr);
 // guard mode: wait for every stream of the trainer, then check its red zones (UMX_OK when the mode is off)
 int trainer_guard_check(umx_trainer* tr);
 
-// ---- training-set kernels (umx_trainset.hip) ----
+// ---- training-set kernels (assembly: umx_trainset_assemble.hip; class counts: umx_trainset.hip) ----
 constexpr int kDescChunk = 64;         // descriptors per assembly launch (passed by value: 2 KiB of kernel arguments)
 struct DescChunk { umx_sample_desc d[kDescChunk]; };
 struct TrainSetView {                  // device layout of one training set
@@ -402,12 +402,8 @@ struct AugImage {
 struct AugChunk { AugImage im[kAugChunk]; };
 hipError_t launch_assemble_augmented(const TrainSetView& ts, const AugChunk& ac, int m, int P, float mean, float std, float* data,
                                      hipStream_t stream);
-// the same for images with a rotation / zoom (umx_warp_desc, never the identity): the data planes resampled, then blur, saturation,
-// transform and jitter as above, and their labels / weights (null: none) from the nearest source pixel.  Needs ts.S >= 2.
-hipError_t launch_assemble_warped(const TrainSetView& ts, const AugChunk& ac, int m, int P, int K, float mean, float std, float* data,
-                                  float* labels, float* weights, hipStream_t stream);
-// the same for images with an elastic deformation (umx_elastic_desc, n != 0): the lattice rides behind the image's other arguments;
-// im.m is always read (the identity for an image without a rotation / zoom).  Needs ts.S >= 2 and P >= 2.
+// an image with an elastic deformation (umx_elastic_desc, n != 0): the lattice rides behind the image's other arguments; a.m is
+// always read (the identity for an image without a rotation / zoom)
 constexpr int kElasticChunk = 8;       // such images per launch (passed by value: 3.2 KiB of the 4 KiB a launch may carry)
 struct ElasticImage {
     AugImage a;
@@ -415,8 +411,12 @@ struct ElasticImage {
     float d[2][UMX_ELASTIC_MAX_GRID][UMX_ELASTIC_MAX_GRID];
 };
 struct ElasticChunk { ElasticImage im[kElasticChunk]; };
-hipError_t launch_assemble_elastic(const TrainSetView& ts, const ElasticChunk& ec, int m, int P, int K, float mean, float std, float* data,
-                                   float* labels, float* weights, hipStream_t stream);
+// the same for images with a rotation / zoom (Chunk = AugChunk: umx_warp_desc, never the identity) or an elastic deformation (Chunk =
+// ElasticChunk): the data planes resampled, then blur, saturation, transform and jitter as above, and their labels / weights (null:
+// none) from the nearest source pixel.  Needs ts.S >= 2, and P >= 2 under a lattice.  Instantiated for these two chunk types.
+template <typename Chunk>
+hipError_t launch_assemble_resampled(const TrainSetView& ts, const Chunk& ch, int m, int P, int K, float mean, float std, float* data,
+                                     float* labels, float* weights, hipStream_t stream);
 // counts [2K] int64 (correct | labelled) and loss [1] double over npix pixels of probs / labels [npix, K]; part: class_counts_parts(npix)
 // doubles of workspace
 size_t class_counts_parts(size_t npix, int K);

@@ -1,23 +1,14 @@
-// libumx device-resident training set: storage, the two kernels that feed the training step from it, and the C ABI of the
-// umx_trainset_* / umx_train_step_sampled / _augmented / _warped / _elastic / umx_trainer_assemble / _augmented / _warped / _elastic /
-// umx_trainer_evaluate / _evaluate_objects / umx_trainer_object_counts / umx_trainset_border_weights / _border_planes entries of
-// include/umx_train.h (the kernels of the border maps: umx_trainset_border.hip; of the object score: umx_trainset_objects.hip).
+// libumx device-resident training set: storage, the host checks, the chunking of a batch into launches, the validation counts and the
+// C ABI of the umx_trainset_* / umx_train_step_sampled / _augmented / _warped / _elastic / umx_trainer_assemble / _augmented / _warped /
+// _elastic / umx_trainer_evaluate / _evaluate_objects / umx_trainer_object_counts / umx_trainset_border_weights / _border_planes entries
+// of include/umx_train.h (the assembly kernels and their launchers: umx_trainset_assemble.hip; the kernels of the border maps:
+// umx_trainset_border.hip; of the object score: umx_trainset_objects.hip).
 //
 // The set is the reference's annotated layout (I%05d_Img.tif pages, _Ant.tif class codes, _wt.tif contour-intersection map;
 // UnMicst1-5.py:295-312, UnMicst2.py:293-309, UnMicst.py:236-243) uploaded once, already normalised.  A step then costs 32 bytes
 // of descriptors per image (passed as kernel arguments) and one small kernel that writes the step's own data / labels / weights
 // buffers; the validation pass reduces the eval-mode softmax to exact per-class counts on the device.  DESIGN.md section 9.2.
 //
-//   assemble_batch_kernel  data[b,y,x,c] = float32((double)v * contrast + brightness) at the transformed crop coordinate;
-//                          labels[b,y,x,k] = (code == k+1); weights[b,y,x,k] = float32((double)iw[k] * wmap + cw[k])
-//   assemble_augmented_kernel  the data planes of the images that ask for a blur level or a saturation gain (umx_augment_desc):
-//                          page plane -> separable Gaussian blur -> saturation -> crop + transform -> jitter, float64 in a fixed order
-//   assemble_augmented_kernel<true>  the same for the images with a rotation / zoom (umx_warp_desc): the window is resampled
-//                          (mirror fold, bilinear, float64 in a fixed order) instead of copied
-//   assemble_warped_labels_kernel  their labels and weights, from the nearest source pixel
-//   assemble_augmented_kernel<true, true>  the images with an elastic deformation (umx_elastic_desc): the B-spline displacement of the
-//                          lattice is added to the pixel's coordinate in front of the warp matrix; one resampling
-//   assemble_elastic_labels_kernel  their labels and weights, from the nearest source pixel
 //   class_counts_kernel    per block: correct / labelled per class (int64) and sum of -log p[label] (float64), fixed order;
 //   class_counts_final     one block sums the block partials in a fixed order
 #include "../../include/umx_train.h"
@@ -34,18 +25,11 @@ using namespace umx;
 
 static_assert(sizeof(umx_sample_desc) == 32, "umx_sample_desc is 32 bytes");
 static_assert(sizeof(umx_label_weights) == 4 + 8 * 4 + 8 * 4 + 7 * 4, "umx_label_weights layout");
-static_assert(sizeof(DescChunk) <= 2048, "a descriptor chunk travels as kernel arguments");
 static_assert(sizeof(umx_augment_desc) == 8, "umx_augment_desc is 8 bytes");
 static_assert(sizeof(umx_augment_table) == 12 + 16 * 4 + 16 * 13 * 4 + 5 * 4, "umx_augment_table layout");
-static_assert(sizeof(AugChunk) <= 2048, "a chunk of augmented images travels as kernel arguments");
 static_assert(sizeof(umx_warp_desc) == 16, "umx_warp_desc is 16 bytes");
-static_assert(sizeof(AugImage) == 112, "an augmented image is 112 bytes of kernel arguments");
 static_assert(sizeof(umx_elastic_desc) == 304, "umx_elastic_desc is 304 bytes");
 static_assert(sizeof(umx_object_options) == 32, "umx_object_options is 32 bytes");
-static_assert(sizeof(ElasticImage) == 404, "an elastic image is 404 bytes of kernel arguments");
-// the widest launch: TrainSetView, the chunk, P, K (or mean, std) and up to two pointers -- inside the 4 KB of arguments a launch may carry
-static_assert(sizeof(TrainSetView) + sizeof(ElasticChunk) + 2 * sizeof(float) + 8 + 2 * sizeof(void*) <= 4096,
-              "a chunk of elastic images travels as kernel arguments");
 
 struct umx_trainset {
     umx_trainer* tr = nullptr;
@@ -73,326 +57,6 @@ namespace {
 constexpr int kCountThreads = 256;
 constexpr int kMaxClasses = 8;       // umx_trainer_create: nClasses 2..8
 constexpr int kMaxCountBlocks = 1024;
-
-// float32(a * b + c) with the product and the sum rounded in float64, never fused into one fma (HIP's __dmul_rn / __dadd_rn are plain
-// operators that the default -ffp-contract=fast fuses): what numpy computes for (a * b + c).astype(float32) on float64 operands
-__device__ inline float mul_add_f64_rn(double a, double b, double c) {
-#pragma clang fp contract(off)
-    return (float)(a * b + c);
-}
-
-// one thread per output pixel (y, x) of image blockIdx.y of the chunk; every thread writes its C data, K label and K weight
-// values, so a wave stores one contiguous run of the NHWC outputs.  The source pixel is read through L2: a transform that swaps
-// the axes reads a column of the crop per wave (S floats apart), which at these sizes (a few MB per step) is not worth an LDS
-// transpose.
-__global__ void __launch_bounds__(256) assemble_batch_kernel(TrainSetView ts, DescChunk dc, int b0, int P, int K,
-                                                             float* __restrict__ data, float* __restrict__ labels,
-                                                             float* __restrict__ weights) {
-    const int j = blockIdx.y;
-    const int pix = blockIdx.x * 256 + threadIdx.x;
-    if (pix >= P * P) return;
-    const umx_sample_desc d = dc.d[j];
-    const size_t o = (size_t)(b0 + j) * P * P + pix;
-    float* dp = data + o * ts.C;
-    float* lp = labels + o * K;
-    float* wp = weights ? weights + o * K : nullptr;
-    if (d.index < 0) {   // padding row
-        for (int c = 0; c < ts.C; ++c) dp[c] = 0.f;
-        for (int k = 0; k < K; ++k) lp[k] = 0.f;
-        if (wp)
-            for (int k = 0; k < K; ++k) wp[k] = 0.f;
-        return;
-    }
-    const int y = pix / P, x = pix - (pix / P) * P;
-    // the dihedral transform of the P x P crop: bit 2 swaps the axes, then bit 1 flips the rows, then bit 0 flips the columns;
-    // out[y, x] therefore reads crop[sy, sx] with (u, v) = (flipped y, flipped x) and (sy, sx) = swap ? (v, u) : (u, v)
-    const int u = (d.transform & 2) ? P - 1 - y : y;
-    const int v = (d.transform & 1) ? P - 1 - x : x;
-    const int sy = d.y0 + ((d.transform & 4) ? v : u);
-    const int sx = d.x0 + ((d.transform & 4) ? u : v);
-    const size_t plane = (size_t)ts.S * ts.row_f;
-    const float* src = ts.planes + ((size_t)d.index * ts.C * ts.pages + d.page) * plane + (size_t)sy * ts.row_f + sx;
-    const double cont = (double)d.contrast, brig = (double)d.brightness;
-    // float64 product and sum, one rounding to float32 (the reference jitters its float64 arrays, UnMicst1-5.py:473-477)
-    for (int c = 0; c < ts.C; ++c) dp[c] = mul_add_f64_rn((double)src[(size_t)c * ts.pages * plane], cont, brig);
-    const int code = ts.ann[((size_t)d.index * ts.S + sy) * ts.row_a + sx];
-    for (int k = 0; k < K; ++k) lp[k] = code == k + 1 ? 1.f : 0.f;   // (im == i + 1), UnMicst1-5.py:306
-    if (wp) {
-        const double w = (double)ts.wmap[((size_t)d.index * ts.S + sy) * ts.row_f + sx];
-        for (int k = 0; k < K; ++k)   // W * intersectWeight + classWeight, UnMicst1-5.py:307-312
-            wp[k] = mul_add_f64_rn((double)ts.iw[k], w, (double)ts.cw[k]);
-    }
-}
-
-constexpr int kAugTile = 32;                                         // output tile of one workgroup, in crop orientation
-constexpr int kAugWin = kAugTile + 2 * UMX_AUGMENT_MAX_RADIUS;       // its source window at the largest radius
-constexpr int kAugHStride = kAugTile + 1;                            // (odd: a wave may walk a column of `hor` without bank conflicts)
-
-// float32(sum over t = -R..R, ascending, of w[|t|] * p[t]); p points at t = -R.  The sum starts at 0.0 and every product and every
-// sum is rounded in float64 on its own, as numpy does it tap by tap.
-__device__ inline float blur_taps(const float* p, int stride, int R, const double* w) {
-#pragma clang fp contract(off)
-    double acc = 0.0;
-    for (int t = -R; t <= R; ++t) acc = acc + w[t < 0 ? -t : t] * (double)p[(t + R) * stride];
-    return (float)acc;
-}
-
-// back to the im2double scale, amplified, clipped at 1 (np.minimum: a NaN stays), normalised again; one rounding per operation
-__device__ inline float saturate_f64_rn(float b, double gain, double mean, double std) {
-#pragma clang fp contract(off)
-    const double r = (double)b * std + mean;
-    const double rg = r * gain;
-    const double r2 = rg > 1.0 ? 1.0 : rg;
-    return (float)((r2 - mean) / std);
-}
-
-// a source coordinate mirrored into 0 .. S-1 about the centres of the sample's edge pixels (d c b | a b c d | c b a), S >= 2.  A
-// quotient that rounds up to the next integer leaves t a hair below 0: that is the edge pixel.
-__device__ inline double warp_fold(double s, int S) {
-#pragma clang fp contract(off)
-    const double T = 2.0 * (double)(S - 1);
-    const double q = floor(s / T);
-    double t = s - T * q;
-    if (t > (double)(S - 1)) t = T - t;
-    return t < 0.0 ? 0.0 : t;
-}
-
-// where pixel (y, x) of the crop's own grid (any integer, also outside 0 .. P-1) lies in the sample: M (y - c, x - c) + the crop's
-// centre, folded.  Every product and every sum is rounded in float64 on its own.
-__device__ inline void warp_source(const float* m, int y, int x, int P, int y0, int x0, int S, double* ty, double* tx) {
-#pragma clang fp contract(off)
-    const double c = 0.5 * (double)(P - 1);
-    const double dy = (double)y - c, dx = (double)x - c;
-    *ty = warp_fold(((double)m[0] * dy + (double)m[1] * dx) + ((double)y0 + c), S);
-    *tx = warp_fold(((double)m[2] * dy + (double)m[3] * dx) + ((double)x0 + c), S);
-}
-
-// bilinear value of a sample plane at a folded coordinate: along the row first, then between the two rows, one float32 rounding
-__device__ inline float warp_bilinear(const float* plane, int row_f, int S, double ty, double tx) {
-#pragma clang fp contract(off)
-    const int iy = min(max((int)ty, 0), S - 1), ix = min(max((int)tx, 0), S - 1);   // (0 <= t <= S-1: truncation is floor; the clamp is for a NaN)
-    const double fy = ty - (double)iy, fx = tx - (double)ix;
-    const int iy1 = min(iy + 1, S - 1), ix1 = min(ix + 1, S - 1);
-    const float* r0 = plane + (size_t)iy * row_f;
-    const float* r1 = plane + (size_t)iy1 * row_f;
-    const double gx = 1.0 - fx;
-    const double top = gx * (double)r0[ix] + fx * (double)r0[ix1];
-    const double bot = gx * (double)r1[ix] + fx * (double)r1[ix1];
-    return (float)((1.0 - fy) * top + fy * bot);
-}
-
-// the nearest source pixel of a folded coordinate (labels and weight maps are never interpolated)
-__device__ inline int warp_nearest(double t, int S) {
-#pragma clang fp contract(off)
-    return min(max((int)(t + 0.5), 0), S - 1);
-}
-
-// six times the uniform cubic B-spline's weights at integer coordinate t of an axis of the crop's grid (recipe 0a of umx_elastic_desc):
-// n - 3 spline cells across 0 .. P-1, a coordinate outside the crop clamped to its edge.  *i0: the first of the 4 lattice points.
-__device__ inline void elastic_weights(int t, int P, int n, double* W, int* i0) {
-#pragma clang fp contract(off)
-    const double tc = (double)min(max(t, 0), P - 1);
-    const double scale = (double)(n - 3) / (double)(P - 1);
-    const double u = tc * scale;
-    const int i = min(max((int)u, 0), n - 4);   // (u >= 0: truncation is floor; the lower clamp is for a NaN)
-    const double f = u - (double)i;
-    const double g = 1.0 - f, f2 = f * f, f3 = f2 * f;
-    W[0] = (g * g) * g;
-    W[1] = (3.0 * f3 - 6.0 * f2) + 4.0;
-    W[2] = ((-3.0 * f3 + 3.0 * f2) + 3.0 * f) + 1.0;
-    W[3] = f3;
-    *i0 = i;
-}
-
-// one component of the displacement (recipe 0b): D the component's 6 x 6 lattice, along the lattice rows first, then between them
-__device__ inline double elastic_disp(const double* D, const double* Wy, int iy, const double* Wx, int ix) {
-#pragma clang fp contract(off)
-    double row[4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        const double* r = D + (iy + a) * UMX_ELASTIC_MAX_GRID + ix;
-        row[a] = ((Wx[0] * r[0] + Wx[1] * r[1]) + Wx[2] * r[2]) + Wx[3] * r[3];
-    }
-    return (((Wy[0] * row[0] + Wy[1] * row[1]) + Wy[2] * row[2]) + Wy[3] * row[3]) / 36.0;
-}
-
-// warp_source for a pixel displaced by (ey, ex) on the crop's own grid (recipe 1')
-__device__ inline void elastic_source(const float* m, int y, int x, double ey, double ex, int P, int y0, int x0, int S, double* ty,
-                                      double* tx) {
-#pragma clang fp contract(off)
-    const double c = 0.5 * (double)(P - 1);
-    const double dy = ((double)y + ey) - c, dx = ((double)x + ex) - c;
-    *ty = warp_fold(((double)m[0] * dy + (double)m[1] * dx) + ((double)y0 + c), S);
-    *tx = warp_fold(((double)m[2] * dy + (double)m[3] * dx) + ((double)x0 + c), S);
-}
-
-// the kernels' argument types: an image's lattice rides behind its AugImage
-template <bool kElastic> struct ChunkOf { using type = AugChunk; };
-template <> struct ChunkOf<true> { using type = ElasticChunk; };
-__device__ inline const AugImage& aug_image(const AugChunk& c, unsigned j) { return c.im[j]; }
-__device__ inline const AugImage& aug_image(const ElasticChunk& c, unsigned j) { return c.im[j].a; }
-
-// one workgroup per (32 x 32 tile of the crop, channel, image).  The (32 + 2R)^2 source window goes to LDS with both coordinates
-// clamped to the sample, so a crop at the sample's edge sees the replicated edge and a crop inside it its real neighbours; the row pass
-// writes `hor` (float32, the rounding the recipe asks for), the column pass reads it.  A wave owns one row of the tile -- or, under a
-// transform that swaps the axes, one column, so that its 32 stores are neighbours in the NHWC output either way.
-// kWarp: every window element is resampled from the plane instead (im.m: rotation and zoom about the crop's centre).  The warped
-// image exists at every integer coordinate, so the window needs no clamp; without a blur each thread resamples its own pixel.
-// kElastic (with kWarp): the source coordinate of a window element also takes the lattice's displacement.  The spline weights depend on
-// the integer coordinate alone, so the workgroup computes those of its window's rows and of its columns once (2 (32 + 2R) sets), next to
-// the lattice as float64, and an element combines them with 16 lattice values per component.
-template <bool kWarp, bool kElastic = false>
-__global__ void __launch_bounds__(256) assemble_augmented_kernel(TrainSetView ts, typename ChunkOf<kElastic>::type ac, int P, float mean,
-                                                                 float std, float* __restrict__ data) {
-    static_assert(kWarp || !kElastic, "the elastic displacement is a term of the warp's source coordinate");
-    __shared__ float win[kAugWin * kAugWin];
-    __shared__ float hor[kAugWin * kAugHStride];
-    __shared__ double w64[UMX_AUGMENT_MAX_RADIUS + 1];
-    __shared__ double lat64[kElastic ? 2 * UMX_ELASTIC_MAX_GRID * UMX_ELASTIC_MAX_GRID : 1];
-    __shared__ double ew64[kElastic ? 2 * kAugWin * 4 : 1];   // [axis][window row resp. column][4]
-    __shared__ int ei[kElastic ? 2 * kAugWin : 1];            // the first lattice point of each
-    const AugImage& im = aug_image(ac, blockIdx.z);
-    const umx_sample_desc d = im.d;
-    const int c = blockIdx.y;
-    const int tiles = (P + kAugTile - 1) / kAugTile;
-    const int cy0 = (blockIdx.x / tiles) * kAugTile, cx0 = (blockIdx.x % tiles) * kAugTile;
-    const int lane = threadIdx.x & 31, grp = threadIdx.x >> 5;
-    const int R = im.R;
-    const bool swap = (d.transform & 4) != 0;
-    const float* src = ts.planes + (((size_t)d.index * ts.C + c) * ts.pages + d.page) * ((size_t)ts.S * ts.row_f);
-    [[maybe_unused]] const int halo = R >= 0 ? R : 0;    // (the elastic tables: window element (r, q) is pixel (cy0 - halo + r, cx0 - halo + q))
-    if constexpr (kElastic) {
-        const ElasticImage& el = ac.im[blockIdx.z];
-        const int W = kAugTile + 2 * halo;
-        const int n = min(max(el.n, 4), UMX_ELASTIC_MAX_GRID);
-        constexpr int kLat = 2 * UMX_ELASTIC_MAX_GRID * UMX_ELASTIC_MAX_GRID;
-        if ((int)threadIdx.x < kLat) lat64[threadIdx.x] = (double)(&el.d[0][0][0])[threadIdx.x];
-        if ((int)threadIdx.x < 2 * W) {
-            const int axis = (int)threadIdx.x >= W, r = (int)threadIdx.x - axis * W;
-            elastic_weights((axis ? cx0 : cy0) - halo + r, P, n, &ew64[(axis * kAugWin + r) * 4], &ei[axis * kAugWin + r]);
-        }
-        __syncthreads();
-    }
-    // the source of window element (r, q) under the lattice, from the tables above
-    [[maybe_unused]] auto displaced = [&](int r, int q, double* ty, double* tx) {
-        if constexpr (kElastic) {
-            const double* wy = &ew64[r * 4];
-            const double* wx = &ew64[(kAugWin + q) * 4];
-            const int iy = ei[r], ix = ei[kAugWin + q];
-            const double ey = elastic_disp(lat64, wy, iy, wx, ix);
-            const double ex = elastic_disp(lat64 + UMX_ELASTIC_MAX_GRID * UMX_ELASTIC_MAX_GRID, wy, iy, wx, ix);
-            elastic_source(im.m, cy0 - halo + r, cx0 - halo + q, ey, ex, P, d.y0, d.x0, ts.S, ty, tx);
-        }
-    };
-    if (R >= 0) {
-        const int W = kAugTile + 2 * R;
-        for (int r = grp; r < W; r += 8) {
-            for (int q = lane; q < W; q += 32) {
-                if constexpr (kElastic) {
-                    double ty, tx;
-                    displaced(r, q, &ty, &tx);
-                    win[r * W + q] = warp_bilinear(src, ts.row_f, ts.S, ty, tx);
-                } else if constexpr (kWarp) {
-                    double ty, tx;
-                    warp_source(im.m, cy0 - R + r, cx0 - R + q, P, d.y0, d.x0, ts.S, &ty, &tx);
-                    win[r * W + q] = warp_bilinear(src, ts.row_f, ts.S, ty, tx);
-                } else {
-                    const int sy = min(max(d.y0 + cy0 - R + r, 0), ts.S - 1);
-                    const int sx = min(max(d.x0 + cx0 - R + q, 0), ts.S - 1);
-                    win[r * W + q] = src[(size_t)sy * ts.row_f + sx];
-                }
-            }
-        }
-        if ((int)threadIdx.x <= R) w64[threadIdx.x] = (double)im.taps[threadIdx.x];
-        __syncthreads();
-        for (int r = grp; r < W; r += 8) hor[r * kAugHStride + lane] = blur_taps(&win[r * W + lane], 1, R, w64);
-        __syncthreads();
-    }
-    const double gain = (double)im.gain, cont = (double)d.contrast, brig = (double)d.brightness;
-    for (int i = 0; i < kAugTile / 8; ++i) {
-        const int yy = swap ? lane : grp + 8 * i, xx = swap ? grp + 8 * i : lane;   // pixel of the tile, crop orientation
-        const int cy = cy0 + yy, cx = cx0 + xx;
-        if (cy >= P || cx >= P) continue;
-        float v;
-        if (R >= 0) {
-            v = blur_taps(&hor[yy * kAugHStride + xx], kAugHStride, R, w64);
-        } else if constexpr (kElastic) {
-            double ty, tx;
-            displaced(yy, xx, &ty, &tx);
-            v = warp_bilinear(src, ts.row_f, ts.S, ty, tx);
-        } else if constexpr (kWarp) {
-            double ty, tx;
-            warp_source(im.m, cy, cx, P, d.y0, d.x0, ts.S, &ty, &tx);
-            v = warp_bilinear(src, ts.row_f, ts.S, ty, tx);
-        } else {
-            v = src[(size_t)(d.y0 + cy) * ts.row_f + d.x0 + cx];
-        }
-        if (im.gain != 1.f) v = saturate_f64_rn(v, gain, (double)mean, (double)std);
-        // where assemble_batch_kernel's out[y, x] reads crop[cy, cx]: the inverse of its map
-        const int u = swap ? cx : cy, w = swap ? cy : cx;
-        const int y = (d.transform & 2) ? P - 1 - u : u;
-        const int x = (d.transform & 1) ? P - 1 - w : w;
-        data[(((size_t)im.row * P + y) * P + x) * ts.C + c] = mul_add_f64_rn((double)v, cont, brig);
-    }
-}
-
-// labels and weights of the warped images, written over what assemble_batch_kernel wrote: one thread per output pixel, its K values
-// each, as there.  The pixel's place in the crop is that kernel's map; its label and its weight come from the one source pixel
-// nearest to the warped coordinate.
-__global__ void __launch_bounds__(256) assemble_warped_labels_kernel(TrainSetView ts, AugChunk ac, int P, int K,
-                                                                     float* __restrict__ labels, float* __restrict__ weights) {
-    const int pix = blockIdx.x * 256 + threadIdx.x;
-    if (pix >= P * P) return;
-    const AugImage& im = ac.im[blockIdx.y];
-    const umx_sample_desc d = im.d;
-    const int y = pix / P, x = pix - (pix / P) * P;
-    const int u = (d.transform & 2) ? P - 1 - y : y;
-    const int v = (d.transform & 1) ? P - 1 - x : x;
-    double ty, tx;
-    warp_source(im.m, (d.transform & 4) ? v : u, (d.transform & 4) ? u : v, P, d.y0, d.x0, ts.S, &ty, &tx);
-    const int sy = warp_nearest(ty, ts.S), sx = warp_nearest(tx, ts.S);
-    const size_t o = ((size_t)im.row * P * P + pix) * K;
-    const int code = ts.ann[((size_t)d.index * ts.S + sy) * ts.row_a + sx];
-    for (int k = 0; k < K; ++k) labels[o + k] = code == k + 1 ? 1.f : 0.f;
-    if (weights) {
-        const double w = (double)ts.wmap[((size_t)d.index * ts.S + sy) * ts.row_f + sx];
-        for (int k = 0; k < K; ++k) weights[o + k] = mul_add_f64_rn((double)ts.iw[k], w, (double)ts.cw[k]);
-    }
-}
-
-// the same for the images with an elastic deformation: the pixel's place in the crop is displaced by its lattice first.  A thread
-// computes the spline weights of its own row and column (once per pixel here, not once per window element and channel).
-__global__ void __launch_bounds__(256) assemble_elastic_labels_kernel(TrainSetView ts, ElasticChunk ec, int P, int K,
-                                                                      float* __restrict__ labels, float* __restrict__ weights) {
-    __shared__ double lat64[2 * UMX_ELASTIC_MAX_GRID * UMX_ELASTIC_MAX_GRID];
-    const ElasticImage& el = ec.im[blockIdx.y];
-    const AugImage& im = el.a;
-    if ((int)threadIdx.x < 2 * UMX_ELASTIC_MAX_GRID * UMX_ELASTIC_MAX_GRID) lat64[threadIdx.x] = (double)(&el.d[0][0][0])[threadIdx.x];
-    __syncthreads();
-    const int pix = blockIdx.x * 256 + threadIdx.x;
-    if (pix >= P * P) return;
-    const umx_sample_desc d = im.d;
-    const int n = min(max(el.n, 4), UMX_ELASTIC_MAX_GRID);
-    const int y = pix / P, x = pix - (pix / P) * P;
-    const int u = (d.transform & 2) ? P - 1 - y : y;
-    const int v = (d.transform & 1) ? P - 1 - x : x;
-    const int cy = (d.transform & 4) ? v : u, cx = (d.transform & 4) ? u : v;
-    double wy[4], wx[4], ty, tx;
-    int iy, ix;
-    elastic_weights(cy, P, n, wy, &iy);
-    elastic_weights(cx, P, n, wx, &ix);
-    const double ey = elastic_disp(lat64, wy, iy, wx, ix);
-    const double ex = elastic_disp(lat64 + UMX_ELASTIC_MAX_GRID * UMX_ELASTIC_MAX_GRID, wy, iy, wx, ix);
-    elastic_source(im.m, cy, cx, ey, ex, P, d.y0, d.x0, ts.S, &ty, &tx);
-    const int sy = warp_nearest(ty, ts.S), sx = warp_nearest(tx, ts.S);
-    const size_t o = ((size_t)im.row * P * P + pix) * K;
-    const int code = ts.ann[((size_t)d.index * ts.S + sy) * ts.row_a + sx];
-    for (int k = 0; k < K; ++k) labels[o + k] = code == k + 1 ? 1.f : 0.f;
-    if (weights) {
-        const double w = (double)ts.wmap[((size_t)d.index * ts.S + sy) * ts.row_f + sx];
-        for (int k = 0; k < K; ++k) weights[o + k] = mul_add_f64_rn((double)ts.iw[k], w, (double)ts.cw[k]);
-    }
-}
 
 int count_blocks(size_t npix) {
     const size_t per = (size_t)kCountThreads * 8;
@@ -468,53 +132,6 @@ __global__ void __launch_bounds__(kCountThreads) class_counts_final(const double
 }
 
 }  // namespace
-
-hipError_t launch_assemble_batch(const TrainSetView& ts, const DescChunk& dc, int m, int b0, int P, int K, float* data, float* labels,
-                                 float* weights, hipStream_t stream) {
-    if (m < 1 || m > kDescChunk || K < 1 || K > 8) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(assemble_batch_kernel, dim3((unsigned)((P * P + 255) / 256), (unsigned)m), dim3(256), 0, stream, ts, dc, b0, P, K,
-                       data, labels, weights);
-    return hipGetLastError();
-}
-
-hipError_t launch_assemble_augmented(const TrainSetView& ts, const AugChunk& ac, int m, int P, float mean, float std, float* data,
-                                     hipStream_t stream) {
-    if (m < 1 || m > kAugChunk || P < 1) return hipErrorInvalidValue;
-    for (int j = 0; j < m; ++j)
-        if (ac.im[j].R < -1 || ac.im[j].R > UMX_AUGMENT_MAX_RADIUS) return hipErrorInvalidValue;   // (the LDS window is sized for 12)
-    const unsigned tiles = (unsigned)((P + kAugTile - 1) / kAugTile);
-    hipLaunchKernelGGL(assemble_augmented_kernel<false>, dim3(tiles * tiles, (unsigned)ts.C, (unsigned)m), dim3(256), 0, stream, ts, ac, P,
-                       mean, std, data);
-    return hipGetLastError();
-}
-
-hipError_t launch_assemble_warped(const TrainSetView& ts, const AugChunk& ac, int m, int P, int K, float mean, float std, float* data,
-                                  float* labels, float* weights, hipStream_t stream) {
-    if (m < 1 || m > kAugChunk || P < 1 || K < 1 || K > 8 || ts.S < 2) return hipErrorInvalidValue;   // (S = 1 has no mirror period)
-    for (int j = 0; j < m; ++j)
-        if (ac.im[j].R < -1 || ac.im[j].R > UMX_AUGMENT_MAX_RADIUS) return hipErrorInvalidValue;
-    const unsigned tiles = (unsigned)((P + kAugTile - 1) / kAugTile);
-    hipLaunchKernelGGL(assemble_augmented_kernel<true>, dim3(tiles * tiles, (unsigned)ts.C, (unsigned)m), dim3(256), 0, stream, ts, ac, P,
-                       mean, std, data);
-    hipLaunchKernelGGL(assemble_warped_labels_kernel, dim3((unsigned)((P * P + 255) / 256), (unsigned)m), dim3(256), 0, stream, ts, ac, P, K,
-                       labels, weights);
-    return hipGetLastError();
-}
-
-hipError_t launch_assemble_elastic(const TrainSetView& ts, const ElasticChunk& ec, int m, int P, int K, float mean, float std, float* data,
-                                   float* labels, float* weights, hipStream_t stream) {
-    if (m < 1 || m > kElasticChunk || P < 2 || K < 1 || K > 8 || ts.S < 2) return hipErrorInvalidValue;   // (P = 1 has no spline cell)
-    for (int j = 0; j < m; ++j) {
-        if (ec.im[j].a.R < -1 || ec.im[j].a.R > UMX_AUGMENT_MAX_RADIUS) return hipErrorInvalidValue;
-        if (ec.im[j].n < 4 || ec.im[j].n > UMX_ELASTIC_MAX_GRID) return hipErrorInvalidValue;             // (the LDS lattice is 6 x 6)
-    }
-    const unsigned tiles = (unsigned)((P + kAugTile - 1) / kAugTile);
-    hipLaunchKernelGGL((assemble_augmented_kernel<true, true>), dim3(tiles * tiles, (unsigned)ts.C, (unsigned)m), dim3(256), 0, stream, ts,
-                       ec, P, mean, std, data);
-    hipLaunchKernelGGL(assemble_elastic_labels_kernel, dim3((unsigned)((P * P + 255) / 256), (unsigned)m), dim3(256), 0, stream, ts, ec, P,
-                       K, labels, weights);
-    return hipGetLastError();
-}
 
 size_t class_counts_parts(size_t npix, int K) { return (size_t)count_blocks(npix) * (2 * K + 1); }
 
@@ -617,10 +234,6 @@ int enqueue_assemble(umx_trainer* tr, const umx_trainset* ts, const umx_sample_d
     return UMX_OK;
 }
 
-// which entry a batch came in by: plain descriptors, + umx_augment_desc, + umx_warp_desc (there aug may be null: no blur, gain 1),
-// + umx_elastic_desc (there warp may be null too: the identity)
-enum Entry { kSampled, kAugmented, kWarped, kElastic };
-
 // the parallel array of umx_augment_desc, checked like the descriptors: before anything is enqueued
 int check_augs(umx_trainer* tr, const umx_trainset* ts, const umx_augment_desc* aug, int n, const char* what) {
     if (!aug) return tsfail(tr, UMX_ERR_INVALID, "null argument");
@@ -656,14 +269,28 @@ int check_elastics(umx_trainer* tr, const umx_trainset* ts, const umx_elastic_de
     return UMX_OK;
 }
 
+// the parallel arrays an entry cannot do without: the one it is named for.  An array in front of that one may be null (aug: no blur,
+// gain 1; warp: the identity), and an entry passes null for the arrays behind it.
+enum : unsigned { kNeedsAug = 1, kNeedsWarp = 2, kNeedsElastic = 4 };
+
 // the checks of an entry, in the order descriptors, augmentations, warps, lattices; nothing is enqueued before all of them pass
 int check_batch(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug, const umx_warp_desc* warp,
-                const umx_elastic_desc* elastic, Entry entry, int n, int n_max, const char* what) {
+                const umx_elastic_desc* elastic, unsigned needs, int n, int n_max, const char* what) {
     TS_TRY(check_descs(tr, ts, desc, n, n_max, what));
-    if (entry == kAugmented || ((entry == kWarped || entry == kElastic) && aug)) TS_TRY(check_augs(tr, ts, aug, n, what));
-    if (entry == kWarped || (entry == kElastic && warp)) TS_TRY(check_warps(tr, ts, warp, n, what));
-    if (entry == kElastic) TS_TRY(check_elastics(tr, ts, elastic, n, what));
+    if (aug || (needs & kNeedsAug)) TS_TRY(check_augs(tr, ts, aug, n, what));
+    if (warp || (needs & kNeedsWarp)) TS_TRY(check_warps(tr, ts, warp, n, what));
+    if (elastic || (needs & kNeedsElastic)) TS_TRY(check_elastics(tr, ts, elastic, n, what));
     return UMX_OK;
+}
+
+// launch(chunk, m) once the chunk's m images fill it, or at the batch's last image if it holds any; the chunk is empty afterwards
+template <typename Chunk, typename Launch>
+hipError_t flush_chunk(Chunk& ch, int& m, bool last, Launch launch) {
+    if (m < (int)(sizeof ch.im / sizeof ch.im[0]) && !(m > 0 && last)) return hipSuccess;
+    const hipError_t e = launch(ch, m);
+    memset(&ch, 0, sizeof ch);
+    m = 0;
+    return e;
 }
 
 // enqueue_assemble for every image (labels, weights and the plain data: today's path), then, on the same stream, the images that ask
@@ -678,6 +305,11 @@ int enqueue_batch(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc
     const TrainerIO io = trainer_io(tr);
     const TrainSetView v = view_of(ts);
     const float mean = ts->has_aug ? ts->aug.mean : 0.f, std = ts->has_aug ? ts->aug.std : 1.f;   // (read only when a gain != 1)
+    float* const wts = weights ? io.weights : nullptr;
+    const auto data_only = [&](const AugChunk& c, int m) { return launch_assemble_augmented(v, c, m, io.P, mean, std, io.data, io.stream); };
+    const auto resampled = [&](const auto& c, int m) {
+        return launch_assemble_resampled(v, c, m, io.P, io.K, mean, std, io.data, io.labels, wts, io.stream);
+    };
     AugChunk chunk[2];   // [0] blur / gain only, [1] warped
     int m[2] = {0, 0};
     memset(chunk, 0, sizeof chunk);
@@ -701,31 +333,20 @@ int enqueue_batch(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc
             if (warped) memcpy(im.m, warp[i].m, sizeof im.m);
             else if (deformed) im.m[0] = im.m[3] = 1.f;
         }
-        if (me == kElasticChunk || (me > 0 && i == n - 1)) {
-            TS_HIP(tr, launch_assemble_elastic(v, ec, me, io.P, io.K, mean, std, io.data, io.labels, weights ? io.weights : nullptr,
-                                               io.stream));
-            memset(&ec, 0, sizeof ec);
-            me = 0;
-        }
-        for (int k = 0; k < 2; ++k)
-            if (m[k] == kAugChunk || (m[k] > 0 && i == n - 1)) {
-                if (k == 0) TS_HIP(tr, launch_assemble_augmented(v, chunk[0], m[0], io.P, mean, std, io.data, io.stream));
-                else
-                    TS_HIP(tr, launch_assemble_warped(v, chunk[1], m[1], io.P, io.K, mean, std, io.data, io.labels,
-                                                      weights ? io.weights : nullptr, io.stream));
-                memset(&chunk[k], 0, sizeof chunk[k]);
-                m[k] = 0;
-            }
+        const bool last = i == n - 1;
+        TS_HIP(tr, flush_chunk(ec, me, last, resampled));
+        TS_HIP(tr, flush_chunk(chunk[0], m[0], last, data_only));
+        TS_HIP(tr, flush_chunk(chunk[1], m[1], last, resampled));
     }
     return UMX_OK;
 }
 
 // umx_train_step_sampled / _augmented / _warped / _elastic
 int step_from_set(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
-                  const umx_warp_desc* warp, const umx_elastic_desc* elastic, Entry entry, int apply_update, const char* what) {
+                  const umx_warp_desc* warp, const umx_elastic_desc* elastic, unsigned needs, int apply_update, const char* what) {
     if (!tr) return tsfail(nullptr, UMX_ERR_INVALID, "null trainer");
     const TrainerIO io = trainer_io(tr);
-    TS_TRY(check_batch(tr, ts, desc, aug, warp, elastic, entry, io.B, io.B, what));
+    TS_TRY(check_batch(tr, ts, desc, aug, warp, elastic, needs, io.B, io.B, what));
     TS_HIP(tr, hipSetDevice(io.device));
     TS_TRY(enqueue_batch(tr, ts, desc, aug, warp, elastic, io.B, ts->weighted));
     TS_TRY(umx_train_step_dev(tr, io.data, io.labels, ts->weighted ? io.weights : nullptr, apply_update));   // (checks the trainer's zones)
@@ -736,11 +357,11 @@ int step_from_set(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc
 
 // umx_trainer_assemble / _augmented / _warped / _elastic
 int assemble_to_host(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
-                     const umx_warp_desc* warp, const umx_elastic_desc* elastic, Entry entry, int n, float* data, float* labels,
+                     const umx_warp_desc* warp, const umx_elastic_desc* elastic, unsigned needs, int n, float* data, float* labels,
                      float* weights, const char* what) {
     if (!tr) return tsfail(nullptr, UMX_ERR_INVALID, "null trainer");
     const TrainerIO io = trainer_io(tr);
-    TS_TRY(check_batch(tr, ts, desc, aug, warp, elastic, entry, n, io.B, what));
+    TS_TRY(check_batch(tr, ts, desc, aug, warp, elastic, needs, n, io.B, what));
     if (!data || !labels) return tsfail(tr, UMX_ERR_INVALID, "null argument");
     TS_HIP(tr, hipSetDevice(io.device));
     TS_TRY(enqueue_batch(tr, ts, desc, aug, warp, elastic, n, ts->weighted));
@@ -970,43 +591,43 @@ void umx_trainset_destroy(umx_trainset* ts) {
 }
 
 int umx_train_step_sampled(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, int apply_update) {
-    return step_from_set(tr, ts, desc, nullptr, nullptr, nullptr, kSampled, apply_update, "umx_train_step_sampled");
+    return step_from_set(tr, ts, desc, nullptr, nullptr, nullptr, 0, apply_update, "umx_train_step_sampled");
 }
 
 int umx_train_step_augmented(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
                              int apply_update) {
-    return step_from_set(tr, ts, desc, aug, nullptr, nullptr, kAugmented, apply_update, "umx_train_step_augmented");
+    return step_from_set(tr, ts, desc, aug, nullptr, nullptr, kNeedsAug, apply_update, "umx_train_step_augmented");
 }
 
 int umx_train_step_warped(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
                           const umx_warp_desc* warp, int apply_update) {
-    return step_from_set(tr, ts, desc, aug, warp, nullptr, kWarped, apply_update, "umx_train_step_warped");
+    return step_from_set(tr, ts, desc, aug, warp, nullptr, kNeedsWarp, apply_update, "umx_train_step_warped");
 }
 
 int umx_trainer_assemble(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, int n, float* data, float* labels,
                          float* weights) {
-    return assemble_to_host(tr, ts, desc, nullptr, nullptr, nullptr, kSampled, n, data, labels, weights, "umx_trainer_assemble");
+    return assemble_to_host(tr, ts, desc, nullptr, nullptr, nullptr, 0, n, data, labels, weights, "umx_trainer_assemble");
 }
 
 int umx_trainer_assemble_augmented(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
                                    int n, float* data, float* labels, float* weights) {
-    return assemble_to_host(tr, ts, desc, aug, nullptr, nullptr, kAugmented, n, data, labels, weights, "umx_trainer_assemble_augmented");
+    return assemble_to_host(tr, ts, desc, aug, nullptr, nullptr, kNeedsAug, n, data, labels, weights, "umx_trainer_assemble_augmented");
 }
 
 int umx_trainer_assemble_warped(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
                                 const umx_warp_desc* warp, int n, float* data, float* labels, float* weights) {
-    return assemble_to_host(tr, ts, desc, aug, warp, nullptr, kWarped, n, data, labels, weights, "umx_trainer_assemble_warped");
+    return assemble_to_host(tr, ts, desc, aug, warp, nullptr, kNeedsWarp, n, data, labels, weights, "umx_trainer_assemble_warped");
 }
 
 int umx_train_step_elastic(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
                            const umx_warp_desc* warp, const umx_elastic_desc* elastic, int apply_update) {
-    return step_from_set(tr, ts, desc, aug, warp, elastic, kElastic, apply_update, "umx_train_step_elastic");
+    return step_from_set(tr, ts, desc, aug, warp, elastic, kNeedsElastic, apply_update, "umx_train_step_elastic");
 }
 
 int umx_trainer_assemble_elastic(umx_trainer* tr, const umx_trainset* ts, const umx_sample_desc* desc, const umx_augment_desc* aug,
                                  const umx_warp_desc* warp, const umx_elastic_desc* elastic, int n, float* data, float* labels,
                                  float* weights) {
-    return assemble_to_host(tr, ts, desc, aug, warp, elastic, kElastic, n, data, labels, weights, "umx_trainer_assemble_elastic");
+    return assemble_to_host(tr, ts, desc, aug, warp, elastic, kNeedsElastic, n, data, labels, weights, "umx_trainer_assemble_elastic");
 }
 
 int umx_elastic_desc_check(const umx_elastic_desc* e, int n_desc, char* msg, size_t cap) {

@@ -104,6 +104,9 @@ WARP_DESC = np.dtype([("m", "<f4", (4,))])
 ELASTIC_MAX_GRID, ELASTIC_MAX_DISP = 6, 32.0
 ELASTIC_DESC = np.dtype([("n", "<i4"), ("reserved", "<i4", (3,)), ("d", "<f4", (2, ELASTIC_MAX_GRID, ELASTIC_MAX_GRID))])
 
+# the arrays parallel to SAMPLE_DESC in the order the entries take them, as Trainer's messages name them
+_PARALLEL_DESCS = ((AUGMENT_DESC, "augmentation", "AUGMENT_DESC"), (WARP_DESC, "warp", "WARP_DESC"), (ELASTIC_DESC, "elastic", "ELASTIC_DESC"))
+
 
 class AugmentTableC(ctypes.Structure):
     """``umx_augment_table`` (include/umx_train.h)."""
@@ -429,119 +432,75 @@ class Trainer:
             raise ValueError("expected 1..%d descriptors (a 1-d SAMPLE_DESC array), got shape %r" % (n_max, d.shape))
         return d
 
-    def step_sampled(self, ts, desc, apply_update: bool = True):
-        """One step on the batch that B descriptors draw from the training set ``ts`` (assembled on the device); only enqueues
-        -- call loss() to synchronise and read the loss."""
+    def _set_batch(self, desc, parallel=(), step=None):
+        """The arrays of one training-set entry: the descriptors, then ``parallel``, the entry's own arrays in the order AUGMENT_DESC,
+        WARP_DESC, ELASTIC_DESC, one row per descriptor.  The last of them is the one the entry is named for; one in front of it may be
+        None, and None stays None.  ``step``: the method's name where it takes exactly B descriptors."""
         d = self._descs(desc, self.batch)
-        if d.size != self.batch:
-            raise ValueError("step_sampled takes exactly %d descriptors, got %d" % (self.batch, d.size))
-        self._check(self._lib.umx_train_step_sampled(self._h, ts._handle(), d.ctypes.data, int(apply_update)))
+        if step and d.size != self.batch:
+            raise ValueError("%s takes exactly %d descriptors, got %d" % (step, self.batch, d.size))
+        arrays = [d]
+        for k, (rows, (dtype, what, name)) in enumerate(zip(parallel, _PARALLEL_DESCS)):
+            if rows is None and k + 1 < len(parallel):
+                arrays.append(None)
+                continue
+            a = np.ascontiguousarray(rows, dtype=dtype)
+            if a.shape != (d.size,):
+                raise ValueError("expected %d %s descriptors (a 1-d %s array), got shape %r" % (d.size, what, name, a.shape))
+            arrays.append(a)
+        return arrays
 
-    def assemble(self, ts, desc):
-        """The batch that n <= B descriptors assemble, copied to the host: (data [n,P,P,C], labels [n,P,P,K], weights or None)."""
-        hp = self.hp
-        d = self._descs(desc, self.batch)
-        n, P = d.size, hp.imSize
+    def _batch_outputs(self, ts, n: int):
+        hp, P = self.hp, self.hp.imSize
         data = np.empty((n, P, P, hp.nChannels), np.float32)
         labels = np.empty((n, P, P, hp.nClasses), np.float32)
         weights = np.empty((n, P, P, hp.nClasses), np.float32) if ts.weighted else None
-        self._check(self._lib.umx_trainer_assemble(self._h, ts._handle(), d.ctypes.data, n, data.ctypes.data, labels.ctypes.data,
-                                                   None if weights is None else weights.ctypes.data))
         return data, labels, weights
 
-    def _augs(self, aug, n: int):
-        a = np.ascontiguousarray(aug, dtype=AUGMENT_DESC)
-        if a.shape != (n,):
-            raise ValueError("expected %d augmentation descriptors (a 1-d AUGMENT_DESC array), got shape %r" % (n, a.shape))
-        return a
+    def _set_call(self, symbol: str, ts, *args):
+        """The C entry ``symbol`` on (trainer, set, args): an array goes as its address, None as NULL."""
+        self._check(getattr(self._lib, symbol)(self._h, ts._handle(), *(a.ctypes.data if isinstance(a, np.ndarray) else a for a in args)))
+
+    def _assemble_call(self, symbol: str, ts, arrays):
+        out = self._batch_outputs(ts, arrays[0].size)
+        self._set_call(symbol, ts, *arrays, arrays[0].size, *out)
+        return out
+
+    def step_sampled(self, ts, desc, apply_update: bool = True):
+        """One step on the batch that B descriptors draw from the training set ``ts`` (assembled on the device); only enqueues
+        -- call loss() to synchronise and read the loss."""
+        self._set_call("umx_train_step_sampled", ts, *self._set_batch(desc, (), "step_sampled"), int(apply_update))
+
+    def assemble(self, ts, desc):
+        """The batch that n <= B descriptors assemble, copied to the host: (data [n,P,P,C], labels [n,P,P,K], weights or None)."""
+        return self._assemble_call("umx_trainer_assemble", ts, self._set_batch(desc))
 
     def step_augmented(self, ts, desc, aug, apply_update: bool = True):
         """``step_sampled`` with a blur level and a saturation gain per image (``aug``: B AUGMENT_DESC rows; the set needs a table,
         ``TrainSet.set_augment``).  Only enqueues."""
-        d = self._descs(desc, self.batch)
-        if d.size != self.batch:
-            raise ValueError("step_augmented takes exactly %d descriptors, got %d" % (self.batch, d.size))
-        a = self._augs(aug, d.size)
-        self._check(self._lib.umx_train_step_augmented(self._h, ts._handle(), d.ctypes.data, a.ctypes.data, int(apply_update)))
+        self._set_call("umx_train_step_augmented", ts, *self._set_batch(desc, (aug,), "step_augmented"), int(apply_update))
 
     def assemble_augmented(self, ts, desc, aug):
         """``assemble`` with a blur level and a saturation gain per image."""
-        hp = self.hp
-        d = self._descs(desc, self.batch)
-        a = self._augs(aug, d.size)
-        n, P = d.size, hp.imSize
-        data = np.empty((n, P, P, hp.nChannels), np.float32)
-        labels = np.empty((n, P, P, hp.nClasses), np.float32)
-        weights = np.empty((n, P, P, hp.nClasses), np.float32) if ts.weighted else None
-        self._check(self._lib.umx_trainer_assemble_augmented(self._h, ts._handle(), d.ctypes.data, a.ctypes.data, n, data.ctypes.data,
-                                                             labels.ctypes.data, None if weights is None else weights.ctypes.data))
-        return data, labels, weights
-
-    def _warps(self, warp, n: int):
-        w = np.ascontiguousarray(warp, dtype=WARP_DESC)
-        if w.shape != (n,):
-            raise ValueError("expected %d warp descriptors (a 1-d WARP_DESC array), got shape %r" % (n, w.shape))
-        return w
+        return self._assemble_call("umx_trainer_assemble_augmented", ts, self._set_batch(desc, (aug,)))
 
     def step_warped(self, ts, desc, aug, warp, apply_update: bool = True):
         """``step_augmented`` with a rotation / zoom matrix per image (``warp``: B WARP_DESC rows, ``trainset.warp_matrix``).  ``aug``
         None: no blur and gain 1 for every image, and the set needs no table.  Only enqueues."""
-        d = self._descs(desc, self.batch)
-        if d.size != self.batch:
-            raise ValueError("step_warped takes exactly %d descriptors, got %d" % (self.batch, d.size))
-        a = None if aug is None else self._augs(aug, d.size)
-        w = self._warps(warp, d.size)
-        self._check(self._lib.umx_train_step_warped(self._h, ts._handle(), d.ctypes.data, None if a is None else a.ctypes.data,
-                                                    w.ctypes.data, int(apply_update)))
+        self._set_call("umx_train_step_warped", ts, *self._set_batch(desc, (aug, warp), "step_warped"), int(apply_update))
 
     def assemble_warped(self, ts, desc, aug, warp):
         """``assemble_augmented`` with a rotation / zoom matrix per image; ``aug`` may be None."""
-        hp = self.hp
-        d = self._descs(desc, self.batch)
-        a = None if aug is None else self._augs(aug, d.size)
-        w = self._warps(warp, d.size)
-        n, P = d.size, hp.imSize
-        data = np.empty((n, P, P, hp.nChannels), np.float32)
-        labels = np.empty((n, P, P, hp.nClasses), np.float32)
-        weights = np.empty((n, P, P, hp.nClasses), np.float32) if ts.weighted else None
-        self._check(self._lib.umx_trainer_assemble_warped(self._h, ts._handle(), d.ctypes.data, None if a is None else a.ctypes.data,
-                                                          w.ctypes.data, n, data.ctypes.data, labels.ctypes.data,
-                                                          None if weights is None else weights.ctypes.data))
-        return data, labels, weights
-
-    def _elastics(self, elastic, n: int):
-        e = np.ascontiguousarray(elastic, dtype=ELASTIC_DESC)
-        if e.shape != (n,):
-            raise ValueError("expected %d elastic descriptors (a 1-d ELASTIC_DESC array), got shape %r" % (n, e.shape))
-        return e
+        return self._assemble_call("umx_trainer_assemble_warped", ts, self._set_batch(desc, (aug, warp)))
 
     def step_elastic(self, ts, desc, aug, warp, elastic, apply_update: bool = True):
         """``step_warped`` with a displacement lattice per image (``elastic``: B ELASTIC_DESC rows, ``trainset.elastic_lattice``).
         ``aug`` None: no blur and gain 1; ``warp`` None: no rotation or zoom.  Only enqueues."""
-        d = self._descs(desc, self.batch)
-        if d.size != self.batch:
-            raise ValueError("step_elastic takes exactly %d descriptors, got %d" % (self.batch, d.size))
-        a = None if aug is None else self._augs(aug, d.size)
-        w = None if warp is None else self._warps(warp, d.size)
-        e = self._elastics(elastic, d.size)
-        self._check(self._lib.umx_train_step_elastic(self._h, ts._handle(), d.ctypes.data, None if a is None else a.ctypes.data,
-                                                     None if w is None else w.ctypes.data, e.ctypes.data, int(apply_update)))
+        self._set_call("umx_train_step_elastic", ts, *self._set_batch(desc, (aug, warp, elastic), "step_elastic"), int(apply_update))
 
     def assemble_elastic(self, ts, desc, aug, warp, elastic):
         """``assemble_warped`` with a displacement lattice per image; ``aug`` and ``warp`` may be None."""
-        hp = self.hp
-        d = self._descs(desc, self.batch)
-        a = None if aug is None else self._augs(aug, d.size)
-        w = None if warp is None else self._warps(warp, d.size)
-        e = self._elastics(elastic, d.size)
-        n, P = d.size, hp.imSize
-        data = np.empty((n, P, P, hp.nChannels), np.float32)
-        labels = np.empty((n, P, P, hp.nClasses), np.float32)
-        weights = np.empty((n, P, P, hp.nClasses), np.float32) if ts.weighted else None
-        self._check(self._lib.umx_trainer_assemble_elastic(self._h, ts._handle(), d.ctypes.data, None if a is None else a.ctypes.data,
-                                                           None if w is None else w.ctypes.data, e.ctypes.data, n, data.ctypes.data,
-                                                           labels.ctypes.data, None if weights is None else weights.ctypes.data))
-        return data, labels, weights
+        return self._assemble_call("umx_trainer_assemble_elastic", ts, self._set_batch(desc, (aug, warp, elastic)))
 
     def evaluate(self, ts, descs, objects=None) -> dict:
         """The validation pass over any number of descriptors, B at a time (eval mode: moving statistics, no dropout):
