@@ -36,7 +36,7 @@ enum umx_status {
     UMX_ERR_HIP = 4,         /* a HIP runtime call failed */
     UMX_ERR_OOM = 5,
     UMX_ERR_RANGE = 6,       /* split-precision path only: an activation left the binary16 range (|v| >= 6e4) */
-    UMX_ERR_GUARD = 7        /* debug guard mode only (UMX_DEBUG_GUARD, include/umx_train.h): a kernel wrote outside its buffer */
+    UMX_ERR_GUARD = 7        /* debug guard mode only (UMX_DEBUG_GUARD, umx_create_opts / include/umx_train.h): a kernel wrote outside its buffer */
 };
 
 /* Arithmetic of the convolutions.  All hold the 1e-4 tolerance on the probability maps.
@@ -107,6 +107,19 @@ UMX_API int umx_create(const umx_hparams* hp, const float* weight_blob, size_t b
 /* umx_create with explicit options (precision, ...). */
 UMX_API int umx_create_opts(const umx_hparams* hp, const float* weight_blob, size_t blob_floats, const umx_options* opts,
                     umx_ctx** out);
+/* Debug guard mode.  UMX_DEBUG_GUARD=<byte> (e.g. 0xff), read by umx_create_opts (on every attempt of the default-precision
+ * cascade; not a byte: UMX_ERR_INVALID), gives every device buffer of that context -- the create-time ones, the ones the entries
+ * grow on demand, the host slots' and a sharded context's -- a red zone of max(64 KiB, its size rounded up to 4 KiB) on both sides,
+ * filled with that byte.  Resident buffers (weights, epilogue constants, stage lists, head fragments, the zero line, the range
+ * flags) are uploaded or cleared at create.  Every other buffer is call-scoped: it is filled with the byte at allocation and again
+ * at the start of every entry that enqueues work, before that entry's first copy or launch, so a result that depends on the byte
+ * read memory that THIS call did not write -- a repeated call cannot lean on the previous call's results.  Every such entry
+ * (umx_forward_tiles[_dev], umx_band_tiles_dev, umx_stitch_dev, umx_infer_image*, the sharded entries) and umx_synchronize then
+ * waits for every stream of the context and checks every zone at its end, umx_infer_image_wait for a submitted call:
+ * UMX_ERR_GUARD names the buffer, the side and the first and last changed byte (umx_last_error).  Between calls the mode waits for
+ * idle streams, and a submit waits for the other slot; inside one call the launches, streams and events are the normal ones.
+ * The umx_test_*_dev entries put their scratch in a call-local arena of the same kind.  Slow; for tests
+ * (tests/test_gpu_infer_guard.py).  Off (unset or empty), allocations and launches are exactly the normal ones. */
 /* The precision a ctx actually runs (enum umx_precision). */
 UMX_API int umx_precision_of(const umx_ctx* ctx);
 

@@ -19,27 +19,52 @@ int fail(umx_ctx* ctx, int code, const char* fmt, ...) {
     return code;
 }
 
-int dev_alloc(umx_ctx* ctx, void** out, size_t bytes) {
+int dev_alloc(umx_ctx* ctx, void** out, size_t bytes, const std::string& label, bool scoped) {
     void* d = nullptr;
-    HIP_TRY(ctx, hipMalloc(&d, bytes ? bytes : 16));
-    ctx->allocs.push_back(d);
+    HIP_TRY(ctx, arena_alloc(&ctx->mem, &d, bytes, false, label.c_str(), scoped));
     *out = d;
     return UMX_OK;
 }
 
 
-int grow(umx_ctx* ctx, void** buf, size_t* cap, size_t bytes, bool device_wide) {
+int grow(umx_ctx* ctx, void** buf, size_t* cap, size_t bytes, const char* label, bool device_wide) {
     if (*cap >= bytes) return UMX_OK;
     if (*buf) {
         if (device_wide) HIP_TRY(ctx, hipDeviceSynchronize());
         else HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx, hipFree(*buf));
+        HIP_TRY(ctx, arena_release(&ctx->mem, *buf));
         *buf = nullptr;
         *cap = 0;
     }
-    HIP_TRY(ctx, hipMalloc(buf, bytes));
+    HIP_TRY(ctx, arena_alloc(&ctx->mem, buf, bytes, false, label, true));
     *cap = bytes;
     return UMX_OK;
+}
+
+// guard mode: every stream that touches the context's buffers -- the context's (or a caller's, umx_set_stream), the second lane's,
+// the copy streams and a sharded context's communication stream
+static int guard_drain(umx_ctx* ctx) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    for (hipStream_t s : {ctx->stream, ctx->own_stream, ctx->stream2, ctx->up_stream, ctx->dn_stream, shard_stream(ctx)})
+        if (s) HIP_TRY(ctx, hipStreamSynchronize(s));
+    return UMX_OK;
+}
+
+int guard_begin(umx_ctx* ctx, bool refill) {
+    if (ctx->guard_depth == 0 && refill) {   // (an entry that only waits keeps its own, bounded, way of waiting)
+        if (const int rc = guard_drain(ctx)) return rc;
+        HIP_TRY(ctx, arena_refill(ctx->mem, ctx->stream));
+    }
+    ++ctx->guard_depth;
+    return UMX_OK;
+}
+
+int guard_end(umx_ctx* ctx, int rc, bool check) {
+    if (--ctx->guard_depth > 0 || rc != UMX_OK || !check) return rc;
+    if ((rc = guard_drain(ctx))) return rc;
+    std::string msg;
+    rc = arena_check(ctx->mem, &msg);
+    return rc == UMX_OK ? UMX_OK : fail(ctx, rc, "%s", msg.c_str());
 }
 
 int site_of(umx_ctx* ctx, const std::string& name, const std::string& kernel) {
@@ -398,17 +423,17 @@ int plan_model(const umx_hparams& hp, const float* blob, bool f16, bool f6, int 
 // a host plan on the device: its arrays in the context's allocations, the launch's parameters with their pointers set
 int upload_plan(umx_ctx* ctx, Launch& L, const HostPlan& P) {
     int rc = UMX_OK;
-    auto up = [&](const auto& v) {   // (an empty array: null)
+    auto up = [&](const auto& v, const std::string& what) {   // (an empty array: null)
         typename std::decay_t<decltype(v)>::value_type* d = nullptr;
-        if (!rc) rc = upload_raw(ctx, v, &d);
+        if (!rc) rc = upload_raw(ctx, v, &d, L.name + " " + what);
         return d;
     };
     HConvParams& h = L.hcp;
     h = P.h;
-    h.stages = up(P.stages);
-    h.econst = reinterpret_cast<const uint4*>(up(P.econst));
-    for (int list = 0; list < 4; ++list) h.ph[list].w = reinterpret_cast<const uint4*>(up(P.wimg[list]));
-    h.head_frag = reinterpret_cast<const uint4*>(up(P.head_frag));
+    h.stages = up(P.stages, "stages");
+    h.econst = reinterpret_cast<const uint4*>(up(P.econst, "econst"));
+    for (int list = 0; list < 4; ++list) h.ph[list].w = reinterpret_cast<const uint4*>(up(P.wimg[list], "weights[" + std::to_string(list) + "]"));
+    h.head_frag = reinterpret_cast<const uint4*>(up(P.head_frag, "head_frag"));
     h.zeros = ctx->d_zeros;
     h.overflow_flag = ctx->d_flag;
     L.nt16 = P.nt16;
@@ -416,7 +441,7 @@ int upload_plan(umx_ctx* ctx, Launch& L, const HostPlan& P) {
     L.use_first = P.use_first;
     if (P.use_first) {
         L.first = P.first;
-        L.first.w = reinterpret_cast<const uint4*>(up(P.first_w));
+        L.first.w = reinterpret_cast<const uint4*>(up(P.first_w, "first weights"));
         L.first.econst = reinterpret_cast<const float*>(h.econst);
     }
     return rc;
@@ -478,14 +503,19 @@ int umx_test_double_to_half_dev(const double* in, uint16_t* out, size_t n) {
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, UMX_ERR_NO_DEVICE, "no HIP device available");
     double* din = nullptr;
     uint16_t* dout = nullptr;
-    HIP_TRY(nullptr, hipMalloc((void**)&din, n * sizeof(double) + 16));
-    if (hipMalloc((void**)&dout, n * sizeof(uint16_t) + 16) != hipSuccess) { hipFree(din); return fail(nullptr, UMX_ERR_OOM, "hipMalloc failed"); }
-    hipError_t e = hipMemcpy(din, in, n * sizeof(double), hipMemcpyHostToDevice);
+    DevArena mem;   // call-local (UMX_DEBUG_GUARD: red zones round both vectors, checked before they are freed)
+    std::string msg;
+    if (arena_init(&mem, &msg) != UMX_OK) return fail(nullptr, UMX_ERR_INVALID, "%s", msg.c_str());
+    hipError_t e = arena_alloc(&mem, (void**)&din, n * sizeof(double) + 16, false, "double_to_half in", true);
+    if (e == hipSuccess) e = arena_alloc(&mem, (void**)&dout, n * sizeof(uint16_t) + 16, false, "double_to_half out", true);
+    if (e == hipSuccess) e = hipMemcpy(din, in, n * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = launch_d2h_rne_test(din, dout, n, nullptr);
     if (e == hipSuccess) e = hipMemcpy(out, dout, n * sizeof(uint16_t), hipMemcpyDeviceToHost);
-    hipFree(din);
-    hipFree(dout);
-    return e == hipSuccess ? UMX_OK : fail(nullptr, UMX_ERR_HIP, "umx_test_double_to_half_dev: %s", hipGetErrorString(e));
+    const int grc = e == hipSuccess ? arena_check(mem, &msg) : UMX_OK;
+    arena_free(&mem);
+    if (e != hipSuccess)
+        return fail(nullptr, e == hipErrorOutOfMemory ? UMX_ERR_OOM : UMX_ERR_HIP, "umx_test_double_to_half_dev: %s", hipGetErrorString(e));
+    return grc == UMX_OK ? UMX_OK : fail(nullptr, grc, "%s", msg.c_str());
 }
 
 int umx_describe(const umx_hparams* hp, int* n_launches, double* flops_per_tile, double* executed_flops_per_tile) {
@@ -574,6 +604,11 @@ int umx_create_opts(const umx_hparams* hp, const float* weight_blob, size_t blob
     if (!out) return fail(nullptr, UMX_ERR_INVALID, "out is NULL");
     *out = nullptr;
     if (!opts) return fail(nullptr, UMX_ERR_INVALID, "opts is NULL");
+    DevArena guard;   // UMX_DEBUG_GUARD, read by every attempt of the cascade below (each is a call of this function)
+    {
+        std::string bad;
+        if (arena_init(&guard, &bad) != UMX_OK) return fail(nullptr, UMX_ERR_INVALID, "%s", bad.c_str());
+    }
     if (opts->precision == UMX_PREC_DEFAULT && !getenv("UMX_PRECISION")) {
         // default = split precision where its planner covers every layer, else the exact-fp32 MFMA kernels (tiny layers
         // under big filters exceed the LDS image of conv_f16x3).  Both are HIP paths; there is no CPU fallback.
@@ -642,6 +677,7 @@ int umx_create_opts(const umx_hparams* hp, const float* weight_blob, size_t blob
     ctx->precision = precision;
     ctx->f6 = f6;
     ctx->act_shift = act_shift;
+    ctx->mem.fill = guard.fill;
     ctx->plan = std::move(mp.plan);
     ctx->bufs = std::move(mp.bufs);
     umx_ctx* c = ctx.get();
@@ -668,21 +704,25 @@ int umx_create_opts(const umx_hparams* hp, const float* weight_blob, size_t blob
         for (Buffer& B : *set) {
             // (hi, lo) binary16 planes with Cs channels take 4*Cs bytes per pixel
             const size_t bytes_per_tile = B.as_f32 ? B.floats_per_tile * sizeof(float) : (size_t)B.S * B.S * B.Cs * 4;
+            const int id = (int)(&B - set->data());
+            std::string label = std::string(set == &c->bufs ? "bufs[" : "bufs2[") + std::to_string(id) + (id ? "]" : "] input tiles");
+            for (const Launch& L : c->plan)
+                if (L.dst == id) label += " <- " + L.name;
             void* d = nullptr;
-            if ((rc = dev_alloc(c, &d, bytes_per_tile * (size_t)max_batch))) return bail(rc);
+            if ((rc = dev_alloc(c, &d, bytes_per_tile * (size_t)max_batch, label, true))) return bail(rc);
             B.d = (float*)d;
         }
     if (f16) {
         void* d = nullptr;
-        if ((rc = dev_alloc(c, &d, c->bufs[0].floats_per_tile * sizeof(float) * (size_t)max_batch))) return bail(rc);
+        if ((rc = dev_alloc(c, &d, c->bufs[0].floats_per_tile * sizeof(float) * (size_t)max_batch, "d_tiles32", true))) return bail(rc);
         c->d_tiles32 = (float*)d;
         if (c->nlanes == 2) {
-            if ((rc = dev_alloc(c, &d, c->bufs[0].floats_per_tile * sizeof(float) * (size_t)max_batch))) return bail(rc);
+            if ((rc = dev_alloc(c, &d, c->bufs[0].floats_per_tile * sizeof(float) * (size_t)max_batch, "d_tiles32_2", true))) return bail(rc);
             c->d_tiles32_2 = (float*)d;
         }
-        if ((rc = dev_alloc(c, &d, 256))) return bail(rc);
+        if ((rc = dev_alloc(c, &d, 256, "d_zeros", false))) return bail(rc);
         c->d_zeros = (uint4*)d;
-        if ((rc = dev_alloc(c, &d, 256))) return bail(rc);
+        if ((rc = dev_alloc(c, &d, 256, "d_flag", false))) return bail(rc);
         c->d_flag = (int*)d;
         if (hipMemset(c->d_zeros, 0, 256) != hipSuccess || hipMemset(c->d_flag, 0, 256) != hipSuccess) {
             c->err = "hipMemset failed";
@@ -705,17 +745,18 @@ int umx_create_opts(const umx_hparams* hp, const float* weight_blob, size_t blob
                 for (int gi = 0; gi < L.ngroups; ++gi) std::vector<float>().swap(L.g[gi].packed[ph]);
             continue;
         }
-        if ((rc = upload_raw(c, L.pre_s, &L.d_pre_s)) || (rc = upload_raw(c, L.pre_b, &L.d_pre_b)) ||
-            (rc = upload_raw(c, L.post_s, &L.d_post_s)) || (rc = upload_raw(c, L.post_b, &L.d_post_b)))
+        if ((rc = upload_raw(c, L.pre_s, &L.d_pre_s, L.name + " pre_s")) || (rc = upload_raw(c, L.pre_b, &L.d_pre_b, L.name + " pre_b")) ||
+            (rc = upload_raw(c, L.post_s, &L.d_post_s, L.name + " post_s")) || (rc = upload_raw(c, L.post_b, &L.d_post_b, L.name + " post_b")))
             return bail(rc);
         if (L.head) {
-            if ((rc = upload_raw(c, L.head_w, &L.d_head_w))) return bail(rc);
+            if ((rc = upload_raw(c, L.head_w, &L.d_head_w, L.name + " head_w"))) return bail(rc);
             continue;
         }
         for (int ph = 0; ph < L.nphase; ++ph)
             for (int gi = 0; gi < L.ngroups; ++gi) {
                 float* d = nullptr;
-                if ((rc = upload_raw(c, L.g[gi].packed[ph], &d))) return bail(rc);
+                if ((rc = upload_raw(c, L.g[gi].packed[ph], &d, L.name + " weights[" + std::to_string(ph) + "][" + std::to_string(gi) + "]")))
+                    return bail(rc);
                 L.cp.ph[ph].w[gi] = d;
                 std::vector<float>().swap(L.g[gi].packed[ph]);
             }
@@ -724,6 +765,8 @@ int umx_create_opts(const umx_hparams* hp, const float* weight_blob, size_t blob
     if (f16) c->split_launch.name = "input.split";
     for (const Launch& L : c->plan)   // compact input tiles: the graph folded the raw skip (and so the first layer runs on the dense-K kernel)
         if (L.app_src == 0) c->in_cw = c->hp.nChannels == 1 ? 1 : c->hp.nChannels == 2 ? 2 : 4;
+    if (c->mem.fill >= 0)
+        fprintf(stderr, "[umx] UMX_DEBUG_GUARD=0x%02x: %zu engine buffers between red zones\n", c->mem.fill, c->mem.blocks.size());
     *out = ctx.release();
     return UMX_OK;
 }
@@ -741,21 +784,13 @@ void umx_destroy(umx_ctx* ctx) {
     shard_release(ctx);   // a communicator / buffers umx_shard_init attached to this context
     for (auto& pe : ctx->pending) { hipEventDestroy(pe.a); hipEventDestroy(pe.b); }
     for (auto e : ctx->free_events) hipEventDestroy(e);
-    for (void* d : ctx->allocs) hipFree(d);
-    if (ctx->d_image) hipFree(ctx->d_image);
-    if (ctx->d_probs) hipFree(ctx->d_probs);
-    if (ctx->d_out) hipFree(ctx->d_out);
-    if (ctx->d_io_tiles) hipFree(ctx->d_io_tiles);
-    if (ctx->d_io_probs) hipFree(ctx->d_io_probs);
+    arena_free(&ctx->mem);   // every device buffer: the create-time ones, the grown ones and the host slots'
     if (ctx->up_stream) { hipStreamSynchronize(ctx->up_stream); hipStreamDestroy(ctx->up_stream); }
     if (ctx->dn_stream) { hipStreamSynchronize(ctx->dn_stream); hipStreamDestroy(ctx->dn_stream); }
     for (auto& h : ctx->hs) {
         for (auto e : h.events) hipEventDestroy(e);
         if (h.done) hipEventDestroy(h.done);
         if (h.flag_host) hipHostFree(h.flag_host);
-        if (h.d_image) hipFree(h.d_image);
-        if (h.d_probs) hipFree(h.d_probs);
-        if (h.d_out) hipFree(h.d_out);
     }
     if (ctx->stream2) { hipStreamSynchronize(ctx->stream2); hipStreamDestroy(ctx->stream2); }
     if (ctx->ev_fork) hipEventDestroy(ctx->ev_fork);
@@ -773,40 +808,46 @@ int umx_set_stream(umx_ctx* ctx, void* hip_stream) {
 
 int umx_synchronize(umx_ctx* ctx) {
     if (!ctx) return fail(nullptr, UMX_ERR_INVALID, "ctx is NULL");
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return check_range_flag(ctx);
+    return guarded(ctx, false, true, [&]() -> int {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return check_range_flag(ctx);
+    });
 }
 
 int umx_forward_tiles_dev(umx_ctx* ctx, const float* tiles_dev, int n, float* probs_dev) {
     if (!ctx) return fail(nullptr, UMX_ERR_INVALID, "ctx is NULL");
     if (n < 0 || (n > 0 && (!tiles_dev || !probs_dev))) return fail(ctx, UMX_ERR_INVALID, "bad tiles/probs/n");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t P = ctx->hp.imSize;
-    const size_t tile_f = P * P * ctx->hp.nChannels, prob_f = P * P * ctx->hp.nClasses;
-    LaneLoop ll(ctx, n);
-    for (int i = 0, nb; i < n; i += nb) {
-        nb = ll.next(n - i);
-        int rc = run_unet(ctx, tiles_dev + (size_t)i * tile_f, nb, probs_dev + (size_t)i * prob_f);
-        if (rc) return rc;
-    }
-    return ll.join();
+    return guarded(ctx, true, true, [&]() -> int {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const size_t P = ctx->hp.imSize;
+        const size_t tile_f = P * P * ctx->hp.nChannels, prob_f = P * P * ctx->hp.nClasses;
+        LaneLoop ll(ctx, n);
+        for (int i = 0, nb; i < n; i += nb) {
+            nb = ll.next(n - i);
+            int rc = run_unet(ctx, tiles_dev + (size_t)i * tile_f, nb, probs_dev + (size_t)i * prob_f);
+            if (rc) return rc;
+        }
+        return ll.join();
+    });
 }
 
 int umx_forward_tiles(umx_ctx* ctx, const float* tiles_host, int n, float* probs_host) {
     if (!ctx) return fail(nullptr, UMX_ERR_INVALID, "ctx is NULL");
     if (n < 0 || (n > 0 && (!tiles_host || !probs_host))) return fail(ctx, UMX_ERR_INVALID, "bad tiles/probs/n");
     if (n == 0) return UMX_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t P = ctx->hp.imSize;
-    const size_t tile_b = P * P * ctx->hp.nChannels * sizeof(float), prob_b = P * P * ctx->hp.nClasses * sizeof(float);
-    int rc;
-    if ((rc = grow(ctx, (void**)&ctx->d_io_tiles, &ctx->io_tiles_cap, tile_b * n))) return rc;
-    if ((rc = grow(ctx, (void**)&ctx->d_io_probs, &ctx->io_probs_cap, prob_b * n))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_io_tiles, tiles_host, tile_b * n, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = umx_forward_tiles_dev(ctx, ctx->d_io_tiles, n, ctx->d_io_probs))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(probs_host, ctx->d_io_probs, prob_b * n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return check_range_flag(ctx);
+    return guarded(ctx, true, true, [&]() -> int {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const size_t P = ctx->hp.imSize;
+        const size_t tile_b = P * P * ctx->hp.nChannels * sizeof(float), prob_b = P * P * ctx->hp.nClasses * sizeof(float);
+        int rc;
+        if ((rc = grow(ctx, (void**)&ctx->d_io_tiles, &ctx->io_tiles_cap, tile_b * n, "d_io_tiles"))) return rc;
+        if ((rc = grow(ctx, (void**)&ctx->d_io_probs, &ctx->io_probs_cap, prob_b * n, "d_io_probs"))) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_io_tiles, tiles_host, tile_b * n, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = umx_forward_tiles_dev(ctx, ctx->d_io_tiles, n, ctx->d_io_probs))) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(probs_host, ctx->d_io_probs, prob_b * n, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return check_range_flag(ctx);
+    });
 }
 
 int umx_tile_grid(const umx_ctx* ctx, int H, int W, int* patch_rows, int* patch_cols, int* padded_rows,
@@ -835,15 +876,17 @@ int umx_band_tiles_dev(umx_ctx* ctx, const double* image_dev, int C_img, int H, 
     if (band_row0 < 0 || band_rows < 0 || (need1 > need0 && (band_row0 > need0 || band_row0 + band_rows < need1)))
         return fail(ctx, UMX_ERR_INVALID, "band rows [%d,%d) do not cover the rows [%d,%d) the patch rows need",
                     band_row0, band_row0 + band_rows, need0, need1);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return tiles_range(ctx, image_dev, C_img, g, band_row0, band_rows, mean, stdv, pr0 * g.npc, pr1 * g.npc, probs_dev);
+    return guarded(ctx, true, true, [&]() -> int {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        return tiles_range(ctx, image_dev, C_img, g, band_row0, band_rows, mean, stdv, pr0 * g.npc, pr1 * g.npc, probs_dev);
+    });
 }
 
 int umx_stitch_dev(umx_ctx* ctx, const float* probs_dev, int tpr0, int tpr1, int H, int W, int mode, int stitch, int y0,
                    int y1, void* out_dev) {
     if (!ctx) return fail(nullptr, UMX_ERR_INVALID, "ctx is NULL");
     if (stitch != UMX_STITCH_FP16_COMPAT && stitch != UMX_STITCH_FP32) return fail(ctx, UMX_ERR_INVALID, "bad stitch %d", stitch);
-    return umx::stitch_rows(ctx, probs_dev, tpr0, tpr1, H, W, mode, stitch, y0, y1, out_dev, 0);
+    return guarded(ctx, true, true, [&]() -> int { return umx::stitch_rows(ctx, probs_dev, tpr0, tpr1, H, W, mode, stitch, y0, y1, out_dev, 0); });
 }
 
 }  // extern "C"
@@ -882,11 +925,13 @@ int umx_infer_image_dev(umx_ctx* ctx, const double* image_dev, int C_img, int H,
     if (H < 1 || W < 1) return fail(ctx, UMX_ERR_INVALID, "bad H/W");
     const TileGeom g = geom_of(ctx->hp, H, W);
     const size_t prob_b = (size_t)g.npr * g.npc * g.P * g.P * ctx->hp.nClasses * sizeof(float);
-    int rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((rc = grow(ctx, (void**)&ctx->d_probs, &ctx->probs_cap, prob_b))) return rc;
-    if ((rc = umx_band_tiles_dev(ctx, image_dev, C_img, H, W, 0, H, mean, stdv, 0, g.npr, ctx->d_probs))) return rc;
-    return umx_stitch_dev(ctx, ctx->d_probs, 0, g.npr, H, W, mode, stitch, 0, H, out_dev);
+    return guarded(ctx, true, true, [&]() -> int {
+        int rc;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        if ((rc = grow(ctx, (void**)&ctx->d_probs, &ctx->probs_cap, prob_b, "d_probs"))) return rc;
+        if ((rc = umx_band_tiles_dev(ctx, image_dev, C_img, H, W, 0, H, mean, stdv, 0, g.npr, ctx->d_probs))) return rc;
+        return umx_stitch_dev(ctx, ctx->d_probs, 0, g.npr, H, W, mode, stitch, 0, H, out_dev);
+    });
 }
 
 int umx_profile_enable(umx_ctx* ctx, int on) {

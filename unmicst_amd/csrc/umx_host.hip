@@ -162,9 +162,12 @@ static int host_enqueue(umx_ctx* ctx, int slot, bool sync_call, const void* src,
     // before the first tile) as it reads -- the float64 image, 8 bytes written and 14 read per pixel and channel, is never made, and
     // not allocated either: 4.3 GB for a two-channel 16384 x 16384 slide
     const bool raw_gather = src_bits != 0 && gathers_raw(ctx);
-    if (!raw_gather && (rc = grow(ctx, (void**)&hs.d_image, &hs.image_cap, plane * C_img * sizeof(double)))) return rc;
-    if ((rc = grow(ctx, &hs.d_out, &hs.out_cap, mm_off + 64 * (size_t)C_img))) return rc;
-    if ((rc = grow(ctx, (void**)&hs.d_probs, &hs.probs_cap, (size_t)g.npr * g.npc * g.P * g.P * K * sizeof(float)))) return rc;
+    if (!raw_gather && (rc = grow(ctx, (void**)&hs.d_image, &hs.image_cap, plane * C_img * sizeof(double), slot ? "slot 1 d_image" : "slot 0 d_image")))
+        return rc;
+    if ((rc = grow(ctx, &hs.d_out, &hs.out_cap, mm_off + 64 * (size_t)C_img, slot ? "slot 1 d_out" : "slot 0 d_out"))) return rc;
+    if ((rc = grow(ctx, (void**)&hs.d_probs, &hs.probs_cap, (size_t)g.npr * g.npc * g.P * g.P * K * sizeof(float),
+                   slot ? "slot 1 d_probs" : "slot 0 d_probs")))
+        return rc;
     unsigned char* const base = (unsigned char*)hs.d_out;
     // slabs = the launch groups of the tile loop (equal groups of <= max_batch tiles, exactly what umx_infer_image_dev
     // runs), so that pipelining the transfers does not change a single kernel launch
@@ -320,10 +323,12 @@ static int host_enqueue(umx_ctx* ctx, int slot, bool sync_call, const void* src,
 // sync_call: a synchronous entry (slot 0), which also waits for the call
 static int host_submit(umx_ctx* ctx, int slot, bool sync_call, const void* src, int src_bits, int C_img, int H, int W, int rescale,
                        const uint32_t* range, double mean, double stdv, int mode, int stitch, int out_u8, void* out_host) {
-    const int rc = slot_submit(ctx, slot, [&] {
-        return host_enqueue(ctx, slot, sync_call, src, src_bits, C_img, H, W, rescale, range, mean, stdv, mode, stitch, out_u8, out_host);
+    return guarded(ctx, true, sync_call, [&]() -> int {   // (guard mode: a submitted call's zones are checked by its wait)
+        const int rc = slot_submit(ctx, slot, [&] {
+            return host_enqueue(ctx, slot, sync_call, src, src_bits, C_img, H, W, rescale, range, mean, stdv, mode, stitch, out_u8, out_host);
+        });
+        return rc || !sync_call ? rc : host_wait(ctx, slot);
     });
-    return rc || !sync_call ? rc : host_wait(ctx, slot);
 }
 
 int umx_infer_image(umx_ctx* ctx, const double* image_host, int C_img, int H, int W, double mean, double stdv, int mode,
@@ -445,7 +450,7 @@ static int infer_raw_scaled_impl(umx_ctx* ctx, const void* raw_host, int bits, i
     int rc;
     umx_ctx::HostSlot& hs = ctx->hs[0];
     if (hs.busy) return fail(ctx, UMX_ERR_INVALID, "slot 0 still holds a submitted call: wait for it first");
-    if ((rc = grow(ctx, &hs.d_out, &hs.out_cap, off))) return rc;
+    if ((rc = grow(ctx, &hs.d_out, &hs.out_cap, off, "slot 0 d_out"))) return rc;
     unsigned char* const base = (unsigned char*)hs.d_out;
     double *A = (double*)(base + o_a), *B = (double*)(base + o_b), *Cw = (double*)(base + o_c), *din = (double*)(base + o_in);
     double* const wdev = (double*)(base + o_w);
@@ -481,13 +486,17 @@ static int infer_raw_scaled_impl(umx_ctx* ctx, const void* raw_host, int bits, i
 
 int umx_infer_image_raw_scaled(umx_ctx* ctx, const void* raw_host, int bits, int C_img, int H, int W, double scaling, int rescale,
                                double mean, double stdv, int mode, uint8_t* out_host) {
-    return infer_raw_scaled_impl(ctx, raw_host, bits, C_img, H, W, scaling, rescale, -1.0, mean, stdv, mode, out_host);
+    return guarded(ctx, true, true, [&]() -> int {
+        return infer_raw_scaled_impl(ctx, raw_host, bits, C_img, H, W, scaling, rescale, -1.0, mean, stdv, mode, out_host);
+    });
 }
 
 int umx_infer_image_raw_outlier(umx_ctx* ctx, const void* raw_host, int bits, int C_img, int H, int W, double scaling, double outlier,
                                 double mean, double stdv, int mode, uint8_t* out_host) {
     if (!(outlier >= 0.0 && outlier <= 100.0)) return fail(ctx, UMX_ERR_INVALID, "outlier percentile must be in [0, 100]");
-    return infer_raw_scaled_impl(ctx, raw_host, bits, C_img, H, W, scaling, 1, outlier, mean, stdv, mode, out_host);
+    return guarded(ctx, true, true, [&]() -> int {
+        return infer_raw_scaled_impl(ctx, raw_host, bits, C_img, H, W, scaling, 1, outlier, mean, stdv, mode, out_host);
+    });
 }
 
 int umx_infer_image_raw_submit(umx_ctx* ctx, int slot, const void* raw_host, int bits, int C_img, int H, int W, int rescale,
@@ -499,7 +508,7 @@ int umx_infer_image_raw_submit(umx_ctx* ctx, int slot, const void* raw_host, int
 
 int umx_infer_image_wait(umx_ctx* ctx, int slot) {
     if (!ctx) return fail(nullptr, UMX_ERR_INVALID, "ctx is NULL");
-    return host_wait(ctx, slot);
+    return guarded(ctx, false, true, [&]() -> int { return host_wait(ctx, slot); });
 }
 
 // ---- test entries of the driver-side image kernels (tests/test_gpu_imagekernels.py, tests/test_imagekernels_cpu.py): thin wrappers
@@ -509,8 +518,22 @@ namespace {
 struct DevScratch {   // one allocation cut into 256-byte-aligned pieces, as infer_raw_scaled_impl cuts the slot's buffer
     unsigned char* base = nullptr;
     size_t off = 0;
+    DevArena mem;         // call-local (UMX_DEBUG_GUARD: red zones round the allocation, its content poisoned)
     size_t take(size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; }
-    ~DevScratch() { if (base) hipFree(base); }
+    int alloc(const char* who) {   // the `off` bytes taken so far
+        std::string why;
+        if (arena_init(&mem, &why) != UMX_OK) return fail(nullptr, UMX_ERR_INVALID, "%s", why.c_str());
+        HIP_TRY(nullptr, arena_alloc(&mem, (void**)&base, off, false, who, true));
+        return UMX_OK;
+    }
+    int check() {                  // at the end of the entry, before the destructor frees the allocation
+        if (mem.fill < 0) return UMX_OK;
+        HIP_TRY(nullptr, hipDeviceSynchronize());
+        std::string msg;
+        const int rc = arena_check(mem, &msg);
+        return rc == UMX_OK ? UMX_OK : fail(nullptr, rc, "%s", msg.c_str());
+    }
+    ~DevScratch() { arena_free(&mem); }
 };
 int test_device(const char* who) {
     int ndev = 0;
@@ -535,7 +558,7 @@ int umx_test_resize_dev(const double* src, int H, int W, int h, int w, double* o
     DevScratch d;
     const size_t o_a = d.take(big * 8), o_b = d.take(big * 8), o_c = d.take(big * 8), o_dst = d.take(sp * 8), o_u8 = d.take(sp);
     const size_t o_w = d.take(2 * kMaxGaussTaps * 8), o_mm = d.take(256);
-    HIP_TRY(nullptr, hipMalloc((void**)&d.base, d.off));
+    if (const int rc = d.alloc("umx_test_resize_dev scratch")) return rc;
     double *A = (double*)(d.base + o_a), *B = (double*)(d.base + o_b), *Cw = (double*)(d.base + o_c);
     HIP_TRY(nullptr, hipMemcpy(A, src, plane * 8, hipMemcpyHostToDevice));
     int rc;
@@ -553,7 +576,7 @@ int umx_test_resize_dev(const double* src, int H, int W, int h, int w, double* o
         HIP_TRY(nullptr, hipMemcpy(out_u8, d.base + o_u8, sp, hipMemcpyDeviceToHost));
     }
     if (out_filtered) HIP_TRY(nullptr, hipMemcpy(out_filtered, filt, plane * 8, hipMemcpyDeviceToHost));
-    return UMX_OK;
+    return d.check();
 }
 
 int umx_test_rescale_dev(const double* plane, size_t n, double outlier, double* out_plane, double* range2) {
@@ -561,7 +584,7 @@ int umx_test_rescale_dev(const double* plane, size_t n, double outlier, double* 
     if (const int rc = test_device("umx_test_rescale_dev")) return rc;
     DevScratch d;
     const size_t o_x = d.take(n * 8), o_mm = d.take(256), o_sel = d.take(64 + 512 * 4);
-    HIP_TRY(nullptr, hipMalloc((void**)&d.base, d.off));
+    if (const int rc = d.alloc("umx_test_rescale_dev scratch")) return rc;
     double* const x = (double*)(d.base + o_x);
     unsigned long long* const mm64 = (unsigned long long*)(d.base + o_mm);
     HIP_TRY(nullptr, hipMemcpy(x, plane, n * 8, hipMemcpyHostToDevice));
@@ -571,7 +594,7 @@ int umx_test_rescale_dev(const double* plane, size_t n, double outlier, double* 
     HIP_TRY(nullptr, launch_rescale_f64(x, n, mm64, nullptr));
     HIP_TRY(nullptr, hipMemcpy(range2, mm64, 16, hipMemcpyDeviceToHost));   // the (min, limit) doubles the rescale read
     HIP_TRY(nullptr, hipMemcpy(out_plane, x, n * 8, hipMemcpyDeviceToHost));
-    return UMX_OK;
+    return d.check();
 }
 
 int umx_test_plane_range_dev(const void* raw, int bits, const size_t* n, const size_t* offset_elems, const int* nslabs, int njobs,
@@ -587,7 +610,7 @@ int umx_test_plane_range_dev(const void* raw, int bits, const size_t* n, const s
     }
     DevScratch d;
     const size_t o_raw = d.take(most), o_mm = d.take((size_t)njobs * 8);
-    HIP_TRY(nullptr, hipMalloc((void**)&d.base, d.off));   // (hipMalloc's addresses are 256-byte aligned, and so is every piece)
+    if (const int rc = d.alloc("umx_test_plane_range_dev scratch")) return rc;   // (hipMalloc's addresses are 256-byte aligned, and so is every piece)
     unsigned* const mm = (unsigned*)(d.base + o_mm);
     const unsigned char* src = (const unsigned char*)raw;
     for (int j = 0; j < njobs; ++j) {   // the jobs share the plane buffer: the default stream orders copy j + 1 behind reduction j
@@ -603,7 +626,7 @@ int umx_test_plane_range_dev(const void* raw, int bits, const size_t* n, const s
         src += n[j] * el;
     }
     HIP_TRY(nullptr, hipMemcpy(range2, mm, (size_t)njobs * 8, hipMemcpyDeviceToHost));
-    return UMX_OK;
+    return d.check();
 }
 
 int umx_test_half_to_u8_dev(const uint16_t* half_bits, size_t n, uint8_t* out_u8, double* out_f64) {
@@ -611,13 +634,13 @@ int umx_test_half_to_u8_dev(const uint16_t* half_bits, size_t n, uint8_t* out_u8
     if (const int rc = test_device("umx_test_half_to_u8_dev")) return rc;
     DevScratch d;
     const size_t o_pm = d.take(n * 2), o_u8 = d.take(n), o_f = d.take(n * 8);
-    HIP_TRY(nullptr, hipMalloc((void**)&d.base, d.off));
+    if (const int rc = d.alloc("umx_test_half_to_u8_dev scratch")) return rc;
     HIP_TRY(nullptr, hipMemcpy(d.base + o_pm, half_bits, n * 2, hipMemcpyHostToDevice));
     HIP_TRY(nullptr, launch_half_to_u8(d.base + o_pm, n, d.base + o_u8, nullptr));
     HIP_TRY(nullptr, launch_half_to_u8_f64(d.base + o_pm, n, (double*)(d.base + o_f), nullptr));
     HIP_TRY(nullptr, hipMemcpy(out_u8, d.base + o_u8, n, hipMemcpyDeviceToHost));
     HIP_TRY(nullptr, hipMemcpy(out_f64, d.base + o_f, n * 8, hipMemcpyDeviceToHost));
-    return UMX_OK;
+    return d.check();
 }
 
 }  // extern "C"

@@ -119,6 +119,36 @@ struct PendingEvent {
     hipEvent_t a, b;
 };
 
+// ---- device memory of a trainer / training set / labeler / inference context (umx_train.hip) ----
+// Every allocation goes through arena_alloc.  Debug guard mode (UMX_DEBUG_GUARD=<byte>, read at umx_trainer_create /
+// umx_trainset_create / umx_create_opts) puts a red zone of max(64 KiB, round_up(bytes, 4 KiB)) in front of and behind each buffer,
+// fills both zones -- and the buffer itself unless the caller zeroes or uploads it -- with that byte, and arena_check names the first
+// buffer whose zones changed.  Off (the default), an allocation is the plain hipMalloc it always was.
+struct DevBlock {
+    void* base;                        // what hipMalloc returned
+    size_t front, bytes, back;         // the buffer is [base + front, base + front + bytes)
+    std::string label;
+    bool scoped;                       // call-scoped (arena_refill poisons it again), not resident
+};
+struct DevArena {
+    int fill = -1;                     // guard mode: the fill byte 0..255; -1 off
+    size_t serial = 0;                 // (guard mode) allocations so far: the "#n" of a label
+    std::vector<void*> allocs;         // what hipFree takes
+    std::vector<DevBlock> blocks;      // (guard mode) one per live allocation, in allocation order
+};
+// UMX_DEBUG_GUARD -> a->fill; UMX_ERR_INVALID (with *why) for a value that is not a byte
+int arena_init(DevArena* a, std::string* why);
+// bytes (at least 16) of device memory -> *out; zero: cleared, else uninitialised (guard mode: filled).  scoped: the buffer holds
+// nothing from one call to the next (the inference context's activations and per-call scratch)
+hipError_t arena_alloc(DevArena* a, void** out, size_t bytes, bool zero, const char* label, bool scoped = false);
+// frees the one allocation arena_alloc returned as p (its zones are not checked); the work that uses it must be done
+hipError_t arena_release(DevArena* a, void* p);
+// guard mode only: every scoped buffer filled again, in the order of `stream` (which the call then waits for)
+hipError_t arena_refill(const DevArena& a, hipStream_t stream);
+// guard mode only, with every stream writing the arena idle: UMX_OK, or UMX_ERR_GUARD with the first damaged zone in *msg
+int arena_check(const DevArena& a, std::string* msg);
+void arena_free(DevArena* a);
+
 struct Shard;   // umx_shard.hip: the communicator, transport and buffers umx_shard_init attaches to a context
 
 // ---- border weight maps (umx_trainset_border.hip) ----
@@ -164,7 +194,8 @@ struct umx_ctx {
         int* flag_host = nullptr;   // pinned copy of the range flag, read back behind the slot's last download
         bool busy = false;
     } hs[2];
-    std::vector<void*> allocs;
+    umx::DevArena mem;          // every device buffer of the context (UMX_DEBUG_GUARD: with red zones, the call-scoped ones poisoned)
+    int guard_depth = 0;        // (guard mode) public entries on the stack: the outermost one refills and checks
     std::string err;
     // whole-image scratch (grown on demand)
     double* d_image = nullptr;  size_t image_cap = 0;
@@ -259,21 +290,38 @@ bool make_d2s(Launch& L);
 bool conv_first_eligible(const umx_hparams& hp);
 
 // ---- umx_engine.hip
-int dev_alloc(umx_ctx* ctx, void** out, size_t bytes);
+// Device memory of a context: ctx->mem (DevArena above).  Resident buffers -- weights, epilogue constants, stage lists, head
+// fragments, the zero line and the range flags -- are uploaded or cleared at create and never refilled; everything else is
+// call-scoped (`scoped`): in guard mode it is poisoned at allocation and again at the start of every public entry that enqueues work.
+// `label` names the buffer in a guard error.
+int dev_alloc(umx_ctx* ctx, void** out, size_t bytes, const std::string& label, bool scoped);
 template <typename T>
-int upload_raw(umx_ctx* ctx, const std::vector<T>& h, T** out) {
+int upload_raw(umx_ctx* ctx, const std::vector<T>& h, T** out, const std::string& label) {
     *out = nullptr;
     if (h.empty()) return UMX_OK;
     void* d = nullptr;
-    int rc = dev_alloc(ctx, &d, h.size() * sizeof(T));
+    int rc = dev_alloc(ctx, &d, h.size() * sizeof(T), label, false);
     if (rc) return rc;
     HIP_TRY(ctx, hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
     *out = (T*)d;
     return UMX_OK;
 }
 
-// a buffer is freed to grow once the context's stream -- or, for one other streams read, the whole device (device_wide) -- is idle
-int grow(umx_ctx* ctx, void** buf, size_t* cap, size_t bytes, bool device_wide = false);
+// a (call-scoped) buffer is freed to grow once the context's stream -- or, for one other streams read, the whole device
+// (device_wide) -- is idle
+int grow(umx_ctx* ctx, void** buf, size_t* cap, size_t bytes, const char* label, bool device_wide = false);
+// Guard mode (ctx->mem.fill >= 0) around the body of a public entry; off, guarded() is body().  The outermost entry on the stack,
+// if it enqueues work (refill), waits for every stream of the context and poisons the call-scoped buffers before the body's first
+// copy or launch; after a body that succeeded -- check: not a submit, whose umx_infer_image_wait does it -- it waits for
+// the streams again and checks every red zone (UMX_ERR_GUARD).  Nothing inside the body changes: same launches, streams and events.
+int guard_begin(umx_ctx* ctx, bool refill);
+int guard_end(umx_ctx* ctx, int rc, bool check);
+template <class F>
+int guarded(umx_ctx* ctx, bool refill, bool check, F&& body) {
+    if (!ctx || ctx->mem.fill < 0) return body();
+    if (const int rc = guard_begin(ctx, refill)) return rc;
+    return guard_end(ctx, body(), check);
+}
 int site_of(umx_ctx* ctx, const std::string& name, const std::string& kernel);
 int prof_fold(umx_ctx* ctx);
 struct ProfScope {
@@ -333,31 +381,9 @@ int slot_finish(umx_ctx* ctx, int slot, hipStream_t dn_s);
 int put_range(umx_ctx* ctx, unsigned* mm, const uint32_t* range, int C_img);
 
 // ---- umx_shard.hip
-void shard_release(umx_ctx* ctx);               // frees ctx->shard
+void shard_release(umx_ctx* ctx);               // frees ctx->shard and its buffers in ctx->mem
+hipStream_t shard_stream(const umx_ctx* ctx);   // the communication stream of a sharded context, else null
 int shard_wait(umx_ctx* ctx, hipEvent_t ev);    // the bounded wait of a submitted call on a sharded context
-
-// ---- device memory of a trainer / training set (umx_train.hip) ----
-// Every allocation goes through arena_alloc.  Debug guard mode (UMX_DEBUG_GUARD=<byte>, read at umx_trainer_create /
-// umx_trainset_create) puts a red zone of max(64 KiB, round_up(bytes, 4 KiB)) in front of and behind each buffer, fills both
-// zones -- and the buffer itself unless the caller zeroes or uploads it -- with that byte, and arena_check names the first
-// buffer whose zones changed.  Off (the default), an allocation is the plain hipMalloc it always was.
-struct DevBlock {
-    void* base;                        // what hipMalloc returned
-    size_t front, bytes, back;         // the buffer is [base + front, base + front + bytes)
-    std::string label;
-};
-struct DevArena {
-    int fill = -1;                     // guard mode: the fill byte 0..255; -1 off
-    std::vector<void*> allocs;         // what hipFree takes
-    std::vector<DevBlock> blocks;      // (guard mode) one per allocation, in allocation order
-};
-// UMX_DEBUG_GUARD -> a->fill; UMX_ERR_INVALID (with *why) for a value that is not a byte
-int arena_init(DevArena* a, std::string* why);
-// bytes (at least 16) of device memory -> *out; zero: cleared, else uninitialised (guard mode: filled)
-hipError_t arena_alloc(DevArena* a, void** out, size_t bytes, bool zero, const char* label);
-// guard mode only, with every stream writing the arena idle: UMX_OK, or UMX_ERR_GUARD with the first damaged zone in *msg
-int arena_check(const DevArena& a, std::string* msg);
-void arena_free(DevArena* a);
 
 // ---- training step (umx_train.hip) as the training set (umx_trainset.hip) sees it ----
 struct TrainerIO {

@@ -99,9 +99,7 @@ struct umx::Shard {
         if (comm && rccl()->CommDestroy) rccl()->CommDestroy(comm);
         if (comm_stream) hipStreamDestroy(comm_stream);
         for (auto& ev : events) for (auto e : ev) hipEventDestroy(e);
-        for (void* d : {probs, gathered[0], gathered[1], full_u8[0], full_u8[1]}) if (d) hipFree(d);
-        for (auto& v : send) for (void* d : v) if (d) hipFree(d);
-    }
+    }   // (the buffers live in the context's arena: shard_release)
 };
 
 namespace {
@@ -159,9 +157,17 @@ int publish(umx_ctx* ctx, std::unique_ptr<Shard> s, int rank, int world) {
 }  // namespace
 
 void umx::shard_release(umx_ctx* ctx) {
+    std::vector<void*> bufs;   // freed behind the communicator, its stream and events, as ever
+    if (Shard* s = ctx->shard) {
+        bufs = {s->probs, s->gathered[0], s->gathered[1], s->full_u8[0], s->full_u8[1]};
+        for (auto& v : s->send) bufs.insert(bufs.end(), v.begin(), v.end());
+    }
     delete ctx->shard;
     ctx->shard = nullptr;
+    for (void* d : bufs) if (d) (void)arena_release(&ctx->mem, d);
 }
+
+hipStream_t umx::shard_stream(const umx_ctx* ctx) { return ctx->shard ? ctx->shard->comm_stream : nullptr; }
 
 // ---- band geometry (the C twin of unmicst_amd/sharding.py: band_partition / owned_rows / needed_image_rows / slab_rows;
 // tests/test_abi.py compares the two over a grid of sizes)
@@ -368,7 +374,7 @@ int sharded_run(umx_ctx* ctx, const RunIO& io, int C_img, int H, int W, int band
     const bool has_prev = pa < pb && pa > 0, has_next = pa < pb && pb < npr;
     const int lo = has_prev ? pa - 1 : pa;
     const size_t tile_f = (size_t)P * P * K, row_f = tile_f * npc;
-    if ((rc = grow(ctx, &s.probs, &s.probs_cap, std::max<size_t>(1, (size_t)std::max(pb - lo, 0)) * row_f * sizeof(float), true))) return rc;
+    if ((rc = grow(ctx, &s.probs, &s.probs_cap, std::max<size_t>(1, (size_t)std::max(pb - lo, 0)) * row_f * sizeof(float), "shard probs", true))) return rc;
     float* const probs = (float*)s.probs;
     std::vector<hipEvent_t>& evs = s.events[slot];
     const int nev = 6 + 4 * n;
@@ -453,9 +459,13 @@ int sharded_run(umx_ctx* ctx, const RunIO& io, int C_img, int H, int W, int band
                 umx_geom::slab(A[q], B[q], npr, sub, margin, H, n, i, &a, &b);
                 mx_all = std::max(mx_all, b - a);
             }
-        if ((rc = grow(ctx, &s.gathered[slot], &s.gathered_cap[slot], (size_t)world * K * mx_all * W * el, true))) return rc;
-        for (int i = 0; i < n; ++i)
-            if ((rc = grow(ctx, &send[i], &s.send_cap[slot][i], (size_t)K * mx_all * W * el, true))) return rc;
+        if ((rc = grow(ctx, &s.gathered[slot], &s.gathered_cap[slot], (size_t)world * K * mx_all * W * el,
+                       slot ? "shard gathered[1]" : "shard gathered[0]", true)))
+            return rc;
+        for (int i = 0; i < n; ++i) {
+            const std::string label = "shard send[" + std::to_string(slot) + "][" + std::to_string(i) + "]";
+            if ((rc = grow(ctx, &send[i], &s.send_cap[slot][i], (size_t)K * mx_all * W * el, label.c_str(), true))) return rc;
+        }
     }
     for (int i = 0; i < n; ++i) {
         // the launch groups slab i still lacks: every tile of the patch rows below its last image row (full groups: one may run into the next slab)
@@ -550,11 +560,13 @@ int umx_infer_image_sharded_dev(umx_ctx* ctx, const double* band_dev, int C_img,
     if (const int rc = shard_check(ctx, band_dev, H, W, band_row0, band_rows)) return rc;
     if (ctx->hs[0].busy || ctx->hs[1].busy)   // (slot 0's gather buffers are this entry's too)
         return fail(ctx, UMX_ERR_INVALID, "a submitted call is still in flight on this context: wait for it first");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    RunIO io;
-    io.band_f64 = band_dev;
-    io.out_full = out_full_dev;
-    return shard_drain(ctx, sharded_run(ctx, io, C_img, H, W, band_row0, band_rows, mean, stdv, mode, stitch, nslabs));
+    return guarded(ctx, true, true, [&]() -> int {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        RunIO io;
+        io.band_f64 = band_dev;
+        io.out_full = out_full_dev;
+        return shard_drain(ctx, sharded_run(ctx, io, C_img, H, W, band_row0, band_rows, mean, stdv, mode, stitch, nslabs));
+    });
 }
 
 // The same schedule fed the way the one-GPU line is fed (umx_infer_image_raw_submit): this rank's raw uint8 / uint16 rows come up
@@ -571,11 +583,11 @@ static int sharded_raw_enqueue(umx_ctx* ctx, int slot, const void* band_host, in
     const size_t raw_b = (size_t)C_img * std::max(band_rows, 0) * W * in_b;
     const size_t mm_off = (raw_b + 255) & ~(size_t)255;
     int rc;
-    if ((rc = grow(ctx, &hs.d_out, &hs.out_cap, mm_off + 64 * (size_t)std::max(C_img, 1) + 256))) return rc;
+    if ((rc = grow(ctx, &hs.d_out, &hs.out_cap, mm_off + 64 * (size_t)std::max(C_img, 1) + 256, slot ? "slot 1 d_out" : "slot 0 d_out"))) return rc;
     unsigned char* const base = (unsigned char*)hs.d_out;
     unsigned* const mm = (unsigned*)(base + mm_off);
     if (!out_full_dev) {
-        if ((rc = grow(ctx, &s.full_u8[slot], &s.full_u8_cap[slot], K * (size_t)H * W, true))) return rc;
+        if ((rc = grow(ctx, &s.full_u8[slot], &s.full_u8_cap[slot], K * (size_t)H * W, slot ? "shard full_u8[1]" : "shard full_u8[0]", true))) return rc;
         out_full_dev = (uint8_t*)s.full_u8[slot];
     }
     RunIO io;
@@ -597,7 +609,9 @@ static int sharded_raw_enqueue(umx_ctx* ctx, int slot, const void* band_host, in
         io.band_host = band_host;
     } else {
         // an engine whose gather reads float64 (exact-fp32 precision): the band goes up whole and is converted first
-        if ((rc = grow(ctx, (void**)&hs.d_image, &hs.image_cap, (size_t)C_img * std::max(band_rows, 1) * W * sizeof(double)))) return rc;
+        if ((rc = grow(ctx, (void**)&hs.d_image, &hs.image_cap, (size_t)C_img * std::max(band_rows, 1) * W * sizeof(double),
+                       slot ? "slot 1 d_image" : "slot 0 d_image")))
+            return rc;
         if (raw_b) HIP_TRY(ctx, hipMemcpyAsync(base, band_host, raw_b, hipMemcpyHostToDevice, ctx->stream));
         for (int c = 0; c < C_img && band_rows > 0; ++c)
             HIP_TRY(ctx, launch_raw_convert(base + (size_t)c * band_rows * W * in_b, bits, (size_t)band_rows * W, range ? 1 : 0, mm + 16 * c,
@@ -617,18 +631,22 @@ int umx_infer_image_sharded_raw_submit(umx_ctx* ctx, int slot, const void* band_
     if (const int rc = check_image(ctx, band_host || band_rows == 0, C_img, H, W, true, bits, stdv, mode, UMX_STITCH_FP16_COMPAT, range))
         return rc;
     if (const int rc = shard_check(ctx, band_host, H, W, band_row0, band_rows)) return rc;
-    return slot_submit(ctx, slot, [&] {
-        return shard_drain(ctx, sharded_raw_enqueue(ctx, slot, band_host, bits, C_img, H, W, band_row0, band_rows, range, mean, stdv, mode,
-                                                    nslabs, own_out_host, out_full_dev));
+    return guarded(ctx, true, false, [&]() -> int {   // (guard mode: umx_infer_image_wait checks the zones)
+        return slot_submit(ctx, slot, [&] {
+            return shard_drain(ctx, sharded_raw_enqueue(ctx, slot, band_host, bits, C_img, H, W, band_row0, band_rows, range, mean, stdv, mode,
+                                                        nslabs, own_out_host, out_full_dev));
+        });
     });
 }
 
 int umx_infer_image_sharded_raw(umx_ctx* ctx, const void* band_host, int bits, int C_img, int H, int W, int band_row0, int band_rows,
                                 const uint32_t* range, double mean, double stdv, int mode, int nslabs, uint8_t* own_out_host,
                                 uint8_t* out_full_dev) {
-    const int rc = umx_infer_image_sharded_raw_submit(ctx, 0, band_host, bits, C_img, H, W, band_row0, band_rows, range, mean, stdv, mode,
-                                                      nslabs, own_out_host, out_full_dev);
-    return rc ? rc : umx_infer_image_wait(ctx, 0);
+    return guarded(ctx, true, true, [&]() -> int {
+        const int rc = umx_infer_image_sharded_raw_submit(ctx, 0, band_host, bits, C_img, H, W, band_row0, band_rows, range, mean, stdv, mode,
+                                                          nslabs, own_out_host, out_full_dev);
+        return rc ? rc : umx_infer_image_wait(ctx, 0);
+    });
 }
 
 }  // extern "C"

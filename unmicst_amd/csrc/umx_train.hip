@@ -1744,7 +1744,7 @@ int arena_init(DevArena* a, std::string* why) {
     return UMX_OK;
 }
 
-hipError_t arena_alloc(DevArena* a, void** out, size_t bytes, bool zero, const char* label) {
+hipError_t arena_alloc(DevArena* a, void** out, size_t bytes, bool zero, const char* label, bool scoped) {
     bytes = std::max<size_t>(16, bytes);
     void* d = nullptr;
     if (a->fill < 0) {
@@ -1765,9 +1765,33 @@ hipError_t arena_alloc(DevArena* a, void** out, size_t bytes, bool zero, const c
     if (zero && (e = hipMemset(p + zone, 0, bytes)) != hipSuccess) return e;
     if ((e = hipDeviceSynchronize()) != hipSuccess) return e;   // (the trainer's streams do not wait for the null stream)
     while (*label == '&') ++label;
-    a->blocks.push_back({d, zone, bytes, zone, std::string(label) + " (#" + std::to_string(a->blocks.size()) + ")"});
+    a->blocks.push_back({d, zone, bytes, zone, std::string(label) + " (#" + std::to_string(a->serial++) + ")", scoped});
     *out = p + zone;
     return hipSuccess;
+}
+
+hipError_t arena_release(DevArena* a, void* p) {
+    void* base = p;
+    for (size_t i = 0; i < a->blocks.size(); ++i)
+        if (static_cast<char*>(a->blocks[i].base) + a->blocks[i].front == p) {
+            base = a->blocks[i].base;
+            a->blocks.erase(a->blocks.begin() + i);
+            break;
+        }
+    const auto it = std::find(a->allocs.begin(), a->allocs.end(), base);
+    if (it == a->allocs.end()) return hipErrorInvalidValue;   // not this arena's
+    a->allocs.erase(it);
+    return hipFree(base);
+}
+
+hipError_t arena_refill(const DevArena& a, hipStream_t stream) {
+    if (a.fill < 0) return hipSuccess;
+    for (const DevBlock& b : a.blocks) {
+        if (!b.scoped) continue;
+        const hipError_t e = hipMemsetAsync(static_cast<char*>(b.base) + b.front, a.fill, b.bytes, stream);
+        if (e != hipSuccess) return e;
+    }
+    return hipStreamSynchronize(stream);
 }
 
 int arena_check(const DevArena& a, std::string* msg) {

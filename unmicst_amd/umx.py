@@ -19,7 +19,7 @@ PREC_DEFAULT, PREC_F32, PREC_F16X3, PREC_F16X3_F6 = 0, 1, 2, 3      # enum umx_p
 PRECISIONS = {"default": PREC_DEFAULT, "f32": PREC_F32, "f16x3": PREC_F16X3, "f16f6": PREC_F16X3_F6}
 ERR_INVALID, ERR_HIP = 1, 4   # UMX_ERR_INVALID, UMX_ERR_HIP
 ERR_RANGE = 6   # UMX_ERR_RANGE
-ERR_GUARD = 7   # UMX_ERR_GUARD (debug guard mode of the trainer: a red zone was written)
+ERR_GUARD = 7   # UMX_ERR_GUARD (debug guard mode, UMX_DEBUG_GUARD: a red zone round a device buffer was written)
 MODE_ACCUMULATE, MODE_REPLACE = 0, 1
 STITCH_FP16_COMPAT, STITCH_FP32 = 0, 1
 
