@@ -405,6 +405,13 @@ UMX_API int umx_test_mx_pack_e2m3(const double* v32, uint8_t* out24);
  * refused layer and the split-precision planner's reason in umx_last_error(NULL) -- what UMX_PREC_DEFAULT falls back to the exact-fp32
  * engine on (and warns about). */
 UMX_API int umx_plan_check(const umx_hparams* hp);
+/* test entry (host only): the trainer's weight-gradient planner and kernel selection on one layer -- batch B, H x H pixels, X with Cxt
+ * channels per pixel of which each slab reads Cx from channel coff[s], G with Cg channels, nslab slabs (dy, dx: tap offset, mslab: tap of
+ * the master tensor); f32_route: as under UMX_TRAIN_WGRAD_F32; planes / XCs / GCs: whether the operands come with (hi, lo) planes and
+ * their stored channels.  line receives the layer's UMX_DEBUG_PLAN text followed by the kernel instantiation, the launch grid, the
+ * dynamic LDS bytes and how the reduce undoes the operand scales.  UMX_ERR_INVALID with the planner's reason in umx_last_error(NULL). */
+UMX_API int umx_test_wgrad_plan(int B, int H, int Cxt, int Cx, int Cg, int nslab, const int* dy, const int* dx, const int* mslab,
+                                const int* coff, int f32_route, int planes, int XCs, int GCs, char* line, size_t cap);
 UMX_API const char* umx_version(void);
 
 #ifdef __cplusplus

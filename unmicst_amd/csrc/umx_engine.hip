@@ -545,6 +545,36 @@ int umx_plan_check(const umx_hparams* hp) {
     return UMX_OK;
 }
 
+// The trainer's weight-gradient planner and kernel selection on one layer (umx_wgrad.hip), host only: wgrad_setup, then wgrad_select on
+// operands with or without planes, as the plan's UMX_DEBUG_PLAN text + the instantiation, its grid, its LDS bytes and the scale handling
+int umx_test_wgrad_plan(int B, int H, int Cxt, int Cx, int Cg, int nslab, const int* dy, const int* dx, const int* mslab, const int* coff,
+                        int f32_route, int planes, int XCs, int GCs, char* line, size_t cap) {
+    if (!dy || !dx || !mslab || !coff || !line || nslab < 1 || nslab > kWgMaxSlabs)
+        return fail(nullptr, UMX_ERR_INVALID, "umx_test_wgrad_plan: bad arguments");
+    WgradPlan w;
+    memset(&w, 0, sizeof w);
+    w.B = B; w.H = H; w.W = H;
+    w.Cxt = Cxt; w.Cx = Cx; w.Cg = Cg;
+    w.nslab = nslab;
+    for (int s = 0; s < nslab; ++s) {
+        w.dy[s] = (short)dy[s]; w.dx[s] = (short)dx[s]; w.mslab[s] = (short)mslab[s];
+        w.coff[s] = coff[s];
+    }
+    std::string why;
+    if (!wgrad_setup(&w, f32_route != 0, &why)) return fail(nullptr, UMX_ERR_INVALID, "%s", why.c_str());
+    WgradOperands o = {};
+    o.planes = planes != 0 && w.f16 && Cxt <= XCs && Cg <= GCs;   // (as the trainer's run_wgrad decides it)
+    o.XCs = XCs; o.GCs = GCs;
+    const WgradLaunch l = wgrad_select(w, o);
+    static const char* const scales[] = {"none", "max words", "plane inverse scales"};
+    char b[256];
+    snprintf(b, sizeof b, ", %s, launch %u x %u x %u, lds %zu, scales %s", l.name, l.grid.x, l.grid.y, l.grid.z, l.lds, scales[l.scales]);
+    const std::string text = wgrad_describe(w, "test") + b;
+    if (text.size() + 1 > cap) return fail(nullptr, UMX_ERR_INVALID, "umx_test_wgrad_plan: the line takes %zu bytes", text.size() + 1);
+    memcpy(line, text.c_str(), text.size() + 1);
+    return UMX_OK;
+}
+
 int umx_describe_graph(const umx_hparams* hp, char* json, size_t cap, size_t* needed) {
     std::string why;
     int rc = check_hp(hp, &why);

@@ -295,8 +295,18 @@ hipError_t launch_act_bwd(const ActParams& a, const float* dy0, const float* dy1
 // sums -> m12[2][C] = (mean g, mean g*xhat); dgamma = sum g*xhat, dbeta = sum g
 hipError_t launch_bn_bwd_finalize(const double* part, int nblk, size_t N, int C, float* dgamma, float* dbeta, float* m12,
                                   hipStream_t stream);
-// (bn_bwd_apply: g <- scale * (g - m1 - xhat*m2) in place, and leaky_bwd_s2d: gS[b,i,j,(pa*2+pb)*C + c] =
-//  d_us[b,2i+pa,2j+pb,c] * (us > 0 ? 1 : slope) -- 0.2 in v2, 0 in the legacy graph -- are declared with the weight-gradient kernels below: they track max |v|)
+// BN input gradient g <- scale * (g - m1 - xhat*m2) (in place) and LeakyReLU backward + space-to-depth of the transposed
+// conv's output gradient, gS[b,i,j,(pa*2+pb)*C + c] = d_us[b,2i+pa,2j+pb,c] * (us > 0 ? 1 : slope) -- 0.2 in v2, 0 in the
+// legacy graph; both track max |v| of what they write (bit pattern of a non-negative float, atomicMax on uint; gmax may be NULL)
+// (hi != NULL: dz also as (hi, lo) planes scaled by the power of two the bound bw[0] * bw[1] * (2 + bw[2]) -- max |gamma rstd|,
+//  max |g|, max |xhat| -- asks for; *inv_scale receives the inverse factor)
+hipError_t launch_bn_bwd_apply_max(float* g, const float* z, const float* stat, const float* m12, size_t N, int C,
+                                   unsigned* gmax, const unsigned* bw, float* inv_scale, _Float16* hi, _Float16* lo, int Cs,
+                                   int* overflow, hipStream_t stream);
+hipError_t launch_leaky_bwd_s2d_max(const float* d_us, const float* us, int B, int S, int C, float slope, float* gS, unsigned* gmax,
+                                    hipStream_t stream);
+// g = v > 0 ? dy : 0 (the legacy graph's ReLU backward; g may alias dy), max |g| into gmax (nullable)
+hipError_t launch_relu_bwd_max(const float* dy, const float* v, float* g, size_t n, unsigned* gmax, hipStream_t stream);
 
 // top layer: t0 = x W (1x1 conv, K <= 8 classes)
 hipError_t launch_head_fwd(const float* x, size_t N, int C, int K, const float* w, float* t0, hipStream_t stream);
@@ -318,11 +328,19 @@ struct RegSeg { const float* w; size_t n; float coef; };
 hipError_t launch_reg_loss(const RegSeg* segs_dev, int nseg, int kind, double* part, double* out, int slot,
                            hipStream_t stream);
 
-// weight gradient of a convolution on the fp32 matrix cores:  dW[s][ci][co] = sum_p X[p + (dy_s,dx_s)][coff_s + ci] * G[p][co]
+// reg'(w) of the regulariser (kind 1: c |w|, 2: c w^2), added by the reduces that finish a regularised tensor's gradient
+__device__ __forceinline__ float reg_grad(float w, int kind, float c) {
+    if (kind == 1) return w > 0.f ? c : (w < 0.f ? -c : 0.f);
+    if (kind == 2) return 2.0f * c * w;
+    return 0.f;
+}
+
+// ---- weight gradient of a convolution (umx_wgrad.hip):  dW[s][ci][co] = sum_p X[p + (dy_s,dx_s)][coff_s + ci] * G[p][co] ----------
 constexpr int kWgMaxSlabs = 32;
-struct WgradParams {
-    const float* X; int Cxt;      // NHWC, Cxt channels per pixel
-    const float* G; int Cg;       // NHWC [B,H,W,Cg]
+// A layer's plan, made once at build by wgrad_setup from B,H,W,Cxt,Cx,Cg,nslab,dy,dx,mslab,coff and never written again
+struct WgradPlan {
+    int Cxt;                      // X: NHWC, Cxt channels per pixel
+    int Cg;                       // G: NHWC [B,H,W,Cg]
     int B, H, W;
     int nslab, Cx;
     short dy[kWgMaxSlabs], dx[kWgMaxSlabs];
@@ -333,42 +351,54 @@ struct WgradParams {
     int tw_log2, th_log2, imgs;   // pixel tile = imgs x TH x TW = 128 pixels
     int hh, hw, imgplane, nhalo, ymin, xmin, tiles_y, tiles_x;
     int ntiles, tiles_per_slice, nslices;
-    int mi;                       // input-channel tiles (of 16) per workgroup: 1..3
     int vecx, vecg;               // 16-byte loads allowed
+    // the kind of kernel: thin > 0, else f16, else the fp32 MFMA kernel with mi channel tiles
+    int thin;                     // > 0: wgrad_thin_kernel (Cx <= 4, one slab group): rows of the image per workgroup
+    int f16;                      // 1: wgrad_f16x3 (W >= 8, Cx > 4, <= 9 slabs per group): 48 x 48 channel tiles, operands staged as (hi, lo) binary16
+    int mi;                       // input-channel tiles (of 16) per workgroup: 1..3
+    int hp, xs, gs;               // (f16) halo row pitch, X / G channel strides in LDS (halves)
+};
+// What one launch binds: the two tensors of this step and where the slices go
+struct WgradOperands {
+    const float* X;
+    const float* G;
     float* ws;                    // [slice][slab][Cx][Cg]
-    // split-precision variant (wgrad_f16x3): 48 x 48 channel tiles, operands staged as (hi, lo) binary16 planes
-    int f16;                      // 1: use it (W >= 8, Cx > 4, <= 9 slabs per group); 0: fp32 MFMA kernel
-    int hp, xs, gs;               // halo row pitch, X / G channel strides in LDS (halves)
     const unsigned* xmax;         // device word holding max|X| as float bits, written by the tensor's producer
     const unsigned* gmax;         // same for G
     int* overflow;                // set when a scaled operand leaves the binary16 range
     // plane-staged variant (planes = 1, f16 only): the operands as (hi, lo) binary16 NHWC planes with XCs / GCs stored channels
     // (multiples of 8, pad channels zero) and the inverse of the power-of-two scale each was stored with (NULL: unscaled)
-    int thin;                     // > 0: wgrad_thin_kernel (Cx <= 4, one slab group): rows of the image per workgroup
     int planes;
     const _Float16 *Xhi, *Xlo, *Ghi, *Glo;
     int XCs, GCs;
     const float *xinv, *ginv;
 };
-// BN input gradient g <- scale * (g - m1 - xhat*m2) (in place) and LeakyReLU backward + space-to-depth of the transposed
-// conv's output gradient; both track max |v| of what they write (bit pattern of a non-negative float, atomicMax on uint;
-// gmax may be NULL)
-// (hi != NULL: dz also as (hi, lo) planes scaled by the power of two the bound bw[0] * bw[1] * (2 + bw[2]) -- max |gamma rstd|,
-//  max |g|, max |xhat| -- asks for; *inv_scale receives the inverse factor)
-hipError_t launch_bn_bwd_apply_max(float* g, const float* z, const float* stat, const float* m12, size_t N, int C,
-                                   unsigned* gmax, const unsigned* bw, float* inv_scale, _Float16* hi, _Float16* lo, int Cs,
-                                   int* overflow, hipStream_t stream);
-hipError_t launch_leaky_bwd_s2d_max(const float* d_us, const float* us, int B, int S, int C, float slope, float* gS, unsigned* gmax,
-                                    hipStream_t stream);
-// g = v > 0 ? dy : 0 (the legacy graph's ReLU backward; g may alias dy), max |g| into gmax (nullable)
-hipError_t launch_relu_bwd_max(const float* dy, const float* v, float* g, size_t n, unsigned* gmax, hipStream_t stream);
-bool wgrad_setup(WgradParams* p, std::string* why);   // fills geometry, slab groups and slices from B,H,W,Cx,Cg,nslab,dy,dx,coff
-size_t wgrad_ws_floats(const WgradParams& p);
-hipError_t launch_wgrad(const WgradParams& p, hipStream_t stream);
-// g[(s*Ctot + c_off + ci)*Cg + co] = sum_slices ws (+ reg'(w)) ; optional second destination g2 (no reg) for the pair
-hipError_t launch_wgrad_reduce(const WgradParams& p, int Ctot, int c_off, float* g, const float* w, int reg_kind,
-                               float reg_c, float* g2, hipStream_t stream);
+struct WgradParams : WgradPlan, WgradOperands {};   // the kernels' by-value argument
 
+// How the reduce undoes the scales the operands were multiplied with: not at all (fp32 kernels), by the scales wgrad_f16x3<false>
+// derived from the tensors' max words, or by the inverse scales the planes were stored with
+enum { WG_SCALES_NONE = 0, WG_SCALES_MAX = 1, WG_SCALES_INV = 2 };
+struct WgGrid { unsigned x, y, z; };   // slices x channel chunks x slab groups (thin: one chunk, one group)
+// Which of the 16 instantiations a plan runs on these operands, and how: the only place that decides it
+struct WgradLaunch {
+    int kernel;                   // index into umx_wgrad.hip's table, -1: the plan fits none (a planner error)
+    const char* name;             // e.g. "wgrad_f16x3<true,true>"
+    WgGrid grid;
+    size_t lds;                   // dynamic LDS bytes
+    int scales;                   // WG_SCALES_*
+};
+// fills geometry, slab groups, slices and the kind of kernel (f32_route: never wgrad_f16x3, UMX_TRAIN_WGRAD_F32)
+bool wgrad_setup(WgradPlan* p, bool f32_route, std::string* why);
+WgGrid wgrad_grid(const WgradPlan& p);
+size_t wgrad_ws_floats(const WgradPlan& p);
+std::string wgrad_describe(const WgradPlan& p, const char* what);   // "wgrad <what>: ...", the plan's line of UMX_DEBUG_PLAN
+WgradLaunch wgrad_select(const WgradPlan& p, const WgradOperands& o);   // (reads o.planes, o.XCs, o.GCs only)
+hipError_t launch_wgrad(const WgradPlan& p, const WgradOperands& o, const WgradLaunch& l, hipStream_t stream);
+// g[(s*Ctot + c_off + ci)*Cg + co] = sum_slices ws (+ reg'(w)) ; optional second destination g2 (no reg) for the pair
+hipError_t launch_wgrad_reduce(const WgradPlan& p, const WgradOperands& o, const WgradLaunch& l, int Ctot, int c_off, float* g,
+                               const float* w, int reg_kind, float reg_c, float* g2, hipStream_t stream);
+
+// ---- optimiser, K-split reduce, initial state (umx_train_kernels.hip) ------------------------------------------------------
 struct OptParams {
     int kind;                 // 0 Adam, 1 Momentum
     float lr, lr_t, beta1, beta2, eps, momentum;

@@ -95,14 +95,14 @@ struct LBlock {                 // one block of the legacy graph: a chain of nEx
     std::vector<TConv> fwd;     // fwd[0] reads the block input (down: w1; up: unused, c_fwd_u is the concat conv), fwd[e >= 1] reads
                                 // a[e-1] (wextra_{e-1}); a down block's last one also reads the block input through the 1x1 shortcut
     std::vector<TConv> dg;      // dg[e >= 1]: input gradient of fwd[e] into a[e-1]
-    std::vector<WgradParams> wg;   // wg[e >= 1]: weight gradient of wextra_{e-1}
+    std::vector<WgradPlan> wg;   // wg[e >= 1]: weight gradient of wextra_{e-1}
     std::vector<size_t> o_wx;   // wextra offsets in the parameter vector
     std::vector<float*> y;      // y[e]: output of conv e, pre-ReLU (down: y[E] = z = main + shortcut)
     std::vector<Act> a;         // a[e] = relu(y[e]) for the convolution after it: e < E (down), e <= E (up: a[E] is the output)
     std::vector<unsigned*> gmax;   // max |d loss / d y[e]| of the current step
     float* ident = nullptr;     // [4][C] identity statistics: act_fwd as a plain ReLU with the plane writer
     TConv dg_sh;                // (down) input gradient of the shortcut
-    WgradParams wg_sh;          // (down) weight gradient of the shortcut: one slab
+    WgradPlan wg_sh;            // (down) weight gradient of the shortcut: one slab
 };
 
 }  // namespace
@@ -156,6 +156,7 @@ struct umx_trainer {
     // forward / input-gradient convolutions on conv_f16x3 (UMX_TRAIN_CONV_F32=1: the exact-fp32 kernels of rounds 1-3)
     bool range_pending = false;         // a training step raised the range flag and an eval pass cleared it before umx_trainer_loss saw it
     bool hconv = true;
+    bool wg_f32 = false;                // UMX_TRAIN_WGRAD_F32: no weight gradient takes the split-precision kernel
     bool wg_planes = true;              // the split-precision weight gradient stages from the planes
     const float* h_blob = nullptr;      // (during build) the initial parameters on the host: weight scales
     std::vector<HConvParams> hls;       // the split-precision plans' launch parameters
@@ -171,8 +172,8 @@ struct umx_trainer {
     // launches
     std::vector<TConv> c_fwd_d, c_dg_d, c_T, c_fwd_u, c_dg_us, c_dg_skip, c_dg_T;
     TConv c_fwd_b, c_dg_b;
-    std::vector<WgradParams> wg_d, wg_u0, wg_u1, wg_T;
-    WgradParams wg_b;
+    std::vector<WgradPlan> wg_d, wg_u0, wg_u1, wg_T;
+    WgradPlan wg_b;
     std::vector<PackDesc> packs;
     PackDesc* d_packs = nullptr;
     RegSeg* d_regsegs = nullptr;  int n_regsegs = 0;
@@ -672,7 +673,7 @@ TapSet same_taps(int ks, bool flipped) {   // stride-1 SAME conv (or its input g
     return t;
 }
 
-int setup_wgrad(umx_trainer* tr, WgradParams& w, const char* what, int H, int Cxt, int Cx, int Cg, const TapSet& slabs,
+int setup_wgrad(umx_trainer* tr, WgradPlan& w, const char* what, int H, int Cxt, int Cx, int Cg, const TapSet& slabs,
                 const std::vector<int>& coff) {
     memset(&w, 0, sizeof w);
     w.B = tr->B; w.H = H; w.W = H;
@@ -686,17 +687,9 @@ int setup_wgrad(umx_trainer* tr, WgradParams& w, const char* what, int H, int Cx
         w.coff[s] = coff.empty() ? 0 : coff[s];
     }
     std::string why;
-    if (!wgrad_setup(&w, &why)) return tfail(tr, UMX_ERR_INVALID, "%s: %s", what, why.c_str());
+    if (!wgrad_setup(&w, tr->wg_f32, &why)) return tfail(tr, UMX_ERR_INVALID, "%s: %s", what, why.c_str());
     tr->ws_floats = std::max(tr->ws_floats, wgrad_ws_floats(w));
-    if (getenv("UMX_DEBUG_PLAN")) {
-        std::string groups;
-        for (int g = 0; g < w.ngroups; ++g) groups += (g ? "/" : "") + std::to_string(w.gcount[g]);
-        fprintf(stderr, "[umx train] wgrad %s: %d x %d, X %d (of %d) ch x G %d ch, %d slabs in groups %s, %s, %d img/tile, %d tiles, %d slices x %d tiles, "
-                        "grid %d x %d x %d\n",
-                what, H, H, Cx, Cxt, Cg, w.nslab, groups.c_str(), w.thin ? "thin" : w.f16 ? "f16x3" : "fp32 mfma", w.imgs, w.ntiles, w.nslices,
-                w.tiles_per_slice, w.nslices,
-                w.thin ? 1 : w.f16 ? ((Cx + 47) / 48) * ((Cg + 47) / 48) : ((Cx + 16 * w.mi - 1) / (16 * w.mi)) * ((Cg + 63) / 64), w.thin ? 1 : w.ngroups);
-    }
+    if (getenv("UMX_DEBUG_PLAN")) fprintf(stderr, "[umx train] %s\n", wgrad_describe(w, what).c_str());
     return UMX_OK;
 }
 
@@ -759,23 +752,24 @@ int bn_backward(umx_trainer* tr, BnSite& s, const ActParams& a, const float* dy0
 
 // (where both operands have (hi, lo) planes the split-precision kernel stages from them -- half the bytes, no conversion -- and undoes
 // the inverse scales they were stored with)
-int run_wgrad(umx_trainer* tr, WgradParams& w, const Act& X, const Act& G, int Ctot, int c_off, size_t w_off, float reg,
+int run_wgrad(umx_trainer* tr, const WgradPlan& w, const Act& X, const Act& G, int Ctot, int c_off, size_t w_off, float reg,
               size_t pair_off /* SIZE_MAX: none */, hipStream_t stream) {
-    w.X = X.x;
-    w.G = G.x;
-    w.planes = 0;
+    WgradOperands o = {};
+    o.X = X.x;
+    o.G = G.x;
     if (w.f16 && tr->wg_planes && X.h.hi && G.h.hi && w.Cxt <= X.h.Cs && w.Cg <= G.h.Cs) {
-        w.planes = 1;
-        w.Xhi = X.h.hi; w.Xlo = X.h.lo; w.XCs = X.h.Cs;
-        w.Ghi = G.h.hi; w.Glo = G.h.lo; w.GCs = G.h.Cs;
-        w.xinv = X.inv; w.ginv = G.inv;
+        o.planes = 1;
+        o.Xhi = X.h.hi; o.Xlo = X.h.lo; o.XCs = X.h.Cs;
+        o.Ghi = G.h.hi; o.Glo = G.h.lo; o.GCs = G.h.Cs;
+        o.xinv = X.inv; o.ginv = G.inv;
     }
-    w.ws = stream == tr->side2 ? tr->d_ws2 : tr->d_ws;   // (each side stream has its own slice workspace)
-    w.xmax = X.max;
-    w.gmax = G.max;
-    w.overflow = reinterpret_cast<int*>(tr->d_maxw + tr->n_maxw);
-    T_HIP(tr, launch_wgrad(w, stream));
-    T_HIP(tr, launch_wgrad_reduce(w, Ctot, c_off, tr->d_g + w_off, tr->d_w + w_off, reg > 0.f ? tr->o.reg_kind : 0, reg,
+    o.ws = stream == tr->side2 ? tr->d_ws2 : tr->d_ws;   // (each side stream has its own slice workspace)
+    o.xmax = X.max;
+    o.gmax = G.max;
+    o.overflow = reinterpret_cast<int*>(tr->d_maxw + tr->n_maxw);
+    const WgradLaunch l = wgrad_select(w, o);
+    T_HIP(tr, launch_wgrad(w, o, l, stream));
+    T_HIP(tr, launch_wgrad_reduce(w, o, l, Ctot, c_off, tr->d_g + w_off, tr->d_w + w_off, reg > 0.f ? tr->o.reg_kind : 0, reg,
                                   pair_off == SIZE_MAX ? nullptr : tr->d_g + pair_off, stream));
     return UMX_OK;
 }
@@ -1150,6 +1144,7 @@ int alloc_params(umx_trainer* tr, const float* blob, size_t blob_floats, size_t 
 // allocates them) unless UMX_TRAIN_CONV_F32 asks for the exact-fp32 kernels
 int select_route(umx_trainer* tr, const float* blob) {
     tr->hconv = !getenv("UMX_TRAIN_CONV_F32");
+    tr->wg_f32 = getenv("UMX_TRAIN_WGRAD_F32") != nullptr;
     if (const char* e = getenv("UMX_TRAIN_WSCALE_EVERY")) tr->wscale_every = atoi(e);
     tr->wg_planes = tr->hconv;
     tr->h_blob = blob;
@@ -1610,7 +1605,7 @@ int enqueue_legacy(umx_trainer* tr, const float* data, const float* labels, cons
         T_HIP(tr, launch_relu_bwd_max(dy, y, g->x, g->npix(B) * C, gw, st));
         return to_h16(tr, *g, st);
     };
-    auto wgrad = [&](WgradParams& w, const Act& X, const Act& G, int Ctot, int c_off, size_t w_off) -> int {
+    auto wgrad = [&](const WgradPlan& w, const Act& X, const Act& G, int Ctot, int c_off, size_t w_off) -> int {
         return run_wgrad(tr, w, X, G, Ctot, c_off, w_off, 0.f, SIZE_MAX, st);
     };
     // the extra convolutions of a chain, last first: *g is d/dy[E] (slot 0) on entry, d/dy[e] in slot (E - e) & 1 on the way, d/dy[0] on return

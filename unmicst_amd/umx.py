@@ -32,7 +32,7 @@ EXPORTS = [
     "umx_infer_image_sharded_dev", "umx_infer_image_sharded_raw", "umx_infer_image_sharded_raw_submit",
     "umx_band_tiles_dev", "umx_stitch_dev", "umx_profile_enable", "umx_profile_read", "umx_prof_entry_size", "umx_test_double_to_half", "umx_test_double_to_half_dev",
     "umx_test_gauss_weights", "umx_test_resize_dev", "umx_test_rescale_dev", "umx_test_plane_range_dev", "umx_test_half_to_u8_dev",
-    "umx_describe", "umx_describe_graph", "umx_plan_check", "umx_test_mx_pack_e2m3", "umx_version",
+    "umx_describe", "umx_describe_graph", "umx_plan_check", "umx_test_wgrad_plan", "umx_test_mx_pack_e2m3", "umx_version",
     "umx_label_options_check", "umx_labeler_create", "umx_labeler_destroy", "umx_labeler_last_error", "umx_labeler_run",
     "umx_labeler_run_dev", "umx_labeler_objects", "umx_labeler_last_ms",
 ]
@@ -341,6 +341,18 @@ def plan_check(hp: HParams) -> str:
     L.umx_plan_check.argtypes = [ctypes.c_void_p]
     rc = L.umx_plan_check(ctypes.byref(h))
     return "" if rc == 0 else L.umx_last_error(None).decode()
+
+
+def wgrad_plan(B: int, H: int, Cxt: int, Cx: int, Cg: int, slabs, f32_route: bool, planes: bool, XCs: int = 0, GCs: int = 0) -> str:
+    """umx_test_wgrad_plan: the weight-gradient plan and kernel selection of one layer as a line of text; slabs = [(dy, dx, master tap,
+    channel offset)].  Host only."""
+    L = load()
+    cols = [(ctypes.c_int * len(slabs))(*[int(s[k]) for s in slabs]) for k in range(4)]
+    buf = ctypes.create_string_buffer(1024)
+    L.umx_test_wgrad_plan.restype = ctypes.c_int
+    L.umx_test_wgrad_plan.argtypes = [ctypes.c_int] * 6 + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4 + [ctypes.c_char_p, ctypes.c_size_t]
+    _check(L, L.umx_test_wgrad_plan(B, H, Cxt, Cx, Cg, len(slabs), *cols, int(f32_route), int(planes), XCs, GCs, buf, len(buf)))
+    return buf.value.decode()
 
 
 def auto_batch(hp: HParams, arena_bytes: float = 12 * 2 ** 30) -> int:
