@@ -274,6 +274,12 @@ UMX_API int umx_infer_image_sharded_raw(umx_ctx* ctx, const void* band_host, int
  *   labels         int32 [H][W]: the kept objects (area >= A) numbered 1..N in raster order of their first pixel, 0 elsewhere --
  *                  scipy.ndimage.label with its default structure, the area filter, and a renumbering that keeps the order;
  *   table          one umx_label_object per kept object in label order, integers throughout (centroid = sum / area on the host).
+ * Growth (grow_radius R >= 1 and a class set G): the contour class keeps touching nuclei apart
+ * and is also the rim of every nucleus, so the objects above are the cores.  With R > 0 the kept objects are seeds (min_area applies
+ * to them, before any growth) and grow back over the domain = pixels with label 0 whose pred is in G, in R synchronous levels: at
+ * every level each domain pixel that is still 0 and has a labelled 4-neighbour takes the smallest label among them, all pixels
+ * deciding on the state of the level before.  N and the numbering do not change; every object keeps its seed and stays
+ * 4-connected; a pixel goes to a seed nearest through the domain, a tie to the smaller label; the table is that of the grown labels.
  * Every value is an integer, so nothing depends on the order in which atomics arrive: two calls give the same bytes.
  * A labeler needs no model: it owns a stream and its device buffers (two int32 planes of H * W, the K input planes, one int32 per
  * UMX_LABEL_SCAN_BLOCK pixels and the table), grown on demand and kept between runs.  UMX_DEBUG_GUARD (include/umx_train.h) puts red
@@ -282,8 +288,10 @@ UMX_API int umx_infer_image_sharded_raw(umx_ctx* ctx, const void* band_host, int
 typedef struct umx_label_options {
     int32_t cls;             /* 0 .. K-1, in the model's class order */
     int32_t min_area;        /* 1 .. UMX_LABEL_MAX_MIN_AREA pixels */
-    int32_t reserved[6];     /* must be zero */
-} umx_label_options;
+    int32_t grow_radius;     /* 0: no growth (then grow_classes must be 0 too); else 1 .. UMX_LABEL_MAX_GROW levels */
+    uint32_t grow_classes;   /* bit k set: class k (model's class order, k < K) belongs to the growth domain */
+    int32_t reserved[4];     /* must be zero */
+} umx_label_options;             /* 32 bytes; grow_radius and grow_classes were reserved words: zero is the call of before */
 typedef struct umx_label_object {
     int32_t area, y0, x0, y1, x1, reserved;   /* pixels; the inclusive bounding box */
     int64_t sum_y, sum_x;                     /* over the object's pixels */
@@ -298,8 +306,13 @@ typedef struct umx_labeler umx_labeler;
 #define UMX_LABEL_STRIP_ROWS 32
 #define UMX_LABEL_THREADS 1024
 #define UMX_LABEL_SCAN_BLOCK 2048
+/* The growth: its largest radius, and the geometry of its kernel -- a workgroup owns a tile of UMX_LABEL_GROW_TILE x
+ * UMX_LABEL_GROW_TILE pixels and loads UMX_LABEL_GROW_HALO more on every side, so one launch advances up to UMX_LABEL_GROW_HALO
+ * levels and a call takes ceil(R / UMX_LABEL_GROW_HALO) of them.  (Enumerators: constant expressions in C and C++ alike.) */
+enum { UMX_LABEL_MAX_GROW = 255, UMX_LABEL_GROW_TILE = 64, UMX_LABEL_GROW_HALO = 8 };
 /* Host only, no device: H, W >= 1; H * W <= 2^31 - 1 (a flat pixel index is an int32); 1 <= K <= 16; 0 <= cls < K;
- * 1 <= min_area <= 65536; reserved words zero.  UMX_OK, or UMX_ERR_INVALID with the reason in msg (cap bytes; may be NULL). */
+ * 1 <= min_area <= 65536; grow_radius 0 with grow_classes 0, or 1 <= grow_radius <= 255 with a non-empty grow_classes that has no
+ * bit at or above K; reserved words zero.  UMX_OK, or UMX_ERR_INVALID with the reason in msg (cap bytes; may be NULL). */
 UMX_API int umx_label_options_check(const umx_label_options* o, int K, int H, int W, char* msg, size_t cap);
 /* UMX_ERR_NO_DEVICE without a gfx950 device: there is no CPU fallback. */
 UMX_API int umx_labeler_create(int device_ordinal, umx_labeler** out);

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time the label mask (umx_labeler_run) on synthetic H x W stacks of K = 3 uint8 planes (GPU box); one JSON
-line.  usage: bench_label.py [H=16384] [W=H] [--reps 3]
+line.  usage: bench_label.py [H=16384] [W=H] [--reps 3] [--grow R]
 
 Two inputs, both made here by pure-numpy recipes (no scipy in the generators, nothing from tests/):
   blobs  nuclei-like discs: the image is cut into 32 x 32 cells; a seeded draw keeps 60 % of them, and each kept cell gets one disc of
@@ -9,7 +9,11 @@ Two inputs, both made here by pure-numpy recipes (no scipy in the generators, no
   salt   every pixel an object pixel with probability 0.6 (seeded): the many-small-objects extreme, about one object per 40 pixels.
 Per input: the upload, kernel and download milliseconds umx_labeler_last_ms reports (HIP events on the labeler's stream; the best
 of --reps runs after one warm-up that also grows the buffers), the object count, and the seconds scipy.ndimage.label + np.bincount
-take on the same object mask on this box's CPU share."""
+take on the same object mask on this box's CPU share.
+--grow R: the blobs input alone, its discs as cores inside bodies whose radii are RIM = 3 pixels larger (the rim is the contour class,
+plane 1, and the growth's default domain).  The same planes are labelled without and with the growth; the object count must agree,
+and "grow_ms" is the difference of the two kernel times: what the growth adds to a call (its ceil(R / 8) launches and the pass that
+writes the labels and the table from the grown plane, less the seed stage's last launch, which it replaces)."""
 import argparse
 import json
 import os
@@ -23,9 +27,11 @@ sys.path.insert(0, ROOT)
 from unmicst_amd import umx  # noqa: E402
 
 CELL = 32
+RIM = 3
 
 
-def blob_mask(H, W, seed=1):
+def blob_mask(H, W, seed=1, rim=0):
+    """rim > 0: the same discs with their radii larger by `rim` (the bodies whose cores the plain discs are)"""
     rng = np.random.default_rng(seed)
     ny, nx = -(-H // CELL), -(-W // CELL)
     keep = rng.random((ny, nx)) < 0.6
@@ -38,7 +44,7 @@ def blob_mask(H, W, seed=1):
     for y0 in range(0, ny, band):
         s = slice(y0, min(ny, y0 + band))
         d2 = (oy[None, None] - cy[s, :, None, None]) ** 2 + (ox[None, None] - cx[s, :, None, None]) ** 2
-        disc = (d2 <= (r[s, :, None, None] ** 2)) & keep[s, :, None, None]          # [cells y, cells x, 32, 32]
+        disc = (d2 <= ((r[s, :, None, None] + rim) ** 2)) & keep[s, :, None, None]          # [cells y, cells x, 32, 32]
         n = disc.shape[0]
         mask[y0 * CELL:(y0 + n) * CELL] = disc.transpose(0, 2, 1, 3).reshape(n * CELL, nx * CELL)
     return mask[:H, :W]
@@ -48,10 +54,11 @@ def salt_mask(H, W, seed=2):
     return np.random.default_rng(seed).random((H, W), dtype=np.float32) < 0.6
 
 
-def planes_of(mask):
+def planes_of(mask, bodies=None):
+    """bodies (a superset of mask): their pixels off the mask are the contour class, plane 1 at 210 over 20 / 25"""
     planes = np.empty((3,) + mask.shape, np.uint8)
-    planes[0] = np.where(mask, 20, 200)
-    planes[1] = 30
+    planes[0] = np.where(mask if bodies is None else bodies, 20, 200)
+    planes[1] = 30 if bodies is None else np.where(bodies & ~mask, 210, 30)
     planes[2] = np.where(mask, 200, 25)
     return planes
 
@@ -64,15 +71,49 @@ def scipy_seconds(mask):
     return time.perf_counter() - t, n, int(area[1:].sum())
 
 
+def best_kernel_ms(lb, planes, reps, **kw):
+    """-> (objects, (upload, kernel, download) ms of the run with the least kernel time) after one warm-up that grows the buffers"""
+    _, objects = lb.run(planes, want_labels=False, **kw)
+    best = None
+    for _ in range(reps):
+        lb.run(planes, want_labels=False, **kw)
+        ms = lb.last_ms()
+        if best is None or ms[1] < best[1]:
+            best = ms
+    return objects, best
+
+
+def grow_bench(a, H, W):
+    core, bodies = blob_mask(H, W), blob_mask(H, W, rim=RIM)
+    planes = planes_of(core, bodies)
+    tile, halo = umx.LABEL_GROW_TILE, umx.LABEL_GROW_HALO
+    launches = -(-a.grow // halo)
+    with umx.Labeler(a.device) as lb:
+        seeds, plain = best_kernel_ms(lb, planes, a.reps)
+        grown, with_growth = best_kernel_ms(lb, planes, a.reps, grow=a.grow)
+    assert len(seeds) == len(grown) and (grown["area"] >= seeds["area"]).all()
+    # what one growth launch moves at most: the label word and, where it is 0, the K class bytes of every pixel of a tile and its halo;
+    # one label word written per pixel
+    read = (1 + 2 * halo / tile) ** 2 * (4 + planes.shape[0])
+    return {"grow": a.grow, "rim": RIM, "objects": len(seeds), "seed_pixels": int(seeds["area"].sum()), "grown_pixels": int(grown["area"].sum()),
+            "kernel_ms": round(plain[1], 3), "kernel_ms_with_growth": round(with_growth[1], 3),
+            "grow_ms": round(with_growth[1] - plain[1], 3), "grow_launches": launches,
+            "bytes_per_launch_upper": int((read + 4) * H * W)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("H", type=int, nargs="?", default=16384)
     ap.add_argument("W", type=int, nargs="?", default=None)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--grow", type=int, default=0)
     a = ap.parse_args()
     H, W = a.H, a.W or a.H
     out = {"tool": "bench_label", "H": H, "W": W, "K": 3, "min_area": 1, "reps": a.reps}
+    if a.grow:
+        print(json.dumps(dict(out, **grow_bench(a, H, W))))
+        return
     with umx.Labeler(a.device) as lb:
         for name, mask in (("blobs", blob_mask(H, W)), ("salt", salt_mask(H, W))):
             planes = planes_of(mask)

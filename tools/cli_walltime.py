@@ -5,7 +5,8 @@ nucleiDAPI weights) on an N x N uint16 TIFF, with the per-stage breakdown the dr
 usage: cli_walltime.py [N=16384] [other-tree ...]   -- every further argument is another checkout of the repo (with its own built
 libumx.so) whose UnMicst.py is timed on the same file, same box: how a round's change is compared with the round before.
        cli_walltime.py N --label   -- only this tree: twice without and twice with --labelMask (the `label` stage: stacking the
-planes, the labelling call, the int32 page and the table)."""
+planes, the labelling call, the int32 page and the table).
+       cli_walltime.py N --label --grow R   -- and twice with --labelMask --labelGrow R as well."""
 import json
 import os
 import subprocess
@@ -38,8 +39,13 @@ def one(tree, path, out, env_extra, label, n, script="UnMicst.py", what="legacy 
 
 def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 16384
-    label_only = "--label" in sys.argv[2:]
-    others = [a for a in sys.argv[2:] if a != "--label"]
+    rest = sys.argv[2:]
+    label_only = "--label" in rest
+    grow = None
+    if "--grow" in rest:
+        grow = str(int(rest[rest.index("--grow") + 1]))
+        del rest[rest.index("--grow"):rest.index("--grow") + 2]
+    others = [a for a in rest if a != "--label"]
     hp, blob, mean, std = helpers.load_nuclei_dapi()
     raw = helpers.load_sample_105()[0]
     reps = (-(-n // raw.shape[0]), -(-n // raw.shape[1]))
@@ -55,6 +61,9 @@ def main():
                 one(ROOT, path, os.path.join(d, "out_plain%d" % rep), env, "this tree, run %d" % (rep + 1), n)
                 one(ROOT, path, os.path.join(d, "out_label%d" % rep), env, "this tree, --labelMask, run %d" % (rep + 1), n,
                     extra=["--labelMask"])
+                if grow:
+                    one(ROOT, path, os.path.join(d, "out_grow%d" % rep), env, "this tree, --labelMask --labelGrow %s, run %d" % (grow, rep + 1), n,
+                        extra=["--labelMask", "--labelGrow", grow])
             for f in sorted(os.listdir(os.path.join(d, "out_label0"))):
                 if "_Labels_" in f or "_Objects_" in f:
                     print("  %-40s %d bytes" % (f, os.path.getsize(os.path.join(d, "out_label0", f))))

@@ -19,6 +19,11 @@
 //   (N comes back to the host: the only synchronisation inside a call; the table is sized for it)
 //   label_table_init_kernel, label_write_kernel   one wave per row: labels = Q[P], 0 off the objects, in place over P or into the
 //                         caller's plane; every run adds its length, y * length, the sum of its x and its extent to record label - 1
+// With a growth (grow_radius R > 0) the last launch is replaced by
+//   label_seed_kernel     one thread per pixel: the seed labels Q[P] in place over P, no table; Q is free from here on
+//   label_grow_kernel     ceil(R / UMX_LABEL_GROW_HALO) launches, P -> Q -> P ...: one workgroup per tile of 64 x 64 pixels loads the
+//                         tile and a halo of 8 into LDS, runs up to 8 synchronous levels there and writes its tile to the other plane
+//   label_grown_kernel    one wave per row: the labels from the plane the last launch wrote to where the call wants them, and the table
 //
 // Why no workgroup waits for another one, and none reads inside a kernel what another one writes in it: in the strip launch a workgroup
 // touches only pixels of its strip -- a link made there joins two run heads of the strip, so a walk from a pixel of the strip stays in
@@ -49,6 +54,13 @@ constexpr int kScanBlock = UMX_LABEL_SCAN_BLOCK;
 constexpr int kScanWaves = 4;                            // a block of the scan: 4 waves x 8 chunks x 64 pixels
 constexpr int kScanChunks = kScanBlock / (64 * kScanWaves);
 static_assert(kScanChunks * 64 * kScanWaves == kScanBlock, "a scan block is a whole number of 64-pixel chunks per wave");
+constexpr int kGrowTile = UMX_LABEL_GROW_TILE, kGrowHalo = UMX_LABEL_GROW_HALO;
+constexpr int kGrowSide = kGrowTile + 2 * kGrowHalo;     // the region a growth workgroup holds in LDS: 80 x 80 int32 = 25 600 B
+constexpr int kGrowPix = kGrowSide * kGrowSide;
+constexpr int kGrowThreads = 256;
+constexpr int kGrowPer = kGrowPix / kGrowThreads;        // region pixels per thread
+static_assert(kGrowPer * kGrowThreads == kGrowPix && (kGrowTile * kGrowTile) % kGrowThreads == 0, "whole rounds over the region and the tile");
+static_assert(kGrowHalo >= 1 && kGrowPix * sizeof(int) <= 32 * 1024, "five growth workgroups or more per CU by LDS");
 static_assert(UMX_LABEL_MAX_MIN_AREA == UMX_OBJECT_MAX_MIN_AREA, "one bound on min_area");
 static_assert(UMX_BORDER_CONNECTIVITY == 4, "the merges below join a pixel with the one above it and row runs: 4-connectivity");
 static_assert(sizeof(umx_label_object) == 40, "the table's record");
@@ -280,6 +292,18 @@ __global__ void __launch_bounds__(kPixThreads) label_table_init_kernel(umx_label
     table[j] = o;
 }
 
+// one row run [start, start + len) of row y into its object's record: integer atomics that nothing reads in the launch
+__device__ inline void table_add(umx_label_object* o, int y, int start, int len) {
+    atomicAdd(&o->area, len);
+    atomicMin(&o->y0, y);
+    atomicMax(&o->y1, y);
+    atomicMin(&o->x0, start);
+    atomicMax(&o->x1, start + len - 1);
+    const unsigned long long l = (unsigned long long)len;
+    atomicAdd(reinterpret_cast<unsigned long long*>(&o->sum_y), (unsigned long long)y * l);
+    atomicAdd(reinterpret_cast<unsigned long long*>(&o->sum_x), (unsigned long long)start * l + l * (l - 1ull) / 2ull);
+}
+
 // grid ceil(H / 4).  P: roots; Q: the numbers at the roots (0: dropped).  out (may be null, may be P itself): a thread reads P at its
 // own pixel and writes out there; Q is only read.  table[label - 1], label <= N: integer atomics that nothing reads in this launch.
 __global__ void __launch_bounds__(64 * kRowWaves) label_write_kernel(const int* P, const int* __restrict__ Q, int H, int W, int* out,
@@ -296,17 +320,119 @@ __global__ void __launch_bounds__(64 * kRowWaves) label_write_kernel(const int* 
             if (out) out[row + x] = label;
             return label - 1;
         },
-        [&](int key, int start, int len) {
-            umx_label_object* o = table + key;
-            atomicAdd(&o->area, len);
-            atomicMin(&o->y0, y);
-            atomicMax(&o->y1, y);
-            atomicMin(&o->x0, start);
-            atomicMax(&o->x1, start + len - 1);
-            const unsigned long long l = (unsigned long long)len;
-            atomicAdd(reinterpret_cast<unsigned long long*>(&o->sum_y), (unsigned long long)y * l);
-            atomicAdd(reinterpret_cast<unsigned long long*>(&o->sum_x), (unsigned long long)start * l + l * (l - 1ull) / 2ull);
-        });
+        [&](int key, int start, int len) { table_add(table + key, y, start, len); });
+}
+
+// ---- the growth ----
+// one thread per pixel, i < npix: the seed labels in place over P (roots, -1 off the objects) from the numbers at the roots in Q.  A
+// thread writes P at its own pixel only and nobody writes Q.  No table: the seeds' records would count their pixels twice.
+__global__ void __launch_bounds__(kPixThreads) label_seed_kernel(int* __restrict__ P, const int* __restrict__ Q, long long npix) {
+    const long long i = (long long)blockIdx.x * kPixThreads + threadIdx.x;
+    if (i >= npix) return;
+    const int p = P[i];
+    P[i] = p >= 0 ? Q[p] : 0;
+}
+
+// `levels` (1 .. kGrowHalo) synchronous levels of the growth, src -> dst (two different planes).  grid tiles_y * tiles_x, one
+// workgroup per tile of 64 x 64 pixels: it loads the tile and a halo of 8 into LDS as one int per pixel -- the label (> 0), -1 for a
+// pixel of the domain that is still empty (label 0 and first maximum of the planes in G), 0 for any other and for every pixel
+// outside the image -- runs the levels there and writes its own tile.  A level: every thread reads its empty pixels' four
+// neighbours (a neighbour outside the loaded region counts as absent) and keeps the least label among them in a register, a
+// barrier, the changed pixels are written, a barrier.  The pixels whose value may be wrong for want of a neighbour are the
+// region's outer ring after the first level and one ring more after each further one: after <= 8 levels they have not reached the
+// tile.  The levels end early, for the whole workgroup, when the region has no empty domain pixel or no label, or when a level
+// changed nothing (then no later one can).
+// Bounds: region pixel r = j * 256 + thread < 6400 = 25 * 256; its image row and column are formed in 64 bits (y0 + 79 may pass
+// 2^31) and a word of src, planes or dst is touched only at 0 <= gy < H, 0 <= gx < W, i.e. flat index < H * W <= INT_MAX.
+// A workgroup reads src and planes, which nobody writes in this launch, and writes the words of dst of its own tile only.
+__global__ void __launch_bounds__(kGrowThreads) label_grow_kernel(const uint8_t* __restrict__ planes, int K, int H, int W, unsigned classes,
+                                                                  const int* __restrict__ src, int* __restrict__ dst, int levels,
+                                                                  int tiles_x) {
+    __shared__ int L[kGrowPix];
+    const int tid = threadIdx.x;
+    const long long ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
+    const long long y0 = ty * kGrowTile - kGrowHalo, x0 = tx * kGrowTile - kGrowHalo;
+    const size_t npix = (size_t)H * W;
+    int open = 0, seen = 0;
+#pragma unroll 5
+    for (int j = 0; j < kGrowPer; ++j) {
+        const int r = j * kGrowThreads + tid;
+        const long long gy = y0 + r / kGrowSide, gx = x0 + r % kGrowSide;
+        int v = 0;
+        if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+            const size_t i = (size_t)gy * W + (size_t)gx;
+            v = src[i];
+            if (v == 0) {                                     // (a labelled pixel's class is never asked for)
+                int arg = 0, best = planes[i];
+                for (int k = 1; k < K; ++k) {
+                    const int p = planes[(size_t)k * npix + i];
+                    if (p > best) { best = p; arg = k; }      // first maximum, as label_runs_kernel
+                }
+                if ((classes >> arg) & 1u) v = -1;
+            }
+        }
+        L[r] = v;
+        open |= v < 0;
+        seen |= v > 0;
+    }
+    const int any_open = __syncthreads_or(open);              // (the barriers that make L whole, too)
+    const int any_seen = __syncthreads_or(seen);
+    if (any_open && any_seen) {
+        for (int t = 0; t < levels; ++t) {
+            int nv[kGrowPer];
+            int changed = 0;
+#pragma unroll
+            for (int j = 0; j < kGrowPer; ++j) {
+                const int r = j * kGrowThreads + tid;
+                int m = 0;
+                if (L[r] < 0) {
+                    const int ry = r / kGrowSide, rx = r % kGrowSide;
+                    const int up = ry > 0 ? L[r - kGrowSide] : 0, down = ry < kGrowSide - 1 ? L[r + kGrowSide] : 0;
+                    const int left = rx > 0 ? L[r - 1] : 0, right = rx < kGrowSide - 1 ? L[r + 1] : 0;
+                    m = INT_MAX;
+                    if (up > 0) m = up;
+                    if (down > 0 && down < m) m = down;
+                    if (left > 0 && left < m) m = left;
+                    if (right > 0 && right < m) m = right;
+                    if (m == INT_MAX) m = 0;
+                }
+                nv[j] = m;                                    // > 0: the pixel is claimed at this level
+                changed |= m;
+            }
+            if (!__syncthreads_or(changed)) break;            // the same answer in every thread
+#pragma unroll
+            for (int j = 0; j < kGrowPer; ++j)
+                if (nv[j] > 0) L[j * kGrowThreads + tid] = nv[j];
+            __syncthreads();
+        }
+    }
+#pragma unroll 4
+    for (int j = 0; j < kGrowTile * kGrowTile / kGrowThreads; ++j) {
+        const int q = j * kGrowThreads + tid;
+        const int iy = q / kGrowTile, ix = q % kGrowTile;
+        const long long gy = ty * kGrowTile + iy, gx = tx * kGrowTile + ix;
+        if (gy < H && gx < W) {
+            const int v = L[(iy + kGrowHalo) * kGrowSide + ix + kGrowHalo];
+            dst[(size_t)gy * W + (size_t)gx] = v > 0 ? v : 0;
+        }
+    }
+}
+
+// grid ceil(H / 4).  F: the grown labels, read by a thread at its own pixel only; out (may be null, may be F itself, may be another
+// plane): written there.  table[label - 1], label <= N, as in label_write_kernel.
+__global__ void __launch_bounds__(64 * kRowWaves) label_grown_kernel(const int* F, int H, int W, int* out, umx_label_object* __restrict__ table) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if ((long long)blockIdx.x * kRowWaves + wave >= H) return;    // (the whole wave: no barrier below)
+    const int y = blockIdx.x * kRowWaves + wave;
+    const size_t row = (size_t)y * W;
+    for_each_run(
+        W, lane,
+        [&](int x) {
+            const int label = F[row + x];
+            if (out && out != F) out[row + x] = label;
+            return label - 1;
+        },
+        [&](int key, int start, int len) { table_add(table + key, y, start, len); });
 }
 
 }  // namespace
@@ -414,7 +540,21 @@ int run_launches(umx_labeler* lb, const uint8_t* planes, int K, int H, int W, co
     if (rc) return rc;
     if (n > 0)
         hipLaunchKernelGGL(label_table_init_kernel, dim3((unsigned)((n + kPixThreads - 1) / kPixThreads)), dim3(kPixThreads), 0, s, lb->d_table, n);
-    hipLaunchKernelGGL(label_write_kernel, dim3(row_grid(H)), dim3(64 * kRowWaves), 0, s, P, Q, H, W, out, lb->d_table);
+    if (o->grow_radius == 0) {
+        hipLaunchKernelGGL(label_write_kernel, dim3(row_grid(H)), dim3(64 * kRowWaves), 0, s, P, Q, H, W, out, lb->d_table);
+    } else {
+        // the seeds into P; Q is free from here on.  ceil(R / 8) launches between the two planes, the last one of R mod 8 levels (8
+        // when that is 0); then one pass over the plane the last launch wrote: the labels to where the call wants them, the table.
+        hipLaunchKernelGGL(label_seed_kernel, dim3(pix_grid), dim3(kPixThreads), 0, s, P, Q, npix);
+        const int tiles_x = (W - 1) / kGrowTile + 1, tiles_y = (H - 1) / kGrowTile + 1;   // tiles_y * tiles_x <= 2^25 + 2^19: H * W <= INT_MAX
+        int *src = P, *dst = Q;
+        for (int left = o->grow_radius; left > 0; left -= kGrowHalo) {
+            hipLaunchKernelGGL(label_grow_kernel, dim3((unsigned)tiles_y * (unsigned)tiles_x), dim3(kGrowThreads), 0, s, planes, K, H, W,
+                               o->grow_classes, src, dst, std::min(left, kGrowHalo), tiles_x);
+            std::swap(src, dst);
+        }
+        hipLaunchKernelGGL(label_grown_kernel, dim3(row_grid(H)), dim3(64 * kRowWaves), 0, s, src, H, W, out, lb->d_table);
+    }
     L_HIP(lb, hipGetLastError());
     *n_out = n;
     return UMX_OK;
@@ -478,7 +618,18 @@ int umx_label_options_check(const umx_label_options* o, int K, int H, int W, cha
     else if (o->cls < 0 || o->cls >= K) snprintf(buf, sizeof buf, "cls is %d: the class is 0..%d, in the model's class order", o->cls, K - 1);
     else if (o->min_area < 1 || o->min_area > UMX_LABEL_MAX_MIN_AREA)
         snprintf(buf, sizeof buf, "min_area is %d: it must be 1..%d pixels", o->min_area, UMX_LABEL_MAX_MIN_AREA);
-    for (int i = 0; o && !buf[0] && i < 6; ++i)
+    // (grow_radius and grow_classes were reserved words: a caller that set one of them alone is told so as well)
+    else if (o->grow_radius < 0 || o->grow_radius > UMX_LABEL_MAX_GROW)
+        snprintf(buf, sizeof buf, "grow_radius is %d: 0 (no growth) or 1..%d levels", o->grow_radius, (int)UMX_LABEL_MAX_GROW);
+    else if (o->grow_radius > 0 && o->grow_classes == 0)
+        snprintf(buf, sizeof buf, "grow_radius is %d and grow_classes is empty: a growth needs a class to grow over (both were reserved words: "
+                                  "both zero is no growth)", o->grow_radius);
+    else if (o->grow_radius == 0 && o->grow_classes != 0)
+        snprintf(buf, sizeof buf, "grow_classes is 0x%x and grow_radius is 0: without a growth the class word must be zero (it was a reserved "
+                                  "word)", o->grow_classes);
+    else if (K < 32 && (o->grow_classes >> K) != 0)
+        snprintf(buf, sizeof buf, "grow_classes is 0x%x: a bit at or above %d, and the classes are 0..%d", o->grow_classes, K, K - 1);
+    for (int i = 0; o && !buf[0] && i < 4; ++i)
         if (o->reserved[i]) snprintf(buf, sizeof buf, "reserved must be zero");
     if (msg && cap) snprintf(msg, cap, "%s", buf);
     return buf[0] ? UMX_ERR_INVALID : UMX_OK;

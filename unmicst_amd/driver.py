@@ -90,13 +90,21 @@ def build_parser(spec: ToolSpec) -> argparse.ArgumentParser:
                    help="class whose objects are labelled, 0-based in the MODEL's class order (not --classOrder's); default: the last")
     p.add_argument("--labelMinArea", dest="labelMinArea", type=int, default=None,
                    help="objects of fewer pixels are dropped from the label mask (default 1)")
+    # the labelled objects are the nuclei without their rims (the contour class keeps touching nuclei apart and is every nucleus' outer
+    # ring): --labelGrow R grows them back, R pixels at most, over the pixels of --labelGrowClasses
+    p.add_argument("--labelGrow", dest="labelGrow", type=int, default=None,
+                   help="grow the labelled objects R pixels (1..255) into the classes of --labelGrowClasses; a shared rim is cut "
+                        "where two objects meet (default: no growth)")
+    p.add_argument("--labelGrowClasses", dest="labelGrowClasses", type=int, nargs="+", default=None,
+                   help="classes the objects grow over, 0-based in the MODEL's class order; default: every class but 0 and --labelClass")
     return p
 
 
 def check_label_args(parser: argparse.ArgumentParser, args) -> None:
     """The refusals of the label flags that need no model (parser.error: exit status 2, like any bad flag)."""
     if not args.labelMask:
-        for flag, v in (("--labelClass", args.labelClass), ("--labelMinArea", args.labelMinArea)):
+        for flag, v in (("--labelClass", args.labelClass), ("--labelMinArea", args.labelMinArea), ("--labelGrow", args.labelGrow),
+                        ("--labelGrowClasses", args.labelGrowClasses)):
             if v is not None:
                 parser.error("%s needs --labelMask" % flag)
         return
@@ -104,6 +112,30 @@ def check_label_args(parser: argparse.ArgumentParser, args) -> None:
         parser.error("--labelClass %d: classes are numbered from 0" % args.labelClass)
     if args.labelMinArea is not None and not 1 <= args.labelMinArea <= 65536:
         parser.error("--labelMinArea %d: it must be 1..65536 pixels" % args.labelMinArea)
+    if args.labelGrowClasses is not None and args.labelGrow is None:
+        parser.error("--labelGrowClasses needs --labelGrow")
+    if args.labelGrow is not None and not 1 <= args.labelGrow <= 255:
+        parser.error("--labelGrow %d: it must be 1..255 pixels" % args.labelGrow)
+    for k in args.labelGrowClasses or ():
+        if k < 0:
+            parser.error("--labelGrowClasses %d: classes are numbered from 0" % k)
+
+
+def label_grow_classes(parser: argparse.ArgumentParser, args, n_classes: int):
+    """The class set of the growth once the model's class count is known (None without --labelGrow); its refusals."""
+    if args.labelGrow is None:
+        return None
+    if args.labelGrowClasses is not None:
+        for k in args.labelGrowClasses:
+            if k >= n_classes:
+                parser.error("--labelGrowClasses %d: the model has classes 0..%d" % (k, n_classes - 1))
+        return sorted(set(args.labelGrowClasses))
+    cls = n_classes - 1 if args.labelClass is None else args.labelClass
+    classes = [k for k in range(1, n_classes) if k != cls]
+    if not classes:
+        parser.error("--labelGrow: a model of %d classes leaves no class to grow over besides 0 and the labelled one; name them "
+                     "with --labelGrowClasses" % n_classes)
+    return classes
 
 
 def write_objects_csv(path: str, objects) -> None:
@@ -227,6 +259,7 @@ def run(tool: str, argv=None, script_dir: str = None) -> int:
         label_art = _model.load_model_dir(model_path, None, synthetic_if_missing=os.environ.get("UMX_SYNTHETIC_WEIGHTS", "0") not in ("", "0"))
         if args.labelClass is not None and args.labelClass >= label_art.hp.nClasses:
             parser.error("--labelClass %d: the model has classes 0..%d" % (args.labelClass, label_art.hp.nClasses - 1))
+        grow_classes = label_grow_classes(parser, args, label_art.hp.nClasses)
 
     # the page(s) are read on a thread while the engine is set up (model load, planning, weight packing: 0.2 - 0.6 s against
     # 0.18 s of file reading for a 16384 x 16384 page; both release the GIL).  An error of the read surfaces where the reference
@@ -340,7 +373,8 @@ def run(tool: str, argv=None, script_dir: str = None) -> int:
             from . import umx as _umx
             stack_u8 = u8_planes if fast else np.stack([plane_u8(k) for k in range(n_class)])
             with _umx.Labeler(UNet2D.Engine.device) as labeler:
-                labels, objects = labeler.run(stack_u8, args.labelClass, 1 if args.labelMinArea is None else args.labelMinArea)
+                labels, objects = labeler.run(stack_u8, args.labelClass, 1 if args.labelMinArea is None else args.labelMinArea,
+                                              grow=args.labelGrow or 0, grow_classes=grow_classes)
             tiffio.imsave(out_dir + "//" + stem + "_Labels_" + suffix + ".tif", labels, append=False)
             write_objects_csv(out_dir + "//" + stem + "_Objects_" + suffix + ".csv", objects)
             st.mark("label")

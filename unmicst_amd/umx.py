@@ -40,6 +40,8 @@ EXPORTS = [
 # the label mask's limits and the geometry of its kernels (the UMX_LABEL_* macros of include/umx.h; tests/test_label_cpu.py compares)
 LABEL_MAX_CLASSES, LABEL_MAX_MIN_AREA = 16, 65536
 LABEL_STRIP_ROWS, LABEL_THREADS, LABEL_SCAN_BLOCK = 32, 1024, 2048
+# the growth: its largest radius, the tile a workgroup owns and the halo it loads round it (= the levels one launch advances)
+LABEL_MAX_GROW, LABEL_GROW_TILE, LABEL_GROW_HALO = 255, 64, 8
 
 
 class UmxError(RuntimeError):
@@ -65,9 +67,21 @@ class ProfEntry(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class _LabelGrow(ctypes.Structure):
+    _fields_ = [("grow_radius", ctypes.c_int32), ("grow_classes", ctypes.c_uint32)]
+
+
+class _LabelTail(ctypes.Union):
+    """the six words after min_area as the header names them (two growth words, four reserved ones) and, as before the growth
+    existed, as six words by index: reserved[0] and [1] are grow_radius and grow_classes, reserved[2..5] the header's reserved[0..3]"""
+    _anonymous_ = ("grow",)
+    _fields_ = [("grow", _LabelGrow), ("reserved", ctypes.c_int32 * 6)]
+
+
 class _LabelOptions(ctypes.Structure):
-    """umx_label_options"""
-    _fields_ = [("cls", ctypes.c_int32), ("min_area", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6)]
+    """umx_label_options: 32 bytes"""
+    _anonymous_ = ("tail",)
+    _fields_ = [("cls", ctypes.c_int32), ("min_area", ctypes.c_int32), ("tail", _LabelTail)]
 
 
 class LabelObject(ctypes.Structure):
@@ -482,10 +496,30 @@ def shard_plan(hp: HParams, H: int, W: int, rank: int, world: int, nslabs: int =
     return {n: x.value for n, x in zip(names, v)}
 
 
-def label_options_check(K: int, H: int, W: int, cls: int, min_area: int = 1, reserved=None) -> str:
-    """umx_label_options_check: "" if a label mask of K planes of H x W for class ``cls`` and ``min_area`` is accepted, else the
-    reason.  Host only."""
-    o = _LabelOptions(int(cls), int(min_area))
+def grow_class_word(K: int, cls: int, grow: int, grow_classes=None) -> int:
+    """The grow_classes word of umx_label_options: bit k per class index of ``grow_classes``; None with grow > 0: every class except
+    0 and the label class; 0 without a growth and without classes."""
+    if grow_classes is None:
+        return sum(1 << k for k in range(1, K) if k != cls) if grow else 0
+    word = 0
+    for k in grow_classes:
+        if not 0 <= int(k) < 32:
+            raise ValueError("grow class %d: classes are 0..%d" % (int(k), K - 1))
+        word |= 1 << int(k)
+    return word
+
+
+def _label_options(K: int, cls: Optional[int], min_area: int, grow: int, grow_classes) -> "_LabelOptions":
+    o = _LabelOptions(K - 1 if cls is None else int(cls), int(min_area))
+    o.grow_radius = int(grow)
+    o.grow_classes = grow_class_word(K, o.cls, o.grow_radius, grow_classes)
+    return o
+
+
+def label_options_check(K: int, H: int, W: int, cls: int, min_area: int = 1, reserved=None, grow: int = 0, grow_classes=None) -> str:
+    """umx_label_options_check: "" if a label mask of K planes of H x W for class ``cls``, ``min_area`` and the growth is accepted,
+    else the reason.  ``reserved``: the six words after min_area by index (the first two are the growth's).  Host only."""
+    o = _label_options(K, cls, min_area, grow, grow_classes)
     for j, v in enumerate(reserved or ()):
         o.reserved[j] = int(v)
     buf = ctypes.create_string_buffer(256)
@@ -541,14 +575,16 @@ class Labeler:
         self._check(self._L.umx_labeler_last_ms(self._lb, *[ctypes.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
-    def run(self, planes: np.ndarray, cls: Optional[int] = None, min_area: int = 1, want_labels: bool = True):
+    def run(self, planes: np.ndarray, cls: Optional[int] = None, min_area: int = 1, want_labels: bool = True, grow: int = 0,
+            grow_classes=None):
         """planes uint8 [K, H, W] in the model's class order -> (labels int32 [H, W], objects); ``cls`` None: the last class.
-        want_labels False: labels is None (only the count and the table come down)."""
+        want_labels False: labels is None (only the count and the table come down).  grow R > 0: the kept objects grow R levels
+        over the pixels whose class is in ``grow_classes`` (an iterable of class indices; None: every class but 0 and ``cls``)."""
         planes = np.ascontiguousarray(planes)
         if planes.dtype != np.uint8 or planes.ndim != 3:
             raise TypeError("planes must be uint8 [K, H, W]")
         K, H, W = planes.shape
-        o = _LabelOptions(K - 1 if cls is None else int(cls), int(min_area))
+        o = _label_options(K, cls, min_area, grow, grow_classes)
         labels = np.empty((H, W), np.int32) if want_labels else None
         n = ctypes.c_int64()
         self._check(self._L.umx_labeler_run(self._lb, planes.ctypes.data, K, H, W, ctypes.byref(o),
@@ -557,10 +593,11 @@ class Labeler:
         assert len(objs) == n.value
         return labels, objs
 
-    def run_ptr(self, planes_ptr: int, K: int, H: int, W: int, labels_ptr: int = 0, cls: Optional[int] = None, min_area: int = 1) -> np.ndarray:
+    def run_ptr(self, planes_ptr: int, K: int, H: int, W: int, labels_ptr: int = 0, cls: Optional[int] = None, min_area: int = 1,
+                grow: int = 0, grow_classes=None) -> np.ndarray:
         """umx_labeler_run_dev on DEVICE addresses (e.g. torch.Tensor.data_ptr()): uint8 [K, H, W] in, int32 [H, W] out (0: no label
-        plane) -> objects.  The planes must be complete; the call returns with the labels complete."""
-        o = _LabelOptions(K - 1 if cls is None else int(cls), int(min_area))
+        plane) -> objects.  The planes must be complete; the call returns with the labels complete.  grow, grow_classes: as run."""
+        o = _label_options(int(K), cls, min_area, grow, grow_classes)
         n = ctypes.c_int64()
         self._check(self._L.umx_labeler_run_dev(self._lb, ctypes.c_void_p(planes_ptr), int(K), int(H), int(W), ctypes.byref(o),
                                                 ctypes.c_void_p(labels_ptr or None), ctypes.byref(n)))
