@@ -334,6 +334,51 @@ UMX_API int umx_labeler_objects(const umx_labeler* lb, umx_label_object* out, in
  * count in their middle included), the download of the labels and the table.  0 for a part the call did not have.  Any may be NULL. */
 UMX_API int umx_labeler_last_ms(const umx_labeler* lb, double* upload_ms, double* kernel_ms, double* download_ms);
 
+/*
+ * Intensity of every labelled object in the planes of an image.  From labels int32 [H][W]
+ * with values in 0..N and image planes v of type T [C][H][W], T uint8 or uint16, for every plane c and label j = 1..N over the
+ * pixels with labels == j:
+ *   8. count, sum = the sum of v, sum_sq = the sum of v * v, min, max -- record c * N + (j - 1), plane-major.  A label no pixel
+ *      carries gives count 0, sum 0, sum_sq 0, min UINT32_MAX, max 0.  A label value < 0 or > N counts as 0 and is never used as an
+ *      index.  sum_sq < 2^31 * 2^32: nothing overflows.
+ *   9. mean = sum / count and std = sqrt(max(sum_sq / count - mean * mean, 0)) are host arithmetic in float64, stated here once.
+ * Everything is an integer and every atomic an integer add / min / max that nothing reads before its launch ends: two calls give
+ * the same bytes.  One launch measures a group of up to UMX_LABEL_MEASURE_GROUP planes with the label plane read once; per row run
+ * and plane it costs two 64-bit adds, one 32-bit add, one min and one max at record [c][label - 1].  Known limit, as for the table
+ * of the labelling ("salt"): an object made of 10^7 row runs serialises its atomics.
+ */
+typedef struct umx_label_measure {
+    uint64_t sum, sum_sq;
+    uint32_t min, max, count, reserved;
+} umx_label_measure;   /* 32 bytes */
+#define UMX_MEASURE_U8 1
+#define UMX_MEASURE_U16 2
+/* Planes one launch measures with the label plane read once, and the most planes of one call.  (The values stand in macros of the
+ * UMX_MEASURE_ family: the sets of UMX_LABEL_ macros and of UMX_LABEL_ enumerators with a literal value are those of the labelling
+ * and of the growth, and tests/test_label_cpu.py and tests/test_label_grow_cpu.py hold them to exactly that.) */
+#define UMX_MEASURE_GROUP_PLANES 4
+#define UMX_MEASURE_MAX_PLANES 1024
+enum { UMX_LABEL_MEASURE_GROUP = UMX_MEASURE_GROUP_PLANES, UMX_LABEL_MAX_MEASURE_PLANES = UMX_MEASURE_MAX_PLANES };
+/* Host only, no device: dtype UMX_MEASURE_U8 or _U16; 1 <= C <= 1024; H, W >= 1; H * W <= 2^31 - 1; 0 <= n_objects <= 2^31 - 1 (a
+ * label is an int32).  UMX_OK, or UMX_ERR_INVALID with the reason in msg (cap bytes; may be NULL). */
+UMX_API int umx_label_measure_check(int dtype, int C, int H, int W, int64_t n_objects, char* msg, size_t cap);
+/* planes_host [C][H][W] against the labels of the last successful umx_labeler_run that was given a labels_host: they are still on
+ * the device.  The planes go up and are measured group by group; C * N records into out (cap: its records), N into *n (may be NULL).
+ * out NULL with cap 0: only N into *n.  UMX_ERR_INVALID -- nothing touched, the labeler usable, the resident labels kept -- when there
+ * was no such run, when a later run had no label plane, was umx_labeler_run_dev or failed, when H or W differ from that run's, or
+ * when cap < C * N.  A refused run leaves the resident labels as they were.  Synchronous: returns with the stream idle, and under
+ * UMX_DEBUG_GUARD ends in the check of the red zones. */
+UMX_API int umx_labeler_measure(umx_labeler* lb, const void* planes_host, int dtype, int C, int H, int W, umx_label_measure* out,
+                                int64_t cap, int64_t* n);
+/* The same on DEVICE pointers of the labeler's device: labels_dev int32 [H][W] with objects 1..n_objects, planes_dev [C][H][W],
+ * both complete when the call is made and only read.  Needs no prior run and leaves the resident labels alone.  C * n_objects
+ * records into out_host (cap >= that).  Synchronous, guard check as above. */
+UMX_API int umx_labeler_measure_dev(umx_labeler* lb, const int32_t* labels_dev, int64_t n_objects, const void* planes_dev, int dtype,
+                                    int C, int H, int W, umx_label_measure* out_host, int64_t cap);
+/* Milliseconds of the last measurement, summed over its groups: the uploads of the planes (0 for _dev), the launches, the downloads
+ * of the records.  Any may be NULL. */
+UMX_API int umx_labeler_measure_last_ms(const umx_labeler* lb, double* upload_ms, double* kernel_ms, double* download_ms);
+
 /* Strip / tile decoders of the drivers' own TIFF reader (unmicst_amd/tiffio.py; the reference reads through tifffile /
  * imagecodecs, UnMicst1-5.py:794-797): TIFF 6.0 LZW (compression 5, the OME-TIFF / Bio-Formats default) and PackBits
  * (32773).  Host code, no device needed.  Return the decoded byte count (<= cap) or -1 on a malformed stream. */

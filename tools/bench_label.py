@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time the label mask (umx_labeler_run) on synthetic H x W stacks of K = 3 uint8 planes (GPU box); one JSON
-line.  usage: bench_label.py [H=16384] [W=H] [--reps 3] [--grow R]
+line.  usage: bench_label.py [H=16384] [W=H] [--reps 3] [--grow R] [--measure C [--measure-dtype u8|u16]]
 
 Two inputs, both made here by pure-numpy recipes (no scipy in the generators, nothing from tests/):
   blobs  nuclei-like discs: the image is cut into 32 x 32 cells; a seeded draw keeps 60 % of them, and each kept cell gets one disc of
@@ -13,7 +13,12 @@ take on the same object mask on this box's CPU share.
 --grow R: the blobs input alone, its discs as cores inside bodies whose radii are RIM = 3 pixels larger (the rim is the contour class,
 plane 1, and the growth's default domain).  The same planes are labelled without and with the growth; the object count must agree,
 and "grow_ms" is the difference of the two kernel times: what the growth adds to a call (its ceil(R / 8) launches and the pass that
-writes the labels and the table from the grown plane, less the seed stage's last launch, which it replaces)."""
+writes the labels and the table from the grown plane, less the seed stage's last launch, which it replaces).
+--measure C: the blobs input alone, labelled with its label plane kept on the device, then C seeded random planes of --measure-dtype
+measured against it (umx_labeler_measure): the upload, kernel and download milliseconds
+umx_labeler_measure_last_ms reports, summed over the groups of 4 planes (the best of --reps by kernel time, after one warm-up), the
+same for the first plane alone (a group of 1), the bytes one full group moves, and the seconds np.bincount takes for the per-object
+sums of the same planes over the same labels on this box's CPU share (one weighted pass per plane: the sum only)."""
 import argparse
 import json
 import os
@@ -101,6 +106,49 @@ def grow_bench(a, H, W):
             "bytes_per_launch_upper": int((read + 4) * H * W)}
 
 
+def best_measure_ms(lb, px, reps):
+    """-> (records, (upload, kernel, download) ms of the measurement with the least kernel time) after one warm-up"""
+    rec = lb.measure(px)
+    best = None
+    for _ in range(reps):
+        lb.measure(px)
+        ms = lb.measure_last_ms()
+        if best is None or ms[1] < best[1]:
+            best = ms
+    return rec, best
+
+
+def measure_bench(a, H, W):
+    dtype = np.uint8 if a.measure_dtype == "u8" else np.uint16
+    C, esz, npix = a.measure, np.dtype(dtype).itemsize, H * W
+    group = min(C, umx.LABEL_MEASURE_GROUP)
+    rng = np.random.default_rng(3)
+    px = np.empty((C, H, W), dtype)
+    for c in range(C):
+        px[c] = rng.integers(0, np.iinfo(dtype).max + 1, (H, W), dtype=dtype)
+    with umx.Labeler(a.device) as lb:
+        planes = planes_of(blob_mask(H, W))
+        labels, objects = lb.run(planes)
+        label_ms = lb.last_ms()
+        del planes
+        N = len(objects)
+        rec, ms = best_measure_ms(lb, px, a.reps)
+        _, ms1 = best_measure_ms(lb, px[:1], a.reps)
+    assert (rec["count"] == objects["area"][None, :]).all()
+    t = time.perf_counter()
+    sums = [np.bincount(labels.ravel(), weights=px[c].ravel(), minlength=N + 1)[1:] for c in range(C)]
+    cpu_s = time.perf_counter() - t
+    assert all(np.array_equal(rec["sum"][c], sums[c].astype(np.uint64)) for c in range(C))   # (exact: every sum is below 2^53)
+    groups = -(-C // umx.LABEL_MEASURE_GROUP)
+    return {"measure": C, "measure_dtype": a.measure_dtype, "objects": N, "object_pixels": int(objects["area"].sum()),
+            "label_kernel_ms": round(label_ms[1], 3), "groups": groups, "upload_ms": round(ms[0], 3), "kernel_ms": round(ms[1], 3),
+            "download_ms": round(ms[2], 3), "kernel_ms_per_plane": round(ms[1] / C, 3),
+            "one_plane_upload_ms": round(ms1[0], 3), "one_plane_kernel_ms": round(ms1[1], 3),
+            # a full group: every label word and every pixel of its planes read once at most, its records written once and added to
+            "group_upload_bytes": group * esz * npix, "group_read_bytes_upper": (4 + group * esz) * npix, "group_record_bytes": 32 * group * N,
+            "numpy_bincount_s": round(cpu_s, 3)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("H", type=int, nargs="?", default=16384)
@@ -108,11 +156,16 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--grow", type=int, default=0)
+    ap.add_argument("--measure", type=int, default=0, metavar="C")
+    ap.add_argument("--measure-dtype", dest="measure_dtype", choices=("u8", "u16"), default="u16")
     a = ap.parse_args()
     H, W = a.H, a.W or a.H
     out = {"tool": "bench_label", "H": H, "W": W, "K": 3, "min_area": 1, "reps": a.reps}
     if a.grow:
         print(json.dumps(dict(out, **grow_bench(a, H, W))))
+        return
+    if a.measure:
+        print(json.dumps(dict(out, **measure_bench(a, H, W))))
         return
     with umx.Labeler(a.device) as lb:
         for name, mask in (("blobs", blob_mask(H, W)), ("salt", salt_mask(H, W))):

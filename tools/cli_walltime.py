@@ -6,7 +6,9 @@ usage: cli_walltime.py [N=16384] [other-tree ...]   -- every further argument is
 libumx.so) whose UnMicst.py is timed on the same file, same box: how a round's change is compared with the round before.
        cli_walltime.py N --label   -- only this tree: twice without and twice with --labelMask (the `label` stage: stacking the
 planes, the labelling call, the int32 page and the table).
-       cli_walltime.py N --label --grow R   -- and twice with --labelMask --labelGrow R as well."""
+       cli_walltime.py N --label --grow R   -- and twice with --labelMask --labelGrow R as well.
+       cli_walltime.py N --label --measure  -- and twice with --labelMask --labelMeasure as well (the `measure` stage: the three
+probability planes and the slide's one page against the labels left on the device, and the Intensities file)."""
 import json
 import os
 import subprocess
@@ -45,7 +47,8 @@ def main():
     if "--grow" in rest:
         grow = str(int(rest[rest.index("--grow") + 1]))
         del rest[rest.index("--grow"):rest.index("--grow") + 2]
-    others = [a for a in rest if a != "--label"]
+    measure = "--measure" in rest
+    others = [a for a in rest if a not in ("--label", "--measure")]
     hp, blob, mean, std = helpers.load_nuclei_dapi()
     raw = helpers.load_sample_105()[0]
     reps = (-(-n // raw.shape[0]), -(-n // raw.shape[1]))
@@ -64,6 +67,12 @@ def main():
                 if grow:
                     one(ROOT, path, os.path.join(d, "out_grow%d" % rep), env, "this tree, --labelMask --labelGrow %s, run %d" % (grow, rep + 1), n,
                         extra=["--labelMask", "--labelGrow", grow])
+                if measure:
+                    one(ROOT, path, os.path.join(d, "out_measure%d" % rep), env, "this tree, --labelMask --labelMeasure, run %d" % (rep + 1), n,
+                        extra=["--labelMask", "--labelMeasure"])
+            if measure:
+                f = [f for f in os.listdir(os.path.join(d, "out_measure0")) if "_Intensities_" in f][0]
+                print("  %-40s %d bytes" % (f, os.path.getsize(os.path.join(d, "out_measure0", f))))
             for f in sorted(os.listdir(os.path.join(d, "out_label0"))):
                 if "_Labels_" in f or "_Objects_" in f:
                     print("  %-40s %d bytes" % (f, os.path.getsize(os.path.join(d, "out_label0", f))))

@@ -24,6 +24,10 @@
 //   label_grow_kernel     ceil(R / UMX_LABEL_GROW_HALO) launches, P -> Q -> P ...: one workgroup per tile of 64 x 64 pixels loads the
 //                         tile and a halo of 8 into LDS, runs up to 8 synchronous levels there and writes its tile to the other plane
 //   label_grown_kernel    one wave per row: the labels from the plane the last launch wrote to where the call wants them, and the table
+// A measurement (umx_labeler_measure / _measure_dev) is, per group of up to 4 image planes,
+//   label_measure_init_kernel, label_measure_kernel   one wave per row: the labels (the P plane a run left, or the caller's) read once
+//                         for the group's planes; every row run adds its count, its sums of v and v * v and its extremes of every plane
+//                         to record [plane][label - 1]
 //
 // Why no workgroup waits for another one, and none reads inside a kernel what another one writes in it: in the strip launch a workgroup
 // touches only pixels of its strip -- a link made there joins two run heads of the strip, so a walk from a pixel of the strip stays in
@@ -435,6 +439,154 @@ __global__ void __launch_bounds__(64 * kRowWaves) label_grown_kernel(const int* 
         [&](int key, int start, int len) { table_add(table + key, y, start, len); });
 }
 
+// ---- the measurement ----
+// What one row run carries of G planes: its pixel count and, per plane, the sum, the sum of squares, the least and the largest value.
+template <int G>
+struct RunSums {
+    unsigned count;
+    unsigned long long sum[G], sq[G];
+    unsigned mn[G], mx[G];
+};
+
+// lane 63's value in every lane, wave-uniform (one v_readlane per word: no LDS crossing)
+__device__ inline unsigned of_lane63(unsigned v) { return (unsigned)__builtin_amdgcn_readlane((int)v, 63); }
+__device__ inline unsigned long long of_lane63(unsigned long long v) {
+    return ((unsigned long long)of_lane63((unsigned)(v >> 32)) << 32) | of_lane63((unsigned)v);
+}
+
+// The sibling of for_each_run that carries a payload: key_at(x) once for every pixel of the row as there; val_at(x, g) <= 65535 once
+// for every pixel with key >= 0 and plane g < G; flush(key, sums) once for every maximal segment of equal key >= 0 -- by one lane, the
+// LAST pixel of the segment (or lane 0 for a carried segment that the next chunk does not continue).  Inside a chunk the sums of a
+// segment are a segmented inclusive scan over the lanes (6 steps; a lane adds the value d lanes to its left iff that lane is in its
+// segment), of two words per plane:
+//   (v << 38) | v * v   64 pixels of v <= 65535: the squares sum to < 64 * 2^32 = 2^38, the values to <= 64 * 65535 < 2^22: 60 bits;
+//   (v << 16) | v       the largest value in the upper half, the least in the lower one, compared half by half.
+// A segment that reaches the end of a chunk is carried in wave-uniform registers with 64-bit sums (one row run of 70 000 pixels of
+// 65535 passes 2^32) and joined to the first segment of the next chunk when the keys agree: one flush however long the run is.
+// ceil(W / 64) rounds; count <= W.  A chunk without any key >= 0 costs its keys and one ballot: no value of it is read.
+template <int G, typename KeyAt, typename ValAt, typename Flush>
+__device__ inline void for_each_run_sums(int W, int lane, KeyAt key_at, ValAt val_at, Flush flush) {
+    constexpr unsigned long long kSqMask = (1ull << 38) - 1ull;
+    RunSums<G> carry;                                     // the carried segment, the same in every lane; ckey < 0: none
+    int ckey = -1;
+    carry.count = 0;
+#pragma unroll
+    for (int g = 0; g < G; ++g) { carry.sum[g] = carry.sq[g] = 0; carry.mn[g] = carry.mx[g] = 0; }
+    const int nchunks = (W - 1) / 64 + 1;
+    for (int c = 0; c < nchunks; ++c) {
+        const int x0 = c * 64;
+        const bool in = lane < W - x0;
+        const int x = in ? x0 + lane : x0;
+        const int t = in ? key_at(x) : -2;                // past the row's end: a key no pixel has
+        const bool last = c + 1 == nchunks;
+        if (__ballot(t >= 0) == 0ull) {                   // (the same answer in every lane)
+            if (ckey >= 0 && lane == 0) flush(ckey, carry);
+            ckey = -1;
+            continue;
+        }
+        const int tl = __shfl_up(t, 1);
+        const bool head = lane == 0 || t != tl;
+        const unsigned long long heads = __ballot(head);  // (bit 0 is always set)
+        const int first = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));   // the lane of this segment's head, <= lane
+        const bool tail = lane == 63 || ((heads >> (lane + 1)) & 1ull);
+        unsigned long long pk[G];
+        unsigned mm[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const unsigned v = t >= 0 ? val_at(x, g) : 0u;
+            pk[g] = ((unsigned long long)v << 38) | (unsigned long long)(v * v);   // (v * v < 2^32)
+            mm[g] = (v << 16) | v;
+        }
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {                // 6 steps
+            const bool take = lane - d >= first;
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const unsigned long long p = __shfl_up(pk[g], d);
+                const unsigned m = __shfl_up(mm[g], d);
+                if (take) {
+                    pk[g] += p;
+                    const unsigned hi = max(mm[g] >> 16, m >> 16), lo = min(mm[g] & 0xffffu, m & 0xffffu);
+                    mm[g] = (hi << 16) | lo;
+                }
+            }
+        }
+        RunSums<G> r;                                     // of the segment's pixels up to this lane: the whole segment at its tail
+        r.count = (unsigned)(lane - first + 1);
+#pragma unroll
+        for (int g = 0; g < G; ++g) { r.sum[g] = pk[g] >> 38; r.sq[g] = pk[g] & kSqMask; r.mn[g] = mm[g] & 0xffffu; r.mx[g] = mm[g] >> 16; }
+        if (ckey >= 0) {
+            if (__shfl(t, 0) == ckey) {                   // the chunk's first segment continues the carried one
+                if (first == 0) {
+                    r.count += carry.count;
+#pragma unroll
+                    for (int g = 0; g < G; ++g) {
+                        r.sum[g] += carry.sum[g]; r.sq[g] += carry.sq[g];
+                        r.mn[g] = min(r.mn[g], carry.mn[g]); r.mx[g] = max(r.mx[g], carry.mx[g]);
+                    }
+                }
+            } else if (lane == 0) {
+                flush(ckey, carry);
+            }
+        }
+        if (tail && t >= 0 && (lane != 63 || last)) flush(t, r);
+        const int t63 = __builtin_amdgcn_readlane(t, 63);
+        if (!last && t63 >= 0) {
+            ckey = t63;
+            carry.count = of_lane63(r.count);
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                carry.sum[g] = of_lane63(r.sum[g]); carry.sq[g] = of_lane63(r.sq[g]);
+                carry.mn[g] = of_lane63(r.mn[g]); carry.mx[g] = of_lane63(r.mx[g]);
+            }
+        } else {
+            ckey = -1;
+        }
+    }
+}
+
+// one thread per record, j < n: the record of a label that no pixel carries
+__global__ void __launch_bounds__(kPixThreads) label_measure_init_kernel(umx_label_measure* __restrict__ rec, long long n) {
+    const long long j = (long long)blockIdx.x * kPixThreads + threadIdx.x;
+    if (j >= n) return;
+    umx_label_measure m;
+    m.sum = 0; m.sum_sq = 0; m.min = UINT_MAX; m.max = 0; m.count = 0; m.reserved = 0;
+    rec[j] = m;
+}
+
+// grid ceil(H / 4).  labels [H][W] and planes [G][H][W] are only read, the labels once for the G planes.  A label outside 1..N is
+// key -1: no record is addressed for it.  rec [G][N]: record g * N + label - 1 < G * N takes, per row run, two 64-bit adds, one
+// 32-bit add, one min and one max -- integer atomics that nothing reads in this launch.  Bounds: row y < H; a pixel word is
+// y * W + x < H * W <= INT_MAX, plane g's at g * H * W + that, formed in 64 bits.
+// Known limit ("salt"): an object made of 10^7 one-pixel runs sends 10^7 sets of atomics to one record, which
+// the memory system serialises; nothing here spreads them.
+template <typename T, int G>
+__global__ void __launch_bounds__(64 * kRowWaves) label_measure_kernel(const int* __restrict__ labels, const T* __restrict__ planes, int H,
+                                                                        int W, int N, umx_label_measure* __restrict__ rec) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if ((long long)blockIdx.x * kRowWaves + wave >= H) return;    // (the whole wave: no barrier below)
+    const int y = blockIdx.x * kRowWaves + wave;
+    const size_t npix = (size_t)H * W, row = (size_t)y * W;
+    for_each_run_sums<G>(
+        W, lane,
+        [&](int x) {
+            const int l = labels[row + x];
+            return l >= 1 && l <= N ? l - 1 : -1;
+        },
+        [&](int x, int g) { return (unsigned)planes[(size_t)g * npix + row + x]; },
+        [&](int key, const RunSums<G>& r) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                umx_label_measure* o = rec + (size_t)g * N + key;
+                atomicAdd(reinterpret_cast<unsigned long long*>(&o->sum), r.sum[g]);
+                atomicAdd(reinterpret_cast<unsigned long long*>(&o->sum_sq), r.sq[g]);
+                atomicAdd(&o->count, r.count);
+                atomicMin(&o->min, r.mn[g]);
+                atomicMax(&o->max, r.mx[g]);
+            }
+        });
+}
+
 }  // namespace
 
 }  // namespace umx
@@ -452,6 +604,15 @@ struct umx_labeler {
     umx_label_object* d_table = nullptr;  size_t table_cap = 0;   // records
     std::vector<umx_label_object> table;                       // of the last run
     double ms[3] = {0.0, 0.0, 0.0};
+    // the resident labels: d_P holds the int32 [res_H][res_W] label plane of res_N objects iff res_why is null; else why it does not
+    int res_H = 0, res_W = 0;
+    long long res_N = 0;
+    const char* res_why = "no umx_labeler_run has given this labeler a label plane yet";
+    // the measurement's own allocations (of the same arena, never part of ensure_buffers' sizes): staging for one group of planes,
+    // the records of one group
+    void* d_mplanes = nullptr;    size_t mplanes_cap = 0;      // bytes
+    umx_label_measure* d_mrec = nullptr;  size_t mrec_cap = 0; // records
+    double mms[3] = {0.0, 0.0, 0.0};
     std::string err;
 };
 
@@ -484,6 +645,7 @@ int ensure_buffers(umx_labeler* lb, size_t plane_bytes, size_t npix, size_t nblo
     L_HIP(lb, hipStreamSynchronize(lb->stream));
     arena_free(&lb->mem);
     lb->d_planes = nullptr; lb->d_P = lb->d_Q = lb->d_counts = nullptr; lb->d_n = nullptr; lb->d_table = nullptr;
+    lb->d_mplanes = nullptr; lb->d_mrec = nullptr; lb->mplanes_cap = lb->mrec_cap = 0;   // (the measurement allocates its own again)
     const size_t pb = std::max(plane_bytes, lb->planes_cap), px = std::max(npix, lb->pix_cap), nb = std::max(nblocks, lb->counts_cap);
     const size_t tc = std::max<size_t>(lb->table_cap, 1024);
     lb->planes_cap = lb->pix_cap = lb->counts_cap = lb->table_cap = 0;
@@ -568,6 +730,7 @@ int run_any(umx_labeler* lb, const uint8_t* planes, bool on_host, int K, int H, 
     if (!planes) return lfail(lb, UMX_ERR_INVALID, "null planes");
     L_HIP(lb, hipSetDevice(lb->device));
     const size_t npix = (size_t)H * W, plane_bytes = (size_t)K * npix;
+    lb->res_why = "the last run of this labeler failed";       // from here on the arena may be emptied and d_P is overwritten
     int rc = ensure_buffers(lb, on_host ? plane_bytes : 0, npix, (npix + kScanBlock - 1) / kScanBlock);
     if (rc) return rc;
     hipStream_t s = lb->stream;
@@ -597,6 +760,76 @@ int run_any(umx_labeler* lb, const uint8_t* planes, bool on_host, int K, int H, 
     std::string gmsg;
     if ((rc = arena_check(lb->mem, &gmsg)) != UMX_OK) return lfail(lb, rc, "%s", gmsg.c_str());
     if (n_objects) *n_objects = n;
+    if (on_host && labels) { lb->res_H = H; lb->res_W = W; lb->res_N = n; lb->res_why = nullptr; }
+    else lb->res_why = on_host ? "the last umx_labeler_run was given no label plane (labels_host was NULL)"
+                               : "the last run was umx_labeler_run_dev, which leaves its labels with the caller: use umx_labeler_measure_dev";
+    return UMX_OK;
+}
+
+// A buffer of the measurement at least `need` (bytes or records) large: its own allocation of the arena, released and made again
+// when it must grow.  Nothing else of the arena moves, so the resident labels stay.
+template <typename P>
+int ensure_measure_buffer(umx_labeler* lb, P** buf, size_t* cap, size_t need, size_t unit, const char* what) {
+    if (*buf && need <= *cap) return UMX_OK;
+    L_HIP(lb, hipStreamSynchronize(lb->stream));
+    if (*buf) L_HIP(lb, arena_release(&lb->mem, *buf));
+    *buf = nullptr; *cap = 0;
+    const size_t n = std::max<size_t>(need, 1);
+    L_HIP(lb, arena_alloc(&lb->mem, (void**)buf, n * unit, false, what));
+    *cap = n;
+    return UMX_OK;
+}
+
+template <typename T>
+void launch_measure(hipStream_t s, int g, const int* labels, const void* planes, int H, int W, int N, umx_label_measure* rec) {
+    const T* p = static_cast<const T*>(planes);
+    const dim3 grid(row_grid(H)), block(64 * kRowWaves);
+    switch (g) {
+        case 1: hipLaunchKernelGGL((label_measure_kernel<T, 1>), grid, block, 0, s, labels, p, H, W, N, rec); break;
+        case 2: hipLaunchKernelGGL((label_measure_kernel<T, 2>), grid, block, 0, s, labels, p, H, W, N, rec); break;
+        case 3: hipLaunchKernelGGL((label_measure_kernel<T, 3>), grid, block, 0, s, labels, p, H, W, N, rec); break;
+        default: hipLaunchKernelGGL((label_measure_kernel<T, 4>), grid, block, 0, s, labels, p, H, W, N, rec); break;
+    }
+}
+
+// C planes against `labels` (device, H x W, objects 1..N), group by group of up to UMX_LABEL_MEASURE_GROUP planes: the group's planes
+// up (on_host), its records cleared, one launch, its records down to out[c0 * N ...]; then the stream is idle.  At most
+// ceil(1024 / 4) = 256 rounds.  The caller has checked the arguments; out holds C * N records.
+int measure_any(umx_labeler* lb, const int* labels, long long N, const void* planes, bool on_host, int dtype, int C, int H, int W,
+                umx_label_measure* out) {
+    L_HIP(lb, hipSetDevice(lb->device));
+    lb->mms[0] = lb->mms[1] = lb->mms[2] = 0.0;
+    if (N == 0) return UMX_OK;
+    const size_t npix = (size_t)H * W, esz = dtype == UMX_MEASURE_U16 ? 2 : 1;
+    const int gmax = std::min(C, (int)UMX_LABEL_MEASURE_GROUP);
+    int rc = on_host ? ensure_measure_buffer(lb, &lb->d_mplanes, &lb->mplanes_cap, (size_t)gmax * npix * esz, 1, "measure planes") : UMX_OK;
+    if (rc) return rc;
+    if ((rc = ensure_measure_buffer(lb, &lb->d_mrec, &lb->mrec_cap, (size_t)gmax * (size_t)N, sizeof(umx_label_measure), "measure records"))) return rc;
+    hipStream_t s = lb->stream;
+    for (int c0 = 0; c0 < C; c0 += UMX_LABEL_MEASURE_GROUP) {
+        const int g = std::min(C - c0, (int)UMX_LABEL_MEASURE_GROUP);
+        const char* src = static_cast<const char*>(planes) + (size_t)c0 * npix * esz;
+        const long long nrec = (long long)g * N;
+        L_HIP(lb, hipEventRecord(lb->ev[0], s));
+        if (on_host) L_HIP(lb, hipMemcpyAsync(lb->d_mplanes, src, (size_t)g * npix * esz, hipMemcpyHostToDevice, s));
+        L_HIP(lb, hipEventRecord(lb->ev[1], s));
+        hipLaunchKernelGGL(label_measure_init_kernel, dim3((unsigned)((nrec + kPixThreads - 1) / kPixThreads)), dim3(kPixThreads), 0, s,
+                           lb->d_mrec, nrec);
+        const void* dev = on_host ? lb->d_mplanes : src;
+        if (dtype == UMX_MEASURE_U16) launch_measure<uint16_t>(s, g, labels, dev, H, W, (int)N, lb->d_mrec);
+        else launch_measure<uint8_t>(s, g, labels, dev, H, W, (int)N, lb->d_mrec);
+        L_HIP(lb, hipGetLastError());
+        L_HIP(lb, hipEventRecord(lb->ev[2], s));
+        L_HIP(lb, hipMemcpyAsync(out + (size_t)c0 * (size_t)N, lb->d_mrec, (size_t)nrec * sizeof(umx_label_measure), hipMemcpyDeviceToHost, s));
+        L_HIP(lb, hipEventRecord(lb->ev[3], s));
+        L_HIP(lb, hipStreamSynchronize(s));
+        for (int k = 0; k < 3; ++k) {
+            float f = 0.f;
+            if (hipEventElapsedTime(&f, lb->ev[k], lb->ev[k + 1]) == hipSuccess && (k > 0 || on_host)) lb->mms[k] += f;
+        }
+    }
+    std::string gmsg;
+    if ((rc = arena_check(lb->mem, &gmsg)) != UMX_OK) return lfail(lb, rc, "%s", gmsg.c_str());
     return UMX_OK;
 }
 
@@ -699,6 +932,58 @@ int umx_labeler_last_ms(const umx_labeler* lb, double* upload_ms, double* kernel
     if (upload_ms) *upload_ms = lb->ms[0];
     if (kernel_ms) *kernel_ms = lb->ms[1];
     if (download_ms) *download_ms = lb->ms[2];
+    return UMX_OK;
+}
+
+int umx_label_measure_check(int dtype, int C, int H, int W, int64_t n_objects, char* msg, size_t cap) {
+    char buf[200] = "";
+    if (dtype != UMX_MEASURE_U8 && dtype != UMX_MEASURE_U16)
+        snprintf(buf, sizeof buf, "dtype is %d: UMX_MEASURE_U8 (%d) or UMX_MEASURE_U16 (%d)", dtype, UMX_MEASURE_U8, UMX_MEASURE_U16);
+    else if (C < 1 || C > UMX_LABEL_MAX_MEASURE_PLANES) snprintf(buf, sizeof buf, "there are %d planes: 1..%d", C, (int)UMX_LABEL_MAX_MEASURE_PLANES);
+    else if (H < 1 || W < 1) snprintf(buf, sizeof buf, "the image is %d x %d: both sides must be at least 1", H, W);
+    else if ((long long)H * W > INT_MAX)
+        snprintf(buf, sizeof buf, "the image is %d x %d: a flat pixel index is an int32, so H * W may be at most %d", H, W, INT_MAX);
+    else if (n_objects < 0 || n_objects > INT_MAX)
+        snprintf(buf, sizeof buf, "n_objects is %lld: a label is an int32, so 0..%d objects", (long long)n_objects, INT_MAX);
+    if (msg && cap) snprintf(msg, cap, "%s", buf);
+    return buf[0] ? UMX_ERR_INVALID : UMX_OK;
+}
+
+int umx_labeler_measure(umx_labeler* lb, const void* planes_host, int dtype, int C, int H, int W, umx_label_measure* out, int64_t cap,
+                        int64_t* n) {
+    if (!lb) return lfail(nullptr, UMX_ERR_INVALID, "null labeler");
+    char msg[200];
+    if (umx_label_measure_check(dtype, C, H, W, 0, msg, sizeof msg) != UMX_OK) return lfail(lb, UMX_ERR_INVALID, "%s", msg);
+    if (lb->res_why) return lfail(lb, UMX_ERR_INVALID, "umx_labeler_measure has no labels to measure against: %s", lb->res_why);
+    if (H != lb->res_H || W != lb->res_W)
+        return lfail(lb, UMX_ERR_INVALID, "the planes are %d x %d and the labels of the last run %d x %d", H, W, lb->res_H, lb->res_W);
+    const long long N = lb->res_N;
+    if (n) *n = N;
+    if (!out && cap == 0) return UMX_OK;                  // the count alone, like umx_labeler_objects
+    if (!out || cap < (long long)C * N)
+        return lfail(lb, UMX_ERR_INVALID, "out holds %lld records: %d planes of %lld objects need %lld", out ? (long long)cap : 0ll, C, N,
+                     (long long)C * N);
+    if (!planes_host) return lfail(lb, UMX_ERR_INVALID, "null planes");
+    return measure_any(lb, lb->d_P, N, planes_host, true, dtype, C, H, W, out);
+}
+
+int umx_labeler_measure_dev(umx_labeler* lb, const int32_t* labels_dev, int64_t n_objects, const void* planes_dev, int dtype, int C, int H,
+                            int W, umx_label_measure* out_host, int64_t cap) {
+    if (!lb) return lfail(nullptr, UMX_ERR_INVALID, "null labeler");
+    char msg[200];
+    if (umx_label_measure_check(dtype, C, H, W, n_objects, msg, sizeof msg) != UMX_OK) return lfail(lb, UMX_ERR_INVALID, "%s", msg);
+    if (!labels_dev || !planes_dev) return lfail(lb, UMX_ERR_INVALID, "null labels or planes");
+    if (cap < (long long)C * n_objects || (!out_host && n_objects > 0))
+        return lfail(lb, UMX_ERR_INVALID, "out_host holds %lld records: %d planes of %lld objects need %lld", out_host ? (long long)cap : 0ll,
+                     C, (long long)n_objects, (long long)C * n_objects);
+    return measure_any(lb, labels_dev, n_objects, planes_dev, false, dtype, C, H, W, out_host);
+}
+
+int umx_labeler_measure_last_ms(const umx_labeler* lb, double* upload_ms, double* kernel_ms, double* download_ms) {
+    if (!lb) return lfail(nullptr, UMX_ERR_INVALID, "null labeler");
+    if (upload_ms) *upload_ms = lb->mms[0];
+    if (kernel_ms) *kernel_ms = lb->mms[1];
+    if (download_ms) *download_ms = lb->mms[2];
     return UMX_OK;
 }
 

@@ -97,6 +97,10 @@ def build_parser(spec: ToolSpec) -> argparse.ArgumentParser:
                         "where two objects meet (default: no growth)")
     p.add_argument("--labelGrowClasses", dest="labelGrowClasses", type=int, nargs="+", default=None,
                    help="classes the objects grow over, 0-based in the MODEL's class order; default: every class but 0 and --labelClass")
+    # how bright every labelled object is in the image's own pages: <stem>_Intensities_<suffix>.csv
+    p.add_argument("--labelMeasure", dest="labelMeasure", type=int, nargs="*", default=None, metavar="PAGE",
+                   help="also write mean, std, min and max of every labelled object in the probability planes and in these pages of "
+                        "the input file, 0-based as --channel counts them (no value: every page)")
     return p
 
 
@@ -104,7 +108,7 @@ def check_label_args(parser: argparse.ArgumentParser, args) -> None:
     """The refusals of the label flags that need no model (parser.error: exit status 2, like any bad flag)."""
     if not args.labelMask:
         for flag, v in (("--labelClass", args.labelClass), ("--labelMinArea", args.labelMinArea), ("--labelGrow", args.labelGrow),
-                        ("--labelGrowClasses", args.labelGrowClasses)):
+                        ("--labelGrowClasses", args.labelGrowClasses), ("--labelMeasure", args.labelMeasure)):
             if v is not None:
                 parser.error("%s needs --labelMask" % flag)
         return
@@ -119,6 +123,9 @@ def check_label_args(parser: argparse.ArgumentParser, args) -> None:
     for k in args.labelGrowClasses or ():
         if k < 0:
             parser.error("--labelGrowClasses %d: classes are numbered from 0" % k)
+    for page in args.labelMeasure or ():
+        if page < 0:
+            parser.error("--labelMeasure %d: pages are numbered from 0" % page)
 
 
 def label_grow_classes(parser: argparse.ArgumentParser, args, n_classes: int):
@@ -146,6 +153,44 @@ def write_objects_csv(path: str, objects) -> None:
         cols = [range(1, len(objects) + 1)] + [objects[n].tolist() for n in ("area", "y0", "x0", "y1", "x1")]
         cols += [(objects["sum_y"] / area).tolist(), (objects["sum_x"] / area).tolist()]   # (sums below 2^53: exact in float64)
         f.writelines("%d,%d,%d,%d,%d,%d,%.6f,%.6f\n" % row for row in zip(*cols))
+
+
+def write_intensities_csv(path: str, objects, planes) -> None:
+    """label,area, then <prefix>_mean,_std,_min,_max per measured plane -- one line per object, label order, the floats written the way
+    write_objects_csv writes centroids.  planes: [(prefix, records umx.LABEL_MEASURE_DTYPE [N])]; every plane's count must be the
+    table's area."""
+    from . import umx as _umx
+    for prefix, records in planes:
+        if not np.array_equal(records["count"], objects["area"]):
+            raise AssertionError("the measurement of %s counted other pixels than the label table" % prefix)
+    cols = [range(1, len(objects) + 1), objects["area"].tolist()]
+    for _, records in planes:
+        mean, std = _umx.measure_mean_std(records)
+        cols += [mean.tolist(), std.tolist(), records["min"].tolist(), records["max"].tolist()]
+    fmt = "%d,%d" + ",%.6f,%.6f,%d,%d" * len(planes) + "\n"
+    with open(path, "w") as f:
+        f.write(",".join(["label,area"] + [prefix + "_" + n for prefix, _ in planes for n in ("mean", "std", "min", "max")]) + "\n")
+        f.writelines(fmt % row for row in zip(*cols))
+
+
+def measure_pages(labeler, path: str, pages, shape) -> list:
+    """[("ch<p>", records [N])] of the pages of the TIFF against the labeler's resident labels.  One page is held at a time: page
+    i + 1 is read on a thread while page i is uploaded and measured.  A page that cannot be measured raises before anything is written."""
+    from concurrent.futures import ThreadPoolExecutor
+    out = []
+    if not pages:
+        return out
+    with ThreadPoolExecutor(1) as pool:
+        job = pool.submit(tiffio.imread, path, int(pages[0]))
+        for i, page in enumerate(pages):
+            plane = job.result()
+            job = pool.submit(tiffio.imread, path, int(pages[i + 1])) if i + 1 < len(pages) else None
+            if plane.dtype not in (np.uint8, np.uint16):
+                raise ValueError("--labelMeasure: page %d of %s is %s; only uint8 and uint16 pages are measured" % (page, path, plane.dtype))
+            if tuple(plane.shape) != tuple(shape):
+                raise ValueError("--labelMeasure: page %d of %s is %s and the label mask %s" % (page, path, plane.shape, tuple(shape)))
+            out.append(("ch%d" % page, labeler.measure(plane)[0]))
+    return out
 
 
 def models_root(script_dir: str) -> str:
@@ -260,6 +305,16 @@ def run(tool: str, argv=None, script_dir: str = None) -> int:
         if args.labelClass is not None and args.labelClass >= label_art.hp.nClasses:
             parser.error("--labelClass %d: the model has classes 0..%d" % (args.labelClass, label_art.hp.nClasses - 1))
         grow_classes = label_grow_classes(parser, args, label_art.hp.nClasses)
+    measure_pages_arg = None
+    if args.labelMeasure is not None:
+        ftype = split_name(os.path.basename(args.imagePath), spec)[1]
+        if not (ftype in spec.tiff_types or ftype == "tif"):     # (what read_plane would say after the set-up)
+            raise NotImplementedError("Don't know how to read image with extension .%s" % ftype)
+        n_pages = tiffio.num_pages(args.imagePath)
+        measure_pages_arg = list(args.labelMeasure) or list(range(n_pages))
+        for page in measure_pages_arg:
+            if page >= n_pages:
+                parser.error("--labelMeasure %d: the file has pages 0..%d" % (page, n_pages - 1))
 
     # the page(s) are read on a thread while the engine is set up (model load, planning, weight packing: 0.2 - 0.6 s against
     # 0.18 s of file reading for a 16384 x 16384 page; both release the GIL).  An error of the read surfaces where the reference
@@ -375,9 +430,17 @@ def run(tool: str, argv=None, script_dir: str = None) -> int:
             with _umx.Labeler(UNet2D.Engine.device) as labeler:
                 labels, objects = labeler.run(stack_u8, args.labelClass, 1 if args.labelMinArea is None else args.labelMinArea,
                                               grow=args.labelGrow or 0, grow_classes=grow_classes)
-            tiffio.imsave(out_dir + "//" + stem + "_Labels_" + suffix + ".tif", labels, append=False)
-            write_objects_csv(out_dir + "//" + stem + "_Objects_" + suffix + ".csv", objects)
-            st.mark("label")
+                tiffio.imsave(out_dir + "//" + stem + "_Labels_" + suffix + ".tif", labels, append=False)
+                write_objects_csv(out_dir + "//" + stem + "_Objects_" + suffix + ".csv", objects)
+                st.mark("label")
+                if measure_pages_arg is not None:
+                    # the labels (the grown ones with --labelGrow) are still on the device: the planes the labeler just used, then
+                    # the file's pages one at a time; the file is written only when every page has been measured
+                    pm = labeler.measure(stack_u8)
+                    measured = [("pm%d" % k, pm[k]) for k in range(len(pm))]
+                    measured += measure_pages(labeler, image_path, measure_pages_arg, labels.shape)
+                    write_intensities_csv(out_dir + "//" + stem + "_Intensities_" + suffix + ".csv", objects, measured)
+                    st.mark("measure")
     finally:
         if args.compat_per_class:
             UNet2D.reuse_pass = reuse_before

@@ -35,6 +35,7 @@ EXPORTS = [
     "umx_describe", "umx_describe_graph", "umx_plan_check", "umx_test_wgrad_plan", "umx_test_mx_pack_e2m3", "umx_version",
     "umx_label_options_check", "umx_labeler_create", "umx_labeler_destroy", "umx_labeler_last_error", "umx_labeler_run",
     "umx_labeler_run_dev", "umx_labeler_objects", "umx_labeler_last_ms",
+    "umx_label_measure_check", "umx_labeler_measure", "umx_labeler_measure_dev", "umx_labeler_measure_last_ms",
 ]
 
 # the label mask's limits and the geometry of its kernels (the UMX_LABEL_* macros of include/umx.h; tests/test_label_cpu.py compares)
@@ -91,6 +92,13 @@ class LabelObject(ctypes.Structure):
 
 # the same record as a numpy dtype: what Labeler.run returns its table in
 LABEL_OBJECT_DTYPE = np.dtype([(n, "<i4") for n in ("area", "y0", "x0", "y1", "x1", "reserved")] + [("sum_y", "<i8"), ("sum_x", "<i8")])
+
+
+# umx_label_measure (32 bytes): what Labeler.measure returns, [C, N]; mean and std are measure_mean_std's
+LABEL_MEASURE_DTYPE = np.dtype([("sum", "<u8"), ("sum_sq", "<u8"), ("min", "<u4"), ("max", "<u4"), ("count", "<u4"), ("reserved", "<u4")])
+MEASURE_U8, MEASURE_U16 = 1, 2                                 # UMX_MEASURE_*
+LABEL_MEASURE_GROUP, LABEL_MAX_MEASURE_PLANES = 4, 1024
+_MEASURE_DTYPES = {np.dtype(np.uint8): MEASURE_U8, np.dtype(np.uint16): MEASURE_U16}
 
 
 _SEND_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p)
@@ -272,6 +280,14 @@ def load(path: Optional[str] = None):
     L.umx_labeler_objects.argtypes = [c_void_p, c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
     L.umx_labeler_last_ms.restype = c_int
     L.umx_labeler_last_ms.argtypes = [c_void_p] + [ctypes.POINTER(c_double)] * 3
+    L.umx_label_measure_check.restype = c_int
+    L.umx_label_measure_check.argtypes = [c_int, c_int, c_int, c_int, ctypes.c_int64, ctypes.c_char_p, ctypes.c_size_t]
+    L.umx_labeler_measure.restype = c_int
+    L.umx_labeler_measure.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+    L.umx_labeler_measure_dev.restype = c_int
+    L.umx_labeler_measure_dev.argtypes = [c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, ctypes.c_int64]
+    L.umx_labeler_measure_last_ms.restype = c_int
+    L.umx_labeler_measure_last_ms.argtypes = [c_void_p] + [ctypes.POINTER(c_double)] * 3
     L.umx_prof_entry_size.restype = c_int
     if L.umx_prof_entry_size() != ctypes.sizeof(ProfEntry):
         raise RuntimeError("libumx (%s) lays umx_prof_entry out in %d bytes, this binding in %d: mixed builds" % (
@@ -527,6 +543,26 @@ def label_options_check(K: int, H: int, W: int, cls: int, min_area: int = 1, res
     return "" if rc == 0 else buf.value.decode()
 
 
+def label_measure_check(dtype: int, C: int, H: int, W: int, n_objects: int = 0) -> str:
+    """umx_label_measure_check: "" if a measurement of C planes of H x W of that dtype code against n_objects labels is accepted, else
+    the reason.  Host only."""
+    buf = ctypes.create_string_buffer(256)
+    rc = load().umx_label_measure_check(int(dtype), int(C), int(H), int(W), int(n_objects), buf, len(buf))
+    return "" if rc == 0 else buf.value.decode()
+
+
+def measure_mean_std(records: np.ndarray):
+    """(mean, std) in float64 of LABEL_MEASURE_DTYPE records, as include/umx.h states them: mean = sum / count, std =
+    sqrt(max(sum_sq / count - mean * mean, 0)); both nan where count is 0.  A constant object has std 0 exactly: every pixel v gives
+    sum = count v and sum_sq = count v^2; count v <= 2^31 * 65535 < 2^53 is exact, so mean is v and mean * mean is the integer v^2
+    exactly, sum_sq / count rounds to the same v^2, and the difference is 0."""
+    count = records["count"].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = records["sum"].astype(np.float64) / count
+        std = np.sqrt(np.maximum(records["sum_sq"].astype(np.float64) / count - mean * mean, 0.0))
+    return mean, std
+
+
 class Labeler:
     """One umx_labeler: the label mask (include/umx.h) of uint8 probability stacks on one MI355X.  It needs no
     model; its device buffers grow on demand and are kept between runs."""
@@ -602,6 +638,41 @@ class Labeler:
         self._check(self._L.umx_labeler_run_dev(self._lb, ctypes.c_void_p(planes_ptr), int(K), int(H), int(W), ctypes.byref(o),
                                                 ctypes.c_void_p(labels_ptr or None), ctypes.byref(n)))
         return self.objects()
+
+    def measure(self, planes: np.ndarray) -> np.ndarray:
+        """umx_labeler_measure: uint8 / uint16 planes [C, H, W] (or one plane [H, W]) against the labels the last run(want_labels=True)
+        left on the device -> LABEL_MEASURE_DTYPE [C, N], record [c, j - 1] of plane c and label j."""
+        planes = np.ascontiguousarray(planes)
+        if planes.ndim == 2:
+            planes = planes[None]
+        if planes.dtype not in _MEASURE_DTYPES or planes.ndim != 3:
+            raise TypeError("planes must be uint8 or uint16 [C, H, W] or [H, W], not %s %s" % (planes.dtype, planes.shape))
+        code = _MEASURE_DTYPES[planes.dtype]
+        C, H, W = planes.shape
+        n = ctypes.c_int64()
+        self._check(self._L.umx_labeler_measure(self._lb, None, code, C, H, W, None, 0, ctypes.byref(n)))
+        out = np.zeros((C, n.value), LABEL_MEASURE_DTYPE)
+        self._check(self._L.umx_labeler_measure(self._lb, planes.ctypes.data, code, C, H, W, out.ctypes.data, out.size, ctypes.byref(n)))
+        return out
+
+    def measure_ptr(self, labels_ptr: int, n_objects: int, planes_ptr: int, dtype, C: int, H: int, W: int) -> np.ndarray:
+        """umx_labeler_measure_dev on DEVICE addresses (e.g. torch.Tensor.data_ptr()): int32 [H, W] labels with objects 1..n_objects
+        and planes [C, H, W] of ``dtype`` (np.uint8 / np.uint16, or a UMX_MEASURE_* code), both complete -> LABEL_MEASURE_DTYPE
+        [C, n_objects].  Needs no prior run."""
+        code = dtype if isinstance(dtype, int) else _MEASURE_DTYPES.get(np.dtype(dtype), 0)
+        why = label_measure_check(code, C, H, W, n_objects)        # (before any buffer is sized from the arguments)
+        if why:
+            raise UmxError(ERR_INVALID, why)
+        out = np.zeros((int(C), int(n_objects)), LABEL_MEASURE_DTYPE)
+        self._check(self._L.umx_labeler_measure_dev(self._lb, ctypes.c_void_p(labels_ptr), int(n_objects), ctypes.c_void_p(planes_ptr), code,
+                                                    int(C), int(H), int(W), out.ctypes.data, out.size))
+        return out
+
+    def measure_last_ms(self):
+        """(upload, kernel, download) milliseconds of the last measurement, summed over its groups of planes."""
+        v = [ctypes.c_double() for _ in range(3)]
+        self._check(self._L.umx_labeler_measure_last_ms(self._lb, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
 
 class Engine:
