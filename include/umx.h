@@ -470,6 +470,14 @@ UMX_API int umx_plan_check(const umx_hparams* hp);
  * dynamic LDS bytes and how the reduce undoes the operand scales.  UMX_ERR_INVALID with the planner's reason in umx_last_error(NULL). */
 UMX_API int umx_test_wgrad_plan(int B, int H, int Cxt, int Cx, int Cg, int nslab, const int* dy, const int* dx, const int* mslab,
                                 const int* coff, int f32_route, int planes, int XCs, int GCs, char* line, size_t cap);
+/* test entry (host only): the host pass of umx_trainer_create -- shape, parameter layout and the plan of every forward / input-gradient
+ * convolution of the training step -- for batch B (<= 0: 8) and the initial parameters `blob`, on the route UMX_TRAIN_CONV_F32 (conv_f32)
+ * / UMX_TRAIN_NO_KSPLIT (no_ksplit) would select.  text receives one line per convolution in build order: its UMX_DEBUG_PLAN text, then
+ * its groups (channels x taps per phase @ channel offset / master dims), the fused activation, `direct`, the weight shift, the numbers of pack descriptors and weight references, the K-split scratch
+ * floats and a 64-bit FNV-1a digest of everything the upload would send.  *needed: the text's bytes with the terminator (set even where
+ * cap is too small: UMX_ERR_INVALID).  A shape the planner refuses: its code, the reason in umx_last_error(NULL). */
+UMX_API int umx_test_train_plan(const umx_hparams* hp, int B, int conv_f32, int no_ksplit, const float* blob, size_t blob_floats,
+                                char* text, size_t cap, size_t* needed);
 UMX_API const char* umx_version(void);
 
 #ifdef __cplusplus

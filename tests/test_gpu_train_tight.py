@@ -130,7 +130,7 @@ def test_the_cases_reach_the_launch_forms(monkeypatch, capfd):
       * wgrad_thin_kernel on strips of more than one row: needs B * H >= 2048 rows (wgrad_setup);
         tests/test_gpu_train.py::test_baseline_config_256x256x2_batch8_against_the_oracle runs it;
       * a convolution that "stays on the fp32 kernel" beside conv_f16x3: no shape the trainer accepts reaches it.  plan_f16 refuses a
-        halo of more than 1024 pixels, and setup_conv refuses the same halo for the whole trainer first ("halo too large"); below
+        halo of more than 1024 pixels, and tconv_plan refuses the same halo for the whole trainer first ("halo too large"); below
         that the planner's last attempt (one octet per chunk, one k-step per stage, a CU's whole LDS) always fits.  Asserted below, so
         that a planner change which makes it reachable asks for a case here."""
     reached = {}

@@ -119,7 +119,7 @@ struct PendingEvent {
     hipEvent_t a, b;
 };
 
-// ---- device memory of a trainer / training set / labeler / inference context (umx_train.hip) ----
+// ---- device memory of a trainer / training set / labeler / inference context (umx_arena.hip) ----
 // Every allocation goes through arena_alloc.  Debug guard mode (UMX_DEBUG_GUARD=<byte>, read at umx_trainer_create /
 // umx_trainset_create / umx_create_opts) puts a red zone of max(64 KiB, round_up(bytes, 4 KiB)) in front of and behind each buffer,
 // fills both zones -- and the buffer itself unless the caller zeroes or uploads it -- with that byte, and arena_check names the first
@@ -150,16 +150,6 @@ int arena_check(const DevArena& a, std::string* msg);
 void arena_free(DevArena* a);
 
 struct Shard;   // umx_shard.hip: the communicator, transport and buffers umx_shard_init attaches to a context
-
-// ---- border weight maps (umx_trainset_border.hip) ----
-// 4-connected components of (annotation == code) of n samples (ann: the first one's plane, [S][row_a] each) into ws [n][S][S]: the
-// flat index of the component's first pixel in raster order, -1 off the objects.  One workgroup per sample; S * S fits an int32.
-hipError_t launch_border_label(const uint8_t* ann, int n, int S, int row_a, int code, int* ws, hipStream_t stream);
-// from those planes: wmap (sample stride plane_w, row stride row_w floats) and, where given, labels (root + 1; 0 off the objects),
-// d1sq and d2sq [n][S][S].  R = border_radius(sigma) <= 32, den = 2 sigma^2.
-hipError_t launch_border_map(const int* ws, int n, int S, int R, double den, float* wmap, int row_w, size_t plane_w, int* labels,
-                             int* d1sq, int* d2sq, hipStream_t stream);
-int border_radius(float sigma);        // ceil(4 sigma)
 
 }  // namespace umx
 
@@ -267,7 +257,7 @@ struct PlanInputs {                // what the plan of a launch depends on besid
     const Launch* head = nullptr;  // the softmax head its epilogue may fuse
 };
 struct HostPlan {
-    HConvParams h;                      // device pointers null: the engine's upload_plan / the trainer's setup_hconv set them
+    HConvParams h;                      // device pointers null: the engine's upload_plan / the trainer's upload_conv set them
     std::vector<HStage> stages;         // the stage table, every list's stages and a dummy behind them
     std::vector<_Float16> wimg[4];      // per stage list: weight slab [N-block][stage blocks] (training plans: k-maps only)
     std::vector<float> econst;          // epilogue constants per N-block (+ depth-to-space table, fused-head constants)
@@ -288,6 +278,69 @@ void plan_first(const Launch& L, HostPlan* P);
 bool make_d2s(Launch& L);
 // the same decision from the hyper-parameters alone (the graph builder folds the raw skip only when the first layer takes this kernel)
 bool conv_first_eligible(const umx_hparams& hp);
+
+// ---- umx_tconv.hip: the host plan of one forward / input-gradient convolution of the training step (no HIP call, no trainer, no getenv)
+struct TapSet {
+    std::vector<std::pair<int, int>> off;   // (dy, dx) input offsets
+    std::vector<int> m;                     // master tap index per (tap, parity) : size off.size() * npar
+};
+// One operand group of a training convolution: a source of C channels and, per phase, a TapSet over the master tensor at w_off;
+// transpose flag, channel offset on the master's d2 axis, (npar, Cblk) parity blocks, optional second tensor summed in
+struct GroupSpec {
+    int C;                      // source channels seen by the kernel
+    size_t w_off, w2_off;       // master tensor(s) in the parameter vector (w2_off = SIZE_MAX: none)
+    int d2, d3;                 // master dims [taps][d2][d3]
+    int transpose, c_off, npar, Cblk;
+    TapSet taps[4];
+};
+TapSet same_taps(int ks, bool flipped);
+GroupSpec one_group(int C, size_t w_off, size_t w2_off, int d2, int d3, int transpose, int c_off, const TapSet& ts);
+// the stride-2 transposed convolution: the four sub-pixel phases of its forward (taps of g, output offsets oy / ox [4]) ...
+void transposed_fwd_taps(int ks, GroupSpec* g, int* oy, int* ox);
+// ... and its backward on the space-to-depth output gradient: the 2 x 2 (ks 3) window and parity table of g, and the weight
+// gradient's slabs with their channel offsets
+void transposed_bwd_taps(int ks, int Cup, GroupSpec* g, TapSet* slabs, std::vector<int>* coff);
+void choose_nt(int Cout, int mtiles, int* nt, int* Np);
+struct WSrc { size_t off, off2, cnt; };   // master tensor(s) an operand group reads: where its weight scale is derived from
+double operand_wmax(const std::vector<WSrc>& wsrc, const float* params);
+int wscale_shift(double wmax);
+
+struct TConvSpec {                     // one convolution as the graph's build describes it
+    std::string name;
+    int H = 0, W = 0, Cout = 0, act = 0, nphase = 1, o_mul = 1;
+    int oy[4] = {0, 0, 0, 0}, ox[4] = {0, 0, 0, 0};
+    int ngroups = 0;
+    GroupSpec g[2];
+    bool bwd = false;                  // it belongs to the backward pass only (its operands are packed on the side stream under the forward pass)
+};
+struct TConvEnv {                      // what its plan depends on besides
+    int B = 0, imSize = 0;
+    bool hconv = true;                 // the route: split precision (conv_f16x3) where the planner takes the shape, else the fp32 kernel
+    bool no_ksplit = false;            // UMX_TRAIN_NO_KSPLIT
+    const float* params = nullptr;     // the parameter vector on the host: weight scales
+};
+struct TConvPlan {
+    ConvParams cp;                     // the fp32 kernel's launch (pointers null)
+    int nt = 1, hpix = 2;
+    double mac = 0.0;                  // algorithmic multiply-accumulates per image
+    struct Operand { int ph, g; size_t elems; };
+    std::vector<Operand> operands;     // the fp32 operands [tap][Cp][Np], one per (phase, group) with taps
+    std::vector<PackDesc> packs;       // their descriptors (pointers null), index for index -- none for a direct convolution
+    size_t max_pack = 0;
+    bool split = false;                // the split-precision planner took it: P, direct, wsrc and wsh hold
+    std::string refused;               // ... or why not
+    HostPlan P;                        // references already in the coordinates the repack reads; ks0 / split_stride set
+    bool direct = false;               // its weight images are gathered straight from the master tensors (no fp32 operand is read)
+    std::vector<WSrc> wsrc;
+    int wsh = 0;                       // the weights are stored times 2^wsh
+    size_t split_floats = 0;           // K-split scratch either kernel needs
+    std::string text;                  // tconv_describe
+};
+// false with *why ("<name>: <reason>") for a shape the trainer cannot run
+bool tconv_plan(const TConvSpec& s, const TConvEnv& env, TConvPlan* out, std::string* why);
+std::string tconv_describe(const TConvSpec& s, const TConvEnv& env, const TConvPlan& p);   // the plan's line of UMX_DEBUG_PLAN
+// FNV-1a over everything the upload sends (serialisation: umx_tconv.hip); P null: the convolution stays on the fp32 kernel
+unsigned long long tconv_digest(const ConvParams& cp, int nt, int hpix, const PackDesc* packs, size_t npacks, const HostPlan* P);
 
 // ---- umx_engine.hip
 // Device memory of a context: ctx->mem (DevArena above).  Resident buffers -- weights, epilogue constants, stage lists, head

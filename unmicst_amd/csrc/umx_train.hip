@@ -1,4 +1,5 @@
-// libumx training step: host side (plan, buffers, launch sequence) and the C ABI of include/umx_train.h.
+// libumx training step: host side (the graphs' builds, buffers, launch sequence) and the C ABI of include/umx_train.h.  The plan of one
+// convolution is umx_tconv.hip's, of one weight gradient umx_wgrad.hip's; the device arena is umx_arena.hip.
 //
 // The step is written out layer by layer rather than as a generic autograd tape: the v2 graph is fixed
 // (reference UnMicst1-5.py:83-237), so every tensor the backward pass needs is known at create time and lives in a
@@ -30,17 +31,15 @@ namespace {
 
 thread_local std::string g_terr;
 
-struct TConv {                       // one convolution of the step: device-packed fp32 operands [tap][Cp][Np], rebuilt every step,
-    ConvParams cp;                   // run by conv_mfma_f32 -- or (hidx >= 0, the default since round 4) repacked into conv_f16x3's
-    int nt = 1, hpix = 2;            // weight images and run in split precision
+struct TConv {                       // one convolution of the step: its host plan (umx_tconv.hip), then what upload_conv bound to it.  Run by
+    TConvSpec spec;                  // conv_mfma_f32 on device-packed fp32 operands [tap][Cp][Np], rebuilt every step -- or (hidx >= 0, the
+    TConvPlan plan;                  // default since round 4) repacked into conv_f16x3's weight images and run in split precision
+    int order = -1;                  // position in the build (-1: the graph has no such convolution)
+    ConvParams cp;                   // plan.cp with the operands bound
     float* packed[4][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
-    double mac = 0.0;                // algorithmic multiply-accumulates per image
     int hidx = -1;                   // index into umx_trainer::hls (split-precision plan), -1: fp32 kernel
-    bool direct = false;             // its weight images are gathered straight from the master tensors (no fp32 operand)
     float* winv = nullptr;           // device scalar 2^-s: undoes the scale of the repacked weights in the epilogue
-    int wsh = 0;                     // s
-    struct WSrc { size_t off, off2, cnt; };
-    std::vector<WSrc> wsrc;          // master tensor(s) each operand group reads: where the scale is re-derived from (refresh_wscales)
+    int wsh = 0;                     // s (refresh_wscales re-derives it from plan.wsrc)
 };
 
 struct H16 {                         // (hi, lo) binary16 NHWC planes of one tensor, channels padded to Cs (what conv_f16x3 reads)
@@ -71,11 +70,6 @@ struct GradSlot {                    // a gradient buffer the layers take turns 
         if (planes && hi) a.h = H16{hi, lo, round_up(C, 8)};
         return a;
     }
-};
-
-struct TapSet {
-    std::vector<std::pair<int, int>> off;   // (dy, dx) input offsets
-    std::vector<int> m;                     // master tap index per (tap, parity) : size off.size() * npar
 };
 
 struct BnSite {            // one batch-normalised tensor
@@ -121,8 +115,8 @@ struct umx_trainer {
     std::vector<Seg> segs;
     float *d_w = nullptr, *d_g = nullptr, *d_m = nullptr, *d_v = nullptr;
     // per-layer offsets into the parameter vector
-    std::vector<size_t> o_w1, o_ws, o_wt, o_w2;
-    size_t o_lb = 0, o_lt = 0;
+    std::vector<size_t> o_w1, o_ws, o_wt, o_w2, o_bn_d, o_bn_u;
+    size_t o_lb = 0, o_lt = 0, o_bn_b = 0, o_bn_t = 0;
     // activations, each with its planes and its max word (max |activation|, for the split-precision weight gradients)
     std::vector<Act> ds;                // ds[0] = data, ds[i+1] = pooled output of down layer i
     std::vector<BnSite> bn_d, bn_u;     // down layers / up layers (index = idx)
@@ -158,6 +152,9 @@ struct umx_trainer {
     bool hconv = true;
     bool wg_f32 = false;                // UMX_TRAIN_WGRAD_F32: no weight gradient takes the split-precision kernel
     bool wg_planes = true;              // the split-precision weight gradient stages from the planes
+    bool no_ksplit = false;             // UMX_TRAIN_NO_KSPLIT: no convolution splits its K loop
+    bool debug_plan = false;            // UMX_DEBUG_PLAN: every plan's line on stderr
+    int nconvs = 0;                     // (during build) convolutions planned so far: TConv::order
     const float* h_blob = nullptr;      // (during build) the initial parameters on the host: weight scales
     std::vector<HConvParams> hls;       // the split-precision plans' launch parameters
     std::vector<TConv*> hconvs;         // the convolutions that took the split-precision route, index = RepackDesc::owner
@@ -245,311 +242,118 @@ int tupload_(umx_trainer* tr, T** out, const T* host, size_t count, const char* 
 #define tzero(tr, out, count) talloc_(tr, out, count, true, #out)
 #define tupload(tr, out, host, count) tupload_(tr, out, host, count, #out)
 
-// N-tiles per workgroup.  A training batch is small (8 images): the deep layers have a handful of 256-pixel M-tiles, so
-// wide N blocks would leave most of the 256 CUs idle.  Cost model: rounds of 512 resident workgroups (2 per CU) times
-// the work of one workgroup (NT MFMAs per fragment pair + a fixed staging share); padded N counts as work.
-void choose_nt(int Cout, int mtiles, int* nt, int* Np) {
-    const int t16 = (Cout + 15) / 16;
-    int best = 1;
-    double best_cost = 1e300;
-    for (int c = 1; c <= kMaxNT; ++c) {
-        const long wgs = (long)mtiles * ((t16 + c - 1) / c);
-        const double cost = (double)((wgs + 511) / 512) * (c + 0.5);
-        if (cost < best_cost - 1e-9 || (std::fabs(cost - best_cost) <= 1e-9 && c > best)) { best = c; best_cost = cost; }
-    }
-    *nt = best;
-    *Np = round_up(t16, best) * 16;
-}
+// ---- a convolution of the step: the host pass plans it (plan_conv -> umx_tconv.hip), the device pass uploads the plan (upload_conv)
 
-// Geometry + packed-operand buffers + pack descriptors of one conv launch.
-//   groups: ngroups sources with C[g] channels; per phase and group a TapSet (master taps of tensor w_off);
-//   pack_mode per group: transpose flag, channel offset on the master's d2 axis, (npar, Cblk), optional second tensor
-struct GroupSpec {
-    int C;                      // source channels seen by the kernel
-    size_t w_off, w2_off;       // master tensor(s) in the parameter vector (w2_off = SIZE_MAX: none)
-    int d2, d3;                 // master dims [taps][d2][d3]
-    int transpose, c_off, npar, Cblk;
-    TapSet taps[4];
-};
-
-// largest |w| a convolution's packed operand can hold: the master tensor(s) each group reads (a summed pair: the sum of the maxima)
-double operand_wmax(const TConv& tc, const float* params) {
-    double wmax = 0.0;
-    for (const TConv::WSrc& w : tc.wsrc) {
-        double m1 = 0.0, m2 = 0.0;
-        for (size_t i = 0; i < w.cnt; ++i) m1 = std::max(m1, (double)std::fabs(params[w.off + i]));
-        if (w.off2 != SIZE_MAX)
-            for (size_t i = 0; i < w.cnt; ++i) m2 = std::max(m2, (double)std::fabs(params[w.off2 + i]));
-        wmax = std::max(wmax, m1 + m2);
-    }
-    return wmax;
-}
-// s such that wmax * 2^s is in [2^10, 2^11): 32 x headroom below binary16's largest finite value for the weights to grow into
-int wscale_shift(double wmax) {
-    if (!(wmax > 0.0) || !std::isfinite(wmax)) return 0;
-    int e;
-    std::frexp(wmax, &e);              // wmax = m * 2^e, m in [0.5, 1)
-    return std::max(-24, std::min(40, 11 - e));
-}
-
-// The same convolution as a split-precision plan (conv_f16x3, fp32 output): stage tables and the LDS-image layout of the weights
-// come from the host plan (plan_f16) once; the values are filled every step by repack_f16x3_kernel from the fp32 operands this TConv already
-// rebuilds on the device.  A shape the planner refuses stays on the fp32 kernel.  bwd: see setup_conv.
-int setup_hconv(umx_trainer* tr, TConv& tc, const char* what, int H, int W, int Cout, int act, int nphase, int o_mul, const int* oy,
-                const int* ox, int ngroups, GroupSpec* gs, bool bwd) {
-    if (!tr->hconv) return UMX_OK;
-    umx::Launch L;
-    L.name = what;
-    L.train = true;
-    L.ngroups = ngroups; L.nphase = nphase; L.o_mul = o_mul;
-    for (int ph = 0; ph < nphase; ++ph) { L.oy_off[ph] = oy ? oy[ph] : 0; L.ox_off[ph] = ox ? ox[ph] : 0; }
-    L.H = H; L.W = W; L.Cout = Cout; L.outH = H * o_mul; L.outW = W * o_mul; L.pool = 0; L.act = act; L.dst = -1;
-    L.Np = tc.cp.Np;
-    double wmax = 0.0;
-    for (int g = 0; g < ngroups; ++g) {
-        L.g[g].src = g;
-        L.g[g].C = gs[g].C;
-        for (int ph = 0; ph < nphase; ++ph) L.g[g].taps[ph] = gs[g].taps[ph].off;
-        if (gs[g].npar > 1 && gs[g].Cblk % 8 == 0) {
-            const int noct = (gs[g].C + 7) / 8;
-            for (int ph = 0; ph < nphase; ++ph) {
-                const TapSet& ts = gs[g].taps[ph];
-                L.g[g].dead[ph].assign(ts.off.size() * (size_t)noct, 0);
-                for (size_t t = 0; t < ts.off.size(); ++t)
-                    for (int o = 0; o < noct; ++o)
-                        if (ts.m[t * gs[g].npar + (size_t)(8 * o / gs[g].Cblk)] < 0) L.g[g].dead[ph][t * noct + o] = 1;
-            }
-        }
-        // largest |w| the packed operand can hold now: the master tensor(s) this group reads (summed pair: the sum of the maxima)
-        int ntap_master = 0;
-        for (int ph = 0; ph < nphase; ++ph)
-            for (int m : gs[g].taps[ph].m) ntap_master = std::max(ntap_master, m + 1);
-        const size_t cnt = (size_t)ntap_master * gs[g].d2 * gs[g].d3;
-        tc.wsrc.push_back({gs[g].w_off, gs[g].w2_off, cnt});
-    }
-    wmax = operand_wmax(tc, tr->h_blob);
+// host pass: tc's plan and its place in the build; with UMX_DEBUG_PLAN its line.  A shape the planner refuses is the build's error.
+int plan_conv(umx_trainer* tr, TConv& tc, const char* what, int H, int W, int Cout, int act, int nphase, int o_mul, const int* oy,
+              const int* ox, int ngroups, const GroupSpec* gs, bool bwd) {
+    TConvSpec& s = tc.spec;
+    s.name = what;
+    s.H = H; s.W = W; s.Cout = Cout; s.act = act; s.nphase = nphase; s.o_mul = o_mul;
+    for (int ph = 0; ph < nphase; ++ph) { s.oy[ph] = oy ? oy[ph] : 0; s.ox[ph] = ox ? ox[ph] : 0; }
+    s.ngroups = ngroups;
+    for (int g = 0; g < ngroups; ++g) s.g[g] = gs[g];
+    s.bwd = bwd;
+    tc.order = tr->nconvs++;
+    TConvEnv env;
+    env.B = tr->B; env.imSize = tr->hp.imSize; env.hconv = tr->hconv; env.no_ksplit = tr->no_ksplit; env.params = tr->h_blob;
     std::string why;
-    umx::PlanInputs in;
-    in.imSize = tr->hp.imSize;
-    in.out_f32 = true;
-    umx::HostPlan P;
-    if (!umx::conv_geometry(L, &why) || umx::plan_f16(L, in, &P, &why) != UMX_OK) {
-        if (getenv("UMX_DEBUG_PLAN")) fprintf(stderr, "[umx train] %s stays on the fp32 kernel: %s\n", what, why.c_str());
-        return UMX_OK;
+    if (!tconv_plan(s, env, &tc.plan, &why)) return tfail(tr, UMX_ERR_INVALID, "%s", why.c_str());
+    if (tr->debug_plan) {
+        if (!tc.plan.refused.empty()) fprintf(stderr, "[umx train] %s stays on the fp32 kernel: %s\n", what, tc.plan.refused.c_str());
+        fprintf(stderr, "[umx train] %s\n", tc.plan.text.c_str());
     }
-    HConvParams& h = P.h;   // (the weight slabs hold the k-maps; repack_f16x3_kernel writes their values every step)
-    HStage* stages = nullptr;
-    float* econst = nullptr;
-    T_TRY(tupload(tr, &stages, P.stages.data(), P.stages.size()));
-    T_TRY(tupload(tr, &econst, P.econst.data(), P.econst.size()));
-    h.stages = stages;
-    h.econst = reinterpret_cast<const uint4*>(econst);
-    for (int ph = 0; ph < nphase; ++ph) {
-        _Float16* slab = nullptr;
-        if (!P.wimg[ph].empty()) T_TRY(tupload(tr, &slab, P.wimg[ph].data(), P.wimg[ph].size()));
-        h.ph[ph].w = reinterpret_cast<const uint4*>(slab);
-    }
-    const int sh = wscale_shift(wmax);
-    tc.wsh = sh;
-    const float inv = std::ldexp(1.f, -sh);
-    T_TRY(tupload(tr, &tc.winv, &inv, 1));
-    static_assert(sizeof(umx::HWRef) == sizeof(HWRefDev) && sizeof(HWRefDev) == 12, "reference record layout");
-    // The planner's references address the packed fp32 operand [tap][Cp][Np]; rewritten here into the master tensor's own
-    // coordinates (the index arithmetic of pack_weights_kernel, done once on the host), the per-step repack reads the parameters
-    // directly and this convolution needs no fp32 operand at all.  An octet that straddles two parity blocks keeps the packed route.
-    bool direct = true;
-    for (int ph = 0; ph < nphase && direct; ++ph)
-        for (const umx::HWRef& r : P.wrefs[ph]) {
-            const GroupSpec& G = gs[r.arr];
-            const int c0 = (int)(((size_t)r.base / L.Np) % round_up(G.C, 4));
-            if (c0 / G.Cblk != (c0 + r.nvalid - 1) / G.Cblk) { direct = false; break; }
-        }
-    if (direct)
-        for (int ph = 0; ph < nphase; ++ph) {
-            std::vector<umx::HWRef> out;
-            out.reserve(P.wrefs[ph].size());
-            for (const umx::HWRef& r : P.wrefs[ph]) {
-                const GroupSpec& G = gs[r.arr];
-                const int Cp = round_up(G.C, 4);
-                const int co = (int)((size_t)r.base % L.Np);
-                const size_t row = (size_t)r.base / L.Np;
-                const int c0 = (int)(row % Cp), t = (int)(row / Cp);
-                const int par = c0 / G.Cblk, cc = c0 - par * G.Cblk;
-                const int m = G.taps[ph].m[(size_t)t * G.npar + par];
-                if (m < 0) continue;   // a tap this parity block does not have: the unit stays zero
-                const size_t idx = G.transpose ? ((size_t)m * G.d2 + G.c_off + co) * G.d3 + cc : ((size_t)m * G.d2 + G.c_off + cc) * G.d3 + co;
-                if (idx > (size_t)INT_MAX) return tfail(tr, UMX_ERR_INVALID, "%s: master tensor too large for a weight reference", what);
-                out.push_back(umx::HWRef{r.dst, (int)idx, r.nvalid, r.arr});
-            }
-            P.wrefs[ph].swap(out);
-        }
-    tc.direct = direct;
-    for (int ph = 0; ph < nphase; ++ph) {
-        const std::vector<umx::HWRef>& refs = P.wrefs[ph];
-        if (refs.empty()) continue;
-        HWRefDev* d = nullptr;
-        T_TRY(talloc(tr, &d, refs.size()));
-        T_HIP(tr, hipMemcpy(d, refs.data(), refs.size() * sizeof(HWRefDev), hipMemcpyHostToDevice));
-        RepackDesc rd;
-        memset(&rd, 0, sizeof rd);
-        rd.refs = d;
-        rd.n = (int)refs.size();
-        for (int g = 0; g < ngroups; ++g) {
-            rd.arr[g] = direct ? tr->d_w + gs[g].w_off : tc.packed[ph][g];
-            rd.arr2[g] = direct && gs[g].w2_off != SIZE_MAX ? tr->d_w + gs[g].w2_off : nullptr;
-            rd.estride[g] = direct ? (gs[g].transpose ? 1 : gs[g].d3) : 0;
-        }
-        rd.stride = tc.cp.Np;
-        rd.scale = std::ldexp(1.f, sh);
-        rd.slab = const_cast<uint4*>(h.ph[ph].w);
-        rd.bwd = bwd ? 1 : 0;
-        rd.owner = (int)tr->hconvs.size();
-        tr->rdescs.push_back(rd);
-        tr->max_refs = std::max(tr->max_refs, rd.n);
-    }
-    {   // K split: enough workgroups to occupy the chip (two per CU) where a batch of 8 leaves a deep layer a few dozen
-        const long wgs = (long)((tr->B + h.imgs - 1) / h.imgs) * h.tiles_y * h.tiles_x * h.nblocks * nphase;
-        // (one workgroup per CU: 512 / 768 / 1024 lose 3 / 7 / 10 % of the step to the ordered reduce over more partial sums, 128 / 192
-        // lose 1 % to idle CUs -- profiles/r04/train_ksplit_sweep.txt)
-        const long target = 256;
-        int S = (int)std::min<long>(kMaxKSplit, wgs > 0 ? (target + wgs - 1) / wgs : 1);
-        if (getenv("UMX_TRAIN_NO_KSPLIT") || wgs * 2 > target) S = 1;
-        std::vector<std::vector<int>> starts(nphase);   // per phase: stage indices (relative) where a halo chunk begins
-        for (int ph = 0; ph < nphase && S > 1; ++ph) {
-            for (int si = 0; si < h.ph[ph].nstages; ++si)
-                if (P.stages[h.ph[ph].stage0 + si].group >= 0) starts[ph].push_back(si);
-            S = std::min(S, (int)starts[ph].size());
-        }
-        if (S > 1) {
-            for (int ph = 0; ph < nphase; ++ph) {
-                const int nch = (int)starts[ph].size();
-                for (int k = 0; k < S; ++k) h.ks0[ph][k] = (short)starts[ph][(size_t)((long)nch * k / S)];
-                h.ks0[ph][S] = (short)h.ph[ph].nstages;
-            }
-            h.ksplit = S;
-            h.split_stride = (size_t)tr->B * L.outH * L.outW * Cout;
-            if (h.xcd_order == 2) h.xcd_order = 1;
-            tr->split_floats = std::max(tr->split_floats, (size_t)S * h.split_stride);
-        }
-        if (getenv("UMX_DEBUG_PLAN"))
-            fprintf(stderr, "[umx train] %s%s: %d x %d -> %d ch, %d phase(s), NT %d x %d blocks, %d k-steps, %ld workgroups, K split %d\n",
-                    what, bwd ? " (backward)" : "", H, W, Cout, nphase, h.NT, h.nblocks, P.n_ksteps, wgs, S);
-    }
-    tc.hidx = (int)tr->hls.size();
-    tr->hls.push_back(h);
-    tr->hconvs.push_back(&tc);
     return UMX_OK;
 }
 
-// bwd: the convolution belongs to the backward pass only (its operands are packed on the side stream while the forward pass runs)
-int setup_conv(umx_trainer* tr, TConv& tc, const char* what, int H, int W, int Cout, int act, int nphase, int o_mul,
-               const int* oy, const int* ox, int ngroups, GroupSpec* gs, bool bwd) {
-    ConvParams& p = tc.cp;
-    memset(&p, 0, sizeof p);
-    {
-        const int TWm0 = std::min(16, W), TH0 = std::min(16, H);
-        const int imgs0 = (16 / TWm0) * (16 / TH0);
-        choose_nt(Cout, ((tr->B + imgs0 - 1) / imgs0) * (H / TH0) * (W / TWm0) * nphase, &tc.nt, &p.Np);
+// device pass: the plan's buffers in the order a convolution always had them -- fp32 operands per (phase, group), stages, epilogue
+// constants, slabs per phase, winv, references per phase -- their pointers bound, and its pack / repack descriptors appended.
+// (A direct convolution's fp32 operands stay allocated, though nothing reads them: the trainer's buffer sequence is unchanged.)
+int upload_conv(umx_trainer* tr, TConv& tc) {
+    const TConvSpec& s = tc.spec;
+    TConvPlan& p = tc.plan;
+    tc.cp = p.cp;
+    for (size_t k = 0; k < p.operands.size(); ++k) {
+        const int ph = p.operands[k].ph, g = p.operands[k].g;
+        T_TRY(talloc(tr, &tc.packed[ph][g], p.operands[k].elems));
+        tc.cp.ph[ph].w[g] = tc.packed[ph][g];
+        if (p.packs.empty()) continue;
+        PackDesc d = p.packs[k];
+        d.dst = tc.packed[ph][g];
+        d.w = tr->d_w + s.g[g].w_off;
+        d.w2 = s.g[g].w2_off == SIZE_MAX ? nullptr : tr->d_w + s.g[g].w2_off;
+        tr->packs.push_back(d);
     }
-    int ymin = 0, ymax = 0, xmin = 0, xmax = 0, ntaps_total = 0;
-    for (int g = 0; g < ngroups; ++g)
-        for (int ph = 0; ph < nphase; ++ph)
-            for (auto& t : gs[g].taps[ph].off) {
-                ymin = std::min(ymin, t.first); ymax = std::max(ymax, t.first);
-                xmin = std::min(xmin, t.second); xmax = std::max(xmax, t.second);
-                ++ntaps_total;
+    tr->max_pack = std::max(tr->max_pack, p.max_pack);
+    tr->split_floats = std::max(tr->split_floats, p.split_floats);
+    if (p.split) {
+        HConvParams h = p.P.h;
+        HStage* stages = nullptr;
+        float* econst = nullptr;
+        T_TRY(tupload(tr, &stages, p.P.stages.data(), p.P.stages.size()));
+        T_TRY(tupload(tr, &econst, p.P.econst.data(), p.P.econst.size()));
+        h.stages = stages;
+        h.econst = reinterpret_cast<const uint4*>(econst);
+        for (int ph = 0; ph < s.nphase; ++ph) {
+            _Float16* slab = nullptr;
+            if (!p.P.wimg[ph].empty()) T_TRY(tupload(tr, &slab, p.P.wimg[ph].data(), p.P.wimg[ph].size()));
+            h.ph[ph].w = reinterpret_cast<const uint4*>(slab);
+        }
+        tc.wsh = p.wsh;
+        const float inv = std::ldexp(1.f, -tc.wsh);
+        T_TRY(tupload(tr, &tc.winv, &inv, 1));
+        for (int ph = 0; ph < s.nphase; ++ph) {
+            const std::vector<HWRef>& refs = p.P.wrefs[ph];
+            if (refs.empty()) continue;
+            HWRefDev* d = nullptr;
+            T_TRY(talloc(tr, &d, refs.size()));
+            T_HIP(tr, hipMemcpy(d, refs.data(), refs.size() * sizeof(HWRefDev), hipMemcpyHostToDevice));
+            RepackDesc rd;
+            memset(&rd, 0, sizeof rd);
+            rd.refs = d;
+            rd.n = (int)refs.size();
+            for (int g = 0; g < s.ngroups; ++g) {
+                rd.arr[g] = p.direct ? tr->d_w + s.g[g].w_off : tc.packed[ph][g];
+                rd.arr2[g] = p.direct && s.g[g].w2_off != SIZE_MAX ? tr->d_w + s.g[g].w2_off : nullptr;
+                rd.estride[g] = p.direct ? (s.g[g].transpose ? 1 : s.g[g].d3) : 0;
             }
-    if (ntaps_total > kMaxTaps) return tfail(tr, UMX_ERR_INVALID, "%s: too many filter taps", what);
-    auto lg2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
-    const int TWm = std::min(16, W), TH = std::min(16, H);
-    if ((TWm & (TWm - 1)) || (TH & (TH - 1)))
-        return tfail(tr, UMX_ERR_INVALID, "%s: layer size %d must be a power of two", what, H);
-    p.twm_log2 = lg2(TWm);
-    p.th_log2 = lg2(TH);
-    p.nimg_m = 16 / TWm;
-    p.imgs = p.nimg_m * (16 / TH);
-    p.hh = TH + ymax - ymin;
-    p.hw = TWm + xmax - xmin;
-    p.imgplane = p.hh * p.hw;
-    int plane = round_up(p.imgs * p.imgplane, 32) + 16;
-    if (plane - 32 >= p.imgs * p.imgplane) plane -= 32;
-    p.plane = plane;
-    p.ymin = ymin;
-    p.xmin = xmin;
-    p.tiles_y = H / TH;
-    p.tiles_x = W / TWm;
-    tc.hpix = (p.imgs * p.imgplane + 255) / 256;
-    if (tc.hpix > 4) return tfail(tr, UMX_ERR_INVALID, "%s: halo too large", what);
-    tc.hpix = tc.hpix <= 2 ? 2 : 4;
-    p.ngroups = ngroups;
-    p.H = H; p.W = W; p.Cout = Cout;
-    p.nphase = nphase; p.o_mul = o_mul;
-    p.outH = H * o_mul; p.outW = W * o_mul; p.pool = 0; p.act = act;
-    {   // K split: a deep layer of a small batch has a few dozen workgroups, each walking thousands of K steps with
-        // exposed staging latency -- spread the channel chunks over more workgroups (partials + ordered reduce)
-        const int img_groups = (tr->B + p.imgs - 1) / p.imgs;
-        const long wgs = (long)img_groups * p.tiles_y * p.tiles_x * nphase * (p.Np / 16 / tc.nt);
-        int min_chunks = 1 << 30;
-        for (int g = 0; g < ngroups; ++g) min_chunks = std::min(min_chunks, (round_up(gs[g].C, 4) + kCC - 1) / kCC);
-        int S = 1;
-        const long target = 1536, smax = 8;
-        if (wgs < target / 2 && !getenv("UMX_TRAIN_NO_KSPLIT"))
-            S = (int)std::max<long>(1, std::min<long>(std::min<long>(smax, target / wgs), min_chunks / 4));
-        p.ksplit = S;
-        p.split_stride = (size_t)tr->B * p.outH * p.outW * Cout;
-        if (S > 1) tr->split_floats = std::max(tr->split_floats, (size_t)S * p.split_stride);
-    }
-    if (conv_lds_bytes(tc.nt, p.plane) > 160 * 1024) return tfail(tr, UMX_ERR_INVALID, "%s: LDS footprint too large", what);
-    int tpos = 0;
-    for (int ph = 0; ph < nphase; ++ph) {
-        p.ph[ph].oy_off = oy ? oy[ph] : 0;
-        p.ph[ph].ox_off = ox ? ox[ph] : 0;
-        for (int g = 0; g < ngroups; ++g) {
-            const TapSet& ts = gs[g].taps[ph];
-            p.ph[ph].tap0[g] = tpos;
-            p.ph[ph].ntaps[g] = (int)ts.off.size();
-            for (auto& t : ts.off) p.tapoff[tpos++] = (short)((t.first - ymin) * p.hw + (t.second - xmin));
+            rd.stride = tc.cp.Np;
+            rd.scale = std::ldexp(1.f, tc.wsh);
+            rd.slab = const_cast<uint4*>(h.ph[ph].w);
+            rd.bwd = s.bwd ? 1 : 0;
+            rd.owner = (int)tr->hconvs.size();
+            tr->rdescs.push_back(rd);
+            tr->max_refs = std::max(tr->max_refs, rd.n);
         }
+        tc.hidx = (int)tr->hls.size();
+        tr->hls.push_back(h);
+        tr->hconvs.push_back(&tc);
     }
-    for (int g = 0; g < ngroups; ++g) {
-        p.C[g] = gs[g].C;
-        p.Cp[g] = round_up(gs[g].C, 4);
-        p.vec4[g] = (gs[g].C % 4) == 0;
-    }
-    // packed operands + descriptors
-    size_t npacks = 0;
-    for (int ph = 0; ph < nphase; ++ph)
-        for (int g = 0; g < ngroups; ++g) {
-            const TapSet& ts = gs[g].taps[ph];
-            const int nt = (int)ts.off.size();
-            if (nt == 0) continue;
-            if (nt * gs[g].npar > 4 * kMaxPackTaps) return tfail(tr, UMX_ERR_INVALID, "%s: too many taps to pack", what);
-            const size_t elems = (size_t)nt * p.Cp[g] * p.Np;
-            T_TRY(talloc(tr, &tc.packed[ph][g], elems));
-            p.ph[ph].w[g] = tc.packed[ph][g];
-            PackDesc d;
-            memset(&d, 0, sizeof d);
-            d.dst = tc.packed[ph][g];
-            d.w = tr->d_w + gs[g].w_off;
-            d.w2 = gs[g].w2_off == SIZE_MAX ? nullptr : tr->d_w + gs[g].w2_off;
-            d.ntaps = nt; d.Cp = p.Cp[g]; d.Np = p.Np; d.C = gs[g].C; d.N = Cout;
-            d.d2 = gs[g].d2; d.d3 = gs[g].d3;
-            d.transpose = gs[g].transpose; d.c_off = gs[g].c_off;
-            d.npar = gs[g].npar; d.Cblk = gs[g].Cblk;
-            for (size_t i = 0; i < ts.m.size(); ++i) d.mtap[i] = (short)ts.m[i];
-            d.bwd = bwd ? 1 : 0;
-            tr->packs.push_back(d);
-            ++npacks;
-            tr->max_pack = std::max(tr->max_pack, elems);
-            tc.mac += (double)H * W * nt * gs[g].C * Cout;
+    p.P = HostPlan();   // (the tables are on the device now)
+    return UMX_OK;
+}
+
+// Every convolution the host pass planned, in build order.  Called once the containers that hold them have their final size: the
+// pointers stay good for the trainer's life (upload_conv, refresh_wscales).
+std::vector<TConv*> planned_convs(umx_trainer* tr) {
+    std::vector<TConv*> all;
+    auto add = [&](TConv& tc) { if (tc.order >= 0) all.push_back(&tc); };
+    for (std::vector<TConv>* v : {&tr->c_fwd_d, &tr->c_dg_d, &tr->c_T, &tr->c_fwd_u, &tr->c_dg_us, &tr->c_dg_skip, &tr->c_dg_T})
+        for (TConv& tc : *v) add(tc);
+    add(tr->c_fwd_b);
+    add(tr->c_dg_b);
+    for (std::vector<LBlock>* v : {&tr->ldb, &tr->lub})
+        for (LBlock& b : *v) {
+            for (TConv& tc : b.fwd) add(tc);
+            for (TConv& tc : b.dg) add(tc);
+            add(b.dg_sh);
         }
-    const size_t packs_before = tr->packs.size() - npacks;
-    T_TRY(setup_hconv(tr, tc, what, H, W, Cout, act, nphase, o_mul, oy, ox, ngroups, gs, bwd));
-    if (tc.hidx >= 0 && tc.direct) tr->packs.resize(packs_before);   // nothing reads this convolution's fp32 operands
-    if (tc.hidx < 0 && getenv("UMX_DEBUG_PLAN"))
-        fprintf(stderr, "[umx train] %s%s: fp32 conv, %d x %d -> %d ch, %d phase(s), NT %d, %d img/group, %ld workgroups, K split %d\n", what,
-                bwd ? " (backward)" : "", H, W, Cout, nphase, tc.nt, p.imgs,
-                (long)((tr->B + p.imgs - 1) / p.imgs) * p.tiles_y * p.tiles_x * nphase * (p.Np / 16 / tc.nt), p.ksplit);
+    std::sort(all.begin(), all.end(), [](const TConv* a, const TConv* b) { return a->order < b->order; });
+    return all;
+}
+
+int upload_convs(umx_trainer* tr) {
+    for (TConv* tc : planned_convs(tr)) T_TRY(upload_conv(tr, *tc));
     return UMX_OK;
 }
 
@@ -601,26 +405,48 @@ int to_h16(umx_trainer* tr, const Act& a, hipStream_t st, bool omax = false) {
     return UMX_OK;
 }
 
-// (s0.inv: the inverse scale of its planes where they hold a gradient)
-int run_hconv(umx_trainer* tr, TConv& tc, const Act& s0, const Act* s1, float* dst, hipStream_t st) {
+int pack_all(umx_trainer* tr, hipStream_t st, int part);
+int refresh_wscales(umx_trainer* tr);
+
+// the K-split scratch of the stream a convolution is enqueued on (one per stream)
+float* split_scratch(const umx_trainer* tr, hipStream_t st) { return st == tr->stream ? tr->d_split : st == tr->aux ? tr->d_split3 : tr->d_split2; }
+
+// a convolution on stream st, on whichever route its plan took: conv_f16x3 reads the (hi, lo) planes of src (+ src1; src.inv: the
+// inverse scale of its planes where they hold a gradient), conv_mfma_f32 their fp32 tensors.  A K-split launch writes raw partial
+// sums to the stream's scratch, then the ordered reduce applies the activation.
+int run_tconv(umx_trainer* tr, TConv& tc, const Act& src, float* dst, const Act* src1, hipStream_t st) {
+    float* const scratch = split_scratch(tr, st);
+    if (tc.hidx < 0) {
+        ConvParams p = tc.cp;
+        p.src[0] = src.x;
+        p.src[1] = src1 ? src1->x : nullptr;
+        p.dst = dst;
+        p.B = tr->B;
+        if (p.ksplit > 1) {
+            p.dst = scratch;
+            p.act = ACT_NONE;
+        }
+        T_HIP(tr, launch_conv(p, tc.plan.nt, tc.plan.hpix, st));
+        if (p.ksplit > 1) T_HIP(tr, launch_split_reduce(scratch, p.ksplit, p.split_stride, p.split_stride, tc.cp.act, dst, st));
+        return UMX_OK;
+    }
     HConvParams p = tr->hls[tc.hidx];
     p.B = tr->B;
     p.overflow_flag = reinterpret_cast<int*>(tr->d_maxw + tr->n_maxw);
-    const H16* src[2] = {&s0.h, s1 ? &s1->h : &s0.h};
+    const H16* h16[2] = {&src.h, src1 ? &src1->h : &src.h};
     for (int gi = 0; gi < 2; ++gi) {
-        p.src_hi[gi] = gi == 0 || s1 ? src[gi]->hi : nullptr;
-        p.src_lo[gi] = gi == 0 || s1 ? src[gi]->lo : nullptr;
-        p.Cs[gi] = src[gi]->Cs;
-        p.srcA[gi] = src[gi]->Cs * 2;
+        p.src_hi[gi] = gi == 0 || src1 ? h16[gi]->hi : nullptr;
+        p.src_lo[gi] = gi == 0 || src1 ? h16[gi]->lo : nullptr;
+        p.Cs[gi] = h16[gi]->Cs;
+        p.srcA[gi] = h16[gi]->Cs * 2;
         p.srcB[gi] = 16;
     }
     p.dst_f32 = dst;
     p.dyn[0] = tc.winv;
-    p.dyn[1] = s0.inv;
-    if (p.ksplit > 1) {   // raw partial sums, then the ordered reduce applies the activation
+    p.dyn[1] = src.inv;
+    if (p.ksplit > 1) {
         const int act = p.act;
         p.act = ACT_NONE;
-        float* const scratch = st == tr->stream ? tr->d_split : st == tr->aux ? tr->d_split3 : tr->d_split2;   // (one scratch per stream)
         p.dst_f32 = scratch;
         T_HIP(tr, launch_conv_f16(p, st));
         T_HIP(tr, launch_split_reduce(scratch, p.ksplit, p.split_stride, p.split_stride, act, dst, st));
@@ -630,47 +456,11 @@ int run_hconv(umx_trainer* tr, TConv& tc, const Act& s0, const Act* s1, float* d
     return UMX_OK;
 }
 
-int pack_all(umx_trainer* tr, hipStream_t st, int part);
-int refresh_wscales(umx_trainer* tr);
-
-int run_conv(umx_trainer* tr, TConv& tc, const float* src0, const float* src1, float* dst) {
-    ConvParams p = tc.cp;
-    p.src[0] = src0;
-    p.src[1] = src1;
-    p.dst = dst;
-    p.B = tr->B;
-    if (p.ksplit > 1) {   // raw partial sums, then the ordered reduce applies the activation
-        p.dst = tr->d_split;
-        p.act = ACT_NONE;
-    }
-    T_HIP(tr, launch_conv(p, tc.nt, tc.hpix, tr->stream));
-    if (p.ksplit > 1) T_HIP(tr, launch_split_reduce(tr->d_split, p.ksplit, p.split_stride, p.split_stride, tc.cp.act, dst, tr->stream));
-    return UMX_OK;
-}
-
-// a convolution on the main stream, on whichever route its plan took: conv_f16x3 reads the (hi, lo) planes of src (+ src1),
-// conv_mfma_f32 their fp32 tensors
-int run_tconv(umx_trainer* tr, TConv& tc, const Act& src, float* dst, const Act* src1 = nullptr) {
-    if (tc.hidx >= 0) return run_hconv(tr, tc, src, src1, dst, tr->stream);
-    return run_conv(tr, tc, src.x, src1 ? src1->x : nullptr, dst);
-}
-
 // an activation written by a kernel without a plane writer (the input batch, the transposed convolutions' outputs): its max |x|
 // for the split-precision weight gradient (training) and, on the split-precision route, its planes -- there in the same pass
 int track_act(umx_trainer* tr, const Act& a, bool training) {
     if (training && !tr->hconv) T_HIP(tr, launch_absmax(a.x, a.npix(tr->B) * a.C, a.max, tr->stream));
     return to_h16(tr, a, tr->stream, training);
-}
-
-TapSet same_taps(int ks, bool flipped) {   // stride-1 SAME conv (or its input gradient: offsets negated)
-    TapSet t;
-    const int ph = (ks - 1) / 2;
-    for (int a = 0; a < ks; ++a)
-        for (int b = 0; b < ks; ++b) {
-            t.off.push_back(flipped ? std::make_pair(ph - a, ph - b) : std::make_pair(a - ph, b - ph));
-            t.m.push_back(a * ks + b);
-        }
-    return t;
 }
 
 int setup_wgrad(umx_trainer* tr, WgradPlan& w, const char* what, int H, int Cxt, int Cx, int Cg, const TapSet& slabs,
@@ -689,7 +479,7 @@ int setup_wgrad(umx_trainer* tr, WgradPlan& w, const char* what, int H, int Cxt,
     std::string why;
     if (!wgrad_setup(&w, tr->wg_f32, &why)) return tfail(tr, UMX_ERR_INVALID, "%s: %s", what, why.c_str());
     tr->ws_floats = std::max(tr->ws_floats, wgrad_ws_floats(w));
-    if (getenv("UMX_DEBUG_PLAN")) fprintf(stderr, "[umx train] %s\n", wgrad_describe(w, what).c_str());
+    if (tr->debug_plan) fprintf(stderr, "[umx train] %s\n", wgrad_describe(w, what).c_str());
     return UMX_OK;
 }
 
@@ -799,19 +589,19 @@ int forward_pass(umx_trainer* tr, const float* data, bool training, bool update)
     T_TRY(track_act(tr, tr->ds[0], training));
     for (int i = 0; i < L; ++i) {
         BnSite& s = tr->bn_d[i];
-        T_TRY(run_tconv(tr, tr->c_fwd_d[i], tr->ds[i], s.z));
+        T_TRY(run_tconv(tr, tr->c_fwd_d[i], tr->ds[i], s.z, nullptr, st));
         T_TRY(bn_forward_stats(tr, s, update, training));
         T_TRY(act(s, 1, down_rate(tr, i), LAYER_DOWN + i, tr->ds[i + 1]));
     }
-    T_TRY(run_tconv(tr, tr->c_fwd_b, tr->ds[L], tr->bn_b.z));
+    T_TRY(run_tconv(tr, tr->c_fwd_b, tr->ds[L], tr->bn_b.z, nullptr, st));
     T_TRY(bn_forward_stats(tr, tr->bn_b, update, training));
     T_TRY(act(tr->bn_b, 0, o.drop_bottom, LAYER_BOTTOM, tr->act_b));
     const Act* cur = &tr->act_b;
     for (int idx = L - 1; idx >= 0; --idx) {
         BnSite& s = tr->bn_u[idx];
-        T_TRY(run_tconv(tr, tr->c_T[idx], *cur, tr->us[idx].x));
+        T_TRY(run_tconv(tr, tr->c_T[idx], *cur, tr->us[idx].x, nullptr, st));
         T_TRY(track_act(tr, tr->us[idx], training));
-        T_TRY(run_tconv(tr, tr->c_fwd_u[idx], tr->ds[idx], s.z, &tr->us[idx]));
+        T_TRY(run_tconv(tr, tr->c_fwd_u[idx], tr->ds[idx], s.z, &tr->us[idx], st));
         T_TRY(bn_forward_stats(tr, s, update, training));
         // (cv[0] has no planes: only the 1x1 head reads it)
         T_TRY(act(s, 0, up_rate(tr, idx), LAYER_UP + idx, tr->cv[idx]));
@@ -943,15 +733,15 @@ int enqueue_step(umx_trainer* tr, const float* data, const float* labels, const 
         T_TRY(dz_slot(s, act_params(tr, s, 0, ACT_LEAKY, up_rate(tr, idx), LAYER_UP + idx), tr->DA, nullptr, true, &dz));
         T_TRY(run_wgrad(tr, tr->wg_u0[idx], tr->ds[idx], dz, Cskip + Cup, 0, tr->o_w2[idx], o.reg_up, SIZE_MAX, ws));
         T_TRY(run_wgrad(tr, tr->wg_u1[idx], tr->us[idx], dz, Cskip + Cup, Cskip, tr->o_w2[idx], o.reg_up, SIZE_MAX, ws));
-        T_TRY(run_tconv(tr, tr->c_dg_us[idx], dz, tr->DB));
+        T_TRY(run_tconv(tr, tr->c_dg_us[idx], dz, tr->DB, nullptr, st));
         if (idx >= 1 && use_aux && tr->c_dg_skip[idx].hidx >= 0) {   // (on the weight gradients' stream it was 2 % slower; this stream is its own)
             T_HIP(tr, hipStreamWaitEvent(tr->aux, tr->ev_dz[slot], 0));
-            T_TRY(run_hconv(tr, tr->c_dg_skip[idx], dz, nullptr, tr->dskip[idx], tr->aux));
+            T_TRY(run_tconv(tr, tr->c_dg_skip[idx], dz, tr->dskip[idx], nullptr, tr->aux));
             T_HIP(tr, hipEventRecord(tr->ev_aux[slot], tr->aux));
             T_HIP(tr, hipEventRecord(tr->ev_skip[idx], tr->aux));
             aux_used[slot] = true;
         } else if (idx >= 1) {
-            T_TRY(run_tconv(tr, tr->c_dg_skip[idx], dz, tr->dskip[idx]));
+            T_TRY(run_tconv(tr, tr->c_dg_skip[idx], dz, tr->dskip[idx], nullptr, st));
         }
         const Act gs = tr->gs[slot].view(Sh, 4 * Cup, tr->smax[idx]);
         T_HIP(tr, launch_leaky_bwd_s2d_max(tr->DB, tr->us[idx].x, B, Sh, Cup, 0.2f, gs.x, gs.max, st));
@@ -965,7 +755,7 @@ int enqueue_step(umx_trainer* tr, const float* data, const float* labels, const 
         // (the transposed convolution's filter: X is gS, G the layer's input)
         T_TRY(run_wgrad(tr, tr->wg_T[idx], gs_planes ? gs : gs.without_planes(), layer_in, Cup, 0, tr->o_wt[idx], o.reg_up, SIZE_MAX, ws));
         T_TRY(side_done(slot));
-        T_TRY(run_tconv(tr, tr->c_dg_T[idx], gs, tr->DA));
+        T_TRY(run_tconv(tr, tr->c_dg_T[idx], gs, tr->DA, nullptr, st));
         slot = (slot + 1) % tr->nslots;
     }
     {   // bottom layer
@@ -973,7 +763,7 @@ int enqueue_step(umx_trainer* tr, const float* data, const float* labels, const 
         T_TRY(dz_slot(tr->bn_b, act_params(tr, tr->bn_b, 0, ACT_LEAKY, o.drop_bottom, LAYER_BOTTOM), tr->DA, nullptr, true, &dz));
         T_TRY(run_wgrad(tr, tr->wg_b, tr->ds[L], dz, tr->n[L], 0, tr->o_lb, o.reg_bottom, SIZE_MAX, ws));
         T_TRY(side_done(slot));
-        T_TRY(run_tconv(tr, tr->c_dg_b, dz, tr->DB));
+        T_TRY(run_tconv(tr, tr->c_dg_b, dz, tr->DB, nullptr, st));
         slot = (slot + 1) % tr->nslots;
     }
     for (int i = L - 1; i >= 0; --i) {     // down layers
@@ -987,7 +777,7 @@ int enqueue_step(umx_trainer* tr, const float* data, const float* labels, const 
         T_TRY(run_wgrad(tr, tr->wg_d[i], i >= 1 ? tr->ds[i] : tr->ds[i].without_planes(), dz, tr->n[i], 0, tr->o_ws[i], o.reg_down,
                         tr->o_w1[i], ws));
         T_TRY(side_done(slot));
-        if (i >= 1) T_TRY(run_tconv(tr, tr->c_dg_d[i], dz, tr->DB));
+        if (i >= 1) T_TRY(run_tconv(tr, tr->c_dg_d[i], dz, tr->DB, nullptr, st));
         slot = (slot + 1) % tr->nslots;
     }
 #undef ws
@@ -1024,15 +814,6 @@ void fill_common(umx_train_options* o) {
     o->seed = 1234;
 }
 
-// a single-phase group of one source: C channels, master tensor(s) at w_off (+ w2_off) of dims [taps][d2][d3]
-GroupSpec one_group(int C, size_t w_off, size_t w2_off, int d2, int d3, int transpose, int c_off, const TapSet& ts) {
-    GroupSpec g;
-    g.C = C; g.w_off = w_off; g.w2_off = w2_off; g.d2 = d2; g.d3 = d3; g.transpose = transpose; g.c_off = c_off;
-    g.npar = 1; g.Cblk = std::max(C, 1);
-    g.taps[0] = ts;
-    return g;
-}
-
 // One up layer's convolutions (shared by both graphs): the stride-2 transposed conv (forward with `act_T` fused, input gradient on
 // the space-to-depth output gradient, weight gradient), then the concat conv [ds_idx, us] -> Cup (forward, input gradients into us and
 // -- idx >= 1 -- into the skip, weight gradients of both halves).  S: the layer's input size on entry, its output size on return.
@@ -1042,58 +823,20 @@ int setup_up_layer(umx_trainer* tr, int idx, int& S, int act_T, double& mac_tota
     const TapSet fwd = same_taps(ks, false), flp = same_taps(ks, true);
     char nm[64];
     snprintf(nm, sizeof nm, "lu%d", idx);
-    const int pb = (ks - 2) / 2;   // pad_before of the stride-2 SAME conv whose gradient the transposed conv is
     const int Cskip = n[idx], Cup = n[idx + 1], Cin = n[idx + 2];
-    {   // transposed conv forward: 4 sub-pixel phases (out[2i+a-pb] += in[i] * Wt[a]); its activation fused
+    {   // transposed conv forward: 4 sub-pixel phases; its activation fused
         GroupSpec g = one_group(Cin, tr->o_wt[idx], SIZE_MAX, Cup, Cin, 1, 0, TapSet());
         int oy[4], ox[4];
-        for (int p = 0; p < 4; ++p) {
-            const int pu = p >> 1, pv = p & 1;
-            oy[p] = pu; ox[p] = pv;
-            for (int a = 0; a < ks; ++a) {
-                if (((a - pb - pu) & 1) != 0) continue;
-                for (int b = 0; b < ks; ++b) {
-                    if (((b - pb - pv) & 1) != 0) continue;
-                    g.taps[p].off.push_back({(pu + pb - a) / 2, (pv + pb - b) / 2});
-                    g.taps[p].m.push_back(a * ks + b);
-                }
-            }
-        }
-        T_TRY(setup_conv(tr, tr->c_T[idx], nm, S, S, Cup, act_T, 4, 2, oy, ox, 1, &g, false));
+        transposed_fwd_taps(ks, &g, oy, ox);
+        T_TRY(plan_conv(tr, tr->c_T[idx], nm, S, S, Cup, act_T, 4, 2, oy, ox, 1, &g, false));
         mac_total += (double)S * S * ks * ks * Cin * Cup;
     }
-    {   // transposed conv backward on the space-to-depth gradient gS[.., (pa,pb)*Cup + c] = dY[2i+pa, 2j+pb, c]:
-        // dX[i] = sum_a dY[2i + a - pb] Wt[a]  ->  q = a - pb = 2*di + pa
-        auto split = [](int q, int* d, int* par) { *par = ((q % 2) + 2) % 2; *d = (q - *par) / 2; };
-        std::vector<std::pair<int, int>> offs;
-        for (int a = 0; a < ks; ++a)
-            for (int b = 0; b < ks; ++b) {
-                int di, pa, dj, pbb;
-                split(a - pb, &di, &pa);
-                split(b - pb, &dj, &pbb);
-                std::pair<int, int> od{di, dj};
-                if (std::find(offs.begin(), offs.end(), od) == offs.end()) offs.push_back(od);
-            }
+    {   // transposed conv backward: a stride-1 conv over the space-to-depth form of the output gradient
         GroupSpec g = one_group(4 * Cup, tr->o_wt[idx], SIZE_MAX, Cup, Cin, 0, 0, TapSet());
-        g.npar = 4; g.Cblk = Cup;
-        g.taps[0].off = offs;
-        g.taps[0].m.assign(offs.size() * 4, -1);
-        TapSet slabs;                 // weight-gradient slabs, grouped by parity block
+        TapSet slabs;
         std::vector<int> coff;
-        for (int par = 0; par < 4; ++par)
-            for (int a = 0; a < ks; ++a)
-                for (int b = 0; b < ks; ++b) {
-                    int di, pa, dj, pbb;
-                    split(a - pb, &di, &pa);
-                    split(b - pb, &dj, &pbb);
-                    if (pa * 2 + pbb != par) continue;
-                    const size_t t = std::find(offs.begin(), offs.end(), std::make_pair(di, dj)) - offs.begin();
-                    g.taps[0].m[t * 4 + par] = a * ks + b;
-                    slabs.off.push_back({di, dj});
-                    slabs.m.push_back(a * ks + b);
-                    coff.push_back(par * Cup);
-                }
-        T_TRY(setup_conv(tr, tr->c_dg_T[idx], nm, S, S, Cin, ACT_NONE, 1, 1, nullptr, nullptr, 1, &g, true));
+        transposed_bwd_taps(ks, Cup, &g, &slabs, &coff);
+        T_TRY(plan_conv(tr, tr->c_dg_T[idx], nm, S, S, Cin, ACT_NONE, 1, 1, nullptr, nullptr, 1, &g, true));
         T_TRY(setup_wgrad(tr, tr->wg_T[idx], nm, S, 4 * Cup, Cup, Cin, slabs, coff));
         mac_total += 2.0 * S * S * ks * ks * Cin * Cup;
     }
@@ -1101,15 +844,15 @@ int setup_up_layer(umx_trainer* tr, int idx, int& S, int act_T, double& mac_tota
     {
         GroupSpec g2[2] = {one_group(Cskip, tr->o_w2[idx], SIZE_MAX, Cskip + Cup, Cup, 0, 0, fwd),
                            one_group(Cup, tr->o_w2[idx], SIZE_MAX, Cskip + Cup, Cup, 0, Cskip, fwd)};
-        T_TRY(setup_conv(tr, tr->c_fwd_u[idx], nm, S, S, Cup, ACT_NONE, 1, 1, nullptr, nullptr, 2, g2, false));
-        mac_total += tr->c_fwd_u[idx].mac;
+        T_TRY(plan_conv(tr, tr->c_fwd_u[idx], nm, S, S, Cup, ACT_NONE, 1, 1, nullptr, nullptr, 2, g2, false));
+        mac_total += tr->c_fwd_u[idx].plan.mac;
         GroupSpec gu = one_group(Cup, tr->o_w2[idx], SIZE_MAX, Cskip + Cup, Cup, 1, Cskip, flp);
-        T_TRY(setup_conv(tr, tr->c_dg_us[idx], nm, S, S, Cup, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gu, true));
-        mac_total += tr->c_dg_us[idx].mac;
+        T_TRY(plan_conv(tr, tr->c_dg_us[idx], nm, S, S, Cup, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gu, true));
+        mac_total += tr->c_dg_us[idx].plan.mac;
         if (idx >= 1) {
             GroupSpec gk = one_group(Cup, tr->o_w2[idx], SIZE_MAX, Cskip + Cup, Cup, 1, 0, flp);
-            T_TRY(setup_conv(tr, tr->c_dg_skip[idx], nm, S, S, Cskip, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gk, true));
-            mac_total += tr->c_dg_skip[idx].mac;
+            T_TRY(plan_conv(tr, tr->c_dg_skip[idx], nm, S, S, Cskip, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gk, true));
+            mac_total += tr->c_dg_skip[idx].plan.mac;
         }
         T_TRY(setup_wgrad(tr, tr->wg_u0[idx], nm, S, Cskip, Cskip, Cup, fwd, {}));
         T_TRY(setup_wgrad(tr, tr->wg_u1[idx], nm, S, Cup, Cup, Cup, fwd, {}));
@@ -1128,11 +871,20 @@ void set_shape(umx_trainer* tr) {
     for (int i = 0; i < tr->L; ++i) tr->n.push_back(tr->n.back() * hp.featMapsFact);
 }
 
-// the parameter vector (nparams floats, laid out by the graph's build) from the blob; its gradient and the optimiser's two slots
-int alloc_params(umx_trainer* tr, const float* blob, size_t blob_floats, size_t nparams) {
+// (host pass) the blob is the parameter vector of nparams floats the graph's build has laid out: the plans' weight scales come from it
+int take_blob(umx_trainer* tr, const float* blob, size_t blob_floats, size_t nparams) {
     tr->nparams = nparams;
     if (blob_floats != nparams)
         return tfail(tr, UMX_ERR_BLOB, "weight blob has %zu floats, the graph needs %zu", blob_floats, nparams);
+    tr->h_blob = blob;
+    tr->ds.resize(tr->L + 1); tr->us.resize(tr->L);
+    return UMX_OK;
+}
+
+// (device pass) the parameter vector from the blob; its gradient and the optimiser's two slots
+int alloc_params(umx_trainer* tr) {
+    const size_t nparams = tr->nparams;
+    const float* blob = tr->h_blob;
     T_TRY(tupload(tr, &tr->d_w, blob, nparams));
     T_TRY(tzero(tr, &tr->d_g, nparams));
     T_TRY(tzero(tr, &tr->d_m, nparams));
@@ -1141,15 +893,13 @@ int alloc_params(umx_trainer* tr, const float* blob, size_t blob_floats, size_t 
 }
 
 // the route of the forward / input-gradient convolutions: split precision (planes of every tensor they read; the graph's build
-// allocates them) unless UMX_TRAIN_CONV_F32 asks for the exact-fp32 kernels
-int select_route(umx_trainer* tr, const float* blob) {
+// allocates them) unless UMX_TRAIN_CONV_F32 asks for the exact-fp32 kernels -- and the other switches of the environment, each read here, once
+void select_route(umx_trainer* tr) {
     tr->hconv = !getenv("UMX_TRAIN_CONV_F32");
     tr->wg_f32 = getenv("UMX_TRAIN_WGRAD_F32") != nullptr;
+    tr->no_ksplit = getenv("UMX_TRAIN_NO_KSPLIT") != nullptr;
+    tr->debug_plan = getenv("UMX_DEBUG_PLAN") != nullptr;
     if (const char* e = getenv("UMX_TRAIN_WSCALE_EVERY")) tr->wscale_every = atoi(e);
-    tr->wg_planes = tr->hconv;
-    tr->h_blob = blob;
-    tr->ds.resize(tr->L + 1); tr->us.resize(tr->L);
-    return UMX_OK;
 }
 
 // the bottom layer (the same in both graphs) at size S: forward conv, input gradient, weight gradient
@@ -1158,19 +908,23 @@ int setup_bottom(umx_trainer* tr, int S, double& mac_total) {
     const int L = tr->L, ks = tr->hp.ks;
     const TapSet fwd = same_taps(ks, false), flp = same_taps(ks, true);
     GroupSpec g = one_group(n[L], tr->o_lb, SIZE_MAX, n[L], n[L + 1], 0, 0, fwd);
-    T_TRY(setup_conv(tr, tr->c_fwd_b, "lb", S, S, n[L + 1], ACT_NONE, 1, 1, nullptr, nullptr, 1, &g, false));
+    T_TRY(plan_conv(tr, tr->c_fwd_b, "lb", S, S, n[L + 1], ACT_NONE, 1, 1, nullptr, nullptr, 1, &g, false));
     GroupSpec gd = one_group(n[L + 1], tr->o_lb, SIZE_MAX, n[L], n[L + 1], 1, 0, flp);
-    T_TRY(setup_conv(tr, tr->c_dg_b, "lb", S, S, n[L], ACT_NONE, 1, 1, nullptr, nullptr, 1, &gd, true));
+    T_TRY(plan_conv(tr, tr->c_dg_b, "lb", S, S, n[L], ACT_NONE, 1, 1, nullptr, nullptr, 1, &gd, true));
     T_TRY(setup_wgrad(tr, tr->wg_b, "lb", S, n[L], n[L], n[L + 1], fwd, {}));
-    mac_total += tr->c_fwd_b.mac + tr->c_dg_b.mac + (double)S * S * ks * ks * n[L] * n[L + 1];
+    mac_total += tr->c_fwd_b.plan.mac + tr->c_dg_b.plan.mac + (double)S * S * ks * ks * n[L] * n[L + 1];
     return UMX_OK;
 }
 
-// end of build, once every convolution is set up: FLOPs per image (+ the 1x1 head), the weight gradients' slice workspace and the
-// K-split scratch (side_streams: also those of the side streams), the regularised segments, and the pack / repack descriptors
-int finish_build(umx_trainer* tr, double mac_total, bool side_streams) {
+// end of the host pass: FLOPs per image (+ the 1x1 head)
+void finish_plan(umx_trainer* tr, double mac_total) {
     mac_total += 3.0 * tr->P * tr->P * tr->n[1] * tr->K;
     tr->flops_per_image = 2.0 * mac_total;
+}
+
+// end of the device pass, once every convolution is uploaded: the weight gradients' slice workspace and the K-split scratch
+// (side_streams: also those of the side streams), the regularised segments, and the pack / repack descriptors
+int finish_build(umx_trainer* tr, bool side_streams) {
     T_TRY(talloc(tr, &tr->d_ws, tr->ws_floats));
     if (side_streams) T_TRY(talloc(tr, &tr->d_ws2, tr->ws_floats));
     T_TRY(talloc(tr, &tr->d_split, tr->split_floats));
@@ -1194,63 +948,96 @@ int finish_build(umx_trainer* tr, double mac_total, bool side_streams) {
     return UMX_OK;
 }
 
-int build_trainer(umx_trainer* tr, const float* blob, size_t blob_floats) {
+// The v2 graph's host pass: shape, parameter layout, and the plan of every convolution and weight gradient.  Nothing is allocated.
+int plan_trainer(umx_trainer* tr, const float* blob, size_t blob_floats) {
     set_shape(tr);
-    const int L = tr->L, ks = tr->hp.ks, P = tr->P, K = tr->K, B = tr->B;
+    const int L = tr->L, ks = tr->hp.ks, P = tr->P, K = tr->K;
     const std::vector<int>& n = tr->n;
     const umx_train_options& o = tr->o;
 
     // ---- parameter vector layout (== unmicst_amd/model.py tensor_specs, nExtraConvs == 0)
     size_t pos = 0;
     auto seg = [&](const std::string& name, size_t cnt, float reg, int last) { tr->segs.push_back({name, pos, cnt, reg, last}); pos += cnt; return pos - cnt; };
-    std::vector<size_t> bn_d_off(L), bn_u_off(L);
-    size_t bn_b_off, bn_t_off;
+    tr->o_bn_d.resize(L); tr->o_bn_u.resize(L);
     tr->o_w1.resize(L); tr->o_ws.resize(L); tr->o_wt.resize(L); tr->o_w2.resize(L);
     char nm[64];
     for (int i = 0; i < L; ++i) {
         snprintf(nm, sizeof nm, "ld%d", i);
         tr->o_w1[i] = seg(std::string(nm) + ".w1", (size_t)ks * ks * n[i] * n[i + 1], 0.f, n[i + 1]);
         tr->o_ws[i] = seg(std::string(nm) + ".wshort", (size_t)ks * ks * n[i] * n[i + 1], o.reg_down, n[i + 1]);
-        bn_d_off[i] = seg(std::string(nm) + ".bn", 4 * (size_t)n[i + 1], 0.f, 0);
+        tr->o_bn_d[i] = seg(std::string(nm) + ".bn", 4 * (size_t)n[i + 1], 0.f, 0);
     }
     tr->o_lb = seg("lb.w", (size_t)ks * ks * n[L] * n[L + 1], o.reg_bottom, n[L + 1]);
-    bn_b_off = seg("lb.bn", 4 * (size_t)n[L + 1], 0.f, 0);
+    tr->o_bn_b = seg("lb.bn", 4 * (size_t)n[L + 1], 0.f, 0);
     for (int idx = L - 1; idx >= 0; --idx) {
         snprintf(nm, sizeof nm, "lu%d", idx);
         tr->o_wt[idx] = seg(std::string(nm) + ".wt", (size_t)ks * ks * n[idx + 1] * n[idx + 2], o.reg_up, n[idx + 2]);
         tr->o_w2[idx] = seg(std::string(nm) + ".w2", (size_t)ks * ks * (n[idx] + n[idx + 1]) * n[idx + 1], o.reg_up, n[idx + 1]);
-        bn_u_off[idx] = seg(std::string(nm) + ".bn", 4 * (size_t)n[idx + 1], 0.f, 0);
+        tr->o_bn_u[idx] = seg(std::string(nm) + ".bn", 4 * (size_t)n[idx + 1], 0.f, 0);
     }
     tr->o_lt = seg("lt.w", (size_t)n[1] * K, o.reg_top, K);
-    bn_t_off = seg("lt.bn", 4 * (size_t)K, 0.f, 0);
-    T_TRY(alloc_params(tr, blob, blob_floats, pos));
+    tr->o_bn_t = seg("lt.bn", 4 * (size_t)K, 0.f, 0);
+    T_TRY(take_blob(tr, blob, blob_floats, pos));
+
+    // ---- conv launches
+    tr->wg_planes = tr->hconv;
+    tr->c_fwd_d.resize(L); tr->c_dg_d.resize(L); tr->c_T.resize(L); tr->c_fwd_u.resize(L);
+    tr->c_dg_us.resize(L); tr->c_dg_skip.resize(L); tr->c_dg_T.resize(L);
+    tr->wg_d.resize(L); tr->wg_u0.resize(L); tr->wg_u1.resize(L); tr->wg_T.resize(L);
+    const TapSet fwd = same_taps(ks, false), flp = same_taps(ks, true);
+    double mac_total = 0.0;
+    int S = P;
+    for (int i = 0; i < L; ++i) {
+        snprintf(nm, sizeof nm, "ld%d", i);
+        GroupSpec g = one_group(n[i], tr->o_w1[i], tr->o_ws[i], n[i], n[i + 1], 0, 0, fwd);
+        T_TRY(plan_conv(tr, tr->c_fwd_d[i], nm, S, S, n[i + 1], ACT_NONE, 1, 1, nullptr, nullptr, 1, &g, false));
+        mac_total += tr->c_fwd_d[i].plan.mac;
+        if (i >= 1) {
+            GroupSpec gd = one_group(n[i + 1], tr->o_w1[i], tr->o_ws[i], n[i], n[i + 1], 1, 0, flp);
+            T_TRY(plan_conv(tr, tr->c_dg_d[i], nm, S, S, n[i], ACT_NONE, 1, 1, nullptr, nullptr, 1, &gd, true));
+            mac_total += tr->c_dg_d[i].plan.mac;
+        }
+        T_TRY(setup_wgrad(tr, tr->wg_d[i], nm, S, n[i], n[i], n[i + 1], fwd, {}));
+        mac_total += (double)S * S * ks * ks * n[i] * n[i + 1];
+        S /= 2;
+    }
+    T_TRY(setup_bottom(tr, S, mac_total));
+    for (int idx = L - 1; idx >= 0; --idx) T_TRY(setup_up_layer(tr, idx, S, ACT_LEAKY, mac_total));
+    finish_plan(tr, mac_total);
+    return UMX_OK;
+}
+
+// The v2 graph's device pass: parameters, activations, planes, every convolution's upload in build order, the shared buffers.
+int alloc_trainer(umx_trainer* tr) {
+    const int L = tr->L, P = tr->P, K = tr->K, B = tr->B;
+    const std::vector<int>& n = tr->n;
+    T_TRY(alloc_params(tr));
 
     // ---- activations: shapes and fp32 buffers; their planes follow below
-    T_TRY(select_route(tr, blob));
     tr->bn_d.resize(L); tr->bn_u.resize(L);
     tr->cv.resize(L); tr->dskip.assign(L, nullptr);
     size_t max_act = (size_t)B * P * P * std::max(n[0], K), max_dz = 0, max_gs = 0;
     auto grad_size = [&](size_t npix, int C) { max_act = std::max(max_act, npix * C); max_dz = std::max(max_dz, npix * round_up(C, 8)); };
     int S = P;
     for (int i = 0; i < L; ++i) {
-        T_TRY(bn_alloc(tr, tr->bn_d[i], n[i + 1], S, bn_d_off[i]));
+        T_TRY(bn_alloc(tr, tr->bn_d[i], n[i + 1], S, tr->o_bn_d[i]));
         grad_size((size_t)B * S * S, n[i + 1]);
         T_TRY(alloc_act(tr, tr->ds[i + 1], label_of("ds", i + 1), S / 2, n[i + 1], false));
         if (i + 1 <= L - 1) T_TRY(talloc(tr, &tr->dskip[i + 1], (size_t)B * (S / 2) * (S / 2) * n[i + 1]));
         S /= 2;
     }
-    T_TRY(bn_alloc(tr, tr->bn_b, n[L + 1], S, bn_b_off));
+    T_TRY(bn_alloc(tr, tr->bn_b, n[L + 1], S, tr->o_bn_b));
     T_TRY(alloc_act(tr, tr->act_b, "act_b", S, n[L + 1], false));
     grad_size((size_t)B * S * S, n[L + 1]);
     for (int idx = L - 1; idx >= 0; --idx) {
         max_gs = std::max(max_gs, (size_t)B * S * S * round_up(4 * n[idx + 1], 8));
         S *= 2;
         T_TRY(alloc_act(tr, tr->us[idx], label_of("us", idx), S, n[idx + 1], false));
-        T_TRY(bn_alloc(tr, tr->bn_u[idx], n[idx + 1], S, bn_u_off[idx]));
+        T_TRY(bn_alloc(tr, tr->bn_u[idx], n[idx + 1], S, tr->o_bn_u[idx]));
         T_TRY(alloc_act(tr, tr->cv[idx], label_of("cv", idx), S, n[idx + 1], false));
         grad_size((size_t)B * S * S, n[idx + 1]);
     }
-    T_TRY(bn_alloc(tr, tr->bn_t, K, P, bn_t_off));
+    T_TRY(bn_alloc(tr, tr->bn_t, K, P, tr->o_bn_t));
     T_TRY(talloc(tr, &tr->d_labels, (size_t)B * P * P * K));
     T_TRY(talloc(tr, &tr->d_weights, (size_t)B * P * P * K));
     T_TRY(talloc(tr, &tr->d_probs, (size_t)B * P * P * K));
@@ -1296,30 +1083,13 @@ int build_trainer(umx_trainer* tr, const float* blob, size_t blob_floats) {
     }
     T_TRY(alloc_slot_planes(tr, slots, max_dz, max_gs));
 
-    // ---- conv launches
-    tr->c_fwd_d.resize(L); tr->c_dg_d.resize(L); tr->c_T.resize(L); tr->c_fwd_u.resize(L);
-    tr->c_dg_us.resize(L); tr->c_dg_skip.resize(L); tr->c_dg_T.resize(L);
-    tr->wg_d.resize(L); tr->wg_u0.resize(L); tr->wg_u1.resize(L); tr->wg_T.resize(L);
-    const TapSet fwd = same_taps(ks, false), flp = same_taps(ks, true);
-    double mac_total = 0.0;
-    S = P;
-    for (int i = 0; i < L; ++i) {
-        snprintf(nm, sizeof nm, "ld%d", i);
-        GroupSpec g = one_group(n[i], tr->o_w1[i], tr->o_ws[i], n[i], n[i + 1], 0, 0, fwd);
-        T_TRY(setup_conv(tr, tr->c_fwd_d[i], nm, S, S, n[i + 1], ACT_NONE, 1, 1, nullptr, nullptr, 1, &g, false));
-        mac_total += tr->c_fwd_d[i].mac;
-        if (i >= 1) {
-            GroupSpec gd = one_group(n[i + 1], tr->o_w1[i], tr->o_ws[i], n[i], n[i + 1], 1, 0, flp);
-            T_TRY(setup_conv(tr, tr->c_dg_d[i], nm, S, S, n[i], ACT_NONE, 1, 1, nullptr, nullptr, 1, &gd, true));
-            mac_total += tr->c_dg_d[i].mac;
-        }
-        T_TRY(setup_wgrad(tr, tr->wg_d[i], nm, S, n[i], n[i], n[i + 1], fwd, {}));
-        mac_total += (double)S * S * ks * ks * n[i] * n[i + 1];
-        S /= 2;
-    }
-    T_TRY(setup_bottom(tr, S, mac_total));
-    for (int idx = L - 1; idx >= 0; --idx) T_TRY(setup_up_layer(tr, idx, S, ACT_LEAKY, mac_total));
-    return finish_build(tr, mac_total, true);
+    T_TRY(upload_convs(tr));
+    return finish_build(tr, true);
+}
+
+int build_trainer(umx_trainer* tr, const float* blob, size_t blob_floats) {
+    T_TRY(plan_trainer(tr, blob, blob_floats));
+    return alloc_trainer(tr);
 }
 
 // the step's weights -> the operands of every convolution: fp32 [tap][Cp][Np] (both routes), then conv_f16x3's weight images
@@ -1335,7 +1105,7 @@ int refresh_wscales(umx_trainer* tr) {
     bool changed = false;
     for (size_t k = 0; k < tr->hconvs.size(); ++k) {
         TConv& tc = *tr->hconvs[k];
-        const int sh = wscale_shift(operand_wmax(tc, tr->h_params.data()));
+        const int sh = wscale_shift(operand_wmax(tc.plan.wsrc, tr->h_params.data()));
         if (sh == tc.wsh) continue;
         tc.wsh = sh;
         const float inv = std::ldexp(1.f, -sh);
@@ -1375,16 +1145,17 @@ int alloc_ident(umx_trainer* tr, float** out, int C) {
     return tupload(tr, out, h.data(), h.size());
 }
 
-int build_legacy(umx_trainer* tr, const float* blob, size_t blob_floats) {
+// The legacy graph's host pass: shape, parameter layout, and the plan of every convolution and weight gradient.  Nothing is allocated.
+int plan_legacy(umx_trainer* tr, const float* blob, size_t blob_floats) {
     set_shape(tr);
-    const int L = tr->L, ks = tr->hp.ks, P = tr->P, K = tr->K, B = tr->B, E = tr->hp.nExtraConvs;
+    const int L = tr->L, ks = tr->hp.ks, P = tr->P, K = tr->K, E = tr->hp.nExtraConvs;
     tr->E = E;
     const std::vector<int>& n = tr->n;
 
     // ---- parameter vector layout (== unmicst_amd/model.py tensor_specs, GRAPH_LEGACY)
     size_t pos = 0;
     auto seg = [&](const std::string& name, size_t cnt, int last) { tr->segs.push_back({name, pos, cnt, 0.f, last}); pos += cnt; return pos - cnt; };
-    std::vector<size_t> bn_d_off(L);
+    tr->o_bn_d.resize(L);
     tr->o_w1.resize(L); tr->o_ws.resize(L); tr->o_wt.resize(L); tr->o_w2.resize(L);
     tr->ldb.resize(L); tr->lub.resize(L);
     char nm[64];
@@ -1393,7 +1164,7 @@ int build_legacy(umx_trainer* tr, const float* blob, size_t blob_floats) {
         tr->o_w1[i] = seg(p + ".w1", (size_t)ks * ks * n[i] * n[i + 1], n[i + 1]);
         for (int e = 0; e < E; ++e) tr->ldb[i].o_wx.push_back(seg(p + ".wextra" + std::to_string(e), (size_t)ks * ks * n[i + 1] * n[i + 1], n[i + 1]));
         tr->o_ws[i] = seg(p + ".wshort", (size_t)n[i] * n[i + 1], n[i + 1]);
-        bn_d_off[i] = seg(p + ".bn", 4 * (size_t)n[i + 1], 0);
+        tr->o_bn_d[i] = seg(p + ".bn", 4 * (size_t)n[i + 1], 0);
     }
     tr->o_lb = seg("lb.w", (size_t)ks * ks * n[L] * n[L + 1], n[L + 1]);
     for (int idx = L - 1; idx >= 0; --idx) {
@@ -1403,7 +1174,67 @@ int build_legacy(umx_trainer* tr, const float* blob, size_t blob_floats) {
         for (int e = 0; e < E; ++e) tr->lub[idx].o_wx.push_back(seg(p + ".wextra" + std::to_string(e), (size_t)ks * ks * n[idx + 1] * n[idx + 1], n[idx + 1]));
     }
     tr->o_lt = seg("lt.w", (size_t)n[1] * K, K);
-    T_TRY(alloc_params(tr, blob, blob_floats, pos));
+    T_TRY(take_blob(tr, blob, blob_floats, pos));
+
+    // ---- conv launches
+    tr->wg_planes = tr->hconv;
+    tr->c_dg_d.resize(L); tr->c_T.resize(L); tr->c_fwd_u.resize(L);
+    tr->c_dg_us.resize(L); tr->c_dg_skip.resize(L); tr->c_dg_T.resize(L);
+    tr->wg_d.resize(L); tr->wg_u0.resize(L); tr->wg_u1.resize(L); tr->wg_T.resize(L);
+    for (std::vector<LBlock>* v : {&tr->ldb, &tr->lub})
+        for (LBlock& b : *v) { b.fwd.resize(E + 1); b.dg.resize(E + 1); b.wg.resize(E + 1); }
+    const TapSet fwd = same_taps(ks, false), flp = same_taps(ks, true);
+    TapSet ctr;   // the 1x1 shortcut: one tap at the centre
+    ctr.off.push_back({0, 0});
+    ctr.m.push_back(0);
+    double mac_total = 0.0;
+    // extra conv e >= 1 of a chain at size S with C channels: forward (ngroups 2: + the shortcut group g1), input and weight gradient
+    auto extra = [&](LBlock& b, int e, int S, int C, int ngroups, const GroupSpec* g1) -> int {
+        GroupSpec g[2] = {one_group(C, b.o_wx[e - 1], SIZE_MAX, C, C, 0, 0, fwd), g1 ? *g1 : GroupSpec()};
+        T_TRY(plan_conv(tr, b.fwd[e], nm, S, S, C, ACT_NONE, 1, 1, nullptr, nullptr, ngroups, g, false));
+        GroupSpec gd = one_group(C, b.o_wx[e - 1], SIZE_MAX, C, C, 1, 0, flp);
+        T_TRY(plan_conv(tr, b.dg[e], nm, S, S, C, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gd, true));
+        T_TRY(setup_wgrad(tr, b.wg[e], nm, S, C, C, C, fwd, {}));
+        mac_total += b.fwd[e].plan.mac + b.dg[e].plan.mac + (double)S * S * ks * ks * C * C;
+        return UMX_OK;
+    };
+    int S = P;
+    for (int i = 0; i < L; ++i) {
+        snprintf(nm, sizeof nm, "ld%d", i);
+        LBlock& b = tr->ldb[i];
+        const int Ci = n[i], C = n[i + 1];
+        const GroupSpec gsh = one_group(Ci, tr->o_ws[i], SIZE_MAX, Ci, C, 0, 0, ctr);
+        GroupSpec g[2] = {one_group(Ci, tr->o_w1[i], SIZE_MAX, Ci, C, 0, 0, fwd), gsh};
+        T_TRY(plan_conv(tr, b.fwd[0], nm, S, S, C, ACT_NONE, 1, 1, nullptr, nullptr, E == 0 ? 2 : 1, g, false));
+        mac_total += b.fwd[0].plan.mac;
+        for (int e = 1; e <= E; ++e) T_TRY(extra(b, e, S, C, e == E ? 2 : 1, &gsh));
+        if (i >= 1) {
+            GroupSpec gd = one_group(C, tr->o_w1[i], SIZE_MAX, Ci, C, 1, 0, flp);
+            GroupSpec gs = one_group(C, tr->o_ws[i], SIZE_MAX, Ci, C, 1, 0, ctr);
+            T_TRY(plan_conv(tr, tr->c_dg_d[i], nm, S, S, Ci, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gd, true));
+            T_TRY(plan_conv(tr, b.dg_sh, nm, S, S, Ci, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gs, true));
+            mac_total += tr->c_dg_d[i].plan.mac + b.dg_sh.plan.mac;
+        }
+        T_TRY(setup_wgrad(tr, tr->wg_d[i], nm, S, Ci, Ci, C, fwd, {}));
+        T_TRY(setup_wgrad(tr, b.wg_sh, nm, S, Ci, Ci, C, ctr, {}));
+        mac_total += (double)S * S * (ks * ks + 1) * Ci * C;
+        S /= 2;
+    }
+    T_TRY(setup_bottom(tr, S, mac_total));
+    for (int idx = L - 1; idx >= 0; --idx) {
+        T_TRY(setup_up_layer(tr, idx, S, ACT_RELU, mac_total));
+        snprintf(nm, sizeof nm, "lu%d", idx);
+        for (int e = 1; e <= E; ++e) T_TRY(extra(tr->lub[idx], e, S, n[idx + 1], 1, nullptr));
+    }
+    finish_plan(tr, mac_total);
+    return UMX_OK;
+}
+
+// The legacy graph's device pass: parameters, activations with their planes, every convolution's upload in build order, the shared buffers.
+int alloc_legacy(umx_trainer* tr) {
+    const int L = tr->L, P = tr->P, K = tr->K, B = tr->B, E = tr->E;
+    const std::vector<int>& n = tr->n;
+    T_TRY(alloc_params(tr));
 
     // ---- max words (zeroed every step), then the range flag; handed out below, once the tensors exist
     tr->n_maxw = 16 + 4 * (L + 1) * (2 * E + 6);
@@ -1412,7 +1243,6 @@ int build_legacy(umx_trainer* tr, const float* blob, size_t blob_floats) {
     // ---- activations
     tr->bn_d.resize(L);
     tr->dskip.assign(L, nullptr);
-    T_TRY(select_route(tr, blob));
     // a chain's tensors: y[0..E], a[0..na)
     auto chain = [&](LBlock& b, const std::string& name, int S, int C, int na) -> int {
         b.y.assign(E + 1, nullptr); b.a.resize(na);
@@ -1426,7 +1256,7 @@ int build_legacy(umx_trainer* tr, const float* blob, size_t blob_floats) {
     T_TRY(alloc_act(tr, tr->ds[0], label_of("ds", 0), P, n[0]));
     for (int i = 0; i < L; ++i) {
         T_TRY(chain(tr->ldb[i], label_of("ldb", i), S, n[i + 1], E));
-        T_TRY(bn_alloc(tr, tr->bn_d[i], n[i + 1], S, bn_d_off[i]));   // (its z: relu(z), what BN normalises)
+        T_TRY(bn_alloc(tr, tr->bn_d[i], n[i + 1], S, tr->o_bn_d[i]));   // (its z: relu(z), what BN normalises)
         grad_size((size_t)B * S * S, n[i + 1]);
         T_TRY(alloc_act(tr, tr->ds[i + 1], label_of("ds", i + 1), S / 2, n[i + 1]));
         if (i + 1 <= L - 1) T_TRY(talloc(tr, &tr->dskip[i + 1], (size_t)B * (S / 2) * (S / 2) * n[i + 1]));
@@ -1480,56 +1310,13 @@ int build_legacy(umx_trainer* tr, const float* blob, size_t blob_floats) {
         }
     if (k > tr->n_maxw) return tfail(tr, UMX_ERR_INVALID, "internal: %d max words for %d", k, tr->n_maxw);
 
-    // ---- conv launches
-    tr->c_dg_d.resize(L); tr->c_T.resize(L); tr->c_fwd_u.resize(L);
-    tr->c_dg_us.resize(L); tr->c_dg_skip.resize(L); tr->c_dg_T.resize(L);
-    tr->wg_d.resize(L); tr->wg_u0.resize(L); tr->wg_u1.resize(L); tr->wg_T.resize(L);
-    for (std::vector<LBlock>* v : {&tr->ldb, &tr->lub})
-        for (LBlock& b : *v) { b.fwd.resize(E + 1); b.dg.resize(E + 1); b.wg.resize(E + 1); }
-    const TapSet fwd = same_taps(ks, false), flp = same_taps(ks, true);
-    TapSet ctr;   // the 1x1 shortcut: one tap at the centre
-    ctr.off.push_back({0, 0});
-    ctr.m.push_back(0);
-    double mac_total = 0.0;
-    // extra conv e >= 1 of a chain at size S with C channels: forward (ngroups 2: + the shortcut group g1), input and weight gradient
-    auto extra = [&](LBlock& b, int e, int S, int C, int ngroups, const GroupSpec* g1) -> int {
-        GroupSpec g[2] = {one_group(C, b.o_wx[e - 1], SIZE_MAX, C, C, 0, 0, fwd), g1 ? *g1 : GroupSpec()};
-        T_TRY(setup_conv(tr, b.fwd[e], nm, S, S, C, ACT_NONE, 1, 1, nullptr, nullptr, ngroups, g, false));
-        GroupSpec gd = one_group(C, b.o_wx[e - 1], SIZE_MAX, C, C, 1, 0, flp);
-        T_TRY(setup_conv(tr, b.dg[e], nm, S, S, C, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gd, true));
-        T_TRY(setup_wgrad(tr, b.wg[e], nm, S, C, C, C, fwd, {}));
-        mac_total += b.fwd[e].mac + b.dg[e].mac + (double)S * S * ks * ks * C * C;
-        return UMX_OK;
-    };
-    S = P;
-    for (int i = 0; i < L; ++i) {
-        snprintf(nm, sizeof nm, "ld%d", i);
-        LBlock& b = tr->ldb[i];
-        const int Ci = n[i], C = n[i + 1];
-        const GroupSpec gsh = one_group(Ci, tr->o_ws[i], SIZE_MAX, Ci, C, 0, 0, ctr);
-        GroupSpec g[2] = {one_group(Ci, tr->o_w1[i], SIZE_MAX, Ci, C, 0, 0, fwd), gsh};
-        T_TRY(setup_conv(tr, b.fwd[0], nm, S, S, C, ACT_NONE, 1, 1, nullptr, nullptr, E == 0 ? 2 : 1, g, false));
-        mac_total += b.fwd[0].mac;
-        for (int e = 1; e <= E; ++e) T_TRY(extra(b, e, S, C, e == E ? 2 : 1, &gsh));
-        if (i >= 1) {
-            GroupSpec gd = one_group(C, tr->o_w1[i], SIZE_MAX, Ci, C, 1, 0, flp);
-            GroupSpec gs = one_group(C, tr->o_ws[i], SIZE_MAX, Ci, C, 1, 0, ctr);
-            T_TRY(setup_conv(tr, tr->c_dg_d[i], nm, S, S, Ci, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gd, true));
-            T_TRY(setup_conv(tr, b.dg_sh, nm, S, S, Ci, ACT_NONE, 1, 1, nullptr, nullptr, 1, &gs, true));
-            mac_total += tr->c_dg_d[i].mac + b.dg_sh.mac;
-        }
-        T_TRY(setup_wgrad(tr, tr->wg_d[i], nm, S, Ci, Ci, C, fwd, {}));
-        T_TRY(setup_wgrad(tr, b.wg_sh, nm, S, Ci, Ci, C, ctr, {}));
-        mac_total += (double)S * S * (ks * ks + 1) * Ci * C;
-        S /= 2;
-    }
-    T_TRY(setup_bottom(tr, S, mac_total));
-    for (int idx = L - 1; idx >= 0; --idx) {
-        T_TRY(setup_up_layer(tr, idx, S, ACT_RELU, mac_total));
-        snprintf(nm, sizeof nm, "lu%d", idx);
-        for (int e = 1; e <= E; ++e) T_TRY(extra(tr->lub[idx], e, S, n[idx + 1], 1, nullptr));
-    }
-    return finish_build(tr, mac_total, false);
+    T_TRY(upload_convs(tr));
+    return finish_build(tr, false);
+}
+
+int build_legacy(umx_trainer* tr, const float* blob, size_t blob_floats) {
+    T_TRY(plan_legacy(tr, blob, blob_floats));
+    return alloc_legacy(tr);
 }
 
 // forward of the legacy graph up to the logits.  training: batch statistics (moving averages updated when `update`) and the max
@@ -1555,23 +1342,23 @@ int forward_legacy(umx_trainer* tr, const float* data, bool training, bool updat
         BnSite& s = tr->bn_d[i];
         for (int e = 0; e <= E; ++e) {
             const bool last = e == E;   // (+ the shortcut on the block input)
-            T_TRY(run_tconv(tr, b.fwd[e], e == 0 ? tr->ds[i] : b.a[e - 1], b.y[e], last ? &tr->ds[i] : nullptr));
+            T_TRY(run_tconv(tr, b.fwd[e], e == 0 ? tr->ds[i] : b.a[e - 1], b.y[e], last ? &tr->ds[i] : nullptr, st));
             if (!last) T_TRY(act(b.y[e], b.ident, 0, ACT_RELU, b.a[e]));
         }
         T_TRY(act(b.y[E], b.ident, 0, ACT_RELU, Act{s.z, H16(), nullptr, nullptr, s.H, s.C}));      // relu(z): what BN normalises
         T_TRY(bn_forward_stats(tr, s, update, training));
         T_TRY(act(s.z, s.stat, 1, ACT_NONE, tr->ds[i + 1]));   // BN, then the pool
     }
-    T_TRY(run_tconv(tr, tr->c_fwd_b, tr->ds[L], tr->lb_z));
+    T_TRY(run_tconv(tr, tr->c_fwd_b, tr->ds[L], tr->lb_z, nullptr, st));
     T_TRY(act(tr->lb_z, tr->lb_ident, 0, ACT_RELU, tr->act_b));
     const Act* cur = &tr->act_b;
     for (int idx = L - 1; idx >= 0; --idx) {
         LBlock& b = tr->lub[idx];
-        T_TRY(run_tconv(tr, tr->c_T[idx], *cur, tr->us[idx].x));   // (ReLU fused)
+        T_TRY(run_tconv(tr, tr->c_T[idx], *cur, tr->us[idx].x, nullptr, st));   // (ReLU fused)
         T_TRY(track_act(tr, tr->us[idx], training));
         for (int e = 0; e <= E; ++e) {
-            if (e == 0) T_TRY(run_tconv(tr, tr->c_fwd_u[idx], tr->ds[idx], b.y[0], &tr->us[idx]));
-            else T_TRY(run_tconv(tr, b.fwd[e], b.a[e - 1], b.y[e]));
+            if (e == 0) T_TRY(run_tconv(tr, tr->c_fwd_u[idx], tr->ds[idx], b.y[0], &tr->us[idx], st));
+            else T_TRY(run_tconv(tr, b.fwd[e], b.a[e - 1], b.y[e], nullptr, st));
             T_TRY(act(b.y[e], b.ident, 0, ACT_RELU, b.a[e]));
         }
         cur = &b.a[E];
@@ -1612,7 +1399,7 @@ int enqueue_legacy(umx_trainer* tr, const float* data, const float* labels, cons
     auto extras_bwd = [&](LBlock& b, Act* g) -> int {
         for (int e = E; e >= 1; --e) {
             T_TRY(wgrad(b.wg[e], b.a[e - 1], *g, g->C, 0, b.o_wx[e - 1]));
-            T_TRY(run_tconv(tr, b.dg[e], *g, tr->DA));
+            T_TRY(run_tconv(tr, b.dg[e], *g, tr->DA, nullptr, st));
             T_TRY(relu_bwd(tr->DA, b.y[e - 1], ((E - e) & 1) ^ 1, g->S, g->C, b.gmax[e - 1], g));
         }
         return UMX_OK;
@@ -1625,19 +1412,19 @@ int enqueue_legacy(umx_trainer* tr, const float* data, const float* labels, cons
         T_TRY(extras_bwd(b, &g));
         T_TRY(wgrad(tr->wg_u0[idx], tr->ds[idx], g, Cskip + Cup, 0, tr->o_w2[idx]));
         T_TRY(wgrad(tr->wg_u1[idx], tr->us[idx], g, Cskip + Cup, Cskip, tr->o_w2[idx]));
-        T_TRY(run_tconv(tr, tr->c_dg_us[idx], g, tr->DB));
-        if (idx >= 1) T_TRY(run_tconv(tr, tr->c_dg_skip[idx], g, tr->dskip[idx]));
+        T_TRY(run_tconv(tr, tr->c_dg_us[idx], g, tr->DB, nullptr, st));
+        if (idx >= 1) T_TRY(run_tconv(tr, tr->c_dg_skip[idx], g, tr->dskip[idx], nullptr, st));
         const Act gs = tr->gs[0].view(S / 2, 4 * Cup, tr->smax[idx]);
         T_HIP(tr, launch_leaky_bwd_s2d_max(tr->DB, tr->us[idx].x, B, S / 2, Cup, 0.f, gs.x, gs.max, st));   // ReLU: slope 0
         T_TRY(to_h16(tr, gs, st));
         // (the transposed convolution's filter: X is gS, G the layer's input)
         T_TRY(wgrad(tr->wg_T[idx], gs, idx == L - 1 ? tr->act_b : tr->lub[idx + 1].a[E], Cup, 0, tr->o_wt[idx]));
-        T_TRY(run_tconv(tr, tr->c_dg_T[idx], gs, tr->DA));
+        T_TRY(run_tconv(tr, tr->c_dg_T[idx], gs, tr->DA, nullptr, st));
     }
     {   // bottom
         T_TRY(relu_bwd(tr->DA, tr->lb_z, 0, tr->act_b.S, n[L + 1], tr->lb_gmax, &g));
         T_TRY(wgrad(tr->wg_b, tr->ds[L], g, n[L], 0, tr->o_lb));
-        T_TRY(run_tconv(tr, tr->c_dg_b, g, tr->DB));
+        T_TRY(run_tconv(tr, tr->c_dg_b, g, tr->DB, nullptr, st));
     }
     for (int i = L - 1; i >= 0; --i) {     // down layers; DB (+ dskip[i+1]): d loss / d ds[i+1]
         LBlock& b = tr->ldb[i];
@@ -1655,15 +1442,42 @@ int enqueue_legacy(umx_trainer* tr, const float* data, const float* labels, cons
         }
         // the shortcut: weight gradient and (i >= 1) input gradient, before the chain reuses slot 0
         T_TRY(wgrad(b.wg_sh, tr->ds[i], g, Ci, 0, tr->o_ws[i]));
-        if (i >= 1) T_TRY(run_tconv(tr, b.dg_sh, g, tr->DSUM + tr->max_act));
+        if (i >= 1) T_TRY(run_tconv(tr, b.dg_sh, g, tr->DSUM + tr->max_act, nullptr, st));
         T_TRY(extras_bwd(b, &g));
         T_TRY(wgrad(tr->wg_d[i], tr->ds[i], g, Ci, 0, tr->o_w1[i]));
         if (i >= 1) {   // d ds[i] = first-conv input gradient + shortcut input gradient
-            T_TRY(run_tconv(tr, tr->c_dg_d[i], g, tr->DSUM));
+            T_TRY(run_tconv(tr, tr->c_dg_d[i], g, tr->DSUM, nullptr, st));
             T_HIP(tr, launch_split_reduce(tr->DSUM, 2, tr->max_act, npix * Ci, ACT_NONE, tr->DB, st));
         }
     }
     return step_end(tr, update);
+}
+
+// what umx_trainer_create asks of the hyper-parameters and options, before it touches a device
+int check_create(const umx_hparams* hp, const umx_train_options* opts) {
+    const bool legacy = hp->graph == UMX_GRAPH_LEGACY;
+    if (legacy) {
+        if (hp->nExtraConvs < 0 || hp->nExtraConvs > 2)
+            return tfail(nullptr, UMX_ERR_INVALID, "the training step covers the legacy graph with nExtraConvs 0..2");
+        if (opts->reg_kind != UMX_REG_NONE || opts->drop_down_step != 0.f || opts->drop_bottom != 0.f || opts->drop_up0 != 0.f ||
+            opts->drop_up_step != 0.f)
+            return tfail(nullptr, UMX_ERR_INVALID, "the legacy graph has no dropout and no regulariser (umx_train_options_legacy)");
+    } else if (hp->graph != UMX_GRAPH_V2 || hp->nExtraConvs != 0) {
+        return tfail(nullptr, UMX_ERR_INVALID, "the training step covers the v2 graph with nExtraConvs == 0");
+    }
+    // one class: the softmax is identically 1, so the cross-entropy and every gradient of it are 0 -- nothing could be learnt
+    if (hp->nClasses < 2 || hp->nClasses > 8) return tfail(nullptr, UMX_ERR_INVALID, "nClasses must be 2..8 (a one-class softmax has no gradient)");
+    if (hp->nLayers < 1 || hp->nLayers > 8 || (hp->ks != 3 && hp->ks != 5) || hp->featMapsFact < 1 ||
+        hp->nChannels < 1 || hp->nOut0 < 1)
+        return tfail(nullptr, UMX_ERR_INVALID, "unsupported hyper-parameters");
+    if ((hp->imSize & (hp->imSize - 1)) || (hp->imSize >> hp->nLayers) < 1)
+        return tfail(nullptr, UMX_ERR_INVALID, "imSize must be a power of two, at least 2^nLayers");
+    for (int i = 0; i < 8; ++i)
+        if (opts->reserved[i]) return tfail(nullptr, UMX_ERR_INVALID, "umx_train_options.reserved must be zero");
+    auto bad_rate = [](float r) { return !(r < 1.0f); };
+    if (bad_rate(opts->drop_bottom) || bad_rate(opts->drop_up0) || bad_rate(opts->drop_down_step * hp->nLayers))
+        return tfail(nullptr, UMX_ERR_INVALID, "dropout rates must be below 1");
+    return UMX_OK;
 }
 
 }  // namespace
@@ -1724,101 +1538,6 @@ int trainer_eval_end(umx_trainer* tr) {
     return UMX_OK;
 }
 
-// ---- the device memory of a trainer / training set (umx_internal.h) ----
-int arena_init(DevArena* a, std::string* why) {
-    a->fill = -1;
-    const char* e = getenv("UMX_DEBUG_GUARD");
-    if (!e || !*e) return UMX_OK;
-    char* end = nullptr;
-    const long v = strtol(e, &end, 0);
-    if (*end || v < 0 || v > 255) {
-        *why = std::string("UMX_DEBUG_GUARD=") + e + ": the fill must be one byte (0..255, e.g. 0xff)";
-        return UMX_ERR_INVALID;
-    }
-    a->fill = (int)v;
-    return UMX_OK;
-}
-
-hipError_t arena_alloc(DevArena* a, void** out, size_t bytes, bool zero, const char* label, bool scoped) {
-    bytes = std::max<size_t>(16, bytes);
-    void* d = nullptr;
-    if (a->fill < 0) {
-        hipError_t e = hipMalloc(&d, bytes);
-        if (e != hipSuccess) return e;
-        a->allocs.push_back(d);
-        if (zero && (e = hipMemset(d, 0, bytes)) != hipSuccess) return e;
-        *out = d;
-        return hipSuccess;
-    }
-    // a zone at least as large as the buffer: an index off by a whole image / plane / row lands in it, not in unmapped memory
-    const size_t zone = std::max<size_t>(64 << 10, (bytes + 4095) / 4096 * 4096);
-    hipError_t e = hipMalloc(&d, zone + bytes + zone);
-    if (e != hipSuccess) return e;
-    a->allocs.push_back(d);
-    char* p = static_cast<char*>(d);
-    if ((e = hipMemset(p, a->fill, zone + bytes + zone)) != hipSuccess) return e;
-    if (zero && (e = hipMemset(p + zone, 0, bytes)) != hipSuccess) return e;
-    if ((e = hipDeviceSynchronize()) != hipSuccess) return e;   // (the trainer's streams do not wait for the null stream)
-    while (*label == '&') ++label;
-    a->blocks.push_back({d, zone, bytes, zone, std::string(label) + " (#" + std::to_string(a->serial++) + ")", scoped});
-    *out = p + zone;
-    return hipSuccess;
-}
-
-hipError_t arena_release(DevArena* a, void* p) {
-    void* base = p;
-    for (size_t i = 0; i < a->blocks.size(); ++i)
-        if (static_cast<char*>(a->blocks[i].base) + a->blocks[i].front == p) {
-            base = a->blocks[i].base;
-            a->blocks.erase(a->blocks.begin() + i);
-            break;
-        }
-    const auto it = std::find(a->allocs.begin(), a->allocs.end(), base);
-    if (it == a->allocs.end()) return hipErrorInvalidValue;   // not this arena's
-    a->allocs.erase(it);
-    return hipFree(base);
-}
-
-hipError_t arena_refill(const DevArena& a, hipStream_t stream) {
-    if (a.fill < 0) return hipSuccess;
-    for (const DevBlock& b : a.blocks) {
-        if (!b.scoped) continue;
-        const hipError_t e = hipMemsetAsync(static_cast<char*>(b.base) + b.front, a.fill, b.bytes, stream);
-        if (e != hipSuccess) return e;
-    }
-    return hipStreamSynchronize(stream);
-}
-
-int arena_check(const DevArena& a, std::string* msg) {
-    if (a.fill < 0) return UMX_OK;
-    std::vector<uint8_t> h;
-    char buf[512];
-    for (const DevBlock& b : a.blocks) {
-        for (int side = 0; side < 2; ++side) {
-            const size_t n = side ? b.back : b.front;
-            const char* src = static_cast<const char*>(b.base) + (side ? b.front + b.bytes : 0);
-            h.resize(n);
-            const hipError_t e = hipMemcpy(h.data(), src, n, hipMemcpyDeviceToHost);
-            if (e != hipSuccess) {
-                *msg = std::string("guard check: hipMemcpy failed: ") + hipGetErrorString(e);
-                return UMX_ERR_HIP;
-            }
-            const int rc = umx_guard_scan(h.data(), n, side, b.bytes, a.fill, b.label.c_str(), buf, sizeof buf);
-            if (rc != UMX_OK) {
-                *msg = buf;
-                return rc;
-            }
-        }
-    }
-    return UMX_OK;
-}
-
-void arena_free(DevArena* a) {
-    for (void* p : a->allocs) (void)hipFree(p);
-    a->allocs.clear();
-    a->blocks.clear();
-}
-
 int trainer_guard_check(umx_trainer* tr) {
     if (tr->mem.fill < 0) return UMX_OK;
     T_HIP(tr, hipSetDevice(tr->device));
@@ -1832,25 +1551,6 @@ int trainer_guard_check(umx_trainer* tr) {
 }  // namespace umx
 
 extern "C" {
-
-int umx_guard_scan(const uint8_t* zone, size_t zone_bytes, int side, size_t buf_bytes, int fill, const char* label, char* msg,
-                   size_t cap) {
-    if (!zone || !label || (side != 0 && side != 1)) return UMX_ERR_INVALID;
-    size_t first = SIZE_MAX, last = 0;
-    for (size_t j = 0; j < zone_bytes; ++j)
-        if (zone[j] != (uint8_t)fill) {
-            if (first == SIZE_MAX) first = j;
-            last = j;
-        }
-    if (first == SIZE_MAX) return UMX_OK;
-    // offsets from the first byte of the buffer: the front zone ends at -1, the back zone starts at buf_bytes
-    const long long o1 = side ? (long long)(buf_bytes + first) : (long long)first - (long long)zone_bytes;
-    const long long o2 = side ? (long long)(buf_bytes + last) : (long long)last - (long long)zone_bytes;
-    if (msg && cap)
-        snprintf(msg, cap, "guard: %s (%zu bytes): the %s red zone was written, bytes %lld .. %lld of the buffer (fill 0x%02x)", label,
-                 buf_bytes, side ? "back" : "front", o1, o2, fill & 0xff);
-    return UMX_ERR_GUARD;
-}
 
 void umx_train_options_solo(umx_train_options* o) {
     fill_common(o);
@@ -1886,28 +1586,8 @@ int umx_trainer_create(const umx_hparams* hp, const float* weight_blob, size_t b
                        umx_trainer** out) {
     if (!hp || !weight_blob || !opts || !out) return tfail(nullptr, UMX_ERR_INVALID, "null argument");
     *out = nullptr;
+    T_TRY(check_create(hp, opts));
     const bool legacy = hp->graph == UMX_GRAPH_LEGACY;
-    if (legacy) {
-        if (hp->nExtraConvs < 0 || hp->nExtraConvs > 2)
-            return tfail(nullptr, UMX_ERR_INVALID, "the training step covers the legacy graph with nExtraConvs 0..2");
-        if (opts->reg_kind != UMX_REG_NONE || opts->drop_down_step != 0.f || opts->drop_bottom != 0.f || opts->drop_up0 != 0.f ||
-            opts->drop_up_step != 0.f)
-            return tfail(nullptr, UMX_ERR_INVALID, "the legacy graph has no dropout and no regulariser (umx_train_options_legacy)");
-    } else if (hp->graph != UMX_GRAPH_V2 || hp->nExtraConvs != 0) {
-        return tfail(nullptr, UMX_ERR_INVALID, "the training step covers the v2 graph with nExtraConvs == 0");
-    }
-    // one class: the softmax is identically 1, so the cross-entropy and every gradient of it are 0 -- nothing could be learnt
-    if (hp->nClasses < 2 || hp->nClasses > 8) return tfail(nullptr, UMX_ERR_INVALID, "nClasses must be 2..8 (a one-class softmax has no gradient)");
-    if (hp->nLayers < 1 || hp->nLayers > 8 || (hp->ks != 3 && hp->ks != 5) || hp->featMapsFact < 1 ||
-        hp->nChannels < 1 || hp->nOut0 < 1)
-        return tfail(nullptr, UMX_ERR_INVALID, "unsupported hyper-parameters");
-    if ((hp->imSize & (hp->imSize - 1)) || (hp->imSize >> hp->nLayers) < 1)
-        return tfail(nullptr, UMX_ERR_INVALID, "imSize must be a power of two, at least 2^nLayers");
-    for (int i = 0; i < 8; ++i)
-        if (opts->reserved[i]) return tfail(nullptr, UMX_ERR_INVALID, "umx_train_options.reserved must be zero");
-    auto bad_rate = [](float r) { return !(r < 1.0f); };
-    if (bad_rate(opts->drop_bottom) || bad_rate(opts->drop_up0) || bad_rate(opts->drop_down_step * hp->nLayers))
-        return tfail(nullptr, UMX_ERR_INVALID, "dropout rates must be below 1");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return tfail(nullptr, UMX_ERR_NO_DEVICE, "no HIP device");
     if (opts->device_ordinal < 0 || opts->device_ordinal >= ndev)
@@ -1924,6 +1604,7 @@ int umx_trainer_create(const umx_hparams* hp, const float* weight_blob, size_t b
     if (rc == UMX_OK && hipSetDevice(tr->device) != hipSuccess) rc = tfail(tr, UMX_ERR_HIP, "hipSetDevice failed");
     if (rc == UMX_OK && hipStreamCreateWithFlags(&tr->stream, hipStreamNonBlocking) != hipSuccess)
         rc = tfail(tr, UMX_ERR_HIP, "hipStreamCreate failed");
+    select_route(tr);
     if (rc == UMX_OK) rc = legacy ? build_legacy(tr, weight_blob, blob_floats) : build_trainer(tr, weight_blob, blob_floats);
     if (rc == UMX_OK)
         for (int i = 0; i < 4; ++i)
@@ -1952,6 +1633,53 @@ int umx_trainer_create(const umx_hparams* hp, const float* weight_blob, size_t b
     if (tr->mem.fill >= 0)
         fprintf(stderr, "[umx train] UMX_DEBUG_GUARD=0x%02x: %zu trainer buffers between red zones\n", tr->mem.fill, tr->mem.blocks.size());
     *out = tr;
+    return UMX_OK;
+}
+
+// The host pass of umx_trainer_create alone (no device): one line per forward / input-gradient convolution, in build order -- its
+// UMX_DEBUG_PLAN text, then its groups (as the master tensors see them), the fused activation, `direct`, the weight shift, the counts of pack descriptors and weight references, the K-split
+// scratch and tconv_digest of everything upload_conv would send.  conv_f32 / no_ksplit: the routes UMX_TRAIN_CONV_F32 /
+// UMX_TRAIN_NO_KSPLIT select.  *needed: bytes of the text with its terminator; UMX_ERR_INVALID where cap is smaller.
+int umx_test_train_plan(const umx_hparams* hp, int B, int conv_f32, int no_ksplit, const float* blob, size_t blob_floats, char* text,
+                        size_t cap, size_t* needed) {
+    if (!hp || !blob || !needed || (!text && cap)) return umx::fail(nullptr, UMX_ERR_INVALID, "umx_test_train_plan: null argument");
+    *needed = 0;
+    umx_train_options o;
+    if (hp->graph == UMX_GRAPH_LEGACY) umx_train_options_legacy(&o); else umx_train_options_solo(&o);
+    if (const int rc = check_create(hp, &o)) return umx::fail(nullptr, rc, "%s", g_terr.c_str());
+    umx_trainer tr;
+    tr.hp = *hp;
+    tr.o = o;
+    tr.B = B > 0 ? B : 8;
+    tr.legacy = hp->graph == UMX_GRAPH_LEGACY;
+    tr.hconv = !conv_f32;
+    tr.no_ksplit = no_ksplit != 0;
+    const int rc = tr.legacy ? plan_legacy(&tr, blob, blob_floats) : plan_trainer(&tr, blob, blob_floats);
+    if (rc != UMX_OK) return umx::fail(nullptr, rc, "%s", tr.err.c_str());
+    std::string out;
+    for (const TConv* tc : planned_convs(&tr)) {
+        const TConvPlan& p = tc->plan;
+        std::string groups;
+        size_t nrefs = 0;
+        for (int g = 0; g < tc->spec.ngroups; ++g) {
+            const GroupSpec& G = tc->spec.g[g];
+            char gb[96];   // channels x taps @ channel offset in the master [taps][d2][d3], T: transposed, s: a second master summed in
+            std::string taps;   // (per phase)
+            for (int ph = 0; ph < tc->spec.nphase; ++ph) taps += (ph ? "/" : "") + std::to_string(G.taps[ph].off.size());
+            snprintf(gb, sizeof gb, "%s%dx%s@%d/%dx%d%s%s", g ? "+" : "", G.C, taps.c_str(), G.c_off, G.d2, G.d3, G.transpose ? "T" : "",
+                     G.w2_off != SIZE_MAX ? "s" : "");
+            groups += gb;
+        }
+        for (int ph = 0; ph < 4; ++ph) nrefs += p.P.wrefs[ph].size();
+        char buf[256];
+        snprintf(buf, sizeof buf, "; groups %s, act %d, direct %d, wsh %d, packs %zu, refs %zu, scratch %zu, digest %016llx\n", groups.c_str(),
+                 tc->spec.act, p.direct ? 1 : 0, p.wsh, p.packs.size(), nrefs, p.split_floats,
+                 tconv_digest(p.cp, p.nt, p.hpix, p.packs.data(), p.packs.size(), p.split ? &p.P : nullptr));
+        out += p.text + buf;
+    }
+    *needed = out.size() + 1;
+    if (cap < *needed) return umx::fail(nullptr, UMX_ERR_INVALID, "umx_test_train_plan: the text takes %zu bytes", *needed);
+    memcpy(text, out.c_str(), *needed);
     return UMX_OK;
 }
 

@@ -32,7 +32,7 @@ EXPORTS = [
     "umx_infer_image_sharded_dev", "umx_infer_image_sharded_raw", "umx_infer_image_sharded_raw_submit",
     "umx_band_tiles_dev", "umx_stitch_dev", "umx_profile_enable", "umx_profile_read", "umx_prof_entry_size", "umx_test_double_to_half", "umx_test_double_to_half_dev",
     "umx_test_gauss_weights", "umx_test_resize_dev", "umx_test_rescale_dev", "umx_test_plane_range_dev", "umx_test_half_to_u8_dev",
-    "umx_describe", "umx_describe_graph", "umx_plan_check", "umx_test_wgrad_plan", "umx_test_mx_pack_e2m3", "umx_version",
+    "umx_describe", "umx_describe_graph", "umx_plan_check", "umx_test_wgrad_plan", "umx_test_train_plan", "umx_test_mx_pack_e2m3", "umx_version",
     "umx_label_options_check", "umx_labeler_create", "umx_labeler_destroy", "umx_labeler_last_error", "umx_labeler_run",
     "umx_labeler_run_dev", "umx_labeler_objects", "umx_labeler_last_ms",
     "umx_label_measure_check", "umx_labeler_measure", "umx_labeler_measure_dev", "umx_labeler_measure_last_ms",
@@ -383,6 +383,29 @@ def wgrad_plan(B: int, H: int, Cxt: int, Cx: int, Cg: int, slabs, f32_route: boo
     L.umx_test_wgrad_plan.argtypes = [ctypes.c_int] * 6 + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4 + [ctypes.c_char_p, ctypes.c_size_t]
     _check(L, L.umx_test_wgrad_plan(B, H, Cxt, Cx, Cg, len(slabs), *cols, int(f32_route), int(planes), XCs, GCs, buf, len(buf)))
     return buf.value.decode()
+
+
+def train_plan(hp, batch: int, blob, conv_f32: bool = False, no_ksplit: bool = False):
+    """umx_test_train_plan: the host pass of the trainer's build for these hyper-parameters, batch and initial parameters, as one line
+    per forward / input-gradient convolution in build order (its UMX_DEBUG_PLAN text, groups, direct, weight shift, descriptor and
+    reference counts, K-split scratch, digest of what the upload would send).  Host only."""
+    import numpy as np
+    L = load()
+    blob = np.ascontiguousarray(blob, dtype=np.float32)
+    hps = _hp_struct(hp)
+    fn = L.umx_test_train_plan
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p,
+                   ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    buf = ctypes.create_string_buffer(1 << 16)
+    need = ctypes.c_size_t(0)
+    args = (ctypes.byref(hps), batch, int(conv_f32), int(no_ksplit), blob.ctypes.data, blob.size)
+    rc = fn(*args, buf, len(buf), ctypes.byref(need))
+    if rc and need.value > len(buf):
+        buf = ctypes.create_string_buffer(need.value)
+        rc = fn(*args, buf, len(buf), ctypes.byref(need))
+    _check(L, rc)
+    return buf.value.decode().splitlines()
 
 
 def auto_batch(hp: HParams, arena_bytes: float = 12 * 2 ** 30) -> int:
