@@ -478,6 +478,19 @@ UMX_API int umx_test_wgrad_plan(int B, int H, int Cxt, int Cx, int Cg, int nslab
  * cap is too small: UMX_ERR_INVALID).  A shape the planner refuses: its code, the reason in umx_last_error(NULL). */
 UMX_API int umx_test_train_plan(const umx_hparams* hp, int B, int conv_f32, int no_ksplit, const float* blob, size_t blob_floats,
                                 char* text, size_t cap, size_t* needed);
+/* test entries (host only): the schedule of a whole-slide call as data.  umx_test_slide_plan: what the image entries enqueue for an
+ * H x W slide of C_img planes (src_bits 0: float64, 8 / 16: raw) at launch groups of max_batch tiles -- rescale, has_range (the caller
+ * hands the planes' (min, max) in), sync_call (else submitted), host_range_ok (UMX_HOST_RANGE is not 0), raw_gather (the engine's tile
+ * gather reads raw planes), stitch (UMX_STITCH_*), out_u8; tile_flops: algorithmic FLOPs of one tile (<= 0: from the graph of `hp`).  text
+ * receives a header line (slabs, single stream or not, events, buffer cuts and sizes) and one line per step in enqueue order.
+ * umx_test_band_plan: what a sharded entry enqueues for the band of `rank` in `world` -- a header line, then one line per launch group
+ * (tiles, staged rows of a host band and their event) and per slab (rows, padding, event, every rank's rows) in order.  *needed: the
+ * text's bytes with the terminator (set even where cap is too small: UMX_ERR_INVALID). */
+UMX_API int umx_test_slide_plan(const umx_hparams* hp, int H, int W, int max_batch, int C_img, int src_bits, int rescale, int has_range,
+                                int sync_call, int host_range_ok, int raw_gather, int stitch, int out_u8, double tile_flops, char* text,
+                                size_t cap, size_t* needed);
+UMX_API int umx_test_band_plan(const umx_hparams* hp, int H, int W, int world, int rank, int nslabs, int max_batch, int band_row0,
+                               int band_rows, int stitch, int u8, int staged, int own_stream, char* text, size_t cap, size_t* needed);
 UMX_API const char* umx_version(void);
 
 #ifdef __cplusplus

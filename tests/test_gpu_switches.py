@@ -173,6 +173,30 @@ def test_raw_gather_equals_the_float64_image_path(dtype, reference):
         assert np.array_equal(got, want)
 
 
+def test_raw_planes_converted_slab_by_slab_equal_the_float64_image_path():
+    """An engine whose tile gather reads float64 (UMX_PREC_F32) on a slide of several slabs: the raw rows are converted on the device
+    (im2double [+ rescale]) as each slab's upload arrives -- behind a device reduction of the whole planes with `rescale`, slab by slab
+    without it or with the planes' range handed in.  The same bytes as the same engine's float64 entry fed with the host's own
+    im2double [+ rescale], compared as the test above compares them."""
+    import helpers
+    hp = helpers.small_hps()["v2_duo_like"]
+    blob = model.random_blob(hp, seed=9)
+    raw = np.random.default_rng(6).integers(0, 65536, size=(2, 70, 45)).astype(np.uint16)
+    I = raw.astype(np.float64) * (1.0 / 65535)
+    R = np.stack([(np.clip(p, p.min(), p.max()) - p.min()) / (p.max() - p.min()) * 0.983 for p in I])
+    with umx.Engine(hp, blob, max_batch=2, precision="f32") as eng:
+        assert eng.precision == "f32"
+        direct = eng.infer_image_raw(raw, False, 0.3, 0.2)
+        rescaled = eng.infer_image_raw(raw, True, 0.3, 0.2)
+        ranged = eng.infer_image_raw(raw, True, 0.3, 0.2, value_range=[(int(p.min()), int(p.max())) for p in raw])
+        planes = eng.infer_image(I, 0.3, 0.2)
+        planes_r = eng.infer_image(R, 0.3, 0.2)
+    for got, pl in ((direct, planes), (rescaled, planes_r), (ranged, planes_r)):
+        first = (np.float16(255) * pl).astype(np.uint8)
+        want = (255.0 * (first.astype(np.float64) * (1.0 / 255))).astype(np.uint8)
+        assert np.array_equal(got, want)
+
+
 def test_the_stitch_kernels_double_to_half_equals_the_host_statement():
     """stitch_kernel converts with d2h_rne (round-to-odd binary32, then v_cvt_f16_f32); the unit test of the conversion only
     exercised the host routine.  Same directed vectors through the device routine: ties at every binade, half subnormals, values of the

@@ -245,7 +245,6 @@ int check_range_flag(umx_ctx* ctx) {   // call with the stream idle
 
 int run_unet(umx_ctx* ctx, const float* tiles, int n, float* probs) {
     if (ctx->precision == UMX_PREC_F16X3) return run_unet_f16(ctx, tiles, n, probs);
-    const umx_hparams& hp = ctx->hp;
     for (auto& L : ctx->plan) {
         const float* src0 = L.g[0].src == 0 ? tiles : cur_bufs(ctx)[L.g[0].src].d;
         if (L.head) {
@@ -266,7 +265,6 @@ int run_unet(umx_ctx* ctx, const float* tiles, int n, float* probs) {
         HIP_TRY(ctx, launch_conv(p, L.nt, L.hpix, run_stream(ctx)));
     }
     if (ctx->prof && ctx->pending.size() > 4096) return prof_fold(ctx);
-    (void)hp;
     return UMX_OK;
 }
 
@@ -305,17 +303,6 @@ struct LaneLoop {
     ~LaneLoop() { join(); }   // error paths: the side stream is still joined into the context's stream
 };
 
-TileGeom geom_of(const umx_hparams& hp, int H, int W) {
-    TileGeom g;
-    g.H = H; g.W = W;
-    g.P = hp.imSize;
-    g.margin = hp.imSize / 8;              // int(imSize/8), UnMicst1-5.py:694
-    g.sub = g.P - 2 * g.margin;
-    g.npr = (H + g.sub - 1) / g.sub;       // ceil, PartitionOfImage.py:49-50
-    g.npc = (W + g.sub - 1) / g.sub;
-    return g;
-}
-
 // tiles [t0, t1) of the slide (row-major tile index) -> probs_dev (tile t0 first): gather + normalise + UNet, in launch
 // groups of <= max_batch tiles
 bool gathers_raw(const umx_ctx* ctx) {
@@ -327,7 +314,7 @@ int tiles_range(umx_ctx* ctx, const double* image_dev, int C_img, const TileGeom
                        const unsigned* mm_dev) {
     const size_t prob_f = (size_t)g.P * g.P * ctx->hp.nClasses;
     if (ctx->site_gather < 0) ctx->site_gather = site_of(ctx, "pi2d.gather_normalise", "gather_normalise");
-    const bool direct16 = ctx->precision == UMX_PREC_F16X3 && ctx->hp.nChannels <= 8 && ctx->bufs[0].Cs == 8;
+    const bool direct16 = gathers_raw(ctx);
     if (raw_dev && !direct16) return fail(ctx, UMX_ERR_INVALID, "internal: raw planes handed to an engine that does not gather from them");
     const void* const src = raw_dev ? raw_dev : (const void*)image_dev;
     const double src_b = raw_dev ? raw_bits / 8.0 : 8.0;

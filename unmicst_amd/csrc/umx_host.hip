@@ -145,178 +145,103 @@ static int host_wait(umx_ctx* ctx, int slot) {
     return UMX_OK;
 }
 
+// The executor of a slide's schedule (slide_plan, umx_pipeline.hip): the slot's buffers sized from the plan, its events, then the
+// plan's steps in order -- their rows and tiles turned into addresses, each step one copy, launch or event per plane.
 // range: the planes' (min, max) as the caller's reader found them, or NULL
 static int host_enqueue(umx_ctx* ctx, int slot, bool sync_call, const void* src, int src_bits, int C_img, int H, int W, int rescale,
                         const uint32_t* range, double mean, double stdv, int mode, int stitch, int out_u8, void* out_host) {
     umx_ctx::HostSlot& hs = ctx->hs[slot];
     const TileGeom g = geom_of(ctx->hp, H, W);
-    const size_t plane = (size_t)H * W, K = ctx->hp.nClasses;
-    const size_t in_b = src_bits ? (size_t)(src_bits / 8) : sizeof(double);
-    const size_t oel = stitch == UMX_STITCH_FP32 ? 4 : 2;
-    const size_t pm_b = K * plane * oel, u8_b = out_u8 ? K * plane : 0;
-    const size_t raw_off = (pm_b + u8_b + 255) & ~(size_t)255;
-    const size_t raw_b = src_bits ? plane * C_img * in_b : 0;
-    const size_t mm_off = (raw_off + raw_b + 255) & ~(size_t)255;
+    SlideSpec sp;
+    sp.max_batch = ctx->max_batch;
+    sp.K = ctx->hp.nClasses;
+    sp.C_img = C_img;
+    sp.src_bits = src_bits;
+    sp.rescale = rescale;
+    sp.has_range = range != nullptr;
+    sp.sync_call = sync_call;
+    // (read only where the plan can use it -- a synchronous call without a range: getenv walks the environment, and a submitted
+    // 1024 x 1024 slide is a 1 ms call)
+    sp.host_range_ok = sync_call && !range && !(getenv("UMX_HOST_RANGE") && atoi(getenv("UMX_HOST_RANGE")) == 0);
+    sp.stitch_el = stitch == UMX_STITCH_FP32 ? 4 : 2;
+    sp.out_u8 = out_u8;
+    sp.raw_gather = src_bits != 0 && gathers_raw(ctx);
+    for (const Launch& L : ctx->plan) sp.tile_flops += L.flops;
+    const SlidePlan p = slide_plan(g, sp);
     int rc;
-    // raw planes: the tile gather converts (and, with `rescale`, rescales to the plane's (min, max) words, ready in stream order
-    // before the first tile) as it reads -- the float64 image, 8 bytes written and 14 read per pixel and channel, is never made, and
-    // not allocated either: 4.3 GB for a two-channel 16384 x 16384 slide
-    const bool raw_gather = src_bits != 0 && gathers_raw(ctx);
-    if (!raw_gather && (rc = grow(ctx, (void**)&hs.d_image, &hs.image_cap, plane * C_img * sizeof(double), slot ? "slot 1 d_image" : "slot 0 d_image")))
-        return rc;
-    if ((rc = grow(ctx, &hs.d_out, &hs.out_cap, mm_off + 64 * (size_t)C_img, slot ? "slot 1 d_out" : "slot 0 d_out"))) return rc;
-    if ((rc = grow(ctx, (void**)&hs.d_probs, &hs.probs_cap, (size_t)g.npr * g.npc * g.P * g.P * K * sizeof(float),
-                   slot ? "slot 1 d_probs" : "slot 0 d_probs")))
-        return rc;
-    unsigned char* const base = (unsigned char*)hs.d_out;
-    // slabs = the launch groups of the tile loop (equal groups of <= max_batch tiles, exactly what umx_infer_image_dev
-    // runs), so that pipelining the transfers does not change a single kernel launch
-    const int T = g.npr * g.npc;
-    const int S = std::max(1, (T + ctx->max_batch - 1) / ctx->max_batch);
-    // A synchronous call on a slide of one launch group has nothing to overlap: its upload, kernels and download go down ONE
-    // stream in order, without the copy streams and the events that hand slabs from one stream to the next (a 1024 x 1024
-    // slide is a 1 - 3 ms call).  Submitted calls keep the copy streams: slide i+1's upload rides under slide i's kernels --
-    // unless the slide is so small (< 0.6 TFLOP, about 2 ms of kernels: the legacy model's 1024 x 1024 slide is 1 ms) that the
-    // cross-stream events cost more than the overlap returns: that call measured 1.03 ms on some boxes and 1.54 on others through
-    // the copy streams, 1.02 as one in-order stream.
-    double slide_flops = 0.0;
-    for (const Launch& L : ctx->plan) slide_flops += L.flops;
-    slide_flops *= (double)T;
-    const bool single = S == 1 && (sync_call || slide_flops < 0.6e12);
-    const hipStream_t up_s = single ? ctx->stream : ctx->up_stream, dn_s = single ? ctx->stream : ctx->dn_stream;
-    while ((int)hs.events.size() < 2 * S + 1) {
+    if (p.image_b && (rc = grow(ctx, (void**)&hs.d_image, &hs.image_cap, p.image_b, slot ? "slot 1 d_image" : "slot 0 d_image"))) return rc;
+    if ((rc = grow(ctx, &hs.d_out, &hs.out_cap, p.out_b, slot ? "slot 1 d_out" : "slot 0 d_out"))) return rc;
+    if ((rc = grow(ctx, (void**)&hs.d_probs, &hs.probs_cap, p.probs_b, slot ? "slot 1 d_probs" : "slot 0 d_probs"))) return rc;
+    while ((int)hs.events.size() < p.nev) {
         hipEvent_t ev;
         HIP_TRY(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         hs.events.push_back(ev);
     }
-    hipEvent_t* const ev_up = hs.events.data();
-    hipEvent_t* const ev_dn = hs.events.data() + S;
-    hipEvent_t ev_start = hs.events[2 * S];
-    (void)ev_start;   // (a slot's buffers are private to it and free again once host_wait has returned: no extra ordering)
-    std::vector<int> tcut(S + 1), cut(S + 1);   // tile cuts; cut[i] = patch rows COMPLETE after slab i-1 (cut[S] = npr)
-    for (int i = 0; i <= S; ++i) {
-        tcut[i] = (int)((long long)T * i / S);
-        cut[i] = tcut[i] / g.npc;
-    }
-    auto rows_needed = [&](int pr1) { return std::min(H, (pr1 - 1) * g.sub + g.P - g.margin); };
-    unsigned* const mm = (unsigned*)(base + mm_off);
-    unsigned char* const d_raw = base + raw_off;
-    auto upload = [&](int r0, int r1) -> int {   // image rows [r0, r1) of every plane
-        for (int c = 0; c < C_img && r1 > r0; ++c) {
-            const size_t off = ((size_t)c * H + r0) * W * in_b, n = (size_t)(r1 - r0) * W * in_b;
-            void* const dst = src_bits ? (void*)(d_raw + off) : (void*)((unsigned char*)hs.d_image + off);
-            HIP_TRY(ctx, hipMemcpyAsync(dst, (const unsigned char*)src + off, n, hipMemcpyHostToDevice, up_s));
-        }
-        return UMX_OK;
-    };
-    auto convert = [&](int r0, int r1) -> int {   // raw rows -> float64 rows (im2double [+ rescale])
-        for (int c = 0; c < C_img && src_bits && !raw_gather && r1 > r0; ++c) {
-            const size_t e0 = ((size_t)c * H + r0) * W;
-            HIP_TRY(ctx, launch_raw_convert(d_raw + e0 * in_b, src_bits, (size_t)(r1 - r0) * W, rescale, mm + 16 * c,
-                                            hs.d_image + e0, ctx->stream));
-        }
-        return UMX_OK;
-    };
-    int up_done = 0;
-    // A synchronous rescaled call whose caller handed no range in: every slab's upload is enqueued first (pinned pages: DMA), the
-    // planes' (min, max) found by host threads while the rows cross the bus (3 ms per 537 MB plane), and the tile kernels start on
-    // the first slab as soon as that pass is done -- instead of behind the whole upload and a device reduction (UMX_HOST_RANGE=0)
+    const hipStream_t cs = ctx->stream, up_s = p.single ? cs : ctx->up_stream, dn_s = p.single ? cs : ctx->dn_stream;
+    const size_t plane = (size_t)H * W, K = sp.K, in_b = src_bits ? (size_t)(src_bits / 8) : sizeof(double);
+    const size_t el = out_u8 ? 1 : sp.stitch_el;   // element of what goes down
+    unsigned char* const base = (unsigned char*)hs.d_out;
+    unsigned char* const d_raw = base + p.raw_off;
+    unsigned char* const d_up = src_bits ? d_raw : (unsigned char*)hs.d_image;         // where the caller's planes go up
+    unsigned char* const d_res = out_u8 ? base + p.pm_b : base;                        // the result: compact slabs [K][rows][W], one after the other
+    unsigned* const mm = (unsigned*)(base + p.mm_off);
     uint32_t own_range[2 * 8];
-    std::vector<int> pre_r1;   // rows up after slab s, when the uploads were enqueued ahead
-    if (src_bits && rescale && !range && sync_call && C_img <= 8 && !(getenv("UMX_HOST_RANGE") && atoi(getenv("UMX_HOST_RANGE")) == 0)) {
-        pre_r1.resize(S);
-        for (int s = 0; s < S; ++s) {
-            const int r1 = s == S - 1 ? H : rows_needed((tcut[s + 1] - 1) / g.npc + 1);
-            if (r1 > up_done) {
-                if ((rc = upload(up_done, r1))) return rc;
-                if (!single) HIP_TRY(ctx, hipEventRecord(ev_up[s], ctx->up_stream));
-                up_done = r1;
+    for (const Step& st : p.steps) {
+        const size_t e0 = (size_t)st.a * W, n = (size_t)(st.b - st.a) * W;             // first element and elements of rows [a, b) in a plane
+        switch (st.kind) {
+        case kStepUpload:
+            for (int c = 0; c < C_img; ++c) {
+                const size_t off = (c * plane + e0) * in_b;
+                HIP_TRY(ctx, hipMemcpyAsync(d_up + off, (const unsigned char*)src + off, n * in_b, hipMemcpyHostToDevice, up_s));
             }
-            pre_r1[s] = up_done;
-        }
-        for (int c = 0; c < C_img; ++c)
-            if (umx_plane_range((const unsigned char*)src + (size_t)c * plane * in_b, src_bits, plane, own_range + 2 * c) != UMX_OK)
-                return fail(ctx, UMX_ERR_INVALID, "plane range");
-        range = own_range;
-    }
-    if (src_bits) {
-        for (int c = 0; c < C_img; ++c) HIP_TRY(ctx, launch_minmax_init(mm + 16 * c, ctx->stream));
-        if (rescale && range) {
-            // the caller's file reader saw every sample and hands the planes' (min, max) in: the words the reduction below would
-            // leave, so the slide goes up slab by slab under the tile kernels like an un-rescaled one (a synchronous rescaled
-            // call otherwise spends the whole upload -- 21 ms for the 1.07 GB metric slide -- in front of its first tile)
+            if (st.c >= 0) HIP_TRY(ctx, hipEventRecord(hs.events[st.c], up_s));
+            break;
+        case kStepWaitUpload:
+            HIP_TRY(ctx, hipStreamWaitEvent(cs, hs.events[st.a], 0));
+            break;
+        case kStepMinMaxInit:
+            for (int c = 0; c < C_img; ++c) HIP_TRY(ctx, launch_minmax_init(mm + 16 * c, cs));
+            break;
+        case kStepHostRange:   // (3 ms per 537 MB plane, while the uploads enqueued so far cross the bus)
+            for (int c = 0; c < C_img; ++c)
+                if (umx_plane_range((const unsigned char*)src + c * plane * in_b, src_bits, plane, own_range + 2 * c) != UMX_OK)
+                    return fail(ctx, UMX_ERR_INVALID, "plane range");
+            range = own_range;
+            break;
+        case kStepPutRange:
             if ((rc = put_range(ctx, mm, range, C_img))) return rc;
-        } else if (rescale) {   // whole planes first: min / max per plane, reduced as the slabs arrive
-            for (int s = 0; s < S; ++s) {
-                const int r1 = s == S - 1 ? H : rows_needed((tcut[s + 1] - 1) / g.npc + 1);
-                if (r1 <= up_done) continue;
-                if ((rc = upload(up_done, r1))) return rc;
-                if (!single) {
-                    HIP_TRY(ctx, hipEventRecord(ev_up[s], ctx->up_stream));
-                    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ev_up[s], 0));
-                }
-                for (int c = 0; c < C_img && r1 > up_done; ++c)
-                    HIP_TRY(ctx, launch_minmax(d_raw + ((size_t)c * H + up_done) * W * in_b, src_bits, (size_t)(r1 - up_done) * W,
-                                               mm + 16 * c, ctx->stream));
-                up_done = r1;
-            }
-            if ((rc = convert(0, H))) return rc;
-        }
-    }
-    int y_done = 0;
-    for (int s = 0; s < S; ++s) {
-        // rows the tiles of this slab read: up to the last patch row it touches
-        const int r1 = s == S - 1 ? H : rows_needed((tcut[s + 1] - 1) / g.npc + 1);
-        if (!pre_r1.empty()) {   // uploaded ahead: wait for this slab's rows, convert them
-            const int r0 = s ? pre_r1[s - 1] : 0;
-            if (pre_r1[s] > r0) {
-                if (!single) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ev_up[s], 0));
-                if ((rc = convert(r0, pre_r1[s]))) return rc;
-            }
-        } else if (r1 > up_done) {
-            if ((rc = upload(up_done, r1))) return rc;
-            if (!single) {
-                HIP_TRY(ctx, hipEventRecord(ev_up[s], ctx->up_stream));
-                HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ev_up[s], 0));
-            }
-            if ((rc = convert(up_done, r1))) return rc;
-            up_done = r1;
-        }
-        if (tcut[s + 1] > tcut[s]) {
-            float* const pr = hs.d_probs + (size_t)tcut[s] * g.P * g.P * K;
-            if ((rc = tiles_range(ctx, raw_gather ? nullptr : hs.d_image, C_img, g, 0, H, mean, stdv, tcut[s], tcut[s + 1], pr, raw_gather ? d_raw : nullptr,
-                                  raw_gather ? src_bits : 0, raw_gather && rescale ? mm : nullptr)))
+            break;
+        case kStepMinMax:
+            for (int c = 0; c < C_img; ++c)
+                HIP_TRY(ctx, launch_minmax(d_raw + (c * plane + e0) * in_b, src_bits, n, mm + 16 * c, cs));
+            break;
+        case kStepConvert:
+            for (int c = 0; c < C_img; ++c)
+                HIP_TRY(ctx, launch_raw_convert(d_raw + (c * plane + e0) * in_b, src_bits, n, rescale, mm + 16 * c, hs.d_image + c * plane + e0, cs));
+            break;
+        case kStepTiles:
+            if ((rc = tiles_range(ctx, sp.raw_gather ? nullptr : hs.d_image, C_img, g, 0, H, mean, stdv, st.a, st.b,
+                                  hs.d_probs + (size_t)st.a * g.P * g.P * K, sp.raw_gather ? d_raw : nullptr, sp.raw_gather ? src_bits : 0,
+                                  sp.raw_gather && rescale ? mm : nullptr)))
                 return rc;
-        }
-        // image rows no later tile touches: below the first incomplete patch row
-        const int y1 = s == S - 1 ? H : std::max(y_done, std::min(H, cut[s + 1] * g.sub - g.margin));
-        if (y1 > y_done && cut[s + 1] > 0) {
-            // the stitch writes a compact slab [K][rows][W]; slabs sit one after the other in the device buffer
-            const size_t rows = (size_t)(y1 - y_done), slab_e = K * (size_t)y_done * W;
-            unsigned char* const d_slab = base + slab_e * oel;
-            // (uint8 out: the cast rides in the stitch -- no float16 slab is written and read back)
-            if ((rc = stitch_rows(ctx, hs.d_probs, 0, cut[s + 1], H, W, mode, out_u8 ? kStitchU8 : stitch, y_done, y1,
-                                  out_u8 ? (void*)(base + pm_b + slab_e) : (void*)d_slab, 0)))
-                return rc;
-            if (!single) {
-                HIP_TRY(ctx, hipEventRecord(ev_dn[s], ctx->stream));
-                HIP_TRY(ctx, hipStreamWaitEvent(ctx->dn_stream, ev_dn[s], 0));
-            }
-            const size_t el = out_u8 ? 1 : oel;
-            const unsigned char* const dsrc = out_u8 ? base + pm_b + slab_e : d_slab;
+            break;
+        case kStepStitch:      // (uint8 out: the cast rides in the stitch -- no float16 slab is written and read back)
+            if ((rc = stitch_rows(ctx, hs.d_probs, 0, st.c, H, W, mode, out_u8 ? kStitchU8 : stitch, st.a, st.b, d_res + K * e0 * el, 0))) return rc;
+            break;
+        case kStepDownloadEvent:
+        case kStepFlag:
+            if (st.kind == kStepFlag && !ctx->d_flag) break;
+            HIP_TRY(ctx, hipEventRecord(hs.events[st.a], cs));
+            HIP_TRY(ctx, hipStreamWaitEvent(dn_s, hs.events[st.a], 0));
+            break;
+        case kStepDownload:
             for (size_t k = 0; k < K; ++k)
-                HIP_TRY(ctx, hipMemcpyAsync((unsigned char*)out_host + (k * plane + (size_t)y_done * W) * el,
-                                            dsrc + k * rows * W * el, rows * W * el, hipMemcpyDeviceToHost, dn_s));
-            y_done = y1;
+                HIP_TRY(ctx, hipMemcpyAsync((unsigned char*)out_host + (k * plane + e0) * el, d_res + (K * e0 + k * n) * el, n * el,
+                                            hipMemcpyDeviceToHost, dn_s));
+            break;
         }
     }
-    // the range flag of the split-precision path rides down behind the last planes; `done` then says the call is complete
-    // (every upload precedes a kernel that precedes a download on the download stream)
-    if (ctx->d_flag && !single) {
-        hipEvent_t ev_f = hs.events[2 * S];
-        HIP_TRY(ctx, hipEventRecord(ev_f, ctx->stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->dn_stream, ev_f, 0));
-    }
+    // `done` then says the call is complete (a slot's buffers are private to it and free again once host_wait has returned)
     return slot_finish(ctx, slot, dn_s);
 }
 
@@ -509,6 +434,43 @@ int umx_infer_image_raw_submit(umx_ctx* ctx, int slot, const void* raw_host, int
 int umx_infer_image_wait(umx_ctx* ctx, int slot) {
     if (!ctx) return fail(nullptr, UMX_ERR_INVALID, "ctx is NULL");
     return guarded(ctx, false, true, [&]() -> int { return host_wait(ctx, slot); });
+}
+
+// The schedule of a whole-slide call on the host alone (no device): slide_describe of the plan host_enqueue would execute for this
+// model, slide and call -- stitch: UMX_STITCH_*; tile_flops <= 0: the graph is built from the hyper-parameters for the figure.
+// *needed: bytes of the text with its terminator; UMX_ERR_INVALID where cap is smaller.
+int umx_test_slide_plan(const umx_hparams* hp, int H, int W, int max_batch, int C_img, int src_bits, int rescale, int has_range, int sync_call,
+                        int host_range_ok, int raw_gather, int stitch, int out_u8, double tile_flops, char* text, size_t cap, size_t* needed) {
+    if (!hp || !needed || (!text && cap)) return fail(nullptr, UMX_ERR_INVALID, "umx_test_slide_plan: null argument");
+    *needed = 0;
+    std::string why;
+    if (const int rc = check_hp(hp, &why)) return fail(nullptr, rc, "%s", why.c_str());
+    if (H < 1 || W < 1 || max_batch < 1 || C_img < 1 || (src_bits != 0 && src_bits != 8 && src_bits != 16))
+        return fail(nullptr, UMX_ERR_INVALID, "umx_test_slide_plan: bad H / W / max_batch / C_img / src_bits");
+    SlideSpec sp;
+    sp.max_batch = max_batch;
+    sp.K = hp->nClasses;
+    sp.C_img = C_img;
+    sp.src_bits = src_bits;
+    sp.rescale = rescale;
+    sp.has_range = has_range != 0;
+    sp.sync_call = sync_call != 0;
+    sp.host_range_ok = host_range_ok != 0;
+    sp.stitch_el = stitch == UMX_STITCH_FP32 ? 4 : 2;
+    sp.out_u8 = out_u8;
+    sp.raw_gather = src_bits != 0 && raw_gather != 0;
+    sp.tile_flops = tile_flops;
+    if (!(tile_flops > 0.0)) {
+        std::vector<Launch> plan;
+        build_graph(*hp, nullptr, &plan, nullptr, nullptr, nullptr);
+        sp.tile_flops = 0.0;
+        for (const Launch& L : plan) sp.tile_flops += L.flops;
+    }
+    const std::string out = slide_describe(slide_plan(geom_of(*hp, H, W), sp));
+    *needed = out.size() + 1;
+    if (cap < *needed) return fail(nullptr, UMX_ERR_INVALID, "umx_test_slide_plan: the text takes %zu bytes", *needed);
+    memcpy(text, out.c_str(), *needed);
+    return UMX_OK;
 }
 
 // ---- test entries of the driver-side image kernels (tests/test_gpu_imagekernels.py, tests/test_imagekernels_cpu.py): thin wrappers

@@ -1,6 +1,7 @@
 // Internal host-side interface of libumx (gfx950 only): the graph / plan / context structures shared by the graph builder
-// (umx_graph.hip), the split-precision planner (umx_plan.hip), the engine and C ABI (umx_engine.hip) and the host pipeline
-// (umx_host.hip).  Nothing here is part of the C ABI (include/umx.h).
+// (umx_graph.hip), the split-precision planner (umx_plan.hip), the engine and C ABI (umx_engine.hip), the schedules of the
+// whole-slide entries (umx_pipeline.hip) and their executors: the host pipeline (umx_host.hip) and the sharded one (umx_shard.hip).
+// Nothing here is part of the C ABI (include/umx.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -413,7 +414,6 @@ int check_range_flag(umx_ctx* ctx);   // call with the stream idle
 // umx_stitch_dev's body with the internal forms: stitch = kStitchU8 (uint8 planes), plane_rows > 0 (rows per class plane of `out_dev`)
 int stitch_rows(umx_ctx* ctx, const float* probs_dev, int tpr0, int tpr1, int H, int W, int mode, int stitch, int y0, int y1,
                 void* out_dev, int plane_rows);
-TileGeom geom_of(const umx_hparams& hp, int H, int W);
 // tiles [t0, t1) of the slide (row-major tile index) -> probs_dev (tile t0 first): gather + normalise + UNet
 // (raw_dev / raw_bits: the same planes as raw uint8 / uint16 values, for an engine that gathers from them -- gathers_raw())
 int tiles_range(umx_ctx* ctx, const double* image_dev, int C_img, const TileGeom& g, int band_row0, int band_rows,
@@ -432,6 +432,93 @@ int slot_submit(umx_ctx* ctx, int slot, const std::function<int()>& enqueue);
 int slot_finish(umx_ctx* ctx, int slot, hipStream_t dn_s);
 // a caller's planes' (min, max) -> each plane's mm words (16 apart), on the context's stream
 int put_range(umx_ctx* ctx, unsigned* mm, const uint32_t* range, int C_img);
+
+// ---- umx_pipeline.hip: the schedules of the whole-slide entries as data (no HIP call, no context, no getenv)
+// A step of a slide's schedule: one thing the executor (umx_host.hip host_enqueue) enqueues, in the plan's order.  Rows are image
+// rows of every plane, tiles row-major tile indices, events indices into the slot's events.
+enum StepKind {
+    kStepUpload,          // rows [a, b) go up on the upload stream; event c is recorded behind them (c < 0: none)
+    kStepWaitUpload,      // the compute stream waits for event a
+    kStepMinMaxInit,      // the planes' (min, max) words are reset
+    kStepPutRange,        // ... and set to the range the caller handed in or the host pass found
+    kStepHostRange,       // the host finds the planes' (min, max) while the rows enqueued so far cross the bus
+    kStepMinMax,          // rows [a, b) are reduced into the (min, max) words on the device
+    kStepConvert,         // raw rows [a, b) -> float64 rows (im2double [+ rescale])
+    kStepTiles,           // tiles [a, b): gather + normalise + UNet
+    kStepStitch,          // output rows [a, b) are stitched from the patch rows < c
+    kStepDownloadEvent,   // event a is recorded on the compute stream and the download stream waits for it
+    kStepDownload,        // output rows [a, b) go down on the download stream
+    kStepFlag             // the range flag's hand-over to the download stream through event a (an engine without the flag skips it)
+};
+TileGeom geom_of(const umx_hparams& hp, int H, int W);
+struct Step { int kind, a, b, c; };
+struct SlideSpec {                 // what the schedule of a slide depends on besides its tile geometry
+    int max_batch = 1, K = 1, C_img = 1;
+    int src_bits = 0;              // 0: float64 planes; 8 / 16: raw integer planes
+    int rescale = 0;
+    bool has_range = false;        // the caller handed the planes' (min, max) in
+    bool sync_call = true;         // a synchronous entry (else submitted: umx_infer_image_raw_submit)
+    bool host_range_ok = true;     // the host may find the range itself (UMX_HOST_RANGE is not 0)
+    size_t stitch_el = 2;          // bytes of a stitched element (fp16-compatible: 2, fp32: 4)
+    int out_u8 = 0;                // the drivers' uint8 planes go down instead of the stitch result
+    bool raw_gather = false;       // the engine's tile gather reads raw planes (gathers_raw)
+    double tile_flops = 0.0;       // algorithmic FLOPs of one tile: the 0.6 TFLOP rule of `single`
+};
+struct SlidePlan {
+    // the slot's d_out: [stitched planes pm_b | uint8 planes u8_b | raw planes at raw_off | (min, max) words at mm_off], out_b in all;
+    // image_b: the float64 image (0: never made); probs_b: the tile probabilities
+    size_t pm_b = 0, u8_b = 0, raw_off = 0, mm_off = 0, out_b = 0, image_b = 0, probs_b = 0;
+    int S = 1;                     // slabs = launch groups
+    bool single = false;           // one in-order stream: no copy streams, no events
+    int nev = 0;                   // events the steps index
+    std::vector<Step> steps;
+};
+SlidePlan slide_plan(const TileGeom& g, const SlideSpec& sp);
+std::string slide_describe(const SlidePlan& p);   // a header line, then one line per step
+
+struct BandSpec {                  // what the schedule of one rank's band depends on besides the slide's tile geometry
+    int world = 1, rank = 0, nslabs = 1, max_batch = 1;
+    int band_row0 = 0, band_rows = 0;
+    int K = 1;
+    size_t gather_el = 2;          // bytes of a gathered element (uint8 result: 1, else the stitched element)
+    bool staged = false;           // a host band goes up piece by piece ahead of the tiles that read it ...
+    bool own_stream = false;       // ... on a stream of its own (an event hands each piece to the compute stream)
+};
+struct BandPlan {
+    std::vector<int> A, B, active; // every rank's patch rows [A[q], B[q]); the ranks that have any
+    int n = 1;                     // slabs
+    int pa = 0, pb = 0, lo = 0;    // this rank's patch rows; the first patch row in `probs` (pa - 1 with a previous rank's halo row)
+    int F = 0;                     // tiles of the first launch group: the band's last ones
+    int send_peer = -1, recv_peer = -1;   // halo: the band's last patch row goes to the next active rank, the previous one's comes in
+    int own0 = 0, own1 = 0;        // output rows this rank stitches
+    int mx_all = 1;                // rows of the largest slab of any rank: the padding of the gather buffers
+    size_t probs_b = 0, send_b = 0, gathered_b = 0;
+    int nev = 0;
+    struct Group { int t0, t1, r0, r1, ev; };   // tiles [t0, t1); staged image rows [r0, r1) in front of them (none: r1 <= r0) and their event (none: < 0)
+    std::vector<Group> groups;     // in launch order; before slab 0's: the first group
+    struct Slab {
+        int g0 = 0, g1 = 0;        // the launch groups it still needs: groups [g0, g1)
+        int s0 = 0, s1 = 0;        // this rank's rows of it
+        std::vector<int> ra, rb;   // every rank's rows of it
+        int mx = 1;                // rows of its largest piece: the padding of this gather
+        int ev = 0;                // recorded behind its stitch
+    };
+    std::vector<Slab> slabs;
+};
+BandPlan band_plan(const TileGeom& g, const BandSpec& sp);
+std::string band_describe(const BandPlan& p);     // a header line, then one line per launch group and per slab, in order
+
+}  // namespace umx
+
+namespace umx_geom {   // band geometry (the C twin of unmicst_amd/sharding.py)
+void band(int npr, int world, int rank, int* pa, int* pb);
+void owned(int pa, int pb, int npr, int sub, int margin, int H, int* y0, int* y1);
+void needed(int pa, int pb, int sub, int margin, int patch, int H, int* r0, int* r1);
+int cut(int pa, int pb, int n, int i);
+void slab(int pa, int pb, int npr, int sub, int margin, int H, int n, int i, int* s0, int* s1);
+}  // namespace umx_geom
+
+namespace umx {
 
 // ---- umx_shard.hip
 void shard_release(umx_ctx* ctx);               // frees ctx->shard and its buffers in ctx->mem

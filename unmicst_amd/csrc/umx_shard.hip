@@ -169,47 +169,6 @@ void umx::shard_release(umx_ctx* ctx) {
 
 hipStream_t umx::shard_stream(const umx_ctx* ctx) { return ctx->shard ? ctx->shard->comm_stream : nullptr; }
 
-// ---- band geometry (the C twin of unmicst_amd/sharding.py: band_partition / owned_rows / needed_image_rows / slab_rows;
-// tests/test_abi.py compares the two over a grid of sizes)
-namespace umx_geom {
-
-void band(int npr, int world, int rank, int* pa, int* pb) {
-    const int active = std::min(world, npr);
-    const int base = active ? npr / active : 0, extra = active ? npr % active : 0;
-    int start = 0;
-    for (int r = 0; r <= rank; ++r) {
-        const int n = r < active ? base + (r < extra ? 1 : 0) : 0;
-        if (r == rank) { *pa = start; *pb = start + n; }
-        start += n;
-    }
-}
-
-void owned(int pa, int pb, int npr, int sub, int margin, int H, int* y0, int* y1) {
-    if (pa >= pb) { *y0 = *y1 = 0; return; }
-    *y0 = pa == 0 ? 0 : std::min(H, std::max(0, pa * sub - margin));
-    *y1 = pb == npr ? H : std::min(H, std::max(0, pb * sub - margin));
-}
-
-void needed(int pa, int pb, int sub, int margin, int patch, int H, int* r0, int* r1) {
-    if (pa >= pb) { *r0 = *r1 = 0; return; }
-    *r0 = std::max(0, pa * sub - margin);
-    *r1 = std::min(H, (pb - 1) * sub + patch - margin);
-}
-
-int cut(int pa, int pb, int n, int i) { return pa + (int)(((long long)(pb - pa) * i) / n); }
-
-void slab(int pa, int pb, int npr, int sub, int margin, int H, int n, int i, int* s0, int* s1) {
-    if (pa >= pb) { *s0 = *s1 = 0; return; }
-    int y0, y1;
-    owned(pa, pb, npr, sub, margin, H, &y0, &y1);
-    const int a = i == 0 ? y0 : std::min(y1, std::max(y0, cut(pa, pb, n, i) * sub - margin));
-    const int b = i == n - 1 ? y1 : std::min(y1, std::max(y0, cut(pa, pb, n, i + 1) * sub - margin));
-    *s0 = a;
-    *s1 = std::max(a, b);
-}
-
-}  // namespace umx_geom
-
 extern "C" {
 
 int umx_shard_unique_id(umx_unique_id* out) {
@@ -289,6 +248,35 @@ int umx_shard_plan(const umx_hparams* hpp, int H, int W, int rank, int world, in
     return UMX_OK;
 }
 
+// The schedule of one rank's band on the host alone (no device, no communicator): band_describe of the plan sharded_run would
+// execute -- stitch: UMX_STITCH_*; u8: the uint8 result is gathered; staged / own_stream: a host band goes up piece by piece, on a
+// stream of its own.  *needed: bytes of the text with its terminator; UMX_ERR_INVALID where cap is smaller.
+int umx_test_band_plan(const umx_hparams* hp, int H, int W, int world, int rank, int nslabs, int max_batch, int band_row0, int band_rows,
+                       int stitch, int u8, int staged, int own_stream, char* text, size_t cap, size_t* needed) {
+    if (!hp || !needed || (!text && cap)) return fail(nullptr, UMX_ERR_INVALID, "umx_test_band_plan: null argument");
+    *needed = 0;
+    std::string why;
+    if (const int rc = check_hp(hp, &why)) return fail(nullptr, rc, "%s", why.c_str());
+    if (H < 1 || W < 1 || world < 1 || rank < 0 || rank >= world || max_batch < 1 || band_row0 < 0 || band_rows < 0 || band_row0 + band_rows > H)
+        return fail(nullptr, UMX_ERR_INVALID, "umx_test_band_plan: bad H / W / rank / world / max_batch / band");
+    BandSpec sp;
+    sp.world = world;
+    sp.rank = rank;
+    sp.nslabs = nslabs;
+    sp.max_batch = max_batch;
+    sp.band_row0 = band_row0;
+    sp.band_rows = band_rows;
+    sp.K = hp->nClasses;
+    sp.gather_el = u8 ? 1 : stitch == UMX_STITCH_FP32 ? 4 : 2;
+    sp.staged = staged != 0;
+    sp.own_stream = own_stream != 0;
+    const std::string out = band_describe(band_plan(geom_of(*hp, H, W), sp));
+    *needed = out.size() + 1;
+    if (cap < *needed) return fail(nullptr, UMX_ERR_INVALID, "umx_test_band_plan: the text takes %zu bytes", *needed);
+    memcpy(text, out.c_str(), *needed);
+    return UMX_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -346,6 +334,9 @@ int shard_drain(umx_ctx* ctx, int rc) {
     return rc;
 }
 
+// The executor of a band's schedule (band_plan, umx_pipeline.hip): the buffers sized from the plan, the events, then its launch groups
+// and slabs in order on the context's stream `cs`, with the halo exchange, the gathers and the scatter copies on the communication
+// stream `ms`.
 int sharded_run(umx_ctx* ctx, const RunIO& io, int C_img, int H, int W, int band_row0, int band_rows, double mean, double stdv, int mode,
                 int stitch, int nslabs) {
     Shard& s = *ctx->shard;
@@ -357,153 +348,98 @@ int sharded_run(umx_ctx* ctx, const RunIO& io, int C_img, int H, int W, int band
     } while (0)
     hipStream_t cs = ctx->stream, ms = s.comm_stream;
     const TileGeom g = geom_of(ctx->hp, H, W);
-    const int npr = g.npr, npc = g.npc, P = g.P, K = ctx->hp.nClasses, margin = g.margin, sub = g.sub;
+    const int K = ctx->hp.nClasses, world = s.world, slot = io.slot;
+    BandSpec sp;
+    sp.world = world;
+    sp.rank = s.rank;
+    sp.nslabs = nslabs;
+    sp.max_batch = ctx->max_batch;
+    sp.band_row0 = band_row0;
+    sp.band_rows = band_rows;
+    sp.K = K;
+    const size_t el = sp.gather_el = io.u8 ? 1 : stitch == UMX_STITCH_FP32 ? 4 : 2;   // element that is gathered (uint8: cast in the stitch)
+    sp.staged = io.band_host != nullptr;
+    sp.own_stream = io.up_s != cs;
+    const BandPlan p = band_plan(g, sp);
+    const int n = p.n;
     int rc;
-    const size_t sel = stitch == UMX_STITCH_FP32 ? 4 : 2;   // element of the stitched slab
-    const size_t el = io.u8 ? 1 : sel;                      // element that is gathered
-    const int world = s.world, rank = s.rank, slot = io.slot;
-    std::vector<int> A(world), B(world);
-    std::vector<int> active;
-    int n = std::max(1, nslabs);
-    for (int q = 0; q < world; ++q) {
-        umx_geom::band(npr, world, q, &A[q], &B[q]);
-        if (B[q] > A[q]) { active.push_back(q); n = std::min(n, B[q] - A[q]); }
+    // every buffer is sized before anything is enqueued (a grow() between enqueued collectives would synchronise the device and free
+    // memory under them when a later slide is larger); the gather buffers hold the largest slab, [K][mx_all][W] per rank
+    if ((rc = grow(ctx, &s.probs, &s.probs_cap, p.probs_b, "shard probs", true))) return rc;
+    std::vector<void*>& send = s.send[slot];
+    if ((int)send.size() < n) { send.resize(n); s.send_cap[slot].resize(n); }
+    if ((rc = grow(ctx, &s.gathered[slot], &s.gathered_cap[slot], p.gathered_b, slot ? "shard gathered[1]" : "shard gathered[0]", true))) return rc;
+    for (int i = 0; i < n; ++i) {
+        const std::string label = "shard send[" + std::to_string(slot) + "][" + std::to_string(i) + "]";
+        if ((rc = grow(ctx, &send[i], &s.send_cap[slot][i], p.send_b, label.c_str(), true))) return rc;
     }
-    n = std::max(1, n);
-    const int pa = A[rank], pb = B[rank];
-    const bool has_prev = pa < pb && pa > 0, has_next = pa < pb && pb < npr;
-    const int lo = has_prev ? pa - 1 : pa;
-    const size_t tile_f = (size_t)P * P * K, row_f = tile_f * npc;
-    if ((rc = grow(ctx, &s.probs, &s.probs_cap, std::max<size_t>(1, (size_t)std::max(pb - lo, 0)) * row_f * sizeof(float), "shard probs", true))) return rc;
     float* const probs = (float*)s.probs;
     std::vector<hipEvent_t>& evs = s.events[slot];
-    const int nev = 6 + 4 * n;
-    while ((int)evs.size() < nev) {
+    while ((int)evs.size() < p.nev) {
         hipEvent_t e;
         HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         evs.push_back(e);
     }
     hipEvent_t ev_in = evs[0], ev_last = evs[1], ev_halo = evs[2], ev_done = evs[3], ev_end = evs[4];
-    // the communication stream starts behind whatever the caller queued on the context's stream
-    HIP_TRY(ctx, hipEventRecord(ev_in, cs));
-    HIP_TRY(ctx, hipStreamWaitEvent(ms, ev_in, 0));
-    // staged upload of a raw band: the rows of the band's LAST patch row go first (its tiles run first), then the rows of the slabs
-    // from the top; what is up = [band_row0, head) and [tail, band end)
-    const int band_end = band_row0 + band_rows;
-    int head = band_row0, tail = band_end, nup = 0;
     const size_t in_b = io.raw_bits ? (size_t)io.raw_bits / 8 : sizeof(double);
-    auto stage = [&](int pr0, int pr1) -> int {
-        if (!io.band_host || pr1 <= pr0) return UMX_OK;
-        int a = std::max(band_row0, std::max(0, pr0 * sub - margin)), b = std::min(band_end, std::min(H, (pr1 - 1) * sub + P - margin));
-        a = std::max(a, head);
-        b = std::min(b, tail);
-        if (b <= a) return UMX_OK;
-        if (a > head && b < tail) a = head;          // (never with this schedule: keep the two intervals contiguous anyway)
-        for (int c = 0; c < C_img; ++c) {
-            const size_t off = ((size_t)c * band_rows + (a - band_row0)) * W * in_b;
-            HIP_TRY(ctx, hipMemcpyAsync((unsigned char*)io.raw_dev + off, (const unsigned char*)io.band_host + off, (size_t)(b - a) * W * in_b,
-                                      hipMemcpyHostToDevice, io.up_s));
-        }
-        if (a == head) head = b; else tail = a;
-        if (io.up_s != cs) {
-            hipEvent_t e = evs[6 + 2 * n + std::min(nup++, 2 * n - 1)];
-            HIP_TRY(ctx, hipEventRecord(e, io.up_s));
-            HIP_TRY(ctx, hipStreamWaitEvent(cs, e, 0));
+    const size_t tile_f = (size_t)g.P * g.P * K, row_f = tile_f * g.npc;
+    // launch groups [g0, g1): each one's staged rows of the host band (if any), then its tiles -> their place in `probs` (patch row lo first)
+    auto groups = [&](int g0, int g1) -> int {
+        for (int i = g0; i < g1; ++i) {
+            const BandPlan::Group& G = p.groups[i];
+            for (int c = 0; c < C_img && G.r1 > G.r0; ++c) {
+                const size_t off = ((size_t)c * band_rows + (G.r0 - band_row0)) * W * in_b;
+                HIP_TRY(ctx, hipMemcpyAsync((unsigned char*)io.raw_dev + off, (const unsigned char*)io.band_host + off, (size_t)(G.r1 - G.r0) * W * in_b,
+                                          hipMemcpyHostToDevice, io.up_s));
+            }
+            if (G.ev >= 0) {
+                HIP_TRY(ctx, hipEventRecord(evs[G.ev], io.up_s));
+                HIP_TRY(ctx, hipStreamWaitEvent(cs, evs[G.ev], 0));
+            }
+            if ((rc = tiles_range(ctx, io.raw_dev ? nullptr : io.band_f64, C_img, g, band_row0, band_rows, mean, stdv, G.t0, G.t1,
+                                  probs + ((size_t)G.t0 - (size_t)p.lo * g.npc) * tile_f, io.raw_dev, io.raw_bits, io.mm)))
+                return rc;
         }
         return UMX_OK;
     };
-    // tiles [t0, t1) of the slide (row-major tile index) -> their place in `probs` (tile lo * npc first)
-    auto tiles = [&](int t0, int t1) -> int {
-        if (t1 <= t0) return UMX_OK;
-        if ((rc = stage(t0 / g.npc, (t1 - 1) / g.npc + 1))) return rc;
-        float* const dst = probs + (size_t)(t0 - lo * g.npc) * tile_f;
-        return tiles_range(ctx, io.raw_dev ? nullptr : io.band_f64, C_img, g, band_row0, band_rows, mean, stdv, t0, t1, dst, io.raw_dev,
-                                io.raw_bits, io.mm);
-    };
-    // Launch groups.  The next rank waits for this band's LAST patch row, so it is computed first -- but not as a launch group of
-    // its own (86 tiles of the 16384-wide slide fill a third of the chip's workgroup slots on the deep layers and still cost every
-    // layer a generation): the first group is the band's last F tiles, F = the remainder of the band's tile count over the launch
-    // group size (raised by whole groups until it holds the last row), and every later group is a full one, whatever slab it
-    // belongs to.  11 patch rows of 86 tiles at 256 per group: 178 + 3 x 256 instead of 86 + 4 x 215 -- the same number of
-    // workgroup generations as an unsharded band.  The last band (nobody waits) runs in order.
-    const int Bt = std::max(1, ctx->max_batch), T0 = pa * g.npc, T1 = pb * g.npc;
-    int F = 0;
-    if (has_next) {
-        F = (T1 - T0) % Bt;
-        while (F < g.npc) F += Bt;
-        F = std::min(F, T1 - T0);
-    }
-    if ((rc = tiles(T1 - F, T1))) return rc;
-    int done = T0;   // tiles [T0, done) and [T1 - F, T1) are enqueued
+    // the communication stream starts behind whatever the caller queued on the context's stream
+    HIP_TRY(ctx, hipEventRecord(ev_in, cs));
+    HIP_TRY(ctx, hipStreamWaitEvent(ms, ev_in, 0));
+    // the band's last tiles first: the next rank waits for their patch row
+    if ((rc = groups(0, p.slabs[0].g0))) return rc;
     HIP_TRY(ctx, hipEventRecord(ev_last, cs));
     HIP_TRY(ctx, hipStreamWaitEvent(ms, ev_last, 0));
-    if (has_next || has_prev) {
-        const int me = (int)(std::find(active.begin(), active.end(), rank) - active.begin());
+    if (p.send_peer >= 0 || p.recv_peer >= 0) {
         if (tp.group_start) S_TP(ctx, tp.group_start(tp.user));
-        if (has_next) S_TP(ctx, tp.send(tp.user, probs + (size_t)(pb - 1 - lo) * row_f, row_f * sizeof(float), active[me + 1], ms));
-        if (has_prev) S_TP(ctx, tp.recv(tp.user, probs, row_f * sizeof(float), active[me - 1], ms));
+        if (p.send_peer >= 0) S_TP(ctx, tp.send(tp.user, probs + (size_t)(p.pb - 1 - p.lo) * row_f, row_f * sizeof(float), p.send_peer, ms));
+        if (p.recv_peer >= 0) S_TP(ctx, tp.recv(tp.user, probs, row_f * sizeof(float), p.recv_peer, ms));
         if (tp.group_end) S_TP(ctx, tp.group_end(tp.user));
     }
     HIP_TRY(ctx, hipEventRecord(ev_halo, ms));
-    std::vector<void*>& send = s.send[slot];
-    if ((int)send.size() < n) { send.resize(n); s.send_cap[slot].resize(n); }
-    int own0 = 0, own1 = 0;
-    umx_geom::owned(pa, pb, npr, sub, margin, H, &own0, &own1);
-    {   // size the gather buffers for the largest slab up front (no reallocation between enqueued operations: a grow() in the slab loop
-        // would synchronise the device and free memory between enqueued collectives when a later slide is larger).  The stitch writes
-        // straight into the padded send buffer [K][mx][W]; the padded tails stay uninitialised: the scatter never reads them.
-        int mx_all = 1;
-        for (int i = 0; i < n; ++i)
-            for (int q = 0; q < world; ++q) {
-                int a, b;
-                umx_geom::slab(A[q], B[q], npr, sub, margin, H, n, i, &a, &b);
-                mx_all = std::max(mx_all, b - a);
-            }
-        if ((rc = grow(ctx, &s.gathered[slot], &s.gathered_cap[slot], (size_t)world * K * mx_all * W * el,
-                       slot ? "shard gathered[1]" : "shard gathered[0]", true)))
-            return rc;
-        for (int i = 0; i < n; ++i) {
-            const std::string label = "shard send[" + std::to_string(slot) + "][" + std::to_string(i) + "]";
-            if ((rc = grow(ctx, &send[i], &s.send_cap[slot][i], (size_t)K * mx_all * W * el, label.c_str(), true))) return rc;
-        }
-    }
     for (int i = 0; i < n; ++i) {
-        // the launch groups slab i still lacks: every tile of the patch rows below its last image row (full groups: one may run into the next slab)
-        const int need = pa < pb ? std::min(umx_geom::cut(pa, pb, n, i + 1) * g.npc, T1 - F) : T0;
-        while (done < need) {
-            const int t1 = std::min(done + Bt, T1 - F);
-            if ((rc = tiles(done, t1))) return rc;
-            done = t1;
-        }
+        const BandPlan::Slab& sl = p.slabs[i];
+        if ((rc = groups(sl.g0, sl.g1))) return rc;
         if (i == 0) HIP_TRY(ctx, hipStreamWaitEvent(cs, ev_halo, 0));   // the previous rank's last patch row feeds this band's first rows
-        int s0, s1;
-        umx_geom::slab(pa, pb, npr, sub, margin, H, n, i, &s0, &s1);
-        std::vector<int> ra(world), rb(world);
-        int mx = 1;
-        for (int q = 0; q < world; ++q) {
-            umx_geom::slab(A[q], B[q], npr, sub, margin, H, n, i, &ra[q], &rb[q]);
-            mx = std::max(mx, rb[q] - ra[q]);
-        }
-        const size_t plane_b = (size_t)mx * W * el, send_b = (size_t)K * plane_b;
-        // straight into the padded gather buffer [K][mx][W] (uint8 path: the drivers' cast rides in the stitch)
-        if (s1 > s0 && (rc = stitch_rows(ctx, probs, lo, pb, H, W, mode, io.u8 ? kStitchU8 : stitch, s0, s1, send[i], mx))) return rc;
-        hipEvent_t ev_s = evs[6 + 2 * i];
+        const size_t plane_b = (size_t)sl.mx * W * el, send_b = (size_t)K * plane_b;
+        // straight into the padded gather buffer [K][mx][W] (the padded tails stay uninitialised: the scatter never reads them)
+        if (sl.s1 > sl.s0 && (rc = stitch_rows(ctx, probs, p.lo, p.pb, H, W, mode, io.u8 ? kStitchU8 : stitch, sl.s0, sl.s1, send[i], sl.mx))) return rc;
+        hipEvent_t ev_s = evs[sl.ev];
         HIP_TRY(ctx, hipEventRecord(ev_s, cs));
         HIP_TRY(ctx, hipStreamWaitEvent(ms, ev_s, 0));
-        if (io.own_host && s1 > s0) {   // this rank's rows of the slab: down to the host under the next slab's tiles
+        if (io.own_host && sl.s1 > sl.s0) {   // this rank's rows of the slab: down to the host under the next slab's tiles
             if (io.dn_s != cs) HIP_TRY(ctx, hipStreamWaitEvent(io.dn_s, ev_s, 0));
-            const size_t own_rows = (size_t)(own1 - own0);
+            const size_t own_rows = (size_t)(p.own1 - p.own0);
             for (int k = 0; k < K; ++k)
-                HIP_TRY(ctx, hipMemcpyAsync(io.own_host + ((size_t)k * own_rows + (size_t)(s0 - own0)) * W, (char*)send[i] + k * plane_b,
-                                          (size_t)(s1 - s0) * W, hipMemcpyDeviceToHost, io.dn_s));
+                HIP_TRY(ctx, hipMemcpyAsync(io.own_host + ((size_t)k * own_rows + (size_t)(sl.s0 - p.own0)) * W, (char*)send[i] + k * plane_b,
+                                          (size_t)(sl.s1 - sl.s0) * W, hipMemcpyDeviceToHost, io.dn_s));
         }
         // (one gather buffer per slot, reused slab after slab: gather i+1 is queued behind the scatter copies of gather i)
         S_TP(ctx, tp.all_gather(tp.user, send[i], s.gathered[slot], send_b, ms));
         for (int q = 0; q < world; ++q)
-            for (int k = 0; k < K && rb[q] > ra[q]; ++k)
-                HIP_TRY(ctx, hipMemcpyAsync((char*)io.out_full + ((size_t)k * H + ra[q]) * W * el,
+            for (int k = 0; k < K && sl.rb[q] > sl.ra[q]; ++k)
+                HIP_TRY(ctx, hipMemcpyAsync((char*)io.out_full + ((size_t)k * H + sl.ra[q]) * W * el,
                                           (char*)s.gathered[slot] + (size_t)q * send_b + k * plane_b,
-                                          (size_t)(rb[q] - ra[q]) * W * el, hipMemcpyDeviceToDevice, ms));
+                                          (size_t)(sl.rb[q] - sl.ra[q]) * W * el, hipMemcpyDeviceToDevice, ms));
     }
     HIP_TRY(ctx, hipEventRecord(ev_done, ms));
     if (io.join) HIP_TRY(ctx, hipStreamWaitEvent(cs, ev_done, 0));   // the result is complete for whatever the caller queues next

@@ -32,7 +32,7 @@ EXPORTS = [
     "umx_infer_image_sharded_dev", "umx_infer_image_sharded_raw", "umx_infer_image_sharded_raw_submit",
     "umx_band_tiles_dev", "umx_stitch_dev", "umx_profile_enable", "umx_profile_read", "umx_prof_entry_size", "umx_test_double_to_half", "umx_test_double_to_half_dev",
     "umx_test_gauss_weights", "umx_test_resize_dev", "umx_test_rescale_dev", "umx_test_plane_range_dev", "umx_test_half_to_u8_dev",
-    "umx_describe", "umx_describe_graph", "umx_plan_check", "umx_test_wgrad_plan", "umx_test_train_plan", "umx_test_mx_pack_e2m3", "umx_version",
+    "umx_describe", "umx_describe_graph", "umx_plan_check", "umx_test_wgrad_plan", "umx_test_train_plan", "umx_test_slide_plan", "umx_test_band_plan", "umx_test_mx_pack_e2m3", "umx_version",
     "umx_label_options_check", "umx_labeler_create", "umx_labeler_destroy", "umx_labeler_last_error", "umx_labeler_run",
     "umx_labeler_run_dev", "umx_labeler_objects", "umx_labeler_last_ms",
     "umx_label_measure_check", "umx_labeler_measure", "umx_labeler_measure_dev", "umx_labeler_measure_last_ms",
@@ -406,6 +406,39 @@ def train_plan(hp, batch: int, blob, conv_f32: bool = False, no_ksplit: bool = F
         rc = fn(*args, buf, len(buf), ctypes.byref(need))
     _check(L, rc)
     return buf.value.decode().splitlines()
+
+
+def _plan_text(fn, argtypes, args):
+    """a host-only test entry that writes text into (buffer, capacity, needed): its lines"""
+    fn.restype = ctypes.c_int
+    fn.argtypes = argtypes + [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    buf = ctypes.create_string_buffer(1 << 14)
+    need = ctypes.c_size_t(0)
+    rc = fn(*args, buf, len(buf), ctypes.byref(need))
+    if rc and need.value > len(buf):
+        buf = ctypes.create_string_buffer(need.value)
+        rc = fn(*args, buf, len(buf), ctypes.byref(need))
+    _check(load(), rc)
+    return buf.value.decode().splitlines()
+
+
+def slide_plan(hp, H: int, W: int, max_batch: int, C_img: int, src_bits: int = 0, rescale: bool = False, has_range: bool = False,
+               sync_call: bool = True, host_range_ok: bool = True, raw_gather: bool = False, stitch: int = 0, out_u8: bool = False,
+               tile_flops: float = 0.0):
+    """umx_test_slide_plan: the schedule of a whole-slide call on one GPU -- a header line, then one line per step.  Host only."""
+    hps = _hp_struct(hp)
+    return _plan_text(load().umx_test_slide_plan, [ctypes.c_void_p] + [ctypes.c_int] * 12 + [ctypes.c_double],
+                      (ctypes.byref(hps), H, W, max_batch, C_img, src_bits, int(rescale), int(has_range), int(sync_call), int(host_range_ok),
+                       int(raw_gather), stitch, int(out_u8), float(tile_flops)))
+
+
+def band_plan(hp, H: int, W: int, world: int, rank: int, nslabs: int, max_batch: int, band_row0: int, band_rows: int, stitch: int = 0,
+              u8: bool = False, staged: bool = False, own_stream: bool = False):
+    """umx_test_band_plan: the schedule of one rank's band of a sharded slide -- a header line, then one line per launch group and per
+    slab.  Host only."""
+    hps = _hp_struct(hp)
+    return _plan_text(load().umx_test_band_plan, [ctypes.c_void_p] + [ctypes.c_int] * 12,
+                      (ctypes.byref(hps), H, W, world, rank, nslabs, max_batch, band_row0, band_rows, stitch, int(u8), int(staged), int(own_stream)))
 
 
 def auto_batch(hp: HParams, arena_bytes: float = 12 * 2 ** 30) -> int:
