@@ -463,6 +463,16 @@ UMX_API int umx_test_mx_pack_e2m3(const double* v32, uint8_t* out24);
  * refused layer and the split-precision planner's reason in umx_last_error(NULL) -- what UMX_PREC_DEFAULT falls back to the exact-fp32
  * engine on (and warns about). */
 UMX_API int umx_plan_check(const umx_hparams* hp);
+/* test entry (host only): the split-precision plan umx_create would make of this model (f6: UMX_PREC_F16X3_F6) under the planner's
+ * switches given as arguments, not through the environment -- nt, override_list, stamps: what UMX_PLAN_NT, UMX_PLAN_OVERRIDE and
+ * UMX_DEBUG_STAMPS would hold (NULL or "": not set), threads: UMX_PLAN_THREADS (0: default).  text receives one line per launch but the
+ * softmax head: its UMX_DEBUG_PLAN text, the kernel instantiation, the destination buffer's layout, the N-tiles per workgroup, the weight
+ * shift, a 64-bit FNV-1a digest of everything the upload would send and, for each of the nbatches batch sizes n (1 .. 4096),
+ * "n:<workgroup order>/<tiles per XCD>" as a launch on n tiles would choose them.  *needed: the text's bytes with the terminator (set
+ * even where cap is too small: UMX_ERR_INVALID).  A model the planner refuses: its code, the layer and reason in umx_last_error(NULL). */
+UMX_API int umx_test_infer_plan(const umx_hparams* hp, int f6, int act_shift, const float* blob, size_t blob_floats, const char* nt,
+                                const char* override_list, const char* stamps, int threads, const int* batches, int nbatches, char* text,
+                                size_t cap, size_t* needed);
 /* test entry (host only): the trainer's weight-gradient planner and kernel selection on one layer -- batch B, H x H pixels, X with Cxt
  * channels per pixel of which each slab reads Cx from channel coff[s], G with Cg channels, nslab slabs (dy, dx: tap offset, mslab: tap of
  * the master tensor); f32_route: as under UMX_TRAIN_WGRAD_F32; planes / XCs / GCs: whether the operands come with (hi, lo) planes and

@@ -7,6 +7,8 @@ FUSED_HEAD, FUSED_CONVT, FIRST, FOLD, CONVT3, NT_TRIAL, D2S_SKIP, D2S, PACKED_TI
 forms they selected are still reached by shape (tests/test_gpu_parity.py's graphs, D2S_SHAPES below: fused-phase, per-phase and
 depth-to-space transposed convolutions; packed and plain last N-tiles; dense-K and generic first layers) and every one is held
 to the oracle there.  What is left: precision, activation headroom, and the planner's debug overrides."""
+import re
+
 import numpy as np
 import pytest
 
@@ -28,6 +30,7 @@ SWITCHES = [
     {"UMX_PLAN_NT": "lu2.convT:4"},         # forced N-tiles per workgroup of one layer (here 8 padded N-tiles in two blocks instead of 7 in one)
     {"UMX_PRECISION": "f32"},               # default precision from the environment
     {"UMX_ACT_SHIFT": "2"},                 # activations stored times 4
+    {"UMX_DEBUG_STAMPS": "lu0.conv"},       # the diagnostic launch of one layer (no layer of the model takes the packed or fp6 form then)
 ]
 
 
@@ -71,10 +74,30 @@ def _kernels_run(eng, x, key="kernel"):
     return {p["name"]: p[key] for p in prof if p["kernel"].startswith("conv_f16x3")}
 
 
+def _planned_orders(hp, blob, n):
+    """layer -> the workgroup order of its launch on n tiles, from the host plan alone (umx.infer_plan, as the default engine plans)"""
+    return {ln.split()[2]: int(re.search(r" %d:(\d)/\d+$" % n, ln).group(1)) for ln in umx.infer_plan(hp, True, 0, blob, batches=(n,))}
+
+
+def test_stamps_diagnostic_prints_one_line_per_launch_of_its_layer(reference, monkeypatch, capfd):
+    """UMX_DEBUG_STAMPS=<layer>: that layer's launches go through the diagnostic path -- 5 tiles in launch groups of 3 are two launches,
+    two "[umx stamps]" lines -- and compute what they compute without it."""
+    blob, x, img, ref = reference
+    monkeypatch.setenv("UMX_DEBUG_STAMPS", "lu0.conv")
+    with umx.Engine(HP, blob, max_batch=3) as eng:
+        capfd.readouterr()
+        got = eng.forward_tiles(x)
+        err = capfd.readouterr().err
+    assert np.abs(got - ref).max() <= TILE_TOL
+    stamps = [ln for ln in err.splitlines() if ln.startswith("[umx stamps]")]
+    assert len(stamps) == 2 and all(ln.startswith("[umx stamps] lu0.conv: ") for ln in stamps), err
+
+
 def test_workgroup_order_2_is_chosen_by_rule(reference):
     """Workgroup order 2 ((N-block, phase) fastest inside an XCD) is taken per launch where the rule of run_launch_f16 asks for it
     -- plain convolutions of 2 - 4 N-blocks and halo-bound many-block layers on >= 64 tiles -- and nowhere on a handful of tiles;
-    the profile entry carries the order a site's last launch used, and the results do not depend on it."""
+    the profile entry carries the order a site's last launch used, and the results do not depend on it.  The order every launch ran in
+    is the one the host plan gives for its batch (launch_shape through umx.infer_plan: tests/test_infer_plan_cpu.py pins that table)."""
     blob, x, img, ref = reference
     hp = model.HParams(model.GRAPH_V2, 32, 2, 3, 40, 3, 3, 0, 2)      # 160 / 320 output channels: layers of 2 and 3 N-blocks
     b2 = model.random_blob(hp, seed=2)
@@ -83,11 +106,16 @@ def test_workgroup_order_2_is_chosen_by_rule(reference):
     many[:5] = few
     with umx.Engine(hp, b2, max_batch=5) as eng:
         small = eng.forward_tiles(few)
-        assert 2 not in _kernels_run(eng, few, "xcd_order").values()     # (5 tiles: below the rule's 64)
+        orders = _kernels_run(eng, few, "xcd_order")
+        assert 2 not in orders.values()     # (5 tiles: below the rule's 64)
+    planned = _planned_orders(hp, b2, 5)
+    assert orders and orders == {name: planned[name] for name in orders}
     with umx.Engine(hp, b2, max_batch=320) as eng:
         big = eng.forward_tiles(many)
         orders = _kernels_run(eng, many, "xcd_order")
     assert sum(1 for o in orders.values() if o == 2) >= 2, orders
+    planned = _planned_orders(hp, b2, 320)
+    assert orders == {name: planned[name] for name in orders}
     assert np.array_equal(big[:5], small)
 
 
@@ -95,8 +123,12 @@ def test_two_lanes_option_equals_one_lane(reference):
     """umx_options.lanes = 2: tile batches alternate between two activation arenas on two streams; same launches, same bits."""
     blob, x, img, ref = reference
     with umx.Engine(HP, blob, max_batch=2, lanes=1) as e1, umx.Engine(HP, blob, max_batch=2, lanes=2) as e2:
+        e1.profile_enable(1)
+        e2.profile_enable(1)
         a, b = e1.forward_tiles(x), e2.forward_tiles(x)
         pa, pb = e1.infer_image(img, 0.3, 0.2), e2.infer_image(img, 0.3, 0.2)
+        s1, s2 = ([(p["name"], p["kernel"]) for p in e.profile_read()] for e in (e1, e2))
+    assert s1 and s1 == s2   # (the same sites in the same order of first use: the lane is no part of a site)
     assert np.array_equal(a, b) and np.abs(a - ref).max() <= TILE_TOL
     assert np.array_equal(pa.view(np.uint16), pb.view(np.uint16))
 

@@ -92,52 +92,44 @@ int prof_fold(umx_ctx* ctx) {
     return UMX_OK;
 }
 
-// run the UNet on n tiles already in bufs[0] layout at `tiles` -> probs
-// the (hi, lo) planes of buffer b for a batch of n tiles
-// One launch of the split-precision plan on tiles [k0, k0+ns) of a batch of n: every tensor lives in its full-batch
-// buffer (hi plane of n tiles, then lo plane of n tiles), a sub-batch is a slice of both planes.
-int run_launch_f16(umx_ctx* ctx, Launch& L, const float* tiles, int n, int k0, int ns, float* probs) {
-    auto hi_at = [&](const Buffer& b) { return hi_of(b) + (size_t)k0 * b.S * b.S * b.Cs; };
-    auto lo_at = [&](const Buffer& b) { return lo_of(b, n) + (size_t)k0 * b.S * b.S * b.Cs; };
-    if (L.name == "input.split") {   // fp32 tiles -> (hi, lo) input planes (2 -> 8 channels, scaled by 2^act_shift)
-        if (!tiles) return UMX_OK;   // the gather kernel already wrote the (hi, lo) planes
-        const Buffer& b0 = cur_bufs(ctx)[0];
-        if (ctx->site_split < 0) ctx->site_split = site_of(ctx, "input.split", "split_f32");
-        ProfScope ps(ctx, ctx->site_split, 0.0, (double)ns * b0.S * b0.S * (4.0 * b0.C + 4.0 * b0.Cs));
-        _Float16* const chi = ctx->in_cw ? reinterpret_cast<_Float16*>(b0.d) + (size_t)k0 * b0.S * b0.S * 2 * ctx->in_cw : hi_at(b0);
-        HIP_TRY(ctx, launch_split_f32(tiles + (size_t)k0 * b0.floats_per_tile, (size_t)ns * b0.S * b0.S, b0.C, b0.Cs,
-                                      std::ldexp(1.f, ctx->act_shift), chi, lo_at(b0), ctx->in_cw, run_stream(ctx)));
-        return UMX_OK;
-    }
-    if (L.head) {
-        if (ctx->head_fused) return UMX_OK;   // computed in the epilogue of the last convolution
-        const Buffer& sb = cur_bufs(ctx)[L.g[0].src];
-        const size_t npix = (size_t)ns * L.H * L.W;
-        ProfScope ps(ctx, site_of(ctx, L.name, "head_softmax"), L.flops * ns, L.bytes * ns);
-        HIP_TRY(ctx, launch_head_softmax(sb.d + (size_t)k0 * sb.floats_per_tile, npix, L.head_C, L.head_K, L.d_head_w,
-                                         L.d_pre_s, L.d_pre_b, probs + (size_t)k0 * L.H * L.W * L.head_K, run_stream(ctx)));
-        return UMX_OK;
-    }
-    HConvParams p = L.hcp;
-    p.B = ns;
+// ---- one launch group of n tiles on a lane: every tensor lives in the lane's full-batch buffer (hi plane of n tiles, then lo plane
+// of n tiles -- lo_of(b, n) moves with n, so operands are bound per launch)
+
+// fp32 tiles -> (hi, lo) input planes (2 -> 8 channels, scaled by 2^act_shift)
+int run_input_split(umx_ctx* ctx, const Lane& lane, const float* tiles, int n) {
+    if (!tiles) return UMX_OK;   // the gather kernel already wrote the (hi, lo) planes
+    const Buffer& b0 = (*lane.bufs)[0];
+    if (ctx->site_split < 0) ctx->site_split = site_of(ctx, "input.split", "split_f32");
+    ProfScope ps(ctx, lane.stream, ctx->site_split, 0.0, (double)n * b0.S * b0.S * (4.0 * b0.C + 4.0 * b0.Cs));
+    HIP_TRY(ctx, launch_split_f32(tiles, (size_t)n * b0.S * b0.S, b0.C, b0.Cs, std::ldexp(1.f, ctx->act_shift), hi_of(b0), lo_of(b0, n),
+                                  ctx->in_cw, lane.stream));
+    return UMX_OK;
+}
+
+// the operands of launch L on n tiles of the lane -> *p: sources, destination, the appended raw skip
+int bind_f16(umx_ctx* ctx, const Lane& lane, const Launch& L, int n, float* probs, HConvParams* out) {
+    const std::vector<Buffer>& bufs = *lane.bufs;
+    HConvParams& p = *out;
+    p = L.hcp;
+    p.B = n;
     p.overflow_flag = ctx->d_flag + ctx->flag_word;
     for (int gi = 0; gi < L.ngroups; ++gi) {
-        const Buffer& sb = cur_bufs(ctx)[L.g[gi].src];
-        p.src_hi[gi] = hi_at(sb);
-        p.src_lo[gi] = lo_at(sb);
+        const Buffer& sb = bufs[L.g[gi].src];
+        p.src_hi[gi] = hi_of(sb);
+        p.src_lo[gi] = lo_of(sb, n);
         p.Cs[gi] = sb.Cs;
         p.srcA[gi] = sb.planar ? 16 : sb.Cs * 2;
         p.srcB[gi] = sb.planar ? sb.S * sb.S * 16 : 16;
     }
     if (L.ngroups < 2) { p.srcA[1] = p.srcA[0]; p.srcB[1] = p.srcB[0]; }
-    const Buffer& db = cur_bufs(ctx)[L.dst];
-    if (p.head_K > 0) p.probs = probs + (size_t)k0 * L.H * L.W * p.head_K;   // fused softmax head
-    else if (db.as_f32) p.dst_f32 = db.d + (size_t)k0 * db.floats_per_tile;
-    else { p.dst_hi = hi_at(db); p.dst_lo = lo_at(db); p.dst_planar = db.planar ? 1 : 0; }
+    const Buffer& db = bufs[L.dst];
+    if (p.head_K > 0) p.probs = probs;   // fused softmax head
+    else if (db.as_f32) p.dst_f32 = db.d;
+    else { p.dst_hi = hi_of(db); p.dst_lo = lo_of(db, n); p.dst_planar = db.planar ? 1 : 0; }
     if (L.app_src >= 0) {   // the raw-input skip rides in the spare channels of this launch's output (Launch::app_src)
-        const Buffer& ab = cur_bufs(ctx)[L.app_src];
+        const Buffer& ab = bufs[L.app_src];
         if (L.app_src != 0 || !ctx->in_cw) return fail(ctx, UMX_ERR_INVALID, "internal: the appended tensor is not in the compact form");
-        p.app_c = reinterpret_cast<const unsigned char*>(ab.d) + (size_t)k0 * ab.S * ab.S * 4 * ctx->in_cw;
+        p.app_c = reinterpret_cast<const unsigned char*>(ab.d);
         p.app_cw = ctx->in_cw;
         p.app_oct = L.app_c0 / 8;                 // the stored octet ...
         p.app_word = (L.app_c0 % 8) / 2;          // ... and its 32-bit word the two appended binary16 values fill
@@ -145,90 +137,73 @@ int run_launch_f16(umx_ctx* ctx, Launch& L, const float* tiles, int n, int k0, i
     for (int gi = 0; gi < L.ngroups; ++gi)
         if (L.g[gi].src == 0 && ctx->in_cw && !L.use_first)
             return fail(ctx, UMX_ERR_INVALID, "internal: %s reads the compact input tiles through the generic kernel", L.name.c_str());
-    {   // workgroup order (HConvParams::xcd_order): (N-block, phase) fastest inside an XCD for the layers that the x-fastest order
-        // makes fabric-bound -- every one of a tile's N-blocks x phases workgroups re-reads its halo, and with 16 - 64 tiles resident
-        // per XCD none of it is shared: if those bytes over the layer's matrix time (its executed FLOPs at 0.9 PFLOP/s) exceed
-        // 4 TB/s the halo goes through ONE L2 instead.  (Settled per launch: the batch decides.  The solo model's 4 x 4 ... 16 x 16
-        // pixel transposed convolutions: 5.9 - 7 TB/s, -13 ... -30 %; the 9-tile layers of the 256-pixel graph: 2.4 - 2.8 TB/s, and
-        // order 2 costs them 8 - 17 % -- their weight slabs then compete for the L2: hence a rule, not a switch -- the A/B
-        // environment variable of rounds 3-4 is retired.)
-        const int ntiles = ((ns + p.imgs - 1) / p.imgs) * p.tiles_y * p.tiles_x;
-        const int YZ = p.nblocks * (p.fused_phases ? 1 : p.nphase);
-        bool want2 = false;
-        // (plain convolutions of 2 - 4 N-blocks: the blocks of a tile share its halo through the L2 and only 2 - 4 weight slabs
-        // compete for it -- the solo model's lu1.conv / lu2.conv -9 / -7 %, the 256-pixel graph's lu3.conv / lu4.conv -2 / -1 %)
-        if (!p.fused_phases && p.nphase == 1 && YZ >= 2 && YZ <= 4 && ntiles >= 64) want2 = true;
-        if (!want2 && YZ >= 4 && ntiles >= 64) {
-            double octets = 0.0;
-            for (int gi = 0; gi < L.ngroups; ++gi) octets += (double)((L.g[gi].C + 7) / 8);
-            const double halo_bytes = 1.3 * (double)p.nhalo * octets * 32.0 * (double)ntiles * YZ;   // (1.3: 128-byte lines of short rows)
-            const double matrix_s = L.exec_flops * ns / 0.9e15;
-            want2 = matrix_s > 0.0 && halo_bytes / matrix_s > 4e12;
-        }
-        if (p.xcd_order == 1 && YZ > 1 && want2 && !p.f6) {   // (the F6 form pairs x-adjacent tiles per workgroup: order 1 only)
-            p.xcd_order = 2;
-            p.ntiles_grid = ntiles;
-            p.tiles_per_xcd = (ntiles + 7) / 8;
-        }
-    }
-    char kn[64];
-    // the instantiation as rocprofv3 names it (<NT, KMT, NPH>): bench.py groups the timed sites by kernel
-    // (<NT, KMT, NPH, DBG, MAXP, PK, D2S, F6, W2>; W2 == F6 always)
-    snprintf(kn, sizeof kn, "conv_f16x3<%d, %d, %d, false, %d, %s, %s, %s, %s>", L.nt16, p.kmt, p.fused_phases ? 4 : 1, p.maxp, p.pk ? "true" : "false",
-             p.d2s ? "true" : "false", p.f6 ? "true" : "false", p.f6 ? "true" : "false");
-    {
-        // diagnostic: UMX_DEBUG_STAMPS=<layer name> prints the mean s_memtime segments of that layer's workgroups
-        const char* const dbg_layer = getenv("UMX_DEBUG_STAMPS");
-        if (dbg_layer && L.name == dbg_layer) {
-            size_t nwg = (size_t)((ns + p.imgs - 1) / p.imgs) * p.tiles_y * p.tiles_x;
-            if (p.f6) nwg = (nwg + 1) / 2;   // (two tiles per workgroup)
-            nwg *= (size_t)p.nblocks * (p.fused_phases ? 1 : p.nphase);
-            long long* d = nullptr;
-            HIP_TRY(ctx, hipMalloc((void**)&d, nwg * 7 * sizeof(long long)));
-            p.dbg = d;
-            if (p.xcd_order == 2) p.xcd_order = 1;   // (the stamp records are indexed by the three-dimensional grid)
-            HIP_TRY(ctx, launch_conv_f16(p, run_stream(ctx)));
-            HIP_TRY(ctx, hipStreamSynchronize(run_stream(ctx)));
-            std::vector<long long> hst(nwg * 7);
-            HIP_TRY(ctx, hipMemcpy(hst.data(), d, hst.size() * sizeof(long long), hipMemcpyDeviceToHost));
-            hipFree(d);
-            double m[7] = {0, 0, 0, 0, 0, 0, 0};
-            for (size_t w = 0; w < nwg; ++w)
-                for (int k = 0; k < 7; ++k) m[k] += (double)hst[w * 7 + k] / nwg;
-            fprintf(stderr, "[umx stamps] %s: %zu workgroups, LDS %d B, wbuf %d B | shader cycles: prologue %.0f, stage waits %.0f "
-                            "(own loads %.0f, barrier %.0f), issuing the next stage's loads %.0f, MFMA blocks %.0f, epilogue %.0f, total %.0f\n",
-                    L.name.c_str(), nwg, p.lds_bytes, p.wbuf_bytes, m[0], m[1], m[5], m[1] - m[5], m[6], m[2] - m[6], m[3], m[4]);
-            return UMX_OK;
-        }
-    }
-    if (L.use_first) {   // dense-K kernel of the first down-sampling layer
-        FirstParams f = L.first;
-        const Buffer& sb = cur_bufs(ctx)[0];
-        f.B = ns;
-        f.src_hi = hi_at(sb); f.src_lo = lo_at(sb);
-        f.src_c = ctx->in_cw ? reinterpret_cast<const unsigned char*>(sb.d) + (size_t)k0 * sb.S * sb.S * 4 * ctx->in_cw : nullptr;
-        f.dst_hi = p.dst_hi; f.dst_lo = p.dst_lo; f.dst_planar = p.dst_planar;
-        f.overflow_flag = p.overflow_flag;
-        snprintf(kn, sizeof kn, "conv_first<%d, %d, %d, false>", f.NT, f.CW, f.NKS);
-        ProfScope ps(ctx, site_of(ctx, L.name, kn), L.flops * ns, L.bytes * ns, 2.0 * 3.0 * f.NKS * 32.0 * f.NT * 16.0 * L.H * L.W * ns);
-        HIP_TRY(ctx, launch_conv_first(f, run_stream(ctx)));
+    return UMX_OK;
+}
+
+// diagnostic: UMX_DEBUG_STAMPS=<layer name> prints the mean s_memtime segments of that layer's workgroups
+int run_stamps(umx_ctx* ctx, const Lane& lane, const Launch& L, HConvParams& p, int n) {
+    size_t nwg = (size_t)((n + p.imgs - 1) / p.imgs) * p.tiles_y * p.tiles_x;
+    if (p.f6) nwg = (nwg + 1) / 2;   // (two tiles per workgroup)
+    nwg *= (size_t)p.nblocks * (p.fused_phases ? 1 : p.nphase);
+    long long* d = nullptr;
+    HIP_TRY(ctx, hipMalloc((void**)&d, nwg * 7 * sizeof(long long)));
+    p.dbg = d;
+    if (p.xcd_order == 2) p.xcd_order = 1;   // (the stamp records are indexed by the three-dimensional grid)
+    HIP_TRY(ctx, launch_conv_f16(p, lane.stream));
+    HIP_TRY(ctx, hipStreamSynchronize(lane.stream));
+    std::vector<long long> hst(nwg * 7);
+    HIP_TRY(ctx, hipMemcpy(hst.data(), d, hst.size() * sizeof(long long), hipMemcpyDeviceToHost));
+    hipFree(d);
+    double m[7] = {0, 0, 0, 0, 0, 0, 0};
+    for (size_t w = 0; w < nwg; ++w)
+        for (int k = 0; k < 7; ++k) m[k] += (double)hst[w * 7 + k] / nwg;
+    fprintf(stderr, "[umx stamps] %s: %zu workgroups, LDS %d B, wbuf %d B | shader cycles: prologue %.0f, stage waits %.0f "
+                    "(own loads %.0f, barrier %.0f), issuing the next stage's loads %.0f, MFMA blocks %.0f, epilogue %.0f, total %.0f\n",
+            L.name.c_str(), nwg, p.lds_bytes, p.wbuf_bytes, m[0], m[1], m[5], m[1] - m[5], m[6], m[2] - m[6], m[3], m[4]);
+    return UMX_OK;
+}
+
+// one launch of the split-precision plan
+int run_launch_f16(umx_ctx* ctx, const Lane& lane, Launch& L, int n, float* probs) {
+    if (L.head) {
+        if (ctx->head_fused) return UMX_OK;   // computed in the epilogue of the last convolution
+        const Buffer& sb = (*lane.bufs)[L.g[0].src];
+        ProfScope ps(ctx, lane.stream, site_of(ctx, L.name, "head_softmax"), L.flops * n, L.bytes * n);
+        HIP_TRY(ctx, launch_head_softmax(sb.d, (size_t)n * L.H * L.W, L.head_C, L.head_K, L.d_head_w, L.d_pre_s, L.d_pre_b, probs, lane.stream));
         return UMX_OK;
     }
-    const int site = site_of(ctx, L.name, kn);
+    HConvParams p;
+    if (const int rc = bind_f16(ctx, lane, L, n, probs, &p)) return rc;
+    const LaunchShape sh = launch_shape(L, p, n);
+    p.xcd_order = sh.xcd_order; p.ntiles_grid = sh.ntiles_grid; p.tiles_per_xcd = sh.tiles_per_xcd;
+    if (!ctx->stamps.empty() && L.name == ctx->stamps) return run_stamps(ctx, lane, L, p, n);
+    if (L.use_first) {   // dense-K kernel of the first down-sampling layer
+        FirstParams f = L.first;
+        const Buffer& sb = (*lane.bufs)[0];
+        f.B = n;
+        f.src_hi = hi_of(sb); f.src_lo = lo_of(sb, n);
+        f.src_c = ctx->in_cw ? reinterpret_cast<const unsigned char*>(sb.d) : nullptr;
+        f.dst_hi = p.dst_hi; f.dst_lo = p.dst_lo; f.dst_planar = p.dst_planar;
+        f.overflow_flag = p.overflow_flag;
+        ProfScope ps(ctx, lane.stream, site_of(ctx, L.name, L.kernel), L.flops * n, L.bytes * n, 2.0 * 3.0 * f.NKS * 32.0 * f.NT * 16.0 * L.H * L.W * n);
+        HIP_TRY(ctx, launch_conv_first(f, lane.stream));
+        return UMX_OK;
+    }
+    const int site = site_of(ctx, L.name, L.kernel);
     ctx->sites[site].xcd_order = p.xcd_order;
-    ProfScope ps(ctx, site, L.flops * ns, L.bytes * ns, L.exec_flops * ns);
-    HIP_TRY(ctx, launch_conv_f16(p, run_stream(ctx)));
+    ProfScope ps(ctx, lane.stream, site, L.flops * n, L.bytes * n, L.exec_flops * n);
+    HIP_TRY(ctx, launch_conv_f16(p, lane.stream));
     return UMX_OK;
 }
 
 // The split-precision plan: input split (unless the gather kernel already wrote the planes), then every launch once
 // over the whole batch.  (Running the full-resolution layers as chains over sub-batches, to keep producer -> consumer
 // tensors in the 256 MiB Infinity Cache, was measured slower at every sub-batch size -- DESIGN.md section 4.)
-int run_unet_f16(umx_ctx* ctx, const float* tiles, int n, float* probs) {
-    int rc = run_launch_f16(ctx, ctx->split_launch, tiles, n, 0, n, probs);
+int run_unet_f16(umx_ctx* ctx, const Lane& lane, const float* tiles, int n, float* probs) {
+    int rc = run_input_split(ctx, lane, tiles, n);
     if (rc) return rc;
     for (auto& L : ctx->plan)
-        if ((rc = run_launch_f16(ctx, L, tiles, n, 0, n, probs))) return rc;
+        if ((rc = run_launch_f16(ctx, lane, L, n, probs))) return rc;
     if (ctx->prof && ctx->pending.size() > 4096) return prof_fold(ctx);
     return UMX_OK;
 }
@@ -243,26 +218,27 @@ int check_range_flag(umx_ctx* ctx) {   // call with the stream idle
                                     "create the context with UMX_PREC_F32 (or UMX_PRECISION=f32)");
 }
 
-int run_unet(umx_ctx* ctx, const float* tiles, int n, float* probs) {
-    if (ctx->precision == UMX_PREC_F16X3) return run_unet_f16(ctx, tiles, n, probs);
+// run the UNet on n tiles already in bufs[0] layout at `tiles` -> probs, on a lane
+int run_unet(umx_ctx* ctx, const Lane& lane, const float* tiles, int n, float* probs) {
+    if (ctx->precision == UMX_PREC_F16X3) return run_unet_f16(ctx, lane, tiles, n, probs);
+    const std::vector<Buffer>& bufs = *lane.bufs;
     for (auto& L : ctx->plan) {
-        const float* src0 = L.g[0].src == 0 ? tiles : cur_bufs(ctx)[L.g[0].src].d;
+        const float* src0 = L.g[0].src == 0 ? tiles : bufs[L.g[0].src].d;
         if (L.head) {
             const size_t npix = (size_t)n * L.H * L.W;
-            ProfScope ps(ctx, site_of(ctx, L.name, "head_softmax"), L.flops * n, L.bytes * n);
-            HIP_TRY(ctx, launch_head_softmax(src0, npix, L.head_C, L.head_K, L.d_head_w, L.d_pre_s, L.d_pre_b, probs,
-                                             run_stream(ctx)));
+            ProfScope ps(ctx, lane.stream, site_of(ctx, L.name, "head_softmax"), L.flops * n, L.bytes * n);
+            HIP_TRY(ctx, launch_head_softmax(src0, npix, L.head_C, L.head_K, L.d_head_w, L.d_pre_s, L.d_pre_b, probs, lane.stream));
             continue;
         }
         ConvParams p = L.cp;
         p.B = n;
         p.src[0] = src0;
-        if (L.ngroups > 1) p.src[1] = L.g[1].src == 0 ? tiles : cur_bufs(ctx)[L.g[1].src].d;
-        p.dst = cur_bufs(ctx)[L.dst].d;
+        if (L.ngroups > 1) p.src[1] = L.g[1].src == 0 ? tiles : bufs[L.g[1].src].d;
+        p.dst = bufs[L.dst].d;
         char kn[48];
         snprintf(kn, sizeof kn, "conv_mfma_f32<%d, %d>", L.nt, L.hpix <= 2 ? 2 : 4);
-        ProfScope ps(ctx, site_of(ctx, L.name, kn), L.flops * n, L.bytes * n, L.exec_flops * n);
-        HIP_TRY(ctx, launch_conv(p, L.nt, L.hpix, run_stream(ctx)));
+        ProfScope ps(ctx, lane.stream, site_of(ctx, L.name, kn), L.flops * n, L.bytes * n, L.exec_flops * n);
+        HIP_TRY(ctx, launch_conv(p, L.nt, L.hpix, lane.stream));
     }
     if (ctx->prof && ctx->pending.size() > 4096) return prof_fold(ctx);
     return UMX_OK;
@@ -271,7 +247,7 @@ int run_unet(umx_ctx* ctx, const float* tiles, int n, float* probs) {
 // Batching of `total` tiles over the lanes of a context: equal batches (<= max_batch), as many as a multiple of the lane
 // count when there is more than one batch, consecutive batches on alternating lanes.  The second lane's stream is forked
 // from the context's stream by an event at the first use and joined back in join(); with one lane (or one batch) every
-// launch stays on the context's stream.
+// launch stays on the context's stream.  next() hands out the batch's size and the lane it runs on.
 struct LaneLoop {
     umx_ctx* ctx;
     int batch, k = 0;
@@ -280,20 +256,19 @@ struct LaneLoop {
         int nbatch = (total + c->max_batch - 1) / c->max_batch;
         if (c->nlanes > 1 && nbatch > 1) nbatch = (nbatch + c->nlanes - 1) / c->nlanes * c->nlanes;
         batch = nbatch > 0 ? (total + nbatch - 1) / nbatch : 1;
-        ctx->lane = 0;
     }
-    int next(int left) {
-        ctx->lane = ctx->nlanes > 1 ? k % ctx->nlanes : 0;
-        if (ctx->lane == 1 && !forked) {
+    int next(int left, Lane* lane) {
+        int i = ctx->nlanes > 1 ? k % ctx->nlanes : 0;
+        if (i == 1 && !forked) {
             forked = true;
             if (hipEventRecord(ctx->ev_fork, ctx->stream) != hipSuccess ||
-                hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0) != hipSuccess) ctx->lane = 0;   // degrade to one lane
+                hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0) != hipSuccess) i = 0;   // degrade to one lane
         }
         ++k;
+        *lane = lane_of(ctx, i);
         return std::min(batch, left);
     }
     int join() {
-        ctx->lane = 0;
         if (!forked) return UMX_OK;
         forked = false;
         HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
@@ -319,92 +294,33 @@ int tiles_range(umx_ctx* ctx, const double* image_dev, int C_img, const TileGeom
     const void* const src = raw_dev ? raw_dev : (const void*)image_dev;
     const double src_b = raw_dev ? raw_bits / 8.0 : 8.0;
     LaneLoop ll(ctx, t1 - t0);
+    Lane lane;
     for (int t = t0, nb; t < t1; t += nb) {
-        nb = ll.next(t1 - t);
-        float* const tiles32 = ctx->precision == UMX_PREC_F16X3 ? (ctx->lane ? ctx->d_tiles32_2 : ctx->d_tiles32)
-                                                                : cur_bufs(ctx)[0].d;
+        nb = ll.next(t1 - t, &lane);
+        const Buffer& b0 = (*lane.bufs)[0];
+        float* const tiles32 = ctx->precision == UMX_PREC_F16X3 ? lane.tiles32 : b0.d;
         {
-            ProfScope ps(ctx, ctx->site_gather, 0.0,
+            ProfScope ps(ctx, lane.stream, ctx->site_gather, 0.0,
                          (double)nb * g.P * g.P * (src_b * C_img + (ctx->in_cw ? 4.0 * ctx->in_cw : direct16 ? 32.0 : 4.0 * ctx->hp.nChannels)));
             if (direct16) {   // gather + normalise + (hi, lo) split in one pass
-                const Buffer& b0 = cur_bufs(ctx)[0];
                 HIP_TRY(ctx, launch_gather_split(src, raw_dev ? raw_bits : 0, C_img, band_row0, band_rows, g, ctx->hp.nChannels, mean, stdv, t, nb,
-                                                 std::ldexp(1.f, ctx->act_shift), hi_of(b0), lo_of(b0, nb), ctx->in_cw, run_stream(ctx),
+                                                 std::ldexp(1.f, ctx->act_shift), hi_of(b0), lo_of(b0, nb), ctx->in_cw, lane.stream,
                                                  raw_dev ? mm_dev : nullptr));
             } else {
                 HIP_TRY(ctx, launch_gather_normalise(image_dev, C_img, band_row0, band_rows, g, ctx->hp.nChannels, mean, stdv, t,
-                                                     nb, tiles32, run_stream(ctx)));
+                                                     nb, tiles32, lane.stream));
             }
         }
-        int rc = run_unet(ctx, direct16 ? nullptr : tiles32, nb, probs_dev + (size_t)(t - t0) * prob_f);
+        int rc = run_unet(ctx, lane, direct16 ? nullptr : tiles32, nb, probs_dev + (size_t)(t - t0) * prob_f);
         if (rc) return rc;
     }
     return ll.join();
 }
 
-// A model planned on the host: the graph, the layout of each activation buffer (which depends on the graph alone) and, for the
-// split-precision engine (f16), the host plan of every launch.  UMX_ERR_INVALID with "<layer>: <reason>" in *why for a refused layer.
-struct ModelPlan {
-    std::vector<Launch> plan;
-    std::vector<Buffer> bufs;           // no device memory yet
-    std::vector<HostPlan> hplans;       // per launch (f16; nothing for the head)
-    size_t pos = 0;                     // blob floats the graph consumed
-};
-int plan_model(const umx_hparams& hp, const float* blob, bool f16, bool f6, int act_shift, ModelPlan* m, std::string* why) {
-    // (the raw-skip fold of the split-precision plan:
-    // only where the first layer takes the dense-K kernel: the input tiles are then stored once, in the compact form both read)
-    bool fold = f16 && conv_first_eligible(hp);
-    for (;;) {
-        std::vector<size_t> buf_floats;
-        std::vector<std::pair<int, int>> buf_geom;
-        m->plan.clear();
-        m->pos = 0;
-        build_graph(hp, blob, &m->plan, &buf_floats, &buf_geom, &m->pos, fold);
-        const int head_src = m->plan.back().g[0].src;   // the tensor the softmax head reads stays fp32
-        m->bufs.assign(buf_floats.size(), Buffer());
-        for (size_t i = 0; i < m->bufs.size(); ++i) {
-            Buffer& B = m->bufs[i];
-            B.floats_per_tile = buf_floats[i];
-            B.S = buf_geom[i].first;
-            B.C = buf_geom[i].second;
-            B.Cs = round_up(B.C, 8);
-            B.as_f32 = !f16 || (int)i == head_src;
-            // Octet-planar storage for the tensors whose consumers work on whole 16 x 16 (or 8 x 16) tiles of ONE image: a
-            // workgroup reads its halo once per octet chunk, and in NHWC every chunk touches every 128-byte line of the
-            // footprint (lu0.conv fetched 8.9 GB per launch through L2 for a 3 GB tensor); planar, a line belongs to one chunk.
-            // Same bytes per image either way, so batches slice identically.  With 8 stored channels the two forms coincide.
-            // Not for the output of a transposed convolution that runs one sub-pixel phase per workgroup (> 5 N-tiles): its
-            // stores are every second pixel of a row, 16 bytes at a 32-byte stride in the planar form (lu2.convT +19 %).
-            bool phase_written = false;
-            for (const Launch& Lp : m->plan)
-                if (Lp.dst == (int)i && Lp.nphase == 4 && !(Lp.o_mul == 2 && Lp.ngroups == 1 && (Lp.Cout + 15) / 16 <= 5 && Lp.H >= 8 && Lp.W >= 16))
-                    phase_written = true;
-            B.planar = !phase_written && !B.as_f32 && i != 0 && B.S >= 16 && B.Cs > 8 &&
-                       (size_t)B.S * B.S * 16 < (1u << 24);   // (the kernels form octet offsets with 24-bit multiplies)
-        }
-        m->hplans.assign(m->plan.size(), HostPlan());
-        bool folded = false, first = false;
-        for (size_t li = 0; li < m->plan.size(); ++li) {
-            Launch& L = m->plan[li];
-            if (L.head) continue;
-            if (f16) make_d2s(L);   // (narrow stride-2 transposed convolutions: depth-to-space form, before the geometry is laid out)
-            std::string w;
-            if (!conv_geometry(L, &w)) { *why = L.name + ": " + w; return UMX_ERR_INVALID; }
-            if (!f16) continue;
-            PlanInputs in;
-            in.f6 = f6; in.imSize = hp.imSize; in.act_shift = act_shift;
-            in.out_f32 = L.dst == head_src; in.head = &m->plan.back(); in.dst_planar = m->bufs[L.dst].planar;
-            if (int rc = plan_f16(L, in, &m->hplans[li], &w)) { *why = L.name + ": " + w; return rc; }
-            plan_first(L, &m->hplans[li]);
-            folded = folded || L.app_src == 0;
-            first = first || m->hplans[li].use_first;
-        }
-        // The fold was decided from the hyper-parameters (conv_first_eligible), the dense-K first layer from the plan: where the
-        // two disagree (a forced N-tile count, a first layer the planner split into N-blocks) the graph is planned again with the
-        // two-group top convolution -- not failed into the 4 x slower exact-fp32 kernels
-        if (!folded || first) return UMX_OK;
-        fold = false;
-    }
+// the planner's switches from the environment; called by umx_create_opts, umx_plan_check and the trainer's select_route, nowhere else
+PlanSwitches plan_switches_from_env() {
+    return plan_switches_parse(getenv("UMX_PLAN_NT"), getenv("UMX_PLAN_OVERRIDE"), getenv("UMX_PLAN_THREADS"), getenv("UMX_DEBUG_PLAN") != nullptr,
+                               getenv("UMX_DEBUG_STAMPS"));
 }
 
 // a host plan on the device: its arrays in the context's allocations, the launch's parameters with their pointers set
@@ -423,9 +339,7 @@ int upload_plan(umx_ctx* ctx, Launch& L, const HostPlan& P) {
     h.head_frag = reinterpret_cast<const uint4*>(up(P.head_frag, "head_frag"));
     h.zeros = ctx->d_zeros;
     h.overflow_flag = ctx->d_flag;
-    L.nt16 = P.nt16;
-    L.exec_flops = P.exec_flops;
-    L.use_first = P.use_first;
+    adopt_plan(L, P);
     if (P.use_first) {
         L.first = P.first;
         L.first.w = reinterpret_cast<const uint4*>(up(P.first_w, "first weights"));
@@ -528,7 +442,55 @@ int umx_plan_check(const umx_hparams* hp) {
     if (rc) return fail(nullptr, rc, "%s", why.c_str());
     std::vector<float> blob(blob_floats_needed(*hp), 0.f);
     ModelPlan m;
-    if ((rc = plan_model(*hp, blob.data(), true, false, 0, &m, &why))) return fail(nullptr, rc, "%s", why.c_str());
+    if ((rc = plan_model(*hp, blob.data(), true, false, 0, plan_switches_from_env(), &m, &why))) return fail(nullptr, rc, "%s", why.c_str());
+    return UMX_OK;
+}
+
+// The split-precision plan of a model as text, host only: plan_model under the given switches (strings as the variables would hold
+// them, NULL or "": not set; threads 0: default), one line per launch but the head -- its UMX_DEBUG_PLAN text, the kernel, the
+// destination's layout, nt16, wshift, infer_digest and, for every batch n, "n:<workgroup order>/<tiles per XCD>" (launch_shape)
+int umx_test_infer_plan(const umx_hparams* hp, int f6, int act_shift, const float* blob, size_t blob_floats, const char* nt,
+                        const char* override_list, const char* stamps, int threads, const int* batches, int nbatches, char* text, size_t cap,
+                        size_t* needed) {
+    if (!hp || !blob || !needed || (!text && cap) || (!batches && nbatches) || nbatches < 0 || act_shift < 0 || act_shift > 8 || threads < 0)
+        return fail(nullptr, UMX_ERR_INVALID, "umx_test_infer_plan: bad arguments");
+    *needed = 0;
+    for (int k = 0; k < nbatches; ++k)
+        if (batches[k] < 1 || batches[k] > 4096) return fail(nullptr, UMX_ERR_INVALID, "umx_test_infer_plan: batch %d outside [1, 4096]", batches[k]);
+    std::string why;
+    int rc = check_hp(hp, &why);
+    if (rc) return fail(nullptr, rc, "%s", why.c_str());
+    if (blob_floats != blob_floats_needed(*hp))
+        return fail(nullptr, UMX_ERR_BLOB, "weight blob has %zu floats, the graph needs %zu", blob_floats, blob_floats_needed(*hp));
+    auto set = [](const char* s) { return s && *s ? s : nullptr; };
+    PlanSwitches sw = plan_switches_parse(set(nt), set(override_list), nullptr, false, set(stamps));
+    sw.threads = threads;
+    ModelPlan m;
+    if ((rc = plan_model(*hp, blob, true, f6 != 0, act_shift, sw, &m, &why))) return fail(nullptr, rc, "%s", why.c_str());
+    std::string out;
+    for (size_t li = 0; li < m.plan.size(); ++li) {
+        Launch& L = m.plan[li];
+        if (L.head) continue;
+        const HostPlan& P = m.hplans[li];
+        adopt_plan(L, P);
+        std::string line = plan_describe(L, P);
+        line.pop_back();
+        for (size_t at; (at = line.find('\n')) != std::string::npos;) line.replace(at, 1, " | ");
+        const Buffer& db = m.bufs[L.dst];
+        char b[256];
+        snprintf(b, sizeof b, " || %s, dst f32 %d planar %d Cs %d, nt16 %d, wshift %d, digest %016llx,", L.kernel.c_str(), db.as_f32 ? 1 : 0,
+                 db.planar ? 1 : 0, db.Cs, P.nt16, P.wshift, infer_digest(P));
+        line += b;
+        for (int k = 0; k < nbatches; ++k) {
+            const LaunchShape sh = launch_shape(L, P.h, batches[k]);
+            snprintf(b, sizeof b, " %d:%d/%d", batches[k], sh.xcd_order, sh.tiles_per_xcd);
+            line += b;
+        }
+        out += line + "\n";
+    }
+    *needed = out.size() + 1;
+    if (cap < *needed) return fail(nullptr, UMX_ERR_INVALID, "umx_test_infer_plan: the text takes %zu bytes", *needed);
+    memcpy(text, out.c_str(), *needed);
     return UMX_OK;
 }
 
@@ -683,7 +645,8 @@ int umx_create_opts(const umx_hparams* hp, const float* weight_blob, size_t blob
 
     const bool f16 = precision == UMX_PREC_F16X3;
     ModelPlan mp;
-    if ((rc = plan_model(*hp, weight_blob, f16, f6, act_shift, &mp, &why))) return fail(nullptr, rc, "%s", why.c_str());
+    const PlanSwitches sw = plan_switches_from_env();
+    if ((rc = plan_model(*hp, weight_blob, f16, f6, act_shift, sw, &mp, &why))) return fail(nullptr, rc, "%s", why.c_str());
     if (mp.pos != blob_floats) return fail(nullptr, UMX_ERR_BLOB, "internal blob walk mismatch");
 
     std::unique_ptr<umx_ctx> ctx(new umx_ctx());
@@ -694,6 +657,7 @@ int umx_create_opts(const umx_hparams* hp, const float* weight_blob, size_t blob
     ctx->precision = precision;
     ctx->f6 = f6;
     ctx->act_shift = act_shift;
+    ctx->stamps = sw.stamps;
     ctx->mem.fill = guard.fill;
     ctx->plan = std::move(mp.plan);
     ctx->bufs = std::move(mp.bufs);
@@ -779,7 +743,6 @@ int umx_create_opts(const umx_hparams* hp, const float* weight_blob, size_t blob
             }
         L.cp.pre_s = L.d_pre_s; L.cp.pre_b = L.d_pre_b; L.cp.post_s = L.d_post_s; L.cp.post_b = L.d_post_b;
     }
-    if (f16) c->split_launch.name = "input.split";
     for (const Launch& L : c->plan)   // compact input tiles: the graph folded the raw skip (and so the first layer runs on the dense-K kernel)
         if (L.app_src == 0) c->in_cw = c->hp.nChannels == 1 ? 1 : c->hp.nChannels == 2 ? 2 : 4;
     if (c->mem.fill >= 0)
@@ -839,9 +802,10 @@ int umx_forward_tiles_dev(umx_ctx* ctx, const float* tiles_dev, int n, float* pr
         const size_t P = ctx->hp.imSize;
         const size_t tile_f = P * P * ctx->hp.nChannels, prob_f = P * P * ctx->hp.nClasses;
         LaneLoop ll(ctx, n);
+        Lane lane;
         for (int i = 0, nb; i < n; i += nb) {
-            nb = ll.next(n - i);
-            int rc = run_unet(ctx, tiles_dev + (size_t)i * tile_f, nb, probs_dev + (size_t)i * prob_f);
+            nb = ll.next(n - i, &lane);
+            int rc = run_unet(ctx, lane, tiles_dev + (size_t)i * tile_f, nb, probs_dev + (size_t)i * prob_f);
             if (rc) return rc;
         }
         return ll.join();
@@ -927,7 +891,7 @@ int stitch_rows(umx_ctx* ctx, const float* probs_dev, int tpr0, int tpr1, int H,
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (ctx->site_stitch < 0) ctx->site_stitch = site_of(ctx, "pi2d.stitch", "stitch");
     const int K = ctx->hp.nClasses;
-    ProfScope ps(ctx, ctx->site_stitch, 0.0,
+    ProfScope ps(ctx, ctx->stream, ctx->site_stitch, 0.0,
                  (double)(y1 - y0) * W * K * (4.0 * ((double)g.P / g.sub) * ((double)g.P / g.sub) + (stitch == 0 ? 2.0 : stitch == kStitchU8 ? 1.0 : 4.0)));
     HIP_TRY(ctx, launch_stitch(probs_dev, tpr0, tpr1, g, K, mode, stitch, y0, y1, out_dev, ctx->stream, plane_rows));
     return UMX_OK;

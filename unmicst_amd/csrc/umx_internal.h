@@ -95,6 +95,7 @@ struct Launch {
     int d2s_oy[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, d2s_ox[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};   // sub-pixel offset of (block, phase slot)
     unsigned char d2s_tapmask[2][16] = {{0}, {0}};   // per block and tap of its window: bit j set = phase slot j has that tap
     int nt16 = 1;             // N-tiles per workgroup of the split-precision kernel
+    std::string kernel;       // ... and its instantiation's name in a profile (HostPlan::kernel)
     float* d_head_w = nullptr;
     float *d_pre_s = nullptr, *d_pre_b = nullptr, *d_post_s = nullptr, *d_post_b = nullptr;
 };
@@ -172,7 +173,7 @@ struct umx_ctx {
     hipStream_t stream2 = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     float* d_tiles32_2 = nullptr;
-    int nlanes = 1, lane = 0;
+    int nlanes = 1;
     int ncu = 256;
     // host entry points: uploads / downloads on their own streams, slab by slab, under the tile kernels
     hipStream_t up_stream = nullptr, dn_stream = nullptr;
@@ -214,7 +215,7 @@ struct umx_ctx {
                                 // only readers are the dense-K first layer and the raw-skip append of the top transposed convolution
     uint4* d_zeros = nullptr;
     bool head_fused = false;
-    Launch split_launch;
+    std::string stamps;         // UMX_DEBUG_STAMPS as umx_create_opts read it: the layer whose launches run the stamped kernel
     umx::Shard* shard = nullptr;   // set by umx_shard_init / umx_shard_init_transport once it has fully succeeded
 };
 
@@ -222,8 +223,16 @@ namespace umx {
 
 extern thread_local std::string g_err;
 
-inline std::vector<Buffer>& cur_bufs(umx_ctx* ctx) { return ctx->lane ? ctx->bufs2 : ctx->bufs; }
-inline hipStream_t run_stream(umx_ctx* ctx) { return ctx->lane ? ctx->stream2 : ctx->stream; }
+// One lane of a context: the activation buffers, stream and fp32 tile staging a tile batch runs on (umx_ctx: lane 0 = bufs, stream,
+// d_tiles32; lane 1 = bufs2, stream2, d_tiles32_2).  A value handed down the launch path, never kept.
+struct Lane {
+    std::vector<Buffer>* bufs;
+    hipStream_t stream;
+    float* tiles32;
+};
+inline Lane lane_of(umx_ctx* ctx, int i) {
+    return i ? Lane{&ctx->bufs2, ctx->stream2, ctx->d_tiles32_2} : Lane{&ctx->bufs, ctx->stream, ctx->d_tiles32};
+}
 
 int fail(umx_ctx* ctx, int code, const char* fmt, ...);
 
@@ -248,17 +257,38 @@ int build_graph(const umx_hparams& hp, const float* blob, std::vector<Launch>* p
                 std::vector<std::pair<int, int>>* buf_geom, size_t* pos, bool fold_top_skip = false);
 bool conv_geometry(Launch& L, std::string* why);
 
-// ---- umx_plan.hip: split-precision plan of one launch, on the host (no context, no HIP call)
+// ---- umx_plan.hip: split-precision plan of one launch and of a model, on the host (no context, no HIP call, no getenv)
 int mx_pack_e2m3(const double (&v)[32], double amax, unsigned char (&out)[24]);   // umx_plan.hip: one OCP MX fp6 (e2m3) block of 32
+// The planner's tuning and debug switches as a value.  plan_switches_from_env is the one place that reads them from the environment;
+// its callers are umx_create_opts, umx_plan_check and the trainer's select_route.  Default-constructed: no switch.
+struct PlanSwitches {
+    bool have_nt = false;          // UMX_PLAN_NT is set (even malformed: the narrower-N-tile trial is then off) ...
+    std::string nt_layer;          // ... "layer:NT" forces that layer's N-tiles per workgroup
+    int nt = 0;
+    struct Override { std::string item, layer; int oc, s, mp; };   // one well-formed "layer:OC:S[:pieces]" entry (mp 0: no fourth field)
+    bool have_override = false;    // UMX_PLAN_OVERRIDE is set ...
+    std::vector<Override> overrides;   // ... its entries in order
+    int threads = 0;               // UMX_PLAN_THREADS: host threads of the weight fill (0: by the size of the images)
+    bool debug_plan = false;       // UMX_DEBUG_PLAN: the caller prints every plan's line (plan_describe) on stderr
+    bool have_stamps = false;      // UMX_DEBUG_STAMPS is set (no layer takes the packed or fp6 form: the stamped kernels have neither) ...
+    std::string stamps;            // ... to this layer's name
+};
+// (a null string: the variable is not set)
+PlanSwitches plan_switches_parse(const char* nt, const char* override_list, const char* threads, bool debug_plan, const char* stamps);
+PlanSwitches plan_switches_from_env();
 struct PlanInputs {                // what the plan of a launch depends on besides the launch
     bool f6 = false;               // the model may take the F6 form (UMX_PREC_F16X3_F6)
     int imSize = 0, act_shift = 0; // the model's tile size; activations are stored times 2^act_shift
     bool out_f32 = false;          // the launch writes fp32 (the head's input; every trainer launch)
     bool dst_planar = false;       // the destination buffer is octet-planar (the depth-to-space table)
     const Launch* head = nullptr;  // the softmax head its epilogue may fuse
+    PlanSwitches sw;
 };
 struct HostPlan {
     HConvParams h;                      // device pointers null: the engine's upload_plan / the trainer's upload_conv set them
+    int S = 0, slots = 1;               // the chosen k-steps per stage and halo slots (the octets per chunk are h.OC)
+    std::string kernel;                 // the instantiation the launch runs under, as rocprofv3 names it: conv_f16x3<NT, KMT, NPH, DBG,
+                                        // MAXP, PK, D2S, F6, W2> (W2 == F6 always) or, with use_first, conv_first<NT, CW, NKS, DBG>
     std::vector<HStage> stages;         // the stage table, every list's stages and a dummy behind them
     std::vector<_Float16> wimg[4];      // per stage list: weight slab [N-block][stage blocks] (training plans: k-maps only)
     std::vector<float> econst;          // epilogue constants per N-block (+ depth-to-space table, fused-head constants)
@@ -279,6 +309,40 @@ void plan_first(const Launch& L, HostPlan* P);
 bool make_d2s(Launch& L);
 // the same decision from the hyper-parameters alone (the graph builder folds the raw skip only when the first layer takes this kernel)
 bool conv_first_eligible(const umx_hparams& hp);
+// the plan's line(s) of UMX_DEBUG_PLAN, each "[umx plan] ...\n" (a dense-K first layer: a second line)
+std::string plan_describe(const Launch& L, const HostPlan& P);
+// the host half of an upload: what the launch path reads of a plan besides the device parameters (nt16, exec_flops, use_first, kernel)
+void adopt_plan(Launch& L, const HostPlan& P);
+// A model planned on the host: the graph, the layout of each activation buffer (which depends on the graph alone) and, for the
+// split-precision engine (f16), the host plan of every launch.  UMX_ERR_INVALID with "<layer>: <reason>" in *why for a refused layer.
+struct ModelPlan {
+    std::vector<Launch> plan;
+    std::vector<Buffer> bufs;           // no device memory yet
+    std::vector<HostPlan> hplans;       // per launch (f16; nothing for the head)
+    size_t pos = 0;                     // blob floats the graph consumed
+};
+int plan_model(const umx_hparams& hp, const float* blob, bool f16, bool f6, int act_shift, const PlanSwitches& sw, ModelPlan* m,
+               std::string* why);
+// the workgroup order of one launch of an adopted plan on a batch of n tiles (the batch decides: run_launch_f16 asks per launch)
+struct LaunchShape { int xcd_order, ntiles_grid, tiles_per_xcd; };
+LaunchShape launch_shape(const Launch& L, const HConvParams& p, int n);
+// 64-bit FNV-1a, and the serialisation of a host plan both digests share (documented in umx_tconv.hip)
+struct Fnv {
+    unsigned long long v = 0xcbf29ce484222325ull;
+    void bytes(const void* p, size_t n) {
+        const unsigned char* b = static_cast<const unsigned char*>(p);
+        for (size_t i = 0; i < n; ++i) v = (v ^ b[i]) * 0x100000001b3ull;
+    }
+    void i(long long x) {
+        unsigned char b[8];
+        for (int k = 0; k < 8; ++k) b[k] = (unsigned char)((unsigned long long)x >> (8 * k));
+        bytes(b, 8);
+    }
+    void f(float x) { bytes(&x, 4); }
+    template <typename... T> void is(T... xs) { (i((long long)xs), ...); }
+};
+void digest_host_plan(Fnv& d, const HostPlan& P);
+unsigned long long infer_digest(const HostPlan& P);   // everything upload_plan sends for one inference launch
 
 // ---- umx_tconv.hip: the host plan of one forward / input-gradient convolution of the training step (no HIP call, no trainer, no getenv)
 struct TapSet {
@@ -319,6 +383,7 @@ struct TConvEnv {                      // what its plan depends on besides
     bool hconv = true;                 // the route: split precision (conv_f16x3) where the planner takes the shape, else the fp32 kernel
     bool no_ksplit = false;            // UMX_TRAIN_NO_KSPLIT
     const float* params = nullptr;     // the parameter vector on the host: weight scales
+    PlanSwitches sw;                   // the planner's switches as select_route read them (umx_test_train_plan: none)
 };
 struct TConvPlan {
     ConvParams cp;                     // the fp32 kernel's launch (pointers null)
@@ -380,10 +445,11 @@ int site_of(umx_ctx* ctx, const std::string& name, const std::string& kernel);
 int prof_fold(umx_ctx* ctx);
 struct ProfScope {
     umx_ctx* ctx;
+    hipStream_t stream;
     int site;
     hipEvent_t a = nullptr, b = nullptr;
     bool on;
-    ProfScope(umx_ctx* c, int s, double flops, double bytes, double exec = 0.0) : ctx(c), site(s), on(c->prof && s >= 0) {
+    ProfScope(umx_ctx* c, hipStream_t st, int s, double flops, double bytes, double exec = 0.0) : ctx(c), stream(st), site(s), on(c->prof && s >= 0) {
         if (!on) return;
         const int64_t k = ctx->sites[site].seen++;
         if (ctx->prof > 1 && k % ctx->prof != 0) { on = false; return; }   // sampling: this launch runs unbracketed
@@ -398,11 +464,11 @@ struct ProfScope {
         ctx->sites[site].flops += flops;
         ctx->sites[site].bytes += bytes;
         ctx->sites[site].exec += exec;
-        hipEventRecord(a, run_stream(ctx));
+        hipEventRecord(a, stream);
     }
     ~ProfScope() {
         if (!on) return;
-        hipEventRecord(b, run_stream(ctx));
+        hipEventRecord(b, stream);
         ctx->pending.push_back({site, a, b});
     }
 };

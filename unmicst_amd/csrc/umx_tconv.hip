@@ -258,8 +258,10 @@ bool plan_split(const TConvSpec& s, const TConvEnv& env, TConvPlan* out, std::st
     PlanInputs in;
     in.imSize = env.imSize;
     in.out_f32 = true;
+    in.sw = env.sw;
     HostPlan& P = out->P;
     if (!conv_geometry(L, why) || plan_f16(L, in, &P, why) != UMX_OK) return false;
+    if (env.sw.debug_plan) fputs(plan_describe(L, P).c_str(), stderr);
     HConvParams& h = P.h;   // (the weight slabs hold the k-maps; repack_f16x3_kernel writes their values every step)
     out->wsh = wscale_shift(operand_wmax(out->wsrc, env.params));
     static_assert(sizeof(HWRef) == sizeof(HWRefDev) && sizeof(HWRefDev) == 12, "reference record layout");
@@ -372,23 +374,13 @@ std::string tconv_describe(const TConvSpec& s, const TConvEnv& env, const TConvP
 //   wimg         per phase (4): the count of halves, then their bytes
 //   econst       the count, then the floats' bytes
 //   HWRef        per phase (4): the count, then each: dst base nvalid arr
-namespace {
-struct Fnv {
-    unsigned long long v = 0xcbf29ce484222325ull;
-    void bytes(const void* p, size_t n) {
-        const unsigned char* b = static_cast<const unsigned char*>(p);
-        for (size_t i = 0; i < n; ++i) v = (v ^ b[i]) * 0x100000001b3ull;
-    }
-    void i(long long x) {
-        unsigned char b[8];
-        for (int k = 0; k < 8; ++k) b[k] = (unsigned char)((unsigned long long)x >> (8 * k));
-        bytes(b, 8);
-    }
-    void f(float x) { bytes(&x, 4); }
-    template <typename... T> void is(T... xs) { (i((long long)xs), ...); }
-};
-}  // namespace
-
+// From HConvParams on this is digest_host_plan (umx_plan.hip), which the inference digest shares: infer_digest is that part alone,
+// followed by
+//   nt16 wshift
+//   head_frag    the count of halves, then their bytes
+//   use_first    1 (else 0 and nothing more), then
+//   FirstParams  P Ci ks ntaps NT CW NKS rw_log2 hh hw inv_hw lds_bytes act post_affine Cds outS
+//   first_w      the count of halves, then their bytes
 unsigned long long tconv_digest(const ConvParams& c, int nt, int hpix, const PackDesc* packs, size_t npacks, const HostPlan* P) {
     Fnv d;
     d.is(nt, hpix, c.C[0], c.C[1], c.Cp[0], c.Cp[1], c.vec4[0], c.vec4[1], c.ngroups, c.H, c.W, c.Cout, c.Np, c.twm_log2, c.th_log2,
@@ -404,33 +396,7 @@ unsigned long long tconv_digest(const ConvParams& c, int nt, int hpix, const Pac
         for (int t = 0; t < 4 * kMaxPackTaps; ++t) d.i(q.mtap[t]);
     }
     d.i(P ? 1 : 0);
-    if (!P) return d.v;
-    const HConvParams& h = P->h;
-    d.is(h.dst_planar, h.H, h.W, h.Cout, h.Cds, h.NT, h.nblocks, h.twm_log2, h.th_log2, h.nimg_m, h.imgs, h.hh, h.hw, h.imgplane, h.nhalo,
-         h.plane_slots, h.OC, h.pix_bytes, h.slot_bytes);
-    d.f(h.inv_OC);
-    d.is(h.PP, h.nact, h.ninst, h.piece_bytes, h.inv_oc_q16, h.kmt, h.xcd_order, h.ntiles_grid, h.tiles_per_xcd, h.maxp, h.lo_off, h.b_off,
-         h.lds_bytes, h.wbuf_bytes, h.ymin, h.xmin, h.tiles_y, h.tiles_x, h.nphase, h.o_mul, h.fused_phases);
-    for (int ph = 0; ph < 4; ++ph) d.is(h.ph[ph].wblk_stride, h.ph[ph].stage0, h.ph[ph].nstages, h.ph[ph].oy_off, h.ph[ph].ox_off);
-    d.is(h.app_cw, h.app_oct, h.app_word, h.head_K, h.outH, h.outW, h.pool);
-    d.f(h.inv_imgplane);
-    d.f(h.inv_hw);
-    d.is(h.act, h.post_affine, h.d2s, h.d2s_mix, h.f6, h.pk, h.ksplit);
-    for (int ph = 0; ph < 4; ++ph)
-        for (int k = 0; k <= kMaxKSplit; ++k) d.i(h.ks0[ph][k]);
-    d.i((long long)h.split_stride);
-    d.i((long long)P->stages.size());
-    for (const HStage& st : P->stages) d.is(st.woff, st.group, st.oct0, st.noct, st.nk, st.plane0, st.phase);
-    for (int ph = 0; ph < 4; ++ph) {
-        d.i((long long)P->wimg[ph].size());
-        d.bytes(P->wimg[ph].data(), P->wimg[ph].size() * sizeof(_Float16));
-    }
-    d.i((long long)P->econst.size());
-    d.bytes(P->econst.data(), P->econst.size() * sizeof(float));
-    for (int ph = 0; ph < 4; ++ph) {
-        d.i((long long)P->wrefs[ph].size());
-        for (const HWRef& r : P->wrefs[ph]) d.is(r.dst, r.base, r.nvalid, r.arr);
-    }
+    if (P) digest_host_plan(d, *P);
     return d.v;
 }
 

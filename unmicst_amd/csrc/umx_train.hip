@@ -153,7 +153,7 @@ struct umx_trainer {
     bool wg_f32 = false;                // UMX_TRAIN_WGRAD_F32: no weight gradient takes the split-precision kernel
     bool wg_planes = true;              // the split-precision weight gradient stages from the planes
     bool no_ksplit = false;             // UMX_TRAIN_NO_KSPLIT: no convolution splits its K loop
-    bool debug_plan = false;            // UMX_DEBUG_PLAN: every plan's line on stderr
+    PlanSwitches sw;                    // the planner's switches (sw.debug_plan, UMX_DEBUG_PLAN: every plan's line on stderr)
     int nconvs = 0;                     // (during build) convolutions planned so far: TConv::order
     const float* h_blob = nullptr;      // (during build) the initial parameters on the host: weight scales
     std::vector<HConvParams> hls;       // the split-precision plans' launch parameters
@@ -256,10 +256,10 @@ int plan_conv(umx_trainer* tr, TConv& tc, const char* what, int H, int W, int Co
     s.bwd = bwd;
     tc.order = tr->nconvs++;
     TConvEnv env;
-    env.B = tr->B; env.imSize = tr->hp.imSize; env.hconv = tr->hconv; env.no_ksplit = tr->no_ksplit; env.params = tr->h_blob;
+    env.B = tr->B; env.imSize = tr->hp.imSize; env.hconv = tr->hconv; env.no_ksplit = tr->no_ksplit; env.params = tr->h_blob; env.sw = tr->sw;
     std::string why;
     if (!tconv_plan(s, env, &tc.plan, &why)) return tfail(tr, UMX_ERR_INVALID, "%s", why.c_str());
-    if (tr->debug_plan) {
+    if (tr->sw.debug_plan) {
         if (!tc.plan.refused.empty()) fprintf(stderr, "[umx train] %s stays on the fp32 kernel: %s\n", what, tc.plan.refused.c_str());
         fprintf(stderr, "[umx train] %s\n", tc.plan.text.c_str());
     }
@@ -479,7 +479,7 @@ int setup_wgrad(umx_trainer* tr, WgradPlan& w, const char* what, int H, int Cxt,
     std::string why;
     if (!wgrad_setup(&w, tr->wg_f32, &why)) return tfail(tr, UMX_ERR_INVALID, "%s: %s", what, why.c_str());
     tr->ws_floats = std::max(tr->ws_floats, wgrad_ws_floats(w));
-    if (tr->debug_plan) fprintf(stderr, "[umx train] %s\n", wgrad_describe(w, what).c_str());
+    if (tr->sw.debug_plan) fprintf(stderr, "[umx train] %s\n", wgrad_describe(w, what).c_str());
     return UMX_OK;
 }
 
@@ -898,7 +898,7 @@ void select_route(umx_trainer* tr) {
     tr->hconv = !getenv("UMX_TRAIN_CONV_F32");
     tr->wg_f32 = getenv("UMX_TRAIN_WGRAD_F32") != nullptr;
     tr->no_ksplit = getenv("UMX_TRAIN_NO_KSPLIT") != nullptr;
-    tr->debug_plan = getenv("UMX_DEBUG_PLAN") != nullptr;
+    tr->sw = plan_switches_from_env();
     if (const char* e = getenv("UMX_TRAIN_WSCALE_EVERY")) tr->wscale_every = atoi(e);
 }
 

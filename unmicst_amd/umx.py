@@ -32,7 +32,7 @@ EXPORTS = [
     "umx_infer_image_sharded_dev", "umx_infer_image_sharded_raw", "umx_infer_image_sharded_raw_submit",
     "umx_band_tiles_dev", "umx_stitch_dev", "umx_profile_enable", "umx_profile_read", "umx_prof_entry_size", "umx_test_double_to_half", "umx_test_double_to_half_dev",
     "umx_test_gauss_weights", "umx_test_resize_dev", "umx_test_rescale_dev", "umx_test_plane_range_dev", "umx_test_half_to_u8_dev",
-    "umx_describe", "umx_describe_graph", "umx_plan_check", "umx_test_wgrad_plan", "umx_test_train_plan", "umx_test_slide_plan", "umx_test_band_plan", "umx_test_mx_pack_e2m3", "umx_version",
+    "umx_describe", "umx_describe_graph", "umx_plan_check", "umx_test_infer_plan", "umx_test_wgrad_plan", "umx_test_train_plan", "umx_test_slide_plan", "umx_test_band_plan", "umx_test_mx_pack_e2m3", "umx_version",
     "umx_label_options_check", "umx_labeler_create", "umx_labeler_destroy", "umx_labeler_last_error", "umx_labeler_run",
     "umx_labeler_run_dev", "umx_labeler_objects", "umx_labeler_last_ms",
     "umx_label_measure_check", "umx_labeler_measure", "umx_labeler_measure_dev", "umx_labeler_measure_last_ms",
@@ -408,11 +408,11 @@ def train_plan(hp, batch: int, blob, conv_f32: bool = False, no_ksplit: bool = F
     return buf.value.decode().splitlines()
 
 
-def _plan_text(fn, argtypes, args):
+def _plan_text(fn, argtypes, args, cap=1 << 14):
     """a host-only test entry that writes text into (buffer, capacity, needed): its lines"""
     fn.restype = ctypes.c_int
     fn.argtypes = argtypes + [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
-    buf = ctypes.create_string_buffer(1 << 14)
+    buf = ctypes.create_string_buffer(cap)
     need = ctypes.c_size_t(0)
     rc = fn(*args, buf, len(buf), ctypes.byref(need))
     if rc and need.value > len(buf):
@@ -420,6 +420,19 @@ def _plan_text(fn, argtypes, args):
         rc = fn(*args, buf, len(buf), ctypes.byref(need))
     _check(load(), rc)
     return buf.value.decode().splitlines()
+
+
+def infer_plan(hp, f6: bool, act_shift: int, blob, nt: str = "", override: str = "", stamps: str = "", threads: int = 0, batches=()):
+    """umx_test_infer_plan: the split-precision plan of a model under the planner's switches (given here, not through the environment), one
+    line per launch but the head: its UMX_DEBUG_PLAN text, kernel, destination layout, nt16, wshift, digest of what the upload would
+    send, and "n:<workgroup order>/<tiles per XCD>" for every batch n.  A model the planner refuses raises UmxError.  Host only."""
+    blob = np.ascontiguousarray(blob, dtype=np.float32)
+    hps = _hp_struct(hp)
+    bt = (ctypes.c_int * len(batches))(*[int(b) for b in batches])
+    return _plan_text(load().umx_test_infer_plan,
+                      [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_char_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int],
+                      (ctypes.byref(hps), int(f6), act_shift, blob.ctypes.data, blob.size, nt.encode(), override.encode(), stamps.encode(), threads, bt, len(batches)),
+                      cap=1 << 17)   # (a second call would plan the model again)
 
 
 def slide_plan(hp, H: int, W: int, max_batch: int, C_img: int, src_bits: int = 0, rescale: bool = False, has_range: bool = False,
