@@ -488,6 +488,12 @@ UMX_API int umx_test_wgrad_plan(int B, int H, int Cxt, int Cx, int Cg, int nslab
  * cap is too small: UMX_ERR_INVALID).  A shape the planner refuses: its code, the reason in umx_last_error(NULL). */
 UMX_API int umx_test_train_plan(const umx_hparams* hp, int B, int conv_f32, int no_ksplit, const float* blob, size_t blob_floats,
                                 char* text, size_t cap, size_t* needed);
+/* test entry (host only): the stream schedule of the v2 training step as data (step_plan, unmicst_amd/csrc/umx_tstep.hip) after the
+ * same host pass, with (reg != 0) or without a regulariser.  text receives one line per step in host enqueue order: "op site stream;
+ * wait e..; record e..; r buf..; w buf.." -- the events its stream waits on before it and records after it, named by role and index,
+ * and the buffers it reads and writes ("-": none).  The legacy graph has no schedule: UMX_ERR_INVALID. */
+UMX_API int umx_test_step_plan(const umx_hparams* hp, int B, int conv_f32, int no_ksplit, int reg, const float* blob, size_t blob_floats,
+                               char* text, size_t cap, size_t* needed);
 /* test entries (host only): the schedule of a whole-slide call as data.  umx_test_slide_plan: what the image entries enqueue for an
  * H x W slide of C_img planes (src_bits 0: float64, 8 / 16: raw) at launch groups of max_batch tiles -- rescale, has_range (the caller
  * hands the planes' (min, max) in), sync_call (else submitted), host_range_ok (UMX_HOST_RANGE is not 0), raw_gather (the engine's tile

@@ -139,6 +139,9 @@ UMX_API int umx_trainer_batch(const umx_trainer* tr);
 UMX_API double umx_trainer_flops_per_image(const umx_trainer* tr);
 /* per-phase time of the steps since the last call (ms, accumulated with HIP events when enabled) */
 UMX_API int umx_trainer_profile(umx_trainer* tr, int enable, double* fwd_ms, double* bwd_ms, double* opt_ms, int* steps);
+/* test entry: on != 0 makes the v2 step enqueue every step of its schedule on the main stream, in plan order, without events -- the
+ * race-free statement of the same step.  The overlapped step equals it bit for bit.  (The legacy step is serial as it is.) */
+UMX_API int umx_test_trainer_serial(umx_trainer* tr, int on);
 
 /* ---- device-resident training set (unmicst_amd/csrc/umx_trainset.hip) ----
  * The reference's annotated set (I%05d_Img.tif / _Ant.tif / _wt.tif, UnMicst1-5.py:295-312, UnMicst2.py:293-309,

@@ -170,6 +170,48 @@ def test_step_is_bit_reproducible_and_trained_blob_serves_inference():
     assert np.abs(got - ref).max() <= 1e-4
 
 
+def _smallest_v2(L):
+    """the v2 shape of L layers (2 channels, 3 classes, 8 features) at the smallest imSize check_create and the planner accept"""
+    for sh in range(L, 10):
+        hp = model.HParams(model.GRAPH_V2, 1 << sh, 2, 3, 8, L, 3, 0)
+        try:
+            umx.step_plan(hp, 3, model.random_blob(hp, seed=17))   # (the host pass alone)
+        except umx.UmxError:
+            continue
+        return hp
+    raise AssertionError("no imSize accepted for %d layers" % L)
+
+
+def _two_steps(hp, blob, batches, serial):
+    tr = trainer.Trainer(hp, blob, trainer.duo_options(), batch=3)   # (regulariser on, dropout everywhere)
+    try:
+        tr.test_serial(serial)
+        losses = [tuple(tr.step(*b)) for b in batches]
+        return losses, tr.probs().tobytes(), tr.grads().tobytes(), tr.blob().tobytes()
+    finally:
+        tr.close()
+
+
+# The overlapped step (four streams, the plan's events) against the serial walk of the same plan (every step on the main stream in plan
+# order, no events: umx_test_trainer_serial).  Every kernel has a fixed summation order and the two loss words are separate, so a step
+# whose events order every hazard equals the serial walk byte for byte: losses, probabilities, the whole gradient vector and the
+# parameters after the second step.  (tests/test_step_plan_cpu.py checks the same plans for hazards on the host.)
+@pytest.mark.parametrize("L,route", [(3, r) for r in ROUTES] + [(1, {}), (2, {})],
+                         ids=lambda v: (",".join("%s=%s" % kv for kv in v.items()) or "f16x3") if isinstance(v, dict) else "L%d" % v)
+def test_overlapped_step_equals_the_serial_walk(L, route, monkeypatch):
+    for k, v in route.items():
+        monkeypatch.setenv(k, v)
+    hp = _smallest_v2(L)
+    blob = model.random_blob(hp, seed=17)
+    batches = [_batch(hp, 3, 23), _batch(hp, 3, 24)]
+    overlapped = _two_steps(hp, blob, batches, False)
+    serial = _two_steps(hp, blob, batches, True)
+    assert overlapped[0] == serial[0]
+    for what, a, b in zip(("probabilities", "gradients", "parameters"), overlapped[1:], serial[1:]):
+        assert a == b, what
+    assert overlapped[3] != blob.tobytes()
+
+
 def test_device_pointer_step_matches_host_step(torch_cuda=None):
     import torch
     hp = helpers.small_hps()["v2_duo_like"]

@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libumx.so")
 SOURCES = ["umx_kernels.hip", "umx_conv_f16.hip", "umx_conv_first.hip", "umx_graph.hip", "umx_plan.hip", "umx_engine.hip", "umx_pipeline.hip", "umx_host.hip",
-           "umx_tiff.hip", "umx_shard.hip", "umx_train_kernels.hip", "umx_wgrad.hip", "umx_tconv.hip", "umx_arena.hip", "umx_train.hip", "umx_trainset.hip", "umx_trainset_assemble.hip",
+           "umx_tiff.hip", "umx_shard.hip", "umx_train_kernels.hip", "umx_wgrad.hip", "umx_tconv.hip", "umx_tstep.hip", "umx_arena.hip", "umx_train.hip", "umx_trainset.hip", "umx_trainset_assemble.hip",
            "umx_trainset_border.hip", "umx_trainset_objects.hip", "umx_label.hip"]
 HEADERS = ["umx_kernels.h", "umx_internal.h", "umx_unionfind.h", os.path.join("..", "..", "include", "umx.h"), os.path.join("..", "..", "include", "umx_train.h")]
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")

@@ -408,6 +408,51 @@ std::string tconv_describe(const TConvSpec& s, const TConvEnv& env, const TConvP
 // FNV-1a over everything the upload sends (serialisation: umx_tconv.hip); P null: the convolution stays on the fp32 kernel
 unsigned long long tconv_digest(const ConvParams& cp, int nt, int hpix, const PackDesc* packs, size_t npacks, const HostPlan* P);
 
+// ---- umx_tstep.hip: the stream schedule of the v2 training step as data (no HIP call, no trainer, no getenv)
+constexpr int kSlots = 4;          // dz / gS buffers the main stream may run ahead of the weight gradients by
+constexpr int kMaxLayers = 8;      // (check_create)
+enum TOp {                         // what a step enqueues (enqueue_step's dispatch; T_JOIN: nothing, only its record)
+    T_BEGIN, T_PACK0, T_PACK1, T_REG, T_FWD, T_LOSS, T_MARK, T_HEAD, T_DZ, T_WG_U0, T_WG_U1, T_WG_T, T_WG_B, T_WG_D,
+    T_CV_US, T_CV_SKIP, T_CV_T, T_CV_B, T_CV_D, T_S2D, T_GSP, T_JOIN, T_OPT, T_NOPS
+};
+enum TStream { TS_MAIN, TS_SIDE0, TS_SIDE1, TS_AUX, kStepStreams };
+// A BN site of the step, in the order the backward pass visits them: up layer idx, the bottom, down layer i, and the top (1x1 head)
+inline int site_up(int idx) { return idx; }
+inline int site_bottom(int L) { return L; }
+inline int site_down(int L, int i) { return 2 * L - i; }
+inline int site_top(int L) { return 2 * L + 1; }
+// A buffer id: kind * 32 + index (layer, site or slot; 0 where the kind has one buffer)
+enum TBufKind {
+    TB_DS, TB_US, TB_CV, TB_ACTB, TB_Z, TB_STAT, TB_M12, TB_DA, TB_DB, TB_DT, TB_DSKIP, TB_DZ, TB_GS, TB_PART, TB_PART2, TB_WS, TB_WS2,
+    TB_SPLIT, TB_SPLIT2, TB_SPLIT3, TB_FPACK, TB_BPACK, TB_LOSS0, TB_LOSS1,
+    TB_G_LT, TB_G_W2, TB_G_WT, TB_G_LB, TB_G_WD, TB_G_BN,   // gradient segments: lt.w, lu<idx>.w2, lu<idx>.wt, lb.w, ld<i>.wshort + .w1, a site's gamma / beta
+    TB_NKINDS
+};
+inline int tbuf(int kind, int index = 0) { return kind * 32 + index; }
+// Event ids: begin, packed, join0 / join1, then per slot dz, gs, side, aux, then skip<idx> per up layer
+enum { TE_BEGIN = 0, TE_PACKED = 1, TE_JOIN = 2, TE_DZ = 4, TE_GS = TE_DZ + kSlots, TE_SIDE = TE_GS + kSlots, TE_AUX = TE_SIDE + kSlots,
+       TE_SKIP = TE_AUX + kSlots };
+struct TStep {
+    unsigned char op, site, stream;          // site: of T_HEAD / T_DZ / T_WG_* / T_CV_* / T_S2D / T_GSP, else 0
+    unsigned char nwait, nrec, nr, nw;
+    unsigned char wait[3], rec[2];           // event ids: waited on by `stream` before the step, recorded on it after
+    unsigned short r0, w0;                   // its reads are StepPlan::bufs[r0, r0 + nr), its writes bufs[w0, w0 + nw)
+};
+struct StepPlan {
+    std::vector<TStep> steps;                // in host enqueue order
+    std::vector<unsigned short> bufs;
+    int L = 0, nevents = 0;
+    int rd(const TStep& s, int k) const { return bufs[s.r0 + k]; }
+    int wr(const TStep& s, int k) const { return bufs[s.w0 + k]; }
+};
+struct StepEnv {                             // what the schedule depends on
+    int L = 0;
+    bool hconv = true, wg_planes = true, reg = false;
+    bool skip_split[kMaxLayers] = {}, T_split[kMaxLayers] = {};   // c_dg_skip[idx] / c_dg_T[idx] took the split-precision route
+};
+StepPlan step_plan(const StepEnv& env);
+std::string step_describe(const StepPlan& p);   // one line per step: "op site stream; wait e..; record e..; r buf..; w buf.."
+
 // ---- umx_engine.hip
 // Device memory of a context: ctx->mem (DevArena above).  Resident buffers -- weights, epilogue constants, stage lists, head
 // fragments, the zero line and the range flags -- are uploaded or cleared at create and never refilled; everything else is

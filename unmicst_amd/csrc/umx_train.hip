@@ -1,5 +1,6 @@
 // libumx training step: host side (the graphs' builds, buffers, launch sequence) and the C ABI of include/umx_train.h.  The plan of one
-// convolution is umx_tconv.hip's, of one weight gradient umx_wgrad.hip's; the device arena is umx_arena.hip.
+// convolution is umx_tconv.hip's, of one weight gradient umx_wgrad.hip's, the v2 step's stream schedule umx_tstep.hip's; the device
+// arena is umx_arena.hip.
 //
 // The step is written out layer by layer rather than as a generic autograd tape: the v2 graph is fixed
 // (reference UnMicst1-5.py:83-237), so every tensor the backward pass needs is known at create time and lives in a
@@ -57,8 +58,6 @@ struct Act {                         // one fp32 NHWC tensor of the step and wha
     size_t npix(int B) const { return (size_t)B * S * S; }
     Act without_planes() const { Act a = *this; a.h = H16(); return a; }
 };
-
-constexpr int kSlots = 4;   // dz / gS buffers the main stream may run ahead of the weight gradients by
 
 struct GradSlot {                    // a gradient buffer the layers take turns in
     float* x = nullptr;              // fp32, max_act floats
@@ -127,16 +126,12 @@ struct umx_trainer {
     std::vector<float*> dskip;          // gradient w.r.t. ds[idx] from the up path (idx >= 1)
     float *DA = nullptr, *DB = nullptr;
     GradSlot dz[kSlots];       // gradient w.r.t. a conv output, one per slot: the weight gradients of layer l run on a side stream
-    GradSlot gs[kSlots];       // while the main stream moves on to layers l+1 .. l+nslots-1 (legacy: a chain alternates between dz[0] and
-    int nslots = kSlots;       // dz[1]; gs[0] is the transposed conv's space-to-depth gradient)
-    hipStream_t side = nullptr;
-    hipStream_t side2 = nullptr;          // a second side stream: the dz / gS slots alternate between the two
-    hipEvent_t ev_join2 = nullptr;
-    hipEvent_t ev_dz[kSlots] = {}, ev_gs[kSlots] = {}, ev_side[kSlots] = {}, ev_join = nullptr;
-    hipStream_t aux = nullptr;                    // the skip connections' input gradients: needed only on the way back down the U, so
-    hipEvent_t ev_aux[kSlots] = {};               // they leave the main stream's dependent chain (slot free again / gradient ready)
-    std::vector<hipEvent_t> ev_skip;
-    bool overlap = true;
+    GradSlot gs[kSlots];       // while the main stream moves on to layers l+1 .. l+kSlots-1 (legacy: a chain alternates between dz[0] and
+                               // dz[1]; gs[0] is the transposed conv's space-to-depth gradient)
+    StepPlan plan;                                  // the v2 step's schedule (umx_tstep.hip), built once at create: enqueue_step walks it
+    hipStream_t streams[kStepStreams] = {};         // by TStream: [TS_MAIN] == stream, the two side streams, the aux stream
+    std::vector<hipEvent_t> events;                 // by the plan's event ids
+    bool serial = false;                            // umx_test_trainer_serial: every step on the main stream in plan order, no events
     double* d_part = nullptr;  size_t part_doubles = 0;
     double* d_part2 = nullptr;          // the side stream's own partial sums (regularisation loss under the forward pass)
     double* d_loss = nullptr;           // [0] data term, [1] regularisation
@@ -164,7 +159,6 @@ struct umx_trainer {
     RepackDesc* d_rdescs = nullptr;
     int max_refs = 0;
     int n_fwd_packs = 0, n_fwd_rdescs = 0;   // descriptors [0, n_fwd) serve the forward pass, the rest the backward pass only
-    hipEvent_t ev_begin = nullptr, ev_packed = nullptr;
     float* d_xinv = nullptr;            // [2 * kSlots] inverse scales of the dz / gS slots' planes, written by split_dyn_kernel
     // launches
     std::vector<TConv> c_fwd_d, c_dg_d, c_T, c_fwd_u, c_dg_us, c_dg_skip, c_dg_T;
@@ -408,14 +402,10 @@ int to_h16(umx_trainer* tr, const Act& a, hipStream_t st, bool omax = false) {
 int pack_all(umx_trainer* tr, hipStream_t st, int part);
 int refresh_wscales(umx_trainer* tr);
 
-// the K-split scratch of the stream a convolution is enqueued on (one per stream)
-float* split_scratch(const umx_trainer* tr, hipStream_t st) { return st == tr->stream ? tr->d_split : st == tr->aux ? tr->d_split3 : tr->d_split2; }
-
 // a convolution on stream st, on whichever route its plan took: conv_f16x3 reads the (hi, lo) planes of src (+ src1; src.inv: the
 // inverse scale of its planes where they hold a gradient), conv_mfma_f32 their fp32 tensors.  A K-split launch writes raw partial
-// sums to the stream's scratch, then the ordered reduce applies the activation.
-int run_tconv(umx_trainer* tr, TConv& tc, const Act& src, float* dst, const Act* src1, hipStream_t st) {
-    float* const scratch = split_scratch(tr, st);
+// sums to `scratch` (one per stream: d_split is the main stream's), then the ordered reduce applies the activation.
+int run_tconv(umx_trainer* tr, TConv& tc, const Act& src, float* dst, const Act* src1, hipStream_t st, float* scratch) {
     if (tc.hidx < 0) {
         ConvParams p = tc.cp;
         p.src[0] = src.x;
@@ -454,6 +444,10 @@ int run_tconv(umx_trainer* tr, TConv& tc, const Act& src, float* dst, const Act*
     }
     T_HIP(tr, launch_conv_f16(p, st));
     return UMX_OK;
+}
+
+int run_tconv(umx_trainer* tr, TConv& tc, const Act& src, float* dst, const Act* src1, hipStream_t st) {   // (on the main stream)
+    return run_tconv(tr, tc, src, dst, src1, st, tr->d_split);
 }
 
 // an activation written by a kernel without a plane writer (the input batch, the transposed convolutions' outputs): its max |x|
@@ -541,9 +535,9 @@ int bn_backward(umx_trainer* tr, BnSite& s, const ActParams& a, const float* dy0
 }
 
 // (where both operands have (hi, lo) planes the split-precision kernel stages from them -- half the bytes, no conversion -- and undoes
-// the inverse scales they were stored with)
+// the inverse scales they were stored with; ws: the slice workspace of the stream it runs on)
 int run_wgrad(umx_trainer* tr, const WgradPlan& w, const Act& X, const Act& G, int Ctot, int c_off, size_t w_off, float reg,
-              size_t pair_off /* SIZE_MAX: none */, hipStream_t stream) {
+              size_t pair_off /* SIZE_MAX: none */, float* ws, hipStream_t stream) {
     WgradOperands o = {};
     o.X = X.x;
     o.G = G.x;
@@ -553,7 +547,7 @@ int run_wgrad(umx_trainer* tr, const WgradPlan& w, const Act& X, const Act& G, i
         o.Ghi = G.h.hi; o.Glo = G.h.lo; o.GCs = G.h.Cs;
         o.xinv = X.inv; o.ginv = G.inv;
     }
-    o.ws = stream == tr->side2 ? tr->d_ws2 : tr->d_ws;   // (each side stream has its own slice workspace)
+    o.ws = ws;
     o.xmax = X.max;
     o.gmax = G.max;
     o.overflow = reinterpret_cast<int*>(tr->d_maxw + tr->n_maxw);
@@ -659,137 +653,112 @@ int step_end(umx_trainer* tr, bool update) {
     return UMX_OK;
 }
 
+struct SiteRef { BnSite* s; int pool, act; float rate; int layer_id; };   // a BN site of the plan and its activation in this graph
+SiteRef site_ref(umx_trainer* tr, int site) {
+    const int L = tr->L, i = 2 * L - site;
+    if (site == site_top(L)) return {&tr->bn_t, 0, ACT_NONE, 0.f, 0};
+    if (site == site_bottom(L)) return {&tr->bn_b, 0, ACT_LEAKY, tr->o.drop_bottom, LAYER_BOTTOM};
+    if (site < L) return {&tr->bn_u[site], 0, ACT_LEAKY, up_rate(tr, site), LAYER_UP + site};
+    return {&tr->bn_d[i], 1, ACT_LEAKY, down_rate(tr, i), LAYER_DOWN + i};
+}
+
+// A buffer of a step at `site` by its id in the plan (umx_tstep.hip): an activation with its planes and max word; a dz slot as the
+// site's gradient w.r.t. its conv output (down layer 0: no convolution reads dz's planes, so none are written, and the weight
+// gradient stages from the fp32 tensors); a gS slot as up layer `site`'s space-to-depth gradient; anything else as its pointer in .x.
+// enqueue_step takes every operand it hands to a helper from here: a step cannot touch a buffer its plan line does not declare.
+Act buffer(umx_trainer* tr, int id, int site) {
+    const int k = id % 32, idx = std::min(site, tr->L - 1);
+    const BnSite& s = *site_ref(tr, site).s;
+    float* raw = nullptr;
+    switch (id / 32) {
+    case TB_DS: return tr->ds[k];
+    case TB_US: return tr->us[k];
+    case TB_CV: return tr->cv[k];
+    case TB_ACTB: return tr->act_b;
+    case TB_DZ: return tr->dz[k].view(s.H, s.C, s.gmax, site != site_down(tr->L, 0));
+    case TB_GS: return tr->gs[k].view(tr->us[idx].S / 2, 4 * tr->n[idx + 1], tr->smax[idx]);
+    case TB_DA: raw = tr->DA; break;
+    case TB_DB: raw = tr->DB; break;
+    case TB_DT: raw = tr->d_dt; break;
+    case TB_DSKIP: raw = tr->dskip[k]; break;
+    case TB_PART: raw = reinterpret_cast<float*>(tr->d_part); break;
+    case TB_PART2: raw = reinterpret_cast<float*>(tr->d_part2); break;
+    case TB_WS: raw = tr->d_ws; break;
+    case TB_WS2: raw = tr->d_ws2; break;
+    case TB_SPLIT: raw = tr->d_split; break;
+    case TB_SPLIT2: raw = tr->d_split2; break;
+    case TB_SPLIT3: raw = tr->d_split3; break;
+    }   // (z / stat / m12, the packs, the loss words and the gradient segments reach their kernels through the site, the descriptors and
+    return Act{raw};   // the parameter offsets: declared for the hazard check, never resolved)
+}
+
+// One v2 training step: a walk over the plan.  Per step: its stream waits on the step's events, the step's helper is enqueued on it
+// with the buffers the step names, and the step's events are recorded.  Which wait protects which buffer is the plan's business
+// (step_plan; tests/test_step_plan_cpu.py checks it); every kernel has a fixed summation order, so the step is bit-reproducible and
+// equal to the serial walk (tr->serial: everything on the main stream in plan order).
 int enqueue_step(umx_trainer* tr, const float* data, const float* labels, const float* weights, bool update) {
-    const int L = tr->L, K = tr->K, B = tr->B, P = tr->P;
-    hipStream_t st = tr->stream;
+    const StepPlan& p = tr->plan;
     const umx_train_options& o = tr->o;
-    const size_t Npix = (size_t)B * P * P;
-    T_TRY(step_begin(tr, update));
-    if (tr->overlap) {
-        // the side stream is idle until the first weight gradient: it packs the backward pass's operands and sums the regularisation
-        // loss (both need nothing but this step's weights) while the main stream runs the forward pass
-        T_HIP(tr, hipEventRecord(tr->ev_begin, st));
-        T_HIP(tr, hipStreamWaitEvent(tr->side, tr->ev_begin, 0));
-        T_TRY(pack_all(tr, st, 0));
-        T_TRY(pack_all(tr, tr->side, 1));
-        if (o.reg_kind != UMX_REG_NONE)
-            T_HIP(tr, launch_reg_loss(tr->d_regsegs, tr->n_regsegs, o.reg_kind, tr->d_part2, tr->d_loss, 1, tr->side));
-        T_HIP(tr, hipEventRecord(tr->ev_packed, tr->side));
-    } else {
-        T_TRY(pack_all(tr, st, 2));
-    }
-
-    T_TRY(forward_pass(tr, data, true, update));
-    BnSite& t = tr->bn_t;
-    T_TRY(loss_head(tr, t.z, t.stat, labels, weights));
-    if (o.reg_kind != UMX_REG_NONE && !tr->overlap)
-        T_HIP(tr, launch_reg_loss(tr->d_regsegs, tr->n_regsegs, o.reg_kind, tr->d_part, tr->d_loss, 1, st));
-    if (tr->overlap) T_HIP(tr, hipStreamWaitEvent(st, tr->ev_packed, 0));   // the backward pass's operands are in place
-    if (tr->prof) T_HIP(tr, hipEventRecord(tr->ev[1], st));
-
-    // ------------------------------------------------------------------ backward
-    {   // top layer: softmax/CE gradient -> BN -> 1x1 conv
-        ActParams a = act_params(tr, t, 0, ACT_NONE, 0.f, 0);
-        T_TRY(bn_backward(tr, t, a, tr->d_dt, nullptr, Act{tr->d_dt}));   // in place: dt -> dt0
-        const int nblk = chan_blocks(Npix, tr->n[1]);
-        T_HIP(tr, launch_head_bwd(tr->cv[0].x, tr->d_dt, tr->d_w + tr->o_lt, Npix, tr->n[1], K, tr->DA, tr->d_part, nblk, st));
-        T_HIP(tr, launch_reduce_partials(tr->d_part, nblk, tr->n[1] * K, 1.0, tr->d_g + tr->o_lt, tr->d_w + tr->o_lt,
-                                         o.reg_top > 0.f ? o.reg_kind : 0, o.reg_top, st));
-    }
-    // The weight gradients hang off the critical path (gradient w.r.t. conv output -> input gradient -> next layer):
-    // they run on a side stream against double-buffered dz / gS while the main stream continues.  Ordering is by events
-    // only; every kernel still has a fixed summation order, so the step stays bit-reproducible.
-    // (two side streams, one per dz / gS slot: consecutive layers' weight gradients -- small grids that leave most CUs idle at a batch
-    // of 8 -- run next to each other as well as next to the main stream)
-    hipStream_t wss[2] = {tr->overlap ? tr->side : st, tr->overlap ? (tr->side2 ? tr->side2 : tr->side) : st};
-#define ws wss[slot & 1]
-    int slot = 0;
-    bool used[kSlots] = {}, aux_used[kSlots] = {};
-    const bool use_aux = tr->overlap && tr->aux && tr->hconv;
-    // the gradient w.r.t. site s's conv output from dy0 (+ dy1), into the current slot (planes: with its (hi, lo) planes): *dz is the
-    // slot's view of it
-    auto dz_slot = [&](BnSite& s, const ActParams& a, const float* dy0, const float* dy1, bool planes, Act* dz) -> int {
-        // main: the slot's previous consumers on the side and aux streams are done
-        if (tr->overlap && used[slot]) T_HIP(tr, hipStreamWaitEvent(st, tr->ev_side[slot], 0));
-        if (aux_used[slot]) { T_HIP(tr, hipStreamWaitEvent(st, tr->ev_aux[slot], 0)); aux_used[slot] = false; }
-        *dz = tr->dz[slot].view(s.H, s.C, s.gmax, planes);
-        T_TRY(bn_backward(tr, s, a, dy0, dy1, *dz));
-        if (tr->overlap) {   // main has written the slot; the side stream may read it
-            T_HIP(tr, hipEventRecord(tr->ev_dz[slot], st));
-            T_HIP(tr, hipStreamWaitEvent(ws, tr->ev_dz[slot], 0));
+    const int L = tr->L, K = tr->K;
+    const std::vector<int>& n = tr->n;
+    const size_t Npix = (size_t)tr->B * tr->P * tr->P;
+    for (const TStep& s : p.steps) {
+        hipStream_t st = tr->streams[tr->serial ? TS_MAIN : s.stream];
+        for (int k = 0; k < s.nwait && !tr->serial; ++k) T_HIP(tr, hipStreamWaitEvent(st, tr->events[s.wait[k]], 0));
+        const SiteRef sr = site_ref(tr, s.site);
+        const int idx = s.site < L ? s.site : 0, i = s.site > L ? 2 * L - s.site : 0;   // the up / down layer of a step that has one
+        const int Cskip = n[idx], Cup = n[idx + 1];
+        auto R = [&](int k) { return buffer(tr, p.rd(s, k), s.site); };
+        auto W = [&](int k) { return buffer(tr, p.wr(s, k), s.site); };
+        auto wgrad = [&](const WgradPlan& w, const Act& X, int Ctot, int c_off, size_t w_off, float reg, size_t pair = SIZE_MAX) {
+            return run_wgrad(tr, w, X, R(1), Ctot, c_off, w_off, reg, pair, W(1).x, st);
+        };
+        auto conv = [&](TConv& tc) { return run_tconv(tr, tc, R(0), W(0).x, nullptr, st, W(1).x); };
+        switch (s.op) {
+        case T_BEGIN: T_TRY(step_begin(tr, update)); break;
+        case T_PACK0: T_TRY(pack_all(tr, st, 0)); break;
+        case T_PACK1: T_TRY(pack_all(tr, st, 1)); break;
+        case T_REG: T_HIP(tr, launch_reg_loss(tr->d_regsegs, tr->n_regsegs, o.reg_kind, reinterpret_cast<double*>(W(0).x), tr->d_loss, 1, st)); break;
+        case T_FWD: T_TRY(forward_pass(tr, data, true, update)); break;
+        case T_LOSS: T_TRY(loss_head(tr, tr->bn_t.z, tr->bn_t.stat, labels, weights)); break;
+        case T_MARK: if (tr->prof) T_HIP(tr, hipEventRecord(tr->ev[1], st)); break;
+        case T_HEAD: {   // top layer: softmax/CE gradient -> BN (in place: dt -> dt0) -> 1x1 conv
+            float* const dt = R(0).x;
+            double* const part = reinterpret_cast<double*>(W(2).x);
+            const int nblk = chan_blocks(Npix, n[1]);
+            T_TRY(bn_backward(tr, *sr.s, act_params(tr, *sr.s, 0, ACT_NONE, 0.f, 0), dt, nullptr, Act{dt}));
+            T_HIP(tr, launch_head_bwd(R(3).x, dt, tr->d_w + tr->o_lt, Npix, n[1], K, W(3).x, part, nblk, st));
+            T_HIP(tr, launch_reduce_partials(part, nblk, n[1] * K, 1.0, tr->d_g + tr->o_lt, tr->d_w + tr->o_lt,
+                                             o.reg_top > 0.f ? o.reg_kind : 0, o.reg_top, st));
+            break;
         }
-        return UMX_OK;
-    };
-    auto side_done = [&](int sl) -> int {
-        if (tr->overlap) T_HIP(tr, hipEventRecord(tr->ev_side[sl], wss[sl & 1]));
-        used[sl] = true;
-        return UMX_OK;
-    };
-    for (int idx = 0; idx < L; ++idx) {    // up layers, output side first
-        BnSite& s = tr->bn_u[idx];
-        const int Cskip = tr->n[idx], Cup = tr->n[idx + 1], Sh = tr->us[idx].S / 2;
-        const Act& layer_in = idx == L - 1 ? tr->act_b : tr->cv[idx + 1];
-        Act dz;
-        T_TRY(dz_slot(s, act_params(tr, s, 0, ACT_LEAKY, up_rate(tr, idx), LAYER_UP + idx), tr->DA, nullptr, true, &dz));
-        T_TRY(run_wgrad(tr, tr->wg_u0[idx], tr->ds[idx], dz, Cskip + Cup, 0, tr->o_w2[idx], o.reg_up, SIZE_MAX, ws));
-        T_TRY(run_wgrad(tr, tr->wg_u1[idx], tr->us[idx], dz, Cskip + Cup, Cskip, tr->o_w2[idx], o.reg_up, SIZE_MAX, ws));
-        T_TRY(run_tconv(tr, tr->c_dg_us[idx], dz, tr->DB, nullptr, st));
-        if (idx >= 1 && use_aux && tr->c_dg_skip[idx].hidx >= 0) {   // (on the weight gradients' stream it was 2 % slower; this stream is its own)
-            T_HIP(tr, hipStreamWaitEvent(tr->aux, tr->ev_dz[slot], 0));
-            T_TRY(run_tconv(tr, tr->c_dg_skip[idx], dz, tr->dskip[idx], nullptr, tr->aux));
-            T_HIP(tr, hipEventRecord(tr->ev_aux[slot], tr->aux));
-            T_HIP(tr, hipEventRecord(tr->ev_skip[idx], tr->aux));
-            aux_used[slot] = true;
-        } else if (idx >= 1) {
-            T_TRY(run_tconv(tr, tr->c_dg_skip[idx], dz, tr->dskip[idx], nullptr, st));
+        case T_DZ:
+            T_TRY(bn_backward(tr, *sr.s, act_params(tr, *sr.s, sr.pool, sr.act, sr.rate, sr.layer_id), R(0).x, s.nr > 3 ? R(3).x : nullptr, W(0)));
+            break;
+        case T_WG_U0: T_TRY(wgrad(tr->wg_u0[idx], R(0), Cskip + Cup, 0, tr->o_w2[idx], o.reg_up)); break;
+        case T_WG_U1: T_TRY(wgrad(tr->wg_u1[idx], R(0), Cskip + Cup, Cskip, tr->o_w2[idx], o.reg_up)); break;
+        case T_WG_T: {   // (the transposed convolution's filter: X is gS, G the layer's input)
+            const bool gs_planes = tr->hconv && (tr->c_dg_T[idx].hidx >= 0 || tr->wg_planes);
+            T_TRY(wgrad(tr->wg_T[idx], gs_planes ? R(0) : R(0).without_planes(), Cup, 0, tr->o_wt[idx], o.reg_up));
+            break;
         }
-        const Act gs = tr->gs[slot].view(Sh, 4 * Cup, tr->smax[idx]);
-        T_HIP(tr, launch_leaky_bwd_s2d_max(tr->DB, tr->us[idx].x, B, Sh, Cup, 0.2f, gs.x, gs.max, st));
-        const bool gs_planes = tr->hconv && (tr->c_dg_T[idx].hidx >= 0 || tr->wg_planes);
-        // (in front of the event: the transposed convolution's weight gradient stages from these planes too)
-        if (gs_planes) T_TRY(to_h16(tr, gs, st));
-        if (tr->overlap) {
-            T_HIP(tr, hipEventRecord(tr->ev_gs[slot], st));
-            T_HIP(tr, hipStreamWaitEvent(ws, tr->ev_gs[slot], 0));
+        case T_WG_B: T_TRY(wgrad(tr->wg_b, R(0), n[L], 0, tr->o_lb, o.reg_bottom)); break;
+        case T_WG_D:   // c00 + shortcut = conv(x, W1 + Wshort): both filters receive the same data gradient (UnMicst1-5.py:102-114)
+            T_TRY(wgrad(tr->wg_d[i], i >= 1 ? R(0) : R(0).without_planes(), n[i], 0, tr->o_ws[i], o.reg_down, tr->o_w1[i]));
+            break;
+        case T_CV_US: T_TRY(conv(tr->c_dg_us[idx])); break;
+        case T_CV_SKIP: T_TRY(conv(tr->c_dg_skip[idx])); break;
+        case T_CV_T: T_TRY(conv(tr->c_dg_T[idx])); break;
+        case T_CV_B: T_TRY(conv(tr->c_dg_b)); break;
+        case T_CV_D: T_TRY(conv(tr->c_dg_d[i])); break;
+        case T_S2D: T_HIP(tr, launch_leaky_bwd_s2d_max(R(0).x, R(1).x, tr->B, W(0).S, Cup, 0.2f, W(0).x, W(0).max, st)); break;
+        case T_GSP: T_TRY(to_h16(tr, W(0), st)); break;
+        case T_JOIN: break;
+        case T_OPT: T_TRY(step_end(tr, update)); break;
         }
-        // (the transposed convolution's filter: X is gS, G the layer's input)
-        T_TRY(run_wgrad(tr, tr->wg_T[idx], gs_planes ? gs : gs.without_planes(), layer_in, Cup, 0, tr->o_wt[idx], o.reg_up, SIZE_MAX, ws));
-        T_TRY(side_done(slot));
-        T_TRY(run_tconv(tr, tr->c_dg_T[idx], gs, tr->DA, nullptr, st));
-        slot = (slot + 1) % tr->nslots;
+        for (int k = 0; k < s.nrec && !tr->serial; ++k) T_HIP(tr, hipEventRecord(tr->events[s.rec[k]], st));
     }
-    {   // bottom layer
-        Act dz;
-        T_TRY(dz_slot(tr->bn_b, act_params(tr, tr->bn_b, 0, ACT_LEAKY, o.drop_bottom, LAYER_BOTTOM), tr->DA, nullptr, true, &dz));
-        T_TRY(run_wgrad(tr, tr->wg_b, tr->ds[L], dz, tr->n[L], 0, tr->o_lb, o.reg_bottom, SIZE_MAX, ws));
-        T_TRY(side_done(slot));
-        T_TRY(run_tconv(tr, tr->c_dg_b, dz, tr->DB, nullptr, st));
-        slot = (slot + 1) % tr->nslots;
-    }
-    for (int i = L - 1; i >= 0; --i) {     // down layers
-        BnSite& s = tr->bn_d[i];
-        const float* dy1 = (i + 1 <= L - 1) ? tr->dskip[i + 1] : nullptr;
-        if (dy1 && use_aux && tr->c_dg_skip[i + 1].hidx >= 0) T_HIP(tr, hipStreamWaitEvent(st, tr->ev_skip[i + 1], 0));
-        // (layer 0: no convolution reads dz's planes, so none are written, and the weight gradient stages from the fp32 tensors)
-        Act dz;
-        T_TRY(dz_slot(s, act_params(tr, s, 1, ACT_LEAKY, down_rate(tr, i), LAYER_DOWN + i), tr->DB, dy1, i >= 1, &dz));
-        // c00 + shortcut = conv(x, W1 + Wshort): both filters receive the same data gradient (UnMicst1-5.py:102-114)
-        T_TRY(run_wgrad(tr, tr->wg_d[i], i >= 1 ? tr->ds[i] : tr->ds[i].without_planes(), dz, tr->n[i], 0, tr->o_ws[i], o.reg_down,
-                        tr->o_w1[i], ws));
-        T_TRY(side_done(slot));
-        if (i >= 1) T_TRY(run_tconv(tr, tr->c_dg_d[i], dz, tr->DB, nullptr, st));
-        slot = (slot + 1) % tr->nslots;
-    }
-#undef ws
-    if (tr->overlap) {   // join: the optimiser (and the caller) see every gradient
-        T_HIP(tr, hipEventRecord(tr->ev_join, wss[0]));
-        T_HIP(tr, hipStreamWaitEvent(st, tr->ev_join, 0));
-        if (wss[1] != wss[0]) {
-            T_HIP(tr, hipEventRecord(tr->ev_join2, wss[1]));
-            T_HIP(tr, hipStreamWaitEvent(st, tr->ev_join2, 0));
-        }
-    }
-    return step_end(tr, update);
+    return UMX_OK;
 }
 
 int fold_profile(umx_trainer* tr) {
@@ -1046,7 +1015,7 @@ int alloc_trainer(umx_trainer* tr) {
     T_TRY(talloc(tr, &tr->DA, max_act));
     T_TRY(talloc(tr, &tr->DB, max_act));
     std::vector<int> slots;   // dz[0], gs[0], dz[1], gs[1], ...
-    for (int sl = 0; sl < tr->nslots; ++sl) { slots.push_back(sl); slots.push_back(kSlots + sl); }
+    for (int sl = 0; sl < kSlots; ++sl) { slots.push_back(sl); slots.push_back(kSlots + sl); }
     T_TRY(alloc_slots(tr, slots, max_act));
     int maxC = K;
     for (int v : n) maxC = std::max(maxC, v);
@@ -1393,7 +1362,7 @@ int enqueue_legacy(umx_trainer* tr, const float* data, const float* labels, cons
         return to_h16(tr, *g, st);
     };
     auto wgrad = [&](const WgradPlan& w, const Act& X, const Act& G, int Ctot, int c_off, size_t w_off) -> int {
-        return run_wgrad(tr, w, X, G, Ctot, c_off, w_off, 0.f, SIZE_MAX, st);
+        return run_wgrad(tr, w, X, G, Ctot, c_off, w_off, 0.f, SIZE_MAX, tr->d_ws, st);
     };
     // the extra convolutions of a chain, last first: *g is d/dy[E] (slot 0) on entry, d/dy[e] in slot (E - e) & 1 on the way, d/dy[0] on return
     auto extras_bwd = [&](LBlock& b, Act* g) -> int {
@@ -1480,6 +1449,41 @@ int check_create(const umx_hparams* hp, const umx_train_options* opts) {
     return UMX_OK;
 }
 
+// what the v2 step's schedule depends on (after the host pass)
+StepEnv step_env(const umx_trainer* tr) {
+    StepEnv env;
+    env.L = tr->L; env.hconv = tr->hconv; env.wg_planes = tr->wg_planes; env.reg = tr->o.reg_kind != UMX_REG_NONE;
+    for (int idx = 0; idx < tr->L; ++idx) { env.skip_split[idx] = tr->c_dg_skip[idx].plan.split; env.T_split[idx] = tr->c_dg_T[idx].plan.split; }
+    return env;
+}
+
+// the test entries that run a graph's host pass alone: the trainer they plan (solo options, or the legacy graph's), on the route
+// conv_f32 / no_ksplit select (UMX_TRAIN_CONV_F32 / UMX_TRAIN_NO_KSPLIT) ...
+int plan_for_test(umx_trainer* tr, const char* who, const umx_hparams* hp, int B, int conv_f32, int no_ksplit, const float* blob,
+                  size_t blob_floats, char* text, size_t cap, size_t* needed) {
+    if (!hp || !blob || !needed || (!text && cap)) return umx::fail(nullptr, UMX_ERR_INVALID, "%s: null argument", who);
+    *needed = 0;
+    umx_train_options o;
+    if (hp->graph == UMX_GRAPH_LEGACY) umx_train_options_legacy(&o); else umx_train_options_solo(&o);
+    if (const int rc = check_create(hp, &o)) return umx::fail(nullptr, rc, "%s", g_terr.c_str());
+    tr->hp = *hp;
+    tr->o = o;
+    tr->B = B > 0 ? B : 8;
+    tr->legacy = hp->graph == UMX_GRAPH_LEGACY;
+    tr->hconv = !conv_f32;
+    tr->no_ksplit = no_ksplit != 0;
+    const int rc = tr->legacy ? plan_legacy(tr, blob, blob_floats) : plan_trainer(tr, blob, blob_floats);
+    return rc == UMX_OK ? UMX_OK : umx::fail(nullptr, rc, "%s", tr->err.c_str());
+}
+
+// ... and the text they return.  *needed: bytes of the text with its terminator; UMX_ERR_INVALID where cap is smaller.
+int text_out(const char* who, const std::string& out, char* text, size_t cap, size_t* needed) {
+    *needed = out.size() + 1;
+    if (cap < *needed) return umx::fail(nullptr, UMX_ERR_INVALID, "%s: the text takes %zu bytes", who, *needed);
+    memcpy(text, out.c_str(), *needed);
+    return UMX_OK;
+}
+
 }  // namespace
 
 // ---- the internal interface of umx_trainset.hip (umx_internal.h) ----
@@ -1541,7 +1545,7 @@ int trainer_eval_end(umx_trainer* tr) {
 int trainer_guard_check(umx_trainer* tr) {
     if (tr->mem.fill < 0) return UMX_OK;
     T_HIP(tr, hipSetDevice(tr->device));
-    for (hipStream_t s : {tr->stream, tr->side, tr->side2, tr->aux})
+    for (hipStream_t s : tr->streams)
         if (s) T_HIP(tr, hipStreamSynchronize(s));
     std::string msg;
     const int rc = arena_check(tr->mem, &msg);
@@ -1604,25 +1608,19 @@ int umx_trainer_create(const umx_hparams* hp, const float* weight_blob, size_t b
     if (rc == UMX_OK && hipSetDevice(tr->device) != hipSuccess) rc = tfail(tr, UMX_ERR_HIP, "hipSetDevice failed");
     if (rc == UMX_OK && hipStreamCreateWithFlags(&tr->stream, hipStreamNonBlocking) != hipSuccess)
         rc = tfail(tr, UMX_ERR_HIP, "hipStreamCreate failed");
+    tr->streams[TS_MAIN] = tr->stream;
     select_route(tr);
     if (rc == UMX_OK) rc = legacy ? build_legacy(tr, weight_blob, blob_floats) : build_trainer(tr, weight_blob, blob_floats);
     if (rc == UMX_OK)
         for (int i = 0; i < 4; ++i)
             if (hipEventCreate(&tr->ev[i]) != hipSuccess) rc = tfail(tr, UMX_ERR_HIP, "hipEventCreate failed");
-    if (rc == UMX_OK) {
-        tr->overlap = true;
-        if (hipStreamCreateWithFlags(&tr->side, hipStreamNonBlocking) != hipSuccess) rc = tfail(tr, UMX_ERR_HIP, "hipStreamCreate failed");
-        if (hipStreamCreateWithFlags(&tr->side2, hipStreamNonBlocking) != hipSuccess)
-            rc = tfail(tr, UMX_ERR_HIP, "hipStreamCreate failed");
-        if (hipStreamCreateWithFlags(&tr->aux, hipStreamNonBlocking) != hipSuccess)
-            rc = tfail(tr, UMX_ERR_HIP, "hipStreamCreate failed");
-        tr->ev_skip.assign(32, nullptr);
-        std::vector<hipEvent_t*> evs = {&tr->ev_join, &tr->ev_begin, &tr->ev_packed, &tr->ev_join2};
-        for (hipEvent_t& e : tr->ev_skip) evs.push_back(&e);
-        for (int sl = 0; sl < kSlots; ++sl) evs.push_back(&tr->ev_aux[sl]);
-        for (int sl = 0; sl < kSlots; ++sl) { evs.push_back(&tr->ev_dz[sl]); evs.push_back(&tr->ev_gs[sl]); evs.push_back(&tr->ev_side[sl]); }
-        for (hipEvent_t* e : evs)
-            if (rc == UMX_OK && hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess)
+    if (rc == UMX_OK) {   // the side and aux streams, and (v2) the step's schedule with its events
+        for (int k = TS_MAIN + 1; k < kStepStreams; ++k)
+            if (hipStreamCreateWithFlags(&tr->streams[k], hipStreamNonBlocking) != hipSuccess) rc = tfail(tr, UMX_ERR_HIP, "hipStreamCreate failed");
+        if (!legacy) tr->plan = step_plan(step_env(tr));
+        tr->events.assign(tr->plan.nevents, nullptr);
+        for (hipEvent_t& e : tr->events)
+            if (rc == UMX_OK && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess)
                 rc = tfail(tr, UMX_ERR_HIP, "hipEventCreate failed");
     }
     if (rc != UMX_OK) {
@@ -1636,26 +1634,20 @@ int umx_trainer_create(const umx_hparams* hp, const float* weight_blob, size_t b
     return UMX_OK;
 }
 
+int umx_test_trainer_serial(umx_trainer* tr, int on) {
+    if (!tr) return tfail(tr, UMX_ERR_INVALID, "null argument");
+    tr->serial = on != 0;
+    return UMX_OK;
+}
+
 // The host pass of umx_trainer_create alone (no device): one line per forward / input-gradient convolution, in build order -- its
 // UMX_DEBUG_PLAN text, then its groups (as the master tensors see them), the fused activation, `direct`, the weight shift, the counts of pack descriptors and weight references, the K-split
 // scratch and tconv_digest of everything upload_conv would send.  conv_f32 / no_ksplit: the routes UMX_TRAIN_CONV_F32 /
 // UMX_TRAIN_NO_KSPLIT select.  *needed: bytes of the text with its terminator; UMX_ERR_INVALID where cap is smaller.
 int umx_test_train_plan(const umx_hparams* hp, int B, int conv_f32, int no_ksplit, const float* blob, size_t blob_floats, char* text,
                         size_t cap, size_t* needed) {
-    if (!hp || !blob || !needed || (!text && cap)) return umx::fail(nullptr, UMX_ERR_INVALID, "umx_test_train_plan: null argument");
-    *needed = 0;
-    umx_train_options o;
-    if (hp->graph == UMX_GRAPH_LEGACY) umx_train_options_legacy(&o); else umx_train_options_solo(&o);
-    if (const int rc = check_create(hp, &o)) return umx::fail(nullptr, rc, "%s", g_terr.c_str());
     umx_trainer tr;
-    tr.hp = *hp;
-    tr.o = o;
-    tr.B = B > 0 ? B : 8;
-    tr.legacy = hp->graph == UMX_GRAPH_LEGACY;
-    tr.hconv = !conv_f32;
-    tr.no_ksplit = no_ksplit != 0;
-    const int rc = tr.legacy ? plan_legacy(&tr, blob, blob_floats) : plan_trainer(&tr, blob, blob_floats);
-    if (rc != UMX_OK) return umx::fail(nullptr, rc, "%s", tr.err.c_str());
+    if (const int rc = plan_for_test(&tr, "umx_test_train_plan", hp, B, conv_f32, no_ksplit, blob, blob_floats, text, cap, needed)) return rc;
     std::string out;
     for (const TConv* tc : planned_convs(&tr)) {
         const TConvPlan& p = tc->plan;
@@ -1677,10 +1669,18 @@ int umx_test_train_plan(const umx_hparams* hp, int B, int conv_f32, int no_kspli
                  tconv_digest(p.cp, p.nt, p.hpix, p.packs.data(), p.packs.size(), p.split ? &p.P : nullptr));
         out += p.text + buf;
     }
-    *needed = out.size() + 1;
-    if (cap < *needed) return umx::fail(nullptr, UMX_ERR_INVALID, "umx_test_train_plan: the text takes %zu bytes", *needed);
-    memcpy(text, out.c_str(), *needed);
-    return UMX_OK;
+    return text_out("umx_test_train_plan", out, text, cap, needed);
+}
+
+// The schedule of the v2 training step for these hyper-parameters on a route (conv_f32 / no_ksplit as above), with (reg) or without a
+// regulariser: the host pass, then step_plan's lines (step_describe).  No device.
+int umx_test_step_plan(const umx_hparams* hp, int B, int conv_f32, int no_ksplit, int reg, const float* blob, size_t blob_floats,
+                       char* text, size_t cap, size_t* needed) {
+    umx_trainer tr;
+    if (const int rc = plan_for_test(&tr, "umx_test_step_plan", hp, B, conv_f32, no_ksplit, blob, blob_floats, text, cap, needed)) return rc;
+    if (tr.legacy) return umx::fail(nullptr, UMX_ERR_INVALID, "umx_test_step_plan: the legacy step has no schedule (one stream, no events)");
+    if (!reg) tr.o.reg_kind = UMX_REG_NONE;
+    return text_out("umx_test_step_plan", step_describe(step_plan(step_env(&tr))), text, cap, needed);
 }
 
 int umx_trainer_init(umx_trainer* tr, const umx_init_options* init) {
@@ -1711,7 +1711,7 @@ int umx_trainer_init(umx_trainer* tr, const umx_init_options* init) {
     if (pos != tr->nparams || tab.empty()) return tfail(tr, UMX_ERR_INVALID, "parameter segments cover %llu of %zu floats", pos, tr->nparams);
     T_HIP(tr, hipSetDevice(tr->device));
     T_TRY(fold_profile(tr));
-    for (hipStream_t s : {tr->stream, tr->side, tr->side2, tr->aux})
+    for (hipStream_t s : tr->streams)
         if (s) T_HIP(tr, hipStreamSynchronize(s));
     if (!tr->d_initsegs) {
         T_TRY(talloc(tr, &tr->d_initsegs, tab.size()));
@@ -1740,18 +1740,10 @@ void umx_trainer_destroy(umx_trainer* tr) {
     arena_free(&tr->mem);
     for (int i = 0; i < 4; ++i)
         if (tr->ev[i]) (void)hipEventDestroy(tr->ev[i]);
-    if (tr->side) { (void)hipStreamSynchronize(tr->side); (void)hipStreamDestroy(tr->side); }
-    if (tr->side2) { (void)hipStreamSynchronize(tr->side2); (void)hipStreamDestroy(tr->side2); }
-    if (tr->aux) { (void)hipStreamSynchronize(tr->aux); (void)hipStreamDestroy(tr->aux); }
-    for (hipEvent_t e : {tr->ev_join, tr->ev_begin, tr->ev_packed, tr->ev_join2})
+    for (int k = TS_MAIN + 1; k < kStepStreams; ++k)
+        if (tr->streams[k]) { (void)hipStreamSynchronize(tr->streams[k]); (void)hipStreamDestroy(tr->streams[k]); }
+    for (hipEvent_t e : tr->events)
         if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : tr->ev_skip)
-        if (e) (void)hipEventDestroy(e);
-    for (int sl = 0; sl < kSlots; ++sl)
-        if (tr->ev_aux[sl]) (void)hipEventDestroy(tr->ev_aux[sl]);
-    for (int sl = 0; sl < kSlots; ++sl)
-        for (hipEvent_t e : {tr->ev_dz[sl], tr->ev_gs[sl], tr->ev_side[sl]})
-            if (e) (void)hipEventDestroy(e);
     if (tr->stream) (void)hipStreamDestroy(tr->stream);
     delete tr;
 }

@@ -28,7 +28,7 @@ EXPORTS = [
     "umx_train_options_solo", "umx_train_options_duo", "umx_train_options_legacy", "umx_trainer_create", "umx_trainer_destroy",
     "umx_trainer_last_error", "umx_train_step", "umx_train_step_dev", "umx_trainer_loss", "umx_trainer_read",
     "umx_trainer_probs", "umx_trainer_read_tensor", "umx_trainer_eval", "umx_trainer_step_count", "umx_trainer_batch", "umx_trainer_flops_per_image",
-    "umx_trainer_profile", "umx_trainset_create", "umx_trainset_set", "umx_trainset_destroy", "umx_train_step_sampled",
+    "umx_trainer_profile", "umx_test_trainer_serial", "umx_trainset_create", "umx_trainset_set", "umx_trainset_destroy", "umx_train_step_sampled",
     "umx_trainer_assemble", "umx_trainer_evaluate", "umx_guard_scan", "umx_augment_table_check", "umx_trainset_set_augment",
     "umx_train_step_augmented", "umx_trainer_assemble_augmented", "umx_warp_desc_check", "umx_train_step_warped",
     "umx_trainer_assemble_warped", "umx_trainer_init", "umx_elastic_desc_check", "umx_train_step_elastic",
@@ -210,6 +210,8 @@ def _bind(L):
     L.umx_trainer_flops_per_image.argtypes = [c_void_p]
     L.umx_trainer_profile.restype = c_int
     L.umx_trainer_profile.argtypes = [c_void_p, c_int, dp, dp, dp, ctypes.POINTER(c_int)]
+    L.umx_test_trainer_serial.restype = c_int
+    L.umx_test_trainer_serial.argtypes = [c_void_p, c_int]
     # the device-resident training set (unmicst_amd/trainset.py)
     L.umx_trainset_create.restype = c_int
     L.umx_trainset_create.argtypes = [c_void_p, c_int, c_int, c_int, ctypes.POINTER(LabelWeightsC), ctypes.POINTER(c_void_p)]
@@ -585,6 +587,10 @@ class Trainer:
     @property
     def flops_per_image(self) -> float:
         return float(self._lib.umx_trainer_flops_per_image(self._h))
+
+    def test_serial(self, on: bool = True) -> None:
+        """umx_test_trainer_serial: the v2 step enqueues its whole schedule on the main stream, in plan order, without events."""
+        self._check(self._lib.umx_test_trainer_serial(self._h, int(on)))
 
     def profile(self, enable: bool = True) -> dict:
         f, b, o = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()

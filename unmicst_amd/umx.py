@@ -32,7 +32,7 @@ EXPORTS = [
     "umx_infer_image_sharded_dev", "umx_infer_image_sharded_raw", "umx_infer_image_sharded_raw_submit",
     "umx_band_tiles_dev", "umx_stitch_dev", "umx_profile_enable", "umx_profile_read", "umx_prof_entry_size", "umx_test_double_to_half", "umx_test_double_to_half_dev",
     "umx_test_gauss_weights", "umx_test_resize_dev", "umx_test_rescale_dev", "umx_test_plane_range_dev", "umx_test_half_to_u8_dev",
-    "umx_describe", "umx_describe_graph", "umx_plan_check", "umx_test_infer_plan", "umx_test_wgrad_plan", "umx_test_train_plan", "umx_test_slide_plan", "umx_test_band_plan", "umx_test_mx_pack_e2m3", "umx_version",
+    "umx_describe", "umx_describe_graph", "umx_plan_check", "umx_test_infer_plan", "umx_test_wgrad_plan", "umx_test_train_plan", "umx_test_step_plan", "umx_test_slide_plan", "umx_test_band_plan", "umx_test_mx_pack_e2m3", "umx_version",
     "umx_label_options_check", "umx_labeler_create", "umx_labeler_destroy", "umx_labeler_last_error", "umx_labeler_run",
     "umx_labeler_run_dev", "umx_labeler_objects", "umx_labeler_last_ms",
     "umx_label_measure_check", "umx_labeler_measure", "umx_labeler_measure_dev", "umx_labeler_measure_last_ms",
@@ -406,6 +406,15 @@ def train_plan(hp, batch: int, blob, conv_f32: bool = False, no_ksplit: bool = F
         rc = fn(*args, buf, len(buf), ctypes.byref(need))
     _check(L, rc)
     return buf.value.decode().splitlines()
+
+
+def step_plan(hp, batch: int, blob, conv_f32: bool = False, no_ksplit: bool = False, reg: bool = True):
+    """umx_test_step_plan: the stream schedule of the v2 training step after the same host pass, one line per step in host enqueue
+    order: "op site stream; wait e..; record e..; r buf..; w buf..".  Host only."""
+    blob = np.ascontiguousarray(blob, dtype=np.float32)
+    hps = _hp_struct(hp)
+    return _plan_text(load().umx_test_step_plan, [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_size_t],
+                      (ctypes.byref(hps), batch, int(conv_f32), int(no_ksplit), int(reg), blob.ctypes.data, blob.size), cap=1 << 16)
 
 
 def _plan_text(fn, argtypes, args, cap=1 << 14):
