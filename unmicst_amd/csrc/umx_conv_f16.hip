@@ -58,6 +58,49 @@ typedef unsigned u32x16 __attribute__((ext_vector_type(16)));
 #define UMX_MAX3(dst, a, b, c) asm volatile("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(dst) : "v"(a), "v"(b), "v"(c))
 #define UMX_MAX3N(dst, a, b, c) asm volatile("v_pk_maximum3_f16 %0, %1, %2, %3 neg_lo:[1,1,1] neg_hi:[1,1,1]" : "=v"(dst) : "v"(a), "v"(b), "v"(c))
 #define UMX_MAX3N2(dst, a, b, c) asm volatile("v_pk_maximum3_f16 %0, %1, %2, %3 neg_lo:[0,0,1] neg_hi:[0,0,1]" : "=v"(dst) : "v"(a), "v"(b), "v"(c))
+// Range tracking of an epilogue on the packed binary16 hi words it stores (two values per word): `pos` collects the largest value per
+// half-word position, `neg` the largest negated value, both starting at +0 -- two instructions per FOUR values (on the fp32 values it
+// was a v_and per value and a share of a v_max3_u32: 1.5 - 1.8 per value).  The instruction is IEEE 754-2019 maximum: a NaN stays.
+// (not volatile: the accumulators carry the order, and the scheduler may place the pair among the conversions that feed it)
+#define UMX_RANGE_TRACK(pos, neg, w0, w1)                                                                                  \
+    do {                                                                                                                   \
+        asm("v_pk_maximum3_f16 %0, %0, %1, %2" : "+v"(pos) : "v"(w0), "v"(w1));                                            \
+        asm("v_pk_maximum3_f16 %0, %0, %1, %2 neg_lo:[0,1,1] neg_hi:[0,1,1]" : "+v"(neg) : "v"(w0), "v"(w1));              \
+    } while (0)
+// The lo words of a (hi, lo) split: lo = binary16(v - hi) for the two values whose packed hi halves are `hw`, as ONE mixed-precision
+// fma per value (-hi * 1.0 + v, the binary16 operand widened inside the instruction, the result rounded to binary16 once).  v - hi is
+// exact in binary32 -- hi is v rounded to 11 bits -- so the single rounding gives the bits of the three instructions it replaces
+// (v_cvt_f32_f16, v_sub_f32, a half of v_cvt_pk_f16_f32; hipcc also converted every value to binary16 a second time to have hi as a
+// scalar).  The instructions of a statement alternate registers, and a statement ends with one idle state: a half-word result must not
+// be forwarded to the instruction behind it (gfx940's dst_sel hazard), and the compiler pads no hazard of an asm statement.
+#define UMX_MIXLO(d, h, v) "v_fma_mixlo_f16 " d ", -" h ", 1.0, " v " op_sel_hi:[1,0,0]\n\t"
+#define UMX_MIXHI(d, h, v) "v_fma_mixhi_f16 " d ", -" h ", 1.0, " v " op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+__device__ __forceinline__ unsigned pack_hi(float v0, float v1) {
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    h2 h;
+    h[0] = (_Float16)v0; h[1] = (_Float16)v1;
+    return __builtin_bit_cast(unsigned, h);
+}
+__device__ __forceinline__ void split_lo2(const unsigned (&hw)[2], const float (&v)[4], unsigned (&lw)[2]) {
+    asm(UMX_MIXLO("%0", "%2", "%4") UMX_MIXLO("%1", "%3", "%6") UMX_MIXHI("%0", "%2", "%5") UMX_MIXHI("%1", "%3", "%7") "s_nop 1"
+        : "=&v"(lw[0]), "=&v"(lw[1])
+        : "v"(hw[0]), "v"(hw[1]), "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]));
+}
+__device__ __forceinline__ void split_lo4(const unsigned (&hw)[4], const float (&v)[8], unsigned (&lw)[4]) {
+    asm(UMX_MIXLO("%0", "%4", "%8") UMX_MIXLO("%1", "%5", "%10") UMX_MIXLO("%2", "%6", "%12") UMX_MIXLO("%3", "%7", "%14")
+        UMX_MIXHI("%0", "%4", "%9") UMX_MIXHI("%1", "%5", "%11") UMX_MIXHI("%2", "%6", "%13") UMX_MIXHI("%3", "%7", "%15") "s_nop 1"
+        : "=&v"(lw[0]), "=&v"(lw[1]), "=&v"(lw[2]), "=&v"(lw[3])
+        : "v"(hw[0]), "v"(hw[1]), "v"(hw[2]), "v"(hw[3]), "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]));
+}
+// binary16's 60000 = 0x7b53: a stored hi word at or above it in magnitude, infinity or NaN (every fp32 value >= 60000 rounds there;
+// so do the values in (59984, 60000), within one binary16 ulp of 32 below it)
+constexpr unsigned kRangeLimitH = 0x7b53u;
+__device__ __forceinline__ bool range_exceeded(unsigned pos, unsigned neg) {
+    unsigned m;
+    asm("v_pk_maximum3_f16 %0, %1, %2, %2" : "=v"(m) : "v"(pos), "v"(neg));
+    m &= 0x7fff7fffu;   // (a NaN may come back with its sign set)
+    return max(m & 0xffffu, m >> 16) >= kRangeLimitH;
+}
 // NB blocks at once (1 or 2: two independent dependency chains interleaved instruction by instruction -- the reduction is a tree of
 // depth 4, one block's chain alone leaves the vector unit waiting for its own results).  volatile: the sequence stays together and in
 // this order -- left to the scheduler, the conversions sink behind every block's reduction and all fragment registers stay live.
@@ -598,8 +641,8 @@ __global__ void __launch_bounds__(F6 ? 512 : 256, conv_f16x3_waves(NT, KMT, NPH,
     // fmaxf() costs an extra canonicalising v_max per value; the second affine exists only in the legacy graph (BN after
     // ReLU) and with a non-zero activation shift: two copies of the loop behind one uniform branch.  Results are scalars,
     // not written back into the accumulator tuples (a 4-vector rebuilt by inserts gets a fresh register tuple).
-    unsigned vmax = 0u;   // max |v| of this lane as a bit pattern (orders NaN and infinity above every finite value): one
-                          // compare against binary16's range at the end
+    unsigned rmax_p = 0u, rmax_n = 0u;   // largest stored hi halves of this lane and largest negated ones (UMX_RANGE_TRACK): one
+                                         // compare against binary16's range at the end
     const float slope = p.act == ACT_RELU ? 0.f : p.act == ACT_LEAKY ? kLeakySlope : 1.f;
     auto arith_v = [&](const f32x4 (&A)[NT], float (&out)[NT][4], auto POST, auto TRACK) {
         constexpr bool post = decltype(POST)::value, track = decltype(TRACK)::value;
@@ -630,7 +673,6 @@ __global__ void __launch_bounds__(F6 ? 512 : 256, conv_f16x3_waves(NT, KMT, NPH,
                 float v = A[n][r] * psa[r] + pba[r];
                 v = __builtin_amdgcn_fmed3f(v, v * slope, INFINITY);
                 if constexpr (post) v = v * qsa[r] + qba[r];
-                if constexpr (track) vmax = max(vmax, __float_as_uint(v) & 0x7fffffffu);
                 out[n][r] = v;
             }
             // four values at a time: left alone, the scheduler runs all fmas, then all multiplies, then all medians, and
@@ -671,14 +713,29 @@ __global__ void __launch_bounds__(F6 ? 512 : 256, conv_f16x3_waves(NT, KMT, NPH,
                 arith(accs[0][m], res, kTrack);   // (range tracked: the head's operands are binary16 pairs)
 #pragma unroll
                 for (int s2 = 0; s2 < NS2; ++s2) {
-                    h8 bh, bl;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int nt = 2 * s2 + (j >> 2);
-                        const float t = nt < NT ? res[nt < NT ? nt : 0][j & 3] : 0.f;
-                        bh[j] = (_Float16)t;
-                        bl[j] = (_Float16)(t - (float)bh[j]);
+                    // (hi, lo) words of N-tiles 2 s2 and 2 s2 + 1 (zeros past the last N-tile; compile-time, the loop is unrolled), and
+                    // the range of the activations on the hi halves the head multiplies
+                    u32x4 bhw = (u32x4){0u, 0u, 0u, 0u}, blw = (u32x4){0u, 0u, 0u, 0u};
+                    const float(&r0)[4] = res[2 * s2];
+                    if (2 * s2 + 1 < NT) {
+                        const float(&r1)[4] = res[2 * s2 + 1 < NT ? 2 * s2 + 1 : 0];
+                        const unsigned hw[4] = {pack_hi(r0[0], r0[1]), pack_hi(r0[2], r0[3]), pack_hi(r1[0], r1[1]), pack_hi(r1[2], r1[3])};
+                        const float v[8] = {r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]};
+                        unsigned lw[4];
+                        split_lo4(hw, v, lw);
+                        bhw = (u32x4){hw[0], hw[1], hw[2], hw[3]};
+                        blw = (u32x4){lw[0], lw[1], lw[2], lw[3]};
+                        UMX_RANGE_TRACK(rmax_p, rmax_n, hw[0], hw[1]);
+                        UMX_RANGE_TRACK(rmax_p, rmax_n, hw[2], hw[3]);
+                    } else {
+                        const unsigned hw[2] = {pack_hi(r0[0], r0[1]), pack_hi(r0[2], r0[3])};
+                        unsigned lw[2];
+                        split_lo2(hw, r0, lw);
+                        bhw[0] = hw[0]; bhw[1] = hw[1];
+                        blw[0] = lw[0]; blw[1] = lw[1];
+                        UMX_RANGE_TRACK(rmax_p, rmax_n, hw[0], hw[1]);
                     }
+                    const h8 bh = __builtin_bit_cast(h8, bhw), bl = __builtin_bit_cast(h8, blw);
                     u32x4 ah = Hh[s2], al = Hl[s2];
                     if constexpr ((m & 3) != 0) {
                         constexpr int ctrl = 0x110 + 4 * (m & 3);   // row_shr:4m, bound_ctrl: rows shifted in are zero
@@ -725,7 +782,7 @@ __global__ void __launch_bounds__(F6 ? 512 : 256, conv_f16x3_waves(NT, KMT, NPH,
                     lg = (f32x4){0.f, 0.f, 0.f, 0.f};
                 }
             });
-            if (vmax >= 0x476a6000u) atomicOr(p.overflow_flag, 1);   // binary16 range exceeded in front of the head
+            if (range_exceeded(rmax_p, rmax_n)) atomicOr(p.overflow_flag, 1);   // binary16 range exceeded in front of the head
             return;
         }
         if (p.dst_f32) {   // (the planner never pairs fp32 output with the fused transposed convolution)
@@ -776,13 +833,15 @@ __global__ void __launch_bounds__(F6 ? 512 : 256, conv_f16x3_waves(NT, KMT, NPH,
     // and every (pixel, octet) offset inside one image far below 2^31)
     unsigned char* const bhi = reinterpret_cast<unsigned char*>(p.dst_hi + (size_t)img0 * dImg);
     unsigned char* const blo = reinterpret_cast<unsigned char*>(p.dst_lo + (size_t)img0 * dImg);
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    auto pack_split = [](float v0, float v1, unsigned& hw, unsigned& lw) {
-        h2 h, l;
-        h[0] = (_Float16)v0; h[1] = (_Float16)v1;
-        l[0] = (_Float16)(v0 - (float)h[0]); l[1] = (_Float16)(v1 - (float)h[1]);
-        hw = __builtin_bit_cast(unsigned, h);
-        lw = __builtin_bit_cast(unsigned, l);
+    // the (hi, lo) words of the four channels of two result sets (split_lo4 above)
+    auto pack_split8 = [](const float (&a)[4], const float (&b)[4], unsigned& ah0, unsigned& ah1, unsigned& bh0, unsigned& bh1,
+                          unsigned& al0, unsigned& al1, unsigned& bl0, unsigned& bl1) {
+        const unsigned hw[4] = {pack_hi(a[0], a[1]), pack_hi(a[2], a[3]), pack_hi(b[0], b[1]), pack_hi(b[2], b[3])};
+        const float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+        unsigned lw[4];
+        split_lo4(hw, v, lw);
+        ah0 = hw[0]; ah1 = hw[1]; bh0 = hw[2]; bh1 = hw[3];
+        al0 = lw[0]; al1 = lw[1]; bl0 = lw[2]; bl1 = lw[3];
     };
     // One value: (acc * pre_s + pre_b) -> activation -> [* post_s + post_b], range-tracked (as arith_v above, one N-tile at a
     // time so that the results of an N-tile leave for memory before the next one is touched: a whole M-tile pair of
@@ -829,14 +888,10 @@ __global__ void __launch_bounds__(F6 ? 512 : 256, conv_f16x3_waves(NT, KMT, NPH,
         // appended channels (the raw-input skip riding in a spare word of this unit), loaded by app_load below
         const int oct_u = (nblk * NT + n) * 2 + oct_q;
         const bool app = kApp && lane_app && apix >= 0 && oct_u == p.app_oct;
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            vmax = max(vmax, max(__float_as_uint(a[r]) & 0x7fffffffu, __float_as_uint(b[r]) & 0x7fffffffu));
         unsigned ah0, ah1, al0, al1, bh0, bh1, bl0, bl1;
-        pack_split(a[0], a[1], ah0, al0);
-        pack_split(a[2], a[3], ah1, al1);
-        pack_split(b[0], b[1], bh0, bl0);
-        pack_split(b[2], b[3], bh1, bl1);
+        pack_split8(a, b, ah0, ah1, bh0, bh1, al0, al1, bl0, bl1);
+        UMX_RANGE_TRACK(rmax_p, rmax_n, ah0, ah1);
+        UMX_RANGE_TRACK(rmax_p, rmax_n, bh0, bh1);
         // (every lane takes part in the exchange: never under a divergent branch)
         const auto h0 = __builtin_amdgcn_permlane16_swap(ah0, bh0, false, false);
         const auto h1 = __builtin_amdgcn_permlane16_swap(ah1, bh1, false, false);
@@ -892,15 +947,24 @@ __global__ void __launch_bounds__(F6 ? 512 : 256, conv_f16x3_waves(NT, KMT, NPH,
             float a[4], b[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float va = fmaxf(act1(R0[n][r], e, r, POST), act1(R1[n][r], e, r, POST));
-                const float vb = fmaxf(act1(R2[n][r], e, r, POST), act1(R3[n][r], e, r, POST));
-                const float sa = __builtin_bit_cast(
-                    float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, va), 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, false));
-                const float sb = __builtin_bit_cast(
-                    float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, vb), 0xB1, 0xF, 0xF, false));
-                a[r] = fmaxf(va, sa);
-                b[r] = fmaxf(vb, sb);
+                a[r] = fmaxf(act1(R0[n][r], e, r, POST), act1(R1[n][r], e, r, POST));
+                b[r] = fmaxf(act1(R2[n][r], e, r, POST), act1(R3[n][r], e, r, POST));
             }
+            // max with the horizontal neighbour (quad_perm [1,0,3,2]) as ONE instruction per value, the neighbour's value being the
+            // DPP operand of the max itself.  Through update_dpp + fmaxf() it was four: a v_mov 0 for the value never shifted in, the
+            // v_mov_dpp, a canonicalising v_max of what to the compiler is an integer of unknown origin, and the max.  (The compiler
+            // pads no hazard of an asm statement: a DPP operand read needs two wait states behind the VALU write of its register --
+            // one s_nop for the eight.)
+            asm("s_nop 1\n\t"
+                "v_max_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                "v_max_f32_dpp %1, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                "v_max_f32_dpp %2, %2, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                "v_max_f32_dpp %3, %3, %3 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                "v_max_f32_dpp %4, %4, %4 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                "v_max_f32_dpp %5, %5, %5 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                "v_max_f32_dpp %6, %6, %6 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                "v_max_f32_dpp %7, %7, %7 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
+                : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]));
             store_unit(n, a, b, off, ok, -1, 0u, 0u);
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -943,14 +1007,10 @@ __global__ void __launch_bounds__(F6 ? 512 : 256, conv_f16x3_waves(NT, KMT, NPH,
                     float a[4], b[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { a[r] = act1(accs[0][m][n][r], e, r, POST); b[r] = act1(accs[0][m + 1][n][r], e, r, POST); }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        vmax = max(vmax, max(__float_as_uint(a[r]) & 0x7fffffffu, __float_as_uint(b[r]) & 0x7fffffffu));
                     unsigned ah0, ah1, al0, al1, bh0, bh1, bl0, bl1;
-                    pack_split(a[0], a[1], ah0, al0);
-                    pack_split(a[2], a[3], ah1, al1);
-                    pack_split(b[0], b[1], bh0, bl0);
-                    pack_split(b[2], b[3], bh1, bl1);
+                    pack_split8(a, b, ah0, ah1, bh0, bh1, al0, al1, bl0, bl1);
+                    UMX_RANGE_TRACK(rmax_p, rmax_n, ah0, ah1);
+                    UMX_RANGE_TRACK(rmax_p, rmax_n, bh0, bh1);
                     // (every lane takes part in the exchange: never under a divergent branch)
                     const auto h0 = __builtin_amdgcn_permlane16_swap(ah0, bh0, false, false);
                     const auto h1 = __builtin_amdgcn_permlane16_swap(ah1, bh1, false, false);
@@ -985,13 +1045,15 @@ __global__ void __launch_bounds__(F6 ? 512 : 256, conv_f16x3_waves(NT, KMT, NPH,
                     const int ib = pix_off(wave * KMT + m, li, yt, xt);
                     float a[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        a[r] = act1(accs[0][m][NTR][r], e, r, POST);
-                        vmax = max(vmax, __float_as_uint(a[r]) & 0x7fffffffu);
-                    }
+                    for (int r = 0; r < 4; ++r) a[r] = act1(accs[0][m][NTR][r], e, r, POST);
                     uint4 uh = make_uint4(0u, 0u, 0u, 0u), ul = make_uint4(0u, 0u, 0u, 0u);
-                    pack_split(a[0], a[1], uh.x, ul.x);
-                    pack_split(a[2], a[3], uh.y, ul.y);
+                    {
+                        const unsigned hw[2] = {pack_hi(a[0], a[1]), pack_hi(a[2], a[3])};
+                        unsigned lw[2];
+                        split_lo2(hw, a, lw);
+                        uh.x = hw[0]; uh.y = hw[1]; ul.x = lw[0]; ul.y = lw[1];
+                    }
+                    UMX_RANGE_TRACK(rmax_p, rmax_n, uh.x, uh.y);   // (before the appended channels take a word)
                     if (app_on && dmix >= 0) {
                         unsigned aph, apl_w;
                         const unsigned char* const src = apl + (wave * KMT + m) * 512;
@@ -1027,14 +1089,10 @@ __global__ void __launch_bounds__(F6 ? 512 : 256, conv_f16x3_waves(NT, KMT, NPH,
                     float a[4], b[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { a[r] = act1(accs[0][m][NTR][r], e, r, POST); b[r] = act1(accs[0][m + 1][NTR][r], e, r, POST); }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        vmax = max(vmax, max(__float_as_uint(a[r]) & 0x7fffffffu, __float_as_uint(b[r]) & 0x7fffffffu));
                     unsigned ah0, ah1, al0, al1, bh0, bh1, bl0, bl1;
-                    pack_split(a[0], a[1], ah0, al0);
-                    pack_split(a[2], a[3], ah1, al1);
-                    pack_split(b[0], b[1], bh0, bl0);
-                    pack_split(b[2], b[3], bh1, bl1);
+                    pack_split8(a, b, ah0, ah1, bh0, bh1, al0, al1, bl0, bl1);
+                    UMX_RANGE_TRACK(rmax_p, rmax_n, ah0, ah1);
+                    UMX_RANGE_TRACK(rmax_p, rmax_n, bh0, bh1);
                     const auto h0 = __builtin_amdgcn_permlane16_swap(ah0, bh0, false, false);
                     const auto h1 = __builtin_amdgcn_permlane16_swap(ah1, bh1, false, false);
                     const auto l0 = __builtin_amdgcn_permlane16_swap(al0, bl0, false, false);
@@ -1093,7 +1151,7 @@ __global__ void __launch_bounds__(F6 ? 512 : 256, conv_f16x3_waves(NT, KMT, NPH,
             emit(accs[0][m], accs[0][m + 1], ib + pix * dPix, ib >= 0, apix, ah, al);
         }
     }
-    if (vmax >= 0x476a6000u) atomicOr(p.overflow_flag, 1);   // |v| >= 60000, infinity or NaN: binary16 range exceeded, the host reports it
+    if (range_exceeded(rmax_p, rmax_n)) atomicOr(p.overflow_flag, 1);   // |v| >= 60000, infinity or NaN: binary16 range exceeded, the host reports it
 }
 
 template <int NT, int KMT, int NPH, bool DBG, int MAXP, bool PK = false, bool D2S = false, bool F6 = false>
