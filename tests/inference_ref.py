@@ -222,7 +222,7 @@ def torch_tensors(hp, blob, dtype=torch.float32):
 def emulate(hp, blob, x, plan_of):
     """The emulated engine on a float32 NHWC batch -> probabilities (numpy float32)."""
     with torch.no_grad():
-        return forward(hp, torch_tensors(hp, blob), torch.from_numpy(np.ascontiguousarray(x, np.float32)), plan_of).numpy()
+        return forward(hp, torch_tensors(hp, blob), torch.from_numpy(np.array(x, np.float32)), plan_of).numpy()   # (a copy: x may be read-only)
 
 
 # ------------------------------------------------------------------------------------------------ the float64 forward
@@ -247,15 +247,23 @@ def _bn64(x, T, p):
     return (x - mu[None, :, None, None]) / torch.sqrt(va + BN_EPS)[None, :, None, None] * g[None, :, None, None] + b[None, :, None, None]
 
 
-def forward64(hp, blob, x_nhwc):
+def forward64(hp, blob, x_nhwc, bn_hook=None):
     """Both graphs in inference mode, float64 end to end, on an NHWC batch -> probabilities [B, P, P, K] (numpy float64).
     v2 (UnMicst1-5.py / UnMicst2.py): block = conv + ks x ks shortcut, leaky(BN(.)), pool; bottom conv with BN; up = leaky(convT),
     concat [skip, up], leaky(BN(conv)); head 1 x 1 + BN + softmax.  legacy (UnMicst.py): 1 x 1 shortcut, BN(relu(.)) in the
-    down blocks and no BatchNorm anywhere else.  Extra convolutions read the activated tensor before them."""
+    down blocks and no BatchNorm anywhere else.  Extra convolutions read the activated tensor before them.
+    bn_hook(prefix, input NCHW, T), if given, runs before every BatchNorm in graph order and may rewrite that BatchNorm's entries of
+    T (tests/trained_like.py sets moving statistics this way); `blob` may then also be the dict of float64 tensors itself."""
     v2 = hp.graph == model.GRAPH_V2
-    T = torch_tensors(hp, blob, torch.float64)
+    T = blob if isinstance(blob, dict) else torch_tensors(hp, blob, torch.float64)
     act = (lambda t: torch.where(t >= 0, t, t * LEAK)) if v2 else (lambda t: t.clamp(min=0))
     L = hp.nLayers
+
+    def bn(t, p):
+        if bn_hook is not None:
+            bn_hook(p, t, T)
+        return _bn64(t, T, p)
+
     with torch.no_grad():
         x = torch.from_numpy(np.ascontiguousarray(x_nhwc, np.float64)).permute(0, 3, 1, 2)
         skips = [x]
@@ -265,20 +273,20 @@ def forward64(hp, blob, x_nhwc):
             for e in range(hp.nExtraConvs):
                 c = _conv64(act(c), T["%s.wextra%d" % (n, e)])
             c = c + _conv64(skips[i], T[n + ".wshort"])
-            c = act(_bn64(c, T, n)) if v2 else _bn64(act(c), T, n)
+            c = act(bn(c, n)) if v2 else bn(act(c), n)
             skips.append(F.max_pool2d(c, 2))
         cur = _conv64(skips[L], T["lb.w"])
-        cur = act(_bn64(cur, T, "lb")) if v2 else act(cur)
+        cur = act(bn(cur, "lb")) if v2 else act(cur)
         for idx in range(L - 1, -1, -1):
             n = "lu%d" % idx
             up = act(_convT64(cur, T[n + ".wt"]))
             cur = _conv64(torch.cat([skips[idx], up], 1), T[n + ".w2"])
-            cur = act(_bn64(cur, T, n)) if v2 else act(cur)
+            cur = act(bn(cur, n)) if v2 else act(cur)
             for e in range(hp.nExtraConvs):
                 cur = act(_conv64(cur, T["%s.wextra%d" % (n, e)]))
         t = _conv64(cur, T["lt.w"])
         if v2:
-            t = _bn64(t, T, "lt")
+            t = bn(t, "lt")
         return torch.softmax(t, 1).permute(0, 2, 3, 1).contiguous().numpy()
 
 

@@ -109,16 +109,24 @@ def test_end_to_end_reference_sample_data(prec):
         assert (d == 0).mean() > 0.98
 
 
-@pytest.mark.parametrize("prec", PRECS)
-@pytest.mark.parametrize("name,shape", [("v2_duo_like", (2, 70, 45)), ("v2_solo_like", (53, 90)), ("legacy_k5", (40, 33))])
+# HP_F6 (tests/inference_ref.py: lb.conv takes the F6 form) under the two precisions the shipped duo runs use; the image of tests/test_gpu_f6.py
+IMAGE_SHAPES = [("v2_duo_like", (2, 70, 45)), ("v2_solo_like", (53, 90)), ("legacy_k5", (40, 33)), ("v2_72_f6", (2, 150, 170))]
+IMAGE_CASES = [pytest.param(n, s, p, id="%s-shape%d-%s" % (n, i, p)) for p in PRECS + ["f16f6", "default"] for i, (n, s) in enumerate(IMAGE_SHAPES)
+               if (n == "v2_72_f6") == (p not in PRECS)]
+
+
+@pytest.mark.parametrize("name,shape,prec", IMAGE_CASES)
 def test_infer_image_matches_oracle_loop(name, shape, prec):
     """Whole-image path (gather+normalise, UNet, stitch) vs the reference-equivalent oracle loop, per class."""
+    import inference_ref
     from oracle import oracle
-    hp = helpers.small_hps()[name]
+    hp = inference_ref.HP_F6 if name == "v2_72_f6" else helpers.small_hps()[name]
     blob = model.random_blob(hp, seed=3)
     img = np.random.default_rng(9).random(shape) * 0.6
     mean, std = 0.21, 0.17
     with umx.Engine(hp, blob, max_batch=4, precision=prec) as eng:
+        if name == "v2_72_f6":
+            assert eng.precision == "f16f6"
         got16 = eng.infer_image(img, mean, std)
         got32 = eng.infer_image(img, mean, std, stitch=umx.STITCH_FP32)
         rep = eng.infer_image(img, mean, std, mode=umx.MODE_REPLACE)
