@@ -1,10 +1,13 @@
 """The inference arithmetic gate on the GPU: every precision of the engine against a float64 forward, at a bound that a lost
-split-precision product on ONE layer cannot meet.
+split-precision product on ONE layer -- or in one launch, one output phase of a transposed convolution or one N-block of a layer --
+cannot meet.
 
 The 1e-4 gates of test_gpu_parity / _switches / _f6 / _shipped_models stay; this is a second, tighter one.  For each case of
 inference_ref.ARITH_CASES (graphs of <= 64 pixels with seeded weights and tiles) tests/arith_cases.json holds, from the CPU side alone
-(tests/test_inference_arith_cpu.py): tol = E_drop / 4, E_drop the smallest error the emulated arithmetic shows when x_lo * w_hi or
-x_hi * w_lo is omitted on a single layer, and tol >= 8 x the error of the correct arithmetic; tol_f6 = 4 x the emulated error of the
+(tests/test_inference_arith_cpu.py): tol = min(E_drop, E_cell) / 4, the smallest error the emulated arithmetic shows when x_lo * w_hi or
+x_hi * w_lo is omitted on a single layer (E_drop) or in a single cell of one launch (E_cell: inference_ref.cells; the two F6 cases
+leave the phases of their transposed convolutions to v2_72_phase, the same widths without an F6 launch), and tol >= 8 x the error of
+the correct arithmetic; tol_f6 = 4 x the emulated error of the
 F6 form (fp6 cross terms).  Here five tiles run through max_batch = 3 (a ragged last batch; for the eight-wave two-tile workgroups
 of the F6 form a half-empty one), and every tile is held to
 
@@ -13,6 +16,10 @@ of the F6 form a half-empty one), and every tile is held to
                                   that take it must be the ones tol_f6 was derived for)
 
 A case over its bound is a finding about a kernel or the planner, never a reason to scale tol.
+
+That the engine's result does depend on the w_lo of a weak cell is shown on the device as well: with the filter entries of the case's
+w_lo_cell rounded to binary16 precision -- their lo halves are then exactly 0, whatever the planner's power-of-two shift -- the float64
+forward moves by D >= 4 x tol, and the engine's output must move by at least D - 2 x tol.
 The coverage tests show that the cases reach the kernel forms the shipped hyper-parameter sets run."""
 import functools
 
@@ -37,6 +44,29 @@ def _case(name):
     for a in (blob, x, p64):
         a.setflags(write=False)
     return hp, blob, x, p64
+
+
+@functools.lru_cache(maxsize=None)
+def _case_without_w_lo(name):
+    """(blob B' of the case with its w_lo_cell's filter rounded to binary16 precision, float64 probabilities of B', D): computed once"""
+    hp, blob, x, p64 = _case(name)
+    blob2 = R.blob_with_cell_rounded(hp, blob, TABLE[name]["w_lo_cell"])
+    p64b = R.forward64(hp, blob2, x)
+    for a in (blob2, p64b):
+        a.setflags(write=False)
+    return blob2, p64b, float(np.abs(p64b - p64).max())
+
+
+@functools.lru_cache(maxsize=None)
+def _engine_output(name, prec):
+    """The five tiles of a case through max_batch = 3 in one precision: run once, shared, never written to."""
+    hp, blob, x, _ = _case(name)
+    assert x.shape[0] == 5
+    with umx.Engine(hp, blob, max_batch=3, precision=prec) as eng:
+        assert eng.precision == prec
+        got = eng.forward_tiles(x)
+    got.setflags(write=False)
+    return got
 
 
 def _tile_errors(got, p64):
@@ -70,12 +100,32 @@ def _profile_of(eng, x):
 def test_five_tiles_within_a_quarter_of_one_lost_product(name, prec):
     hp, blob, x, p64 = _case(name)
     tol = TABLE[name]["tol"]
-    assert x.shape[0] == 5
-    with umx.Engine(hp, blob, max_batch=3, precision=prec) as eng:
-        assert eng.precision == prec
-        got = eng.forward_tiles(x)
+    got = _engine_output(name, prec)
     errs = _tile_errors(got, p64)
     _report(name, prec, errs, tol)
+    assert np.all(errs <= tol), (name, prec, errs.tolist(), tol)
+
+
+@pytest.mark.parametrize("prec", ["f32", "f16x3"])
+@pytest.mark.parametrize("name", list(R.ARITH_CASES))
+def test_the_output_moves_when_the_weak_cells_w_lo_is_taken_away(name, prec):
+    """B' = the case's blob with the filter of its w_lo_cell (the weakest phase or N-block of lb.conv / lu*.convT / lu*.conv, whose
+    filters the engine splits as stored) rounded to binary16 precision.  On the CPU D = max |forward64(B') - forward64(B)| >= 4 x tol;
+    a correct engine is within tol of the float64 forward on either blob, so its two outputs differ by >= D - 2 x tol -- which an engine
+    that never multiplied by that cell's w_lo (the same output for B and B', up to w_hi's last bit) cannot show."""
+    hp, blob, x, p64 = _case(name)
+    tol, cell = TABLE[name]["tol"], TABLE[name]["w_lo_cell"]
+    blob2, p64b, D = _case_without_w_lo(name)
+    assert R.qualifies_for_w_lo_test(cell) and R.kept(name, cell)
+    assert D >= 4 * tol, (name, cell, D, tol)
+    with umx.Engine(hp, blob2, max_batch=3, precision=prec) as eng:
+        assert eng.precision == prec
+        got2 = eng.forward_tiles(x)
+    moved = float(np.abs(got2.astype(np.float64) - _engine_output(name, prec).astype(np.float64)).max())
+    errs = _tile_errors(got2, p64b)
+    print("%s %s %s: D %.3g = %.2f x tol, the engine moved by %.3g = %.3f x D (needed: %.3g); on B' E_gpu %.3g = %.3f x tol" % (
+        name, prec, cell, D, D / tol, moved, moved / D, D - 2 * tol, errs.max(), errs.max() / tol))
+    assert moved >= D - 2 * tol, (name, prec, cell, moved, D, tol)
     assert np.all(errs <= tol), (name, prec, errs.tolist(), tol)
 
 
