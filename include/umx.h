@@ -282,7 +282,8 @@ UMX_API int umx_infer_image_sharded_raw(umx_ctx* ctx, const void* band_host, int
  * 4-connected; a pixel goes to a seed nearest through the domain, a tie to the smaller label; the table is that of the grown labels.
  * Every value is an integer, so nothing depends on the order in which atomics arrive: two calls give the same bytes.
  * A labeler needs no model: it owns a stream and its device buffers (two int32 planes of H * W, the K input planes, one int32 per
- * UMX_LABEL_SCAN_BLOCK pixels and the table), grown on demand and kept between runs.  UMX_DEBUG_GUARD (include/umx_train.h) puts red
+ * UMX_LABEL_SCAN_BLOCK pixels and the table; from its first split run on one more int32 plane and one byte plane), grown on demand and
+ * kept between runs.  UMX_DEBUG_GUARD (include/umx_train.h) puts red
  * zones round them; a run then ends with their check (UMX_ERR_GUARD).  One labeler per host thread.
  */
 typedef struct umx_label_options {
@@ -378,6 +379,54 @@ UMX_API int umx_labeler_measure_dev(umx_labeler* lb, const int32_t* labels_dev, 
 /* Milliseconds of the last measurement, summed over its groups: the uploads of the planes (0 for _dev), the launches, the downloads
  * of the records.  Any may be NULL. */
 UMX_API int umx_labeler_measure_last_ms(const umx_labeler* lb, double* upload_ms, double* kernel_ms, double* download_ms);
+
+/*
+ * Splitting touching nuclei at their necks by erosion cores (the definition is the project's
+ * own).  Two nuclei are separate objects only where an unbroken line of another class lies between them; where that line has a gap
+ * the labelling joins them.  With a depth D, a minimum core area C and a regrow bound L, on top of the options of a labelling run:
+ *   10. objects: the kept objects (area >= A) of the plain labelling, N0 of them; M = their pixels.  Dropped objects play no part.
+ *   11. erosion: E = the pixels of M whose city-block ball of radius D lies wholly in M; outside the image is not in M --
+ *       scipy.ndimage.binary_erosion(M, cross, iterations=D, border_value=0).  Objects are never 4-adjacent, so every 4-connected
+ *       component of E lies in one object.
+ *   12. cores: the 4-connected components of E with area >= C.  An object that contains at least one is cored.
+ *   13. seeds: S = the pixels of all cores and all pixels of every kept object that is not cored (it stays whole: a nucleus thinner
+ *       than 2 D + 1 is never lost).  The seed objects are the 4-connected components of S, numbered 1..N in raster order of their
+ *       first pixel; N >= N0.
+ *   14. regrow: L synchronous levels of the growth rule above from these seeds over the domain "label 0 and pred == cls": a neck
+ *       pixel goes to the core nearest through the object, a tie to the smaller label; fronts cannot leave an object, and a dropped
+ *       object touches no seed.  unreached = the pixels of M still 0 after the L levels; they stay background.  (The launches stop
+ *       as soon as one claimed nothing: the state is closed, so the result is that of all L levels.)
+ *   15. if grow_radius > 0 the growth above over grow_classes from the labels of step 14; then the table of the final labels.
+ * The result is a function of the planes and the options only; every final object contains its seed and is 4-connected; an object
+ * with one core or none keeps exactly its pixels when L is large enough; a bar of width w joining two bodies is cut iff w <= 2 D.
+ * Not here: h-maxima, an intensity-weighted watershed, merging fragments back (a ragged outline can throw small cores; C is the only
+ * guard).  A split run allocates, beyond a plain run's buffers, one more int32 plane and one byte plane of H * W, kept like the others.
+ */
+typedef struct umx_label_split_options {
+    umx_label_options base;  /* the labelling (and the rim growth of step 15) as in umx_labeler_run */
+    int32_t depth;           /* D: 1 .. UMX_SPLIT_MAX_DEPTH erosion levels */
+    int32_t core_min_area;   /* C: 1 .. UMX_SPLIT_MAX_CORE_AREA pixels */
+    int32_t regrow;          /* L: 1 .. UMX_SPLIT_MAX_REGROW levels */
+    int32_t reserved[5];     /* must be zero */
+} umx_label_split_options;   /* 64 bytes */
+typedef struct umx_label_split_counts {
+    int64_t n_objects;       /* N: the seed objects = the objects of the result */
+    int64_t n_before;        /* N0: the kept objects of the plain labelling */
+    int64_t n_cored;         /* of those, the ones with at least one core */
+    int64_t unreached;       /* pixels of kept objects that the L levels did not reach: background in the result */
+} umx_label_split_counts;    /* 32 bytes */
+/* The erosion kernel holds a halo of UMX_LABEL_GROW_HALO pixels, which bounds the depth. */
+enum { UMX_SPLIT_MAX_DEPTH = 8, UMX_SPLIT_MAX_CORE_AREA = 65536, UMX_SPLIT_MAX_REGROW = 255 };
+/* Host only, no device: umx_label_options_check on the base first, its message passed through unchanged; then 1 <= depth <= 8,
+ * 1 <= core_min_area <= 65536, 1 <= regrow <= 255, reserved words zero.  UMX_OK, or UMX_ERR_INVALID with the reason in msg. */
+UMX_API int umx_label_split_check(const umx_label_split_options* o, int K, int H, int W, char* msg, size_t cap);
+/* umx_labeler_run / _run_dev with the split: the same contracts.  A refused call (UMX_ERR_INVALID) has touched nothing and leaves
+ * the resident labels as they were; a successful host call with a label plane makes the split labels the resident ones, so
+ * umx_labeler_measure measures them.  umx_labeler_objects, _last_ms and _last_error serve these calls too.  counts may be NULL. */
+UMX_API int umx_labeler_run_split(umx_labeler* lb, const uint8_t* planes_host, int K, int H, int W, const umx_label_split_options* o,
+                                  int32_t* labels_host, umx_label_split_counts* counts);
+UMX_API int umx_labeler_run_split_dev(umx_labeler* lb, const uint8_t* planes_dev, int K, int H, int W, const umx_label_split_options* o,
+                                      int32_t* labels_dev, umx_label_split_counts* counts);
 
 /* Strip / tile decoders of the drivers' own TIFF reader (unmicst_amd/tiffio.py; the reference reads through tifffile /
  * imagecodecs, UnMicst1-5.py:794-797): TIFF 6.0 LZW (compression 5, the OME-TIFF / Bio-Formats default) and PackBits

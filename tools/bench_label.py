@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time the label mask (umx_labeler_run) on synthetic H x W stacks of K = 3 uint8 planes (GPU box); one JSON
-line.  usage: bench_label.py [H=16384] [W=H] [--reps 3] [--grow R] [--measure C [--measure-dtype u8|u16]]
+line.  usage: bench_label.py [H=16384] [W=H] [--reps 3] [--grow R] [--measure C [--measure-dtype u8|u16]] [--split D [--split-core C]]
 
 Two inputs, both made here by pure-numpy recipes (no scipy in the generators, nothing from tests/):
   blobs  nuclei-like discs: the image is cut into 32 x 32 cells; a seeded draw keeps 60 % of them, and each kept cell gets one disc of
@@ -18,7 +18,11 @@ writes the labels and the table from the grown plane, less the seed stage's last
 measured against it (umx_labeler_measure): the upload, kernel and download milliseconds
 umx_labeler_measure_last_ms reports, summed over the groups of 4 planes (the best of --reps by kernel time, after one warm-up), the
 same for the first plane alone (a group of 1), the bytes one full group moves, and the seconds np.bincount takes for the per-object
-sums of the same planes over the same labels on this box's CPU share (one weighted pass per plane: the sum only)."""
+sums of the same planes over the same labels on this box's CPU share (one weighted pass per plane: the sum only).
+--split D: an input of its own, bodies joined in pairs: the image is cut into cells of 32 x 64; a seeded draw keeps 60 % of them, and each
+kept cell gets two squares of 24 x 24 joined by a bridge of 2 D rows -- the widest neck that depth D cuts, so every pair must come back
+as two objects.  The same planes are labelled without and with the split; "split_ms" is the
+difference of the two kernel times, and the four counts of the split are reported."""
 import argparse
 import json
 import os
@@ -53,6 +57,34 @@ def blob_mask(H, W, seed=1, rim=0):
         n = disc.shape[0]
         mask[y0 * CELL:(y0 + n) * CELL] = disc.transpose(0, 2, 1, 3).reshape(n * CELL, nx * CELL)
     return mask[:H, :W]
+
+
+PAIR_H, PAIR_W, SQUARE = 32, 64, 24
+
+
+def bridged_mask(H, W, D, seed=4):
+    """pairs of squares joined by a bridge of 2 D rows (D <= 8), one pair per kept cell of 32 x 64; no two pairs touch"""
+    rng = np.random.default_rng(seed)
+    ny, nx = -(-H // PAIR_H), -(-W // PAIR_W)
+    keep = rng.random((ny, nx)) < 0.6
+    cell = np.zeros((PAIR_H, PAIR_W), bool)
+    cell[4:4 + SQUARE, 4:4 + SQUARE] = True
+    cell[4:4 + SQUARE, PAIR_W - 4 - SQUARE:PAIR_W - 4] = True
+    cell[PAIR_H // 2 - D:PAIR_H // 2 + D, 4 + SQUARE:PAIR_W - 4 - SQUARE] = True
+    mask = (keep[:, None, :, None] & cell[None, :, None, :]).reshape(ny * PAIR_H, nx * PAIR_W)
+    return mask[:H, :W]
+
+
+def split_bench(a, H, W):
+    planes = planes_of(bridged_mask(H, W, a.split))
+    with umx.Labeler(a.device) as lb:
+        before, plain = best_kernel_ms(lb, planes, a.reps)
+        after, with_split = best_kernel_ms(lb, planes, a.reps, split=a.split, split_core=a.split_core)
+        counts = lb.split_counts()
+    assert counts["n_before"] == len(before) and counts["n_objects"] == len(after) and int(before["area"].sum()) == int(after["area"].sum()) + counts["unreached"]
+    return dict({"split": a.split, "split_core": a.split_core, "object_pixels": int(before["area"].sum()),
+                 "kernel_ms": round(plain[1], 3), "kernel_ms_with_split": round(with_split[1], 3),
+                 "split_ms": round(with_split[1] - plain[1], 3)}, **counts)
 
 
 def salt_mask(H, W, seed=2):
@@ -157,12 +189,17 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--grow", type=int, default=0)
     ap.add_argument("--measure", type=int, default=0, metavar="C")
+    ap.add_argument("--split", type=int, default=0, metavar="D")
+    ap.add_argument("--split-core", dest="split_core", type=int, default=1, metavar="C")
     ap.add_argument("--measure-dtype", dest="measure_dtype", choices=("u8", "u16"), default="u16")
     a = ap.parse_args()
     H, W = a.H, a.W or a.H
     out = {"tool": "bench_label", "H": H, "W": W, "K": 3, "min_area": 1, "reps": a.reps}
     if a.grow:
         print(json.dumps(dict(out, **grow_bench(a, H, W))))
+        return
+    if a.split:
+        print(json.dumps(dict(out, **split_bench(a, H, W))))
         return
     if a.measure:
         print(json.dumps(dict(out, **measure_bench(a, H, W))))

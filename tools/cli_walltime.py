@@ -7,6 +7,8 @@ libumx.so) whose UnMicst.py is timed on the same file, same box: how a round's c
        cli_walltime.py N --label   -- only this tree: twice without and twice with --labelMask (the `label` stage: stacking the
 planes, the labelling call, the int32 page and the table).
        cli_walltime.py N --label --grow R   -- and twice with --labelMask --labelGrow R as well.
+       cli_walltime.py N --label --split D  -- and twice with --labelMask --labelSplit D as well (the stage line then carries the
+split's four counts as "label_split").
        cli_walltime.py N --label --measure  -- and twice with --labelMask --labelMeasure as well (the `measure` stage: the three
 probability planes and the slide's one page against the labels left on the device, and the Intensities file)."""
 import json
@@ -47,6 +49,10 @@ def main():
     if "--grow" in rest:
         grow = str(int(rest[rest.index("--grow") + 1]))
         del rest[rest.index("--grow"):rest.index("--grow") + 2]
+    split = None
+    if "--split" in rest:
+        split = str(int(rest[rest.index("--split") + 1]))
+        del rest[rest.index("--split"):rest.index("--split") + 2]
     measure = "--measure" in rest
     others = [a for a in rest if a not in ("--label", "--measure")]
     hp, blob, mean, std = helpers.load_nuclei_dapi()
@@ -67,6 +73,9 @@ def main():
                 if grow:
                     one(ROOT, path, os.path.join(d, "out_grow%d" % rep), env, "this tree, --labelMask --labelGrow %s, run %d" % (grow, rep + 1), n,
                         extra=["--labelMask", "--labelGrow", grow])
+                if split:
+                    one(ROOT, path, os.path.join(d, "out_split%d" % rep), env, "this tree, --labelMask --labelSplit %s, run %d" % (split, rep + 1), n,
+                        extra=["--labelMask", "--labelSplit", split])
                 if measure:
                     one(ROOT, path, os.path.join(d, "out_measure%d" % rep), env, "this tree, --labelMask --labelMeasure, run %d" % (rep + 1), n,
                         extra=["--labelMask", "--labelMeasure"])

@@ -21,9 +21,16 @@
 //                         caller's plane; every run adds its length, y * length, the sum of its x and its extent to record label - 1
 // With a growth (grow_radius R > 0) the last launch is replaced by
 //   label_seed_kernel     one thread per pixel: the seed labels Q[P] in place over P, no table; Q is free from here on
-//   label_grow_kernel     ceil(R / UMX_LABEL_GROW_HALO) launches, P -> Q -> P ...: one workgroup per tile of 64 x 64 pixels loads the
+//   label_grow_kernel<false>  ceil(R / UMX_LABEL_GROW_HALO) launches, P -> Q -> P ...: one workgroup per tile of 64 x 64 pixels loads the
 //                         tile and a halo of 8 into LDS, runs up to 8 synchronous levels there and writes its tile to the other plane
 //   label_grown_kernel    one wave per row: the labels from the plane the last launch wrote to where the call wants them, and the table
+// A split run (umx_labeler_run_split / _run_split_dev) uses a third int32 plane R and a byte
+// plane B of flags; its sequence of launches stands at run_split_launches.  New in it are
+//   label_erode_kernel    one workgroup per tile of 64 x 64: "belongs to a kept object" of the tile and a halo of 8 as one bit per
+//                         pixel in LDS, up to 8 levels of erosion on the bit string, the flags of its tile into B
+//   label_runs_mask_kernel, label_core_mark_kernel, label_split_ids_kernel   the eroded set's row runs into R; which objects hold a
+//                         core; the seed components' ids in place over P, which the count / scan / number kernels then number
+//   label_grow_kernel<true>   the growth kernel over the label class itself, counting the pixels it claims so that the host can stop
 // A measurement (umx_labeler_measure / _measure_dev) is, per group of up to 4 image planes,
 //   label_measure_init_kernel, label_measure_kernel   one wave per row: the labels (the P plane a run left, or the caller's) read once
 //                         for the group's planes; every row run adds its count, its sums of v and v * v and its extremes of every plane
@@ -69,29 +76,19 @@ static_assert(UMX_LABEL_MAX_MIN_AREA == UMX_OBJECT_MAX_MIN_AREA, "one bound on m
 static_assert(UMX_BORDER_CONNECTIVITY == 4, "the merges below join a pixel with the one above it and row runs: 4-connectivity");
 static_assert(sizeof(umx_label_object) == 40, "the table's record");
 
-// grid ceil(H / 4).  planes [K][H][W].  Bounds: row y < H; ceil(W / 64) chunks; a lane is in the row iff lane < W - x0 (no x0 + lane
-// is formed past the row's end, W may be 2^31 - 1); the word written is y * W + x < H * W <= INT_MAX, its value y * W + start likewise.
-__global__ void __launch_bounds__(64 * kRowWaves) label_runs_kernel(const uint8_t* __restrict__ planes, int K, int H, int W, int cls,
-                                                                     int* __restrict__ P) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if ((long long)blockIdx.x * kRowWaves + wave >= H) return;    // (the whole wave: no barrier below)
-    const int y = blockIdx.x * kRowWaves + wave;
-    const size_t npix = (size_t)H * W, row = (size_t)y * W;
+// The row runs of one row by one wave: obj_at(x) is called once for every pixel of the row; every object pixel's word of P gets the
+// flat index of its run's head, every other pixel's -1.  Bounds: ceil(W / 64) chunks; a lane is in the row iff lane < W - x0 (no
+// x0 + lane is formed past the row's end, W may be 2^31 - 1); the word written is row + x < H * W <= INT_MAX, its value row + start
+// likewise.
+template <typename ObjAt>
+__device__ inline void write_row_runs(int W, int lane, size_t row, int* __restrict__ P, ObjAt obj_at) {
     const int nchunks = (W - 1) / 64 + 1;
     int carry = -1;   // first column of the run that reaches the end of the previous chunk; -1: none
     for (int c = 0; c < nchunks; ++c) {
         const int x0 = c * 64;
         const bool in = lane < W - x0;
         const int x = in ? x0 + lane : x0;
-        bool obj = false;
-        if (in) {
-            int arg = 0, best = planes[row + x];
-            for (int k = 1; k < K; ++k) {
-                const int v = planes[(size_t)k * npix + row + x];
-                if (v > best) { best = v; arg = k; }      // first maximum, as object_planes_kernel
-            }
-            obj = arg == cls;
-        }
+        const bool obj = in && obj_at(x);
         const unsigned long long mask = __ballot(obj);
         if (in) {
             int v = -1;
@@ -109,6 +106,23 @@ __global__ void __launch_bounds__(64 * kRowWaves) label_runs_kernel(const uint8_
             carry = -1;
         }
     }
+}
+
+// grid ceil(H / 4).  planes [K][H][W].  Bounds: row y < H; the rest is write_row_runs'.
+__global__ void __launch_bounds__(64 * kRowWaves) label_runs_kernel(const uint8_t* __restrict__ planes, int K, int H, int W, int cls,
+                                                                     int* __restrict__ P) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if ((long long)blockIdx.x * kRowWaves + wave >= H) return;    // (the whole wave: no barrier below)
+    const int y = blockIdx.x * kRowWaves + wave;
+    const size_t npix = (size_t)H * W, row = (size_t)y * W;
+    write_row_runs(W, lane, row, P, [&](int x) {
+        int arg = 0, best = planes[row + x];
+        for (int k = 1; k < K; ++k) {
+            const int v = planes[(size_t)k * npix + row + x];
+            if (v > best) { best = v; arg = k; }      // first maximum, as object_planes_kernel
+        }
+        return arg == cls;
+    });
 }
 
 // the merge of pixel i (row >= 1, column x) with the one above it, pruned as in border_label_kernel: skipped when the left neighbour
@@ -349,10 +363,16 @@ __global__ void __launch_bounds__(kPixThreads) label_seed_kernel(int* __restrict
 // Bounds: region pixel r = j * 256 + thread < 6400 = 25 * 256; its image row and column are formed in 64 bits (y0 + 79 may pass
 // 2^31) and a word of src, planes or dst is touched only at 0 <= gy < H, 0 <= gx < W, i.e. flat index < H * W <= INT_MAX.
 // A workgroup reads src and planes, which nobody writes in this launch, and writes the words of dst of its own tile only.
+// kCount (the regrow of the split, step 14): the workgroup also adds the pixels of its own tile that it claimed to *claimed -- one
+// integer atomic per workgroup that claimed any, which nothing reads before the launch ends.  A claim inside the tile is never one
+// of the possibly wrong ones, so the sum over the tiles is the number of pixels the launch labelled.  Without kCount the kernel
+// is the one the plain growth always launched, and `claimed` is not touched.
+template <bool kCount>
 __global__ void __launch_bounds__(kGrowThreads) label_grow_kernel(const uint8_t* __restrict__ planes, int K, int H, int W, unsigned classes,
                                                                   const int* __restrict__ src, int* __restrict__ dst, int levels,
-                                                                  int tiles_x) {
+                                                                  int tiles_x, long long* __restrict__ claimed) {
     __shared__ int L[kGrowPix];
+    int mine = 0;                                             // (kCount) claims of this thread inside the tile
     const int tid = threadIdx.x;
     const long long ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
     const long long y0 = ty * kGrowTile - kGrowHalo, x0 = tx * kGrowTile - kGrowHalo;
@@ -399,6 +419,7 @@ __global__ void __launch_bounds__(kGrowThreads) label_grow_kernel(const uint8_t*
                     if (left > 0 && left < m) m = left;
                     if (right > 0 && right < m) m = right;
                     if (m == INT_MAX) m = 0;
+                    if (kCount && m > 0 && ry >= kGrowHalo && ry < kGrowHalo + kGrowTile && rx >= kGrowHalo && rx < kGrowHalo + kGrowTile) ++mine;
                 }
                 nv[j] = m;                                    // > 0: the pixel is claimed at this level
                 changed |= m;
@@ -420,6 +441,14 @@ __global__ void __launch_bounds__(kGrowThreads) label_grow_kernel(const uint8_t*
             dst[(size_t)gy * W + (size_t)gx] = v > 0 ? v : 0;
         }
     }
+    if (kCount) {
+        __shared__ int tile_claims;
+        if (tid == 0) tile_claims = 0;
+        __syncthreads();
+        if (mine) atomicAdd(&tile_claims, mine);              // (LDS)
+        __syncthreads();
+        if (tid == 0 && tile_claims) atomicAdd(reinterpret_cast<unsigned long long*>(claimed), (unsigned long long)tile_claims);
+    }
 }
 
 // grid ceil(H / 4).  F: the grown labels, read by a thread at its own pixel only; out (may be null, may be F itself, may be another
@@ -437,6 +466,140 @@ __global__ void __launch_bounds__(64 * kRowWaves) label_grown_kernel(const int* 
             return label - 1;
         },
         [&](int key, int start, int len) { table_add(table + key, y, start, len); });
+}
+
+// ---- the split ----
+// A third int32 plane R (the components of the eroded set E, as P holds those of the objects) and a byte plane B of flags per pixel:
+constexpr unsigned kFlagKept = 1u;    // the pixel belongs to a kept object (step 10: a pixel of M)
+constexpr unsigned kFlagEroded = 2u;  // the pixel is in E (step 11); not read any more once R holds E's components
+constexpr unsigned kFlagCored = 4u;   // at the ROOT pixel of an object only: the object contains a core (step 12)
+constexpr int kSplitWords = 4, kSplitBefore = 0, kSplitPacked = 1, kSplitClaimed = 2;   // the words of umx_labeler::d_split
+constexpr int kErodeWords = kGrowPix / 64;                // the region of an erosion workgroup as one string of bits: 100 words, 800 B
+constexpr int kErodeShift = kGrowSide - 64;               // a row down is kGrowSide bits on: one word and this many bits
+static_assert(kErodeWords * 64 == kGrowPix && kErodeShift > 0 && kErodeShift < 64, "whole words; a row is between 64 and 128 bits");
+static_assert(UMX_SPLIT_MAX_DEPTH <= kGrowHalo, "the erosion's halo argument");
+static_assert(UMX_SPLIT_MAX_REGROW <= UMX_LABEL_MAX_GROW && UMX_SPLIT_MAX_CORE_AREA == UMX_LABEL_MAX_MIN_AREA, "the split's bounds");
+static_assert(sizeof(umx_label_split_options) == 64 && sizeof(umx_label_split_counts) == 32, "the split's records");
+
+// grid ceil(H / 4).  B: the flags, only read; R: every pixel of E gets its row run's head, every other one -1.
+__global__ void __launch_bounds__(64 * kRowWaves) label_runs_mask_kernel(const uint8_t* __restrict__ B, int H, int W, int* __restrict__ R) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if ((long long)blockIdx.x * kRowWaves + wave >= H) return;    // (the whole wave: no barrier below)
+    const int y = blockIdx.x * kRowWaves + wave;
+    const size_t row = (size_t)y * W;
+    write_row_runs(W, lane, row, R, [&](int x) { return (B[row + x] & kFlagEroded) != 0; });
+}
+
+// `depth` (1 .. 8) levels of erosion by the city-block ball.  grid tiles_y * tiles_x, the geometry of label_grow_kernel: one workgroup
+// per tile of 64 x 64 pixels loads "the pixel belongs to a kept object" -- P[i] >= 0 and Q[P[i]] >= min_area: P holds the roots and Q
+// the areas at the roots -- for the tile and a halo of 8 into LDS as ONE BIT per pixel, 0 for every pixel outside the image (step 11:
+// outside the image is not in M).  Region pixel r = ry * 80 + rx is bit r of a string of 6400 bits = 100 words of 64: a wave's ballot
+// over 64 consecutive region pixels IS one word, so the load needs no atomic and no shuffle.  A level is, per word,
+//     m & (m << 1) & (m >> 1) & (m << 80) & (m >> 80)
+// on the string (the shifts carry across words; past either end of the string they bring in 0): 100 threads, one word each, from one
+// buffer into the other, one barrier.
+// Why a halo of 8 suffices: a shift by 1 takes the left neighbour of a pixel of column 0 from column 79 of the row above, and the first
+// and the last row get zeros for their missing neighbours -- so after the first level the region's outer ring may be wrong, and after
+// each further level one ring more (a pixel's new value depends on its own and its four neighbours' old ones only).  After
+// depth <= 8 levels the wrong pixels lie in the 8 outer rings, which is the halo: every pixel of the tile is right.  Equivalently:
+// E(p) depends on the pixels of the ball of radius depth round p, and for p in the tile that ball lies in the region.
+// Bounds: r < 6400; image row and column in 64 bits as in the growth; P and B are touched at 0 <= gy < H, 0 <= gx < W only, Q at a
+// root P[i] < H * W.  A workgroup reads P and Q, which nobody writes in this launch, and writes the bytes of B of its own tile only:
+// kFlagKept | kFlagEroded, every byte of the tile (B needs no clearing).
+__global__ void __launch_bounds__(kGrowThreads) label_erode_kernel(const int* __restrict__ P, const int* __restrict__ Q, int H, int W, int min_area,
+                                                                   int depth, int tiles_x, uint8_t* __restrict__ B) {
+    __shared__ unsigned long long M0[kErodeWords], E[2][kErodeWords];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
+    const long long y0 = ty * kGrowTile - kGrowHalo, x0 = tx * kGrowTile - kGrowHalo;
+    int seen = 0;
+    for (int w = wave; w < kErodeWords; w += kGrowThreads / 64) {
+        const int r = w * 64 + lane;
+        const long long gy = y0 + r / kGrowSide, gx = x0 + r % kGrowSide;
+        bool kept = false;
+        if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+            const int p = P[(size_t)gy * W + (size_t)gx];
+            kept = p >= 0 && Q[p] >= min_area;
+        }
+        const unsigned long long mask = __ballot(kept);
+        if (lane == 0) { M0[w] = mask; E[0][w] = mask; }
+        seen |= mask != 0ull;
+    }
+    int cur = 0;
+    if (__syncthreads_or(seen)) {                             // (the barrier that makes the string whole, too)
+        for (int t = 0; t < depth; ++t) {
+            if (tid < kErodeWords) {
+                const unsigned long long* m = E[cur];
+                const unsigned long long c = m[tid];
+                const unsigned long long b1 = tid >= 1 ? m[tid - 1] : 0ull, b2 = tid >= 2 ? m[tid - 2] : 0ull;
+                const unsigned long long a1 = tid + 1 < kErodeWords ? m[tid + 1] : 0ull, a2 = tid + 2 < kErodeWords ? m[tid + 2] : 0ull;
+                const unsigned long long left = (c << 1) | (b1 >> 63), right = (c >> 1) | (a1 << 63);
+                const unsigned long long up = (b1 << kErodeShift) | (b2 >> (64 - kErodeShift));
+                const unsigned long long down = (a1 >> kErodeShift) | (a2 << (64 - kErodeShift));
+                E[cur ^ 1][tid] = c & left & right & up & down;
+            }
+            __syncthreads();
+            cur ^= 1;
+        }
+    }
+#pragma unroll 4
+    for (int j = 0; j < kGrowTile * kGrowTile / kGrowThreads; ++j) {
+        const int q = j * kGrowThreads + tid;
+        const int iy = q / kGrowTile, ix = q % kGrowTile;
+        const long long gy = ty * kGrowTile + iy, gx = tx * kGrowTile + ix;
+        if (gy < H && gx < W) {
+            const int r = (iy + kGrowHalo) * kGrowSide + ix + kGrowHalo;
+            const unsigned k = (unsigned)(M0[r >> 6] >> (r & 63)) & 1u, e = (unsigned)(E[cur][r >> 6] >> (r & 63)) & 1u;
+            B[(size_t)gy * W + (size_t)gx] = (uint8_t)(k * kFlagKept | e * kFlagEroded);
+        }
+    }
+}
+
+// one thread per pixel, i < npix.  R: the roots of E's components, Q: their areas at the roots, P: the roots of the objects -- all
+// only read.  The root pixel of every core (area >= core_min: one thread per core) sets kFlagCored in the byte of its OBJECT's root:
+// an integer atomic OR on the aligned word that holds the byte (B is a whole number of words), which nothing reads in this launch.
+__global__ void __launch_bounds__(kPixThreads) label_core_mark_kernel(const int* __restrict__ P, const int* __restrict__ R, const int* __restrict__ Q,
+                                                                      long long npix, int core_min, uint8_t* __restrict__ B) {
+    const long long i = (long long)blockIdx.x * kPixThreads + threadIdx.x;
+    if (i >= npix) return;
+    if (R[i] != (int)i || Q[i] < core_min) return;
+    const int p = P[i];                                       // (>= 0: E is a subset of the objects' pixels)
+    if (p < 0) return;
+    atomicOr(reinterpret_cast<unsigned*>(B + ((size_t)p & ~(size_t)3)), kFlagCored << (8 * (p & 3)));
+}
+
+// grid ceil(npix / 2048), 256 threads, 8 pixels each.  The component id of every seed pixel (step 13) in place over P, -1 elsewhere:
+// the core's root in R for a pixel of a core, the object's root in P for a pixel of a kept object that is not cored.  Both are flat
+// indices of first pixels in raster order and distinct components have distinct ids, so label_count / _scan / _number_kernel number
+// them as they number objects: a pixel is a seed root iff P[i] == i afterwards, and Q[i] >= 0 there (an area of E, or 0), so the
+// numbering is asked with min_area 0.  A thread reads P at its own pixel only, which is the only word of P it writes; R, Q and B are
+// only read.  *packed += (kept pixels that are no seed pixels) << 32 | (roots of cored objects): one 64-bit integer atomic per
+// workgroup that has any, which nothing reads in this launch; the low half cannot carry (a cored object has 5 pixels or more).
+__global__ void __launch_bounds__(kPixThreads) label_split_ids_kernel(int* __restrict__ P, const int* __restrict__ R, const int* __restrict__ Q,
+                                                                      const uint8_t* __restrict__ B, long long npix, int core_min,
+                                                                      unsigned long long* __restrict__ packed) {
+    __shared__ unsigned s_pending, s_cored;
+    if (threadIdx.x == 0) { s_pending = 0; s_cored = 0; }
+    __syncthreads();
+    unsigned pending = 0, cored = 0;
+    for (int j = 0; j < kScanBlock / kPixThreads; ++j) {
+        const long long i = (long long)blockIdx.x * kScanBlock + j * kPixThreads + threadIdx.x;
+        if (i >= npix) break;
+        const unsigned b = B[i];
+        int id = -1;
+        if (b & kFlagKept) {
+            const int p = P[i], r = R[i];
+            if (r >= 0 && Q[r] >= core_min) id = r;
+            else if (!(B[p] & kFlagCored)) id = p;
+            pending += id < 0;
+            cored += p == (int)i && (b & kFlagCored);
+        }
+        P[i] = id;
+    }
+    if (pending) atomicAdd(&s_pending, pending);              // (LDS)
+    if (cored) atomicAdd(&s_cored, cored);
+    __syncthreads();
+    if (threadIdx.x == 0 && (s_pending | s_cored)) atomicAdd(packed, ((unsigned long long)s_pending << 32) | s_cored);
 }
 
 // ---- the measurement ----
@@ -602,6 +765,10 @@ struct umx_labeler {
     int* d_counts = nullptr;      size_t counts_cap = 0;       // words
     long long* d_n = nullptr;
     umx_label_object* d_table = nullptr;  size_t table_cap = 0;   // records
+    // the split's own (allocated from the first split run on, then kept like the others): the third plane, the flags, three words
+    int* d_R = nullptr;
+    uint8_t* d_B = nullptr;       size_t split_cap = 0;        // words of d_R = bytes of d_B (rounded up to a whole word); 0: never asked for
+    long long* d_split = nullptr;                              // kSplitWords words the kernels of a split run add to
     std::vector<umx_label_object> table;                       // of the last run
     double ms[3] = {0.0, 0.0, 0.0};
     // the resident labels: d_P holds the int32 [res_H][res_W] label plane of res_N objects iff res_why is null; else why it does not
@@ -640,22 +807,31 @@ int lfail(umx_labeler* lb, int code, const char* fmt, ...) {
 
 // Buffers for K planes of H x W.  Nothing shrinks; when one is too small the arena is emptied and every buffer allocated again at the
 // larger of its old and its needed size (the arena frees as a whole, and the red zones of guard mode are per allocation).
-int ensure_buffers(umx_labeler* lb, size_t plane_bytes, size_t npix, size_t nblocks) {
-    if (plane_bytes <= lb->planes_cap && npix <= lb->pix_cap && nblocks <= lb->counts_cap && lb->d_n) return UMX_OK;
+// split: the call is a split run, which also needs the third plane and the flags; once allocated they are kept and grow with the rest.
+int ensure_buffers(umx_labeler* lb, size_t plane_bytes, size_t npix, size_t nblocks, bool split) {
+    const size_t split_need = split ? npix : 0;
+    if (plane_bytes <= lb->planes_cap && npix <= lb->pix_cap && nblocks <= lb->counts_cap && split_need <= lb->split_cap && lb->d_n) return UMX_OK;
     L_HIP(lb, hipStreamSynchronize(lb->stream));
     arena_free(&lb->mem);
     lb->d_planes = nullptr; lb->d_P = lb->d_Q = lb->d_counts = nullptr; lb->d_n = nullptr; lb->d_table = nullptr;
+    lb->d_R = nullptr; lb->d_B = nullptr; lb->d_split = nullptr;
     lb->d_mplanes = nullptr; lb->d_mrec = nullptr; lb->mplanes_cap = lb->mrec_cap = 0;   // (the measurement allocates its own again)
     const size_t pb = std::max(plane_bytes, lb->planes_cap), px = std::max(npix, lb->pix_cap), nb = std::max(nblocks, lb->counts_cap);
     const size_t tc = std::max<size_t>(lb->table_cap, 1024);
-    lb->planes_cap = lb->pix_cap = lb->counts_cap = lb->table_cap = 0;
+    const size_t sp = std::max(split_need, lb->split_cap);
+    lb->planes_cap = lb->pix_cap = lb->counts_cap = lb->table_cap = lb->split_cap = 0;
     L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_P, px * sizeof(int), false, "label parents"));
     L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_Q, px * sizeof(int), false, "label areas"));
     L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_counts, nb * sizeof(int), false, "label block counts"));
     L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_n, sizeof(long long), true, "label count"));
     L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_table, tc * sizeof(umx_label_object), false, "label table"));
     if (pb) L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_planes, pb, false, "label planes"));
-    lb->planes_cap = pb; lb->pix_cap = px; lb->counts_cap = nb; lb->table_cap = tc;
+    if (sp) {
+        L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_R, sp * sizeof(int), false, "label core parents"));
+        L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_B, (sp + 3) / 4 * 4, false, "label split flags"));
+        L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_split, kSplitWords * sizeof(long long), true, "label split counts"));
+    }
+    lb->planes_cap = pb; lb->pix_cap = px; lb->counts_cap = nb; lb->table_cap = tc; lb->split_cap = sp;
     return UMX_OK;
 }
 
@@ -672,27 +848,34 @@ int ensure_table(umx_labeler* lb, size_t n) {
 
 inline unsigned row_grid(int H) { return (unsigned)((H - 1) / kRowWaves + 1); }
 
-// the launches of one call on planes already on the device; out: null, the caller's plane or lb->d_P.  Returns with the stream idle
-// up to the count's read-back and the last launches enqueued.
-int run_launches(umx_labeler* lb, const uint8_t* planes, int K, int H, int W, const umx_label_options* o, int* out, long long* n_out) {
+// The components of the run heads in X (label_runs_kernel's or label_runs_mask_kernel's): X = the root of every object pixel, -1 off
+// the objects; Q = the areas at the roots, 0 elsewhere.
+int launch_components(umx_labeler* lb, int* X, int* Q, int H, int W) {
     const long long npix = (long long)H * W;
-    const int nblocks = (int)((npix + kScanBlock - 1) / kScanBlock);
     const unsigned pix_grid = (unsigned)((npix + kPixThreads - 1) / kPixThreads);
     hipStream_t s = lb->stream;
-    int *P = lb->d_P, *Q = lb->d_Q;
-    hipLaunchKernelGGL(label_runs_kernel, dim3(row_grid(H)), dim3(64 * kRowWaves), 0, s, planes, K, H, W, o->cls, P);
-    hipLaunchKernelGGL(label_strip_kernel, dim3((unsigned)((H - 1) / kStripRows + 1)), dim3(kMergeThreads), 0, s, P, H, W);
+    hipLaunchKernelGGL(label_strip_kernel, dim3((unsigned)((H - 1) / kStripRows + 1)), dim3(kMergeThreads), 0, s, X, H, W);
     for (long long span = kStripRows; span < H; span *= 2) {   // at most 26 levels
         const long long seams = (H - span + 2 * span - 1) / (2 * span);
-        hipLaunchKernelGGL(label_seam_kernel, dim3((unsigned)seams), dim3(kMergeThreads), 0, s, P, H, W, span);
+        hipLaunchKernelGGL(label_seam_kernel, dim3((unsigned)seams), dim3(kMergeThreads), 0, s, X, H, W, span);
     }
-    hipLaunchKernelGGL(label_heads_kernel, dim3(pix_grid), dim3(kPixThreads), 0, s, P, Q, npix, W);
-    hipLaunchKernelGGL(label_flatten_kernel, dim3(row_grid(H)), dim3(64 * kRowWaves), 0, s, P, Q, H, W);
+    hipLaunchKernelGGL(label_heads_kernel, dim3(pix_grid), dim3(kPixThreads), 0, s, X, Q, npix, W);
+    hipLaunchKernelGGL(label_flatten_kernel, dim3(row_grid(H)), dim3(64 * kRowWaves), 0, s, X, Q, H, W);
     L_HIP(lb, hipMemsetAsync(Q, 0, (size_t)npix * sizeof(int), s));
-    hipLaunchKernelGGL(label_area_kernel, dim3(row_grid(H)), dim3(64 * kRowWaves), 0, s, P, Q, H, W);
-    hipLaunchKernelGGL(label_count_kernel, dim3((unsigned)nblocks), dim3(64 * kScanWaves), 0, s, P, Q, npix, o->min_area, lb->d_counts);
-    hipLaunchKernelGGL(label_scan_kernel, dim3(1), dim3(kMergeThreads), 0, s, lb->d_counts, nblocks, lb->d_n);
-    hipLaunchKernelGGL(label_number_kernel, dim3((unsigned)nblocks), dim3(64 * kScanWaves), 0, s, P, Q, npix, o->min_area, lb->d_counts);
+    hipLaunchKernelGGL(label_area_kernel, dim3(row_grid(H)), dim3(64 * kRowWaves), 0, s, X, Q, H, W);
+    return UMX_OK;
+}
+
+// The count of the numbering (kept(i) = P[i] == i and Q[i] >= min_area) to *total on the device.
+void launch_count(umx_labeler* lb, const int* P, const int* Q, long long npix, int min_area, long long* total) {
+    const int nblocks = (int)((npix + kScanBlock - 1) / kScanBlock);
+    hipLaunchKernelGGL(label_count_kernel, dim3((unsigned)nblocks), dim3(64 * kScanWaves), 0, lb->stream, P, Q, npix, min_area, lb->d_counts);
+    hipLaunchKernelGGL(label_scan_kernel, dim3(1), dim3(kMergeThreads), 0, lb->stream, lb->d_counts, nblocks, total);
+}
+
+// n (the count the device left in d_n) to the host -- the stream is idle afterwards -- and the table sized and cleared for it
+int read_count_and_init_table(umx_labeler* lb, long long npix, long long* n_out) {
+    hipStream_t s = lb->stream;
     L_HIP(lb, hipGetLastError());
     long long n = 0;
     L_HIP(lb, hipMemcpyAsync(&n, lb->d_n, sizeof n, hipMemcpyDeviceToHost, s));
@@ -702,36 +885,130 @@ int run_launches(umx_labeler* lb, const uint8_t* planes, int K, int H, int W, co
     if (rc) return rc;
     if (n > 0)
         hipLaunchKernelGGL(label_table_init_kernel, dim3((unsigned)((n + kPixThreads - 1) / kPixThreads)), dim3(kPixThreads), 0, s, lb->d_table, n);
+    *n_out = n;
+    return UMX_OK;
+}
+
+// The rim growth (step 6) from the labels in src, with dst as the other plane -- ceil(R / 8) launches between the two, the last one
+// of R mod 8 levels (8 when that is 0); none when grow_radius is 0 -- then one pass over the plane that holds the result: the labels
+// to where the call wants them, the table.
+void launch_grow_and_table(umx_labeler* lb, const uint8_t* planes, int K, int H, int W, const umx_label_options* o, int* src, int* dst, int* out) {
+    hipStream_t s = lb->stream;
+    const int tiles_x = (W - 1) / kGrowTile + 1, tiles_y = (H - 1) / kGrowTile + 1;   // tiles_y * tiles_x <= 2^25 + 2^19: H * W <= INT_MAX
+    for (int left = o->grow_radius; left > 0; left -= kGrowHalo) {
+        hipLaunchKernelGGL(label_grow_kernel<false>, dim3((unsigned)tiles_y * (unsigned)tiles_x), dim3(kGrowThreads), 0, s, planes, K, H, W,
+                           o->grow_classes, src, dst, std::min(left, kGrowHalo), tiles_x, (long long*)nullptr);
+        std::swap(src, dst);
+    }
+    hipLaunchKernelGGL(label_grown_kernel, dim3(row_grid(H)), dim3(64 * kRowWaves), 0, s, src, H, W, out, lb->d_table);
+}
+
+// the launches of one call on planes already on the device; out: null, the caller's plane or lb->d_P.  Returns with the stream idle
+// up to the count's read-back and the last launches enqueued.
+int run_launches(umx_labeler* lb, const uint8_t* planes, int K, int H, int W, const umx_label_options* o, int* out, long long* n_out) {
+    const long long npix = (long long)H * W;
+    const int nblocks = (int)((npix + kScanBlock - 1) / kScanBlock);
+    const unsigned pix_grid = (unsigned)((npix + kPixThreads - 1) / kPixThreads);
+    hipStream_t s = lb->stream;
+    int *P = lb->d_P, *Q = lb->d_Q;
+    hipLaunchKernelGGL(label_runs_kernel, dim3(row_grid(H)), dim3(64 * kRowWaves), 0, s, planes, K, H, W, o->cls, P);
+    int rc = launch_components(lb, P, Q, H, W);
+    if (rc) return rc;
+    launch_count(lb, P, Q, npix, o->min_area, lb->d_n);
+    hipLaunchKernelGGL(label_number_kernel, dim3((unsigned)nblocks), dim3(64 * kScanWaves), 0, s, P, Q, npix, o->min_area, lb->d_counts);
+    long long n = 0;
+    if ((rc = read_count_and_init_table(lb, npix, &n))) return rc;
     if (o->grow_radius == 0) {
         hipLaunchKernelGGL(label_write_kernel, dim3(row_grid(H)), dim3(64 * kRowWaves), 0, s, P, Q, H, W, out, lb->d_table);
     } else {
-        // the seeds into P; Q is free from here on.  ceil(R / 8) launches between the two planes, the last one of R mod 8 levels (8
-        // when that is 0); then one pass over the plane the last launch wrote: the labels to where the call wants them, the table.
+        // the seeds into P; Q is free from here on
         hipLaunchKernelGGL(label_seed_kernel, dim3(pix_grid), dim3(kPixThreads), 0, s, P, Q, npix);
-        const int tiles_x = (W - 1) / kGrowTile + 1, tiles_y = (H - 1) / kGrowTile + 1;   // tiles_y * tiles_x <= 2^25 + 2^19: H * W <= INT_MAX
-        int *src = P, *dst = Q;
-        for (int left = o->grow_radius; left > 0; left -= kGrowHalo) {
-            hipLaunchKernelGGL(label_grow_kernel, dim3((unsigned)tiles_y * (unsigned)tiles_x), dim3(kGrowThreads), 0, s, planes, K, H, W,
-                               o->grow_classes, src, dst, std::min(left, kGrowHalo), tiles_x);
-            std::swap(src, dst);
-        }
-        hipLaunchKernelGGL(label_grown_kernel, dim3(row_grid(H)), dim3(64 * kRowWaves), 0, s, src, H, W, out, lb->d_table);
+        launch_grow_and_table(lb, planes, K, H, W, o, P, Q, out);
     }
     L_HIP(lb, hipGetLastError());
     *n_out = n;
     return UMX_OK;
 }
 
+// The launches of a split run, in the same frame as run_launches:
+//   the objects as there up to label_area_kernel: P = roots, Q = areas; label_count / _scan_kernel: N0 to a word of its own
+//   label_erode_kernel        B = kept | eroded per pixel (the last reader of the objects' areas)
+//   label_runs_mask_kernel    E's row runs into R; strip, seams, heads, flatten, area as for the objects: R = roots of E's components,
+//                             Q = their areas
+//   label_core_mark_kernel    kFlagCored at the root of every object that holds a core
+//   label_split_ids_kernel    the seed components' ids in place over P; label_count / _scan / _number_kernel number them (min_area 0)
+//   (N, N0 and the counts come back to the host; the table is sized for N)
+//   label_seed_kernel         the seed labels in place over P; Q and R are free from here on
+//   label_grow_kernel<true>   the regrow over class cls, P -> Q -> P ..., up to ceil(L / 8) launches; after each one the host reads the
+//                             number of pixels claimed so far and stops when a launch claimed none: the state is closed -- nothing but
+//                             these launches changes it -- so every later level would claim nothing either
+//   the rim growth and label_grown_kernel as in run_launches
+int run_split_launches(umx_labeler* lb, const uint8_t* planes, int K, int H, int W, const umx_label_split_options* so, int* out,
+                       umx_label_split_counts* counts) {
+    const umx_label_options* o = &so->base;
+    const long long npix = (long long)H * W;
+    const int nblocks = (int)((npix + kScanBlock - 1) / kScanBlock);
+    const unsigned pix_grid = (unsigned)((npix + kPixThreads - 1) / kPixThreads);
+    const int tiles_x = (W - 1) / kGrowTile + 1, tiles_y = (H - 1) / kGrowTile + 1;
+    const dim3 tile_grid((unsigned)tiles_y * (unsigned)tiles_x);
+    hipStream_t s = lb->stream;
+    int *P = lb->d_P, *Q = lb->d_Q, *R = lb->d_R;
+    uint8_t* B = lb->d_B;
+    L_HIP(lb, hipMemsetAsync(lb->d_split, 0, kSplitWords * sizeof(long long), s));
+    hipLaunchKernelGGL(label_runs_kernel, dim3(row_grid(H)), dim3(64 * kRowWaves), 0, s, planes, K, H, W, o->cls, P);
+    int rc = launch_components(lb, P, Q, H, W);
+    if (rc) return rc;
+    launch_count(lb, P, Q, npix, o->min_area, lb->d_split + kSplitBefore);
+    hipLaunchKernelGGL(label_erode_kernel, tile_grid, dim3(kGrowThreads), 0, s, P, Q, H, W, o->min_area, so->depth, tiles_x, B);
+    hipLaunchKernelGGL(label_runs_mask_kernel, dim3(row_grid(H)), dim3(64 * kRowWaves), 0, s, B, H, W, R);
+    if ((rc = launch_components(lb, R, Q, H, W))) return rc;
+    hipLaunchKernelGGL(label_core_mark_kernel, dim3(pix_grid), dim3(kPixThreads), 0, s, P, R, Q, npix, so->core_min_area, B);
+    hipLaunchKernelGGL(label_split_ids_kernel, dim3((unsigned)nblocks), dim3(kPixThreads), 0, s, P, R, Q, B, npix, so->core_min_area,
+                       reinterpret_cast<unsigned long long*>(lb->d_split + kSplitPacked));
+    launch_count(lb, P, Q, npix, 0, lb->d_n);
+    hipLaunchKernelGGL(label_number_kernel, dim3((unsigned)nblocks), dim3(64 * kScanWaves), 0, s, P, Q, npix, 0, lb->d_counts);
+    long long words[kSplitWords] = {0, 0, 0, 0};
+    L_HIP(lb, hipMemcpyAsync(words, lb->d_split, sizeof words, hipMemcpyDeviceToHost, s));
+    long long n = 0;
+    if ((rc = read_count_and_init_table(lb, npix, &n))) return rc;
+    const long long n_before = words[kSplitBefore], n_cored = words[kSplitPacked] & 0xffffffffll;
+    const long long pending = (long long)((unsigned long long)words[kSplitPacked] >> 32);
+    if (n_before < 0 || n_before > n || n_cored > n_before || pending > npix)
+        return lfail(lb, UMX_ERR_HIP, "the split counted %lld objects before, %lld cored, %lld after and %lld pixels to regrow in %lld pixels",
+                     n_before, n_cored, n, pending, npix);
+    hipLaunchKernelGGL(label_seed_kernel, dim3(pix_grid), dim3(kPixThreads), 0, s, P, Q, npix);
+    int *src = P, *dst = Q;
+    long long claimed = 0;
+    for (int left = so->regrow; left > 0 && claimed < pending; left -= kGrowHalo) {
+        hipLaunchKernelGGL(label_grow_kernel<true>, tile_grid, dim3(kGrowThreads), 0, s, planes, K, H, W, 1u << o->cls, src, dst,
+                           std::min(left, kGrowHalo), tiles_x, lb->d_split + kSplitClaimed);
+        std::swap(src, dst);
+        L_HIP(lb, hipGetLastError());
+        long long now = 0;
+        L_HIP(lb, hipMemcpyAsync(&now, lb->d_split + kSplitClaimed, sizeof now, hipMemcpyDeviceToHost, s));
+        L_HIP(lb, hipStreamSynchronize(s));
+        if (now < claimed || now > pending) return lfail(lb, UMX_ERR_HIP, "the regrow claimed %lld of %lld pixels", now, pending);
+        if (now == claimed) break;
+        claimed = now;
+    }
+    launch_grow_and_table(lb, planes, K, H, W, o, src, dst, out);
+    L_HIP(lb, hipGetLastError());
+    counts->n_objects = n; counts->n_before = n_before; counts->n_cored = n_cored; counts->unreached = pending - claimed;
+    return UMX_OK;
+}
+
+// split: a split run -- so holds its options (o is not looked at) and counts takes the four counts
 int run_any(umx_labeler* lb, const uint8_t* planes, bool on_host, int K, int H, int W, const umx_label_options* o, int32_t* labels,
-            int64_t* n_objects) {
+            int64_t* n_objects, bool split = false, const umx_label_split_options* so = nullptr, umx_label_split_counts* counts = nullptr) {
     if (!lb) return lfail(nullptr, UMX_ERR_INVALID, "null labeler");
     char msg[200];
-    if (umx_label_options_check(o, K, H, W, msg, sizeof msg) != UMX_OK) return lfail(lb, UMX_ERR_INVALID, "%s", msg);
+    if ((split ? umx_label_split_check(so, K, H, W, msg, sizeof msg) : umx_label_options_check(o, K, H, W, msg, sizeof msg)) != UMX_OK)
+        return lfail(lb, UMX_ERR_INVALID, "%s", msg);
     if (!planes) return lfail(lb, UMX_ERR_INVALID, "null planes");
     L_HIP(lb, hipSetDevice(lb->device));
     const size_t npix = (size_t)H * W, plane_bytes = (size_t)K * npix;
     lb->res_why = "the last run of this labeler failed";       // from here on the arena may be emptied and d_P is overwritten
-    int rc = ensure_buffers(lb, on_host ? plane_bytes : 0, npix, (npix + kScanBlock - 1) / kScanBlock);
+    int rc = ensure_buffers(lb, on_host ? plane_bytes : 0, npix, (npix + kScanBlock - 1) / kScanBlock, split);
     if (rc) return rc;
     hipStream_t s = lb->stream;
     lb->table.clear();
@@ -741,7 +1018,13 @@ int run_any(umx_labeler* lb, const uint8_t* planes, bool on_host, int K, int H, 
     L_HIP(lb, hipEventRecord(lb->ev[1], s));
     long long n = 0;
     int* out = !labels ? nullptr : on_host ? lb->d_P : labels;
-    rc = run_launches(lb, on_host ? lb->d_planes : planes, K, H, W, o, out, &n);
+    umx_label_split_counts sc = {0, 0, 0, 0};
+    if (split) {
+        rc = run_split_launches(lb, on_host ? lb->d_planes : planes, K, H, W, so, out, &sc);
+        n = sc.n_objects;
+    } else {
+        rc = run_launches(lb, on_host ? lb->d_planes : planes, K, H, W, o, out, &n);
+    }
     if (rc) {
         (void)hipStreamSynchronize(s);
         return rc;
@@ -760,6 +1043,7 @@ int run_any(umx_labeler* lb, const uint8_t* planes, bool on_host, int K, int H, 
     std::string gmsg;
     if ((rc = arena_check(lb->mem, &gmsg)) != UMX_OK) return lfail(lb, rc, "%s", gmsg.c_str());
     if (n_objects) *n_objects = n;
+    if (counts) *counts = sc;
     if (on_host && labels) { lb->res_H = H; lb->res_W = W; lb->res_N = n; lb->res_why = nullptr; }
     else lb->res_why = on_host ? "the last umx_labeler_run was given no label plane (labels_host was NULL)"
                                : "the last run was umx_labeler_run_dev, which leaves its labels with the caller: use umx_labeler_measure_dev";
@@ -917,6 +1201,32 @@ int umx_labeler_run(umx_labeler* lb, const uint8_t* planes_host, int K, int H, i
 int umx_labeler_run_dev(umx_labeler* lb, const uint8_t* planes_dev, int K, int H, int W, const umx_label_options* o, int32_t* labels_dev,
                         int64_t* n_objects) {
     return run_any(lb, planes_dev, false, K, H, W, o, labels_dev, n_objects);
+}
+
+int umx_label_split_check(const umx_label_split_options* o, int K, int H, int W, char* msg, size_t cap) {
+    char buf[200] = "";
+    if (!o) snprintf(buf, sizeof buf, "null label split options");
+    else if (umx_label_options_check(&o->base, K, H, W, buf, sizeof buf) != UMX_OK) {}   // (its words, unchanged)
+    else if (o->depth < 1 || o->depth > UMX_SPLIT_MAX_DEPTH)
+        snprintf(buf, sizeof buf, "depth is %d: the split erodes 1..%d levels", o->depth, (int)UMX_SPLIT_MAX_DEPTH);
+    else if (o->core_min_area < 1 || o->core_min_area > UMX_SPLIT_MAX_CORE_AREA)
+        snprintf(buf, sizeof buf, "core_min_area is %d: it must be 1..%d pixels", o->core_min_area, (int)UMX_SPLIT_MAX_CORE_AREA);
+    else if (o->regrow < 1 || o->regrow > UMX_SPLIT_MAX_REGROW)
+        snprintf(buf, sizeof buf, "regrow is %d: it must be 1..%d levels", o->regrow, (int)UMX_SPLIT_MAX_REGROW);
+    for (int i = 0; o && !buf[0] && i < 5; ++i)
+        if (o->reserved[i]) snprintf(buf, sizeof buf, "reserved must be zero (word %d of the split's reserved words is %d)", i, o->reserved[i]);
+    if (msg && cap) snprintf(msg, cap, "%s", buf);
+    return buf[0] ? UMX_ERR_INVALID : UMX_OK;
+}
+
+int umx_labeler_run_split(umx_labeler* lb, const uint8_t* planes_host, int K, int H, int W, const umx_label_split_options* o,
+                          int32_t* labels_host, umx_label_split_counts* counts) {
+    return run_any(lb, planes_host, true, K, H, W, nullptr, labels_host, nullptr, true, o, counts);
+}
+
+int umx_labeler_run_split_dev(umx_labeler* lb, const uint8_t* planes_dev, int K, int H, int W, const umx_label_split_options* o,
+                              int32_t* labels_dev, umx_label_split_counts* counts) {
+    return run_any(lb, planes_dev, false, K, H, W, nullptr, labels_dev, nullptr, true, o, counts);
 }
 
 int umx_labeler_objects(const umx_labeler* lb, umx_label_object* out, int64_t cap, int64_t* n) {

@@ -97,6 +97,15 @@ def build_parser(spec: ToolSpec) -> argparse.ArgumentParser:
                         "where two objects meet (default: no growth)")
     p.add_argument("--labelGrowClasses", dest="labelGrowClasses", type=int, nargs="+", default=None,
                    help="classes the objects grow over, 0-based in the MODEL's class order; default: every class but 0 and --labelClass")
+    # touching nuclei that the contour class did not keep apart are one object: --labelSplit D cuts an object at its necks (erosion
+    # cores of depth D, regrown inside the object), before any --labelGrow
+    p.add_argument("--labelSplit", dest="labelSplit", type=int, default=None, metavar="D",
+                   help="split the labelled objects at necks of up to 2 D pixels (D 1..8): erosion cores of depth D, regrown inside "
+                        "their object (the project's own definition)")
+    p.add_argument("--labelSplitCore", dest="labelSplitCore", type=int, default=None, metavar="C",
+                   help="erosion cores of fewer pixels seed no object (1..65536, default 1)")
+    p.add_argument("--labelSplitRegrow", dest="labelSplitRegrow", type=int, default=None, metavar="L",
+                   help="levels the cores grow back inside their object (1..255, default 255)")
     # how bright every labelled object is in the image's own pages: <stem>_Intensities_<suffix>.csv
     p.add_argument("--labelMeasure", dest="labelMeasure", type=int, nargs="*", default=None, metavar="PAGE",
                    help="also write mean, std, min and max of every labelled object in the probability planes and in these pages of "
@@ -108,7 +117,9 @@ def check_label_args(parser: argparse.ArgumentParser, args) -> None:
     """The refusals of the label flags that need no model (parser.error: exit status 2, like any bad flag)."""
     if not args.labelMask:
         for flag, v in (("--labelClass", args.labelClass), ("--labelMinArea", args.labelMinArea), ("--labelGrow", args.labelGrow),
-                        ("--labelGrowClasses", args.labelGrowClasses), ("--labelMeasure", args.labelMeasure)):
+                        ("--labelGrowClasses", args.labelGrowClasses), ("--labelMeasure", args.labelMeasure),
+                        ("--labelSplit", args.labelSplit), ("--labelSplitCore", args.labelSplitCore),
+                        ("--labelSplitRegrow", args.labelSplitRegrow)):
             if v is not None:
                 parser.error("%s needs --labelMask" % flag)
         return
@@ -120,6 +131,15 @@ def check_label_args(parser: argparse.ArgumentParser, args) -> None:
         parser.error("--labelGrowClasses needs --labelGrow")
     if args.labelGrow is not None and not 1 <= args.labelGrow <= 255:
         parser.error("--labelGrow %d: it must be 1..255 pixels" % args.labelGrow)
+    for flag, v in (("--labelSplitCore", args.labelSplitCore), ("--labelSplitRegrow", args.labelSplitRegrow)):
+        if v is not None and args.labelSplit is None:
+            parser.error("%s needs --labelSplit" % flag)
+    if args.labelSplit is not None and not 1 <= args.labelSplit <= 8:
+        parser.error("--labelSplit %d: it must be 1..8 pixels" % args.labelSplit)
+    if args.labelSplitCore is not None and not 1 <= args.labelSplitCore <= 65536:
+        parser.error("--labelSplitCore %d: it must be 1..65536 pixels" % args.labelSplitCore)
+    if args.labelSplitRegrow is not None and not 1 <= args.labelSplitRegrow <= 255:
+        parser.error("--labelSplitRegrow %d: it must be 1..255 levels" % args.labelSplitRegrow)
     for k in args.labelGrowClasses or ():
         if k < 0:
             parser.error("--labelGrowClasses %d: classes are numbered from 0" % k)
@@ -240,6 +260,7 @@ class _Stages:
         self.on = bool(os.environ.get("UMX_CLI_TIMING"))
         self.t = time.perf_counter()
         self.stages = []
+        self.notes = {}
         t0 = float(os.environ.get("UMX_CLI_T0", "0") or 0)
         if self.on and t0:
             self.stages.append(("interpreter_start_and_imports", time.time() - t0))
@@ -250,12 +271,18 @@ class _Stages:
             self.stages.append((name, now - self.t))
             self.t = now
 
+    def note(self, name, value):
+        """a value that goes into the report next to the stages' seconds"""
+        if self.on:
+            self.notes[name] = value
+
     def report(self):
         if self.on:
             import json
             import resource
             t0 = float(os.environ.get("UMX_CLI_T0", "0") or 0)
             d = {k: round(v, 4) for k, v in self.stages}
+            d.update(self.notes)
             if t0:
                 d["since_parent_spawned"] = round(time.time() - t0, 4)
             d["user_cpu_s"] = round(resource.getrusage(resource.RUSAGE_SELF).ru_utime, 3)
@@ -429,10 +456,16 @@ def run(tool: str, argv=None, script_dir: str = None) -> int:
             stack_u8 = u8_planes if fast else np.stack([plane_u8(k) for k in range(n_class)])
             with _umx.Labeler(UNet2D.Engine.device) as labeler:
                 labels, objects = labeler.run(stack_u8, args.labelClass, 1 if args.labelMinArea is None else args.labelMinArea,
-                                              grow=args.labelGrow or 0, grow_classes=grow_classes)
+                                              grow=args.labelGrow or 0, grow_classes=grow_classes, split=args.labelSplit or 0,
+                                              split_core=args.labelSplitCore or 1, split_regrow=args.labelSplitRegrow or 255)
                 tiffio.imsave(out_dir + "//" + stem + "_Labels_" + suffix + ".tif", labels, append=False)
                 write_objects_csv(out_dir + "//" + stem + "_Objects_" + suffix + ".csv", objects)
                 st.mark("label")
+                if args.labelSplit:
+                    c = labeler.split_counts()
+                    print("Label split: %d objects from %d (%d with a core), %d pixels unreached"
+                          % (c["n_objects"], c["n_before"], c["n_cored"], c["unreached"]))
+                    st.note("label_split", c)
                 if measure_pages_arg is not None:
                     # the labels (the grown ones with --labelGrow) are still on the device: the planes the labeler just used, then
                     # the file's pages one at a time; the file is written only when every page has been measured

@@ -36,6 +36,7 @@ EXPORTS = [
     "umx_label_options_check", "umx_labeler_create", "umx_labeler_destroy", "umx_labeler_last_error", "umx_labeler_run",
     "umx_labeler_run_dev", "umx_labeler_objects", "umx_labeler_last_ms",
     "umx_label_measure_check", "umx_labeler_measure", "umx_labeler_measure_dev", "umx_labeler_measure_last_ms",
+    "umx_label_split_check", "umx_labeler_run_split", "umx_labeler_run_split_dev",
 ]
 
 # the label mask's limits and the geometry of its kernels (the UMX_LABEL_* macros of include/umx.h; tests/test_label_cpu.py compares)
@@ -43,6 +44,8 @@ LABEL_MAX_CLASSES, LABEL_MAX_MIN_AREA = 16, 65536
 LABEL_STRIP_ROWS, LABEL_THREADS, LABEL_SCAN_BLOCK = 32, 1024, 2048
 # the growth: its largest radius, the tile a workgroup owns and the halo it loads round it (= the levels one launch advances)
 LABEL_MAX_GROW, LABEL_GROW_TILE, LABEL_GROW_HALO = 255, 64, 8
+# the split at the necks: its largest depth, core area and regrow bound (the UMX_SPLIT_* enumerators; tests/test_label_split_cpu.py compares)
+SPLIT_MAX_DEPTH, SPLIT_MAX_CORE_AREA, SPLIT_MAX_REGROW = 8, 65536, 255
 
 
 class UmxError(RuntimeError):
@@ -83,6 +86,17 @@ class _LabelOptions(ctypes.Structure):
     """umx_label_options: 32 bytes"""
     _anonymous_ = ("tail",)
     _fields_ = [("cls", ctypes.c_int32), ("min_area", ctypes.c_int32), ("tail", _LabelTail)]
+
+
+class _LabelSplitOptions(ctypes.Structure):
+    """umx_label_split_options: 64 bytes"""
+    _fields_ = [("base", _LabelOptions), ("depth", ctypes.c_int32), ("core_min_area", ctypes.c_int32), ("regrow", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 5)]
+
+
+class _LabelSplitCounts(ctypes.Structure):
+    """umx_label_split_counts: 32 bytes"""
+    _fields_ = [(n, ctypes.c_int64) for n in ("n_objects", "n_before", "n_cored", "unreached")]
 
 
 class LabelObject(ctypes.Structure):
@@ -276,6 +290,11 @@ def load(path: Optional[str] = None):
     for fn in (L.umx_labeler_run, L.umx_labeler_run_dev):
         fn.restype = c_int
         fn.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(_LabelOptions), c_void_p, ctypes.POINTER(ctypes.c_int64)]
+    L.umx_label_split_check.restype = c_int
+    L.umx_label_split_check.argtypes = [ctypes.POINTER(_LabelSplitOptions), c_int, c_int, c_int, ctypes.c_char_p, ctypes.c_size_t]
+    for fn in (L.umx_labeler_run_split, L.umx_labeler_run_split_dev):
+        fn.restype = c_int
+        fn.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(_LabelSplitOptions), c_void_p, ctypes.POINTER(_LabelSplitCounts)]
     L.umx_labeler_objects.restype = c_int
     L.umx_labeler_objects.argtypes = [c_void_p, c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
     L.umx_labeler_last_ms.restype = c_int
@@ -621,6 +640,28 @@ def label_options_check(K: int, H: int, W: int, cls: int, min_area: int = 1, res
     return "" if rc == 0 else buf.value.decode()
 
 
+def _label_split_options(base: "_LabelOptions", split: int, split_core: int, split_regrow: int) -> "_LabelSplitOptions":
+    o = _LabelSplitOptions()
+    o.base = base
+    o.depth, o.core_min_area, o.regrow = int(split), int(split_core), int(split_regrow)
+    return o
+
+
+def label_split_check(K: int, H: int, W: int, cls: int, min_area: int = 1, grow: int = 0, grow_classes=None, split: int = 1,
+                      split_core: int = 1, split_regrow: int = 255, base_reserved=None, reserved=None, null: bool = False) -> str:
+    """umx_label_split_check: "" if a split run of K planes of H x W is accepted, else the reason.  ``base_reserved``: the six words after
+    min_area of the base by index, as label_options_check's ``reserved``; ``reserved``: the split's own five.  ``null``: a NULL record.
+    Host only."""
+    o = _label_split_options(_label_options(K, cls, min_area, grow, grow_classes), split, split_core, split_regrow)
+    for j, v in enumerate(base_reserved or ()):
+        o.base.reserved[j] = int(v)
+    for j, v in enumerate(reserved or ()):
+        o.reserved[j] = int(v)
+    buf = ctypes.create_string_buffer(256)
+    rc = load().umx_label_split_check(None if null else ctypes.byref(o), int(K), int(H), int(W), buf, len(buf))
+    return "" if rc == 0 else buf.value.decode()
+
+
 def label_measure_check(dtype: int, C: int, H: int, W: int, n_objects: int = 0) -> str:
     """umx_label_measure_check: "" if a measurement of C planes of H x W of that dtype code against n_objects labels is accepted, else
     the reason.  Host only."""
@@ -652,6 +693,7 @@ class Labeler:
         if rc:
             raise UmxError(rc, self._L.umx_labeler_last_error(None).decode())
         self.device = device
+        self._split_counts = None
 
     def close(self) -> None:
         if getattr(self, "_lb", None) and self._lb.value:
@@ -689,32 +731,54 @@ class Labeler:
         self._check(self._L.umx_labeler_last_ms(self._lb, *[ctypes.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
+    def split_counts(self) -> dict:
+        """n_objects (N), n_before (N0), n_cored and unreached of the last run with split > 0 of this Labeler; None before one, and
+        after a later run without a split."""
+        return self._split_counts
+
+    def _run_any(self, planes_ptr, dev: bool, K: int, H: int, W: int, o: "_LabelOptions", labels_ptr, split: int, split_core: int,
+                 split_regrow: int) -> int:
+        """the entry of today when split is 0, else the split's; -> N"""
+        planes_ptr, labels_ptr = ctypes.c_void_p(planes_ptr), ctypes.c_void_p(labels_ptr or None)
+        self._split_counts = None
+        if not split:
+            n = ctypes.c_int64()
+            fn = self._L.umx_labeler_run_dev if dev else self._L.umx_labeler_run
+            self._check(fn(self._lb, planes_ptr, K, H, W, ctypes.byref(o), labels_ptr, ctypes.byref(n)))
+            return n.value
+        so = _label_split_options(o, split, split_core, split_regrow)
+        c = _LabelSplitCounts()
+        fn = self._L.umx_labeler_run_split_dev if dev else self._L.umx_labeler_run_split
+        self._check(fn(self._lb, planes_ptr, K, H, W, ctypes.byref(so), labels_ptr, ctypes.byref(c)))
+        self._split_counts = {name: int(getattr(c, name)) for name, _ in _LabelSplitCounts._fields_}
+        return int(c.n_objects)
+
     def run(self, planes: np.ndarray, cls: Optional[int] = None, min_area: int = 1, want_labels: bool = True, grow: int = 0,
-            grow_classes=None):
+            grow_classes=None, split: int = 0, split_core: int = 1, split_regrow: int = 255):
         """planes uint8 [K, H, W] in the model's class order -> (labels int32 [H, W], objects); ``cls`` None: the last class.
         want_labels False: labels is None (only the count and the table come down).  grow R > 0: the kept objects grow R levels
-        over the pixels whose class is in ``grow_classes`` (an iterable of class indices; None: every class but 0 and ``cls``)."""
+        over the pixels whose class is in ``grow_classes`` (an iterable of class indices; None: every class but 0 and ``cls``).
+        split D > 0: the kept objects are split at their necks first (erosion cores of depth D and area >= ``split_core``, regrown
+        at most ``split_regrow`` levels inside their objects); split_counts() has the counts.
+        split 0 is the call of before."""
         planes = np.ascontiguousarray(planes)
         if planes.dtype != np.uint8 or planes.ndim != 3:
             raise TypeError("planes must be uint8 [K, H, W]")
         K, H, W = planes.shape
         o = _label_options(K, cls, min_area, grow, grow_classes)
         labels = np.empty((H, W), np.int32) if want_labels else None
-        n = ctypes.c_int64()
-        self._check(self._L.umx_labeler_run(self._lb, planes.ctypes.data, K, H, W, ctypes.byref(o),
-                                            labels.ctypes.data if want_labels else None, ctypes.byref(n)))
+        n = self._run_any(planes.ctypes.data, False, K, H, W, o, labels.ctypes.data if want_labels else None, split, split_core, split_regrow)
         objs = self.objects()
-        assert len(objs) == n.value
+        assert len(objs) == n
         return labels, objs
 
     def run_ptr(self, planes_ptr: int, K: int, H: int, W: int, labels_ptr: int = 0, cls: Optional[int] = None, min_area: int = 1,
-                grow: int = 0, grow_classes=None) -> np.ndarray:
+                grow: int = 0, grow_classes=None, split: int = 0, split_core: int = 1, split_regrow: int = 255) -> np.ndarray:
         """umx_labeler_run_dev on DEVICE addresses (e.g. torch.Tensor.data_ptr()): uint8 [K, H, W] in, int32 [H, W] out (0: no label
-        plane) -> objects.  The planes must be complete; the call returns with the labels complete.  grow, grow_classes: as run."""
+        plane) -> objects.  The planes must be complete; the call returns with the labels complete.  grow, grow_classes and the
+        split's three: as run."""
         o = _label_options(int(K), cls, min_area, grow, grow_classes)
-        n = ctypes.c_int64()
-        self._check(self._L.umx_labeler_run_dev(self._lb, ctypes.c_void_p(planes_ptr), int(K), int(H), int(W), ctypes.byref(o),
-                                                ctypes.c_void_p(labels_ptr or None), ctypes.byref(n)))
+        self._run_any(planes_ptr, True, int(K), int(H), int(W), o, labels_ptr, split, split_core, split_regrow)
         return self.objects()
 
     def measure(self, planes: np.ndarray) -> np.ndarray:
