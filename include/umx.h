@@ -381,6 +381,49 @@ UMX_API int umx_labeler_measure_dev(umx_labeler* lb, const int32_t* labels_dev, 
 UMX_API int umx_labeler_measure_last_ms(const umx_labeler* lb, double* upload_ms, double* kernel_ms, double* download_ms);
 
 /*
+ * Shape of every labelled object (the definition is the project's own).  From labels int32
+ * [H][W] with objects 1..N -- a value < 0 or > N counts as 0 and is never used as an index; a label need not be connected -- for
+ * every label j, with M_j the mask labels == j padded with one ring of 0:
+ *   16. one umx_label_shape, record j - 1: the sums of y, x, y * y, y * x and x * x over the pixels of M_j in image coordinates, and
+ *       the numbers of the (H + 1) x (W + 1) 2x2 windows of the padded mask that hold exactly one pixel of M_j (q1), two that share
+ *       an edge (q2), two on a diagonal (qd), three (q3), four (q4).  A window is classified per label: one with pixels of two labels
+ *       counts once for each, by that label's own pattern.  A label no pixel carries gives all zeros.
+ *   17. 4 * area = q1 + 2 q2 + 2 qd + 3 q3 + 4 q4;  edges = q1 + q2 + 2 qd + q3 is the number of pixel edges between M_j and its
+ *       complement, the image border included;  euler = (q1 - q3 + 2 qd) / 4 divides exactly and is the Euler number for a
+ *       4-connected foreground and an 8-connected background; for a 4-connected object holes = 1 - euler.
+ *   18. axes, eccentricity, orientation and the perimeter estimate are host arithmetic in float64 on these integers, stated once in
+ *       unmicst_amd/umx.py shape_descriptors (DESIGN.md has the formulas).
+ * Limits: 1 <= H, W <= 65536, H * W <= 2^31 - 1, 0 <= n_objects <= 2^31 - 1.  Then y * y and x * x are below 2^32 and area below
+ * 2^31, so every sum stays below 2^63; a window count is at most (H + 1) * (W + 1) <= 2^31 + 2^17 + 1 < 2^32.
+ * Everything is an integer and every atomic an integer add that nothing reads before its launch ends: two calls give the same
+ * bytes.  One launch, one wave per row; per row run at most five 64-bit adds and five 32-bit ones (an addend of 0 is skipped; a run
+ * inside an object has only q4) at record label - 1.  Known limit, as for the measurement ("salt"): an object made of 10^7 row runs
+ * serialises its atomics.
+ */
+typedef struct umx_label_shape {
+    int64_t sum_y, sum_x, sum_yy, sum_xy, sum_xx;
+    uint32_t q1, q2, qd, q3, q4, reserved;
+} umx_label_shape;   /* 64 bytes */
+/* The largest side of a plane whose shapes are taken: the squares of its coordinates stay below 2^32. */
+#define UMX_SHAPE_MAX_SIDE 65536
+/* Host only, no device: 1 <= H, W <= 65536; H * W <= 2^31 - 1; 0 <= n_objects <= 2^31 - 1.  UMX_OK, or UMX_ERR_INVALID with the
+ * reason in msg (cap bytes; may be NULL). */
+UMX_API int umx_label_shape_check(int H, int W, int64_t n_objects, char* msg, size_t cap);
+/* The shapes of the labels of the last successful host run that was given a label plane (plain, grown or split): they are still on
+ * the device.  N records into out (cap: its records), N into *n (may be NULL); out NULL with cap 0: only N into *n.  Refusals as
+ * umx_labeler_measure's (UMX_ERR_INVALID, nothing touched, the labeler usable, the resident labels kept): no such run, a later run
+ * without a label plane or on device pointers or a failed one, H or W other than that run's, cap < N.  Synchronous: returns with
+ * the stream idle, and under UMX_DEBUG_GUARD ends in the check of the red zones.  The records live in the labeler's arena, grown on
+ * demand and kept. */
+UMX_API int umx_labeler_shape(umx_labeler* lb, int H, int W, umx_label_shape* out, int64_t cap, int64_t* n);
+/* The same on a DEVICE pointer of the labeler's device: labels_dev int32 [H][W] with objects 1..n_objects, complete when the call is
+ * made and only read.  Needs no prior run and leaves the resident labels alone.  n_objects records into out_host (cap >= that). */
+UMX_API int umx_labeler_shape_dev(umx_labeler* lb, const int32_t* labels_dev, int64_t n_objects, int H, int W, umx_label_shape* out_host,
+                                  int64_t cap);
+/* Milliseconds of the last shape call: the two launches, the download of the records.  Either may be NULL. */
+UMX_API int umx_labeler_shape_last_ms(const umx_labeler* lb, double* kernel_ms, double* download_ms);
+
+/*
  * Splitting touching nuclei at their necks by erosion cores (the definition is the project's
  * own).  Two nuclei are separate objects only where an unbroken line of another class lies between them; where that line has a gap
  * the labelling joins them.  With a depth D, a minimum core area C and a regrow bound L, on top of the options of a labelling run:

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Time the label mask (umx_labeler_run) on synthetic H x W stacks of K = 3 uint8 planes (GPU box); one JSON
 line.  usage: bench_label.py [H=16384] [W=H] [--reps 3] [--grow R] [--measure C [--measure-dtype u8|u16]] [--split D [--split-core C]]
+       [--shape [--no-host]]
 
 Two inputs, both made here by pure-numpy recipes (no scipy in the generators, nothing from tests/):
   blobs  nuclei-like discs: the image is cut into 32 x 32 cells; a seeded draw keeps 60 % of them, and each kept cell gets one disc of
@@ -22,7 +23,13 @@ sums of the same planes over the same labels on this box's CPU share (one weight
 --split D: an input of its own, bodies joined in pairs: the image is cut into cells of 32 x 64; a seeded draw keeps 60 % of them, and each
 kept cell gets two squares of 24 x 24 joined by a bridge of 2 D rows -- the widest neck that depth D cuts, so every pair must come back
 as two objects.  The same planes are labelled without and with the split; "split_ms" is the
-difference of the two kernel times, and the four counts of the split are reported."""
+difference of the two kernel times, and the four counts of the split are reported.
+--shape: the blobs input alone, labelled with its label plane kept on the device, then the shapes of its objects (umx_labeler_shape,
+DESIGN.md section 8.1 steps 16 to 18): the kernel and download milliseconds umx_labeler_shape_last_ms reports (the best of --reps by
+kernel time, after one warm-up), beside them the one-plane uint16 measurement of the same labels (the yardstick: it reads the same
+label plane once and 2 bytes a pixel more), the bytes the shape launch moves at most and at least, and the seconds numpy / scipy take
+for the same table on this box's CPU share: five weighted np.bincount passes for the moments, band by band, and the window counts
+object by object on scipy.ndimage.find_objects' boxes."""
 import argparse
 import json
 import os
@@ -181,6 +188,70 @@ def measure_bench(a, H, W):
             "numpy_bincount_s": round(cpu_s, 3)}
 
 
+def best_shape_ms(lb, reps):
+    """-> (records, (kernel, download) ms of the shape call with the least kernel time) after one warm-up"""
+    rec = lb.shape()
+    best = None
+    for _ in range(reps):
+        lb.shape()
+        ms = lb.shape_last_ms()
+        if best is None or ms[0] < best[0]:
+            best = ms
+    return rec, best
+
+
+def host_shapes(labels, N, band=1024):
+    """the same table by numpy / scipy -> (sum_y, sum_x, sum_yy, sum_xy, sum_xx, q1, q2, qd, q3, q4), int64 [N] each"""
+    from scipy import ndimage
+    H, W = labels.shape
+    mom = np.zeros((5, N + 1))
+    xx = np.arange(W, dtype=np.float64)
+    for y0 in range(0, H, band):                             # (every sum stays below 2^53: exact in float64)
+        lab = labels[y0:y0 + band]
+        yy = np.arange(y0, y0 + lab.shape[0], dtype=np.float64)[:, None]
+        for k, w in enumerate((yy + 0 * xx, xx + 0 * yy, yy * yy + 0 * xx, yy * xx, xx * xx + 0 * yy)):
+            mom[k] += np.bincount(lab.ravel(), weights=w.ravel(), minlength=N + 1)
+    q = np.zeros((5, N), np.int64)
+    for j, box in enumerate(ndimage.find_objects(labels, max_label=N)):
+        if box is None:
+            continue
+        m = np.pad(labels[box] == j + 1, 1)
+        a, b, c, d = m[:-1, :-1], m[:-1, 1:], m[1:, :-1], m[1:, 1:]
+        n = a.astype(np.int8) + b + c + d
+        two = n == 2
+        diag = int((two & (a == d)).sum())
+        q[:, j] = (int((n == 1).sum()), int(two.sum()) - diag, diag, int((n == 3).sum()), int((n == 4).sum()))
+    return tuple(mom[:, 1:].astype(np.int64)) + tuple(q)
+
+
+def shape_bench(a, H, W):
+    npix = H * W
+    px = np.random.default_rng(3).integers(0, 65536, (1, H, W), dtype=np.uint16)
+    with umx.Labeler(a.device) as lb:
+        planes = planes_of(blob_mask(H, W))
+        labels, objects = lb.run(planes)
+        label_ms = lb.last_ms()
+        del planes
+        N = len(objects)
+        rec, ms = best_shape_ms(lb, a.reps)
+        _, ms1 = best_measure_ms(lb, px, a.reps)
+    d = umx.shape_descriptors(rec)
+    assert np.array_equal(d["area"], objects["area"]) and np.array_equal(rec["sum_y"], objects["sum_y"])
+    cpu_s = None
+    if not a.no_host:
+        t = time.perf_counter()
+        host = host_shapes(labels, N)
+        cpu_s = time.perf_counter() - t
+        names = ("sum_y", "sum_x", "sum_yy", "sum_xy", "sum_xx", "q1", "q2", "qd", "q3", "q4")
+        assert all(np.array_equal(rec[n].astype(np.int64), h) for n, h in zip(names, host))
+    return {"shape": True, "objects": N, "object_pixels": int(objects["area"].sum()), "holes": int(d["holes"].sum()),
+            "label_kernel_ms": round(label_ms[1], 3), "kernel_ms": round(ms[0], 3), "download_ms": round(ms[1], 3),
+            "one_plane_u16_measure_kernel_ms": round(ms1[1], 3), "ratio_to_measure": round(ms[0] / ms1[1], 3),
+            # every label word once from memory at least; three times (the rows above and below again) at most; the records written and added to
+            "read_bytes_lower": 4 * npix, "read_bytes_upper": 12 * npix, "record_bytes": 64 * N,
+            "numpy_scipy_s": None if cpu_s is None else round(cpu_s, 3)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("H", type=int, nargs="?", default=16384)
@@ -192,6 +263,8 @@ def main():
     ap.add_argument("--split", type=int, default=0, metavar="D")
     ap.add_argument("--split-core", dest="split_core", type=int, default=1, metavar="C")
     ap.add_argument("--measure-dtype", dest="measure_dtype", choices=("u8", "u16"), default="u16")
+    ap.add_argument("--shape", action="store_true")
+    ap.add_argument("--no-host", dest="no_host", action="store_true", help="with --shape: leave the numpy / scipy figure out (a traced run)")
     a = ap.parse_args()
     H, W = a.H, a.W or a.H
     out = {"tool": "bench_label", "H": H, "W": W, "K": 3, "min_area": 1, "reps": a.reps}
@@ -203,6 +276,9 @@ def main():
         return
     if a.measure:
         print(json.dumps(dict(out, **measure_bench(a, H, W))))
+        return
+    if a.shape:
+        print(json.dumps(dict(out, **shape_bench(a, H, W))))
         return
     with umx.Labeler(a.device) as lb:
         for name, mask in (("blobs", blob_mask(H, W)), ("salt", salt_mask(H, W))):

@@ -35,6 +35,10 @@
 //   label_measure_init_kernel, label_measure_kernel   one wave per row: the labels (the P plane a run left, or the caller's) read once
 //                         for the group's planes; every row run adds its count, its sums of v and v * v and its extremes of every plane
 //                         to record [plane][label - 1]
+// The shapes (umx_labeler_shape / _shape_dev) are
+//   label_shape_init_kernel, label_shape_kernel   one wave per row: the labels of the row and of the rows above and below it; every
+//                         row run adds its moments (closed forms of its row and its two ends) and the counts of the 2x2 windows
+//                         that its pixels own to record label - 1
 //
 // Why no workgroup waits for another one, and none reads inside a kernel what another one writes in it: in the strip launch a workgroup
 // touches only pixels of its strip -- a link made there joins two run heads of the strip, so a walk from a pixel of the strip stays in
@@ -750,6 +754,173 @@ __global__ void __launch_bounds__(64 * kRowWaves) label_measure_kernel(const int
         });
 }
 
+// ---- the shapes ----
+// The five window counts of step 16 as one word: fields of kQuadBits bits, q1 lowest.  A pixel adds at most 4 (one per window that
+// holds it), a 64-pixel chunk at most 256 to a field: 9 bits would do, 12 leave room and still fit five fields.
+constexpr int kQuads = 5, kQuadBits = 12;
+constexpr unsigned long long kQ1 = 1ull, kQ2 = 1ull << kQuadBits, kQd = 1ull << (2 * kQuadBits), kQ3 = 1ull << (3 * kQuadBits),
+                             kQ4 = 1ull << (4 * kQuadBits);
+static_assert(4 * 64 < (1 << kQuadBits) && kQuads * kQuadBits <= 64, "a chunk's counts fit their fields, the fields one word");
+static_assert(sizeof(umx_label_shape) == 64, "the shape record");
+
+// What one row run carries: its pixel count (its columns are [xb - count + 1, xb] at the flush) and its five window counts.
+struct RunQuads {
+    unsigned count;
+    unsigned q[kQuads];
+};
+
+// The sibling of for_each_run_sums whose payload is one packed word of small counts: key_at(x) once for every pixel of the row as
+// there; word_at(x, t) -- t the pixel's key, -2 past the row's end -- is called by ALL 64 lanes together in every chunk that holds a
+// key >= 0 (so it may shuffle) and returns the pixel's fields, 0 where t < 0; flush(key, xb, r) once for every maximal segment of
+// equal key >= 0, xb its last column -- by one lane, the last pixel of the segment (or lane 0 for a carried segment that the next
+// chunk does not continue).  Inside a chunk the fields of a segment are one segmented inclusive scan of the word (6 steps); a
+// segment that reaches the end of a chunk is carried unpacked in wave-uniform registers (a run of 65536 pixels counts to 2^18) and
+// joined to the first segment of the next chunk when the keys agree.  ceil(W / 64) rounds; count <= W.
+template <typename KeyAt, typename WordAt, typename Flush>
+__device__ inline void for_each_run_quads(int W, int lane, KeyAt key_at, WordAt word_at, Flush flush) {
+    constexpr unsigned kField = (1u << kQuadBits) - 1u;
+    RunQuads carry;                                       // the carried segment, the same in every lane; ckey < 0: none
+    int ckey = -1, cend = 0;                              // cend: the last column of the chunk the carry ends in
+    carry.count = 0;
+#pragma unroll
+    for (int k = 0; k < kQuads; ++k) carry.q[k] = 0;
+    const int nchunks = (W - 1) / 64 + 1;
+    for (int c = 0; c < nchunks; ++c) {
+        const int x0 = c * 64;
+        const bool in = lane < W - x0;
+        const int x = in ? x0 + lane : x0;
+        const int t = in ? key_at(x) : -2;                // past the row's end: a key no pixel has
+        const bool last = c + 1 == nchunks;
+        if (__ballot(t >= 0) == 0ull) {                   // (the same answer in every lane)
+            if (ckey >= 0 && lane == 0) flush(ckey, cend, carry);
+            ckey = -1;
+            continue;
+        }
+        const int tl = __shfl_up(t, 1);
+        const bool head = lane == 0 || t != tl;
+        const unsigned long long heads = __ballot(head);  // (bit 0 is always set)
+        const int first = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));   // the lane of this segment's head, <= lane
+        const bool tail = lane == 63 || ((heads >> (lane + 1)) & 1ull);
+        unsigned long long pk = word_at(x, t);
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {                // 6 steps
+            const unsigned long long p = __shfl_up(pk, d);
+            if (lane - d >= first) pk += p;
+        }
+        RunQuads r;                                       // of the segment's pixels up to this lane: the whole segment at its tail
+        r.count = (unsigned)(lane - first + 1);
+#pragma unroll
+        for (int k = 0; k < kQuads; ++k) r.q[k] = (unsigned)(pk >> (k * kQuadBits)) & kField;
+        if (ckey >= 0) {
+            if (__shfl(t, 0) == ckey) {                   // the chunk's first segment continues the carried one
+                if (first == 0) {
+                    r.count += carry.count;
+#pragma unroll
+                    for (int k = 0; k < kQuads; ++k) r.q[k] += carry.q[k];
+                }
+            } else if (lane == 0) {
+                flush(ckey, cend, carry);
+            }
+        }
+        if (tail && t >= 0 && (lane != 63 || last)) flush(t, x, r);
+        const int t63 = __builtin_amdgcn_readlane(t, 63);
+        if (!last && t63 >= 0) {
+            ckey = t63;
+            cend = x0 + 63;
+            carry.count = of_lane63(r.count);
+#pragma unroll
+            for (int k = 0; k < kQuads; ++k) carry.q[k] = of_lane63(r.q[k]);
+        } else {
+            ckey = -1;
+        }
+    }
+}
+
+// one thread per record, j < n: the record of a label that no pixel carries
+__global__ void __launch_bounds__(kPixThreads) label_shape_init_kernel(umx_label_shape* __restrict__ rec, long long n) {
+    const long long j = (long long)blockIdx.x * kPixThreads + threadIdx.x;
+    if (j >= n) return;
+    umx_label_shape z;
+    z.sum_y = z.sum_x = z.sum_yy = z.sum_xy = z.sum_xx = 0;
+    z.q1 = z.q2 = z.qd = z.q3 = z.q4 = z.reserved = 0;
+    rec[j] = z;
+}
+
+// 0^2 + 1^2 + ... + m^2 for -1 <= m < 65536: the product is below 2^49
+__device__ inline long long squares_to(long long m) { return m * (m + 1) * (2 * m + 1) / 6; }
+
+// grid ceil(H / 4).  labels [H][W] is only read: row y by its wave's lanes, rows y - 1 and y + 1 alongside it (outside the image is
+// 0, which no object carries).  A label outside 1..N is key -1: no record is addressed for it, and as a neighbour it equals no label
+// that is.  rec [N]: record label - 1 takes, per row run, the moments -- closed forms of y and the run's two ends -- and the window
+// counts: integer atomic adds that nothing reads in this launch, those with an addend of 0 left out.
+// The windows: a pixel lies in four 2x2 windows of the padded plane, as their down-right, down-left, up-right and up-left corner.  A
+// (window, label) pair is counted by the FIRST pixel of that label in the window in the order up-left, up-right, down-left,
+// down-right, so exactly once, and by a function of the pixel's 3x3 neighbourhood: e.g. as the down-right corner a pixel counts
+// the window only when none of the three others has its label, and then the window holds one pixel of it.
+// Bounds: row y < H; a pixel word is r * W + x < H * W <= INT_MAX for 0 <= r < H and 0 <= x < W, formed in 64 bits; the columns
+// x0 - 1 and x0 + 64 are read by one lane each and only where they are >= 0 and < W; H, W <= 65536 (umx_label_shape_check), so
+// m * (m + 1) * (2 m + 1) and y * y * W stay far inside 64 bits.
+// Known limit ("salt"): an object made of 10^7 one-pixel runs sends 10^7 sets of atomics to one record.
+__global__ void __launch_bounds__(64 * kRowWaves) label_shape_kernel(const int* __restrict__ labels, int H, int W, int N,
+                                                                      umx_label_shape* __restrict__ rec) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if ((long long)blockIdx.x * kRowWaves + wave >= H) return;    // (the whole wave: no barrier below)
+    const int y = blockIdx.x * kRowWaves + wave;
+    const int* mid = labels + (size_t)y * W;
+    const int* up = y > 0 ? labels + (size_t)(y - 1) * W : nullptr;
+    const int* dn = y + 1 < H ? labels + (size_t)(y + 1) * W : nullptr;
+    // the labels at columns x - 1 and x + 1 of one row (null: outside the image) from the lanes' own m at column x, by all lanes
+    // together; a lane past the row's end holds an m that is no label
+    auto three = [&](const int* row, int x, bool in, int& l, int& m, int& r) {
+        l = __shfl_up(m, 1);
+        r = __shfl_down(m, 1);
+        if (lane == 0) l = row && in && x > 0 ? row[x - 1] : 0;
+        if (lane == 63) r = row && in && x + 1 < W ? row[x + 1] : 0;
+    };
+    for_each_run_quads(
+        W, lane,
+        [&](int x) {
+            const int l = mid[x];
+            return l >= 1 && l <= N ? l - 1 : -1;
+        },
+        [&](int x, int t) {
+            const bool in = t != -2;
+            const int L = t + 1;                          // the pixel's label; 0 or less where it has no record: equal to no label
+            int ul, uc = up && in ? up[x] : 0, ur, ml, mc = L, mr, dl, dc = dn && in ? dn[x] : 0, dr;
+            three(up, x, in, ul, uc, ur);
+            three(mid, x, in, ml, mc, mr);
+            three(dn, x, in, dl, dc, dr);
+            if (t < 0) return 0ull;
+            const bool e_ul = ul == L, e_uc = uc == L, e_ur = ur == L, e_ml = ml == L, e_mr = mr == L, e_dl = dl == L, e_dc = dc == L,
+                       e_dr = dr == L;
+            unsigned long long w = 0;
+            if (!e_ul && !e_uc && !e_ml) w += kQ1;                               // down-right corner: alone in it
+            if (!e_uc && !e_ur) w += e_mr ? kQ2 : kQ1;                           // down-left: with its right neighbour at most
+            if (!e_ml) w += e_dl ? (e_dc ? kQ3 : kQd) : (e_dc ? kQ2 : kQ1);      // up-right: the row below decides
+            const int n = (int)e_mr + (int)e_dc + (int)e_dr;                     // up-left: always the first
+            w += n == 0 ? kQ1 : n == 3 ? kQ4 : n == 2 ? kQ3 : e_dr ? kQd : kQ2;
+            return w;
+        },
+        [&](int key, int xb, const RunQuads& r) {
+            umx_label_shape* o = rec + key;
+            const long long n = r.count, xa = xb - n + 1;
+            const long long sx = (xa + xb) * n / 2;       // (xa + xb and n are not both odd)
+            const long long sxx = squares_to(xb) - squares_to(xa - 1);
+            auto add64 = [](int64_t* p, long long v) {
+                if (v) atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
+            };
+            add64(&o->sum_y, (long long)y * n);
+            add64(&o->sum_x, sx);
+            add64(&o->sum_yy, (long long)y * y * n);
+            add64(&o->sum_xy, (long long)y * sx);
+            add64(&o->sum_xx, sxx);
+            unsigned* const q[kQuads] = {&o->q1, &o->q2, &o->qd, &o->q3, &o->q4};
+#pragma unroll
+            for (int k = 0; k < kQuads; ++k)
+                if (r.q[k]) atomicAdd(q[k], r.q[k]);
+        });
+}
+
 }  // namespace
 
 }  // namespace umx
@@ -780,6 +951,9 @@ struct umx_labeler {
     void* d_mplanes = nullptr;    size_t mplanes_cap = 0;      // bytes
     umx_label_measure* d_mrec = nullptr;  size_t mrec_cap = 0; // records
     double mms[3] = {0.0, 0.0, 0.0};
+    // the shapes' own allocation, as the measurement's: the records
+    umx_label_shape* d_srec = nullptr;    size_t srec_cap = 0; // records
+    double sms[2] = {0.0, 0.0};                                // launches | download
     std::string err;
 };
 
@@ -816,6 +990,7 @@ int ensure_buffers(umx_labeler* lb, size_t plane_bytes, size_t npix, size_t nblo
     lb->d_planes = nullptr; lb->d_P = lb->d_Q = lb->d_counts = nullptr; lb->d_n = nullptr; lb->d_table = nullptr;
     lb->d_R = nullptr; lb->d_B = nullptr; lb->d_split = nullptr;
     lb->d_mplanes = nullptr; lb->d_mrec = nullptr; lb->mplanes_cap = lb->mrec_cap = 0;   // (the measurement allocates its own again)
+    lb->d_srec = nullptr; lb->srec_cap = 0;                                              // (and so do the shapes)
     const size_t pb = std::max(plane_bytes, lb->planes_cap), px = std::max(npix, lb->pix_cap), nb = std::max(nblocks, lb->counts_cap);
     const size_t tc = std::max<size_t>(lb->table_cap, 1024);
     const size_t sp = std::max(split_need, lb->split_cap);
@@ -1117,6 +1292,32 @@ int measure_any(umx_labeler* lb, const int* labels, long long N, const void* pla
     return UMX_OK;
 }
 
+// The shapes of `labels` (device, H x W, objects 1..N): the records cleared, one launch, the records down to out; then the stream is
+// idle.  The caller has checked the arguments; out holds N records.
+int shape_any(umx_labeler* lb, const int* labels, long long N, int H, int W, umx_label_shape* out) {
+    L_HIP(lb, hipSetDevice(lb->device));
+    lb->sms[0] = lb->sms[1] = 0.0;
+    if (N == 0) return UMX_OK;
+    int rc = ensure_measure_buffer(lb, &lb->d_srec, &lb->srec_cap, (size_t)N, sizeof(umx_label_shape), "shape records");
+    if (rc) return rc;
+    hipStream_t s = lb->stream;
+    L_HIP(lb, hipEventRecord(lb->ev[1], s));
+    hipLaunchKernelGGL(label_shape_init_kernel, dim3((unsigned)((N + kPixThreads - 1) / kPixThreads)), dim3(kPixThreads), 0, s, lb->d_srec, N);
+    hipLaunchKernelGGL(label_shape_kernel, dim3(row_grid(H)), dim3(64 * kRowWaves), 0, s, labels, H, W, (int)N, lb->d_srec);
+    L_HIP(lb, hipGetLastError());
+    L_HIP(lb, hipEventRecord(lb->ev[2], s));
+    L_HIP(lb, hipMemcpyAsync(out, lb->d_srec, (size_t)N * sizeof(umx_label_shape), hipMemcpyDeviceToHost, s));
+    L_HIP(lb, hipEventRecord(lb->ev[3], s));
+    L_HIP(lb, hipStreamSynchronize(s));
+    for (int k = 0; k < 2; ++k) {
+        float f = 0.f;
+        if (hipEventElapsedTime(&f, lb->ev[k + 1], lb->ev[k + 2]) == hipSuccess) lb->sms[k] = f;
+    }
+    std::string gmsg;
+    if ((rc = arena_check(lb->mem, &gmsg)) != UMX_OK) return lfail(lb, rc, "%s", gmsg.c_str());
+    return UMX_OK;
+}
+
 }  // namespace
 
 }  // namespace umx
@@ -1294,6 +1495,54 @@ int umx_labeler_measure_last_ms(const umx_labeler* lb, double* upload_ms, double
     if (upload_ms) *upload_ms = lb->mms[0];
     if (kernel_ms) *kernel_ms = lb->mms[1];
     if (download_ms) *download_ms = lb->mms[2];
+    return UMX_OK;
+}
+
+int umx_label_shape_check(int H, int W, int64_t n_objects, char* msg, size_t cap) {
+    char buf[200] = "";
+    if (H < 1 || W < 1) snprintf(buf, sizeof buf, "the image is %d x %d: both sides must be at least 1", H, W);
+    else if (H > UMX_SHAPE_MAX_SIDE || W > UMX_SHAPE_MAX_SIDE)
+        snprintf(buf, sizeof buf, "the image is %d x %d: a side may be at most %d, so that the square of a coordinate stays below 2^32", H, W,
+                 UMX_SHAPE_MAX_SIDE);
+    else if ((long long)H * W > INT_MAX)
+        snprintf(buf, sizeof buf, "the image is %d x %d: a flat pixel index is an int32, so H * W may be at most %d", H, W, INT_MAX);
+    else if (n_objects < 0 || n_objects > INT_MAX)
+        snprintf(buf, sizeof buf, "n_objects is %lld: a label is an int32, so 0..%d objects", (long long)n_objects, INT_MAX);
+    if (msg && cap) snprintf(msg, cap, "%s", buf);
+    return buf[0] ? UMX_ERR_INVALID : UMX_OK;
+}
+
+int umx_labeler_shape(umx_labeler* lb, int H, int W, umx_label_shape* out, int64_t cap, int64_t* n) {
+    if (!lb) return lfail(nullptr, UMX_ERR_INVALID, "null labeler");
+    char msg[200];
+    if (umx_label_shape_check(H, W, 0, msg, sizeof msg) != UMX_OK) return lfail(lb, UMX_ERR_INVALID, "%s", msg);
+    if (lb->res_why) return lfail(lb, UMX_ERR_INVALID, "umx_labeler_shape has no labels to take the shapes of: %s", lb->res_why);
+    if (H != lb->res_H || W != lb->res_W)
+        return lfail(lb, UMX_ERR_INVALID, "the call names %d x %d and the labels of the last run are %d x %d", H, W, lb->res_H, lb->res_W);
+    const long long N = lb->res_N;
+    if (n) *n = N;
+    if (!out && cap == 0) return UMX_OK;                  // the count alone, like umx_labeler_objects
+    if (!out || cap < N)
+        return lfail(lb, UMX_ERR_INVALID, "out holds %lld records: %lld objects need as many", out ? (long long)cap : 0ll, N);
+    return shape_any(lb, lb->d_P, N, H, W, out);
+}
+
+int umx_labeler_shape_dev(umx_labeler* lb, const int32_t* labels_dev, int64_t n_objects, int H, int W, umx_label_shape* out_host,
+                          int64_t cap) {
+    if (!lb) return lfail(nullptr, UMX_ERR_INVALID, "null labeler");
+    char msg[200];
+    if (umx_label_shape_check(H, W, n_objects, msg, sizeof msg) != UMX_OK) return lfail(lb, UMX_ERR_INVALID, "%s", msg);
+    if (!labels_dev) return lfail(lb, UMX_ERR_INVALID, "null labels");
+    if (cap < n_objects || (!out_host && n_objects > 0))
+        return lfail(lb, UMX_ERR_INVALID, "out_host holds %lld records: %lld objects need as many", out_host ? (long long)cap : 0ll,
+                     (long long)n_objects);
+    return shape_any(lb, labels_dev, n_objects, H, W, out_host);
+}
+
+int umx_labeler_shape_last_ms(const umx_labeler* lb, double* kernel_ms, double* download_ms) {
+    if (!lb) return lfail(nullptr, UMX_ERR_INVALID, "null labeler");
+    if (kernel_ms) *kernel_ms = lb->sms[0];
+    if (download_ms) *download_ms = lb->sms[1];
     return UMX_OK;
 }
 

@@ -110,6 +110,10 @@ def build_parser(spec: ToolSpec) -> argparse.ArgumentParser:
     p.add_argument("--labelMeasure", dest="labelMeasure", type=int, nargs="*", default=None, metavar="PAGE",
                    help="also write mean, std, min and max of every labelled object in the probability planes and in these pages of "
                         "the input file, 0-based as --channel counts them (no value: every page)")
+    # what shape every labelled object has: <stem>_Shapes_<suffix>.csv
+    p.add_argument("--labelShape", dest="labelShape", action="store_true",
+                   help="also write perimeter, holes, major and minor axis, eccentricity, orientation and extent of every labelled "
+                        "object (the grown or split ones with --labelGrow / --labelSplit)")
     return p
 
 
@@ -119,7 +123,7 @@ def check_label_args(parser: argparse.ArgumentParser, args) -> None:
         for flag, v in (("--labelClass", args.labelClass), ("--labelMinArea", args.labelMinArea), ("--labelGrow", args.labelGrow),
                         ("--labelGrowClasses", args.labelGrowClasses), ("--labelMeasure", args.labelMeasure),
                         ("--labelSplit", args.labelSplit), ("--labelSplitCore", args.labelSplitCore),
-                        ("--labelSplitRegrow", args.labelSplitRegrow)):
+                        ("--labelSplitRegrow", args.labelSplitRegrow), ("--labelShape", args.labelShape or None)):
             if v is not None:
                 parser.error("%s needs --labelMask" % flag)
         return
@@ -191,6 +195,27 @@ def write_intensities_csv(path: str, objects, planes) -> None:
     with open(path, "w") as f:
         f.write(",".join(["label,area"] + [prefix + "_" + n for prefix, _ in planes for n in ("mean", "std", "min", "max")]) + "\n")
         f.writelines(fmt % row for row in zip(*cols))
+
+
+SHAPE_COLUMNS = ("label", "area", "perimeter_edges", "perimeter", "euler", "holes", "major_axis_length", "minor_axis_length",
+                 "eccentricity", "orientation", "extent")
+
+
+def write_shapes_csv(path: str, objects, records) -> None:
+    """SHAPE_COLUMNS -- one line per object, label order.  records: umx.LABEL_SHAPE_DTYPE [N], turned into the columns by
+    umx.shape_descriptors alone; extent = area / the area of the table's bounding box, one float64 division.  The area the window
+    counts give must be the table's.  Unlike the centroids and the intensities, whose six decimals say all there is to say about a
+    mean of integers, these floats are written with repr: the shortest digits that read back to the same float64."""
+    from . import umx as _umx
+    d = _umx.shape_descriptors(records)
+    if not np.array_equal(d["area"], objects["area"]):
+        raise AssertionError("the shapes counted other pixels than the label table")
+    box = (objects["y1"].astype(np.int64) - objects["y0"] + 1) * (objects["x1"].astype(np.int64) - objects["x0"] + 1)
+    extent = d["area"].astype(np.float64) / box.astype(np.float64)
+    cols = [range(1, len(objects) + 1)] + [d[n].tolist() for n in SHAPE_COLUMNS[1:-1]] + [extent.tolist()]
+    with open(path, "w") as f:
+        f.write(",".join(SHAPE_COLUMNS) + "\n")
+        f.writelines("%d,%d,%d,%r,%d,%d,%r,%r,%r,%r,%r\n" % row for row in zip(*cols))
 
 
 def measure_pages(labeler, path: str, pages, shape) -> list:
@@ -474,6 +499,9 @@ def run(tool: str, argv=None, script_dir: str = None) -> int:
                     measured += measure_pages(labeler, image_path, measure_pages_arg, labels.shape)
                     write_intensities_csv(out_dir + "//" + stem + "_Intensities_" + suffix + ".csv", objects, measured)
                     st.mark("measure")
+                if args.labelShape:
+                    write_shapes_csv(out_dir + "//" + stem + "_Shapes_" + suffix + ".csv", objects, labeler.shape())
+                    st.mark("shape")
     finally:
         if args.compat_per_class:
             UNet2D.reuse_pass = reuse_before

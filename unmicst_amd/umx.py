@@ -37,6 +37,7 @@ EXPORTS = [
     "umx_labeler_run_dev", "umx_labeler_objects", "umx_labeler_last_ms",
     "umx_label_measure_check", "umx_labeler_measure", "umx_labeler_measure_dev", "umx_labeler_measure_last_ms",
     "umx_label_split_check", "umx_labeler_run_split", "umx_labeler_run_split_dev",
+    "umx_label_shape_check", "umx_labeler_shape", "umx_labeler_shape_dev", "umx_labeler_shape_last_ms",
 ]
 
 # the label mask's limits and the geometry of its kernels (the UMX_LABEL_* macros of include/umx.h; tests/test_label_cpu.py compares)
@@ -113,6 +114,18 @@ LABEL_MEASURE_DTYPE = np.dtype([("sum", "<u8"), ("sum_sq", "<u8"), ("min", "<u4"
 MEASURE_U8, MEASURE_U16 = 1, 2                                 # UMX_MEASURE_*
 LABEL_MEASURE_GROUP, LABEL_MAX_MEASURE_PLANES = 4, 1024
 _MEASURE_DTYPES = {np.dtype(np.uint8): MEASURE_U8, np.dtype(np.uint16): MEASURE_U16}
+
+
+class LabelShape(ctypes.Structure):
+    """umx_label_shape: 64 bytes"""
+    _fields_ = [(n, ctypes.c_int64) for n in ("sum_y", "sum_x", "sum_yy", "sum_xy", "sum_xx")] + \
+               [(n, ctypes.c_uint32) for n in ("q1", "q2", "qd", "q3", "q4", "reserved")]
+
+
+# the same record as a numpy dtype: what Labeler.shape returns, [N]; the descriptors are shape_descriptors'
+LABEL_SHAPE_DTYPE = np.dtype([(n, "<i8") for n in ("sum_y", "sum_x", "sum_yy", "sum_xy", "sum_xx")] +
+                             [(n, "<u4") for n in ("q1", "q2", "qd", "q3", "q4", "reserved")])
+SHAPE_MAX_SIDE = 65536                                         # UMX_SHAPE_MAX_SIDE
 
 
 _SEND_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p)
@@ -307,6 +320,14 @@ def load(path: Optional[str] = None):
     L.umx_labeler_measure_dev.argtypes = [c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, ctypes.c_int64]
     L.umx_labeler_measure_last_ms.restype = c_int
     L.umx_labeler_measure_last_ms.argtypes = [c_void_p] + [ctypes.POINTER(c_double)] * 3
+    L.umx_label_shape_check.restype = c_int
+    L.umx_label_shape_check.argtypes = [c_int, c_int, ctypes.c_int64, ctypes.c_char_p, ctypes.c_size_t]
+    L.umx_labeler_shape.restype = c_int
+    L.umx_labeler_shape.argtypes = [c_void_p, c_int, c_int, c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+    L.umx_labeler_shape_dev.restype = c_int
+    L.umx_labeler_shape_dev.argtypes = [c_void_p, c_void_p, ctypes.c_int64, c_int, c_int, c_void_p, ctypes.c_int64]
+    L.umx_labeler_shape_last_ms.restype = c_int
+    L.umx_labeler_shape_last_ms.argtypes = [c_void_p] + [ctypes.POINTER(c_double)] * 2
     L.umx_prof_entry_size.restype = c_int
     if L.umx_prof_entry_size() != ctypes.sizeof(ProfEntry):
         raise RuntimeError("libumx (%s) lays umx_prof_entry out in %d bytes, this binding in %d: mixed builds" % (
@@ -682,6 +703,53 @@ def measure_mean_std(records: np.ndarray):
     return mean, std
 
 
+def label_shape_check(H: int, W: int, n_objects: int = 0) -> str:
+    """umx_label_shape_check: "" if the shapes of n_objects labels on H x W are accepted, else the reason.  Host only."""
+    buf = ctypes.create_string_buffer(256)
+    rc = load().umx_label_shape_check(int(H), int(W), int(n_objects), buf, len(buf))
+    return "" if rc == 0 else buf.value.decode()
+
+
+SHAPE_DESCRIPTORS = ("area", "perimeter_edges", "perimeter", "euler", "holes", "mu_yy", "mu_xx", "mu_yx", "major_axis_length",
+                     "minor_axis_length", "eccentricity", "orientation")
+
+
+def shape_descriptors(records: np.ndarray) -> dict:
+    """Step 18 of DESIGN.md section 8.1, stated here once: LABEL_SHAPE_DTYPE records [N] -> {name: array [N]} for SHAPE_DESCRIPTORS.
+    int64: area = (q1 + 2 q2 + 2 qd + 3 q3 + 4 q4) / 4, perimeter_edges = q1 + q2 + 2 qd + q3, euler = (q1 - q3 + 2 qd) / 4 (both
+    divisions are exact), holes = 1 - euler.  float64, with A = area: the numerators A sum_yy - sum_y^2, A sum_xx - sum_x^2 and
+    A sum_xy - sum_y sum_x are formed exactly (Python integers: they pass 2^64) and each divided once by A * A -- one correctly
+    rounded division -- to mu_yy, mu_xx, mu_yx; then l1, l2 = (mu_yy + mu_xx) / 2 +- sqrt(((mu_yy - mu_xx) / 2)^2 + mu_yx^2),
+    major = 4 sqrt(l1), minor = 4 sqrt(max(l2, 0)), eccentricity = sqrt(1 - l2 / l1) (0 when l1 == 0), orientation =
+    0.5 atan2(2 mu_yx, mu_yy - mu_xx): the angle of the major axis from the row axis, 0 for an isotropic object; perimeter =
+    q2 + (q1 + q3 + 2 qd) / sqrt(2), the bit-quad estimate.  A record of area 0 (a label no pixel carries) has nan in the moment
+    columns.  These are the project's reading of the usual regionprops conventions; nothing is pinned to scikit-image."""
+    rec = np.asarray(records)
+    q1, q2, qd, q3, q4 = (rec[n].astype(np.int64) for n in ("q1", "q2", "qd", "q3", "q4"))
+    four = q1 + 2 * q2 + 2 * qd + 3 * q3 + 4 * q4
+    e4 = q1 - q3 + 2 * qd
+    if (four % 4).any() or (e4 % 4).any():
+        raise ValueError("window counts that are no object's: 4 * area or 4 * euler is not a multiple of 4")
+    area, euler = four // 4, e4 // 4
+    out = {"area": area, "perimeter_edges": q1 + q2 + 2 * qd + q3, "euler": euler, "holes": 1 - euler,
+           "perimeter": q2.astype(np.float64) + (q1 + q3 + 2 * qd).astype(np.float64) / np.sqrt(2.0)}
+    mu = np.full((3, len(rec)), np.nan)
+    for j in np.flatnonzero(area > 0):
+        A, sy, sx = int(area[j]), int(rec["sum_y"][j]), int(rec["sum_x"][j])
+        mu[0, j] = (A * int(rec["sum_yy"][j]) - sy * sy) / (A * A)
+        mu[1, j] = (A * int(rec["sum_xx"][j]) - sx * sx) / (A * A)
+        mu[2, j] = (A * int(rec["sum_xy"][j]) - sy * sx) / (A * A)
+    myy, mxx, myx = mu
+    half, root = (myy + mxx) / 2.0, np.sqrt(((myy - mxx) / 2.0) ** 2 + myx * myx)
+    l1, l2 = half + root, half - root
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ecc = np.where(l1 == 0.0, 0.0, np.sqrt(1.0 - l2 / l1))
+    out.update({"mu_yy": myy, "mu_xx": mxx, "mu_yx": myx, "major_axis_length": 4.0 * np.sqrt(l1),
+                "minor_axis_length": 4.0 * np.sqrt(np.maximum(l2, 0.0)), "eccentricity": ecc,
+                "orientation": 0.5 * np.arctan2(2.0 * myx, myy - mxx)})
+    return out
+
+
 class Labeler:
     """One umx_labeler: the label mask (include/umx.h) of uint8 probability stacks on one MI355X.  It needs no
     model; its device buffers grow on demand and are kept between runs."""
@@ -694,6 +762,7 @@ class Labeler:
             raise UmxError(rc, self._L.umx_labeler_last_error(None).decode())
         self.device = device
         self._split_counts = None
+        self._last_shape = (1, 1)                                  # H, W of the last run: what shape() names when not told
 
     def close(self) -> None:
         if getattr(self, "_lb", None) and self._lb.value:
@@ -768,6 +837,8 @@ class Labeler:
         o = _label_options(K, cls, min_area, grow, grow_classes)
         labels = np.empty((H, W), np.int32) if want_labels else None
         n = self._run_any(planes.ctypes.data, False, K, H, W, o, labels.ctypes.data if want_labels else None, split, split_core, split_regrow)
+        if want_labels:
+            self._last_shape = (H, W)                              # (of the resident labels: a refused run above has left them)
         objs = self.objects()
         assert len(objs) == n
         return labels, objs
@@ -814,6 +885,34 @@ class Labeler:
         """(upload, kernel, download) milliseconds of the last measurement, summed over its groups of planes."""
         v = [ctypes.c_double() for _ in range(3)]
         self._check(self._L.umx_labeler_measure_last_ms(self._lb, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def shape(self, H: Optional[int] = None, W: Optional[int] = None) -> np.ndarray:
+        """umx_labeler_shape: the shapes of the labels the last run(want_labels=True) left on the device -- plain, grown or split --
+        -> LABEL_SHAPE_DTYPE [N], record j - 1 of label j; shape_descriptors turns them into axes, perimeter and holes.  H, W: the
+        size the caller believes the labels have (refused when it is not theirs); None: that of the last run of this Labeler."""
+        H, W = (self._last_shape[0] if H is None else H), (self._last_shape[1] if W is None else W)
+        n = ctypes.c_int64()
+        self._check(self._L.umx_labeler_shape(self._lb, int(H), int(W), None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, LABEL_SHAPE_DTYPE)
+        self._check(self._L.umx_labeler_shape(self._lb, int(H), int(W), out.ctypes.data, out.size, ctypes.byref(n)))
+        return out
+
+    def shape_ptr(self, labels_ptr: int, n_objects: int, H: int, W: int) -> np.ndarray:
+        """umx_labeler_shape_dev on a DEVICE address (e.g. torch.Tensor.data_ptr()): int32 [H, W] labels with objects 1..n_objects,
+        complete -> LABEL_SHAPE_DTYPE [n_objects].  Needs no prior run."""
+        why = label_shape_check(H, W, n_objects)                   # (before any buffer is sized from the arguments)
+        if why:
+            raise UmxError(ERR_INVALID, why)
+        out = np.zeros(int(n_objects), LABEL_SHAPE_DTYPE)
+        self._check(self._L.umx_labeler_shape_dev(self._lb, ctypes.c_void_p(labels_ptr), int(n_objects), int(H), int(W), out.ctypes.data,
+                                                  out.size))
+        return out
+
+    def shape_last_ms(self):
+        """(kernel, download) milliseconds of the last shape call."""
+        v = [ctypes.c_double() for _ in range(2)]
+        self._check(self._L.umx_labeler_shape_last_ms(self._lb, *[ctypes.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
 
