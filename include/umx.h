@@ -282,7 +282,7 @@ UMX_API int umx_infer_image_sharded_raw(umx_ctx* ctx, const void* band_host, int
  * 4-connected; a pixel goes to a seed nearest through the domain, a tie to the smaller label; the table is that of the grown labels.
  * Every value is an integer, so nothing depends on the order in which atomics arrive: two calls give the same bytes.
  * A labeler needs no model: it owns a stream and its device buffers (two int32 planes of H * W, the K input planes, one int32 per
- * UMX_LABEL_SCAN_BLOCK pixels and the table; from its first split run on one more int32 plane and one byte plane), grown on demand and
+ * UMX_LABEL_SCAN_BLOCK pixels and the table; from its first split or flood run on one more int32 plane and one byte plane), grown on demand and
  * kept between runs.  UMX_DEBUG_GUARD (include/umx_train.h) puts red
  * zones round them; a run then ends with their check (UMX_ERR_GUARD).  One labeler per host thread.
  */
@@ -442,8 +442,8 @@ UMX_API int umx_labeler_shape_last_ms(const umx_labeler* lb, double* kernel_ms, 
  *   15. if grow_radius > 0 the growth above over grow_classes from the labels of step 14; then the table of the final labels.
  * The result is a function of the planes and the options only; every final object contains its seed and is 4-connected; an object
  * with one core or none keeps exactly its pixels when L is large enough; a bar of width w joining two bodies is cut iff w <= 2 D.
- * Not here: h-maxima, an intensity-weighted watershed, merging fragments back (a ragged outline can throw small cores; C is the only
- * guard).  A split run allocates, beyond a plain run's buffers, one more int32 plane and one byte plane of H * W, kept like the others.
+ * Not here: h-maxima, merging fragments back (a ragged outline can throw small cores; C is the only guard).  The regrow of step 14
+ * cuts a neck on the midline between its cores; umx_labeler_run_flood below cuts it along a ridge of one of the planes instead.  A split run allocates, beyond a plain run's buffers, one more int32 plane and one byte plane of H * W, kept like the others.
  */
 typedef struct umx_label_split_options {
     umx_label_options base;  /* the labelling (and the rim growth of step 15) as in umx_labeler_run */
@@ -470,6 +470,55 @@ UMX_API int umx_labeler_run_split(umx_labeler* lb, const uint8_t* planes_host, i
                                   int32_t* labels_host, umx_label_split_counts* counts);
 UMX_API int umx_labeler_run_split_dev(umx_labeler* lb, const uint8_t* planes_dev, int K, int H, int W, const umx_label_split_options* o,
                                       int32_t* labels_dev, umx_label_split_counts* counts);
+
+/*
+ * The level flood: the split's cut laid along a ridge of the planes (the definition is the
+ * project's own).  A marker-controlled watershed by immersion, integer throughout.  On top of a split run -- whose steps 10 to 13
+ * run unchanged and give the seed objects 1..N -- with a relief plane P, an invert flag and a level step q:
+ *   19. relief and levels: r(p) = planes[P][p], or 255 - planes[P][p] with invert.  The levels are t_j = min(255, (j + 1) * q - 1)
+ *       for j = 0 .. 256 / q - 1, in ascending order.
+ *   20. flood, in place of step 14: at level t the domain is every pixel with label 0, pred == cls and r(p) <= t; synchronous
+ *       steps of the growth rule (a labelled 4-neighbour of the step before, the smallest such label, every pixel deciding on the
+ *       state of the step before) are repeated until one claims nothing; the next level starts from that state.  The steps have no
+ *       bound: the split record's regrow must be UMX_SPLIT_MAX_REGROW in a flood call.
+ *   21. rim growth, table and labels as step 15.
+ * Consequences: with q = 256 there is one level, t = 255, and the result is that of umx_labeler_run_split with regrow 255 bit for
+ * bit wherever that run leaves nothing unreached; N, the numbering and the seeds are the split's, every object contains its seed
+ * and is 4-connected; an object with one core or none keeps exactly its pixels; two bodies joined by a neck whose relief has a
+ * one-pixel-wide ridge of value v, everything else in the neck below v, are cut on the ridge wherever it stands (q small enough
+ * that the ridge is alone at its level); the result is a function of the planes and the options only.  unreached is 0 for every
+ * input (every kept object contains a seed and every pixel is admitted at t = 255); it is returned all the same.
+ * The relief is read from the planes: a flood run allocates two words beyond a split run's buffers.
+ */
+typedef struct umx_label_flood_options {
+    umx_label_split_options split;   /* the split run; split.regrow must be UMX_SPLIT_MAX_REGROW */
+    int32_t relief_plane;            /* P: 0 .. K-1, in the model's class order */
+    int32_t invert;                  /* 0: r = planes[P]; 1: r = 255 - planes[P] */
+    int32_t level_step;              /* q: a power of two, 1 .. UMX_FLOOD_MAX_STEP */
+    int32_t reserved[5];             /* must be zero */
+} umx_label_flood_options;           /* 96 bytes */
+typedef struct umx_label_flood_counts {
+    int64_t n_objects, n_before, n_cored, unreached;   /* as umx_label_split_counts, in its order */
+    int64_t levels_claimed;          /* levels at which at least one pixel was claimed */
+    int64_t claimed;                 /* pixels claimed in all */
+    int64_t launches;                /* flood launches: informative, not part of the definition */
+    int64_t reserved;
+} umx_label_flood_counts;            /* 64 bytes */
+/* The largest level step (one level), the step of the drivers when none is given, and the steps one flood launch runs at most
+ * (the halo of the growth kernel, whose geometry the flood kernel has). */
+enum { UMX_FLOOD_MAX_STEP = 256, UMX_FLOOD_DEFAULT_STEP = 16, UMX_FLOOD_LAUNCH_STEPS = 8 };
+/* Host only, no device: umx_label_split_check on the split record first, its message passed through unchanged; then
+ * split.regrow == 255, 0 <= relief_plane < K, invert 0 or 1, level_step one of 1, 2, 4 .. 256, reserved words zero.  UMX_OK, or
+ * UMX_ERR_INVALID with the reason in msg. */
+UMX_API int umx_label_flood_check(const umx_label_flood_options* o, int K, int H, int W, char* msg, size_t cap);
+/* umx_labeler_run_split / _run_split_dev with the flood in place of the regrow: the same contracts.  A refused call
+ * (UMX_ERR_INVALID) has touched nothing and leaves the resident labels as they were; a successful host call with a label plane
+ * makes the flooded labels the resident ones for umx_labeler_measure and umx_labeler_shape.  Synchronous; under UMX_DEBUG_GUARD the
+ * call ends in the check of the red zones.  counts may be NULL. */
+UMX_API int umx_labeler_run_flood(umx_labeler* lb, const uint8_t* planes_host, int K, int H, int W, const umx_label_flood_options* o,
+                                  int32_t* labels_host, umx_label_flood_counts* counts);
+UMX_API int umx_labeler_run_flood_dev(umx_labeler* lb, const uint8_t* planes_dev, int K, int H, int W, const umx_label_flood_options* o,
+                                      int32_t* labels_dev, umx_label_flood_counts* counts);
 
 /* Strip / tile decoders of the drivers' own TIFF reader (unmicst_amd/tiffio.py; the reference reads through tifffile /
  * imagecodecs, UnMicst1-5.py:794-797): TIFF 6.0 LZW (compression 5, the OME-TIFF / Bio-Formats default) and PackBits

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time the label mask (umx_labeler_run) on synthetic H x W stacks of K = 3 uint8 planes (GPU box); one JSON
 line.  usage: bench_label.py [H=16384] [W=H] [--reps 3] [--grow R] [--measure C [--measure-dtype u8|u16]] [--split D [--split-core C]]
-       [--shape [--no-host]]
+       [--flood P [--flood-step Q]] [--shape [--no-host]]
 
 Two inputs, both made here by pure-numpy recipes (no scipy in the generators, nothing from tests/):
   blobs  nuclei-like discs: the image is cut into 32 x 32 cells; a seeded draw keeps 60 % of them, and each kept cell gets one disc of
@@ -24,6 +24,10 @@ sums of the same planes over the same labels on this box's CPU share (one weight
 kept cell gets two squares of 24 x 24 joined by a bridge of 2 D rows -- the widest neck that depth D cuts, so every pair must come back
 as two objects.  The same planes are labelled without and with the split; "split_ms" is the
 difference of the two kernel times, and the four counts of the split are reported.
+--flood P (with --split D): the same bridged pairs, with plane P given a ridge of RIDGE in the third column of every bridge -- off the
+bridge's middle, where the split's regrow cuts -- over the plane's 30 elsewhere.  The planes are labelled with the split alone (the
+yardstick) and with the flood on plane P in levels of --flood-step; "flood_ms" is the difference
+of the two kernel times, and the flood's counts -- its launches among them -- are reported.
 --shape: the blobs input alone, labelled with its label plane kept on the device, then the shapes of its objects (umx_labeler_shape,
 DESIGN.md section 8.1 steps 16 to 18): the kernel and download milliseconds umx_labeler_shape_last_ms reports (the best of --reps by
 kernel time, after one warm-up), beside them the one-plane uint16 measurement of the same labels (the yardstick: it reads the same
@@ -80,6 +84,36 @@ def bridged_mask(H, W, D, seed=4):
     cell[PAIR_H // 2 - D:PAIR_H // 2 + D, 4 + SQUARE:PAIR_W - 4 - SQUARE] = True
     mask = (keep[:, None, :, None] & cell[None, :, None, :]).reshape(ny * PAIR_H, nx * PAIR_W)
     return mask[:H, :W]
+
+
+RIDGE, RIDGE_COLUMN = 180, 4 + SQUARE + 2                    # below the nuclei plane's 200; the third column of the bridge
+
+
+def ridged_planes(H, W, D, P):
+    """planes_of the bridged pairs with plane P raised to RIDGE on column RIDGE_COLUMN of every bridge"""
+    mask = bridged_mask(H, W, D)
+    planes = planes_of(mask)
+    x = np.arange(W) % PAIR_W == RIDGE_COLUMN
+    y = np.abs(np.arange(H) % PAIR_H - PAIR_H // 2 + 0.5) < D    # the bridge's 2 D rows
+    planes[P][mask & y[:, None] & x[None, :]] = RIDGE
+    return planes
+
+
+def flood_bench(a, H, W):
+    planes = ridged_planes(H, W, a.split, a.flood)
+    with umx.Labeler(a.device) as lb:
+        cut, with_split = best_kernel_ms(lb, planes, a.reps, split=a.split, split_core=a.split_core)
+        flooded, with_flood = best_kernel_ms(lb, planes, a.reps, split=a.split, split_core=a.split_core, flood=a.flood, flood_step=a.flood_step)
+        counts = lb.flood_counts()
+    assert len(cut) == len(flooded) == counts["n_objects"] and int(cut["area"].sum()) == int(flooded["area"].sum()) and counts["unreached"] == 0
+    assert not np.array_equal(cut["area"], flooded["area"])      # the cut has moved
+    return dict({"split": a.split, "split_core": a.split_core, "flood": a.flood, "flood_step": a.flood_step,
+                 "object_pixels": int(cut["area"].sum()), "kernel_ms_with_split": round(with_split[1], 3),
+                 "kernel_ms_with_flood": round(with_flood[1], 3), "flood_ms": round(with_flood[1] - with_split[1], 3),
+                 # what one flood launch moves at most, as a growth launch: the label word and, where it is 0, the K class bytes of
+                 # every pixel of a tile and its halo (the relief byte is one of them); one label word written per pixel
+                 "bytes_per_launch_upper": int(((1 + 2 * umx.LABEL_GROW_HALO / umx.LABEL_GROW_TILE) ** 2 * (4 + planes.shape[0]) + 4) * H * W)},
+                **counts)
 
 
 def split_bench(a, H, W):
@@ -262,6 +296,8 @@ def main():
     ap.add_argument("--measure", type=int, default=0, metavar="C")
     ap.add_argument("--split", type=int, default=0, metavar="D")
     ap.add_argument("--split-core", dest="split_core", type=int, default=1, metavar="C")
+    ap.add_argument("--flood", type=int, default=None, metavar="P", help="with --split: the relief plane of the level flood")
+    ap.add_argument("--flood-step", dest="flood_step", type=int, default=umx.FLOOD_DEFAULT_STEP, metavar="Q")
     ap.add_argument("--measure-dtype", dest="measure_dtype", choices=("u8", "u16"), default="u16")
     ap.add_argument("--shape", action="store_true")
     ap.add_argument("--no-host", dest="no_host", action="store_true", help="with --shape: leave the numpy / scipy figure out (a traced run)")
@@ -270,6 +306,11 @@ def main():
     out = {"tool": "bench_label", "H": H, "W": W, "K": 3, "min_area": 1, "reps": a.reps}
     if a.grow:
         print(json.dumps(dict(out, **grow_bench(a, H, W))))
+        return
+    if a.flood is not None:
+        if not a.split:
+            ap.error("--flood needs --split")
+        print(json.dumps(dict(out, **flood_bench(a, H, W))))
         return
     if a.split:
         print(json.dumps(dict(out, **split_bench(a, H, W))))

@@ -9,6 +9,8 @@ planes, the labelling call, the int32 page and the table).
        cli_walltime.py N --label --grow R   -- and twice with --labelMask --labelGrow R as well.
        cli_walltime.py N --label --split D  -- and twice with --labelMask --labelSplit D as well (the stage line then carries the
 split's four counts as "label_split").
+       cli_walltime.py N --label --split D --flood P  -- and twice with --labelFlood P beside the split as well (the stage line then
+carries the flood's counts as "label_flood").
        cli_walltime.py N --label --measure  -- and twice with --labelMask --labelMeasure as well (the `measure` stage: the three
 probability planes and the slide's one page against the labels left on the device, and the Intensities file)."""
 import json
@@ -53,6 +55,10 @@ def main():
     if "--split" in rest:
         split = str(int(rest[rest.index("--split") + 1]))
         del rest[rest.index("--split"):rest.index("--split") + 2]
+    flood = None
+    if "--flood" in rest:
+        flood = str(int(rest[rest.index("--flood") + 1]))
+        del rest[rest.index("--flood"):rest.index("--flood") + 2]
     measure = "--measure" in rest
     others = [a for a in rest if a not in ("--label", "--measure")]
     hp, blob, mean, std = helpers.load_nuclei_dapi()
@@ -76,6 +82,10 @@ def main():
                 if split:
                     one(ROOT, path, os.path.join(d, "out_split%d" % rep), env, "this tree, --labelMask --labelSplit %s, run %d" % (split, rep + 1), n,
                         extra=["--labelMask", "--labelSplit", split])
+                if split and flood:
+                    one(ROOT, path, os.path.join(d, "out_flood%d" % rep), env,
+                        "this tree, --labelMask --labelSplit %s --labelFlood %s, run %d" % (split, flood, rep + 1), n,
+                        extra=["--labelMask", "--labelSplit", split, "--labelFlood", flood])
                 if measure:
                     one(ROOT, path, os.path.join(d, "out_measure%d" % rep), env, "this tree, --labelMask --labelMeasure, run %d" % (rep + 1), n,
                         extra=["--labelMask", "--labelMeasure"])

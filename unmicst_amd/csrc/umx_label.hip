@@ -31,6 +31,10 @@
 //   label_runs_mask_kernel, label_core_mark_kernel, label_split_ids_kernel   the eroded set's row runs into R; which objects hold a
 //                         core; the seed components' ids in place over P, which the count / scan / number kernels then number
 //   label_grow_kernel<true>   the growth kernel over the label class itself, counting the pixels it claims so that the host can stop
+// A flood run (umx_labeler_run_flood / _run_flood_dev) is a split run with, in the regrow's place,
+//   label_flood_kernel    the growth's tile and halo at one level t of a relief taken from the planes: up to 8 steps over the empty
+//                         pixels of class cls with relief <= t; it counts its claims and reports the least relief that waits beside
+//                         a label, from which the host picks the next level (run_flood_launches)
 // A measurement (umx_labeler_measure / _measure_dev) is, per group of up to 4 image planes,
 //   label_measure_init_kernel, label_measure_kernel   one wave per row: the labels (the P plane a run left, or the caller's) read once
 //                         for the group's planes; every row run adds its count, its sums of v and v * v and its extremes of every plane
@@ -606,6 +610,129 @@ __global__ void __launch_bounds__(kPixThreads) label_split_ids_kernel(int* __res
     if (threadIdx.x == 0 && (s_pending | s_cored)) atomicAdd(packed, ((unsigned long long)s_pending << 32) | s_cored);
 }
 
+// ---- the level flood ----
+constexpr int kFloodWords = 2, kFloodClaimed = 0, kFloodLeast = 1;   // the words of umx_labeler::d_flood
+constexpr int kFloodNone = 0x7f7f7f7f;                               // the least-relief word before a launch: above every relief
+static_assert(UMX_FLOOD_LAUNCH_STEPS == kGrowHalo && UMX_FLOOD_MAX_STEP == 256, "a flood launch runs a halo's worth of steps; reliefs are bytes");
+static_assert(sizeof(umx_label_flood_options) == 96 && sizeof(umx_label_flood_counts) == 64, "the flood's records");
+
+// Up to `steps` (1 .. kGrowHalo) synchronous steps of the flood at ONE level t, src -> dst (two different planes): the geometry of
+// label_grow_kernel -- grid tiles_y * tiles_x, one workgroup per tile of 64 x 64 pixels, the tile and a halo of 8 in LDS as one int
+// per pixel:
+//     > 0            the label
+//     -1             an empty pixel of the level's domain: label 0, first maximum of the planes == cls, relief r <= t
+//     -2 - r         an empty pixel of class cls that the level does not admit yet, with its relief r in t + 1 .. 255
+//     0              any other pixel, and every pixel outside the image
+// (the relief r = planes[relief_plane], or 255 - that with invert, is read for the empty pixels of class cls only: the LDS holds what
+// the launch needs of it inside the state word).  A step is the growth's: every -1 pixel takes the least label among its four
+// neighbours of the step before; the steps end, for the whole workgroup, when one changed nothing.  The admission is fixed for the
+// launch and a pixel's new value depends on its own and its four neighbours' old ones only, so the halo argument is the growth's
+// word for word: after s <= 8 steps from an exact global state the wrong pixels lie in the s outer rings, and the tile is exact.
+// What a launch reports besides its tile, both by integer atomics that nothing reads before the launch ends:
+//   *claimed += the pixels of its own tile that it labelled (one 64-bit add per workgroup that claimed any);
+//   *least = min(*least, r) over the pixels of its own tile that are -2 - r and have a labelled 4-neighbour in the LDS state at the
+//            end of the launch (one 32-bit atomicMin per workgroup that has one).  A tile pixel has all four neighbours in the
+//            region.  The LDS state of the halo may be stale while the launch still claims; the host uses the word only of a launch
+//            that claimed nothing, in which every LDS state is the global one (run_flood_launches).
+// Bounds: as label_grow_kernel -- region pixel r < 6400, image row and column in 64 bits, src / planes / dst touched at
+// 0 <= gy < H, 0 <= gx < W only; relief_plane < K (umx_label_flood_check), so its word is below K * H * W.  A workgroup reads src
+// and planes, which nobody writes in this launch, and writes the words of dst of its own tile only.
+__global__ void __launch_bounds__(kGrowThreads) label_flood_kernel(const uint8_t* __restrict__ planes, int K, int H, int W, int cls,
+                                                                   int relief_plane, int invert, int t, const int* __restrict__ src,
+                                                                   int* __restrict__ dst, int steps, int tiles_x,
+                                                                   long long* __restrict__ claimed, int* __restrict__ least) {
+    __shared__ int L[kGrowPix];
+    __shared__ int tile_claims, tile_least;
+    int mine = 0;                                             // claims of this thread inside the tile
+    const int tid = threadIdx.x;
+    const long long ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
+    const long long y0 = ty * kGrowTile - kGrowHalo, x0 = tx * kGrowTile - kGrowHalo;
+    const size_t npix = (size_t)H * W;
+    if (tid == 0) { tile_claims = 0; tile_least = kFloodNone; }
+    int open = 0, seen = 0, later = 0;
+#pragma unroll 5
+    for (int j = 0; j < kGrowPer; ++j) {
+        const int r = j * kGrowThreads + tid;
+        const long long gy = y0 + r / kGrowSide, gx = x0 + r % kGrowSide;
+        int v = 0;
+        if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+            const size_t i = (size_t)gy * W + (size_t)gx;
+            v = src[i];
+            if (v == 0) {                                     // (a labelled pixel's class and relief are never asked for)
+                int arg = 0, best = planes[i];
+                for (int k = 1; k < K; ++k) {
+                    const int p = planes[(size_t)k * npix + i];
+                    if (p > best) { best = p; arg = k; }      // first maximum, as label_runs_kernel
+                }
+                if (arg == cls) {
+                    const int b = planes[(size_t)relief_plane * npix + i];
+                    const int relief = invert ? 255 - b : b;
+                    v = relief <= t ? -1 : -2 - relief;
+                }
+            }
+        }
+        L[r] = v;
+        open |= v == -1;
+        seen |= v > 0;
+        later |= v < -1;
+    }
+    const int any_open = __syncthreads_or(open);              // (the barriers that make L and the two tile words whole, too)
+    const int any_seen = __syncthreads_or(seen);
+    const int any_later = __syncthreads_or(later);
+    if (any_open && any_seen) {
+        for (int s = 0; s < steps; ++s) {
+            int nv[kGrowPer];
+            int changed = 0;
+#pragma unroll
+            for (int j = 0; j < kGrowPer; ++j) {
+                const int r = j * kGrowThreads + tid;
+                int m = 0;
+                if (L[r] == -1) {
+                    const int ry = r / kGrowSide, rx = r % kGrowSide;
+                    const int up = ry > 0 ? L[r - kGrowSide] : 0, down = ry < kGrowSide - 1 ? L[r + kGrowSide] : 0;
+                    const int left = rx > 0 ? L[r - 1] : 0, right = rx < kGrowSide - 1 ? L[r + 1] : 0;
+                    m = INT_MAX;
+                    if (up > 0) m = up;
+                    if (down > 0 && down < m) m = down;
+                    if (left > 0 && left < m) m = left;
+                    if (right > 0 && right < m) m = right;
+                    if (m == INT_MAX) m = 0;
+                    if (m > 0 && ry >= kGrowHalo && ry < kGrowHalo + kGrowTile && rx >= kGrowHalo && rx < kGrowHalo + kGrowTile) ++mine;
+                }
+                nv[j] = m;                                    // > 0: the pixel is claimed at this step
+                changed |= m;
+            }
+            if (!__syncthreads_or(changed)) break;            // the same answer in every thread
+#pragma unroll
+            for (int j = 0; j < kGrowPer; ++j)
+                if (nv[j] > 0) L[j * kGrowThreads + tid] = nv[j];
+            __syncthreads();
+        }
+    }
+    int low = kFloodNone;                                     // the least relief of this thread's waiting tile pixels beside a label
+#pragma unroll 4
+    for (int j = 0; j < kGrowTile * kGrowTile / kGrowThreads; ++j) {
+        const int q = j * kGrowThreads + tid;
+        const int iy = q / kGrowTile, ix = q % kGrowTile;
+        const long long gy = ty * kGrowTile + iy, gx = tx * kGrowTile + ix;
+        if (gy < H && gx < W) {
+            const int r = (iy + kGrowHalo) * kGrowSide + ix + kGrowHalo;   // (kGrowHalo >= 1: the four neighbours are region pixels)
+            const int v = L[r];
+            dst[(size_t)gy * W + (size_t)gx] = v > 0 ? v : 0;
+            if (any_seen && any_later && v < -1 && -2 - v < low &&
+                (L[r - kGrowSide] > 0 || L[r + kGrowSide] > 0 || L[r - 1] > 0 || L[r + 1] > 0))
+                low = -2 - v;
+        }
+    }
+    if (mine) atomicAdd(&tile_claims, mine);                  // (LDS)
+    if (low != kFloodNone) atomicMin(&tile_least, low);
+    __syncthreads();
+    if (tid == 0) {
+        if (tile_claims) atomicAdd(reinterpret_cast<unsigned long long*>(claimed), (unsigned long long)tile_claims);
+        if (tile_least != kFloodNone) atomicMin(least, tile_least);
+    }
+}
+
 // ---- the measurement ----
 // What one row run carries of G planes: its pixel count and, per plane, the sum, the sum of squares, the least and the largest value.
 template <int G>
@@ -940,6 +1067,7 @@ struct umx_labeler {
     int* d_R = nullptr;
     uint8_t* d_B = nullptr;       size_t split_cap = 0;        // words of d_R = bytes of d_B (rounded up to a whole word); 0: never asked for
     long long* d_split = nullptr;                              // kSplitWords words the kernels of a split run add to
+    long long* d_flood = nullptr;                              // kFloodWords words a flood launch reports in (allocated with d_split)
     std::vector<umx_label_object> table;                       // of the last run
     double ms[3] = {0.0, 0.0, 0.0};
     // the resident labels: d_P holds the int32 [res_H][res_W] label plane of res_N objects iff res_why is null; else why it does not
@@ -988,7 +1116,7 @@ int ensure_buffers(umx_labeler* lb, size_t plane_bytes, size_t npix, size_t nblo
     L_HIP(lb, hipStreamSynchronize(lb->stream));
     arena_free(&lb->mem);
     lb->d_planes = nullptr; lb->d_P = lb->d_Q = lb->d_counts = nullptr; lb->d_n = nullptr; lb->d_table = nullptr;
-    lb->d_R = nullptr; lb->d_B = nullptr; lb->d_split = nullptr;
+    lb->d_R = nullptr; lb->d_B = nullptr; lb->d_split = nullptr; lb->d_flood = nullptr;
     lb->d_mplanes = nullptr; lb->d_mrec = nullptr; lb->mplanes_cap = lb->mrec_cap = 0;   // (the measurement allocates its own again)
     lb->d_srec = nullptr; lb->srec_cap = 0;                                              // (and so do the shapes)
     const size_t pb = std::max(plane_bytes, lb->planes_cap), px = std::max(npix, lb->pix_cap), nb = std::max(nblocks, lb->counts_cap);
@@ -1005,6 +1133,7 @@ int ensure_buffers(umx_labeler* lb, size_t plane_bytes, size_t npix, size_t nblo
         L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_R, sp * sizeof(int), false, "label core parents"));
         L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_B, (sp + 3) / 4 * 4, false, "label split flags"));
         L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_split, kSplitWords * sizeof(long long), true, "label split counts"));
+        L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_flood, kFloodWords * sizeof(long long), true, "label flood words"));
     }
     lb->planes_cap = pb; lb->pix_cap = px; lb->counts_cap = nb; lb->table_cap = tc; lb->split_cap = sp;
     return UMX_OK;
@@ -1105,6 +1234,57 @@ int run_launches(umx_labeler* lb, const uint8_t* planes, int K, int H, int W, co
     return UMX_OK;
 }
 
+// The flood from the seed labels in *src, with *dst as the other plane; on return *src holds the
+// flooded labels.  `pending`: the pixels of kept objects that are no seed pixels -- what there is to claim.
+//   At a level t the host launches label_flood_kernel (8 steps each, src -> dst -> src ...) until a launch claims nothing: the state
+//   is closed under the steps of that level.  After every launch one 16-byte read-back: the pixels claimed so far and the launch's
+//   least waiting relief.
+//   In a launch that claimed nothing every workgroup's LDS state is the global state (its first step changed nothing anywhere: a
+//   halo pixel that one workgroup could claim is a tile pixel that its owner would claim and count), so the least-relief word m of
+//   that launch -- and of no other -- is exact: the least r > t over the empty pixels of class cls beside a labelled pixel.  No pixel
+//   can be claimed at a level below m: a level t' < m admits no pixel beside a label, so its first step claims nothing.  The flood
+//   continues at the first level t_j >= m, j = m / q; the levels in between would each cost one launch and change nothing.
+//   No candidate (the word is untouched), or every pending pixel claimed: the flood is over.
+// Every launch but the last of a level claims a pixel or more, so there are at most pending + 256 / q launches.
+int run_flood_launches(umx_labeler* lb, const uint8_t* planes, int K, int H, int W, const umx_label_flood_options* fo, int** src, int** dst,
+                       long long pending, umx_label_flood_counts* fc) {
+    const int tiles_x = (W - 1) / kGrowTile + 1, tiles_y = (H - 1) / kGrowTile + 1;
+    const dim3 tile_grid((unsigned)tiles_y * (unsigned)tiles_x);
+    hipStream_t s = lb->stream;
+    const int q = fo->level_step, nlevels = UMX_FLOOD_MAX_STEP / q;
+    long long claimed = 0, levels_claimed = 0, launches = 0;
+    for (int j = 0; j < nlevels && claimed < pending;) {
+        const int t = std::min(255, (j + 1) * q - 1);
+        long long words[kFloodWords] = {0, 0};
+        bool level_claimed = false;
+        for (;;) {
+            L_HIP(lb, hipMemsetAsync(lb->d_flood + kFloodLeast, kFloodNone & 0xff, sizeof(long long), s));
+            hipLaunchKernelGGL(label_flood_kernel, tile_grid, dim3(kGrowThreads), 0, s, planes, K, H, W, fo->split.base.cls, fo->relief_plane,
+                               fo->invert, t, (const int*)*src, *dst, kGrowHalo, tiles_x, lb->d_flood + kFloodClaimed,
+                               reinterpret_cast<int*>(lb->d_flood + kFloodLeast));
+            std::swap(*src, *dst);
+            ++launches;
+            L_HIP(lb, hipGetLastError());
+            L_HIP(lb, hipMemcpyAsync(words, lb->d_flood, sizeof words, hipMemcpyDeviceToHost, s));
+            L_HIP(lb, hipStreamSynchronize(s));
+            const long long now = words[kFloodClaimed];
+            if (now < claimed || now > pending) return lfail(lb, UMX_ERR_HIP, "the flood claimed %lld of %lld pixels", now, pending);
+            if (now == claimed) break;
+            claimed = now;
+            level_claimed = true;
+            if (claimed == pending) break;
+        }
+        levels_claimed += level_claimed;
+        if (claimed == pending) break;
+        const int m = (int)(words[kFloodLeast] & 0xffffffffll);   // of a launch that claimed nothing
+        if (m == kFloodNone) break;
+        if (m <= t || m > 255) return lfail(lb, UMX_ERR_HIP, "the flood reported a waiting relief of %d at level %d", m, t);
+        j = m / q;                                            // t_j = (j + 1) q - 1 >= m > t: a later level
+    }
+    fc->unreached = pending - claimed; fc->levels_claimed = levels_claimed; fc->claimed = claimed; fc->launches = launches;
+    return UMX_OK;
+}
+
 // The launches of a split run, in the same frame as run_launches:
 //   the objects as there up to label_area_kernel: P = roots, Q = areas; label_count / _scan_kernel: N0 to a word of its own
 //   label_erode_kernel        B = kept | eroded per pixel (the last reader of the objects' areas)
@@ -1118,8 +1298,9 @@ int run_launches(umx_labeler* lb, const uint8_t* planes, int K, int H, int W, co
 //                             number of pixels claimed so far and stops when a launch claimed none: the state is closed -- nothing but
 //                             these launches changes it -- so every later level would claim nothing either
 //   the rim growth and label_grown_kernel as in run_launches
+// A flood run (fo: its options, so == &fo->split; fc takes its counts) has run_flood_launches in the regrow's place.
 int run_split_launches(umx_labeler* lb, const uint8_t* planes, int K, int H, int W, const umx_label_split_options* so, int* out,
-                       umx_label_split_counts* counts) {
+                       umx_label_split_counts* counts, const umx_label_flood_options* fo = nullptr, umx_label_flood_counts* fc = nullptr) {
     const umx_label_options* o = &so->base;
     const long long npix = (long long)H * W;
     const int nblocks = (int)((npix + kScanBlock - 1) / kScanBlock);
@@ -1130,6 +1311,7 @@ int run_split_launches(umx_labeler* lb, const uint8_t* planes, int K, int H, int
     int *P = lb->d_P, *Q = lb->d_Q, *R = lb->d_R;
     uint8_t* B = lb->d_B;
     L_HIP(lb, hipMemsetAsync(lb->d_split, 0, kSplitWords * sizeof(long long), s));
+    if (fo) L_HIP(lb, hipMemsetAsync(lb->d_flood, 0, kFloodWords * sizeof(long long), s));
     hipLaunchKernelGGL(label_runs_kernel, dim3(row_grid(H)), dim3(64 * kRowWaves), 0, s, planes, K, H, W, o->cls, P);
     int rc = launch_components(lb, P, Q, H, W);
     if (rc) return rc;
@@ -1154,7 +1336,11 @@ int run_split_launches(umx_labeler* lb, const uint8_t* planes, int K, int H, int
     hipLaunchKernelGGL(label_seed_kernel, dim3(pix_grid), dim3(kPixThreads), 0, s, P, Q, npix);
     int *src = P, *dst = Q;
     long long claimed = 0;
-    for (int left = so->regrow; left > 0 && claimed < pending; left -= kGrowHalo) {
+    if (fo) {
+        if ((rc = run_flood_launches(lb, planes, K, H, W, fo, &src, &dst, pending, fc))) return rc;
+        claimed = fc->claimed;
+    }
+    for (int left = fo ? 0 : so->regrow; left > 0 && claimed < pending; left -= kGrowHalo) {
         hipLaunchKernelGGL(label_grow_kernel<true>, tile_grid, dim3(kGrowThreads), 0, s, planes, K, H, W, 1u << o->cls, src, dst,
                            std::min(left, kGrowHalo), tiles_x, lb->d_split + kSplitClaimed);
         std::swap(src, dst);
@@ -1172,13 +1358,16 @@ int run_split_launches(umx_labeler* lb, const uint8_t* planes, int K, int H, int
     return UMX_OK;
 }
 
-// split: a split run -- so holds its options (o is not looked at) and counts takes the four counts
+// split: a split run -- so holds its options (o is not looked at) and counts takes the four counts.  fo: a flood run -- its options
+// (then split is set and so is &fo->split) and fcounts takes its counts, the four of the split among them.
 int run_any(umx_labeler* lb, const uint8_t* planes, bool on_host, int K, int H, int W, const umx_label_options* o, int32_t* labels,
-            int64_t* n_objects, bool split = false, const umx_label_split_options* so = nullptr, umx_label_split_counts* counts = nullptr) {
+            int64_t* n_objects, bool split = false, const umx_label_split_options* so = nullptr, umx_label_split_counts* counts = nullptr,
+            const umx_label_flood_options* fo = nullptr, umx_label_flood_counts* fcounts = nullptr) {
     if (!lb) return lfail(nullptr, UMX_ERR_INVALID, "null labeler");
     char msg[200];
-    if ((split ? umx_label_split_check(so, K, H, W, msg, sizeof msg) : umx_label_options_check(o, K, H, W, msg, sizeof msg)) != UMX_OK)
-        return lfail(lb, UMX_ERR_INVALID, "%s", msg);
+    const int refused = fo ? umx_label_flood_check(fo, K, H, W, msg, sizeof msg)
+                           : split ? umx_label_split_check(so, K, H, W, msg, sizeof msg) : umx_label_options_check(o, K, H, W, msg, sizeof msg);
+    if (refused != UMX_OK) return lfail(lb, UMX_ERR_INVALID, "%s", msg);
     if (!planes) return lfail(lb, UMX_ERR_INVALID, "null planes");
     L_HIP(lb, hipSetDevice(lb->device));
     const size_t npix = (size_t)H * W, plane_bytes = (size_t)K * npix;
@@ -1194,8 +1383,9 @@ int run_any(umx_labeler* lb, const uint8_t* planes, bool on_host, int K, int H, 
     long long n = 0;
     int* out = !labels ? nullptr : on_host ? lb->d_P : labels;
     umx_label_split_counts sc = {0, 0, 0, 0};
+    umx_label_flood_counts fc = {0, 0, 0, 0, 0, 0, 0, 0};
     if (split) {
-        rc = run_split_launches(lb, on_host ? lb->d_planes : planes, K, H, W, so, out, &sc);
+        rc = run_split_launches(lb, on_host ? lb->d_planes : planes, K, H, W, so, out, &sc, fo, &fc);
         n = sc.n_objects;
     } else {
         rc = run_launches(lb, on_host ? lb->d_planes : planes, K, H, W, o, out, &n);
@@ -1219,6 +1409,10 @@ int run_any(umx_labeler* lb, const uint8_t* planes, bool on_host, int K, int H, 
     if ((rc = arena_check(lb->mem, &gmsg)) != UMX_OK) return lfail(lb, rc, "%s", gmsg.c_str());
     if (n_objects) *n_objects = n;
     if (counts) *counts = sc;
+    if (fcounts) {
+        fc.n_objects = sc.n_objects; fc.n_before = sc.n_before; fc.n_cored = sc.n_cored;   // (unreached is the flood's own)
+        *fcounts = fc;
+    }
     if (on_host && labels) { lb->res_H = H; lb->res_W = W; lb->res_N = n; lb->res_why = nullptr; }
     else lb->res_why = on_host ? "the last umx_labeler_run was given no label plane (labels_host was NULL)"
                                : "the last run was umx_labeler_run_dev, which leaves its labels with the caller: use umx_labeler_measure_dev";
@@ -1428,6 +1622,36 @@ int umx_labeler_run_split(umx_labeler* lb, const uint8_t* planes_host, int K, in
 int umx_labeler_run_split_dev(umx_labeler* lb, const uint8_t* planes_dev, int K, int H, int W, const umx_label_split_options* o,
                               int32_t* labels_dev, umx_label_split_counts* counts) {
     return run_any(lb, planes_dev, false, K, H, W, nullptr, labels_dev, nullptr, true, o, counts);
+}
+
+int umx_label_flood_check(const umx_label_flood_options* o, int K, int H, int W, char* msg, size_t cap) {
+    char buf[200] = "";
+    if (!o) snprintf(buf, sizeof buf, "null label flood options");
+    else if (umx_label_split_check(&o->split, K, H, W, buf, sizeof buf) != UMX_OK) {}   // (its words, unchanged)
+    else if (o->split.regrow != UMX_SPLIT_MAX_REGROW)
+        snprintf(buf, sizeof buf, "regrow is %d: the flood's steps have no bound, so a flood call must name %d", o->split.regrow,
+                 (int)UMX_SPLIT_MAX_REGROW);
+    else if (o->relief_plane < 0 || o->relief_plane >= K)
+        snprintf(buf, sizeof buf, "relief_plane is %d: the plane is 0..%d, in the model's class order", o->relief_plane, K - 1);
+    else if (o->invert != 0 && o->invert != 1) snprintf(buf, sizeof buf, "invert is %d: 0 or 1", o->invert);
+    else if (o->level_step < 1 || o->level_step > UMX_FLOOD_MAX_STEP || (o->level_step & (o->level_step - 1)) != 0)
+        snprintf(buf, sizeof buf, "level_step is %d: a power of two, 1..%d", o->level_step, (int)UMX_FLOOD_MAX_STEP);
+    for (int i = 0; o && !buf[0] && i < 5; ++i)
+        if (o->reserved[i]) snprintf(buf, sizeof buf, "reserved must be zero (word %d of the flood's reserved words is %d)", i, o->reserved[i]);
+    if (msg && cap) snprintf(msg, cap, "%s", buf);
+    return buf[0] ? UMX_ERR_INVALID : UMX_OK;
+}
+
+int umx_labeler_run_flood(umx_labeler* lb, const uint8_t* planes_host, int K, int H, int W, const umx_label_flood_options* o,
+                          int32_t* labels_host, umx_label_flood_counts* counts) {
+    if (lb && !o) return lfail(lb, UMX_ERR_INVALID, "null label flood options");
+    return run_any(lb, planes_host, true, K, H, W, nullptr, labels_host, nullptr, true, o ? &o->split : nullptr, nullptr, o, counts);
+}
+
+int umx_labeler_run_flood_dev(umx_labeler* lb, const uint8_t* planes_dev, int K, int H, int W, const umx_label_flood_options* o,
+                              int32_t* labels_dev, umx_label_flood_counts* counts) {
+    if (lb && !o) return lfail(lb, UMX_ERR_INVALID, "null label flood options");
+    return run_any(lb, planes_dev, false, K, H, W, nullptr, labels_dev, nullptr, true, o ? &o->split : nullptr, nullptr, o, counts);
 }
 
 int umx_labeler_objects(const umx_labeler* lb, umx_label_object* out, int64_t cap, int64_t* n) {

@@ -106,6 +106,15 @@ def build_parser(spec: ToolSpec) -> argparse.ArgumentParser:
                    help="erosion cores of fewer pixels seed no object (1..65536, default 1)")
     p.add_argument("--labelSplitRegrow", dest="labelSplitRegrow", type=int, default=None, metavar="L",
                    help="levels the cores grow back inside their object (1..255, default 255)")
+    # the regrow cuts a neck on the midline between its cores; --labelFlood P regrows the cores by a level flood on probability plane
+    # P instead, so the cut follows that plane's ridge
+    p.add_argument("--labelFlood", dest="labelFlood", type=int, default=None, metavar="PLANE",
+                   help="with --labelSplit: regrow the cores by a level flood on this probability plane (0-based in the MODEL's class "
+                        "order, e.g. the contour class), cutting touching nuclei along its ridge")
+    p.add_argument("--labelFloodStep", dest="labelFloodStep", type=int, default=None, metavar="Q",
+                   help="the flood rises in levels of Q grey values: a power of two, 1..256 (default 16)")
+    p.add_argument("--labelFloodInvert", dest="labelFloodInvert", action="store_true",
+                   help="flood on 255 - plane (for a plane that is high inside the nuclei, e.g. --labelClass itself)")
     # how bright every labelled object is in the image's own pages: <stem>_Intensities_<suffix>.csv
     p.add_argument("--labelMeasure", dest="labelMeasure", type=int, nargs="*", default=None, metavar="PAGE",
                    help="also write mean, std, min and max of every labelled object in the probability planes and in these pages of "
@@ -123,7 +132,9 @@ def check_label_args(parser: argparse.ArgumentParser, args) -> None:
         for flag, v in (("--labelClass", args.labelClass), ("--labelMinArea", args.labelMinArea), ("--labelGrow", args.labelGrow),
                         ("--labelGrowClasses", args.labelGrowClasses), ("--labelMeasure", args.labelMeasure),
                         ("--labelSplit", args.labelSplit), ("--labelSplitCore", args.labelSplitCore),
-                        ("--labelSplitRegrow", args.labelSplitRegrow), ("--labelShape", args.labelShape or None)):
+                        ("--labelSplitRegrow", args.labelSplitRegrow), ("--labelShape", args.labelShape or None),
+                        ("--labelFlood", args.labelFlood), ("--labelFloodStep", args.labelFloodStep),
+                        ("--labelFloodInvert", args.labelFloodInvert or None)):
             if v is not None:
                 parser.error("%s needs --labelMask" % flag)
         return
@@ -144,6 +155,17 @@ def check_label_args(parser: argparse.ArgumentParser, args) -> None:
         parser.error("--labelSplitCore %d: it must be 1..65536 pixels" % args.labelSplitCore)
     if args.labelSplitRegrow is not None and not 1 <= args.labelSplitRegrow <= 255:
         parser.error("--labelSplitRegrow %d: it must be 1..255 levels" % args.labelSplitRegrow)
+    if args.labelFlood is not None and args.labelSplit is None:
+        parser.error("--labelFlood needs --labelSplit")
+    for flag, v in (("--labelFloodStep", args.labelFloodStep), ("--labelFloodInvert", args.labelFloodInvert or None)):
+        if v is not None and args.labelFlood is None:
+            parser.error("%s needs --labelFlood" % flag)
+    if args.labelFlood is not None and not 0 <= args.labelFlood < 16:
+        parser.error("--labelFlood %d: planes are numbered 0..15 at the most" % args.labelFlood)
+    if args.labelFlood is not None and args.labelSplitRegrow not in (None, 255):
+        parser.error("--labelSplitRegrow %d: the flood's steps have no bound, with --labelFlood it must be 255" % args.labelSplitRegrow)
+    if args.labelFloodStep is not None and args.labelFloodStep not in (1, 2, 4, 8, 16, 32, 64, 128, 256):
+        parser.error("--labelFloodStep %d: it must be a power of two, 1..256" % args.labelFloodStep)
     for k in args.labelGrowClasses or ():
         if k < 0:
             parser.error("--labelGrowClasses %d: classes are numbered from 0" % k)
@@ -357,6 +379,8 @@ def run(tool: str, argv=None, script_dir: str = None) -> int:
         if args.labelClass is not None and args.labelClass >= label_art.hp.nClasses:
             parser.error("--labelClass %d: the model has classes 0..%d" % (args.labelClass, label_art.hp.nClasses - 1))
         grow_classes = label_grow_classes(parser, args, label_art.hp.nClasses)
+        if args.labelFlood is not None and args.labelFlood >= label_art.hp.nClasses:
+            parser.error("--labelFlood %d: the model has planes 0..%d" % (args.labelFlood, label_art.hp.nClasses - 1))
     measure_pages_arg = None
     if args.labelMeasure is not None:
         ftype = split_name(os.path.basename(args.imagePath), spec)[1]
@@ -482,7 +506,9 @@ def run(tool: str, argv=None, script_dir: str = None) -> int:
             with _umx.Labeler(UNet2D.Engine.device) as labeler:
                 labels, objects = labeler.run(stack_u8, args.labelClass, 1 if args.labelMinArea is None else args.labelMinArea,
                                               grow=args.labelGrow or 0, grow_classes=grow_classes, split=args.labelSplit or 0,
-                                              split_core=args.labelSplitCore or 1, split_regrow=args.labelSplitRegrow or 255)
+                                              split_core=args.labelSplitCore or 1, split_regrow=args.labelSplitRegrow or 255,
+                                              flood=args.labelFlood, flood_step=args.labelFloodStep or _umx.FLOOD_DEFAULT_STEP,
+                                              flood_invert=args.labelFloodInvert)
                 tiffio.imsave(out_dir + "//" + stem + "_Labels_" + suffix + ".tif", labels, append=False)
                 write_objects_csv(out_dir + "//" + stem + "_Objects_" + suffix + ".csv", objects)
                 st.mark("label")
@@ -491,6 +517,11 @@ def run(tool: str, argv=None, script_dir: str = None) -> int:
                     print("Label split: %d objects from %d (%d with a core), %d pixels unreached"
                           % (c["n_objects"], c["n_before"], c["n_cored"], c["unreached"]))
                     st.note("label_split", c)
+                if args.labelFlood is not None:
+                    c = labeler.flood_counts()
+                    print("Label flood: %d pixels claimed at %d levels in %d launches, %d pixels unreached"
+                          % (c["claimed"], c["levels_claimed"], c["launches"], c["unreached"]))
+                    st.note("label_flood", c)
                 if measure_pages_arg is not None:
                     # the labels (the grown ones with --labelGrow) are still on the device: the planes the labeler just used, then
                     # the file's pages one at a time; the file is written only when every page has been measured

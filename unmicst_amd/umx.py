@@ -37,6 +37,7 @@ EXPORTS = [
     "umx_labeler_run_dev", "umx_labeler_objects", "umx_labeler_last_ms",
     "umx_label_measure_check", "umx_labeler_measure", "umx_labeler_measure_dev", "umx_labeler_measure_last_ms",
     "umx_label_split_check", "umx_labeler_run_split", "umx_labeler_run_split_dev",
+    "umx_label_flood_check", "umx_labeler_run_flood", "umx_labeler_run_flood_dev",
     "umx_label_shape_check", "umx_labeler_shape", "umx_labeler_shape_dev", "umx_labeler_shape_last_ms",
 ]
 
@@ -47,6 +48,8 @@ LABEL_STRIP_ROWS, LABEL_THREADS, LABEL_SCAN_BLOCK = 32, 1024, 2048
 LABEL_MAX_GROW, LABEL_GROW_TILE, LABEL_GROW_HALO = 255, 64, 8
 # the split at the necks: its largest depth, core area and regrow bound (the UMX_SPLIT_* enumerators; tests/test_label_split_cpu.py compares)
 SPLIT_MAX_DEPTH, SPLIT_MAX_CORE_AREA, SPLIT_MAX_REGROW = 8, 65536, 255
+# the level flood: its largest and its default level step, the steps of one launch (the UMX_FLOOD_* enumerators; tests/test_label_flood_cpu.py compares)
+FLOOD_MAX_STEP, FLOOD_DEFAULT_STEP, FLOOD_LAUNCH_STEPS = 256, 16, 8
 
 
 class UmxError(RuntimeError):
@@ -98,6 +101,18 @@ class _LabelSplitOptions(ctypes.Structure):
 class _LabelSplitCounts(ctypes.Structure):
     """umx_label_split_counts: 32 bytes"""
     _fields_ = [(n, ctypes.c_int64) for n in ("n_objects", "n_before", "n_cored", "unreached")]
+
+
+class _LabelFloodOptions(ctypes.Structure):
+    """umx_label_flood_options: 96 bytes"""
+    _fields_ = [("split", _LabelSplitOptions), ("relief_plane", ctypes.c_int32), ("invert", ctypes.c_int32), ("level_step", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 5)]
+
+
+class _LabelFloodCounts(ctypes.Structure):
+    """umx_label_flood_counts: 64 bytes"""
+    _fields_ = [(n, ctypes.c_int64) for n in ("n_objects", "n_before", "n_cored", "unreached", "levels_claimed", "claimed", "launches",
+                                              "reserved")]
 
 
 class LabelObject(ctypes.Structure):
@@ -308,6 +323,11 @@ def load(path: Optional[str] = None):
     for fn in (L.umx_labeler_run_split, L.umx_labeler_run_split_dev):
         fn.restype = c_int
         fn.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(_LabelSplitOptions), c_void_p, ctypes.POINTER(_LabelSplitCounts)]
+    L.umx_label_flood_check.restype = c_int
+    L.umx_label_flood_check.argtypes = [ctypes.POINTER(_LabelFloodOptions), c_int, c_int, c_int, ctypes.c_char_p, ctypes.c_size_t]
+    for fn in (L.umx_labeler_run_flood, L.umx_labeler_run_flood_dev):
+        fn.restype = c_int
+        fn.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(_LabelFloodOptions), c_void_p, ctypes.POINTER(_LabelFloodCounts)]
     L.umx_labeler_objects.restype = c_int
     L.umx_labeler_objects.argtypes = [c_void_p, c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
     L.umx_labeler_last_ms.restype = c_int
@@ -683,6 +703,33 @@ def label_split_check(K: int, H: int, W: int, cls: int, min_area: int = 1, grow:
     return "" if rc == 0 else buf.value.decode()
 
 
+def _label_flood_options(split: "_LabelSplitOptions", flood: int, flood_step: int, flood_invert) -> "_LabelFloodOptions":
+    o = _LabelFloodOptions()
+    o.split = split
+    o.relief_plane, o.level_step = int(flood), int(flood_step)
+    o.invert = int(flood_invert)                                   # (True and False are 1 and 0)
+    return o
+
+
+def label_flood_check(K: int, H: int, W: int, cls: int, min_area: int = 1, grow: int = 0, grow_classes=None, split: int = 1,
+                      split_core: int = 1, split_regrow: int = 255, flood: int = 0, flood_step: int = FLOOD_DEFAULT_STEP, flood_invert=False,
+                      base_reserved=None, split_reserved=None, reserved=None, null: bool = False) -> str:
+    """umx_label_flood_check: "" if a flood run of K planes of H x W is accepted, else the reason.  ``base_reserved`` and
+    ``split_reserved``: as label_split_check's ``base_reserved`` and ``reserved``; ``reserved``: the flood's own five words.  ``null``:
+    a NULL record.  Host only."""
+    so = _label_split_options(_label_options(K, cls, min_area, grow, grow_classes), split, split_core, split_regrow)
+    for j, v in enumerate(base_reserved or ()):
+        so.base.reserved[j] = int(v)
+    for j, v in enumerate(split_reserved or ()):
+        so.reserved[j] = int(v)
+    o = _label_flood_options(so, flood, flood_step, flood_invert)
+    for j, v in enumerate(reserved or ()):
+        o.reserved[j] = int(v)
+    buf = ctypes.create_string_buffer(256)
+    rc = load().umx_label_flood_check(None if null else ctypes.byref(o), int(K), int(H), int(W), buf, len(buf))
+    return "" if rc == 0 else buf.value.decode()
+
+
 def label_measure_check(dtype: int, C: int, H: int, W: int, n_objects: int = 0) -> str:
     """umx_label_measure_check: "" if a measurement of C planes of H x W of that dtype code against n_objects labels is accepted, else
     the reason.  Host only."""
@@ -762,6 +809,7 @@ class Labeler:
             raise UmxError(rc, self._L.umx_labeler_last_error(None).decode())
         self.device = device
         self._split_counts = None
+        self._flood_counts = None
         self._last_shape = (1, 1)                                  # H, W of the last run: what shape() names when not told
 
     def close(self) -> None:
@@ -805,11 +853,25 @@ class Labeler:
         after a later run without a split."""
         return self._split_counts
 
+    def flood_counts(self) -> dict:
+        """The counts of the last run with a flood of this Labeler: the four of split_counts(), levels_claimed (levels at which a pixel
+        was claimed), claimed (pixels claimed in all) and launches (informative); None before one, and after a later run without."""
+        return self._flood_counts
+
     def _run_any(self, planes_ptr, dev: bool, K: int, H: int, W: int, o: "_LabelOptions", labels_ptr, split: int, split_core: int,
-                 split_regrow: int) -> int:
-        """the entry of today when split is 0, else the split's; -> N"""
+                 split_regrow: int, flood: Optional[int] = None, flood_step: int = FLOOD_DEFAULT_STEP, flood_invert=False) -> int:
+        """the entry of today when split is 0, else the split's, or the flood's when ``flood`` names a plane; -> N"""
         planes_ptr, labels_ptr = ctypes.c_void_p(planes_ptr), ctypes.c_void_p(labels_ptr or None)
         self._split_counts = None
+        self._flood_counts = None
+        if flood is not None:                                      # (without a split the library refuses the depth of 0)
+            fo = _label_flood_options(_label_split_options(o, split, split_core, split_regrow), flood, flood_step, flood_invert)
+            fc = _LabelFloodCounts()
+            fn = self._L.umx_labeler_run_flood_dev if dev else self._L.umx_labeler_run_flood
+            self._check(fn(self._lb, planes_ptr, K, H, W, ctypes.byref(fo), labels_ptr, ctypes.byref(fc)))
+            self._flood_counts = {name: int(getattr(fc, name)) for name, _ in _LabelFloodCounts._fields_ if name != "reserved"}
+            self._split_counts = {name: self._flood_counts[name] for name, _ in _LabelSplitCounts._fields_}
+            return int(fc.n_objects)
         if not split:
             n = ctypes.c_int64()
             fn = self._L.umx_labeler_run_dev if dev else self._L.umx_labeler_run
@@ -823,20 +885,25 @@ class Labeler:
         return int(c.n_objects)
 
     def run(self, planes: np.ndarray, cls: Optional[int] = None, min_area: int = 1, want_labels: bool = True, grow: int = 0,
-            grow_classes=None, split: int = 0, split_core: int = 1, split_regrow: int = 255):
+            grow_classes=None, split: int = 0, split_core: int = 1, split_regrow: int = 255, flood: Optional[int] = None,
+            flood_step: int = FLOOD_DEFAULT_STEP, flood_invert: bool = False):
         """planes uint8 [K, H, W] in the model's class order -> (labels int32 [H, W], objects); ``cls`` None: the last class.
         want_labels False: labels is None (only the count and the table come down).  grow R > 0: the kept objects grow R levels
         over the pixels whose class is in ``grow_classes`` (an iterable of class indices; None: every class but 0 and ``cls``).
         split D > 0: the kept objects are split at their necks first (erosion cores of depth D and area >= ``split_core``, regrown
         at most ``split_regrow`` levels inside their objects); split_counts() has the counts.
-        split 0 is the call of before."""
+        split 0 is the call of before.
+        flood P (with split > 0): the cores are regrown by the level flood on the relief planes[P] (255 - planes[P] with
+        ``flood_invert``) in levels of ``flood_step`` (a power of two, 1..256) instead of by distance, so a neck is cut along the
+        relief's ridge (steps 19 to 21; split_regrow must stay 255); flood_counts() has the counts.  None is the call of before."""
         planes = np.ascontiguousarray(planes)
         if planes.dtype != np.uint8 or planes.ndim != 3:
             raise TypeError("planes must be uint8 [K, H, W]")
         K, H, W = planes.shape
         o = _label_options(K, cls, min_area, grow, grow_classes)
         labels = np.empty((H, W), np.int32) if want_labels else None
-        n = self._run_any(planes.ctypes.data, False, K, H, W, o, labels.ctypes.data if want_labels else None, split, split_core, split_regrow)
+        n = self._run_any(planes.ctypes.data, False, K, H, W, o, labels.ctypes.data if want_labels else None, split, split_core, split_regrow,
+                          flood, flood_step, flood_invert)
         if want_labels:
             self._last_shape = (H, W)                              # (of the resident labels: a refused run above has left them)
         objs = self.objects()
@@ -844,12 +911,13 @@ class Labeler:
         return labels, objs
 
     def run_ptr(self, planes_ptr: int, K: int, H: int, W: int, labels_ptr: int = 0, cls: Optional[int] = None, min_area: int = 1,
-                grow: int = 0, grow_classes=None, split: int = 0, split_core: int = 1, split_regrow: int = 255) -> np.ndarray:
+                grow: int = 0, grow_classes=None, split: int = 0, split_core: int = 1, split_regrow: int = 255,
+                flood: Optional[int] = None, flood_step: int = FLOOD_DEFAULT_STEP, flood_invert: bool = False) -> np.ndarray:
         """umx_labeler_run_dev on DEVICE addresses (e.g. torch.Tensor.data_ptr()): uint8 [K, H, W] in, int32 [H, W] out (0: no label
         plane) -> objects.  The planes must be complete; the call returns with the labels complete.  grow, grow_classes and the
-        split's three: as run."""
+        split's three and the flood's three: as run."""
         o = _label_options(int(K), cls, min_area, grow, grow_classes)
-        self._run_any(planes_ptr, True, int(K), int(H), int(W), o, labels_ptr, split, split_core, split_regrow)
+        self._run_any(planes_ptr, True, int(K), int(H), int(W), o, labels_ptr, split, split_core, split_regrow, flood, flood_step, flood_invert)
         return self.objects()
 
     def measure(self, planes: np.ndarray) -> np.ndarray:
