@@ -424,6 +424,73 @@ UMX_API int umx_labeler_shape_dev(umx_labeler* lb, const int32_t* labels_dev, in
 UMX_API int umx_labeler_shape_last_ms(const umx_labeler* lb, double* kernel_ms, double* download_ms);
 
 /*
+ * Which labelled objects touch, and along how many pixel edges (the definition is the
+ * project's own).  From labels int32 [H][W] with objects 1..N -- a value < 0 or > N counts as 0 and is never used as an index:
+ *   22. contacts: a pixel edge is a pair of horizontally or vertically adjacent pixels, both inside the image (diagonal neighbours
+ *       do not count: UMX_BORDER_CONNECTIVITY).  For labels a < b, edges(a, b) is the number of pixel edges whose two pixels carry a
+ *       and b, in either order; the pair is a contact iff edges > 0.  One umx_label_contact per contact, sorted by (a, b) ascending;
+ *       M is their number.  edges <= 2 H W < 2^32.
+ *   23. reach R, 1 .. UMX_CONTACT_MAX_REACH: the contacts are taken from a scratch plane S instead -- the labels (values outside 1..N
+ *       as 0) grown R levels by the growth rule of umx_labeler_run's step 6 over the domain "label 0", no class consulted.  Two
+ *       objects with a gap between them are then neighbours when their fronts meet within R levels and no third object lies
+ *       between.  S is scratch: the labels, the object table and what the measurement and the shapes see are bit for bit what they
+ *       were.  R = 0 is step 22 on the labels themselves.
+ *   24. the degree of an object (the contacts it takes part in) and its total shared edges are host arithmetic on the list, stated
+ *       once in unmicst_amd/umx.py contact_degrees.
+ * After a plain run the list is empty (4-connected components of one class never touch); after a growth, a split or a flood it
+ * is the set of cut lines those steps drew.  Everything is an integer and the list a set with counts in canonical order: two calls
+ * give the same bytes, in whatever order threads and atomics run.
+ * The device side: one pass over the plane (one wave per row; equal pairs on consecutive pixels collapse to one insertion) into an
+ * open-addressing table of UMX_CONTACT_TABLE_MIN entries or the power of two at or above n_objects, whichever is larger, of 12
+ * bytes each; a pass that finds no slot within UMX_CONTACT_PROBE_MAX probes is run again with the table doubled, and beyond
+ * UMX_CONTACT_TABLE_MAX entries the call is refused with a message (UMX_ERR_OOM).  The list is ordered on the device when no object has more
+ * than UMX_CONTACT_DEVICE_SORT_MAX contacts (a rank by counting inside each object's row), else on the host; both give the same
+ * bytes.  A reach of R needs one scratch plane of H * W int32, two when R > 8: the labeler's second plane and the split's third one
+ * where a run has allocated them large enough, else allocations of their own, kept like the others.
+ */
+typedef struct umx_label_contact {
+    int32_t a, b;            /* the two labels, 1 <= a < b <= N */
+    uint32_t edges;          /* pixel edges between them, >= 1 */
+    uint32_t reserved;       /* 0 */
+} umx_label_contact;         /* 16 bytes */
+typedef struct umx_label_contact_stats {
+    int64_t table_capacity;  /* entries of the table of the last pass */
+    int64_t reruns;          /* passes of the last call that found the table too small and were run again */
+    int64_t longest_row;     /* the largest number of contacts (a, .) of one label a: what the ordering is chosen by */
+    int32_t ordered_by;      /* who ordered the list: one of the three codes below */
+    int32_t reserved;
+} umx_label_contact_stats;   /* 32 bytes */
+#define UMX_CONTACT_MAX_REACH 255
+#define UMX_CONTACT_TABLE_MIN 65536
+#define UMX_CONTACT_TABLE_MAX 268435456
+#define UMX_CONTACT_PROBE_MAX 1024
+#define UMX_CONTACT_DEVICE_SORT_MAX 1024
+/* ordered_by: nothing to order (M == 0, or only M was asked for) | the device | the host (a row longer than the cap above) */
+#define UMX_CONTACT_ORDER_NONE 0
+#define UMX_CONTACT_ORDER_DEVICE 1
+#define UMX_CONTACT_ORDER_HOST 2
+/* Host only, no device: H, W >= 1; H * W <= 2^31 - 1; 0 <= n_objects <= 2^31 - 1; 0 <= reach <= 255.  UMX_OK, or UMX_ERR_INVALID
+ * with the reason in msg (cap bytes; may be NULL). */
+UMX_API int umx_label_contact_check(int H, int W, int64_t n_objects, int reach, char* msg, size_t cap);
+/* The contacts of the labels of the last successful host run that was given a label plane (plain, grown, split or flooded): they
+ * are still on the device.  M records into out (cap: its records), M into *m (may be NULL); out NULL with cap 0: only M into *m.
+ * Refusals as umx_labeler_shape's (UMX_ERR_INVALID, nothing touched, the labeler usable, the resident labels kept): no such run, a
+ * later run without a label plane or on device pointers or a failed one, H or W other than that run's, a reach outside 0..255; and
+ * cap < M, with M stored in *m (M is known only after the pass: the device has worked, out is untouched).  Synchronous: returns with
+ * the stream idle, and under UMX_DEBUG_GUARD ends in the check of the red zones.  All device memory is the labeler's arena's, grown
+ * on demand and kept. */
+UMX_API int umx_labeler_contacts(umx_labeler* lb, int H, int W, int reach, umx_label_contact* out, int64_t cap, int64_t* m);
+/* The same on a DEVICE pointer of the labeler's device: labels_dev int32 [H][W] with objects 1..n_objects, complete when the call is
+ * made and only read.  Needs no prior run and leaves the resident labels alone. */
+UMX_API int umx_labeler_contacts_dev(umx_labeler* lb, const int32_t* labels_dev, int64_t n_objects, int H, int W, int reach,
+                                     umx_label_contact* out_host, int64_t cap, int64_t* m);
+/* Milliseconds of the last contacts call: its launches (every pass, the growth of a reach and the ordering), the download of the
+ * records.  Either may be NULL. */
+UMX_API int umx_labeler_contacts_last_ms(const umx_labeler* lb, double* kernel_ms, double* download_ms);
+/* How the last contacts call went.  UMX_ERR_INVALID for a null argument. */
+UMX_API int umx_labeler_contacts_last_stats(const umx_labeler* lb, umx_label_contact_stats* stats);
+
+/*
  * Splitting touching nuclei at their necks by erosion cores (the definition is the project's
  * own).  Two nuclei are separate objects only where an unbroken line of another class lies between them; where that line has a gap
  * the labelling joins them.  With a depth D, a minimum core area C and a regrow bound L, on top of the options of a labelling run:

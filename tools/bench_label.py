@@ -286,6 +286,63 @@ def shape_bench(a, H, W):
             "numpy_scipy_s": None if cpu_s is None else round(cpu_s, 3)}
 
 
+def host_contacts(labels, reach=0, band=1024):
+    """the same list by numpy -> (a, b, edges), int64 [M] each: every horizontal and vertical neighbour pair of two different labels,
+    counted by np.unique; a reach first grows the labels level by level over the unlabelled pixels (the least labelled 4-neighbour)"""
+    lab = labels.astype(np.int64)
+    big = np.iinfo(np.int64).max
+    for _ in range(reach):
+        c = np.pad(np.where(lab > 0, lab, big), 1, constant_values=big)
+        least = np.minimum(np.minimum(c[:-2, 1:-1], c[2:, 1:-1]), np.minimum(c[1:-1, :-2], c[1:-1, 2:]))
+        lab = np.where((lab == 0) & (least < big), least, lab)
+    keys = []
+    for y0 in range(0, lab.shape[0], band):                  # (band by band: the pairs of a whole slide at once are tens of GB)
+        rows = lab[y0:y0 + band + 1]                         # the band and the row below it
+        for p, q in ((rows[:band, :-1], rows[:band, 1:]), (rows[:-1], rows[1:])):
+            keep = (p > 0) & (q > 0) & (p != q)
+            p, q = p[keep], q[keep]
+            keys.append((np.minimum(p, q) << 32) | np.maximum(p, q))
+    key, count = np.unique(np.concatenate(keys), return_counts=True)
+    return key >> 32, key & 0xFFFFFFFF, count
+
+
+def contacts_bench(a, H, W):
+    """the grown-blobs input of --grow (every shared rim is a contact): the labelling with the growth once, then the contacts of the
+    resident labels; the first call grows the table (its reruns are reported), the timed ones find it large enough"""
+    core, bodies = blob_mask(H, W), blob_mask(H, W, rim=RIM)
+    planes = planes_of(core, bodies)
+    grow = a.grow or RIM
+    with umx.Labeler(a.device) as lb:
+        labels, objects = lb.run(planes, grow=grow)
+        label_ms = lb.last_ms()
+        del planes
+        N = len(objects)
+        rec = lb.contacts(reach=a.reach)
+        first_ms, first = lb.contacts_last_ms(), lb.contacts_stats()
+        best = None
+        for _ in range(a.reps):
+            again = lb.contacts(reach=a.reach)
+            ms = lb.contacts_last_ms()
+            if best is None or ms[0] < best[0]:
+                best = ms
+        stats = lb.contacts_stats()
+        assert again.tobytes() == rec.tobytes()
+    degree, shared = umx.contact_degrees(rec, N)
+    cpu_s = None
+    if not a.no_host:
+        t = time.perf_counter()
+        ha, hb, hn = host_contacts(labels, a.reach)
+        cpu_s = time.perf_counter() - t
+        assert np.array_equal(rec["a"], ha) and np.array_equal(rec["b"], hb) and np.array_equal(rec["edges"], hn)
+    return {"contacts": True, "grow": grow, "reach": a.reach, "objects": N, "M": len(rec), "largest_degree": int(degree.max()) if N else 0,
+            "shared_edges": int(rec["edges"].sum()), "label_kernel_ms": round(label_ms[1], 3),
+            "kernel_ms": round(best[0], 3), "download_ms": round(best[1], 3),
+            "first_call_kernel_ms": round(first_ms[0], 3), "first_call_reruns": first["reruns"], "stats": stats,
+            # every label word once from memory at least, twice (the row below again) at most; the table cleared and, per segment, a key read and a count added to
+            "read_bytes_lower": 4 * H * W, "read_bytes_upper": 8 * H * W, "table_bytes": 12 * stats["table_capacity"], "record_bytes": 16 * len(rec),
+            "numpy_unique_s": None if cpu_s is None else round(cpu_s, 3)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("H", type=int, nargs="?", default=16384)
@@ -300,10 +357,15 @@ def main():
     ap.add_argument("--flood-step", dest="flood_step", type=int, default=umx.FLOOD_DEFAULT_STEP, metavar="Q")
     ap.add_argument("--measure-dtype", dest="measure_dtype", choices=("u8", "u16"), default="u16")
     ap.add_argument("--shape", action="store_true")
-    ap.add_argument("--no-host", dest="no_host", action="store_true", help="with --shape: leave the numpy / scipy figure out (a traced run)")
+    ap.add_argument("--no-host", dest="no_host", action="store_true", help="with --shape / --contacts: leave the numpy / scipy figure out (a traced run)")
+    ap.add_argument("--contacts", action="store_true", help="the contacts of the grown-blobs input (--grow R, default the rim)")
+    ap.add_argument("--reach", type=int, default=0, metavar="R", help="with --contacts: the reach")
     a = ap.parse_args()
     H, W = a.H, a.W or a.H
     out = {"tool": "bench_label", "H": H, "W": W, "K": 3, "min_area": 1, "reps": a.reps}
+    if a.contacts:
+        print(json.dumps(dict(out, **contacts_bench(a, H, W))))
+        return
     if a.grow:
         print(json.dumps(dict(out, **grow_bench(a, H, W))))
         return

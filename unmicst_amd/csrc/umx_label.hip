@@ -43,6 +43,10 @@
 //   label_shape_init_kernel, label_shape_kernel   one wave per row: the labels of the row and of the rows above and below it; every
 //                         row run adds its moments (closed forms of its row and its two ends) and the counts of the 2x2 windows
 //                         that its pixels own to record label - 1
+// The contacts (umx_labeler_contacts / _contacts_dev) live in umx_label_contact.hip; the
+// labeler's state, which both sources share, in umx_label_state.h.  From here they use
+//   label_grow_kernel<false, true>   the growth kernel over "every pixel without a label", no class consulted (the reach, step 23)
+//   label_scan_kernel     the one-workgroup scan of the numbering, for the prefix sums of the contacts per label
 //
 // Why no workgroup waits for another one, and none reads inside a kernel what another one writes in it: in the strip launch a workgroup
 // touches only pixels of its strip -- a link made there joins two run heads of the strip, so a walk from a pixel of the strip stays in
@@ -55,6 +59,7 @@
 #include "../../include/umx.h"
 #include "../../include/umx_train.h"
 #include "umx_internal.h"
+#include "umx_label_state.h"
 #include "umx_unionfind.h"
 
 #include <climits>
@@ -375,10 +380,13 @@ __global__ void __launch_bounds__(kPixThreads) label_seed_kernel(int* __restrict
 // integer atomic per workgroup that claimed any, which nothing reads before the launch ends.  A claim inside the tile is never one
 // of the possibly wrong ones, so the sum over the tiles is the number of pixels the launch labelled.  Without kCount the kernel
 // is the one the plain growth always launched, and `claimed` is not touched.
-template <bool kCount>
+// kFree (the reach of the contacts, step 23): every pixel whose value in src is outside 1..n_labels counts as 0 and is domain; no
+// class is consulted and `planes` is never read (it may be null).  Chosen at compile time: without kFree n_labels is not looked
+// at and the kernel is what it was.
+template <bool kCount, bool kFree = false>
 __global__ void __launch_bounds__(kGrowThreads) label_grow_kernel(const uint8_t* __restrict__ planes, int K, int H, int W, unsigned classes,
                                                                   const int* __restrict__ src, int* __restrict__ dst, int levels,
-                                                                  int tiles_x, long long* __restrict__ claimed) {
+                                                                  int tiles_x, long long* __restrict__ claimed, int n_labels) {
     __shared__ int L[kGrowPix];
     int mine = 0;                                             // (kCount) claims of this thread inside the tile
     const int tid = threadIdx.x;
@@ -394,7 +402,9 @@ __global__ void __launch_bounds__(kGrowThreads) label_grow_kernel(const uint8_t*
         if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
             const size_t i = (size_t)gy * W + (size_t)gx;
             v = src[i];
-            if (v == 0) {                                     // (a labelled pixel's class is never asked for)
+            if (kFree) {
+                if (v < 1 || v > n_labels) v = -1;
+            } else if (v == 0) {                              // (a labelled pixel's class is never asked for)
                 int arg = 0, best = planes[i];
                 for (int k = 1; k < K; ++k) {
                     const int p = planes[(size_t)k * npix + i];
@@ -1052,42 +1062,7 @@ __global__ void __launch_bounds__(64 * kRowWaves) label_shape_kernel(const int* 
 
 }  // namespace umx
 
-struct umx_labeler {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // upload begins | launches begin | downloads begin | all done
-    umx::DevArena mem;
-    uint8_t* d_planes = nullptr;  size_t planes_cap = 0;       // bytes
-    int* d_P = nullptr;
-    int* d_Q = nullptr;           size_t pix_cap = 0;          // words of either plane
-    int* d_counts = nullptr;      size_t counts_cap = 0;       // words
-    long long* d_n = nullptr;
-    umx_label_object* d_table = nullptr;  size_t table_cap = 0;   // records
-    // the split's own (allocated from the first split run on, then kept like the others): the third plane, the flags, three words
-    int* d_R = nullptr;
-    uint8_t* d_B = nullptr;       size_t split_cap = 0;        // words of d_R = bytes of d_B (rounded up to a whole word); 0: never asked for
-    long long* d_split = nullptr;                              // kSplitWords words the kernels of a split run add to
-    long long* d_flood = nullptr;                              // kFloodWords words a flood launch reports in (allocated with d_split)
-    std::vector<umx_label_object> table;                       // of the last run
-    double ms[3] = {0.0, 0.0, 0.0};
-    // the resident labels: d_P holds the int32 [res_H][res_W] label plane of res_N objects iff res_why is null; else why it does not
-    int res_H = 0, res_W = 0;
-    long long res_N = 0;
-    const char* res_why = "no umx_labeler_run has given this labeler a label plane yet";
-    // the measurement's own allocations (of the same arena, never part of ensure_buffers' sizes): staging for one group of planes,
-    // the records of one group
-    void* d_mplanes = nullptr;    size_t mplanes_cap = 0;      // bytes
-    umx_label_measure* d_mrec = nullptr;  size_t mrec_cap = 0; // records
-    double mms[3] = {0.0, 0.0, 0.0};
-    // the shapes' own allocation, as the measurement's: the records
-    umx_label_shape* d_srec = nullptr;    size_t srec_cap = 0; // records
-    double sms[2] = {0.0, 0.0};                                // launches | download
-    std::string err;
-};
-
 namespace umx {
-
-namespace {
 
 int lfail(umx_labeler* lb, int code, const char* fmt, ...) {
     char buf[512];
@@ -1100,12 +1075,7 @@ int lfail(umx_labeler* lb, int code, const char* fmt, ...) {
     return code;
 }
 
-#define L_HIP(lb, expr)                                                                                                  \
-    do {                                                                                                                 \
-        hipError_t e__ = (expr);                                                                                         \
-        if (e__ != hipSuccess)                                                                                           \
-            return lfail(lb, e__ == hipErrorOutOfMemory ? UMX_ERR_OOM : UMX_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e__)); \
-    } while (0)
+namespace {
 
 // Buffers for K planes of H x W.  Nothing shrinks; when one is too small the arena is emptied and every buffer allocated again at the
 // larger of its old and its needed size (the arena frees as a whole, and the red zones of guard mode are per allocation).
@@ -1119,6 +1089,7 @@ int ensure_buffers(umx_labeler* lb, size_t plane_bytes, size_t npix, size_t nblo
     lb->d_R = nullptr; lb->d_B = nullptr; lb->d_split = nullptr; lb->d_flood = nullptr;
     lb->d_mplanes = nullptr; lb->d_mrec = nullptr; lb->mplanes_cap = lb->mrec_cap = 0;   // (the measurement allocates its own again)
     lb->d_srec = nullptr; lb->srec_cap = 0;                                              // (and so do the shapes)
+    contact_buffers_forget(lb);                                                          // (and the contacts)
     const size_t pb = std::max(plane_bytes, lb->planes_cap), px = std::max(npix, lb->pix_cap), nb = std::max(nblocks, lb->counts_cap);
     const size_t tc = std::max<size_t>(lb->table_cap, 1024);
     const size_t sp = std::max(split_need, lb->split_cap);
@@ -1201,7 +1172,7 @@ void launch_grow_and_table(umx_labeler* lb, const uint8_t* planes, int K, int H,
     const int tiles_x = (W - 1) / kGrowTile + 1, tiles_y = (H - 1) / kGrowTile + 1;   // tiles_y * tiles_x <= 2^25 + 2^19: H * W <= INT_MAX
     for (int left = o->grow_radius; left > 0; left -= kGrowHalo) {
         hipLaunchKernelGGL(label_grow_kernel<false>, dim3((unsigned)tiles_y * (unsigned)tiles_x), dim3(kGrowThreads), 0, s, planes, K, H, W,
-                           o->grow_classes, src, dst, std::min(left, kGrowHalo), tiles_x, (long long*)nullptr);
+                           o->grow_classes, src, dst, std::min(left, kGrowHalo), tiles_x, (long long*)nullptr, 0);
         std::swap(src, dst);
     }
     hipLaunchKernelGGL(label_grown_kernel, dim3(row_grid(H)), dim3(64 * kRowWaves), 0, s, src, H, W, out, lb->d_table);
@@ -1342,7 +1313,7 @@ int run_split_launches(umx_labeler* lb, const uint8_t* planes, int K, int H, int
     }
     for (int left = fo ? 0 : so->regrow; left > 0 && claimed < pending; left -= kGrowHalo) {
         hipLaunchKernelGGL(label_grow_kernel<true>, tile_grid, dim3(kGrowThreads), 0, s, planes, K, H, W, 1u << o->cls, src, dst,
-                           std::min(left, kGrowHalo), tiles_x, lb->d_split + kSplitClaimed);
+                           std::min(left, kGrowHalo), tiles_x, lb->d_split + kSplitClaimed, 0);
         std::swap(src, dst);
         L_HIP(lb, hipGetLastError());
         long long now = 0;
@@ -1416,20 +1387,6 @@ int run_any(umx_labeler* lb, const uint8_t* planes, bool on_host, int K, int H, 
     if (on_host && labels) { lb->res_H = H; lb->res_W = W; lb->res_N = n; lb->res_why = nullptr; }
     else lb->res_why = on_host ? "the last umx_labeler_run was given no label plane (labels_host was NULL)"
                                : "the last run was umx_labeler_run_dev, which leaves its labels with the caller: use umx_labeler_measure_dev";
-    return UMX_OK;
-}
-
-// A buffer of the measurement at least `need` (bytes or records) large: its own allocation of the arena, released and made again
-// when it must grow.  Nothing else of the arena moves, so the resident labels stay.
-template <typename P>
-int ensure_measure_buffer(umx_labeler* lb, P** buf, size_t* cap, size_t need, size_t unit, const char* what) {
-    if (*buf && need <= *cap) return UMX_OK;
-    L_HIP(lb, hipStreamSynchronize(lb->stream));
-    if (*buf) L_HIP(lb, arena_release(&lb->mem, *buf));
-    *buf = nullptr; *cap = 0;
-    const size_t n = std::max<size_t>(need, 1);
-    L_HIP(lb, arena_alloc(&lb->mem, (void**)buf, n * unit, false, what));
-    *cap = n;
     return UMX_OK;
 }
 
@@ -1513,6 +1470,16 @@ int shape_any(umx_labeler* lb, const int* labels, long long N, int H, int W, umx
 }
 
 }  // namespace
+
+void launch_grow_free(hipStream_t s, int H, int W, int N, const int* src, int* dst, int levels) {
+    const int tiles_x = (W - 1) / kGrowTile + 1, tiles_y = (H - 1) / kGrowTile + 1;   // tiles_y * tiles_x <= 2^25 + 2^19: H * W <= INT_MAX
+    hipLaunchKernelGGL((label_grow_kernel<false, true>), dim3((unsigned)tiles_y * (unsigned)tiles_x), dim3(kGrowThreads), 0, s,
+                       (const uint8_t*)nullptr, 0, H, W, 0u, src, dst, levels, tiles_x, (long long*)nullptr, N);
+}
+
+void launch_block_scan(hipStream_t s, int* counts, int nblocks, long long* total) {
+    hipLaunchKernelGGL(label_scan_kernel, dim3(1), dim3(kMergeThreads), 0, s, counts, nblocks, total);
+}
 
 }  // namespace umx
 

@@ -123,6 +123,13 @@ def build_parser(spec: ToolSpec) -> argparse.ArgumentParser:
     p.add_argument("--labelShape", dest="labelShape", action="store_true",
                    help="also write perimeter, holes, major and minor axis, eccentricity, orientation and extent of every labelled "
                         "object (the grown or split ones with --labelGrow / --labelSplit)")
+    # which labelled objects touch: <stem>_Neighbors_<suffix>.csv
+    p.add_argument("--labelNeighbors", dest="labelNeighbors", action="store_true",
+                   help="also write which labelled objects (the grown or split ones with --labelGrow / --labelSplit) touch, and along "
+                        "how many pixel edges")
+    p.add_argument("--labelNeighborsReach", dest="labelNeighborsReach", type=int, default=None, metavar="R",
+                   help="with --labelNeighbors: objects also count as neighbours when fronts grown R pixels (0..255, default 0) from them "
+                        "over the unlabelled pixels meet; the label mask itself is not changed")
     return p
 
 
@@ -134,7 +141,8 @@ def check_label_args(parser: argparse.ArgumentParser, args) -> None:
                         ("--labelSplit", args.labelSplit), ("--labelSplitCore", args.labelSplitCore),
                         ("--labelSplitRegrow", args.labelSplitRegrow), ("--labelShape", args.labelShape or None),
                         ("--labelFlood", args.labelFlood), ("--labelFloodStep", args.labelFloodStep),
-                        ("--labelFloodInvert", args.labelFloodInvert or None)):
+                        ("--labelFloodInvert", args.labelFloodInvert or None), ("--labelNeighbors", args.labelNeighbors or None),
+                        ("--labelNeighborsReach", args.labelNeighborsReach)):
             if v is not None:
                 parser.error("%s needs --labelMask" % flag)
         return
@@ -166,6 +174,10 @@ def check_label_args(parser: argparse.ArgumentParser, args) -> None:
         parser.error("--labelSplitRegrow %d: the flood's steps have no bound, with --labelFlood it must be 255" % args.labelSplitRegrow)
     if args.labelFloodStep is not None and args.labelFloodStep not in (1, 2, 4, 8, 16, 32, 64, 128, 256):
         parser.error("--labelFloodStep %d: it must be a power of two, 1..256" % args.labelFloodStep)
+    if args.labelNeighborsReach is not None and not args.labelNeighbors:
+        parser.error("--labelNeighborsReach needs --labelNeighbors")
+    if args.labelNeighborsReach is not None and not 0 <= args.labelNeighborsReach <= 255:
+        parser.error("--labelNeighborsReach %d: it must be 0..255 pixels" % args.labelNeighborsReach)
     for k in args.labelGrowClasses or ():
         if k < 0:
             parser.error("--labelGrowClasses %d: classes are numbered from 0" % k)
@@ -238,6 +250,17 @@ def write_shapes_csv(path: str, objects, records) -> None:
     with open(path, "w") as f:
         f.write(",".join(SHAPE_COLUMNS) + "\n")
         f.writelines("%d,%d,%d,%r,%d,%d,%r,%r,%r,%r,%r\n" % row for row in zip(*cols))
+
+
+NEIGHBOR_COLUMNS = ("label_a", "label_b", "shared_edges")
+
+
+def write_neighbors_csv(path: str, contacts) -> None:
+    """NEIGHBOR_COLUMNS -- one line per contact of umx.LABEL_CONTACT_DTYPE records [M], in their order: (label_a, label_b) ascending,
+    label_a < label_b."""
+    with open(path, "w") as f:
+        f.write(",".join(NEIGHBOR_COLUMNS) + "\n")
+        f.writelines("%d,%d,%d\n" % row for row in zip(contacts["a"].tolist(), contacts["b"].tolist(), contacts["edges"].tolist()))
 
 
 def measure_pages(labeler, path: str, pages, shape) -> list:
@@ -533,6 +556,13 @@ def run(tool: str, argv=None, script_dir: str = None) -> int:
                 if args.labelShape:
                     write_shapes_csv(out_dir + "//" + stem + "_Shapes_" + suffix + ".csv", objects, labeler.shape())
                     st.mark("shape")
+                if args.labelNeighbors:
+                    contacts = labeler.contacts(reach=args.labelNeighborsReach or 0)
+                    write_neighbors_csv(out_dir + "//" + stem + "_Neighbors_" + suffix + ".csv", contacts)
+                    degree = _umx.contact_degrees(contacts, len(objects))[0]
+                    print("Label neighbors: %d contacts, largest degree %d" % (len(contacts), int(degree.max()) if len(degree) else 0))
+                    st.note("label_neighbors", dict(labeler.contacts_stats(), contacts=len(contacts)))
+                    st.mark("neighbors")
     finally:
         if args.compat_per_class:
             UNet2D.reuse_pass = reuse_before

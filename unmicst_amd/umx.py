@@ -39,6 +39,8 @@ EXPORTS = [
     "umx_label_split_check", "umx_labeler_run_split", "umx_labeler_run_split_dev",
     "umx_label_flood_check", "umx_labeler_run_flood", "umx_labeler_run_flood_dev",
     "umx_label_shape_check", "umx_labeler_shape", "umx_labeler_shape_dev", "umx_labeler_shape_last_ms",
+    "umx_label_contact_check", "umx_labeler_contacts", "umx_labeler_contacts_dev", "umx_labeler_contacts_last_ms",
+    "umx_labeler_contacts_last_stats",
 ]
 
 # the label mask's limits and the geometry of its kernels (the UMX_LABEL_* macros of include/umx.h; tests/test_label_cpu.py compares)
@@ -141,6 +143,24 @@ class LabelShape(ctypes.Structure):
 LABEL_SHAPE_DTYPE = np.dtype([(n, "<i8") for n in ("sum_y", "sum_x", "sum_yy", "sum_xy", "sum_xx")] +
                              [(n, "<u4") for n in ("q1", "q2", "qd", "q3", "q4", "reserved")])
 SHAPE_MAX_SIDE = 65536                                         # UMX_SHAPE_MAX_SIDE
+
+
+class LabelContact(ctypes.Structure):
+    """umx_label_contact: 16 bytes"""
+    _fields_ = [("a", ctypes.c_int32), ("b", ctypes.c_int32), ("edges", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class _LabelContactStats(ctypes.Structure):
+    """umx_label_contact_stats: 32 bytes"""
+    _fields_ = [("table_capacity", ctypes.c_int64), ("reruns", ctypes.c_int64), ("longest_row", ctypes.c_int64),
+                ("ordered_by", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+# the same record as a numpy dtype: what Labeler.contacts returns, [M], sorted by (a, b)
+LABEL_CONTACT_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("edges", "<u4"), ("reserved", "<u4")])
+# the UMX_CONTACT_* macros of include/umx.h (tests/test_label_contacts_cpu.py compares)
+CONTACT_MAX_REACH, CONTACT_TABLE_MIN, CONTACT_TABLE_MAX, CONTACT_PROBE_MAX, CONTACT_DEVICE_SORT_MAX = 255, 65536, 268435456, 1024, 1024
+CONTACT_ORDER_NONE, CONTACT_ORDER_DEVICE, CONTACT_ORDER_HOST = 0, 1, 2
 
 
 _SEND_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p)
@@ -348,6 +368,17 @@ def load(path: Optional[str] = None):
     L.umx_labeler_shape_dev.argtypes = [c_void_p, c_void_p, ctypes.c_int64, c_int, c_int, c_void_p, ctypes.c_int64]
     L.umx_labeler_shape_last_ms.restype = c_int
     L.umx_labeler_shape_last_ms.argtypes = [c_void_p] + [ctypes.POINTER(c_double)] * 2
+    L.umx_label_contact_check.restype = c_int
+    L.umx_label_contact_check.argtypes = [c_int, c_int, ctypes.c_int64, c_int, ctypes.c_char_p, ctypes.c_size_t]
+    L.umx_labeler_contacts.restype = c_int
+    L.umx_labeler_contacts.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+    L.umx_labeler_contacts_dev.restype = c_int
+    L.umx_labeler_contacts_dev.argtypes = [c_void_p, c_void_p, ctypes.c_int64, c_int, c_int, c_int, c_void_p, ctypes.c_int64,
+                                           ctypes.POINTER(ctypes.c_int64)]
+    L.umx_labeler_contacts_last_ms.restype = c_int
+    L.umx_labeler_contacts_last_ms.argtypes = [c_void_p] + [ctypes.POINTER(c_double)] * 2
+    L.umx_labeler_contacts_last_stats.restype = c_int
+    L.umx_labeler_contacts_last_stats.argtypes = [c_void_p, ctypes.POINTER(_LabelContactStats)]
     L.umx_prof_entry_size.restype = c_int
     if L.umx_prof_entry_size() != ctypes.sizeof(ProfEntry):
         raise RuntimeError("libumx (%s) lays umx_prof_entry out in %d bytes, this binding in %d: mixed builds" % (
@@ -797,6 +828,28 @@ def shape_descriptors(records: np.ndarray) -> dict:
     return out
 
 
+def label_contact_check(H: int, W: int, n_objects: int = 0, reach: int = 0) -> str:
+    """umx_label_contact_check: "" if the contacts of n_objects labels on H x W at this reach are accepted, else the reason.  Host only."""
+    buf = ctypes.create_string_buffer(256)
+    rc = load().umx_label_contact_check(int(H), int(W), int(n_objects), int(reach), buf, len(buf))
+    return "" if rc == 0 else buf.value.decode()
+
+
+def contact_degrees(records: np.ndarray, N: int):
+    """Step 24 of DESIGN.md section 8.1, stated here once: LABEL_CONTACT_DTYPE records [M] of labels 1..N -> (degree, shared_edges),
+    both int64 [N]: entry j - 1 is the number of contacts label j takes part in and the sum of their edges.  With the shape table's
+    perimeter_edges, shared_edges / perimeter_edges is the share of an object's outline that is in contact."""
+    rec = np.asarray(records)
+    a, b = rec["a"].astype(np.int64), rec["b"].astype(np.int64)
+    if len(rec) and (a.min() < 1 or b.max() > N or (a >= b).any()):
+        raise ValueError("records that are no contact list of %d labels: 1 <= a < b <= N does not hold" % N)
+    both = np.concatenate([a, b]) - 1
+    degree = np.bincount(both, minlength=int(N)).astype(np.int64)
+    shared = np.zeros(int(N), np.int64)
+    np.add.at(shared, both, np.tile(rec["edges"].astype(np.int64), 2))
+    return degree, shared
+
+
 class Labeler:
     """One umx_labeler: the label mask (include/umx.h) of uint8 probability stacks on one MI355X.  It needs no
     model; its device buffers grow on demand and are kept between runs."""
@@ -811,6 +864,8 @@ class Labeler:
         self._split_counts = None
         self._flood_counts = None
         self._last_shape = (1, 1)                                  # H, W of the last run: what shape() names when not told
+        self._contacts_room = 1024                                 # records the next contacts call offers: the last list's length
+        self._contacts_reruns_before = 0                           # reruns of a first pass that was offered too little room
 
     def close(self) -> None:
         if getattr(self, "_lb", None) and self._lb.value:
@@ -982,6 +1037,54 @@ class Labeler:
         v = [ctypes.c_double() for _ in range(2)]
         self._check(self._L.umx_labeler_shape_last_ms(self._lb, *[ctypes.byref(x) for x in v]))
         return tuple(x.value for x in v)
+
+
+    def _contacts(self, call) -> np.ndarray:
+        """call(out_ptr, cap, m_ref) -> rc.  The length of the list is known only after the pass over the plane: the call offers room
+        for as many records as the last list had and, when the library refuses that as too little, once more what it asked for
+        (contacts_stats() then counts the reruns of both passes; contacts_last_ms() is the second one's)."""
+        m = ctypes.c_int64(-1)
+        out = np.zeros(self._contacts_room, LABEL_CONTACT_DTYPE)
+        self._contacts_reruns_before = 0
+        rc = call(out.ctypes.data, out.size, ctypes.byref(m))
+        if rc == ERR_INVALID and m.value > out.size:
+            self._contacts_reruns_before = self.contacts_stats()["reruns"]
+            out = np.zeros(m.value, LABEL_CONTACT_DTYPE)
+            rc = call(out.ctypes.data, out.size, ctypes.byref(m))
+        self._check(rc)
+        self._contacts_room = max(1024, int(m.value))
+        return out[:m.value].copy()
+
+    def contacts(self, reach: int = 0, H: Optional[int] = None, W: Optional[int] = None) -> np.ndarray:
+        """umx_labeler_contacts: which objects of the labels the last run(want_labels=True) left on the device -- plain, grown, split
+        or flooded -- touch: LABEL_CONTACT_DTYPE [M] sorted by (a, b), a < b, ``edges`` the pixel edges they share (4-neighbours).
+        reach R > 0: on a scratch copy grown R levels over every unlabelled pixel, so that objects up to about 2 R apart with
+        nothing between them count as neighbours; the resident labels are untouched.  H, W: as shape()."""
+        H, W = (self._last_shape[0] if H is None else H), (self._last_shape[1] if W is None else W)
+        return self._contacts(lambda out, cap, m: self._L.umx_labeler_contacts(self._lb, int(H), int(W), int(reach), out, cap, m))
+
+    def contacts_ptr(self, labels_ptr: int, n_objects: int, H: int, W: int, reach: int = 0) -> np.ndarray:
+        """umx_labeler_contacts_dev on a DEVICE address (e.g. torch.Tensor.data_ptr()): int32 [H, W] labels with objects 1..n_objects,
+        complete and only read -> LABEL_CONTACT_DTYPE [M].  Needs no prior run."""
+        why = label_contact_check(H, W, n_objects, reach)          # (before any buffer is sized from the arguments)
+        if why:
+            raise UmxError(ERR_INVALID, why)
+        return self._contacts(lambda out, cap, m: self._L.umx_labeler_contacts_dev(self._lb, ctypes.c_void_p(labels_ptr), int(n_objects),
+                                                                                     int(H), int(W), int(reach), out, cap, m))
+
+    def contacts_last_ms(self):
+        """(kernel, download) milliseconds of the last contacts call."""
+        v = [ctypes.c_double() for _ in range(2)]
+        self._check(self._L.umx_labeler_contacts_last_ms(self._lb, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def contacts_stats(self) -> dict:
+        """umx_labeler_contacts_last_stats: table_capacity (entries), reruns (passes repeated with the table doubled), longest_row
+        (the most contacts (a, .) of one label a) and ordered_by ("device", "host", or "none" for an empty list) of the last call."""
+        st = _LabelContactStats()
+        self._check(self._L.umx_labeler_contacts_last_stats(self._lb, ctypes.byref(st)))
+        return {"table_capacity": int(st.table_capacity), "reruns": int(st.reruns) + self._contacts_reruns_before, "longest_row": int(st.longest_row),
+                "ordered_by": {CONTACT_ORDER_NONE: "none", CONTACT_ORDER_DEVICE: "device", CONTACT_ORDER_HOST: "host"}[st.ordered_by]}
 
 
 class Engine:
