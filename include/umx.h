@@ -491,6 +491,66 @@ UMX_API int umx_labeler_contacts_last_ms(const umx_labeler* lb, double* kernel_m
 UMX_API int umx_labeler_contacts_last_stats(const umx_labeler* lb, umx_label_contact_stats* stats);
 
 /*
+ * The convex hull of every labelled object, and with it solidity and the Feret diameters (the
+ * definition is the project's own).  From labels int32 [H][W] with objects 1..N -- a value < 0 or > N counts as 0 and is never used
+ * as an index; a label need not be connected and need not occur.  Pixel (y, x) is the closed unit square [y, y + 1] x [x, x + 1];
+ * its four corners are lattice points with 0 <= y <= H and 0 <= x <= W, and every coordinate below is on that corner lattice.
+ *   25. hull(j) is the convex hull of the squares of all pixels with label j.  It is never degenerate: one pixel gives the unit
+ *       square.  Its vertices are the strictly convex corners only (collinear points are dropped), listed from the vertex with the
+ *       smallest (y, x) in the direction in which sum_i (x_i * y_{i+1} - x_{i+1} * y_i) is positive: the second vertex is the other
+ *       end of the top edge, with the same y and a larger x.
+ *   26. one umx_label_hull per label, record j - 1.  A label no pixel carries gives zeros in every field but `first`, which is the
+ *       running offset: first[j] = the sum of n_vertices of all labels below j, for every record.
+ *   27. the vertex list: all hulls one after the other in label order, V umx_label_hull_vertex in all.
+ *   28. hull area, solidity (area over hull area), the Feret diameters and the hull's perimeter are host arithmetic in float64 on
+ *       these integers, stated once in unmicst_amd/umx.py hull_descriptors (DESIGN.md has the formulas).
+ * Limits: 1 <= H, W <= 65536, H * W <= 2^31 - 1, 0 <= n_objects <= 2^31 - 1.  Then a coordinate is at most 2^16, a squared distance
+ * at most 2^33, every cross-product term at most 2^32 (formed in 64 bits) and area2 at most 2^32.  A second limit is known only after
+ * the first pass: E, the sum over the labels of ymax - ymin + 1 (the rows of their boxes), is at most the number of object pixels
+ * for 4-connected objects but reaches N * H for labels in far-apart pieces; above UMX_HULL_MAX_ROWS the call is refused with
+ * UMX_ERR_OOM and a message, before anything is allocated for it, and the resident labels are kept.
+ * Everything is an integer and both lists are canonical: two calls give the same bytes, in whatever order threads and atomics run.
+ * The device side: one wave per row for each label's row range (atomicMin / atomicMax of y per row run), a 64-bit prefix sum of the
+ * heights (E comes back to the host), one wave per row again for the least x and the largest x + 1 of each label in each row of its
+ * box (8 bytes a row), one wave per object for the hull (a gift wrap by wave reductions on 64-bit cross products, down the right
+ * chain and up the left one; the vertices into a scratch area of 2 * rows + 2 places an object, a bound that is attained), a
+ * prefix sum of the vertex counts (V comes back) and one wave per object again to compact the vertices into the list.
+ */
+typedef struct umx_label_hull {
+    int64_t area2;           /* twice the hull's area: the shoelace sum of step 25, an integer */
+    int64_t feret_max_sq;    /* the largest squared distance between two hull vertices */
+    int64_t first;           /* index of the label's first vertex in the vertex list */
+    int32_t n_vertices;      /* hull vertices, 0 or >= 4 */
+    int32_t rows;            /* image rows in which the label has at least one pixel */
+} umx_label_hull;            /* 32 bytes */
+typedef struct umx_label_hull_vertex {
+    int32_t y, x;            /* a corner: 0 <= y <= H, 0 <= x <= W */
+} umx_label_hull_vertex;     /* 8 bytes */
+/* The largest side of a plane whose hulls are taken, and the largest E (above). */
+#define UMX_HULL_MAX_SIDE 65536
+#define UMX_HULL_MAX_ROWS 268435456
+/* Host only, no device: 1 <= H, W <= 65536; H * W <= 2^31 - 1; 0 <= n_objects <= 2^31 - 1.  UMX_OK, or UMX_ERR_INVALID with the
+ * reason in msg (cap bytes; may be NULL). */
+UMX_API int umx_label_hull_check(int H, int W, int64_t n_objects, char* msg, size_t cap);
+/* The hulls of the labels of the last successful host run that was given a label plane (plain, grown, split or flooded): they are
+ * still on the device.  N records into out (cap: its records) and N into *n, V vertices into verts (vcap: its entries) and V into
+ * *v; n and v may be NULL.  out NULL with cap 0 and verts NULL with vcap 0: only N and V.  Refusals as umx_labeler_shape's
+ * (UMX_ERR_INVALID, nothing touched, the labeler usable, the resident labels kept): no such run, a later run without a label plane
+ * or on device pointers or a failed one, H or W other than that run's, cap < N; and vcap < V, with V stored in *v (V is known only
+ * after the passes: the device has worked, out and verts are untouched); and E > UMX_HULL_MAX_ROWS (UMX_ERR_OOM).  Synchronous:
+ * returns with the stream idle, and under UMX_DEBUG_GUARD ends in the check of the red zones.  All device memory is the labeler's
+ * arena's, grown on demand and kept. */
+UMX_API int umx_labeler_hull(umx_labeler* lb, int H, int W, umx_label_hull* out, int64_t cap, int64_t* n, umx_label_hull_vertex* verts,
+                             int64_t vcap, int64_t* v);
+/* The same on a DEVICE pointer of the labeler's device: labels_dev int32 [H][W] with objects 1..n_objects, complete when the call is
+ * made and only read.  Needs no prior run and leaves the resident labels alone.  n_objects records into out_host (cap >= that). */
+UMX_API int umx_labeler_hull_dev(umx_labeler* lb, const int32_t* labels_dev, int64_t n_objects, int H, int W, umx_label_hull* out_host,
+                                 int64_t cap, umx_label_hull_vertex* verts_host, int64_t vcap, int64_t* v);
+/* Milliseconds of the last hull call: its launches (the two host synchronisations for E and V among them), the download of the
+ * records and the vertices.  Either may be NULL. */
+UMX_API int umx_labeler_hull_last_ms(const umx_labeler* lb, double* kernel_ms, double* download_ms);
+
+/*
  * Splitting touching nuclei at their necks by erosion cores (the definition is the project's
  * own).  Two nuclei are separate objects only where an unbroken line of another class lies between them; where that line has a gap
  * the labelling joins them.  With a depth D, a minimum core area C and a regrow bound L, on top of the options of a labelling run:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time the label mask (umx_labeler_run) on synthetic H x W stacks of K = 3 uint8 planes (GPU box); one JSON
 line.  usage: bench_label.py [H=16384] [W=H] [--reps 3] [--grow R] [--measure C [--measure-dtype u8|u16]] [--split D [--split-core C]]
-       [--flood P [--flood-step Q]] [--shape [--no-host]]
+       [--flood P [--flood-step Q]] [--shape [--no-host]] [--contacts [--reach R] [--no-host]] [--hull [--no-host]]
 
 Two inputs, both made here by pure-numpy recipes (no scipy in the generators, nothing from tests/):
   blobs  nuclei-like discs: the image is cut into 32 x 32 cells; a seeded draw keeps 60 % of them, and each kept cell gets one disc of
@@ -33,7 +33,13 @@ DESIGN.md section 8.1 steps 16 to 18): the kernel and download milliseconds umx_
 kernel time, after one warm-up), beside them the one-plane uint16 measurement of the same labels (the yardstick: it reads the same
 label plane once and 2 bytes a pixel more), the bytes the shape launch moves at most and at least, and the seconds numpy / scipy take
 for the same table on this box's CPU share: five weighted np.bincount passes for the moments, band by band, and the window counts
-object by object on scipy.ndimage.find_objects' boxes."""
+object by object on scipy.ndimage.find_objects' boxes.
+--hull: the blobs input alone, labelled with its label plane kept on the device, then the hulls of its objects (umx_labeler_hull,
+DESIGN.md section 8.1 steps 25 to 28): the kernel and download milliseconds umx_labeler_hull_last_ms reports (the best of --reps by
+kernel time, after one warm-up that also grows the buffers and learns V), beside them the shape call on the same labels in the same
+process (the yardstick of DESIGN.md's expectation), E (the rows of all boxes, from the object table) and V, and the seconds numpy / scipy
+take for the same hulls on this box's CPU share: scipy.spatial.ConvexHull over the corners of every object's boundary pixels, object by
+object on scipy.ndimage.find_objects' boxes, its area held to area2 / 2 and its vertex count to n_vertices."""
 import argparse
 import json
 import os
@@ -286,6 +292,60 @@ def shape_bench(a, H, W):
             "numpy_scipy_s": None if cpu_s is None else round(cpu_s, 3)}
 
 
+def host_hulls(labels, N):
+    """the same hulls by numpy / scipy -> (area float64 [N], n_vertices int64 [N]): Qhull over the corners of the boundary pixels"""
+    from scipy import ndimage
+    from scipy.spatial import ConvexHull
+    area, count = np.zeros(N), np.zeros(N, np.int64)
+    for j, box in enumerate(ndimage.find_objects(labels, max_label=N)):
+        if box is None:
+            continue
+        m = np.pad(labels[box] == j + 1, 1)
+        inner = m[1:-1, 1:-1] & m[:-2, 1:-1] & m[2:, 1:-1] & m[1:-1, :-2] & m[1:-1, 2:]
+        ys, xs = np.nonzero(m[1:-1, 1:-1] & ~inner)
+        pts = np.unique(np.concatenate([np.stack([ys + dy, xs + dx], 1) for dy in (0, 1) for dx in (0, 1)]), axis=0)
+        q = ConvexHull(pts)
+        area[j], count[j] = q.volume, len(q.vertices)
+    return area, count
+
+
+def hull_bench(a, H, W):
+    with umx.Labeler(a.device) as lb:
+        planes = planes_of(blob_mask(H, W))
+        labels, objects = lb.run(planes)
+        label_ms = lb.last_ms()
+        del planes
+        N = len(objects)
+        rec, verts = lb.hull()
+        first_ms = lb.hull_last_ms()
+        best = None
+        for _ in range(a.reps):
+            again = lb.hull()
+            ms = lb.hull_last_ms()
+            if best is None or ms[0] < best[0]:
+                best = ms
+        assert again[0].tobytes() == rec.tobytes() and again[1].tobytes() == verts.tobytes()
+        _, shape_ms = best_shape_ms(lb, a.reps)
+    E = int((objects["y1"].astype(np.int64) - objects["y0"] + 1).sum())
+    assert int(rec["rows"].sum()) == E and (2 * objects["area"].astype(np.int64) <= rec["area2"]).all()
+    cpu_s = None
+    if not a.no_host:
+        t = time.perf_counter()
+        area, count = host_hulls(labels, N)
+        cpu_s = time.perf_counter() - t
+        assert np.array_equal(count, rec["n_vertices"]) and np.allclose(area, rec["area2"] / 2.0, rtol=1e-9, atol=0.0)
+    solidity = objects["area"] / (rec["area2"] / 2.0)
+    return {"hull": True, "objects": N, "object_pixels": int(objects["area"].sum()), "E": E, "V": len(verts),
+            "most_vertices": int(rec["n_vertices"].max()) if N else 0, "mean_solidity": round(float(solidity.mean()), 4) if N else None,
+            "label_kernel_ms": round(label_ms[1], 3), "kernel_ms": round(best[0], 3), "download_ms": round(best[1], 3),
+            "first_call_kernel_ms": round(first_ms[0], 3), "shape_kernel_ms": round(shape_ms[0], 3),
+            "ratio_to_shape": round(best[0] / shape_ms[0], 3),
+            # every label word twice from memory (the two row passes); the row entries cleared, added to and read; the scratch vertices
+            # written and read; the records and the list written
+            "read_bytes_labels": 8 * H * W, "row_entry_bytes": 8 * E, "scratch_bytes": 16 * (E + N), "record_bytes": 32 * N, "vertex_bytes": 8 * len(verts),
+            "numpy_scipy_s": None if cpu_s is None else round(cpu_s, 3)}
+
+
 def host_contacts(labels, reach=0, band=1024):
     """the same list by numpy -> (a, b, edges), int64 [M] each: every horizontal and vertical neighbour pair of two different labels,
     counted by np.unique; a reach first grows the labels level by level over the unlabelled pixels (the least labelled 4-neighbour)"""
@@ -357,12 +417,16 @@ def main():
     ap.add_argument("--flood-step", dest="flood_step", type=int, default=umx.FLOOD_DEFAULT_STEP, metavar="Q")
     ap.add_argument("--measure-dtype", dest="measure_dtype", choices=("u8", "u16"), default="u16")
     ap.add_argument("--shape", action="store_true")
-    ap.add_argument("--no-host", dest="no_host", action="store_true", help="with --shape / --contacts: leave the numpy / scipy figure out (a traced run)")
+    ap.add_argument("--no-host", dest="no_host", action="store_true", help="with --shape / --contacts / --hull: leave the numpy / scipy figure out (a traced run)")
     ap.add_argument("--contacts", action="store_true", help="the contacts of the grown-blobs input (--grow R, default the rim)")
     ap.add_argument("--reach", type=int, default=0, metavar="R", help="with --contacts: the reach")
+    ap.add_argument("--hull", action="store_true", help="the hulls of the blobs input")
     a = ap.parse_args()
     H, W = a.H, a.W or a.H
     out = {"tool": "bench_label", "H": H, "W": W, "K": 3, "min_area": 1, "reps": a.reps}
+    if a.hull:
+        print(json.dumps(dict(out, **hull_bench(a, H, W))))
+        return
     if a.contacts:
         print(json.dumps(dict(out, **contacts_bench(a, H, W))))
         return

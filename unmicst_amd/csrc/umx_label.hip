@@ -1090,6 +1090,7 @@ int ensure_buffers(umx_labeler* lb, size_t plane_bytes, size_t npix, size_t nblo
     lb->d_mplanes = nullptr; lb->d_mrec = nullptr; lb->mplanes_cap = lb->mrec_cap = 0;   // (the measurement allocates its own again)
     lb->d_srec = nullptr; lb->srec_cap = 0;                                              // (and so do the shapes)
     contact_buffers_forget(lb);                                                          // (and the contacts)
+    hull_buffers_forget(lb);                                                             // (and the hulls)
     const size_t pb = std::max(plane_bytes, lb->planes_cap), px = std::max(npix, lb->pix_cap), nb = std::max(nblocks, lb->counts_cap);
     const size_t tc = std::max<size_t>(lb->table_cap, 1024);
     const size_t sp = std::max(split_need, lb->split_cap);

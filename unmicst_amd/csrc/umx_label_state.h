@@ -1,5 +1,5 @@
-// libumx label mask: the labeler's state and the few host pieces that its two sources share -- umx_label.hip (labelling, growth,
-// split, flood, measurement, shapes) and umx_label_contact.hip (contacts).  Nothing here is part of the C ABI (include/umx.h).
+// libumx label mask: the labeler's state and the few host pieces that its three sources share -- umx_label.hip (labelling, growth,
+// split, flood, measurement, shapes), umx_label_contact.hip (contacts) and umx_label_hull.hip (hulls).  Nothing here is part of the C ABI (include/umx.h).
 #pragma once
 
 #include "umx_internal.h"
@@ -46,6 +46,16 @@ struct umx_labeler {
     size_t ctable = 0;                                         // entries the next pass starts with (0: the least)
     double cms[2] = {0.0, 0.0};                                // launches | download
     umx_label_contact_stats cstats = {0, 0, 0, 0, 0};
+    // the hulls' own allocations, as the measurement's (umx_label_hull.hip): the row range of every label (ymin [N] | ymax [N]), the
+    // 64-bit words (an offset per label, a sum per block of labels, the words the host reads), the row entries (least x [E] | largest
+    // x + 1 [E]), the scratch vertices, the records and the vertex list
+    int* d_hrange = nullptr;                 size_t hrange_cap = 0;    // words
+    long long* d_hoff = nullptr;             size_t hoff_cap = 0;      // words
+    int* d_hrows = nullptr;                  size_t hrows_cap = 0;     // words
+    umx_label_hull_vertex* d_hscratch = nullptr;  size_t hscratch_cap = 0;   // vertices
+    umx_label_hull* d_hrec = nullptr;        size_t hrec_cap = 0;      // records
+    umx_label_hull_vertex* d_hverts = nullptr;    size_t hverts_cap = 0;     // vertices
+    double hms[2] = {0.0, 0.0};                                // launches | download
     std::string err;
 };
 
@@ -80,6 +90,12 @@ inline void contact_buffers_forget(umx_labeler* lb) {
     lb->d_ckeys = nullptr; lb->d_cedges = nullptr; lb->d_crows = nullptr; lb->d_crec = nullptr; lb->d_cwords = nullptr;
     lb->d_cplane[0] = lb->d_cplane[1] = nullptr;
     lb->ckeys_cap = lb->cedges_cap = lb->crows_cap = lb->crec_cap = lb->cwords_cap = lb->cplane_cap[0] = lb->cplane_cap[1] = 0;
+}
+
+// and so are the hulls'
+inline void hull_buffers_forget(umx_labeler* lb) {
+    lb->d_hrange = nullptr; lb->d_hoff = nullptr; lb->d_hrows = nullptr; lb->d_hscratch = nullptr; lb->d_hrec = nullptr; lb->d_hverts = nullptr;
+    lb->hrange_cap = lb->hoff_cap = lb->hrows_cap = lb->hscratch_cap = lb->hrec_cap = lb->hverts_cap = 0;
 }
 
 // Launches of kernels that live in umx_label.hip, for umx_label_contact.hip.

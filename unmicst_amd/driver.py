@@ -130,6 +130,12 @@ def build_parser(spec: ToolSpec) -> argparse.ArgumentParser:
     p.add_argument("--labelNeighborsReach", dest="labelNeighborsReach", type=int, default=None, metavar="R",
                    help="with --labelNeighbors: objects also count as neighbours when fronts grown R pixels (0..255, default 0) from them "
                         "over the unlabelled pixels meet; the label mask itself is not changed")
+    # the convex hull of every labelled object: <stem>_Hulls_<suffix>.csv
+    p.add_argument("--labelHull", dest="labelHull", action="store_true",
+                   help="also write convex-hull area, solidity, largest and least Feret diameter and hull perimeter of every labelled "
+                        "object (the grown or split ones with --labelGrow / --labelSplit)")
+    p.add_argument("--labelHullVertices", dest="labelHullVertices", action="store_true",
+                   help="with --labelHull: also write the hulls' vertices, corners of the pixel squares (<stem>_HullVertices_<suffix>.csv)")
     return p
 
 
@@ -142,7 +148,8 @@ def check_label_args(parser: argparse.ArgumentParser, args) -> None:
                         ("--labelSplitRegrow", args.labelSplitRegrow), ("--labelShape", args.labelShape or None),
                         ("--labelFlood", args.labelFlood), ("--labelFloodStep", args.labelFloodStep),
                         ("--labelFloodInvert", args.labelFloodInvert or None), ("--labelNeighbors", args.labelNeighbors or None),
-                        ("--labelNeighborsReach", args.labelNeighborsReach)):
+                        ("--labelNeighborsReach", args.labelNeighborsReach), ("--labelHull", args.labelHull or None),
+                        ("--labelHullVertices", args.labelHullVertices or None)):
             if v is not None:
                 parser.error("%s needs --labelMask" % flag)
         return
@@ -178,6 +185,8 @@ def check_label_args(parser: argparse.ArgumentParser, args) -> None:
         parser.error("--labelNeighborsReach needs --labelNeighbors")
     if args.labelNeighborsReach is not None and not 0 <= args.labelNeighborsReach <= 255:
         parser.error("--labelNeighborsReach %d: it must be 0..255 pixels" % args.labelNeighborsReach)
+    if args.labelHullVertices and not args.labelHull:
+        parser.error("--labelHullVertices needs --labelHull")
     for k in args.labelGrowClasses or ():
         if k < 0:
             parser.error("--labelGrowClasses %d: classes are numbered from 0" % k)
@@ -261,6 +270,34 @@ def write_neighbors_csv(path: str, contacts) -> None:
     with open(path, "w") as f:
         f.write(",".join(NEIGHBOR_COLUMNS) + "\n")
         f.writelines("%d,%d,%d\n" % row for row in zip(contacts["a"].tolist(), contacts["b"].tolist(), contacts["edges"].tolist()))
+
+
+HULL_COLUMNS = ("label", "hull_area", "solidity", "feret_max", "feret_min", "hull_perimeter", "n_vertices")
+HULL_VERTEX_COLUMNS = ("label", "index", "y", "x")
+
+
+def write_hulls_csv(path: str, objects, records, vertices) -> None:
+    """HULL_COLUMNS -- one line per object, label order.  records, vertices: umx.LABEL_HULL_DTYPE [N] and umx.LABEL_HULL_VERTEX_DTYPE
+    [V], turned into the columns by umx.hull_descriptors alone with the table's areas.  Every object of the table must have a hull
+    and no hull fewer pixels' worth of area than the object.  The floats are written with repr, as in the Shapes file."""
+    from . import umx as _umx
+    if len(records) != len(objects) or (records["n_vertices"] < 4).any() or (2 * objects["area"].astype(np.int64) > records["area2"]).any():
+        raise AssertionError("the hulls are not those of the label table's objects")
+    d = _umx.hull_descriptors(records, vertices, objects["area"])
+    cols = [range(1, len(objects) + 1)] + [d[n].tolist() for n in HULL_COLUMNS[1:]]
+    with open(path, "w") as f:
+        f.write(",".join(HULL_COLUMNS) + "\n")
+        f.writelines("%d,%r,%r,%r,%r,%r,%d\n" % row for row in zip(*cols))
+
+
+def write_hull_vertices_csv(path: str, records, vertices) -> None:
+    """HULL_VERTEX_COLUMNS -- one line per hull vertex, label order and inside a label the list's order (index from 0): corners of
+    the pixel squares, 0 <= y <= H and 0 <= x <= W."""
+    label = np.repeat(np.arange(1, len(records) + 1), records["n_vertices"])
+    index = np.arange(len(vertices)) - np.repeat(records["first"], records["n_vertices"])
+    with open(path, "w") as f:
+        f.write(",".join(HULL_VERTEX_COLUMNS) + "\n")
+        f.writelines("%d,%d,%d,%d\n" % row for row in zip(label.tolist(), index.tolist(), vertices["y"].tolist(), vertices["x"].tolist()))
 
 
 def measure_pages(labeler, path: str, pages, shape) -> list:
@@ -563,6 +600,12 @@ def run(tool: str, argv=None, script_dir: str = None) -> int:
                     print("Label neighbors: %d contacts, largest degree %d" % (len(contacts), int(degree.max()) if len(degree) else 0))
                     st.note("label_neighbors", dict(labeler.contacts_stats(), contacts=len(contacts)))
                     st.mark("neighbors")
+                if args.labelHull:
+                    hulls, hull_vertices = labeler.hull()
+                    write_hulls_csv(out_dir + "//" + stem + "_Hulls_" + suffix + ".csv", objects, hulls, hull_vertices)
+                    if args.labelHullVertices:
+                        write_hull_vertices_csv(out_dir + "//" + stem + "_HullVertices_" + suffix + ".csv", hulls, hull_vertices)
+                    st.mark("hull")
     finally:
         if args.compat_per_class:
             UNet2D.reuse_pass = reuse_before

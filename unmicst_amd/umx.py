@@ -6,6 +6,7 @@ raise, they never route to a CPU path.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from typing import List, Optional
 
@@ -41,6 +42,7 @@ EXPORTS = [
     "umx_label_shape_check", "umx_labeler_shape", "umx_labeler_shape_dev", "umx_labeler_shape_last_ms",
     "umx_label_contact_check", "umx_labeler_contacts", "umx_labeler_contacts_dev", "umx_labeler_contacts_last_ms",
     "umx_labeler_contacts_last_stats",
+    "umx_label_hull_check", "umx_labeler_hull", "umx_labeler_hull_dev", "umx_labeler_hull_last_ms",
 ]
 
 # the label mask's limits and the geometry of its kernels (the UMX_LABEL_* macros of include/umx.h; tests/test_label_cpu.py compares)
@@ -161,6 +163,23 @@ LABEL_CONTACT_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("edges", "<u4"), ("
 # the UMX_CONTACT_* macros of include/umx.h (tests/test_label_contacts_cpu.py compares)
 CONTACT_MAX_REACH, CONTACT_TABLE_MIN, CONTACT_TABLE_MAX, CONTACT_PROBE_MAX, CONTACT_DEVICE_SORT_MAX = 255, 65536, 268435456, 1024, 1024
 CONTACT_ORDER_NONE, CONTACT_ORDER_DEVICE, CONTACT_ORDER_HOST = 0, 1, 2
+
+
+class LabelHull(ctypes.Structure):
+    """umx_label_hull: 32 bytes"""
+    _fields_ = [("area2", ctypes.c_int64), ("feret_max_sq", ctypes.c_int64), ("first", ctypes.c_int64), ("n_vertices", ctypes.c_int32),
+                ("rows", ctypes.c_int32)]
+
+
+class LabelHullVertex(ctypes.Structure):
+    """umx_label_hull_vertex: 8 bytes"""
+    _fields_ = [("y", ctypes.c_int32), ("x", ctypes.c_int32)]
+
+
+# the same records as numpy dtypes: what Labeler.hull returns, [N] and [V]; the descriptors are hull_descriptors'
+LABEL_HULL_DTYPE = np.dtype([("area2", "<i8"), ("feret_max_sq", "<i8"), ("first", "<i8"), ("n_vertices", "<i4"), ("rows", "<i4")])
+LABEL_HULL_VERTEX_DTYPE = np.dtype([("y", "<i4"), ("x", "<i4")])
+HULL_MAX_SIDE, HULL_MAX_ROWS = 65536, 268435456                # UMX_HULL_* (tests/test_label_hull_cpu.py compares)
 
 
 _SEND_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p)
@@ -379,6 +398,16 @@ def load(path: Optional[str] = None):
     L.umx_labeler_contacts_last_ms.argtypes = [c_void_p] + [ctypes.POINTER(c_double)] * 2
     L.umx_labeler_contacts_last_stats.restype = c_int
     L.umx_labeler_contacts_last_stats.argtypes = [c_void_p, ctypes.POINTER(_LabelContactStats)]
+    L.umx_label_hull_check.restype = c_int
+    L.umx_label_hull_check.argtypes = [c_int, c_int, ctypes.c_int64, ctypes.c_char_p, ctypes.c_size_t]
+    L.umx_labeler_hull.restype = c_int
+    L.umx_labeler_hull.argtypes = [c_void_p, c_int, c_int, c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), c_void_p, ctypes.c_int64,
+                                   ctypes.POINTER(ctypes.c_int64)]
+    L.umx_labeler_hull_dev.restype = c_int
+    L.umx_labeler_hull_dev.argtypes = [c_void_p, c_void_p, ctypes.c_int64, c_int, c_int, c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64,
+                                       ctypes.POINTER(ctypes.c_int64)]
+    L.umx_labeler_hull_last_ms.restype = c_int
+    L.umx_labeler_hull_last_ms.argtypes = [c_void_p] + [ctypes.POINTER(c_double)] * 2
     L.umx_prof_entry_size.restype = c_int
     if L.umx_prof_entry_size() != ctypes.sizeof(ProfEntry):
         raise RuntimeError("libumx (%s) lays umx_prof_entry out in %d bytes, this binding in %d: mixed builds" % (
@@ -850,6 +879,68 @@ def contact_degrees(records: np.ndarray, N: int):
     return degree, shared
 
 
+def label_hull_check(H: int, W: int, n_objects: int = 0) -> str:
+    """umx_label_hull_check: "" if the hulls of n_objects labels on H x W are accepted, else the reason.  Host only."""
+    buf = ctypes.create_string_buffer(256)
+    rc = load().umx_label_hull_check(int(H), int(W), int(n_objects), buf, len(buf))
+    return "" if rc == 0 else buf.value.decode()
+
+
+HULL_DESCRIPTORS = ("hull_area", "solidity", "feret_max", "feret_min", "hull_perimeter", "n_vertices")
+
+
+def hull_feret_min_sq(y, x):
+    """The square of the least width of one hull as an exact rational (numerator, denominator) of Python integers: the minimum over
+    the hull's edges e of max_k cross(e, v_k - e_0)^2 / |e|^2.  y, x: the hull's vertices in list order, at least 3.  The largest
+    cross product of an edge is taken in int64 (it is at most 2^33); the squares and the comparison of two edges' quotients -- by
+    cross-multiplication -- are Python integers."""
+    y, x = np.asarray(y, np.int64), np.asarray(x, np.int64)
+    n = len(y)
+    ey, ex = np.roll(y, -1) - y, np.roll(x, -1) - x
+    best = None
+    step = max(1, (1 << 20) // n)                               # edges per round: bounds the n x step temporaries
+    for i0 in range(0, n, step):
+        s = slice(i0, i0 + step)
+        cross = ex[s, None] * (y[None, :] - y[s, None]) - ey[s, None] * (x[None, :] - x[s, None])
+        widest = np.abs(cross).max(axis=1)
+        for c, dy, dx in zip(widest.tolist(), ey[s].tolist(), ex[s].tolist()):
+            num, den = c * c, dy * dy + dx * dx
+            if best is None or num * best[1] < best[0] * den:
+                best = (num, den)
+    return best
+
+
+def hull_descriptors(records: np.ndarray, vertices: np.ndarray, area) -> dict:
+    """Step 28 of DESIGN.md section 8.1, stated here once: LABEL_HULL_DTYPE records [N], LABEL_HULL_VERTEX_DTYPE vertices [V] and the
+    objects' pixel counts [N] (the label table's or the shape table's area) -> {name: array [N]} for HULL_DESCRIPTORS, float64 but
+    n_vertices (int64).  hull_area = area2 / 2; solidity = area / hull_area, at most 1 and 1 exactly for a full rectangle; feret_max
+    = sqrt(feret_max_sq); feret_min = the least width of the hull, the minimum over its edges e of max_k cross(e, v_k)^2 / |e|^2
+    chosen exactly (hull_feret_min_sq) and rounded once, by one division and one sqrt; hull_perimeter = the sum of hypot over the
+    edges, added in list order.  A label no pixel carries (n_vertices 0) has 0 in every column."""
+    rec, verts = np.asarray(records), np.asarray(vertices)
+    N = len(rec)
+    area = np.asarray(area).astype(np.float64)
+    if area.shape != (N,):
+        raise ValueError("area has shape %s for %d records" % (area.shape, N))
+    n = rec["n_vertices"].astype(np.int64)
+    first = rec["first"].astype(np.int64)
+    if N and (not np.array_equal(first, np.cumsum(n) - n) or int(n.sum()) != len(verts) or ((n != 0) & (n < 4)).any()):
+        raise ValueError("records and vertices that are no hull table: first is not the running sum of n_vertices over %d vertices" % len(verts))
+    hull_area = rec["area2"].astype(np.float64) / 2.0
+    out = {"hull_area": hull_area, "solidity": np.zeros(N), "feret_max": np.sqrt(rec["feret_max_sq"].astype(np.float64)),
+           "feret_min": np.zeros(N), "hull_perimeter": np.zeros(N), "n_vertices": n}
+    present = n > 0
+    out["solidity"][present] = area[present] / hull_area[present]
+    vy, vx = verts["y"].astype(np.int64), verts["x"].astype(np.int64)
+    for j in np.flatnonzero(present):
+        y, x = vy[first[j]:first[j] + n[j]], vx[first[j]:first[j] + n[j]]
+        num, den = hull_feret_min_sq(y, x)
+        out["feret_min"][j] = math.sqrt(num / den)
+        edges = np.hypot((np.roll(y, -1) - y).astype(np.float64), (np.roll(x, -1) - x).astype(np.float64))
+        out["hull_perimeter"][j] = np.cumsum(edges)[-1]        # (cumsum adds in order; np.sum adds pairwise)
+    return out
+
+
 class Labeler:
     """One umx_labeler: the label mask (include/umx.h) of uint8 probability stacks on one MI355X.  It needs no
     model; its device buffers grow on demand and are kept between runs."""
@@ -866,6 +957,7 @@ class Labeler:
         self._last_shape = (1, 1)                                  # H, W of the last run: what shape() names when not told
         self._contacts_room = 1024                                 # records the next contacts call offers: the last list's length
         self._contacts_reruns_before = 0                           # reruns of a first pass that was offered too little room
+        self._hull_room = (1024, 16384)                            # records and vertices the next hull call offers: the last call's
 
     def close(self) -> None:
         if getattr(self, "_lb", None) and self._lb.value:
@@ -1085,6 +1177,53 @@ class Labeler:
         self._check(self._L.umx_labeler_contacts_last_stats(self._lb, ctypes.byref(st)))
         return {"table_capacity": int(st.table_capacity), "reruns": int(st.reruns) + self._contacts_reruns_before, "longest_row": int(st.longest_row),
                 "ordered_by": {CONTACT_ORDER_NONE: "none", CONTACT_ORDER_DEVICE: "device", CONTACT_ORDER_HOST: "host"}[st.ordered_by]}
+
+    def _hull(self, call, n_known=None):
+        """call(out_ptr, cap, n_ref, verts_ptr, vcap, v_ref) -> rc.  The number of vertices is known only after the passes over the
+        plane, the number of records of hull() only to the library: the call offers the room of the last call and, when the library
+        refuses that as too little, what it asked for (too few records are refused before the device works; hull_last_ms() is the
+        last call's)."""
+        n, v = ctypes.c_int64(-1), ctypes.c_int64(-1)
+        rec = np.zeros(self._hull_room[0] if n_known is None else int(n_known), LABEL_HULL_DTYPE)
+        verts = np.zeros(self._hull_room[1], LABEL_HULL_VERTEX_DTYPE)
+        for _ in range(3):
+            n.value, v.value = -1, -1
+            rc = call(rec.ctypes.data if rec.size else None, rec.size, ctypes.byref(n), verts.ctypes.data if verts.size else None, verts.size,
+                      ctypes.byref(v))
+            if rc == ERR_INVALID and n.value > rec.size:
+                rec = np.zeros(n.value, LABEL_HULL_DTYPE)
+            elif rc == ERR_INVALID and v.value > verts.size:
+                verts = np.zeros(v.value, LABEL_HULL_VERTEX_DTYPE)
+            else:
+                break
+        self._check(rc)
+        N = int(n_known) if n_known is not None else int(n.value)
+        self._hull_room = (max(1024, N), max(16384, int(v.value)))
+        return rec[:N].copy(), verts[:v.value].copy()
+
+    def hull(self, H: Optional[int] = None, W: Optional[int] = None):
+        """umx_labeler_hull: the convex hulls of the labels the last run(want_labels=True) left on the device -- plain, grown, split
+        or flooded -- -> (LABEL_HULL_DTYPE [N], LABEL_HULL_VERTEX_DTYPE [V]): record j - 1 of label j, whose vertices are
+        vertices[first : first + n_vertices], corners of the pixel squares, from the top-left one along the top edge.
+        hull_descriptors turns them into solidity and the Feret diameters.  H, W: as shape()."""
+        H, W = (self._last_shape[0] if H is None else H), (self._last_shape[1] if W is None else W)
+        return self._hull(lambda out, cap, n, verts, vcap, v: self._L.umx_labeler_hull(self._lb, int(H), int(W), out, cap, n, verts, vcap, v))
+
+    def hull_ptr(self, labels_ptr: int, n_objects: int, H: int, W: int):
+        """umx_labeler_hull_dev on a DEVICE address (e.g. torch.Tensor.data_ptr()): int32 [H, W] labels with objects 1..n_objects,
+        complete and only read -> (LABEL_HULL_DTYPE [n_objects], LABEL_HULL_VERTEX_DTYPE [V]).  Needs no prior run."""
+        why = label_hull_check(H, W, n_objects)                    # (before any buffer is sized from the arguments)
+        if why:
+            raise UmxError(ERR_INVALID, why)
+        return self._hull(lambda out, cap, n, verts, vcap, v: self._L.umx_labeler_hull_dev(self._lb, ctypes.c_void_p(labels_ptr), int(n_objects),
+                                                                                             int(H), int(W), out, cap, verts, vcap, v),
+                          n_known=n_objects)
+
+    def hull_last_ms(self):
+        """(kernel, download) milliseconds of the last hull call."""
+        v = [ctypes.c_double() for _ in range(2)]
+        self._check(self._L.umx_labeler_hull_last_ms(self._lb, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
 
 class Engine:
