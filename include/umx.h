@@ -551,6 +551,51 @@ UMX_API int umx_labeler_hull_dev(umx_labeler* lb, const int32_t* labels_dev, int
 UMX_API int umx_labeler_hull_last_ms(const umx_labeler* lb, double* kernel_ms, double* download_ms);
 
 /*
+ * Relabel: drop some objects, merge others, renumber the rest 1..N' without a gap (the
+ * definition is the project's own).  From labels int32 [H][W] with values in 0..N, keep (N bytes, keep[j - 1] != 0 keeps label j; NULL
+ * keeps all) and M pairs of int32 labels (a, b):
+ *   29. classes: the equivalence closure of the pairs on 1..N.  a == b, repeated pairs and (b, a) change nothing; pairs need not
+ *       touch (a merged object may be disconnected).  A pair that names a label outside 1..N, or a label that keep drops, is
+ *       refused, and the message gives the pair's index: a label is dropped or merged, never both.
+ *   30. numbering: a class is kept iff its members are (by 29 it is wholly kept or one dropped label); the kept classes are
+ *       numbered 1..N' in order of their least member; map[0] = 0 and map[j] = the number of j's class, 0 when j is dropped.  The
+ *       order of the least members is kept, so labels in raster order of their first pixel stay so.
+ *   31. labels'(y, x) = map[labels(y, x)]; a value < 0 or > N counts as 0 and is never used as an index (the rule of step 8).
+ *   32. the umx_label_object of a new label is the merge of its members' records: area, sum_y, sum_x added, y0 and x0 by minimum,
+ *       y1 and x1 by maximum -- what step 4 gives on labels'.
+ * Everything is an integer: two calls give the same bytes, whatever the order of the pairs.  keep all with no pair is the identity;
+ * relabel(k2) after relabel(k1) is relabel(k1 & k2[map1]).
+ * Steps 29 and 30 run on the host (a union-find with path compression over the N + 1 words of map), 31 and 32 on the device: the map
+ * is uploaded into an allocation of its own (4 (N + 1) bytes), the new table is a second table buffer that changes places with the
+ * first, and the plane pass looks the map up once per row run, not per pixel.
+ */
+#define UMX_RELABEL_MAX_PAIRS 268435456   /* == UMX_CONTACT_TABLE_MAX: the pairs come from a contacts list */
+/* Host only, no device: H, W >= 1; H * W <= 2^31 - 1; 0 <= n_objects <= 2^31 - 2 (the map has n_objects + 1 int32 words);
+ * 0 <= n_pairs <= UMX_RELABEL_MAX_PAIRS.  UMX_OK, or UMX_ERR_INVALID with the reason in msg (cap bytes; may be NULL). */
+UMX_API int umx_label_relabel_check(int H, int W, int64_t n_objects, int64_t n_pairs, char* msg, size_t cap);
+/* Steps 29 and 30, host only, no device: map (n_objects + 1 words) and *n_new = N'.  keep: n_objects bytes, or NULL for all; pairs:
+ * 2 * n_pairs words.  map NULL: the arguments are only validated and *n_new is not written.  UMX_OK, or UMX_ERR_INVALID with the
+ * reason in msg (a refused call may have written map). */
+UMX_API int umx_label_relabel_map(int64_t n_objects, const uint8_t* keep /* NULL: all */, const int32_t* pairs, int64_t n_pairs,
+                                  int32_t* map /* n_objects + 1 */, int64_t* n_new, char* msg, size_t cap);
+/* On the resident labels (those of the last umx_labeler_run that was given a label plane): edits the label plane and the object
+ * table on the device in place and sets their count to N'; labels_host (may be NULL) receives the new plane, map_host (may be NULL;
+ * N + 1 words) the map.  keep == NULL goes with n_keep == 0; else n_keep must be N.  Synchronous.  Refused (UMX_ERR_INVALID) before
+ * any device work, with the labels, the table and the labeler as they were: no valid resident labels, another H or W, n_keep != N, a
+ * bad pair.  A HIP failure after the first launch leaves the labeler without resident labels.  Afterwards umx_labeler_objects,
+ * _measure, _shape, _contacts and _hull see the new labels and N'; the counts of a split or a flood stay those of the run. */
+UMX_API int umx_labeler_relabel(umx_labeler* lb, int H, int W, const uint8_t* keep, int64_t n_keep, const int32_t* pairs, int64_t n_pairs,
+                                int32_t* labels_host, int32_t* map_host /* may be NULL; N + 1 */, int64_t* n_new);
+/* The same on the caller's DEVICE plane with objects 1..n_objects, complete when the call is made; labels_out_dev may equal
+ * labels_dev.  keep: n_objects bytes or NULL.  No table: the caller remaps its own with the map.  Needs no prior run and leaves the
+ * resident labels alone. */
+UMX_API int umx_labeler_relabel_dev(umx_labeler* lb, const int32_t* labels_dev, int64_t n_objects, int H, int W, const uint8_t* keep,
+                                    const int32_t* pairs, int64_t n_pairs, int32_t* labels_out_dev, int32_t* map_host, int64_t* n_new);
+/* Milliseconds of the last relabel call: the upload of the map, the launches, the download of the plane and the table.  Any may be
+ * NULL. */
+UMX_API int umx_labeler_relabel_last_ms(const umx_labeler* lb, double* upload_ms, double* kernel_ms, double* download_ms);
+
+/*
  * Splitting touching nuclei at their necks by erosion cores (the definition is the project's
  * own).  Two nuclei are separate objects only where an unbroken line of another class lies between them; where that line has a gap
  * the labelling joins them.  With a depth D, a minimum core area C and a regrow bound L, on top of the options of a labelling run:

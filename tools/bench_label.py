@@ -2,6 +2,7 @@
 """Time the label mask (umx_labeler_run) on synthetic H x W stacks of K = 3 uint8 planes (GPU box); one JSON
 line.  usage: bench_label.py [H=16384] [W=H] [--reps 3] [--grow R] [--measure C [--measure-dtype u8|u16]] [--split D [--split-core C]]
        [--flood P [--flood-step Q]] [--shape [--no-host]] [--contacts [--reach R] [--no-host]] [--hull [--no-host]]
+       [--relabel [--no-host]]
 
 Two inputs, both made here by pure-numpy recipes (no scipy in the generators, nothing from tests/):
   blobs  nuclei-like discs: the image is cut into 32 x 32 cells; a seeded draw keeps 60 % of them, and each kept cell gets one disc of
@@ -39,7 +40,13 @@ DESIGN.md section 8.1 steps 25 to 28): the kernel and download milliseconds umx_
 kernel time, after one warm-up that also grows the buffers and learns V), beside them the shape call on the same labels in the same
 process (the yardstick of DESIGN.md's expectation), E (the rows of all boxes, from the object table) and V, and the seconds numpy / scipy
 take for the same hulls on this box's CPU share: scipy.spatial.ConvexHull over the corners of every object's boundary pixels, object by
-object on scipy.ndimage.find_objects' boxes, its area held to area2 / 2 and its vertex count to n_vertices."""
+object on scipy.ndimage.find_objects' boxes, its area held to area2 / 2 and its vertex count to n_vertices.
+--relabel: the blobs input alone, labelled with its label plane kept on the device, then relabelled (umx_labeler_relabel, DESIGN.md
+section 8.1 steps 29 to 32) with a seeded keep that drops about half the objects: the upload, kernel and download milliseconds
+umx_labeler_relabel_last_ms reports (the best of --reps by kernel time; every repetition labels the planes again first, since the call
+edits the resident labels), beside them the labelling call of the same process (the yardstick of DESIGN.md's expectation), the seconds
+umx.relabel_map takes for the map on the host, and the seconds numpy takes for map[labels] on this box's CPU share, held to the device's
+plane.  The host route (relabel_keep, host_relabel) needs no device."""
 import argparse
 import json
 import os
@@ -346,6 +353,62 @@ def hull_bench(a, H, W):
             "numpy_scipy_s": None if cpu_s is None else round(cpu_s, 3)}
 
 
+def relabel_keep(N, seed=5):
+    """uint8 [N]: a seeded draw that keeps about half the objects"""
+    return (np.random.default_rng(seed).random(N) < 0.5).astype(np.uint8)
+
+
+def host_relabel(labels, N, keep):
+    """the same relabel on the host -> (labels', map, N', seconds of umx.relabel_map, seconds of numpy's map[labels])"""
+    t = time.perf_counter()
+    m, n_new = umx.relabel_map(N, keep=keep)
+    map_s = time.perf_counter() - t
+    t = time.perf_counter()
+    out = m[labels]
+    return out, m, n_new, map_s, time.perf_counter() - t
+
+
+def relabel_bench(a, H, W):
+    with umx.Labeler(a.device) as lb:
+        planes = planes_of(blob_mask(H, W))
+        labels, objects = lb.run(planes)
+        N = len(objects)
+        keep = relabel_keep(N)
+        first = lb.relabel(keep=keep)                         # warm-up: allocates the map and the second table
+        first_ms = lb.relabel_last_ms()
+        best = label_ms = None
+        for _ in range(a.reps):
+            lb.run(planes)
+            run_ms = lb.last_ms()
+            again = lb.relabel(keep=keep, want_labels=False)
+            ms = lb.relabel_last_ms()
+            assert again[1].tobytes() == first[1].tobytes() and again[2].tobytes() == first[2].tobytes()
+            if best is None or ms[1] < best[1]:
+                best = ms
+            if label_ms is None or run_ms[1] < label_ms[1]:
+                label_ms = run_ms
+        shapes = lb.shape()                                    # the tables afterwards are those of the new labels
+        assert len(shapes) == len(first[1]) and np.array_equal(umx.shape_descriptors(shapes)["area"], first[1]["area"])
+    del planes
+    new_labels, new_objects, m = first
+    n_new = len(new_objects)
+    assert n_new == int(keep.sum()) and np.array_equal(new_objects["area"], objects["area"][keep != 0])
+    map_s = numpy_s = None
+    if not a.no_host:
+        want, hm, hn, map_s, numpy_s = host_relabel(labels, N, keep)
+        assert hn == n_new and np.array_equal(hm, m) and np.array_equal(want, new_labels)
+        assert umx.relabel_objects(objects, m).tobytes() == new_objects.tobytes()
+    return {"relabel": True, "objects": N, "objects_after": n_new, "object_pixels": int(objects["area"].sum()),
+            "object_pixels_after": int(new_objects["area"].sum()),
+            "label_kernel_ms": round(label_ms[1], 3), "upload_ms": round(best[0], 3), "kernel_ms": round(best[1], 3),
+            "first_call_kernel_ms": round(first_ms[1], 3), "first_call_download_ms": round(first_ms[2], 3),
+            "ratio_to_label": round(best[1] / label_ms[1], 3),
+            # every label word read once; at most every word written (in place only the words that change are); the map up and read;
+            # both tables
+            "read_bytes_labels": 4 * H * W, "write_bytes_upper": 4 * H * W, "map_bytes": 4 * (N + 1), "table_bytes": 40 * (N + n_new),
+            "host_map_s": None if map_s is None else round(map_s, 4), "numpy_remap_s": None if numpy_s is None else round(numpy_s, 3)}
+
+
 def host_contacts(labels, reach=0, band=1024):
     """the same list by numpy -> (a, b, edges), int64 [M] each: every horizontal and vertical neighbour pair of two different labels,
     counted by np.unique; a reach first grows the labels level by level over the unlabelled pixels (the least labelled 4-neighbour)"""
@@ -417,13 +480,17 @@ def main():
     ap.add_argument("--flood-step", dest="flood_step", type=int, default=umx.FLOOD_DEFAULT_STEP, metavar="Q")
     ap.add_argument("--measure-dtype", dest="measure_dtype", choices=("u8", "u16"), default="u16")
     ap.add_argument("--shape", action="store_true")
-    ap.add_argument("--no-host", dest="no_host", action="store_true", help="with --shape / --contacts / --hull: leave the numpy / scipy figure out (a traced run)")
+    ap.add_argument("--no-host", dest="no_host", action="store_true", help="with --shape / --contacts / --hull / --relabel: leave the numpy / scipy figure out (a traced run)")
     ap.add_argument("--contacts", action="store_true", help="the contacts of the grown-blobs input (--grow R, default the rim)")
     ap.add_argument("--reach", type=int, default=0, metavar="R", help="with --contacts: the reach")
     ap.add_argument("--hull", action="store_true", help="the hulls of the blobs input")
+    ap.add_argument("--relabel", action="store_true", help="a relabel of the blobs input that drops about half its objects")
     a = ap.parse_args()
     H, W = a.H, a.W or a.H
     out = {"tool": "bench_label", "H": H, "W": W, "K": 3, "min_area": 1, "reps": a.reps}
+    if a.relabel:
+        print(json.dumps(dict(out, **relabel_bench(a, H, W))))
+        return
     if a.hull:
         print(json.dumps(dict(out, **hull_bench(a, H, W))))
         return

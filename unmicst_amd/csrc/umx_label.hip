@@ -1091,6 +1091,7 @@ int ensure_buffers(umx_labeler* lb, size_t plane_bytes, size_t npix, size_t nblo
     lb->d_srec = nullptr; lb->srec_cap = 0;                                              // (and so do the shapes)
     contact_buffers_forget(lb);                                                          // (and the contacts)
     hull_buffers_forget(lb);                                                             // (and the hulls)
+    relabel_buffers_forget(lb);                                                          // (and the relabel)
     const size_t pb = std::max(plane_bytes, lb->planes_cap), px = std::max(npix, lb->pix_cap), nb = std::max(nblocks, lb->counts_cap);
     const size_t tc = std::max<size_t>(lb->table_cap, 1024);
     const size_t sp = std::max(split_need, lb->split_cap);

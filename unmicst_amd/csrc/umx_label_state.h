@@ -1,5 +1,6 @@
-// libumx label mask: the labeler's state and the few host pieces that its three sources share -- umx_label.hip (labelling, growth,
-// split, flood, measurement, shapes), umx_label_contact.hip (contacts) and umx_label_hull.hip (hulls).  Nothing here is part of the C ABI (include/umx.h).
+// libumx label mask: the labeler's state and the few host pieces that its four sources share -- umx_label.hip (labelling, growth,
+// split, flood, measurement, shapes), umx_label_contact.hip (contacts), umx_label_hull.hip (hulls) and umx_label_relabel.hip
+// (relabel).  Nothing here is part of the C ABI (include/umx.h).
 #pragma once
 
 #include "umx_internal.h"
@@ -56,6 +57,11 @@ struct umx_labeler {
     umx_label_hull* d_hrec = nullptr;        size_t hrec_cap = 0;      // records
     umx_label_hull_vertex* d_hverts = nullptr;    size_t hverts_cap = 0;     // vertices
     double hms[2] = {0.0, 0.0};                                // launches | download
+    // the relabel's own allocations, as the measurement's (umx_label_relabel.hip): the map, and the second object table -- after a
+    // relabel of the resident labels it and d_table have changed places, capacities included
+    int* d_rmap = nullptr;                   size_t rmap_cap = 0;      // words
+    umx_label_object* d_rtable = nullptr;    size_t rtable_cap = 0;    // records
+    double rms[3] = {0.0, 0.0, 0.0};                           // upload | launches | download
     std::string err;
 };
 
@@ -96,6 +102,12 @@ inline void contact_buffers_forget(umx_labeler* lb) {
 inline void hull_buffers_forget(umx_labeler* lb) {
     lb->d_hrange = nullptr; lb->d_hoff = nullptr; lb->d_hrows = nullptr; lb->d_hscratch = nullptr; lb->d_hrec = nullptr; lb->d_hverts = nullptr;
     lb->hrange_cap = lb->hoff_cap = lb->hrows_cap = lb->hscratch_cap = lb->hrec_cap = lb->hverts_cap = 0;
+}
+
+// and so are the relabel's
+inline void relabel_buffers_forget(umx_labeler* lb) {
+    lb->d_rmap = nullptr; lb->d_rtable = nullptr;
+    lb->rmap_cap = lb->rtable_cap = 0;
 }
 
 // Launches of kernels that live in umx_label.hip, for umx_label_contact.hip.

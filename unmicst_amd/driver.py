@@ -136,6 +136,15 @@ def build_parser(spec: ToolSpec) -> argparse.ArgumentParser:
                         "object (the grown or split ones with --labelGrow / --labelSplit)")
     p.add_argument("--labelHullVertices", dest="labelHullVertices", action="store_true",
                    help="with --labelHull: also write the hulls' vertices, corners of the pixel squares (<stem>_HullVertices_<suffix>.csv)")
+    # acting on the tables: objects are merged, then dropped, and the rest renumbered on the
+    # device before any file is written, so the Labels page and every table are those of the final objects
+    p.add_argument("--labelKeep", dest="labelKeep", nargs="+", default=None, metavar="RULE",
+                   help="keep only the labelled objects for which every RULE holds and renumber them; a RULE is NAME OP VALUE without "
+                        "spaces, OP one of >= <= > < == !=, NAME one of area, border (1 when the object's box touches the image border) "
+                        "or a column of the Shapes, Hulls or Intensities file (e.g. 'area>=30' 'border==0' 'pm2_mean>=128')")
+    p.add_argument("--labelMerge", dest="labelMerge", type=float, default=None, metavar="F",
+                   help="merge touching objects whose shared edges are at least F (0 < F <= 1) of the smaller one's perimeter edges: "
+                        "takes back the cuts of --labelSplit / --labelFlood through a body; applied before --labelKeep")
     return p
 
 
@@ -149,7 +158,8 @@ def check_label_args(parser: argparse.ArgumentParser, args) -> None:
                         ("--labelFlood", args.labelFlood), ("--labelFloodStep", args.labelFloodStep),
                         ("--labelFloodInvert", args.labelFloodInvert or None), ("--labelNeighbors", args.labelNeighbors or None),
                         ("--labelNeighborsReach", args.labelNeighborsReach), ("--labelHull", args.labelHull or None),
-                        ("--labelHullVertices", args.labelHullVertices or None)):
+                        ("--labelHullVertices", args.labelHullVertices or None), ("--labelKeep", args.labelKeep),
+                        ("--labelMerge", args.labelMerge)):
             if v is not None:
                 parser.error("%s needs --labelMask" % flag)
         return
@@ -187,6 +197,13 @@ def check_label_args(parser: argparse.ArgumentParser, args) -> None:
         parser.error("--labelNeighborsReach %d: it must be 0..255 pixels" % args.labelNeighborsReach)
     if args.labelHullVertices and not args.labelHull:
         parser.error("--labelHullVertices needs --labelHull")
+    if args.labelMerge is not None and not 0.0 < args.labelMerge <= 1.0:     # (nan fails both)
+        parser.error("--labelMerge %r: it must be a fraction above 0 and at most 1" % args.labelMerge)
+    for rule in args.labelKeep or ():
+        try:
+            parse_keep_rule(rule)
+        except ValueError as e:
+            parser.error("--labelKeep %s" % e)
     for k in args.labelGrowClasses or ():
         if k < 0:
             parser.error("--labelGrowClasses %d: classes are numbered from 0" % k)
@@ -212,6 +229,110 @@ def label_grow_classes(parser: argparse.ArgumentParser, args, n_classes: int):
     return classes
 
 
+KEEP_OPS = {">=": np.greater_equal, "<=": np.less_equal, ">": np.greater, "<": np.less, "==": np.equal, "!=": np.not_equal}
+MEASURE_COLUMNS = ("mean", "std", "min", "max")
+
+
+def parse_keep_rule(text: str):
+    """'NAME OP VALUE' without spaces -> (name, op, value float, table): table is "objects" (area, border), "shape", "hull", or
+    ("pm", k) / ("ch", p) for a column of the Intensities file.  ValueError with the reason for anything else.  Whether the model has
+    plane k and the file page p is the caller's check (keep_rule_refusal)."""
+    import re
+    m = re.fullmatch(r"([A-Za-z_][A-Za-z0-9_]*)(>=|<=|==|!=|>|<)(\S+)", text)
+    if not m:
+        raise ValueError("%r: a rule is NAME OP VALUE without spaces, OP one of >= <= > < == !=" % text)
+    name, op, number = m.groups()
+    try:
+        value = float(number)
+    except ValueError:
+        value = float("nan")
+    if value != value or value in (float("inf"), float("-inf")):
+        raise ValueError("%r: %r is no number" % (text, number))
+    if name in ("area", "border"):
+        return name, op, value, "objects"
+    if name in SHAPE_COLUMNS[1:]:
+        return name, op, value, "shape"
+    if name in HULL_COLUMNS[1:]:
+        return name, op, value, "hull"
+    im = re.fullmatch(r"(pm|ch)(\d+)_(%s)" % "|".join(MEASURE_COLUMNS), name)
+    if im:
+        return name, op, value, (im.group(1), int(im.group(2)))
+    raise ValueError("%r: %r is neither area, border nor a column of the Shapes, Hulls or Intensities file" % (text, name))
+
+
+def keep_rule_refusal(rules, n_classes: int, n_pages) -> str:
+    """"" when every parsed rule names a plane the model has (pm<k>) and a page the file has (ch<p>; n_pages None: the file is no
+    TIFF whose pages can be measured), else the reason"""
+    for name, _, _, table in rules:
+        if isinstance(table, tuple) and table[0] == "pm" and table[1] >= n_classes:
+            return "%s: the model has planes 0..%d" % (name, n_classes - 1)
+        if isinstance(table, tuple) and table[0] == "ch" and (n_pages is None or table[1] >= n_pages):
+            return "%s: only pages of a TIFF are measured" % name if n_pages is None else "%s: the file has pages 0..%d" % (name, n_pages - 1)
+    return ""
+
+
+def object_columns(objects, shape) -> dict:
+    """the columns a rule reads from the object table alone: area, and border = 1 where the inclusive box touches the image border"""
+    H, W = shape
+    border = (objects["y0"] == 0) | (objects["x0"] == 0) | (objects["y1"] == H - 1) | (objects["x1"] == W - 1)
+    return {"area": objects["area"], "border": border.astype(np.int64)}
+
+
+def shape_columns(objects, records) -> dict:
+    """SHAPE_COLUMNS[1:] -> arrays [N]: umx.shape_descriptors of the records, and extent = area / the area of the table's bounding
+    box, one float64 division.  The area the window counts give must be the table's."""
+    from . import umx as _umx
+    d = _umx.shape_descriptors(records)
+    if not np.array_equal(d["area"], objects["area"]):
+        raise AssertionError("the shapes counted other pixels than the label table")
+    box = (objects["y1"].astype(np.int64) - objects["y0"] + 1) * (objects["x1"].astype(np.int64) - objects["x0"] + 1)
+    cols = {n: d[n] for n in SHAPE_COLUMNS[1:-1]}
+    cols["extent"] = d["area"].astype(np.float64) / box.astype(np.float64)
+    return cols
+
+
+def hull_columns(objects, records, vertices) -> dict:
+    """HULL_COLUMNS[1:] -> arrays [N]: umx.hull_descriptors of the records with the table's areas.  Every object of the table must have
+    a hull and no hull fewer pixels' worth of area than the object."""
+    from . import umx as _umx
+    if len(records) != len(objects) or (records["n_vertices"] < 4).any() or (2 * objects["area"].astype(np.int64) > records["area2"]).any():
+        raise AssertionError("the hulls are not those of the label table's objects")
+    d = _umx.hull_descriptors(records, vertices, objects["area"])
+    return {n: d[n] for n in HULL_COLUMNS[1:]}
+
+
+def intensity_columns(objects, planes) -> dict:
+    """<prefix>_mean, _std, _min, _max -> arrays [N] for planes [(prefix, records umx.LABEL_MEASURE_DTYPE [N])]: what
+    write_intensities_csv prints from.  Every plane's count must be the table's area."""
+    from . import umx as _umx
+    cols = {}
+    for prefix, records in planes:
+        if not np.array_equal(records["count"], objects["area"]):
+            raise AssertionError("the measurement of %s counted other pixels than the label table" % prefix)
+        mean, std = _umx.measure_mean_std(records)
+        cols.update({prefix + "_mean": mean, prefix + "_std": std, prefix + "_min": records["min"], prefix + "_max": records["max"]})
+    return cols
+
+
+def keep_mask(rules, columns: dict) -> np.ndarray:
+    """uint8 [N]: 1 where every rule (name, op, value, ...) holds on its column, compared in float64 on the values the CSV writers
+    print from, before formatting (a nan holds only under !=)"""
+    n = len(next(iter(columns.values())))
+    keep = np.ones(n, bool)
+    for name, op, value, *_ in rules:
+        keep &= KEEP_OPS[op](np.asarray(columns[name]).astype(np.float64), np.float64(value))
+    return keep.astype(np.uint8)
+
+
+def merge_pairs(contacts, perimeter_edges, fraction: float) -> np.ndarray:
+    """int32 [M, 2]: the contacts (umx.LABEL_CONTACT_DTYPE, reach 0) whose shared edges are >= fraction * the lesser of the two
+    objects' perimeter edges, compared in float64"""
+    pe = np.asarray(perimeter_edges).astype(np.float64)
+    a, b = contacts["a"].astype(np.int64), contacts["b"].astype(np.int64)
+    take = contacts["edges"].astype(np.float64) >= np.float64(fraction) * np.minimum(pe[a - 1], pe[b - 1])
+    return np.stack([a[take], b[take]], axis=1).astype(np.int32).reshape(-1, 2)
+
+
 def write_objects_csv(path: str, objects) -> None:
     """label,area,y0,x0,y1,x1,centroid_y,centroid_x -- one line per kept object, label order; centroid = sum / area in float64."""
     with open(path, "w") as f:
@@ -226,14 +347,10 @@ def write_intensities_csv(path: str, objects, planes) -> None:
     """label,area, then <prefix>_mean,_std,_min,_max per measured plane -- one line per object, label order, the floats written the way
     write_objects_csv writes centroids.  planes: [(prefix, records umx.LABEL_MEASURE_DTYPE [N])]; every plane's count must be the
     table's area."""
-    from . import umx as _umx
-    for prefix, records in planes:
-        if not np.array_equal(records["count"], objects["area"]):
-            raise AssertionError("the measurement of %s counted other pixels than the label table" % prefix)
+    c = intensity_columns(objects, planes)
     cols = [range(1, len(objects) + 1), objects["area"].tolist()]
-    for _, records in planes:
-        mean, std = _umx.measure_mean_std(records)
-        cols += [mean.tolist(), std.tolist(), records["min"].tolist(), records["max"].tolist()]
+    for prefix, _ in planes:
+        cols += [c[prefix + "_" + n].tolist() for n in MEASURE_COLUMNS]
     fmt = "%d,%d" + ",%.6f,%.6f,%d,%d" * len(planes) + "\n"
     with open(path, "w") as f:
         f.write(",".join(["label,area"] + [prefix + "_" + n for prefix, _ in planes for n in ("mean", "std", "min", "max")]) + "\n")
@@ -249,13 +366,8 @@ def write_shapes_csv(path: str, objects, records) -> None:
     umx.shape_descriptors alone; extent = area / the area of the table's bounding box, one float64 division.  The area the window
     counts give must be the table's.  Unlike the centroids and the intensities, whose six decimals say all there is to say about a
     mean of integers, these floats are written with repr: the shortest digits that read back to the same float64."""
-    from . import umx as _umx
-    d = _umx.shape_descriptors(records)
-    if not np.array_equal(d["area"], objects["area"]):
-        raise AssertionError("the shapes counted other pixels than the label table")
-    box = (objects["y1"].astype(np.int64) - objects["y0"] + 1) * (objects["x1"].astype(np.int64) - objects["x0"] + 1)
-    extent = d["area"].astype(np.float64) / box.astype(np.float64)
-    cols = [range(1, len(objects) + 1)] + [d[n].tolist() for n in SHAPE_COLUMNS[1:-1]] + [extent.tolist()]
+    d = shape_columns(objects, records)
+    cols = [range(1, len(objects) + 1)] + [d[n].tolist() for n in SHAPE_COLUMNS[1:]]
     with open(path, "w") as f:
         f.write(",".join(SHAPE_COLUMNS) + "\n")
         f.writelines("%d,%d,%d,%r,%d,%d,%r,%r,%r,%r,%r\n" % row for row in zip(*cols))
@@ -280,10 +392,7 @@ def write_hulls_csv(path: str, objects, records, vertices) -> None:
     """HULL_COLUMNS -- one line per object, label order.  records, vertices: umx.LABEL_HULL_DTYPE [N] and umx.LABEL_HULL_VERTEX_DTYPE
     [V], turned into the columns by umx.hull_descriptors alone with the table's areas.  Every object of the table must have a hull
     and no hull fewer pixels' worth of area than the object.  The floats are written with repr, as in the Shapes file."""
-    from . import umx as _umx
-    if len(records) != len(objects) or (records["n_vertices"] < 4).any() or (2 * objects["area"].astype(np.int64) > records["area2"]).any():
-        raise AssertionError("the hulls are not those of the label table's objects")
-    d = _umx.hull_descriptors(records, vertices, objects["area"])
+    d = hull_columns(objects, records, vertices)
     cols = [range(1, len(objects) + 1)] + [d[n].tolist() for n in HULL_COLUMNS[1:]]
     with open(path, "w") as f:
         f.write(",".join(HULL_COLUMNS) + "\n")
@@ -451,6 +560,13 @@ def run(tool: str, argv=None, script_dir: str = None) -> int:
         for page in measure_pages_arg:
             if page >= n_pages:
                 parser.error("--labelMeasure %d: the file has pages 0..%d" % (page, n_pages - 1))
+    keep_rules = [parse_keep_rule(rule) for rule in args.labelKeep or ()]
+    if keep_rules:
+        ftype = split_name(os.path.basename(args.imagePath), spec)[1]
+        pages_known = any(isinstance(r[3], tuple) and r[3][0] == "ch" for r in keep_rules) and (ftype in spec.tiff_types or ftype == "tif")
+        why = keep_rule_refusal(keep_rules, label_art.hp.nClasses, tiffio.num_pages(args.imagePath) if pages_known else None)
+        if why:
+            parser.error("--labelKeep " + why)
 
     # the page(s) are read on a thread while the engine is set up (model load, planning, weight packing: 0.2 - 0.6 s against
     # 0.18 s of file reading for a 16384 x 16384 page; both release the GIL).  An error of the read surfaces where the reference
@@ -569,9 +685,35 @@ def run(tool: str, argv=None, script_dir: str = None) -> int:
                                               split_core=args.labelSplitCore or 1, split_regrow=args.labelSplitRegrow or 255,
                                               flood=args.labelFlood, flood_step=args.labelFloodStep or _umx.FLOOD_DEFAULT_STEP,
                                               flood_invert=args.labelFloodInvert)
+                if args.labelMerge is not None or keep_rules:
+                    # merge, then drop, on the device: every file below is written from the final resident labels
+                    st.mark("label")
+                    n0 = len(objects)
+                    if args.labelMerge is not None:
+                        perimeter_edges = _umx.shape_descriptors(labeler.shape())["perimeter_edges"]
+                        pairs = merge_pairs(labeler.contacts(reach=0), perimeter_edges, args.labelMerge)
+                        labels, objects, _ = labeler.relabel(pairs=pairs, want_labels=not keep_rules)
+                    merged = n0 - len(objects)
+                    if keep_rules:
+                        tables = {r[3] for r in keep_rules}
+                        columns = object_columns(objects, stack_u8.shape[1:])
+                        if "shape" in tables:
+                            columns.update(shape_columns(objects, labeler.shape()))
+                        if "hull" in tables:
+                            columns.update(hull_columns(objects, *labeler.hull()))
+                        if any(isinstance(t, tuple) and t[0] == "pm" for t in tables):
+                            pm = labeler.measure(stack_u8)
+                            columns.update(intensity_columns(objects, [("pm%d" % k, pm[k]) for k in range(len(pm))]))
+                        pages = sorted(t[1] for t in tables if isinstance(t, tuple) and t[0] == "ch")
+                        columns.update(intensity_columns(objects, measure_pages(labeler, image_path, pages, stack_u8.shape[1:])))
+                        labels, objects, _ = labeler.relabel(keep=keep_mask(keep_rules, columns))
+                    dropped = n0 - merged - len(objects)
+                    print("Label relabel: %d objects from %d (%d dropped, %d merged away)" % (len(objects), n0, dropped, merged))
+                    st.note("label_relabel", {"n_objects": len(objects), "n_before": n0, "dropped": dropped, "merged_away": merged})
+                    st.mark("relabel")
                 tiffio.imsave(out_dir + "//" + stem + "_Labels_" + suffix + ".tif", labels, append=False)
                 write_objects_csv(out_dir + "//" + stem + "_Objects_" + suffix + ".csv", objects)
-                st.mark("label")
+                st.mark("label_write" if args.labelMerge is not None or keep_rules else "label")
                 if args.labelSplit:
                     c = labeler.split_counts()
                     print("Label split: %d objects from %d (%d with a core), %d pixels unreached"

@@ -43,6 +43,7 @@ EXPORTS = [
     "umx_label_contact_check", "umx_labeler_contacts", "umx_labeler_contacts_dev", "umx_labeler_contacts_last_ms",
     "umx_labeler_contacts_last_stats",
     "umx_label_hull_check", "umx_labeler_hull", "umx_labeler_hull_dev", "umx_labeler_hull_last_ms",
+    "umx_label_relabel_check", "umx_label_relabel_map", "umx_labeler_relabel", "umx_labeler_relabel_dev", "umx_labeler_relabel_last_ms",
 ]
 
 # the label mask's limits and the geometry of its kernels (the UMX_LABEL_* macros of include/umx.h; tests/test_label_cpu.py compares)
@@ -180,6 +181,7 @@ class LabelHullVertex(ctypes.Structure):
 LABEL_HULL_DTYPE = np.dtype([("area2", "<i8"), ("feret_max_sq", "<i8"), ("first", "<i8"), ("n_vertices", "<i4"), ("rows", "<i4")])
 LABEL_HULL_VERTEX_DTYPE = np.dtype([("y", "<i4"), ("x", "<i4")])
 HULL_MAX_SIDE, HULL_MAX_ROWS = 65536, 268435456                # UMX_HULL_* (tests/test_label_hull_cpu.py compares)
+RELABEL_MAX_PAIRS = 268435456                                  # UMX_RELABEL_MAX_PAIRS (tests/test_label_relabel_cpu.py compares)
 
 
 _SEND_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p)
@@ -408,6 +410,19 @@ def load(path: Optional[str] = None):
                                        ctypes.POINTER(ctypes.c_int64)]
     L.umx_labeler_hull_last_ms.restype = c_int
     L.umx_labeler_hull_last_ms.argtypes = [c_void_p] + [ctypes.POINTER(c_double)] * 2
+    L.umx_label_relabel_check.restype = c_int
+    L.umx_label_relabel_check.argtypes = [c_int, c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_char_p, ctypes.c_size_t]
+    L.umx_label_relabel_map.restype = c_int
+    L.umx_label_relabel_map.argtypes = [ctypes.c_int64, c_void_p, c_void_p, ctypes.c_int64, c_void_p, ctypes.POINTER(ctypes.c_int64),
+                                        ctypes.c_char_p, ctypes.c_size_t]
+    L.umx_labeler_relabel.restype = c_int
+    L.umx_labeler_relabel.argtypes = [c_void_p, c_int, c_int, c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p, c_void_p,
+                                      ctypes.POINTER(ctypes.c_int64)]
+    L.umx_labeler_relabel_dev.restype = c_int
+    L.umx_labeler_relabel_dev.argtypes = [c_void_p, c_void_p, ctypes.c_int64, c_int, c_int, c_void_p, c_void_p, ctypes.c_int64, c_void_p,
+                                          c_void_p, ctypes.POINTER(ctypes.c_int64)]
+    L.umx_labeler_relabel_last_ms.restype = c_int
+    L.umx_labeler_relabel_last_ms.argtypes = [c_void_p] + [ctypes.POINTER(c_double)] * 3
     L.umx_prof_entry_size.restype = c_int
     if L.umx_prof_entry_size() != ctypes.sizeof(ProfEntry):
         raise RuntimeError("libumx (%s) lays umx_prof_entry out in %d bytes, this binding in %d: mixed builds" % (
@@ -941,6 +956,73 @@ def hull_descriptors(records: np.ndarray, vertices: np.ndarray, area) -> dict:
     return out
 
 
+def label_relabel_check(H: int, W: int, n_objects: int = 0, n_pairs: int = 0) -> str:
+    """umx_label_relabel_check: "" if a relabel of n_objects labels on H x W with n_pairs pairs is accepted, else the reason.  Host only."""
+    buf = ctypes.create_string_buffer(256)
+    rc = load().umx_label_relabel_check(int(H), int(W), int(n_objects), int(n_pairs), buf, len(buf))
+    return "" if rc == 0 else buf.value.decode()
+
+
+def _relabel_args(n_objects: int, keep, pairs):
+    """keep (None, or n_objects values: nonzero keeps) and pairs (None, or [M, 2] labels) as the contiguous uint8 and int32 arrays the
+    library reads, either None when not given; what cannot be such arguments raises UmxError(ERR_INVALID) as the library would"""
+    if keep is not None:
+        keep = np.ascontiguousarray(np.asarray(keep) != 0, np.uint8).ravel()
+        if keep.size != int(n_objects):
+            raise UmxError(ERR_INVALID, "keep has %d entries: %d objects need as many" % (keep.size, int(n_objects)))
+    if pairs is not None:
+        p = np.asarray(pairs)
+        if p.size and (p.ndim != 2 or p.shape[1] != 2):
+            raise UmxError(ERR_INVALID, "pairs must be [M, 2] labels, not %s" % (p.shape,))
+        p = p.reshape(-1, 2)
+        if p.size and (p.dtype.kind not in "iu" or p.min() < -2 ** 31 or p.max() > 2 ** 31 - 1):
+            raise UmxError(ERR_INVALID, "pairs must be integers that fit an int32")
+        pairs = np.ascontiguousarray(p, np.int32)
+    return keep, pairs
+
+
+def relabel_map(n_objects: int, keep=None, pairs=None):
+    """umx_label_relabel_map, steps 29 and 30 of DESIGN.md section 8.1 on the host (no device): -> (map int32 [n_objects + 1], N').
+    keep: None (all) or n_objects values, nonzero keeps label j at keep[j - 1]; pairs: None or [M, 2] labels to merge.  map[j] is
+    the new number of label j, 0 for a dropped one; the kept classes are numbered in order of their least member.  A pair outside
+    1..n_objects, or one that names a dropped label, raises UmxError with the pair's index."""
+    why = label_relabel_check(1, 1, n_objects, 0 if pairs is None else len(pairs))   # (before the map is sized from the arguments)
+    if why:
+        raise UmxError(ERR_INVALID, why)
+    keep, pairs = _relabel_args(n_objects, keep, pairs)
+    out = np.zeros(int(n_objects) + 1, np.int32)
+    n = ctypes.c_int64(-1)
+    buf = ctypes.create_string_buffer(256)
+    rc = load().umx_label_relabel_map(int(n_objects), None if keep is None else keep.ctypes.data, None if pairs is None else pairs.ctypes.data,
+                                      0 if pairs is None else len(pairs), out.ctypes.data, ctypes.byref(n), buf, len(buf))
+    if rc:
+        raise UmxError(rc, buf.value.decode())
+    return out, int(n.value)
+
+
+def relabel_objects(objects: np.ndarray, map: np.ndarray) -> np.ndarray:
+    """Step 32 of DESIGN.md section 8.1 on the host, for callers of relabel_ptr: LABEL_OBJECT_DTYPE records [N] and a map [N + 1] of
+    relabel_map -> the records [N'] of the new labels: area, sum_y and sum_x added, y0 and x0 by minimum, y1 and x1 by maximum over
+    the members.  A new label whose members have no pixel has the empty record (area 0, y0 = x0 = 2^31 - 1, y1 = x1 = -1)."""
+    objects, m = np.asarray(objects), np.asarray(map).astype(np.int64)
+    if objects.dtype != LABEL_OBJECT_DTYPE or m.ndim != 1 or len(m) != len(objects) + 1 or m[0] != 0 or (len(m) > 1 and m.min() < 0):
+        raise ValueError("objects must be LABEL_OBJECT_DTYPE [N] and map the N + 1 words of relabel_map")
+    n_new = int(m.max())
+    out = np.zeros(n_new, LABEL_OBJECT_DTYPE)
+    out["y0"] = out["x0"] = 2 ** 31 - 1
+    out["y1"] = out["x1"] = -1
+    to = m[1:] - 1
+    live = (to >= 0) & (objects["area"] > 0)
+    to, src = to[live], objects[live]
+    for name in ("area", "sum_y", "sum_x"):
+        np.add.at(out[name], to, src[name])
+    for name in ("y0", "x0"):
+        np.minimum.at(out[name], to, src[name])
+    for name in ("y1", "x1"):
+        np.maximum.at(out[name], to, src[name])
+    return out
+
+
 class Labeler:
     """One umx_labeler: the label mask (include/umx.h) of uint8 probability stacks on one MI355X.  It needs no
     model; its device buffers grow on demand and are kept between runs."""
@@ -1223,6 +1305,53 @@ class Labeler:
         """(kernel, download) milliseconds of the last hull call."""
         v = [ctypes.c_double() for _ in range(2)]
         self._check(self._L.umx_labeler_hull_last_ms(self._lb, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def relabel(self, keep=None, pairs=None, want_labels: bool = True, H: Optional[int] = None, W: Optional[int] = None):
+        """umx_labeler_relabel: drops and merges objects of the labels the last run(want_labels=True) left on the device and renumbers
+        the rest 1..N'  -> (labels int32 [H, W] or None, objects [N'], map int32 [N + 1]).
+        keep: None (all) or one value per object, nonzero keeps it; pairs: None or [M, 2] labels to merge (their closure is merged;
+        a pair that names a dropped label is refused).  The labels and the table on the device are edited in place: objects(),
+        measure(), shape(), contacts() and hull() afterwards see the new ones.  A refused call has changed nothing.  H, W: as shape()."""
+        H, W = (self._last_shape[0] if H is None else H), (self._last_shape[1] if W is None else W)
+        n = ctypes.c_int64()
+        self._check(self._L.umx_labeler_objects(self._lb, None, 0, ctypes.byref(n)))
+        keep, pairs = _relabel_args(n.value if keep is None else len(np.asarray(keep).ravel()), keep, pairs)
+        why = label_relabel_check(H, W, 0, 0 if pairs is None else len(pairs))   # (before any buffer is sized from the arguments)
+        if why:
+            raise UmxError(ERR_INVALID, why)
+        labels = np.empty((int(H), int(W)), np.int32) if want_labels else None
+        map_ = np.zeros(n.value + 1, np.int32)
+        n_new = ctypes.c_int64(-1)
+        self._check(self._L.umx_labeler_relabel(self._lb, int(H), int(W), None if keep is None else keep.ctypes.data,
+                                                0 if keep is None else keep.size, None if pairs is None else pairs.ctypes.data,
+                                                0 if pairs is None else len(pairs), labels.ctypes.data if want_labels else None,
+                                                map_.ctypes.data, ctypes.byref(n_new)))
+        objs = self.objects()
+        assert len(objs) == n_new.value
+        return labels, objs, map_
+
+    def relabel_ptr(self, labels_ptr: int, n_objects: int, H: int, W: int, keep=None, pairs=None, out_ptr: Optional[int] = None):
+        """umx_labeler_relabel_dev on DEVICE addresses (e.g. torch.Tensor.data_ptr()): int32 [H, W] labels with objects 1..n_objects,
+        complete, remapped into the int32 [H, W] plane at out_ptr (None: in place) -> (map int32 [n_objects + 1], N').  A value
+        outside 0..n_objects comes out 0.  No table: relabel_objects remaps the caller's.  Needs no prior run and leaves the resident
+        labels alone."""
+        why = label_relabel_check(H, W, n_objects, 0 if pairs is None else len(pairs))   # (before any buffer is sized from the arguments)
+        if why:
+            raise UmxError(ERR_INVALID, why)
+        keep, pairs = _relabel_args(n_objects, keep, pairs)
+        map_ = np.zeros(int(n_objects) + 1, np.int32)
+        n_new = ctypes.c_int64(-1)
+        self._check(self._L.umx_labeler_relabel_dev(self._lb, ctypes.c_void_p(labels_ptr), int(n_objects), int(H), int(W),
+                                                    None if keep is None else keep.ctypes.data, None if pairs is None else pairs.ctypes.data,
+                                                    0 if pairs is None else len(pairs), ctypes.c_void_p(labels_ptr if out_ptr is None else out_ptr),
+                                                    map_.ctypes.data, ctypes.byref(n_new)))
+        return map_, int(n_new.value)
+
+    def relabel_last_ms(self):
+        """(upload, kernel, download) milliseconds of the last relabel call."""
+        v = [ctypes.c_double() for _ in range(3)]
+        self._check(self._L.umx_labeler_relabel_last_ms(self._lb, *[ctypes.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
 
