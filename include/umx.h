@@ -35,7 +35,8 @@ enum umx_status {
     UMX_ERR_NO_DEVICE = 3,   /* no usable HIP device */
     UMX_ERR_HIP = 4,         /* a HIP runtime call failed */
     UMX_ERR_OOM = 5,
-    UMX_ERR_RANGE = 6,       /* split-precision path only: an activation left the binary16 range (|v| >= 6e4) */
+    UMX_ERR_RANGE = 6,       /* split-precision path: an activation left the binary16 range (|v| >= 6e4); umx_labeler_run_hmax: a
+                              * reconstruction was still rising after UMX_HMAX_MAX_LAUNCHES launches */
     UMX_ERR_GUARD = 7        /* debug guard mode only (UMX_DEBUG_GUARD, umx_create_opts / include/umx_train.h): a kernel wrote outside its buffer */
 };
 
@@ -614,7 +615,8 @@ UMX_API int umx_labeler_relabel_last_ms(const umx_labeler* lb, double* upload_ms
  *   15. if grow_radius > 0 the growth above over grow_classes from the labels of step 14; then the table of the final labels.
  * The result is a function of the planes and the options only; every final object contains its seed and is 4-connected; an object
  * with one core or none keeps exactly its pixels when L is large enough; a bar of width w joining two bodies is cut iff w <= 2 D.
- * Not here: h-maxima, merging fragments back (a ragged outline can throw small cores; C is the only guard).  The regrow of step 14
+ * Not here: merging fragments back (a ragged outline can throw small cores; C is the only guard; umx_labeler_run_hmax below places
+ * the seeds by the planes' own peaks instead of by erosion).  The regrow of step 14
  * cuts a neck on the midline between its cores; umx_labeler_run_flood below cuts it along a ridge of one of the planes instead.  A split run allocates, beyond a plain run's buffers, one more int32 plane and one byte plane of H * W, kept like the others.
  */
 typedef struct umx_label_split_options {
@@ -691,6 +693,58 @@ UMX_API int umx_labeler_run_flood(umx_labeler* lb, const uint8_t* planes_host, i
                                   int32_t* labels_host, umx_label_flood_counts* counts);
 UMX_API int umx_labeler_run_flood_dev(umx_labeler* lb, const uint8_t* planes_dev, int K, int H, int W, const umx_label_flood_options* o,
                                       int32_t* labels_dev, umx_label_flood_counts* counts);
+
+/*
+ * h-maxima seeds: the seed set of a flood run taken from the peaks of one of the planes instead of from erosion cores (DESIGN.md
+ * section 8.1, steps 33 to 36; the definition is the project's own and integer throughout).  Erosion cores see geometry alone: two
+ * nuclei joined along a front wider than 2 D are never separated, and D is bounded at 8.  With a seed plane S, an invert flag and a
+ * height h on top of a flood run (whose split.depth is not used):
+ *   33. seed relief: f(p) = planes[S][p] on M (the pixels of the kept objects, step 10), or 255 - planes[S][p] with seed_invert;
+ *       f(p) = 0 off M and outside the image.
+ *   34. h-maxima: g = the reconstruction by dilation of the marker max(f - h, 0) under the mask f, 4-connectivity: the limit of
+ *       g <- min(f, max(g(p), g(its four neighbours))) started at the marker = the least function above the marker that satisfies
+ *       that equation.  Objects are never 4-adjacent and f is 0 between them: nothing passes from one object to another.
+ *   35. extended maxima: r = the reconstruction of max(g - 1, 0) under g; E = { p : g(p) > r(p) } = the union of the 4-connected
+ *       plateaus of g with value > 0 that have no 4-neighbour of greater g.  E is a subset of M.
+ *   36. steps 12 and 13 with this E in the place of the eroded set (cores: the components of E with area >= core_min_area; uncored
+ *       kept objects stay whole), then steps 19 to 21 (level_step 256: the regrow by distance) and 15.
+ * Consequences: (a) with core_min_area 1, n_cored = the kept objects whose largest f exceeds h; (b) h = 255 gives no core: labels,
+ * table and n_objects are those of umx_labeler_run with the same base, bit for bit; (c) a relief constant and above h on M gives
+ * E = M and again the plain labelling; (d) two peaks a <= b joined over a saddle s are two seeds iff a - s > h; (e) every final
+ * object contains its seed and is 4-connected, N >= N0; (f) the result is a function of the planes and the options only.
+ * An h-maxima run allocates what a flood run allocates and three words: the byte planes of the reconstructions live in the split's
+ * third int32 plane.  Not here: seeds by a threshold on the probability, a distance-transform relief, h-maxima inside the sharded
+ * schedule.
+ */
+typedef struct umx_label_hmax_options {
+    umx_label_flood_options flood;   /* the flood run; flood.split.depth must pass the split's check and is otherwise not looked at */
+    int32_t seed_plane;              /* S: 0 .. K-1, in the model's class order */
+    int32_t seed_invert;             /* 0: f = planes[S]; 1: f = 255 - planes[S] */
+    int32_t height;                  /* h: 1 .. UMX_HMAX_MAX_HEIGHT */
+    int32_t reserved[5];             /* must be zero */
+} umx_label_hmax_options;            /* 128 bytes */
+typedef struct umx_label_hmax_counts {
+    umx_label_flood_counts flood;    /* as umx_labeler_run_flood gives them */
+    int64_t seed_pixels;             /* |E| */
+    int64_t recon_launches[2];       /* launches of the reconstructions of steps 34 and 35: informative, not part of the definition */
+    int64_t reserved;
+} umx_label_hmax_counts;             /* 96 bytes */
+/* The largest height, the steps one reconstruction launch runs at most, and the launches one reconstruction may take: a launch
+ * carries a value at least UMX_LABEL_GROW_HALO pixels along any path, so a path of 16 384 pixels converges; a run that reaches the
+ * bound fails (UMX_ERR_RANGE) with a message that names it. */
+enum { UMX_HMAX_MAX_HEIGHT = 255, UMX_HMAX_LAUNCH_STEPS = 64, UMX_HMAX_MAX_LAUNCHES = 2048 };
+/* Host only, no device: umx_label_flood_check on the flood record first, its message passed through unchanged; then
+ * 0 <= seed_plane < K, seed_invert 0 or 1, 1 <= height <= 255, reserved words zero.  UMX_OK, or UMX_ERR_INVALID with the reason in
+ * msg. */
+UMX_API int umx_label_hmax_check(const umx_label_hmax_options* o, int K, int H, int W, char* msg, size_t cap);
+/* umx_labeler_run_flood / _run_flood_dev with the h-maxima seeds in place of the erosion cores: the same contracts.  A refused call
+ * (UMX_ERR_INVALID) has touched nothing and leaves the resident labels as they were; a successful host call with a label plane
+ * makes the result the resident labels for umx_labeler_measure, _shape, _contacts, _hull and _relabel.  Synchronous; under
+ * UMX_DEBUG_GUARD the call ends in the check of the red zones.  counts may be NULL. */
+UMX_API int umx_labeler_run_hmax(umx_labeler* lb, const uint8_t* planes_host, int K, int H, int W, const umx_label_hmax_options* o,
+                                 int32_t* labels_host, umx_label_hmax_counts* counts);
+UMX_API int umx_labeler_run_hmax_dev(umx_labeler* lb, const uint8_t* planes_dev, int K, int H, int W, const umx_label_hmax_options* o,
+                                     int32_t* labels_dev, umx_label_hmax_counts* counts);
 
 /* Strip / tile decoders of the drivers' own TIFF reader (unmicst_amd/tiffio.py; the reference reads through tifffile /
  * imagecodecs, UnMicst1-5.py:794-797): TIFF 6.0 LZW (compression 5, the OME-TIFF / Bio-Formats default) and PackBits

@@ -2,7 +2,7 @@
 """Time the label mask (umx_labeler_run) on synthetic H x W stacks of K = 3 uint8 planes (GPU box); one JSON
 line.  usage: bench_label.py [H=16384] [W=H] [--reps 3] [--grow R] [--measure C [--measure-dtype u8|u16]] [--split D [--split-core C]]
        [--flood P [--flood-step Q]] [--shape [--no-host]] [--contacts [--reach R] [--no-host]] [--hull [--no-host]]
-       [--relabel [--no-host]]
+       [--relabel [--no-host]] [--hmax H]
 
 Two inputs, both made here by pure-numpy recipes (no scipy in the generators, nothing from tests/):
   blobs  nuclei-like discs: the image is cut into 32 x 32 cells; a seeded draw keeps 60 % of them, and each kept cell gets one disc of
@@ -29,6 +29,11 @@ difference of the two kernel times, and the four counts of the split are reporte
 bridge's middle, where the split's regrow cuts -- over the plane's 30 elsewhere.  The planes are labelled with the split alone (the
 yardstick) and with the flood on plane P in levels of --flood-step; "flood_ms" is the difference
 of the two kernel times, and the flood's counts -- its launches among them -- are reported.
+--hmax H: an input of its own, overlapping discs: the image is cut into cells of 48 x 48, each with two discs of radius 12 whose centres
+are 14 apart -- their common neck is 19 pixels wide, more than 2 * 8, so no --split can cut it -- and plane 1 carries one dome per disc
+(30 at the rim to 190 at the centre, 96 on the saddle between the two).  The same planes are labelled plainly, with --split 3 and with
+the h-maxima seeds of height H on plane 1, in one process; "hmax_ms" is what the seeds and their
+regrow add to the plain call, and the counts -- the launches of the two reconstructions among them -- are reported.
 --shape: the blobs input alone, labelled with its label plane kept on the device, then the shapes of its objects (umx_labeler_shape,
 DESIGN.md section 8.1 steps 16 to 18): the kernel and download milliseconds umx_labeler_shape_last_ms reports (the best of --reps by
 kernel time, after one warm-up), beside them the one-plane uint16 measurement of the same labels (the yardstick: it reads the same
@@ -127,6 +132,40 @@ def flood_bench(a, H, W):
                  # every pixel of a tile and its halo (the relief byte is one of them); one label word written per pixel
                  "bytes_per_launch_upper": int(((1 + 2 * umx.LABEL_GROW_HALO / umx.LABEL_GROW_TILE) ** 2 * (4 + planes.shape[0]) + 4) * H * W)},
                 **counts)
+
+
+DISC_PITCH, DISC_RADIUS, DISC_SHIFT, DISC_H = 48, 12, 14, 40
+
+
+def disc_planes(H, W):
+    """planes_of pairs of overlapping discs, one pair per cell of 48 x 48, with plane 1 one dome per disc on them"""
+    oy, ox = np.mgrid[0:DISC_PITCH, 0:DISC_PITCH]
+    cy, cx = DISC_PITCH // 2, (DISC_PITCH - DISC_SHIFT) // 2
+    d = np.minimum(np.hypot(oy - cy, ox - cx), np.hypot(oy - cy, ox - cx - DISC_SHIFT))
+    ny, nx = -(-H // DISC_PITCH), -(-W // DISC_PITCH)
+    dome = np.where(d <= DISC_RADIUS, 30 + (160 * (DISC_RADIUS - d) / DISC_RADIUS).astype(np.int64), 0).astype(np.uint8)
+    mask = np.tile(d <= DISC_RADIUS, (ny, nx))[:H, :W]
+    planes = planes_of(mask)
+    planes[1] = np.where(mask, np.tile(dome, (ny, nx))[:H, :W], 30)
+    return planes
+
+
+def hmax_bench(a, H, W):
+    planes = disc_planes(H, W)
+    tile, halo = umx.LABEL_GROW_TILE, umx.LABEL_GROW_HALO
+    with umx.Labeler(a.device) as lb:
+        before, plain = best_kernel_ms(lb, planes, a.reps)
+        cut, with_split = best_kernel_ms(lb, planes, a.reps, split=3)
+        after, with_hmax = best_kernel_ms(lb, planes, a.reps, hmax=a.hmax, hmax_plane=1)
+        counts = lb.hmax_counts()
+    assert len(cut) == len(before) == counts["n_before"] and len(after) == counts["n_objects"] and counts["unreached"] == 0
+    assert int(before["area"].sum()) == int(after["area"].sum())
+    return dict({"hmax": a.hmax, "object_pixels": int(before["area"].sum()), "kernel_ms": round(plain[1], 3),
+                 "kernel_ms_with_split3": round(with_split[1], 3), "kernel_ms_with_hmax": round(with_hmax[1], 3),
+                 "hmax_ms": round(with_hmax[1] - plain[1], 3),
+                 # what one reconstruction launch moves at most: the mask and the marker byte of every pixel of a tile and its halo,
+                 # one marker byte written per pixel
+                 "bytes_per_recon_launch_upper": int(((1 + 2 * halo / tile) ** 2 * 2 + 1) * H * W)}, **counts)
 
 
 def split_bench(a, H, W):
@@ -485,11 +524,15 @@ def main():
     ap.add_argument("--reach", type=int, default=0, metavar="R", help="with --contacts: the reach")
     ap.add_argument("--hull", action="store_true", help="the hulls of the blobs input")
     ap.add_argument("--relabel", action="store_true", help="a relabel of the blobs input that drops about half its objects")
+    ap.add_argument("--hmax", type=int, default=None, metavar="H", help="h-maxima seeds of this height on the overlapping-discs input")
     a = ap.parse_args()
     H, W = a.H, a.W or a.H
     out = {"tool": "bench_label", "H": H, "W": W, "K": 3, "min_area": 1, "reps": a.reps}
     if a.relabel:
         print(json.dumps(dict(out, **relabel_bench(a, H, W))))
+        return
+    if a.hmax is not None:
+        print(json.dumps(dict(out, **hmax_bench(a, H, W))))
         return
     if a.hull:
         print(json.dumps(dict(out, **hull_bench(a, H, W))))

@@ -14,7 +14,7 @@ OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libumx.so")
 SOURCES = ["umx_kernels.hip", "umx_conv_f16.hip", "umx_conv_first.hip", "umx_graph.hip", "umx_plan.hip", "umx_engine.hip", "umx_pipeline.hip", "umx_host.hip",
            "umx_tiff.hip", "umx_shard.hip", "umx_train_kernels.hip", "umx_wgrad.hip", "umx_tconv.hip", "umx_tstep.hip", "umx_arena.hip", "umx_train.hip", "umx_trainset.hip", "umx_trainset_assemble.hip",
-           "umx_trainset_border.hip", "umx_trainset_objects.hip", "umx_label.hip", "umx_label_contact.hip", "umx_label_hull.hip", "umx_label_relabel.hip"]
+           "umx_trainset_border.hip", "umx_trainset_objects.hip", "umx_label.hip", "umx_label_hmax.hip", "umx_label_contact.hip", "umx_label_hull.hip", "umx_label_relabel.hip"]
 HEADERS = ["umx_kernels.h", "umx_internal.h", "umx_unionfind.h", "umx_label_state.h", "umx_contact_host.h", "umx_hull_host.h", "umx_relabel_host.h", os.path.join("..", "..", "include", "umx.h"), os.path.join("..", "..", "include", "umx_train.h")]
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function",

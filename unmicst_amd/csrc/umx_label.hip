@@ -35,6 +35,8 @@
 //   label_flood_kernel    the growth's tile and halo at one level t of a relief taken from the planes: up to 8 steps over the empty
 //                         pixels of class cls with relief <= t; it counts its claims and reports the least relief that waits beside
 //                         a label, from which the host picks the next level (run_flood_launches)
+// An h-maxima run (umx_labeler_run_hmax / _run_hmax_dev) is a flood run whose set E comes from
+// the kernels of umx_label_hmax.hip (a relief of the planes, two grey-scale reconstructions) instead of from label_erode_kernel.
 // A measurement (umx_labeler_measure / _measure_dev) is, per group of up to 4 image planes,
 //   label_measure_init_kernel, label_measure_kernel   one wave per row: the labels (the P plane a run left, or the caller's) read once
 //                         for the group's planes; every row run adds its count, its sums of v and v * v and its extremes of every plane
@@ -487,10 +489,8 @@ __global__ void __launch_bounds__(64 * kRowWaves) label_grown_kernel(const int* 
 }
 
 // ---- the split ----
-// A third int32 plane R (the components of the eroded set E, as P holds those of the objects) and a byte plane B of flags per pixel:
-constexpr unsigned kFlagKept = 1u;    // the pixel belongs to a kept object (step 10: a pixel of M)
-constexpr unsigned kFlagEroded = 2u;  // the pixel is in E (step 11); not read any more once R holds E's components
-constexpr unsigned kFlagCored = 4u;   // at the ROOT pixel of an object only: the object contains a core (step 12)
+// A third int32 plane R (the components of the eroded set E, as P holds those of the objects) and a byte plane B of flags per pixel,
+// the kFlag* of umx_label_state.h.
 constexpr int kSplitWords = 4, kSplitBefore = 0, kSplitPacked = 1, kSplitClaimed = 2;   // the words of umx_labeler::d_split
 constexpr int kErodeWords = kGrowPix / 64;                // the region of an erosion workgroup as one string of bits: 100 words, 800 B
 constexpr int kErodeShift = kGrowSide - 64;               // a row down is kGrowSide bits on: one word and this many bits
@@ -592,7 +592,8 @@ __global__ void __launch_bounds__(kPixThreads) label_core_mark_kernel(const int*
 // them as they number objects: a pixel is a seed root iff P[i] == i afterwards, and Q[i] >= 0 there (an area of E, or 0), so the
 // numbering is asked with min_area 0.  A thread reads P at its own pixel only, which is the only word of P it writes; R, Q and B are
 // only read.  *packed += (kept pixels that are no seed pixels) << 32 | (roots of cored objects): one 64-bit integer atomic per
-// workgroup that has any, which nothing reads in this launch; the low half cannot carry (a cored object has 5 pixels or more).
+// workgroup that has any, which nothing reads in this launch; the low half cannot carry (with h-maxima seeds a cored object may be one
+// pixel, but there are at most H * W < 2^31 roots).
 __global__ void __launch_bounds__(kPixThreads) label_split_ids_kernel(int* __restrict__ P, const int* __restrict__ R, const int* __restrict__ Q,
                                                                       const uint8_t* __restrict__ B, long long npix, int core_min,
                                                                       unsigned long long* __restrict__ packed) {
@@ -625,6 +626,7 @@ constexpr int kFloodWords = 2, kFloodClaimed = 0, kFloodLeast = 1;   // the word
 constexpr int kFloodNone = 0x7f7f7f7f;                               // the least-relief word before a launch: above every relief
 static_assert(UMX_FLOOD_LAUNCH_STEPS == kGrowHalo && UMX_FLOOD_MAX_STEP == 256, "a flood launch runs a halo's worth of steps; reliefs are bytes");
 static_assert(sizeof(umx_label_flood_options) == 96 && sizeof(umx_label_flood_counts) == 64, "the flood's records");
+static_assert(sizeof(umx_label_hmax_options) == 128 && sizeof(umx_label_hmax_counts) == 96, "the h-maxima records");
 
 // Up to `steps` (1 .. kGrowHalo) synchronous steps of the flood at ONE level t, src -> dst (two different planes): the geometry of
 // label_grow_kernel -- grid tiles_y * tiles_x, one workgroup per tile of 64 x 64 pixels, the tile and a halo of 8 in LDS as one int
@@ -1086,7 +1088,7 @@ int ensure_buffers(umx_labeler* lb, size_t plane_bytes, size_t npix, size_t nblo
     L_HIP(lb, hipStreamSynchronize(lb->stream));
     arena_free(&lb->mem);
     lb->d_planes = nullptr; lb->d_P = lb->d_Q = lb->d_counts = nullptr; lb->d_n = nullptr; lb->d_table = nullptr;
-    lb->d_R = nullptr; lb->d_B = nullptr; lb->d_split = nullptr; lb->d_flood = nullptr;
+    lb->d_R = nullptr; lb->d_B = nullptr; lb->d_split = nullptr; lb->d_flood = nullptr; lb->d_hmax = nullptr;
     lb->d_mplanes = nullptr; lb->d_mrec = nullptr; lb->mplanes_cap = lb->mrec_cap = 0;   // (the measurement allocates its own again)
     lb->d_srec = nullptr; lb->srec_cap = 0;                                              // (and so do the shapes)
     contact_buffers_forget(lb);                                                          // (and the contacts)
@@ -1107,6 +1109,7 @@ int ensure_buffers(umx_labeler* lb, size_t plane_bytes, size_t npix, size_t nblo
         L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_B, (sp + 3) / 4 * 4, false, "label split flags"));
         L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_split, kSplitWords * sizeof(long long), true, "label split counts"));
         L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_flood, kFloodWords * sizeof(long long), true, "label flood words"));
+        L_HIP(lb, arena_alloc(&lb->mem, (void**)&lb->d_hmax, kHmaxWords * sizeof(long long), true, "label h-maxima words"));
     }
     lb->planes_cap = pb; lb->pix_cap = px; lb->counts_cap = nb; lb->table_cap = tc; lb->split_cap = sp;
     return UMX_OK;
@@ -1272,8 +1275,11 @@ int run_flood_launches(umx_labeler* lb, const uint8_t* planes, int K, int H, int
 //                             these launches changes it -- so every later level would claim nothing either
 //   the rim growth and label_grown_kernel as in run_launches
 // A flood run (fo: its options, so == &fo->split; fc takes its counts) has run_flood_launches in the regrow's place.
+// An h-maxima run (ho: its options, fo == &ho->flood; hc takes seed_pixels and recon_launches) is a flood run with launch_hmax_seeds
+// (umx_label_hmax.hip: the relief, two reconstructions, the mark; steps 33 to 35) in the place of the label_erode_kernel launch.
 int run_split_launches(umx_labeler* lb, const uint8_t* planes, int K, int H, int W, const umx_label_split_options* so, int* out,
-                       umx_label_split_counts* counts, const umx_label_flood_options* fo = nullptr, umx_label_flood_counts* fc = nullptr) {
+                       umx_label_split_counts* counts, const umx_label_flood_options* fo = nullptr, umx_label_flood_counts* fc = nullptr,
+                       const umx_label_hmax_options* ho = nullptr, umx_label_hmax_counts* hc = nullptr) {
     const umx_label_options* o = &so->base;
     const long long npix = (long long)H * W;
     const int nblocks = (int)((npix + kScanBlock - 1) / kScanBlock);
@@ -1289,7 +1295,11 @@ int run_split_launches(umx_labeler* lb, const uint8_t* planes, int K, int H, int
     int rc = launch_components(lb, P, Q, H, W);
     if (rc) return rc;
     launch_count(lb, P, Q, npix, o->min_area, lb->d_split + kSplitBefore);
-    hipLaunchKernelGGL(label_erode_kernel, tile_grid, dim3(kGrowThreads), 0, s, P, Q, H, W, o->min_area, so->depth, tiles_x, B);
+    if (ho) {
+        if ((rc = launch_hmax_seeds(lb, planes, H, W, P, Q, o->min_area, ho, hc->recon_launches))) return rc;
+    } else {
+        hipLaunchKernelGGL(label_erode_kernel, tile_grid, dim3(kGrowThreads), 0, s, P, Q, H, W, o->min_area, so->depth, tiles_x, B);
+    }
     hipLaunchKernelGGL(label_runs_mask_kernel, dim3(row_grid(H)), dim3(64 * kRowWaves), 0, s, B, H, W, R);
     if ((rc = launch_components(lb, R, Q, H, W))) return rc;
     hipLaunchKernelGGL(label_core_mark_kernel, dim3(pix_grid), dim3(kPixThreads), 0, s, P, R, Q, npix, so->core_min_area, B);
@@ -1299,8 +1309,12 @@ int run_split_launches(umx_labeler* lb, const uint8_t* planes, int K, int H, int
     hipLaunchKernelGGL(label_number_kernel, dim3((unsigned)nblocks), dim3(64 * kScanWaves), 0, s, P, Q, npix, 0, lb->d_counts);
     long long words[kSplitWords] = {0, 0, 0, 0};
     L_HIP(lb, hipMemcpyAsync(words, lb->d_split, sizeof words, hipMemcpyDeviceToHost, s));
+    long long seed_pixels = 0;
+    if (ho) L_HIP(lb, hipMemcpyAsync(&seed_pixels, lb->d_hmax + kHmaxSeeds, sizeof seed_pixels, hipMemcpyDeviceToHost, s));
     long long n = 0;
     if ((rc = read_count_and_init_table(lb, npix, &n))) return rc;
+    if (seed_pixels < 0 || seed_pixels > npix) return lfail(lb, UMX_ERR_HIP, "the h-maxima counted %lld seed pixels in %lld pixels", seed_pixels, npix);
+    if (ho) hc->seed_pixels = seed_pixels;
     const long long n_before = words[kSplitBefore], n_cored = words[kSplitPacked] & 0xffffffffll;
     const long long pending = (long long)((unsigned long long)words[kSplitPacked] >> 32);
     if (n_before < 0 || n_before > n || n_cored > n_before || pending > npix)
@@ -1332,13 +1346,16 @@ int run_split_launches(umx_labeler* lb, const uint8_t* planes, int K, int H, int
 }
 
 // split: a split run -- so holds its options (o is not looked at) and counts takes the four counts.  fo: a flood run -- its options
-// (then split is set and so is &fo->split) and fcounts takes its counts, the four of the split among them.
+// (then split is set and so is &fo->split) and fcounts takes its counts, the four of the split among them.  ho: an h-maxima run -- its
+// options (then fo is &ho->flood) and hcounts takes its counts, the flood's among them (fcounts is not used).
 int run_any(umx_labeler* lb, const uint8_t* planes, bool on_host, int K, int H, int W, const umx_label_options* o, int32_t* labels,
             int64_t* n_objects, bool split = false, const umx_label_split_options* so = nullptr, umx_label_split_counts* counts = nullptr,
-            const umx_label_flood_options* fo = nullptr, umx_label_flood_counts* fcounts = nullptr) {
+            const umx_label_flood_options* fo = nullptr, umx_label_flood_counts* fcounts = nullptr,
+            const umx_label_hmax_options* ho = nullptr, umx_label_hmax_counts* hcounts = nullptr) {
     if (!lb) return lfail(nullptr, UMX_ERR_INVALID, "null labeler");
     char msg[200];
-    const int refused = fo ? umx_label_flood_check(fo, K, H, W, msg, sizeof msg)
+    const int refused = ho ? umx_label_hmax_check(ho, K, H, W, msg, sizeof msg)
+                           : fo ? umx_label_flood_check(fo, K, H, W, msg, sizeof msg)
                            : split ? umx_label_split_check(so, K, H, W, msg, sizeof msg) : umx_label_options_check(o, K, H, W, msg, sizeof msg);
     if (refused != UMX_OK) return lfail(lb, UMX_ERR_INVALID, "%s", msg);
     if (!planes) return lfail(lb, UMX_ERR_INVALID, "null planes");
@@ -1357,8 +1374,9 @@ int run_any(umx_labeler* lb, const uint8_t* planes, bool on_host, int K, int H, 
     int* out = !labels ? nullptr : on_host ? lb->d_P : labels;
     umx_label_split_counts sc = {0, 0, 0, 0};
     umx_label_flood_counts fc = {0, 0, 0, 0, 0, 0, 0, 0};
+    umx_label_hmax_counts hc = {fc, 0, {0, 0}, 0};
     if (split) {
-        rc = run_split_launches(lb, on_host ? lb->d_planes : planes, K, H, W, so, out, &sc, fo, &fc);
+        rc = run_split_launches(lb, on_host ? lb->d_planes : planes, K, H, W, so, out, &sc, fo, &fc, ho, &hc);
         n = sc.n_objects;
     } else {
         rc = run_launches(lb, on_host ? lb->d_planes : planes, K, H, W, o, out, &n);
@@ -1385,6 +1403,11 @@ int run_any(umx_labeler* lb, const uint8_t* planes, bool on_host, int K, int H, 
     if (fcounts) {
         fc.n_objects = sc.n_objects; fc.n_before = sc.n_before; fc.n_cored = sc.n_cored;   // (unreached is the flood's own)
         *fcounts = fc;
+    }
+    if (hcounts) {
+        fc.n_objects = sc.n_objects; fc.n_before = sc.n_before; fc.n_cored = sc.n_cored;
+        hc.flood = fc;
+        *hcounts = hc;
     }
     if (on_host && labels) { lb->res_H = H; lb->res_W = W; lb->res_N = n; lb->res_why = nullptr; }
     else lb->res_why = on_host ? "the last umx_labeler_run was given no label plane (labels_host was NULL)"
@@ -1621,6 +1644,35 @@ int umx_labeler_run_flood_dev(umx_labeler* lb, const uint8_t* planes_dev, int K,
                               int32_t* labels_dev, umx_label_flood_counts* counts) {
     if (lb && !o) return lfail(lb, UMX_ERR_INVALID, "null label flood options");
     return run_any(lb, planes_dev, false, K, H, W, nullptr, labels_dev, nullptr, true, o ? &o->split : nullptr, nullptr, o, counts);
+}
+
+int umx_label_hmax_check(const umx_label_hmax_options* o, int K, int H, int W, char* msg, size_t cap) {
+    char buf[200] = "";
+    if (!o) snprintf(buf, sizeof buf, "null label h-maxima options");
+    else if (umx_label_flood_check(&o->flood, K, H, W, buf, sizeof buf) != UMX_OK) {}   // (its words, unchanged)
+    else if (o->seed_plane < 0 || o->seed_plane >= K)
+        snprintf(buf, sizeof buf, "seed_plane is %d: the plane is 0..%d, in the model's class order", o->seed_plane, K - 1);
+    else if (o->seed_invert != 0 && o->seed_invert != 1) snprintf(buf, sizeof buf, "seed_invert is %d: 0 or 1", o->seed_invert);
+    else if (o->height < 1 || o->height > UMX_HMAX_MAX_HEIGHT)
+        snprintf(buf, sizeof buf, "height is %d: a peak must stand 1..%d grey values above its saddle", o->height, (int)UMX_HMAX_MAX_HEIGHT);
+    for (int i = 0; o && !buf[0] && i < 5; ++i)
+        if (o->reserved[i]) snprintf(buf, sizeof buf, "reserved must be zero (word %d of the h-maxima's reserved words is %d)", i, o->reserved[i]);
+    if (msg && cap) snprintf(msg, cap, "%s", buf);
+    return buf[0] ? UMX_ERR_INVALID : UMX_OK;
+}
+
+int umx_labeler_run_hmax(umx_labeler* lb, const uint8_t* planes_host, int K, int H, int W, const umx_label_hmax_options* o,
+                         int32_t* labels_host, umx_label_hmax_counts* counts) {
+    if (lb && !o) return lfail(lb, UMX_ERR_INVALID, "null label h-maxima options");
+    return run_any(lb, planes_host, true, K, H, W, nullptr, labels_host, nullptr, true, o ? &o->flood.split : nullptr, nullptr,
+                   o ? &o->flood : nullptr, nullptr, o, counts);
+}
+
+int umx_labeler_run_hmax_dev(umx_labeler* lb, const uint8_t* planes_dev, int K, int H, int W, const umx_label_hmax_options* o,
+                             int32_t* labels_dev, umx_label_hmax_counts* counts) {
+    if (lb && !o) return lfail(lb, UMX_ERR_INVALID, "null label h-maxima options");
+    return run_any(lb, planes_dev, false, K, H, W, nullptr, labels_dev, nullptr, true, o ? &o->flood.split : nullptr, nullptr,
+                   o ? &o->flood : nullptr, nullptr, o, counts);
 }
 
 int umx_labeler_objects(const umx_labeler* lb, umx_label_object* out, int64_t cap, int64_t* n) {

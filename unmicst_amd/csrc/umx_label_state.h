@@ -1,6 +1,6 @@
-// libumx label mask: the labeler's state and the few host pieces that its four sources share -- umx_label.hip (labelling, growth,
-// split, flood, measurement, shapes), umx_label_contact.hip (contacts), umx_label_hull.hip (hulls) and umx_label_relabel.hip
-// (relabel).  Nothing here is part of the C ABI (include/umx.h).
+// libumx label mask: the labeler's state and the few host pieces that its five sources share -- umx_label.hip (labelling, growth,
+// split, flood, measurement, shapes), umx_label_hmax.hip (h-maxima seeds), umx_label_contact.hip (contacts), umx_label_hull.hip
+// (hulls) and umx_label_relabel.hip (relabel).  Nothing here is part of the C ABI (include/umx.h).
 #pragma once
 
 #include "umx_internal.h"
@@ -21,6 +21,7 @@ struct umx_labeler {
     uint8_t* d_B = nullptr;       size_t split_cap = 0;        // words of d_R = bytes of d_B (rounded up to a whole word); 0: never asked for
     long long* d_split = nullptr;                              // kSplitWords words the kernels of a split run add to
     long long* d_flood = nullptr;                              // kFloodWords words a flood launch reports in (allocated with d_split)
+    long long* d_hmax = nullptr;                               // kHmaxWords words the h-maxima seeds report in (allocated with d_split)
     std::vector<umx_label_object> table;                       // of the last run
     double ms[3] = {0.0, 0.0, 0.0};
     // the resident labels: d_P holds the int32 [res_H][res_W] label plane of res_N objects iff res_why is null; else why it does not
@@ -66,6 +67,13 @@ struct umx_labeler {
 };
 
 namespace umx {
+
+// The byte plane B of a split run (umx_label.hip, umx_label_hmax.hip): flags per pixel
+constexpr unsigned kFlagKept = 1u;    // the pixel belongs to a kept object (step 10: a pixel of M)
+constexpr unsigned kFlagEroded = 2u;  // the pixel is in E (step 11, or step 35 with h-maxima seeds); not read any more once R holds E's components
+constexpr unsigned kFlagCored = 4u;   // at the ROOT pixel of an object only: the object contains a core (step 12)
+// the words of umx_labeler::d_hmax: the pixels the launches of either reconstruction raised so far, |E|
+constexpr int kHmaxWords = 3, kHmaxRaised = 0, kHmaxSeeds = 2;
 
 // the message into the labeler (and the thread's), the code back
 int lfail(umx_labeler* lb, int code, const char* fmt, ...);
@@ -116,5 +124,13 @@ inline void relabel_buffers_forget(umx_labeler* lb) {
 void launch_grow_free(hipStream_t s, int H, int W, int N, const int* src, int* dst, int levels);
 // label_scan_kernel: counts[0 .. nblocks) -> their exclusive prefix sums in place, the sum to *total; nblocks <= 2^20
 void launch_block_scan(hipStream_t s, int* counts, int nblocks, long long* total);
+
+// The h-maxima seeds (umx_label_hmax.hip), for run_split_launches in the erosion's place.  P:
+// the objects' roots, Q: their areas at the roots (read here for the last time).  B gets kFlagKept | kFlagEroded for every pixel as
+// label_erode_kernel leaves them, with E the extended maxima; the int32 plane R is used as four byte planes.  d_hmax is cleared and
+// takes the raised counts and |E|; recon_launches: the launches of the two reconstructions.  The stream is idle on return but for
+// the last launch.
+int launch_hmax_seeds(umx_labeler* lb, const uint8_t* planes, int H, int W, const int* P, const int* Q, int min_area,
+                      const umx_label_hmax_options* ho, int64_t recon_launches[2]);
 
 }  // namespace umx

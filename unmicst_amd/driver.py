@@ -115,6 +115,18 @@ def build_parser(spec: ToolSpec) -> argparse.ArgumentParser:
                    help="the flood rises in levels of Q grey values: a power of two, 1..256 (default 16)")
     p.add_argument("--labelFloodInvert", dest="labelFloodInvert", action="store_true",
                    help="flood on 255 - plane (for a plane that is high inside the nuclei, e.g. --labelClass itself)")
+    # erosion cores see geometry alone; --labelHmax H places the seeds by the probability's own peaks instead: the extended maxima of
+    # the h-maxima transform of a plane inside the objects, regrown by --labelFlood or by distance
+    p.add_argument("--labelHmax", dest="labelHmax", type=int, default=None, metavar="H",
+                   help="split the labelled objects by h-maxima seeds instead of --labelSplit: a peak of the seed plane seeds an object "
+                        "of its own iff it stands more than H grey values (1..255) above the saddle to a higher one")
+    p.add_argument("--labelHmaxPlane", dest="labelHmaxPlane", type=int, default=None, metavar="PLANE",
+                   help="with --labelHmax: the probability plane the peaks are taken from (0-based in the MODEL's class order; "
+                        "default: --labelClass)")
+    p.add_argument("--labelHmaxInvert", dest="labelHmaxInvert", action="store_true",
+                   help="with --labelHmax: take the peaks of 255 - plane (the basins of e.g. the contour plane)")
+    p.add_argument("--labelHmaxCore", dest="labelHmaxCore", type=int, default=None, metavar="C",
+                   help="with --labelHmax: seed components of fewer pixels seed no object (1..65536, default 1)")
     # how bright every labelled object is in the image's own pages: <stem>_Intensities_<suffix>.csv
     p.add_argument("--labelMeasure", dest="labelMeasure", type=int, nargs="*", default=None, metavar="PAGE",
                    help="also write mean, std, min and max of every labelled object in the probability planes and in these pages of "
@@ -156,7 +168,9 @@ def check_label_args(parser: argparse.ArgumentParser, args) -> None:
                         ("--labelSplit", args.labelSplit), ("--labelSplitCore", args.labelSplitCore),
                         ("--labelSplitRegrow", args.labelSplitRegrow), ("--labelShape", args.labelShape or None),
                         ("--labelFlood", args.labelFlood), ("--labelFloodStep", args.labelFloodStep),
-                        ("--labelFloodInvert", args.labelFloodInvert or None), ("--labelNeighbors", args.labelNeighbors or None),
+                        ("--labelFloodInvert", args.labelFloodInvert or None), ("--labelHmax", args.labelHmax),
+                        ("--labelHmaxPlane", args.labelHmaxPlane), ("--labelHmaxInvert", args.labelHmaxInvert or None),
+                        ("--labelHmaxCore", args.labelHmaxCore), ("--labelNeighbors", args.labelNeighbors or None),
                         ("--labelNeighborsReach", args.labelNeighborsReach), ("--labelHull", args.labelHull or None),
                         ("--labelHullVertices", args.labelHullVertices or None), ("--labelKeep", args.labelKeep),
                         ("--labelMerge", args.labelMerge)):
@@ -180,7 +194,20 @@ def check_label_args(parser: argparse.ArgumentParser, args) -> None:
         parser.error("--labelSplitCore %d: it must be 1..65536 pixels" % args.labelSplitCore)
     if args.labelSplitRegrow is not None and not 1 <= args.labelSplitRegrow <= 255:
         parser.error("--labelSplitRegrow %d: it must be 1..255 levels" % args.labelSplitRegrow)
-    if args.labelFlood is not None and args.labelSplit is None:
+    for flag, v in (("--labelSplit", args.labelSplit), ("--labelSplitCore", args.labelSplitCore), ("--labelSplitRegrow", args.labelSplitRegrow)):
+        if v is not None and args.labelHmax is not None:
+            parser.error("--labelHmax places the seeds itself: it excludes %s" % flag)
+    for flag, v in (("--labelHmaxPlane", args.labelHmaxPlane), ("--labelHmaxInvert", args.labelHmaxInvert or None),
+                    ("--labelHmaxCore", args.labelHmaxCore)):
+        if v is not None and args.labelHmax is None:
+            parser.error("%s needs --labelHmax" % flag)
+    if args.labelHmax is not None and not 1 <= args.labelHmax <= 255:
+        parser.error("--labelHmax %d: it must be 1..255 grey values" % args.labelHmax)
+    if args.labelHmaxPlane is not None and not 0 <= args.labelHmaxPlane < 16:
+        parser.error("--labelHmaxPlane %d: planes are numbered 0..15 at the most" % args.labelHmaxPlane)
+    if args.labelHmaxCore is not None and not 1 <= args.labelHmaxCore <= 65536:
+        parser.error("--labelHmaxCore %d: it must be 1..65536 pixels" % args.labelHmaxCore)
+    if args.labelFlood is not None and args.labelSplit is None and args.labelHmax is None:
         parser.error("--labelFlood needs --labelSplit")
     for flag, v in (("--labelFloodStep", args.labelFloodStep), ("--labelFloodInvert", args.labelFloodInvert or None)):
         if v is not None and args.labelFlood is None:
@@ -550,6 +577,8 @@ def run(tool: str, argv=None, script_dir: str = None) -> int:
         grow_classes = label_grow_classes(parser, args, label_art.hp.nClasses)
         if args.labelFlood is not None and args.labelFlood >= label_art.hp.nClasses:
             parser.error("--labelFlood %d: the model has planes 0..%d" % (args.labelFlood, label_art.hp.nClasses - 1))
+        if args.labelHmaxPlane is not None and args.labelHmaxPlane >= label_art.hp.nClasses:
+            parser.error("--labelHmaxPlane %d: the model has planes 0..%d" % (args.labelHmaxPlane, label_art.hp.nClasses - 1))
     measure_pages_arg = None
     if args.labelMeasure is not None:
         ftype = split_name(os.path.basename(args.imagePath), spec)[1]
@@ -684,7 +713,8 @@ def run(tool: str, argv=None, script_dir: str = None) -> int:
                                               grow=args.labelGrow or 0, grow_classes=grow_classes, split=args.labelSplit or 0,
                                               split_core=args.labelSplitCore or 1, split_regrow=args.labelSplitRegrow or 255,
                                               flood=args.labelFlood, flood_step=args.labelFloodStep or _umx.FLOOD_DEFAULT_STEP,
-                                              flood_invert=args.labelFloodInvert)
+                                              flood_invert=args.labelFloodInvert, hmax=args.labelHmax, hmax_plane=args.labelHmaxPlane,
+                                              hmax_invert=args.labelHmaxInvert, hmax_core=args.labelHmaxCore or 1)
                 if args.labelMerge is not None or keep_rules:
                     # merge, then drop, on the device: every file below is written from the final resident labels
                     st.mark("label")
@@ -719,6 +749,11 @@ def run(tool: str, argv=None, script_dir: str = None) -> int:
                     print("Label split: %d objects from %d (%d with a core), %d pixels unreached"
                           % (c["n_objects"], c["n_before"], c["n_cored"], c["unreached"]))
                     st.note("label_split", c)
+                if args.labelHmax is not None:
+                    c = labeler.hmax_counts()
+                    print("Label hmax: %d seed pixels, %d objects from %d (%d with a core), reconstructions in %d and %d launches"
+                          % ((c["seed_pixels"], c["n_objects"], c["n_before"], c["n_cored"]) + tuple(c["recon_launches"])))
+                    st.note("label_hmax", c)
                 if args.labelFlood is not None:
                     c = labeler.flood_counts()
                     print("Label flood: %d pixels claimed at %d levels in %d launches, %d pixels unreached"

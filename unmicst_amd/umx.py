@@ -39,6 +39,7 @@ EXPORTS = [
     "umx_label_measure_check", "umx_labeler_measure", "umx_labeler_measure_dev", "umx_labeler_measure_last_ms",
     "umx_label_split_check", "umx_labeler_run_split", "umx_labeler_run_split_dev",
     "umx_label_flood_check", "umx_labeler_run_flood", "umx_labeler_run_flood_dev",
+    "umx_label_hmax_check", "umx_labeler_run_hmax", "umx_labeler_run_hmax_dev",
     "umx_label_shape_check", "umx_labeler_shape", "umx_labeler_shape_dev", "umx_labeler_shape_last_ms",
     "umx_label_contact_check", "umx_labeler_contacts", "umx_labeler_contacts_dev", "umx_labeler_contacts_last_ms",
     "umx_labeler_contacts_last_stats",
@@ -55,6 +56,9 @@ LABEL_MAX_GROW, LABEL_GROW_TILE, LABEL_GROW_HALO = 255, 64, 8
 SPLIT_MAX_DEPTH, SPLIT_MAX_CORE_AREA, SPLIT_MAX_REGROW = 8, 65536, 255
 # the level flood: its largest and its default level step, the steps of one launch (the UMX_FLOOD_* enumerators; tests/test_label_flood_cpu.py compares)
 FLOOD_MAX_STEP, FLOOD_DEFAULT_STEP, FLOOD_LAUNCH_STEPS = 256, 16, 8
+# the h-maxima seeds: the largest height, the steps of one reconstruction launch, the launches one reconstruction may take (the
+# UMX_HMAX_* enumerators; tests/test_label_hmax_cpu.py compares)
+HMAX_MAX_HEIGHT, HMAX_LAUNCH_STEPS, HMAX_MAX_LAUNCHES = 255, 64, 2048
 
 
 class UmxError(RuntimeError):
@@ -118,6 +122,17 @@ class _LabelFloodCounts(ctypes.Structure):
     """umx_label_flood_counts: 64 bytes"""
     _fields_ = [(n, ctypes.c_int64) for n in ("n_objects", "n_before", "n_cored", "unreached", "levels_claimed", "claimed", "launches",
                                               "reserved")]
+
+
+class _LabelHmaxOptions(ctypes.Structure):
+    """umx_label_hmax_options: 128 bytes"""
+    _fields_ = [("flood", _LabelFloodOptions), ("seed_plane", ctypes.c_int32), ("seed_invert", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 5)]
+
+
+class _LabelHmaxCounts(ctypes.Structure):
+    """umx_label_hmax_counts: 96 bytes"""
+    _fields_ = [("flood", _LabelFloodCounts), ("seed_pixels", ctypes.c_int64), ("recon_launches", ctypes.c_int64 * 2), ("reserved", ctypes.c_int64)]
 
 
 class LabelObject(ctypes.Structure):
@@ -366,6 +381,11 @@ def load(path: Optional[str] = None):
         fn.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(_LabelSplitOptions), c_void_p, ctypes.POINTER(_LabelSplitCounts)]
     L.umx_label_flood_check.restype = c_int
     L.umx_label_flood_check.argtypes = [ctypes.POINTER(_LabelFloodOptions), c_int, c_int, c_int, ctypes.c_char_p, ctypes.c_size_t]
+    L.umx_label_hmax_check.restype = c_int
+    L.umx_label_hmax_check.argtypes = [ctypes.POINTER(_LabelHmaxOptions), c_int, c_int, c_int, ctypes.c_char_p, ctypes.c_size_t]
+    for fn in (L.umx_labeler_run_hmax, L.umx_labeler_run_hmax_dev):
+        fn.restype = c_int
+        fn.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(_LabelHmaxOptions), c_void_p, ctypes.POINTER(_LabelHmaxCounts)]
     for fn in (L.umx_labeler_run_flood, L.umx_labeler_run_flood_dev):
         fn.restype = c_int
         fn.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(_LabelFloodOptions), c_void_p, ctypes.POINTER(_LabelFloodCounts)]
@@ -805,6 +825,46 @@ def label_flood_check(K: int, H: int, W: int, cls: int, min_area: int = 1, grow:
     return "" if rc == 0 else buf.value.decode()
 
 
+def _label_hmax_options(base: "_LabelOptions", hmax: int, hmax_plane: Optional[int], hmax_invert, hmax_core: int, flood: Optional[int],
+                        flood_step: int, flood_invert) -> "_LabelHmaxOptions":
+    """the record of an h-maxima run: the split's depth is not used (1 is sent), its regrow is the flood's 255; without ``flood`` the
+    regrow is by distance -- one level (step 256) on the plane of the class itself; ``hmax_plane`` None is that plane too"""
+    so = _label_split_options(base, 1, hmax_core, SPLIT_MAX_REGROW)
+    o = _LabelHmaxOptions()
+    if flood is None:
+        o.flood = _label_flood_options(so, base.cls, FLOOD_MAX_STEP, False)
+    else:
+        o.flood = _label_flood_options(so, flood, flood_step, flood_invert)
+    o.seed_plane = base.cls if hmax_plane is None else int(hmax_plane)
+    o.seed_invert = int(hmax_invert)
+    o.height = int(hmax)
+    return o
+
+
+def label_hmax_check(K: int, H: int, W: int, cls: int, min_area: int = 1, grow: int = 0, grow_classes=None, hmax: int = 1,
+                     hmax_plane: Optional[int] = None, hmax_invert=False, hmax_core: int = 1, flood: Optional[int] = None,
+                     flood_step: int = FLOOD_DEFAULT_STEP, flood_invert=False, depth: int = 1, base_reserved=None, split_reserved=None,
+                     flood_reserved=None, reserved=None, null: bool = False) -> str:
+    """umx_label_hmax_check: "" if an h-maxima run of K planes of H x W is accepted, else the reason.  ``depth``: the split record's
+    depth, which must pass the split's check and is otherwise not used.  ``base_reserved``, ``split_reserved`` and ``flood_reserved``:
+    the reserved words of the inner records as label_flood_check names them; ``reserved``: the h-maxima's own five words.  ``null``: a
+    NULL record.  Host only."""
+    o = _label_hmax_options(_label_options(K, cls, min_area, grow, grow_classes), hmax, hmax_plane, hmax_invert, hmax_core, flood, flood_step,
+                            flood_invert)
+    o.flood.split.depth = int(depth)
+    for j, v in enumerate(base_reserved or ()):
+        o.flood.split.base.reserved[j] = int(v)
+    for j, v in enumerate(split_reserved or ()):
+        o.flood.split.reserved[j] = int(v)
+    for j, v in enumerate(flood_reserved or ()):
+        o.flood.reserved[j] = int(v)
+    for j, v in enumerate(reserved or ()):
+        o.reserved[j] = int(v)
+    buf = ctypes.create_string_buffer(256)
+    rc = load().umx_label_hmax_check(None if null else ctypes.byref(o), int(K), int(H), int(W), buf, len(buf))
+    return "" if rc == 0 else buf.value.decode()
+
+
 def label_measure_check(dtype: int, C: int, H: int, W: int, n_objects: int = 0) -> str:
     """umx_label_measure_check: "" if a measurement of C planes of H x W of that dtype code against n_objects labels is accepted, else
     the reason.  Host only."""
@@ -1036,6 +1096,7 @@ class Labeler:
         self.device = device
         self._split_counts = None
         self._flood_counts = None
+        self._hmax_counts = None
         self._last_shape = (1, 1)                                  # H, W of the last run: what shape() names when not told
         self._contacts_room = 1024                                 # records the next contacts call offers: the last list's length
         self._contacts_reruns_before = 0                           # reruns of a first pass that was offered too little room
@@ -1087,12 +1148,32 @@ class Labeler:
         was claimed), claimed (pixels claimed in all) and launches (informative); None before one, and after a later run without."""
         return self._flood_counts
 
+    def hmax_counts(self) -> dict:
+        """The counts of the last run with h-maxima seeds of this Labeler: the seven of flood_counts(), seed_pixels (|E|) and
+        recon_launches (a pair, informative); None before one, and after a later run without."""
+        return self._hmax_counts
+
     def _run_any(self, planes_ptr, dev: bool, K: int, H: int, W: int, o: "_LabelOptions", labels_ptr, split: int, split_core: int,
-                 split_regrow: int, flood: Optional[int] = None, flood_step: int = FLOOD_DEFAULT_STEP, flood_invert=False) -> int:
-        """the entry of today when split is 0, else the split's, or the flood's when ``flood`` names a plane; -> N"""
+                 split_regrow: int, flood: Optional[int] = None, flood_step: int = FLOOD_DEFAULT_STEP, flood_invert=False,
+                 hmax: Optional[int] = None, hmax_plane: Optional[int] = None, hmax_invert=False, hmax_core: int = 1) -> int:
+        """the entry of today when split is 0, else the split's, or the flood's when ``flood`` names a plane; the h-maxima's when
+        ``hmax`` names a height; -> N"""
+        if hmax is not None and split:
+            raise ValueError("hmax and split both place the seeds: give one of them")
         planes_ptr, labels_ptr = ctypes.c_void_p(planes_ptr), ctypes.c_void_p(labels_ptr or None)
+        if hmax is not None:
+            ho = _label_hmax_options(o, hmax, hmax_plane, hmax_invert, hmax_core, flood, flood_step, flood_invert)
+            hc = _LabelHmaxCounts()
+            fn = self._L.umx_labeler_run_hmax_dev if dev else self._L.umx_labeler_run_hmax
+            self._split_counts = self._flood_counts = self._hmax_counts = None
+            self._check(fn(self._lb, planes_ptr, K, H, W, ctypes.byref(ho), labels_ptr, ctypes.byref(hc)))
+            self._flood_counts = {name: int(getattr(hc.flood, name)) for name, _ in _LabelFloodCounts._fields_ if name != "reserved"}
+            self._split_counts = {name: self._flood_counts[name] for name, _ in _LabelSplitCounts._fields_}
+            self._hmax_counts = dict(self._flood_counts, seed_pixels=int(hc.seed_pixels), recon_launches=tuple(int(v) for v in hc.recon_launches))
+            return int(hc.flood.n_objects)
         self._split_counts = None
         self._flood_counts = None
+        self._hmax_counts = None
         if flood is not None:                                      # (without a split the library refuses the depth of 0)
             fo = _label_flood_options(_label_split_options(o, split, split_core, split_regrow), flood, flood_step, flood_invert)
             fc = _LabelFloodCounts()
@@ -1115,7 +1196,8 @@ class Labeler:
 
     def run(self, planes: np.ndarray, cls: Optional[int] = None, min_area: int = 1, want_labels: bool = True, grow: int = 0,
             grow_classes=None, split: int = 0, split_core: int = 1, split_regrow: int = 255, flood: Optional[int] = None,
-            flood_step: int = FLOOD_DEFAULT_STEP, flood_invert: bool = False):
+            flood_step: int = FLOOD_DEFAULT_STEP, flood_invert: bool = False, hmax: Optional[int] = None, hmax_plane: Optional[int] = None,
+            hmax_invert: bool = False, hmax_core: int = 1):
         """planes uint8 [K, H, W] in the model's class order -> (labels int32 [H, W], objects); ``cls`` None: the last class.
         want_labels False: labels is None (only the count and the table come down).  grow R > 0: the kept objects grow R levels
         over the pixels whose class is in ``grow_classes`` (an iterable of class indices; None: every class but 0 and ``cls``).
@@ -1124,7 +1206,12 @@ class Labeler:
         split 0 is the call of before.
         flood P (with split > 0): the cores are regrown by the level flood on the relief planes[P] (255 - planes[P] with
         ``flood_invert``) in levels of ``flood_step`` (a power of two, 1..256) instead of by distance, so a neck is cut along the
-        relief's ridge (steps 19 to 21; split_regrow must stay 255); flood_counts() has the counts.  None is the call of before."""
+        relief's ridge (steps 19 to 21; split_regrow must stay 255); flood_counts() has the counts.  None is the call of before.
+        hmax h (1..255, without split): the seeds are the extended maxima of the h-maxima transform of planes[``hmax_plane``]
+        (255 - that with ``hmax_invert``; None: the plane of ``cls``) inside the kept objects -- a peak seeds an object of its own
+        iff it stands more than h above the saddle to a higher one -- with components of fewer than ``hmax_core`` pixels seeding
+        nothing (steps 33 to 36); they are regrown by the flood of ``flood`` / ``flood_step`` / ``flood_invert``, or by distance
+        without ``flood``; hmax_counts() has the counts.  hmax together with split is a ValueError.  None is the call of before."""
         planes = np.ascontiguousarray(planes)
         if planes.dtype != np.uint8 or planes.ndim != 3:
             raise TypeError("planes must be uint8 [K, H, W]")
@@ -1132,7 +1219,7 @@ class Labeler:
         o = _label_options(K, cls, min_area, grow, grow_classes)
         labels = np.empty((H, W), np.int32) if want_labels else None
         n = self._run_any(planes.ctypes.data, False, K, H, W, o, labels.ctypes.data if want_labels else None, split, split_core, split_regrow,
-                          flood, flood_step, flood_invert)
+                          flood, flood_step, flood_invert, hmax, hmax_plane, hmax_invert, hmax_core)
         if want_labels:
             self._last_shape = (H, W)                              # (of the resident labels: a refused run above has left them)
         objs = self.objects()
@@ -1141,12 +1228,14 @@ class Labeler:
 
     def run_ptr(self, planes_ptr: int, K: int, H: int, W: int, labels_ptr: int = 0, cls: Optional[int] = None, min_area: int = 1,
                 grow: int = 0, grow_classes=None, split: int = 0, split_core: int = 1, split_regrow: int = 255,
-                flood: Optional[int] = None, flood_step: int = FLOOD_DEFAULT_STEP, flood_invert: bool = False) -> np.ndarray:
+                flood: Optional[int] = None, flood_step: int = FLOOD_DEFAULT_STEP, flood_invert: bool = False, hmax: Optional[int] = None,
+                hmax_plane: Optional[int] = None, hmax_invert: bool = False, hmax_core: int = 1) -> np.ndarray:
         """umx_labeler_run_dev on DEVICE addresses (e.g. torch.Tensor.data_ptr()): uint8 [K, H, W] in, int32 [H, W] out (0: no label
         plane) -> objects.  The planes must be complete; the call returns with the labels complete.  grow, grow_classes and the
-        split's three and the flood's three: as run."""
+        split's three, the flood's three and the h-maxima's four: as run."""
         o = _label_options(int(K), cls, min_area, grow, grow_classes)
-        self._run_any(planes_ptr, True, int(K), int(H), int(W), o, labels_ptr, split, split_core, split_regrow, flood, flood_step, flood_invert)
+        self._run_any(planes_ptr, True, int(K), int(H), int(W), o, labels_ptr, split, split_core, split_regrow, flood, flood_step, flood_invert,
+                      hmax, hmax_plane, hmax_invert, hmax_core)
         return self.objects()
 
     def measure(self, planes: np.ndarray) -> np.ndarray:
