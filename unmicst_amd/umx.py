@@ -1140,7 +1140,7 @@ class Labeler:
 
     def split_counts(self) -> dict:
         """n_objects (N), n_before (N0), n_cored and unreached of the last run with split > 0 of this Labeler; None before one, and
-        after a later run without a split."""
+        after a later run without a split.  A refused run (ERR_INVALID) leaves these and the two below as they were."""
         return self._split_counts
 
     def flood_counts(self) -> dict:
@@ -1157,9 +1157,21 @@ class Labeler:
                  split_regrow: int, flood: Optional[int] = None, flood_step: int = FLOOD_DEFAULT_STEP, flood_invert=False,
                  hmax: Optional[int] = None, hmax_plane: Optional[int] = None, hmax_invert=False, hmax_core: int = 1) -> int:
         """the entry of today when split is 0, else the split's, or the flood's when ``flood`` names a plane; the h-maxima's when
-        ``hmax`` names a height; -> N"""
+        ``hmax`` names a height; -> N.  A refused call (ERR_INVALID) has touched nothing: the counts of the run before stand too."""
         if hmax is not None and split:
             raise ValueError("hmax and split both place the seeds: give one of them")
+        before = tuple(getattr(self, name, None) for name in ("_split_counts", "_flood_counts", "_hmax_counts"))
+        try:
+            return self._run_counted(planes_ptr, dev, K, H, W, o, labels_ptr, split, split_core, split_regrow, flood, flood_step, flood_invert,
+                                     hmax, hmax_plane, hmax_invert, hmax_core)
+        except UmxError as e:
+            if e.code == ERR_INVALID:
+                self._split_counts, self._flood_counts, self._hmax_counts = before
+            raise
+
+    def _run_counted(self, planes_ptr, dev, K, H, W, o, labels_ptr, split, split_core, split_regrow, flood, flood_step, flood_invert, hmax,
+                     hmax_plane, hmax_invert, hmax_core) -> int:
+        """_run_any's call; the three counts are those of this call, None where it has none or fails"""
         planes_ptr, labels_ptr = ctypes.c_void_p(planes_ptr), ctypes.c_void_p(labels_ptr or None)
         if hmax is not None:
             ho = _label_hmax_options(o, hmax, hmax_plane, hmax_invert, hmax_core, flood, flood_step, flood_invert)
